@@ -12,21 +12,35 @@ WORLD_SIZE in the environment) this process IS one rank; started directly with N
 the N rank processes (before anything here touches the GPU), relays rank 0's line and exits with
 their status.
 
-Prints ONE JSON line on rank 0 (contract in the round brief).  Everything the driver keeps is inside the objects it
-preserves whole:
+Prints ONE JSON line on rank 0 (contract in the round brief).  A plain run does only what that line's headline needs:
+it builds the table and the batches, runs the wake launches and the W warm-up steps, times the K steps, writes what
+the last timed step computed if --dump-outputs DIR is given, and prints the line (`config` the workload, `roofline`
+from the HIP events of the K timed steps).  Everything else the line can carry is measured with --full only; the
+numbers it adds are then inside the objects the driver preserves whole:
   "config":       the workload, and config.e2e (N=1 only): nh_run() files-in -> files-out on gzip pairs (configs[2] shape
                   at a stated scale) and on one gzip file of ONT-like reads (configs[3] shape, scaled) -- Mreads/s and wall
                   seconds only, never mixed into `value`;
   "roofline":     algorithmic bytes (sum len + 64*D + 16 per fragment) per launch / average kernel
-                  duration measured with HIP events on the launch stream; value_two_streams: the same launches issued on two
+                  duration measured with HIP events on the launch stream; with --full also value_without_wake (the W + K
+                  launches with no wake phase in front) and value_two_streams: the same launches issued on two
                   alternating streams (what nh_run's stream slots do); roofline.variants (N=1 only, reduced step counts):
                   single-end configs[1], hit path, ONT-like long reads, a table of > 2^32 cells, 2 x 250 bp pairs -- frac,
                   kernel_ms, both values, checked against the oracle on a sample;
   "cpu_baseline": kraken2 itself with the reference's argv (src/main.rs:215-267) when a `kraken2` binary is on PATH
                   (kind "kraken2"), else the CPU oracle (oracle/k2_oracle.c, kind "port") timed on the host cores on a
                   bounded sample of the same workload.
-The long descriptions (workload strings, per-stage traces, what each leg did) go to stderr and to bench_details.json
-(directory NOHUMAN_BENCH_LOGDIR, default the current one), not into the line.
+The long descriptions of a --full run (workload strings, per-stage traces, what each leg did) go to stderr and to
+bench_details.json (directory NOHUMAN_BENCH_LOGDIR, default the current one), not into the line.
+
+--dump-outputs DIR (rank 0): the per-fragment records of the last timed step as DIR/call.npy (float64: a taxon id is a
+uint32), DIR/total_kmers.npy, DIR/clade_hits.npy, DIR/hit_groups.npy (float32: counts below 2^24), and the four counters
+of the timed steps (fragments, classified, bases, look-ups) as DIR/counters.npy (float64).  The reads are seeded and the
+same arguments give the same reads on every run.  The synthetic table is not bit-for-bit the same: nh_open_synthetic
+inserts its keys concurrently, and where two keys share a compacted key or a probe run, which one lands where depends on
+the order the device ran them in (its size moved by one in 1 of 5 runs of 28 M keys).  A read whose probe crosses such a
+spot can count one hit more or less: clade_hits / hit_groups (and so, rarely, call) of a few records in a million may
+differ between runs, while total_kmers and the fragment, base and look-up counters never do.  Above 64 MB in all, a
+fixed sample of the fragments is written instead, with their positions as DIR/row_index.npy.
 """
 import argparse
 import json
@@ -62,10 +76,15 @@ def parse_args(argv=None):
     ap.add_argument("--wake-ms", type=float, default=80.0,
                     help="untimed launches of the same step before the warm-up steps until this much wall time has passed: the "
                          "chip's power-management transient after idle (profiles/r05_launch_series.txt); 0 = none")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the contract's sequence without the wake phase, the "
+                         "two-stream launches, the CPU baseline, the end-to-end and gzip legs, the variants")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU baseline leg")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-variants", action="store_true", help="skip the hit-path / single-end legs")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the nh_run files-in -> files-out leg")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--no-variants", action="store_true", help="--full: skip the hit-path / single-end legs")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the nh_run files-in -> files-out leg")
     ap.add_argument("--e2e-pairs", type=int, default=5_000_000, help="pairs per gzip member of the e2e inputs")
     ap.add_argument("--e2e-reps", type=int, default=10, help="members per e2e input file")
     ap.add_argument("--e2e-distinct", type=int, default=5,
@@ -177,9 +196,10 @@ class Ctx:
 
 
 def measure(cx, args, *, steps, warmup, single_end=False, ont=False, hit_frac=0.0, n_rate=0.0, pairs=None,
-            keep=False, capacity=None, read_len=None, contract_first=False):
+            keep=False, capacity=None, read_len=None, contract_first=False, snapshot=False):
     """Builds the synthetic table and batches in this GPU's HBM and times `steps` launches.  Returns a
-    dict with the numbers of one bench line; with keep=True also the live objects (engine, batches)."""
+    dict with the numbers of one bench line; with keep=True also the live objects (engine, batches), and with
+    snapshot=True there a host copy of what the last timed launch wrote (live["last_outputs"])."""
     torch, dist, np = cx.torch, cx.dist, cx.np
     from nohuman_amd import Engine
     dev = cx.dev
@@ -258,8 +278,9 @@ def measure(cx, args, *, steps, warmup, single_end=False, ont=False, hit_frac=0.
     # all the while; afterwards launch-to-launch spread is +-1 %).  A run of nh_run keeps the GPU busy for seconds, so the
     # steady state is what a launch costs: the same launches are issued untimed until --wake-ms of GPU work have run, THEN
     # the W warm-up steps and the K timed steps follow as the contract says.
-    # the contract's own sequence -- W warm-up steps, K timed, nothing before them -- is measured FIRST and reported
-    # beside `value` (roofline.value_without_wake / kernel_ms_without_wake), so that rounds 1-4's numbers stay comparable.
+    # with --full the contract's own sequence -- W warm-up steps, K timed, nothing before them -- is measured FIRST
+    # and reported beside `value` (roofline.value_without_wake / kernel_ms_without_wake), so that rounds 1-4's numbers stay
+    # comparable.
     no_wake = None
     if contract_first and args.wake_ms > 0:
         for i in range(warmup):
@@ -298,47 +319,53 @@ def measure(cx, args, *, steps, warmup, single_end=False, ont=False, hit_frac=0.
     barrier()
     elapsed = time.perf_counter() - t_start
     kernel_ms = ev0.elapsed_time(ev1) / max(steps, 1)
+    # what a caller of the timed path receives from its last launch (taken before anything below reuses `results`)
+    last_outputs = {"results": results.cpu().numpy().view(np.uint32),
+                    "counters": counters.cpu().numpy()} if snapshot else None
 
     # ---- the same launches on TWO alternating streams: what nh_run's stream slots do in production (a launch's tail
-    # overlaps the next one's ramp).  Reported beside the single-stream value, never instead of it.
-    s2 = [torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)]
-    res2 = [results, torch.empty_like(results)]
-    counters2 = torch.zeros(4, dtype=torch.int64, device=dev)
+    # overlaps the next one's ramp).  Reported beside the single-stream value, never instead of it (--full only).
+    elapsed2 = None
+    if args.full:
+        s2 = [torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)]
+        res2 = [results, torch.empty_like(results)]
+        counters2 = torch.zeros(4, dtype=torch.int64, device=dev)
 
-    def step2(i):
-        eng.classify_device(pool[i % len(pool)].data_ptr(), offsets.data_ptr(), n_frag, paired, args.confidence,
-                            res2[i % 2].data_ptr(), counters2.data_ptr(), s2[i % 2].cuda_stream, long_reads=ont)
+        def step2(i):
+            eng.classify_device(pool[i % len(pool)].data_ptr(), offsets.data_ptr(), n_frag, paired, args.confidence,
+                                res2[i % 2].data_ptr(), counters2.data_ptr(), s2[i % 2].cuda_stream, long_reads=ont)
 
-    # (the few hundred microseconds of synchronising and allocating above are enough of an idle moment to bring part of the
-    #  transient back -- the profiler's per-dispatch times show it, profiles/r05_launch_series.txt --: the same wake phase here)
-    if args.wake_ms > 0:
-        tw = time.perf_counter()
-        k = 0
-        while (time.perf_counter() - tw) * 1e3 < args.wake_ms / 2:
-            step2(k)
-            k += 1
-            if k % 4 == 0:
-                torch.cuda.synchronize()
-    for i in range(min(warmup, 2)):
-        step2(i)
-    torch.cuda.synchronize()
-    barrier()
-    t2 = time.perf_counter()
-    for i in range(steps):
-        step2(warmup + i)
-    torch.cuda.synchronize()
-    barrier()
-    elapsed2 = time.perf_counter() - t2
-    del res2, counters2
+        # (the few hundred microseconds of synchronising and allocating above are enough of an idle moment to bring part of
+        #  the transient back -- the profiler's per-dispatch times show it, profiles/r05_launch_series.txt --: the same wake
+        #  phase here)
+        if args.wake_ms > 0:
+            tw = time.perf_counter()
+            k = 0
+            while (time.perf_counter() - tw) * 1e3 < args.wake_ms / 2:
+                step2(k)
+                k += 1
+                if k % 4 == 0:
+                    torch.cuda.synchronize()
+        for i in range(min(warmup, 2)):
+            step2(i)
+        torch.cuda.synchronize()
+        barrier()
+        t2 = time.perf_counter()
+        for i in range(steps):
+            step2(warmup + i)
+        torch.cuda.synchronize()
+        barrier()
+        elapsed2 = time.perf_counter() - t2
+        del res2, counters2
 
     # ---- totals: the one collective of the path (classified-count all-reduce) ------------------
     from nohuman_amd.dist import gather_floats, reduce_counters
     (frags, classified, nbases, lookups), elapsed_max = reduce_counters(counters, elapsed)
     rank_kernel_ms = gather_floats(kernel_ms, dev)
-    elapsed2_max = max(gather_floats(elapsed2, dev))
+    elapsed2_max = max(gather_floats(elapsed2, dev)) if elapsed2 is not None else None
     reads_total = frags * mates
     value = reads_total / elapsed_max / 1e6
-    value2 = reads_total / elapsed2_max / 1e6
+    value2 = reads_total / elapsed2_max / 1e6 if elapsed2_max else None
 
     # per-launch algorithmic bytes on this rank
     c = [int(x) for x in counters.tolist()]
@@ -406,12 +433,12 @@ def measure(cx, args, *, steps, warmup, single_end=False, ont=False, hit_frac=0.
             "value_without_wake": round(n_frag * mates * cx.world / (no_wake * 1e-3) / 1e6, 3) if no_wake else None,
             "algorithmic_bytes_per_launch": int(alg_bytes_launch),
             # the same launches on two alternating streams (nh_run's slots): whole-job Mreads/s and its roofline fraction
-            "value_two_streams": round(value2, 3),
-            "frac_two_streams": round(alg_bytes_launch * steps / elapsed2_max / 1e9 / HBM_PEAK_GBS, 4) if elapsed2_max > 0 else None,
+            "value_two_streams": round(value2, 3) if value2 else None,
+            "frac_two_streams": round(alg_bytes_launch * steps / elapsed2_max / 1e9 / HBM_PEAK_GBS, 4) if elapsed2_max else None,
         },
     }
     live = dict(eng=eng, pool=pool, offsets=offsets, results=results, step=step, mates=mates, paired=paired,
-                n_frag=n_frag, ont=ont)
+                n_frag=n_frag, ont=ont, last_outputs=last_outputs)
     if keep:
         return m, live
     eng.close()
@@ -476,7 +503,11 @@ def main():
         backend = dist.get_backend()
 
     m, live = measure(cx, args, steps=args.steps, warmup=args.warmup, single_end=args.single_end, ont=args.ont,
-                      hit_frac=args.hit_frac, n_rate=args.n_rate, keep=True, contract_first=True)
+                      hit_frac=args.hit_frac, n_rate=args.n_rate, keep=True, contract_first=args.full,
+                      snapshot=bool(args.dump_outputs) and cx.rank == 0)
+    if live["last_outputs"] is not None:
+        dump_outputs(args.dump_outputs, live["last_outputs"])
+        live["last_outputs"] = None
     out = {
         "metric": "Mreads/sec classified (HPRC.r2 DB, 150bp PE)" if not args.ont else "Mreads/sec classified (ONT)",
         "value": m["value"],
@@ -511,11 +542,11 @@ def main():
     details = {"headline_workload": m["workload"]}
     out["config"]["workload"] = short_workload(m)
     # ---- CPU baseline: kraken2 itself when the box has it, else the oracle on the host cores; bounded sample (rank 0, N=1 only)
-    if solo and not args.no_cpu_baseline:
+    if args.full and solo and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cx, args, live, args.cpu_seconds)
     # ---- e2e: files in -> files out through nh_run on the same engine (N=1 only) --------------------
     plain_pe = not (args.ont or args.single_end)
-    if solo and not args.no_e2e and plain_pe:
+    if args.full and solo and not args.no_e2e and plain_pe:
         try:
             out["config"]["e2e"], details["e2e"] = e2e_leg(cx, args, live["eng"])
         except Exception as ex:  # the e2e leg must never cost the headline line
@@ -529,13 +560,13 @@ def main():
     # over the devices, peer copies, ncclCommInitAll, one writer per file -- which N single-device rank processes never
     # touch.  Rank 0 writes the inputs and the database directory now and runs the leg in a FRESH child
     # process once every rank has closed its engine and left the process group (below).
-    multi = cx.rank == 0 and cx.world > 1 and not args.no_e2e and not (args.ont or args.single_end)
+    multi = args.full and cx.rank == 0 and cx.world > 1 and not args.no_e2e and not (args.ont or args.single_end)
     if not multi:  # (rank 0 keeps its engine until the leg's database directory is written, below)
         live["eng"].close()
         del live
         torch.cuda.empty_cache()
     # ---- the output stage on its own: the GPU gzip encoder on FASTQ text (N=1 only) ------------------------------
-    if solo and not args.no_e2e and plain_pe:
+    if args.full and solo and not args.no_e2e and plain_pe:
         try:
             gzl = gzip_leg(cx, args)
             details["gzip_encoder"] = gzl
@@ -546,7 +577,7 @@ def main():
         except Exception as ex:
             out["config"].setdefault("e2e", {})["gzip_encoder"] = {"error": repr(ex)[:300]}
     # ---- variants at reduced step counts (N=1 only): inside `roofline`, numbers only ------------------------
-    if solo and not args.no_variants and not (args.ont or args.single_end or args.hit_frac):
+    if args.full and solo and not args.no_variants and not (args.ont or args.single_end or args.hit_frac):
         variants = {}
         details["variants"] = {}
         for name, kw in (("se", dict(single_end=True, pairs=1_000_000)),            # configs[1]
@@ -607,7 +638,7 @@ def main():
                 import shutil
                 shutil.rmtree(multi_spec["tmp"], ignore_errors=True)
     flatten_e2e(out["config"])
-    if cx.rank == 0:
+    if args.full and cx.rank == 0:
         write_details(details)
     if cx.rank == 0:
         print(json.dumps(out), flush=True)
@@ -672,6 +703,34 @@ def write_details(details):
             fo.write(txt + "\n")
     except OSError:
         pass
+
+
+DUMP_LIMIT_BYTES = 64_000_000 - 4096  # (64 MB in all, the .npy headers included)
+
+
+def dump_outputs(out_dir, last):
+    """--dump-outputs: the records of the last timed launch, one .npy per field (module docstring).  call in float64
+    (a uint32 taxon id), the three counts in float32 (a read of at most 200000 bases has fewer than 2^24 k-mers); when
+    that exceeds DUMP_LIMIT_BYTES, the rows of a fixed seeded sample, in order, and their positions."""
+    import numpy as np
+    rec, counters = last["results"], last["counters"]
+    n = rec.shape[0]
+    row_bytes = 8 + 3 * 4
+    rows = None
+    if n * row_bytes + counters.nbytes > DUMP_LIMIT_BYTES:
+        k = (DUMP_LIMIT_BYTES - counters.nbytes) // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(20250101).choice(n, size=k, replace=False))
+        rec = rec[rows]
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"call": rec[:, 0].astype(np.float64), "total_kmers": rec[:, 1].astype(np.float32),
+              "clade_hits": rec[:, 2].astype(np.float32), "hit_groups": rec[:, 3].astype(np.float32),
+              "counters": counters.astype(np.float64)}
+    if rows is not None:
+        arrays["row_index"] = rows.astype(np.float64)
+    elif os.path.exists(os.path.join(out_dir, "row_index.npy")):  # (left by an earlier, sampled dump)
+        os.remove(os.path.join(out_dir, "row_index.npy"))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def rank_table(cx, kernel_ms):

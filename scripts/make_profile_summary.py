@@ -63,7 +63,7 @@ if bj:
         bj['value'], bj['unit'], bj['ms_per_step'], bj['roofline']['kernel_ms'], bj['roofline']['frac']))
     out.append("# workload: " + bj['config']['workload'])
 out.append("")
-out.append("== rocprofv3 --kernel-trace --stats (trace_kernel_stats.csv), our kernels (ALL dispatches: wake launches, %d warm-ups, the timed steps, the two-stream repetition)" % WARMUP)
+out.append("== rocprofv3 --kernel-trace --stats (trace_kernel_stats.csv), our kernels (ALL dispatches: wake launches, %d warm-ups, the timed steps)" % WARMUP)
 for row in csv.reader(open(os.path.join(src, 'trace/trace_kernel_stats.csv'))):
     if row and (row[0] == 'Name' or 'nh::' in row[0]):
         out.append("  " + ", ".join(c[:70] for c in row))
@@ -75,8 +75,8 @@ for f in glob.glob(os.path.join(src, 'trace/*kernel_trace.csv')):
     d = [(int(r['End_Timestamp']) - int(r['Start_Timestamp'])) for r in rows]
     if GENERIC and d:
         d = [x for x in d if x > 0.2 * max(d)]
-    # the trace holds: bench.py's untimed wake launches (roofline.wake_launches), the warm-up steps, the K timed steps, then the
-    # two-stream repetition (2 + K launches): the timed region is what counts
+    # the trace holds bench.py's untimed wake launches (roofline.wake_launches), the warm-up steps and the K timed steps (a run
+    # without --full): the timed region is what counts
     wake = int(bj['roofline'].get('wake_launches', 0)) if bj else 0
     durs = d[wake + WARMUP:wake + WARMUP + int(bj['steps'])] if bj else d[WARMUP:]
 steady = None

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 OUT=$REPO/gpurun_out/prof_${TAG}_e2e
 mkdir -p "$OUT"
 cd /tmp
-rocprofv3 --output-format csv --kernel-trace --stats -d "$OUT/trace" -o trace -- python3 $REPO/bench.py --no-variants --no-cpu-baseline --steps 3 --warmup 1 > "$OUT/bench.json" 2> "$OUT/trace.err"
+rocprofv3 --output-format csv --kernel-trace --stats -d "$OUT/trace" -o trace -- python3 $REPO/bench.py --full --no-variants --no-cpu-baseline --steps 3 --warmup 1 > "$OUT/bench.json" 2> "$OUT/trace.err"
 cd "$REPO"
 find "$OUT" -name "*.db" -delete 2>/dev/null
 find "$OUT" -name "*kernel_trace.csv" -delete 2>/dev/null

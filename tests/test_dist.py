@@ -238,7 +238,7 @@ def test_bench_gpus_n_measures_the_products_own_multi_device_run(tmp_path):
                NOHUMAN_GZDEV_MIN_BYTES="0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--pairs", "100000",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--pairs", "100000",
            "--capacity", "200000033", "--pool", "2", "--no-cpu-baseline", "--no-variants", "--e2e-pairs", "20000", "--e2e-distinct", "2",
            "--e2e-multi-pairs", "40000", "--wake-ms", "10"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
