@@ -300,6 +300,17 @@ int nh_allreduce_counters(const int32_t *device_ids, int32_t n_devices, uint64_t
                           size_t backend_len);
 /* nh_run on an already opened engine (single device) */
 int nh_run_engine(nh_engine *e, const nh_run_args *args, nh_stats *stats);
+/*
+ * Split run: nh_run that also writes the classified (human) records, in the same pass.  out1 / out2 of `args` receive
+ * exactly what nh_run writes with keep_human = 0, human_out1 / human_out2 exactly what it writes with keep_human = 1
+ * (" kraken:taxid|<id>" suffix included); kraken_output / report / stats exactly as one nh_run.  One codec
+ * (args->out_codec) for all outputs.  The classified-out text is built in the GPU's memory.  NH_EINVAL, before any device
+ * is touched: human_out1 NULL; keep_human not 0; human_out2 given without in2 or missing with in2; a human output that
+ * names an input, out1, out2, kraken_output, report or the other human output.
+ */
+int nh_run_split(const nh_run_args *args, const char *human_out1, const char *human_out2, nh_stats *stats);
+int nh_run_engine_split(nh_engine *e, const nh_run_args *args, const char *human_out1, const char *human_out2,
+                        nh_stats *stats);
 
 #ifdef __cplusplus
 }

@@ -500,6 +500,7 @@ void destroy(Engine *e) {
     if (e->d_parent) (void)hipFree(e->d_parent);
     if (e->d_counters) (void)hipFree(e->d_counters);
     if (e->d_error) (void)hipFree(e->d_error);
+    if (e->d_external) (void)hipFree(e->d_external);
     if (e->d_work) (void)hipFree(e->d_work);
     if (e->d_cshard) (void)hipFree(e->d_cshard);
     if (e->d_defer) (void)hipFree(e->d_defer);
@@ -981,6 +982,8 @@ int check_error_flag(Engine *e) {
         HIP_TRY(hipMemset(e->d_error + LAUNCH_SLOTS, 0, sizeof(int)));
         if (flag & 2)
             return set_error(NH_EINVAL, "a sequence of 2^31 bases or more is not supported");
+        if (flag & 4)
+            return set_error(NH_EDEVICE, "classified-out builder: a record lies outside its batch's text or output buffer");
         return set_error(NH_ECAPACITY, "a fragment hit more than 2048 distinct taxa");
     }
     return NH_OK;

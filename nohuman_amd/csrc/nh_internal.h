@@ -81,6 +81,7 @@ struct Engine {
     hipStream_t stream = nullptr;
     std::vector<uint32_t> parent;
     std::vector<uint64_t> external;
+    uint64_t *d_external = nullptr;  // `external` in HBM (the classified-out builder, nh_split.hip): made by a run that needs it
     std::vector<uint8_t> taxo_image, opts_image;
     Staging st;
     std::mutex mu;
@@ -121,6 +122,27 @@ int classify_host(Engine *e, const uint8_t *bases, const uint64_t *seq_offsets, 
                   uint32_t flags, double confidence, nh_result *results, uint32_t *kmer_taxa,
                   uint64_t *kmer_taxa_offsets, uint64_t kmer_taxa_cap);
 int check_error_flag(Engine *e);
+// The classified-out records of one batch built in HBM (nh_split.hip; nh_run_split's human outputs): both mates' text as
+// the classifier sees it, out[m] receives mate m's records of the fragments with call != 0, total[m] their bytes.
+struct HumanOutArgs {
+    const char *text;         // the batch's text (d_text), ntext bytes
+    uint64_t ntext;
+    const uint64_t *seq_off;  // n * mates sequence starts (absolute), as classified
+    const uint32_t *seq_len;  // n * mates sequence lengths
+    const uint32_t *rec;      // n * mates {header start (absolute), header length, qualities start (absolute), length}
+    const nh_result *res;     // n results
+    const uint64_t *ext;      // internal -> external taxon id, n_ext entries
+    uint64_t n_ext, n, nblk;  // nblk = human_out_blocks(n)
+    int mates;
+    int fastq[2];             // per mate: FASTQ (else FASTA)
+    char *out[2];
+    uint64_t cap[2];          // bytes of out[m]
+    uint64_t *blk;            // 2 * nblk words of scratch
+    uint64_t *total;          // 2 words
+    int *error;               // the engine's sticky error word (bit 4: a record outside its text or buffer)
+};
+uint64_t human_out_blocks(uint64_t n);
+hipError_t launch_human_out(const HumanOutArgs &a, hipStream_t stream);
 // buffers kept between the runs of a process (nh_run.hip: page-locked batch text; nh_gunzip.hip: the gzip reader's HBM and
 // staging): emptied when an engine is closed
 void run_cache_trim();

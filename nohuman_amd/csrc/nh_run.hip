@@ -340,6 +340,15 @@ struct Slot {  // pinned host + device buffers of one in-flight batch
     size_t cap_text = 0, cap_frag = 0, cap_taxa = 0;
     uint64_t n_taxa = 0;
     bool busy = false;
+    // split runs (nh_run_split): per sequence {h, hlen, q, qlen}, the classified-out records built in HBM per mate, the
+    // builder's scratch, and the per-mate byte totals that come back with the results (host copies: only where an encoder
+    // cannot take the HBM range)
+    uint32_t *h_rec = nullptr;
+    void *d_rec = nullptr, *d_hblk = nullptr;
+    char *d_hout[2] = {nullptr, nullptr}, *h_hout[2] = {nullptr, nullptr};
+    size_t cap_hout[2] = {0, 0}, cap_hhost[2] = {0, 0}, cap_rec = 0, cap_hblk = 0;
+    uint64_t *h_htotal = nullptr;
+    hipEvent_t hev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around the builder's launches (its kernel time)
 };
 
 static int slot_reserve(Slot &s, size_t ntext, size_t nfrag, size_t ntaxa) {
@@ -382,9 +391,56 @@ static int slot_reserve(Slot &s, size_t ntext, size_t nfrag, size_t ntaxa) {
     return NH_OK;
 }
 
+// the split run's buffers of a slot: records of n fragments (mates per fragment), out_cap[m] bytes of classified-out text
+static int slot_reserve_human(Slot &s, size_t n, int mates, const size_t out_cap[2]) {
+    auto grow = [](size_t need) { return need + need / 4 + 4096; };
+    if (!s.h_htotal && host_malloc((void **)&s.h_htotal, 64, hipHostMallocDefault) != hipSuccess)
+        return set_error(NH_EOOM, "cannot allocate batch buffers");
+    if (n * mates > s.cap_rec) {
+        if (s.h_rec) (void)hipHostFree(s.h_rec);
+        if (s.d_rec) (void)hipFree(s.d_rec);
+        s.h_rec = nullptr, s.d_rec = nullptr;
+        s.cap_rec = grow(n * mates);
+        if (host_malloc((void **)&s.h_rec, s.cap_rec * 16, hipHostMallocDefault) != hipSuccess || dev_malloc(&s.d_rec, s.cap_rec * 16) != hipSuccess)
+            return set_error(NH_EOOM, "cannot allocate batch buffers (%zu records)", s.cap_rec);
+    }
+    const size_t words = 2 * human_out_blocks(n) + 2;
+    if (words > s.cap_hblk) {
+        if (s.d_hblk) (void)hipFree(s.d_hblk);
+        s.cap_hblk = grow(words);
+        if (dev_malloc(&s.d_hblk, s.cap_hblk * 8) != hipSuccess) return set_error(NH_EOOM, "cannot allocate batch buffers");
+    }
+    for (int m = 0; m < mates; m++)
+        if (out_cap[m] > s.cap_hout[m]) {
+            if (s.d_hout[m]) (void)hipFree(s.d_hout[m]);
+            s.cap_hout[m] = grow(out_cap[m]);
+            if (dev_malloc((void **)&s.d_hout[m], s.cap_hout[m]) != hipSuccess)
+                return set_error(NH_EOOM, "cannot allocate classified-out buffers (%zu bytes)", s.cap_hout[m]);
+        }
+    return NH_OK;
+}
+
+// page-locked room for `n` bytes of mate m's classified-out text on the host (the writer's copy for host encoders)
+static int slot_reserve_human_host(Slot &s, int m, size_t n) {
+    if (n <= s.cap_hhost[m]) return NH_OK;
+    if (s.h_hout[m]) (void)hipHostFree(s.h_hout[m]);
+    s.cap_hhost[m] = n + n / 4 + 4096;
+    if (host_malloc((void **)&s.h_hout[m], s.cap_hhost[m], hipHostMallocDefault) != hipSuccess) {
+        s.h_hout[m] = nullptr, s.cap_hhost[m] = 0;
+        return set_error(NH_EOOM, "cannot allocate classified-out buffers (%zu bytes)", n);
+    }
+    return NH_OK;
+}
+
 static void slot_free(Slot &s) {
     if (!s.e) return;
     (void)dev_set(s.e->device);
+    for (void *p : {(void *)s.h_rec, (void *)s.h_hout[0], (void *)s.h_hout[1], (void *)s.h_htotal})
+        if (p) (void)hipHostFree(p);
+    for (void *p : {s.d_rec, s.d_hblk, (void *)s.d_hout[0], (void *)s.d_hout[1]})
+        if (p) (void)hipFree(p);
+    for (hipEvent_t ev : s.hev)
+        if (ev) (void)hipEventDestroy(ev);
     for (void *p : {(void *)s.h_off, (void *)s.h_len, (void *)s.h_res, (void *)s.h_taxa, (void *)s.h_taxa_off, (void *)s.h_flag})
         if (p) (void)hipHostFree(p);
     for (void *p : {s.d_text, s.d_off, s.d_len, s.d_res, s.d_taxa, s.d_taxa_off})
@@ -465,6 +521,11 @@ struct RunState {
     bool paired, want_k;
     // results of the run
     uint64_t total = 0, classified = 0, total_bases = 0;
+    // split runs (NOHUMAN_TRACE): what the classified-out builder made, and the bytes of record text the run copied back to
+    // the host -- classified-out text for host encoders, and batches of the reader on the GPU fetched for the other side
+    uint64_t human_records = 0, human_bytes = 0;
+    double human_kernel_ms = 0;  // NOHUMAN_TRACE: the builder's launches, by events on the slots' streams
+    std::atomic<uint64_t> text_fetched{0};
     std::vector<uint64_t> dev_counts;  // per device {fragments, classified, bases, 0} as the writer saw them (checker)
     std::vector<uint64_t *> d_run_counters;  // per device: the counters the classify kernels of THIS run add to (HBM)
     std::vector<uint64_t> call_counts;
@@ -786,9 +847,62 @@ static void format_batch(RunState *rs, const Batch &b, const Slot &s, OutFile &o
     dc[2] += bases;
 }
 
-int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_stats *stats) {
+// the engine's internal -> external taxon ids in its HBM (once per engine): the digits of "kraken:taxid|N" built there
+static int ensure_device_external(Engine *e) {
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (e->d_external) return NH_OK;
+    if (dev_set(e->device) != hipSuccess) return set_error(NH_EDEVICE, "hipSetDevice failed");
+    const size_t nb = std::max<size_t>(1, e->external.size()) * sizeof(uint64_t);
+    uint64_t *d = nullptr;
+    if (dev_malloc(&d, nb) != hipSuccess) return set_error(NH_EOOM, "cannot allocate the taxon id table on device %d", e->device);
+    if (!e->external.empty() && hipMemcpy(d, e->external.data(), e->external.size() * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(d);
+        return set_error(NH_EDEVICE, "cannot copy the taxon id table to device %d", e->device);
+    }
+    e->d_external = d;
+    return NH_OK;
+}
+
+// nh_run_split's own arguments, checked before any device is touched
+static int check_split_args(const nh_run_args *a, const char *h1, const char *h2) {
+    if (!a) return set_error(NH_EINVAL, "nh_run_split: null arguments");
+    if (!h1 || !h1[0]) return set_error(NH_EINVAL, "nh_run_split: human_out1 is required");
+    if (a->keep_human != 0) return set_error(NH_EINVAL, "nh_run_split: keep_human must be 0 (the human reads go to human_out1 / human_out2)");
+    if (a->in2 && !h2) return set_error(NH_EINVAL, "nh_run_split: paired input needs human_out2");
+    if (!a->in2 && h2) return set_error(NH_EINVAL, "nh_run_split: human_out2 is given without in2");
+    if (h2 && !strcmp(h1, h2)) return set_error(NH_EINVAL, "nh_run_split: human_out1 and human_out2 are the same file");
+    for (const char *h : {h1, h2}) {
+        if (!h) continue;
+        struct stat sh;
+        const bool hs = stat(h, &sh) == 0 && S_ISREG(sh.st_mode);
+        for (const char *p : {a->in1, a->in2}) {
+            struct stat si;
+            if (p && (!strcmp(p, h) || (hs && stat(p, &si) == 0 && si.st_dev == sh.st_dev && si.st_ino == sh.st_ino)))
+                return set_error(NH_EINVAL, "nh_run_split: human output %s is the input %s", h, p);
+        }
+        for (const char *o : {a->out1, a->out2, a->kraken_output, a->report}) {
+            struct stat so;
+            if (o && o[0] && (!strcmp(o, h) || (hs && stat(o, &so) == 0 && so.st_dev == sh.st_dev && so.st_ino == sh.st_ino)))
+                return set_error(NH_EINVAL, "nh_run_split: human output %s is also the output %s", h, o);
+        }
+    }
+    return NH_OK;
+}
+
+// hout1 set: a split run (nh_run_split) -- a->keep_human is 0, hout1 / hout2 receive the classified records
+int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_stats *stats, const char *hout1 = nullptr,
+                const char *hout2 = nullptr) {
     if (!a || !a->in1 || !a->out1) return set_error(NH_EINVAL, "nh_run: in1 and out1 are required");
     if (engines.empty()) return set_error(NH_EINVAL, "nh_run: no engine");
+    const bool split = hout1 != nullptr;
+    if (split) {
+        const int vrc = check_split_args(a, hout1, hout2);
+        if (vrc) return vrc;
+        for (Engine *e : engines) {
+            const int erc = ensure_device_external(e);
+            if (erc) return erc;
+        }
+    }
     RunState rs;
     rs.a = a;
     rs.engines = engines;
@@ -807,7 +921,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
     }
     // outputs are created with O_TRUNC before the first input byte is read: an output that IS an input
     // (same device and inode) would be emptied -- refuse (the CLI host stages its outputs and renames)
-    for (const char *o : {a->out1, a->out2, rs.want_k ? a->kraken_output : nullptr, a->report}) {
+    for (const char *o : {a->out1, a->out2, rs.want_k ? a->kraken_output : nullptr, a->report, hout1, hout2}) {
         struct stat so;
         if (!o || !o[0] || stat(o, &so) != 0 || !S_ISREG(so.st_mode)) continue;
         for (const char *p : {a->in1, a->in2}) {
@@ -816,7 +930,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 return set_error(NH_EINVAL, "nh_run: output %s is the input %s", o, p);
         }
     }
-    OutFile o1, o2, ok;
+    OutFile o1, o2, ok, h1, h2;  // (h1, h2: the classified records of a split run)
     int rc;
     if (a->out_codec < NH_CODEC_NONE || a->out_codec > NH_CODEC_ZSTD)
         return set_error(NH_EINVAL, "nh_run: unknown out_codec %d", a->out_codec);
@@ -831,10 +945,28 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 rc2 = o2.open(a->out2, a->out_codec, a->codec_threads, engines[engines.size() > 1 ? 1 : 0]->device);
                 if (rc2) err2 = g_last_error;
             });
+        int rch1 = NH_OK, rch2 = NH_OK;
+        std::string errh1, errh2;
+        std::thread th1, th2;
+        if (split) {
+            th1 = std::thread([&] {
+                rch1 = h1.open(hout1, a->out_codec, a->codec_threads, engines[0]->device);
+                if (rch1) errh1 = g_last_error;
+            });
+            if (rs.paired)
+                th2 = std::thread([&] {
+                    rch2 = h2.open(hout2, a->out_codec, a->codec_threads, engines[engines.size() > 1 ? 1 : 0]->device);
+                    if (rch2) errh2 = g_last_error;
+                });
+        }
         rc = o1.open(a->out1, a->out_codec, a->codec_threads, engines[0]->device);
         if (t2.joinable()) t2.join();
+        if (th1.joinable()) th1.join();
+        if (th2.joinable()) th2.join();
         if (rc) return rc;
         if (rc2) return set_error(rc2, "%s", err2.c_str());
+        if (rch1) return set_error(rch1, "%s", errh1.c_str());
+        if (rch2) return set_error(rch2, "%s", errh2.c_str());
     }
     if (rs.want_k && (rc = ok.open(a->kraken_output))) return rc;
 
@@ -863,6 +995,10 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                                     (!rs.paired || (o2.enc && o2.enc->takes_device_spans()))) ||
                                   rs.want_k || a->keep_human != 0 || G > 1;  // (G > 1: a batch's slot and its file's encoder may sit on different GPUs)
     const uint32_t flags = rs.paired ? NH_FLAG_PAIRED : 0;
+    // split runs: the classified-out text is built in HBM; an encoder on the slot's GPU takes it from there, any other output
+    // gets exactly the built bytes copied to the host (G > 1: a batch's slot and its file's encoder may sit on different GPUs)
+    const bool human_in_hbm = split && G == 1 && h1.enc && h1.enc->takes_device_spans() &&
+                              (!rs.paired || (h2.enc && h2.enc->takes_device_spans()));
     auto t0 = std::chrono::steady_clock::now();
 
     rs.d_run_counters.assign((size_t)G, nullptr);
@@ -892,7 +1028,9 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
         slots[i].e = engines[i / NS];
         slots[i].work_slot = i % NS;
         if (dev_set(slots[i].e->device) != hipSuccess ||
-            hipStreamCreateWithFlags(&slots[i].stream, hipStreamNonBlocking) != hipSuccess) {
+            hipStreamCreateWithFlags(&slots[i].stream, hipStreamNonBlocking) != hipSuccess ||
+            (split && getenv("NOHUMAN_TRACE") &&
+             (hipEventCreate(&slots[i].hev[0]) != hipSuccess || hipEventCreate(&slots[i].hev[1]) != hipSuccess))) {
             for (auto &s : slots) slot_free(s);
             free_run_counters();
             return set_error(NH_EDEVICE, "cannot create streams");
@@ -992,7 +1130,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
     // formatting came on top, profiles/r04_e2e.txt.)
     struct FlushJob {
         Batch b;
-        Spans s1, s2, sk;
+        Spans s1, s2, sk, hs1, hs2;  // (hs1, hs2: a split run's classified records, one span a mate)
         bool valid = false;  // (false: the run had failed when the batch arrived -- only its buffers go back)
     };
     BoundedQueue<Batch> wq((size_t)(NS * G));
@@ -1002,7 +1140,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
     std::mutex w2_mu;
     std::condition_variable w2_cv;
     int w2_state = 0;  // 0 idle, 1 flush requested, 2 done, -1 quit
-    Spans *w2_spans = nullptr;
+    Spans *w2_spans = nullptr, *w2_hspans = nullptr;
     int w2_rc = NH_OK;
     std::string w2_err;
     std::thread tw2;
@@ -1012,9 +1150,10 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 std::unique_lock<std::mutex> lk(w2_mu);
                 w2_cv.wait(lk, [&] { return w2_state == 1 || w2_state == -1; });
                 if (w2_state == -1) return;
-                Spans *sp2 = w2_spans;
+                Spans *sp2 = w2_spans, *hsp2 = w2_hspans;
                 lk.unlock();
                 int frc = o2.flush(*sp2);
+                if (!frc && hsp2) frc = h2.flush(*hsp2);
                 lk.lock();
                 w2_rc = frc;
                 if (frc) w2_err = g_last_error;
@@ -1037,14 +1176,22 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 if (o1.enc) o1.enc->map_device(b.h1->text.data(), b.len1, s.d_text, s.e->device, b.h1->host_text_valid);
                 if (rs.paired && o2.enc)
                     o2.enc->map_device(b.h2->text.data(), b.len2, (const char *)s.d_text + base2w, s.e->device, b.h2->host_text_valid);
+                // the classified records that only exist in HBM: their span's address is the device buffer's, never read on the host
+                if (human_in_hbm)
+                    for (int m = 0; m < mates; m++) {
+                        Spans &hs = m ? j->hs2 : j->hs1;
+                        if (!hs.iov.empty()) (m ? h2 : h1).enc->map_device(hs.iov[0].iov_base, hs.iov[0].iov_len, s.d_hout[m], s.e->device, false);
+                    }
                 if (rs.paired) {
                     std::lock_guard<std::mutex> lk(w2_mu);
                     w2_spans = &j->s2;
+                    w2_hspans = split ? &j->hs2 : nullptr;
                     w2_state = 1;
                     w2_cv.notify_all();
                 }
                 int wrc = o1.flush(j->s1);
                 if (!wrc && rs.want_k) wrc = ok.flush(j->sk);
+                if (!wrc && split) wrc = h1.flush(j->hs1);
                 if (rs.paired) {
                     std::unique_lock<std::mutex> lk(w2_mu);
                     w2_cv.wait(lk, [&] { return w2_state == 2; });
@@ -1102,11 +1249,35 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                             if (!dst) wrc = set_error(NH_EOOM, "out of memory");
                             if (!wrc && hipMemcpy(dst.get(), (const char *)s.d_text + (m ? base2w : 0), L, hipMemcpyDeviceToHost) != hipSuccess)
                                 wrc = set_error(NH_EDEVICE, "fetching a batch's text from the device failed");
+                            rs.text_fetched += L;
                         }
                     }
                 }
                 if (!wrc) {
                     format_batch(&rs, b, s, o1, o2, ok);
+                    // a split run's classified records: the text the builder made, one span a mate -- in HBM, or copied here
+                    if (split && s.hev[1]) {  // (the stream was synchronised above: both events have completed)
+                        float ms = 0;
+                        if (hipEventElapsedTime(&ms, s.hev[0], s.hev[1]) == hipSuccess) rs.human_kernel_ms += ms;
+                    }
+                    for (int m = 0; split && m < mates && !wrc; m++) {
+                        const size_t tot = (size_t)s.h_htotal[m];
+                        rs.human_bytes += tot;
+                        if (!tot) continue;
+                        char *at = s.d_hout[m];
+                        if (!human_in_hbm) {
+                            wrc = slot_reserve_human_host(s, m, tot);
+                            if (!wrc && hipMemcpy(s.h_hout[m], s.d_hout[m], tot, hipMemcpyDeviceToHost) != hipSuccess)
+                                wrc = set_error(NH_EDEVICE, "fetching a batch's classified records from the device failed");
+                            at = s.h_hout[m];
+                            rs.text_fetched += tot;
+                        }
+                        Spans &hs = m ? j->hs2 : j->hs1;
+                        hs.iov.push_back({(void *)at, tot});
+                        hs.is_scratch.push_back(0);
+                    }
+                    if (split)
+                        for (size_t i = 0; i < b.n; i++) rs.human_records += s.h_res[i].call != 0;
                     clk.ns[ST_WFORMAT] += StageClock::now() - c2;
                     j->s1 = std::move(o1.sp);
                     j->s2 = std::move(o2.sp);
@@ -1221,6 +1392,10 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 }
             }
             rc = slot_reserve(s, ntext, b.n, ntaxa + 1);
+            if (!rc && split) {  // a mate's classified-out text: its records less what normalisation drops, plus 36 bytes a suffix
+                const size_t out_cap[2] = {len1 + b.n * 36 + 64, len2 + b.n * 36 + 64};
+                rc = slot_reserve_human(s, b.n, mates, out_cap);
+            }
             if (rc) {
                 rs.fail(rc, g_last_error);
                 wq.push(std::move(b));
@@ -1233,6 +1408,14 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 s.h_off[i * mates] = r1.s;
                 s.h_len[i * mates] = r1.slen;
                 nbases += r1.slen;
+                if (split) {
+                    uint32_t *hr = s.h_rec + 4 * i * mates;
+                    hr[0] = r1.h, hr[1] = r1.hlen, hr[2] = r1.q, hr[3] = r1.qlen;
+                    if (rs.paired) {
+                        const RecRef &r2 = b.h2->recs[b.off2 + i];
+                        hr[4] = (uint32_t)(base2 + r2.h), hr[5] = r2.hlen, hr[6] = (uint32_t)(base2 + r2.q), hr[7] = r2.qlen;
+                    }
+                }
                 if (rs.want_k) {
                     s.h_taxa_off[i] = toff;
                     toff += r1.slen >= k ? r1.slen - k + 1 : 0;
@@ -1266,6 +1449,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                     if (!hb.text.reserve(len + 64)) return hipErrorOutOfMemory;
                     hb.text.set_size(len);
                     e2 = hipMemcpyAsync(hb.text.data(), (char *)s.d_text + at, len, hipMemcpyDeviceToHost, s.stream);
+                    rs.text_fetched += len;
                     hb.host_text_valid = true;  // (once the stream has been synchronised: the writer does that first)
                 }
                 return e2;
@@ -1278,6 +1462,8 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 he = hipMemcpyAsync(s.d_len, s.h_len, b.n * mates * 4, hipMemcpyHostToDevice, s.stream);
             if (he == hipSuccess && rs.want_k)
                 he = hipMemcpyAsync(s.d_taxa_off, s.h_taxa_off, (b.n + 1) * 8, hipMemcpyHostToDevice, s.stream);
+            if (he == hipSuccess && split)
+                he = hipMemcpyAsync(s.d_rec, s.h_rec, b.n * mates * 16, hipMemcpyHostToDevice, s.stream);
             if (he != hipSuccess) {
                 rs.fail(NH_EDEVICE, std::string("H2D: ") + hipGetErrorString(he));
             } else {
@@ -1287,12 +1473,39 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                                      rs.d_run_counters[(size_t)(si / NS)], s.stream, s.d_len, ntext);
                 if (rc) rs.fail(rc, g_last_error);
             }
+            uint64_t *d_htotal = nullptr;
+            if (!rs.failed() && split) {  // the classified records of both mates, built behind the classifier on the same stream
+                HumanOutArgs ha{};
+                ha.text = (const char *)s.d_text;
+                ha.ntext = ntext;
+                ha.seq_off = (const uint64_t *)s.d_off;
+                ha.seq_len = (const uint32_t *)s.d_len;
+                ha.rec = (const uint32_t *)s.d_rec;
+                ha.res = (const nh_result *)s.d_res;
+                ha.ext = s.e->d_external;
+                ha.n_ext = s.e->external.size();
+                ha.n = b.n;
+                ha.nblk = human_out_blocks(b.n);
+                ha.mates = mates;
+                ha.fastq[0] = b.h1->format == FMT_FASTQ;
+                ha.fastq[1] = rs.paired && b.h2->format == FMT_FASTQ;
+                for (int m = 0; m < mates; m++) ha.out[m] = s.d_hout[m], ha.cap[m] = s.cap_hout[m];
+                ha.blk = (uint64_t *)s.d_hblk;
+                ha.total = d_htotal = (uint64_t *)s.d_hblk + 2 * ha.nblk;
+                ha.error = s.e->d_error + LAUNCH_SLOTS;
+                if (s.hev[0]) (void)hipEventRecord(s.hev[0], s.stream);
+                he = launch_human_out(ha, s.stream);
+                if (s.hev[1] && he == hipSuccess) he = hipEventRecord(s.hev[1], s.stream);
+                if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("classified-out builder: ") + hipGetErrorString(he));
+            }
             if (!rs.failed()) {
                 he = hipMemcpyAsync(s.h_res, s.d_res, b.n * sizeof(nh_result), hipMemcpyDeviceToHost, s.stream);
                 if (he == hipSuccess)
                     he = hipMemcpyAsync(s.h_flag, s.e->d_error + LAUNCH_SLOTS, sizeof(int), hipMemcpyDeviceToHost, s.stream);
                 if (he == hipSuccess && rs.want_k && toff)
                     he = hipMemcpyAsync(s.h_taxa, s.d_taxa, toff * 4, hipMemcpyDeviceToHost, s.stream);
+                if (he == hipSuccess && split)
+                    he = hipMemcpyAsync(s.h_htotal, d_htotal, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
                 if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("D2H: ") + hipGetErrorString(he));
             }
             batch_no++;
@@ -1335,6 +1548,10 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                     std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
             for (int i = 0; i < 12; i++) fprintf(stderr, " %s %.3f", names[i], (double)clk.ns[i].load() * 1e-9);
             fprintf(stderr, "\n");
+            if (split)
+                fprintf(stderr, "[nohuman trace] human-out: %llu records, %llu bytes built on device; %llu fetched to host; builder kernels %.3f ms (%.1f GB/s of text)\n",
+                        (unsigned long long)rs.human_records, (unsigned long long)rs.human_bytes, (unsigned long long)rs.text_fetched.load(),
+                        rs.human_kernel_ms, rs.human_kernel_ms > 0 ? (double)rs.human_bytes / (rs.human_kernel_ms * 1e6) : 0.0);
             if (g_pageable_batches.load())
                 fprintf(stderr, "[nohuman trace] %d batch buffers could not be page-locked (pageable memory used)\n",
                         g_pageable_batches.load());
@@ -1414,10 +1631,28 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 rc2 = o2.close();
                 if (rc2) err2 = g_last_error;
             });
+        int rch1 = NH_OK, rch2 = NH_OK;
+        std::string errh1, errh2;
+        std::thread th1, th2;
+        if (split) {
+            th1 = std::thread([&] {
+                rch1 = h1.close();
+                if (rch1) errh1 = g_last_error;
+            });
+            if (rs.paired)
+                th2 = std::thread([&] {
+                    rch2 = h2.close();
+                    if (rch2) errh2 = g_last_error;
+                });
+        }
         rc = o1.close();
         if (t2.joinable()) t2.join();
+        if (th1.joinable()) th1.join();
+        if (th2.joinable()) th2.join();
         if (rc) return rc;
         if (rc2) return set_error(rc2, "%s", err2.c_str());
+        if (rch1) return set_error(rch1, "%s", errh1.c_str());
+        if (rch2) return set_error(rch2, "%s", errh2.c_str());
     }
     if (rs.want_k && (rc = ok.close())) return rc;
     if (stats) {
@@ -1433,9 +1668,9 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
     return NH_OK;
 }
 
-int run_engine(Engine *e, const nh_run_args *a, nh_stats *stats) {
+int run_engine(Engine *e, const nh_run_args *a, nh_stats *stats, const char *hout1 = nullptr, const char *hout2 = nullptr) {
     std::vector<Engine *> v{e};
-    return run_engines(v, a, stats);
+    return run_engines(v, a, stats, hout1, hout2);
 }
 
 }  // namespace nh
@@ -1445,6 +1680,13 @@ extern "C" {
 int nh_run_engine(nh_engine *e, const nh_run_args *args, nh_stats *stats) {
     if (!e) return nh::set_error(NH_EINVAL, "null engine");
     return nh::run_engine((nh::Engine *)e, args, stats);
+}
+
+int nh_run_engine_split(nh_engine *e, const nh_run_args *args, const char *human_out1, const char *human_out2, nh_stats *stats) {
+    const int rc = nh::check_split_args(args, human_out1, human_out2);
+    if (rc) return rc;
+    if (!e) return nh::set_error(NH_EINVAL, "null engine");
+    return nh::run_engine((nh::Engine *)e, args, stats, human_out1, human_out2);
 }
 
 int nh_fastx_scan(const char *path, uint64_t *n_records, uint64_t *n_bases, uint64_t *digest) {
@@ -1483,7 +1725,7 @@ int nh_fastx_scan(const char *path, uint64_t *n_records, uint64_t *n_bases, uint
 
 // Whole run on one or several devices: the database is loaded into every device's HBM, batches go
 // round-robin, outputs stay in input order, the counts are summed on the host.
-int nh_run(const nh_run_args *args, nh_stats *stats) {
+static int run_devices(const nh_run_args *args, nh_stats *stats, const char *hout1, const char *hout2) {
     if (!args || !args->db_dir) return nh::set_error(NH_EINVAL, "nh_run: db_dir is required");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -1519,7 +1761,7 @@ int nh_run(const nh_run_args *args, nh_stats *stats) {
     }
     const double t_load = since(t_begin);
     const auto t_run = std::chrono::steady_clock::now();
-    if (!rc) rc = nh::run_engines(engines, args, stats);
+    if (!rc) rc = nh::run_engines(engines, args, stats, hout1, hout2);
     const double s_run = since(t_run);
     std::string keep = nh::g_last_error;
     const auto t_close = std::chrono::steady_clock::now();
@@ -1529,6 +1771,14 @@ int nh_run(const nh_run_args *args, nh_stats *stats) {
                 s_run, since(t_close));
     if (rc) nh::g_last_error = keep;
     return rc;
+}
+
+int nh_run(const nh_run_args *args, nh_stats *stats) { return run_devices(args, stats, nullptr, nullptr); }
+
+int nh_run_split(const nh_run_args *args, const char *human_out1, const char *human_out2, nh_stats *stats) {
+    const int rc = nh::check_split_args(args, human_out1, human_out2);  // (before any device is touched)
+    if (rc) return rc;
+    return run_devices(args, stats, human_out1, human_out2);
 }
 
 }  // extern "C"

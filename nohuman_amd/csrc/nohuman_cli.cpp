@@ -29,6 +29,7 @@
 
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "nohuman_engine.h"
@@ -213,6 +214,8 @@ static std::vector<Installed> installed_databases(const std::string &root) {
 struct Args {
     std::vector<std::string> input;
     std::string out1, out2, database, db_version, kraken_output, kraken_report;
+    std::string human_out1, human_out2;  // split run: the human reads in the same pass (nh_run_split)
+    bool has_human_out1 = false, has_human_out2 = false;
     bool has_out1 = false, has_out2 = false, check = false, download = false, list = false, human = false;
     bool has_type = false;
     Codec type = C_NONE;
@@ -235,6 +238,8 @@ static void usage(FILE *f) {
           "  -F, --output-type <FORMAT>   Output compression format. u: uncompressed; b: Bzip2; g: Gzip; x: Xz (Lzma); z: Zstd\n"
           "  -t, --threads <INT>          Number of threads to use [default: 1]\n"
           "  -H, --human                  Output human reads instead of removing them\n"
+          "      --human-out1 <PATH>      Also write the human reads, in the same run, to this file (as -H would)\n"
+          "      --human-out2 <PATH>      Second human output file (required with two inputs)\n"
           "  -C, --conf <[0, 1]>          Kraken2 minimum confidence score [default: 0.0]\n"
           "  -k, --kraken-output <FILE>   Write the Kraken2 read classification output to a file\n"
           "  -r, --kraken-report <FILE>   Write the Kraken2 report with aggregate counts/clade to file\n"
@@ -294,6 +299,8 @@ static Args parse_args(int argc, char **argv) {
             if (*end || t.empty() || n <= 0) arg_error("invalid value '%s' for '--threads <INT>': number would be zero for non-zero type", t.c_str());
             a.threads = (unsigned)n;
         } else if (s == "-H" || s == "--human") a.human = true;
+        else if (s == "--human-out1") { a.human_out1 = val(); a.has_human_out1 = true; }
+        else if (s == "--human-out2") { a.human_out2 = val(); a.has_human_out2 = true; }
         else if (s == "-C" || s == "--conf") {
             std::string t = val();
             char *end;
@@ -314,6 +321,23 @@ static Args parse_args(int argc, char **argv) {
     }
     if (a.input.empty() && !a.check && !a.download && !a.list)
         arg_error("the following required arguments were not provided:\n  <INPUT>...");
+    // split run (--human-out1 / --human-out2): the non-human reads to -o / -O, the human ones to these, in one pass
+    if (a.has_human_out1 || a.has_human_out2) {
+        const bool paired = a.input.size() == 2;
+        if (a.human) arg_error("the argument '--human' cannot be used with '--human-out1 <PATH>'");
+        if (!a.has_human_out1) arg_error("the following required arguments were not provided:\n  --human-out1 <PATH>");
+        if (a.has_human_out2 && !paired) arg_error("the argument '--human-out2 <PATH>' needs two inputs");
+        if (paired && !a.has_human_out2)
+            arg_error("the following required arguments were not provided:\n  --human-out2 <PATH> (two inputs)");
+        for (const std::string *h : {&a.human_out1, &a.human_out2}) {
+            if (h == &a.human_out2 && !a.has_human_out2) continue;
+            const char *flag = h == &a.human_out1 ? "--human-out1" : "--human-out2";
+            if ((a.has_out1 && *h == a.out1) || (a.has_out2 && *h == a.out2))
+                arg_error("the argument '%s <PATH>' names the same file as '--out1' / '--out2': %s", flag, h->c_str());
+        }
+        if (a.has_human_out2 && a.human_out1 == a.human_out2)
+            arg_error("the arguments '--human-out1 <PATH>' and '--human-out2 <PATH>' name the same file: %s", a.human_out1.c_str());
+    }
     return a;
 }
 
@@ -344,6 +368,15 @@ static std::string default_out_name(const std::string &in, Codec out_codec) {
 
 int main(int argc, char **argv) {
     Args args = parse_args(argc, argv);
+    if (args.has_human_out1 && !args.input.empty()) {  // a human output equal to a DEFAULT output name: an argument error as well
+        const Codec c = args.has_type ? args.type : args.has_out1 ? codec_from_path(args.out1) : codec_from_magic(args.input[0]);
+        const std::string o1 = args.has_out1 ? args.out1 : default_out_name(args.input[0], c);
+        const std::string o2 = args.input.size() == 2 ? (args.has_out2 ? args.out2 : default_out_name(args.input[1], c)) : "";
+        for (const std::string *h : {&args.human_out1, &args.human_out2})
+            if (!h->empty() && (*h == o1 || *h == o2))
+                arg_error("the argument '%s <PATH>' names the same file as the output %s", h == &args.human_out1 ? "--human-out1" : "--human-out2",
+                          h->c_str());
+    }
     if (args.list) die("Failed to download database manifest: network access is not available in this build");
     if (args.download) {
         INFO("Downloading database...");
@@ -434,6 +467,20 @@ int main(int argc, char **argv) {
         return out + ".partial";
     };
     const std::string part1 = staged(out1), part2 = paired ? staged(out2) : "";
+    const bool split = args.has_human_out1;
+    const std::string hpart1 = split ? staged(args.human_out1) : "", hpart2 = split && paired ? staged(args.human_out2) : "";
+    // the staged files of this run (final path, the one written): removed when the run fails
+    // (renamed in this order: the human outputs first, so that a rename that fails part-way never leaves the non-human outputs --
+    // what the next step of a pipeline looks for -- in place without their human counterparts)
+    std::vector<std::pair<std::string, std::string>> staged_files;
+    if (split) staged_files.push_back({args.human_out1, hpart1});
+    if (split && paired) staged_files.push_back({args.human_out2, hpart2});
+    staged_files.push_back({out1, part1});
+    if (paired) staged_files.push_back({out2, part2});
+    auto unlink_staged = [&] {
+        for (const auto &f : staged_files)
+            if (f.second != f.first) unlink(f.second.c_str());
+    };
     ra.out1 = part1.c_str();
     ra.out2 = paired ? part2.c_str() : nullptr;
     ra.out_codec = codec;
@@ -454,20 +501,19 @@ int main(int argc, char **argv) {
         ra.device_ids = devs.data();
     }
     nh_stats st;
-    if (nh_run(&ra, &st) != 0) {
+    const int run_rc = split ? nh_run_split(&ra, hpart1.c_str(), paired ? hpart2.c_str() : nullptr, &st) : nh_run(&ra, &st);
+    if (run_rc != 0) {
         std::string msg = nh_last_error();
         // nothing half-written stays behind, and nothing this run did not create is touched
-        if (part1 != out1) unlink(part1.c_str());
-        if (paired && part2 != out2) unlink(part2.c_str());
+        unlink_staged();
         die("Failed to run kraken2\n\nCaused by:\n    kraken2 failed with stderr %s", msg.c_str());
     }
-    if ((part1 != out1 && rename(part1.c_str(), out1.c_str()) != 0) ||
-        (paired && part2 != out2 && rename(part2.c_str(), out2.c_str()) != 0)) {
-        const std::string why = strerror(errno);
-        if (part1 != out1) unlink(part1.c_str());
-        if (paired && part2 != out2) unlink(part2.c_str());
-        die("Failed to move the output into place: %s", why.c_str());
-    }
+    for (const auto &f : staged_files)
+        if (f.second != f.first && rename(f.second.c_str(), f.first.c_str()) != 0) {
+            const std::string why = strerror(errno);
+            unlink_staged();
+            die("Failed to move the output into place: %s", why.c_str());
+        }
     // src/lib.rs:38-45 (0/0 prints NaN there as well)
     auto pct = [&](uint64_t a) -> std::string {
         if (st.total_sequences == 0) return "NaN";
@@ -486,6 +532,10 @@ int main(int argc, char **argv) {
     } else {
         INFO("Output file written to: %s", quoted(out1).c_str());
         if (paired) INFO("Output file written to: %s", quoted(out2).c_str());
+    }
+    if (split) {
+        INFO("Human reads written to: %s", quoted(args.human_out1).c_str());
+        if (paired) INFO("Human reads written to: %s", quoted(args.human_out2).c_str());
     }
     if (!args.kraken_output.empty() && args.kraken_output != "/dev/null")
         INFO("Kraken output file written to: %s", quoted(args.kraken_output).c_str());
