@@ -311,6 +311,18 @@ int nh_run_engine(nh_engine *e, const nh_run_args *args, nh_stats *stats);
 int nh_run_split(const nh_run_args *args, const char *human_out1, const char *human_out2, nh_stats *stats);
 int nh_run_engine_split(nh_engine *e, const nh_run_args *args, const char *human_out1, const char *human_out2,
                         nh_stats *stats);
+/*
+ * Masked run: nh_run with keep_human = 0 in which no fragment is dropped.  out1 / out2 receive every record, in input
+ * order: an unclassified fragment's exactly as nh_run writes it, a classified fragment's (both mates) in the same form with
+ * every base of its sequence replaced by 'N' (length and qualities unchanged, no " kraken:taxid|" suffix).  kraken_output /
+ * report / stats exactly as one nh_run.  human_out1 (and, paired, human_out2) given: the classified records also go there
+ * exactly as nh_run_split writes them; NULL: no human outputs.  The masked text is built in the GPU's memory.  NH_EINVAL,
+ * before any device is touched: keep_human not 0; a human output that fails nh_run_split's checks; an output that names an
+ * input.
+ */
+int nh_run_mask(const nh_run_args *args, const char *human_out1, const char *human_out2, nh_stats *stats);
+int nh_run_engine_mask(nh_engine *e, const nh_run_args *args, const char *human_out1, const char *human_out2,
+                       nh_stats *stats);
 
 #ifdef __cplusplus
 }

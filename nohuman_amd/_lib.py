@@ -90,6 +90,8 @@ SYMBOLS = {
     "nh_run_engine": (C.c_int, [_P, C.POINTER(nh_run_args), C.POINTER(nh_stats)]),
     "nh_run_split": (C.c_int, [C.POINTER(nh_run_args), C.c_char_p, C.c_char_p, C.POINTER(nh_stats)]),
     "nh_run_engine_split": (C.c_int, [_P, C.POINTER(nh_run_args), C.c_char_p, C.c_char_p, C.POINTER(nh_stats)]),
+    "nh_run_mask": (C.c_int, [C.POINTER(nh_run_args), C.c_char_p, C.c_char_p, C.POINTER(nh_stats)]),
+    "nh_run_engine_mask": (C.c_int, [_P, C.POINTER(nh_run_args), C.c_char_p, C.c_char_p, C.POINTER(nh_stats)]),
     "nh_allreduce_counters": (C.c_int, [C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_uint64), C.c_char_p,
                                         C.c_size_t]),
 }

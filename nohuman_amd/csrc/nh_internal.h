@@ -143,6 +143,27 @@ struct HumanOutArgs {
 };
 uint64_t human_out_blocks(uint64_t n);
 hipError_t launch_human_out(const HumanOutArgs &a, hipStream_t stream);
+// The masked records of one batch built in HBM (nh_mask.hip; nh_run_mask's outputs): out[m] receives mate m's record of every
+// fragment, in order, the sequence of a classified fragment as 'N'; total[m] their bytes.
+struct MaskArgs {
+    const char *text;         // the batch's text (d_text), ntext bytes
+    uint64_t ntext;
+    const uint64_t *seq_off;  // n * mates sequence starts (absolute), as classified
+    const uint32_t *seq_len;  // n * mates sequence lengths
+    const uint32_t *rec;      // n * mates {header start (absolute), header length, qualities start (absolute), length}
+    const nh_result *res;     // n results
+    uint64_t n, nblk;         // nblk = mask_blocks(n)
+    int mates;
+    int fastq[2];             // per mate: FASTQ (else FASTA)
+    char *out[2];
+    uint64_t cap[2];          // bytes of out[m]
+    uint64_t *blk;            // 2 * nblk words of scratch
+    uint32_t *fast;           // 2 * nblk words of scratch
+    uint64_t *total;          // 2 words
+    int *error;               // the engine's sticky error word (bit 8: a record outside its text or buffer)
+};
+uint64_t mask_blocks(uint64_t n);
+hipError_t launch_mask(const MaskArgs &a, hipStream_t stream);
 // buffers kept between the runs of a process (nh_run.hip: page-locked batch text; nh_gunzip.hip: the gzip reader's HBM and
 // staging): emptied when an engine is closed
 void run_cache_trim();

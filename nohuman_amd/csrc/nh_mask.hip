@@ -1,0 +1,313 @@
+// nh_mask.hip -- the masked text of a batch, built in HBM (nh_run_mask: every read written, a human read's bases as 'N').
+//
+// For every fragment, in input order, each mate's output receives the record nh_run's put_record() writes without a suffix:
+//   FASTQ: header, "\n", sequence, "\n+\n", qualities, "\n"
+//   FASTA: header, "\n", sequence, "\n"
+// where the sequence is all 'N' (same length) when the fragment's call is not 0.  For a record already in that form in the
+// batch's text, the bytes are the same as the normal keep_human = 0 output (the raw text); for the others (CRLF, "+id",
+// trailing blanks, joined FASTA, no final newline) they are made from the parsed fields as the host's put_record() does.
+//
+// Four launches on the batch's stream, both mates in each (grid.y = mate):
+//   k_mask_sizes  per block of MB_FRAGS fragments: the sum of their output lengths, and whether the block is FAST: every
+//                 record already in output form in the text (the same test as nh_fastx.h's raw_end, made on the device from
+//                 the fields and a few bytes around them) and each record's text starting where the one before ends
+//   k_mask_scan   per mate, one workgroup: exclusive scan of the block sums in place -> block offsets; the mate's total
+//   k_mask_copy   MB_SUB workgroups per block.  FAST block: its text is one contiguous range, copied 16 bytes a lane (aligned
+//                 dwordx4 stores; the two partial chunks at the range's ends, shared with the neighbouring blocks, byte by
+//                 byte).  Other blocks: the lengths again, an exclusive scan inside the block, then one wave per record
+//                 writes it as aligned dwords (the split builder's scheme, nh_split.hip), the sequence of a classified
+//                 fragment as 'N' dwords
+//   k_mask_fill   FAST blocks only: 'N' over the sequence ranges of the classified fragments
+// The kernel boundaries are the only hand-off between the launches.  Every load stays inside the dwords that hold bytes of
+// [0, ntext); every store inside [0, cap) of its mate's buffer.  A record whose fields lie outside the text or a total above
+// the buffer sets bit 8 of the engine's error word and writes nothing.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "nh_internal.h"
+
+namespace nh {
+
+namespace {
+
+constexpr int MB_THREADS = 256;
+constexpr int MB_PER_THREAD = 4;
+constexpr int MB_FRAGS = MB_THREADS * MB_PER_THREAD;  // fragments of one block
+constexpr int MB_WAVES = MB_THREADS / 64;
+constexpr int MB_SUB = 4;  // workgroups of k_mask_copy / k_mask_fill per block
+constexpr int ERR_MASK = 8;
+constexpr uint32_t NNNN = 0x4E4E4E4Eu;
+
+typedef uint32_t u32x4a4 __attribute__((ext_vector_type(4), aligned(4)));
+
+struct MRec {  // one record's fields, absolute offsets into the batch's text
+    uint64_t h, s, q;
+    uint32_t hlen, slen, qlen;
+    bool cls;      // its fragment is classified: the sequence is written as 'N'
+    uint64_t len;  // bytes of its output, 0: nothing (no record, or a record that fails its bounds: error set)
+};
+
+__device__ inline MRec load_mrec(const MaskArgs &a, uint64_t f, int m, bool report) {
+    MRec r{};
+    if (f >= a.n) return r;
+    const uint64_t i = f * (uint64_t)a.mates + (uint64_t)m;
+    const uint4 fr = reinterpret_cast<const uint4 *>(a.rec)[i];
+    const bool fastq = a.fastq[m] != 0;
+    r.h = fr.x;
+    r.hlen = fr.y;
+    r.q = fr.z;
+    r.qlen = fastq ? fr.w : 0;
+    r.s = a.seq_off[i];
+    r.slen = a.seq_len[i];
+    r.cls = a.res[f].call != 0;
+    const bool ok = r.h + r.hlen <= a.ntext && (r.slen == 0 || r.s + r.slen <= a.ntext) && (r.qlen == 0 || r.q + r.qlen <= a.ntext);
+    if (!ok) {
+        if (report) atomicOr(a.error, ERR_MASK);
+        return r;
+    }
+    r.len = (uint64_t)r.hlen + 1 + r.slen + 1 + (fastq ? 3ull + r.qlen : 0ull);
+    return r;
+}
+
+// text[r.h, r.h + r.len) is byte for byte the record's output (nh_fastx.h raw_end): "header\nseq\n+\nquals\n" / "header\nseq\n"
+__device__ inline bool in_output_form(const MaskArgs &a, const MRec &r, bool fastq) {
+    if (r.len == 0 || r.h + r.len > a.ntext) return false;
+    const char *t = a.text;
+    if (t[r.h + r.hlen] != '\n' || r.s != r.h + r.hlen + 1 || t[r.s + r.slen] != '\n') return false;
+    if (!fastq) return true;
+    return t[r.s + r.slen + 1] == '+' && t[r.s + r.slen + 2] == '\n' && r.q == r.s + r.slen + 3 && t[r.q + r.qlen] == '\n';
+}
+
+// exclusive scan over the block's threads (MB_THREADS) of one value each; *total: the block's sum
+__device__ inline uint64_t block_exclusive_scan(uint64_t v, uint64_t *wsum, uint64_t *total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint64_t incl = v;
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t t = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += t;
+    }
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    uint64_t before = 0, all = 0;
+    for (int w = 0; w < MB_WAVES; w++) {
+        before += w < wave ? wsum[w] : 0;
+        all += wsum[w];
+    }
+    *total = all;
+    return before + incl - v;
+}
+
+__global__ void __launch_bounds__(MB_THREADS) k_mask_sizes(MaskArgs a) {
+    __shared__ uint64_t wsum[MB_WAVES];
+    const int m = blockIdx.y;
+    const bool fastq = a.fastq[m] != 0;
+    const uint64_t fb = (uint64_t)blockIdx.x * MB_FRAGS;
+    const uint64_t fend = fb + MB_FRAGS < a.n ? fb + MB_FRAGS : a.n;
+    const uint64_t f0 = fb + (uint64_t)threadIdx.x * MB_PER_THREAD;
+    uint64_t mine = 0;
+    bool fast = true;
+    for (int j = 0; j < MB_PER_THREAD; j++) {
+        const uint64_t f = f0 + j;
+        const MRec r = load_mrec(a, f, m, true);
+        mine += r.len;
+        if (f >= a.n) continue;
+        fast = fast && in_output_form(a, r, fastq);
+        if (fast && f + 1 < fend)  // the next record of the block starts where this one ends
+            fast = reinterpret_cast<const uint4 *>(a.rec)[(f + 1) * (uint64_t)a.mates + (uint64_t)m].x == r.h + r.len;
+    }
+    uint64_t total;
+    (void)block_exclusive_scan(mine, wsum, &total);
+    const int all_fast = __syncthreads_and(fast ? 1 : 0);
+    if (threadIdx.x == 0) {
+        a.blk[(uint64_t)m * a.nblk + blockIdx.x] = total;
+        a.fast[(uint64_t)m * a.nblk + blockIdx.x] = all_fast ? 1u : 0u;
+    }
+}
+
+// one workgroup per mate: block sums -> exclusive block offsets (in place), the mate's total
+__global__ void __launch_bounds__(MB_THREADS) k_mask_scan(MaskArgs a) {
+    __shared__ uint64_t wsum[MB_WAVES];
+    const int m = blockIdx.x;
+    uint64_t *b = a.blk + (uint64_t)m * a.nblk;
+    uint64_t carry = 0;
+    for (uint64_t c = 0; c < a.nblk; c += MB_THREADS) {
+        const uint64_t i = c + threadIdx.x;
+        const uint64_t v = i < a.nblk ? b[i] : 0;
+        uint64_t sum;
+        const uint64_t ex = block_exclusive_scan(v, wsum, &sum);
+        if (i < a.nblk) b[i] = carry + ex;
+        carry += sum;
+        __syncthreads();  // (wsum is written again by the next chunk)
+    }
+    if (threadIdx.x == 0) {
+        if (carry > a.cap[m]) {
+            atomicOr(a.error, ERR_MASK);
+            carry = 0;
+        }
+        a.total[m] = carry;
+    }
+}
+
+// byte p of the record's masked output (0 <= p < r.len)
+__device__ inline uint8_t mrec_byte(const MaskArgs &a, const MRec &r, bool fastq, uint64_t p) {
+    if (p < r.hlen) return (uint8_t)a.text[r.h + p];
+    p -= r.hlen;
+    if (p == 0) return '\n';
+    p -= 1;
+    if (p < r.slen) return r.cls ? (uint8_t)'N' : (uint8_t)a.text[r.s + p];
+    p -= r.slen;
+    if (!fastq) return '\n';
+    if (p < 3) return p == 1 ? '+' : '\n';
+    p -= 3;
+    if (p < r.qlen) return (uint8_t)a.text[r.q + p];
+    return '\n';
+}
+
+// the 4 text bytes at src (src + 3 < ntext): two aligned loads, the second only where the bytes reach into it
+__device__ inline uint32_t text_dword(const char *text, uint64_t src) {
+    const uint32_t *w = reinterpret_cast<const uint32_t *>(text + (src & ~3ull));
+    const uint32_t sh = (uint32_t)(src & 3);
+    const uint32_t lo = w[0];
+    if (sh == 0) return lo;
+    return __builtin_amdgcn_alignbyte(w[1], lo, sh);
+}
+
+// the 16 text bytes at src (src + 15 < ntext): four aligned dwords, a fifth only where the bytes reach into it
+__device__ inline uint4 text_x4(const char *text, uint64_t src) {
+    const uint64_t A = src & ~3ull;
+    const uint32_t sh = (uint32_t)(src & 3);
+    const u32x4a4 v = *reinterpret_cast<const u32x4a4 *>(text + A);
+    if (sh == 0) return make_uint4(v.x, v.y, v.z, v.w);
+    const uint32_t e = *reinterpret_cast<const uint32_t *>(text + A + 16);
+    return make_uint4(__builtin_amdgcn_alignbyte(v.y, v.x, sh), __builtin_amdgcn_alignbyte(v.z, v.y, sh),
+                      __builtin_amdgcn_alignbyte(v.w, v.z, sh), __builtin_amdgcn_alignbyte(e, v.w, sh));
+}
+
+// a FAST block: its records' text is [h0, h0 + L), written at out[base, base + L); false (error set): outside text or buffer
+__device__ inline bool fast_range(const MaskArgs &a, int m, uint64_t fb, uint64_t base, uint64_t *h0, uint64_t *L, bool report) {
+    const uint64_t last = (fb + MB_FRAGS < a.n ? fb + MB_FRAGS : a.n) - 1;
+    const MRec r0 = load_mrec(a, fb, m, false), r1 = load_mrec(a, last, m, false);
+    *h0 = r0.h;
+    *L = r1.h + r1.len - r0.h;
+    const bool ok = r0.len && r1.len && r1.h >= r0.h && r1.h + r1.len <= a.ntext && base + *L <= a.cap[m];
+    if (!ok && report) atomicOr(a.error, ERR_MASK);
+    return ok;
+}
+
+__global__ void __launch_bounds__(MB_THREADS) k_mask_copy(MaskArgs a) {
+    __shared__ uint64_t wsum[MB_WAVES];
+    __shared__ uint64_t s_off[MB_FRAGS];
+    const int m = blockIdx.y;
+    const uint64_t blk = blockIdx.x / MB_SUB;
+    const int u = blockIdx.x % MB_SUB;
+    const bool fastq = a.fastq[m] != 0;
+    const uint64_t fb = blk * MB_FRAGS;
+    char *out = a.out[m];
+    const uint64_t cap = a.cap[m];
+    const uint64_t base = a.blk[(uint64_t)m * a.nblk + blk];
+    if (a.fast[(uint64_t)m * a.nblk + blk]) {
+        uint64_t h0, L;
+        if (!fast_range(a, m, fb, base, &h0, &L, u == 0 && threadIdx.x == 0)) return;
+        const uint64_t end = base + L;
+        const uint64_t step = 16ull * MB_THREADS * MB_SUB;
+        for (uint64_t D = (base & ~15ull) + 16ull * ((uint64_t)u * MB_THREADS + threadIdx.x); D < end; D += step) {
+            if (D >= base && D + 16 <= end) {
+                *reinterpret_cast<uint4 *>(out + D) = text_x4(a.text, h0 + (D - base));
+            } else {  // the range's first or last chunk: the neighbouring blocks own the other bytes
+                for (uint64_t x = D; x < D + 16; x++)
+                    if (x >= base && x < end) out[x] = a.text[h0 + (x - base)];
+            }
+        }
+        return;
+    }
+    {
+        uint64_t len[MB_PER_THREAD], mine = 0;
+        for (int j = 0; j < MB_PER_THREAD; j++) {
+            len[j] = load_mrec(a, fb + threadIdx.x * MB_PER_THREAD + j, m, false).len;
+            mine += len[j];
+        }
+        uint64_t total;
+        uint64_t o = block_exclusive_scan(mine, wsum, &total);
+        for (int j = 0; j < MB_PER_THREAD; j++) {
+            s_off[threadIdx.x * MB_PER_THREAD + j] = o;
+            o += len[j];
+        }
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int gw = u * MB_WAVES + (threadIdx.x >> 6);
+    // wave gw of the block's MB_SUB * MB_WAVES writes the records gw, gw + MB_SUB * MB_WAVES, ... one after another
+    for (int fl = gw; fl < MB_FRAGS; fl += MB_SUB * MB_WAVES) {
+        const MRec r = load_mrec(a, fb + fl, m, false);
+        if (r.len == 0) continue;
+        const uint64_t o = base + s_off[fl];
+        if (o + r.len > cap) {  // (the scan found the total too large: nothing is written)
+            if (lane == 0) atomicOr(a.error, ERR_MASK);
+            continue;
+        }
+        const uint64_t pB = (uint64_t)r.hlen + 1, pC = pB + r.slen + 3;
+        const uint64_t end = o + r.len;
+        for (uint64_t D = (o & ~3ull) + 4ull * lane; D < end; D += 256) {
+            if (D >= o && D + 4 <= end) {
+                const uint64_t p = D - o;
+                uint32_t v;
+                if (p + 4 <= r.hlen) v = text_dword(a.text, r.h + p);
+                else if (p >= pB && p + 4 <= pB + r.slen) v = r.cls ? NNNN : text_dword(a.text, r.s + (p - pB));
+                else if (fastq && p >= pC && p + 4 <= pC + r.qlen) v = text_dword(a.text, r.q + (p - pC));
+                else
+                    v = (uint32_t)mrec_byte(a, r, fastq, p) | (uint32_t)mrec_byte(a, r, fastq, p + 1) << 8 |
+                        (uint32_t)mrec_byte(a, r, fastq, p + 2) << 16 | (uint32_t)mrec_byte(a, r, fastq, p + 3) << 24;
+                *reinterpret_cast<uint32_t *>(out + D) = v;
+            } else {  // the record's first or last dword: its neighbours own the other bytes
+                for (uint64_t x = D; x < D + 4; x++)
+                    if (x >= o && x < end) out[x] = (char)mrec_byte(a, r, fastq, x - o);
+            }
+        }
+    }
+}
+
+// FAST blocks: the copy wrote the raw text; 'N' over the sequences of the classified fragments
+__global__ void __launch_bounds__(MB_THREADS) k_mask_fill(MaskArgs a) {
+    const int m = blockIdx.y;
+    const uint64_t blk = blockIdx.x / MB_SUB;
+    const int u = blockIdx.x % MB_SUB;
+    if (!a.fast[(uint64_t)m * a.nblk + blk]) return;
+    const uint64_t fb = blk * MB_FRAGS;
+    const uint64_t base = a.blk[(uint64_t)m * a.nblk + blk];
+    uint64_t h0, L;
+    if (!fast_range(a, m, fb, base, &h0, &L, false)) return;  // (the copy reported it and wrote nothing)
+    char *out = a.out[m];
+    const int lane = threadIdx.x & 63;
+    const int gw = u * MB_WAVES + (threadIdx.x >> 6);
+    for (int fl = gw; fl < MB_FRAGS; fl += MB_SUB * MB_WAVES) {
+        const uint64_t f = fb + fl;
+        if (f >= a.n || a.res[f].call == 0) continue;
+        const MRec r = load_mrec(a, f, m, false);
+        if (r.len == 0 || r.slen == 0 || r.h < h0 || r.h + r.len > h0 + L) continue;
+        const uint64_t o = base + (r.h - h0) + r.hlen + 1, end = o + r.slen;
+        for (uint64_t D = (o & ~3ull) + 4ull * lane; D < end; D += 256) {
+            if (D >= o && D + 4 <= end) {
+                *reinterpret_cast<uint32_t *>(out + D) = NNNN;
+            } else {  // the sequence's first or last dword: the header's or the separator's bytes stay
+                for (uint64_t x = D; x < D + 4; x++)
+                    if (x >= o && x < end) out[x] = 'N';
+            }
+        }
+    }
+}
+
+}  // namespace
+
+uint64_t mask_blocks(uint64_t n) { return (n + MB_FRAGS - 1) / MB_FRAGS; }
+
+hipError_t launch_mask(const MaskArgs &a, hipStream_t stream) {
+    if (a.n == 0) return hipMemsetAsync(a.total, 0, 2 * sizeof(uint64_t), stream);
+    const dim3 grid((unsigned)a.nblk, (unsigned)a.mates), sub((unsigned)(a.nblk * MB_SUB), (unsigned)a.mates);
+    hipLaunchKernelGGL(k_mask_sizes, grid, dim3(MB_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(k_mask_scan, dim3((unsigned)a.mates), dim3(MB_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(k_mask_copy, sub, dim3(MB_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(k_mask_fill, sub, dim3(MB_THREADS), 0, stream, a);
+    return hipGetLastError();
+}
+
+}  // namespace nh

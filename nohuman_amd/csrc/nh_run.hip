@@ -347,8 +347,14 @@ struct Slot {  // pinned host + device buffers of one in-flight batch
     void *d_rec = nullptr, *d_hblk = nullptr;
     char *d_hout[2] = {nullptr, nullptr}, *h_hout[2] = {nullptr, nullptr};
     size_t cap_hout[2] = {0, 0}, cap_hhost[2] = {0, 0}, cap_rec = 0, cap_hblk = 0;
-    uint64_t *h_htotal = nullptr;
+    uint64_t *h_htotal = nullptr;  // [0..1]: the classified-out totals, [2..3]: the masked totals
     hipEvent_t hev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around the builder's launches (its kernel time)
+    // masked runs (nh_run_mask): every record of each mate built in HBM (the same record table as split runs), the builder's
+    // scratch, and the host copies where an encoder cannot take the HBM range
+    void *d_mblk = nullptr;
+    char *d_mout[2] = {nullptr, nullptr}, *h_mout[2] = {nullptr, nullptr};
+    size_t cap_mout[2] = {0, 0}, cap_mhost[2] = {0, 0}, cap_mblk = 0;
+    hipEvent_t mev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around the mask builder's launches
 };
 
 static int slot_reserve(Slot &s, size_t ntext, size_t nfrag, size_t ntaxa) {
@@ -420,6 +426,47 @@ static int slot_reserve_human(Slot &s, size_t n, int mates, const size_t out_cap
     return NH_OK;
 }
 
+// the masked run's buffers of a slot: records of n fragments (mates per fragment), out_cap[m] bytes of masked text
+static int slot_reserve_mask(Slot &s, size_t n, int mates, const size_t out_cap[2]) {
+    auto grow = [](size_t need) { return need + need / 4 + 4096; };
+    if (!s.h_htotal && host_malloc((void **)&s.h_htotal, 64, hipHostMallocDefault) != hipSuccess)
+        return set_error(NH_EOOM, "cannot allocate batch buffers");
+    if (n * mates > s.cap_rec) {
+        if (s.h_rec) (void)hipHostFree(s.h_rec);
+        if (s.d_rec) (void)hipFree(s.d_rec);
+        s.h_rec = nullptr, s.d_rec = nullptr;
+        s.cap_rec = grow(n * mates);
+        if (host_malloc((void **)&s.h_rec, s.cap_rec * 16, hipHostMallocDefault) != hipSuccess || dev_malloc(&s.d_rec, s.cap_rec * 16) != hipSuccess)
+            return set_error(NH_EOOM, "cannot allocate batch buffers (%zu records)", s.cap_rec);
+    }
+    const size_t words = 3 * mask_blocks(n) + 2;  // (block offsets, totals, block flags: MaskArgs)
+    if (words > s.cap_mblk) {
+        if (s.d_mblk) (void)hipFree(s.d_mblk);
+        s.cap_mblk = grow(words);
+        if (dev_malloc(&s.d_mblk, s.cap_mblk * 8) != hipSuccess) return set_error(NH_EOOM, "cannot allocate batch buffers");
+    }
+    for (int m = 0; m < mates; m++)
+        if (out_cap[m] > s.cap_mout[m]) {
+            if (s.d_mout[m]) (void)hipFree(s.d_mout[m]);
+            s.cap_mout[m] = grow(out_cap[m]);
+            if (dev_malloc((void **)&s.d_mout[m], s.cap_mout[m]) != hipSuccess)
+                return set_error(NH_EOOM, "cannot allocate masked-out buffers (%zu bytes)", s.cap_mout[m]);
+        }
+    return NH_OK;
+}
+
+// page-locked room for `n` bytes of mate m's masked text on the host (the writer's copy for host encoders)
+static int slot_reserve_mask_host(Slot &s, int m, size_t n) {
+    if (n <= s.cap_mhost[m]) return NH_OK;
+    if (s.h_mout[m]) (void)hipHostFree(s.h_mout[m]);
+    s.cap_mhost[m] = n + n / 4 + 4096;
+    if (host_malloc((void **)&s.h_mout[m], s.cap_mhost[m], hipHostMallocDefault) != hipSuccess) {
+        s.h_mout[m] = nullptr, s.cap_mhost[m] = 0;
+        return set_error(NH_EOOM, "cannot allocate masked-out buffers (%zu bytes)", n);
+    }
+    return NH_OK;
+}
+
 // page-locked room for `n` bytes of mate m's classified-out text on the host (the writer's copy for host encoders)
 static int slot_reserve_human_host(Slot &s, int m, size_t n) {
     if (n <= s.cap_hhost[m]) return NH_OK;
@@ -435,11 +482,11 @@ static int slot_reserve_human_host(Slot &s, int m, size_t n) {
 static void slot_free(Slot &s) {
     if (!s.e) return;
     (void)dev_set(s.e->device);
-    for (void *p : {(void *)s.h_rec, (void *)s.h_hout[0], (void *)s.h_hout[1], (void *)s.h_htotal})
+    for (void *p : {(void *)s.h_rec, (void *)s.h_hout[0], (void *)s.h_hout[1], (void *)s.h_htotal, (void *)s.h_mout[0], (void *)s.h_mout[1]})
         if (p) (void)hipHostFree(p);
-    for (void *p : {s.d_rec, s.d_hblk, (void *)s.d_hout[0], (void *)s.d_hout[1]})
+    for (void *p : {s.d_rec, s.d_hblk, (void *)s.d_hout[0], (void *)s.d_hout[1], s.d_mblk, (void *)s.d_mout[0], (void *)s.d_mout[1]})
         if (p) (void)hipFree(p);
-    for (hipEvent_t ev : s.hev)
+    for (hipEvent_t ev : {s.hev[0], s.hev[1], s.mev[0], s.mev[1]})
         if (ev) (void)hipEventDestroy(ev);
     for (void *p : {(void *)s.h_off, (void *)s.h_len, (void *)s.h_res, (void *)s.h_taxa, (void *)s.h_taxa_off, (void *)s.h_flag})
         if (p) (void)hipHostFree(p);
@@ -525,6 +572,9 @@ struct RunState {
     // the host -- classified-out text for host encoders, and batches of the reader on the GPU fetched for the other side
     uint64_t human_records = 0, human_bytes = 0;
     double human_kernel_ms = 0;  // NOHUMAN_TRACE: the builder's launches, by events on the slots' streams
+    // masked runs (NOHUMAN_TRACE): records masked and written, the bytes the mask builder made, its kernel time
+    uint64_t mask_masked = 0, mask_records = 0, mask_bytes = 0;
+    double mask_kernel_ms = 0;
     std::atomic<uint64_t> text_fetched{0};
     std::vector<uint64_t> dev_counts;  // per device {fragments, classified, bases, 0} as the writer saw them (checker)
     std::vector<uint64_t *> d_run_counters;  // per device: the counters the classify kernels of THIS run add to (HBM)
@@ -778,7 +828,8 @@ static inline void put_record(std::string &dst, const char *text, int format, co
 
 // decide + format one finished batch into the span lists of the output files (runs on the writer
 // thread, batches arrive in input order)
-static void format_batch(RunState *rs, const Batch &b, const Slot &s, OutFile &o1, OutFile &o2, OutFile &ok) {
+// (emit false: a masked run -- its records are built on the device, only the counts and the -k lines are made here)
+static void format_batch(RunState *rs, const Batch &b, const Slot &s, OutFile &o1, OutFile &o2, OutFile &ok, bool emit = true) {
     const nh_run_args *a = rs->a;
     const Engine *e = s.e;
     const bool keep_class = a->keep_human != 0;
@@ -795,7 +846,7 @@ static void format_batch(RunState *rs, const Batch &b, const Slot &s, OutFile &o
         classified += is_class;
         rs->call_counts[call] += is_class;
         bases += r1.slen + (rs->paired ? R2[i].slen : 0);
-        if (is_class == keep_class) {
+        if (emit && is_class == keep_class) {
             if (!is_class && r1.raw_end) {
                 o1.add_raw(t1 + r1.h, r1.raw_end - r1.h);
             } else {
@@ -864,13 +915,13 @@ static int ensure_device_external(Engine *e) {
 }
 
 // nh_run_split's own arguments, checked before any device is touched
-static int check_split_args(const nh_run_args *a, const char *h1, const char *h2) {
-    if (!a) return set_error(NH_EINVAL, "nh_run_split: null arguments");
-    if (!h1 || !h1[0]) return set_error(NH_EINVAL, "nh_run_split: human_out1 is required");
-    if (a->keep_human != 0) return set_error(NH_EINVAL, "nh_run_split: keep_human must be 0 (the human reads go to human_out1 / human_out2)");
-    if (a->in2 && !h2) return set_error(NH_EINVAL, "nh_run_split: paired input needs human_out2");
-    if (!a->in2 && h2) return set_error(NH_EINVAL, "nh_run_split: human_out2 is given without in2");
-    if (h2 && !strcmp(h1, h2)) return set_error(NH_EINVAL, "nh_run_split: human_out1 and human_out2 are the same file");
+static int check_split_args(const nh_run_args *a, const char *h1, const char *h2, const char *who = "nh_run_split") {
+    if (!a) return set_error(NH_EINVAL, "%s: null arguments", who);
+    if (!h1 || !h1[0]) return set_error(NH_EINVAL, "%s: human_out1 is required", who);
+    if (a->keep_human != 0) return set_error(NH_EINVAL, "%s: keep_human must be 0 (the human reads go to human_out1 / human_out2)", who);
+    if (a->in2 && !h2) return set_error(NH_EINVAL, "%s: paired input needs human_out2", who);
+    if (!a->in2 && h2) return set_error(NH_EINVAL, "%s: human_out2 is given without in2", who);
+    if (h2 && !strcmp(h1, h2)) return set_error(NH_EINVAL, "%s: human_out1 and human_out2 are the same file", who);
     for (const char *h : {h1, h2}) {
         if (!h) continue;
         struct stat sh;
@@ -878,25 +929,51 @@ static int check_split_args(const nh_run_args *a, const char *h1, const char *h2
         for (const char *p : {a->in1, a->in2}) {
             struct stat si;
             if (p && (!strcmp(p, h) || (hs && stat(p, &si) == 0 && si.st_dev == sh.st_dev && si.st_ino == sh.st_ino)))
-                return set_error(NH_EINVAL, "nh_run_split: human output %s is the input %s", h, p);
+                return set_error(NH_EINVAL, "%s: human output %s is the input %s", who, h, p);
         }
         for (const char *o : {a->out1, a->out2, a->kraken_output, a->report}) {
             struct stat so;
             if (o && o[0] && (!strcmp(o, h) || (hs && stat(o, &so) == 0 && so.st_dev == sh.st_dev && so.st_ino == sh.st_ino)))
-                return set_error(NH_EINVAL, "nh_run_split: human output %s is also the output %s", h, o);
+                return set_error(NH_EINVAL, "%s: human output %s is also the output %s", who, h, o);
+        }
+    }
+    return NH_OK;
+}
+
+// nh_run_mask's own arguments, checked before any device is touched
+static int check_mask_args(const nh_run_args *a, const char *h1, const char *h2) {
+    if (!a) return set_error(NH_EINVAL, "nh_run_mask: null arguments");
+    if (a->keep_human != 0) return set_error(NH_EINVAL, "nh_run_mask: keep_human must be 0 (the human reads are masked, not kept)");
+    if (h1 || h2) {
+        const int rc = check_split_args(a, h1, h2, "nh_run_mask");
+        if (rc) return rc;
+    }
+    for (const char *o : {a->out1, a->out2, a->kraken_output, a->report}) {
+        if (!o || !o[0]) continue;
+        struct stat so;
+        const bool oreg = stat(o, &so) == 0 && S_ISREG(so.st_mode);
+        for (const char *p : {a->in1, a->in2}) {
+            struct stat si;
+            if (p && (!strcmp(p, o) || (oreg && stat(p, &si) == 0 && si.st_dev == so.st_dev && si.st_ino == so.st_ino)))
+                return set_error(NH_EINVAL, "nh_run_mask: output %s is the input %s", o, p);
         }
     }
     return NH_OK;
 }
 
 // hout1 set: a split run (nh_run_split) -- a->keep_human is 0, hout1 / hout2 receive the classified records
+// mask: a masked run (nh_run_mask) -- a->keep_human is 0, out1 / out2 receive every record, a classified one's bases as 'N'
 int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_stats *stats, const char *hout1 = nullptr,
-                const char *hout2 = nullptr) {
+                const char *hout2 = nullptr, bool mask = false) {
     if (!a || !a->in1 || !a->out1) return set_error(NH_EINVAL, "nh_run: in1 and out1 are required");
     if (engines.empty()) return set_error(NH_EINVAL, "nh_run: no engine");
     const bool split = hout1 != nullptr;
+    if (mask) {
+        const int vrc = check_mask_args(a, hout1, hout2);
+        if (vrc) return vrc;
+    }
     if (split) {
-        const int vrc = check_split_args(a, hout1, hout2);
+        const int vrc = check_split_args(a, hout1, hout2, mask ? "nh_run_mask" : "nh_run_split");
         if (vrc) return vrc;
         for (Engine *e : engines) {
             const int erc = ensure_device_external(e);
@@ -991,14 +1068,19 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
     // Batches of the reader on the GPU keep their text in HBM.  The host needs the bytes for plain outputs and the host's
     // codecs, for the ids of --output lines and for the suffix of classified-out headers; gzip outputs encoded on the GPU
     // take the kept records from HBM (a record that needs reformatting -- CRLF, "+id" -- makes the writer fetch its batch).
-    const bool host_text_wanted = !(a->out_codec == NH_CODEC_GZIP && o1.enc && o1.enc->takes_device_spans() &&
-                                    (!rs.paired || (o2.enc && o2.enc->takes_device_spans()))) ||
-                                  rs.want_k || a->keep_human != 0 || G > 1;  // (G > 1: a batch's slot and its file's encoder may sit on different GPUs)
+    // A masked run builds every output record on the device (the split side as well): only --output lines need the bytes.
+    const bool host_text_wanted = mask ? rs.want_k || G > 1
+                                       : !(a->out_codec == NH_CODEC_GZIP && o1.enc && o1.enc->takes_device_spans() &&
+                                           (!rs.paired || (o2.enc && o2.enc->takes_device_spans()))) ||
+                                             rs.want_k || a->keep_human != 0 || G > 1;  // (G > 1: a batch's slot and its file's encoder may sit on different GPUs)
     const uint32_t flags = rs.paired ? NH_FLAG_PAIRED : 0;
     // split runs: the classified-out text is built in HBM; an encoder on the slot's GPU takes it from there, any other output
     // gets exactly the built bytes copied to the host (G > 1: a batch's slot and its file's encoder may sit on different GPUs)
     const bool human_in_hbm = split && G == 1 && h1.enc && h1.enc->takes_device_spans() &&
                               (!rs.paired || (h2.enc && h2.enc->takes_device_spans()));
+    // masked runs: the same for out1 / out2 -- one span a mate and batch, from HBM or copied to page-locked slot memory
+    const bool mask_in_hbm = mask && G == 1 && o1.enc && o1.enc->takes_device_spans() &&
+                             (!rs.paired || (o2.enc && o2.enc->takes_device_spans()));
     auto t0 = std::chrono::steady_clock::now();
 
     rs.d_run_counters.assign((size_t)G, nullptr);
@@ -1030,7 +1112,9 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
         if (dev_set(slots[i].e->device) != hipSuccess ||
             hipStreamCreateWithFlags(&slots[i].stream, hipStreamNonBlocking) != hipSuccess ||
             (split && getenv("NOHUMAN_TRACE") &&
-             (hipEventCreate(&slots[i].hev[0]) != hipSuccess || hipEventCreate(&slots[i].hev[1]) != hipSuccess))) {
+             (hipEventCreate(&slots[i].hev[0]) != hipSuccess || hipEventCreate(&slots[i].hev[1]) != hipSuccess)) ||
+            (mask && getenv("NOHUMAN_TRACE") &&
+             (hipEventCreate(&slots[i].mev[0]) != hipSuccess || hipEventCreate(&slots[i].mev[1]) != hipSuccess))) {
             for (auto &s : slots) slot_free(s);
             free_run_counters();
             return set_error(NH_EDEVICE, "cannot create streams");
@@ -1066,8 +1150,11 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
         const bool named = how && !strcmp(how, "device");
         const bool by_host = a->keep_human == 0 && !(a->out_codec == NH_CODEC_GZIP && o1.enc && o1.enc->takes_device_spans() &&
                                                      (!rs.paired || (o2.enc && o2.enc->takes_device_spans())));
-        dev_reader1 = !off && dev_gunzip_wants(a->in1) && (named || device_reader_pays(a->in1, mean_rec, host_text_wanted, by_host));
-        dev_reader2 = rs.paired && !off && dev_gunzip_wants(a->in2) && (named || device_reader_pays(a->in2, mean_rec, host_text_wanted, by_host));
+        // (a masked run whose outputs are written by the host: every byte leaves through it, as the kept reads of a normal run
+        // do -- the same choice; with GPU gzip outputs nothing does and the reader on the GPU is taken, profiles/mask_e2e.txt)
+        const bool text_to_host = host_text_wanted || (mask && !mask_in_hbm);
+        dev_reader1 = !off && dev_gunzip_wants(a->in1) && (named || device_reader_pays(a->in1, mean_rec, text_to_host, by_host));
+        dev_reader2 = rs.paired && !off && dev_gunzip_wants(a->in2) && (named || device_reader_pays(a->in2, mean_rec, text_to_host, by_host));
         if (rs.paired && !named && dev_reader1 != dev_reader2 && dev_gunzip_wants(a->in1) && dev_gunzip_wants(a->in2)) dev_reader1 = dev_reader2 = false;
         // "split": the two mate files on the two KINDS of reader at once -- file 1 inflated and indexed on the GPU, file 2 by all
         // the host's inflate workers (round 6: the GPU's codec kernels and the host's cores idle in turn otherwise)
@@ -1173,9 +1260,15 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 // the batch's raw text is still in the slot's device buffer: an encoder on that GPU takes
                 // the kept records from there instead of a second trip over PCIe
                 // (a part that fetched its own host copy has its spans there: they are staged like any host memory)
-                if (o1.enc) o1.enc->map_device(b.h1->text.data(), b.len1, s.d_text, s.e->device, b.h1->host_text_valid);
-                if (rs.paired && o2.enc)
+                // (a masked run's spans are the built text: in HBM, mapped here, or in the slot's page-locked copy)
+                if (o1.enc && !mask) o1.enc->map_device(b.h1->text.data(), b.len1, s.d_text, s.e->device, b.h1->host_text_valid);
+                if (rs.paired && o2.enc && !mask)
                     o2.enc->map_device(b.h2->text.data(), b.len2, (const char *)s.d_text + base2w, s.e->device, b.h2->host_text_valid);
+                if (mask_in_hbm)
+                    for (int m = 0; m < mates; m++) {
+                        Spans &ms = m ? j->s2 : j->s1;
+                        if (!ms.iov.empty()) (m ? o2 : o1).enc->map_device(ms.iov[0].iov_base, ms.iov[0].iov_len, s.d_mout[m], s.e->device, false);
+                    }
                 // the classified records that only exist in HBM: their span's address is the device buffer's, never read on the host
                 if (human_in_hbm)
                     for (int m = 0; m < mates; m++) {
@@ -1234,7 +1327,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                     // a batch whose text is only in HBM, and a kept record that must be rewritten (CRLF, "+id" line): fetch it
                     // (into a buffer of this part: the half itself may be in use by other parts -- Batch)
                     auto need_fetch = [&](const HalfBatch &hb) {
-                        if (hb.host_text_valid) return false;
+                        if (hb.host_text_valid || mask) return false;
                         const size_t off = &hb == b.h1.get() ? b.off1 : b.off2;
                         for (size_t i = 0; i < b.n; i++)
                             if (!hb.recs[off + i].raw_end && (s.h_res[i].call != 0) == (a->keep_human != 0)) return true;
@@ -1254,7 +1347,30 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                     }
                 }
                 if (!wrc) {
-                    format_batch(&rs, b, s, o1, o2, ok);
+                    format_batch(&rs, b, s, o1, o2, ok, !mask);
+                    // a masked run's records: the text the builder made, one span a mate -- in HBM, or copied here
+                    if (mask && s.mev[1]) {
+                        float ms = 0;
+                        if (hipEventElapsedTime(&ms, s.mev[0], s.mev[1]) == hipSuccess) rs.mask_kernel_ms += ms;
+                    }
+                    for (int m = 0; mask && m < mates && !wrc; m++) {
+                        const size_t tot = (size_t)s.h_htotal[2 + m];
+                        rs.mask_bytes += tot;
+                        if (!tot) continue;
+                        char *at = s.d_mout[m];
+                        if (!mask_in_hbm) {
+                            wrc = slot_reserve_mask_host(s, m, tot);
+                            if (!wrc && hipMemcpy(s.h_mout[m], s.d_mout[m], tot, hipMemcpyDeviceToHost) != hipSuccess)
+                                wrc = set_error(NH_EDEVICE, "fetching a batch's masked records from the device failed");
+                            at = s.h_mout[m];
+                            rs.text_fetched += tot;
+                        }
+                        (m ? o2 : o1).add_raw(at, tot);
+                    }
+                    if (mask) {
+                        rs.mask_records += b.n * (size_t)mates;
+                        for (size_t i = 0; i < b.n; i++) rs.mask_masked += (s.h_res[i].call != 0) * (uint64_t)mates;
+                    }
                     // a split run's classified records: the text the builder made, one span a mate -- in HBM, or copied here
                     if (split && s.hev[1]) {  // (the stream was synchronised above: both events have completed)
                         float ms = 0;
@@ -1396,6 +1512,10 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 const size_t out_cap[2] = {len1 + b.n * 36 + 64, len2 + b.n * 36 + 64};
                 rc = slot_reserve_human(s, b.n, mates, out_cap);
             }
+            if (!rc && mask) {  // a mate's masked text: its records less what normalisation drops, plus a final newline each
+                const size_t out_cap[2] = {len1 + b.n + 64, len2 + b.n + 64};
+                rc = slot_reserve_mask(s, b.n, mates, out_cap);
+            }
             if (rc) {
                 rs.fail(rc, g_last_error);
                 wq.push(std::move(b));
@@ -1408,7 +1528,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 s.h_off[i * mates] = r1.s;
                 s.h_len[i * mates] = r1.slen;
                 nbases += r1.slen;
-                if (split) {
+                if (split || mask) {
                     uint32_t *hr = s.h_rec + 4 * i * mates;
                     hr[0] = r1.h, hr[1] = r1.hlen, hr[2] = r1.q, hr[3] = r1.qlen;
                     if (rs.paired) {
@@ -1462,7 +1582,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 he = hipMemcpyAsync(s.d_len, s.h_len, b.n * mates * 4, hipMemcpyHostToDevice, s.stream);
             if (he == hipSuccess && rs.want_k)
                 he = hipMemcpyAsync(s.d_taxa_off, s.h_taxa_off, (b.n + 1) * 8, hipMemcpyHostToDevice, s.stream);
-            if (he == hipSuccess && split)
+            if (he == hipSuccess && (split || mask))
                 he = hipMemcpyAsync(s.d_rec, s.h_rec, b.n * mates * 16, hipMemcpyHostToDevice, s.stream);
             if (he != hipSuccess) {
                 rs.fail(NH_EDEVICE, std::string("H2D: ") + hipGetErrorString(he));
@@ -1498,6 +1618,30 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 if (s.hev[1] && he == hipSuccess) he = hipEventRecord(s.hev[1], s.stream);
                 if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("classified-out builder: ") + hipGetErrorString(he));
             }
+            uint64_t *d_mtotal = nullptr;
+            if (!rs.failed() && mask) {  // every record of both mates, masked, built behind the classifier on the same stream
+                MaskArgs ma{};
+                ma.text = (const char *)s.d_text;
+                ma.ntext = ntext;
+                ma.seq_off = (const uint64_t *)s.d_off;
+                ma.seq_len = (const uint32_t *)s.d_len;
+                ma.rec = (const uint32_t *)s.d_rec;
+                ma.res = (const nh_result *)s.d_res;
+                ma.n = b.n;
+                ma.nblk = mask_blocks(b.n);
+                ma.mates = mates;
+                ma.fastq[0] = b.h1->format == FMT_FASTQ;
+                ma.fastq[1] = rs.paired && b.h2->format == FMT_FASTQ;
+                for (int m = 0; m < mates; m++) ma.out[m] = s.d_mout[m], ma.cap[m] = s.cap_mout[m];
+                ma.blk = (uint64_t *)s.d_mblk;
+                ma.total = d_mtotal = (uint64_t *)s.d_mblk + 2 * ma.nblk;
+                ma.fast = (uint32_t *)((uint64_t *)s.d_mblk + 2 * ma.nblk + 2);
+                ma.error = s.e->d_error + LAUNCH_SLOTS;
+                if (s.mev[0]) (void)hipEventRecord(s.mev[0], s.stream);
+                he = launch_mask(ma, s.stream);
+                if (s.mev[1] && he == hipSuccess) he = hipEventRecord(s.mev[1], s.stream);
+                if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("mask builder: ") + hipGetErrorString(he));
+            }
             if (!rs.failed()) {
                 he = hipMemcpyAsync(s.h_res, s.d_res, b.n * sizeof(nh_result), hipMemcpyDeviceToHost, s.stream);
                 if (he == hipSuccess)
@@ -1506,6 +1650,8 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                     he = hipMemcpyAsync(s.h_taxa, s.d_taxa, toff * 4, hipMemcpyDeviceToHost, s.stream);
                 if (he == hipSuccess && split)
                     he = hipMemcpyAsync(s.h_htotal, d_htotal, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
+                if (he == hipSuccess && mask)
+                    he = hipMemcpyAsync(s.h_htotal + 2, d_mtotal, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
                 if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("D2H: ") + hipGetErrorString(he));
             }
             batch_no++;
@@ -1552,6 +1698,11 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 fprintf(stderr, "[nohuman trace] human-out: %llu records, %llu bytes built on device; %llu fetched to host; builder kernels %.3f ms (%.1f GB/s of text)\n",
                         (unsigned long long)rs.human_records, (unsigned long long)rs.human_bytes, (unsigned long long)rs.text_fetched.load(),
                         rs.human_kernel_ms, rs.human_kernel_ms > 0 ? (double)rs.human_bytes / (rs.human_kernel_ms * 1e6) : 0.0);
+            if (mask)
+                fprintf(stderr, "[nohuman trace] mask: %llu records masked, %llu written, %llu bytes built on device; %llu fetched to host; builder kernels %.3f ms (%.1f GB/s of text)\n",
+                        (unsigned long long)rs.mask_masked, (unsigned long long)rs.mask_records, (unsigned long long)rs.mask_bytes,
+                        (unsigned long long)rs.text_fetched.load(), rs.mask_kernel_ms,
+                        rs.mask_kernel_ms > 0 ? (double)rs.mask_bytes / (rs.mask_kernel_ms * 1e6) : 0.0);
             if (g_pageable_batches.load())
                 fprintf(stderr, "[nohuman trace] %d batch buffers could not be page-locked (pageable memory used)\n",
                         g_pageable_batches.load());
@@ -1668,9 +1819,10 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
     return NH_OK;
 }
 
-int run_engine(Engine *e, const nh_run_args *a, nh_stats *stats, const char *hout1 = nullptr, const char *hout2 = nullptr) {
+int run_engine(Engine *e, const nh_run_args *a, nh_stats *stats, const char *hout1 = nullptr, const char *hout2 = nullptr,
+               bool mask = false) {
     std::vector<Engine *> v{e};
-    return run_engines(v, a, stats, hout1, hout2);
+    return run_engines(v, a, stats, hout1, hout2, mask);
 }
 
 }  // namespace nh
@@ -1687,6 +1839,13 @@ int nh_run_engine_split(nh_engine *e, const nh_run_args *args, const char *human
     if (rc) return rc;
     if (!e) return nh::set_error(NH_EINVAL, "null engine");
     return nh::run_engine((nh::Engine *)e, args, stats, human_out1, human_out2);
+}
+
+int nh_run_engine_mask(nh_engine *e, const nh_run_args *args, const char *human_out1, const char *human_out2, nh_stats *stats) {
+    const int rc = nh::check_mask_args(args, human_out1, human_out2);
+    if (rc) return rc;
+    if (!e) return nh::set_error(NH_EINVAL, "null engine");
+    return nh::run_engine((nh::Engine *)e, args, stats, human_out1, human_out2, true);
 }
 
 int nh_fastx_scan(const char *path, uint64_t *n_records, uint64_t *n_bases, uint64_t *digest) {
@@ -1725,7 +1884,7 @@ int nh_fastx_scan(const char *path, uint64_t *n_records, uint64_t *n_bases, uint
 
 // Whole run on one or several devices: the database is loaded into every device's HBM, batches go
 // round-robin, outputs stay in input order, the counts are summed on the host.
-static int run_devices(const nh_run_args *args, nh_stats *stats, const char *hout1, const char *hout2) {
+static int run_devices(const nh_run_args *args, nh_stats *stats, const char *hout1, const char *hout2, bool mask = false) {
     if (!args || !args->db_dir) return nh::set_error(NH_EINVAL, "nh_run: db_dir is required");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -1761,7 +1920,7 @@ static int run_devices(const nh_run_args *args, nh_stats *stats, const char *hou
     }
     const double t_load = since(t_begin);
     const auto t_run = std::chrono::steady_clock::now();
-    if (!rc) rc = nh::run_engines(engines, args, stats, hout1, hout2);
+    if (!rc) rc = nh::run_engines(engines, args, stats, hout1, hout2, mask);
     const double s_run = since(t_run);
     std::string keep = nh::g_last_error;
     const auto t_close = std::chrono::steady_clock::now();
@@ -1779,6 +1938,12 @@ int nh_run_split(const nh_run_args *args, const char *human_out1, const char *hu
     const int rc = nh::check_split_args(args, human_out1, human_out2);  // (before any device is touched)
     if (rc) return rc;
     return run_devices(args, stats, human_out1, human_out2);
+}
+
+int nh_run_mask(const nh_run_args *args, const char *human_out1, const char *human_out2, nh_stats *stats) {
+    const int rc = nh::check_mask_args(args, human_out1, human_out2);  // (before any device is touched)
+    if (rc) return rc;
+    return run_devices(args, stats, human_out1, human_out2, true);
 }
 
 }  // extern "C"

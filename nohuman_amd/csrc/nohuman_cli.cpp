@@ -216,6 +216,7 @@ struct Args {
     std::string out1, out2, database, db_version, kraken_output, kraken_report;
     std::string human_out1, human_out2;  // split run: the human reads in the same pass (nh_run_split)
     bool has_human_out1 = false, has_human_out2 = false;
+    bool mask = false;  // masked run: every read written, the human ones' bases as N (nh_run_mask)
     bool has_out1 = false, has_out2 = false, check = false, download = false, list = false, human = false;
     bool has_type = false;
     Codec type = C_NONE;
@@ -240,6 +241,7 @@ static void usage(FILE *f) {
           "  -H, --human                  Output human reads instead of removing them\n"
           "      --human-out1 <PATH>      Also write the human reads, in the same run, to this file (as -H would)\n"
           "      --human-out2 <PATH>      Second human output file (required with two inputs)\n"
+          "      --mask                   Replace the bases of human reads with N instead of removing them (every read is written, in input order)\n"
           "  -C, --conf <[0, 1]>          Kraken2 minimum confidence score [default: 0.0]\n"
           "  -k, --kraken-output <FILE>   Write the Kraken2 read classification output to a file\n"
           "  -r, --kraken-report <FILE>   Write the Kraken2 report with aggregate counts/clade to file\n"
@@ -301,6 +303,7 @@ static Args parse_args(int argc, char **argv) {
         } else if (s == "-H" || s == "--human") a.human = true;
         else if (s == "--human-out1") { a.human_out1 = val(); a.has_human_out1 = true; }
         else if (s == "--human-out2") { a.human_out2 = val(); a.has_human_out2 = true; }
+        else if (s == "--mask") a.mask = true;
         else if (s == "-C" || s == "--conf") {
             std::string t = val();
             char *end;
@@ -321,6 +324,7 @@ static Args parse_args(int argc, char **argv) {
     }
     if (a.input.empty() && !a.check && !a.download && !a.list)
         arg_error("the following required arguments were not provided:\n  <INPUT>...");
+    if (a.mask && a.human) arg_error("the argument '--mask' cannot be used with '--human'");
     // split run (--human-out1 / --human-out2): the non-human reads to -o / -O, the human ones to these, in one pass
     if (a.has_human_out1 || a.has_human_out2) {
         const bool paired = a.input.size() == 2;
@@ -442,7 +446,7 @@ int main(int argc, char **argv) {
     std::string out2 = paired ? (args.has_out2 ? args.out2 : default_out_name(args.input[1], out_codec)) : "";
     const int codec = out_codec == C_GZ ? NH_CODEC_GZIP : out_codec == C_BZ2 ? NH_CODEC_BZIP2 : out_codec == C_XZ ? NH_CODEC_XZ
                     : out_codec == C_ZST ? NH_CODEC_ZSTD : NH_CODEC_NONE;
-    INFO(args.human ? "Keeping human reads..." : "Removing human reads...");
+    INFO(args.mask ? "Masking human reads..." : args.human ? "Keeping human reads..." : "Removing human reads...");
 
     std::string conf_text;
     const double conf64 = confidence_as_kraken2_sees_it(args.confidence, conf_text);
@@ -501,7 +505,8 @@ int main(int argc, char **argv) {
         ra.device_ids = devs.data();
     }
     nh_stats st;
-    const int run_rc = split ? nh_run_split(&ra, hpart1.c_str(), paired ? hpart2.c_str() : nullptr, &st) : nh_run(&ra, &st);
+    const char *hp1 = split ? hpart1.c_str() : nullptr, *hp2 = split && paired ? hpart2.c_str() : nullptr;
+    const int run_rc = args.mask ? nh_run_mask(&ra, hp1, hp2, &st) : split ? nh_run_split(&ra, hp1, hp2, &st) : nh_run(&ra, &st);
     if (run_rc != 0) {
         std::string msg = nh_last_error();
         // nothing half-written stays behind, and nothing this run did not create is touched

@@ -39,10 +39,11 @@ def probe() -> str:
 
 def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None, confidence: float = 0.0,
         threads: int = 1, keep_human: bool = False, device_ids=None, out_codec: int = 0,
-        codec_threads: int = 0, human_out1=None, human_out2=None) -> "_lib.nh_stats":
+        codec_threads: int = 0, human_out1=None, human_out2=None, mask: bool = False) -> "_lib.nh_stats":
     """nh_run: whole run, database loaded into every listed device (default: all visible).  human_out1 (and, paired,
     human_out2) given: nh_run_split -- the non-human reads go to out1 / out2 and, in the same pass, the human reads to
-    human_out1 / human_out2 exactly as a keep_human run would write them."""
+    human_out1 / human_out2 exactly as a keep_human run would write them.  mask: nh_run_mask -- every read goes to
+    out1 / out2 in input order, a human read's bases replaced by N (with human_out1 / human_out2 as well, if given)."""
     a = _lib.nh_run_args()
     a.db_dir = os.fsencode(db_dir)
     a.in1 = os.fsencode(in1)
@@ -65,7 +66,9 @@ def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
         a.n_devices = 0
         a.device_ids = None
     s = _lib.nh_stats()
-    if human_out1 is not None or human_out2 is not None:
+    if mask:
+        _check(_lib.lib().nh_run_mask(C.byref(a), _path_or_none(human_out1), _path_or_none(human_out2), C.byref(s)))
+    elif human_out1 is not None or human_out2 is not None:
         _check(_lib.lib().nh_run_split(C.byref(a), _path_or_none(human_out1), _path_or_none(human_out2), C.byref(s)))
     else:
         _check(_lib.lib().nh_run(C.byref(a), C.byref(s)))
@@ -270,8 +273,9 @@ class Engine:
     # -- whole run -----------------------------------------------------------------------------
     def run(self, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
             confidence: float = 0.0, threads: int = 1, keep_human: bool = False, out_codec: int = 0,
-            codec_threads: int = 0, human_out1=None, human_out2=None) -> _lib.nh_stats:
-        """nh_run_engine; with human_out1 (and, paired, human_out2): nh_run_engine_split, as run() above."""
+            codec_threads: int = 0, human_out1=None, human_out2=None, mask: bool = False) -> _lib.nh_stats:
+        """nh_run_engine; with human_out1 (and, paired, human_out2): nh_run_engine_split; mask: nh_run_engine_mask -- as
+        run() above."""
         a = _lib.nh_run_args()
         a.db_dir = None
         a.in1 = os.fsencode(in1)
@@ -288,7 +292,10 @@ class Engine:
         a.out_codec = int(out_codec)
         a.codec_threads = int(codec_threads)
         s = _lib.nh_stats()
-        if human_out1 is not None or human_out2 is not None:
+        if mask:
+            _check(self._L.nh_run_engine_mask(self._h, C.byref(a), _path_or_none(human_out1), _path_or_none(human_out2),
+                                              C.byref(s)))
+        elif human_out1 is not None or human_out2 is not None:
             _check(self._L.nh_run_engine_split(self._h, C.byref(a), _path_or_none(human_out1), _path_or_none(human_out2),
                                                C.byref(s)))
         else:
