@@ -159,7 +159,7 @@ struct MaskArgs {
     uint64_t cap[2];          // bytes of out[m]
     uint64_t *blk;            // 2 * nblk words of scratch
     uint32_t *fast;           // 2 * nblk words of scratch
-    uint64_t *total;          // 2 words
+    uint64_t *total;          // 4 words: [m] the bytes of mate m's output, [2 + m] how many of its blocks are FAST
     int *error;               // the engine's sticky error word (bit 8: a record outside its text or buffer)
 };
 uint64_t mask_blocks(uint64_t n);

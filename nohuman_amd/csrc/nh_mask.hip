@@ -11,7 +11,8 @@
 //   k_mask_sizes  per block of MB_FRAGS fragments: the sum of their output lengths, and whether the block is FAST: every
 //                 record already in output form in the text (the same test as nh_fastx.h's raw_end, made on the device from
 //                 the fields and a few bytes around them) and each record's text starting where the one before ends
-//   k_mask_scan   per mate, one workgroup: exclusive scan of the block sums in place -> block offsets; the mate's total
+//   k_mask_scan   per mate, one workgroup: exclusive scan of the block sums in place -> block offsets; the mate's total and
+//                 (for the trace line) its number of FAST blocks
 //   k_mask_copy   MB_SUB workgroups per block.  FAST block: its text is one contiguous range, copied 16 bytes a lane (aligned
 //                 dwordx4 stores; the two partial chunks at the range's ends, shared with the neighbouring blocks, byte by
 //                 byte).  Other blocks: the lengths again, an exclusive scan inside the block, then one wave per record
@@ -124,12 +125,13 @@ __global__ void __launch_bounds__(MB_THREADS) k_mask_sizes(MaskArgs a) {
     }
 }
 
-// one workgroup per mate: block sums -> exclusive block offsets (in place), the mate's total
+// one workgroup per mate: block sums -> exclusive block offsets (in place), the mate's total and its number of FAST blocks
 __global__ void __launch_bounds__(MB_THREADS) k_mask_scan(MaskArgs a) {
     __shared__ uint64_t wsum[MB_WAVES];
     const int m = blockIdx.x;
     uint64_t *b = a.blk + (uint64_t)m * a.nblk;
-    uint64_t carry = 0;
+    const uint32_t *fast = a.fast + (uint64_t)m * a.nblk;
+    uint64_t carry = 0, nfast = 0;
     for (uint64_t c = 0; c < a.nblk; c += MB_THREADS) {
         const uint64_t i = c + threadIdx.x;
         const uint64_t v = i < a.nblk ? b[i] : 0;
@@ -137,7 +139,7 @@ __global__ void __launch_bounds__(MB_THREADS) k_mask_scan(MaskArgs a) {
         const uint64_t ex = block_exclusive_scan(v, wsum, &sum);
         if (i < a.nblk) b[i] = carry + ex;
         carry += sum;
-        __syncthreads();  // (wsum is written again by the next chunk)
+        nfast += (uint64_t)__syncthreads_count(i < a.nblk && fast[i] != 0);  // (also: wsum is written again by the next chunk)
     }
     if (threadIdx.x == 0) {
         if (carry > a.cap[m]) {
@@ -145,6 +147,7 @@ __global__ void __launch_bounds__(MB_THREADS) k_mask_scan(MaskArgs a) {
             carry = 0;
         }
         a.total[m] = carry;
+        a.total[2 + m] = nfast;
     }
 }
 
@@ -301,7 +304,7 @@ __global__ void __launch_bounds__(MB_THREADS) k_mask_fill(MaskArgs a) {
 uint64_t mask_blocks(uint64_t n) { return (n + MB_FRAGS - 1) / MB_FRAGS; }
 
 hipError_t launch_mask(const MaskArgs &a, hipStream_t stream) {
-    if (a.n == 0) return hipMemsetAsync(a.total, 0, 2 * sizeof(uint64_t), stream);
+    if (a.n == 0) return hipMemsetAsync(a.total, 0, 4 * sizeof(uint64_t), stream);
     const dim3 grid((unsigned)a.nblk, (unsigned)a.mates), sub((unsigned)(a.nblk * MB_SUB), (unsigned)a.mates);
     hipLaunchKernelGGL(k_mask_sizes, grid, dim3(MB_THREADS), 0, stream, a);
     hipLaunchKernelGGL(k_mask_scan, dim3((unsigned)a.mates), dim3(MB_THREADS), 0, stream, a);

@@ -347,7 +347,7 @@ struct Slot {  // pinned host + device buffers of one in-flight batch
     void *d_rec = nullptr, *d_hblk = nullptr;
     char *d_hout[2] = {nullptr, nullptr}, *h_hout[2] = {nullptr, nullptr};
     size_t cap_hout[2] = {0, 0}, cap_hhost[2] = {0, 0}, cap_rec = 0, cap_hblk = 0;
-    uint64_t *h_htotal = nullptr;  // [0..1]: the classified-out totals, [2..3]: the masked totals
+    uint64_t *h_htotal = nullptr;  // [0..1]: the classified-out totals, [2..3]: the masked totals, [4..5]: the masked FAST blocks
     hipEvent_t hev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around the builder's launches (its kernel time)
     // masked runs (nh_run_mask): every record of each mate built in HBM (the same record table as split runs), the builder's
     // scratch, and the host copies where an encoder cannot take the HBM range
@@ -439,7 +439,7 @@ static int slot_reserve_mask(Slot &s, size_t n, int mates, const size_t out_cap[
         if (host_malloc((void **)&s.h_rec, s.cap_rec * 16, hipHostMallocDefault) != hipSuccess || dev_malloc(&s.d_rec, s.cap_rec * 16) != hipSuccess)
             return set_error(NH_EOOM, "cannot allocate batch buffers (%zu records)", s.cap_rec);
     }
-    const size_t words = 3 * mask_blocks(n) + 2;  // (block offsets, totals, block flags: MaskArgs)
+    const size_t words = 3 * mask_blocks(n) + 4;  // (block offsets, totals and FAST counts, block flags: MaskArgs)
     if (words > s.cap_mblk) {
         if (s.d_mblk) (void)hipFree(s.d_mblk);
         s.cap_mblk = grow(words);
@@ -573,7 +573,7 @@ struct RunState {
     uint64_t human_records = 0, human_bytes = 0;
     double human_kernel_ms = 0;  // NOHUMAN_TRACE: the builder's launches, by events on the slots' streams
     // masked runs (NOHUMAN_TRACE): records masked and written, the bytes the mask builder made, its kernel time
-    uint64_t mask_masked = 0, mask_records = 0, mask_bytes = 0;
+    uint64_t mask_masked = 0, mask_records = 0, mask_bytes = 0, mask_nblk = 0, mask_fast = 0;
     double mask_kernel_ms = 0;
     std::atomic<uint64_t> text_fetched{0};
     std::vector<uint64_t> dev_counts;  // per device {fragments, classified, bases, 0} as the writer saw them (checker)
@@ -1369,6 +1369,8 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                     }
                     if (mask) {
                         rs.mask_records += b.n * (size_t)mates;
+                        rs.mask_nblk += mask_blocks(b.n) * (uint64_t)mates;
+                        for (int m = 0; m < mates; m++) rs.mask_fast += s.h_htotal[4 + m];
                         for (size_t i = 0; i < b.n; i++) rs.mask_masked += (s.h_res[i].call != 0) * (uint64_t)mates;
                     }
                     // a split run's classified records: the text the builder made, one span a mate -- in HBM, or copied here
@@ -1635,7 +1637,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 for (int m = 0; m < mates; m++) ma.out[m] = s.d_mout[m], ma.cap[m] = s.cap_mout[m];
                 ma.blk = (uint64_t *)s.d_mblk;
                 ma.total = d_mtotal = (uint64_t *)s.d_mblk + 2 * ma.nblk;
-                ma.fast = (uint32_t *)((uint64_t *)s.d_mblk + 2 * ma.nblk + 2);
+                ma.fast = (uint32_t *)((uint64_t *)s.d_mblk + 2 * ma.nblk + 4);
                 ma.error = s.e->d_error + LAUNCH_SLOTS;
                 if (s.mev[0]) (void)hipEventRecord(s.mev[0], s.stream);
                 he = launch_mask(ma, s.stream);
@@ -1651,7 +1653,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 if (he == hipSuccess && split)
                     he = hipMemcpyAsync(s.h_htotal, d_htotal, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
                 if (he == hipSuccess && mask)
-                    he = hipMemcpyAsync(s.h_htotal + 2, d_mtotal, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
+                    he = hipMemcpyAsync(s.h_htotal + 2, d_mtotal, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
                 if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("D2H: ") + hipGetErrorString(he));
             }
             batch_no++;
@@ -1699,10 +1701,11 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                         (unsigned long long)rs.human_records, (unsigned long long)rs.human_bytes, (unsigned long long)rs.text_fetched.load(),
                         rs.human_kernel_ms, rs.human_kernel_ms > 0 ? (double)rs.human_bytes / (rs.human_kernel_ms * 1e6) : 0.0);
             if (mask)
-                fprintf(stderr, "[nohuman trace] mask: %llu records masked, %llu written, %llu bytes built on device; %llu fetched to host; builder kernels %.3f ms (%.1f GB/s of text)\n",
+                fprintf(stderr, "[nohuman trace] mask: %llu records masked, %llu written, %llu bytes built on device; %llu fetched to host; builder kernels %.3f ms (%.1f GB/s of text); %llu of %llu blocks copied whole\n",
                         (unsigned long long)rs.mask_masked, (unsigned long long)rs.mask_records, (unsigned long long)rs.mask_bytes,
                         (unsigned long long)rs.text_fetched.load(), rs.mask_kernel_ms,
-                        rs.mask_kernel_ms > 0 ? (double)rs.mask_bytes / (rs.mask_kernel_ms * 1e6) : 0.0);
+                        rs.mask_kernel_ms > 0 ? (double)rs.mask_bytes / (rs.mask_kernel_ms * 1e6) : 0.0,
+                        (unsigned long long)rs.mask_fast, (unsigned long long)rs.mask_nblk);
             if (g_pageable_batches.load())
                 fprintf(stderr, "[nohuman trace] %d batch buffers could not be page-locked (pageable memory used)\n",
                         g_pageable_batches.load());

@@ -21,6 +21,7 @@ DB = os.path.join(GOLD, "toy_db")
 BIN = os.path.join(ROOT, "nohuman_amd", "bin", "nohuman")
 TRACE = re.compile(r"mask: (\d+) records masked, (\d+) written, (\d+) bytes built on device; (\d+) fetched to host; "
                    r"builder kernels ([0-9.]+) ms")
+WHOLE = re.compile(r"mask: [^\n]*; (\d+) of (\d+) blocks copied whole")  # (behind what TRACE matches)
 SFX = re.compile(rb" kraken:taxid\|\d+$")
 
 
@@ -58,7 +59,8 @@ def compare(tmp, name, in1, in2=None, codec=0, conf=0.0, device_ids=(0,), env=No
             fasta=False, human=False):
     """normal run, -H run, masked run: every masked record is the normal run's (unclassified) or the -H run's with the
     suffix stripped and the sequence as N (classified); -k, -r and the stats are the normal run's.  human: the masked run
-    also writes human outputs, compared with a split run's.  Returns (stats, trace, masked text per mate)."""
+    also writes human outputs, compared with a split run's.  Returns (stats, trace, masked text per mate); trace[5:7]: how
+    many blocks the builder copied whole, and how many there were."""
     from nohuman_amd import engine
     old = {k: os.environ.get(k) for k in (env or {})}
     os.environ.update(env or {})
@@ -87,7 +89,9 @@ def compare(tmp, name, in1, in2=None, codec=0, conf=0.0, device_ids=(0,), env=No
                 err = errf.read_bytes().decode(errors="replace")
                 t = TRACE.findall(err)
                 assert len(t) == 1, err[-3000:]
-                trace = tuple(int(x) for x in t[0][:4]) + (float(t[0][4]),)
+                w = WHOLE.findall(err)
+                assert len(w) == 1, err[-3000:]
+                trace = tuple(int(x) for x in t[0][:4]) + (float(t[0][4]),) + tuple(int(x) for x in w[0])
         n, h, m = paths["n"], paths["h"], paths["m"]
         calls = [ln.split(b"\t")[0] == b"C" for ln in open(n["k"], "rb").read().splitlines()]
         mates = ("1", "2") if in2 else ("1",)
@@ -223,6 +227,7 @@ def test_large_batches_take_the_fast_path(tmp_path):
     for codec in (0, 2):
         st, trace, _ = compare(tmp_path, "big%d" % codec, str(p), codec=codec, want_k=False)
         assert st.total_sequences >= 4096 and st.classified > 0
+        assert trace[5] == trace[6] > 1, trace  # every block copied whole, and more than one of them
 
 
 def test_multiline_fasta_and_ultra_long_reads(tmp_path, toy):
