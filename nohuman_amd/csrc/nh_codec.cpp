@@ -663,7 +663,7 @@ extern "C" int nh_debug_gunzip_ranges(const char *in, const char *out, uint32_t 
             const size_t cap = (size_t)std::min<uint64_t>((std::min<uint64_t>(hi, size) - lo + 65536) * 1040, (uint64_t)1 << 33);
             std::unique_ptr<uint8_t[]> text(new uint8_t[cap]);
             std::vector<nh::GzSeg> segs;
-            const long n = rg.finish(P, window.data(), text.get(), cap, &end_bit, &ended, wafter.data(), segs);
+            const long n = rg.finish(P, window.data(), run_len, text.get(), cap, &end_bit, &ended, wafter.data(), segs);
             if (n < 0) {
                 rc = nh::set_error(NH_EIO, "%s", rg.error().c_str());
                 break;
@@ -683,7 +683,8 @@ extern "C" int nh_debug_gunzip_ranges(const char *in, const char *out, uint32_t 
             std::vector<uint8_t> o;
             std::vector<nh::GzMemberEnd> members;
             std::string err;
-            if (nh::inflate_from(base, base + size, P, hi * 8, window.data(), window.size(), o, members, &end_bit, &ended, err) != 0) {
+            const size_t wl = (size_t)std::min<uint64_t>(window.size(), run_len);  // (of the member the stream stands in)
+            if (nh::inflate_from(base, base + size, P, hi * 8, window.data() + window.size() - wl, wl, o, members, &end_bit, &ended, err) != 0) {
                 rc = nh::set_error(NH_EIO, "%s", err.c_str());
                 break;
             }

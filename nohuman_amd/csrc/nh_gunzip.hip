@@ -62,7 +62,9 @@ struct ChunkDesc {  // one per stretch of the piece
     uint32_t status;
     uint32_t n_members;  // member ends inside the chunk
     uint32_t flags;      // 1: the stream ended in this chunk
-    uint32_t blocks, pad1;
+    uint32_t blocks;
+    uint32_t reach;      // how far before the chunk's first symbol its matches reach into the member it starts in (the host checks it against
+                         // that member's text so far: a chunk that starts inside a member does not know where the member began)
     uint32_t m_off[MAX_MEMBERS], m_crc[MAX_MEMBERS], m_isize[MAX_MEMBERS];
     uint32_t piece_crc[MAX_MEMBERS + 1];  // k_crc: CRC-32 of the text between the chunk's start, its member ends, its end
     uint32_t pad2;
@@ -262,7 +264,9 @@ __device__ __forceinline__ uint32_t lit_entry3(uint32_t s, uint32_t l) {
 __device__ __forceinline__ uint32_t dist_entry3(uint32_t s, uint32_t l) { return s >= 30u ? 0u : (l | (s << 4) | ((uint32_t)DEXT[s] << 9)); }
 
 // build() for Lds3: counts, canonical symbol list, codes, 16-bit root table; mode 0 the code-length code, 1 literals /
-// lengths, 2 distances.  False: over-subscribed.
+// lengths, 2 distances.  False: over-subscribed, or incomplete -- refused like zlib and the host decoder (nh_inflate.cpp,
+// build_table) refuse it: the code-length code must be complete, the other two may be a single one-bit code (and the
+// distances no code at all).
 __device__ __forceinline__ bool build3(Lds3 &S, const uint8_t *lens, int n, uint16_t *count, uint16_t *symlist, uint16_t *root, int rootbits,
                                        int mode, int lane) {
     LDS_ORDER();
@@ -282,6 +286,7 @@ __device__ __forceinline__ bool build3(Lds3 &S, const uint8_t *lens, int n, uint
             c = (c + count[l - 1]) << 1;
             next[l] = (uint16_t)c;
         }
+        if (left > 0 && (mode == 0 || (o != 0 && !(o == 1 && count[1] == 1)))) over = 1;
         if (!over)
             for (int s = 0; s < n; s++) {
                 const int l = lens[s];
@@ -369,6 +374,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 8))) void
             cd.n_members = 0;
             cd.flags = 0;
             cd.blocks = 0;
+            cd.reach = 0;
         }
         return;
     }
@@ -389,6 +395,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 8))) void
     uint32_t status = 0, blocks = 0, n_members = 0, flags = 0;
     uint32_t floor_op = 0;
     bool fresh_member = false;
+    uint32_t reach = 0;  // (a lane's own maximum; joined at the end)
     uint32_t tok = 0, tpos = 0;  // this lane's token of the window: literal 0x80000000 | byte, match distance | symbols << 16; offset in the window's output
 #ifdef NH_GZ_PROF
     uint64_t pf[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -487,7 +494,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 8))) void
                 for (int s = lane; s < 288; s += 64) S.lens[s] = s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : 8;
                 if (lane < 32) S.lens[288 + lane] = 5;
                 nlit = 288;
-                ndist = 30;
+                ndist = 32;  // (all 32 five-bit codes: the set is complete; 30 and 31 have no entry and no meaning, like 286 and 287)
             } else {
                 status = parse_dynamic3(S, br, lane, nlit, ndist);
                 if (status) break;
@@ -617,6 +624,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 8))) void
                         status = ST_FAR;
                         break;
                     }
+                    if (act && !isl && !fresh_member && dd > at) reach = max(reach, dd - at);
                 }
                 if (isl) S.ring[(op + tpos) & M3] = (uint16_t)(tok & 0xFFu);
                 const uint64_t mall = __ballot(act && !isl);
@@ -787,9 +795,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 8))) void
     if (lane == 0)
         for (int i = 0; i < 12; i++) cd.prof[i] = pf[i];
 #endif
+#pragma unroll
+    for (int o2 = 32; o2 > 0; o2 >>= 1) reach = max(reach, (uint32_t)__shfl_xor((int)reach, o2));
     if (lane == 0) {
         cd.status = status;
         cd.blocks = blocks;
+        cd.reach = reach;
         cd.bit_end = br.bitpos();
         cd.out_len = op;
         cd.n_members = n_members;
@@ -2028,6 +2039,8 @@ private:
 #ifdef NH_GZ_PROF
             for (int i = 0; i < 12; i++) prof_[i] += cd.prof[i];
 #endif
+            // (a distance that reaches before the first byte of the member the chunk starts in: zlib's "invalid distance too far back")
+            if (cd.reach > run_len_) return fail("gzip: invalid distance too far back");
             uint32_t a = 0;
             for (uint32_t p = 0; p <= cd.n_members; p++) {
                 const uint32_t b = p < cd.n_members ? cd.m_off[p] : cd.out_len;
@@ -2259,7 +2272,7 @@ private:
             bool stream_end = false;
             std::vector<GzSeg> segs;
             const auto t0 = std::chrono::steady_clock::now();
-            const long n = hc_->finish(pos_bit_, window, h_text_, h_text_cap_, &eb, &stream_end, wafter, segs);
+            const long n = hc_->finish(pos_bit_, window, run_len_, h_text_, h_text_cap_, &eb, &stream_end, wafter, segs);
             if (n < 0) {
                 error_ = hc_->error() + " (" + path_ + ")";
                 hc_->close();
@@ -2328,9 +2341,9 @@ private:
         uint64_t eb = 0;
         bool stream_end = false;
         std::string err;
-        // (a member that started before this piece keeps its window; one that starts here has none -- the window only
-        //  matters for valid references, which never reach before a member's start)
-        if (inflate_from(base_, base_ + size_, from, stop, window.data(), WSIZE, out, members, &eb, &stream_end, err, room / 2) != 0) {
+        // (a member that started before this piece keeps what there is of it in the window; one that starts here has none)
+        const size_t wl = (size_t)std::min<uint64_t>(WSIZE, run_len_);
+        if (inflate_from(base_, base_ + size_, from, stop, window.data() + WSIZE - wl, wl, out, members, &eb, &stream_end, err, room / 2) != 0) {
             error_ = err + " (" + path_ + ")";
             return -1;
         }

@@ -531,9 +531,10 @@ int decode_bytes(BitIn &in, const Tables &T, const uint8_t *min_src, uint8_t *&o
 // 16-bit symbols with unknown history: `start` is the first symbol of the chunk; a source before it
 // becomes the marker 0x8000 | index into the 32 KiB window that precedes the chunk.  marker_end = one
 // past the index of the last symbol that is (or may be a copy of) a marker.  Returns D_CLEAN as soon
-// as the last 32 KiB are free of markers.
+// as the last 32 KiB are free of markers.  reach = how far before `start` the matches have reached (the chunk does not
+// know where its member began: whoever stitches it holds that against the member's text so far).
 int decode_markers(BitIn &in, const Tables &T, uint16_t *start, uint16_t *&op_ref, uint16_t *limit,
-                   size_t &marker_end) {
+                   size_t &marker_end, size_t &reach) {
     uint16_t *op = op_ref;
     int rc;
     for (;;) {
@@ -586,6 +587,7 @@ int decode_markers(BitIn &in, const Tables &T, uint16_t *start, uint16_t *&op_re
                     rc = D_ERR;
                     break;
                 }
+                if (dist - produced > reach) reach = dist - produced;
                 const uint32_t in_window = (uint32_t)(dist - produced) < len ? (uint32_t)(dist - produced) : len;
                 const uint32_t w0 = (uint32_t)(WSIZE - (dist - produced));
                 for (; i < in_window; i++) op[i] = (uint16_t)(0x8000u | (w0 + i));
@@ -737,6 +739,7 @@ struct ChunkDecoder {
     ptrdiff_t floor_off = 0;  // sources may reach back to out8.data() + floor_off (history / member start)
     bool bytes_mode = false;
     size_t marker_end = 0;
+    size_t reach = 0;  // 16-bit part: how far before the chunk's first symbol its matches reach (decode_markers)
     std::vector<MemberEnd> members;
     size_t out_limit = (size_t)-1;  // stop at the first block boundary with this much output (inflate_from)
     // result
@@ -749,7 +752,7 @@ struct ChunkDecoder {
     void reset(const uint8_t *b, const uint8_t *e) {
         base = b;
         end = e;
-        n16 = n8 = marker_end = 0;
+        n16 = n8 = marker_end = reach = 0;
         floor_off = 0;
         at_block = nullptr;
         bytes_mode = false;
@@ -775,8 +778,9 @@ struct ChunkDecoder {
     std::function<bool(ChunkDecoder &)> at_block;
 
     // The WSIZE bytes before the chunk are known now: the last WSIZE symbols (markers replaced) become
-    // the byte decoder's history and the rest of the chunk is decoded as bytes.
-    bool adopt_window(const uint8_t *window) {
+    // the byte decoder's history and the rest of the chunk is decoded as bytes.  member_len: text of the chunk's member
+    // before the chunk -- sources reach no further back.
+    bool adopt_window(const uint8_t *window, uint64_t member_len) {
         if (!out8.reserve(1u << 20)) return false;
         uint8_t *h = out8.data() - WSIZE;
         const uint16_t *s = out16.data();
@@ -788,7 +792,7 @@ struct ChunkDecoder {
             uint8_t *d = h + (WSIZE - n16);
             for (size_t i = 0; i < n16; i++) d[i] = s[i] & 0x8000u ? window[s[i] & 0x7fffu] : (uint8_t)s[i];
         }
-        floor_off = -(ptrdiff_t)WSIZE;
+        floor_off = -(ptrdiff_t)std::min<uint64_t>(WSIZE, member_len + n16);
         bytes_mode = true;
         return true;
     }
@@ -847,7 +851,7 @@ struct ChunkDecoder {
             } else {
                 if (!out16.reserve(n16 + (1u << 17))) return fail("out of memory");
                 uint16_t *op = out16.data() + n16;
-                rc = decode_markers(in, *tab, out16.data(), op, out16.data() + out16.size() - 320, marker_end);
+                rc = decode_markers(in, *tab, out16.data(), op, out16.data() + out16.size() - 320, marker_end, reach);
                 n16 = (size_t)(op - out16.data());
                 if (rc == D_OUT_FULL) continue;
                 if (rc == D_CLEAN) {
@@ -928,6 +932,7 @@ struct Chunk {
     ChunkDecoder dec;
     bool found = false;
     bool chained = false;  // decoded from the known end of its predecessor: start and window are certain
+    uint64_t member_before = 0;  // chained: text of the member the chunk starts in before the chunk
     bool spec_done = false, resolved = false;
     uint8_t window_before[WSIZE];
     std::vector<Seg> segs;
@@ -1040,6 +1045,7 @@ public:
         memset(window_, 0, sizeof window_);
         cur_crc_ = 0;
         cur_len_ = 0;
+        member_len_ = 0;
         accepted_ = rejected_ = gap_bytes_ = 0;
         for (unsigned i = 0; i < threads_; i++) workers_.emplace_back([this] { worker(); });
         return 0;
@@ -1100,6 +1106,7 @@ public:
         memset(window_, 0, sizeof window_);
         cur_crc_ = 0;
         cur_len_ = 0;
+        member_len_ = 0;
         accepted_ = rejected_ = gap_bytes_ = 0;
         out_total_ = 0;
         for (unsigned i = 0; i < threads_; i++) workers_.emplace_back([this] { worker(); });
@@ -1118,11 +1125,12 @@ public:
     // range's text goes to dst; returns its length (-1: error()), the bit the stream stands at afterwards -- the first block
     // boundary at or behind the range's end that passes the seam test, or the end of the stream --, the window there and the
     // stretches of text by gzip member with their CRC-32 (the caller keeps the members' books: a member may have begun
-    // long before the range).
-    long finish_range(uint64_t from_bit, const uint8_t *window, uint8_t *dst, size_t cap, uint64_t *end_bit, bool *stream_end,
-                      uint8_t *window_after, std::vector<GzSeg> &segs) {
+    // long before the range; member_len: how much text of it there is before from_bit -- no distance reaches further back).
+    long finish_range(uint64_t from_bit, const uint8_t *window, uint64_t member_len, uint8_t *dst, size_t cap, uint64_t *end_bit,
+                      bool *stream_end, uint8_t *window_after, std::vector<GzSeg> &segs) {
         if (!range_ || failed_) return -1;
         P_ = from_bit;
+        member_len_ = member_len;
         memcpy(window_, window, WSIZE);
         range_dst_ = dst;
         range_cap_ = cap;
@@ -1211,8 +1219,16 @@ private:
     struct TailInfo {
         uint64_t end_bit = 0;
         bool stream_end = false, failed = false;
+        uint64_t member_len = 0;  // text of the member the stream stands in, up to here
         uint8_t window[WSIZE];
     };
+
+    // text of the member the stream stands in behind a chunk, given that before it
+    static uint64_t member_after(uint64_t before, const ChunkDecoder &d) {
+        return d.members.empty() ? before + d.total() : d.total() - (uint64_t)d.members.back().out_pos;
+    }
+    // the window a decoder may start with: of the WSIZE bytes before a position, those of the member it stands in
+    static size_t own_window(uint64_t member_len) { return (size_t)std::min<uint64_t>(WSIZE, member_len); }
 
     void worker() {
         for (;;) {
@@ -1277,6 +1293,7 @@ private:
         std::shared_ptr<TailInfo> t(new TailInfo());
         t->end_bit = c.dec.end_bit;
         t->stream_end = c.dec.stop == STOP_STREAM_END;
+        t->member_len = member_after(c.member_before, c.dec);
         const size_t n16 = c.dec.n16, n8 = c.dec.n8, total = n16 + n8;
         const uint16_t *s = c.dec.out16.data();
         const uint8_t *w = c.window_before;
@@ -1298,6 +1315,7 @@ private:
         c.chained = false;
         if (c.index == 0 && !range_) {
             memset(c.window_before, 0, WSIZE);
+            c.member_before = 0;
             c.dec.start_bytes(nullptr, 0);
             c.dec.run(first_block_bit_, chunk_bit(1), chunk_bit(2), false);
             c.found = true;  // errors of the first chunk are real errors
@@ -1320,7 +1338,8 @@ private:
                     return;
                 }
                 memcpy(c.window_before, t->window, WSIZE);
-                c.dec.start_bytes(t->window, WSIZE);
+                c.member_before = t->member_len;
+                c.dec.start_bytes(t->window + WSIZE - own_window(t->member_len), own_window(t->member_len));
                 c.dec.run(t->end_bit, chunk_bit(c.index + 1), chunk_bit(c.index + 2), false);
                 c.found = c.dec.stop != STOP_ERROR;
                 c.chained = c.found;
@@ -1354,7 +1373,8 @@ private:
                 pred_known = true;
                 if (t->failed || t->stream_end || t->end_bit != d.start_bit) return false;
                 memcpy(c.window_before, t->window, WSIZE);
-                if (!d.adopt_window(t->window)) return false;
+                if (d.reach > t->member_len || !d.adopt_window(t->window, t->member_len)) return false;
+                c.member_before = t->member_len;
                 c.chained = true;
                 return true;
             };
@@ -1445,7 +1465,12 @@ private:
         return true;
     }
     void accept(std::unique_ptr<Chunk> c) {
+        if (c->dec.reach > member_len_) {  // (zlib: "invalid distance too far back")
+            fail("gzip: invalid deflate data");
+            return;
+        }
         if (!place(*c)) return;
+        member_len_ = member_after(member_len_, c->dec);
         memcpy(c->window_before, window_, WSIZE);
         advance_window(*c);
         P_ = c->dec.end_bit;
@@ -1456,6 +1481,7 @@ private:
             t.reset(new TailInfo());
             t->end_bit = P_;
             t->stream_end = ended_;
+            t->member_len = member_len_;
             memcpy(t->window, window_, WSIZE);
         }
         pieces_.push_back(std::move(c));
@@ -1476,13 +1502,14 @@ private:
         g->resolved = g->verified = false;
         g->read_off = 0;
         g->dec.reset(base_, base_ + size_);
-        g->dec.start_bytes(window_, WSIZE);
+        g->dec.start_bytes(window_ + WSIZE - own_window(member_len_), own_window(member_len_));
         uint64_t soft = P_ + (uint64_t)chunk_ * 8;
         if (soft > target) soft = target;
         g->dec.run(P_, soft, (uint64_t)-1, true);
         if (g->dec.stop == STOP_ERROR) return fail(g->dec.error);
         if (!place(*g)) return false;
         gap_bytes_ += g->dec.total();
+        member_len_ = member_after(member_len_, g->dec);
         memcpy(g->window_before, window_, WSIZE);
         advance_window(*g);
         P_ = g->dec.end_bit;
@@ -1548,6 +1575,7 @@ private:
         if (ended_ || P_ < chunk_bit(idx + 1)) return;
         std::shared_ptr<TailInfo> t(new TailInfo());
         t->end_bit = P_;
+        t->member_len = member_len_;
         memcpy(t->window, window_, WSIZE);
         {
             std::lock_guard<std::mutex> lk(mu_);
@@ -1598,6 +1626,7 @@ private:
     std::atomic<uint64_t> t_spec_ns_{0}, t_resolve_ns_{0};  // the workers' time decoding / replacing markers + CRC (NOHUMAN_TRACE)
     uint64_t t_wait_ns_ = 0, t_copy_ns_ = 0;  // the consumer's time waiting for the head chunk / copying it out (NOHUMAN_TRACE)
     std::map<size_t, std::shared_ptr<TailInfo>> tails_;
+    uint64_t member_len_ = 0;  // the consumer's: text of the member the stream stands in, up to P_
     bool quit_ = false;
     std::vector<std::thread> workers_;
 };
@@ -1608,9 +1637,9 @@ int RangeGunzip::start(const uint8_t *base, size_t size, uint64_t lo_byte, uint6
     return impl_->open_range(base, size, lo_byte, hi_byte, threads, chunk_bytes);
 }
 void RangeGunzip::wait_speculated() { impl_->wait_speculated(); }
-long RangeGunzip::finish(uint64_t from_bit, const uint8_t *window, uint8_t *dst, size_t cap, uint64_t *end_bit, bool *stream_end,
-                         uint8_t *window_after, std::vector<GzSeg> &segs) {
-    return impl_->finish_range(from_bit, window, dst, cap, end_bit, stream_end, window_after, segs);
+long RangeGunzip::finish(uint64_t from_bit, const uint8_t *window, uint64_t member_len, uint8_t *dst, size_t cap, uint64_t *end_bit,
+                         bool *stream_end, uint8_t *window_after, std::vector<GzSeg> &segs) {
+    return impl_->finish_range(from_bit, window, member_len, dst, cap, end_bit, stream_end, window_after, segs);
 }
 const std::string &RangeGunzip::error() const { return impl_->error(); }
 void RangeGunzip::stats(uint64_t *a, uint64_t *r, uint64_t *g) const { impl_->stats(a, r, g); }

@@ -89,8 +89,9 @@ public:
     int start(const uint8_t *base, size_t size, uint64_t lo_byte, uint64_t hi_byte, unsigned threads, size_t chunk_bytes);
     void wait_speculated();  // every chunk has been tried (needs neither the stream's position nor its window)
     // -1: error(); else the bytes of text written to dst
-    long finish(uint64_t from_bit, const uint8_t *window, uint8_t *dst, size_t cap, uint64_t *end_bit, bool *stream_end,
-                uint8_t *window_after, std::vector<GzSeg> &segs);
+    // (member_len: text of the member the stream stands in before from_bit: a distance that reaches further back is an error)
+    long finish(uint64_t from_bit, const uint8_t *window, uint64_t member_len, uint8_t *dst, size_t cap, uint64_t *end_bit,
+                bool *stream_end, uint8_t *window_after, std::vector<GzSeg> &segs);
     const std::string &error() const;
     void stats(uint64_t *accepted, uint64_t *rejected, uint64_t *gap_bytes) const;
     void close();
