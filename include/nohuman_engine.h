@@ -214,7 +214,13 @@ typedef enum nh_codec {
     NH_CODEC_BZIP2 = 1,
     NH_CODEC_GZIP = 2,
     NH_CODEC_XZ = 3,
-    NH_CODEC_ZSTD = 4 /* through the system's libzstd.so.1 (level 3, frame checksum, `threads` workers) */
+    NH_CODEC_ZSTD = 4, /* through the system's libzstd.so.1 (level 3, frame checksum, `threads` workers) */
+    /* gzip in bgzip's blocked container (BGZF): a series of gzip members of 65280 bytes of text each (the last data member
+     * 1 to 65280), every one with its compressed size in a 'B' 'C' extra field and its own CRC-32 / ISIZE, closed by the
+     * 28-byte EOF member; an empty text is the EOF member alone.  Any gzip reader takes it; htslib tools seek in it, and
+     * this library's GPU reader finds its chunks by the headers.  Encoded like NH_CODEC_GZIP: on the GPU where nh_run has one
+     * (NOHUMAN_GZIP=host: zlib level 6 on `threads` workers), accepted wherever a codec is.  No .gzi index is written. */
+    NH_CODEC_BGZF = 5
 } nh_codec;
 
 /*
@@ -255,7 +261,7 @@ int nh_fastx_scan(const char *path, uint64_t *n_records, uint64_t *n_bases, uint
  * `in` to file `out`; gzip runs block-parallel on `threads` workers like the reference's gzp
  * encoder (compression.rs:214-233) and produces one ordinary gzip member at level 6; bzip2 and xz
  * go through libbz2.so.1 / liblzma.so.5 (one thread / `threads` workers, preset 6, CRC64), zstd through
- * libzstd.so.1; NH_CODEC_NONE copies.  Parity target is the decompressed content and
+ * libzstd.so.1; NH_CODEC_BGZF is zlib level 6 per 65280-byte member on `threads` workers; NH_CODEC_NONE copies.  Parity target is the decompressed content and
  * the container magic (compression.rs:282-288).  Needs no GPU. */
 int nh_compress_file(const char *in, const char *out, int codec, uint32_t threads);
 /* The gzip case of that stage on the GPU (nohuman_amd/csrc/nh_deflate.hip; replaces gzip_compress,
@@ -265,8 +271,11 @@ int nh_compress_file(const char *in, const char *out, int codec, uint32_t thread
  * (NOHUMAN_GZIP=host selects the host encoder above).  stats (may be NULL): [0] bytes of the file, [1] microseconds
  * of kernel time (HIP events).  Parity target as above: the decompressed content. */
 int nh_gzip_gpu_file(int32_t device, const void *in, uint64_t n, const char *out, uint64_t *stats);
+/* The same through the encoder's BGZF mode (NH_CODEC_BGZF): a member per 65280-byte region, framed on the GPU, then the EOF
+ * member.  Arguments and stats as nh_gzip_gpu_file. */
+int nh_bgzf_gpu_file(int32_t device, const void *in, uint64_t n, const char *out, uint64_t *stats);
 /* nh_compress_file for a host that keeps the reference's two stages (kraken2-style temporary file, then compress,
- * src/main.rs:342-368) but has the GPU at hand: NH_CODEC_GZIP is encoded on `device` as above, the other codecs as in
+ * src/main.rs:342-368) but has the GPU at hand: NH_CODEC_GZIP and NH_CODEC_BGZF are encoded on `device` as above, the other codecs as in
  * nh_compress_file. */
 int nh_compress_file_device(const char *in, const char *out, int codec, uint32_t threads, int32_t device);
 /* Test / tool support for the multi-threaded gzip input decoder nh_run reads .gz inputs with

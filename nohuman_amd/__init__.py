@@ -6,8 +6,10 @@ include/nohuman_engine.h (csrc/), and a thin Python host mirror of the reference
 loudly when libnohuman_engine.so or a gfx950 device is missing.
 """
 from .engine import Engine, EngineError, RESULT_DTYPE, probe, device_count  # noqa: F401
+from .engine import CODEC_NONE, CODEC_BZIP2, CODEC_GZIP, CODEC_XZ, CODEC_ZSTD, CODEC_BGZF  # noqa: F401
 from .runner import CommandRunner, parse_kraken_stderr, validate_db_directory, \
     parse_confidence_score  # noqa: F401
 
 __all__ = ["Engine", "EngineError", "RESULT_DTYPE", "probe", "device_count", "CommandRunner",
-           "parse_kraken_stderr", "validate_db_directory", "parse_confidence_score"]
+           "parse_kraken_stderr", "validate_db_directory", "parse_confidence_score",
+           "CODEC_NONE", "CODEC_BZIP2", "CODEC_GZIP", "CODEC_XZ", "CODEC_ZSTD", "CODEC_BGZF"]

@@ -7,6 +7,8 @@
 // (nh_codec.h), so that nh_run can feed kept records to it directly.  Parity target is the decompressed content and the container magic
 // (compression.rs:282-288), not byte-identical streams.
 //
+// BGZF (NH_CODEC_BGZF): gzip in bgzip's container -- a member of its own per 65280 bytes of text, see BgzfEncoder.
+//
 // gzip: the input is cut into 512 KiB blocks; each worker deflates one block as a raw deflate stream
 // primed with the previous block's last 32 KiB as dictionary and closed with a sync flush (byte
 // aligned, not final); the blocks are written in order inside ONE gzip member whose CRC-32 is
@@ -231,6 +233,149 @@ private:
     size_t max_inflight_ = 4;
     uint32_t crc_ = 0;
     uint64_t total_ = 0;
+    int rc_ = NH_OK;
+};
+
+// ---- BGZF: what bgzip writes -- a gzip member per 65280 bytes of text (the last one shorter), no dictionary between them,
+// zlib level 6; `threads` workers deflate whole members, written in order; the EOF member closes the file
+struct BgzfJob {
+    unsigned char in[BGZF_TEXT];
+    size_t len = 0;
+    unsigned char out[65536];  // the whole member
+    size_t out_len = 0;
+    bool done = false, failed = false;
+};
+struct BgzfShared {
+    std::mutex mu;
+    std::condition_variable work_cv, done_cv;
+    std::deque<BgzfJob *> pending;
+    bool quit = false;
+};
+
+void bgzf_worker(BgzfShared *sh) {
+    z_stream zs;
+    memset(&zs, 0, sizeof zs);
+    bool init = false;
+    for (;;) {
+        BgzfJob *j;
+        {
+            std::unique_lock<std::mutex> lk(sh->mu);
+            sh->work_cv.wait(lk, [&] { return sh->quit || !sh->pending.empty(); });
+            if (sh->pending.empty()) break;
+            j = sh->pending.front();
+            sh->pending.pop_front();
+        }
+        bool ok = init ? deflateReset(&zs) == Z_OK : deflateInit2(&zs, 6, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) == Z_OK;
+        init = init || ok;
+        if (ok) {
+            // (65280 bytes that do not shrink leave zlib as stored blocks of 5 bytes each: the member stays below 65536)
+            zs.next_in = j->in;
+            zs.avail_in = (uInt)j->len;
+            zs.next_out = j->out + 18;
+            zs.avail_out = (uInt)(sizeof j->out - 26);
+            ok = deflate(&zs, Z_FINISH) == Z_STREAM_END;
+            const size_t body = sizeof j->out - 26 - zs.avail_out;
+            j->out_len = body + 26;
+            memcpy(j->out, BGZF_EOF, 16);  // the fixed part of the header
+            const uint32_t bsize = (uint32_t)j->out_len - 1, crc = crc32_fast(0, j->in, j->len), isize = (uint32_t)j->len;
+            j->out[16] = (unsigned char)bsize;
+            j->out[17] = (unsigned char)(bsize >> 8);
+            for (int i = 0; i < 4; i++) {
+                j->out[18 + body + i] = (unsigned char)(crc >> (8 * i));
+                j->out[22 + body + i] = (unsigned char)(isize >> (8 * i));
+            }
+        }
+        {
+            std::lock_guard<std::mutex> lk(sh->mu);
+            j->failed = !ok;
+            j->done = true;
+        }
+        sh->done_cv.notify_all();
+    }
+    if (init) deflateEnd(&zs);
+}
+
+class BgzfEncoder : public StreamEncoder {
+public:
+    BgzfEncoder(int fd, unsigned threads, const char *name) : fd_(fd), name_(name) {
+        if (threads < 1) threads = 1;
+        for (unsigned i = 0; i < threads; i++) pool_.emplace_back(bgzf_worker, &sh_);
+        max_inflight_ = 8 * (size_t)threads + 2;
+    }
+    ~BgzfEncoder() override {
+        while (!inflight_.empty()) retire_head();  // workers still hold pointers
+        {
+            std::lock_guard<std::mutex> lk(sh_.mu);
+            sh_.quit = true;
+        }
+        sh_.work_cv.notify_all();
+        for (auto &t : pool_) t.join();
+    }
+    int write(const void *p, size_t n) override {
+        const unsigned char *c = (const unsigned char *)p;
+        while (n && rc_ == NH_OK) {
+            if (!cur_) begin_block();
+            const size_t room = BGZF_TEXT - cur_->len;
+            const size_t take = n < room ? n : room;
+            memcpy(cur_->in + cur_->len, c, take);
+            cur_->len += take;
+            c += take;
+            n -= take;
+            if (cur_->len == BGZF_TEXT) submit();
+        }
+        return rc_;
+    }
+    int finish() override {
+        if (cur_ && cur_->len) submit();
+        while (!inflight_.empty()) retire_head();
+        if (rc_ != NH_OK) return rc_;
+        if (!write_all(fd_, BGZF_EOF, sizeof BGZF_EOF)) rc_ = set_error(NH_EIO, "write error on %s", name_.c_str());
+        return rc_;
+    }
+
+private:
+    void begin_block() {
+        if (!spare_.empty()) {
+            cur_ = std::move(spare_.back());
+            spare_.pop_back();
+        } else {
+            cur_.reset(new BgzfJob());
+        }
+        cur_->done = cur_->failed = false;
+        cur_->len = 0;
+    }
+    void submit() {
+        {
+            std::lock_guard<std::mutex> lk(sh_.mu);
+            sh_.pending.push_back(cur_.get());
+        }
+        sh_.work_cv.notify_one();
+        inflight_.push_back(std::move(cur_));
+        while (inflight_.size() >= max_inflight_) retire_head();
+    }
+    void retire_head() {  // wait for the oldest member and write it
+        BgzfJob *j = inflight_.front().get();
+        {
+            std::unique_lock<std::mutex> lk(sh_.mu);
+            sh_.done_cv.wait(lk, [&] { return j->done; });
+        }
+        if (rc_ == NH_OK) {
+            if (j->failed)
+                rc_ = set_error(NH_EIO, "deflate failed on %s", name_.c_str());
+            else if (!write_all(fd_, j->out, j->out_len))
+                rc_ = set_error(NH_EIO, "write error on %s", name_.c_str());
+        }
+        spare_.push_back(std::move(inflight_.front()));
+        inflight_.pop_front();
+    }
+    int fd_;
+    std::string name_;
+    BgzfShared sh_;
+    std::vector<std::thread> pool_;
+    std::deque<std::unique_ptr<BgzfJob>> inflight_;
+    std::vector<std::unique_ptr<BgzfJob>> spare_;
+    std::unique_ptr<BgzfJob> cur_;
+    size_t max_inflight_ = 10;
     int rc_ = NH_OK;
 };
 
@@ -507,10 +652,12 @@ StreamEncoder *make_encoder(int codec, int fd, unsigned threads, const char *nam
     switch (codec) {
         case NH_CODEC_NONE:
             return new PlainEncoder(fd, name);
-        case NH_CODEC_GZIP: {
+        case NH_CODEC_GZIP:
+        case NH_CODEC_BGZF: {  // (the same choice between the two encoders for both containers)
+            const bool bgzf = codec == NH_CODEC_BGZF;
             const char *how = getenv("NOHUMAN_GZIP");
             if (device >= 0 && !(how && !strcmp(how, "host"))) {
-                StreamEncoder *e = make_gpu_gzip_encoder(fd, device, name);
+                StreamEncoder *e = make_gpu_gzip_encoder(fd, device, name, bgzf);
                 if (e) return e;
                 // The encoder's buffers (about 1 GiB of HBM, 0.5 GiB page-locked) could not be had -- a large database
                 // or a small host.  Loud, never silent: one WARN line and the host encoder (the same gzip container,
@@ -523,6 +670,7 @@ StreamEncoder *make_encoder(int codec, int fd, unsigned threads, const char *nam
                 fprintf(stderr, "nohuman: WARN gzip output %s: the GPU encoder could not be set up (%s); encoding on the host\n",
                         name ? name : "", why.c_str());
             }
+            if (bgzf) return new BgzfEncoder(fd, threads, name);
             return new GzipEncoder(fd, threads, name);
         }
         case NH_CODEC_ZSTD:
@@ -552,7 +700,7 @@ StreamEncoder *make_encoder(int codec, int fd, unsigned threads, const char *nam
 int compress_file(const char *in, const char *out, int codec, unsigned threads, int device = -1) {
     if (!in || !out) return set_error(NH_EINVAL, "nh_compress_file: null path");
     if (codec != NH_CODEC_NONE && codec != NH_CODEC_GZIP && codec != NH_CODEC_BZIP2 && codec != NH_CODEC_XZ &&
-        codec != NH_CODEC_ZSTD)
+        codec != NH_CODEC_ZSTD && codec != NH_CODEC_BGZF)
         return set_error(NH_EINVAL, "nh_compress_file: unknown codec %d", codec);
     int fin = ::open(in, O_RDONLY | O_CLOEXEC);
     if (fin < 0) return set_error(NH_EIO, "cannot open %s", in);

@@ -28,9 +28,16 @@ public:
 
 // codec: nh_codec of the C ABI.  The encoder writes to fd (not closed by it); `name` only labels errors.
 // Returns nullptr with the error set when the codec's library cannot be loaded.
-// device >= 0: gzip is encoded on that GPU (nh_deflate.hip) unless NOHUMAN_GZIP=host asks for the host encoder.
+// device >= 0: gzip and BGZF are encoded on that GPU (nh_deflate.hip) unless NOHUMAN_GZIP=host asks for the host encoder.
+// NH_CODEC_BGZF is gzip in bgzip's container: members of 65280 bytes of text (the last one shorter), each with its own
+// size in a 'B' 'C' extra field, its own CRC-32 and ISIZE, then the 28-byte EOF member below; both encoders cut the text
+// at the same places.
 StreamEncoder *make_encoder(int codec, int fd, unsigned threads, const char *name, int device = -1);
-// the GPU gzip encoder itself (nullptr with the error set when its buffers cannot be had)
-StreamEncoder *make_gpu_gzip_encoder(int fd, int device, const char *name);
+// the GPU gzip encoder itself (nullptr with the error set when its buffers cannot be had); bgzf: its BGZF mode
+StreamEncoder *make_gpu_gzip_encoder(int fd, int device, const char *name, bool bgzf = false);
+
+// BGZF: bytes of text per member, and the empty member that ends every file (SAM specification, section 4.1.2)
+constexpr unsigned BGZF_TEXT = 65280;
+constexpr unsigned char BGZF_EOF[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
 }  // namespace nh

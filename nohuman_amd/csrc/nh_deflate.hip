@@ -20,7 +20,14 @@
 //
 // The host side (GpuGzipEncoder, a StreamEncoder of nh_codec.h) stages the writer's spans in page-locked chunks,
 // keeps two chunks in flight, joins the regions' CRC-32s (computed by the same waves, a byte-table look-up a byte) and writes header, streams and
-// trailer: one ordinary gzip member.  Parity target is the decompressed content (compression.rs:282-288), checked
+// trailer: one ordinary gzip member.
+//
+// BGZF mode (NH_CODEC_BGZF; DeflateDev::bgzf): regions of 65280 bytes, what bgzip cuts, and chunks of whole regions; a region's
+// closing block is the FINAL one (k_deflate<WAYS, true>), so its stream is a gzip member's own; k_bgzf_offsets / k_bgzf_pack put
+// the 18-byte header with the member's size ('B' 'C', BSIZE) and CRC-32 + ISIZE around it; the host writes the packed chunks as
+// they come and the 28-byte EOF member last -- no stream header, no joined CRC.  Prices, pilot and device spans as in gzip mode.
+//
+// Parity target is the decompressed content (compression.rs:282-288), checked
 // by zlib and by this repo's own reader in tests/test_gpu_deflate.py.
 #include <errno.h>
 #include <fcntl.h>
@@ -395,7 +402,9 @@ __device__ void finish_block(RegionLds<WAYS> &S, BitOut &bo, const uint32_t *tok
     wave_put2(bo, lane, S.lcode[256], lane == 0 ? S.llen[256] : 0u, 0u, 0u);
 }
 
-template <int WAYS>
+// FINAL (the BGZF mode): the region's stream is a member's whole deflate stream -- the block that closes it is the final one.  A
+// template argument, so that the gzip mode's kernels are the same code objects with or without the mode.
+template <int WAYS, bool FINAL = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_deflate(DeflateArgs a) {
     __shared__ RegionLds<WAYS> S;
     const int lane = (int)threadIdx.x;
@@ -563,11 +572,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void
         atomicAdd(&prof[3], __builtin_amdgcn_s_memtime() - t_all);
         atomicAdd(&prof[4], 1ull);
     }
-    // the region ends on a byte boundary: an empty stored block (BFINAL 0, BTYPE 0, padding, LEN 0, NLEN 0xFFFF)
+    // the region ends on a byte boundary: an empty stored block (BFINAL 0, BTYPE 0, padding, LEN 0, NLEN 0xFFFF).  BGZF: the
+    // same block with BFINAL 1 -- the region's stream is complete and a member of its own
     {
         const uint32_t pos = (bo.out_dw * 32u + bo.obits + 3u) & 7u;
         const uint32_t pad = pos ? 8u - pos : 0u;
-        wave_put2(bo, lane, 0u, lane == 0 ? 3u + pad : 0u, 0xFFFF0000u, lane == 0 ? 32u : 0u);
+        wave_put2(bo, lane, FINAL ? 1u : 0u, lane == 0 ? 3u + pad : 0u, 0xFFFF0000u, lane == 0 ? 32u : 0u);
     }
     if (lane == 0) {
         if (bo.obits) bo.out[bo.out_dw] = S.ob[0];
@@ -608,6 +618,101 @@ __global__ __launch_bounds__(256) void k_deflate_pack(const uint8_t *slots, uint
     uint8_t *d = out + offsets[r];
     const uint32_t n = sizes[r];
     for (uint32_t i = threadIdx.x; i < n; i += 256) d[i] = s[i];
+}
+
+// ---- BGZF: every region a gzip member of its own ------------------------------------------------------------------
+// A member is an 18-byte header (FEXTRA with the 'B' 'C' subfield: BSIZE = the member's size - 1, 16 bits), the region's deflate
+// stream and CRC-32 + ISIZE: 26 bytes around the stream, 65536 at most in all.  A region is 65280 bytes of text (what bgzip
+// cuts), which k_deflate ends after two blocks: the first closes once 32768 bytes are parsed, fewer than 32768 remain for the
+// second.  A block that would not shrink goes out stored, so a block of b bytes of text takes at most b + 5 (3 bits, the
+// padding, LEN / NLEN; a coded block is taken only when it has fewer bits than that), the closing empty stored block 5, a bit
+// position rounded up 1: 65280 + 2 * 5 + 5 + 1 = 65296 bytes of stream, 65322 of member.  The sizes the kernel reports are
+// checked all the same (k_bgzf_offsets counts the members that would not fit; the host fails the run on any): a wrong BSIZE is
+// never written.
+constexpr uint32_t BGZF_REGION = BGZF_TEXT;  // 65280: a multiple of 16, which the CRC's slices need
+constexpr uint32_t BGZF_HEADER = 18, BGZF_FRAME = 26, BGZF_MAX_MEMBER = 65536;
+
+// offsets[i] = bytes of the members before i; offsets[n] = all; offsets[n + 1] = members that do not fit (they count as empty
+// and are not written).  One wave, as k_deflate_offsets.
+__global__ __launch_bounds__(64) void k_bgzf_offsets(const uint32_t *sizes, uint32_t n, uint64_t *offsets) {
+    if (blockIdx.x != 0) return;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t per = (n + 63u) / 64u;
+    const uint32_t lo = lane * per < n ? lane * per : n, hi = lo + per < n ? lo + per : n;
+    uint64_t sum = 0;
+    uint32_t bad = 0;
+    for (uint32_t i = lo; i < hi; i++) {
+        const bool fits = sizes[i] <= BGZF_MAX_MEMBER - BGZF_FRAME;
+        sum += fits ? sizes[i] + BGZF_FRAME : 0u;
+        bad += !fits;
+    }
+    uint64_t incl = sum;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint64_t t = (uint64_t)__shfl_up((long long)incl, o);
+        if ((int)lane >= o) incl += t;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) bad += (uint32_t)__shfl_xor((int)bad, o);
+    uint64_t acc = incl - sum;
+    for (uint32_t i = lo; i < hi; i++) {
+        offsets[i] = acc;
+        acc += sizes[i] <= BGZF_MAX_MEMBER - BGZF_FRAME ? sizes[i] + BGZF_FRAME : 0u;
+    }
+    if (lane == 63) {
+        offsets[n] = incl;
+        offsets[n + 1] = bad;
+    }
+}
+
+// byte p of region r's member: header, the slot's stream, CRC-32, ISIZE
+__device__ __forceinline__ uint32_t bgzf_member_byte(const uint8_t *slot, uint32_t size, uint32_t crc, uint32_t isize, uint32_t p) {
+    if (p < BGZF_HEADER) {
+        // ID1 ID2 CM FLG(FEXTRA) | MTIME 0 | XFL 0, OS unknown | XLEN 6 | 'B' 'C' SLEN 2 | BSIZE
+        const uint32_t bsize = size + BGZF_FRAME - 1u;
+        const uint64_t h0 = 0x00000000'04088B1Full, h1 = 0x00024342'0006FF00ull;
+        return p < 8u ? (uint32_t)(h0 >> (8u * p)) & 0xFFu : p < 16u ? (uint32_t)(h1 >> (8u * (p - 8u))) & 0xFFu : (bsize >> (8u * (p - 16u))) & 0xFFu;
+    }
+    p -= BGZF_HEADER;
+    if (p < size) return slot[p];
+    p -= size;
+    return ((p < 4u ? crc : isize) >> (8u * (p & 3u))) & 0xFFu;
+}
+
+// A block writes region r's member at offsets[r].  The output goes in aligned 16-byte stores; the stream's bytes for one come
+// from the slot (4-byte aligned) as aligned dwords put together by v_alignbyte, the idiom of nh_split.hip's copy.  The pieces
+// that hold header or trailer bytes, and the member's first and last (shared with its neighbours), are stored byte by byte.
+__global__ __launch_bounds__(256) void k_bgzf_pack(const uint8_t *slots, uint32_t slot_stride, const uint32_t *sizes,
+                                                   const uint32_t *crcs, const uint64_t *offsets, uint64_t n, uint32_t region,
+                                                   uint8_t *out) {
+    const uint32_t r = blockIdx.x;
+    const uint32_t size = sizes[r];
+    if (size > BGZF_MAX_MEMBER - BGZF_FRAME) return;  // (counted by k_bgzf_offsets: the run fails)
+    const uint8_t *slot = slots + (size_t)r * slot_stride;
+    const uint64_t o = offsets[r], end = o + size + BGZF_FRAME;
+    const uint64_t body = o + BGZF_HEADER, body_end = body + size;
+    const uint64_t left = n - (uint64_t)r * region;
+    const uint32_t isize = left < region ? (uint32_t)left : region;
+    const uint32_t crc = crcs[r];
+    for (uint64_t D = (o & ~15ull) + 16ull * threadIdx.x; D < end; D += 16ull * 256ull) {
+        if (D >= body && D + 16 <= body_end) {
+            const uint32_t src = (uint32_t)(D - body);
+            const uint32_t *w = reinterpret_cast<const uint32_t *>(slot + (src & ~3u));
+            const uint32_t sh = src & 3u;
+            uint4 v;
+            if (sh == 0) {
+                v = make_uint4(w[0], w[1], w[2], w[3]);
+            } else {  // (w[4] reaches at most 3 bytes past the stream: inside the slot of 65536 bytes, a stream that passed the check has 65510 at most)
+                const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4];
+                v = make_uint4(__builtin_amdgcn_alignbyte(w1, w0, sh), __builtin_amdgcn_alignbyte(w2, w1, sh),
+                               __builtin_amdgcn_alignbyte(w3, w2, sh), __builtin_amdgcn_alignbyte(w4, w3, sh));
+            }
+            *reinterpret_cast<uint4 *>(out + D) = v;
+        } else {
+            for (uint64_t x = D; x < D + 16; x++)
+                if (x >= o && x < end) out[x] = (uint8_t)bgzf_member_byte(slot, size, crc, isize, (uint32_t)(x - o));
+        }
+    }
 }
 
 }  // namespace dfl
@@ -672,7 +777,9 @@ struct DeflateDev {  // device side of one encoder: buffers for chunks in flight
         }();
         return r;
     }
-    const uint32_t REGION = region_bytes();
+    uint32_t REGION = region_bytes();
+    bool bgzf = false;      // BGZF mode: regions of 65280 bytes, each a member of its own (NOHUMAN_GZIP_REGION does not apply)
+    uint32_t full_pow = 0;  // x^(8 * REGION) in the CRC's field: joins a whole region's CRC-32 to the stream's
     static constexpr int NBUF = 2;
     static constexpr uint32_t PILOT_REGIONS = 16;
     int device = -1;
@@ -706,14 +813,18 @@ struct DeflateDev {  // device side of one encoder: buffers for chunks in flight
 
     int fail(hipError_t e, const char *what) { return set_error(NH_EDEVICE, "gzip encoder: %s: %s", what, hipGetErrorString(e)); }
 
-    int init(int dev) {
+    int init(int dev, bool bgzf_mode = false) {
         device = dev;
+        bgzf = bgzf_mode;
+        if (bgzf) REGION = dfl::BGZF_REGION;
+        full_pow = dfl::gf2_xpow8(REGION);
         hipError_t e = dev_set(device);
         if (e != hipSuccess) return fail(e, "hipSetDevice");
         if ((e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking)) != hipSuccess) return fail(e, "stream");
         if ((e = hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking)) != hipSuccess) return fail(e, "stream");
         if ((e = hipStreamCreateWithFlags(&out_stream, hipStreamNonBlocking)) != hipSuccess) return fail(e, "stream");
         chunk = chunk_bytes_now();
+        if (bgzf) chunk -= chunk % REGION;  // whole regions: a chunk's end never makes a short member in mid-file
         max_regions = (uint32_t)((chunk + REGION - 1) / REGION);
         slot_stride = REGION + 256;
         for (Buf &b : buf) {
@@ -724,7 +835,7 @@ struct DeflateDev {  // device side of one encoder: buffers for chunks in flight
             if ((e = dev_malloc((void **)&b.d_sizes, max_regions * sizeof(uint32_t))) != hipSuccess) return fail(e, "sizes");
             if ((e = dev_malloc((void **)&b.d_crcs, max_regions * sizeof(uint32_t))) != hipSuccess) return fail(e, "crcs");
             if (!(b.h_crcs = (uint32_t *)host_alloc(max_regions * sizeof(uint32_t)))) return set_error(NH_EOOM, "gzip encoder: no memory for the staging buffers");
-            if ((e = dev_malloc((void **)&b.d_offsets, (max_regions + 1) * sizeof(uint64_t))) != hipSuccess) return fail(e, "offsets");
+            if ((e = dev_malloc((void **)&b.d_offsets, (max_regions + 2) * sizeof(uint64_t))) != hipSuccess) return fail(e, "offsets");
             if ((e = dev_malloc((void **)&b.d_out, (size_t)max_regions * slot_stride)) != hipSuccess) return fail(e, "packed output");
             if (!(b.h_out = (uint8_t *)host_alloc((size_t)max_regions * slot_stride)) || !(b.h_total = (uint64_t *)host_alloc(64)))
                 return set_error(NH_EOOM, "gzip encoder: no memory for the staging buffers");
@@ -821,6 +932,16 @@ struct DeflateDev {  // device side of one encoder: buffers for chunks in flight
         const hipError_t e = hipStreamSynchronize(copy_stream);
         return e == hipSuccess ? NH_OK : fail(e, "copy");
     }
+    template <bool FINAL>
+    void launch_deflate_as(const DeflateArgs &a, uint32_t nr) {
+        if (gzip_ways() == 4)
+            hipLaunchKernelGGL((dfl::k_deflate<4, FINAL>), dim3(nr), dim3(64), 0, stream, a);
+        else if (gzip_ways() == 6)
+            hipLaunchKernelGGL((dfl::k_deflate<6, FINAL>), dim3(nr), dim3(64), 0, stream, a);
+        else
+            hipLaunchKernelGGL((dfl::k_deflate<8, FINAL>), dim3(nr), dim3(64), 0, stream, a);
+    }
+    void launch_deflate(const DeflateArgs &a, uint32_t nr) { bgzf ? launch_deflate_as<true>(a, nr) : launch_deflate_as<false>(a, nr); }
     // the first regions of a stream under both candidate price sets; the smaller result's prices start the stream
     int pilot(Buf &b) {
         static const char *force = getenv("NOHUMAN_GZIP_PRICES");  // "0" / "1": no pilot, that candidate (tuning)
@@ -844,12 +965,7 @@ struct DeflateDev {  // device side of one encoder: buffers for chunks in flight
                 a.prior = d_prior + (2 + c) * dfl::PRIOR_BYTES;
                 a.prior_out = nullptr;
                 a.prof = nullptr;
-                if (gzip_ways() == 4)
-                    hipLaunchKernelGGL(dfl::k_deflate<4>, dim3(nr), dim3(64), 0, stream, a);
-                else if (gzip_ways() == 6)
-                    hipLaunchKernelGGL(dfl::k_deflate<6>, dim3(nr), dim3(64), 0, stream, a);
-                else
-                    hipLaunchKernelGGL(dfl::k_deflate<8>, dim3(nr), dim3(64), 0, stream, a);
+                launch_deflate(a, nr);
             }
             hipError_t e = hipGetLastError();
             if (e != hipSuccess) return fail(e, "launch");
@@ -897,20 +1013,21 @@ struct DeflateDev {  // device side of one encoder: buffers for chunks in flight
         a.prior_out = d_prior + ((chunks + 1) & 1) * dfl::PRIOR_BYTES;
         a.prof = d_prof;
         (void)hipEventRecord(b.k0, stream);
-        if (gzip_ways() == 4)
-            hipLaunchKernelGGL(dfl::k_deflate<4>, dim3(b.n_regions), dim3(64), 0, stream, a);
-        else if (gzip_ways() == 6)
-            hipLaunchKernelGGL(dfl::k_deflate<6>, dim3(b.n_regions), dim3(64), 0, stream, a);
-        else
-            hipLaunchKernelGGL(dfl::k_deflate<8>, dim3(b.n_regions), dim3(64), 0, stream, a);
-        hipLaunchKernelGGL(dfl::k_deflate_offsets, dim3(1), dim3(64), 0, stream, b.d_sizes, b.n_regions, b.d_offsets);
-        hipLaunchKernelGGL(dfl::k_deflate_pack, dim3(b.n_regions), dim3(256), 0, stream, b.d_slots, slot_stride, b.d_sizes,
-                           b.d_offsets, b.d_out);
+        launch_deflate(a, b.n_regions);
+        if (bgzf) {
+            hipLaunchKernelGGL(dfl::k_bgzf_offsets, dim3(1), dim3(64), 0, stream, b.d_sizes, b.n_regions, b.d_offsets);
+            hipLaunchKernelGGL(dfl::k_bgzf_pack, dim3(b.n_regions), dim3(256), 0, stream, b.d_slots, slot_stride, b.d_sizes, b.d_crcs,
+                               b.d_offsets, (uint64_t)b.fill, REGION, b.d_out);
+        } else {
+            hipLaunchKernelGGL(dfl::k_deflate_offsets, dim3(1), dim3(64), 0, stream, b.d_sizes, b.n_regions, b.d_offsets);
+            hipLaunchKernelGGL(dfl::k_deflate_pack, dim3(b.n_regions), dim3(256), 0, stream, b.d_slots, slot_stride, b.d_sizes,
+                               b.d_offsets, b.d_out);
+        }
         (void)hipEventRecord(b.k1, stream);
         if ((e = hipGetLastError()) != hipSuccess) return fail(e, "launch");
-        if ((e = hipMemcpyAsync(b.h_total, b.d_offsets + b.n_regions, sizeof(uint64_t), hipMemcpyDeviceToHost, stream)) != hipSuccess)
+        if ((e = hipMemcpyAsync(b.h_total, b.d_offsets + b.n_regions, (bgzf ? 2 : 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, stream)) != hipSuccess)
             return fail(e, "D2H");
-        if ((e = hipMemcpyAsync(b.h_crcs, b.d_crcs, b.n_regions * sizeof(uint32_t), hipMemcpyDeviceToHost, stream)) != hipSuccess)
+        if (!bgzf && (e = hipMemcpyAsync(b.h_crcs, b.d_crcs, b.n_regions * sizeof(uint32_t), hipMemcpyDeviceToHost, stream)) != hipSuccess)
             return fail(e, "D2H");
         if ((e = hipEventRecord(b.done, stream)) != hipSuccess) return fail(e, "event");
         b.submitted = b.fill;
@@ -928,14 +1045,28 @@ struct DeflateDev {  // device side of one encoder: buffers for chunks in flight
         if (hipEventElapsedTime(&ms, b.k0, b.k1) == hipSuccess) kernel_ms += ms;
         const uint64_t total = *b.h_total;
         if (total > (uint64_t)max_regions * slot_stride) return set_error(NH_EDEVICE, "gzip encoder: impossible stream size");
+        if (bgzf && b.h_total[1])
+            return set_error(NH_EDEVICE, "gzip encoder: %llu BGZF member(s) of this chunk would be larger than 65536 bytes",
+                             (unsigned long long)b.h_total[1]);
         if ((e = hipMemcpyAsync(b.h_out, b.d_out, total, hipMemcpyDeviceToHost, out_stream)) != hipSuccess) return fail(e, "D2H");
         if ((e = hipStreamSynchronize(out_stream)) != hipSuccess) return fail(e, "D2H");
         // NOHUMAN_GZIP_VERIFY=1: the chunk's stream is inflated again on the host (zlib, raw deflate) and its length and
         // CRC-32 are compared with the text's -- a paranoid mode, one core at ~0.5 GB/s of text
         static const bool verify = getenv("NOHUMAN_GZIP_VERIFY") != nullptr;
+        if (bgzf) {  // (every member carries its own CRC-32: nothing to join)
+            if (verify) {
+                const int vrc = verify_members(b, total);
+                if (vrc != NH_OK) return vrc;
+            }
+            b.in_flight = false;
+            b.fill = 0;
+            b.staged_from = 0;
+            *len = (size_t)total;
+            return NH_OK;
+        }
         uint32_t crc_before = *crc;
         {
-            static const uint32_t full = dfl::gf2_xpow8(REGION);
+            const uint32_t full = full_pow;
             uint32_t c = *crc;
             size_t left = b.submitted;
             for (uint32_t r = 0; r < b.n_regions; r++) {
@@ -976,6 +1107,43 @@ struct DeflateDev {  // device side of one encoder: buffers for chunks in flight
         *len = (size_t)total;
         return NH_OK;
     }
+    // NOHUMAN_GZIP_VERIFY=1 in BGZF mode: the chunk's members one by one -- header and BSIZE, the stream inflated by zlib, its
+    // length and CRC-32 against the trailer's (which the GPU computed from the text) and against the region's length
+    int verify_members(const Buf &b, uint64_t total) {
+        std::vector<unsigned char> back(dfl::BGZF_REGION + 1);
+        uint64_t at = 0, left = b.submitted;
+        for (uint32_t r = 0; r < b.n_regions; r++) {
+            const unsigned char *m = b.h_out + at;
+            static const unsigned char head[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
+            if (at + dfl::BGZF_FRAME > total || memcmp(m, head, sizeof head) != 0)
+                return set_error(NH_EDEVICE, "gzip encoder: verification failed (member %u: no BGZF header)", r);
+            const uint64_t msize = (uint64_t)(m[16] | (m[17] << 8)) + 1;
+            if (msize < dfl::BGZF_FRAME || at + msize > total)
+                return set_error(NH_EDEVICE, "gzip encoder: verification failed (member %u: BSIZE %llu)", r, (unsigned long long)msize - 1);
+            const uint64_t want = left < REGION ? left : REGION;
+            z_stream zs;
+            memset(&zs, 0, sizeof zs);
+            if (inflateInit2(&zs, -15) != Z_OK) return set_error(NH_EIO, "gzip encoder: verify: inflateInit2 failed");
+            zs.next_in = (Bytef *)(m + dfl::BGZF_HEADER);
+            zs.avail_in = (uInt)(msize - dfl::BGZF_FRAME);
+            zs.next_out = back.data();
+            zs.avail_out = (uInt)back.size();
+            const int zrc = inflate(&zs, Z_FINISH);
+            const uint64_t got = back.size() - zs.avail_out;
+            const uInt unread = zs.avail_in;
+            inflateEnd(&zs);
+            uint32_t t[2];
+            memcpy(t, m + msize - 8, 8);
+            const uint32_t vcrc = crc32_fast(0, back.data(), (size_t)got);
+            if (zrc != Z_STREAM_END || unread != 0 || got != want || t[1] != (uint32_t)want || t[0] != vcrc)
+                return set_error(NH_EDEVICE, "gzip encoder: verification failed (member %u: zlib %d, %llu of %llu bytes, CRC %08x / %08x)", r,
+                                 zrc, (unsigned long long)got, (unsigned long long)want, vcrc, t[0]);
+            at += msize;
+            left -= want;
+        }
+        if (at != total) return set_error(NH_EDEVICE, "gzip encoder: verification failed (%llu bytes behind the last member)", (unsigned long long)(total - at));
+        return NH_OK;
+    }
 };
 
 bool write_fd(int fd, const void *p, size_t n) {
@@ -999,9 +1167,10 @@ public:
         stop_writer();
         dev_.destroy();
     }
-    int init(int device) {
-        const int rc = dev_.init(device);
+    int init(int device, bool bgzf = false) {
+        const int rc = dev_.init(device, bgzf);
         if (rc != NH_OK) return rc;
+        if (bgzf) return NH_OK;  // (every member has its own header)
         static const unsigned char header[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0, 0, 3};  // no name, no mtime, unix
         if (!write_fd(fd_, header, sizeof header)) return rc_ = set_error(NH_EIO, "write error on %s", name_.c_str());
         return NH_OK;
@@ -1062,7 +1231,7 @@ public:
             tail[2 + i] = (unsigned char)(crc_ >> (8 * i));
             tail[6 + i] = (unsigned char)((uint32_t)total_ >> (8 * i));
         }
-        if (!write_fd(fd_, tail, sizeof tail)) rc_ = set_error(NH_EIO, "write error on %s", name_.c_str());
+        if (dev_.bgzf ? !write_fd(fd_, BGZF_EOF, sizeof BGZF_EOF) : !write_fd(fd_, tail, sizeof tail)) rc_ = set_error(NH_EIO, "write error on %s", name_.c_str());
         if (getenv("NOHUMAN_TRACE"))
             fprintf(stderr, "[nohuman trace] gzip encoder %s: write() %.3f s (of it: waiting for chunks + D2H %.3f, file %.3f), settle %.3f s, "
                             "kernels %.3f s, %.2f GB in, %.2f GB out\n",
@@ -1160,9 +1329,9 @@ private:
 
 }  // namespace
 
-StreamEncoder *make_gpu_gzip_encoder(int fd, int device, const char *name) {
+StreamEncoder *make_gpu_gzip_encoder(int fd, int device, const char *name, bool bgzf) {
     GpuGzipEncoder *e = new GpuGzipEncoder(fd, name);
-    if (e->init(device) != NH_OK) {
+    if (e->init(device, bgzf) != NH_OK) {
         delete e;
         return nullptr;
     }
@@ -1173,21 +1342,28 @@ StreamEncoder *make_gpu_gzip_encoder(int fd, int device, const char *name) {
 
 // One gzip member of a host buffer through the GPU encoder, to a file: what tests and bench.py drive.
 // stats: [0] bytes written, [1] kernel microseconds (HIP events around the three kernels of every chunk).
-extern "C" int nh_gzip_gpu_file(int32_t device, const void *in, uint64_t n, const char *out_path, uint64_t *stats) {
-    if ((!in && n) || !out_path) return nh::set_error(NH_EINVAL, "nh_gzip_gpu_file: null argument");
+static int gpu_file(const char *entry, bool bgzf, int32_t device, const void *in, uint64_t n, const char *out_path, uint64_t *stats) {
+    if ((!in && n) || !out_path) return nh::set_error(NH_EINVAL, "%s: null argument", entry);
     int fd = ::open(out_path, O_WRONLY | O_CREAT | O_TRUNC | O_CLOEXEC, 0666);
     if (fd < 0) return nh::set_error(NH_EIO, "cannot create %s", out_path);
     int rc = NH_OK;
     {
         nh::GpuGzipEncoder enc(fd, out_path);
-        rc = enc.init(device);
+        rc = enc.init(device, bgzf);
         if (rc == NH_OK) rc = enc.write(in, (size_t)n);
         if (rc == NH_OK) rc = enc.finish();
         if (stats) {
-            stats[0] = enc.bytes_out() + 20;
+            stats[0] = enc.bytes_out() + (bgzf ? sizeof nh::BGZF_EOF : 20);  // (gzip: header and trailer; BGZF: the EOF member)
             stats[1] = (uint64_t)(enc.kernel_ms() * 1000.0);
         }
     }
     if (::close(fd) != 0 && rc == NH_OK) rc = nh::set_error(NH_EIO, "write error on %s", out_path);
     return rc;
+}
+extern "C" int nh_gzip_gpu_file(int32_t device, const void *in, uint64_t n, const char *out_path, uint64_t *stats) {
+    return gpu_file("nh_gzip_gpu_file", false, device, in, n, out_path, stats);
+}
+// The same text as BGZF: a member per 65280 bytes, the EOF member last.  stats as above.
+extern "C" int nh_bgzf_gpu_file(int32_t device, const void *in, uint64_t n, const char *out_path, uint64_t *stats) {
+    return gpu_file("nh_bgzf_gpu_file", true, device, in, n, out_path, stats);
 }

@@ -1816,8 +1816,10 @@ private:
         if (data_at) *data_at = h + 12 + xlen;
         return bsize;
     }
-    // the chunks' starts of a piece from the members' headers: chunk c starts at the first member whose data begin in stretch c
-    bool bgzf_starts(DevSet &d, const PieceJob &j, uint32_t n_str) {
+    // the chunks' starts of a piece from the members' headers: chunk c starts at the first member whose data begin in stretch c;
+    // *next_bit = where the first member behind the piece's stretches begins (NONE: there is none)
+    bool bgzf_starts(DevSet &d, const PieceJob &j, uint32_t n_str, uint64_t *next_bit) {
+        *next_bit = NONE;
         for (uint32_t c = 0; c < n_str; c++) d.h_start_[c] = NONE;
         d.h_start_[0] = j.first_bit;
         // the member the stream stands at: walk on from the last one known
@@ -1836,8 +1838,12 @@ private:
         for (;;) {
             uint64_t at = 0;
             const uint64_t bs = bgzf_block_size(h, &at);
-            if (!bs || at >= end_byte) break;
+            if (!bs) break;
             const uint64_t bit = 8 * (at - j.a_byte);
+            if (at >= end_byte) {
+                *next_bit = bit;
+                break;
+            }
             const uint32_t c = (uint32_t)(bit / (8 * (uint64_t)stretch_));
             if (c > 0 && c < n_str && d.h_start_[c] == NONE && bit > j.first_bit) d.h_start_[c] = bit;
             h += bs;
@@ -1914,8 +1920,14 @@ private:
         if (trace_) (void)hipEventRecord(d.ev_[0], stream);
         bool by_headers = false;
         if (bgzf_ && !spec && d.h_start_ && j.first_bit != NONE) {
-            by_headers = bgzf_starts(d, j, n_str);
+            uint64_t next_bit = NONE;
+            by_headers = bgzf_starts(d, j, n_str, &next_bit);
             j.by_headers = by_headers;
+            // The piece ends where the first member behind its stretches begins, so that the next piece starts at a member too.
+            // "The first block boundary behind the stretches" is that place in bgzip's files (a member is one block); this repo's
+            // encoder writes three blocks a member, and a piece that ended between two of them would leave the next one without
+            // a header at its start -- and the rest of the file to the block search.
+            if (by_headers && !j.limit_bits && next_bit != NONE && next_bit <= valid_bits) j.end_bit = end_bit = next_bit;
             if (by_headers) GZA_TRY(hipMemcpyAsync(d.d_start_, d.h_start_, (size_t)n_str * 8, hipMemcpyHostToDevice, stream));
             else bgzf_ = false;  // (the headers do not go on as they began: an ordinary gzip stream from here on)
         }

@@ -1009,7 +1009,8 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
     }
     OutFile o1, o2, ok, h1, h2;  // (h1, h2: the classified records of a split run)
     int rc;
-    if (a->out_codec < NH_CODEC_NONE || a->out_codec > NH_CODEC_ZSTD)
+    const bool gzip_family = a->out_codec == NH_CODEC_GZIP || a->out_codec == NH_CODEC_BGZF;  // the codecs the GPU encodes
+    if (a->out_codec < NH_CODEC_NONE || a->out_codec > NH_CODEC_BGZF)
         return set_error(NH_EINVAL, "nh_run: unknown out_codec %d", a->out_codec);
     // gzip output is encoded on the GPU (nh_deflate.hip); with two devices each mate file has its own
     // (the two are opened side by side: a GPU encoder takes 70 ms to set up -- page-locked buffers, a trial of its prices)
@@ -1070,7 +1071,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
     // take the kept records from HBM (a record that needs reformatting -- CRLF, "+id" -- makes the writer fetch its batch).
     // A masked run builds every output record on the device (the split side as well): only --output lines need the bytes.
     const bool host_text_wanted = mask ? rs.want_k || G > 1
-                                       : !(a->out_codec == NH_CODEC_GZIP && o1.enc && o1.enc->takes_device_spans() &&
+                                       : !(gzip_family && o1.enc && o1.enc->takes_device_spans() &&
                                            (!rs.paired || (o2.enc && o2.enc->takes_device_spans()))) ||
                                              rs.want_k || a->keep_human != 0 || G > 1;  // (G > 1: a batch's slot and its file's encoder may sit on different GPUs)
     const uint32_t flags = rs.paired ? NH_FLAG_PAIRED : 0;
@@ -1148,7 +1149,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
         const char *how = getenv("NOHUMAN_GZ_READER");
         const bool off = how && (!strcmp(how, "host") || !strcmp(how, "device-text"));
         const bool named = how && !strcmp(how, "device");
-        const bool by_host = a->keep_human == 0 && !(a->out_codec == NH_CODEC_GZIP && o1.enc && o1.enc->takes_device_spans() &&
+        const bool by_host = a->keep_human == 0 && !(gzip_family && o1.enc && o1.enc->takes_device_spans() &&
                                                      (!rs.paired || (o2.enc && o2.enc->takes_device_spans())));
         // (a masked run whose outputs are written by the host: every byte leaves through it, as the kept reads of a normal run
         // do -- the same choice; with GPU gzip outputs nothing does and the reader on the GPU is taken, profiles/mask_e2e.txt)

@@ -216,6 +216,7 @@ struct Args {
     std::string out1, out2, database, db_version, kraken_output, kraken_report;
     std::string human_out1, human_out2;  // split run: the human reads in the same pass (nh_run_split)
     bool has_human_out1 = false, has_human_out2 = false;
+    bool bgzf = false;  // gzip outputs in bgzip's blocked form (NH_CODEC_BGZF)
     bool mask = false;  // masked run: every read written, the human ones' bases as N (nh_run_mask)
     bool has_out1 = false, has_out2 = false, check = false, download = false, list = false, human = false;
     bool has_type = false;
@@ -237,6 +238,7 @@ static void usage(FILE *f) {
           "      --db-version <VERSION>   Name of the database version to use\n"
           "      --list-db-versions       List available database versions and exit\n"
           "  -F, --output-type <FORMAT>   Output compression format. u: uncompressed; b: Bzip2; g: Gzip; x: Xz (Lzma); z: Zstd\n"
+          "      --bgzf                   Write gzip outputs as BGZF (blocked gzip, as bgzip writes it); needs the output format g\n"
           "  -t, --threads <INT>          Number of threads to use [default: 1]\n"
           "  -H, --human                  Output human reads instead of removing them\n"
           "      --human-out1 <PATH>      Also write the human reads, in the same run, to this file (as -H would)\n"
@@ -304,6 +306,7 @@ static Args parse_args(int argc, char **argv) {
         else if (s == "--human-out1") { a.human_out1 = val(); a.has_human_out1 = true; }
         else if (s == "--human-out2") { a.human_out2 = val(); a.has_human_out2 = true; }
         else if (s == "--mask") a.mask = true;
+        else if (s == "--bgzf") a.bgzf = true;
         else if (s == "-C" || s == "--conf") {
             std::string t = val();
             char *end;
@@ -372,6 +375,12 @@ static std::string default_out_name(const std::string &in, Codec out_codec) {
 
 int main(int argc, char **argv) {
     Args args = parse_args(argc, argv);
+    if (args.bgzf && !args.input.empty()) {  // BGZF is a form of gzip: any other resolved output format is an argument error
+        const Codec c = args.has_type ? args.type : args.has_out1 ? codec_from_path(args.out1) : codec_from_magic(args.input[0]);
+        if (c != C_GZ)
+            arg_error("the argument '--bgzf' needs the output format g (Gzip), but the output format is %s",
+                      c == C_NONE ? "u (uncompressed)" : c == C_BZ2 ? "b (Bzip2)" : c == C_XZ ? "x (Xz)" : "z (Zstd)");
+    }
     if (args.has_human_out1 && !args.input.empty()) {  // a human output equal to a DEFAULT output name: an argument error as well
         const Codec c = args.has_type ? args.type : args.has_out1 ? codec_from_path(args.out1) : codec_from_magic(args.input[0]);
         const std::string o1 = args.has_out1 ? args.out1 : default_out_name(args.input[0], c);
@@ -444,7 +453,7 @@ int main(int argc, char **argv) {
     // encoder: no temporary file, one pass.
     std::string out1 = args.has_out1 ? args.out1 : default_out_name(args.input[0], out_codec);
     std::string out2 = paired ? (args.has_out2 ? args.out2 : default_out_name(args.input[1], out_codec)) : "";
-    const int codec = out_codec == C_GZ ? NH_CODEC_GZIP : out_codec == C_BZ2 ? NH_CODEC_BZIP2 : out_codec == C_XZ ? NH_CODEC_XZ
+    const int codec = out_codec == C_GZ ? (args.bgzf ? NH_CODEC_BGZF : NH_CODEC_GZIP) : out_codec == C_BZ2 ? NH_CODEC_BZIP2 : out_codec == C_XZ ? NH_CODEC_XZ
                     : out_codec == C_ZST ? NH_CODEC_ZSTD : NH_CODEC_NONE;
     INFO(args.mask ? "Masking human reads..." : args.human ? "Keeping human reads..." : "Removing human reads...");
 

@@ -14,6 +14,8 @@ TAXON_AMBIGUOUS = 0xFFFFFFFF
 TAXON_MATE_BORDER = 0xFFFFFFFE
 FLAG_PAIRED = 1
 FLAG_LONG = 2
+# nh_codec of include/nohuman_engine.h: what out_codec takes
+CODEC_NONE, CODEC_BZIP2, CODEC_GZIP, CODEC_XZ, CODEC_ZSTD, CODEC_BGZF = 0, 1, 2, 3, 4, 5
 
 
 class EngineError(RuntimeError):
@@ -43,7 +45,8 @@ def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
     """nh_run: whole run, database loaded into every listed device (default: all visible).  human_out1 (and, paired,
     human_out2) given: nh_run_split -- the non-human reads go to out1 / out2 and, in the same pass, the human reads to
     human_out1 / human_out2 exactly as a keep_human run would write them.  mask: nh_run_mask -- every read goes to
-    out1 / out2 in input order, a human read's bases replaced by N (with human_out1 / human_out2 as well, if given)."""
+    out1 / out2 in input order, a human read's bases replaced by N (with human_out1 / human_out2 as well, if given).
+    out_codec: the container of every output, one of the CODEC_* numbers (CODEC_BGZF: gzip in bgzip's blocked form)."""
     a = _lib.nh_run_args()
     a.db_dir = os.fsencode(db_dir)
     a.in1 = os.fsencode(in1)

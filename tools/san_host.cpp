@@ -5,6 +5,7 @@
 //   san_host gunzip file.gz threads chunk_bytes   ParallelGunzip against zlib byte for byte, then the block reader over the file
 //   san_host gzip file threads                    the host gzip encoder (make_encoder, the pool of block workers) on the file's
 //                                                 bytes, written in odd-sized pieces; zlib inflates the result back to the input
+//   san_host bgzf file threads                    the same through the host BGZF encoder (a member per 65280 bytes)
 //   san_host ranges file.gz threads cell chunk every   RangeGunzip (the hybrid reader's host lane, round 6): the file as a chain of cells,
 //                                                 every `every`-th by a fresh RangeGunzip decoded ahead and stitched, against zlib
 #include <stdio.h>
@@ -25,7 +26,7 @@
 #include "nh_inflate.h"
 #include "nohuman_engine.h"
 
-static int gzip_mode(const char *path, unsigned threads) {
+static int gzip_mode(const char *path, unsigned threads, int codec = NH_CODEC_GZIP) {
     std::vector<uint8_t> data;
     {
         FILE *f = fopen(path, "rb");
@@ -38,7 +39,7 @@ static int gzip_mode(const char *path, unsigned threads) {
     const std::string out = std::string(path) + ".san.gz";
     const int fd = open(out.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0600);
     if (fd < 0) return 2;
-    std::unique_ptr<nh::StreamEncoder> enc(nh::make_encoder(NH_CODEC_GZIP, fd, threads, out.c_str(), -1));
+    std::unique_ptr<nh::StreamEncoder> enc(nh::make_encoder(codec, fd, threads, out.c_str(), -1));
     if (!enc) {
         printf("no encoder: %s\n", nh_last_error());
         return 1;
@@ -129,6 +130,7 @@ static int ranges_mode(const char *path, unsigned threads, uint64_t cell, uint64
 
 int main(int argc, char **argv) {
     if (argc >= 4 && !strcmp(argv[1], "gzip")) return gzip_mode(argv[2], (unsigned)atoi(argv[3]));
+    if (argc >= 4 && !strcmp(argv[1], "bgzf")) return gzip_mode(argv[2], (unsigned)atoi(argv[3]), NH_CODEC_BGZF);
     if (argc >= 7 && !strcmp(argv[1], "ranges"))
         return ranges_mode(argv[2], (unsigned)atoi(argv[3]), (uint64_t)atoll(argv[4]), (uint64_t)atoll(argv[5]), (unsigned)atoi(argv[6]));
     if (argc < 5 || strcmp(argv[1], "gunzip")) return 2;

@@ -28,7 +28,7 @@ hipError_t dev_malloc(void **p, size_t) {
 }
 hipError_t dev_set(int) { return hipErrorNoDevice; }
 bool dev_gunzip_wants(const char *) { return false; }
-StreamEncoder *make_gpu_gzip_encoder(int, int, const char *) {
+StreamEncoder *make_gpu_gzip_encoder(int, int, const char *, bool) {
     set_error(NH_EDEVICE, "no device in the sanitizer build");
     return nullptr;
 }
