@@ -332,6 +332,33 @@ int nh_run_engine_split(nh_engine *e, const nh_run_args *args, const char *human
 int nh_run_mask(const nh_run_args *args, const char *human_out1, const char *human_out2, nh_stats *stats);
 int nh_run_engine_mask(nh_engine *e, const nh_run_args *args, const char *human_out1, const char *human_out2,
                        nh_stats *stats);
+/*
+ * Extended run: one entry for everything a run can write beside out1 / out2.  With calls and human_ids NULL it is exactly the
+ * entry its other fields select (mask: nh_run_mask; a human output: nh_run_split; neither: nh_run).  The two read lists are plain
+ * text whatever out_codec is, one line per fragment, in input order, no header line, built in the GPU's memory behind the
+ * classifier in the same pass -- without the per-k-mer taxon lists and without the batches' text on the host that
+ * kraken_output costs -- and mean the same in a normal, a keep_human, a split and a masked run:
+ *   calls      a line for EVERY fragment:
+ *                <C|U> \t <id> \t <taxid> \t <len>  or  <len1>|<len2> \t <total_kmers> \t <clade_hits> \t <hit_groups> \n
+ *              columns 1-4 are byte for byte columns 1-4 of the fragment's kraken_output line (<id>: mate 1's header from the
+ *              byte behind '@' / '>' to the first space, tab or '\r'; a paired run drops a trailing "/1" or "/2" from an id
+ *              longer than two bytes; <taxid>: the external id of the call, 0 for U), columns 5-7 the fragment's nh_result as
+ *              the classifier left it.  clade_hits / total_kmers is the confidence that nh_run_args.confidence thresholds:
+ *              a threshold can be chosen from this table without running again.
+ *   human_ids  <id> \n for every classified fragment, the same id; a run without human reads writes an empty file.
+ * NH_EINVAL, before any device is touched: struct_size smaller than the struct; every check of nh_run_split / nh_run_mask for
+ * the fields they share; calls or human_ids that names an input (the same path, or the same device and inode), out1, out2,
+ * kraken_output, report, a human output, or each other.
+ */
+typedef struct {
+    uint32_t struct_size;      /* sizeof(nh_run_extras) of the caller */
+    int32_t mask;              /* 1: as nh_run_mask */
+    const char *human_out1, *human_out2; /* as nh_run_split / nh_run_mask */
+    const char *calls;         /* calls table, NULL = none */
+    const char *human_ids;     /* ids of the classified fragments, NULL = none */
+} nh_run_extras;
+int nh_run_ex(const nh_run_args *args, const nh_run_extras *extras, nh_stats *stats);
+int nh_run_engine_ex(nh_engine *e, const nh_run_args *args, const nh_run_extras *extras, nh_stats *stats);
 
 #ifdef __cplusplus
 }

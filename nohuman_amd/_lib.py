@@ -47,6 +47,11 @@ class nh_run_args(C.Structure):
                 ("device_ids", C.POINTER(C.c_int32)), ("out_codec", C.c_int32), ("codec_threads", C.c_uint32)]
 
 
+class nh_run_extras(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("mask", C.c_int32), ("human_out1", C.c_char_p),
+                ("human_out2", C.c_char_p), ("calls", C.c_char_p), ("human_ids", C.c_char_p)]
+
+
 # every symbol include/nohuman_engine.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -93,6 +98,8 @@ SYMBOLS = {
     "nh_run_engine_split": (C.c_int, [_P, C.POINTER(nh_run_args), C.c_char_p, C.c_char_p, C.POINTER(nh_stats)]),
     "nh_run_mask": (C.c_int, [C.POINTER(nh_run_args), C.c_char_p, C.c_char_p, C.POINTER(nh_stats)]),
     "nh_run_engine_mask": (C.c_int, [_P, C.POINTER(nh_run_args), C.c_char_p, C.c_char_p, C.POINTER(nh_stats)]),
+    "nh_run_ex": (C.c_int, [C.POINTER(nh_run_args), C.POINTER(nh_run_extras), C.POINTER(nh_stats)]),
+    "nh_run_engine_ex": (C.c_int, [_P, C.POINTER(nh_run_args), C.POINTER(nh_run_extras), C.POINTER(nh_stats)]),
     "nh_allreduce_counters": (C.c_int, [C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_uint64), C.c_char_p,
                                         C.c_size_t]),
 }

@@ -986,6 +986,8 @@ int check_error_flag(Engine *e) {
             return set_error(NH_EDEVICE, "classified-out builder: a record lies outside its batch's text or output buffer");
         if (flag & 8)
             return set_error(NH_EDEVICE, "mask builder: a record lies outside its batch's text or output buffer");
+        if (flag & 16)
+            return set_error(NH_EDEVICE, "read-list builder: a record lies outside its batch's text or output buffer");
         return set_error(NH_ECAPACITY, "a fragment hit more than 2048 distinct taxa");
     }
     return NH_OK;

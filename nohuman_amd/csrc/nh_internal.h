@@ -164,6 +164,27 @@ struct MaskArgs {
 };
 uint64_t mask_blocks(uint64_t n);
 hipError_t launch_mask(const MaskArgs &a, hipStream_t stream);
+// The read lists of one batch built in HBM (nh_calls.hip; nh_run_ex's calls table and human ids): out[0] receives a table line
+// for every fragment, out[1] the id of every fragment with call != 0; total[o] their bytes, total[2 + o] their lines.
+struct CallsArgs {
+    const char *text;         // the batch's text (d_text), ntext bytes
+    uint64_t ntext;
+    const uint32_t *seq_len;  // n * mates sequence lengths, as classified
+    const uint32_t *rec;      // n * mates {header start (absolute), header length, qualities start (absolute), length}
+    const uint32_t *idlen;    // n: the length of mate 1's id (RecRef::idlen)
+    const nh_result *res;     // n results
+    const uint64_t *ext;      // internal -> external taxon id, n_ext entries
+    uint64_t n_ext, n, nblk;  // nblk = calls_blocks(n)
+    int mates;
+    int want[2];              // per output: asked for (an output that is not builds nothing: total 0)
+    char *out[2];
+    uint64_t cap[2];          // bytes of out[o]
+    uint64_t *blk;            // 4 * nblk words of scratch
+    uint64_t *total;          // 4 words
+    int *error;               // the engine's sticky error word (bit 16: a record outside its text or buffer)
+};
+uint64_t calls_blocks(uint64_t n);
+hipError_t launch_calls(const CallsArgs &a, hipStream_t stream);
 // buffers kept between the runs of a process (nh_run.hip: page-locked batch text; nh_gunzip.hip: the gzip reader's HBM and
 // staging): emptied when an engine is closed
 void run_cache_trim();

@@ -355,6 +355,15 @@ struct Slot {  // pinned host + device buffers of one in-flight batch
     char *d_mout[2] = {nullptr, nullptr}, *h_mout[2] = {nullptr, nullptr};
     size_t cap_mout[2] = {0, 0}, cap_mhost[2] = {0, 0}, cap_mblk = 0;
     hipEvent_t mev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around the mask builder's launches
+    // read lists (nh_run_ex: calls table [0], human ids [1]): mate 1's id lengths beside the record table, the two texts
+    // built in HBM, the builder's scratch, the totals {bytes[2], lines[2]} that come back with the results, and the page-locked
+    // copies the writer hands to the files
+    uint32_t *h_idl = nullptr;
+    void *d_idl = nullptr, *d_cblk = nullptr;
+    char *d_cout[2] = {nullptr, nullptr}, *h_cout[2] = {nullptr, nullptr};
+    size_t cap_cout[2] = {0, 0}, cap_chost[2] = {0, 0}, cap_idl = 0, cap_cblk = 0;
+    uint64_t *h_ctotal = nullptr;
+    hipEvent_t cev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around the list builder's launches
 };
 
 static int slot_reserve(Slot &s, size_t ntext, size_t nfrag, size_t ntaxa) {
@@ -455,6 +464,55 @@ static int slot_reserve_mask(Slot &s, size_t n, int mates, const size_t out_cap[
     return NH_OK;
 }
 
+// the read lists' buffers of a slot: records and id lengths of n fragments (mates per fragment), out_cap[o] bytes of list text
+static int slot_reserve_calls(Slot &s, size_t n, int mates, const size_t out_cap[2]) {
+    auto grow = [](size_t need) { return need + need / 4 + 4096; };
+    if (!s.h_ctotal && host_malloc((void **)&s.h_ctotal, 64, hipHostMallocDefault) != hipSuccess)
+        return set_error(NH_EOOM, "cannot allocate batch buffers");
+    if (n * mates > s.cap_rec) {
+        if (s.h_rec) (void)hipHostFree(s.h_rec);
+        if (s.d_rec) (void)hipFree(s.d_rec);
+        s.h_rec = nullptr, s.d_rec = nullptr;
+        s.cap_rec = grow(n * mates);
+        if (host_malloc((void **)&s.h_rec, s.cap_rec * 16, hipHostMallocDefault) != hipSuccess || dev_malloc(&s.d_rec, s.cap_rec * 16) != hipSuccess)
+            return set_error(NH_EOOM, "cannot allocate batch buffers (%zu records)", s.cap_rec);
+    }
+    if (n > s.cap_idl) {
+        if (s.h_idl) (void)hipHostFree(s.h_idl);
+        if (s.d_idl) (void)hipFree(s.d_idl);
+        s.h_idl = nullptr, s.d_idl = nullptr;
+        s.cap_idl = grow(n);
+        if (host_malloc((void **)&s.h_idl, s.cap_idl * 4, hipHostMallocDefault) != hipSuccess || dev_malloc(&s.d_idl, s.cap_idl * 4) != hipSuccess)
+            return set_error(NH_EOOM, "cannot allocate batch buffers (%zu id lengths)", s.cap_idl);
+    }
+    const size_t words = 4 * calls_blocks(n) + 4;  // (block offsets and line counts of both outputs, totals: CallsArgs)
+    if (words > s.cap_cblk) {
+        if (s.d_cblk) (void)hipFree(s.d_cblk);
+        s.cap_cblk = grow(words);
+        if (dev_malloc(&s.d_cblk, s.cap_cblk * 8) != hipSuccess) return set_error(NH_EOOM, "cannot allocate batch buffers");
+    }
+    for (int o = 0; o < 2; o++)
+        if (out_cap[o] > s.cap_cout[o]) {
+            if (s.d_cout[o]) (void)hipFree(s.d_cout[o]);
+            s.cap_cout[o] = grow(out_cap[o]);
+            if (dev_malloc((void **)&s.d_cout[o], s.cap_cout[o]) != hipSuccess)
+                return set_error(NH_EOOM, "cannot allocate read-list buffers (%zu bytes)", s.cap_cout[o]);
+        }
+    return NH_OK;
+}
+
+// page-locked room for `n` bytes of read list o on the host (the writer's copy for the file)
+static int slot_reserve_calls_host(Slot &s, int o, size_t n) {
+    if (n <= s.cap_chost[o]) return NH_OK;
+    if (s.h_cout[o]) (void)hipHostFree(s.h_cout[o]);
+    s.cap_chost[o] = n + n / 4 + 4096;
+    if (host_malloc((void **)&s.h_cout[o], s.cap_chost[o], hipHostMallocDefault) != hipSuccess) {
+        s.h_cout[o] = nullptr, s.cap_chost[o] = 0;
+        return set_error(NH_EOOM, "cannot allocate read-list buffers (%zu bytes)", n);
+    }
+    return NH_OK;
+}
+
 // page-locked room for `n` bytes of mate m's masked text on the host (the writer's copy for host encoders)
 static int slot_reserve_mask_host(Slot &s, int m, size_t n) {
     if (n <= s.cap_mhost[m]) return NH_OK;
@@ -486,7 +544,11 @@ static void slot_free(Slot &s) {
         if (p) (void)hipHostFree(p);
     for (void *p : {s.d_rec, s.d_hblk, (void *)s.d_hout[0], (void *)s.d_hout[1], s.d_mblk, (void *)s.d_mout[0], (void *)s.d_mout[1]})
         if (p) (void)hipFree(p);
-    for (hipEvent_t ev : {s.hev[0], s.hev[1], s.mev[0], s.mev[1]})
+    for (void *p : {(void *)s.h_idl, (void *)s.h_cout[0], (void *)s.h_cout[1], (void *)s.h_ctotal})
+        if (p) (void)hipHostFree(p);
+    for (void *p : {s.d_idl, s.d_cblk, (void *)s.d_cout[0], (void *)s.d_cout[1]})
+        if (p) (void)hipFree(p);
+    for (hipEvent_t ev : {s.hev[0], s.hev[1], s.mev[0], s.mev[1], s.cev[0], s.cev[1]})
         if (ev) (void)hipEventDestroy(ev);
     for (void *p : {(void *)s.h_off, (void *)s.h_len, (void *)s.h_res, (void *)s.h_taxa, (void *)s.h_taxa_off, (void *)s.h_flag})
         if (p) (void)hipHostFree(p);
@@ -575,6 +637,9 @@ struct RunState {
     // masked runs (NOHUMAN_TRACE): records masked and written, the bytes the mask builder made, its kernel time
     uint64_t mask_masked = 0, mask_records = 0, mask_bytes = 0, mask_nblk = 0, mask_fast = 0;
     double mask_kernel_ms = 0;
+    // read lists (NOHUMAN_TRACE): lines and bytes of the calls table [0] and the human ids [1], the builder's kernel time
+    uint64_t list_lines[2] = {0, 0}, list_bytes[2] = {0, 0};
+    double list_kernel_ms = 0;
     std::atomic<uint64_t> text_fetched{0};
     std::vector<uint64_t> dev_counts;  // per device {fragments, classified, bases, 0} as the writer saw them (checker)
     std::vector<uint64_t *> d_run_counters;  // per device: the counters the classify kernels of THIS run add to (HBM)
@@ -961,13 +1026,44 @@ static int check_mask_args(const nh_run_args *a, const char *h1, const char *h2)
     return NH_OK;
 }
 
+// nh_run_ex's read lists (the calls table, the human ids), checked before any device is touched: a list names no input and no
+// other output of the run (the same path, or the same device and inode)
+static int check_list_args(const nh_run_args *a, const char *h1, const char *h2, const char *calls, const char *ids) {
+    if (!a) return set_error(NH_EINVAL, "nh_run_ex: null arguments");
+    const char *const what[2] = {"calls", "human_ids"};
+    const char *const list[2] = {calls, ids};
+    for (int o = 0; o < 2; o++) {
+        const char *l = list[o];
+        if (!l) continue;
+        if (!l[0]) return set_error(NH_EINVAL, "nh_run_ex: %s is an empty path", what[o]);
+        struct stat sl;
+        const bool ls = stat(l, &sl) == 0 && S_ISREG(sl.st_mode);
+        auto same = [&](const char *p) {
+            struct stat sp;
+            return p && p[0] && (!strcmp(p, l) || (ls && stat(p, &sp) == 0 && sp.st_dev == sl.st_dev && sp.st_ino == sl.st_ino));
+        };
+        for (const char *p : {a->in1, a->in2})
+            if (same(p)) return set_error(NH_EINVAL, "nh_run_ex: %s %s is the input %s", what[o], l, p);
+        for (const char *p : {a->out1, a->out2, a->kraken_output, a->report, h1, h2})
+            if (same(p)) return set_error(NH_EINVAL, "nh_run_ex: %s %s is also the output %s", what[o], l, p);
+        if (o == 1 && same(calls)) return set_error(NH_EINVAL, "nh_run_ex: calls and human_ids are the same file %s", l);
+    }
+    return NH_OK;
+}
+
 // hout1 set: a split run (nh_run_split) -- a->keep_human is 0, hout1 / hout2 receive the classified records
 // mask: a masked run (nh_run_mask) -- a->keep_human is 0, out1 / out2 receive every record, a classified one's bases as 'N'
+// calls / ids set (nh_run_ex): the calls table / the human read ids, built in HBM beside whatever else the run writes
 int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_stats *stats, const char *hout1 = nullptr,
-                const char *hout2 = nullptr, bool mask = false) {
+                const char *hout2 = nullptr, bool mask = false, const char *calls = nullptr, const char *ids = nullptr) {
     if (!a || !a->in1 || !a->out1) return set_error(NH_EINVAL, "nh_run: in1 and out1 are required");
     if (engines.empty()) return set_error(NH_EINVAL, "nh_run: no engine");
     const bool split = hout1 != nullptr;
+    const bool lists = calls || ids;
+    if (lists) {
+        const int vrc = check_list_args(a, hout1, hout2, calls, ids);
+        if (vrc) return vrc;
+    }
     if (mask) {
         const int vrc = check_mask_args(a, hout1, hout2);
         if (vrc) return vrc;
@@ -975,11 +1071,12 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
     if (split) {
         const int vrc = check_split_args(a, hout1, hout2, mask ? "nh_run_mask" : "nh_run_split");
         if (vrc) return vrc;
+    }
+    if (split || lists)
         for (Engine *e : engines) {
             const int erc = ensure_device_external(e);
             if (erc) return erc;
         }
-    }
     RunState rs;
     rs.a = a;
     rs.engines = engines;
@@ -998,7 +1095,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
     }
     // outputs are created with O_TRUNC before the first input byte is read: an output that IS an input
     // (same device and inode) would be emptied -- refuse (the CLI host stages its outputs and renames)
-    for (const char *o : {a->out1, a->out2, rs.want_k ? a->kraken_output : nullptr, a->report, hout1, hout2}) {
+    for (const char *o : {a->out1, a->out2, rs.want_k ? a->kraken_output : nullptr, a->report, hout1, hout2, calls, ids}) {
         struct stat so;
         if (!o || !o[0] || stat(o, &so) != 0 || !S_ISREG(so.st_mode)) continue;
         for (const char *p : {a->in1, a->in2}) {
@@ -1047,6 +1144,9 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
         if (rch2) return set_error(rch2, "%s", errh2.c_str());
     }
     if (rs.want_k && (rc = ok.open(a->kraken_output))) return rc;
+    OutFile oc, oi;  // the read lists: plain text whatever the codec of the records
+    if (calls && (rc = oc.open(calls))) return rc;
+    if (ids && (rc = oi.open(ids))) return rc;
 
     // fragments per batch: ~96 MB of sequence, at most 262144; both readers cut at the same record
     // count so that paired batches stay aligned (a byte budget only cuts single-end batches)
@@ -1115,7 +1215,9 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
             (split && getenv("NOHUMAN_TRACE") &&
              (hipEventCreate(&slots[i].hev[0]) != hipSuccess || hipEventCreate(&slots[i].hev[1]) != hipSuccess)) ||
             (mask && getenv("NOHUMAN_TRACE") &&
-             (hipEventCreate(&slots[i].mev[0]) != hipSuccess || hipEventCreate(&slots[i].mev[1]) != hipSuccess))) {
+             (hipEventCreate(&slots[i].mev[0]) != hipSuccess || hipEventCreate(&slots[i].mev[1]) != hipSuccess)) ||
+            (lists && getenv("NOHUMAN_TRACE") &&
+             (hipEventCreate(&slots[i].cev[0]) != hipSuccess || hipEventCreate(&slots[i].cev[1]) != hipSuccess))) {
             for (auto &s : slots) slot_free(s);
             free_run_counters();
             return set_error(NH_EDEVICE, "cannot create streams");
@@ -1219,6 +1321,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
     struct FlushJob {
         Batch b;
         Spans s1, s2, sk, hs1, hs2;  // (hs1, hs2: a split run's classified records, one span a mate)
+        Spans sc, si;                // (the batch's part of the calls table and of the human ids, one span each)
         bool valid = false;  // (false: the run had failed when the batch arrived -- only its buffers go back)
     };
     BoundedQueue<Batch> wq((size_t)(NS * G));
@@ -1286,6 +1389,8 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 int wrc = o1.flush(j->s1);
                 if (!wrc && rs.want_k) wrc = ok.flush(j->sk);
                 if (!wrc && split) wrc = h1.flush(j->hs1);
+                if (!wrc && calls) wrc = oc.flush(j->sc);
+                if (!wrc && ids) wrc = oi.flush(j->si);
                 if (rs.paired) {
                     std::unique_lock<std::mutex> lk(w2_mu);
                     w2_cv.wait(lk, [&] { return w2_state == 2; });
@@ -1397,6 +1502,24 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                     }
                     if (split)
                         for (size_t i = 0; i < b.n; i++) rs.human_records += s.h_res[i].call != 0;
+                    // the read lists: exactly the built bytes, copied to the slot's page-locked memory, one span a file
+                    if (lists && s.cev[1]) {
+                        float ms = 0;
+                        if (hipEventElapsedTime(&ms, s.cev[0], s.cev[1]) == hipSuccess) rs.list_kernel_ms += ms;
+                    }
+                    for (int o = 0; lists && o < 2 && !wrc; o++) {
+                        const size_t tot = (size_t)s.h_ctotal[o];
+                        rs.list_bytes[o] += tot;
+                        rs.list_lines[o] += s.h_ctotal[2 + o];
+                        if (!tot) continue;
+                        wrc = slot_reserve_calls_host(s, o, tot);
+                        if (!wrc && hipMemcpy(s.h_cout[o], s.d_cout[o], tot, hipMemcpyDeviceToHost) != hipSuccess)
+                            wrc = set_error(NH_EDEVICE, "fetching a batch's read list from the device failed");
+                        rs.text_fetched += tot;
+                        Spans &ls = o ? j->si : j->sc;
+                        ls.iov.push_back({(void *)s.h_cout[o], tot});
+                        ls.is_scratch.push_back(0);
+                    }
                     clk.ns[ST_WFORMAT] += StageClock::now() - c2;
                     j->s1 = std::move(o1.sp);
                     j->s2 = std::move(o2.sp);
@@ -1519,6 +1642,14 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 const size_t out_cap[2] = {len1 + b.n + 64, len2 + b.n + 64};
                 rc = slot_reserve_mask(s, b.n, mates, out_cap);
             }
+            if (!rc && lists) {
+                // a table line: "C\t", the id, then at most 1 + 20 + 1 + 21 + 1 + 3 * 11 bytes of numbers, separators and
+                // the newline; an id line: the id and a newline
+                uint64_t idsum = 0;
+                for (size_t i = 0; i < b.n; i++) idsum += b.h1->recs[b.off1 + i].idlen;
+                const size_t out_cap[2] = {calls ? (size_t)idsum + b.n * 79 + 64 : 0, ids ? (size_t)idsum + b.n + 64 : 0};
+                rc = slot_reserve_calls(s, b.n, mates, out_cap);
+            }
             if (rc) {
                 rs.fail(rc, g_last_error);
                 wq.push(std::move(b));
@@ -1531,7 +1662,8 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 s.h_off[i * mates] = r1.s;
                 s.h_len[i * mates] = r1.slen;
                 nbases += r1.slen;
-                if (split || mask) {
+                if (lists) s.h_idl[i] = r1.idlen;
+                if (split || mask || lists) {
                     uint32_t *hr = s.h_rec + 4 * i * mates;
                     hr[0] = r1.h, hr[1] = r1.hlen, hr[2] = r1.q, hr[3] = r1.qlen;
                     if (rs.paired) {
@@ -1585,8 +1717,10 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 he = hipMemcpyAsync(s.d_len, s.h_len, b.n * mates * 4, hipMemcpyHostToDevice, s.stream);
             if (he == hipSuccess && rs.want_k)
                 he = hipMemcpyAsync(s.d_taxa_off, s.h_taxa_off, (b.n + 1) * 8, hipMemcpyHostToDevice, s.stream);
-            if (he == hipSuccess && (split || mask))
+            if (he == hipSuccess && (split || mask || lists))
                 he = hipMemcpyAsync(s.d_rec, s.h_rec, b.n * mates * 16, hipMemcpyHostToDevice, s.stream);
+            if (he == hipSuccess && lists)
+                he = hipMemcpyAsync(s.d_idl, s.h_idl, b.n * 4, hipMemcpyHostToDevice, s.stream);
             if (he != hipSuccess) {
                 rs.fail(NH_EDEVICE, std::string("H2D: ") + hipGetErrorString(he));
             } else {
@@ -1595,6 +1729,31 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                                      rs.want_k ? s.d_taxa : nullptr, rs.want_k ? s.d_taxa_off : nullptr,
                                      rs.d_run_counters[(size_t)(si / NS)], s.stream, s.d_len, ntext);
                 if (rc) rs.fail(rc, g_last_error);
+            }
+            uint64_t *d_ctotal = nullptr;
+            if (!rs.failed() && lists) {  // the calls table and the human ids, built behind the classifier on the same stream
+                CallsArgs ca{};
+                ca.text = (const char *)s.d_text;
+                ca.ntext = ntext;
+                ca.seq_len = (const uint32_t *)s.d_len;
+                ca.rec = (const uint32_t *)s.d_rec;
+                ca.idlen = (const uint32_t *)s.d_idl;
+                ca.res = (const nh_result *)s.d_res;
+                ca.ext = s.e->d_external;
+                ca.n_ext = s.e->external.size();
+                ca.n = b.n;
+                ca.nblk = calls_blocks(b.n);
+                ca.mates = mates;
+                ca.want[0] = calls != nullptr;
+                ca.want[1] = ids != nullptr;
+                for (int o = 0; o < 2; o++) ca.out[o] = s.d_cout[o], ca.cap[o] = s.cap_cout[o];
+                ca.blk = (uint64_t *)s.d_cblk;
+                ca.total = d_ctotal = (uint64_t *)s.d_cblk + 4 * ca.nblk;
+                ca.error = s.e->d_error + LAUNCH_SLOTS;
+                if (s.cev[0]) (void)hipEventRecord(s.cev[0], s.stream);
+                he = launch_calls(ca, s.stream);
+                if (s.cev[1] && he == hipSuccess) he = hipEventRecord(s.cev[1], s.stream);
+                if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("read-list builder: ") + hipGetErrorString(he));
             }
             uint64_t *d_htotal = nullptr;
             if (!rs.failed() && split) {  // the classified records of both mates, built behind the classifier on the same stream
@@ -1655,6 +1814,8 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                     he = hipMemcpyAsync(s.h_htotal, d_htotal, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
                 if (he == hipSuccess && mask)
                     he = hipMemcpyAsync(s.h_htotal + 2, d_mtotal, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
+                if (he == hipSuccess && lists)
+                    he = hipMemcpyAsync(s.h_ctotal, d_ctotal, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
                 if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("D2H: ") + hipGetErrorString(he));
             }
             batch_no++;
@@ -1707,6 +1868,10 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                         (unsigned long long)rs.text_fetched.load(), rs.mask_kernel_ms,
                         rs.mask_kernel_ms > 0 ? (double)rs.mask_bytes / (rs.mask_kernel_ms * 1e6) : 0.0,
                         (unsigned long long)rs.mask_fast, (unsigned long long)rs.mask_nblk);
+            if (lists)
+                fprintf(stderr, "[nohuman trace] calls: %llu lines, %llu bytes; ids: %llu lines, %llu bytes built on device; %llu fetched to host; builder kernels %.3f ms\n",
+                        (unsigned long long)rs.list_lines[0], (unsigned long long)rs.list_bytes[0], (unsigned long long)rs.list_lines[1],
+                        (unsigned long long)rs.list_bytes[1], (unsigned long long)rs.text_fetched.load(), rs.list_kernel_ms);
             if (g_pageable_batches.load())
                 fprintf(stderr, "[nohuman trace] %d batch buffers could not be page-locked (pageable memory used)\n",
                         g_pageable_batches.load());
@@ -1810,6 +1975,8 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
         if (rch2) return set_error(rch2, "%s", errh2.c_str());
     }
     if (rs.want_k && (rc = ok.close())) return rc;
+    if (calls && (rc = oc.close())) return rc;
+    if (ids && (rc = oi.close())) return rc;
     if (stats) {
         nh_stats st;
         memset(&st, 0, sizeof st);
@@ -1824,9 +1991,23 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
 }
 
 int run_engine(Engine *e, const nh_run_args *a, nh_stats *stats, const char *hout1 = nullptr, const char *hout2 = nullptr,
-               bool mask = false) {
+               bool mask = false, const char *calls = nullptr, const char *ids = nullptr) {
     std::vector<Engine *> v{e};
-    return run_engines(v, a, stats, hout1, hout2, mask);
+    return run_engines(v, a, stats, hout1, hout2, mask, calls, ids);
+}
+
+// nh_run_ex's arguments, checked before any device is touched: the struct, what nh_run_split / nh_run_mask check for the fields
+// they share, and the read lists
+int check_extras(const nh_run_args *a, const nh_run_extras *x) {
+    if (!a) return set_error(NH_EINVAL, "nh_run_ex: null arguments");
+    if (!x) return set_error(NH_EINVAL, "nh_run_ex: null extras");
+    if (x->struct_size < sizeof(nh_run_extras))
+        return set_error(NH_EINVAL, "nh_run_ex: struct_size %u is smaller than nh_run_extras (%zu bytes)", x->struct_size, sizeof(nh_run_extras));
+    int rc = NH_OK;
+    if (x->mask) rc = check_mask_args(a, x->human_out1, x->human_out2);
+    else if (x->human_out1 || x->human_out2) rc = check_split_args(a, x->human_out1, x->human_out2);
+    if (rc) return rc;
+    return check_list_args(a, x->human_out1, x->human_out2, x->calls, x->human_ids);
 }
 
 }  // namespace nh
@@ -1850,6 +2031,14 @@ int nh_run_engine_mask(nh_engine *e, const nh_run_args *args, const char *human_
     if (rc) return rc;
     if (!e) return nh::set_error(NH_EINVAL, "null engine");
     return nh::run_engine((nh::Engine *)e, args, stats, human_out1, human_out2, true);
+}
+
+int nh_run_engine_ex(nh_engine *e, const nh_run_args *args, const nh_run_extras *extras, nh_stats *stats) {
+    const int rc = nh::check_extras(args, extras);
+    if (rc) return rc;
+    if (!e) return nh::set_error(NH_EINVAL, "null engine");
+    return nh::run_engine((nh::Engine *)e, args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls,
+                          extras->human_ids);
 }
 
 int nh_fastx_scan(const char *path, uint64_t *n_records, uint64_t *n_bases, uint64_t *digest) {
@@ -1888,7 +2077,8 @@ int nh_fastx_scan(const char *path, uint64_t *n_records, uint64_t *n_bases, uint
 
 // Whole run on one or several devices: the database is loaded into every device's HBM, batches go
 // round-robin, outputs stay in input order, the counts are summed on the host.
-static int run_devices(const nh_run_args *args, nh_stats *stats, const char *hout1, const char *hout2, bool mask = false) {
+static int run_devices(const nh_run_args *args, nh_stats *stats, const char *hout1, const char *hout2, bool mask = false,
+                       const char *calls = nullptr, const char *ids = nullptr) {
     if (!args || !args->db_dir) return nh::set_error(NH_EINVAL, "nh_run: db_dir is required");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -1924,7 +2114,7 @@ static int run_devices(const nh_run_args *args, nh_stats *stats, const char *hou
     }
     const double t_load = since(t_begin);
     const auto t_run = std::chrono::steady_clock::now();
-    if (!rc) rc = nh::run_engines(engines, args, stats, hout1, hout2, mask);
+    if (!rc) rc = nh::run_engines(engines, args, stats, hout1, hout2, mask, calls, ids);
     const double s_run = since(t_run);
     std::string keep = nh::g_last_error;
     const auto t_close = std::chrono::steady_clock::now();
@@ -1948,6 +2138,12 @@ int nh_run_mask(const nh_run_args *args, const char *human_out1, const char *hum
     const int rc = nh::check_mask_args(args, human_out1, human_out2);  // (before any device is touched)
     if (rc) return rc;
     return run_devices(args, stats, human_out1, human_out2, true);
+}
+
+int nh_run_ex(const nh_run_args *args, const nh_run_extras *extras, nh_stats *stats) {
+    const int rc = nh::check_extras(args, extras);  // (before any device is touched)
+    if (rc) return rc;
+    return run_devices(args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls, extras->human_ids);
 }
 
 }  // extern "C"

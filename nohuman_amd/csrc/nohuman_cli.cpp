@@ -218,6 +218,7 @@ struct Args {
     bool has_human_out1 = false, has_human_out2 = false;
     bool bgzf = false;  // gzip outputs in bgzip's blocked form (NH_CODEC_BGZF)
     bool mask = false;  // masked run: every read written, the human ones' bases as N (nh_run_mask)
+    std::string calls, human_ids;  // read lists (nh_run_ex): a table line per read; the ids of the human reads
     bool has_out1 = false, has_out2 = false, check = false, download = false, list = false, human = false;
     bool has_type = false;
     Codec type = C_NONE;
@@ -247,6 +248,8 @@ static void usage(FILE *f) {
           "  -C, --conf <[0, 1]>          Kraken2 minimum confidence score [default: 0.0]\n"
           "  -k, --kraken-output <FILE>   Write the Kraken2 read classification output to a file\n"
           "  -r, --kraken-report <FILE>   Write the Kraken2 report with aggregate counts/clade to file\n"
+          "      --calls <FILE>           Write a table with one line per read: C/U, id, taxid, length(s), k-mers, clade hits (hits / k-mers is the confidence -C thresholds), hit groups\n"
+          "      --human-ids <FILE>       Write the ids of the human reads, one per line\n"
           "  -v, --verbose                Set the logging level to verbose\n"
           "  -h, --help                   Print help\n"
           "  -V, --version                Print version\n",
@@ -316,6 +319,8 @@ static Args parse_args(int argc, char **argv) {
             a.confidence = c;
         } else if (s == "-k" || s == "--kraken-output") a.kraken_output = val();
         else if (s == "-r" || s == "--kraken-report") a.kraken_report = val();
+        else if (s == "--calls") a.calls = val();
+        else if (s == "--human-ids") a.human_ids = val();
         else if (s == "-v" || s == "--verbose") g_verbose = true;
         else if (s == "-h" || s == "--help") { usage(stdout); exit(0); }
         else if (s == "-V" || s == "--version") { puts("nohuman 0.5.1 (MI355X engine)"); exit(0); }
@@ -345,6 +350,8 @@ static Args parse_args(int argc, char **argv) {
         if (a.has_human_out2 && a.human_out1 == a.human_out2)
             arg_error("the arguments '--human-out1 <PATH>' and '--human-out2 <PATH>' name the same file: %s", a.human_out1.c_str());
     }
+    if (!a.calls.empty() && a.calls == a.human_ids)
+        arg_error("the arguments '--calls <FILE>' and '--human-ids <FILE>' name the same file: %s", a.calls.c_str());
     return a;
 }
 
@@ -488,6 +495,10 @@ int main(int argc, char **argv) {
     std::vector<std::pair<std::string, std::string>> staged_files;
     if (split) staged_files.push_back({args.human_out1, hpart1});
     if (split && paired) staged_files.push_back({args.human_out2, hpart2});
+    const bool lists = !args.calls.empty() || !args.human_ids.empty();
+    const std::string cpart = args.calls.empty() ? "" : staged(args.calls), ipart = args.human_ids.empty() ? "" : staged(args.human_ids);
+    if (!args.calls.empty()) staged_files.push_back({args.calls, cpart});
+    if (!args.human_ids.empty()) staged_files.push_back({args.human_ids, ipart});
     staged_files.push_back({out1, part1});
     if (paired) staged_files.push_back({out2, part2});
     auto unlink_staged = [&] {
@@ -515,7 +526,17 @@ int main(int argc, char **argv) {
     }
     nh_stats st;
     const char *hp1 = split ? hpart1.c_str() : nullptr, *hp2 = split && paired ? hpart2.c_str() : nullptr;
-    const int run_rc = args.mask ? nh_run_mask(&ra, hp1, hp2, &st) : split ? nh_run_split(&ra, hp1, hp2, &st) : nh_run(&ra, &st);
+    nh_run_extras rx;
+    memset(&rx, 0, sizeof rx);
+    rx.struct_size = (uint32_t)sizeof rx;
+    rx.mask = args.mask ? 1 : 0;
+    rx.human_out1 = hp1, rx.human_out2 = hp2;
+    rx.calls = args.calls.empty() ? nullptr : cpart.c_str();
+    rx.human_ids = args.human_ids.empty() ? nullptr : ipart.c_str();
+    const int run_rc = lists       ? nh_run_ex(&ra, &rx, &st)
+                       : args.mask ? nh_run_mask(&ra, hp1, hp2, &st)
+                       : split     ? nh_run_split(&ra, hp1, hp2, &st)
+                                   : nh_run(&ra, &st);
     if (run_rc != 0) {
         std::string msg = nh_last_error();
         // nothing half-written stays behind, and nothing this run did not create is touched
@@ -553,6 +574,8 @@ int main(int argc, char **argv) {
     }
     if (!args.kraken_output.empty() && args.kraken_output != "/dev/null")
         INFO("Kraken output file written to: %s", quoted(args.kraken_output).c_str());
+    if (!args.calls.empty()) INFO("Calls table written to: %s", quoted(args.calls).c_str());
+    if (!args.human_ids.empty()) INFO("Human read ids written to: %s", quoted(args.human_ids).c_str());
     if (!args.kraken_report.empty()) INFO("Kraken report file written to: %s", quoted(args.kraken_report).c_str());
     INFO("Done.");
     return 0;

@@ -41,12 +41,16 @@ def probe() -> str:
 
 def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None, confidence: float = 0.0,
         threads: int = 1, keep_human: bool = False, device_ids=None, out_codec: int = 0,
-        codec_threads: int = 0, human_out1=None, human_out2=None, mask: bool = False) -> "_lib.nh_stats":
+        codec_threads: int = 0, human_out1=None, human_out2=None, mask: bool = False, calls=None,
+        human_ids=None) -> "_lib.nh_stats":
     """nh_run: whole run, database loaded into every listed device (default: all visible).  human_out1 (and, paired,
     human_out2) given: nh_run_split -- the non-human reads go to out1 / out2 and, in the same pass, the human reads to
     human_out1 / human_out2 exactly as a keep_human run would write them.  mask: nh_run_mask -- every read goes to
     out1 / out2 in input order, a human read's bases replaced by N (with human_out1 / human_out2 as well, if given).
-    out_codec: the container of every output, one of the CODEC_* numbers (CODEC_BGZF: gzip in bgzip's blocked form)."""
+    out_codec: the container of every output, one of the CODEC_* numbers (CODEC_BGZF: gzip in bgzip's blocked form).
+    calls / human_ids (nh_run_ex; any kind of run): two plain-text read lists built on the GPU in the same pass -- calls: a
+    line per fragment, C/U, id, taxid, length(s), total_kmers, clade_hits, hit_groups, tab-separated (clade_hits /
+    total_kmers is the confidence that `confidence` thresholds); human_ids: the id of every human fragment."""
     a = _lib.nh_run_args()
     a.db_dir = os.fsencode(db_dir)
     a.in1 = os.fsencode(in1)
@@ -69,7 +73,10 @@ def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
         a.n_devices = 0
         a.device_ids = None
     s = _lib.nh_stats()
-    if mask:
+    if calls is not None or human_ids is not None:
+        x = _extras(mask, human_out1, human_out2, calls, human_ids)
+        _check(_lib.lib().nh_run_ex(C.byref(a), C.byref(x), C.byref(s)))
+    elif mask:
         _check(_lib.lib().nh_run_mask(C.byref(a), _path_or_none(human_out1), _path_or_none(human_out2), C.byref(s)))
     elif human_out1 is not None or human_out2 is not None:
         _check(_lib.lib().nh_run_split(C.byref(a), _path_or_none(human_out1), _path_or_none(human_out2), C.byref(s)))
@@ -80,6 +87,17 @@ def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
 
 def _path_or_none(p):
     return os.fsencode(p) if p is not None else None
+
+
+def _extras(mask, human_out1, human_out2, calls, human_ids) -> "_lib.nh_run_extras":
+    x = _lib.nh_run_extras()
+    x.struct_size = C.sizeof(_lib.nh_run_extras)
+    x.mask = int(bool(mask))
+    x.human_out1 = _path_or_none(human_out1)
+    x.human_out2 = _path_or_none(human_out2)
+    x.calls = _path_or_none(calls)
+    x.human_ids = _path_or_none(human_ids)
+    return x
 
 
 def device_count() -> int:
@@ -276,9 +294,10 @@ class Engine:
     # -- whole run -----------------------------------------------------------------------------
     def run(self, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
             confidence: float = 0.0, threads: int = 1, keep_human: bool = False, out_codec: int = 0,
-            codec_threads: int = 0, human_out1=None, human_out2=None, mask: bool = False) -> _lib.nh_stats:
-        """nh_run_engine; with human_out1 (and, paired, human_out2): nh_run_engine_split; mask: nh_run_engine_mask -- as
-        run() above."""
+            codec_threads: int = 0, human_out1=None, human_out2=None, mask: bool = False, calls=None,
+            human_ids=None) -> _lib.nh_stats:
+        """nh_run_engine; with human_out1 (and, paired, human_out2): nh_run_engine_split; mask: nh_run_engine_mask; with
+        calls / human_ids: nh_run_engine_ex -- as run() above."""
         a = _lib.nh_run_args()
         a.db_dir = None
         a.in1 = os.fsencode(in1)
@@ -295,7 +314,10 @@ class Engine:
         a.out_codec = int(out_codec)
         a.codec_threads = int(codec_threads)
         s = _lib.nh_stats()
-        if mask:
+        if calls is not None or human_ids is not None:
+            x = _extras(mask, human_out1, human_out2, calls, human_ids)
+            _check(self._L.nh_run_engine_ex(self._h, C.byref(a), C.byref(x), C.byref(s)))
+        elif mask:
             _check(self._L.nh_run_engine_mask(self._h, C.byref(a), _path_or_none(human_out1), _path_or_none(human_out2),
                                               C.byref(s)))
         elif human_out1 is not None or human_out2 is not None:

@@ -100,7 +100,8 @@ class CommandRunner:
     def parse_argv(args):
         """The kraken2 options nohuman emits (src/main.rs:215-267) -> dict."""
         opts = {"threads": 1, "db": None, "output": None, "confidence": 0.0, "report": None,
-                "paired": False, "classified_out": None, "unclassified_out": None, "inputs": []}
+                "paired": False, "classified_out": None, "unclassified_out": None, "inputs": [],
+                "calls": None, "human_ids": None}
         it = iter(args)
         for a in it:
             if a == "--threads":
@@ -119,6 +120,10 @@ class CommandRunner:
                 opts["classified_out"] = next(it)
             elif a == "--unclassified-out":
                 opts["unclassified_out"] = next(it)
+            elif a == "--calls":  # the engine's own read lists (nohuman --calls / --human-ids), not kraken2 options
+                opts["calls"] = next(it)
+            elif a == "--human-ids":
+                opts["human_ids"] = next(it)
             elif a.startswith("--"):
                 raise OSError("%s failed with stderr Unknown option: %s" % ("kraken2", a))
             else:
@@ -185,7 +190,16 @@ class CommandRunner:
             a.device_ids = dev
             s = _lib.nh_stats()
             L = _lib.lib()
-            rc = L.nh_run(C.byref(a), C.byref(s))
+            if o["calls"] is not None or o["human_ids"] is not None:
+                if o["calls"] is not None and o["calls"] == o["human_ids"]:
+                    raise EngineError(-1, "--calls and --human-ids name the same file: %s" % o["calls"])
+                x = _lib.nh_run_extras()
+                x.struct_size = C.sizeof(_lib.nh_run_extras)
+                x.calls = os.fsencode(o["calls"]) if o["calls"] is not None else None
+                x.human_ids = os.fsencode(o["human_ids"]) if o["human_ids"] is not None else None
+                rc = L.nh_run_ex(C.byref(a), C.byref(x), C.byref(s))
+            else:
+                rc = L.nh_run(C.byref(a), C.byref(s))
             if rc != 0:
                 raise EngineError(rc, L.nh_last_error().decode(errors="replace"))
         except EngineError as e:
