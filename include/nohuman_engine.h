@@ -77,7 +77,8 @@ typedef struct {
 } nh_db_info;
 
 /* Behaviour switches; defaults reproduce kraken2 as nohuman invokes it (src/main.rs:215-224:
- * no --minimum-hit-groups, no --quick, no quality masking). */
+ * no --minimum-hit-groups, no --quick, no quality masking).  kraken2's --minimum-base-quality is not a field here (the struct
+ * keeps its size): it is an argument of nh_run_minq / nh_quality_mask_device below. */
 typedef struct {
     uint32_t minimum_hit_groups; /* default 2 */
     int32_t linear_probing;      /* default 1 (kraken2 builds with -DLINEAR_PROBING) */
@@ -359,6 +360,36 @@ typedef struct {
 } nh_run_extras;
 int nh_run_ex(const nh_run_args *args, const nh_run_extras *extras, nh_stats *stats);
 int nh_run_engine_ex(nh_engine *e, const nh_run_args *args, const nh_run_extras *extras, nh_stats *stats);
+
+/*
+ * kraken2's --minimum-base-quality (classify.cc MaskLowQualityBases; a recollection like the rest of SURVEY.md A.5, parity
+ * UNPINNED): with a threshold Q > 0 a base of a FASTQ record whose quality byte satisfies  qual - 33 < Q  (Phred+33 only, the
+ * byte read as unsigned) is classified as an ambiguous base, in both mates; FASTA records have no qualities and are never
+ * masked.  Only classification changes: nh_result, the hit list of kraken_output (masked stretches show as "A:n"), the calls
+ * table, the report and the three totals; total_kmers, the lengths of kraken_output / calls and total_bases do not.
+ * ONE DELIBERATE DEVIATION: kraken2 masks the sequence object itself and (as far as it is recalled) then writes the masked
+ * 'x' bases into --unclassified-out; here EVERY OUTPUT RECORD KEEPS THE INPUT'S BASES -- kept, human, masked and split outputs
+ * alike -- because a decontamination tool must not alter the reads it returns.  The mask byte the classifier sees is 'N'
+ * (kraken2: 'x'; the scanner cannot tell them apart).
+ *
+ * nh_quality_mask_device: the pass itself, asynchronous on `stream`, on the engine's device.  Sequence i is
+ * d_text[d_seq_starts[i], +d_seq_lens[i]) (uint64 / uint32, the arrays of nh_classify_records_device), its qualities start at
+ * d_qual_starts[i] (uint64; all-ones: no qualities, the sequence is copied unmasked).  d_out[d_seq_starts[i], +d_seq_lens[i])
+ * receives the masked bases; no other byte of d_out is written, so nh_classify_records_device can be launched on d_out with the
+ * same starts and lengths.  A record whose quality line is not exactly as long as its sequence (a '\n' among the bytes, or a
+ * byte above ' ' behind them) or whose ranges leave the text is not written at all and sets a sticky error bit (value 32) that
+ * fails the engine's next blocking call or run.  Q = 0 masks nothing (bytes below '!' excepted).
+ */
+/* out must be 4-byte aligned and text_len + 8 bytes long; d_masked (may be NULL): one uint64 the kernel adds to */
+int nh_quality_mask_device(nh_engine *e, const void *d_text, uint64_t text_len, const void *d_seq_starts,
+                           const void *d_seq_lens, const void *d_qual_starts, uint64_t n_seq,
+                           uint32_t min_base_quality, void *d_out, void *d_masked, void *stream);
+/* nh_run_ex with kraken2's --minimum-base-quality; extras may be NULL (plain nh_run); 0 = exactly nh_run_ex.  Above 93 (the
+ * highest printable quality is '~'): NH_EINVAL before any device is touched.  A FASTQ record whose quality line is not as long
+ * as its sequence ends a kraken2 run; here, with Q > 0, it fails the run with NH_EIO and a message that names both lengths. */
+int nh_run_minq(const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality, nh_stats *stats);
+int nh_run_engine_minq(nh_engine *e, const nh_run_args *args, const nh_run_extras *extras,
+                       uint32_t min_base_quality, nh_stats *stats);
 
 #ifdef __cplusplus
 }

@@ -100,6 +100,9 @@ SYMBOLS = {
     "nh_run_engine_mask": (C.c_int, [_P, C.POINTER(nh_run_args), C.c_char_p, C.c_char_p, C.POINTER(nh_stats)]),
     "nh_run_ex": (C.c_int, [C.POINTER(nh_run_args), C.POINTER(nh_run_extras), C.POINTER(nh_stats)]),
     "nh_run_engine_ex": (C.c_int, [_P, C.POINTER(nh_run_args), C.POINTER(nh_run_extras), C.POINTER(nh_stats)]),
+    "nh_quality_mask_device": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P, _P]),
+    "nh_run_minq": (C.c_int, [C.POINTER(nh_run_args), C.POINTER(nh_run_extras), C.c_uint32, C.POINTER(nh_stats)]),
+    "nh_run_engine_minq": (C.c_int, [_P, C.POINTER(nh_run_args), C.POINTER(nh_run_extras), C.c_uint32, C.POINTER(nh_stats)]),
     "nh_allreduce_counters": (C.c_int, [C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_uint64), C.c_char_p,
                                         C.c_size_t]),
 }

@@ -364,6 +364,13 @@ struct Slot {  // pinned host + device buffers of one in-flight batch
     size_t cap_cout[2] = {0, 0}, cap_chost[2] = {0, 0}, cap_idl = 0, cap_cblk = 0;
     uint64_t *h_ctotal = nullptr;
     hipEvent_t cev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around the list builder's launches
+    // runs with a minimum base quality (nh_run_minq): the text-sized buffer the classifier reads instead of d_text -- the
+    // sequences with 'N' where the quality is low (nh_qmask.hip; the record table tells where the qualities lie) -- allocated
+    // when first needed, and the masked bases of the slot's batches, read once, at the end of the run
+    void *d_qtext = nullptr;
+    unsigned long long *d_qcnt = nullptr;
+    size_t cap_qtext = 0;
+    hipEvent_t qev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around k_qmask
 };
 
 static int slot_reserve(Slot &s, size_t ntext, size_t nfrag, size_t ntaxa) {
@@ -501,6 +508,31 @@ static int slot_reserve_calls(Slot &s, size_t n, int mates, const size_t out_cap
     return NH_OK;
 }
 
+// the quality mask's buffers of a slot: the record table of nrec sequences, ntext bytes of masked text, the counter
+static int slot_reserve_qmask(Slot &s, size_t ntext, size_t nrec) {
+    auto grow = [](size_t need) { return need + need / 4 + 4096; };
+    if (nrec > s.cap_rec) {
+        if (s.h_rec) (void)hipHostFree(s.h_rec);
+        if (s.d_rec) (void)hipFree(s.d_rec);
+        s.h_rec = nullptr, s.d_rec = nullptr;
+        s.cap_rec = grow(nrec);
+        if (host_malloc((void **)&s.h_rec, s.cap_rec * 16, hipHostMallocDefault) != hipSuccess || dev_malloc(&s.d_rec, s.cap_rec * 16) != hipSuccess)
+            return set_error(NH_EOOM, "cannot allocate batch buffers (%zu records)", s.cap_rec);
+    }
+    if (ntext + 64 > s.cap_qtext) {
+        if (s.d_qtext) (void)hipFree(s.d_qtext);
+        s.d_qtext = nullptr;
+        s.cap_qtext = grow(ntext + 64);
+        if (dev_malloc(&s.d_qtext, s.cap_qtext) != hipSuccess)
+            return set_error(NH_EOOM, "cannot allocate quality-mask buffers (%zu bytes)", s.cap_qtext);
+    }
+    if (!s.d_qcnt) {
+        if (dev_malloc((void **)&s.d_qcnt, 8) != hipSuccess) return set_error(NH_EOOM, "cannot allocate batch buffers");
+        if (hipMemsetAsync(s.d_qcnt, 0, 8, s.stream) != hipSuccess) return set_error(NH_EDEVICE, "cannot clear the quality mask's counter");
+    }
+    return NH_OK;
+}
+
 // page-locked room for `n` bytes of read list o on the host (the writer's copy for the file)
 static int slot_reserve_calls_host(Slot &s, int o, size_t n) {
     if (n <= s.cap_chost[o]) return NH_OK;
@@ -548,7 +580,9 @@ static void slot_free(Slot &s) {
         if (p) (void)hipHostFree(p);
     for (void *p : {s.d_idl, s.d_cblk, (void *)s.d_cout[0], (void *)s.d_cout[1]})
         if (p) (void)hipFree(p);
-    for (hipEvent_t ev : {s.hev[0], s.hev[1], s.mev[0], s.mev[1], s.cev[0], s.cev[1]})
+    for (void *p : {s.d_qtext, (void *)s.d_qcnt})
+        if (p) (void)hipFree(p);
+    for (hipEvent_t ev : {s.hev[0], s.hev[1], s.mev[0], s.mev[1], s.cev[0], s.cev[1], s.qev[0], s.qev[1]})
         if (ev) (void)hipEventDestroy(ev);
     for (void *p : {(void *)s.h_off, (void *)s.h_len, (void *)s.h_res, (void *)s.h_taxa, (void *)s.h_taxa_off, (void *)s.h_flag})
         if (p) (void)hipHostFree(p);
@@ -640,6 +674,9 @@ struct RunState {
     // read lists (NOHUMAN_TRACE): lines and bytes of the calls table [0] and the human ids [1], the builder's kernel time
     uint64_t list_lines[2] = {0, 0}, list_bytes[2] = {0, 0};
     double list_kernel_ms = 0;
+    // runs with a minimum base quality (NOHUMAN_TRACE): the bases k_qmask replaced, its kernel time
+    uint64_t qmask_masked = 0;
+    double qmask_kernel_ms = 0;
     std::atomic<uint64_t> text_fetched{0};
     std::vector<uint64_t> dev_counts;  // per device {fragments, classified, bases, 0} as the writer saw them (checker)
     std::vector<uint64_t *> d_run_counters;  // per device: the counters the classify kernels of THIS run add to (HBM)
@@ -1054,12 +1091,18 @@ static int check_list_args(const nh_run_args *a, const char *h1, const char *h2,
 // hout1 set: a split run (nh_run_split) -- a->keep_human is 0, hout1 / hout2 receive the classified records
 // mask: a masked run (nh_run_mask) -- a->keep_human is 0, out1 / out2 receive every record, a classified one's bases as 'N'
 // calls / ids set (nh_run_ex): the calls table / the human read ids, built in HBM beside whatever else the run writes
+// minq > 0 (nh_run_minq): kraken2's --minimum-base-quality -- the classifier reads a copy of each batch's sequences in which the
+// bases of a FASTQ record with a quality below minq are 'N' (k_qmask, in front of it on the slot's stream); every output is made
+// from the batch's text as before, so the records written keep their bases.  0: nothing of this runs.
 int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_stats *stats, const char *hout1 = nullptr,
-                const char *hout2 = nullptr, bool mask = false, const char *calls = nullptr, const char *ids = nullptr) {
+                const char *hout2 = nullptr, bool mask = false, const char *calls = nullptr, const char *ids = nullptr,
+                uint32_t minq = 0) {
     if (!a || !a->in1 || !a->out1) return set_error(NH_EINVAL, "nh_run: in1 and out1 are required");
     if (engines.empty()) return set_error(NH_EINVAL, "nh_run: no engine");
     const bool split = hout1 != nullptr;
     const bool lists = calls || ids;
+    const bool qm = minq > 0;
+    if (minq > 93) return set_error(NH_EINVAL, "nh_run: minimum base quality %u is not in 0..93 (Phred+33)", minq);
     if (lists) {
         const int vrc = check_list_args(a, hout1, hout2, calls, ids);
         if (vrc) return vrc;
@@ -1217,7 +1260,9 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
             (mask && getenv("NOHUMAN_TRACE") &&
              (hipEventCreate(&slots[i].mev[0]) != hipSuccess || hipEventCreate(&slots[i].mev[1]) != hipSuccess)) ||
             (lists && getenv("NOHUMAN_TRACE") &&
-             (hipEventCreate(&slots[i].cev[0]) != hipSuccess || hipEventCreate(&slots[i].cev[1]) != hipSuccess))) {
+             (hipEventCreate(&slots[i].cev[0]) != hipSuccess || hipEventCreate(&slots[i].cev[1]) != hipSuccess)) ||
+            (qm && getenv("NOHUMAN_TRACE") &&
+             (hipEventCreate(&slots[i].qev[0]) != hipSuccess || hipEventCreate(&slots[i].qev[1]) != hipSuccess))) {
             for (auto &s : slots) slot_free(s);
             free_run_counters();
             return set_error(NH_EDEVICE, "cannot create streams");
@@ -1507,6 +1552,10 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                         float ms = 0;
                         if (hipEventElapsedTime(&ms, s.cev[0], s.cev[1]) == hipSuccess) rs.list_kernel_ms += ms;
                     }
+                    if (qm && s.qev[1]) {
+                        float ms = 0;
+                        if (hipEventElapsedTime(&ms, s.qev[0], s.qev[1]) == hipSuccess) rs.qmask_kernel_ms += ms;
+                    }
                     for (int o = 0; lists && o < 2 && !wrc; o++) {
                         const size_t tot = (size_t)s.h_ctotal[o];
                         rs.list_bytes[o] += tot;
@@ -1538,7 +1587,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
     });
 
     // main: pair halves, stage, launch
-    uint64_t batch_no = 0;
+    uint64_t batch_no = 0, frags_out = 0;  // (frags_out: the fragments of the batches before this one)
     std::vector<uint64_t> home_turn((size_t)G, 0);
     // the half of each file in hand and how many of its records have gone out (a half is normally used whole: Batch)
     std::shared_ptr<HalfBatch> c1, c2;
@@ -1650,6 +1699,16 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 const size_t out_cap[2] = {calls ? (size_t)idsum + b.n * 79 + 64 : 0, ids ? (size_t)idsum + b.n + 64 : 0};
                 rc = slot_reserve_calls(s, b.n, mates, out_cap);
             }
+            if (!rc && qm) rc = slot_reserve_qmask(s, ntext, b.n * (size_t)mates);
+            // kraken2 ends a run at a FASTQ record whose quality line is not as long as its sequence when it masks by quality
+            for (size_t i = 0; qm && !rc && i < b.n; i++)
+                for (int m = 0; m < mates && !rc; m++) {
+                    const HalfBatch &hb = m ? *b.h2 : *b.h1;
+                    const RecRef &r = hb.recs[(m ? b.off2 : b.off1) + i];
+                    if (hb.format == FMT_FASTQ && r.qlen != r.slen)
+                        rc = set_error(NH_EIO, "%s, read %llu: sequence length (%u) != quality string length (%u), which --minimum-base-quality cannot mask",
+                                       m ? a->in2 : a->in1, (unsigned long long)(frags_out + i + 1), r.slen, r.qlen);
+                }
             if (rc) {
                 rs.fail(rc, g_last_error);
                 wq.push(std::move(b));
@@ -1663,7 +1722,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 s.h_len[i * mates] = r1.slen;
                 nbases += r1.slen;
                 if (lists) s.h_idl[i] = r1.idlen;
-                if (split || mask || lists) {
+                if (split || mask || lists || qm) {
                     uint32_t *hr = s.h_rec + 4 * i * mates;
                     hr[0] = r1.h, hr[1] = r1.hlen, hr[2] = r1.q, hr[3] = r1.qlen;
                     if (rs.paired) {
@@ -1717,14 +1776,35 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 he = hipMemcpyAsync(s.d_len, s.h_len, b.n * mates * 4, hipMemcpyHostToDevice, s.stream);
             if (he == hipSuccess && rs.want_k)
                 he = hipMemcpyAsync(s.d_taxa_off, s.h_taxa_off, (b.n + 1) * 8, hipMemcpyHostToDevice, s.stream);
-            if (he == hipSuccess && (split || mask || lists))
+            if (he == hipSuccess && (split || mask || lists || qm))
                 he = hipMemcpyAsync(s.d_rec, s.h_rec, b.n * mates * 16, hipMemcpyHostToDevice, s.stream);
             if (he == hipSuccess && lists)
                 he = hipMemcpyAsync(s.d_idl, s.h_idl, b.n * 4, hipMemcpyHostToDevice, s.stream);
             if (he != hipSuccess) {
                 rs.fail(NH_EDEVICE, std::string("H2D: ") + hipGetErrorString(he));
-            } else {
-                rc = classify_device(s.e, s.d_text, s.d_off, b.n,
+            } else if (qm) {  // the sequences the classifier reads: a copy with 'N' where the quality is below minq
+                dev_check_ptr(s.d_qtext, s.e->device, "nh_run, a slot's quality-masked text");
+                QmaskArgs qa{};
+                qa.text = (const char *)s.d_text;
+                qa.ntext = ntext;
+                qa.seq_off = (const uint64_t *)s.d_off;
+                qa.seq_len = (const uint32_t *)s.d_len;
+                qa.rec = (const uint32_t *)s.d_rec;
+                qa.n = b.n * (uint64_t)mates;
+                qa.mates = mates;
+                qa.fastq[0] = b.h1->format == FMT_FASTQ;
+                qa.fastq[1] = rs.paired && b.h2->format == FMT_FASTQ;
+                qa.thresh = minq + 33;
+                qa.out = (char *)s.d_qtext;
+                qa.masked = s.d_qcnt;
+                qa.error = s.e->d_error + LAUNCH_SLOTS;
+                if (s.qev[0]) (void)hipEventRecord(s.qev[0], s.stream);
+                he = launch_qmask(qa, s.stream);
+                if (s.qev[1] && he == hipSuccess) he = hipEventRecord(s.qev[1], s.stream);
+                if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("quality mask: ") + hipGetErrorString(he));
+            }
+            if (!rs.failed()) {
+                rc = classify_device(s.e, qm ? s.d_qtext : s.d_text, s.d_off, b.n,
                                      flags | (nbases / b.n > 2000 ? NH_FLAG_LONG : 0u), a->confidence, s.d_res,
                                      rs.want_k ? s.d_taxa : nullptr, rs.want_k ? s.d_taxa_off : nullptr,
                                      rs.d_run_counters[(size_t)(si / NS)], s.stream, s.d_len, ntext);
@@ -1819,6 +1899,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("D2H: ") + hipGetErrorString(he));
             }
             batch_no++;
+            frags_out += b.n;
             wq.push(std::move(b));
             clk.ns[ST_MLAUNCH] += StageClock::now() - m3;
         }
@@ -1849,6 +1930,11 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
         w2_cv.notify_all();
         tw2.join();
     }
+    for (auto &s : slots)  // (every stream has been synchronised by the writer, or the run has failed)
+        if (s.d_qcnt && rs.err_code == NH_OK) {
+            unsigned long long c = 0;
+            if (dev_set(s.e->device) == hipSuccess && hipMemcpy(&c, s.d_qcnt, 8, hipMemcpyDeviceToHost) == hipSuccess) rs.qmask_masked += c;
+        }
     for (auto &s : slots) slot_free(s);
     if (const char *tr = getenv("NOHUMAN_TRACE")) {
         if (tr[0] == '1') {
@@ -1872,6 +1958,9 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 fprintf(stderr, "[nohuman trace] calls: %llu lines, %llu bytes; ids: %llu lines, %llu bytes built on device; %llu fetched to host; builder kernels %.3f ms\n",
                         (unsigned long long)rs.list_lines[0], (unsigned long long)rs.list_bytes[0], (unsigned long long)rs.list_lines[1],
                         (unsigned long long)rs.list_bytes[1], (unsigned long long)rs.text_fetched.load(), rs.list_kernel_ms);
+            if (qm)
+                fprintf(stderr, "[nohuman trace] qmask: Q %u, %llu of %llu bases masked, kernel %.3f ms\n", minq,
+                        (unsigned long long)rs.qmask_masked, (unsigned long long)rs.total_bases, rs.qmask_kernel_ms);
             if (g_pageable_batches.load())
                 fprintf(stderr, "[nohuman trace] %d batch buffers could not be page-locked (pageable memory used)\n",
                         g_pageable_batches.load());
@@ -1991,9 +2080,15 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
 }
 
 int run_engine(Engine *e, const nh_run_args *a, nh_stats *stats, const char *hout1 = nullptr, const char *hout2 = nullptr,
-               bool mask = false, const char *calls = nullptr, const char *ids = nullptr) {
+               bool mask = false, const char *calls = nullptr, const char *ids = nullptr, uint32_t minq = 0) {
     std::vector<Engine *> v{e};
-    return run_engines(v, a, stats, hout1, hout2, mask, calls, ids);
+    return run_engines(v, a, stats, hout1, hout2, mask, calls, ids, minq);
+}
+
+// nh_run_minq's own argument, checked before any device is touched: the highest printable quality is '~', Phred 93
+int check_minq(uint32_t minq) {
+    if (minq > 93) return set_error(NH_EINVAL, "minimum base quality %u is not in 0..93 (Phred+33)", minq);
+    return NH_OK;
 }
 
 // nh_run_ex's arguments, checked before any device is touched: the struct, what nh_run_split / nh_run_mask check for the fields
@@ -2041,6 +2136,16 @@ int nh_run_engine_ex(nh_engine *e, const nh_run_args *args, const nh_run_extras 
                           extras->human_ids);
 }
 
+int nh_run_engine_minq(nh_engine *e, const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality, nh_stats *stats) {
+    int rc = nh::check_minq(min_base_quality);
+    if (!rc && extras) rc = nh::check_extras(args, extras);
+    if (rc) return rc;
+    if (!e) return nh::set_error(NH_EINVAL, "null engine");
+    if (!extras) return nh::run_engine((nh::Engine *)e, args, stats, nullptr, nullptr, false, nullptr, nullptr, min_base_quality);
+    return nh::run_engine((nh::Engine *)e, args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls,
+                          extras->human_ids, min_base_quality);
+}
+
 int nh_fastx_scan(const char *path, uint64_t *n_records, uint64_t *n_bases, uint64_t *digest) {
     if (!path || !n_records || !n_bases || !digest) return nh::set_error(NH_EINVAL, "null argument");
     nh::BlockReader r;
@@ -2078,7 +2183,7 @@ int nh_fastx_scan(const char *path, uint64_t *n_records, uint64_t *n_bases, uint
 // Whole run on one or several devices: the database is loaded into every device's HBM, batches go
 // round-robin, outputs stay in input order, the counts are summed on the host.
 static int run_devices(const nh_run_args *args, nh_stats *stats, const char *hout1, const char *hout2, bool mask = false,
-                       const char *calls = nullptr, const char *ids = nullptr) {
+                       const char *calls = nullptr, const char *ids = nullptr, uint32_t minq = 0) {
     if (!args || !args->db_dir) return nh::set_error(NH_EINVAL, "nh_run: db_dir is required");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -2114,7 +2219,7 @@ static int run_devices(const nh_run_args *args, nh_stats *stats, const char *hou
     }
     const double t_load = since(t_begin);
     const auto t_run = std::chrono::steady_clock::now();
-    if (!rc) rc = nh::run_engines(engines, args, stats, hout1, hout2, mask, calls, ids);
+    if (!rc) rc = nh::run_engines(engines, args, stats, hout1, hout2, mask, calls, ids, minq);
     const double s_run = since(t_run);
     std::string keep = nh::g_last_error;
     const auto t_close = std::chrono::steady_clock::now();
@@ -2144,6 +2249,15 @@ int nh_run_ex(const nh_run_args *args, const nh_run_extras *extras, nh_stats *st
     const int rc = nh::check_extras(args, extras);  // (before any device is touched)
     if (rc) return rc;
     return run_devices(args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls, extras->human_ids);
+}
+
+int nh_run_minq(const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality, nh_stats *stats) {
+    int rc = nh::check_minq(min_base_quality);  // (before any device is touched)
+    if (!rc && extras) rc = nh::check_extras(args, extras);
+    if (rc) return rc;
+    if (!extras) return run_devices(args, stats, nullptr, nullptr, false, nullptr, nullptr, min_base_quality);
+    return run_devices(args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls, extras->human_ids,
+                       min_base_quality);
 }
 
 }  // extern "C"

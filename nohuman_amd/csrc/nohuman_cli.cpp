@@ -219,6 +219,7 @@ struct Args {
     bool bgzf = false;  // gzip outputs in bgzip's blocked form (NH_CODEC_BGZF)
     bool mask = false;  // masked run: every read written, the human ones' bases as N (nh_run_mask)
     std::string calls, human_ids;  // read lists (nh_run_ex): a table line per read; the ids of the human reads
+    unsigned min_base_quality = 0;  // kraken2's --minimum-base-quality (nh_run_minq); 0: off
     bool has_out1 = false, has_out2 = false, check = false, download = false, list = false, human = false;
     bool has_type = false;
     Codec type = C_NONE;
@@ -246,6 +247,7 @@ static void usage(FILE *f) {
           "      --human-out2 <PATH>      Second human output file (required with two inputs)\n"
           "      --mask                   Replace the bases of human reads with N instead of removing them (every read is written, in input order)\n"
           "  -C, --conf <[0, 1]>          Kraken2 minimum confidence score [default: 0.0]\n"
+          "      --minimum-base-quality <INT>  Kraken2 minimum base quality: classify FASTQ bases with a lower Phred+33 quality as ambiguous (0-93; the reads written keep their bases) [default: 0]\n"
           "  -k, --kraken-output <FILE>   Write the Kraken2 read classification output to a file\n"
           "  -r, --kraken-report <FILE>   Write the Kraken2 report with aggregate counts/clade to file\n"
           "      --calls <FILE>           Write a table with one line per read: C/U, id, taxid, length(s), k-mers, clade hits (hits / k-mers is the confidence -C thresholds), hit groups\n"
@@ -317,6 +319,15 @@ static Args parse_args(int argc, char **argv) {
             if (*end || t.empty()) arg_error("invalid value '%s' for '--conf <[0, 1]>': Confidence score must be a number", t.c_str());
             if (!(c >= 0.0f && c <= 1.0f)) arg_error("invalid value '%s' for '--conf <[0, 1]>': Confidence score must be in the closed interval [0, 1]", t.c_str());
             a.confidence = c;
+        } else if (s == "--minimum-base-quality") {
+            std::string t = val();
+            char *end;
+            errno = 0;
+            long n = strtol(t.c_str(), &end, 10);
+            if (*end || t.empty() || t[0] == ' ' || t[0] == '\t')
+                arg_error("invalid value '%s' for '--minimum-base-quality <INT>': invalid digit found in string", t.c_str());
+            if (errno || n < 0 || n > 93) arg_error("invalid value '%s' for '--minimum-base-quality <INT>': %s is not in 0..=93", t.c_str(), t.c_str());
+            a.min_base_quality = (unsigned)n;
         } else if (s == "-k" || s == "--kraken-output") a.kraken_output = val();
         else if (s == "-r" || s == "--kraken-report") a.kraken_report = val();
         else if (s == "--calls") a.calls = val();
@@ -533,7 +544,8 @@ int main(int argc, char **argv) {
     rx.human_out1 = hp1, rx.human_out2 = hp2;
     rx.calls = args.calls.empty() ? nullptr : cpart.c_str();
     rx.human_ids = args.human_ids.empty() ? nullptr : ipart.c_str();
-    const int run_rc = lists       ? nh_run_ex(&ra, &rx, &st)
+    const int run_rc = args.min_base_quality ? nh_run_minq(&ra, lists || args.mask || split ? &rx : nullptr, args.min_base_quality, &st)
+                       : lists     ? nh_run_ex(&ra, &rx, &st)
                        : args.mask ? nh_run_mask(&ra, hp1, hp2, &st)
                        : split     ? nh_run_split(&ra, hp1, hp2, &st)
                                    : nh_run(&ra, &st);

@@ -42,7 +42,7 @@ def probe() -> str:
 def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None, confidence: float = 0.0,
         threads: int = 1, keep_human: bool = False, device_ids=None, out_codec: int = 0,
         codec_threads: int = 0, human_out1=None, human_out2=None, mask: bool = False, calls=None,
-        human_ids=None) -> "_lib.nh_stats":
+        human_ids=None, min_base_quality: int = 0) -> "_lib.nh_stats":
     """nh_run: whole run, database loaded into every listed device (default: all visible).  human_out1 (and, paired,
     human_out2) given: nh_run_split -- the non-human reads go to out1 / out2 and, in the same pass, the human reads to
     human_out1 / human_out2 exactly as a keep_human run would write them.  mask: nh_run_mask -- every read goes to
@@ -50,7 +50,9 @@ def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
     out_codec: the container of every output, one of the CODEC_* numbers (CODEC_BGZF: gzip in bgzip's blocked form).
     calls / human_ids (nh_run_ex; any kind of run): two plain-text read lists built on the GPU in the same pass -- calls: a
     line per fragment, C/U, id, taxid, length(s), total_kmers, clade_hits, hit_groups, tab-separated (clade_hits /
-    total_kmers is the confidence that `confidence` thresholds); human_ids: the id of every human fragment."""
+    total_kmers is the confidence that `confidence` thresholds); human_ids: the id of every human fragment.
+    min_base_quality (nh_run_minq; kraken2's --minimum-base-quality, 0..93): a base of a FASTQ record with a Phred+33 quality
+    below it is classified as an ambiguous base; every record written keeps its bases.  0: exactly the run without it."""
     a = _lib.nh_run_args()
     a.db_dir = os.fsencode(db_dir)
     a.in1 = os.fsencode(in1)
@@ -73,7 +75,10 @@ def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
         a.n_devices = 0
         a.device_ids = None
     s = _lib.nh_stats()
-    if calls is not None or human_ids is not None:
+    if min_base_quality:
+        _check(_lib.lib().nh_run_minq(C.byref(a), _extras_or_none(mask, human_out1, human_out2, calls, human_ids),
+                                      _minq(min_base_quality), C.byref(s)))
+    elif calls is not None or human_ids is not None:
         x = _extras(mask, human_out1, human_out2, calls, human_ids)
         _check(_lib.lib().nh_run_ex(C.byref(a), C.byref(x), C.byref(s)))
     elif mask:
@@ -98,6 +103,20 @@ def _extras(mask, human_out1, human_out2, calls, human_ids) -> "_lib.nh_run_extr
     x.calls = _path_or_none(calls)
     x.human_ids = _path_or_none(human_ids)
     return x
+
+
+def _extras_or_none(mask, human_out1, human_out2, calls, human_ids):
+    """nh_run_minq's extras: NULL for a plain run"""
+    if not mask and human_out1 is None and human_out2 is None and calls is None and human_ids is None:
+        return None
+    return C.byref(_extras(mask, human_out1, human_out2, calls, human_ids))
+
+
+def _minq(q) -> int:
+    q = int(q)
+    if q < 0:
+        raise EngineError(-1, "minimum base quality %d is not in 0..93 (Phred+33)" % q)
+    return min(q, 0xFFFFFFFF)
 
 
 def device_count() -> int:
@@ -278,6 +297,15 @@ class Engine:
             (FLAG_PAIRED if paired else 0) | (FLAG_LONG if long_reads else 0), float(confidence), d_results,
             d_kmer_taxa or None, d_kmer_taxa_offsets or None, d_counters or None, stream or None))
 
+    def quality_mask_device(self, d_text: int, text_len: int, d_seq_starts: int, d_seq_lens: int, d_qual_starts: int,
+                            n_seq: int, min_base_quality: int, d_out: int, d_masked: int = 0, stream: int = 0):
+        """kraken2's --minimum-base-quality as a pass in front of classify_records_device: d_out (text_len + 8 bytes, the
+        layout of d_text) receives every sequence's bases, N where the Phred+33 quality at d_qual_starts[i] + j is below
+        min_base_quality (an all-ones quality start: copied); nothing else of d_out is written.  d_masked: one uint64 the
+        kernel adds its masked bases to.  Asynchronous on `stream`."""
+        _check(self._L.nh_quality_mask_device(self._h, d_text, text_len, d_seq_starts, d_seq_lens, d_qual_starts, n_seq,
+                                              _minq(min_base_quality), d_out, d_masked or None, stream or None))
+
     def add_sequences(self, d_bases: int, d_seq_offsets: int, n_seq: int, value: int, stream: int = 0):
         """Bench/test support: insert the minimizers of device-resident sequences into the table."""
         _check(self._L.nh_synthetic_add_sequences(self._h, d_bases, d_seq_offsets, n_seq, value,
@@ -295,9 +323,9 @@ class Engine:
     def run(self, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
             confidence: float = 0.0, threads: int = 1, keep_human: bool = False, out_codec: int = 0,
             codec_threads: int = 0, human_out1=None, human_out2=None, mask: bool = False, calls=None,
-            human_ids=None) -> _lib.nh_stats:
+            human_ids=None, min_base_quality: int = 0) -> _lib.nh_stats:
         """nh_run_engine; with human_out1 (and, paired, human_out2): nh_run_engine_split; mask: nh_run_engine_mask; with
-        calls / human_ids: nh_run_engine_ex -- as run() above."""
+        calls / human_ids: nh_run_engine_ex; with min_base_quality: nh_run_engine_minq -- as run() above."""
         a = _lib.nh_run_args()
         a.db_dir = None
         a.in1 = os.fsencode(in1)
@@ -314,7 +342,10 @@ class Engine:
         a.out_codec = int(out_codec)
         a.codec_threads = int(codec_threads)
         s = _lib.nh_stats()
-        if calls is not None or human_ids is not None:
+        if min_base_quality:
+            _check(self._L.nh_run_engine_minq(self._h, C.byref(a), _extras_or_none(mask, human_out1, human_out2, calls, human_ids),
+                                              _minq(min_base_quality), C.byref(s)))
+        elif calls is not None or human_ids is not None:
             x = _extras(mask, human_out1, human_out2, calls, human_ids)
             _check(self._L.nh_run_engine_ex(self._h, C.byref(a), C.byref(x), C.byref(s)))
         elif mask:

@@ -101,7 +101,7 @@ class CommandRunner:
         """The kraken2 options nohuman emits (src/main.rs:215-267) -> dict."""
         opts = {"threads": 1, "db": None, "output": None, "confidence": 0.0, "report": None,
                 "paired": False, "classified_out": None, "unclassified_out": None, "inputs": [],
-                "calls": None, "human_ids": None}
+                "calls": None, "human_ids": None, "minimum_base_quality": 0}
         it = iter(args)
         for a in it:
             if a == "--threads":
@@ -120,6 +120,11 @@ class CommandRunner:
                 opts["classified_out"] = next(it)
             elif a == "--unclassified-out":
                 opts["unclassified_out"] = next(it)
+            elif a == "--minimum-base-quality":
+                v = next(it)
+                if not (v.isascii() and v.isdigit() and int(v) <= 93):
+                    raise OSError("%s failed with stderr --minimum-base-quality must be an integer in 0..93: %s" % ("kraken2", v))
+                opts["minimum_base_quality"] = int(v)
             elif a == "--calls":  # the engine's own read lists (nohuman --calls / --human-ids), not kraken2 options
                 opts["calls"] = next(it)
             elif a == "--human-ids":
@@ -190,6 +195,7 @@ class CommandRunner:
             a.device_ids = dev
             s = _lib.nh_stats()
             L = _lib.lib()
+            minq = o["minimum_base_quality"]
             if o["calls"] is not None or o["human_ids"] is not None:
                 if o["calls"] is not None and o["calls"] == o["human_ids"]:
                     raise EngineError(-1, "--calls and --human-ids name the same file: %s" % o["calls"])
@@ -197,7 +203,12 @@ class CommandRunner:
                 x.struct_size = C.sizeof(_lib.nh_run_extras)
                 x.calls = os.fsencode(o["calls"]) if o["calls"] is not None else None
                 x.human_ids = os.fsencode(o["human_ids"]) if o["human_ids"] is not None else None
-                rc = L.nh_run_ex(C.byref(a), C.byref(x), C.byref(s))
+                if minq:
+                    rc = L.nh_run_minq(C.byref(a), C.byref(x), minq, C.byref(s))
+                else:
+                    rc = L.nh_run_ex(C.byref(a), C.byref(x), C.byref(s))
+            elif minq:
+                rc = L.nh_run_minq(C.byref(a), None, minq, C.byref(s))
             else:
                 rc = L.nh_run(C.byref(a), C.byref(s))
             if rc != 0:
