@@ -391,6 +391,55 @@ int nh_run_minq(const nh_run_args *args, const nh_run_extras *extras, uint32_t m
 int nh_run_engine_minq(nh_engine *e, const nh_run_args *args, const nh_run_extras *extras,
                        uint32_t min_base_quality, nh_stats *stats);
 
+/*
+ * Read statistics (--read-stats): the QC summary a user would otherwise get from a second pass over the input and the output
+ * (seqkit stats -a, NanoPlot), counted in the run itself, on the device, for three sets of reads -- all the reads read
+ * ("input"), the non-human ones and the human ones -- per mate.  The sets follow the CALLS, whatever the run writes: their
+ * naming does not depend on keep_human, mask or the human outputs.  The bases are the input's, also in a run with a minimum
+ * base quality (the class counts then follow the masked calls) and in a masked run.
+ * THE DEFINITIONS ARE THIS PROJECT'S OWN, NOT seqkit's: the median is the lower nearest-rank element (0-based index
+ * ceil(n/2) - 1 of the ascending lengths; seqkit averages the two middle ones); N50 is the largest L such that the reads of
+ * length >= L hold at least half of the set's bases (2 * sum >= bases); gc counts G, C, g, c over ALL bases of the set (not over
+ * A, C, G, T only); other counts the bytes not in ACGTacgt; qhist[q] counts the bases whose quality byte, read as unsigned, less
+ * 33, clamped to 0 .. 93, is q, over the records that have qualities (FASTQ).  A read of length 0 is a read.  All of it is
+ * integer sums, minima and maxima: bit-exact, whatever the batches, devices or order.
+ */
+#define NH_RS_QBINS 94
+typedef struct {
+    uint64_t reads, bases, min_len, max_len, gc, other, qual_reads, qual_bases, qhist[NH_RS_QBINS];
+} nh_read_class;
+typedef struct {
+    nh_read_class cls[2][2];   /* [0 non-human | 1 human][mate]; a class without reads: all 0 (min_len too) */
+    uint64_t median_len[3][2]; /* [0 input | 1 non-human | 2 human][mate]; 0 for an empty set */
+    uint64_t n50[3][2];
+    int32_t mates, reserved;
+} nh_read_stats;
+/* The counting pass itself, asynchronous on `stream`, on the engine's device: the arrays of nh_quality_mask_device (n_frag
+ * fragments; with NH_FLAG_PAIRED in flags sequences 2f and 2f + 1 are the mates of fragment f) and the classifier's results:
+ * sequence i goes to class d_results[i / mates].call != 0, mate i % mates.  d_acc: four nh_read_class in HBM, [class][mate], that
+ * the kernel ADDS to (two launches accumulate); the caller zeroes them and sets the four min_len words to all-ones.  d_text must
+ * be 4-byte aligned, readable for text_len + 8 bytes, text_len below 4 GiB, the sequences of a launch disjoint.  A record whose
+ * quality line is not as long as its sequence or whose ranges leave the text is not counted and sets the sticky error bit of
+ * nh_quality_mask_device (value 32).  max_workgroups: 0, or a cap on the grid (each workgroup loops over its share of the
+ * sequences and adds its totals to d_acc once). */
+int nh_read_stats_device(nh_engine *e, const void *d_text, uint64_t text_len, const void *d_seq_starts, const void *d_seq_lens,
+                         const void *d_qual_starts, const void *d_results, uint64_t n_frag, uint32_t flags, void *d_acc,
+                         uint32_t max_workgroups, void *stream);
+/* nh_run_minq with read statistics: read_stats_path (may be NULL) receives the table -- plain text whatever out_codec is, a header
+ * line and a row per set (input, nonhuman, human) and mate, tab-separated:
+ *   set mate reads bases min_len mean_len median_len max_len N50 gc_pct other_bases q20_pct q30_pct mean_qual
+ * integers as integers, ratios as %.2f ("NA" where the denominator is 0), mean_qual = -10 log10(sum qhist[q] 10^(-q/10) /
+ * qual_bases) -- and `out` (may be NULL) the numbers.  Both NULL: exactly nh_run_minq.  extras may be NULL.  A path that names an
+ * input or another output of the run (the same path, or the same device and inode): NH_EINVAL before any device is touched.
+ * With statistics on, a FASTQ record whose quality line is not as long as its sequence fails the run with NH_EIO, as with
+ * min_base_quality > 0.  The table is written when the run has succeeded. */
+int nh_run_rstats(const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality, const char *read_stats_path,
+                  nh_read_stats *out, nh_stats *stats);
+int nh_run_engine_rstats(nh_engine *e, const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality,
+                         const char *read_stats_path, nh_read_stats *out, nh_stats *stats);
+/* the table of nh_run_rstats from the numbers; host only, no device needed */
+int nh_read_stats_write(const nh_read_stats *stats, const char *path);
+
 #ifdef __cplusplus
 }
 #endif

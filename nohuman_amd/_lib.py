@@ -52,6 +52,20 @@ class nh_run_extras(C.Structure):
                 ("human_out2", C.c_char_p), ("calls", C.c_char_p), ("human_ids", C.c_char_p)]
 
 
+NH_RS_QBINS = 94
+
+
+class nh_read_class(C.Structure):
+    _fields_ = [("reads", C.c_uint64), ("bases", C.c_uint64), ("min_len", C.c_uint64), ("max_len", C.c_uint64),
+                ("gc", C.c_uint64), ("other", C.c_uint64), ("qual_reads", C.c_uint64), ("qual_bases", C.c_uint64),
+                ("qhist", C.c_uint64 * NH_RS_QBINS)]
+
+
+class nh_read_stats(C.Structure):
+    _fields_ = [("cls", (nh_read_class * 2) * 2), ("median_len", (C.c_uint64 * 2) * 3), ("n50", (C.c_uint64 * 2) * 3),
+                ("mates", C.c_int32), ("reserved", C.c_int32)]
+
+
 # every symbol include/nohuman_engine.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -103,6 +117,12 @@ SYMBOLS = {
     "nh_quality_mask_device": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, C.c_uint32, _P, _P, _P]),
     "nh_run_minq": (C.c_int, [C.POINTER(nh_run_args), C.POINTER(nh_run_extras), C.c_uint32, C.POINTER(nh_stats)]),
     "nh_run_engine_minq": (C.c_int, [_P, C.POINTER(nh_run_args), C.POINTER(nh_run_extras), C.c_uint32, C.POINTER(nh_stats)]),
+    "nh_read_stats_device": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, _P, C.c_uint64, C.c_uint32, _P, C.c_uint32, _P]),
+    "nh_run_rstats": (C.c_int, [C.POINTER(nh_run_args), C.POINTER(nh_run_extras), C.c_uint32, C.c_char_p,
+                                C.POINTER(nh_read_stats), C.POINTER(nh_stats)]),
+    "nh_run_engine_rstats": (C.c_int, [_P, C.POINTER(nh_run_args), C.POINTER(nh_run_extras), C.c_uint32, C.c_char_p,
+                                       C.POINTER(nh_read_stats), C.POINTER(nh_stats)]),
+    "nh_read_stats_write": (C.c_int, [C.POINTER(nh_read_stats), C.c_char_p]),
     "nh_allreduce_counters": (C.c_int, [C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_uint64), C.c_char_p,
                                         C.c_size_t]),
 }

@@ -6,6 +6,7 @@
 #include <atomic>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "nh_device.h"
@@ -185,25 +186,40 @@ struct CallsArgs {
 };
 uint64_t calls_blocks(uint64_t n);
 hipError_t launch_calls(const CallsArgs &a, hipStream_t stream);
-// The quality-masked bases of one batch (nh_qmask.hip; kraken2's --minimum-base-quality): out, a buffer with the layout of the
-// text, receives for every sequence its bases with 'N' where the quality byte is below thresh; no other byte of out is written.
-// The classifier is then launched in place on out with the same seq_off / seq_len.
-struct QmaskArgs {
+// Where the sequences of one batch and their quality lines lie (nh_qseq.h): what the kernels that walk both take.
+struct QSeqSrc {
     const char *text;         // the batch's text (d_text), ntext bytes, readable for 8 more
     uint64_t ntext;
     const uint64_t *seq_off;  // n sequence starts (absolute), as classified
     const uint32_t *seq_len;  // n sequence lengths
-    const uint64_t *qual_off; // rec == NULL: n quality starts (absolute); all-ones: no qualities, the sequence is copied
+    const uint64_t *qual_off; // rec == NULL: n quality starts (absolute); all-ones: the sequence has no qualities
     const uint32_t *rec;      // or the run's record table: n * {header start, header length, qualities start (absolute), length}
     uint64_t n;               // sequences (a paired run: 2 a fragment, mate m at odd / even entries)
     int mates;                // rec: 1 or 2
-    int fastq[2];             // rec: per mate, FASTQ (else FASTA: copied)
+    int fastq[2];             // rec: per mate, FASTQ (else FASTA: no qualities)
+};
+// The quality-masked bases of one batch (nh_qmask.hip; kraken2's --minimum-base-quality): out, a buffer with the layout of the
+// text, receives for every sequence its bases with 'N' where the quality byte is below thresh (a sequence without qualities is
+// copied); no other byte of out is written.  The classifier is then launched in place on out with the same seq_off / seq_len.
+struct QmaskArgs : QSeqSrc {
     uint32_t thresh;          // Q + 33: a quality byte below it masks its base
     char *out;                // ntext + 8 bytes
     unsigned long long *masked;  // NULL or one counter the waves add their masked bases to
     int *error;               // the engine's sticky error word (bit 32: a quality line not as long as its sequence, a range outside the text)
 };
 hipError_t launch_qmask(const QmaskArgs &a, hipStream_t stream);
+// The read statistics of one batch (nh_rstats.hip; nh_run_rstats): every sequence adds its counts to acc[2 * class + mate], class
+// 1 where its fragment's call is not 0 (res[i / mates]), mate i % mates.  A record that fails the checks of the quality mask is
+// not counted and sets the same error bit.
+struct RstatsArgs : QSeqSrc {
+    const nh_result *res;     // n / mates results
+    unsigned long long *acc;  // 4 nh_read_class the workgroups add to (min_len: atomic minimum)
+    int *error;               // the engine's sticky error word (bit 32, as the quality mask)
+};
+// max_workgroups 0: as many as an n_cu-CU device holds at once
+hipError_t launch_rstats(const RstatsArgs &a, int n_cu, uint32_t max_workgroups, hipStream_t stream);
+// median and N50 of a set of read lengths given as (length, reads) in ascending order of length (nh_rstats.hip, host)
+void length_summary(const std::vector<std::pair<uint64_t, uint64_t>> &lens, uint64_t *median, uint64_t *n50);
 // buffers kept between the runs of a process (nh_run.hip: page-locked batch text; nh_gunzip.hip: the gzip reader's HBM and
 // staging): emptied when an engine is closed
 void run_cache_trim();

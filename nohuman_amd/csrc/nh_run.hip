@@ -21,6 +21,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <deque>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <thread>
@@ -371,6 +372,7 @@ struct Slot {  // pinned host + device buffers of one in-flight batch
     unsigned long long *d_qcnt = nullptr;
     size_t cap_qtext = 0;
     hipEvent_t qev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around k_qmask
+    hipEvent_t rev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around k_rstats (runs with read statistics)
 };
 
 static int slot_reserve(Slot &s, size_t ntext, size_t nfrag, size_t ntaxa) {
@@ -508,17 +510,23 @@ static int slot_reserve_calls(Slot &s, size_t n, int mates, const size_t out_cap
     return NH_OK;
 }
 
+// the record table of nrec sequences of a slot (read statistics need nothing else)
+static int slot_reserve_rec(Slot &s, size_t nrec) {
+    if (nrec <= s.cap_rec) return NH_OK;
+    if (s.h_rec) (void)hipHostFree(s.h_rec);
+    if (s.d_rec) (void)hipFree(s.d_rec);
+    s.h_rec = nullptr, s.d_rec = nullptr;
+    s.cap_rec = nrec + nrec / 4 + 4096;
+    if (host_malloc((void **)&s.h_rec, s.cap_rec * 16, hipHostMallocDefault) != hipSuccess || dev_malloc(&s.d_rec, s.cap_rec * 16) != hipSuccess)
+        return set_error(NH_EOOM, "cannot allocate batch buffers (%zu records)", s.cap_rec);
+    return NH_OK;
+}
+
 // the quality mask's buffers of a slot: the record table of nrec sequences, ntext bytes of masked text, the counter
 static int slot_reserve_qmask(Slot &s, size_t ntext, size_t nrec) {
     auto grow = [](size_t need) { return need + need / 4 + 4096; };
-    if (nrec > s.cap_rec) {
-        if (s.h_rec) (void)hipHostFree(s.h_rec);
-        if (s.d_rec) (void)hipFree(s.d_rec);
-        s.h_rec = nullptr, s.d_rec = nullptr;
-        s.cap_rec = grow(nrec);
-        if (host_malloc((void **)&s.h_rec, s.cap_rec * 16, hipHostMallocDefault) != hipSuccess || dev_malloc(&s.d_rec, s.cap_rec * 16) != hipSuccess)
-            return set_error(NH_EOOM, "cannot allocate batch buffers (%zu records)", s.cap_rec);
-    }
+    const int rrc = slot_reserve_rec(s, nrec);
+    if (rrc) return rrc;
     if (ntext + 64 > s.cap_qtext) {
         if (s.d_qtext) (void)hipFree(s.d_qtext);
         s.d_qtext = nullptr;
@@ -582,7 +590,7 @@ static void slot_free(Slot &s) {
         if (p) (void)hipFree(p);
     for (void *p : {s.d_qtext, (void *)s.d_qcnt})
         if (p) (void)hipFree(p);
-    for (hipEvent_t ev : {s.hev[0], s.hev[1], s.mev[0], s.mev[1], s.cev[0], s.cev[1], s.qev[0], s.qev[1]})
+    for (hipEvent_t ev : {s.hev[0], s.hev[1], s.mev[0], s.mev[1], s.cev[0], s.cev[1], s.qev[0], s.qev[1], s.rev[0], s.rev[1]})
         if (ev) (void)hipEventDestroy(ev);
     for (void *p : {(void *)s.h_off, (void *)s.h_len, (void *)s.h_res, (void *)s.h_taxa, (void *)s.h_taxa_off, (void *)s.h_flag})
         if (p) (void)hipHostFree(p);
@@ -677,6 +685,11 @@ struct RunState {
     // runs with a minimum base quality (NOHUMAN_TRACE): the bases k_qmask replaced, its kernel time
     uint64_t qmask_masked = 0;
     double qmask_kernel_ms = 0;
+    // runs with read statistics: the exact length histogram of each [class][mate] -- a vector for the lengths below 2^20, a map
+    // above -- that the writer keeps from the batch's lengths and calls (median and N50 need every length), k_rstats' time
+    std::vector<uint64_t> len_hist[2][2];
+    std::map<uint64_t, uint64_t> len_long[2][2];
+    double rstats_kernel_ms = 0;
     std::atomic<uint64_t> text_fetched{0};
     std::vector<uint64_t> dev_counts;  // per device {fragments, classified, bases, 0} as the writer saw them (checker)
     std::vector<uint64_t *> d_run_counters;  // per device: the counters the classify kernels of THIS run add to (HBM)
@@ -1088,23 +1101,52 @@ static int check_list_args(const nh_run_args *a, const char *h1, const char *h2,
     return NH_OK;
 }
 
+// nh_run_rstats' table, checked before any device is touched: it names no input and no other output of the run
+static int check_rstats_args(const nh_run_args *a, const nh_run_extras *x, const char *path) {
+    if (!path) return NH_OK;
+    if (!a) return set_error(NH_EINVAL, "nh_run_rstats: null arguments");
+    if (!path[0]) return set_error(NH_EINVAL, "nh_run_rstats: read_stats_path is an empty path");
+    struct stat sl;
+    const bool ls = stat(path, &sl) == 0 && S_ISREG(sl.st_mode);
+    auto same = [&](const char *p) {
+        struct stat sp;
+        return p && p[0] && (!strcmp(p, path) || (ls && stat(p, &sp) == 0 && sp.st_dev == sl.st_dev && sp.st_ino == sl.st_ino));
+    };
+    for (const char *p : {a->in1, a->in2})
+        if (same(p)) return set_error(NH_EINVAL, "nh_run_rstats: the read statistics table %s is the input %s", path, p);
+    for (const char *p : {a->out1, a->out2, a->kraken_output, a->report, x ? x->human_out1 : nullptr, x ? x->human_out2 : nullptr,
+                          x ? x->calls : nullptr, x ? x->human_ids : nullptr})
+        if (same(p)) return set_error(NH_EINVAL, "nh_run_rstats: the read statistics table %s is also the output %s", path, p);
+    return NH_OK;
+}
+
 // hout1 set: a split run (nh_run_split) -- a->keep_human is 0, hout1 / hout2 receive the classified records
 // mask: a masked run (nh_run_mask) -- a->keep_human is 0, out1 / out2 receive every record, a classified one's bases as 'N'
 // calls / ids set (nh_run_ex): the calls table / the human read ids, built in HBM beside whatever else the run writes
 // minq > 0 (nh_run_minq): kraken2's --minimum-base-quality -- the classifier reads a copy of each batch's sequences in which the
 // bases of a FASTQ record with a quality below minq are 'N' (k_qmask, in front of it on the slot's stream); every output is made
 // from the batch's text as before, so the records written keep their bases.  0: nothing of this runs.
+// rs_path / rs_out set (nh_run_rstats): read statistics -- k_rstats behind the classifier on the slot's stream adds every sequence
+// of the batch to the device's four accumulators (nh_rstats.hip), fetched once, at the end; the writer keeps the lengths by class
+// for median and N50.  Both NULL: nothing of this runs.
 int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_stats *stats, const char *hout1 = nullptr,
                 const char *hout2 = nullptr, bool mask = false, const char *calls = nullptr, const char *ids = nullptr,
-                uint32_t minq = 0) {
+                uint32_t minq = 0, const char *rs_path = nullptr, nh_read_stats *rs_out = nullptr) {
     if (!a || !a->in1 || !a->out1) return set_error(NH_EINVAL, "nh_run: in1 and out1 are required");
     if (engines.empty()) return set_error(NH_EINVAL, "nh_run: no engine");
     const bool split = hout1 != nullptr;
     const bool lists = calls || ids;
     const bool qm = minq > 0;
+    const bool rst = rs_path || rs_out;
     if (minq > 93) return set_error(NH_EINVAL, "nh_run: minimum base quality %u is not in 0..93 (Phred+33)", minq);
     if (lists) {
         const int vrc = check_list_args(a, hout1, hout2, calls, ids);
+        if (vrc) return vrc;
+    }
+    if (rs_path) {
+        nh_run_extras x{};
+        x.human_out1 = hout1, x.human_out2 = hout2, x.calls = calls, x.human_ids = ids;
+        const int vrc = check_rstats_args(a, &x, rs_path);
         if (vrc) return vrc;
     }
     if (mask) {
@@ -1228,13 +1270,17 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
     auto t0 = std::chrono::steady_clock::now();
 
     rs.d_run_counters.assign((size_t)G, nullptr);
+    // read statistics: one block of four accumulators per device of the run, zeroed with min_len all-ones
+    std::vector<unsigned long long *> d_racc((size_t)G, nullptr);
+    std::vector<nh_read_class> racc;  // the devices' blocks summed: [class][mate]
     auto free_run_counters = [&] {
-        for (int g = 0; g < G; g++)
-            if (rs.d_run_counters[g]) {
-                (void)dev_set(engines[g]->device);
-                (void)hipFree(rs.d_run_counters[g]);
-                rs.d_run_counters[g] = nullptr;
-            }
+        for (int g = 0; g < G; g++) {
+            if (!rs.d_run_counters[g] && !d_racc[g]) continue;
+            (void)dev_set(engines[g]->device);
+            if (rs.d_run_counters[g]) (void)hipFree(rs.d_run_counters[g]);
+            if (d_racc[g]) (void)hipFree(d_racc[g]);
+            rs.d_run_counters[g] = nullptr, d_racc[g] = nullptr;
+        }
     };
     for (int g = 0; g < G; g++) {
         const size_t nb = (CNT_N + 12) * sizeof(uint64_t);  // (+12: the words of the instrumented kernel variant)
@@ -1242,6 +1288,15 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
             hipMemset(rs.d_run_counters[g], 0, nb) != hipSuccess) {
             free_run_counters();
             return set_error(NH_EDEVICE, "cannot allocate the run's counters on device %d", engines[g]->device);
+        }
+        if (rst) {
+            nh_read_class init[4];
+            memset(init, 0, sizeof init);
+            for (nh_read_class &c : init) c.min_len = ~0ull;
+            if (dev_malloc((void **)&d_racc[g], sizeof init) != hipSuccess || hipMemcpy(d_racc[g], init, sizeof init, hipMemcpyHostToDevice) != hipSuccess) {
+                free_run_counters();
+                return set_error(NH_EDEVICE, "cannot allocate the read statistics' accumulators on device %d", engines[g]->device);
+            }
         }
     }
     // stream slots a device: two keep the classifier busy; a third lets the copy of a batch's text back to the host (batches
@@ -1262,7 +1317,9 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
             (lists && getenv("NOHUMAN_TRACE") &&
              (hipEventCreate(&slots[i].cev[0]) != hipSuccess || hipEventCreate(&slots[i].cev[1]) != hipSuccess)) ||
             (qm && getenv("NOHUMAN_TRACE") &&
-             (hipEventCreate(&slots[i].qev[0]) != hipSuccess || hipEventCreate(&slots[i].qev[1]) != hipSuccess))) {
+             (hipEventCreate(&slots[i].qev[0]) != hipSuccess || hipEventCreate(&slots[i].qev[1]) != hipSuccess)) ||
+            (rst && getenv("NOHUMAN_TRACE") &&
+             (hipEventCreate(&slots[i].rev[0]) != hipSuccess || hipEventCreate(&slots[i].rev[1]) != hipSuccess))) {
             for (auto &s : slots) slot_free(s);
             free_run_counters();
             return set_error(NH_EDEVICE, "cannot create streams");
@@ -1556,6 +1613,24 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                         float ms = 0;
                         if (hipEventElapsedTime(&ms, s.qev[0], s.qev[1]) == hipSuccess) rs.qmask_kernel_ms += ms;
                     }
+                    if (rst && s.rev[1]) {
+                        float ms = 0;
+                        if (hipEventElapsedTime(&ms, s.rev[0], s.rev[1]) == hipSuccess) rs.rstats_kernel_ms += ms;
+                    }
+                    // read statistics: every length of the batch, by the class of its fragment and its mate
+                    for (size_t i = 0; rst && i < b.n; i++) {
+                        const int c = s.h_res[i].call != 0;
+                        for (int m = 0; m < mates; m++) {
+                            const uint64_t L = s.h_len[i * mates + m];
+                            if (L >= (1u << 20)) {
+                                rs.len_long[c][m][L]++;
+                                continue;
+                            }
+                            std::vector<uint64_t> &h = rs.len_hist[c][m];
+                            if (L >= h.size()) h.resize(std::max<size_t>(L + 1, std::min<size_t>(2 * h.size(), 1u << 20)), 0);
+                            h[L]++;
+                        }
+                    }
                     for (int o = 0; lists && o < 2 && !wrc; o++) {
                         const size_t tot = (size_t)s.h_ctotal[o];
                         rs.list_bytes[o] += tot;
@@ -1700,14 +1775,17 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 rc = slot_reserve_calls(s, b.n, mates, out_cap);
             }
             if (!rc && qm) rc = slot_reserve_qmask(s, ntext, b.n * (size_t)mates);
-            // kraken2 ends a run at a FASTQ record whose quality line is not as long as its sequence when it masks by quality
-            for (size_t i = 0; qm && !rc && i < b.n; i++)
+            if (!rc && rst) rc = slot_reserve_rec(s, b.n * (size_t)mates);
+            // kraken2 ends a run at a FASTQ record whose quality line is not as long as its sequence when it masks by quality;
+            // the read statistics count a base per quality as well
+            for (size_t i = 0; (qm || rst) && !rc && i < b.n; i++)
                 for (int m = 0; m < mates && !rc; m++) {
                     const HalfBatch &hb = m ? *b.h2 : *b.h1;
                     const RecRef &r = hb.recs[(m ? b.off2 : b.off1) + i];
                     if (hb.format == FMT_FASTQ && r.qlen != r.slen)
-                        rc = set_error(NH_EIO, "%s, read %llu: sequence length (%u) != quality string length (%u), which --minimum-base-quality cannot mask",
-                                       m ? a->in2 : a->in1, (unsigned long long)(frags_out + i + 1), r.slen, r.qlen);
+                        rc = set_error(NH_EIO, "%s, read %llu: sequence length (%u) != quality string length (%u), which %s",
+                                       m ? a->in2 : a->in1, (unsigned long long)(frags_out + i + 1), r.slen, r.qlen,
+                                       qm ? "--minimum-base-quality cannot mask" : "--read-stats cannot count");
                 }
             if (rc) {
                 rs.fail(rc, g_last_error);
@@ -1722,7 +1800,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 s.h_len[i * mates] = r1.slen;
                 nbases += r1.slen;
                 if (lists) s.h_idl[i] = r1.idlen;
-                if (split || mask || lists || qm) {
+                if (split || mask || lists || qm || rst) {
                     uint32_t *hr = s.h_rec + 4 * i * mates;
                     hr[0] = r1.h, hr[1] = r1.hlen, hr[2] = r1.q, hr[3] = r1.qlen;
                     if (rs.paired) {
@@ -1776,7 +1854,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 he = hipMemcpyAsync(s.d_len, s.h_len, b.n * mates * 4, hipMemcpyHostToDevice, s.stream);
             if (he == hipSuccess && rs.want_k)
                 he = hipMemcpyAsync(s.d_taxa_off, s.h_taxa_off, (b.n + 1) * 8, hipMemcpyHostToDevice, s.stream);
-            if (he == hipSuccess && (split || mask || lists || qm))
+            if (he == hipSuccess && (split || mask || lists || qm || rst))
                 he = hipMemcpyAsync(s.d_rec, s.h_rec, b.n * mates * 16, hipMemcpyHostToDevice, s.stream);
             if (he == hipSuccess && lists)
                 he = hipMemcpyAsync(s.d_idl, s.h_idl, b.n * 4, hipMemcpyHostToDevice, s.stream);
@@ -1809,6 +1887,25 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                                      rs.want_k ? s.d_taxa : nullptr, rs.want_k ? s.d_taxa_off : nullptr,
                                      rs.d_run_counters[(size_t)(si / NS)], s.stream, s.d_len, ntext);
                 if (rc) rs.fail(rc, g_last_error);
+            }
+            if (!rs.failed() && rst) {  // the read statistics, counted behind the classifier on the same stream: the INPUT's bases
+                RstatsArgs ta{};
+                ta.text = (const char *)s.d_text;
+                ta.ntext = ntext;
+                ta.seq_off = (const uint64_t *)s.d_off;
+                ta.seq_len = (const uint32_t *)s.d_len;
+                ta.rec = (const uint32_t *)s.d_rec;
+                ta.n = b.n * (uint64_t)mates;
+                ta.mates = mates;
+                ta.fastq[0] = b.h1->format == FMT_FASTQ;
+                ta.fastq[1] = rs.paired && b.h2->format == FMT_FASTQ;
+                ta.res = (const nh_result *)s.d_res;
+                ta.acc = d_racc[(size_t)(si / NS)];
+                ta.error = s.e->d_error + LAUNCH_SLOTS;
+                if (s.rev[0]) (void)hipEventRecord(s.rev[0], s.stream);
+                he = launch_rstats(ta, s.e->n_cu, 0, s.stream);
+                if (s.rev[1] && he == hipSuccess) he = hipEventRecord(s.rev[1], s.stream);
+                if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("read statistics: ") + hipGetErrorString(he));
             }
             uint64_t *d_ctotal = nullptr;
             if (!rs.failed() && lists) {  // the calls table and the human ids, built behind the classifier on the same stream
@@ -1935,6 +2032,25 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
             unsigned long long c = 0;
             if (dev_set(s.e->device) == hipSuccess && hipMemcpy(&c, s.d_qcnt, 8, hipMemcpyDeviceToHost) == hipSuccess) rs.qmask_masked += c;
         }
+    if (rst && rs.err_code == NH_OK) {  // the devices' accumulators, once: rows summed on the host
+        racc.assign(4, nh_read_class{});
+        for (nh_read_class &c : racc) c.min_len = ~0ull;
+        for (int g = 0; g < G && rs.err_code == NH_OK; g++) {
+            nh_read_class part[4];
+            if (dev_set(engines[g]->device) != hipSuccess || hipMemcpy(part, d_racc[g], sizeof part, hipMemcpyDeviceToHost) != hipSuccess) {
+                rs.fail(NH_EDEVICE, "reading the read statistics' accumulators failed");
+                break;
+            }
+            for (int k = 0; k < 4; k++) {
+                const uint64_t *src = (const uint64_t *)&part[k];
+                uint64_t *dst = (uint64_t *)&racc[k];
+                for (size_t w = 0; w < sizeof(nh_read_class) / 8; w++)
+                    if (w == 2) dst[w] = std::min(dst[w], src[w]);
+                    else if (w == 3) dst[w] = std::max(dst[w], src[w]);
+                    else dst[w] += src[w];
+            }
+        }
+    }
     for (auto &s : slots) slot_free(s);
     if (const char *tr = getenv("NOHUMAN_TRACE")) {
         if (tr[0] == '1') {
@@ -1961,6 +2077,9 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
             if (qm)
                 fprintf(stderr, "[nohuman trace] qmask: Q %u, %llu of %llu bases masked, kernel %.3f ms\n", minq,
                         (unsigned long long)rs.qmask_masked, (unsigned long long)rs.total_bases, rs.qmask_kernel_ms);
+            if (rst && racc.size() == 4)
+                fprintf(stderr, "[nohuman trace] rstats: %llu bases, kernel %.3f ms\n",
+                        (unsigned long long)(racc[0].bases + racc[1].bases + racc[2].bases + racc[3].bases), rs.rstats_kernel_ms);
             if (g_pageable_batches.load())
                 fprintf(stderr, "[nohuman trace] %d batch buffers could not be page-locked (pageable memory used)\n",
                         g_pageable_batches.load());
@@ -2066,6 +2185,39 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
     if (rs.want_k && (rc = ok.close())) return rc;
     if (calls && (rc = oc.close())) return rc;
     if (ids && (rc = oi.close())) return rc;
+    if (rst) {
+        nh_read_stats out;
+        memset(&out, 0, sizeof out);
+        out.mates = mates;
+        uint64_t dev_reads = 0, dev_bases = 0, host_reads = 0, host_bases = 0;
+        for (int m = 0; m < mates; m++) {
+            std::vector<std::pair<uint64_t, uint64_t>> lens[3];  // (length, reads) ascending: input, non-human, human
+            for (int c = 0; c < 2; c++) {
+                nh_read_class &k = out.cls[c][m];
+                k = racc[(size_t)(2 * c + m)];
+                if (!k.reads) k.min_len = 0;
+                dev_reads += k.reads, dev_bases += k.bases;
+                const std::vector<uint64_t> &h = rs.len_hist[c][m];
+                for (size_t L = 0; L < h.size(); L++)
+                    if (h[L]) lens[1 + c].push_back({L, h[L]});
+                for (const auto &p : rs.len_long[c][m]) lens[1 + c].push_back(p);
+                for (const auto &p : lens[1 + c]) host_reads += p.second, host_bases += p.first * p.second;
+            }
+            // the input: the union of the two classes (both ascending)
+            std::map<uint64_t, uint64_t> all;
+            for (int c = 1; c < 3; c++)
+                for (const auto &p : lens[c]) all[p.first] += p.second;
+            lens[0].assign(all.begin(), all.end());
+            for (int set = 0; set < 3; set++) length_summary(lens[set], &out.median_len[set][m], &out.n50[set][m]);
+        }
+        // (the lengths the writer kept are the checker of what the devices counted, as for the run's counters)
+        if (dev_reads != host_reads || dev_bases != host_bases || dev_reads != rs.total * (uint64_t)mates)
+            return set_error(NH_EDEVICE, "read statistics: the devices counted %llu reads / %llu bases, the writer %llu / %llu",
+                             (unsigned long long)dev_reads, (unsigned long long)dev_bases, (unsigned long long)host_reads,
+                             (unsigned long long)host_bases);
+        if (rs_path && (rc = nh_read_stats_write(&out, rs_path))) return rc;
+        if (rs_out) *rs_out = out;
+    }
     if (stats) {
         nh_stats st;
         memset(&st, 0, sizeof st);
@@ -2080,9 +2232,10 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
 }
 
 int run_engine(Engine *e, const nh_run_args *a, nh_stats *stats, const char *hout1 = nullptr, const char *hout2 = nullptr,
-               bool mask = false, const char *calls = nullptr, const char *ids = nullptr, uint32_t minq = 0) {
+               bool mask = false, const char *calls = nullptr, const char *ids = nullptr, uint32_t minq = 0,
+               const char *rs_path = nullptr, nh_read_stats *rs_out = nullptr) {
     std::vector<Engine *> v{e};
-    return run_engines(v, a, stats, hout1, hout2, mask, calls, ids, minq);
+    return run_engines(v, a, stats, hout1, hout2, mask, calls, ids, minq, rs_path, rs_out);
 }
 
 // nh_run_minq's own argument, checked before any device is touched: the highest printable quality is '~', Phred 93
@@ -2103,6 +2256,14 @@ int check_extras(const nh_run_args *a, const nh_run_extras *x) {
     else if (x->human_out1 || x->human_out2) rc = check_split_args(a, x->human_out1, x->human_out2);
     if (rc) return rc;
     return check_list_args(a, x->human_out1, x->human_out2, x->calls, x->human_ids);
+}
+
+// nh_run_rstats' arguments, checked before any device is touched: nh_run_minq's, then the table's path
+int check_rstats(const nh_run_args *a, const nh_run_extras *x, uint32_t minq, const char *rs_path) {
+    int rc = check_minq(minq);
+    if (!rc && x) rc = check_extras(a, x);
+    if (!rc) rc = check_rstats_args(a, x, rs_path);
+    return rc;
 }
 
 }  // namespace nh
@@ -2146,6 +2307,17 @@ int nh_run_engine_minq(nh_engine *e, const nh_run_args *args, const nh_run_extra
                           extras->human_ids, min_base_quality);
 }
 
+int nh_run_engine_rstats(nh_engine *e, const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality,
+                         const char *read_stats_path, nh_read_stats *out, nh_stats *stats) {
+    const int rc = nh::check_rstats(args, extras, min_base_quality, read_stats_path);
+    if (rc) return rc;
+    if (!e) return nh::set_error(NH_EINVAL, "null engine");
+    if (!extras)
+        return nh::run_engine((nh::Engine *)e, args, stats, nullptr, nullptr, false, nullptr, nullptr, min_base_quality, read_stats_path, out);
+    return nh::run_engine((nh::Engine *)e, args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls,
+                          extras->human_ids, min_base_quality, read_stats_path, out);
+}
+
 int nh_fastx_scan(const char *path, uint64_t *n_records, uint64_t *n_bases, uint64_t *digest) {
     if (!path || !n_records || !n_bases || !digest) return nh::set_error(NH_EINVAL, "null argument");
     nh::BlockReader r;
@@ -2183,7 +2355,8 @@ int nh_fastx_scan(const char *path, uint64_t *n_records, uint64_t *n_bases, uint
 // Whole run on one or several devices: the database is loaded into every device's HBM, batches go
 // round-robin, outputs stay in input order, the counts are summed on the host.
 static int run_devices(const nh_run_args *args, nh_stats *stats, const char *hout1, const char *hout2, bool mask = false,
-                       const char *calls = nullptr, const char *ids = nullptr, uint32_t minq = 0) {
+                       const char *calls = nullptr, const char *ids = nullptr, uint32_t minq = 0, const char *rs_path = nullptr,
+                       nh_read_stats *rs_out = nullptr) {
     if (!args || !args->db_dir) return nh::set_error(NH_EINVAL, "nh_run: db_dir is required");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -2219,7 +2392,7 @@ static int run_devices(const nh_run_args *args, nh_stats *stats, const char *hou
     }
     const double t_load = since(t_begin);
     const auto t_run = std::chrono::steady_clock::now();
-    if (!rc) rc = nh::run_engines(engines, args, stats, hout1, hout2, mask, calls, ids, minq);
+    if (!rc) rc = nh::run_engines(engines, args, stats, hout1, hout2, mask, calls, ids, minq, rs_path, rs_out);
     const double s_run = since(t_run);
     std::string keep = nh::g_last_error;
     const auto t_close = std::chrono::steady_clock::now();
@@ -2258,6 +2431,15 @@ int nh_run_minq(const nh_run_args *args, const nh_run_extras *extras, uint32_t m
     if (!extras) return run_devices(args, stats, nullptr, nullptr, false, nullptr, nullptr, min_base_quality);
     return run_devices(args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls, extras->human_ids,
                        min_base_quality);
+}
+
+int nh_run_rstats(const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality, const char *read_stats_path,
+                  nh_read_stats *out, nh_stats *stats) {
+    const int rc = nh::check_rstats(args, extras, min_base_quality, read_stats_path);  // (before any device is touched)
+    if (rc) return rc;
+    if (!extras) return run_devices(args, stats, nullptr, nullptr, false, nullptr, nullptr, min_base_quality, read_stats_path, out);
+    return run_devices(args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls, extras->human_ids,
+                       min_base_quality, read_stats_path, out);
 }
 
 }  // extern "C"

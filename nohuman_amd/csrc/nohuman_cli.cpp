@@ -220,6 +220,7 @@ struct Args {
     bool mask = false;  // masked run: every read written, the human ones' bases as N (nh_run_mask)
     std::string calls, human_ids;  // read lists (nh_run_ex): a table line per read; the ids of the human reads
     unsigned min_base_quality = 0;  // kraken2's --minimum-base-quality (nh_run_minq); 0: off
+    std::string read_stats;         // the read statistics table (nh_run_rstats)
     bool has_out1 = false, has_out2 = false, check = false, download = false, list = false, human = false;
     bool has_type = false;
     Codec type = C_NONE;
@@ -251,6 +252,7 @@ static void usage(FILE *f) {
           "  -k, --kraken-output <FILE>   Write the Kraken2 read classification output to a file\n"
           "  -r, --kraken-report <FILE>   Write the Kraken2 report with aggregate counts/clade to file\n"
           "      --calls <FILE>           Write a table with one line per read: C/U, id, taxid, length(s), k-mers, clade hits (hits / k-mers is the confidence -C thresholds), hit groups\n"
+          "      --read-stats <FILE>      Write a QC table of all, non-human and human reads per mate: reads, bases, min/mean/median/max length, N50, GC %, other bases, Q20 %, Q30 %, mean quality (counted on the GPU in the same pass)\n"
           "      --human-ids <FILE>       Write the ids of the human reads, one per line\n"
           "  -v, --verbose                Set the logging level to verbose\n"
           "  -h, --help                   Print help\n"
@@ -332,6 +334,7 @@ static Args parse_args(int argc, char **argv) {
         else if (s == "-r" || s == "--kraken-report") a.kraken_report = val();
         else if (s == "--calls") a.calls = val();
         else if (s == "--human-ids") a.human_ids = val();
+        else if (s == "--read-stats") a.read_stats = val();
         else if (s == "-v" || s == "--verbose") g_verbose = true;
         else if (s == "-h" || s == "--help") { usage(stdout); exit(0); }
         else if (s == "-V" || s == "--version") { puts("nohuman 0.5.1 (MI355X engine)"); exit(0); }
@@ -363,6 +366,10 @@ static Args parse_args(int argc, char **argv) {
     }
     if (!a.calls.empty() && a.calls == a.human_ids)
         arg_error("the arguments '--calls <FILE>' and '--human-ids <FILE>' name the same file: %s", a.calls.c_str());
+    for (const std::string *o : {&a.calls, &a.human_ids})
+        if (!a.read_stats.empty() && a.read_stats == *o)
+            arg_error("the argument '--read-stats <FILE>' names the same file as '%s <FILE>': %s", o == &a.calls ? "--calls" : "--human-ids",
+                      a.read_stats.c_str());
     return a;
 }
 
@@ -510,6 +517,8 @@ int main(int argc, char **argv) {
     const std::string cpart = args.calls.empty() ? "" : staged(args.calls), ipart = args.human_ids.empty() ? "" : staged(args.human_ids);
     if (!args.calls.empty()) staged_files.push_back({args.calls, cpart});
     if (!args.human_ids.empty()) staged_files.push_back({args.human_ids, ipart});
+    const std::string spart = args.read_stats.empty() ? "" : staged(args.read_stats);
+    if (!args.read_stats.empty()) staged_files.push_back({args.read_stats, spart});
     staged_files.push_back({out1, part1});
     if (paired) staged_files.push_back({out2, part2});
     auto unlink_staged = [&] {
@@ -544,7 +553,8 @@ int main(int argc, char **argv) {
     rx.human_out1 = hp1, rx.human_out2 = hp2;
     rx.calls = args.calls.empty() ? nullptr : cpart.c_str();
     rx.human_ids = args.human_ids.empty() ? nullptr : ipart.c_str();
-    const int run_rc = args.min_base_quality ? nh_run_minq(&ra, lists || args.mask || split ? &rx : nullptr, args.min_base_quality, &st)
+    const int run_rc = !args.read_stats.empty() ? nh_run_rstats(&ra, lists || args.mask || split ? &rx : nullptr, args.min_base_quality, spart.c_str(), nullptr, &st)
+                       : args.min_base_quality ? nh_run_minq(&ra, lists || args.mask || split ? &rx : nullptr, args.min_base_quality, &st)
                        : lists     ? nh_run_ex(&ra, &rx, &st)
                        : args.mask ? nh_run_mask(&ra, hp1, hp2, &st)
                        : split     ? nh_run_split(&ra, hp1, hp2, &st)
@@ -588,6 +598,7 @@ int main(int argc, char **argv) {
         INFO("Kraken output file written to: %s", quoted(args.kraken_output).c_str());
     if (!args.calls.empty()) INFO("Calls table written to: %s", quoted(args.calls).c_str());
     if (!args.human_ids.empty()) INFO("Human read ids written to: %s", quoted(args.human_ids).c_str());
+    if (!args.read_stats.empty()) INFO("Read statistics written to: %s", quoted(args.read_stats).c_str());
     if (!args.kraken_report.empty()) INFO("Kraken report file written to: %s", quoted(args.kraken_report).c_str());
     INFO("Done.");
     return 0;

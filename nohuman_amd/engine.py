@@ -42,7 +42,7 @@ def probe() -> str:
 def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None, confidence: float = 0.0,
         threads: int = 1, keep_human: bool = False, device_ids=None, out_codec: int = 0,
         codec_threads: int = 0, human_out1=None, human_out2=None, mask: bool = False, calls=None,
-        human_ids=None, min_base_quality: int = 0) -> "_lib.nh_stats":
+        human_ids=None, min_base_quality: int = 0, read_stats=None) -> "_lib.nh_stats":
     """nh_run: whole run, database loaded into every listed device (default: all visible).  human_out1 (and, paired,
     human_out2) given: nh_run_split -- the non-human reads go to out1 / out2 and, in the same pass, the human reads to
     human_out1 / human_out2 exactly as a keep_human run would write them.  mask: nh_run_mask -- every read goes to
@@ -52,7 +52,10 @@ def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
     line per fragment, C/U, id, taxid, length(s), total_kmers, clade_hits, hit_groups, tab-separated (clade_hits /
     total_kmers is the confidence that `confidence` thresholds); human_ids: the id of every human fragment.
     min_base_quality (nh_run_minq; kraken2's --minimum-base-quality, 0..93): a base of a FASTQ record with a Phred+33 quality
-    below it is classified as an ambiguous base; every record written keeps its bases.  0: exactly the run without it."""
+    below it is classified as an ambiguous base; every record written keeps its bases.  0: exactly the run without it.
+    read_stats (nh_run_rstats; any kind of run): a path, or a ReadStats -- the QC summary of all, non-human and human reads per
+    mate (reads, bases, lengths, N50, GC, quality histogram), counted on the GPU in the same pass; the table goes to the path,
+    the numbers into the ReadStats."""
     a = _lib.nh_run_args()
     a.db_dir = os.fsencode(db_dir)
     a.in1 = os.fsencode(in1)
@@ -75,7 +78,11 @@ def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
         a.n_devices = 0
         a.device_ids = None
     s = _lib.nh_stats()
-    if min_base_quality:
+    if read_stats is not None:
+        rs = _read_stats(read_stats)
+        _check(_lib.lib().nh_run_rstats(C.byref(a), _extras_or_none(mask, human_out1, human_out2, calls, human_ids),
+                                        _minq(min_base_quality), _path_or_none(rs.path), C.byref(rs.raw), C.byref(s)))
+    elif min_base_quality:
         _check(_lib.lib().nh_run_minq(C.byref(a), _extras_or_none(mask, human_out1, human_out2, calls, human_ids),
                                       _minq(min_base_quality), C.byref(s)))
     elif calls is not None or human_ids is not None:
@@ -117,6 +124,26 @@ def _minq(q) -> int:
     if q < 0:
         raise EngineError(-1, "minimum base quality %d is not in 0..93 (Phred+33)" % q)
     return min(q, 0xFFFFFFFF)
+
+
+class ReadStats:
+    """What a run with read statistics counted (nh_read_stats): `raw` is the C struct -- raw.cls[class][mate] with class 0
+    non-human, 1 human (reads, bases, min_len, max_len, gc, other, qual_reads, qual_bases, qhist[94]), raw.median_len[set][mate]
+    and raw.n50[set][mate] with set 0 input, 1 non-human, 2 human, raw.mates.  `path`: where the run also writes the table (None:
+    nowhere).  The definitions are the project's own (include/nohuman_engine.h), not seqkit's."""
+
+    def __init__(self, path=None):
+        self.path = path
+        self.raw = _lib.nh_read_stats()
+
+    def write(self, path):
+        """the table of these numbers (nh_read_stats_write; no GPU needed)"""
+        _check(_lib.lib().nh_read_stats_write(C.byref(self.raw), os.fsencode(path)))
+
+
+def _read_stats(v) -> "ReadStats":
+    """run(read_stats=...): a ReadStats as it is, a path as a ReadStats that writes there"""
+    return v if isinstance(v, ReadStats) else ReadStats(v)
 
 
 def device_count() -> int:
@@ -306,6 +333,15 @@ class Engine:
         _check(self._L.nh_quality_mask_device(self._h, d_text, text_len, d_seq_starts, d_seq_lens, d_qual_starts, n_seq,
                                               _minq(min_base_quality), d_out, d_masked or None, stream or None))
 
+    def read_stats_device(self, d_text: int, text_len: int, d_seq_starts: int, d_seq_lens: int, d_qual_starts: int,
+                          d_results: int, n_frag: int, d_acc: int, paired: bool = False, max_workgroups: int = 0, stream: int = 0):
+        """The read statistics' counting pass behind classify_records_device (nh_read_stats_device): every sequence adds its
+        reads, bases, length extrema, GC, other bases and quality histogram to d_acc[class][mate] -- four nh_read_class (102
+        uint64 each) the caller zeroed, min_len all-ones -- class 1 where d_results[i / mates].call != 0.  The arrays are those of
+        quality_mask_device.  Asynchronous on `stream`."""
+        _check(self._L.nh_read_stats_device(self._h, d_text, text_len, d_seq_starts, d_seq_lens, d_qual_starts, d_results, n_frag,
+                                            FLAG_PAIRED if paired else 0, d_acc, int(max_workgroups), stream or None))
+
     def add_sequences(self, d_bases: int, d_seq_offsets: int, n_seq: int, value: int, stream: int = 0):
         """Bench/test support: insert the minimizers of device-resident sequences into the table."""
         _check(self._L.nh_synthetic_add_sequences(self._h, d_bases, d_seq_offsets, n_seq, value,
@@ -323,9 +359,10 @@ class Engine:
     def run(self, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
             confidence: float = 0.0, threads: int = 1, keep_human: bool = False, out_codec: int = 0,
             codec_threads: int = 0, human_out1=None, human_out2=None, mask: bool = False, calls=None,
-            human_ids=None, min_base_quality: int = 0) -> _lib.nh_stats:
+            human_ids=None, min_base_quality: int = 0, read_stats=None) -> _lib.nh_stats:
         """nh_run_engine; with human_out1 (and, paired, human_out2): nh_run_engine_split; mask: nh_run_engine_mask; with
-        calls / human_ids: nh_run_engine_ex; with min_base_quality: nh_run_engine_minq -- as run() above."""
+        calls / human_ids: nh_run_engine_ex; with min_base_quality: nh_run_engine_minq; with read_stats:
+        nh_run_engine_rstats -- as run() above."""
         a = _lib.nh_run_args()
         a.db_dir = None
         a.in1 = os.fsencode(in1)
@@ -342,7 +379,11 @@ class Engine:
         a.out_codec = int(out_codec)
         a.codec_threads = int(codec_threads)
         s = _lib.nh_stats()
-        if min_base_quality:
+        if read_stats is not None:
+            rs = _read_stats(read_stats)
+            _check(self._L.nh_run_engine_rstats(self._h, C.byref(a), _extras_or_none(mask, human_out1, human_out2, calls, human_ids),
+                                                _minq(min_base_quality), _path_or_none(rs.path), C.byref(rs.raw), C.byref(s)))
+        elif min_base_quality:
             _check(self._L.nh_run_engine_minq(self._h, C.byref(a), _extras_or_none(mask, human_out1, human_out2, calls, human_ids),
                                               _minq(min_base_quality), C.byref(s)))
         elif calls is not None or human_ids is not None:

@@ -101,7 +101,7 @@ class CommandRunner:
         """The kraken2 options nohuman emits (src/main.rs:215-267) -> dict."""
         opts = {"threads": 1, "db": None, "output": None, "confidence": 0.0, "report": None,
                 "paired": False, "classified_out": None, "unclassified_out": None, "inputs": [],
-                "calls": None, "human_ids": None, "minimum_base_quality": 0}
+                "calls": None, "human_ids": None, "minimum_base_quality": 0, "read_stats": None}
         it = iter(args)
         for a in it:
             if a == "--threads":
@@ -129,6 +129,8 @@ class CommandRunner:
                 opts["calls"] = next(it)
             elif a == "--human-ids":
                 opts["human_ids"] = next(it)
+            elif a == "--read-stats":  # (the engine's own as well: nohuman --read-stats)
+                opts["read_stats"] = next(it)
             elif a.startswith("--"):
                 raise OSError("%s failed with stderr Unknown option: %s" % ("kraken2", a))
             else:
@@ -196,6 +198,8 @@ class CommandRunner:
             s = _lib.nh_stats()
             L = _lib.lib()
             minq = o["minimum_base_quality"]
+            rstats = os.fsencode(o["read_stats"]) if o["read_stats"] is not None else None
+            x = None
             if o["calls"] is not None or o["human_ids"] is not None:
                 if o["calls"] is not None and o["calls"] == o["human_ids"]:
                     raise EngineError(-1, "--calls and --human-ids name the same file: %s" % o["calls"])
@@ -203,6 +207,9 @@ class CommandRunner:
                 x.struct_size = C.sizeof(_lib.nh_run_extras)
                 x.calls = os.fsencode(o["calls"]) if o["calls"] is not None else None
                 x.human_ids = os.fsencode(o["human_ids"]) if o["human_ids"] is not None else None
+            if rstats is not None:
+                rc = L.nh_run_rstats(C.byref(a), C.byref(x) if x is not None else None, minq, rstats, None, C.byref(s))
+            elif x is not None:
                 if minq:
                     rc = L.nh_run_minq(C.byref(a), C.byref(x), minq, C.byref(s))
                 else:
