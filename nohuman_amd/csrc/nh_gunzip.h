@@ -123,6 +123,9 @@ public:
     int next_batch(HalfBatch &hb, size_t max_recs, size_t max_text = 0);
     uint64_t records_handed() const;
     const std::string &handover_reason() const;  // empty: "not ours" (no FASTQ)
+    // For the tests (nh_debug_reader_dump): where the body of every piece decoded so far begins, as an offset into the
+    // inflated stream -- what was carried over from the piece before lies in front of it.
+    std::vector<uint64_t> piece_starts() const;
     void close();  // waits until every batch handed out has been released
 
 private:

@@ -2813,6 +2813,10 @@ public:
 
     uint64_t records_handed() const { return handed_recs_; }
     const std::string &handover_reason() const { return reason_; }  // (set by the next_batch() call that returned 1)
+    std::vector<uint64_t> piece_starts() {
+        std::lock_guard<std::mutex> lk(mu_);
+        return piece_starts_;
+    }
 
     void close() {
         {
@@ -3184,6 +3188,8 @@ private:
         {
             std::lock_guard<std::mutex> lk(mu_);
             indexq_.push_back((size_t)(pp - &buf_[0]));
+            piece_starts_.push_back(stream_off_);
+            stream_off_ += (uint64_t)n;
         }
         cv_.notify_all();
         return 0;
@@ -3294,6 +3300,13 @@ private:
         if (!grow_dev(dev, p.d_nl, p.nl_cap, (size_t)n_lines + 4)) return fail("the record index's buffers cannot be had");
         if (n_lines) hipLaunchKernelGGL(k_nl_list, dim3(n_tiles), dim3(256), 0, stream_, (const uint8_t *)p.text0, (uint64_t)p.text_len, (const uint32_t *)p.d_tiles, p.d_nl);
         size_t n_rec = n_lines / 4;
+        bool ended_early = false;  // an empty header line or a lone "@" ended the input: what lies behind it is never looked at
+        // kraken2's message, with the whole line it saw (the host parser's, nh_fastx.cpp parse_one)
+        auto malformed = [&](size_t at, size_t len) {
+            std::vector<char> line(len);
+            if (len) (void)hipMemcpy(line.data(), p.text0 + at, len, hipMemcpyDeviceToHost);
+            return fail("malformed FASTQ file (exp. '@', saw \"" + std::string(line.begin(), line.end()) + "\"), aborting", true);
+        };
         if (n_rec) {
             const size_t nb = (n_rec + bf_ - 1) / bf_;
             if (n_rec > p.rec_cap) {
@@ -3322,24 +3335,36 @@ private:
                 const unsigned kind = (unsigned)(*h_bad_ & 3);
                 if (kind == 2) {
                     if (!handed_out_ && pieces_ == 1 && br == 0) return 1;  // no FASTQ at all (FASTA, ...): the host reader's business
-                    // kraken2's message, with the line it saw
-                    const size_t b = br / bf_;
-                    const size_t at = (size_t)p.h_bstart[b] + p.h_recs[br].h;
-                    std::vector<char> line(std::min<size_t>(p.h_recs[br].hlen, 200));
-                    (void)hipMemcpy(line.data(), p.text0 + at, line.size(), hipMemcpyDeviceToHost);
-                    return fail("malformed FASTQ file (exp. '@', saw \"" + std::string(line.begin(), line.end()) + "\"), aborting", true);
+                    return malformed((size_t)p.h_bstart[br / bf_] + p.h_recs[br].h, p.h_recs[br].hlen);
                 }
                 // an empty header line (or "@" alone): kraken2 stops reading there
                 n_rec = br;
                 p.last = true;
-                if (n_rec) {
-                    const size_t nb2 = (n_rec + bf_ - 1) / bf_;
-                    const RecRef &lr = p.h_recs[n_rec - 1];
-                    const size_t lb = (n_rec - 1) / bf_;
-                    // the end of the last record that counts: its quality line's end (+ newline)
-                    uint32_t endq = p.h_bstart[lb] + lr.q + lr.qlen;
-                    p.h_bstart[nb2] = lr.raw_end ? p.h_bstart[lb] + lr.raw_end : endq + 1;
-                }
+                ended_early = true;
+                // the last record that counts ends where the line that ended the input begins (its quality line's newline,
+                // whatever blanks stand in front of it)
+                if (n_rec) p.h_bstart[(n_rec + bf_ - 1) / bf_] = p.h_bstart[br / bf_] + p.h_recs[br].h;
+            }
+        }
+        // The input's last one to three lines are no record (kraken2 drops a record the file ends inside), but the host parser
+        // looks at a header line BEFORE it looks for the rest of the record: a first left-over line that is neither blank nor
+        // begins with '@' is malformed there, whichever reader the file's size selected.  (Blank, "@" alone, a proper header:
+        // the input ends quietly.)
+        if (p.last && !ended_early && (n_lines & 3)) {
+            uint32_t ends[2] = {0, 0};  // the newline in front of the first left-over line, and the line's own
+            const size_t l0 = 4 * n_rec;
+            if (hipStreamSynchronize(stream_) != hipSuccess ||  // (no record in the piece: the newline list is still in flight)
+                hipMemcpy(ends + (l0 ? 0 : 1), p.d_nl + (l0 ? l0 - 1 : 0), l0 ? 8 : 4, hipMemcpyDeviceToHost) != hipSuccess)
+                return fail("the newline list could not be read");
+            const size_t lb = l0 ? (size_t)ends[0] + 1 : 0;
+            size_t le = ends[1];
+            std::vector<uint8_t> line(le - lb);
+            if (le > lb && hipMemcpy(line.data(), p.text0 + lb, le - lb, hipMemcpyDeviceToHost) != hipSuccess)
+                return fail("the text's last lines could not be read");
+            while (le > lb && (line[le - lb - 1] == ' ' || (line[le - lb - 1] >= 9 && line[le - lb - 1] <= 13))) le--;
+            if (le > lb && line[0] != '@') {
+                if (!handed_out_ && pieces_ == 1 && n_rec == 0) return 1;  // nothing but that: no FASTQ at all, the host reader's business
+                return malformed(lb, le - lb);
             }
         }
         p.n_rec = n_rec;
@@ -3373,6 +3398,8 @@ private:
     bool decode_done_ = false;
     Piece *last_ = nullptr;      // the piece produced last: what it could not hand out as whole batches goes in front of the next
     uint64_t piece_no_ = 0, next_cell_ = 0;
+    std::vector<uint64_t> piece_starts_;  // (piece_starts(): where each decoded piece's body begins in the inflated stream)
+    uint64_t stream_off_ = 0;
     size_t n_dev_lanes_ = 1;  // lanes_[0, n_dev_lanes_) are devices; one more behind them: the host lane (hybrid reader)
     bool ahead_ = false;
     size_t room_ = 0, bf_ = 0;
@@ -3393,6 +3420,7 @@ int DevFastqReader::open(const char *path, const int *devices, int n_devices, st
 int DevFastqReader::next_batch(HalfBatch &hb, size_t max_recs, size_t max_text) { return impl_->next_batch(hb, max_recs, max_text); }
 uint64_t DevFastqReader::records_handed() const { return impl_->records_handed(); }
 const std::string &DevFastqReader::handover_reason() const { return impl_->handover_reason(); }
+std::vector<uint64_t> DevFastqReader::piece_starts() const { return impl_->piece_starts(); }
 void DevFastqReader::close() { impl_->close(); }
 
 }  // namespace nh

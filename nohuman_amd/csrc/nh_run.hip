@@ -2352,6 +2352,114 @@ int nh_fastx_scan(const char *path, uint64_t *n_records, uint64_t *n_bases, uint
     return NH_OK;
 }
 
+// Test hook (not part of the ABI in include/nohuman_engine.h, like nh_debug_sched): one reader driven alone -- no engine, no
+// classification, no outputs -- and what it handed out, record by record.  reader 0: the host's BlockReader; 1: DevFastqReader
+// on `device` (the batches' bytes are copied back from HalfBatch::dev_text; every batch is released).  next_batch() is called
+// until the reader reports the end of the input, hands the file over to the host reader (reported, not followed) or fails.
+//   recs     NH_DUMP_REC_WORDS words a record, in input order: hlen, idlen, slen, qlen, canonical (raw_end != 0), raw length
+//            (raw_end - h), index of its batch, digest of header / sequence / qualities (mixed like nh_fastx_scan, from the
+//            start value for every record), digest of text[h, raw_end) for a canonical record (else 0)
+//   batches  two words a batch: records, bytes of text
+//   pieces   reader 1: where each piece's body begins in the inflated stream
+//   end      0: end of the input, 1: handover (msg: handover_reason()), 2: error (msg: its text)
+// NH_EINVAL when one of the tables is too small (n_recs / n_batches / n_pieces say what it takes).
+enum { NH_DUMP_REC_WORDS = 9 };
+int nh_debug_reader_dump(const char *path, int reader, int device, uint64_t batch_recs, uint64_t max_text, uint64_t *recs, uint64_t rec_cap,
+                         uint64_t *n_recs, uint64_t *batches, uint64_t batch_cap, uint64_t *n_batches, uint64_t *pieces, uint64_t piece_cap,
+                         uint64_t *n_pieces, int *end, char *msg, uint64_t msg_cap) {
+    if (!path || !recs || !n_recs || !batches || !n_batches || !pieces || !n_pieces || !end || !msg || !msg_cap || !batch_recs || (reader != 0 && reader != 1))
+        return nh::set_error(NH_EINVAL, "nh_debug_reader_dump: bad argument");
+    auto fnv = [](const uint8_t *p, size_t len, uint64_t h) {
+        for (size_t i = 0; i < len; i++) h = (h ^ p[i]) * 0x100000001b3ull;
+        return h * 0x100000001b3ull;
+    };
+    uint64_t nr = 0, nb = 0;
+    std::vector<uint8_t> host;  // a device batch's bytes
+    std::string text;           // msg
+    bool short_text = false;
+    auto take = [&](nh::HalfBatch &hb) -> bool {  // false: the batch's bytes could not be had
+        const uint8_t *t = (const uint8_t *)hb.text.data();
+        const size_t len = hb.text.size();
+        if (hb.dev_text) {
+            host.resize(len + 1);
+            if (len && hipMemcpy(host.data(), hb.dev_text, len, hipMemcpyDeviceToHost) != hipSuccess) return false;
+            t = host.data();
+        }
+        if (nb < batch_cap) {
+            batches[2 * nb] = hb.recs.size();
+            batches[2 * nb + 1] = len;
+        }
+        for (const nh::RecRef &x : hb.recs) {
+            if ((size_t)x.h + x.hlen > len || (size_t)x.s + x.slen > len || (size_t)x.q + x.qlen > len || x.raw_end > len || (x.raw_end && x.raw_end < x.h))
+                short_text = true;  // (an offset beyond the batch's text: reported, never read)
+            else if (nr < rec_cap) {
+                uint64_t *o = recs + NH_DUMP_REC_WORDS * nr;
+                o[0] = x.hlen, o[1] = x.idlen, o[2] = x.slen, o[3] = x.qlen, o[4] = x.raw_end != 0, o[5] = x.raw_end ? x.raw_end - x.h : 0, o[6] = nb;
+                o[7] = fnv(t + x.q, x.qlen, fnv(t + x.s, x.slen, fnv(t + x.h, x.hlen, 0xcbf29ce484222325ull)));
+                o[8] = x.raw_end ? fnv(t + x.h, x.raw_end - x.h, 0xcbf29ce484222325ull) : 0;
+            }
+            nr++;
+        }
+        nb++;
+        return true;
+    };
+    *end = 0;
+    *n_pieces = 0;
+    std::string err;
+    nh::HalfBatch hb;
+    if (reader == 0) {
+        nh::BlockReader r;
+        if (r.open(path, err) != 0) return nh::set_error(NH_EIO, "%s", err.c_str());
+        for (;;) {
+            r.next_batch(hb, (size_t)batch_recs, max_text ? (size_t)max_text : (size_t)3u << 30);
+            if (!hb.error.empty()) {
+                *end = 2;
+                text = hb.error;
+                break;
+            }
+            if (!hb.recs.empty() || !hb.eof) (void)take(hb);
+            if (hb.eof) break;
+        }
+    } else {
+        nh::DevFastqReader dr;
+        const int orc = dr.open(path, device, err);
+        if (orc != 0) return nh::set_error(NH_EIO, "nh_debug_reader_dump: the reader on the GPU does not take the file (%s)", err.c_str());
+        for (;;) {
+            const int rc = dr.next_batch(hb, (size_t)batch_recs, (size_t)max_text);
+            if (rc == 1) {
+                *end = 1;
+                text = dr.handover_reason();
+                break;
+            }
+            if (!hb.error.empty()) {
+                *end = 2;
+                text = hb.error;
+                break;
+            }
+            if ((!hb.recs.empty() || !hb.eof) && !take(hb)) {
+                hb.reset();
+                dr.close();
+                return nh::set_error(NH_EDEVICE, "nh_debug_reader_dump: a batch's text could not be copied back");
+            }
+            const bool eof = hb.eof;
+            hb.reset();  // (releases the batch: the reader's close() waits for every batch it handed out)
+            if (eof) break;
+        }
+        hb.reset();
+        dr.close();  // (joins the decode stage: the list of pieces is final)
+        const std::vector<uint64_t> ps = dr.piece_starts();
+        *n_pieces = ps.size();
+        for (size_t i = 0; i < ps.size() && i < piece_cap; i++) pieces[i] = ps[i];
+    }
+    *n_recs = nr;
+    *n_batches = nb;
+    snprintf(msg, (size_t)msg_cap, "%s", text.c_str());
+    if (short_text) return nh::set_error(NH_EIO, "nh_debug_reader_dump: a record's offsets lie beyond its batch's text");
+    if (nr > rec_cap || nb > batch_cap || *n_pieces > piece_cap || text.size() >= msg_cap)
+        return nh::set_error(NH_EINVAL, "nh_debug_reader_dump: a table is too small");
+    return NH_OK;
+}
+
 // Whole run on one or several devices: the database is loaded into every device's HBM, batches go
 // round-robin, outputs stay in input order, the counts are summed on the host.
 static int run_devices(const nh_run_args *args, nh_stats *stats, const char *hout1, const char *hout2, bool mask = false,

@@ -201,6 +201,39 @@ def test_record_index_on_the_gpu_keeps_kraken2s_record_semantics(tmp_path, monke
                 assert got[3][0] == len(rs)
 
 
+def test_a_tail_that_is_no_record_ends_the_run_the_same_on_every_reader(tmp_path, monkeypatch):
+    """The host parser looks at a header line before it looks for the rest of the record: one to three last lines whose first
+    does not begin with '@' are malformed (kraken2 aborts there), with a proper header they are a record the file ends inside,
+    dropped.  The record index on the GPU used to drop both kinds, so the run's result depended on which reader the file's
+    size had selected (record by record: tests/test_gpu_record_index.py)."""
+    from nohuman_amd import Engine, EngineError
+    raw = open(os.path.join(GOLD, "reads_se.fq"), "rb").read()
+    n = raw.count(b"\n") // 4
+    monkeypatch.setenv("NOHUMAN_GZDEV_MIN_BYTES", "0")  # (no reader named: the one on the GPU is chosen)
+    cases = [(b"ACGTTGCA\n", "ACGTTGCA"), (b"Xtail \r\nACGT\n+\n", "Xtail"), (b"@tail.1 d\n", None), (b"@tail.1\nACGT\n+\n", None)]
+    for k, (tail, saw) in enumerate(cases):
+        p = tmp_path / ("t%d.fq.gz" % k)
+        p.write_bytes(gzip.compress(raw + tail, 6))
+        res = {}
+        for reader in ("host", "device", "device-text", None):
+            if reader:
+                monkeypatch.setenv("NOHUMAN_GZ_READER", reader)
+            else:
+                monkeypatch.delenv("NOHUMAN_GZ_READER")
+            o = tmp_path / ("o%d_%s" % (k, reader))
+            try:
+                with Engine.open(DB) as eng:
+                    st = eng.run(str(p), str(o), threads=4)
+                res[reader] = (st.total_sequences, st.classified, st.total_bases, o.read_bytes())
+            except EngineError as ex:
+                res[reader] = str(ex)
+        for reader, got in res.items():
+            if saw:
+                assert isinstance(got, str) and "malformed FASTQ file (exp. '@', saw \"%s\"), aborting" % saw in got, (tail, reader, got)
+            else:
+                assert got == res["host"] and got[0] == n, (tail, reader, got[:3] if not isinstance(got, str) else got)
+
+
 def test_record_index_on_the_gpu_pairs_and_classified_out(tmp_path, monkeypatch):
     raw1 = open(os.path.join(GOLD, "reads_pe_1.fq"), "rb").read()
     raw2 = open(os.path.join(GOLD, "reads_pe_2.fq"), "rb").read()

@@ -7,52 +7,9 @@ import os
 
 import pytest
 
+from tests.record_model import fnv, py_records  # (the model the record tests share)
+
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-
-
-def fnv(parts):
-    h = 0xcbf29ce484222325
-    for p in parts:
-        for b in p:
-            h = ((h ^ b) * 0x100000001b3) & 0xFFFFFFFFFFFFFFFF
-        h = ((h ^ 0) * 0x100000001b3) & 0xFFFFFFFFFFFFFFFF
-    return h
-
-
-def py_records(data: bytes):
-    """kraken2 BatchSequenceReader semantics, line by line (getline + StripString)."""
-    lines = data.split(b"\n")
-    if lines and lines[-1] == b"":
-        lines.pop()  # a final newline does not start another line
-    i, recs, fmt = 0, [], None
-    while i < len(lines):
-        h = lines[i].rstrip()
-        i += 1
-        if fmt is None:
-            fmt = "fq" if h[:1] == b"@" else "fa" if h[:1] == b">" else None
-            if fmt is None:
-                raise ValueError("unrecognized file format")
-        if fmt == "fq":
-            if not h:
-                break
-            if h[:1] != b"@":
-                raise ValueError("malformed FASTQ")
-            if len(h) <= 1 or i + 2 >= len(lines):  # sequence, '+' and quality lines must exist
-                break
-            seq, qual = lines[i].rstrip(), lines[i + 2].rstrip()
-            i += 3
-            recs.append((h, seq, qual))
-        else:
-            if h[:1] != b">":
-                raise ValueError("malformed FASTA")
-            if len(h) <= 1:
-                break
-            seq = b""
-            while i < len(lines) and lines[i][:1] != b">":
-                seq += lines[i].rstrip()
-                i += 1
-            recs.append((h, seq, b""))
-    return recs
 
 
 def scan(path):
