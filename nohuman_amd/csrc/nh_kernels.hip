@@ -59,6 +59,12 @@ template <bool STD> struct CandPad { static constexpr int value = STD ? 6 : 66; 
 #ifndef NH_LPO
 #define NH_LPO 4  // lanes that fetch an owner's probe round together (probe_queue_quad): 4 = 16 cells per round, 2 = 8
 #endif
+#ifndef NH_LPL
+#define NH_LPL 1  // look-ups an owner lane holds in the short-read kernel's probe rounds (probe_queue_quad): 2 = probe_rounds_two_slots, measured and not adopted
+#endif
+#ifndef NH_PROBE_DESC
+#define NH_PROBE_DESC 1  // the short-read kernel's one-slot probe round issues its wave-loads from the last to the first: all four in flight together
+#endif
 #ifndef NH_QCAP
 #define NH_QCAP 256  // 5 waves per SIMD need <= 31 KB of LDS per workgroup (a 32 KB one fits only 4 times: profiles/r02_tuning.txt)
 #endif
@@ -501,6 +507,9 @@ struct LaneLookup {
     uint64_t step;       // double hashing: stride
     uint32_t ckey;       // compacted key << value_bits
     uint32_t budget;     // rounds left before the whole table was seen
+    // second slot (probe_queue_quad with LPL = 2 only; there budget != 0 is what "busy" means, in both slots)
+    uint32_t r2, ckey2, budget2;
+    uint64_t pos2;
 };
 
 // Which copy of the table a lookup probes (DevDB::copy_stride): the one where its HOME cell lies in the
@@ -569,7 +578,10 @@ __device__ __forceinline__ void scan4(const uint4 &c, uint32_t ckey, uint32_t vm
 // in flight per lane.  Half the round trips per group, 10 % fewer instructions -- and 16 % slower: a fully
 // divergent wave-load occupies the CU's L1 path for ~152 cycles (2.4 per distinct line,
 // profiles/r02_mem_study.txt), and that path was the second wall next to HBM.  probe_queue_quad below is
-// what came of it.)
+// what came of it.  Round 7 tried two look-ups per owner lane on quad loads, 44 cycles of that path each
+// (probe_rounds_two_slots, -DNH_LPL=2): the waiting fell, the instruction count rose by more, 3-7 % slower.  What
+// the short-read kernel did gain from is having the four loads of ONE round in flight together, which its object
+// code did not do: NH_PROBE_DESC, profiles/r07_probe_slots.txt.)
 template <bool LINEAR, bool STD, bool CAP32, bool PROF, class WL>
 __device__ __forceinline__ void probe_queue(KArgsP ap, WL &S, const int lane,
                                             const uint32_t par,
@@ -779,10 +791,163 @@ __device__ __forceinline__ void probe_queue(KArgsP ap, WL &S, const int lane,
 // verdict of a quad comes back through a ballot.
 // WIDE: tables of 2^32 - 256 cells and more.  Cell positions are 64-bit in the owner; what travels to the
 // loading lanes is the low dword, and the high dword rides in the spare bits of the round's meta word.
+// LPL (look-ups per lane): 1 = an owner lane holds one look-up, a loop iteration is one round trip for at most 64 of
+// them (the generic kernel, whose register budget has no room for more: 34 vector spills with two);
+// 2 = probe_rounds_two_slots below (the short-read kernel).
+//
+// The probe rounds with TWO look-ups per owner lane, slots A and B (-DNH_LPL=2, make ab-lpl2).  An iteration refills
+// both slots from the queue, issues the round of every A look-up (LPO wave-loads) and right behind it the round of
+// every B look-up, then scans and retires A, then B: up to 128 look-ups share one memory round trip.
+// Measured and NOT adopted (profiles/r07_probe_slots.txt): the waiting falls as meant (SQ_WAIT_ANY -7 %), but a
+// wave-load instruction serves 16 owners' slots whether they hold a look-up or not, and with two half-filled slots
+// a launch executes 24 % more of them, 19 % more VALU and 27 % more LDS instructions: -3 % to -7 % on 2 x 150 bp.
+// (A's scan does not start before B's loads are back as well: the loads are conditional, so the compiler cannot
+// count how many are outstanding and waits for all of them.  What is shared is the round trip, not the scan.)
+// Registers: only the 2 x LPO load destinations live across the wait; the loading lanes fetch the owners' keys and
+// cell counts (ds_bpermute) when the data is back -- the owners' state does not change in between -- and a slot
+// has no busy flag: budget != 0 says it holds a look-up.  96 VGPRs, no vector spill, 5 waves per SIMD
+// (profiles/r07_resource_usage.txt); keeping the keys and counts across the wait: 6 spills.
 template <bool PROF, bool WIDE, class WL>
+__device__ __forceinline__ void probe_rounds_two_slots(KArgsP ap, WL &S, const int lane, const uint32_t par,
+                                                       const uint32_t qn, LaneLookup &lk, uint64_t (&prof)[12]) {
+    constexpr bool STD = true;
+    typedef typename std::conditional<WIDE, uint64_t, uint32_t>::type Pos;
+    ap = launder(ap);
+    const uint32_t vbits = ap->db.value_bits;
+    const uint32_t kbits = 32 - vbits;
+    const uint32_t vmask = ap->db.vmask;
+    const uint64_t cap = ap->db.capacity;
+    const uint32_t max_rounds = ap->db.max_chunks;  // (>= 2: capacity + 1)
+    const uint32_t *const table = ap->db.table;
+    const uint64_t copy_stride = ap->db.copy_stride;
+    const uint32_t copy_shift = ap->db.copy_shift;
+    constexpr uint32_t LPO = NH_LPO, OPI = 64 / LPO, RCELLS = 4 * LPO;
+    const uint32_t q4 = ((uint32_t)lane % LPO) * 4u;
+    const uint32_t own_sub = (uint32_t)lane / LPO;
+
+    uint32_t qhead = 0;  // next queue entry to hand out (uniform)
+    uint32_t rA = lk.r, ckA = lk.ckey, bA = lk.budget, rB = lk.r2, ckB = lk.ckey2, bB = lk.budget2;
+    Pos posA = (Pos)lk.pos, posB = (Pos)lk.pos2;
+
+    // hands queue entries to the lanes whose slot is free
+    auto refill = [&](uint32_t &r, uint32_t &ckey, uint32_t &budget, Pos &pos) {
+        const uint64_t idle_mask = __ballot(budget == 0);
+        if (idle_mask) {
+            const uint32_t my = qhead + below(idle_mask);
+            if (budget == 0 && my < qn) {
+                const uint64_t e = S.q[par][my];
+                if (WIDE) {
+                    pos = (Pos)(e >> kbits);
+                    ckey = (uint32_t)(e & ((1ull << kbits) - 1)) << vbits;
+                } else {
+                    pos = (Pos)(uint32_t)e;
+                    ckey = (uint32_t)(e >> 32);
+                }
+                r = my | (par << 9) | (pick_copy((uint32_t)pos, copy_shift) << 10);
+                budget = max_rounds;
+            }
+            const uint32_t taken = __popcll(idle_mask);
+            qhead = qhead + taken < qn ? qhead + taken : qn;
+        }
+    };
+    // owner side: cells of this round (from pos to the end of its line / of the table, 16 at most) | copy << 8 | pos high << 11
+    auto round_meta = [&](const uint32_t r, const uint32_t budget, const Pos pos) -> uint32_t {
+        const uint32_t cj = (r >> 10) & 7u;
+        uint32_t nv = 0;
+        if (budget) {
+            const uint32_t in_line = 32u - (((uint32_t)pos - (cj << copy_shift)) & 31u);
+            const Pos room = (Pos)cap - pos;
+            nv = room < (Pos)in_line ? (uint32_t)room : in_line;
+            nv = nv < RCELLS ? nv : RCELLS;
+        }
+        return nv | (cj << 8) | (WIDE ? (uint32_t)((uint64_t)pos >> 32) << 11 : 0u);
+    };
+    // loading side: instruction k fetches the rounds of owner lanes OPI k .. OPI k + OPI - 1, LPO lanes each
+    auto issue_round = [&](uint4 (&c)[LPO], const Pos pos, const uint32_t meta) {
+#pragma unroll
+        for (int k = 0; k < (int)LPO; k++) c[k] = make_uint4(0, 0, 0, 0);
+        // (from the last instruction to the first, as the one-slot loop does under DESC and for its reason)
+#pragma unroll
+        for (int k = (int)LPO - 1; k >= 0; k--) {
+            const int src = (int)(4u * (OPI * (uint32_t)k + own_sub));
+            const uint32_t p = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)(uint32_t)pos);
+            const uint32_t m = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)meta);
+            if (q4 < (m & 0xFFu)) {  // (a chunk without eligible cells is not loaded: every line-visit costs the L1)
+                const uint64_t cell = WIDE ? (((uint64_t)(m >> 11) << 32) | p) : (uint64_t)p;
+                const uint32_t copy = WIDE ? ((m >> 8) & 7u) : (m >> 8);
+                c[k] = probe_load16(table + (uint64_t)copy * copy_stride + cell + q4);
+            }
+        }
+    };
+    // the loaded chunks are scanned with the owners' keys; the verdict of a quad comes back through a ballot
+    auto scan_round = [&](const uint4 (&c)[LPO], const uint32_t ckey, const uint32_t nv, bool &found, uint32_t &val) {
+#pragma unroll
+        for (int k = 0; k < (int)LPO; k++) {
+            const int src = (int)(4u * (OPI * (uint32_t)k + own_sub));
+            const uint32_t ck = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)ckey);
+            const uint32_t nvk = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)nv);
+            uint32_t res = 0, resj = 64;
+            scan4(c[k], ck, vmask, 0u, res, resj);
+            const bool hit = q4 + resj < nvk;  // (resj = 64: no stopping cell in this chunk)
+            const uint64_t hm = __ballot(hit);
+            const uint32_t nib = (uint32_t)(hm >> (LPO * ((uint32_t)lane % OPI))) & ((1u << LPO) - 1u);
+            const uint32_t win = LPO * ((uint32_t)lane % OPI) + (nib ? (uint32_t)__builtin_ctz(nib) : 0u);
+            const uint32_t rv = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(4u * win), (int)res);
+            if (((uint32_t)lane / OPI) == (uint32_t)k && nib != 0) {
+                found = true;
+                val = rv;
+            }
+        }
+    };
+    auto retire = [&](const uint32_t r, uint32_t &budget, Pos &pos, const uint32_t nv, const bool found, const uint32_t val) {
+        if (budget) {
+            const Pos np = pos + nv;
+            pos = np >= (Pos)cap ? (Pos)0 : np;
+            budget--;
+            if (found | (budget == 0)) {
+                tax_at<STD>(S, (r >> 9) & 1u, r & 0x1FFu) = (found && val <= vmask) ? val : 0u;
+                budget = 0;
+            }
+        }
+    };
+
+    for (;;) {
+        if (qhead < qn) refill(rA, ckA, bA, posA);
+        if (qhead < qn) refill(rB, ckB, bB, posB);
+        // done when everything is handed out and neither slot of any lane still works for the previous group
+        if (qhead >= qn && __ballot((bA != 0 && ((rA >> 9) & 1u) != par) || (bB != 0 && ((rB >> 9) & 1u) != par)) == 0) break;
+        if (PROF) prof[11] += 1;  // loop iterations = memory round trips
+        const uint32_t metaA = round_meta(rA, bA, posA), metaB = round_meta(rB, bB, posB);
+        uint4 cA[LPO], cB[LPO];
+        bool foundA = false, foundB = false;
+        uint32_t valA = 0, valB = 0;
+        issue_round(cA, posA, metaA);
+        if (__ballot(bB != 0)) {
+            issue_round(cB, posB, metaB);
+            scan_round(cA, ckA, metaA & 0xFFu, foundA, valA);  // (B's loads are still in flight)
+            retire(rA, bA, posA, metaA & 0xFFu, foundA, valA);
+            scan_round(cB, ckB, metaB & 0xFFu, foundB, valB);
+            retire(rB, bB, posB, metaB & 0xFFu, foundB, valB);
+        } else {  // (a small group, or the tail of one: slot B is empty in every lane)
+            scan_round(cA, ckA, metaA & 0xFFu, foundA, valA);
+            retire(rA, bA, posA, metaA & 0xFFu, foundA, valA);
+        }
+    }
+    lk.r = rA;
+    lk.ckey = ckA;
+    lk.budget = bA;
+    lk.pos = posA;
+    lk.r2 = rB;
+    lk.ckey2 = ckB;
+    lk.budget2 = bB;
+    lk.pos2 = posB;
+}
+
+template <bool PROF, bool WIDE, int LPL, bool DESC, class WL>
 __device__ __forceinline__ void probe_queue_quad(KArgsP ap, WL &S, const int lane, const uint32_t par,
                                                  const uint32_t qn, LaneLookup &lk, const bool count_lookups,
                                                  const uint64_t carry_pack, uint64_t (&prof)[12], uint64_t &tprev) {
+    static_assert(LPL == 1 || LPL == 2, "look-ups per lane: 1 or 2");
     constexpr bool STD = true;
     typedef typename std::conditional<WIDE, uint64_t, uint32_t>::type Pos;
     ap = launder(ap);
@@ -810,6 +975,12 @@ __device__ __forceinline__ void probe_queue_quad(KArgsP ap, WL &S, const int lan
     wave_sync();
     NH_STAMP(4);
 
+    if constexpr (LPL == 2) {
+        probe_rounds_two_slots<PROF, WIDE>(ap, S, lane, par, qn, lk, prof);
+        wave_sync();
+        NH_STAMP(5);
+        return;
+    }
     uint32_t qhead = 0;  // next queue entry to hand out (uniform)
     uint32_t busy = lk.busy, r = lk.r, ckey = lk.ckey, budget = lk.budget;
     Pos pos = (Pos)lk.pos;
@@ -856,7 +1027,12 @@ __device__ __forceinline__ void probe_queue_quad(KArgsP ap, WL &S, const int lan
         uint4 c[LPO];
         uint32_t ck[LPO], nvk[LPO];
 #pragma unroll
-        for (int k = 0; k < (int)LPO; k++) {  // instruction k: the lookups of owner lanes OPI k .. OPI k + OPI - 1, LPO lanes each
+        for (int kk = 0; kk < (int)LPO; kk++) {  // instruction k: the lookups of owner lanes OPI k .. OPI k + OPI - 1, LPO lanes each
+            // DESC (the short-read kernel): issued from the last to the first.  In ascending order that kernel's object code
+            // has `s_waitcnt vmcnt(0)` between the second and the third load, in front of the zeroing of c[3] (seen in the -S
+            // output; nothing in the source asks for it) -- two memory round trips per round; descending, the four loads are
+            // back to back as they are in the generic kernel in either order (profiles/r07_probe_slots.txt).
+            const int k = DESC ? (int)LPO - 1 - kk : kk;
             const int src = (int)(4u * (OPI * (uint32_t)k + own_sub));
             const uint32_t p = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)(uint32_t)pos);
             ck[k] = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)ckey);
@@ -1443,6 +1619,8 @@ __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK, BIG ? 1 : (STD ? NH_MIN_WAV
     lk.pos = lk.first_pos = lk.step = 0;
     lk.ckey = 0;
     lk.budget = 0;
+    lk.r2 = lk.ckey2 = lk.budget2 = 0;
+    lk.pos2 = 0;
 
     if (lane == 0) S.frag_state = make_uint4(0, 0, 0, 0);
     uint64_t carry_pack = 0;  // queue entries of the current group that are look-ups of an inherited minimizer
@@ -1452,7 +1630,7 @@ __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK, BIG ? 1 : (STD ? NH_MIN_WAV
         flush_records<STD>(ap, S, lane);
 #ifndef NH_NO_QUAD
         if constexpr (LINEAR && STD)
-            probe_queue_quad<PROF, !CAP32>(ap, S, lane, par, qn, lk, !BIG, carry_pack, prof, tprev);
+            probe_queue_quad<PROF, !CAP32, 1, false>(ap, S, lane, par, qn, lk, !BIG, carry_pack, prof, tprev);
         else
 #endif
             probe_queue<LINEAR, STD, CAP32, PROF>(ap, S, lane, par, qn, lk, !BIG, carry_pack, prof, tprev);
@@ -1771,6 +1949,8 @@ __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK, PROF ? 4 : NH_MIN_WAVES) vo
     lk.pos = lk.first_pos = lk.step = 0;
     lk.ckey = 0;
     lk.budget = 0;
+    lk.r2 = lk.ckey2 = lk.budget2 = 0;
+    lk.pos2 = 0;
     if (lane == 0) S.frag_state = make_uint4(0, 0, 0, 0);
 
     // tuning aid (KArgs::timeline): looked up again at every stamp, so that nothing of it lives in registers
@@ -1969,7 +2149,7 @@ __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK, PROF ? 4 : NH_MIN_WAVES) vo
 #ifdef NH_NO_QUAD
                 probe_queue<true, STD, !WIDE, PROF>(ap, S, lane, par, qn, lk, true, 0ull, prof, tprev);
 #else
-                probe_queue_quad<PROF, WIDE>(ap, S, lane, par, qn, lk, true, 0ull, prof, tprev);
+                probe_queue_quad<PROF, WIDE, NH_LPL, NH_PROBE_DESC != 0>(ap, S, lane, par, qn, lk, true, 0ull, prof, tprev);
 #endif
                 if (TLINE && lane == 0) {
                     unsigned long long *const tline = tl_row();
