@@ -440,6 +440,48 @@ int nh_run_engine_rstats(nh_engine *e, const nh_run_args *args, const nh_run_ext
 /* the table of nh_run_rstats from the numbers; host only, no device needed */
 int nh_read_stats_write(const nh_read_stats *stats, const char *path);
 
+/*
+ * Database builder (--build-db; nohuman_amd/csrc/nh_build.hip): FASTA in, a kraken2 database directory out (hash.k2d, opts.k2d,
+ * taxo.k2d), built on the GPU.  What kraken2-build does for ONE taxon at the default geometry, and nothing more: k = 35, l = 31,
+ * the default spaced-seed and toggle masks, revcom_version 1, dna_db 1, minimum_acceptable_hash_value 0, linear probing -- the
+ * geometry of the HPRC databases and the one the classifier's fast path is built for.  No low-complexity masking (kraken2-build's
+ * dustmasker step is optional there).  A k-mer is skipped exactly when the classifier's scanner calls it ambiguous under the rule in
+ * force (NH_AMBIGUITY_DEFAULT, NOHUMAN_OPT_AMBIGUITY_RULE honoured); bases are read as the classifier reads them, lowercase included.
+ * taxo.k2d: node 0 the null sentinel, node 1 "root" (external id 1), node 2 the taxon (external `taxid`, child of 1); every
+ * inserted value is 2, value_bits 2, key_bits 30.
+ * The text goes to the device in batches of bounded size, every sequence cut into pieces of piece_kmers k-mers that overlap by
+ * k - 1 bases, a wave per piece.  Two passes over the input: COUNT the distinct minimizers exactly in a device set of 64-bit keys
+ * (it grows by doubling and stays at most half full: 16 bytes of HBM per distinct minimizer at the least, 48 at the most while it
+ * grows), which gives capacity = ceil(distinct_minimizers / load_factor); INSERT into a zeroed table (CompareAndSet, linear
+ * probing, 64-bit cell indices).  Which key sits in which cell of a probe run depends on the order of arrival, as in kraken2's
+ * threaded build; the set of occupied cells and the sorted cells do not.  The three files are written under temporary names in
+ * out_dir and renamed into place when all three are complete; any failure removes them and leaves out_dir as it was.
+ * NH_EINVAL before any device is touched: struct_size too small; n_fasta 0 or a NULL path; out_dir NULL; load_factor outside
+ * (0, 0.95]; taxid 1; a database already in out_dir without `force`; an input that lies in out_dir under one of the three names.
+ * NH_EIO: an input that cannot be read.  NH_EDB: no k-mer at all in the input.  NH_EOOM: the counting set or the table cannot be
+ * allocated (the message names `capacity` as the way round the set).  NH_ECAPACITY: a given `capacity` that the minimizers fill.
+ * FASTQ inputs are accepted (their sequences are read).  One device; no multi-GPU build.
+ */
+typedef struct {
+    uint32_t struct_size;        /* sizeof(nh_build_args) of the caller */
+    uint32_t n_fasta;
+    const char *const *fasta;    /* plain or gzip FASTA, wrapped lines allowed, any number of records */
+    const char *out_dir;         /* receives hash.k2d, opts.k2d, taxo.k2d (created if missing) */
+    uint64_t taxid;              /* external id of the one taxon; 0 = 9606 */
+    const char *taxon_name;      /* NULL = "Homo sapiens" when taxid is 9606, else "taxon<taxid>" */
+    double load_factor;          /* 0 = 0.7 (kraken2-build's default, a recollection: unpinned like SURVEY.md A) */
+    uint64_t capacity;           /* 0 = ceil(distinct_minimizers / load_factor); else used as given, counting pass skipped */
+    uint64_t piece_kmers;        /* 0 = default (1984, 16 tiles); k-mers per piece (tests set it small) */
+    int32_t device;
+    uint32_t threads;            /* host reader workers (gzip inputs) */
+    int32_t force;               /* 0: refuse an out_dir that already holds any of the three files */
+} nh_build_args;
+typedef struct {
+    uint64_t sequences, bases, kmers, ambiguous_kmers, distinct_minimizers, capacity, size;
+    double seconds_read, seconds_count, seconds_insert, seconds_write;
+} nh_build_stats;
+int nh_build_db(const nh_build_args *args, nh_build_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

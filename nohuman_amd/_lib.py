@@ -66,6 +66,20 @@ class nh_read_stats(C.Structure):
                 ("mates", C.c_int32), ("reserved", C.c_int32)]
 
 
+class nh_build_args(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_fasta", C.c_uint32), ("fasta", C.POINTER(C.c_char_p)),
+                ("out_dir", C.c_char_p), ("taxid", C.c_uint64), ("taxon_name", C.c_char_p), ("load_factor", C.c_double),
+                ("capacity", C.c_uint64), ("piece_kmers", C.c_uint64), ("device", C.c_int32), ("threads", C.c_uint32),
+                ("force", C.c_int32)]
+
+
+class nh_build_stats(C.Structure):
+    _fields_ = [("sequences", C.c_uint64), ("bases", C.c_uint64), ("kmers", C.c_uint64), ("ambiguous_kmers", C.c_uint64),
+                ("distinct_minimizers", C.c_uint64), ("capacity", C.c_uint64), ("size", C.c_uint64),
+                ("seconds_read", C.c_double), ("seconds_count", C.c_double), ("seconds_insert", C.c_double),
+                ("seconds_write", C.c_double)]
+
+
 # every symbol include/nohuman_engine.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -123,6 +137,7 @@ SYMBOLS = {
     "nh_run_engine_rstats": (C.c_int, [_P, C.POINTER(nh_run_args), C.POINTER(nh_run_extras), C.c_uint32, C.c_char_p,
                                        C.POINTER(nh_read_stats), C.POINTER(nh_stats)]),
     "nh_read_stats_write": (C.c_int, [C.POINTER(nh_read_stats), C.c_char_p]),
+    "nh_build_db": (C.c_int, [C.POINTER(nh_build_args), C.POINTER(nh_build_stats)]),
     "nh_allreduce_counters": (C.c_int, [C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_uint64), C.c_char_p,
                                         C.c_size_t]),
 }

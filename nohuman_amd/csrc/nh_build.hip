@@ -1,0 +1,713 @@
+// nh_build.hip -- nh_build_db: FASTA in, a kraken2 database directory out, built on the GPU (include/nohuman_engine.h).
+//
+// What it replaces: kraken2-build's build_db.cc for ONE taxon at the default geometry (k = 35, l = 31, default spaced seed and
+// toggle mask, revcom_version 1, minimum_acceptable_hash_value 0, linear probing).  That is the limit, on purpose: it is what the
+// HPRC databases are and what the classifier's fast path (is_std) is built for.
+//
+// The sequence text goes to HBM in batches of bounded size (BATCH_BYTES; a 3 Gbase genome is never resident as a whole).  Every
+// sequence is cut into PIECES of P k-mers: piece p covers k-mers [p P, min((p + 1) P, n - 34)), i.e. bases [p P, p P + P + 34), so
+// consecutive pieces overlap by k - 1 bases and every k-mer belongs to exactly one piece.  A k-mer's minimizer and its ambiguity
+// depend only on that k-mer's own 35 bases, so the union over the pieces is the set of the whole sequence; a sequence that does not
+// fit what is left of a batch is cut the same way at the batch's end.  One wave scans one piece with the classifier's own scanner
+// (nh_scan.h: scan_tile) -- the builder skips a k-mer exactly when the classifier would not look it up.
+//
+// Two passes over the text:
+//   COUNT   every run-start minimizer goes into a device open-addressing set of 64-bit keys (key = minimizer + 1, 0 = empty; the
+//           minimizer is below 2^62).  A slot is claimed by compare-and-swap exactly once per distinct key, so the claims counted
+//           are the distinct minimizers.  Before a batch is counted the set is grown (doubling, re-inserting the keys on the
+//           device) until slots >= 2 x (distinct so far + k-mers of the batch): it is never more than half full, a probe always
+//           ends, and no batch can overflow it.  HBM: 8 bytes a slot, 16 to 32 bytes per distinct minimizer when idle and old + new
+//           = up to 48 while it grows -- about 1.5 G minimizers of a human genome: 32 GiB resident, 48 GiB at the last doubling.
+//   INSERT  into a zeroed table of `capacity` cells: kraken2's CompareAndSet with a constant value, linear probing, 64-bit cell
+//           indices.  The probe loop is bounded by the capacity; a lane that has seen every cell raises `full`, which every other
+//           lane polls, and the call ends with NH_ECAPACITY.
+// Both kernels add their totals with one atomic per wave behind a wave-level reduction; cells and slots are written by
+// compare-and-swap only.
+#include <errno.h>
+#include <hip/hip_runtime.h>
+#include <limits.h>
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <chrono>
+#include <exception>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "nh_device.h"
+#include "nh_fastx.h"
+#include "nh_internal.h"
+#include "nh_scan.h"
+#include "nohuman_engine.h"
+
+namespace nh {
+namespace {
+
+// second kernel argument of k_build_pieces (the first is the classifier's KArgs: scan_tile reads the geometry from it)
+struct BuildDev {
+    unsigned long long *set;       // COUNT: slots of the key set
+    uint64_t set_cap, set_magic;   // slots, floor((2^64 - 1) / slots)
+    unsigned long long *counters;  // [0] slots / cells claimed, [1] k-mers that are not ambiguous
+    int *full;                     // raised by a lane whose probe saw every slot / cell
+    uint32_t value, pad;           // INSERT: the value field of every cell
+};
+
+constexpr uint32_t FULL_POLL = 1023;  // a probing lane looks at `full` every 1024 cells
+
+// One wave per piece: sequence text[seq_off[p], +seq_len[p]) (starts and lengths, so that pieces may overlap).
+template <bool COUNT>
+__global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_build_pieces(const KArgs args_by_kernarg_pointer, const BuildDev b) {
+    KArgsP ap = (KArgsP)__builtin_amdgcn_kernarg_segment_ptr();
+    typedef WaveLdsT<true, 1, QCAP_GENERIC> WL;
+    __shared__ WL lds_all[WAVES_PER_BLOCK];
+    const int lane = threadIdx.x & 63;
+    const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    WL &S = lds_all[wib];
+    init_wave_lds<true>(S, lane);
+    const uint32_t TQ = TL - 4u;  // k-mers of a full tile
+    const uint64_t n_piece = ap->n_frag;
+    const uint64_t *const start = ap->seq_off;
+    const uint32_t *const len = ap->seq_len;
+    const uint64_t text_len = ap->bases_end;
+    const uint64_t last_dw = (text_len + 4) >> 2;  // the text is readable for 8 bytes behind its end
+    const uint32_t *const text = reinterpret_cast<const uint32_t *>(ap->bases);
+    const uint32_t pl = (uint32_t)lane < PREF_LANES ? (uint32_t)lane : PREF_LANES - 1;
+    uint32_t *const table = const_cast<uint32_t *>(ap->db.table);
+    const uint64_t cap = COUNT ? b.set_cap : ap->db.capacity;
+    const uint64_t magic = COUNT ? b.set_magic : ap->db.cap_magic;
+    const uint32_t vbits = ap->db.value_bits;
+    uint64_t prof[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    uint64_t tprev = 0;
+    unsigned long long claimed = 0;  // per lane
+    unsigned long long clean = 0;    // wave-uniform
+    bool gave_up = false;
+    const uint64_t n_waves = (uint64_t)gridDim.x * WAVES_PER_BLOCK;
+    for (uint64_t p = (uint64_t)blockIdx.x * WAVES_PER_BLOCK + wib; p < n_piece; p += n_waves) {
+        const uint64_t o0 = start[p];
+        const uint32_t n = len[p];
+        if (n < 35u || o0 > text_len || text_len - o0 < n) continue;  // (wave-uniform; the host makes no such piece)
+        const uint32_t nk = n - 34u;
+        uint64_t carry_min = NH_FULL;
+        uint32_t w;
+        {
+            uint64_t dw = (o0 >> 2) + pl;
+            dw = dw < last_dw ? dw : last_dw;
+            w = text[dw];
+        }
+        for (uint32_t q0 = 0; q0 < nk; q0 += TQ) {
+            const uint64_t g0 = o0 + q0;
+            const uint32_t nl_left = (n - 31u + 1) - q0;
+            const uint32_t nlt = nl_left < (uint32_t)TL ? nl_left : (uint32_t)TL;
+            const uint32_t nq_left = nk - q0;
+            const uint32_t nqt = nq_left < TQ ? nq_left : TQ;
+            // the next tile's dword is loaded while this one is scanned
+            const bool more = nq_left > TQ;
+            uint64_t dwn = ((g0 + TQ) >> 2) + pl;
+            dwn = dwn < last_dw ? dwn : last_dw;
+            uint32_t ps, w_next = 0;
+            int last_lane;
+            const uint32_t nruns = scan_tile<true, false>(ap, S, lane, w, (uint32_t)g0 & 3u, nlt, nqt, 0u, 0u, carry_min, ps, last_lane,
+                                                          text + dwn, more, w_next, prof, tprev);
+            if (!COUNT) clean += (unsigned long long)(__popcll(__ballot(ps & 1u)) + __popcll(__ballot(ps & 2u)));
+            wave_sync();
+            for (uint32_t r = lane; r < nruns && !gave_up; r += 64) {
+                const uint64_t mz = S.q[0][r];
+                const uint64_t hc = fmix64(mz);
+                uint64_t idx = mod_capacity(hc, cap, magic);
+                bool placed = false;
+                if (COUNT) {
+                    const unsigned long long key = mz + 1;
+                    for (uint64_t tries = 0; tries < cap; tries++) {
+                        // (a slot never changes once it holds a key: only an empty one needs the compare-and-swap)
+                        unsigned long long cur = __hip_atomic_load(&b.set[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        if (cur == 0) {
+                            cur = atomicCAS(&b.set[idx], 0ull, key);
+                            if (cur == 0) {
+                                claimed++;
+                                placed = true;
+                                break;
+                            }
+                        }
+                        if (cur == key) {
+                            placed = true;
+                            break;
+                        }
+                        idx++;
+                        if (idx >= cap) idx = 0;
+                        if ((tries & FULL_POLL) == FULL_POLL && __hip_atomic_load(b.full, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
+                    }
+                } else {
+                    const uint32_t compacted = (uint32_t)(hc >> (32 + vbits));
+                    const uint32_t cell = (compacted << vbits) | b.value;
+                    for (uint64_t tries = 0; tries < cap; tries++) {
+                        uint32_t cur = __hip_atomic_load(&table[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        if (cur == 0) {
+                            cur = atomicCAS(&table[idx], 0u, cell);
+                            if (cur == 0) {
+                                claimed++;
+                                placed = true;
+                                break;
+                            }
+                        }
+                        if ((cur >> vbits) == compacted) {
+                            placed = true;
+                            break;
+                        }
+                        idx++;
+                        if (idx >= cap) idx = 0;
+                        if ((tries & FULL_POLL) == FULL_POLL && __hip_atomic_load(b.full, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
+                    }
+                }
+                if (!placed) {
+                    __hip_atomic_store(b.full, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    gave_up = true;
+                }
+            }
+            wave_sync();
+            w = w_next;
+        }
+        // a full table: no piece after this one can do anything but find it full again
+        if (__hip_atomic_load(b.full, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
+    }
+    for (int d = 32; d >= 1; d >>= 1) claimed += __shfl_xor(claimed, d, 64);
+    if (lane == 0) {
+        if (claimed) atomicAdd(&b.counters[0], claimed);
+        if (!COUNT && clean) atomicAdd(&b.counters[1], clean);
+    }
+}
+
+// the keys of the old set into the new, larger one (no key is in it twice: a plain claim of the first empty slot)
+__global__ __launch_bounds__(256) void k_set_rehash(const unsigned long long *old, const uint64_t old_cap, unsigned long long *set,
+                                                    const uint64_t cap, const uint64_t magic, int *full) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < old_cap; i += stride) {
+        const unsigned long long key = old[i];
+        if (key == 0) continue;
+        uint64_t idx = mod_capacity(fmix64(key - 1), cap, magic);
+        bool placed = false;
+        for (uint64_t tries = 0; tries < cap; tries++) {
+            if (atomicCAS(&set[idx], 0ull, key) == 0) {
+                placed = true;
+                break;
+            }
+            idx++;
+            if (idx >= cap) idx = 0;
+        }
+        if (!placed) __hip_atomic_store(full, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// ---- host ------------------------------------------------------------------------------------------------------------------
+#define BUILD_TRY(expr)                                                                                                        \
+    do {                                                                                                                       \
+        hipError_t _e = (expr);                                                                                                \
+        if (_e != hipSuccess) {                                                                                                \
+            (void)hipGetLastError();                                                                                           \
+            return set_error(_e == hipErrorOutOfMemory ? NH_EOOM : NH_EDEVICE, "%s: %s", #expr, hipGetErrorString(_e));        \
+        }                                                                                                                      \
+    } while (0)
+
+constexpr uint64_t DEFAULT_PIECE_KMERS = 16 * (TL - 4);  // 1984: 16 tiles, 1.7 % of the text read twice
+constexpr uint64_t DEFAULT_BATCH_BYTES = 128ull << 20;
+constexpr uint64_t TOGGLE_MASK = 0xe37e28c4271b5a2dull;
+constexpr uint64_t SPACED_MASK = 0x3FFFFFFFF3333333ull;  // "1" x 17 + "01" x 7, two bits a base
+constexpr uint32_t VALUE_BITS = 2, TAXON_NODE = 2;       // three nodes: 0 the null sentinel, 1 root, 2 the taxon
+const char *const DB_FILES[3] = {"hash.k2d", "opts.k2d", "taxo.k2d"};
+
+double since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+}
+
+struct Builder {
+    // arguments
+    uint64_t piece = DEFAULT_PIECE_KMERS, batch_cap = DEFAULT_BATCH_BYTES;
+    int device = 0;
+    unsigned threads = 0;
+    int ambig_rule = 1;
+    // the batch being filled (host)
+    std::vector<char> text;
+    std::vector<uint64_t> starts;
+    std::vector<uint32_t> lens;
+    uint64_t batch_kmers = 0;
+    // device
+    hipStream_t stream = nullptr;
+    int grid_max = 0;
+    char *d_text = nullptr;
+    uint64_t *d_starts = nullptr;
+    uint32_t *d_lens = nullptr;
+    uint64_t piece_cap = 0;
+    unsigned long long *d_counters = nullptr;  // two counters, then `full` as an int
+    unsigned long long *d_set = nullptr;
+    uint64_t set_cap = 0;
+    uint32_t *d_table = nullptr;
+    uint64_t capacity = 0;
+    // results
+    bool counting = false;
+    unsigned long long claimed = 0, clean = 0;
+    bool full = false;
+    double t_read = 0, t_gpu = 0;
+    double t_kernel = 0;  // of t_gpu: the pass's kernel alone (HIP events; the rest is copies, set growth and waits)
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    uint64_t sequences = 0, bases = 0, kmers = 0;
+
+    ~Builder() {
+        if (device >= 0 && stream) (void)dev_set(device);
+        for (void *p : {(void *)d_text, (void *)d_starts, (void *)d_lens, (void *)d_counters, (void *)d_set, (void *)d_table})
+            if (p) (void)hipFree(p);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+
+    int *d_full() const { return (int *)(d_counters + 2); }
+
+    int init() {
+        BUILD_TRY(dev_set(device));
+        hipDeviceProp_t prop;
+        BUILD_TRY(hipGetDeviceProperties(&prop, dev_phys(device)));
+        int per_cu = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_build_pieces<false>, WAVE * WAVES_PER_BLOCK, 0) != hipSuccess || per_cu < 1) {
+            (void)hipGetLastError();
+            per_cu = 4;
+        }
+        grid_max = prop.multiProcessorCount * (per_cu > 8 ? 8 : per_cu);
+        BUILD_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        for (hipEvent_t &e : ev) BUILD_TRY(hipEventCreate(&e));
+        BUILD_TRY(dev_malloc(&d_text, batch_cap + 64));
+        BUILD_TRY(dev_malloc(&d_counters, 4 * sizeof(unsigned long long)));
+        text.reserve(batch_cap);
+        return NH_OK;
+    }
+
+    int reset_counters() {
+        BUILD_TRY(hipMemsetAsync(d_counters, 0, 4 * sizeof(unsigned long long), stream));
+        BUILD_TRY(hipStreamSynchronize(stream));
+        claimed = clean = 0;
+        full = false;
+        return NH_OK;
+    }
+
+    // COUNT: slots >= 2 x (keys in the set + keys this batch can add)
+    int grow_set(uint64_t need_keys) {
+        uint64_t need = 2 * need_keys + 64;
+        if (need <= set_cap) return NH_OK;
+        uint64_t ncap = set_cap ? set_cap : (1ull << 16);
+        while (ncap < need) ncap *= 2;
+        unsigned long long *nset = nullptr;
+        hipError_t he = dev_malloc(&nset, ncap * sizeof(unsigned long long));
+        if (he != hipSuccess) {
+            (void)hipGetLastError();
+            return set_error(NH_EOOM, "cannot allocate the counting set of the build (%llu slots, %.1f GiB, beside %.1f GiB in use): give the "
+                             "table's size with `capacity` (--capacity) and the counting pass is skipped",
+                             (unsigned long long)ncap, (double)ncap * 8 / (1ull << 30), (double)set_cap * 8 / (1ull << 30));
+        }
+        he = hipMemsetAsync(nset, 0, ncap * sizeof(unsigned long long), stream);
+        if (he == hipSuccess && d_set) {
+            const uint64_t want = (set_cap + 255) / 256;
+            hipLaunchKernelGGL(k_set_rehash, dim3((unsigned)(want < 65536 ? want : 65536)), dim3(256), 0, stream, d_set, set_cap, nset, ncap,
+                               ~0ull / ncap, d_full());
+            he = hipGetLastError();
+        }
+        if (he == hipSuccess) he = hipStreamSynchronize(stream);
+        if (he != hipSuccess) {
+            (void)hipFree(nset);
+            return set_error(NH_EDEVICE, "growing the counting set: %s", hipGetErrorString(he));
+        }
+        if (d_set) (void)hipFree(d_set);
+        d_set = nset;
+        set_cap = ncap;
+        return NH_OK;
+    }
+
+    int alloc_table(uint64_t cap) {
+        capacity = cap;
+        const uint64_t cells = ((cap + 3) & ~3ull) + 32;
+        hipError_t he = dev_malloc(&d_table, cells * sizeof(uint32_t));
+        if (he != hipSuccess) {
+            (void)hipGetLastError();
+            return set_error(NH_EOOM, "cannot allocate the hash table of the build (%llu cells, %.1f GiB)", (unsigned long long)cap,
+                             (double)cells * 4 / (1ull << 30));
+        }
+        BUILD_TRY(hipMemsetAsync(d_table, 0, cells * sizeof(uint32_t), stream));
+        BUILD_TRY(hipStreamSynchronize(stream));
+        return NH_OK;
+    }
+
+    void free_set() {
+        if (d_set) (void)hipFree(d_set);
+        d_set = nullptr;
+        set_cap = 0;
+    }
+
+    // the batch to the device, one launch, its totals back
+    int flush() {
+        if (starts.empty()) {
+            text.clear();
+            batch_kmers = 0;
+            return NH_OK;
+        }
+        auto t0 = std::chrono::steady_clock::now();
+        const uint64_t n_piece = starts.size();
+        if (counting) {
+            int rc = grow_set(claimed + batch_kmers);
+            if (rc) return rc;
+        }
+        if (n_piece > piece_cap) {
+            if (d_starts) (void)hipFree(d_starts);
+            if (d_lens) (void)hipFree(d_lens);
+            d_starts = nullptr, d_lens = nullptr, piece_cap = 0;
+            const uint64_t ncap = n_piece + n_piece / 2 + 1024;
+            BUILD_TRY(dev_malloc(&d_starts, ncap * sizeof(uint64_t)));
+            BUILD_TRY(dev_malloc(&d_lens, ncap * sizeof(uint32_t)));
+            piece_cap = ncap;
+        }
+        BUILD_TRY(hipMemcpyAsync(d_text, text.data(), text.size(), hipMemcpyHostToDevice, stream));
+        BUILD_TRY(hipMemsetAsync(d_text + text.size(), 0, 64, stream));
+        BUILD_TRY(hipMemcpyAsync(d_starts, starts.data(), n_piece * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+        BUILD_TRY(hipMemcpyAsync(d_lens, lens.data(), n_piece * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        KArgs ka;
+        memset(&ka, 0, sizeof ka);
+        DevDB &d = ka.db;
+        d.table = d_table;
+        d.n_copies = 1;
+        d.copy_shift = 5;
+        d.capacity = counting ? 1 : capacity;
+        d.cap_magic = ~0ull / d.capacity;
+        d.node_count = 3;
+        d.value_bits = VALUE_BITS;
+        d.vmask = (1u << VALUE_BITS) - 1;
+        d.k = 35, d.l = 31, d.window = 4;
+        d.lmer_mask = (1ull << 62) - 1;
+        d.spaced_mask = SPACED_MASK;
+        d.toggle = TOGGLE_MASK & d.lmer_mask;
+        d.min_hash = 0;
+        d.revcom_version = 1;
+        d.linear_probing = 1;
+        d.ambig_rule = ambig_rule;
+        ka.bases = (const uint8_t *)d_text;
+        ka.seq_off = d_starts;
+        ka.seq_len = d_lens;
+        ka.bases_end = text.size();
+        ka.n_frag = n_piece;
+        BuildDev b;
+        memset(&b, 0, sizeof b);
+        b.set = d_set;
+        b.set_cap = counting ? set_cap : 1;
+        b.set_magic = ~0ull / b.set_cap;
+        b.counters = d_counters;
+        b.full = d_full();
+        b.value = TAXON_NODE;
+        const uint64_t want = (n_piece + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
+        const unsigned grid = (unsigned)(want < (uint64_t)grid_max ? want : (uint64_t)grid_max);
+        BUILD_TRY(hipEventRecord(ev[0], stream));
+        if (counting)
+            hipLaunchKernelGGL(k_build_pieces<true>, dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, stream, ka, b);
+        else
+            hipLaunchKernelGGL(k_build_pieces<false>, dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, stream, ka, b);
+        BUILD_TRY(hipGetLastError());
+        BUILD_TRY(hipEventRecord(ev[1], stream));
+        unsigned long long out[4] = {0, 0, 0, 0};
+        BUILD_TRY(hipMemcpyAsync(out, d_counters, sizeof out, hipMemcpyDeviceToHost, stream));
+        BUILD_TRY(hipStreamSynchronize(stream));
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) t_kernel += ms * 1e-3;
+        else (void)hipGetLastError();
+        claimed = out[0];
+        clean = out[1];
+        int f;
+        memcpy(&f, &out[2], sizeof f);
+        full = f != 0;
+        text.clear();
+        starts.clear();
+        lens.clear();
+        batch_kmers = 0;
+        t_gpu += since(t0);
+        if (full && counting) return set_error(NH_EDEVICE, "the counting set of the build overflowed (%llu slots): this is a bug", (unsigned long long)set_cap);
+        if (full)
+            return set_error(NH_ECAPACITY, "the table of %llu cells is full: the input has more distinct minimizers than `capacity` holds "
+                             "(leave capacity 0 and it is counted)", (unsigned long long)capacity);
+        return NH_OK;
+    }
+
+    // one sequence into the batches: pieces of `piece` k-mers, the batch's end a cut like any other
+    int add_sequence(const char *s, size_t n) {
+        if (n < 35) return NH_OK;
+        const size_t nk = n - 34;
+        size_t pos = 0;  // the first k-mer not yet in a piece (= its first base)
+        while (pos < nk) {
+            const size_t room = batch_cap - text.size();
+            if (room < 35) {
+                int rc = flush();
+                if (rc) return rc;
+                continue;
+            }
+            const size_t left = n - pos;
+            const size_t take = left < room ? left : room;  // bases, >= 35
+            const size_t mk = take - 34;                     // their k-mers
+            const uint64_t t = text.size();
+            text.insert(text.end(), s + pos, s + pos + take);
+            for (size_t p = 0; p < mk; p += piece) {
+                const size_t pk = mk - p < piece ? mk - p : (size_t)piece;
+                starts.push_back(t + p);
+                lens.push_back((uint32_t)(pk + 34));
+            }
+            batch_kmers += mk;
+            pos += mk;
+        }
+        return NH_OK;
+    }
+
+    // every record of every input through add_sequence
+    int pass(const nh_build_args *a, bool count, bool totals) {
+        counting = count;
+        int rc = reset_counters();
+        if (rc) return rc;
+        SeqRecord rec;
+        for (uint32_t i = 0; i < a->n_fasta; i++) {
+            FastxReader rd;
+            std::string err;
+            auto t0 = std::chrono::steady_clock::now();
+            if (rd.open(a->fasta[i], err, threads) != 0) return set_error(NH_EIO, "%s", err.c_str());
+            for (;;) {
+                const int got = rd.next(rec, err);
+                if (got < 0) return set_error(NH_EIO, "%s: %s", a->fasta[i], err.c_str());
+                if (got == 0) break;
+                t_read += since(t0);
+                if (totals) {
+                    sequences++;
+                    bases += rec.seq.size();
+                    if (rec.seq.size() >= 35) kmers += rec.seq.size() - 34;
+                }
+                rc = add_sequence(rec.seq.data(), rec.seq.size());
+                if (rc) return rc;
+                t0 = std::chrono::steady_clock::now();
+            }
+            t_read += since(t0);
+        }
+        return flush();
+    }
+};
+
+bool file_there(const std::string &p) {
+    struct stat st;
+    return lstat(p.c_str(), &st) == 0;
+}
+
+std::string real_of(const std::string &p) {
+    char buf[PATH_MAX];
+    return realpath(p.c_str(), buf) ? std::string(buf) : std::string();
+}
+
+// is `input` one of the three files of out_dir (by inode where the file exists, by name where it does not yet)
+bool input_is_output(const char *input, const std::string &out_dir) {
+    struct stat si;
+    const bool have_i = stat(input, &si) == 0;
+    std::string in = input;
+    const size_t slash = in.find_last_of('/');
+    const std::string base = slash == std::string::npos ? in : in.substr(slash + 1);
+    const std::string dir = slash == std::string::npos ? "." : slash == 0 ? "/" : in.substr(0, slash);
+    for (const char *name : DB_FILES) {
+        struct stat so;
+        if (have_i && stat((out_dir + "/" + name).c_str(), &so) == 0 && so.st_dev == si.st_dev && so.st_ino == si.st_ino) return true;
+        if (base == name) {
+            const std::string a = real_of(dir), b = real_of(out_dir);
+            if (!a.empty() && a == b) return true;
+        }
+    }
+    return false;
+}
+
+std::vector<uint8_t> opts_image() {
+    std::vector<uint8_t> ob(64, 0);
+    const uint64_t v[4] = {35, 31, SPACED_MASK, TOGGLE_MASK};
+    memcpy(ob.data(), v, 32);
+    ob[32] = 1;  // dna_db
+    const int32_t rv = 1;
+    memcpy(ob.data() + 48, &rv, 4);  // (minimum_acceptable_hash_value at 40, db_version and db_type behind revcom_version: 0)
+    return ob;
+}
+
+// "K2TAXDAT", node count, bytes of the name and the rank strings, 56-byte nodes {parent, first child, child count,
+// name offset, rank offset, external id, godparent}, the two string tables
+std::vector<uint8_t> taxo_image(uint64_t taxid, const std::string &name) {
+    const std::string names = std::string("root") + '\0' + name + '\0', ranks = std::string("no rank") + '\0';
+    uint64_t nodes[3][7];
+    memset(nodes, 0, sizeof nodes);
+    nodes[1][1] = 2, nodes[1][2] = 1, nodes[1][5] = 1;        // root: one child, node 2
+    nodes[2][0] = 1, nodes[2][3] = 5, nodes[2][5] = taxid;    // the taxon: child of 1, its name behind "root\0"
+    std::vector<uint8_t> img;
+    img.insert(img.end(), (const uint8_t *)"K2TAXDAT", (const uint8_t *)"K2TAXDAT" + 8);
+    const uint64_t hdr[3] = {3, names.size(), ranks.size()};
+    img.insert(img.end(), (const uint8_t *)hdr, (const uint8_t *)hdr + 24);
+    img.insert(img.end(), (const uint8_t *)nodes, (const uint8_t *)nodes + sizeof nodes);
+    img.insert(img.end(), names.begin(), names.end());
+    img.insert(img.end(), ranks.begin(), ranks.end());
+    return img;
+}
+
+bool write_all(FILE *f, const void *p, size_t n) { return n == 0 || fwrite(p, 1, n, f) == n; }
+
+bool write_file(const std::string &path, const std::vector<uint8_t> &img) {
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f) return false;
+    const bool ok = write_all(f, img.data(), img.size());
+    return (fclose(f) == 0) && ok;
+}
+
+// the three files under temporary names, then renamed into place; on any failure nothing of this call stays behind
+int write_database(Builder &B, const nh_build_args *a, uint64_t taxid, const std::string &name, uint64_t size) {
+    const std::string dir = a->out_dir;
+    bool made_dir = false;
+    struct stat st;
+    if (stat(dir.c_str(), &st) != 0) {
+        if (mkdir(dir.c_str(), 0777) != 0) return set_error(NH_EIO, "cannot create %s: %s", dir.c_str(), strerror(errno));
+        made_dir = true;
+    }
+    char suffix[48];
+    snprintf(suffix, sizeof suffix, ".tmp%ld", (long)getpid());
+    std::string tmp[3], fin[3];
+    for (int i = 0; i < 3; i++) fin[i] = dir + "/" + DB_FILES[i], tmp[i] = fin[i] + suffix;
+    auto fail = [&](int code, const std::string &msg) {
+        for (const std::string &t : tmp) unlink(t.c_str());
+        if (made_dir) rmdir(dir.c_str());
+        return set_error(code, "%s", msg.c_str());
+    };
+    {   // hash.k2d: {capacity, size, key_bits, value_bits}, then the cells, fetched from the device a stretch at a time
+        FILE *f = fopen(tmp[0].c_str(), "wb");
+        if (!f) return fail(NH_EIO, "cannot write " + tmp[0] + ": " + strerror(errno));
+        const uint64_t hdr[4] = {B.capacity, size, 32 - VALUE_BITS, VALUE_BITS};
+        bool ok = write_all(f, hdr, sizeof hdr);
+        const uint64_t step = 16ull << 20;  // cells
+        std::vector<uint32_t> buf((size_t)(B.capacity < step ? B.capacity : step));
+        hipError_t he = hipSuccess;
+        for (uint64_t c = 0; ok && c < B.capacity; c += step) {
+            const uint64_t n = B.capacity - c < step ? B.capacity - c : step;
+            he = hipMemcpy(buf.data(), B.d_table + c, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+            if (he != hipSuccess) break;
+            ok = write_all(f, buf.data(), n * sizeof(uint32_t));
+        }
+        ok = (fclose(f) == 0) && ok;
+        if (he != hipSuccess) return fail(NH_EDEVICE, std::string("fetching the table: ") + hipGetErrorString(he));
+        if (!ok) return fail(NH_EIO, "cannot write " + tmp[0]);
+    }
+    if (!write_file(tmp[1], opts_image())) return fail(NH_EIO, "cannot write " + tmp[1]);
+    if (!write_file(tmp[2], taxo_image(taxid, name))) return fail(NH_EIO, "cannot write " + tmp[2]);
+    for (int i = 0; i < 3; i++)
+        if (rename(tmp[i].c_str(), fin[i].c_str()) != 0) return fail(NH_EIO, "cannot move " + tmp[i] + " into place: " + strerror(errno));
+    return NH_OK;
+}
+
+int build_db(const nh_build_args *a, nh_build_stats *stats) {
+    if (stats) memset(stats, 0, sizeof *stats);
+    // ---- arguments: everything refused here is refused before any device is touched and before anything is created
+    if (!a) return set_error(NH_EINVAL, "nh_build_db: null arguments");
+    if (a->struct_size < sizeof(nh_build_args))
+        return set_error(NH_EINVAL, "nh_build_db: struct_size %u is smaller than nh_build_args (%zu)", a->struct_size, sizeof(nh_build_args));
+    if (a->n_fasta == 0 || !a->fasta) return set_error(NH_EINVAL, "nh_build_db: no input (n_fasta 0)");
+    for (uint32_t i = 0; i < a->n_fasta; i++)
+        if (!a->fasta[i]) return set_error(NH_EINVAL, "nh_build_db: input %u is a null path", i);
+    if (!a->out_dir || !*a->out_dir) return set_error(NH_EINVAL, "nh_build_db: no output directory");
+    const double lf = a->load_factor == 0 ? 0.7 : a->load_factor;
+    if (!(lf > 0 && lf <= 0.95)) return set_error(NH_EINVAL, "nh_build_db: load factor %g is not in (0, 0.95]", a->load_factor);
+    if (a->taxid == 1) return set_error(NH_EINVAL, "nh_build_db: taxid 1 is the root of the taxonomy, not a taxon to build");
+    const uint64_t taxid = a->taxid ? a->taxid : 9606;
+    // (a probe-queue entry of the classifier packs the home cell and the 30-bit key into 63 bits)
+    if (a->capacity >> 33) return set_error(NH_EINVAL, "nh_build_db: capacity %llu is not below 2^33", (unsigned long long)a->capacity);
+    const std::string dir = a->out_dir;
+    struct stat st;
+    if (stat(dir.c_str(), &st) == 0 && !S_ISDIR(st.st_mode)) return set_error(NH_EINVAL, "nh_build_db: %s is not a directory", dir.c_str());
+    for (uint32_t i = 0; i < a->n_fasta; i++)
+        if (input_is_output(a->fasta[i], dir))
+            return set_error(NH_EINVAL, "nh_build_db: the input %s is a database file of the output directory %s", a->fasta[i], dir.c_str());
+    if (!a->force)
+        for (const char *name : DB_FILES)
+            if (file_there(dir + "/" + name))
+                return set_error(NH_EINVAL, "nh_build_db: %s already holds %s (`force` replaces a database)", dir.c_str(), name);
+    std::string name;
+    if (a->taxon_name) name = a->taxon_name;
+    else if (taxid == 9606) name = "Homo sapiens";
+    else name = "taxon" + std::to_string(taxid);
+
+    int rc = check_device(a->device);
+    if (rc) return rc;
+    Builder B;
+    B.device = a->device;
+    B.threads = a->threads;
+    if (a->piece_kmers) B.piece = a->piece_kmers < (1ull << 31) ? a->piece_kmers : (1ull << 31);
+    if (const char *env = getenv("NOHUMAN_BUILD_BATCH")) {  // test knob: bytes of text per batch (sequences cut at the batches' ends)
+        const long long v = atoll(env);
+        if (v > 0) B.batch_cap = (uint64_t)v < 64 ? 64 : (uint64_t)v;
+    }
+    if (const char *env = getenv("NOHUMAN_OPT_AMBIGUITY_RULE")) B.ambig_rule = atoi(env) != 0 ? 1 : 0;  // as the classifier reads it
+    else B.ambig_rule = NH_AMBIGUITY_DEFAULT == NH_AMBIGUITY_LAST_LMER ? 0 : 1;
+    rc = B.init();
+    if (rc) return rc;
+
+    nh_build_stats s;
+    memset(&s, 0, sizeof s);
+    uint64_t capacity = a->capacity;
+    double count_kernel = 0;
+    if (!capacity) {
+        rc = B.pass(a, true, true);
+        if (rc) return rc;
+        s.distinct_minimizers = B.claimed;
+        s.seconds_count = B.t_gpu;
+        count_kernel = B.t_kernel;
+        B.t_gpu = B.t_kernel = 0;
+        B.free_set();
+        if (s.distinct_minimizers == 0)
+            return set_error(NH_EDB, "the input holds no k-mer to build from: %llu sequences, %llu bases, every sequence shorter than 35 bases or "
+                             "ambiguous throughout", (unsigned long long)B.sequences, (unsigned long long)B.bases);
+        capacity = (uint64_t)ceil((double)s.distinct_minimizers / lf);
+        if (capacity >> 33) return set_error(NH_ECAPACITY, "%llu distinct minimizers need a table of 2^33 cells or more", (unsigned long long)s.distinct_minimizers);
+    }
+    rc = B.alloc_table(capacity);
+    if (rc) return rc;
+    rc = B.pass(a, false, a->capacity != 0);
+    if (rc) return rc;
+    s.seconds_insert = B.t_gpu;
+    s.seconds_read = B.t_read;
+    s.sequences = B.sequences;
+    s.bases = B.bases;
+    s.kmers = B.kmers;
+    s.ambiguous_kmers = B.kmers - B.clean;
+    s.capacity = capacity;
+    s.size = B.claimed;
+    if (s.size == 0)
+        return set_error(NH_EDB, "the input holds no k-mer to build from: %llu sequences, %llu bases, every sequence shorter than 35 bases or "
+                         "ambiguous throughout", (unsigned long long)B.sequences, (unsigned long long)B.bases);
+    // (a table without one empty cell is no kraken2 table: a look-up of an absent key would never end there)
+    if (s.size >= capacity)
+        return set_error(NH_ECAPACITY, "the table of %llu cells is full: the input has more distinct minimizers than `capacity` holds "
+                         "(leave capacity 0 and it is counted)", (unsigned long long)capacity);
+    auto t0 = std::chrono::steady_clock::now();
+    rc = write_database(B, a, taxid, name, s.size);
+    if (rc) return rc;
+    s.seconds_write = since(t0);
+    if (getenv("NOHUMAN_TRACE"))
+        fprintf(stderr, "[nohuman trace] build: %llu k-mers, %llu ambiguous, %llu distinct minimizers, %llu cells of %llu; kernels alone: count %.4f s, "
+                        "insert %.4f s (batches of %llu bytes, pieces of %llu k-mers)\n",
+                (unsigned long long)s.kmers, (unsigned long long)s.ambiguous_kmers, (unsigned long long)s.distinct_minimizers,
+                (unsigned long long)s.size, (unsigned long long)s.capacity, count_kernel, B.t_kernel, (unsigned long long)B.batch_cap,
+                (unsigned long long)B.piece);
+    if (stats) *stats = s;
+    return NH_OK;
+}
+
+}  // namespace
+}  // namespace nh
+
+extern "C" int nh_build_db(const nh_build_args *args, nh_build_stats *stats) {
+    try {
+        return nh::build_db(args, stats);
+    } catch (const std::bad_alloc &) {
+        return nh::set_error(NH_EOOM, "nh_build_db: out of host memory");
+    } catch (const std::exception &e) {
+        return nh::set_error(NH_EIO, "nh_build_db: %s", e.what());
+    }
+}

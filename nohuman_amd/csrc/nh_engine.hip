@@ -216,7 +216,7 @@ static uint64_t rd64(const uint8_t *p) {
     return v;
 }
 
-static int check_device(int device) {
+int check_device(int device) {
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
     if (e != hipSuccess || n <= 0)

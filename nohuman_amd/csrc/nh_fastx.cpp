@@ -465,12 +465,12 @@ void ByteSource::close() {
     gz_ = nullptr;
 }
 
-int FastxReader::open(const char *path, std::string &err) {
+int FastxReader::open(const char *path, std::string &err, unsigned gz_threads) {
     buf_.resize(4u << 20);
     pos_ = len_ = 0;
     eof_ = false;
     format_ = FMT_AUTO;
-    return src_.open(path, err);
+    return src_.open(path, err, gz_threads);
 }
 
 int FastxReader::peek() {

@@ -52,7 +52,7 @@ private:
 
 class FastxReader {
 public:
-    int open(const char *path, std::string &err);
+    int open(const char *path, std::string &err, unsigned gz_threads = 0);  // gz_threads: as ByteSource::open
     // 1 = record read, 0 = end of input, -1 = malformed input (err set)
     int next(SeqRecord &rec, std::string &err);
     void close() { src_.close(); }

@@ -106,6 +106,7 @@ hipError_t launch_synth_insert(uint32_t *table, uint64_t capacity, uint64_t cap_
                                uint32_t value_bits, uint32_t value, uint64_t n_keys, uint64_t seed,
                                uint64_t key_mask, unsigned long long *d_size, hipStream_t stream);
 
+int check_device(int device);  // NH_OK, or NH_EDEVICE with a message: no HIP device, `device` out of range, not a gfx950
 int open_dir(const char *db_dir, int device, Engine **out);
 int open_images(const void *opts, size_t opts_len, const void *taxo, size_t taxo_len,
                 const void *hash, size_t hash_len, int device, Engine **out);

@@ -224,6 +224,12 @@ struct Args {
     bool has_out1 = false, has_out2 = false, check = false, download = false, list = false, human = false;
     bool has_type = false;
     Codec type = C_NONE;
+    // --build-db: make a database from FASTA instead of running on reads (nh_build_db)
+    std::string build_db, taxon_name;
+    bool has_build_db = false, has_taxon_name = false, has_build_opt = false, force = false;
+    std::vector<std::string> reference;
+    unsigned long long taxid = 0, capacity = 0;
+    double load_factor = 0;
     unsigned threads = 1;
     float confidence = 0.0f;
     std::string conf_text = "0.0";
@@ -254,6 +260,13 @@ static void usage(FILE *f) {
           "      --calls <FILE>           Write a table with one line per read: C/U, id, taxid, length(s), k-mers, clade hits (hits / k-mers is the confidence -C thresholds), hit groups\n"
           "      --read-stats <FILE>      Write a QC table of all, non-human and human reads per mate: reads, bases, min/mean/median/max length, N50, GC %, other bases, Q20 %, Q30 %, mean quality (counted on the GPU in the same pass)\n"
           "      --human-ids <FILE>       Write the ids of the human reads, one per line\n"
+          "      --build-db <DIR>         Build a database (hash.k2d, opts.k2d, taxo.k2d) in DIR from the --reference files, on the GPU, and exit\n"
+          "      --reference <FILE>       FASTA file (plain or gzip) of the host genome for --build-db; may be given more than once\n"
+          "      --taxid <INT>            Taxonomy id of the host for --build-db [default: 9606]\n"
+          "      --taxon-name <NAME>      Name of the host in the database's taxonomy for --build-db\n"
+          "      --load-factor <FLOAT>    Load factor of the hash table for --build-db, in (0, 0.95] [default: 0.7]\n"
+          "      --capacity <INT>         Cells of the hash table for --build-db; skips the counting pass [default: distinct minimizers / load factor]\n"
+          "      --force                  Let --build-db replace a database that DIR already holds\n"
           "  -v, --verbose                Set the logging level to verbose\n"
           "  -h, --help                   Print help\n"
           "  -V, --version                Print version\n",
@@ -335,6 +348,26 @@ static Args parse_args(int argc, char **argv) {
         else if (s == "--calls") a.calls = val();
         else if (s == "--human-ids") a.human_ids = val();
         else if (s == "--read-stats") a.read_stats = val();
+        else if (s == "--build-db") { a.build_db = val(); a.has_build_db = true; }
+        else if (s == "--reference") a.reference.push_back(val());
+        else if (s == "--taxid" || s == "--capacity") {
+            std::string t = val();
+            char *end;
+            errno = 0;
+            unsigned long long n = strtoull(t.c_str(), &end, 10);
+            if (*end || t.empty() || t[0] == '-' || errno || (s == "--taxid" && n == 0) || (s == "--capacity" && n == 0))
+                arg_error("invalid value '%s' for '%s <INT>': a positive integer is expected", t.c_str(), s.c_str());
+            (s == "--taxid" ? a.taxid : a.capacity) = n;
+            a.has_build_opt = true;
+        } else if (s == "--taxon-name") { a.taxon_name = val(); a.has_taxon_name = a.has_build_opt = true; }
+        else if (s == "--load-factor") {
+            std::string t = val();
+            char *end;
+            double f = strtod(t.c_str(), &end);
+            if (*end || t.empty() || !(f > 0 && f <= 0.95)) arg_error("invalid value '%s' for '--load-factor <FLOAT>': a number in (0, 0.95] is expected", t.c_str());
+            a.load_factor = f;
+            a.has_build_opt = true;
+        } else if (s == "--force") a.force = a.has_build_opt = true;
         else if (s == "-v" || s == "--verbose") g_verbose = true;
         else if (s == "-h" || s == "--help") { usage(stdout); exit(0); }
         else if (s == "-V" || s == "--version") { puts("nohuman 0.5.1 (MI355X engine)"); exit(0); }
@@ -344,6 +377,20 @@ static Args parse_args(int argc, char **argv) {
             a.input.push_back(s);
         }
     }
+    if (a.has_build_db) {  // builds and exits: nothing of a run may come with it
+        if (a.reference.empty()) arg_error("the following required arguments were not provided:\n  --reference <FILE> (with '--build-db <DIR>')");
+        if (!a.input.empty()) arg_error("the argument '--build-db <DIR>' cannot be used with read inputs ('%s'): the genome is given with '--reference <FILE>'", a.input[0].c_str());
+        const char *out_flag = a.has_out1 ? "--out1" : a.has_out2 ? "--out2" : a.has_human_out1 ? "--human-out1" : a.has_human_out2 ? "--human-out2"
+                             : !a.kraken_output.empty() ? "--kraken-output" : !a.kraken_report.empty() ? "--kraken-report" : !a.calls.empty() ? "--calls"
+                             : !a.human_ids.empty() ? "--human-ids" : !a.read_stats.empty() ? "--read-stats" : a.has_type ? "--output-type"
+                             : a.bgzf ? "--bgzf" : a.mask ? "--mask" : a.human ? "--human" : nullptr;
+        if (out_flag) arg_error("the argument '--build-db <DIR>' cannot be used with '%s'", out_flag);
+        for (const std::string &r : a.reference)
+            if (!exists(r)) arg_error("invalid value '%s' for '--reference <FILE>': %s does not exist", r.c_str(), quoted(r).c_str());
+        return a;
+    }
+    if (!a.reference.empty()) arg_error("the argument '--reference <FILE>' needs '--build-db <DIR>'");
+    if (a.has_build_opt) arg_error("the arguments '--taxid', '--taxon-name', '--load-factor', '--capacity' and '--force' need '--build-db <DIR>'");
     if (a.input.empty() && !a.check && !a.download && !a.list)
         arg_error("the following required arguments were not provided:\n  <INPUT>...");
     if (a.mask && a.human) arg_error("the argument '--mask' cannot be used with '--human'");
@@ -431,6 +478,34 @@ int main(int argc, char **argv) {
     DEBUG("kraken2 is executable (in-process engine: %s)", probe);
     if (args.check) {
         INFO("All dependencies are available");
+        return 0;
+    }
+    if (args.has_build_db) {
+        INFO("Building database in %s...", quoted(args.build_db).c_str());
+        std::vector<const char *> refs;
+        for (const std::string &r : args.reference) refs.push_back(r.c_str());
+        nh_build_args ba;
+        memset(&ba, 0, sizeof ba);
+        ba.struct_size = (uint32_t)sizeof ba;
+        ba.n_fasta = (uint32_t)refs.size();
+        ba.fasta = refs.data();
+        ba.out_dir = args.build_db.c_str();
+        ba.taxid = args.taxid;
+        ba.taxon_name = args.has_taxon_name ? args.taxon_name.c_str() : nullptr;
+        ba.load_factor = args.load_factor;
+        ba.capacity = args.capacity;
+        ba.threads = args.threads;
+        ba.force = args.force ? 1 : 0;
+        if (const char *dv = getenv("NOHUMAN_DEVICES")) ba.device = (int32_t)strtol(dv, nullptr, 10);  // (one device: the first listed)
+        nh_build_stats bs;
+        if (nh_build_db(&ba, &bs) != 0) die("Failed to build the database\n\nCaused by:\n    %s", nh_last_error());
+        INFO("Database built: %llu sequences, %llu bases, %llu distinct minimizers, capacity %llu, size %llu, load %.4f; read %.2f s, count %.2f s, "
+             "insert %.2f s, write %.2f s",
+             (unsigned long long)bs.sequences, (unsigned long long)bs.bases, (unsigned long long)bs.distinct_minimizers,
+             (unsigned long long)bs.capacity, (unsigned long long)bs.size, bs.capacity ? (double)bs.size / (double)bs.capacity : 0.0, bs.seconds_read,
+             bs.seconds_count, bs.seconds_insert, bs.seconds_write);
+        INFO("Database written to: %s", quoted(args.build_db).c_str());
+        INFO("Done.");
         return 0;
     }
     if (args.input.empty()) die("No input files provided");

@@ -146,6 +146,37 @@ def _read_stats(v) -> "ReadStats":
     return v if isinstance(v, ReadStats) else ReadStats(v)
 
 
+def build_db(fasta_paths, out_dir, *, taxid: int = 0, taxon_name=None, load_factor: float = 0.0, capacity: int = 0,
+             piece_kmers: int = 0, device: int = 0, threads: int = 1, force: bool = False) -> dict:
+    """nh_build_db: a kraken2 database directory (hash.k2d, opts.k2d, taxo.k2d) built on the GPU from FASTA files (plain or
+    gzip, wrapped lines, any number of records; one path or a list).  One taxon (taxid, 0 = 9606; taxon_name), the default
+    geometry (k = 35, l = 31) only.  load_factor 0 = 0.7; capacity 0 = ceil(distinct minimizers / load_factor), counted on the
+    device -- a capacity given is used as it is and the counting pass skipped; piece_kmers: k-mers per piece a wave scans (0 =
+    default); force: replace a database already in out_dir.  Returns nh_build_stats as a dict (sequences, bases, kmers,
+    ambiguous_kmers, distinct_minimizers, capacity, size, seconds_read / _count / _insert / _write); Engine.open(out_dir) and
+    run(out_dir, ...) work on the result."""
+    if isinstance(fasta_paths, (str, bytes, os.PathLike)):
+        fasta_paths = [fasta_paths]
+    paths = [os.fsencode(p) for p in fasta_paths]
+    a = _lib.nh_build_args()
+    a.struct_size = C.sizeof(_lib.nh_build_args)
+    a.n_fasta = len(paths)
+    arr = (C.c_char_p * max(len(paths), 1))(*paths)
+    a.fasta = arr
+    a.out_dir = os.fsencode(out_dir) if out_dir is not None else None
+    a.taxid = int(taxid)
+    a.taxon_name = taxon_name.encode() if isinstance(taxon_name, str) else taxon_name
+    a.load_factor = float(load_factor)
+    a.capacity = int(capacity)
+    a.piece_kmers = int(piece_kmers)
+    a.device = int(device)
+    a.threads = int(threads)
+    a.force = int(bool(force))
+    s = _lib.nh_build_stats()
+    _check(_lib.lib().nh_build_db(C.byref(a), C.byref(s)))
+    return {name: getattr(s, name) for name, _ in _lib.nh_build_stats._fields_}
+
+
 def device_count() -> int:
     n = C.c_int(0)
     _check(_lib.lib().nh_device_count(C.byref(n)))

@@ -1,0 +1,169 @@
+#!/usr/bin/env python3
+"""nh_build_db at genome scale, stage by stage, beside the only insert baseline there is.
+
+A synthetic genome (iid ACGT in a few records, a few long N runs; generated from a seed, no file from outside) is written as FASTA
+wrapped at 60 columns and built into a database with nh_build_db (nohuman_amd.build_db): the four stage times of nh_build_stats, and
+from the library's trace line the two passes' kernel time alone (HIP events around every batch's launch).  The build runs `--runs`
+times; the first run also loads the code objects and is reported apart.
+
+Baseline: the same bases, resident in HBM, cut into contiguous NON-overlapping sequences of piece_kmers + 34 bases and pushed through
+nh_synthetic_add_sequences (k_insert_sequences, one wave a sequence) into an nh_open_synthetic table of the same capacity, one copy
+of the table (NOHUMAN_TABLE_COPIES=1, so that the call does not also copy the table).  It loses the k-mers that span two of its
+sequences (34 in every piece_kmers + 34), so it inserts slightly fewer minimizers: the rates are per inserted cell.  Host clock around
+the call, which ends in a device synchronise.
+
+    python tools/build_db_bench.py --bases 512000000 --out profiles/build_db.txt
+"""
+import argparse
+import json
+import os
+import re
+import shutil
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+TRACE = re.compile(r"kernels alone: count ([0-9.]+) s, insert ([0-9.]+) s")
+PIECE = 1984  # the library's default piece: 16 tiles of 124 k-mers
+
+
+def make_genome(bases, n_records, n_runs, seed):
+    """uint8 array of ACGT with n_runs stretches of N (10 kb to 1 Mb), and the records' boundaries"""
+    rng = np.random.default_rng(seed)
+    g = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, size=bases, dtype=np.uint8)]
+    for _ in range(n_runs):
+        ln = int(min(bases // 20 + 1, 10 ** rng.uniform(4, 6)))
+        p = int(rng.integers(0, bases - ln))
+        g[p:p + ln] = ord("N")
+    cuts = np.linspace(0, bases, n_records + 1).astype(np.int64)
+    return g, cuts
+
+
+def write_fasta(path, g, cuts, width=60):
+    with open(path, "wb") as f:
+        for i in range(len(cuts) - 1):
+            s = g[cuts[i]:cuts[i + 1]]
+            f.write(b">chr%d synthetic\n" % (i + 1))
+            full = s.size // width * width
+            if full:
+                rows = np.empty((full // width, width + 1), dtype=np.uint8)
+                rows[:, :width] = s[:full].reshape(-1, width)
+                rows[:, width] = ord("\n")
+                f.write(rows.tobytes())
+            if s.size > full:
+                f.write(s[full:].tobytes() + b"\n")
+    return os.path.getsize(path)
+
+
+def traced(fn, errf):
+    """fn() with the library's stderr (fd 2) in a file: the trace line"""
+    saved = os.dup(2)
+    fd = os.open(errf, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
+    os.dup2(fd, 2)
+    os.close(fd)
+    try:
+        return fn()
+    finally:
+        os.dup2(saved, 2)
+        os.close(saved)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--bases", type=int, default=256_000_000)
+    ap.add_argument("--records", type=int, default=8)
+    ap.add_argument("--n-runs", type=int, default=6, help="stretches of N")
+    ap.add_argument("--seed", type=int, default=20250101)
+    ap.add_argument("--runs", type=int, default=3, help="builds; the first is the warm-up")
+    ap.add_argument("--threads", type=int, default=4)
+    ap.add_argument("--workdir", default=None, help="where the FASTA and the databases go (default: a temporary directory)")
+    ap.add_argument("--out", default=None, help="append the result lines to this file")
+    a = ap.parse_args()
+
+    import torch
+
+    import nohuman_amd
+    if not torch.cuda.is_available():
+        sys.exit("build_db_bench: no GPU (there is no CPU path to measure)")
+    print("probe:", nohuman_amd.probe(), file=sys.stderr)
+    work = a.workdir or tempfile.mkdtemp(prefix="build_db_bench")
+    os.makedirs(work, exist_ok=True)
+    res = {"bases": a.bases, "records": a.records, "n_runs": a.n_runs, "seed": a.seed, "piece_kmers": PIECE, "threads": a.threads}
+    try:
+        t0 = time.time()
+        g, cuts = make_genome(a.bases, a.records, a.n_runs, a.seed)
+        fa = os.path.join(work, "genome.fa")
+        res["fasta_bytes"] = write_fasta(fa, g, cuts)
+        res["generate_s"] = round(time.time() - t0, 2)
+        os.environ["NOHUMAN_TRACE"] = "1"
+        builds = []
+        for r in range(a.runs):
+            d = os.path.join(work, "db%d" % r)
+            errf = os.path.join(work, "trace%d.txt" % r)
+            t0 = time.time()
+            st = traced(lambda: nohuman_amd.build_db([fa], d, threads=a.threads), errf)
+            wall = time.time() - t0
+            m = TRACE.search(open(errf, errors="replace").read())
+            b = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in st.items()}
+            b["wall_s"] = round(wall, 3)
+            b["count_kernel_s"], b["insert_kernel_s"] = (float(m.group(1)), float(m.group(2))) if m else (None, None)
+            b["hash_bytes"] = os.path.getsize(os.path.join(d, "hash.k2d"))
+            builds.append(b)
+            if r + 1 < a.runs:
+                shutil.rmtree(d)
+        res["builds"] = builds
+        last = builds[-1]
+        cap, size = last["capacity"], last["size"]
+        res["load_factor"] = round(size / cap, 4)
+        if last["insert_kernel_s"]:
+            res["insert_kernel_Mcells_s"] = round(size / last["insert_kernel_s"] / 1e6, 1)
+            res["count_kernel_Mkeys_s"] = round(last["distinct_minimizers"] / last["count_kernel_s"] / 1e6, 1)
+        res["insert_stage_Mcells_s"] = round(size / last["seconds_insert"] / 1e6, 1)
+        res["whole_build_Mbases_s"] = round(a.bases / last["wall_s"] / 1e6, 1)
+        # the database opens (content check) and holds what the build says
+        with nohuman_amd.Engine.open(os.path.join(work, "db%d" % (a.runs - 1))) as eng:
+            assert eng.db_check().non_empty_cells == size
+
+        # ---- baseline: k_insert_sequences on the same bases, resident, contiguous sequences of one piece each
+        os.environ["NOHUMAN_TABLE_COPIES"] = "1"
+        dev = torch.device("cuda:0")
+        seg = PIECE + 34
+        offs = []
+        for i in range(len(cuts) - 1):
+            o = np.arange(cuts[i], cuts[i + 1], seg, dtype=np.int64)
+            offs.append(o)
+        offs = np.concatenate(offs + [np.array([a.bases], dtype=np.int64)])
+        # (a record's last sequence ends where the next record starts: boundaries are sequence starts)
+        d_bases = torch.empty(a.bases + 64, dtype=torch.uint8, device=dev)
+        d_bases[:a.bases] = torch.from_numpy(g).to(dev)
+        d_bases[a.bases:] = 0
+        d_offs = torch.from_numpy(offs).to(dev)
+        base = []
+        for r in range(a.runs):
+            with nohuman_amd.Engine.synthetic(cap, 0, depth=2, seed=1) as eng:
+                torch.cuda.synchronize()
+                t0 = time.time()
+                eng.add_sequences(d_bases.data_ptr(), d_offs.data_ptr(), offs.size - 1, 2)
+                torch.cuda.synchronize()
+                dt = time.time() - t0
+                base.append({"seconds": round(dt, 4), "size": int(eng.info.size)})
+        res["baseline"] = base
+        res["baseline_sequences"] = int(offs.size - 1)
+        res["baseline_Mcells_s"] = round(base[-1]["size"] / base[-1]["seconds"] / 1e6, 1)
+    finally:
+        if not a.workdir:
+            shutil.rmtree(work, ignore_errors=True)
+    line = "BUILD_DB " + json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "a") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
