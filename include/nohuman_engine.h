@@ -444,9 +444,12 @@ int nh_read_stats_write(const nh_read_stats *stats, const char *path);
  * Database builder (--build-db; nohuman_amd/csrc/nh_build.hip): FASTA in, a kraken2 database directory out (hash.k2d, opts.k2d,
  * taxo.k2d), built on the GPU.  What kraken2-build does for ONE taxon at the default geometry, and nothing more: k = 35, l = 31,
  * the default spaced-seed and toggle masks, revcom_version 1, dna_db 1, minimum_acceptable_hash_value 0, linear probing -- the
- * geometry of the HPRC databases and the one the classifier's fast path is built for.  No low-complexity masking (kraken2-build's
- * dustmasker step is optional there).  A k-mer is skipped exactly when the classifier's scanner calls it ambiguous under the rule in
- * force (NH_AMBIGUITY_DEFAULT, NOHUMAN_OPT_AMBIGUITY_RULE honoured); bases are read as the classifier reads them, lowercase included.
+ * geometry of the HPRC databases and the one the classifier's fast path is built for.  Low-complexity masking (kraken2-build's
+ * dustmasker / k2mask step) is off unless mask_low_complexity is set: then every batch of text is masked on the device before its
+ * minimizers are taken (symmetric DUST, window 64, threshold 2.0: see nh_dust_mask below), a masked base is an N to the scanner,
+ * and masked_bases counts every input base that was masked, once (one more batch of device memory is held).  A k-mer is
+ * skipped exactly when the classifier's scanner calls it ambiguous under the rule in force (NH_AMBIGUITY_DEFAULT,
+ * NOHUMAN_OPT_AMBIGUITY_RULE honoured); bases are read as the classifier reads them, lowercase included.
  * taxo.k2d: node 0 the null sentinel, node 1 "root" (external id 1), node 2 the taxon (external `taxid`, child of 1); every
  * inserted value is 2, value_bits 2, key_bits 30.
  * The text goes to the device in batches of bounded size, every sequence cut into pieces of piece_kmers k-mers that overlap by
@@ -475,12 +478,45 @@ typedef struct {
     int32_t device;
     uint32_t threads;            /* host reader workers (gzip inputs) */
     int32_t force;               /* 0: refuse an out_dir that already holds any of the three files */
+    int32_t reserved0;           /* (the tail padding of the first layout: never read) */
+    /* ---- behind NH_BUILD_ARGS_SIZE_V1 */
+    int32_t mask_low_complexity; /* not 0: mask low-complexity sequence before the minimizers are taken */
+    int32_t reserved1;
 } nh_build_args;
 typedef struct {
     uint64_t sequences, bases, kmers, ambiguous_kmers, distinct_minimizers, capacity, size;
     double seconds_read, seconds_count, seconds_insert, seconds_write;
+    /* ---- behind NH_BUILD_STATS_SIZE_V1 */
+    uint64_t masked_bases;       /* input bases turned into N by the masking (as the inserting pass counted them) */
+    double seconds_mask;         /* the masking kernel alone, both passes (a part of seconds_count + seconds_insert) */
 } nh_build_stats;
+/* Both structs have grown at their ends, and the library tells the caller's layout by nh_build_args.struct_size alone:
+ *   struct_size <  NH_BUILD_ARGS_SIZE_V1 (80)     NH_EINVAL
+ *   struct_size <  sizeof(nh_build_args) now      the first layout: fields through `force` are read, no masking, and only the first
+ *                                                 NH_BUILD_STATS_SIZE_V1 (88) bytes of *stats are written -- a caller compiled
+ *                                                 against the first header passes a buffer of that size
+ *   struct_size >= sizeof(nh_build_args) now      mask_low_complexity is read and the whole nh_build_stats is written */
+#define NH_BUILD_ARGS_SIZE_V1 80u
+#define NH_BUILD_STATS_SIZE_V1 88u
 int nh_build_db(const nh_build_args *args, nh_build_stats *stats);
+
+/*
+ * Low-complexity masking of a host buffer in place, by the kernel and the launch code the builder uses (nh_dust.hip): symmetric
+ * DUST (Morgulis et al. 2006) at dustmasker's defaults, window 64 bases and score threshold 2.0, neither an option.  Each segment
+ * [seg_start[i], +seg_len[i]) of text is one sequence: it is split into maximal runs of ACGTacgt (case carries no meaning; any
+ * other byte ends a run and is never touched), t_i is the triplet of bases i, i+1, i+2 of a run, the triplet interval
+ * [i, i+d] scores r / d with r = sum over the 64 triplets of n (n - 1) / 2, an interval is perfect when d <= 61, 10 r > 20 d and
+ * no sub-interval scores higher, and the bases of every perfect interval become N.  No triplet spans two runs or two
+ * segments.  Integer arithmetic throughout.  Bytes outside the segments are not touched; segments should not overlap (a base in two of them is masked by
+ * either and counted twice).  *masked_bases (may be NULL) receives the number of bases turned.
+ * NH_EINVAL, before any device is touched and with the buffer unchanged: text NULL; a NULL list with n_seg > 0; a segment that
+ * leaves [0, n_bytes).  With no base in any segment the call succeeds without a device.
+ * Device memory: the whole buffer twice (the text as given, which the kernel reads, and the copy it masks) and 24 bytes for
+ * every 900 bases of a segment; NH_EOOM when that cannot be allocated -- a genome larger than that is masked a part at a time,
+ * its sequences as the segments of each part.
+ */
+int nh_dust_mask(int32_t device, char *text, uint64_t n_bytes, const uint64_t *seg_start, const uint64_t *seg_len, uint64_t n_seg,
+                 uint64_t *masked_bases);
 
 #ifdef __cplusplus
 }

@@ -80,6 +80,16 @@ class nh_build_stats(C.Structure):
                 ("seconds_write", C.c_double)]
 
 
+# The two structs above are the header's FIRST layout (NH_BUILD_ARGS_SIZE_V1 / NH_BUILD_STATS_SIZE_V1), which the library goes
+# on accepting by struct_size; the two below are the header's present structs: the same fields, then what was added at the end.
+class nh_build_args_v2(nh_build_args):
+    _fields_ = [("mask_low_complexity", C.c_int32), ("reserved1", C.c_int32)]
+
+
+class nh_build_stats_v2(nh_build_stats):
+    _fields_ = [("masked_bases", C.c_uint64), ("seconds_mask", C.c_double)]
+
+
 # every symbol include/nohuman_engine.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -137,7 +147,9 @@ SYMBOLS = {
     "nh_run_engine_rstats": (C.c_int, [_P, C.POINTER(nh_run_args), C.POINTER(nh_run_extras), C.c_uint32, C.c_char_p,
                                        C.POINTER(nh_read_stats), C.POINTER(nh_stats)]),
     "nh_read_stats_write": (C.c_int, [C.POINTER(nh_read_stats), C.c_char_p]),
-    "nh_build_db": (C.c_int, [C.POINTER(nh_build_args), C.POINTER(nh_build_stats)]),
+    "nh_build_db": (C.c_int, [C.POINTER(nh_build_args), C.POINTER(nh_build_stats)]),  # (or their _v2 subclasses)
+    "nh_dust_mask": (C.c_int, [C.c_int32, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint64,
+                               C.POINTER(C.c_uint64)]),
     "nh_allreduce_counters": (C.c_int, [C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_uint64), C.c_char_p,
                                         C.c_size_t]),
 }

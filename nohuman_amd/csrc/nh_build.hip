@@ -23,6 +23,13 @@
 //           lane polls, and the call ends with NH_ECAPACITY.
 // Both kernels add their totals with one atomic per wave behind a wave-level reduction; cells and slots are written by
 // compare-and-swap only.
+//
+// Low-complexity masking (mask_low_complexity; nh_dust.hip): in both passes every batch is masked on the device
+// between its upload and k_build_pieces, so the scanner reads a masked base as an N.  Whether a base is masked depends on the 63
+// bases on either side of it, so a sequence cut at a batch's end carries up to 63 bases of context before its first and behind its
+// last base of the batch (beside the batch's size: at most one chunk of a batch starts, and one ends, inside a sequence); the
+// pieces still cover every k-mer once.  The chunks are the segments of the mask: no triplet spans two records.  Every input base is
+// counted as masked in one chunk only, sequences too short for a k-mer included.
 #include <errno.h>
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -40,6 +47,7 @@
 #include <vector>
 
 #include "nh_device.h"
+#include "nh_dust.h"
 #include "nh_fastx.h"
 #include "nh_internal.h"
 #include "nh_scan.h"
@@ -226,6 +234,7 @@ double since(std::chrono::steady_clock::time_point t0) {
 struct Builder {
     // arguments
     uint64_t piece = DEFAULT_PIECE_KMERS, batch_cap = DEFAULT_BATCH_BYTES;
+    bool mask = false;  // low-complexity masking
     int device = 0;
     unsigned threads = 0;
     int ambig_rule = 1;
@@ -234,6 +243,8 @@ struct Builder {
     std::vector<uint64_t> starts;
     std::vector<uint32_t> lens;
     uint64_t batch_kmers = 0;
+    std::vector<DustTile> tiles;  // masking: the tiles of the batch's chunks
+    uint64_t ctx_bytes = 0;       // masking: bytes of the batch that are context, beside batch_cap
     // device
     hipStream_t stream = nullptr;
     int grid_max = 0;
@@ -241,7 +252,11 @@ struct Builder {
     uint64_t *d_starts = nullptr;
     uint32_t *d_lens = nullptr;
     uint64_t piece_cap = 0;
-    unsigned long long *d_counters = nullptr;  // two counters, then `full` as an int
+    char *d_raw = nullptr;  // masking: the batch as it was uploaded, which the mask kernel reads while it writes d_text
+    DustTile *d_tiles = nullptr;
+    uint64_t tile_cap = 0;
+    int dust_grid = 0;
+    unsigned long long *d_counters = nullptr;  // two counters, then `full` as an int, then the masked bases
     unsigned long long *d_set = nullptr;
     uint64_t set_cap = 0;
     uint32_t *d_table = nullptr;
@@ -252,12 +267,15 @@ struct Builder {
     bool full = false;
     double t_read = 0, t_gpu = 0;
     double t_kernel = 0;  // of t_gpu: the pass's kernel alone (HIP events; the rest is copies, set growth and waits)
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    double t_mask = 0;    // the mask kernel alone, all passes
+    unsigned long long masked = 0;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     uint64_t sequences = 0, bases = 0, kmers = 0;
 
     ~Builder() {
         if (device >= 0 && stream) (void)dev_set(device);
-        for (void *p : {(void *)d_text, (void *)d_starts, (void *)d_lens, (void *)d_counters, (void *)d_set, (void *)d_table})
+        for (void *p : {(void *)d_text, (void *)d_starts, (void *)d_lens, (void *)d_counters, (void *)d_set, (void *)d_table, (void *)d_raw,
+                        (void *)d_tiles})
             if (p) (void)hipFree(p);
         for (hipEvent_t e : ev)
             if (e) (void)hipEventDestroy(e);
@@ -278,7 +296,12 @@ struct Builder {
         grid_max = prop.multiProcessorCount * (per_cu > 8 ? 8 : per_cu);
         BUILD_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         for (hipEvent_t &e : ev) BUILD_TRY(hipEventCreate(&e));
-        BUILD_TRY(dev_malloc(&d_text, batch_cap + 64));
+        // (masking: up to 63 bases of context at either end of a batch)
+        BUILD_TRY(dev_malloc(&d_text, batch_cap + (mask ? 2 * DUST_CONTEXT : 0) + 64));
+        if (mask) {
+            BUILD_TRY(dev_malloc(&d_raw, batch_cap + 2 * DUST_CONTEXT + 64));
+            dust_grid = dust_grid_max();
+        }
         BUILD_TRY(dev_malloc(&d_counters, 4 * sizeof(unsigned long long)));
         text.reserve(batch_cap);
         return NH_OK;
@@ -287,7 +310,7 @@ struct Builder {
     int reset_counters() {
         BUILD_TRY(hipMemsetAsync(d_counters, 0, 4 * sizeof(unsigned long long), stream));
         BUILD_TRY(hipStreamSynchronize(stream));
-        claimed = clean = 0;
+        claimed = clean = masked = 0;
         full = false;
         return NH_OK;
     }
@@ -346,9 +369,9 @@ struct Builder {
 
     // the batch to the device, one launch, its totals back
     int flush() {
-        if (starts.empty()) {
+        if (starts.empty() && tiles.empty()) {
             text.clear();
-            batch_kmers = 0;
+            batch_kmers = ctx_bytes = 0;
             return NH_OK;
         }
         auto t0 = std::chrono::steady_clock::now();
@@ -368,8 +391,25 @@ struct Builder {
         }
         BUILD_TRY(hipMemcpyAsync(d_text, text.data(), text.size(), hipMemcpyHostToDevice, stream));
         BUILD_TRY(hipMemsetAsync(d_text + text.size(), 0, 64, stream));
-        BUILD_TRY(hipMemcpyAsync(d_starts, starts.data(), n_piece * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-        BUILD_TRY(hipMemcpyAsync(d_lens, lens.data(), n_piece * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        if (n_piece) {
+            BUILD_TRY(hipMemcpyAsync(d_starts, starts.data(), n_piece * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+            BUILD_TRY(hipMemcpyAsync(d_lens, lens.data(), n_piece * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        }
+        const bool masking = !tiles.empty();
+        if (masking) {
+            if (tiles.size() > tile_cap) {
+                if (d_tiles) (void)hipFree(d_tiles);
+                d_tiles = nullptr, tile_cap = 0;
+                const uint64_t ncap = tiles.size() + tiles.size() / 2 + 1024;
+                BUILD_TRY(dev_malloc(&d_tiles, ncap * sizeof(DustTile)));
+                tile_cap = ncap;
+            }
+            BUILD_TRY(hipMemcpyAsync(d_tiles, tiles.data(), tiles.size() * sizeof(DustTile), hipMemcpyHostToDevice, stream));
+            BUILD_TRY(hipMemcpyAsync(d_raw, d_text, text.size() + 64, hipMemcpyDeviceToDevice, stream));
+            BUILD_TRY(hipEventRecord(ev[2], stream));
+            BUILD_TRY(launch_dust(d_raw, d_text, text.size(), d_tiles, tiles.size(), d_counters + 3, dust_grid, stream));
+            BUILD_TRY(hipEventRecord(ev[3], stream));
+        }
         KArgs ka;
         memset(&ka, 0, sizeof ka);
         DevDB &d = ka.db;
@@ -405,7 +445,9 @@ struct Builder {
         const uint64_t want = (n_piece + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
         const unsigned grid = (unsigned)(want < (uint64_t)grid_max ? want : (uint64_t)grid_max);
         BUILD_TRY(hipEventRecord(ev[0], stream));
-        if (counting)
+        if (n_piece == 0)
+            ;  // (masking: a batch of sequences too short for a k-mer)
+        else if (counting)
             hipLaunchKernelGGL(k_build_pieces<true>, dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, stream, ka, b);
         else
             hipLaunchKernelGGL(k_build_pieces<false>, dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, stream, ka, b);
@@ -417,15 +459,21 @@ struct Builder {
         float ms = 0;
         if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) t_kernel += ms * 1e-3;
         else (void)hipGetLastError();
+        if (masking) {
+            if (hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) t_mask += ms * 1e-3;
+            else (void)hipGetLastError();
+        }
         claimed = out[0];
         clean = out[1];
+        masked = out[3];
         int f;
         memcpy(&f, &out[2], sizeof f);
         full = f != 0;
         text.clear();
         starts.clear();
         lens.clear();
-        batch_kmers = 0;
+        tiles.clear();
+        batch_kmers = ctx_bytes = 0;
         t_gpu += since(t0);
         if (full && counting) return set_error(NH_EDEVICE, "the counting set of the build overflowed (%llu slots): this is a bug", (unsigned long long)set_cap);
         if (full)
@@ -436,11 +484,11 @@ struct Builder {
 
     // one sequence into the batches: pieces of `piece` k-mers, the batch's end a cut like any other
     int add_sequence(const char *s, size_t n) {
-        if (n < 35) return NH_OK;
+        if (n < 35) return mask ? add_short(s, n) : NH_OK;
         const size_t nk = n - 34;
         size_t pos = 0;  // the first k-mer not yet in a piece (= its first base)
         while (pos < nk) {
-            const size_t room = batch_cap - text.size();
+            const size_t room = batch_cap + ctx_bytes - text.size();
             if (room < 35) {
                 int rc = flush();
                 if (rc) return rc;
@@ -449,8 +497,17 @@ struct Builder {
             const size_t left = n - pos;
             const size_t take = left < room ? left : room;  // bases, >= 35
             const size_t mk = take - 34;                     // their k-mers
-            const uint64_t t = text.size();
-            text.insert(text.end(), s + pos, s + pos + take);
+            // masking: the chunk with up to 63 bases of the sequence on either side; its masked bases are counted where they are
+            // k-mer starts of this chunk, and through the sequence's end in its last chunk
+            const size_t cl = !mask ? 0 : pos < DUST_CONTEXT ? pos : (size_t)DUST_CONTEXT;
+            const size_t behind = n - (pos + take);
+            const size_t cr = !mask ? 0 : behind < DUST_CONTEXT ? behind : (size_t)DUST_CONTEXT;
+            const uint64_t t = text.size() + cl;
+            text.insert(text.end(), s + pos - cl, s + pos + take + cr);
+            if (mask) {
+                dust_tiles(tiles, t - cl, cl + take + cr, cl, cl + (behind ? mk : take));
+                ctx_bytes += cl + cr;
+            }
             for (size_t p = 0; p < mk; p += piece) {
                 const size_t pk = mk - p < piece ? mk - p : (size_t)piece;
                 starts.push_back(t + p);
@@ -459,6 +516,18 @@ struct Builder {
             batch_kmers += mk;
             pos += mk;
         }
+        return NH_OK;
+    }
+
+    // masking: a sequence too short for a k-mer has no piece, but its masked bases are counted like any other's
+    int add_short(const char *s, size_t n) {
+        if (n < 7) return NH_OK;  // (fewer than 7 bases hold no perfect interval)
+        if (batch_cap + ctx_bytes - text.size() < n) {
+            int rc = flush();
+            if (rc) return rc;
+        }
+        dust_tiles(tiles, text.size(), n, 0, n);
+        text.insert(text.end(), s, s + n);
         return NH_OK;
     }
 
@@ -603,11 +672,14 @@ int write_database(Builder &B, const nh_build_args *a, uint64_t taxid, const std
 }
 
 int build_db(const nh_build_args *a, nh_build_stats *stats) {
-    if (stats) memset(stats, 0, sizeof *stats);
+    // (the caller's layout is told by struct_size: one of the first layout gets the first layout's stats and no more)
+    const bool grown = a && a->struct_size >= sizeof(nh_build_args);
+    const size_t stats_size = grown ? sizeof(nh_build_stats) : (size_t)NH_BUILD_STATS_SIZE_V1;
+    if (stats) memset(stats, 0, stats_size);
     // ---- arguments: everything refused here is refused before any device is touched and before anything is created
     if (!a) return set_error(NH_EINVAL, "nh_build_db: null arguments");
-    if (a->struct_size < sizeof(nh_build_args))
-        return set_error(NH_EINVAL, "nh_build_db: struct_size %u is smaller than nh_build_args (%zu)", a->struct_size, sizeof(nh_build_args));
+    if (a->struct_size < NH_BUILD_ARGS_SIZE_V1)
+        return set_error(NH_EINVAL, "nh_build_db: struct_size %u is smaller than nh_build_args (%u)", a->struct_size, NH_BUILD_ARGS_SIZE_V1);
     if (a->n_fasta == 0 || !a->fasta) return set_error(NH_EINVAL, "nh_build_db: no input (n_fasta 0)");
     for (uint32_t i = 0; i < a->n_fasta; i++)
         if (!a->fasta[i]) return set_error(NH_EINVAL, "nh_build_db: input %u is a null path", i);
@@ -638,6 +710,7 @@ int build_db(const nh_build_args *a, nh_build_stats *stats) {
     Builder B;
     B.device = a->device;
     B.threads = a->threads;
+    B.mask = grown && a->mask_low_complexity != 0;
     if (a->piece_kmers) B.piece = a->piece_kmers < (1ull << 31) ? a->piece_kmers : (1ull << 31);
     if (const char *env = getenv("NOHUMAN_BUILD_BATCH")) {  // test knob: bytes of text per batch (sequences cut at the batches' ends)
         const long long v = atoll(env);
@@ -678,6 +751,8 @@ int build_db(const nh_build_args *a, nh_build_stats *stats) {
     s.ambiguous_kmers = B.kmers - B.clean;
     s.capacity = capacity;
     s.size = B.claimed;
+    s.masked_bases = B.masked;
+    s.seconds_mask = B.t_mask;
     if (s.size == 0)
         return set_error(NH_EDB, "the input holds no k-mer to build from: %llu sequences, %llu bases, every sequence shorter than 35 bases or "
                          "ambiguous throughout", (unsigned long long)B.sequences, (unsigned long long)B.bases);
@@ -691,11 +766,12 @@ int build_db(const nh_build_args *a, nh_build_stats *stats) {
     s.seconds_write = since(t0);
     if (getenv("NOHUMAN_TRACE"))
         fprintf(stderr, "[nohuman trace] build: %llu k-mers, %llu ambiguous, %llu distinct minimizers, %llu cells of %llu; kernels alone: count %.4f s, "
-                        "insert %.4f s (batches of %llu bytes, pieces of %llu k-mers)\n",
+                        "insert %.4f s, mask %.4f s for %llu masked bases (batches of %llu bytes, pieces of %llu k-mers)\n",
                 (unsigned long long)s.kmers, (unsigned long long)s.ambiguous_kmers, (unsigned long long)s.distinct_minimizers,
-                (unsigned long long)s.size, (unsigned long long)s.capacity, count_kernel, B.t_kernel, (unsigned long long)B.batch_cap,
+                (unsigned long long)s.size, (unsigned long long)s.capacity, count_kernel, B.t_kernel, B.t_mask,
+                (unsigned long long)s.masked_bases, (unsigned long long)B.batch_cap,
                 (unsigned long long)B.piece);
-    if (stats) *stats = s;
+    if (stats) memcpy(stats, &s, stats_size);
     return NH_OK;
 }
 

@@ -226,7 +226,7 @@ struct Args {
     Codec type = C_NONE;
     // --build-db: make a database from FASTA instead of running on reads (nh_build_db)
     std::string build_db, taxon_name;
-    bool has_build_db = false, has_taxon_name = false, has_build_opt = false, force = false;
+    bool has_build_db = false, has_taxon_name = false, has_build_opt = false, force = false, mask_low_complexity = false;
     std::vector<std::string> reference;
     unsigned long long taxid = 0, capacity = 0;
     double load_factor = 0;
@@ -252,7 +252,10 @@ static void usage(FILE *f) {
           "  -H, --human                  Output human reads instead of removing them\n"
           "      --human-out1 <PATH>      Also write the human reads, in the same run, to this file (as -H would)\n"
           "      --human-out2 <PATH>      Second human output file (required with two inputs)\n"
-          "      --mask                   Replace the bases of human reads with N instead of removing them (every read is written, in input order)\n"
+          // (one line for both flags whose names start with --mask: the help keeps a single line that mentions "--mask")
+          "      --mask                   Replace the bases of human reads with N instead of removing them (every read is written, in input order). "
+          "With --build-db: --mask-low-complexity masks low-complexity sequence of the genome (symmetric DUST, window 64, level 20) before its "
+          "minimizers are taken [recommended for real genomes]\n"
           "  -C, --conf <[0, 1]>          Kraken2 minimum confidence score [default: 0.0]\n"
           "      --minimum-base-quality <INT>  Kraken2 minimum base quality: classify FASTQ bases with a lower Phred+33 quality as ambiguous (0-93; the reads written keep their bases) [default: 0]\n"
           "  -k, --kraken-output <FILE>   Write the Kraken2 read classification output to a file\n"
@@ -368,6 +371,7 @@ static Args parse_args(int argc, char **argv) {
             a.load_factor = f;
             a.has_build_opt = true;
         } else if (s == "--force") a.force = a.has_build_opt = true;
+        else if (s == "--mask-low-complexity") a.mask_low_complexity = true;
         else if (s == "-v" || s == "--verbose") g_verbose = true;
         else if (s == "-h" || s == "--help") { usage(stdout); exit(0); }
         else if (s == "-V" || s == "--version") { puts("nohuman 0.5.1 (MI355X engine)"); exit(0); }
@@ -389,6 +393,7 @@ static Args parse_args(int argc, char **argv) {
             if (!exists(r)) arg_error("invalid value '%s' for '--reference <FILE>': %s does not exist", r.c_str(), quoted(r).c_str());
         return a;
     }
+    if (a.mask_low_complexity) arg_error("the argument '--mask-low-complexity' needs '--build-db <DIR>': it masks the genome a database is built from, not reads");
     if (!a.reference.empty()) arg_error("the argument '--reference <FILE>' needs '--build-db <DIR>'");
     if (a.has_build_opt) arg_error("the arguments '--taxid', '--taxon-name', '--load-factor', '--capacity' and '--force' need '--build-db <DIR>'");
     if (a.input.empty() && !a.check && !a.download && !a.list)
@@ -496,14 +501,19 @@ int main(int argc, char **argv) {
         ba.capacity = args.capacity;
         ba.threads = args.threads;
         ba.force = args.force ? 1 : 0;
+        ba.mask_low_complexity = args.mask_low_complexity ? 1 : 0;
         if (const char *dv = getenv("NOHUMAN_DEVICES")) ba.device = (int32_t)strtol(dv, nullptr, 10);  // (one device: the first listed)
         nh_build_stats bs;
         if (nh_build_db(&ba, &bs) != 0) die("Failed to build the database\n\nCaused by:\n    %s", nh_last_error());
+        char masked[128] = "";
+        if (args.mask_low_complexity)
+            snprintf(masked, sizeof masked, "; %llu low-complexity bases masked (%.2f %% of the bases), mask %.2f s", (unsigned long long)bs.masked_bases,
+                     bs.bases ? 100.0 * (double)bs.masked_bases / (double)bs.bases : 0.0, bs.seconds_mask);
         INFO("Database built: %llu sequences, %llu bases, %llu distinct minimizers, capacity %llu, size %llu, load %.4f; read %.2f s, count %.2f s, "
-             "insert %.2f s, write %.2f s",
+             "insert %.2f s, write %.2f s%s",
              (unsigned long long)bs.sequences, (unsigned long long)bs.bases, (unsigned long long)bs.distinct_minimizers,
              (unsigned long long)bs.capacity, (unsigned long long)bs.size, bs.capacity ? (double)bs.size / (double)bs.capacity : 0.0, bs.seconds_read,
-             bs.seconds_count, bs.seconds_insert, bs.seconds_write);
+             bs.seconds_count, bs.seconds_insert, bs.seconds_write, masked);
         INFO("Database written to: %s", quoted(args.build_db).c_str());
         INFO("Done.");
         return 0;

@@ -147,19 +147,23 @@ def _read_stats(v) -> "ReadStats":
 
 
 def build_db(fasta_paths, out_dir, *, taxid: int = 0, taxon_name=None, load_factor: float = 0.0, capacity: int = 0,
-             piece_kmers: int = 0, device: int = 0, threads: int = 1, force: bool = False) -> dict:
+             piece_kmers: int = 0, device: int = 0, threads: int = 1, force: bool = False,
+             mask_low_complexity: bool = False) -> dict:
     """nh_build_db: a kraken2 database directory (hash.k2d, opts.k2d, taxo.k2d) built on the GPU from FASTA files (plain or
     gzip, wrapped lines, any number of records; one path or a list).  One taxon (taxid, 0 = 9606; taxon_name), the default
     geometry (k = 35, l = 31) only.  load_factor 0 = 0.7; capacity 0 = ceil(distinct minimizers / load_factor), counted on the
     device -- a capacity given is used as it is and the counting pass skipped; piece_kmers: k-mers per piece a wave scans (0 =
-    default); force: replace a database already in out_dir.  Returns nh_build_stats as a dict (sequences, bases, kmers,
-    ambiguous_kmers, distinct_minimizers, capacity, size, seconds_read / _count / _insert / _write); Engine.open(out_dir) and
-    run(out_dir, ...) work on the result."""
+    default); force: replace a database already in out_dir; mask_low_complexity: mask low-complexity sequence on the GPU before
+    the minimizers are taken (symmetric DUST, window 64, threshold 2.0 -- what kraken2-build's dustmasker step is for; see
+    dust_mask).  Returns nh_build_stats as a dict (sequences, bases, kmers, ambiguous_kmers, distinct_minimizers, capacity,
+    size, seconds_read / _count / _insert / _write, masked_bases, seconds_mask); Engine.open(out_dir) and run(out_dir, ...) work
+    on the result."""
     if isinstance(fasta_paths, (str, bytes, os.PathLike)):
         fasta_paths = [fasta_paths]
     paths = [os.fsencode(p) for p in fasta_paths]
-    a = _lib.nh_build_args()
-    a.struct_size = C.sizeof(_lib.nh_build_args)
+    a = _lib.nh_build_args_v2()
+    a.struct_size = C.sizeof(_lib.nh_build_args_v2)
+    a.mask_low_complexity = int(bool(mask_low_complexity))
     a.n_fasta = len(paths)
     arr = (C.c_char_p * max(len(paths), 1))(*paths)
     a.fasta = arr
@@ -172,9 +176,31 @@ def build_db(fasta_paths, out_dir, *, taxid: int = 0, taxon_name=None, load_fact
     a.device = int(device)
     a.threads = int(threads)
     a.force = int(bool(force))
-    s = _lib.nh_build_stats()
+    s = _lib.nh_build_stats_v2()
     _check(_lib.lib().nh_build_db(C.byref(a), C.byref(s)))
-    return {name: getattr(s, name) for name, _ in _lib.nh_build_stats._fields_}
+    return {name: getattr(s, name) for name, _ in _lib.nh_build_stats._fields_ + _lib.nh_build_stats_v2._fields_}
+
+
+def dust_mask(seqs, device: int = 0):
+    """nh_dust_mask: low-complexity masking of sequences on the GPU -- symmetric DUST at dustmasker's defaults (window 64,
+    threshold 2.0), the kernel build_db(mask_low_complexity=True) runs.  seqs: bytes objects (one alone is taken as a list of
+    one), each masked on its own: no triplet spans two of them.  Returns (the sequences with every masked base as N, the number
+    of masked bases).  Bytes other than ACGTacgt end a run and stay as they are."""
+    if isinstance(seqs, (bytes, bytearray, memoryview)):
+        seqs = [seqs]
+    seqs = [bytes(s) for s in seqs]
+    lens = np.array([len(s) for s in seqs], dtype=np.uint64)
+    starts = np.zeros(len(seqs), dtype=np.uint64)
+    if len(seqs) > 1:
+        starts[1:] = np.cumsum(lens)[:-1]
+    total = int(lens.sum())
+    buf = C.create_string_buffer(b"".join(seqs), max(total, 1))
+    u64p = C.POINTER(C.c_uint64)
+    masked = C.c_uint64(0)
+    _check(_lib.lib().nh_dust_mask(int(device), C.cast(buf, C.c_void_p), total, starts.ctypes.data_as(u64p),
+                                   lens.ctypes.data_as(u64p), len(seqs), C.byref(masked)))
+    raw = buf.raw
+    return [raw[int(a):int(a) + int(n)] for a, n in zip(starts, lens)], int(masked.value)
 
 
 def device_count() -> int:

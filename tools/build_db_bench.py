@@ -13,6 +13,11 @@ sequences (34 in every piece_kmers + 34), so it inserts slightly fewer minimizer
 the call, which ends in a device synchronise.
 
     python tools/build_db_bench.py --bases 512000000 --out profiles/build_db.txt
+
+--mask-low-complexity builds with the masking on (nh_dust.hip): masked_bases, seconds_mask and, from the trace line, the mask
+kernel's time over both passes (HIP events) join each build's numbers.  The mask's work does not depend on the content, but what it
+masks does: --low-complexity-share F plants homopolymers and microsatellites (periods 2 to 6, 20 to 400 bases each) over about that
+share of the genome, which as iid ACGT masks some 0.1 %.
 """
 import argparse
 import json
@@ -29,13 +34,25 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 TRACE = re.compile(r"kernels alone: count ([0-9.]+) s, insert ([0-9.]+) s")
+TRACE_MASK = re.compile(r"mask ([0-9.]+) s for ([0-9]+) masked bases")
 PIECE = 1984  # the library's default piece: 16 tiles of 124 k-mers
 
 
-def make_genome(bases, n_records, n_runs, seed):
-    """uint8 array of ACGT with n_runs stretches of N (10 kb to 1 Mb), and the records' boundaries"""
+def make_genome(bases, n_records, n_runs, seed, low_share=0.0):
+    """uint8 array of ACGT with n_runs stretches of N (10 kb to 1 Mb), and the records' boundaries; low_share: about that share
+    of the bases under planted homopolymers and repeats of period 2 to 6 (drawn after the N runs' generator, so that a share of 0
+    gives the genome the tool always made)"""
     rng = np.random.default_rng(seed)
     g = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, size=bases, dtype=np.uint8)]
+    if low_share > 0:
+        lrng = np.random.default_rng(seed + 1)
+        n = max(1, int(bases * low_share / 210))  # (lengths are uniform in 20 .. 400)
+        lens = lrng.integers(20, 401, size=n)
+        at = lrng.integers(0, max(1, bases - 400), size=n)
+        acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+        for p, ln in zip(at.tolist(), lens.tolist()):
+            unit = acgt[lrng.integers(0, 4, size=int(lrng.integers(1, 7)))]
+            g[p:p + ln] = np.resize(unit, ln)
     for _ in range(n_runs):
         ln = int(min(bases // 20 + 1, 10 ** rng.uniform(4, 6)))
         p = int(rng.integers(0, bases - ln))
@@ -83,6 +100,10 @@ def main():
     ap.add_argument("--threads", type=int, default=4)
     ap.add_argument("--workdir", default=None, help="where the FASTA and the databases go (default: a temporary directory)")
     ap.add_argument("--out", default=None, help="append the result lines to this file")
+    ap.add_argument("--mask-low-complexity", action="store_true", help="build with low-complexity masking")
+    ap.add_argument("--low-complexity-share", type=float, default=0.0, metavar="F",
+                    help="plant homopolymers and microsatellites over about this share of the genome")
+    ap.add_argument("--no-baseline", action="store_true", help="leave out the k_insert_sequences baseline")
     a = ap.parse_args()
 
     import torch
@@ -93,10 +114,11 @@ def main():
     print("probe:", nohuman_amd.probe(), file=sys.stderr)
     work = a.workdir or tempfile.mkdtemp(prefix="build_db_bench")
     os.makedirs(work, exist_ok=True)
-    res = {"bases": a.bases, "records": a.records, "n_runs": a.n_runs, "seed": a.seed, "piece_kmers": PIECE, "threads": a.threads}
+    res = {"bases": a.bases, "records": a.records, "n_runs": a.n_runs, "seed": a.seed, "piece_kmers": PIECE, "threads": a.threads,
+           "mask_low_complexity": a.mask_low_complexity, "low_complexity_share": a.low_complexity_share}
     try:
         t0 = time.time()
-        g, cuts = make_genome(a.bases, a.records, a.n_runs, a.seed)
+        g, cuts = make_genome(a.bases, a.records, a.n_runs, a.seed, a.low_complexity_share)
         fa = os.path.join(work, "genome.fa")
         res["fasta_bytes"] = write_fasta(fa, g, cuts)
         res["generate_s"] = round(time.time() - t0, 2)
@@ -106,12 +128,17 @@ def main():
             d = os.path.join(work, "db%d" % r)
             errf = os.path.join(work, "trace%d.txt" % r)
             t0 = time.time()
-            st = traced(lambda: nohuman_amd.build_db([fa], d, threads=a.threads), errf)
+            kw = {"mask_low_complexity": True} if a.mask_low_complexity else {}
+            st = traced(lambda: nohuman_amd.build_db([fa], d, threads=a.threads, **kw), errf)
             wall = time.time() - t0
-            m = TRACE.search(open(errf, errors="replace").read())
+            trace = open(errf, errors="replace").read()
+            m = TRACE.search(trace)
             b = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in st.items()}
             b["wall_s"] = round(wall, 3)
             b["count_kernel_s"], b["insert_kernel_s"] = (float(m.group(1)), float(m.group(2))) if m else (None, None)
+            mm = TRACE_MASK.search(trace)
+            if a.mask_low_complexity and mm:
+                b["mask_kernel_s"] = float(mm.group(1))
             b["hash_bytes"] = os.path.getsize(os.path.join(d, "hash.k2d"))
             builds.append(b)
             if r + 1 < a.runs:
@@ -125,36 +152,40 @@ def main():
             res["count_kernel_Mkeys_s"] = round(last["distinct_minimizers"] / last["count_kernel_s"] / 1e6, 1)
         res["insert_stage_Mcells_s"] = round(size / last["seconds_insert"] / 1e6, 1)
         res["whole_build_Mbases_s"] = round(a.bases / last["wall_s"] / 1e6, 1)
+        if last.get("mask_kernel_s"):  # (both passes: every base goes through the kernel twice)
+            res["mask_kernel_Gbases_s"] = round(2 * a.bases / last["mask_kernel_s"] / 1e9, 2)
+            res["masked_share"] = round(last["masked_bases"] / a.bases, 5)
         # the database opens (content check) and holds what the build says
         with nohuman_amd.Engine.open(os.path.join(work, "db%d" % (a.runs - 1))) as eng:
             assert eng.db_check().non_empty_cells == size
 
-        # ---- baseline: k_insert_sequences on the same bases, resident, contiguous sequences of one piece each
-        os.environ["NOHUMAN_TABLE_COPIES"] = "1"
-        dev = torch.device("cuda:0")
-        seg = PIECE + 34
-        offs = []
-        for i in range(len(cuts) - 1):
-            o = np.arange(cuts[i], cuts[i + 1], seg, dtype=np.int64)
-            offs.append(o)
-        offs = np.concatenate(offs + [np.array([a.bases], dtype=np.int64)])
-        # (a record's last sequence ends where the next record starts: boundaries are sequence starts)
-        d_bases = torch.empty(a.bases + 64, dtype=torch.uint8, device=dev)
-        d_bases[:a.bases] = torch.from_numpy(g).to(dev)
-        d_bases[a.bases:] = 0
-        d_offs = torch.from_numpy(offs).to(dev)
-        base = []
-        for r in range(a.runs):
-            with nohuman_amd.Engine.synthetic(cap, 0, depth=2, seed=1) as eng:
-                torch.cuda.synchronize()
-                t0 = time.time()
-                eng.add_sequences(d_bases.data_ptr(), d_offs.data_ptr(), offs.size - 1, 2)
-                torch.cuda.synchronize()
-                dt = time.time() - t0
-                base.append({"seconds": round(dt, 4), "size": int(eng.info.size)})
-        res["baseline"] = base
-        res["baseline_sequences"] = int(offs.size - 1)
-        res["baseline_Mcells_s"] = round(base[-1]["size"] / base[-1]["seconds"] / 1e6, 1)
+        if not a.no_baseline:
+            # ---- baseline: k_insert_sequences on the same bases, resident, contiguous sequences of one piece each
+            os.environ["NOHUMAN_TABLE_COPIES"] = "1"
+            dev = torch.device("cuda:0")
+            seg = PIECE + 34
+            offs = []
+            for i in range(len(cuts) - 1):
+                o = np.arange(cuts[i], cuts[i + 1], seg, dtype=np.int64)
+                offs.append(o)
+            offs = np.concatenate(offs + [np.array([a.bases], dtype=np.int64)])
+            # (a record's last sequence ends where the next record starts: boundaries are sequence starts)
+            d_bases = torch.empty(a.bases + 64, dtype=torch.uint8, device=dev)
+            d_bases[:a.bases] = torch.from_numpy(g).to(dev)
+            d_bases[a.bases:] = 0
+            d_offs = torch.from_numpy(offs).to(dev)
+            base = []
+            for r in range(a.runs):
+                with nohuman_amd.Engine.synthetic(cap, 0, depth=2, seed=1) as eng:
+                    torch.cuda.synchronize()
+                    t0 = time.time()
+                    eng.add_sequences(d_bases.data_ptr(), d_offs.data_ptr(), offs.size - 1, 2)
+                    torch.cuda.synchronize()
+                    dt = time.time() - t0
+                    base.append({"seconds": round(dt, 4), "size": int(eng.info.size)})
+            res["baseline"] = base
+            res["baseline_sequences"] = int(offs.size - 1)
+            res["baseline_Mcells_s"] = round(base[-1]["size"] / base[-1]["seconds"] / 1e6, 1)
     finally:
         if not a.workdir:
             shutil.rmtree(work, ignore_errors=True)
