@@ -119,7 +119,8 @@ def order_free(seqs, capacity, mins=None):
     if mins is None:
         mins, _, _ = minimizers(seqs)
     keys = {lit.fmix64(m) >> (32 + VALUE_BITS) for m in mins}
-    assert len(keys) == len(mins) == size, "two minimizers share a compacted key: choose another seed"
+    assert len(keys) == len(mins) == size, "two minimizers share a compacted key: choose another seed.  (An input that shares " \
+        "keys on purpose has no order-free table to compare with: hold it to build_forge.valid_table instead.)"
     return fwd, size, mins
 
 

@@ -5,7 +5,7 @@ table, the CPU oracle, the CLI.
 Which key sits in which occupied cell of a probe run depends on the order in which the waves arrive (as in kraken2's threaded
 build), so tables are compared by header, occupied positions and sorted cells (tests/build_db_util.py same_table).  That is the
 whole table only while no two distinct minimizers share a compacted key: build_db_util.order_free asserts it for every input
-used here, on the CPU, before anything is compared."""
+used here, on the CPU, before anything is compared.  Inputs that share keys on purpose: tests/test_gpu_build_db_forge.py."""
 import os
 import subprocess
 
