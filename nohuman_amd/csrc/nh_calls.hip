@@ -10,31 +10,26 @@
 // <id> is mate 1's header from the byte behind '@' / '>' for the id length the reader found (RecRef::idlen: up to the first
 // space, tab or '\r'); a paired run drops a trailing "/1" or "/2" from an id longer than two bytes (kraken2 TrimPairInfo).
 //
-// Three launches on the batch's stream, both outputs in each (grid.y = output):
+// Three launches on the batch's stream, both outputs in each (grid.y = output); the scheme and its parts are nh_outbuild.h's:
 //   k_calls_sizes  per block of CB_FRAGS fragments: the sum of their line lengths and the number of lines
-//   k_calls_scan   per output, one workgroup: exclusive scan of the block sums in place -> block offsets; the output's
-//                  total bytes and lines
-//   k_calls_write  per block: the fragments' lengths again, an exclusive scan inside the block, then one wave per line writes
-//                  it: aligned dwords of the output; a dword that lies inside the id is two aligned loads and v_alignbyte; the
-//                  dwords at field boundaries and of the numbers are put together byte by byte (decimal digits by division,
-//                  no printf), and the first and last partial dwords of a line (shared with its neighbours) are written with
-//                  byte stores.  Nothing is sized by the id's length.
-// The kernel boundaries are the only hand-off between the launches.  Every load stays inside the dwords that hold bytes of
-// [0, ntext); every store inside [0, cap) of its output's buffer.  A record whose header lies outside the text, an id longer
+//   k_calls_scan   per output, one workgroup: block sums -> block offsets; the output's total bytes and lines
+//   k_calls_write  per block: the lines' offsets, then one wave per line writes it; the only field that is copied as dwords
+//                  is the id, the numbers are put together byte by byte (decimal digits by division, no printf).  Nothing
+//                  is sized by the id's length.
+// Every load stays inside the dwords that hold bytes of [0, ntext); every store inside [0, cap) of its output's buffer.  A record whose header lies outside the text, an id longer
 // than its header, a call outside the taxon table or a total above the buffer sets bit 16 of the engine's error word and
 // writes nothing.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "nh_internal.h"
+#include "nh_outbuild.h"
 
 namespace nh {
 
 namespace {
 
-constexpr int CB_THREADS = 256;
-constexpr int CB_FRAGS = CB_THREADS;  // fragments of one block: one a thread in the scans, 64 a wave in the write
-constexpr int CB_WAVES = CB_THREADS / 64;
+constexpr int CB_FRAGS = OB_THREADS;  // fragments of one block: one a thread in the scans, 64 a wave in the write
 constexpr int ERR_CALLS = 16;
 constexpr int N_FIELDS = 6;  // the numbers of a table line: taxid, len1, len2 (paired), total_kmers, clade_hits, hit_groups
 
@@ -46,15 +41,6 @@ struct Line {  // one fragment's lines
     uint32_t nd[N_FIELDS];  // decimal digits of v[k]; 0: the field is absent (len2 of a single-end run)
     uint64_t len[2];        // bytes of its line in output 0 / 1, 0: none
 };
-
-__device__ inline uint32_t decimal_digits(uint64_t v) {
-    uint32_t n = 1;
-    while (v >= 10) {
-        v /= 10;
-        n++;
-    }
-    return n;
-}
 
 // the lines of fragment f; both lengths 0 for a fragment that fails its bounds (error set)
 __device__ inline Line load_line(const CallsArgs &a, uint64_t f, bool report) {
@@ -91,28 +77,9 @@ __device__ inline Line load_line(const CallsArgs &a, uint64_t f, bool report) {
     return L;
 }
 
-// exclusive scan over the block's threads of one value each; *total: the block's sum
-__device__ inline uint64_t block_exclusive_scan(uint64_t v, uint64_t *wsum, uint64_t *total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint64_t incl = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t t = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += t;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint64_t before = 0, all = 0;
-    for (int w = 0; w < CB_WAVES; w++) {
-        before += w < wave ? wsum[w] : 0;
-        all += wsum[w];
-    }
-    *total = all;
-    return before + incl - v;
-}
-
 // blk: [o * nblk + b] the bytes of block b in output o, [(2 + o) * nblk + b] its lines
-__global__ void __launch_bounds__(CB_THREADS) k_calls_sizes(CallsArgs a) {
-    __shared__ uint64_t wsum[CB_WAVES], wcnt[CB_WAVES];
+__global__ void __launch_bounds__(OB_THREADS) k_calls_sizes(CallsArgs a) {
+    __shared__ uint64_t wsum[OB_WAVES], wcnt[OB_WAVES];
     const int o = blockIdx.y;
     const Line L = load_line(a, (uint64_t)blockIdx.x * CB_FRAGS + threadIdx.x, o == 0);
     const uint64_t len = o ? L.len[1] : L.len[0];
@@ -126,31 +93,23 @@ __global__ void __launch_bounds__(CB_THREADS) k_calls_sizes(CallsArgs a) {
 }
 
 // one workgroup per output: block sums -> exclusive block offsets (in place), the output's total bytes and lines
-__global__ void __launch_bounds__(CB_THREADS) k_calls_scan(CallsArgs a) {
-    __shared__ uint64_t wsum[CB_WAVES], wcnt[CB_WAVES];
+__global__ void __launch_bounds__(OB_THREADS) k_calls_scan(CallsArgs a) {
+    __shared__ uint64_t wsum[OB_WAVES], wcnt[OB_WAVES];
     const int o = blockIdx.x;
-    uint64_t *b = a.blk + (uint64_t)o * a.nblk;
+    const uint64_t total = scan_block_sums(a.blk + (uint64_t)o * a.nblk, a.nblk, wsum);
     const uint64_t *cnt = a.blk + (uint64_t)(2 + o) * a.nblk;
-    uint64_t carry = 0, lines = 0;
-    for (uint64_t c = 0; c < a.nblk; c += CB_THREADS) {
+    uint64_t lines = 0;
+    for (uint64_t c = 0; c < a.nblk; c += OB_THREADS) {
         const uint64_t i = c + threadIdx.x;
-        const uint64_t v = i < a.nblk ? b[i] : 0;
-        uint64_t sum, nl;
-        const uint64_t ex = block_exclusive_scan(v, wsum, &sum);
+        uint64_t nl;
         (void)block_exclusive_scan(i < a.nblk ? cnt[i] : 0, wcnt, &nl);
-        if (i < a.nblk) b[i] = carry + ex;
-        carry += sum;
         lines += nl;
-        __syncthreads();  // (wsum and wcnt are written again by the next chunk)
+        __syncthreads();  // (wcnt is written again by the next chunk)
     }
     if (threadIdx.x == 0) {
-        if (carry > a.cap[o]) {
-            atomicOr(a.error, ERR_CALLS);
-            carry = 0;
-            lines = 0;
-        }
-        a.total[o] = carry;
-        a.total[2 + o] = lines;
+        const bool fits = total_fits(total, a.cap[o], a.error, ERR_CALLS);
+        a.total[o] = fits ? total : 0;
+        a.total[2 + o] = fits ? lines : 0;
     }
 }
 
@@ -179,33 +138,22 @@ __device__ inline uint8_t line_byte(const CallsArgs &a, const Line &L, int o, ui
     return (uint8_t)('0' + v % 10);
 }
 
-// the 4 text bytes at src (src + 3 < ntext): two aligned loads, the second only where the bytes reach into it
-__device__ inline uint32_t text_dword(const char *text, uint64_t src) {
-    const uint32_t *w = reinterpret_cast<const uint32_t *>(text + (src & ~3ull));
-    const uint32_t sh = (uint32_t)(src & 3);
-    const uint32_t lo = w[0];
-    if (sh == 0) return lo;
-    return __builtin_amdgcn_alignbyte(w[1], lo, sh);
-}
-
-__global__ void __launch_bounds__(CB_THREADS) k_calls_write(CallsArgs a) {
-    __shared__ uint64_t wsum[CB_WAVES];
+__global__ void __launch_bounds__(OB_THREADS) k_calls_write(CallsArgs a) {
+    __shared__ uint64_t wsum[OB_WAVES];
     __shared__ uint64_t s_off[CB_FRAGS];
     const int o = blockIdx.y;
     const uint64_t fb = (uint64_t)blockIdx.x * CB_FRAGS;
-    {
-        const Line L = load_line(a, fb + threadIdx.x, false);
-        uint64_t total;
-        s_off[threadIdx.x] = block_exclusive_scan(o ? L.len[1] : L.len[0], wsum, &total);
-    }
-    __syncthreads();
+    block_offsets<1>(s_off, wsum, [&](uint32_t fl) {
+        const Line L = load_line(a, fb + fl, false);
+        return o ? L.len[1] : L.len[0];
+    });
     char *out = a.out[o];
     const uint64_t cap = a.cap[o];
     const uint64_t base = a.blk[(uint64_t)o * a.nblk + blockIdx.x];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // wave w writes the lines of fragments [w * 64, w * 64 + 64) of the block, one after another
-    for (int k = 0; k < CB_FRAGS / CB_WAVES; k++) {
-        const int fl = wave * (CB_FRAGS / CB_WAVES) + k;
+    for (int k = 0; k < CB_FRAGS / OB_WAVES; k++) {
+        const int fl = wave * (CB_FRAGS / OB_WAVES) + k;
         if (fb + fl >= a.n) break;
         const Line L = load_line(a, fb + fl, false);
         const uint64_t len = o ? L.len[1] : L.len[0];
@@ -216,21 +164,13 @@ __global__ void __launch_bounds__(CB_THREADS) k_calls_write(CallsArgs a) {
             continue;
         }
         const uint64_t pI = o ? 0 : 2;  // where the id starts in the line
-        const uint64_t end = at + len;
-        for (uint64_t D = (at & ~3ull) + 4ull * lane; D < end; D += 256) {
-            if (D >= at && D + 4 <= end) {
-                const uint64_t p = D - at;
-                uint32_t v;
-                if (p >= pI && p + 4 <= pI + L.idlen) v = text_dword(a.text, L.id + (p - pI));
-                else
-                    v = (uint32_t)line_byte(a, L, o, p) | (uint32_t)line_byte(a, L, o, p + 1) << 8 |
-                        (uint32_t)line_byte(a, L, o, p + 2) << 16 | (uint32_t)line_byte(a, L, o, p + 3) << 24;
-                *reinterpret_cast<uint32_t *>(out + D) = v;
-            } else {  // the line's first or last dword: its neighbours own the other bytes
-                for (uint64_t x = D; x < D + 4; x++)
-                    if (x >= at && x < end) out[x] = (char)line_byte(a, L, o, x - at);
-            }
-        }
+        wave_write(
+            out, at, len, lane, [&](uint64_t p) { return line_byte(a, L, o, p); },
+            [&](uint64_t p, uint32_t *v) {
+                if (!(p >= pI && p + 4 <= pI + L.idlen)) return false;
+                *v = text_dword(a.text, L.id + (p - pI));
+                return true;
+            });
     }
 }
 
@@ -241,9 +181,9 @@ uint64_t calls_blocks(uint64_t n) { return (n + CB_FRAGS - 1) / CB_FRAGS; }
 hipError_t launch_calls(const CallsArgs &a, hipStream_t stream) {
     if (a.n == 0) return hipMemsetAsync(a.total, 0, 4 * sizeof(uint64_t), stream);
     const dim3 grid((unsigned)a.nblk, 2);
-    hipLaunchKernelGGL(k_calls_sizes, grid, dim3(CB_THREADS), 0, stream, a);
-    hipLaunchKernelGGL(k_calls_scan, dim3(2), dim3(CB_THREADS), 0, stream, a);
-    hipLaunchKernelGGL(k_calls_write, grid, dim3(CB_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(k_calls_sizes, grid, dim3(OB_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(k_calls_scan, dim3(2), dim3(OB_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(k_calls_write, grid, dim3(OB_THREADS), 0, stream, a);
     return hipGetLastError();
 }
 

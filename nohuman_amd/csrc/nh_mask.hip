@@ -7,34 +7,32 @@
 // batch's text, the bytes are the same as the normal keep_human = 0 output (the raw text); for the others (CRLF, "+id",
 // trailing blanks, joined FASTA, no final newline) they are made from the parsed fields as the host's put_record() does.
 //
-// Four launches on the batch's stream, both mates in each (grid.y = mate):
+// Four launches on the batch's stream, both mates in each (grid.y = mate); the scheme of sizes, scan and write and its
+// parts are nh_outbuild.h's, the FAST blocks are this builder's own:
 //   k_mask_sizes  per block of MB_FRAGS fragments: the sum of their output lengths, and whether the block is FAST: every
 //                 record already in output form in the text (the same test as nh_fastx.h's raw_end, made on the device from
 //                 the fields and a few bytes around them) and each record's text starting where the one before ends
-//   k_mask_scan   per mate, one workgroup: exclusive scan of the block sums in place -> block offsets; the mate's total and
-//                 (for the trace line) its number of FAST blocks
+//   k_mask_scan   per mate, one workgroup: block sums -> block offsets; the mate's total and (for the trace line) its
+//                 number of FAST blocks
 //   k_mask_copy   MB_SUB workgroups per block.  FAST block: its text is one contiguous range, copied 16 bytes a lane (aligned
 //                 dwordx4 stores; the two partial chunks at the range's ends, shared with the neighbouring blocks, byte by
-//                 byte).  Other blocks: the lengths again, an exclusive scan inside the block, then one wave per record
-//                 writes it as aligned dwords (the split builder's scheme, nh_split.hip), the sequence of a classified
-//                 fragment as 'N' dwords
-//   k_mask_fill   FAST blocks only: 'N' over the sequence ranges of the classified fragments
-// The kernel boundaries are the only hand-off between the launches.  Every load stays inside the dwords that hold bytes of
-// [0, ntext); every store inside [0, cap) of its mate's buffer.  A record whose fields lie outside the text or a total above
-// the buffer sets bit 8 of the engine's error word and writes nothing.
+//                 byte).  Other blocks: the records' offsets, then one wave per record writes it; the fields that are
+//                 copied as dwords are the header, the sequence (of a classified fragment: 'N' dwords) and the qualities
+//   k_mask_fill   FAST blocks only: 'N' over the sequence ranges of the classified fragments, written as pieces of one field
+// Every load stays inside the dwords that hold bytes of [0, ntext); every store inside [0, cap) of its mate's buffer.  A
+// record whose fields lie outside the text or a total above the buffer sets bit 8 of the engine's error word and writes nothing.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "nh_internal.h"
+#include "nh_outbuild.h"
 
 namespace nh {
 
 namespace {
 
-constexpr int MB_THREADS = 256;
 constexpr int MB_PER_THREAD = 4;
-constexpr int MB_FRAGS = MB_THREADS * MB_PER_THREAD;  // fragments of one block
-constexpr int MB_WAVES = MB_THREADS / 64;
+constexpr int MB_FRAGS = OB_THREADS * MB_PER_THREAD;  // fragments of one block
 constexpr int MB_SUB = 4;  // workgroups of k_mask_copy / k_mask_fill per block
 constexpr int ERR_MASK = 8;
 constexpr uint32_t NNNN = 0x4E4E4E4Eu;
@@ -79,27 +77,8 @@ __device__ inline bool in_output_form(const MaskArgs &a, const MRec &r, bool fas
     return t[r.s + r.slen + 1] == '+' && t[r.s + r.slen + 2] == '\n' && r.q == r.s + r.slen + 3 && t[r.q + r.qlen] == '\n';
 }
 
-// exclusive scan over the block's threads (MB_THREADS) of one value each; *total: the block's sum
-__device__ inline uint64_t block_exclusive_scan(uint64_t v, uint64_t *wsum, uint64_t *total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint64_t incl = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t t = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += t;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint64_t before = 0, all = 0;
-    for (int w = 0; w < MB_WAVES; w++) {
-        before += w < wave ? wsum[w] : 0;
-        all += wsum[w];
-    }
-    *total = all;
-    return before + incl - v;
-}
-
-__global__ void __launch_bounds__(MB_THREADS) k_mask_sizes(MaskArgs a) {
-    __shared__ uint64_t wsum[MB_WAVES];
+__global__ void __launch_bounds__(OB_THREADS) k_mask_sizes(MaskArgs a) {
+    __shared__ uint64_t wsum[OB_WAVES];
     const int m = blockIdx.y;
     const bool fastq = a.fastq[m] != 0;
     const uint64_t fb = (uint64_t)blockIdx.x * MB_FRAGS;
@@ -126,27 +105,18 @@ __global__ void __launch_bounds__(MB_THREADS) k_mask_sizes(MaskArgs a) {
 }
 
 // one workgroup per mate: block sums -> exclusive block offsets (in place), the mate's total and its number of FAST blocks
-__global__ void __launch_bounds__(MB_THREADS) k_mask_scan(MaskArgs a) {
-    __shared__ uint64_t wsum[MB_WAVES];
+__global__ void __launch_bounds__(OB_THREADS) k_mask_scan(MaskArgs a) {
+    __shared__ uint64_t wsum[OB_WAVES];
     const int m = blockIdx.x;
-    uint64_t *b = a.blk + (uint64_t)m * a.nblk;
+    const uint64_t total = scan_block_sums(a.blk + (uint64_t)m * a.nblk, a.nblk, wsum);
     const uint32_t *fast = a.fast + (uint64_t)m * a.nblk;
-    uint64_t carry = 0, nfast = 0;
-    for (uint64_t c = 0; c < a.nblk; c += MB_THREADS) {
+    uint64_t nfast = 0;
+    for (uint64_t c = 0; c < a.nblk; c += OB_THREADS) {
         const uint64_t i = c + threadIdx.x;
-        const uint64_t v = i < a.nblk ? b[i] : 0;
-        uint64_t sum;
-        const uint64_t ex = block_exclusive_scan(v, wsum, &sum);
-        if (i < a.nblk) b[i] = carry + ex;
-        carry += sum;
-        nfast += (uint64_t)__syncthreads_count(i < a.nblk && fast[i] != 0);  // (also: wsum is written again by the next chunk)
+        nfast += (uint64_t)__syncthreads_count(i < a.nblk && fast[i] != 0);
     }
     if (threadIdx.x == 0) {
-        if (carry > a.cap[m]) {
-            atomicOr(a.error, ERR_MASK);
-            carry = 0;
-        }
-        a.total[m] = carry;
+        a.total[m] = total_fits(total, a.cap[m], a.error, ERR_MASK) ? total : 0;
         a.total[2 + m] = nfast;
     }
 }
@@ -164,15 +134,6 @@ __device__ inline uint8_t mrec_byte(const MaskArgs &a, const MRec &r, bool fastq
     p -= 3;
     if (p < r.qlen) return (uint8_t)a.text[r.q + p];
     return '\n';
-}
-
-// the 4 text bytes at src (src + 3 < ntext): two aligned loads, the second only where the bytes reach into it
-__device__ inline uint32_t text_dword(const char *text, uint64_t src) {
-    const uint32_t *w = reinterpret_cast<const uint32_t *>(text + (src & ~3ull));
-    const uint32_t sh = (uint32_t)(src & 3);
-    const uint32_t lo = w[0];
-    if (sh == 0) return lo;
-    return __builtin_amdgcn_alignbyte(w[1], lo, sh);
 }
 
 // the 16 text bytes at src (src + 15 < ntext): four aligned dwords, a fifth only where the bytes reach into it
@@ -197,8 +158,8 @@ __device__ inline bool fast_range(const MaskArgs &a, int m, uint64_t fb, uint64_
     return ok;
 }
 
-__global__ void __launch_bounds__(MB_THREADS) k_mask_copy(MaskArgs a) {
-    __shared__ uint64_t wsum[MB_WAVES];
+__global__ void __launch_bounds__(OB_THREADS) k_mask_copy(MaskArgs a) {
+    __shared__ uint64_t wsum[OB_WAVES];
     __shared__ uint64_t s_off[MB_FRAGS];
     const int m = blockIdx.y;
     const uint64_t blk = blockIdx.x / MB_SUB;
@@ -212,8 +173,8 @@ __global__ void __launch_bounds__(MB_THREADS) k_mask_copy(MaskArgs a) {
         uint64_t h0, L;
         if (!fast_range(a, m, fb, base, &h0, &L, u == 0 && threadIdx.x == 0)) return;
         const uint64_t end = base + L;
-        const uint64_t step = 16ull * MB_THREADS * MB_SUB;
-        for (uint64_t D = (base & ~15ull) + 16ull * ((uint64_t)u * MB_THREADS + threadIdx.x); D < end; D += step) {
+        const uint64_t step = 16ull * OB_THREADS * MB_SUB;
+        for (uint64_t D = (base & ~15ull) + 16ull * ((uint64_t)u * OB_THREADS + threadIdx.x); D < end; D += step) {
             if (D >= base && D + 16 <= end) {
                 *reinterpret_cast<uint4 *>(out + D) = text_x4(a.text, h0 + (D - base));
             } else {  // the range's first or last chunk: the neighbouring blocks own the other bytes
@@ -223,24 +184,11 @@ __global__ void __launch_bounds__(MB_THREADS) k_mask_copy(MaskArgs a) {
         }
         return;
     }
-    {
-        uint64_t len[MB_PER_THREAD], mine = 0;
-        for (int j = 0; j < MB_PER_THREAD; j++) {
-            len[j] = load_mrec(a, fb + threadIdx.x * MB_PER_THREAD + j, m, false).len;
-            mine += len[j];
-        }
-        uint64_t total;
-        uint64_t o = block_exclusive_scan(mine, wsum, &total);
-        for (int j = 0; j < MB_PER_THREAD; j++) {
-            s_off[threadIdx.x * MB_PER_THREAD + j] = o;
-            o += len[j];
-        }
-    }
-    __syncthreads();
+    block_offsets<MB_PER_THREAD>(s_off, wsum, [&](uint32_t fl) { return load_mrec(a, fb + fl, m, false).len; });
     const int lane = threadIdx.x & 63;
-    const int gw = u * MB_WAVES + (threadIdx.x >> 6);
-    // wave gw of the block's MB_SUB * MB_WAVES writes the records gw, gw + MB_SUB * MB_WAVES, ... one after another
-    for (int fl = gw; fl < MB_FRAGS; fl += MB_SUB * MB_WAVES) {
+    const int gw = u * OB_WAVES + (threadIdx.x >> 6);
+    // wave gw of the block's MB_SUB * OB_WAVES writes the records gw, gw + MB_SUB * OB_WAVES, ... one after another
+    for (int fl = gw; fl < MB_FRAGS; fl += MB_SUB * OB_WAVES) {
         const MRec r = load_mrec(a, fb + fl, m, false);
         if (r.len == 0) continue;
         const uint64_t o = base + s_off[fl];
@@ -249,28 +197,20 @@ __global__ void __launch_bounds__(MB_THREADS) k_mask_copy(MaskArgs a) {
             continue;
         }
         const uint64_t pB = (uint64_t)r.hlen + 1, pC = pB + r.slen + 3;
-        const uint64_t end = o + r.len;
-        for (uint64_t D = (o & ~3ull) + 4ull * lane; D < end; D += 256) {
-            if (D >= o && D + 4 <= end) {
-                const uint64_t p = D - o;
-                uint32_t v;
-                if (p + 4 <= r.hlen) v = text_dword(a.text, r.h + p);
-                else if (p >= pB && p + 4 <= pB + r.slen) v = r.cls ? NNNN : text_dword(a.text, r.s + (p - pB));
-                else if (fastq && p >= pC && p + 4 <= pC + r.qlen) v = text_dword(a.text, r.q + (p - pC));
-                else
-                    v = (uint32_t)mrec_byte(a, r, fastq, p) | (uint32_t)mrec_byte(a, r, fastq, p + 1) << 8 |
-                        (uint32_t)mrec_byte(a, r, fastq, p + 2) << 16 | (uint32_t)mrec_byte(a, r, fastq, p + 3) << 24;
-                *reinterpret_cast<uint32_t *>(out + D) = v;
-            } else {  // the record's first or last dword: its neighbours own the other bytes
-                for (uint64_t x = D; x < D + 4; x++)
-                    if (x >= o && x < end) out[x] = (char)mrec_byte(a, r, fastq, x - o);
-            }
-        }
+        wave_write(
+            out, o, r.len, lane, [&](uint64_t p) { return mrec_byte(a, r, fastq, p); },
+            [&](uint64_t p, uint32_t *v) {
+                if (p + 4 <= r.hlen) *v = text_dword(a.text, r.h + p);
+                else if (p >= pB && p + 4 <= pB + r.slen) *v = r.cls ? NNNN : text_dword(a.text, r.s + (p - pB));
+                else if (fastq && p >= pC && p + 4 <= pC + r.qlen) *v = text_dword(a.text, r.q + (p - pC));
+                else return false;
+                return true;
+            });
     }
 }
 
 // FAST blocks: the copy wrote the raw text; 'N' over the sequences of the classified fragments
-__global__ void __launch_bounds__(MB_THREADS) k_mask_fill(MaskArgs a) {
+__global__ void __launch_bounds__(OB_THREADS) k_mask_fill(MaskArgs a) {
     const int m = blockIdx.y;
     const uint64_t blk = blockIdx.x / MB_SUB;
     const int u = blockIdx.x % MB_SUB;
@@ -281,21 +221,19 @@ __global__ void __launch_bounds__(MB_THREADS) k_mask_fill(MaskArgs a) {
     if (!fast_range(a, m, fb, base, &h0, &L, false)) return;  // (the copy reported it and wrote nothing)
     char *out = a.out[m];
     const int lane = threadIdx.x & 63;
-    const int gw = u * MB_WAVES + (threadIdx.x >> 6);
-    for (int fl = gw; fl < MB_FRAGS; fl += MB_SUB * MB_WAVES) {
+    const int gw = u * OB_WAVES + (threadIdx.x >> 6);
+    for (int fl = gw; fl < MB_FRAGS; fl += MB_SUB * OB_WAVES) {
         const uint64_t f = fb + fl;
         if (f >= a.n || a.res[f].call == 0) continue;
         const MRec r = load_mrec(a, f, m, false);
         if (r.len == 0 || r.slen == 0 || r.h < h0 || r.h + r.len > h0 + L) continue;
-        const uint64_t o = base + (r.h - h0) + r.hlen + 1, end = o + r.slen;
-        for (uint64_t D = (o & ~3ull) + 4ull * lane; D < end; D += 256) {
-            if (D >= o && D + 4 <= end) {
-                *reinterpret_cast<uint32_t *>(out + D) = NNNN;
-            } else {  // the sequence's first or last dword: the header's or the separator's bytes stay
-                for (uint64_t x = D; x < D + 4; x++)
-                    if (x >= o && x < end) out[x] = 'N';
-            }
-        }
+        // (the sequence's first or last dword: the header's or the separator's bytes stay)
+        wave_write(
+            out, base + (r.h - h0) + r.hlen + 1, r.slen, lane, [](uint64_t) { return (uint8_t)'N'; },
+            [](uint64_t, uint32_t *v) {
+                *v = NNNN;
+                return true;
+            });
     }
 }
 
@@ -306,10 +244,10 @@ uint64_t mask_blocks(uint64_t n) { return (n + MB_FRAGS - 1) / MB_FRAGS; }
 hipError_t launch_mask(const MaskArgs &a, hipStream_t stream) {
     if (a.n == 0) return hipMemsetAsync(a.total, 0, 4 * sizeof(uint64_t), stream);
     const dim3 grid((unsigned)a.nblk, (unsigned)a.mates), sub((unsigned)(a.nblk * MB_SUB), (unsigned)a.mates);
-    hipLaunchKernelGGL(k_mask_sizes, grid, dim3(MB_THREADS), 0, stream, a);
-    hipLaunchKernelGGL(k_mask_scan, dim3((unsigned)a.mates), dim3(MB_THREADS), 0, stream, a);
-    hipLaunchKernelGGL(k_mask_copy, sub, dim3(MB_THREADS), 0, stream, a);
-    hipLaunchKernelGGL(k_mask_fill, sub, dim3(MB_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(k_mask_sizes, grid, dim3(OB_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(k_mask_scan, dim3((unsigned)a.mates), dim3(OB_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(k_mask_copy, sub, dim3(OB_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(k_mask_fill, sub, dim3(OB_THREADS), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -325,6 +325,19 @@ struct Batch {
     int dev_index = 0;  // index of the slot's device among the run's engines
 };
 
+// One builder's side of a slot: the texts (one a mate, or one a list) that nh_split / nh_mask / nh_calls.hip make in HBM behind
+// the classifier, the builder's scratch, its totals as they come back with the results (in the order its kernel writes them:
+// *Args::total), and the page-locked copies the writer makes where the consumer cannot take the HBM range.
+struct BuiltOut {
+    void *d_blk = nullptr;  // block sums / offsets, then the totals (d_total), then what else the builder keeps (*Args)
+    size_t cap_blk = 0;     // in 8-byte words
+    char *d_out[2] = {nullptr, nullptr}, *h_out[2] = {nullptr, nullptr};
+    size_t cap_out[2] = {0, 0}, cap_host[2] = {0, 0};
+    uint64_t *d_total = nullptr;  // where in d_blk the batch's launch leaves its totals
+    uint64_t *h_total = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around the builder's launches (its kernel time)
+};
+
 struct Slot {  // pinned host + device buffers of one in-flight batch
     Engine *e = nullptr;
     hipStream_t stream = nullptr;
@@ -341,30 +354,17 @@ struct Slot {  // pinned host + device buffers of one in-flight batch
     size_t cap_text = 0, cap_frag = 0, cap_taxa = 0;
     uint64_t n_taxa = 0;
     bool busy = false;
-    // split runs (nh_run_split): per sequence {h, hlen, q, qlen}, the classified-out records built in HBM per mate, the
-    // builder's scratch, and the per-mate byte totals that come back with the results (host copies: only where an encoder
-    // cannot take the HBM range)
+    // the record table, per sequence {h, hlen, q, qlen}: what the builders, the quality mask and the read statistics read
     uint32_t *h_rec = nullptr;
-    void *d_rec = nullptr, *d_hblk = nullptr;
-    char *d_hout[2] = {nullptr, nullptr}, *h_hout[2] = {nullptr, nullptr};
-    size_t cap_hout[2] = {0, 0}, cap_hhost[2] = {0, 0}, cap_rec = 0, cap_hblk = 0;
-    uint64_t *h_htotal = nullptr;  // [0..1]: the classified-out totals, [2..3]: the masked totals, [4..5]: the masked FAST blocks
-    hipEvent_t hev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around the builder's launches (its kernel time)
-    // masked runs (nh_run_mask): every record of each mate built in HBM (the same record table as split runs), the builder's
-    // scratch, and the host copies where an encoder cannot take the HBM range
-    void *d_mblk = nullptr;
-    char *d_mout[2] = {nullptr, nullptr}, *h_mout[2] = {nullptr, nullptr};
-    size_t cap_mout[2] = {0, 0}, cap_mhost[2] = {0, 0}, cap_mblk = 0;
-    hipEvent_t mev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around the mask builder's launches
-    // read lists (nh_run_ex: calls table [0], human ids [1]): mate 1's id lengths beside the record table, the two texts
-    // built in HBM, the builder's scratch, the totals {bytes[2], lines[2]} that come back with the results, and the page-locked
-    // copies the writer hands to the files
+    void *d_rec = nullptr;
+    size_t cap_rec = 0;
+    // read lists: mate 1's id lengths beside the record table
     uint32_t *h_idl = nullptr;
-    void *d_idl = nullptr, *d_cblk = nullptr;
-    char *d_cout[2] = {nullptr, nullptr}, *h_cout[2] = {nullptr, nullptr};
-    size_t cap_cout[2] = {0, 0}, cap_chost[2] = {0, 0}, cap_idl = 0, cap_cblk = 0;
-    uint64_t *h_ctotal = nullptr;
-    hipEvent_t cev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around the list builder's launches
+    void *d_idl = nullptr;
+    size_t cap_idl = 0;
+    BuiltOut human;  // split runs (nh_run_split): the classified-out records per mate; totals: bytes[2]
+    BuiltOut mask;   // masked runs (nh_run_mask): every record per mate; totals: bytes[2], FAST blocks[2]
+    BuiltOut lists;  // read lists (nh_run_ex): the calls table [0] and the human ids [1]; totals: bytes[2], lines[2]
     // runs with a minimum base quality (nh_run_minq): the text-sized buffer the classifier reads instead of d_text -- the
     // sequences with 'N' where the quality is low (nh_qmask.hip; the record table tells where the qualities lie) -- allocated
     // when first needed, and the masked bases of the slot's batches, read once, at the end of the run
@@ -375,9 +375,11 @@ struct Slot {  // pinned host + device buffers of one in-flight batch
     hipEvent_t rev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around k_rstats (runs with read statistics)
 };
 
+// what a buffer that must hold `need` is allocated with: some room, so that batches a little larger do not reallocate
+static size_t grow(size_t need) { return need + need / 4 + 4096; }
+
 static int slot_reserve(Slot &s, size_t ntext, size_t nfrag, size_t ntaxa) {
     if (dev_set(s.e->device) != hipSuccess) return set_error(NH_EDEVICE, "hipSetDevice failed");
-    auto grow = [](size_t need) { return need + need / 4 + 4096; };
     if (!s.h_flag) {
         if (host_malloc((void **)&s.h_flag, 64, hipHostMallocDefault) != hipSuccess) return set_error(NH_EOOM, "cannot allocate batch buffers");
         *s.h_flag = 0;
@@ -415,98 +417,37 @@ static int slot_reserve(Slot &s, size_t ntext, size_t nfrag, size_t ntaxa) {
     return NH_OK;
 }
 
-// the split run's buffers of a slot: records of n fragments (mates per fragment), out_cap[m] bytes of classified-out text
-static int slot_reserve_human(Slot &s, size_t n, int mates, const size_t out_cap[2]) {
-    auto grow = [](size_t need) { return need + need / 4 + 4096; };
-    if (!s.h_htotal && host_malloc((void **)&s.h_htotal, 64, hipHostMallocDefault) != hipSuccess)
+// a builder's buffers of a slot: blk_words words of scratch, out_cap[i] bytes of text for each of its n_out outputs;
+// `what` names the text buffers in the error message
+static int built_reserve(BuiltOut &o, size_t blk_words, const size_t out_cap[2], int n_out, const char *what) {
+    if (!o.h_total && host_malloc((void **)&o.h_total, 64, hipHostMallocDefault) != hipSuccess)
         return set_error(NH_EOOM, "cannot allocate batch buffers");
-    if (n * mates > s.cap_rec) {
-        if (s.h_rec) (void)hipHostFree(s.h_rec);
-        if (s.d_rec) (void)hipFree(s.d_rec);
-        s.h_rec = nullptr, s.d_rec = nullptr;
-        s.cap_rec = grow(n * mates);
-        if (host_malloc((void **)&s.h_rec, s.cap_rec * 16, hipHostMallocDefault) != hipSuccess || dev_malloc(&s.d_rec, s.cap_rec * 16) != hipSuccess)
-            return set_error(NH_EOOM, "cannot allocate batch buffers (%zu records)", s.cap_rec);
+    if (blk_words > o.cap_blk) {
+        if (o.d_blk) (void)hipFree(o.d_blk);
+        o.d_blk = nullptr;
+        o.cap_blk = grow(blk_words);
+        if (dev_malloc(&o.d_blk, o.cap_blk * 8) != hipSuccess) return set_error(NH_EOOM, "cannot allocate batch buffers");
     }
-    const size_t words = 2 * human_out_blocks(n) + 2;
-    if (words > s.cap_hblk) {
-        if (s.d_hblk) (void)hipFree(s.d_hblk);
-        s.cap_hblk = grow(words);
-        if (dev_malloc(&s.d_hblk, s.cap_hblk * 8) != hipSuccess) return set_error(NH_EOOM, "cannot allocate batch buffers");
-    }
-    for (int m = 0; m < mates; m++)
-        if (out_cap[m] > s.cap_hout[m]) {
-            if (s.d_hout[m]) (void)hipFree(s.d_hout[m]);
-            s.cap_hout[m] = grow(out_cap[m]);
-            if (dev_malloc((void **)&s.d_hout[m], s.cap_hout[m]) != hipSuccess)
-                return set_error(NH_EOOM, "cannot allocate classified-out buffers (%zu bytes)", s.cap_hout[m]);
+    for (int i = 0; i < n_out; i++)
+        if (out_cap[i] > o.cap_out[i]) {
+            if (o.d_out[i]) (void)hipFree(o.d_out[i]);
+            o.d_out[i] = nullptr;
+            o.cap_out[i] = grow(out_cap[i]);
+            if (dev_malloc((void **)&o.d_out[i], o.cap_out[i]) != hipSuccess)
+                return set_error(NH_EOOM, "cannot allocate %s (%zu bytes)", what, o.cap_out[i]);
         }
     return NH_OK;
 }
 
-// the masked run's buffers of a slot: records of n fragments (mates per fragment), out_cap[m] bytes of masked text
-static int slot_reserve_mask(Slot &s, size_t n, int mates, const size_t out_cap[2]) {
-    auto grow = [](size_t need) { return need + need / 4 + 4096; };
-    if (!s.h_htotal && host_malloc((void **)&s.h_htotal, 64, hipHostMallocDefault) != hipSuccess)
-        return set_error(NH_EOOM, "cannot allocate batch buffers");
-    if (n * mates > s.cap_rec) {
-        if (s.h_rec) (void)hipHostFree(s.h_rec);
-        if (s.d_rec) (void)hipFree(s.d_rec);
-        s.h_rec = nullptr, s.d_rec = nullptr;
-        s.cap_rec = grow(n * mates);
-        if (host_malloc((void **)&s.h_rec, s.cap_rec * 16, hipHostMallocDefault) != hipSuccess || dev_malloc(&s.d_rec, s.cap_rec * 16) != hipSuccess)
-            return set_error(NH_EOOM, "cannot allocate batch buffers (%zu records)", s.cap_rec);
+// page-locked room for `n` bytes of a builder's output i on the host (the writer's copy for host encoders and files)
+static int built_reserve_host(BuiltOut &o, int i, size_t n, const char *what) {
+    if (n <= o.cap_host[i]) return NH_OK;
+    if (o.h_out[i]) (void)hipHostFree(o.h_out[i]);
+    o.cap_host[i] = grow(n);
+    if (host_malloc((void **)&o.h_out[i], o.cap_host[i], hipHostMallocDefault) != hipSuccess) {
+        o.h_out[i] = nullptr, o.cap_host[i] = 0;
+        return set_error(NH_EOOM, "cannot allocate %s (%zu bytes)", what, n);
     }
-    const size_t words = 3 * mask_blocks(n) + 4;  // (block offsets, totals and FAST counts, block flags: MaskArgs)
-    if (words > s.cap_mblk) {
-        if (s.d_mblk) (void)hipFree(s.d_mblk);
-        s.cap_mblk = grow(words);
-        if (dev_malloc(&s.d_mblk, s.cap_mblk * 8) != hipSuccess) return set_error(NH_EOOM, "cannot allocate batch buffers");
-    }
-    for (int m = 0; m < mates; m++)
-        if (out_cap[m] > s.cap_mout[m]) {
-            if (s.d_mout[m]) (void)hipFree(s.d_mout[m]);
-            s.cap_mout[m] = grow(out_cap[m]);
-            if (dev_malloc((void **)&s.d_mout[m], s.cap_mout[m]) != hipSuccess)
-                return set_error(NH_EOOM, "cannot allocate masked-out buffers (%zu bytes)", s.cap_mout[m]);
-        }
-    return NH_OK;
-}
-
-// the read lists' buffers of a slot: records and id lengths of n fragments (mates per fragment), out_cap[o] bytes of list text
-static int slot_reserve_calls(Slot &s, size_t n, int mates, const size_t out_cap[2]) {
-    auto grow = [](size_t need) { return need + need / 4 + 4096; };
-    if (!s.h_ctotal && host_malloc((void **)&s.h_ctotal, 64, hipHostMallocDefault) != hipSuccess)
-        return set_error(NH_EOOM, "cannot allocate batch buffers");
-    if (n * mates > s.cap_rec) {
-        if (s.h_rec) (void)hipHostFree(s.h_rec);
-        if (s.d_rec) (void)hipFree(s.d_rec);
-        s.h_rec = nullptr, s.d_rec = nullptr;
-        s.cap_rec = grow(n * mates);
-        if (host_malloc((void **)&s.h_rec, s.cap_rec * 16, hipHostMallocDefault) != hipSuccess || dev_malloc(&s.d_rec, s.cap_rec * 16) != hipSuccess)
-            return set_error(NH_EOOM, "cannot allocate batch buffers (%zu records)", s.cap_rec);
-    }
-    if (n > s.cap_idl) {
-        if (s.h_idl) (void)hipHostFree(s.h_idl);
-        if (s.d_idl) (void)hipFree(s.d_idl);
-        s.h_idl = nullptr, s.d_idl = nullptr;
-        s.cap_idl = grow(n);
-        if (host_malloc((void **)&s.h_idl, s.cap_idl * 4, hipHostMallocDefault) != hipSuccess || dev_malloc(&s.d_idl, s.cap_idl * 4) != hipSuccess)
-            return set_error(NH_EOOM, "cannot allocate batch buffers (%zu id lengths)", s.cap_idl);
-    }
-    const size_t words = 4 * calls_blocks(n) + 4;  // (block offsets and line counts of both outputs, totals: CallsArgs)
-    if (words > s.cap_cblk) {
-        if (s.d_cblk) (void)hipFree(s.d_cblk);
-        s.cap_cblk = grow(words);
-        if (dev_malloc(&s.d_cblk, s.cap_cblk * 8) != hipSuccess) return set_error(NH_EOOM, "cannot allocate batch buffers");
-    }
-    for (int o = 0; o < 2; o++)
-        if (out_cap[o] > s.cap_cout[o]) {
-            if (s.d_cout[o]) (void)hipFree(s.d_cout[o]);
-            s.cap_cout[o] = grow(out_cap[o]);
-            if (dev_malloc((void **)&s.d_cout[o], s.cap_cout[o]) != hipSuccess)
-                return set_error(NH_EOOM, "cannot allocate read-list buffers (%zu bytes)", s.cap_cout[o]);
-        }
     return NH_OK;
 }
 
@@ -516,15 +457,26 @@ static int slot_reserve_rec(Slot &s, size_t nrec) {
     if (s.h_rec) (void)hipHostFree(s.h_rec);
     if (s.d_rec) (void)hipFree(s.d_rec);
     s.h_rec = nullptr, s.d_rec = nullptr;
-    s.cap_rec = nrec + nrec / 4 + 4096;
+    s.cap_rec = grow(nrec);
     if (host_malloc((void **)&s.h_rec, s.cap_rec * 16, hipHostMallocDefault) != hipSuccess || dev_malloc(&s.d_rec, s.cap_rec * 16) != hipSuccess)
         return set_error(NH_EOOM, "cannot allocate batch buffers (%zu records)", s.cap_rec);
     return NH_OK;
 }
 
+// mate 1's id lengths of n fragments of a slot (read lists)
+static int slot_reserve_idl(Slot &s, size_t n) {
+    if (n <= s.cap_idl) return NH_OK;
+    if (s.h_idl) (void)hipHostFree(s.h_idl);
+    if (s.d_idl) (void)hipFree(s.d_idl);
+    s.h_idl = nullptr, s.d_idl = nullptr;
+    s.cap_idl = grow(n);
+    if (host_malloc((void **)&s.h_idl, s.cap_idl * 4, hipHostMallocDefault) != hipSuccess || dev_malloc(&s.d_idl, s.cap_idl * 4) != hipSuccess)
+        return set_error(NH_EOOM, "cannot allocate batch buffers (%zu id lengths)", s.cap_idl);
+    return NH_OK;
+}
+
 // the quality mask's buffers of a slot: the record table of nrec sequences, ntext bytes of masked text, the counter
 static int slot_reserve_qmask(Slot &s, size_t ntext, size_t nrec) {
-    auto grow = [](size_t need) { return need + need / 4 + 4096; };
     const int rrc = slot_reserve_rec(s, nrec);
     if (rrc) return rrc;
     if (ntext + 64 > s.cap_qtext) {
@@ -541,56 +493,24 @@ static int slot_reserve_qmask(Slot &s, size_t ntext, size_t nrec) {
     return NH_OK;
 }
 
-// page-locked room for `n` bytes of read list o on the host (the writer's copy for the file)
-static int slot_reserve_calls_host(Slot &s, int o, size_t n) {
-    if (n <= s.cap_chost[o]) return NH_OK;
-    if (s.h_cout[o]) (void)hipHostFree(s.h_cout[o]);
-    s.cap_chost[o] = n + n / 4 + 4096;
-    if (host_malloc((void **)&s.h_cout[o], s.cap_chost[o], hipHostMallocDefault) != hipSuccess) {
-        s.h_cout[o] = nullptr, s.cap_chost[o] = 0;
-        return set_error(NH_EOOM, "cannot allocate read-list buffers (%zu bytes)", n);
-    }
-    return NH_OK;
-}
-
-// page-locked room for `n` bytes of mate m's masked text on the host (the writer's copy for host encoders)
-static int slot_reserve_mask_host(Slot &s, int m, size_t n) {
-    if (n <= s.cap_mhost[m]) return NH_OK;
-    if (s.h_mout[m]) (void)hipHostFree(s.h_mout[m]);
-    s.cap_mhost[m] = n + n / 4 + 4096;
-    if (host_malloc((void **)&s.h_mout[m], s.cap_mhost[m], hipHostMallocDefault) != hipSuccess) {
-        s.h_mout[m] = nullptr, s.cap_mhost[m] = 0;
-        return set_error(NH_EOOM, "cannot allocate masked-out buffers (%zu bytes)", n);
-    }
-    return NH_OK;
-}
-
-// page-locked room for `n` bytes of mate m's classified-out text on the host (the writer's copy for host encoders)
-static int slot_reserve_human_host(Slot &s, int m, size_t n) {
-    if (n <= s.cap_hhost[m]) return NH_OK;
-    if (s.h_hout[m]) (void)hipHostFree(s.h_hout[m]);
-    s.cap_hhost[m] = n + n / 4 + 4096;
-    if (host_malloc((void **)&s.h_hout[m], s.cap_hhost[m], hipHostMallocDefault) != hipSuccess) {
-        s.h_hout[m] = nullptr, s.cap_hhost[m] = 0;
-        return set_error(NH_EOOM, "cannot allocate classified-out buffers (%zu bytes)", n);
-    }
-    return NH_OK;
-}
-
 static void slot_free(Slot &s) {
     if (!s.e) return;
     (void)dev_set(s.e->device);
-    for (void *p : {(void *)s.h_rec, (void *)s.h_hout[0], (void *)s.h_hout[1], (void *)s.h_htotal, (void *)s.h_mout[0], (void *)s.h_mout[1]})
+    for (BuiltOut *o : {&s.human, &s.mask, &s.lists}) {
+        for (void *p : {(void *)o->h_out[0], (void *)o->h_out[1], (void *)o->h_total})
+            if (p) (void)hipHostFree(p);
+        for (void *p : {o->d_blk, (void *)o->d_out[0], (void *)o->d_out[1]})
+            if (p) (void)hipFree(p);
+        for (hipEvent_t ev : o->ev)
+            if (ev) (void)hipEventDestroy(ev);
+    }
+    for (void *p : {(void *)s.h_rec, (void *)s.h_idl})
         if (p) (void)hipHostFree(p);
-    for (void *p : {s.d_rec, s.d_hblk, (void *)s.d_hout[0], (void *)s.d_hout[1], s.d_mblk, (void *)s.d_mout[0], (void *)s.d_mout[1]})
-        if (p) (void)hipFree(p);
-    for (void *p : {(void *)s.h_idl, (void *)s.h_cout[0], (void *)s.h_cout[1], (void *)s.h_ctotal})
-        if (p) (void)hipHostFree(p);
-    for (void *p : {s.d_idl, s.d_cblk, (void *)s.d_cout[0], (void *)s.d_cout[1]})
+    for (void *p : {s.d_rec, s.d_idl})
         if (p) (void)hipFree(p);
     for (void *p : {s.d_qtext, (void *)s.d_qcnt})
         if (p) (void)hipFree(p);
-    for (hipEvent_t ev : {s.hev[0], s.hev[1], s.mev[0], s.mev[1], s.cev[0], s.cev[1], s.qev[0], s.qev[1], s.rev[0], s.rev[1]})
+    for (hipEvent_t ev : {s.qev[0], s.qev[1], s.rev[0], s.rev[1]})
         if (ev) (void)hipEventDestroy(ev);
     for (void *p : {(void *)s.h_off, (void *)s.h_len, (void *)s.h_res, (void *)s.h_taxa, (void *)s.h_taxa_off, (void *)s.h_flag})
         if (p) (void)hipHostFree(p);
@@ -760,6 +680,24 @@ private:
     std::thread filler_;
     std::atomic<bool> stop_{false};
 };
+
+// NOHUMAN_TRACE: the time between a slot's pair of events is added to *sum (the slot's stream was synchronised: both have
+// completed; without the trace there are no events)
+static void add_event_ms(const hipEvent_t ev[2], double *sum) {
+    float ms = 0;
+    if (ev[1] && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) *sum += ms;
+}
+
+// The span of built text the writer hands on, output i's `tot` bytes: in HBM where the consumer takes the range, else copied
+// to the slot's page-locked buffer and counted as fetched.  `what` / `item` name the buffers / the text in the error messages.
+static char *built_span(BuiltOut &o, int i, size_t tot, bool in_hbm, RunState &rs, int *wrc, const char *what, const char *item) {
+    if (in_hbm) return o.d_out[i];
+    *wrc = built_reserve_host(o, i, tot, what);
+    if (!*wrc && hipMemcpy(o.h_out[i], o.d_out[i], tot, hipMemcpyDeviceToHost) != hipSuccess)
+        *wrc = set_error(NH_EDEVICE, "fetching a batch's %s from the device failed", item);
+    rs.text_fetched += tot;
+    return o.h_out[i];
+}
 
 struct StageClock {  // NOHUMAN_TRACE=1: where the wall time of a run goes, per thread
     std::atomic<uint64_t> ns[12];
@@ -1311,11 +1249,11 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
         if (dev_set(slots[i].e->device) != hipSuccess ||
             hipStreamCreateWithFlags(&slots[i].stream, hipStreamNonBlocking) != hipSuccess ||
             (split && getenv("NOHUMAN_TRACE") &&
-             (hipEventCreate(&slots[i].hev[0]) != hipSuccess || hipEventCreate(&slots[i].hev[1]) != hipSuccess)) ||
+             (hipEventCreate(&slots[i].human.ev[0]) != hipSuccess || hipEventCreate(&slots[i].human.ev[1]) != hipSuccess)) ||
             (mask && getenv("NOHUMAN_TRACE") &&
-             (hipEventCreate(&slots[i].mev[0]) != hipSuccess || hipEventCreate(&slots[i].mev[1]) != hipSuccess)) ||
+             (hipEventCreate(&slots[i].mask.ev[0]) != hipSuccess || hipEventCreate(&slots[i].mask.ev[1]) != hipSuccess)) ||
             (lists && getenv("NOHUMAN_TRACE") &&
-             (hipEventCreate(&slots[i].cev[0]) != hipSuccess || hipEventCreate(&slots[i].cev[1]) != hipSuccess)) ||
+             (hipEventCreate(&slots[i].lists.ev[0]) != hipSuccess || hipEventCreate(&slots[i].lists.ev[1]) != hipSuccess)) ||
             (qm && getenv("NOHUMAN_TRACE") &&
              (hipEventCreate(&slots[i].qev[0]) != hipSuccess || hipEventCreate(&slots[i].qev[1]) != hipSuccess)) ||
             (rst && getenv("NOHUMAN_TRACE") &&
@@ -1473,13 +1411,13 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 if (mask_in_hbm)
                     for (int m = 0; m < mates; m++) {
                         Spans &ms = m ? j->s2 : j->s1;
-                        if (!ms.iov.empty()) (m ? o2 : o1).enc->map_device(ms.iov[0].iov_base, ms.iov[0].iov_len, s.d_mout[m], s.e->device, false);
+                        if (!ms.iov.empty()) (m ? o2 : o1).enc->map_device(ms.iov[0].iov_base, ms.iov[0].iov_len, s.mask.d_out[m], s.e->device, false);
                     }
                 // the classified records that only exist in HBM: their span's address is the device buffer's, never read on the host
                 if (human_in_hbm)
                     for (int m = 0; m < mates; m++) {
                         Spans &hs = m ? j->hs2 : j->hs1;
-                        if (!hs.iov.empty()) (m ? h2 : h1).enc->map_device(hs.iov[0].iov_base, hs.iov[0].iov_len, s.d_hout[m], s.e->device, false);
+                        if (!hs.iov.empty()) (m ? h2 : h1).enc->map_device(hs.iov[0].iov_base, hs.iov[0].iov_len, s.human.d_out[m], s.e->device, false);
                     }
                 if (rs.paired) {
                     std::lock_guard<std::mutex> lk(w2_mu);
@@ -1557,66 +1495,36 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 if (!wrc) {
                     format_batch(&rs, b, s, o1, o2, ok, !mask);
                     // a masked run's records: the text the builder made, one span a mate -- in HBM, or copied here
-                    if (mask && s.mev[1]) {
-                        float ms = 0;
-                        if (hipEventElapsedTime(&ms, s.mev[0], s.mev[1]) == hipSuccess) rs.mask_kernel_ms += ms;
-                    }
+                    add_event_ms(s.mask.ev, &rs.mask_kernel_ms);
                     for (int m = 0; mask && m < mates && !wrc; m++) {
-                        const size_t tot = (size_t)s.h_htotal[2 + m];
+                        const size_t tot = (size_t)s.mask.h_total[m];
                         rs.mask_bytes += tot;
                         if (!tot) continue;
-                        char *at = s.d_mout[m];
-                        if (!mask_in_hbm) {
-                            wrc = slot_reserve_mask_host(s, m, tot);
-                            if (!wrc && hipMemcpy(s.h_mout[m], s.d_mout[m], tot, hipMemcpyDeviceToHost) != hipSuccess)
-                                wrc = set_error(NH_EDEVICE, "fetching a batch's masked records from the device failed");
-                            at = s.h_mout[m];
-                            rs.text_fetched += tot;
-                        }
+                        char *at = built_span(s.mask, m, tot, mask_in_hbm, rs, &wrc, "masked-out buffers", "masked records");
                         (m ? o2 : o1).add_raw(at, tot);
                     }
                     if (mask) {
                         rs.mask_records += b.n * (size_t)mates;
                         rs.mask_nblk += mask_blocks(b.n) * (uint64_t)mates;
-                        for (int m = 0; m < mates; m++) rs.mask_fast += s.h_htotal[4 + m];
+                        for (int m = 0; m < mates; m++) rs.mask_fast += s.mask.h_total[2 + m];
                         for (size_t i = 0; i < b.n; i++) rs.mask_masked += (s.h_res[i].call != 0) * (uint64_t)mates;
                     }
                     // a split run's classified records: the text the builder made, one span a mate -- in HBM, or copied here
-                    if (split && s.hev[1]) {  // (the stream was synchronised above: both events have completed)
-                        float ms = 0;
-                        if (hipEventElapsedTime(&ms, s.hev[0], s.hev[1]) == hipSuccess) rs.human_kernel_ms += ms;
-                    }
+                    add_event_ms(s.human.ev, &rs.human_kernel_ms);
                     for (int m = 0; split && m < mates && !wrc; m++) {
-                        const size_t tot = (size_t)s.h_htotal[m];
+                        const size_t tot = (size_t)s.human.h_total[m];
                         rs.human_bytes += tot;
                         if (!tot) continue;
-                        char *at = s.d_hout[m];
-                        if (!human_in_hbm) {
-                            wrc = slot_reserve_human_host(s, m, tot);
-                            if (!wrc && hipMemcpy(s.h_hout[m], s.d_hout[m], tot, hipMemcpyDeviceToHost) != hipSuccess)
-                                wrc = set_error(NH_EDEVICE, "fetching a batch's classified records from the device failed");
-                            at = s.h_hout[m];
-                            rs.text_fetched += tot;
-                        }
+                        char *at = built_span(s.human, m, tot, human_in_hbm, rs, &wrc, "classified-out buffers", "classified records");
                         Spans &hs = m ? j->hs2 : j->hs1;
                         hs.iov.push_back({(void *)at, tot});
                         hs.is_scratch.push_back(0);
                     }
                     if (split)
                         for (size_t i = 0; i < b.n; i++) rs.human_records += s.h_res[i].call != 0;
-                    // the read lists: exactly the built bytes, copied to the slot's page-locked memory, one span a file
-                    if (lists && s.cev[1]) {
-                        float ms = 0;
-                        if (hipEventElapsedTime(&ms, s.cev[0], s.cev[1]) == hipSuccess) rs.list_kernel_ms += ms;
-                    }
-                    if (qm && s.qev[1]) {
-                        float ms = 0;
-                        if (hipEventElapsedTime(&ms, s.qev[0], s.qev[1]) == hipSuccess) rs.qmask_kernel_ms += ms;
-                    }
-                    if (rst && s.rev[1]) {
-                        float ms = 0;
-                        if (hipEventElapsedTime(&ms, s.rev[0], s.rev[1]) == hipSuccess) rs.rstats_kernel_ms += ms;
-                    }
+                    add_event_ms(s.lists.ev, &rs.list_kernel_ms);
+                    add_event_ms(s.qev, &rs.qmask_kernel_ms);
+                    add_event_ms(s.rev, &rs.rstats_kernel_ms);
                     // read statistics: every length of the batch, by the class of its fragment and its mate
                     for (size_t i = 0; rst && i < b.n; i++) {
                         const int c = s.h_res[i].call != 0;
@@ -1631,17 +1539,15 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                             h[L]++;
                         }
                     }
+                    // the read lists: exactly the built bytes, copied to the slot's page-locked memory, one span a file
                     for (int o = 0; lists && o < 2 && !wrc; o++) {
-                        const size_t tot = (size_t)s.h_ctotal[o];
+                        const size_t tot = (size_t)s.lists.h_total[o];
                         rs.list_bytes[o] += tot;
-                        rs.list_lines[o] += s.h_ctotal[2 + o];
+                        rs.list_lines[o] += s.lists.h_total[2 + o];
                         if (!tot) continue;
-                        wrc = slot_reserve_calls_host(s, o, tot);
-                        if (!wrc && hipMemcpy(s.h_cout[o], s.d_cout[o], tot, hipMemcpyDeviceToHost) != hipSuccess)
-                            wrc = set_error(NH_EDEVICE, "fetching a batch's read list from the device failed");
-                        rs.text_fetched += tot;
+                        char *at = built_span(s.lists, o, tot, false, rs, &wrc, "read-list buffers", "read list");
                         Spans &ls = o ? j->si : j->sc;
-                        ls.iov.push_back({(void *)s.h_cout[o], tot});
+                        ls.iov.push_back({(void *)at, tot});
                         ls.is_scratch.push_back(0);
                     }
                     clk.ns[ST_WFORMAT] += StageClock::now() - c2;
@@ -1760,11 +1666,14 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
             rc = slot_reserve(s, ntext, b.n, ntaxa + 1);
             if (!rc && split) {  // a mate's classified-out text: its records less what normalisation drops, plus 36 bytes a suffix
                 const size_t out_cap[2] = {len1 + b.n * 36 + 64, len2 + b.n * 36 + 64};
-                rc = slot_reserve_human(s, b.n, mates, out_cap);
+                rc = slot_reserve_rec(s, b.n * (size_t)mates);
+                if (!rc) rc = built_reserve(s.human, 2 * human_out_blocks(b.n) + 2, out_cap, mates, "classified-out buffers");
             }
             if (!rc && mask) {  // a mate's masked text: its records less what normalisation drops, plus a final newline each
                 const size_t out_cap[2] = {len1 + b.n + 64, len2 + b.n + 64};
-                rc = slot_reserve_mask(s, b.n, mates, out_cap);
+                rc = slot_reserve_rec(s, b.n * (size_t)mates);
+                // (the scratch: block offsets, totals and FAST counts, block flags: MaskArgs)
+                if (!rc) rc = built_reserve(s.mask, 3 * mask_blocks(b.n) + 4, out_cap, mates, "masked-out buffers");
             }
             if (!rc && lists) {
                 // a table line: "C\t", the id, then at most 1 + 20 + 1 + 21 + 1 + 3 * 11 bytes of numbers, separators and
@@ -1772,7 +1681,10 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 uint64_t idsum = 0;
                 for (size_t i = 0; i < b.n; i++) idsum += b.h1->recs[b.off1 + i].idlen;
                 const size_t out_cap[2] = {calls ? (size_t)idsum + b.n * 79 + 64 : 0, ids ? (size_t)idsum + b.n + 64 : 0};
-                rc = slot_reserve_calls(s, b.n, mates, out_cap);
+                rc = slot_reserve_rec(s, b.n * (size_t)mates);
+                if (!rc) rc = slot_reserve_idl(s, b.n);
+                // (the scratch: block offsets and line counts of both outputs, totals: CallsArgs)
+                if (!rc) rc = built_reserve(s.lists, 4 * calls_blocks(b.n) + 4, out_cap, 2, "read-list buffers");
             }
             if (!rc && qm) rc = slot_reserve_qmask(s, ntext, b.n * (size_t)mates);
             if (!rc && rst) rc = slot_reserve_rec(s, b.n * (size_t)mates);
@@ -1907,7 +1819,6 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 if (s.rev[1] && he == hipSuccess) he = hipEventRecord(s.rev[1], s.stream);
                 if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("read statistics: ") + hipGetErrorString(he));
             }
-            uint64_t *d_ctotal = nullptr;
             if (!rs.failed() && lists) {  // the calls table and the human ids, built behind the classifier on the same stream
                 CallsArgs ca{};
                 ca.text = (const char *)s.d_text;
@@ -1923,16 +1834,15 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 ca.mates = mates;
                 ca.want[0] = calls != nullptr;
                 ca.want[1] = ids != nullptr;
-                for (int o = 0; o < 2; o++) ca.out[o] = s.d_cout[o], ca.cap[o] = s.cap_cout[o];
-                ca.blk = (uint64_t *)s.d_cblk;
-                ca.total = d_ctotal = (uint64_t *)s.d_cblk + 4 * ca.nblk;
+                for (int o = 0; o < 2; o++) ca.out[o] = s.lists.d_out[o], ca.cap[o] = s.lists.cap_out[o];
+                ca.blk = (uint64_t *)s.lists.d_blk;
+                ca.total = s.lists.d_total = ca.blk + 4 * ca.nblk;
                 ca.error = s.e->d_error + LAUNCH_SLOTS;
-                if (s.cev[0]) (void)hipEventRecord(s.cev[0], s.stream);
+                if (s.lists.ev[0]) (void)hipEventRecord(s.lists.ev[0], s.stream);
                 he = launch_calls(ca, s.stream);
-                if (s.cev[1] && he == hipSuccess) he = hipEventRecord(s.cev[1], s.stream);
+                if (s.lists.ev[1] && he == hipSuccess) he = hipEventRecord(s.lists.ev[1], s.stream);
                 if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("read-list builder: ") + hipGetErrorString(he));
             }
-            uint64_t *d_htotal = nullptr;
             if (!rs.failed() && split) {  // the classified records of both mates, built behind the classifier on the same stream
                 HumanOutArgs ha{};
                 ha.text = (const char *)s.d_text;
@@ -1948,16 +1858,15 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 ha.mates = mates;
                 ha.fastq[0] = b.h1->format == FMT_FASTQ;
                 ha.fastq[1] = rs.paired && b.h2->format == FMT_FASTQ;
-                for (int m = 0; m < mates; m++) ha.out[m] = s.d_hout[m], ha.cap[m] = s.cap_hout[m];
-                ha.blk = (uint64_t *)s.d_hblk;
-                ha.total = d_htotal = (uint64_t *)s.d_hblk + 2 * ha.nblk;
+                for (int m = 0; m < mates; m++) ha.out[m] = s.human.d_out[m], ha.cap[m] = s.human.cap_out[m];
+                ha.blk = (uint64_t *)s.human.d_blk;
+                ha.total = s.human.d_total = ha.blk + 2 * ha.nblk;
                 ha.error = s.e->d_error + LAUNCH_SLOTS;
-                if (s.hev[0]) (void)hipEventRecord(s.hev[0], s.stream);
+                if (s.human.ev[0]) (void)hipEventRecord(s.human.ev[0], s.stream);
                 he = launch_human_out(ha, s.stream);
-                if (s.hev[1] && he == hipSuccess) he = hipEventRecord(s.hev[1], s.stream);
+                if (s.human.ev[1] && he == hipSuccess) he = hipEventRecord(s.human.ev[1], s.stream);
                 if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("classified-out builder: ") + hipGetErrorString(he));
             }
-            uint64_t *d_mtotal = nullptr;
             if (!rs.failed() && mask) {  // every record of both mates, masked, built behind the classifier on the same stream
                 MaskArgs ma{};
                 ma.text = (const char *)s.d_text;
@@ -1971,14 +1880,14 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 ma.mates = mates;
                 ma.fastq[0] = b.h1->format == FMT_FASTQ;
                 ma.fastq[1] = rs.paired && b.h2->format == FMT_FASTQ;
-                for (int m = 0; m < mates; m++) ma.out[m] = s.d_mout[m], ma.cap[m] = s.cap_mout[m];
-                ma.blk = (uint64_t *)s.d_mblk;
-                ma.total = d_mtotal = (uint64_t *)s.d_mblk + 2 * ma.nblk;
-                ma.fast = (uint32_t *)((uint64_t *)s.d_mblk + 2 * ma.nblk + 4);
+                for (int m = 0; m < mates; m++) ma.out[m] = s.mask.d_out[m], ma.cap[m] = s.mask.cap_out[m];
+                ma.blk = (uint64_t *)s.mask.d_blk;
+                ma.total = s.mask.d_total = ma.blk + 2 * ma.nblk;
+                ma.fast = (uint32_t *)(ma.total + 4);
                 ma.error = s.e->d_error + LAUNCH_SLOTS;
-                if (s.mev[0]) (void)hipEventRecord(s.mev[0], s.stream);
+                if (s.mask.ev[0]) (void)hipEventRecord(s.mask.ev[0], s.stream);
                 he = launch_mask(ma, s.stream);
-                if (s.mev[1] && he == hipSuccess) he = hipEventRecord(s.mev[1], s.stream);
+                if (s.mask.ev[1] && he == hipSuccess) he = hipEventRecord(s.mask.ev[1], s.stream);
                 if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("mask builder: ") + hipGetErrorString(he));
             }
             if (!rs.failed()) {
@@ -1988,11 +1897,11 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 if (he == hipSuccess && rs.want_k && toff)
                     he = hipMemcpyAsync(s.h_taxa, s.d_taxa, toff * 4, hipMemcpyDeviceToHost, s.stream);
                 if (he == hipSuccess && split)
-                    he = hipMemcpyAsync(s.h_htotal, d_htotal, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
+                    he = hipMemcpyAsync(s.human.h_total, s.human.d_total, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
                 if (he == hipSuccess && mask)
-                    he = hipMemcpyAsync(s.h_htotal + 2, d_mtotal, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
+                    he = hipMemcpyAsync(s.mask.h_total, s.mask.d_total, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
                 if (he == hipSuccess && lists)
-                    he = hipMemcpyAsync(s.h_ctotal, d_ctotal, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
+                    he = hipMemcpyAsync(s.lists.h_total, s.lists.d_total, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
                 if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("D2H: ") + hipGetErrorString(he));
             }
             batch_no++;

@@ -7,29 +7,26 @@
 // The record is made from its parsed fields (header without trailing blanks, the sequence joined in place), never from
 // its raw text, so CRLF and "+id" records come out normalised by the same rule as on the host.
 //
-// Three launches on the batch's stream, both mates in each (grid.y = mate):
+// Three launches on the batch's stream, both mates in each (grid.y = mate); the scheme and its parts are nh_outbuild.h's:
 //   k_hout_sizes  per block of HB_FRAGS fragments: the sum of their output lengths
-//   k_hout_scan   per mate, one workgroup: exclusive scan of the block sums in place -> block offsets; the mate's total
-//   k_hout_copy   per block: the fragments' lengths again, an exclusive scan inside the block, then one wave per record
-//                 writes it: aligned dwords of the output, a dword that lies in one text field is two aligned loads and
-//                 v_alignbyte; the dwords at field boundaries are put together byte by byte, and the first and last
-//                 partial dwords of a record (shared with its neighbours) are written with byte stores.
-// The kernel boundaries are the only hand-off between the launches.  Every load stays inside the dwords that hold
-// bytes of [0, ntext); every store inside [0, cap) of its mate's buffer.  A record whose fields lie outside the text,
-// a call outside the taxon table or a total above the buffer sets bit 4 of the engine's error word and writes nothing.
+//   k_hout_scan   per mate, one workgroup: block sums -> block offsets; the mate's total
+//   k_hout_copy   per block: the records' offsets, then one wave per record writes it; the fields that are copied as
+//                 dwords are the header, the sequence and the qualities
+// Every load stays inside the dwords that hold bytes of [0, ntext); every store inside [0, cap) of its mate's buffer.
+// A record whose fields lie outside the text, a call outside the taxon table or a total above the buffer sets bit 4 of
+// the engine's error word and writes nothing.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "nh_internal.h"
+#include "nh_outbuild.h"
 
 namespace nh {
 
 namespace {
 
-constexpr int HB_THREADS = 256;
 constexpr int HB_PER_THREAD = 4;
-constexpr int HB_FRAGS = HB_THREADS * HB_PER_THREAD;  // fragments of one block
-constexpr int HB_WAVES = HB_THREADS / 64;
+constexpr int HB_FRAGS = OB_THREADS * HB_PER_THREAD;  // fragments of one block
 constexpr int ERR_HUMAN_OUT = 4;
 constexpr uint32_t SFX_FIXED = 14;  // " kraken:taxid|"
 
@@ -42,15 +39,6 @@ struct Rec {  // one record's fields, absolute offsets into the batch's text
     uint32_t ndig;  // decimal digits of ext
     uint64_t len;   // bytes of its output, 0: not written
 };
-
-__device__ inline uint32_t decimal_digits(uint64_t v) {
-    uint32_t n = 1;
-    while (v >= 10) {
-        v /= 10;
-        n++;
-    }
-    return n;
-}
 
 // the record of fragment f, mate m; len 0 for an unclassified fragment or a record that fails its bounds (error set)
 __device__ inline Rec load_rec(const HumanOutArgs &a, uint64_t f, int m, bool report) {
@@ -78,27 +66,8 @@ __device__ inline Rec load_rec(const HumanOutArgs &a, uint64_t f, int m, bool re
     return r;
 }
 
-// exclusive scan over the block's threads (HB_THREADS) of one value each; *total: the block's sum
-__device__ inline uint64_t block_exclusive_scan(uint64_t v, uint64_t *wsum, uint64_t *total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint64_t incl = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t t = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += t;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    uint64_t before = 0, all = 0;
-    for (int w = 0; w < HB_WAVES; w++) {
-        before += w < wave ? wsum[w] : 0;
-        all += wsum[w];
-    }
-    *total = all;
-    return before + incl - v;
-}
-
-__global__ void __launch_bounds__(HB_THREADS) k_hout_sizes(HumanOutArgs a) {
-    __shared__ uint64_t wsum[HB_WAVES];
+__global__ void __launch_bounds__(OB_THREADS) k_hout_sizes(HumanOutArgs a) {
+    __shared__ uint64_t wsum[OB_WAVES];
     const int m = blockIdx.y;
     const uint64_t f0 = (uint64_t)blockIdx.x * HB_FRAGS + (uint64_t)threadIdx.x * HB_PER_THREAD;
     uint64_t mine = 0;
@@ -109,27 +78,11 @@ __global__ void __launch_bounds__(HB_THREADS) k_hout_sizes(HumanOutArgs a) {
 }
 
 // one workgroup per mate: block sums -> exclusive block offsets (in place), the mate's total
-__global__ void __launch_bounds__(HB_THREADS) k_hout_scan(HumanOutArgs a) {
-    __shared__ uint64_t wsum[HB_WAVES];
+__global__ void __launch_bounds__(OB_THREADS) k_hout_scan(HumanOutArgs a) {
+    __shared__ uint64_t wsum[OB_WAVES];
     const int m = blockIdx.x;
-    uint64_t *b = a.blk + (uint64_t)m * a.nblk;
-    uint64_t carry = 0;
-    for (uint64_t c = 0; c < a.nblk; c += HB_THREADS) {
-        const uint64_t i = c + threadIdx.x;
-        const uint64_t v = i < a.nblk ? b[i] : 0;
-        uint64_t sum;
-        const uint64_t ex = block_exclusive_scan(v, wsum, &sum);
-        if (i < a.nblk) b[i] = carry + ex;
-        carry += sum;
-        __syncthreads();  // (wsum is written again by the next chunk)
-    }
-    if (threadIdx.x == 0) {
-        if (carry > a.cap[m]) {
-            atomicOr(a.error, ERR_HUMAN_OUT);
-            carry = 0;
-        }
-        a.total[m] = carry;
-    }
+    const uint64_t total = scan_block_sums(a.blk + (uint64_t)m * a.nblk, a.nblk, wsum);
+    if (threadIdx.x == 0) a.total[m] = total_fits(total, a.cap[m], a.error, ERR_HUMAN_OUT) ? total : 0;
 }
 
 // byte p of the record's output (0 <= p < r.len)
@@ -155,42 +108,20 @@ __device__ inline uint8_t rec_byte(const HumanOutArgs &a, const Rec &r, bool fas
     return '\n';
 }
 
-// the 4 text bytes at src (src + 3 < ntext): two aligned loads, the second only where the bytes reach into it
-__device__ inline uint32_t text_dword(const char *text, uint64_t src) {
-    const uint32_t *w = reinterpret_cast<const uint32_t *>(text + (src & ~3ull));
-    const uint32_t sh = (uint32_t)(src & 3);
-    const uint32_t lo = w[0];
-    if (sh == 0) return lo;
-    return __builtin_amdgcn_alignbyte(w[1], lo, sh);
-}
-
-__global__ void __launch_bounds__(HB_THREADS) k_hout_copy(HumanOutArgs a) {
-    __shared__ uint64_t wsum[HB_WAVES];
+__global__ void __launch_bounds__(OB_THREADS) k_hout_copy(HumanOutArgs a) {
+    __shared__ uint64_t wsum[OB_WAVES];
     __shared__ uint64_t s_off[HB_FRAGS];
     const int m = blockIdx.y;
     const bool fastq = a.fastq[m] != 0;
     const uint64_t fb = (uint64_t)blockIdx.x * HB_FRAGS;
-    {
-        uint64_t len[HB_PER_THREAD], mine = 0;
-        for (int j = 0; j < HB_PER_THREAD; j++) {
-            len[j] = load_rec(a, fb + threadIdx.x * HB_PER_THREAD + j, m, false).len;
-            mine += len[j];
-        }
-        uint64_t total;
-        uint64_t o = block_exclusive_scan(mine, wsum, &total);
-        for (int j = 0; j < HB_PER_THREAD; j++) {
-            s_off[threadIdx.x * HB_PER_THREAD + j] = o;
-            o += len[j];
-        }
-    }
-    __syncthreads();
+    block_offsets<HB_PER_THREAD>(s_off, wsum, [&](uint32_t fl) { return load_rec(a, fb + fl, m, false).len; });
     char *out = a.out[m];
     const uint64_t cap = a.cap[m];
     const uint64_t base = a.blk[(uint64_t)m * a.nblk + blockIdx.x];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // wave w writes the records of fragments [w * 256, w * 256 + 256) of the block, one after another
-    for (int k = 0; k < HB_FRAGS / HB_WAVES; k++) {
-        const int fl = wave * (HB_FRAGS / HB_WAVES) + k;
+    for (int k = 0; k < HB_FRAGS / OB_WAVES; k++) {
+        const int fl = wave * (HB_FRAGS / OB_WAVES) + k;
         const Rec r = load_rec(a, fb + fl, m, false);
         if (r.len == 0) continue;
         const uint64_t o = base + s_off[fl];
@@ -199,23 +130,15 @@ __global__ void __launch_bounds__(HB_THREADS) k_hout_copy(HumanOutArgs a) {
             continue;
         }
         const uint64_t pB = (uint64_t)r.hlen + SFX_FIXED + r.ndig + 1, pC = pB + r.slen + 3;
-        const uint64_t end = o + r.len;
-        for (uint64_t D = (o & ~3ull) + 4ull * lane; D < end; D += 256) {
-            if (D >= o && D + 4 <= end) {
-                const uint64_t p = D - o;
-                uint32_t v;
-                if (p + 4 <= r.hlen) v = text_dword(a.text, r.h + p);
-                else if (p >= pB && p + 4 <= pB + r.slen) v = text_dword(a.text, r.s + (p - pB));
-                else if (fastq && p >= pC && p + 4 <= pC + r.qlen) v = text_dword(a.text, r.q + (p - pC));
-                else
-                    v = (uint32_t)rec_byte(a, r, fastq, p) | (uint32_t)rec_byte(a, r, fastq, p + 1) << 8 |
-                        (uint32_t)rec_byte(a, r, fastq, p + 2) << 16 | (uint32_t)rec_byte(a, r, fastq, p + 3) << 24;
-                *reinterpret_cast<uint32_t *>(out + D) = v;
-            } else {  // the record's first or last dword: its neighbours own the other bytes
-                for (uint64_t x = D; x < D + 4; x++)
-                    if (x >= o && x < end) out[x] = (char)rec_byte(a, r, fastq, x - o);
-            }
-        }
+        wave_write(
+            out, o, r.len, lane, [&](uint64_t p) { return rec_byte(a, r, fastq, p); },
+            [&](uint64_t p, uint32_t *v) {
+                if (p + 4 <= r.hlen) *v = text_dword(a.text, r.h + p);
+                else if (p >= pB && p + 4 <= pB + r.slen) *v = text_dword(a.text, r.s + (p - pB));
+                else if (fastq && p >= pC && p + 4 <= pC + r.qlen) *v = text_dword(a.text, r.q + (p - pC));
+                else return false;
+                return true;
+            });
     }
 }
 
@@ -226,9 +149,9 @@ uint64_t human_out_blocks(uint64_t n) { return (n + HB_FRAGS - 1) / HB_FRAGS; }
 hipError_t launch_human_out(const HumanOutArgs &a, hipStream_t stream) {
     if (a.n == 0) return hipMemsetAsync(a.total, 0, 2 * sizeof(uint64_t), stream);
     const dim3 grid((unsigned)a.nblk, (unsigned)a.mates);
-    hipLaunchKernelGGL(k_hout_sizes, grid, dim3(HB_THREADS), 0, stream, a);
-    hipLaunchKernelGGL(k_hout_scan, dim3((unsigned)a.mates), dim3(HB_THREADS), 0, stream, a);
-    hipLaunchKernelGGL(k_hout_copy, grid, dim3(HB_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(k_hout_sizes, grid, dim3(OB_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(k_hout_scan, dim3((unsigned)a.mates), dim3(OB_THREADS), 0, stream, a);
+    hipLaunchKernelGGL(k_hout_copy, grid, dim3(OB_THREADS), 0, stream, a);
     return hipGetLastError();
 }
 
