@@ -464,7 +464,28 @@ int nh_read_stats_write(const nh_read_stats *stats, const char *path);
  * NH_EIO: an input that cannot be read.  NH_EDB: no k-mer at all in the input.  NH_EOOM: the counting set or the table cannot be
  * allocated (the message names `capacity` as the way round the set).  NH_ECAPACITY: a given `capacity` that the minimizers fill.
  * FASTQ inputs are accepted (their sequences are read).  One device; no multi-GPU build.
+ *
+ * Several taxa (taxa_file; nh_build.hip, nh_taxa.h): a manifest with one taxon a line,
+ *     taxid <TAB> parent taxid <TAB> name [<TAB> FASTA path]...
+ * `#` lines and empty lines skipped, CRLF tolerated; a line without a path is an inner node, a node with children may carry
+ * sequences too; parent 1 is the root, which is implicit and never a line; relative paths resolve against the manifest's
+ * directory; every rank is "no rank".  Internal ids: 0 the null sentinel, 1 the root, then breadth first with the children of a
+ * node in ascending taxid.  At most 4095 taxa, 4096 nodes with the root.  value_bits is the smallest b >= 1 with 2^b >= nodes + 1
+ * (the sentinel takes a value: 12 bits up to 4094 taxa, 13 at 4095), key_bits = 32 - value_bits.  A minimizer found in two
+ * taxa is stored as their lowest common ancestor (kraken2-build's CompareAndSet with taxonomy.LowestCommonAncestor), merged on the
+ * device with compare-and-swap; the files are read in internal-id order.  taxon_stats receives, per node, what its own files
+ * held and the cells of the finished table that hold it (counted on the device); stats->taxa the nodes without the sentinel.
+ * NH_EINVAL before any device is touched, out_dir as it was, every message with the file and the line: a line with fewer than
+ * three fields; a taxid that is not a number, is 0 or 1, or appears twice; an empty name; a parent that is neither 1 nor a line; a
+ * cycle; no FASTA in the whole file; one FASTA given twice (by real path); more than 4095 taxa; the manifest or a listed FASTA
+ * being one of out_dir's three files; taxa_file together with fasta / n_fasta, a non-zero taxid or a taxon_name.  NH_EIO: a
+ * manifest or a listed FASTA that cannot be read.  A build without taxa_file writes its three files as it always did.
  */
+typedef struct {
+    uint64_t taxid;              /* external id of the node (1 for the root) */
+    uint64_t sequences, bases, kmers; /* of the node's own FASTA files (not of its descendants) */
+    uint64_t cells;              /* cells of the finished table that hold this node; the sum over all nodes is `size` */
+} nh_build_taxon_stats;
 typedef struct {
     uint32_t struct_size;        /* sizeof(nh_build_args) of the caller */
     uint32_t n_fasta;
@@ -482,6 +503,12 @@ typedef struct {
     /* ---- behind NH_BUILD_ARGS_SIZE_V1 */
     int32_t mask_low_complexity; /* not 0: mask low-complexity sequence before the minimizers are taken */
     int32_t reserved1;
+    /* ---- behind NH_BUILD_ARGS_SIZE_V2 */
+    const char *taxa_file;       /* not NULL: the taxa manifest of a build of several taxa (below); excludes fasta / n_fasta,
+                                  * taxid and taxon_name */
+    nh_build_taxon_stats *taxon_stats; /* NULL, or receives one entry a node in internal-id order, starting at the root */
+    uint32_t taxon_stats_cap;    /* entries of taxon_stats: at most that many are written */
+    uint32_t reserved2;
 } nh_build_args;
 typedef struct {
     uint64_t sequences, bases, kmers, ambiguous_kmers, distinct_minimizers, capacity, size;
@@ -489,16 +516,26 @@ typedef struct {
     /* ---- behind NH_BUILD_STATS_SIZE_V1 */
     uint64_t masked_bases;       /* input bases turned into N by the masking (as the inserting pass counted them) */
     double seconds_mask;         /* the masking kernel alone, both passes (a part of seconds_count + seconds_insert) */
+    /* ---- behind NH_BUILD_STATS_SIZE_V2 */
+    uint64_t taxa;               /* nodes of the taxonomy without the sentinel: 2 for a build of one taxon */
 } nh_build_stats;
-/* Both structs have grown at their ends, and the library tells the caller's layout by nh_build_args.struct_size alone:
+/* Both structs have grown at their ends, twice, and the library tells the caller's layout by nh_build_args.struct_size alone:
  *   struct_size <  NH_BUILD_ARGS_SIZE_V1 (80)     NH_EINVAL
- *   struct_size <  sizeof(nh_build_args) now      the first layout: fields through `force` are read, no masking, and only the first
+ *   struct_size <  NH_BUILD_ARGS_SIZE_V2 (88)     the first layout: fields through `force` are read, no masking, and only the first
  *                                                 NH_BUILD_STATS_SIZE_V1 (88) bytes of *stats are written -- a caller compiled
  *                                                 against the first header passes a buffer of that size
- *   struct_size >= sizeof(nh_build_args) now      mask_low_complexity is read and the whole nh_build_stats is written */
+ *   struct_size <  sizeof(nh_build_args) now      the second layout: mask_low_complexity is read too, and the first
+ *                                                 NH_BUILD_STATS_SIZE_V2 (104) bytes of *stats are written
+ *   struct_size >= sizeof(nh_build_args) now      taxa_file and taxon_stats are read and the whole nh_build_stats is written */
 #define NH_BUILD_ARGS_SIZE_V1 80u
 #define NH_BUILD_STATS_SIZE_V1 88u
+#define NH_BUILD_ARGS_SIZE_V2 88u
+#define NH_BUILD_STATS_SIZE_V2 104u
 int nh_build_db(const nh_build_args *args, nh_build_stats *stats);
+/* Every check nh_build_db makes before it touches a device, and no more: the same return code and message, nothing created, no
+ * device needed.  With the present layout and a taxa_file, stats->taxa and the taxid of every taxon_stats entry (the internal-id
+ * order of the manifest's nodes) are written as well; stats may be NULL. */
+int nh_build_check(const nh_build_args *args, nh_build_stats *stats);
 
 /*
  * Low-complexity masking of a host buffer in place, by the kernel and the launch code the builder uses (nh_dust.hip): symmetric

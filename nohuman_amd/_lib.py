@@ -81,13 +81,28 @@ class nh_build_stats(C.Structure):
 
 
 # The two structs above are the header's FIRST layout (NH_BUILD_ARGS_SIZE_V1 / NH_BUILD_STATS_SIZE_V1), which the library goes
-# on accepting by struct_size; the two below are the header's present structs: the same fields, then what was added at the end.
+# on accepting by struct_size; the _v2 pair is its second (NH_BUILD_ARGS_SIZE_V2 / NH_BUILD_STATS_SIZE_V2: masking), accepted
+# likewise; the _v3 pair is the header's present structs: the same fields, then what was added at the end (several taxa).
 class nh_build_args_v2(nh_build_args):
     _fields_ = [("mask_low_complexity", C.c_int32), ("reserved1", C.c_int32)]
 
 
 class nh_build_stats_v2(nh_build_stats):
     _fields_ = [("masked_bases", C.c_uint64), ("seconds_mask", C.c_double)]
+
+
+class nh_build_taxon_stats(C.Structure):
+    _fields_ = [("taxid", C.c_uint64), ("sequences", C.c_uint64), ("bases", C.c_uint64), ("kmers", C.c_uint64),
+                ("cells", C.c_uint64)]
+
+
+class nh_build_args_v3(nh_build_args_v2):
+    _fields_ = [("taxa_file", C.c_char_p), ("taxon_stats", C.POINTER(nh_build_taxon_stats)), ("taxon_stats_cap", C.c_uint32),
+                ("reserved2", C.c_uint32)]
+
+
+class nh_build_stats_v3(nh_build_stats_v2):
+    _fields_ = [("taxa", C.c_uint64)]
 
 
 # every symbol include/nohuman_engine.h declares: name -> (restype, argtypes)
@@ -147,7 +162,8 @@ SYMBOLS = {
     "nh_run_engine_rstats": (C.c_int, [_P, C.POINTER(nh_run_args), C.POINTER(nh_run_extras), C.c_uint32, C.c_char_p,
                                        C.POINTER(nh_read_stats), C.POINTER(nh_stats)]),
     "nh_read_stats_write": (C.c_int, [C.POINTER(nh_read_stats), C.c_char_p]),
-    "nh_build_db": (C.c_int, [C.POINTER(nh_build_args), C.POINTER(nh_build_stats)]),  # (or their _v2 subclasses)
+    "nh_build_db": (C.c_int, [C.POINTER(nh_build_args), C.POINTER(nh_build_stats)]),  # (or their _v2 / _v3 subclasses)
+    "nh_build_check": (C.c_int, [C.POINTER(nh_build_args), C.POINTER(nh_build_stats)]),
     "nh_dust_mask": (C.c_int, [C.c_int32, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint64,
                                C.POINTER(C.c_uint64)]),
     "nh_allreduce_counters": (C.c_int, [C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_uint64), C.c_char_p,

@@ -1,6 +1,6 @@
 // nh_build.hip -- nh_build_db: FASTA in, a kraken2 database directory out, built on the GPU (include/nohuman_engine.h).
 //
-// What it replaces: kraken2-build's build_db.cc for ONE taxon at the default geometry (k = 35, l = 31, default spaced seed and
+// What it replaces: kraken2-build's build_db.cc for one taxon, or the taxa of a manifest, at the default geometry (k = 35, l = 31, default spaced seed and
 // toggle mask, revcom_version 1, minimum_acceptable_hash_value 0, linear probing).  That is the limit, on purpose: it is what the
 // HPRC databases are and what the classifier's fast path (is_std) is built for.
 //
@@ -30,6 +30,12 @@
 // last base of the batch (beside the batch's size: at most one chunk of a batch starts, and one ends, inside a sequence); the
 // pieces still cover every k-mer once.  The chunks are the segments of the mask: no triplet spans two records.  Every input base is
 // counted as masked in one chunk only, sequences too short for a k-mer included.
+//
+// Several taxa (taxa_file; nh_taxa.h): every piece carries the internal id of its taxon (piece_value), INSERT runs as
+// k_build_pieces<false, true> and merges a key that two taxa share into their lowest common ancestor with compare-and-swap -- the
+// node table (parent) is read from global memory: it is at most 16 KB, shared by every wave and looked at only on that path -- and
+// k_value_cells counts the cells per node of the finished table.  COUNT knows no taxon.  A build of one taxon launches the kernels
+// it always did (MULTI = false).
 #include <errno.h>
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -51,6 +57,7 @@
 #include "nh_fastx.h"
 #include "nh_internal.h"
 #include "nh_scan.h"
+#include "nh_taxa.h"
 #include "nohuman_engine.h"
 
 namespace nh {
@@ -62,13 +69,18 @@ struct BuildDev {
     uint64_t set_cap, set_magic;   // slots, floor((2^64 - 1) / slots)
     unsigned long long *counters;  // [0] slots / cells claimed, [1] k-mers that are not ambiguous
     int *full;                     // raised by a lane whose probe saw every slot / cell
-    uint32_t value, pad;           // INSERT: the value field of every cell
+    uint32_t value, pad;           // INSERT: the value field of every cell (one taxon)
+    // INSERT of several taxa (MULTI)
+    const uint32_t *piece_value;   // the internal id of each piece's taxon
+    const uint32_t *parent;        // the node table: parent[id] < id, 2^value_bits entries (zero behind the last node)
 };
 
 constexpr uint32_t FULL_POLL = 1023;  // a probing lane looks at `full` every 1024 cells
 
 // One wave per piece: sequence text[seq_off[p], +seq_len[p]) (starts and lengths, so that pieces may overlap).
-template <bool COUNT>
+// MULTI (INSERT only): the value of a piece is its taxon's, and a cell that already holds the key under another value becomes the
+// lowest common ancestor of the two.
+template <bool COUNT, bool MULTI>
 __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_build_pieces(const KArgs args_by_kernarg_pointer, const BuildDev b) {
     KArgsP ap = (KArgsP)__builtin_amdgcn_kernarg_segment_ptr();
     typedef WaveLdsT<true, 1, QCAP_GENERIC> WL;
@@ -93,6 +105,7 @@ __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_build_pieces(const K
     uint64_t tprev = 0;
     unsigned long long claimed = 0;  // per lane
     unsigned long long clean = 0;    // wave-uniform
+    unsigned long long merges = 0, swaps = 0, inserts = 0;  // per lane (MULTI): own key found under another value; values replaced; insertions
     bool gave_up = false;
     const uint64_t n_waves = (uint64_t)gridDim.x * WAVES_PER_BLOCK;
     for (uint64_t p = (uint64_t)blockIdx.x * WAVES_PER_BLOCK + wib; p < n_piece; p += n_waves) {
@@ -100,6 +113,7 @@ __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_build_pieces(const K
         const uint32_t n = len[p];
         if (n < 35u || o0 > text_len || text_len - o0 < n) continue;  // (wave-uniform; the host makes no such piece)
         const uint32_t nk = n - 34u;
+        const uint32_t mine = MULTI ? b.piece_value[p] : b.value;  // (wave-uniform)
         uint64_t carry_min = NH_FULL;
         uint32_t w;
         {
@@ -125,6 +139,7 @@ __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_build_pieces(const K
             wave_sync();
             for (uint32_t r = lane; r < nruns && !gave_up; r += 64) {
                 const uint64_t mz = S.q[0][r];
+                if (MULTI) inserts++;
                 const uint64_t hc = fmix64(mz);
                 uint64_t idx = mod_capacity(hc, cap, magic);
                 bool placed = false;
@@ -151,7 +166,7 @@ __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_build_pieces(const K
                     }
                 } else {
                     const uint32_t compacted = (uint32_t)(hc >> (32 + vbits));
-                    const uint32_t cell = (compacted << vbits) | b.value;
+                    const uint32_t cell = (compacted << vbits) | mine;
                     for (uint64_t tries = 0; tries < cap; tries++) {
                         uint32_t cur = __hip_atomic_load(&table[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         if (cur == 0) {
@@ -163,6 +178,30 @@ __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_build_pieces(const K
                             }
                         }
                         if ((cur >> vbits) == compacted) {
+                            if (MULTI) {
+                                // kraken2's CompareAndSet with LowestCommonAncestor: the larger id walks up its parent.  The key of a
+                                // cell never changes and its value only moves towards the root, so a lane that loses the swap
+                                // goes on from the value that won, at most as often as the tree is deep.
+                                const uint32_t vmask = (1u << vbits) - 1u;
+                                bool first = true;
+                                for (;;) {
+                                    const uint32_t v = cur & vmask;
+                                    uint32_t x = v, y = mine;
+                                    while (x != y) {
+                                        if (x > y) x = b.parent[x];
+                                        else y = b.parent[y];
+                                    }
+                                    if (first && v != mine) merges++;
+                                    first = false;
+                                    if (x == v) break;
+                                    const uint32_t seen = atomicCAS(&table[idx], cur, (compacted << vbits) | x);
+                                    if (seen == cur) {
+                                        swaps++;
+                                        break;
+                                    }
+                                    cur = seen;
+                                }
+                            }
                             placed = true;
                             break;
                         }
@@ -187,6 +226,36 @@ __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_build_pieces(const K
         if (claimed) atomicAdd(&b.counters[0], claimed);
         if (!COUNT && clean) atomicAdd(&b.counters[1], clean);
     }
+    if (MULTI) {
+        for (int d = 32; d >= 1; d >>= 1)
+            merges += __shfl_xor(merges, d, 64), swaps += __shfl_xor(swaps, d, 64), inserts += __shfl_xor(inserts, d, 64);
+        if (lane == 0 && merges) atomicAdd(&b.counters[4], merges);
+        if (lane == 0 && swaps) atomicAdd(&b.counters[5], swaps);
+        if (lane == 0 && inserts) atomicAdd(&b.counters[6], inserts);
+    }
+}
+
+// Cells per node of the finished table (several taxa): bins in LDS, one global atomic per non-zero bin and workgroup.  No occupied
+// cell holds the value 0, so bin i counts the value i + 1: VALUE_BINS bins hold every node of the largest taxonomy.  The table is
+// read four cells a lane; it is allocated, and zero, through the next multiple of four behind `cap`.
+constexpr uint32_t VALUE_BINS = TAXA_MAX_NODES;
+__global__ __launch_bounds__(256) void k_value_cells(const uint32_t *table, const uint64_t cap, const uint32_t vmask, const uint32_t nodes,
+                                                     unsigned long long *cells) {
+    __shared__ uint32_t bins[VALUE_BINS];
+    for (uint32_t i = threadIdx.x; i < VALUE_BINS; i += blockDim.x) bins[i] = 0;
+    __syncthreads();
+    const uint64_t n4 = (cap + 3) >> 2, stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint4 *const t4 = reinterpret_cast<const uint4 *>(table);
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        const uint4 c = t4[i];
+        for (uint32_t w : {c.x, c.y, c.z, c.w}) {
+            const uint32_t bin = (w & vmask) - 1u;  // (an empty cell: 0 - 1 is no bin; nor is a value without a node)
+            if (w != 0 && bin < nodes - 1u && bin < VALUE_BINS) atomicAdd(&bins[bin], 1u);
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < VALUE_BINS && i < nodes - 1u; i += blockDim.x)
+        if (bins[i]) atomicAdd(&cells[i + 1], (unsigned long long)bins[i]);
 }
 
 // the keys of the old set into the new, larger one (no key is in it twice: a plain claim of the first empty slot)
@@ -224,12 +293,19 @@ constexpr uint64_t DEFAULT_PIECE_KMERS = 16 * (TL - 4);  // 1984: 16 tiles, 1.7 
 constexpr uint64_t DEFAULT_BATCH_BYTES = 128ull << 20;
 constexpr uint64_t TOGGLE_MASK = 0xe37e28c4271b5a2dull;
 constexpr uint64_t SPACED_MASK = 0x3FFFFFFFF3333333ull;  // "1" x 17 + "01" x 7, two bits a base
-constexpr uint32_t VALUE_BITS = 2, TAXON_NODE = 2;       // three nodes: 0 the null sentinel, 1 root, 2 the taxon
+constexpr uint32_t TAXON_NODE = 2;                       // one taxon: three nodes, 0 the null sentinel, 1 root, 2 the taxon
+constexpr int N_COUNTERS = 7;  // claimed, clean, `full` (an int), masked bases, then of several taxa: LCA merges, values replaced, insertions
 const char *const DB_FILES[3] = {"hash.k2d", "opts.k2d", "taxo.k2d"};
 
 double since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
+
+// one input file and the node (internal id) its sequences belong to
+struct BuildInput {
+    std::string path;
+    uint32_t node;
+};
 
 struct Builder {
     // arguments
@@ -242,6 +318,8 @@ struct Builder {
     std::vector<char> text;
     std::vector<uint64_t> starts;
     std::vector<uint32_t> lens;
+    std::vector<uint32_t> values;  // several taxa: the internal id of each piece's taxon
+    uint32_t cur_value = TAXON_NODE;  // the taxon of the file being read (a sequence cut at a batch's end keeps it in the next batch)
     uint64_t batch_kmers = 0;
     std::vector<DustTile> tiles;  // masking: the tiles of the batch's chunks
     uint64_t ctx_bytes = 0;       // masking: bytes of the batch that are context, beside batch_cap
@@ -251,12 +329,21 @@ struct Builder {
     char *d_text = nullptr;
     uint64_t *d_starts = nullptr;
     uint32_t *d_lens = nullptr;
+    uint32_t *d_values = nullptr;
     uint64_t piece_cap = 0;
+    // several taxa: the node table and the cells per node, resident for the whole build
+    bool multi = false;
+    uint32_t node_count = 3, vbits = 2;
+    std::vector<uint32_t> parent;  // 2^vbits entries
+    uint32_t *d_parent = nullptr;
+    unsigned long long *d_cells = nullptr;
+    unsigned long long merges = 0, swaps = 0, inserts = 0;
+    double t_cells = 0;  // k_value_cells alone
     char *d_raw = nullptr;  // masking: the batch as it was uploaded, which the mask kernel reads while it writes d_text
     DustTile *d_tiles = nullptr;
     uint64_t tile_cap = 0;
     int dust_grid = 0;
-    unsigned long long *d_counters = nullptr;  // two counters, then `full` as an int, then the masked bases
+    unsigned long long *d_counters = nullptr;  // N_COUNTERS: two counters, then `full` as an int, then the masked bases, ...
     unsigned long long *d_set = nullptr;
     uint64_t set_cap = 0;
     uint32_t *d_table = nullptr;
@@ -271,11 +358,12 @@ struct Builder {
     unsigned long long masked = 0;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     uint64_t sequences = 0, bases = 0, kmers = 0;
+    std::vector<nh_build_taxon_stats> per_node;  // by internal id
 
     ~Builder() {
         if (device >= 0 && stream) (void)dev_set(device);
         for (void *p : {(void *)d_text, (void *)d_starts, (void *)d_lens, (void *)d_counters, (void *)d_set, (void *)d_table, (void *)d_raw,
-                        (void *)d_tiles})
+                        (void *)d_tiles, (void *)d_values, (void *)d_parent, (void *)d_cells})
             if (p) (void)hipFree(p);
         for (hipEvent_t e : ev)
             if (e) (void)hipEventDestroy(e);
@@ -289,7 +377,7 @@ struct Builder {
         hipDeviceProp_t prop;
         BUILD_TRY(hipGetDeviceProperties(&prop, dev_phys(device)));
         int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_build_pieces<false>, WAVE * WAVES_PER_BLOCK, 0) != hipSuccess || per_cu < 1) {
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_build_pieces<false, false>, WAVE * WAVES_PER_BLOCK, 0) != hipSuccess || per_cu < 1) {
             (void)hipGetLastError();
             per_cu = 4;
         }
@@ -302,15 +390,22 @@ struct Builder {
             BUILD_TRY(dev_malloc(&d_raw, batch_cap + 2 * DUST_CONTEXT + 64));
             dust_grid = dust_grid_max();
         }
-        BUILD_TRY(dev_malloc(&d_counters, 4 * sizeof(unsigned long long)));
+        BUILD_TRY(dev_malloc(&d_counters, N_COUNTERS * sizeof(unsigned long long)));
+        if (multi) {
+            BUILD_TRY(dev_malloc(&d_parent, parent.size() * sizeof(uint32_t)));
+            BUILD_TRY(hipMemcpyAsync(d_parent, parent.data(), parent.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+            BUILD_TRY(dev_malloc(&d_cells, (size_t)node_count * sizeof(unsigned long long)));
+            BUILD_TRY(hipMemsetAsync(d_cells, 0, (size_t)node_count * sizeof(unsigned long long), stream));
+            BUILD_TRY(hipStreamSynchronize(stream));
+        }
         text.reserve(batch_cap);
         return NH_OK;
     }
 
     int reset_counters() {
-        BUILD_TRY(hipMemsetAsync(d_counters, 0, 4 * sizeof(unsigned long long), stream));
+        BUILD_TRY(hipMemsetAsync(d_counters, 0, N_COUNTERS * sizeof(unsigned long long), stream));
         BUILD_TRY(hipStreamSynchronize(stream));
-        claimed = clean = masked = 0;
+        claimed = clean = masked = merges = swaps = inserts = 0;
         full = false;
         return NH_OK;
     }
@@ -383,10 +478,12 @@ struct Builder {
         if (n_piece > piece_cap) {
             if (d_starts) (void)hipFree(d_starts);
             if (d_lens) (void)hipFree(d_lens);
-            d_starts = nullptr, d_lens = nullptr, piece_cap = 0;
+            if (d_values) (void)hipFree(d_values);
+            d_starts = nullptr, d_lens = nullptr, d_values = nullptr, piece_cap = 0;
             const uint64_t ncap = n_piece + n_piece / 2 + 1024;
             BUILD_TRY(dev_malloc(&d_starts, ncap * sizeof(uint64_t)));
             BUILD_TRY(dev_malloc(&d_lens, ncap * sizeof(uint32_t)));
+            if (multi) BUILD_TRY(dev_malloc(&d_values, ncap * sizeof(uint32_t)));
             piece_cap = ncap;
         }
         BUILD_TRY(hipMemcpyAsync(d_text, text.data(), text.size(), hipMemcpyHostToDevice, stream));
@@ -394,6 +491,7 @@ struct Builder {
         if (n_piece) {
             BUILD_TRY(hipMemcpyAsync(d_starts, starts.data(), n_piece * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
             BUILD_TRY(hipMemcpyAsync(d_lens, lens.data(), n_piece * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+            if (multi && !counting) BUILD_TRY(hipMemcpyAsync(d_values, values.data(), n_piece * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
         }
         const bool masking = !tiles.empty();
         if (masking) {
@@ -418,9 +516,9 @@ struct Builder {
         d.copy_shift = 5;
         d.capacity = counting ? 1 : capacity;
         d.cap_magic = ~0ull / d.capacity;
-        d.node_count = 3;
-        d.value_bits = VALUE_BITS;
-        d.vmask = (1u << VALUE_BITS) - 1;
+        d.node_count = node_count;
+        d.value_bits = vbits;
+        d.vmask = (1u << vbits) - 1;
         d.k = 35, d.l = 31, d.window = 4;
         d.lmer_mask = (1ull << 62) - 1;
         d.spaced_mask = SPACED_MASK;
@@ -442,18 +540,22 @@ struct Builder {
         b.counters = d_counters;
         b.full = d_full();
         b.value = TAXON_NODE;
+        b.piece_value = d_values;
+        b.parent = d_parent;
         const uint64_t want = (n_piece + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
         const unsigned grid = (unsigned)(want < (uint64_t)grid_max ? want : (uint64_t)grid_max);
         BUILD_TRY(hipEventRecord(ev[0], stream));
         if (n_piece == 0)
             ;  // (masking: a batch of sequences too short for a k-mer)
         else if (counting)
-            hipLaunchKernelGGL(k_build_pieces<true>, dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, stream, ka, b);
+            hipLaunchKernelGGL((k_build_pieces<true, false>), dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, stream, ka, b);
+        else if (multi)
+            hipLaunchKernelGGL((k_build_pieces<false, true>), dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, stream, ka, b);
         else
-            hipLaunchKernelGGL(k_build_pieces<false>, dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, stream, ka, b);
+            hipLaunchKernelGGL((k_build_pieces<false, false>), dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, stream, ka, b);
         BUILD_TRY(hipGetLastError());
         BUILD_TRY(hipEventRecord(ev[1], stream));
-        unsigned long long out[4] = {0, 0, 0, 0};
+        unsigned long long out[N_COUNTERS] = {0, 0, 0, 0, 0, 0, 0};
         BUILD_TRY(hipMemcpyAsync(out, d_counters, sizeof out, hipMemcpyDeviceToHost, stream));
         BUILD_TRY(hipStreamSynchronize(stream));
         float ms = 0;
@@ -466,12 +568,16 @@ struct Builder {
         claimed = out[0];
         clean = out[1];
         masked = out[3];
+        merges = out[4];
+        swaps = out[5];
+        inserts = out[6];
         int f;
         memcpy(&f, &out[2], sizeof f);
         full = f != 0;
         text.clear();
         starts.clear();
         lens.clear();
+        values.clear();
         tiles.clear();
         batch_kmers = ctx_bytes = 0;
         t_gpu += since(t0);
@@ -512,6 +618,7 @@ struct Builder {
                 const size_t pk = mk - p < piece ? mk - p : (size_t)piece;
                 starts.push_back(t + p);
                 lens.push_back((uint32_t)(pk + 34));
+                if (multi) values.push_back(cur_value);
             }
             batch_kmers += mk;
             pos += mk;
@@ -531,26 +638,48 @@ struct Builder {
         return NH_OK;
     }
 
+    // the cells per node of the finished table into per_node (several taxa)
+    int count_cells() {
+        const uint64_t want = (capacity + 4095) / 4096;
+        const unsigned grid = (unsigned)(want < (uint64_t)grid_max ? (want ? want : 1) : (uint64_t)grid_max);
+        BUILD_TRY(hipEventRecord(ev[0], stream));
+        hipLaunchKernelGGL(k_value_cells, dim3(grid), dim3(256), 0, stream, d_table, capacity, (1u << vbits) - 1u, node_count, d_cells);
+        BUILD_TRY(hipGetLastError());
+        BUILD_TRY(hipEventRecord(ev[1], stream));
+        std::vector<unsigned long long> out(node_count, 0);
+        BUILD_TRY(hipMemcpyAsync(out.data(), d_cells, out.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+        BUILD_TRY(hipStreamSynchronize(stream));
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) t_cells = ms * 1e-3;
+        else (void)hipGetLastError();
+        for (uint32_t i = 1; i < node_count; i++) per_node[i].cells = out[i];
+        return NH_OK;
+    }
+
     // every record of every input through add_sequence
-    int pass(const nh_build_args *a, bool count, bool totals) {
+    int pass(const std::vector<BuildInput> &inputs, bool count, bool totals) {
         counting = count;
         int rc = reset_counters();
         if (rc) return rc;
         SeqRecord rec;
-        for (uint32_t i = 0; i < a->n_fasta; i++) {
+        for (const BuildInput &in : inputs) {
             FastxReader rd;
             std::string err;
             auto t0 = std::chrono::steady_clock::now();
-            if (rd.open(a->fasta[i], err, threads) != 0) return set_error(NH_EIO, "%s", err.c_str());
+            if (rd.open(in.path.c_str(), err, threads) != 0) return set_error(NH_EIO, "%s", err.c_str());
+            cur_value = in.node;
+            nh_build_taxon_stats &pn = per_node[in.node];
             for (;;) {
                 const int got = rd.next(rec, err);
-                if (got < 0) return set_error(NH_EIO, "%s: %s", a->fasta[i], err.c_str());
+                if (got < 0) return set_error(NH_EIO, "%s: %s", in.path.c_str(), err.c_str());
                 if (got == 0) break;
                 t_read += since(t0);
                 if (totals) {
                     sequences++;
                     bases += rec.seq.size();
-                    if (rec.seq.size() >= 35) kmers += rec.seq.size() - 34;
+                    pn.sequences++;
+                    pn.bases += rec.seq.size();
+                    if (rec.seq.size() >= 35) kmers += rec.seq.size() - 34, pn.kmers += rec.seq.size() - 34;
                 }
                 rc = add_sequence(rec.seq.data(), rec.seq.size());
                 if (rc) return rc;
@@ -602,18 +731,25 @@ std::vector<uint8_t> opts_image() {
 }
 
 // "K2TAXDAT", node count, bytes of the name and the rank strings, 56-byte nodes {parent, first child, child count,
-// name offset, rank offset, external id, godparent}, the two string tables
-std::vector<uint8_t> taxo_image(uint64_t taxid, const std::string &name) {
-    const std::string names = std::string("root") + '\0' + name + '\0', ranks = std::string("no rank") + '\0';
-    uint64_t nodes[3][7];
-    memset(nodes, 0, sizeof nodes);
-    nodes[1][1] = 2, nodes[1][2] = 1, nodes[1][5] = 1;        // root: one child, node 2
-    nodes[2][0] = 1, nodes[2][3] = 5, nodes[2][5] = taxid;    // the taxon: child of 1, its name behind "root\0"
+// name offset, rank offset, external id, godparent}, the two string tables.  The sentinel shares the root's name, "root".
+std::vector<uint8_t> taxo_image(const std::vector<TaxaNode> &nodes) {
+    std::string names = std::string("root") + '\0';
+    const std::string ranks = std::string("no rank") + '\0';
+    std::vector<uint64_t> recs(nodes.size() * 7, 0);
+    for (size_t i = 1; i < nodes.size(); i++) {
+        uint64_t *r = &recs[i * 7];
+        r[0] = nodes[i].parent, r[1] = nodes[i].first_child, r[2] = nodes[i].children, r[5] = nodes[i].taxid;
+        if (i >= 2) {
+            r[3] = names.size();
+            names += nodes[i].name;
+            names += '\0';
+        }
+    }
     std::vector<uint8_t> img;
     img.insert(img.end(), (const uint8_t *)"K2TAXDAT", (const uint8_t *)"K2TAXDAT" + 8);
-    const uint64_t hdr[3] = {3, names.size(), ranks.size()};
+    const uint64_t hdr[3] = {nodes.size(), names.size(), ranks.size()};
     img.insert(img.end(), (const uint8_t *)hdr, (const uint8_t *)hdr + 24);
-    img.insert(img.end(), (const uint8_t *)nodes, (const uint8_t *)nodes + sizeof nodes);
+    img.insert(img.end(), (const uint8_t *)recs.data(), (const uint8_t *)recs.data() + recs.size() * sizeof(uint64_t));
     img.insert(img.end(), names.begin(), names.end());
     img.insert(img.end(), ranks.begin(), ranks.end());
     return img;
@@ -629,7 +765,7 @@ bool write_file(const std::string &path, const std::vector<uint8_t> &img) {
 }
 
 // the three files under temporary names, then renamed into place; on any failure nothing of this call stays behind
-int write_database(Builder &B, const nh_build_args *a, uint64_t taxid, const std::string &name, uint64_t size) {
+int write_database(Builder &B, const nh_build_args *a, const std::vector<TaxaNode> &nodes, uint64_t size) {
     const std::string dir = a->out_dir;
     bool made_dir = false;
     struct stat st;
@@ -649,7 +785,7 @@ int write_database(Builder &B, const nh_build_args *a, uint64_t taxid, const std
     {   // hash.k2d: {capacity, size, key_bits, value_bits}, then the cells, fetched from the device a stretch at a time
         FILE *f = fopen(tmp[0].c_str(), "wb");
         if (!f) return fail(NH_EIO, "cannot write " + tmp[0] + ": " + strerror(errno));
-        const uint64_t hdr[4] = {B.capacity, size, 32 - VALUE_BITS, VALUE_BITS};
+        const uint64_t hdr[4] = {B.capacity, size, 32 - B.vbits, B.vbits};
         bool ok = write_all(f, hdr, sizeof hdr);
         const uint64_t step = 16ull << 20;  // cells
         std::vector<uint32_t> buf((size_t)(B.capacity < step ? B.capacity : step));
@@ -665,52 +801,132 @@ int write_database(Builder &B, const nh_build_args *a, uint64_t taxid, const std
         if (!ok) return fail(NH_EIO, "cannot write " + tmp[0]);
     }
     if (!write_file(tmp[1], opts_image())) return fail(NH_EIO, "cannot write " + tmp[1]);
-    if (!write_file(tmp[2], taxo_image(taxid, name))) return fail(NH_EIO, "cannot write " + tmp[2]);
+    if (!write_file(tmp[2], taxo_image(nodes))) return fail(NH_EIO, "cannot write " + tmp[2]);
     for (int i = 0; i < 3; i++)
         if (rename(tmp[i].c_str(), fin[i].c_str()) != 0) return fail(NH_EIO, "cannot move " + tmp[i] + " into place: " + strerror(errno));
     return NH_OK;
 }
 
-int build_db(const nh_build_args *a, nh_build_stats *stats) {
-    // (the caller's layout is told by struct_size: one of the first layout gets the first layout's stats and no more)
-    const bool grown = a && a->struct_size >= sizeof(nh_build_args);
-    const size_t stats_size = grown ? sizeof(nh_build_stats) : (size_t)NH_BUILD_STATS_SIZE_V1;
-    if (stats) memset(stats, 0, stats_size);
-    // ---- arguments: everything refused here is refused before any device is touched and before anything is created
+// what the arguments ask for, once they have passed every check that needs no device
+struct BuildPlan {
+    bool grown = false, v3 = false;  // the caller's layout: masking is read; the taxa fields are read
+    size_t stats_size = NH_BUILD_STATS_SIZE_V1;
+    double lf = 0.7;
+    std::vector<TaxaNode> nodes;     // [0] the sentinel, [1] the root, then the taxa in internal-id order
+    std::vector<BuildInput> inputs;  // in the order they are read: by node, a node's files as given
+};
+
+// (the caller's layout is told by struct_size: one of an earlier layout gets that layout's stats and no more)
+void layout_of(const nh_build_args *a, BuildPlan &P) {
+    P.grown = a && a->struct_size >= NH_BUILD_ARGS_SIZE_V2;
+    P.v3 = a && a->struct_size >= sizeof(nh_build_args);
+    P.stats_size = P.v3 ? sizeof(nh_build_stats) : P.grown ? (size_t)NH_BUILD_STATS_SIZE_V2 : (size_t)NH_BUILD_STATS_SIZE_V1;
+}
+
+// ---- arguments: everything refused here is refused before any device is touched and before anything is created
+int plan_build(const nh_build_args *a, BuildPlan &P) {
     if (!a) return set_error(NH_EINVAL, "nh_build_db: null arguments");
     if (a->struct_size < NH_BUILD_ARGS_SIZE_V1)
         return set_error(NH_EINVAL, "nh_build_db: struct_size %u is smaller than nh_build_args (%u)", a->struct_size, NH_BUILD_ARGS_SIZE_V1);
-    if (a->n_fasta == 0 || !a->fasta) return set_error(NH_EINVAL, "nh_build_db: no input (n_fasta 0)");
-    for (uint32_t i = 0; i < a->n_fasta; i++)
-        if (!a->fasta[i]) return set_error(NH_EINVAL, "nh_build_db: input %u is a null path", i);
+    const char *taxa_file = P.v3 ? a->taxa_file : nullptr;
+    if (taxa_file) {
+        if (!*taxa_file) return set_error(NH_EINVAL, "nh_build_db: taxa_file is an empty path");
+        if (a->n_fasta != 0 || a->fasta) return set_error(NH_EINVAL, "nh_build_db: taxa_file cannot be combined with fasta / n_fasta: the manifest lists the FASTA files");
+        if (a->taxid != 0) return set_error(NH_EINVAL, "nh_build_db: taxa_file cannot be combined with taxid: the manifest gives the taxids");
+        if (a->taxon_name) return set_error(NH_EINVAL, "nh_build_db: taxa_file cannot be combined with taxon_name: the manifest gives the names");
+    } else {
+        if (a->n_fasta == 0 || !a->fasta) return set_error(NH_EINVAL, "nh_build_db: no input (n_fasta 0)");
+        for (uint32_t i = 0; i < a->n_fasta; i++)
+            if (!a->fasta[i]) return set_error(NH_EINVAL, "nh_build_db: input %u is a null path", i);
+    }
     if (!a->out_dir || !*a->out_dir) return set_error(NH_EINVAL, "nh_build_db: no output directory");
-    const double lf = a->load_factor == 0 ? 0.7 : a->load_factor;
-    if (!(lf > 0 && lf <= 0.95)) return set_error(NH_EINVAL, "nh_build_db: load factor %g is not in (0, 0.95]", a->load_factor);
+    P.lf = a->load_factor == 0 ? 0.7 : a->load_factor;
+    if (!(P.lf > 0 && P.lf <= 0.95)) return set_error(NH_EINVAL, "nh_build_db: load factor %g is not in (0, 0.95]", a->load_factor);
     if (a->taxid == 1) return set_error(NH_EINVAL, "nh_build_db: taxid 1 is the root of the taxonomy, not a taxon to build");
-    const uint64_t taxid = a->taxid ? a->taxid : 9606;
     // (a probe-queue entry of the classifier packs the home cell and the 30-bit key into 63 bits)
     if (a->capacity >> 33) return set_error(NH_EINVAL, "nh_build_db: capacity %llu is not below 2^33", (unsigned long long)a->capacity);
     const std::string dir = a->out_dir;
     struct stat st;
     if (stat(dir.c_str(), &st) == 0 && !S_ISDIR(st.st_mode)) return set_error(NH_EINVAL, "nh_build_db: %s is not a directory", dir.c_str());
-    for (uint32_t i = 0; i < a->n_fasta; i++)
-        if (input_is_output(a->fasta[i], dir))
-            return set_error(NH_EINVAL, "nh_build_db: the input %s is a database file of the output directory %s", a->fasta[i], dir.c_str());
+    if (taxa_file) {
+        if (input_is_output(taxa_file, dir))
+            return set_error(NH_EINVAL, "nh_build_db: the taxa manifest %s is a database file of the output directory %s", taxa_file, dir.c_str());
+        std::string err;
+        const int rc = parse_taxa(taxa_file, P.nodes, err);
+        if (rc) return set_error(rc, "%s", err.c_str());
+        for (size_t i = 2; i < P.nodes.size(); i++)
+            for (const std::string &f : P.nodes[i].files) {
+                if (input_is_output(f.c_str(), dir))
+                    return set_error(NH_EINVAL, "nh_build_db: %s line %u: the input %s is a database file of the output directory %s", taxa_file,
+                                     P.nodes[i].line, f.c_str(), dir.c_str());
+                P.inputs.push_back({f, (uint32_t)i});
+            }
+    } else {
+        for (uint32_t i = 0; i < a->n_fasta; i++)
+            if (input_is_output(a->fasta[i], dir))
+                return set_error(NH_EINVAL, "nh_build_db: the input %s is a database file of the output directory %s", a->fasta[i], dir.c_str());
+    }
     if (!a->force)
         for (const char *name : DB_FILES)
             if (file_there(dir + "/" + name))
                 return set_error(NH_EINVAL, "nh_build_db: %s already holds %s (`force` replaces a database)", dir.c_str(), name);
-    std::string name;
-    if (a->taxon_name) name = a->taxon_name;
-    else if (taxid == 9606) name = "Homo sapiens";
-    else name = "taxon" + std::to_string(taxid);
+    if (!taxa_file) {  // one taxon: the three nodes it always had
+        const uint64_t taxid = a->taxid ? a->taxid : 9606;
+        P.nodes.resize(3);
+        P.nodes[1].taxid = 1, P.nodes[1].name = "root", P.nodes[1].first_child = 2, P.nodes[1].children = 1;
+        P.nodes[2].taxid = taxid, P.nodes[2].parent = 1;
+        if (a->taxon_name) P.nodes[2].name = a->taxon_name;
+        else if (taxid == 9606) P.nodes[2].name = "Homo sapiens";
+        else P.nodes[2].name = "taxon" + std::to_string(taxid);
+        for (uint32_t i = 0; i < a->n_fasta; i++) P.inputs.push_back({a->fasta[i], TAXON_NODE});
+    }
+    return NH_OK;
+}
 
-    int rc = check_device(a->device);
+// the per-node results into the caller's array (present layout only)
+void give_taxon_stats(const nh_build_args *a, const BuildPlan &P, const std::vector<nh_build_taxon_stats> &per_node) {
+    if (!P.v3 || !a->taxon_stats) return;
+    for (uint32_t i = 1; i < per_node.size() && i - 1 < a->taxon_stats_cap; i++) a->taxon_stats[i - 1] = per_node[i];
+}
+
+int build_check(const nh_build_args *a, nh_build_stats *stats) {
+    BuildPlan P;
+    layout_of(a, P);
+    if (stats) memset(stats, 0, P.stats_size);
+    const int rc = plan_build(a, P);
+    if (rc) return rc;
+    std::vector<nh_build_taxon_stats> per_node(P.nodes.size());
+    for (size_t i = 0; i < P.nodes.size(); i++) memset(&per_node[i], 0, sizeof per_node[i]), per_node[i].taxid = P.nodes[i].taxid;
+    give_taxon_stats(a, P, per_node);
+    if (stats && P.v3) stats->taxa = P.nodes.size() - 1;
+    return NH_OK;
+}
+
+int build_db(const nh_build_args *a, nh_build_stats *stats) {
+    BuildPlan P;
+    layout_of(a, P);
+    const size_t stats_size = P.stats_size;
+    if (stats) memset(stats, 0, stats_size);
+    int rc = plan_build(a, P);
+    if (rc) return rc;
+    const double lf = P.lf;
+
+    rc = check_device(a->device);
     if (rc) return rc;
     Builder B;
     B.device = a->device;
     B.threads = a->threads;
-    B.mask = grown && a->mask_low_complexity != 0;
+    B.mask = P.grown && a->mask_low_complexity != 0;
+    B.node_count = (uint32_t)P.nodes.size();
+    B.multi = B.node_count > 3;  // (a manifest of one taxon is the one-taxon build)
+    B.vbits = value_bits_for(B.node_count);
+    B.parent.assign((size_t)1 << B.vbits, 0);
+    B.per_node.resize(B.node_count);
+    for (uint32_t i = 0; i < B.node_count; i++) {
+        B.parent[i] = P.nodes[i].parent;
+        memset(&B.per_node[i], 0, sizeof B.per_node[i]);
+        B.per_node[i].taxid = P.nodes[i].taxid;
+    }
     if (a->piece_kmers) B.piece = a->piece_kmers < (1ull << 31) ? a->piece_kmers : (1ull << 31);
     if (const char *env = getenv("NOHUMAN_BUILD_BATCH")) {  // test knob: bytes of text per batch (sequences cut at the batches' ends)
         const long long v = atoll(env);
@@ -726,7 +942,7 @@ int build_db(const nh_build_args *a, nh_build_stats *stats) {
     uint64_t capacity = a->capacity;
     double count_kernel = 0;
     if (!capacity) {
-        rc = B.pass(a, true, true);
+        rc = B.pass(P.inputs, true, true);
         if (rc) return rc;
         s.distinct_minimizers = B.claimed;
         s.seconds_count = B.t_gpu;
@@ -741,7 +957,7 @@ int build_db(const nh_build_args *a, nh_build_stats *stats) {
     }
     rc = B.alloc_table(capacity);
     if (rc) return rc;
-    rc = B.pass(a, false, a->capacity != 0);
+    rc = B.pass(P.inputs, false, a->capacity != 0);
     if (rc) return rc;
     s.seconds_insert = B.t_gpu;
     s.seconds_read = B.t_read;
@@ -760,8 +976,15 @@ int build_db(const nh_build_args *a, nh_build_stats *stats) {
     if (s.size >= capacity)
         return set_error(NH_ECAPACITY, "the table of %llu cells is full: the input has more distinct minimizers than `capacity` holds "
                          "(leave capacity 0 and it is counted)", (unsigned long long)capacity);
+    s.taxa = B.node_count - 1;
+    if (B.multi) {
+        rc = B.count_cells();
+        if (rc) return rc;
+    } else {
+        B.per_node[TAXON_NODE].cells = s.size;
+    }
     auto t0 = std::chrono::steady_clock::now();
-    rc = write_database(B, a, taxid, name, s.size);
+    rc = write_database(B, a, P.nodes, s.size);
     if (rc) return rc;
     s.seconds_write = since(t0);
     if (getenv("NOHUMAN_TRACE"))
@@ -771,12 +994,27 @@ int build_db(const nh_build_args *a, nh_build_stats *stats) {
                 (unsigned long long)s.size, (unsigned long long)s.capacity, count_kernel, B.t_kernel, B.t_mask,
                 (unsigned long long)s.masked_bases, (unsigned long long)B.batch_cap,
                 (unsigned long long)B.piece);
+    if (getenv("NOHUMAN_TRACE") && B.multi)
+        fprintf(stderr, "[nohuman trace] build taxa: %u nodes, value_bits %u; insertions %llu, of them %llu found their key under another "
+                        "value (the LCA path), values replaced %llu; cells per node %.6f s\n", B.node_count - 1, B.vbits, B.inserts, B.merges,
+                B.swaps, B.t_cells);
+    give_taxon_stats(a, P, B.per_node);
     if (stats) memcpy(stats, &s, stats_size);
     return NH_OK;
 }
 
 }  // namespace
 }  // namespace nh
+
+extern "C" int nh_build_check(const nh_build_args *args, nh_build_stats *stats) {
+    try {
+        return nh::build_check(args, stats);
+    } catch (const std::bad_alloc &) {
+        return nh::set_error(NH_EOOM, "nh_build_check: out of host memory");
+    } catch (const std::exception &e) {
+        return nh::set_error(NH_EIO, "nh_build_check: %s", e.what());
+    }
+}
 
 extern "C" int nh_build_db(const nh_build_args *args, nh_build_stats *stats) {
     try {

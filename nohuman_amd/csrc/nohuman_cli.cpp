@@ -225,7 +225,8 @@ struct Args {
     bool has_type = false;
     Codec type = C_NONE;
     // --build-db: make a database from FASTA instead of running on reads (nh_build_db)
-    std::string build_db, taxon_name;
+    std::string build_db, taxon_name, taxa;  // taxa: the manifest of a build of several taxa (nh_build_args.taxa_file)
+    bool has_taxa = false, has_taxid = false;
     bool has_build_db = false, has_taxon_name = false, has_build_opt = false, force = false, mask_low_complexity = false;
     std::vector<std::string> reference;
     unsigned long long taxid = 0, capacity = 0;
@@ -267,6 +268,8 @@ static void usage(FILE *f) {
           "      --reference <FILE>       FASTA file (plain or gzip) of the host genome for --build-db; may be given more than once\n"
           "      --taxid <INT>            Taxonomy id of the host for --build-db [default: 9606]\n"
           "      --taxon-name <NAME>      Name of the host in the database's taxonomy for --build-db\n"
+          "      --taxa <FILE>            Build a database of several taxa from a manifest, one taxon per line, tab-separated: taxid, parent taxid (1 is the root), name, "
+          "FASTA files; a minimizer shared by two taxa is stored as their lowest common ancestor\n"
           "      --load-factor <FLOAT>    Load factor of the hash table for --build-db, in (0, 0.95] [default: 0.7]\n"
           "      --capacity <INT>         Cells of the hash table for --build-db; skips the counting pass [default: distinct minimizers / load factor]\n"
           "      --force                  Let --build-db replace a database that DIR already holds\n"
@@ -361,6 +364,7 @@ static Args parse_args(int argc, char **argv) {
             if (*end || t.empty() || t[0] == '-' || errno || (s == "--taxid" && n == 0) || (s == "--capacity" && n == 0))
                 arg_error("invalid value '%s' for '%s <INT>': a positive integer is expected", t.c_str(), s.c_str());
             (s == "--taxid" ? a.taxid : a.capacity) = n;
+            if (s == "--taxid") a.has_taxid = true;
             a.has_build_opt = true;
         } else if (s == "--taxon-name") { a.taxon_name = val(); a.has_taxon_name = a.has_build_opt = true; }
         else if (s == "--load-factor") {
@@ -372,6 +376,7 @@ static Args parse_args(int argc, char **argv) {
             a.has_build_opt = true;
         } else if (s == "--force") a.force = a.has_build_opt = true;
         else if (s == "--mask-low-complexity") a.mask_low_complexity = true;
+        else if (s == "--taxa") { a.taxa = val(); a.has_taxa = true; }
         else if (s == "-v" || s == "--verbose") g_verbose = true;
         else if (s == "-h" || s == "--help") { usage(stdout); exit(0); }
         else if (s == "-V" || s == "--version") { puts("nohuman 0.5.1 (MI355X engine)"); exit(0); }
@@ -382,7 +387,12 @@ static Args parse_args(int argc, char **argv) {
         }
     }
     if (a.has_build_db) {  // builds and exits: nothing of a run may come with it
-        if (a.reference.empty()) arg_error("the following required arguments were not provided:\n  --reference <FILE> (with '--build-db <DIR>')");
+        if (a.has_taxa) {
+            const char *with = !a.reference.empty() ? "--reference <FILE>" : a.has_taxid ? "--taxid <INT>" : a.has_taxon_name ? "--taxon-name <NAME>" : nullptr;
+            if (with) arg_error("the argument '--taxa <FILE>' cannot be used with '%s': the manifest gives the taxids, the names and the FASTA files", with);
+            if (!exists(a.taxa)) arg_error("invalid value '%s' for '--taxa <FILE>': %s does not exist", a.taxa.c_str(), quoted(a.taxa).c_str());
+        } else if (a.reference.empty())
+            arg_error("the following required arguments were not provided:\n  --reference <FILE> (with '--build-db <DIR>')");
         if (!a.input.empty()) arg_error("the argument '--build-db <DIR>' cannot be used with read inputs ('%s'): the genome is given with '--reference <FILE>'", a.input[0].c_str());
         const char *out_flag = a.has_out1 ? "--out1" : a.has_out2 ? "--out2" : a.has_human_out1 ? "--human-out1" : a.has_human_out2 ? "--human-out2"
                              : !a.kraken_output.empty() ? "--kraken-output" : !a.kraken_report.empty() ? "--kraken-report" : !a.calls.empty() ? "--calls"
@@ -395,6 +405,7 @@ static Args parse_args(int argc, char **argv) {
     }
     if (a.mask_low_complexity) arg_error("the argument '--mask-low-complexity' needs '--build-db <DIR>': it masks the genome a database is built from, not reads");
     if (!a.reference.empty()) arg_error("the argument '--reference <FILE>' needs '--build-db <DIR>'");
+    if (a.has_taxa) arg_error("the argument '--taxa <FILE>' needs '--build-db <DIR>'");
     if (a.has_build_opt) arg_error("the arguments '--taxid', '--taxon-name', '--load-factor', '--capacity' and '--force' need '--build-db <DIR>'");
     if (a.input.empty() && !a.check && !a.download && !a.list)
         arg_error("the following required arguments were not provided:\n  <INPUT>...");
@@ -450,8 +461,58 @@ static std::string default_out_name(const std::string &in, Codec out_codec) {
     return add_extension(out_codec, join(parent_of(in), stem + ".nohuman.fq"));
 }
 
+// the names of a database's nodes from the root on, read from its taxo.k2d ("K2TAXDAT", node count, bytes of names and of ranks,
+// 56-byte nodes with the name's offset as their fourth word, the names)
+static std::vector<std::string> node_names(const std::string &db_dir) {
+    std::vector<std::string> out;
+    FILE *f = fopen(join(db_dir, "taxo.k2d").c_str(), "rb");
+    if (!f) return out;
+    std::string img;
+    char buf[1 << 16];
+    size_t n;
+    while ((n = fread(buf, 1, sizeof buf, f)) > 0) img.append(buf, n);
+    fclose(f);
+    uint64_t hdr[3];
+    if (img.size() < 32 || memcmp(img.data(), "K2TAXDAT", 8) != 0) return out;
+    memcpy(hdr, img.data() + 8, 24);
+    if (hdr[0] > (1u << 20) || hdr[1] > img.size() || 32 + hdr[0] * 56 + hdr[1] > img.size()) return out;
+    const char *names = img.data() + 32 + hdr[0] * 56;
+    for (uint64_t i = 1; i < hdr[0]; i++) {
+        uint64_t off;
+        memcpy(&off, img.data() + 32 + i * 56 + 24, 8);
+        out.push_back(off < hdr[1] ? std::string(names + off, strnlen(names + off, hdr[1] - off)) : std::string("?"));
+    }
+    return out;
+}
+
+static void fill_build_args(const Args &args, std::vector<const char *> &refs, nh_build_args &ba) {
+    for (const std::string &r : args.reference) refs.push_back(r.c_str());
+    memset(&ba, 0, sizeof ba);
+    ba.struct_size = (uint32_t)sizeof ba;
+    ba.n_fasta = (uint32_t)refs.size();
+    ba.fasta = refs.empty() ? nullptr : refs.data();
+    ba.out_dir = args.build_db.c_str();
+    ba.taxid = args.taxid;
+    ba.taxon_name = args.has_taxon_name ? args.taxon_name.c_str() : nullptr;
+    ba.load_factor = args.load_factor;
+    ba.capacity = args.capacity;
+    ba.threads = args.threads;
+    ba.force = args.force ? 1 : 0;
+    ba.mask_low_complexity = args.mask_low_complexity ? 1 : 0;
+    ba.taxa_file = args.has_taxa ? args.taxa.c_str() : nullptr;
+    if (const char *dv = getenv("NOHUMAN_DEVICES")) ba.device = (int32_t)strtol(dv, nullptr, 10);  // (one device: the first listed)
+}
+
 int main(int argc, char **argv) {
     Args args = parse_args(argc, argv);
+    if (args.has_build_db && args.has_taxa) {  // what the manifest says wrongly is an argument error too: read before any device is asked for
+        std::vector<const char *> refs;
+        nh_build_args ba;
+        fill_build_args(args, refs, ba);
+        const int rc = nh_build_check(&ba, nullptr);
+        if (rc == NH_EINVAL) arg_error("invalid value '%s' for '--taxa <FILE>': %s", args.taxa.c_str(), nh_last_error());
+        if (rc != 0) die("Failed to build the database\n\nCaused by:\n    %s", nh_last_error());
+    }
     if (args.bgzf && !args.input.empty()) {  // BGZF is a form of gzip: any other resolved output format is an argument error
         const Codec c = args.has_type ? args.type : args.has_out1 ? codec_from_path(args.out1) : codec_from_magic(args.input[0]);
         if (c != C_GZ)
@@ -488,21 +549,11 @@ int main(int argc, char **argv) {
     if (args.has_build_db) {
         INFO("Building database in %s...", quoted(args.build_db).c_str());
         std::vector<const char *> refs;
-        for (const std::string &r : args.reference) refs.push_back(r.c_str());
         nh_build_args ba;
-        memset(&ba, 0, sizeof ba);
-        ba.struct_size = (uint32_t)sizeof ba;
-        ba.n_fasta = (uint32_t)refs.size();
-        ba.fasta = refs.data();
-        ba.out_dir = args.build_db.c_str();
-        ba.taxid = args.taxid;
-        ba.taxon_name = args.has_taxon_name ? args.taxon_name.c_str() : nullptr;
-        ba.load_factor = args.load_factor;
-        ba.capacity = args.capacity;
-        ba.threads = args.threads;
-        ba.force = args.force ? 1 : 0;
-        ba.mask_low_complexity = args.mask_low_complexity ? 1 : 0;
-        if (const char *dv = getenv("NOHUMAN_DEVICES")) ba.device = (int32_t)strtol(dv, nullptr, 10);  // (one device: the first listed)
+        fill_build_args(args, refs, ba);
+        std::vector<nh_build_taxon_stats> per_taxon(4096);
+        ba.taxon_stats = per_taxon.data();
+        ba.taxon_stats_cap = (uint32_t)per_taxon.size();
         nh_build_stats bs;
         if (nh_build_db(&ba, &bs) != 0) die("Failed to build the database\n\nCaused by:\n    %s", nh_last_error());
         char masked[128] = "";
@@ -514,6 +565,13 @@ int main(int argc, char **argv) {
              (unsigned long long)bs.sequences, (unsigned long long)bs.bases, (unsigned long long)bs.distinct_minimizers,
              (unsigned long long)bs.capacity, (unsigned long long)bs.size, bs.capacity ? (double)bs.size / (double)bs.capacity : 0.0, bs.seconds_read,
              bs.seconds_count, bs.seconds_insert, bs.seconds_write, masked);
+        const std::vector<std::string> taxon_names = args.has_taxa ? node_names(args.build_db) : std::vector<std::string>();
+        if (args.has_taxa)
+            for (uint64_t i = 0; i < bs.taxa && i < per_taxon.size(); i++) {
+                const nh_build_taxon_stats &t = per_taxon[i];
+                INFO("  %s (taxid %llu): %llu sequences, %llu bases, %llu cells", taxon_names.size() > i ? taxon_names[i].c_str() : "?",
+                     (unsigned long long)t.taxid, (unsigned long long)t.sequences, (unsigned long long)t.bases, (unsigned long long)t.cells);
+            }
         INFO("Database written to: %s", quoted(args.build_db).c_str());
         INFO("Done.");
         return 0;

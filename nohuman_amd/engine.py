@@ -146,27 +146,41 @@ def _read_stats(v) -> "ReadStats":
     return v if isinstance(v, ReadStats) else ReadStats(v)
 
 
-def build_db(fasta_paths, out_dir, *, taxid: int = 0, taxon_name=None, load_factor: float = 0.0, capacity: int = 0,
+MAX_TAXA_NODES = 4096  # nodes of a taxa manifest with the root (include/nohuman_engine.h)
+
+
+def build_db(fasta_paths=None, out_dir=None, *, taxid: int = 0, taxon_name=None, load_factor: float = 0.0, capacity: int = 0,
              piece_kmers: int = 0, device: int = 0, threads: int = 1, force: bool = False,
-             mask_low_complexity: bool = False) -> dict:
+             mask_low_complexity: bool = False, taxa=None) -> dict:
     """nh_build_db: a kraken2 database directory (hash.k2d, opts.k2d, taxo.k2d) built on the GPU from FASTA files (plain or
-    gzip, wrapped lines, any number of records; one path or a list).  One taxon (taxid, 0 = 9606; taxon_name), the default
-    geometry (k = 35, l = 31) only.  load_factor 0 = 0.7; capacity 0 = ceil(distinct minimizers / load_factor), counted on the
-    device -- a capacity given is used as it is and the counting pass skipped; piece_kmers: k-mers per piece a wave scans (0 =
-    default); force: replace a database already in out_dir; mask_low_complexity: mask low-complexity sequence on the GPU before
-    the minimizers are taken (symmetric DUST, window 64, threshold 2.0 -- what kraken2-build's dustmasker step is for; see
-    dust_mask).  Returns nh_build_stats as a dict (sequences, bases, kmers, ambiguous_kmers, distinct_minimizers, capacity,
-    size, seconds_read / _count / _insert / _write, masked_bases, seconds_mask); Engine.open(out_dir) and run(out_dir, ...) work
-    on the result."""
+    gzip, wrapped lines, any number of records; one path or a list).  One taxon (taxid, 0 = 9606; taxon_name), or several:
+    taxa is the path of a manifest with a line `taxid <TAB> parent taxid <TAB> name [<TAB> FASTA path]...` per taxon (parent 1
+    is the root; the library parses it), and excludes fasta_paths, taxid and taxon_name -- a minimizer found in two taxa is
+    stored as their lowest common ancestor.  The default geometry (k = 35, l = 31) only.  load_factor 0 = 0.7; capacity 0 =
+    ceil(distinct minimizers / load_factor), counted on the device -- a capacity given is used as it is and the counting pass
+    skipped; piece_kmers: k-mers per piece a wave scans (0 = default); force: replace a database already in out_dir;
+    mask_low_complexity: mask low-complexity sequence on the GPU before the minimizers are taken (symmetric DUST, window 64,
+    threshold 2.0 -- what kraken2-build's dustmasker step is for; see dust_mask).  Returns nh_build_stats as a dict
+    (sequences, bases, kmers, ambiguous_kmers, distinct_minimizers, capacity, size, seconds_read / _count / _insert / _write,
+    masked_bases, seconds_mask, taxa) with taxon_stats, a list of dicts (taxid, sequences, bases, kmers, cells), one a node
+    in internal-id order from the root on; Engine.open(out_dir) and run(out_dir, ...) work on the result."""
+    if fasta_paths is None:  # (the library refuses taxa together with fasta_paths, taxid or taxon_name, and neither of them)
+        fasta_paths = []
     if isinstance(fasta_paths, (str, bytes, os.PathLike)):
         fasta_paths = [fasta_paths]
     paths = [os.fsencode(p) for p in fasta_paths]
-    a = _lib.nh_build_args_v2()
-    a.struct_size = C.sizeof(_lib.nh_build_args_v2)
+    a = _lib.nh_build_args_v3()
+    a.struct_size = C.sizeof(_lib.nh_build_args_v3)
     a.mask_low_complexity = int(bool(mask_low_complexity))
     a.n_fasta = len(paths)
     arr = (C.c_char_p * max(len(paths), 1))(*paths)
-    a.fasta = arr
+    if paths or taxa is None:
+        a.fasta = arr
+    if taxa is not None:
+        a.taxa_file = os.fsencode(taxa)
+    per_node = (_lib.nh_build_taxon_stats * MAX_TAXA_NODES)()
+    a.taxon_stats = per_node
+    a.taxon_stats_cap = MAX_TAXA_NODES
     a.out_dir = os.fsencode(out_dir) if out_dir is not None else None
     a.taxid = int(taxid)
     a.taxon_name = taxon_name.encode() if isinstance(taxon_name, str) else taxon_name
@@ -176,9 +190,12 @@ def build_db(fasta_paths, out_dir, *, taxid: int = 0, taxon_name=None, load_fact
     a.device = int(device)
     a.threads = int(threads)
     a.force = int(bool(force))
-    s = _lib.nh_build_stats_v2()
+    s = _lib.nh_build_stats_v3()
     _check(_lib.lib().nh_build_db(C.byref(a), C.byref(s)))
-    return {name: getattr(s, name) for name, _ in _lib.nh_build_stats._fields_ + _lib.nh_build_stats_v2._fields_}
+    out = {name: getattr(s, name) for name, _ in _lib.nh_build_stats._fields_ + _lib.nh_build_stats_v2._fields_ + _lib.nh_build_stats_v3._fields_}
+    out["taxon_stats"] = [{name: getattr(per_node[i], name) for name, _ in _lib.nh_build_taxon_stats._fields_}
+                          for i in range(min(int(s.taxa), MAX_TAXA_NODES))]
+    return out
 
 
 def dust_mask(seqs, device: int = 0):

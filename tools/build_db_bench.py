@@ -18,6 +18,12 @@ the call, which ends in a device synchronise.
 kernel's time over both passes (HIP events) join each build's numbers.  The mask's work does not depend on the content, but what it
 masks does: --low-complexity-share F plants homopolymers and microsatellites (periods 2 to 6, 20 to 400 bases each) over about that
 share of the genome, which as iid ACGT masks some 0.1 %.
+
+--taxa N --shared F splits the genome over N taxa under the root, a FASTA file each: every file holds bases / N bases, of which the
+share F is one stretch that all the files have and the rest the taxon's own.  The files are first built as ONE taxon (all of them
+under one taxid: the same bases, the one-taxon insert kernel), then through a manifest; both in this process, `--runs` times each.
+From the trace lines: the insert kernel's time of either build, the time of the kernel that counts the cells per node, and the
+share of the insertions that found their key under another taxon's value (the LCA path) with the values they replaced.
 """
 import argparse
 import json
@@ -35,6 +41,7 @@ sys.path.insert(0, ROOT)
 
 TRACE = re.compile(r"kernels alone: count ([0-9.]+) s, insert ([0-9.]+) s")
 TRACE_MASK = re.compile(r"mask ([0-9.]+) s for ([0-9]+) masked bases")
+TRACE_TAXA = re.compile(r"insertions ([0-9]+), of them ([0-9]+) found .* values replaced ([0-9]+); cells per node ([0-9.]+) s")
 PIECE = 1984  # the library's default piece: 16 tiles of 124 k-mers
 
 
@@ -77,6 +84,25 @@ def write_fasta(path, g, cuts, width=60):
     return os.path.getsize(path)
 
 
+def write_taxa(work, g, n_taxa, shared):
+    """the genome over n_taxa FASTA files of g.size / n_taxa bases each, the first `shared` of every file the same stretch (the
+    genome's first bases), and their manifest: leaves under the root -> (the files, the manifest's path)"""
+    per = g.size // n_taxa
+    n_shared = int(per * shared)
+    own = per - n_shared
+    files, lines = [], []
+    for i in range(n_taxa):
+        p = os.path.join(work, "taxon%d.fa" % i)
+        part = np.concatenate([g[:n_shared], g[n_shared + i * own:n_shared + (i + 1) * own]])
+        write_fasta(p, part, np.linspace(0, part.size, 3).astype(np.int64))
+        files.append(p)
+        lines.append("%d\t1\ttaxon %d\t%s\n" % (100 + i, i, p))
+    manifest = os.path.join(work, "taxa.tsv")
+    with open(manifest, "w") as f:
+        f.writelines(lines)
+    return files, manifest
+
+
 def traced(fn, errf):
     """fn() with the library's stderr (fd 2) in a file: the trace line"""
     saved = os.dup(2)
@@ -104,6 +130,8 @@ def main():
     ap.add_argument("--low-complexity-share", type=float, default=0.0, metavar="F",
                     help="plant homopolymers and microsatellites over about this share of the genome")
     ap.add_argument("--no-baseline", action="store_true", help="leave out the k_insert_sequences baseline")
+    ap.add_argument("--taxa", type=int, default=0, metavar="N", help="split the genome over N taxa and build it through a manifest too")
+    ap.add_argument("--shared", type=float, default=0.0, metavar="FRACTION", help="with --taxa: the share of every taxon's bases that all taxa have")
     a = ap.parse_args()
 
     import torch
@@ -123,17 +151,38 @@ def main():
         res["fasta_bytes"] = write_fasta(fa, g, cuts)
         res["generate_s"] = round(time.time() - t0, 2)
         os.environ["NOHUMAN_TRACE"] = "1"
-        builds = []
-        for r in range(a.runs):
+        inputs, manifest = [fa], None
+        if a.taxa:
+            inputs, manifest = write_taxa(work, g, a.taxa, a.shared)
+            os.unlink(fa)
+            res["taxa"], res["shared"] = a.taxa, a.shared
+        builds, taxa_builds = [], []
+        for r in range(a.runs * (2 if a.taxa else 1)):
+            by_manifest = r >= a.runs
             d = os.path.join(work, "db%d" % r)
             errf = os.path.join(work, "trace%d.txt" % r)
             t0 = time.time()
             kw = {"mask_low_complexity": True} if a.mask_low_complexity else {}
-            st = traced(lambda: nohuman_amd.build_db([fa], d, threads=a.threads, **kw), errf)
+            if by_manifest:
+                st = traced(lambda: nohuman_amd.build_db(None, d, taxa=manifest, threads=a.threads, **kw), errf)
+            else:
+                st = traced(lambda: nohuman_amd.build_db(inputs, d, threads=a.threads, **kw), errf)
             wall = time.time() - t0
             trace = open(errf, errors="replace").read()
             m = TRACE.search(trace)
-            b = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in st.items()}
+            b = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in st.items() if k != "taxon_stats"}
+            if by_manifest:
+                mt = TRACE_TAXA.search(trace)
+                b["cells_per_taxon"] = [x["cells"] for x in st["taxon_stats"]]
+                if mt:
+                    b["insertions"], b["lca_path"], b["values_replaced"] = (int(mt.group(i)) for i in (1, 2, 3))
+                    b["value_cells_kernel_s"] = float(mt.group(4))
+                    b["lca_share"] = round(b["lca_path"] / max(1, b["insertions"]), 5)
+                b["wall_s"] = round(wall, 3)
+                b["count_kernel_s"], b["insert_kernel_s"] = (float(m.group(1)), float(m.group(2))) if m else (None, None)
+                taxa_builds.append(b)
+                shutil.rmtree(d)
+                continue
             b["wall_s"] = round(wall, 3)
             b["count_kernel_s"], b["insert_kernel_s"] = (float(m.group(1)), float(m.group(2))) if m else (None, None)
             mm = TRACE_MASK.search(trace)
@@ -144,6 +193,11 @@ def main():
             if r + 1 < a.runs:
                 shutil.rmtree(d)
         res["builds"] = builds
+        if taxa_builds:
+            res["taxa_builds"] = taxa_builds
+            one, many = builds[-1]["insert_kernel_s"], taxa_builds[-1]["insert_kernel_s"]
+            if one and many:
+                res["taxa_insert_kernel_ratio"] = round(many / one, 3)
         last = builds[-1]
         cap, size = last["capacity"], last["size"]
         res["load_factor"] = round(size / cap, 4)
@@ -159,7 +213,7 @@ def main():
         with nohuman_amd.Engine.open(os.path.join(work, "db%d" % (a.runs - 1))) as eng:
             assert eng.db_check().non_empty_cells == size
 
-        if not a.no_baseline:
+        if not a.no_baseline and not a.taxa:
             # ---- baseline: k_insert_sequences on the same bases, resident, contiguous sequences of one piece each
             os.environ["NOHUMAN_TABLE_COPIES"] = "1"
             dev = torch.device("cuda:0")
