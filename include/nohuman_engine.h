@@ -441,6 +441,34 @@ int nh_run_engine_rstats(nh_engine *e, const nh_run_args *args, const nh_run_ext
 int nh_read_stats_write(const nh_read_stats *stats, const char *path);
 
 /*
+ * Per-taxon outputs (--taxon-out): nh_run_rstats that also sorts the classified records by clade, in the same pass.  Up to
+ * NH_MAX_TAXON_OUTS selectors, each a taxid of the database's taxonomy or NH_TAXON_OTHER, each with a file per mate.  A classified
+ * fragment goes to exactly one selector: the deepest selected taxon that is its call or an ancestor of its call; where none is, to
+ * NH_TAXON_OTHER if that was given, else to no per-taxon file.  Unclassified fragments go to none.  The record written is byte for
+ * byte the one nh_run writes with keep_human = 1 (" kraken:taxid|<id>" suffix, normalised), in input order within each file, in the
+ * run's out_codec; a selector without reads gets an empty file of that codec.  `fragments` receives the selector's fragments.
+ * Every other output and the stats are exactly those of nh_run_rstats with the same arguments; n_outs == 0 IS nh_run_rstats.
+ * The records are sorted in the GPU's memory (nh_split.hip, k_tout_*): one more copy of the classified text per batch in HBM,
+ * whatever the number of selectors.  Taxid 1 (the root) is a selector like any other: everything not selected deeper.
+ * NH_EINVAL, before any device is touched and with no file created: n_outs above NH_MAX_TAXON_OUTS; outs NULL with n_outs > 0; a
+ * taxid given twice; out1 NULL or empty; out2 given without in2 or missing with in2; keep_human set; a path that names an input (the
+ * same path, or the same device and inode), out1, out2, a human output, kraken_output, report, calls, human_ids, the read statistics
+ * table or another per-taxon file; every check of nh_run_rstats.  A taxid that the opened database's taxonomy does not hold:
+ * NH_EINVAL with the taxid in the message, once the database is open, before any input is read or any output created.
+ */
+#define NH_MAX_TAXON_OUTS 8
+#define NH_TAXON_OTHER 0u /* selector: classified, in no other selector's clade */
+typedef struct {
+    uint64_t taxid;          /* external (NCBI) id, or NH_TAXON_OTHER */
+    const char *out1, *out2; /* out2: the second mate's file, NULL for single-end input */
+    uint64_t fragments;      /* out: fragments written to this selector */
+} nh_taxon_out;
+int nh_run_taxa(const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality, const char *read_stats_path,
+                nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs, nh_stats *stats);
+int nh_run_engine_taxa(nh_engine *e, const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality,
+                       const char *read_stats_path, nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs, nh_stats *stats);
+
+/*
  * Database builder (--build-db; nohuman_amd/csrc/nh_build.hip): FASTA in, a kraken2 database directory out (hash.k2d, opts.k2d,
  * taxo.k2d), built on the GPU.  What kraken2-build does for ONE taxon at the default geometry, and nothing more: k = 35, l = 31,
  * the default spaced-seed and toggle masks, revcom_version 1, dna_db 1, minimum_acceptable_hash_value 0, linear probing -- the

@@ -66,6 +66,14 @@ class nh_read_stats(C.Structure):
                 ("mates", C.c_int32), ("reserved", C.c_int32)]
 
 
+NH_MAX_TAXON_OUTS = 8
+NH_TAXON_OTHER = 0
+
+
+class nh_taxon_out(C.Structure):
+    _fields_ = [("taxid", C.c_uint64), ("out1", C.c_char_p), ("out2", C.c_char_p), ("fragments", C.c_uint64)]
+
+
 class nh_build_args(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_fasta", C.c_uint32), ("fasta", C.POINTER(C.c_char_p)),
                 ("out_dir", C.c_char_p), ("taxid", C.c_uint64), ("taxon_name", C.c_char_p), ("load_factor", C.c_double),
@@ -161,6 +169,10 @@ SYMBOLS = {
                                 C.POINTER(nh_read_stats), C.POINTER(nh_stats)]),
     "nh_run_engine_rstats": (C.c_int, [_P, C.POINTER(nh_run_args), C.POINTER(nh_run_extras), C.c_uint32, C.c_char_p,
                                        C.POINTER(nh_read_stats), C.POINTER(nh_stats)]),
+    "nh_run_taxa": (C.c_int, [C.POINTER(nh_run_args), C.POINTER(nh_run_extras), C.c_uint32, C.c_char_p,
+                              C.POINTER(nh_read_stats), C.POINTER(nh_taxon_out), C.c_uint32, C.POINTER(nh_stats)]),
+    "nh_run_engine_taxa": (C.c_int, [_P, C.POINTER(nh_run_args), C.POINTER(nh_run_extras), C.c_uint32, C.c_char_p,
+                                     C.POINTER(nh_read_stats), C.POINTER(nh_taxon_out), C.c_uint32, C.POINTER(nh_stats)]),
     "nh_read_stats_write": (C.c_int, [C.POINTER(nh_read_stats), C.c_char_p]),
     "nh_build_db": (C.c_int, [C.POINTER(nh_build_args), C.POINTER(nh_build_stats)]),  # (or their _v2 / _v3 subclasses)
     "nh_build_check": (C.c_int, [C.POINTER(nh_build_args), C.POINTER(nh_build_stats)]),

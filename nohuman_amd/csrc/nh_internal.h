@@ -145,6 +145,15 @@ struct HumanOutArgs {
 };
 uint64_t human_out_blocks(uint64_t n);
 hipError_t launch_human_out(const HumanOutArgs &a, hipStream_t stream);
+// The same records sorted into K bins by the taxon of the call (nh_split.hip, k_tout_*; nh_run_taxa's per-taxon outputs): out[m]
+// is mate m's ONE buffer, bin k of it the region [start[m * K + k], + total[m * K + k]), every start a multiple of 256; a fragment
+// whose call has bin_of 0xFF is written nowhere.  Records in input order inside each bin.
+struct TaxonOutArgs : HumanOutArgs {  // blk: 2 * K * nblk words of scratch; total: 2 * K words
+    const uint8_t *bin_of;    // n_ext bytes: internal taxon id -> bin, 0xFF = none
+    int K;                    // bins, 1 .. NH_MAX_TAXON_OUTS
+    uint64_t *start;          // 2 * K words; error: bit 64 (a record outside its text or buffer, a bin index >= K)
+};
+hipError_t launch_taxon_out(const TaxonOutArgs &a, hipStream_t stream);
 // The masked records of one batch built in HBM (nh_mask.hip; nh_run_mask's outputs): out[m] receives mate m's record of every
 // fragment, in order, the sequence of a classified fragment as 'N'; total[m] their bytes.
 struct MaskArgs {

@@ -365,6 +365,7 @@ struct Slot {  // pinned host + device buffers of one in-flight batch
     BuiltOut human;  // split runs (nh_run_split): the classified-out records per mate; totals: bytes[2]
     BuiltOut mask;   // masked runs (nh_run_mask): every record per mate; totals: bytes[2], FAST blocks[2]
     BuiltOut lists;  // read lists (nh_run_ex): the calls table [0] and the human ids [1]; totals: bytes[2], lines[2]
+    BuiltOut taxon;  // per-taxon outputs (nh_run_taxa): one buffer a mate, K bins in it; totals: start[2][K], bytes[2][K]
     // runs with a minimum base quality (nh_run_minq): the text-sized buffer the classifier reads instead of d_text -- the
     // sequences with 'N' where the quality is low (nh_qmask.hip; the record table tells where the qualities lie) -- allocated
     // when first needed, and the masked bases of the slot's batches, read once, at the end of the run
@@ -496,7 +497,7 @@ static int slot_reserve_qmask(Slot &s, size_t ntext, size_t nrec) {
 static void slot_free(Slot &s) {
     if (!s.e) return;
     (void)dev_set(s.e->device);
-    for (BuiltOut *o : {&s.human, &s.mask, &s.lists}) {
+    for (BuiltOut *o : {&s.human, &s.mask, &s.lists, &s.taxon}) {
         for (void *p : {(void *)o->h_out[0], (void *)o->h_out[1], (void *)o->h_total})
             if (p) (void)hipHostFree(p);
         for (void *p : {o->d_blk, (void *)o->d_out[0], (void *)o->d_out[1]})
@@ -602,6 +603,10 @@ struct RunState {
     // read lists (NOHUMAN_TRACE): lines and bytes of the calls table [0] and the human ids [1], the builder's kernel time
     uint64_t list_lines[2] = {0, 0}, list_bytes[2] = {0, 0};
     double list_kernel_ms = 0;
+    // per-taxon outputs: the fragments of every selector (nh_taxon_out.fragments); NOHUMAN_TRACE: the bytes the binned builder
+    // made, its kernel time
+    uint64_t taxon_frags[NH_MAX_TAXON_OUTS] = {}, taxon_records = 0, taxon_bytes = 0;
+    double taxon_kernel_ms = 0;
     // runs with a minimum base quality (NOHUMAN_TRACE): the bases k_qmask replaced, its kernel time
     uint64_t qmask_masked = 0;
     double qmask_kernel_ms = 0;
@@ -1058,21 +1063,69 @@ static int check_rstats_args(const nh_run_args *a, const nh_run_extras *x, const
     return NH_OK;
 }
 
+// nh_run_taxa's selectors, checked before any device is touched: their number, their taxids, their files -- a per-taxon file
+// names no input and no other output of the run (the same path, or the same device and inode)
+static int check_taxon_args(const nh_run_args *a, const nh_run_extras *x, const char *rs_path, const nh_taxon_out *outs, uint32_t n) {
+    if (n == 0) return NH_OK;
+    if (!a) return set_error(NH_EINVAL, "nh_run_taxa: null arguments");
+    if (n > NH_MAX_TAXON_OUTS) return set_error(NH_EINVAL, "nh_run_taxa: n_outs %u is above NH_MAX_TAXON_OUTS (%d)", n, NH_MAX_TAXON_OUTS);
+    if (!outs) return set_error(NH_EINVAL, "nh_run_taxa: outs is NULL with n_outs %u", n);
+    if (a->keep_human != 0) return set_error(NH_EINVAL, "nh_run_taxa: keep_human must be 0 (the classified reads go to the selectors' files)");
+    for (uint32_t i = 0; i < n; i++) {
+        const nh_taxon_out &t = outs[i];
+        if (!t.out1 || !t.out1[0]) return set_error(NH_EINVAL, "nh_run_taxa: outs[%u].out1 is required", i);
+        if (t.out2 && !t.out2[0]) return set_error(NH_EINVAL, "nh_run_taxa: outs[%u].out2 is an empty path", i);
+        if (a->in2 && !t.out2) return set_error(NH_EINVAL, "nh_run_taxa: paired input needs outs[%u].out2", i);
+        if (!a->in2 && t.out2) return set_error(NH_EINVAL, "nh_run_taxa: outs[%u].out2 is given without in2", i);
+        for (uint32_t j = 0; j < i; j++)
+            if (outs[j].taxid == t.taxid) {
+                if (t.taxid == NH_TAXON_OTHER) return set_error(NH_EINVAL, "nh_run_taxa: outs[%u].taxid: `other` is given twice", i);
+                return set_error(NH_EINVAL, "nh_run_taxa: outs[%u].taxid %llu is given twice", i, (unsigned long long)t.taxid);
+            }
+    }
+    for (uint32_t i = 0; i < n; i++)
+        for (int m = 0; m < 2; m++) {
+            const char *l = m ? outs[i].out2 : outs[i].out1;
+            if (!l) continue;
+            struct stat sl;
+            const bool ls = stat(l, &sl) == 0 && S_ISREG(sl.st_mode);
+            auto same = [&](const char *p) {
+                struct stat sp;
+                return p && p[0] && (!strcmp(p, l) || (ls && stat(p, &sp) == 0 && sp.st_dev == sl.st_dev && sp.st_ino == sl.st_ino));
+            };
+            for (const char *p : {a->in1, a->in2})
+                if (same(p)) return set_error(NH_EINVAL, "nh_run_taxa: outs[%u].out%d %s is the input %s", i, m + 1, l, p);
+            for (const char *p : {a->out1, a->out2, a->kraken_output, a->report, x ? x->human_out1 : nullptr, x ? x->human_out2 : nullptr,
+                                  x ? x->calls : nullptr, x ? x->human_ids : nullptr, rs_path})
+                if (same(p)) return set_error(NH_EINVAL, "nh_run_taxa: outs[%u].out%d %s is also the output %s", i, m + 1, l, p);
+            for (uint32_t j = 0; j <= i; j++)
+                for (int mj = 0; mj < (j < i ? 2 : m); mj++)
+                    if (same(mj ? outs[j].out2 : outs[j].out1))
+                        return set_error(NH_EINVAL, "nh_run_taxa: outs[%u].out%d %s is also outs[%u].out%d", i, m + 1, l, j, mj + 1);
+        }
+    return NH_OK;
+}
+
 // hout1 set: a split run (nh_run_split) -- a->keep_human is 0, hout1 / hout2 receive the classified records
 // mask: a masked run (nh_run_mask) -- a->keep_human is 0, out1 / out2 receive every record, a classified one's bases as 'N'
 // calls / ids set (nh_run_ex): the calls table / the human read ids, built in HBM beside whatever else the run writes
 // minq > 0 (nh_run_minq): kraken2's --minimum-base-quality -- the classifier reads a copy of each batch's sequences in which the
 // bases of a FASTQ record with a quality below minq are 'N' (k_qmask, in front of it on the slot's stream); every output is made
 // from the batch's text as before, so the records written keep their bases.  0: nothing of this runs.
+// touts / n_touts (nh_run_taxa): per-taxon outputs -- k_tout_* behind the classifier on the slot's stream sort the classified
+// records of the batch into the selectors' bins (nh_split.hip), a span a bin and mate goes to the selector's file.  0: nothing runs.
 // rs_path / rs_out set (nh_run_rstats): read statistics -- k_rstats behind the classifier on the slot's stream adds every sequence
 // of the batch to the device's four accumulators (nh_rstats.hip), fetched once, at the end; the writer keeps the lengths by class
 // for median and N50.  Both NULL: nothing of this runs.
 int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_stats *stats, const char *hout1 = nullptr,
                 const char *hout2 = nullptr, bool mask = false, const char *calls = nullptr, const char *ids = nullptr,
-                uint32_t minq = 0, const char *rs_path = nullptr, nh_read_stats *rs_out = nullptr) {
+                uint32_t minq = 0, const char *rs_path = nullptr, nh_read_stats *rs_out = nullptr, nh_taxon_out *touts = nullptr,
+                uint32_t n_touts = 0) {
     if (!a || !a->in1 || !a->out1) return set_error(NH_EINVAL, "nh_run: in1 and out1 are required");
     if (engines.empty()) return set_error(NH_EINVAL, "nh_run: no engine");
     const bool split = hout1 != nullptr;
+    const int K = (int)n_touts;  // per-taxon outputs: the selectors
+    const bool taxa = K > 0;
     const bool lists = calls || ids;
     const bool qm = minq > 0;
     const bool rst = rs_path || rs_out;
@@ -1095,7 +1148,35 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
         const int vrc = check_split_args(a, hout1, hout2, mask ? "nh_run_mask" : "nh_run_split");
         if (vrc) return vrc;
     }
-    if (split || lists)
+    // per-taxon outputs: the bin of every node of the taxonomy -- its deepest selected ancestor-or-self, else `other`'s, else none
+    std::vector<uint8_t> bin_of;
+    if (taxa) {
+        nh_run_extras x{};
+        x.human_out1 = hout1, x.human_out2 = hout2, x.calls = calls, x.human_ids = ids;
+        const int vrc = check_taxon_args(a, &x, rs_path, touts, n_touts);
+        if (vrc) return vrc;
+        const Engine *e0 = engines[0];
+        const size_t nn = e0->external.size();
+        bin_of.assign(std::max<size_t>(nn, 1), 0xFF);
+        std::vector<int> own(nn, -1);
+        int other = -1;
+        for (int k = 0; k < K; k++) {
+            if (touts[k].taxid == NH_TAXON_OTHER) {
+                other = k;
+                continue;
+            }
+            size_t at = 0;
+            for (size_t i = 1; i < nn && !at; i++)
+                if (e0->external[i] == touts[k].taxid) at = i;
+            if (!at) return set_error(NH_EINVAL, "nh_run_taxa: taxid %llu is not in the database's taxonomy", (unsigned long long)touts[k].taxid);
+            own[at] = k;
+        }
+        for (size_t i = 1; i < nn; i++) {  // (parents have smaller ids than their children: nh_open checked)
+            const uint32_t p = e0->parent[i];
+            bin_of[i] = own[i] >= 0 ? (uint8_t)own[i] : (i > 1 && p >= 1 && p < i) ? bin_of[p] : other >= 0 ? (uint8_t)other : (uint8_t)0xFF;
+        }
+    }
+    if (split || lists || taxa)
         for (Engine *e : engines) {
             const int erc = ensure_device_external(e);
             if (erc) return erc;
@@ -1118,7 +1199,9 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
     }
     // outputs are created with O_TRUNC before the first input byte is read: an output that IS an input
     // (same device and inode) would be emptied -- refuse (the CLI host stages its outputs and renames)
-    for (const char *o : {a->out1, a->out2, rs.want_k ? a->kraken_output : nullptr, a->report, hout1, hout2, calls, ids}) {
+    std::vector<const char *> outputs{a->out1, a->out2, rs.want_k ? a->kraken_output : nullptr, a->report, hout1, hout2, calls, ids};
+    for (int k = 0; k < K; k++) outputs.push_back(touts[k].out1), outputs.push_back(touts[k].out2);
+    for (const char *o : outputs) {
         struct stat so;
         if (!o || !o[0] || stat(o, &so) != 0 || !S_ISREG(so.st_mode)) continue;
         for (const char *p : {a->in1, a->in2}) {
@@ -1166,6 +1249,12 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
         if (rch1) return set_error(rch1, "%s", errh1.c_str());
         if (rch2) return set_error(rch2, "%s", errh2.c_str());
     }
+    // the selectors' files, [mate][selector]: like the human outputs, mate 1's on the first device, mate 2's on the second
+    OutFile tx[2][NH_MAX_TAXON_OUTS];
+    for (int k = 0; k < K; k++)
+        for (int m = 0; m < (rs.paired ? 2 : 1); m++)
+            if ((rc = tx[m][k].open(m ? touts[k].out2 : touts[k].out1, a->out_codec, a->codec_threads, engines[m && engines.size() > 1 ? 1 : 0]->device)))
+                return rc;
     if (rs.want_k && (rc = ok.open(a->kraken_output))) return rc;
     OutFile oc, oi;  // the read lists: plain text whatever the codec of the records
     if (calls && (rc = oc.open(calls))) return rc;
@@ -1205,19 +1294,24 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
     // masked runs: the same for out1 / out2 -- one span a mate and batch, from HBM or copied to page-locked slot memory
     const bool mask_in_hbm = mask && G == 1 && o1.enc && o1.enc->takes_device_spans() &&
                              (!rs.paired || (o2.enc && o2.enc->takes_device_spans()));
+    bool taxon_in_hbm = taxa && G == 1;
+    for (int k = 0; k < K; k++)
+        for (int m = 0; m < mates; m++) taxon_in_hbm = taxon_in_hbm && tx[m][k].enc && tx[m][k].enc->takes_device_spans();
     auto t0 = std::chrono::steady_clock::now();
 
     rs.d_run_counters.assign((size_t)G, nullptr);
+    std::vector<uint8_t *> d_bin_of((size_t)G, nullptr);  // per device: bin_of in HBM for the run
     // read statistics: one block of four accumulators per device of the run, zeroed with min_len all-ones
     std::vector<unsigned long long *> d_racc((size_t)G, nullptr);
     std::vector<nh_read_class> racc;  // the devices' blocks summed: [class][mate]
     auto free_run_counters = [&] {
         for (int g = 0; g < G; g++) {
-            if (!rs.d_run_counters[g] && !d_racc[g]) continue;
+            if (!rs.d_run_counters[g] && !d_racc[g] && !d_bin_of[g]) continue;
             (void)dev_set(engines[g]->device);
             if (rs.d_run_counters[g]) (void)hipFree(rs.d_run_counters[g]);
             if (d_racc[g]) (void)hipFree(d_racc[g]);
-            rs.d_run_counters[g] = nullptr, d_racc[g] = nullptr;
+            if (d_bin_of[g]) (void)hipFree(d_bin_of[g]);
+            rs.d_run_counters[g] = nullptr, d_racc[g] = nullptr, d_bin_of[g] = nullptr;
         }
     };
     for (int g = 0; g < G; g++) {
@@ -1226,6 +1320,11 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
             hipMemset(rs.d_run_counters[g], 0, nb) != hipSuccess) {
             free_run_counters();
             return set_error(NH_EDEVICE, "cannot allocate the run's counters on device %d", engines[g]->device);
+        }
+        if (taxa && (dev_malloc((void **)&d_bin_of[g], bin_of.size()) != hipSuccess ||
+                     hipMemcpy(d_bin_of[g], bin_of.data(), bin_of.size(), hipMemcpyHostToDevice) != hipSuccess)) {
+            free_run_counters();
+            return set_error(NH_EDEVICE, "cannot copy the selectors' bins to device %d", engines[g]->device);
         }
         if (rst) {
             nh_read_class init[4];
@@ -1254,6 +1353,8 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
              (hipEventCreate(&slots[i].mask.ev[0]) != hipSuccess || hipEventCreate(&slots[i].mask.ev[1]) != hipSuccess)) ||
             (lists && getenv("NOHUMAN_TRACE") &&
              (hipEventCreate(&slots[i].lists.ev[0]) != hipSuccess || hipEventCreate(&slots[i].lists.ev[1]) != hipSuccess)) ||
+            (taxa && getenv("NOHUMAN_TRACE") &&
+             (hipEventCreate(&slots[i].taxon.ev[0]) != hipSuccess || hipEventCreate(&slots[i].taxon.ev[1]) != hipSuccess)) ||
             (qm && getenv("NOHUMAN_TRACE") &&
              (hipEventCreate(&slots[i].qev[0]) != hipSuccess || hipEventCreate(&slots[i].qev[1]) != hipSuccess)) ||
             (rst && getenv("NOHUMAN_TRACE") &&
@@ -1362,6 +1463,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
         Batch b;
         Spans s1, s2, sk, hs1, hs2;  // (hs1, hs2: a split run's classified records, one span a mate)
         Spans sc, si;                // (the batch's part of the calls table and of the human ids, one span each)
+        Spans ts[2][NH_MAX_TAXON_OUTS];  // (per-taxon outputs: a span a mate and selector with records in the batch)
         bool valid = false;  // (false: the run had failed when the batch arrived -- only its buffers go back)
     };
     BoundedQueue<Batch> wq((size_t)(NS * G));
@@ -1371,7 +1473,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
     std::mutex w2_mu;
     std::condition_variable w2_cv;
     int w2_state = 0;  // 0 idle, 1 flush requested, 2 done, -1 quit
-    Spans *w2_spans = nullptr, *w2_hspans = nullptr;
+    Spans *w2_spans = nullptr, *w2_hspans = nullptr, *w2_tspans = nullptr;
     int w2_rc = NH_OK;
     std::string w2_err;
     std::thread tw2;
@@ -1381,10 +1483,12 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 std::unique_lock<std::mutex> lk(w2_mu);
                 w2_cv.wait(lk, [&] { return w2_state == 1 || w2_state == -1; });
                 if (w2_state == -1) return;
-                Spans *sp2 = w2_spans, *hsp2 = w2_hspans;
+                Spans *sp2 = w2_spans, *hsp2 = w2_hspans, *tsp2 = w2_tspans;
                 lk.unlock();
                 int frc = o2.flush(*sp2);
                 if (!frc && hsp2) frc = h2.flush(*hsp2);
+                for (int k = 0; k < K && !frc; k++)
+                    if (!tsp2[k].iov.empty()) frc = tx[1][k].flush(tsp2[k]);
                 lk.lock();
                 w2_rc = frc;
                 if (frc) w2_err = g_last_error;
@@ -1419,16 +1523,25 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                         Spans &hs = m ? j->hs2 : j->hs1;
                         if (!hs.iov.empty()) (m ? h2 : h1).enc->map_device(hs.iov[0].iov_base, hs.iov[0].iov_len, s.human.d_out[m], s.e->device, false);
                     }
+                if (taxon_in_hbm)
+                    for (int m = 0; m < mates; m++)
+                        for (int k = 0; k < K; k++) {
+                            Spans &t = j->ts[m][k];
+                            if (!t.iov.empty()) tx[m][k].enc->map_device(t.iov[0].iov_base, t.iov[0].iov_len, t.iov[0].iov_base, s.e->device, false);
+                        }
                 if (rs.paired) {
                     std::lock_guard<std::mutex> lk(w2_mu);
                     w2_spans = &j->s2;
                     w2_hspans = split ? &j->hs2 : nullptr;
+                    w2_tspans = j->ts[1];
                     w2_state = 1;
                     w2_cv.notify_all();
                 }
                 int wrc = o1.flush(j->s1);
                 if (!wrc && rs.want_k) wrc = ok.flush(j->sk);
                 if (!wrc && split) wrc = h1.flush(j->hs1);
+                for (int k = 0; k < K && !wrc; k++)
+                    if (!j->ts[0][k].iov.empty()) wrc = tx[0][k].flush(j->ts[0][k]);
                 if (!wrc && calls) wrc = oc.flush(j->sc);
                 if (!wrc && ids) wrc = oi.flush(j->si);
                 if (rs.paired) {
@@ -1522,6 +1635,32 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                     }
                     if (split)
                         for (size_t i = 0; i < b.n; i++) rs.human_records += s.h_res[i].call != 0;
+                    // the per-taxon records: a mate's buffer with the bins in it -- in HBM, or copied here as far as the last bin
+                    // reaches -- and a span a bin that has bytes
+                    add_event_ms(s.taxon.ev, &rs.taxon_kernel_ms);
+                    for (int m = 0; taxa && m < mates && !wrc; m++) {
+                        const uint64_t *start = s.taxon.h_total + m * K, *bytes = s.taxon.h_total + 2 * K + m * K;
+                        size_t end = 0;
+                        for (int k = 0; k < K; k++)
+                            if (bytes[k]) end = (size_t)(start[k] + bytes[k]);
+                        if (!end) continue;
+                        if (end > s.taxon.cap_out[m]) {
+                            wrc = set_error(NH_EDEVICE, "per-taxon builder: a bin ends outside its buffer");
+                            break;
+                        }
+                        char *at = built_span(s.taxon, m, end, taxon_in_hbm, rs, &wrc, "per-taxon buffers", "per-taxon records");
+                        for (int k = 0; k < K; k++) {
+                            if (!bytes[k]) continue;
+                            rs.taxon_bytes += bytes[k];
+                            j->ts[m][k].iov.push_back({(void *)(at + start[k]), (size_t)bytes[k]});
+                            j->ts[m][k].is_scratch.push_back(0);
+                        }
+                    }
+                    for (size_t i = 0; taxa && i < b.n; i++) {
+                        const uint32_t call = s.h_res[i].call;
+                        const uint8_t bin = call && call < bin_of.size() ? bin_of[call] : 0xFF;
+                        if (bin < K) rs.taxon_frags[bin]++, rs.taxon_records++;
+                    }
                     add_event_ms(s.lists.ev, &rs.list_kernel_ms);
                     add_event_ms(s.qev, &rs.qmask_kernel_ms);
                     add_event_ms(s.rev, &rs.rstats_kernel_ms);
@@ -1669,6 +1808,14 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 rc = slot_reserve_rec(s, b.n * (size_t)mates);
                 if (!rc) rc = built_reserve(s.human, 2 * human_out_blocks(b.n) + 2, out_cap, mates, "classified-out buffers");
             }
+            if (!rc && taxa) {  // a mate's bins: the classified-out text at most, and the bins' alignment
+                const size_t out_cap[2] = {len1 + b.n * 36 + 64 + 256 * (size_t)K, len2 + b.n * 36 + 64 + 256 * (size_t)K};
+                rc = slot_reserve_rec(s, b.n * (size_t)mates);
+                if (!rc && !s.taxon.h_total && host_malloc((void **)&s.taxon.h_total, 4 * NH_MAX_TAXON_OUTS * sizeof(uint64_t), hipHostMallocDefault) != hipSuccess)
+                    rc = set_error(NH_EOOM, "cannot allocate batch buffers");
+                // (the scratch: block sums of every mate and bin, then start[2][K] and total[2][K]: TaxonOutArgs)
+                if (!rc) rc = built_reserve(s.taxon, 2 * (size_t)K * human_out_blocks(b.n) + 4 * (size_t)K, out_cap, mates, "per-taxon buffers");
+            }
             if (!rc && mask) {  // a mate's masked text: its records less what normalisation drops, plus a final newline each
                 const size_t out_cap[2] = {len1 + b.n + 64, len2 + b.n + 64};
                 rc = slot_reserve_rec(s, b.n * (size_t)mates);
@@ -1712,7 +1859,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 s.h_len[i * mates] = r1.slen;
                 nbases += r1.slen;
                 if (lists) s.h_idl[i] = r1.idlen;
-                if (split || mask || lists || qm || rst) {
+                if (split || mask || lists || qm || rst || taxa) {
                     uint32_t *hr = s.h_rec + 4 * i * mates;
                     hr[0] = r1.h, hr[1] = r1.hlen, hr[2] = r1.q, hr[3] = r1.qlen;
                     if (rs.paired) {
@@ -1766,7 +1913,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 he = hipMemcpyAsync(s.d_len, s.h_len, b.n * mates * 4, hipMemcpyHostToDevice, s.stream);
             if (he == hipSuccess && rs.want_k)
                 he = hipMemcpyAsync(s.d_taxa_off, s.h_taxa_off, (b.n + 1) * 8, hipMemcpyHostToDevice, s.stream);
-            if (he == hipSuccess && (split || mask || lists || qm || rst))
+            if (he == hipSuccess && (split || mask || lists || qm || rst || taxa))
                 he = hipMemcpyAsync(s.d_rec, s.h_rec, b.n * mates * 16, hipMemcpyHostToDevice, s.stream);
             if (he == hipSuccess && lists)
                 he = hipMemcpyAsync(s.d_idl, s.h_idl, b.n * 4, hipMemcpyHostToDevice, s.stream);
@@ -1867,6 +2014,33 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 if (s.human.ev[1] && he == hipSuccess) he = hipEventRecord(s.human.ev[1], s.stream);
                 if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("classified-out builder: ") + hipGetErrorString(he));
             }
+            if (!rs.failed() && taxa) {  // the classified records of both mates sorted into the selectors' bins, on the same stream
+                TaxonOutArgs ta{};
+                ta.text = (const char *)s.d_text;
+                ta.ntext = ntext;
+                ta.seq_off = (const uint64_t *)s.d_off;
+                ta.seq_len = (const uint32_t *)s.d_len;
+                ta.rec = (const uint32_t *)s.d_rec;
+                ta.res = (const nh_result *)s.d_res;
+                ta.ext = s.e->d_external;
+                ta.n_ext = s.e->external.size();
+                ta.n = b.n;
+                ta.nblk = human_out_blocks(b.n);
+                ta.mates = mates;
+                ta.fastq[0] = b.h1->format == FMT_FASTQ;
+                ta.fastq[1] = rs.paired && b.h2->format == FMT_FASTQ;
+                for (int m = 0; m < mates; m++) ta.out[m] = s.taxon.d_out[m], ta.cap[m] = s.taxon.cap_out[m];
+                ta.blk = (uint64_t *)s.taxon.d_blk;
+                ta.bin_of = d_bin_of[(size_t)(si / NS)];
+                ta.K = K;
+                ta.start = s.taxon.d_total = ta.blk + 2 * (uint64_t)K * ta.nblk;
+                ta.total = ta.start + 2 * K;
+                ta.error = s.e->d_error + LAUNCH_SLOTS;
+                if (s.taxon.ev[0]) (void)hipEventRecord(s.taxon.ev[0], s.stream);
+                he = launch_taxon_out(ta, s.stream);
+                if (s.taxon.ev[1] && he == hipSuccess) he = hipEventRecord(s.taxon.ev[1], s.stream);
+                if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("per-taxon builder: ") + hipGetErrorString(he));
+            }
             if (!rs.failed() && mask) {  // every record of both mates, masked, built behind the classifier on the same stream
                 MaskArgs ma{};
                 ma.text = (const char *)s.d_text;
@@ -1898,6 +2072,8 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                     he = hipMemcpyAsync(s.h_taxa, s.d_taxa, toff * 4, hipMemcpyDeviceToHost, s.stream);
                 if (he == hipSuccess && split)
                     he = hipMemcpyAsync(s.human.h_total, s.human.d_total, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
+                if (he == hipSuccess && taxa)
+                    he = hipMemcpyAsync(s.taxon.h_total, s.taxon.d_total, 4 * (size_t)K * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
                 if (he == hipSuccess && mask)
                     he = hipMemcpyAsync(s.mask.h_total, s.mask.d_total, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
                 if (he == hipSuccess && lists)
@@ -1979,6 +2155,10 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                         (unsigned long long)rs.text_fetched.load(), rs.mask_kernel_ms,
                         rs.mask_kernel_ms > 0 ? (double)rs.mask_bytes / (rs.mask_kernel_ms * 1e6) : 0.0,
                         (unsigned long long)rs.mask_fast, (unsigned long long)rs.mask_nblk);
+            if (taxa)
+                fprintf(stderr, "[nohuman trace] taxon-out: %llu records, %llu bytes built on device; %llu fetched to host; kernel %.3f ms\n",
+                        (unsigned long long)rs.taxon_records, (unsigned long long)rs.taxon_bytes, (unsigned long long)rs.text_fetched.load(),
+                        rs.taxon_kernel_ms);
             if (lists)
                 fprintf(stderr, "[nohuman trace] calls: %llu lines, %llu bytes; ids: %llu lines, %llu bytes built on device; %llu fetched to host; builder kernels %.3f ms\n",
                         (unsigned long long)rs.list_lines[0], (unsigned long long)rs.list_bytes[0], (unsigned long long)rs.list_lines[1],
@@ -2091,6 +2271,9 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
         if (rch1) return set_error(rch1, "%s", errh1.c_str());
         if (rch2) return set_error(rch2, "%s", errh2.c_str());
     }
+    for (int k = 0; k < K; k++)
+        for (int m = 0; m < mates; m++)
+            if ((rc = tx[m][k].close())) return rc;
     if (rs.want_k && (rc = ok.close())) return rc;
     if (calls && (rc = oc.close())) return rc;
     if (ids && (rc = oi.close())) return rc;
@@ -2127,6 +2310,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
         if (rs_path && (rc = nh_read_stats_write(&out, rs_path))) return rc;
         if (rs_out) *rs_out = out;
     }
+    for (int k = 0; k < K; k++) touts[k].fragments = rs.taxon_frags[k];
     if (stats) {
         nh_stats st;
         memset(&st, 0, sizeof st);
@@ -2142,9 +2326,9 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
 
 int run_engine(Engine *e, const nh_run_args *a, nh_stats *stats, const char *hout1 = nullptr, const char *hout2 = nullptr,
                bool mask = false, const char *calls = nullptr, const char *ids = nullptr, uint32_t minq = 0,
-               const char *rs_path = nullptr, nh_read_stats *rs_out = nullptr) {
+               const char *rs_path = nullptr, nh_read_stats *rs_out = nullptr, nh_taxon_out *touts = nullptr, uint32_t n_touts = 0) {
     std::vector<Engine *> v{e};
-    return run_engines(v, a, stats, hout1, hout2, mask, calls, ids, minq, rs_path, rs_out);
+    return run_engines(v, a, stats, hout1, hout2, mask, calls, ids, minq, rs_path, rs_out, touts, n_touts);
 }
 
 // nh_run_minq's own argument, checked before any device is touched: the highest printable quality is '~', Phred 93
@@ -2172,6 +2356,13 @@ int check_rstats(const nh_run_args *a, const nh_run_extras *x, uint32_t minq, co
     int rc = check_minq(minq);
     if (!rc && x) rc = check_extras(a, x);
     if (!rc) rc = check_rstats_args(a, x, rs_path);
+    return rc;
+}
+
+// nh_run_taxa's arguments, checked before any device is touched: nh_run_rstats', then the selectors
+int check_taxa(const nh_run_args *a, const nh_run_extras *x, uint32_t minq, const char *rs_path, const nh_taxon_out *outs, uint32_t n) {
+    int rc = check_rstats(a, x, minq, rs_path);
+    if (!rc) rc = check_taxon_args(a, x, rs_path, outs, n);
     return rc;
 }
 
@@ -2225,6 +2416,18 @@ int nh_run_engine_rstats(nh_engine *e, const nh_run_args *args, const nh_run_ext
         return nh::run_engine((nh::Engine *)e, args, stats, nullptr, nullptr, false, nullptr, nullptr, min_base_quality, read_stats_path, out);
     return nh::run_engine((nh::Engine *)e, args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls,
                           extras->human_ids, min_base_quality, read_stats_path, out);
+}
+
+int nh_run_engine_taxa(nh_engine *e, const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality,
+                       const char *read_stats_path, nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs, nh_stats *stats) {
+    const int rc = nh::check_taxa(args, extras, min_base_quality, read_stats_path, outs, n_outs);
+    if (rc) return rc;
+    if (!e) return nh::set_error(NH_EINVAL, "null engine");
+    if (!extras)
+        return nh::run_engine((nh::Engine *)e, args, stats, nullptr, nullptr, false, nullptr, nullptr, min_base_quality, read_stats_path, read_stats,
+                              outs, n_outs);
+    return nh::run_engine((nh::Engine *)e, args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls,
+                          extras->human_ids, min_base_quality, read_stats_path, read_stats, outs, n_outs);
 }
 
 int nh_fastx_scan(const char *path, uint64_t *n_records, uint64_t *n_bases, uint64_t *digest) {
@@ -2373,7 +2576,7 @@ int nh_debug_reader_dump(const char *path, int reader, int device, uint64_t batc
 // round-robin, outputs stay in input order, the counts are summed on the host.
 static int run_devices(const nh_run_args *args, nh_stats *stats, const char *hout1, const char *hout2, bool mask = false,
                        const char *calls = nullptr, const char *ids = nullptr, uint32_t minq = 0, const char *rs_path = nullptr,
-                       nh_read_stats *rs_out = nullptr) {
+                       nh_read_stats *rs_out = nullptr, nh_taxon_out *touts = nullptr, uint32_t n_touts = 0) {
     if (!args || !args->db_dir) return nh::set_error(NH_EINVAL, "nh_run: db_dir is required");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -2409,7 +2612,7 @@ static int run_devices(const nh_run_args *args, nh_stats *stats, const char *hou
     }
     const double t_load = since(t_begin);
     const auto t_run = std::chrono::steady_clock::now();
-    if (!rc) rc = nh::run_engines(engines, args, stats, hout1, hout2, mask, calls, ids, minq, rs_path, rs_out);
+    if (!rc) rc = nh::run_engines(engines, args, stats, hout1, hout2, mask, calls, ids, minq, rs_path, rs_out, touts, n_touts);
     const double s_run = since(t_run);
     std::string keep = nh::g_last_error;
     const auto t_close = std::chrono::steady_clock::now();
@@ -2457,6 +2660,16 @@ int nh_run_rstats(const nh_run_args *args, const nh_run_extras *extras, uint32_t
     if (!extras) return run_devices(args, stats, nullptr, nullptr, false, nullptr, nullptr, min_base_quality, read_stats_path, out);
     return run_devices(args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls, extras->human_ids,
                        min_base_quality, read_stats_path, out);
+}
+
+int nh_run_taxa(const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality, const char *read_stats_path,
+                nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs, nh_stats *stats) {
+    const int rc = nh::check_taxa(args, extras, min_base_quality, read_stats_path, outs, n_outs);  // (before any device is touched)
+    if (rc) return rc;
+    if (!extras)
+        return run_devices(args, stats, nullptr, nullptr, false, nullptr, nullptr, min_base_quality, read_stats_path, read_stats, outs, n_outs);
+    return run_devices(args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls, extras->human_ids,
+                       min_base_quality, read_stats_path, read_stats, outs, n_outs);
 }
 
 }  // extern "C"

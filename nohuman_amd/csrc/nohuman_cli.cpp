@@ -221,6 +221,8 @@ struct Args {
     std::string calls, human_ids;  // read lists (nh_run_ex): a table line per read; the ids of the human reads
     unsigned min_base_quality = 0;  // kraken2's --minimum-base-quality (nh_run_minq); 0: off
     std::string read_stats;         // the read statistics table (nh_run_rstats)
+    // per-taxon outputs (nh_run_taxa): the selectors in the order given -- taxid (0: `other`), the path as given ('#' in it: the mate)
+    std::vector<std::pair<unsigned long long, std::string>> taxon_out;
     bool has_out1 = false, has_out2 = false, check = false, download = false, list = false, human = false;
     bool has_type = false;
     Codec type = C_NONE;
@@ -264,6 +266,9 @@ static void usage(FILE *f) {
           "      --calls <FILE>           Write a table with one line per read: C/U, id, taxid, length(s), k-mers, clade hits (hits / k-mers is the confidence -C thresholds), hit groups\n"
           "      --read-stats <FILE>      Write a QC table of all, non-human and human reads per mate: reads, bases, min/mean/median/max length, N50, GC %, other bases, Q20 %, Q30 %, mean quality (counted on the GPU in the same pass)\n"
           "      --human-ids <FILE>       Write the ids of the human reads, one per line\n"
+          "      --taxon-out <TAXID|other>:<PATH>  Also write the classified reads of this taxon's clade to PATH, in the same run (as -H would write them); "
+          "may be given up to 8 times: a read goes to the deepest selected taxon that is its call or an ancestor of it, `other` takes the "
+          "classified reads in no selected clade. With two inputs PATH must contain '#', which becomes _1 / _2\n"
           "      --build-db <DIR>         Build a database (hash.k2d, opts.k2d, taxo.k2d) in DIR from the --reference files, on the GPU, and exit\n"
           "      --reference <FILE>       FASTA file (plain or gzip) of the host genome for --build-db; may be given more than once\n"
           "      --taxid <INT>            Taxonomy id of the host for --build-db [default: 9606]\n"
@@ -277,6 +282,16 @@ static void usage(FILE *f) {
           "  -h, --help                   Print help\n"
           "  -V, --version                Print version\n",
           f);
+}
+
+// the file of mate m (0, 1) of a --taxon-out path: every '#' becomes _1 / _2 (kraken2's convention for its paired outputs)
+static std::string taxon_out_path(const std::string &path, int m) {
+    std::string out;
+    for (char c : path) {
+        if (c == '#') out += m ? "_2" : "_1";
+        else out += c;
+    }
+    return out;
 }
 
 [[noreturn]] static void arg_error(const char *fmt, ...) {  // clap: message, exit code 2
@@ -354,6 +369,25 @@ static Args parse_args(int argc, char **argv) {
         else if (s == "--calls") a.calls = val();
         else if (s == "--human-ids") a.human_ids = val();
         else if (s == "--read-stats") a.read_stats = val();
+        else if (s == "--taxon-out") {
+            const std::string t = val();
+            const size_t colon = t.find(':');
+            if (colon == std::string::npos || colon + 1 == t.size())
+                arg_error("invalid value '%s' for '--taxon-out <TAXID|other>:<PATH>': a selector, a ':' and a path are expected", t.c_str());
+            const std::string sel = t.substr(0, colon);
+            unsigned long long id = 0;
+            if (sel != "other") {
+                char *end;
+                errno = 0;
+                id = strtoull(sel.c_str(), &end, 10);
+                if (*end || sel.empty() || sel[0] < '0' || sel[0] > '9' || errno || id == 0)
+                    arg_error("invalid value '%s' for '--taxon-out <TAXID|other>:<PATH>': %s is neither a taxid nor `other`", t.c_str(), quoted(sel).c_str());
+            }
+            for (const auto &o : a.taxon_out)
+                if (o.first == id) arg_error("the argument '--taxon-out <TAXID|other>:<PATH>' selects %s more than once", sel.c_str());
+            if (a.taxon_out.size() == NH_MAX_TAXON_OUTS) arg_error("the argument '--taxon-out <TAXID|other>:<PATH>' cannot be used more than %d times", NH_MAX_TAXON_OUTS);
+            a.taxon_out.push_back({id, t.substr(colon + 1)});
+        }
         else if (s == "--build-db") { a.build_db = val(); a.has_build_db = true; }
         else if (s == "--reference") a.reference.push_back(val());
         else if (s == "--taxid" || s == "--capacity") {
@@ -397,7 +431,7 @@ static Args parse_args(int argc, char **argv) {
         const char *out_flag = a.has_out1 ? "--out1" : a.has_out2 ? "--out2" : a.has_human_out1 ? "--human-out1" : a.has_human_out2 ? "--human-out2"
                              : !a.kraken_output.empty() ? "--kraken-output" : !a.kraken_report.empty() ? "--kraken-report" : !a.calls.empty() ? "--calls"
                              : !a.human_ids.empty() ? "--human-ids" : !a.read_stats.empty() ? "--read-stats" : a.has_type ? "--output-type"
-                             : a.bgzf ? "--bgzf" : a.mask ? "--mask" : a.human ? "--human" : nullptr;
+                             : a.bgzf ? "--bgzf" : a.mask ? "--mask" : a.human ? "--human" : !a.taxon_out.empty() ? "--taxon-out" : nullptr;
         if (out_flag) arg_error("the argument '--build-db <DIR>' cannot be used with '%s'", out_flag);
         for (const std::string &r : a.reference)
             if (!exists(r)) arg_error("invalid value '%s' for '--reference <FILE>': %s does not exist", r.c_str(), quoted(r).c_str());
@@ -426,6 +460,30 @@ static Args parse_args(int argc, char **argv) {
         }
         if (a.has_human_out2 && a.human_out1 == a.human_out2)
             arg_error("the arguments '--human-out1 <PATH>' and '--human-out2 <PATH>' name the same file: %s", a.human_out1.c_str());
+    }
+    // per-taxon outputs (--taxon-out): a file per selector and mate, written in the same pass
+    if (!a.taxon_out.empty()) {
+        const bool paired = a.input.size() == 2;
+        if (a.human) arg_error("the argument '--human' cannot be used with '--taxon-out <TAXID|other>:<PATH>'");
+        std::vector<std::string> mine;
+        for (const auto &o : a.taxon_out) {
+            const bool hash = o.second.find('#') != std::string::npos;
+            if (paired && !hash) arg_error("invalid value '%s' for '--taxon-out <TAXID|other>:<PATH>': with two inputs the path needs a '#' (it becomes _1 / _2)", o.second.c_str());
+            if (!paired && hash) arg_error("invalid value '%s' for '--taxon-out <TAXID|other>:<PATH>': a '#' in the path needs two inputs", o.second.c_str());
+            for (int m = 0; m < (paired ? 2 : 1); m++) {
+                const std::string p = taxon_out_path(o.second, m);
+                const char *other = (a.has_out1 && p == a.out1) ? "--out1" : (a.has_out2 && p == a.out2) ? "--out2"
+                                  : (a.has_human_out1 && p == a.human_out1) ? "--human-out1" : (a.has_human_out2 && p == a.human_out2) ? "--human-out2"
+                                  : p == a.kraken_output ? "--kraken-output" : p == a.kraken_report ? "--kraken-report" : p == a.calls ? "--calls"
+                                  : p == a.human_ids ? "--human-ids" : p == a.read_stats ? "--read-stats" : nullptr;
+                if (other) arg_error("the argument '--taxon-out <TAXID|other>:<PATH>' names the same file as '%s': %s", other, p.c_str());
+                for (const std::string &q : mine)
+                    if (p == q) arg_error("the argument '--taxon-out <TAXID|other>:<PATH>' names the same file twice: %s", p.c_str());
+                for (const std::string &in : a.input)
+                    if (p == in) arg_error("the argument '--taxon-out <TAXID|other>:<PATH>' names the input %s", p.c_str());
+                mine.push_back(p);
+            }
+        }
     }
     if (!a.calls.empty() && a.calls == a.human_ids)
         arg_error("the arguments '--calls <FILE>' and '--human-ids <FILE>' name the same file: %s", a.calls.c_str());
@@ -485,6 +543,29 @@ static std::vector<std::string> node_names(const std::string &db_dir) {
     return out;
 }
 
+// the name of the node with this external id in a database's taxo.k2d (the id is the node's sixth word); "?" when it has none
+static std::string taxon_name_of(const std::string &db_dir, unsigned long long taxid) {
+    FILE *f = fopen(join(db_dir, "taxo.k2d").c_str(), "rb");
+    if (!f) return "?";
+    std::string img;
+    char buf[1 << 16];
+    size_t n;
+    while ((n = fread(buf, 1, sizeof buf, f)) > 0) img.append(buf, n);
+    fclose(f);
+    uint64_t hdr[3];
+    if (img.size() < 32 || memcmp(img.data(), "K2TAXDAT", 8) != 0) return "?";
+    memcpy(hdr, img.data() + 8, 24);
+    if (hdr[0] > (1u << 20) || hdr[1] > img.size() || 32 + hdr[0] * 56 + hdr[1] > img.size()) return "?";
+    const char *names = img.data() + 32 + hdr[0] * 56;
+    for (uint64_t i = 1; i < hdr[0]; i++) {
+        uint64_t off, ext;
+        memcpy(&off, img.data() + 32 + i * 56 + 24, 8);
+        memcpy(&ext, img.data() + 32 + i * 56 + 40, 8);
+        if (ext == taxid) return off < hdr[1] ? std::string(names + off, strnlen(names + off, hdr[1] - off)) : std::string("?");
+    }
+    return "?";
+}
+
 static void fill_build_args(const Args &args, std::vector<const char *> &refs, nh_build_args &ba) {
     for (const std::string &r : args.reference) refs.push_back(r.c_str());
     memset(&ba, 0, sizeof ba);
@@ -527,6 +608,16 @@ int main(int argc, char **argv) {
             if (!h->empty() && (*h == o1 || *h == o2))
                 arg_error("the argument '%s <PATH>' names the same file as the output %s", h == &args.human_out1 ? "--human-out1" : "--human-out2",
                           h->c_str());
+    }
+    if (!args.taxon_out.empty() && !args.input.empty()) {  // and a per-taxon file equal to a DEFAULT output name
+        const Codec c = args.has_type ? args.type : args.has_out1 ? codec_from_path(args.out1) : codec_from_magic(args.input[0]);
+        const std::string o1 = args.has_out1 ? args.out1 : default_out_name(args.input[0], c);
+        const std::string o2 = args.input.size() == 2 ? (args.has_out2 ? args.out2 : default_out_name(args.input[1], c)) : "";
+        for (const auto &o : args.taxon_out)
+            for (int m = 0; m < (int)args.input.size() && m < 2; m++) {
+                const std::string p = taxon_out_path(o.second, m);
+                if (p == o1 || p == o2) arg_error("the argument '--taxon-out <TAXID|other>:<PATH>' names the same file as the output %s", p.c_str());
+            }
     }
     if (args.list) die("Failed to download database manifest: network access is not available in this build");
     if (args.download) {
@@ -662,6 +753,21 @@ int main(int argc, char **argv) {
     if (!args.human_ids.empty()) staged_files.push_back({args.human_ids, ipart});
     const std::string spart = args.read_stats.empty() ? "" : staged(args.read_stats);
     if (!args.read_stats.empty()) staged_files.push_back({args.read_stats, spart});
+    // the per-taxon files: staged and renamed like the human outputs
+    std::vector<std::string> tfinal, tpart;  // [2 * selector + mate]
+    for (const auto &o : args.taxon_out)
+        for (int m = 0; m < 2; m++) {
+            tfinal.push_back(m && !paired ? "" : taxon_out_path(o.second, m));
+            tpart.push_back(m && !paired ? "" : staged(tfinal.back()));
+            if (!tfinal.back().empty()) staged_files.push_back({tfinal.back(), tpart.back()});
+        }
+    std::vector<nh_taxon_out> touts(args.taxon_out.size());
+    for (size_t k = 0; k < touts.size(); k++) {
+        touts[k].taxid = args.taxon_out[k].first ? args.taxon_out[k].first : NH_TAXON_OTHER;
+        touts[k].out1 = tpart[2 * k].c_str();
+        touts[k].out2 = paired ? tpart[2 * k + 1].c_str() : nullptr;
+        touts[k].fragments = 0;
+    }
     staged_files.push_back({out1, part1});
     if (paired) staged_files.push_back({out2, part2});
     auto unlink_staged = [&] {
@@ -696,7 +802,9 @@ int main(int argc, char **argv) {
     rx.human_out1 = hp1, rx.human_out2 = hp2;
     rx.calls = args.calls.empty() ? nullptr : cpart.c_str();
     rx.human_ids = args.human_ids.empty() ? nullptr : ipart.c_str();
-    const int run_rc = !args.read_stats.empty() ? nh_run_rstats(&ra, lists || args.mask || split ? &rx : nullptr, args.min_base_quality, spart.c_str(), nullptr, &st)
+    const int run_rc = !touts.empty() ? nh_run_taxa(&ra, lists || args.mask || split ? &rx : nullptr, args.min_base_quality,
+                                                    args.read_stats.empty() ? nullptr : spart.c_str(), nullptr, touts.data(), (uint32_t)touts.size(), &st)
+                       : !args.read_stats.empty() ? nh_run_rstats(&ra, lists || args.mask || split ? &rx : nullptr, args.min_base_quality, spart.c_str(), nullptr, &st)
                        : args.min_base_quality ? nh_run_minq(&ra, lists || args.mask || split ? &rx : nullptr, args.min_base_quality, &st)
                        : lists     ? nh_run_ex(&ra, &rx, &st)
                        : args.mask ? nh_run_mask(&ra, hp1, hp2, &st)
@@ -736,6 +844,12 @@ int main(int argc, char **argv) {
     if (split) {
         INFO("Human reads written to: %s", quoted(args.human_out1).c_str());
         if (paired) INFO("Human reads written to: %s", quoted(args.human_out2).c_str());
+    }
+    for (size_t k = 0; k < touts.size(); k++) {
+        const unsigned long long id = args.taxon_out[k].first;
+        const std::string files = paired ? quoted(tfinal[2 * k]) + " " + quoted(tfinal[2 * k + 1]) : quoted(tfinal[2 * k]);
+        if (id) INFO("Taxon %llu (%s): %llu reads written to: %s", id, taxon_name_of(db_path, id).c_str(), (unsigned long long)touts[k].fragments, files.c_str());
+        else INFO("Taxon other (classified, in no selected clade): %llu reads written to: %s", (unsigned long long)touts[k].fragments, files.c_str());
     }
     if (!args.kraken_output.empty() && args.kraken_output != "/dev/null")
         INFO("Kraken output file written to: %s", quoted(args.kraken_output).c_str());

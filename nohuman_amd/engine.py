@@ -42,7 +42,7 @@ def probe() -> str:
 def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None, confidence: float = 0.0,
         threads: int = 1, keep_human: bool = False, device_ids=None, out_codec: int = 0,
         codec_threads: int = 0, human_out1=None, human_out2=None, mask: bool = False, calls=None,
-        human_ids=None, min_base_quality: int = 0, read_stats=None) -> "_lib.nh_stats":
+        human_ids=None, min_base_quality: int = 0, read_stats=None, taxon_outs=None) -> "_lib.nh_stats":
     """nh_run: whole run, database loaded into every listed device (default: all visible).  human_out1 (and, paired,
     human_out2) given: nh_run_split -- the non-human reads go to out1 / out2 and, in the same pass, the human reads to
     human_out1 / human_out2 exactly as a keep_human run would write them.  mask: nh_run_mask -- every read goes to
@@ -55,7 +55,11 @@ def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
     below it is classified as an ambiguous base; every record written keeps its bases.  0: exactly the run without it.
     read_stats (nh_run_rstats; any kind of run): a path, or a ReadStats -- the QC summary of all, non-human and human reads per
     mate (reads, bases, lengths, N50, GC, quality histogram), counted on the GPU in the same pass; the table goes to the path,
-    the numbers into the ReadStats."""
+    the numbers into the ReadStats.
+    taxon_outs (nh_run_taxa; not with keep_human): up to 8 selectors [(taxid or "other", out1, out2 or None), ...] -- the
+    classified reads sorted by clade on the GPU in the same pass, each to the deepest selected taxon that is its call or an
+    ancestor of it ("other": in no selector's clade), written as a keep_human run writes them.  The stats returned then carry
+    taxon_fragments: the selectors' fragment counts, in the order given."""
     a = _lib.nh_run_args()
     a.db_dir = os.fsencode(db_dir)
     a.in1 = os.fsencode(in1)
@@ -78,7 +82,14 @@ def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
         a.n_devices = 0
         a.device_ids = None
     s = _lib.nh_stats()
-    if read_stats is not None:
+    if taxon_outs:
+        rs = _read_stats(read_stats) if read_stats is not None else None
+        t = _taxon_outs(taxon_outs)
+        _check(_lib.lib().nh_run_taxa(C.byref(a), _extras_or_none(mask, human_out1, human_out2, calls, human_ids),
+                                      _minq(min_base_quality), _path_or_none(rs.path) if rs else None,
+                                      C.byref(rs.raw) if rs else None, t, len(t), C.byref(s)))
+        s.taxon_fragments = [int(x.fragments) for x in t]
+    elif read_stats is not None:
         rs = _read_stats(read_stats)
         _check(_lib.lib().nh_run_rstats(C.byref(a), _extras_or_none(mask, human_out1, human_out2, calls, human_ids),
                                         _minq(min_base_quality), _path_or_none(rs.path), C.byref(rs.raw), C.byref(s)))
@@ -99,6 +110,19 @@ def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
 
 def _path_or_none(p):
     return os.fsencode(p) if p is not None else None
+
+
+def _taxon_outs(sel):
+    """run(taxon_outs=...): the nh_taxon_out array of [(taxid or "other", out1, out2 or None), ...]"""
+    sel = list(sel)
+    t = (_lib.nh_taxon_out * len(sel))()
+    for x, (taxid, out1, out2) in zip(t, sel):
+        if isinstance(taxid, str) and taxid != "other":
+            raise EngineError(-1, "taxon_outs: a selector is a taxid or \"other\", not %r" % (taxid,))
+        x.taxid = _lib.NH_TAXON_OTHER if taxid == "other" else int(taxid)
+        x.out1 = _path_or_none(out1)
+        x.out2 = _path_or_none(out2)
+    return t
 
 
 def _extras(mask, human_out1, human_out2, calls, human_ids) -> "_lib.nh_run_extras":
@@ -433,10 +457,10 @@ class Engine:
     def run(self, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
             confidence: float = 0.0, threads: int = 1, keep_human: bool = False, out_codec: int = 0,
             codec_threads: int = 0, human_out1=None, human_out2=None, mask: bool = False, calls=None,
-            human_ids=None, min_base_quality: int = 0, read_stats=None) -> _lib.nh_stats:
+            human_ids=None, min_base_quality: int = 0, read_stats=None, taxon_outs=None) -> _lib.nh_stats:
         """nh_run_engine; with human_out1 (and, paired, human_out2): nh_run_engine_split; mask: nh_run_engine_mask; with
         calls / human_ids: nh_run_engine_ex; with min_base_quality: nh_run_engine_minq; with read_stats:
-        nh_run_engine_rstats -- as run() above."""
+        nh_run_engine_rstats; with taxon_outs: nh_run_engine_taxa -- as run() above."""
         a = _lib.nh_run_args()
         a.db_dir = None
         a.in1 = os.fsencode(in1)
@@ -453,7 +477,14 @@ class Engine:
         a.out_codec = int(out_codec)
         a.codec_threads = int(codec_threads)
         s = _lib.nh_stats()
-        if read_stats is not None:
+        if taxon_outs:
+            rs = _read_stats(read_stats) if read_stats is not None else None
+            t = _taxon_outs(taxon_outs)
+            _check(self._L.nh_run_engine_taxa(self._h, C.byref(a), _extras_or_none(mask, human_out1, human_out2, calls, human_ids),
+                                              _minq(min_base_quality), _path_or_none(rs.path) if rs else None,
+                                              C.byref(rs.raw) if rs else None, t, len(t), C.byref(s)))
+            s.taxon_fragments = [int(x.fragments) for x in t]
+        elif read_stats is not None:
             rs = _read_stats(read_stats)
             _check(self._L.nh_run_engine_rstats(self._h, C.byref(a), _extras_or_none(mask, human_out1, human_out2, calls, human_ids),
                                                 _minq(min_base_quality), _path_or_none(rs.path), C.byref(rs.raw), C.byref(s)))
