@@ -169,6 +169,9 @@ int nh_opts_image(const nh_engine *e, void *buf, size_t cap, size_t *len);
  *                two markers above -- the material of the `-k` hit list.
  *                kmer_taxa_offsets[f] = sum over fragments < f of (k-mers of both mates + paired);
  *                the caller sizes kmer_taxa with nh_kmer_taxa_entries.
+ * NH_ECAPACITY: a fragment (both mates together) hit more than 2048 distinct taxa.  The whole call fails, here and in every
+ * nh_run*: `results` and `kmer_taxa` are not to be read.  The error is cleared with the call that reports it, so the engine
+ * classifies the next batch as if nothing had happened.
  */
 int nh_classify_batch(nh_engine *e, const uint8_t *bases, const uint64_t *seq_offsets,
                       uint64_t n_frag, uint32_t flags, double confidence, nh_result *results,

@@ -60,15 +60,15 @@ class Env:
                 os.environ[k] = v
 
 
-def _run(errf, **kw):
-    """one engine.run with fd 2 (the library's trace lines) in errf"""
+def _run(errf, db=DB, **kw):
+    """one engine.run on the database directory `db` with fd 2 (the library's trace lines) in errf"""
     from nohuman_amd import engine
     saved = os.dup(2)
     fd = os.open(str(errf), os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
     os.dup2(fd, 2)
     os.close(fd)
     try:
-        return engine.run(DB, **kw)
+        return engine.run(db, **kw)
     finally:
         os.dup2(saved, 2)
         os.close(saved)
@@ -77,10 +77,13 @@ def _run(errf, **kw):
 class Case:
     """the two reference runs of an input (keep_human = 1; the run without selectors), made once, then any number of selector
     lists against them.  extra: further keyword arguments of every run but the keep_human one (mask, calls, ...), whose values
-    that start with '@' are file names inside the run's directory."""
+    that start with '@' are file names inside the run's directory.  db, parent: the database directory and the parent map of
+    its taxonomy (the toy database's by default)."""
 
-    def __init__(self, tmp, name, in1, in2=None, codec=0, env=None, device_ids=(0,), extra=None, fasta=False, minq=0):
+    def __init__(self, tmp, name, in1, in2=None, codec=0, env=None, device_ids=(0,), extra=None, fasta=False, minq=0, db=DB,
+                 parent=PARENT):
         self.tmp, self.name, self.in1, self.in2, self.codec, self.env = tmp, name, in1, in2, codec, env
+        self.db, self.parent = str(db), parent
         self.device_ids, self.extra, self.fastq, self.minq = list(device_ids), dict(extra or {}), not fasta, minq
         self.mates = ("1", "2") if in2 else ("1",)
         self.runs = 0
@@ -90,7 +93,7 @@ class Case:
             d.mkdir()
             kw = dict(in1=in1, out1=str(d / ("o1" + EXT[codec])), in2=in2, out2=str(d / ("o2" + EXT[codec])) if in2 else None, threads=4,
                       out_codec=codec, keep_human=True, min_base_quality=minq, device_ids=self.device_ids)
-            self.keep_stats = _run(tmp / (name + "_keep.stderr"), **kw)
+            self.keep_stats = _run(tmp / (name + "_keep.stderr"), db=self.db, **kw)
             self.keep = [_read(d / ("o%s%s" % (m, EXT[codec])), codec) for m in self.mates]
 
     def _one(self, tag, sel):
@@ -105,7 +108,7 @@ class Case:
             kw["taxon_outs"] = [(s, str(d / ("t%d_1%s" % (i, EXT[self.codec]))), str(d / ("t%d_2%s" % (i, EXT[self.codec]))) if self.in2 else None)
                                 for i, s in enumerate(sel)]
         errf = self.tmp / ("%s_%s.stderr" % (self.name, tag))
-        st = _run(errf, **kw)
+        st = _run(errf, db=self.db, **kw)
         return d, st, errf.read_bytes().decode(errors="replace")
 
     def check(self, sel):
@@ -116,7 +119,7 @@ class Case:
         want_counts = None
         built = 0
         for mi, m in enumerate(self.mates):
-            files, counts = tm.partition(self.keep[mi], self.fastq, PARENT, sel)
+            files, counts = tm.partition(self.keep[mi], self.fastq, self.parent, sel)
             assert want_counts in (None, counts)
             want_counts = counts
             for i in range(len(sel)):
@@ -267,6 +270,34 @@ def test_several_batches(tmp_path, pool):
     assert all(counts)
     c = Case(tmp_path, "bt2", str(p), codec=2, env={"NOHUMAN_BATCH_FRAGS": "400"})
     c.check([10, 11, 9606, 21, tm.OTHER])
+
+
+def bins_end(sizes):
+    """where the last bin that has bytes ends in a mate's buffer of one batch: every bin starts at the next multiple of 256 bytes
+    behind the end of the bin before it (k_tout_scan).  With a host codec that is what the run fetches of the buffer"""
+    at = end = 0
+    for n in sizes:
+        at = (at + 255) & ~255
+        if n:
+            end = at + n
+        at += n
+    return end
+
+
+def test_more_than_256_blocks_with_eight_selectors(tmp_path, pool):
+    """258 blocks in one batch and the largest number of selectors: scan_block_sums takes 256 block sums a round, so every bin's
+    second round starts with the sum carried over from its first (the size of test_gpu_builders.py's
+    test_more_than_256_blocks_in_one_batch; the one case here that takes more than a few seconds)"""
+    n = 262144 + 1025
+    p = tmp_path / "d.fq"
+    p.write_bytes(_designed(pool, n))
+    c = Case(tmp_path, "wide", str(p), env={"NOHUMAN_BATCH_FRAGS": "270000"})
+    sel = [10, 11, 12, 111, 20, 21, 9606, tm.OTHER]
+    counts, trace = c.check(sel)
+    assert counts[5] == counts[6] == 1 and all(counts) and sum(counts) == c.ref.classified
+    files, _ = tm.partition(c.keep[0], True, PARENT, sel)
+    assert trace[2] == bins_end([len(f) for f in files])  # the eight bins' starts in the one batch's buffer
+    assert (n + HB_FRAGS - 1) // HB_FRAGS == 258
 
 
 CHILD = r"""
