@@ -472,6 +472,69 @@ int nh_run_engine_taxa(nh_engine *e, const nh_run_args *args, const nh_run_extra
                        const char *read_stats_path, nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs, nh_stats *stats);
 
 /*
+ * Minimizer data (--report-minimizer-data, --minimizer-table; nohuman_amd/csrc/nh_mdata.hip): per taxon, how many
+ * minimizer hits the reads of a run produced and how many DISTINCT database minimizers they were -- kraken2's
+ * --report-minimizer-data, the KrakenUniq idea: many reads on few distinct minimizers is the signature of a false positive.
+ * DEFINITIONS.  A HIT GROUP is what the classifier counts in nh_result.hit_groups: a run start of the scanner whose look-up found a
+ * cell with a non-zero value.  A run start is a minimizer that differs from the fragment's previous non-ambiguous minimizer; the
+ * previous minimizer survives ambiguous stretches and is reset at mate 2 exactly when nh_options.reset_per_mate is set.  For every
+ * hit group, over ALL fragments of the run and both mates, classified or not, let t be the value found and c the index of the cell
+ * where the key matched.  Per taxonomy node t:
+ *   minimizers_own[t]  hit groups with value t (kraken2's n_kmers)
+ *   distinct_own[t]    distinct cells c among them (kraken2: a HyperLogLog estimate of the distinct minimizers; here exact)
+ *   db_cells_own[t]    cells of the table whose value is t (kraken2-inspect's number)
+ *   *_clade[t]         the sum over t's subtree, reads_* as the report has them
+ * Every database minimizer lives in exactly one cell, so one bit per cell counts exactly: the numbers do not depend on batches,
+ * streams or devices, and clades sum.  Two minimizers that the compact hash cannot tell apart (one compacted key inside one probe
+ * run) are one entry of the database and count once, as the classifier treats them.  With a minimum base quality the pass reads
+ * the masked sequences the classifier reads.  Always: sum_t minimizers_own[t] == sum over the fragments of hit_groups;
+ * distinct_own[t] <= min(minimizers_own[t], db_cells_own[t]); sum_t db_cells_own[t] == nh_db_info.size.
+ * The pass is one of its own behind the classifier, launched only when asked for; it costs capacity / 8 bytes of device memory a
+ * device.  It supports the default geometry (k = 35, l = 31, the default spaced-seed and toggle masks, revcom_version 1,
+ * minimum_acceptable_hash_value 0) and linear probing: any other database is NH_EDB with the field in the message, linear_probing
+ * = 0 in the engine's options NH_EINVAL -- once the database is open, before any input is read or any output created.
+ */
+typedef struct {            /* 72 bytes */
+    uint64_t taxid;         /* external id */
+    uint64_t reads_clade, reads_own, minimizers_clade, minimizers_own, distinct_clade, distinct_own, db_cells_clade, db_cells_own;
+} nh_taxon_minimizers;
+typedef struct {            /* 32 bytes */
+    uint32_t struct_size;   /* sizeof(nh_minimizer_data) of the caller */
+    int32_t in_report;      /* not 0: args->report gets kraken2's two extra columns (below) */
+    const char *table;      /* the project's own table (below), NULL = none */
+    nh_taxon_minimizers *taxa; /* NULL, or receives one entry a node in internal-id order from the root (at most taxa_cap) */
+    uint32_t taxa_cap, n_taxa; /* n_taxa: out, nodes of the taxonomy without the sentinel */
+} nh_minimizer_data;
+/* nh_run_taxa with minimizer data; any kind of run.  md NULL, or md with in_report 0, table NULL and taxa NULL: exactly nh_run_taxa,
+ * nothing allocated or launched.
+ * in_report: columns 4 and 5 of the report become minimizers_clade and distinct_clade --
+ *   pct <TAB> reads_clade <TAB> reads_own <TAB> minimizers_clade <TAB> distinct_clade <TAB> rank <TAB> taxid <TAB> name
+ * -- the `unclassified` line carries 0 and 0, the lines and their order are those of the report without it (a clade without reads is
+ * not printed).  A recollection of kraken2's reports.cc, unpinned like the rest (PINDAY.md).
+ * table: plain text, a header line, then a row for every node with reads_clade > 0 or minimizers_clade > 0 in internal-id order,
+ * tab-separated:  taxid name reads_clade reads_own minimizers_clade minimizers_own distinct_clade distinct_own db_cells_clade
+ * db_cells_own coverage_pct,  coverage_pct = 100 distinct_clade / db_cells_clade as %.4f, "NA" where the denominator is 0.  Written
+ * when the run has succeeded.
+ * NH_EINVAL before any device is touched, nothing created: struct_size too small; in_report without args->report; table empty;
+ * table naming an input or any other output of the run (the same path, or the same device and inode); taxa with taxa_cap 0; every
+ * check of nh_run_taxa.  NH_EOOM (the bytes in the message) where the bitmap cannot be allocated. */
+int nh_run_mdata(const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality, const char *read_stats_path,
+                 nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs, nh_minimizer_data *md, nh_stats *stats);
+int nh_run_engine_mdata(nh_engine *e, const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality,
+                        const char *read_stats_path, nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs,
+                        nh_minimizer_data *md, nh_stats *stats);
+/* The two passes themselves, asynchronous on `stream`, on the engine's device.  bytes: of the bitmap, 4 ceil(capacity / 32). */
+int nh_minimizer_marks_bytes(const nh_engine *e, uint64_t *bytes);
+/* The sequences are addressed as in nh_classify_records_device (d_text 4-byte aligned and readable for text_len + 8 bytes; with
+ * NH_FLAG_PAIRED sequences 2f and 2f + 1 are the mates of fragment f).  Every hit group sets the bit of its cell in d_marks (bit
+ * c & 31 of word c / 32; bits at and above the capacity are never set) and adds 1 to d_groups[value] (node_count uint64).  The
+ * kernels ADD: the caller zeroes d_marks and d_groups; two launches accumulate. */
+int nh_minimizer_mark_device(nh_engine *e, const void *d_text, uint64_t text_len, const void *d_seq_starts,
+                             const void *d_seq_lens, uint64_t n_frag, uint32_t flags, void *d_marks, void *d_groups, void *stream);
+/* d_counts[value] (node_count uint64, zeroed by the caller) grows by the marked cells of that value; d_marks NULL: by all its cells. */
+int nh_minimizer_count_device(nh_engine *e, const void *d_marks, void *d_counts, void *stream);
+
+/*
  * Database builder (--build-db; nohuman_amd/csrc/nh_build.hip): FASTA in, a kraken2 database directory out (hash.k2d, opts.k2d,
  * taxo.k2d), built on the GPU.  What kraken2-build does for ONE taxon at the default geometry, and nothing more: k = 35, l = 31,
  * the default spaced-seed and toggle masks, revcom_version 1, dna_db 1, minimum_acceptable_hash_value 0, linear probing -- the

@@ -74,6 +74,17 @@ class nh_taxon_out(C.Structure):
     _fields_ = [("taxid", C.c_uint64), ("out1", C.c_char_p), ("out2", C.c_char_p), ("fragments", C.c_uint64)]
 
 
+class nh_taxon_minimizers(C.Structure):
+    _fields_ = [("taxid", C.c_uint64), ("reads_clade", C.c_uint64), ("reads_own", C.c_uint64), ("minimizers_clade", C.c_uint64),
+                ("minimizers_own", C.c_uint64), ("distinct_clade", C.c_uint64), ("distinct_own", C.c_uint64),
+                ("db_cells_clade", C.c_uint64), ("db_cells_own", C.c_uint64)]
+
+
+class nh_minimizer_data(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("in_report", C.c_int32), ("table", C.c_char_p),
+                ("taxa", C.POINTER(nh_taxon_minimizers)), ("taxa_cap", C.c_uint32), ("n_taxa", C.c_uint32)]
+
+
 class nh_build_args(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_fasta", C.c_uint32), ("fasta", C.POINTER(C.c_char_p)),
                 ("out_dir", C.c_char_p), ("taxid", C.c_uint64), ("taxon_name", C.c_char_p), ("load_factor", C.c_double),
@@ -173,6 +184,14 @@ SYMBOLS = {
                               C.POINTER(nh_read_stats), C.POINTER(nh_taxon_out), C.c_uint32, C.POINTER(nh_stats)]),
     "nh_run_engine_taxa": (C.c_int, [_P, C.POINTER(nh_run_args), C.POINTER(nh_run_extras), C.c_uint32, C.c_char_p,
                                      C.POINTER(nh_read_stats), C.POINTER(nh_taxon_out), C.c_uint32, C.POINTER(nh_stats)]),
+    "nh_run_mdata": (C.c_int, [C.POINTER(nh_run_args), C.POINTER(nh_run_extras), C.c_uint32, C.c_char_p, C.POINTER(nh_read_stats),
+                               C.POINTER(nh_taxon_out), C.c_uint32, C.POINTER(nh_minimizer_data), C.POINTER(nh_stats)]),
+    "nh_run_engine_mdata": (C.c_int, [_P, C.POINTER(nh_run_args), C.POINTER(nh_run_extras), C.c_uint32, C.c_char_p,
+                                      C.POINTER(nh_read_stats), C.POINTER(nh_taxon_out), C.c_uint32, C.POINTER(nh_minimizer_data),
+                                      C.POINTER(nh_stats)]),
+    "nh_minimizer_marks_bytes": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    "nh_minimizer_mark_device": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint64, C.c_uint32, _P, _P, _P]),
+    "nh_minimizer_count_device": (C.c_int, [_P, _P, _P, _P]),
     "nh_read_stats_write": (C.c_int, [C.POINTER(nh_read_stats), C.c_char_p]),
     "nh_build_db": (C.c_int, [C.POINTER(nh_build_args), C.POINTER(nh_build_stats)]),  # (or their _v2 / _v3 subclasses)
     "nh_build_check": (C.c_int, [C.POINTER(nh_build_args), C.POINTER(nh_build_stats)]),

@@ -230,6 +230,14 @@ struct RstatsArgs : QSeqSrc {
 hipError_t launch_rstats(const RstatsArgs &a, int n_cu, uint32_t max_workgroups, hipStream_t stream);
 // median and N50 of a set of read lengths given as (length, reads) in ascending order of length (nh_rstats.hip, host)
 void length_summary(const std::vector<std::pair<uint64_t, uint64_t>> &lens, uint64_t *median, uint64_t *n50);
+// Minimizer data (nh_mdata.hip; nh_run_mdata): k_mdata_mark behind the classifier sets, for every hit group of the batch, the bit of
+// the cell where the key was found in d_marks (mdata_mark_words() uint32) and adds the group to d_groups[value] (node_count
+// uint64); k_mdata_count adds the marked cells (d_marks NULL: all cells) per value to d_counts (node_count uint64).
+int mdata_check_db(const Engine *e);  // NH_OK, NH_EDB (a geometry the pass does not support: the field named) or NH_EINVAL (linear_probing 0)
+uint64_t mdata_mark_words(const Engine *e);
+hipError_t launch_mdata_mark(Engine *e, const void *d_text, uint64_t text_len, const void *d_seq_starts, const void *d_seq_lens, uint64_t n_frag,
+                             int mates, void *d_marks, void *d_groups, hipStream_t stream);
+hipError_t launch_mdata_count(Engine *e, const void *d_marks, void *d_counts, hipStream_t stream);
 // buffers kept between the runs of a process (nh_run.hip: page-locked batch text; nh_gunzip.hip: the gzip reader's HBM and
 // staging): emptied when an engine is closed
 void run_cache_trim();

@@ -191,9 +191,11 @@ struct TaxoView {
     }
 };
 
+// md_clade (kraken2's --report-minimizer-data; NULL: the report as it always was): {minimizers_clade, distinct_clade} per node, two
+// more columns behind the read counts
 static void report_dfs(FILE *f, const TaxoView &t, const std::vector<uint64_t> &clade,
                        const std::vector<uint64_t> &own, uint64_t total, uint64_t id, char rank_code,
-                       int rank_depth, int depth) {
+                       int rank_depth, int depth, const std::vector<uint64_t> *md_clade = nullptr) {
     if (clade[id] == 0) return;  // clades absent from the sample are not printed
     const std::string rank = t.ranks + t.field(id, 4);
     if (rank == "superkingdom" || rank == "domain") { rank_code = 'D'; rank_depth = 0; }
@@ -207,9 +209,9 @@ static void report_dfs(FILE *f, const TaxoView &t, const std::vector<uint64_t> &
     else rank_depth++;
     std::string rank_str(1, rank_code);
     if (rank_depth != 0) rank_str += std::to_string(rank_depth);
-    fprintf(f, "%6.2f\t%llu\t%llu\t%s\t%llu\t", 100.0 * (double)clade[id] / (double)total,
-            (unsigned long long)clade[id], (unsigned long long)own[id], rank_str.c_str(),
-            (unsigned long long)t.field(id, 5));
+    fprintf(f, "%6.2f\t%llu\t%llu\t", 100.0 * (double)clade[id] / (double)total, (unsigned long long)clade[id], (unsigned long long)own[id]);
+    if (md_clade) fprintf(f, "%llu\t%llu\t", (unsigned long long)md_clade[0][id], (unsigned long long)md_clade[1][id]);
+    fprintf(f, "%s\t%llu\t", rank_str.c_str(), (unsigned long long)t.field(id, 5));
     for (int i = 0; i < depth; i++) fputs("  ", f);
     fprintf(f, "%s\n", t.names + t.field(id, 3));
     const uint64_t first = t.field(id, 1), cnt = t.field(id, 2);
@@ -217,11 +219,10 @@ static void report_dfs(FILE *f, const TaxoView &t, const std::vector<uint64_t> &
     for (uint64_t i = 0; i < cnt; i++) kids[i] = first + i;
     std::stable_sort(kids.begin(), kids.end(),
                      [&](uint64_t x, uint64_t y) { return clade[x] > clade[y]; });
-    for (uint64_t c : kids) report_dfs(f, t, clade, own, total, c, rank_code, rank_depth, depth + 1);
+    for (uint64_t c : kids) report_dfs(f, t, clade, own, total, c, rank_code, rank_depth, depth + 1, md_clade);
 }
 
-static int write_report(const Engine *e, const char *path, const std::vector<uint64_t> &own,
-                        uint64_t total, uint64_t unclassified) {
+static TaxoView taxo_view(const Engine *e) {
     TaxoView t;
     const uint8_t *img = e->taxo_image.data();
     memcpy(&t.n, img + 8, 8);
@@ -230,17 +231,54 @@ static int write_report(const Engine *e, const char *path, const std::vector<uin
     t.nodes = img + 32;
     t.names = (const char *)(img + 32 + 56 * t.n);
     t.ranks = t.names + name_len;
+    return t;
+}
+
+static int write_report(const Engine *e, const char *path, const std::vector<uint64_t> &own,
+                        uint64_t total, uint64_t unclassified, const std::vector<uint64_t> *md_clade = nullptr) {
+    const TaxoView t = taxo_view(e);
     std::vector<uint64_t> clade(own);
     for (uint64_t i = t.n; i-- > 1;)  // children have larger ids than their parents
         if (clade[i]) clade[t.field(i, 0)] += clade[i];
     FILE *f = fopen(path, "w");
     if (!f) return set_error(NH_EIO, "cannot create %s", path);
     if (unclassified != 0)
-        fprintf(f, "%6.2f\t%llu\t%llu\tU\t0\tunclassified\n",
+        fprintf(f, "%6.2f\t%llu\t%llu\t%sU\t0\tunclassified\n",
                 100.0 * (double)unclassified / (double)total, (unsigned long long)unclassified,
-                (unsigned long long)unclassified);
-    if (t.n > 1 && total) report_dfs(f, t, clade, own, total, 1, 'R', -1, 0);
+                (unsigned long long)unclassified, md_clade ? "0\t0\t" : "");
+    if (t.n > 1 && total) report_dfs(f, t, clade, own, total, 1, 'R', -1, 0, md_clade);
     if (fclose(f) != 0) return set_error(NH_EIO, "write error on %s", path);
+    return NH_OK;
+}
+
+// Minimizer data (nh_run_mdata): the per-node numbers of a run -- own counts in, clade sums made here (children have larger ids
+// than their parents) -- the struct array and the table.
+struct MdataNumbers {
+    std::vector<uint64_t> v[8];  // reads, minimizers, distinct, db_cells: [2 * quantity] clade, [2 * quantity + 1] own
+};
+static void mdata_clades(const TaxoView &t, MdataNumbers &m) {
+    for (int q = 0; q < 4; q++) {
+        m.v[2 * q + 1].resize(t.n, 0);
+        m.v[2 * q] = m.v[2 * q + 1];
+        for (uint64_t i = t.n; i-- > 1;) {
+            const uint64_t p = t.field(i, 0);
+            if (p < i) m.v[2 * q][p] += m.v[2 * q][i];
+        }
+    }
+}
+static int write_mdata_table(const TaxoView &t, const MdataNumbers &m, const char *path) {
+    FILE *f = fopen(path, "w");
+    if (!f) return set_error(NH_EIO, "cannot create %s: %s", path, strerror(errno));
+    fputs("taxid\tname\treads_clade\treads_own\tminimizers_clade\tminimizers_own\tdistinct_clade\tdistinct_own\tdb_cells_clade\tdb_cells_own\tcoverage_pct\n", f);
+    for (uint64_t i = 1; i < t.n; i++) {
+        if (!m.v[0][i] && !m.v[2][i]) continue;
+        fprintf(f, "%llu\t%s", (unsigned long long)t.field(i, 5), t.names + t.field(i, 3));
+        for (int k = 0; k < 8; k++) fprintf(f, "\t%llu", (unsigned long long)m.v[k][i]);
+        if (m.v[6][i]) fprintf(f, "\t%.4f\n", 100.0 * (double)m.v[4][i] / (double)m.v[6][i]);
+        else fputs("\tNA\n", f);
+    }
+    const bool bad = ferror(f) != 0;
+    if (fclose(f) != 0 || bad) return set_error(NH_EIO, "cannot write %s", path);
     return NH_OK;
 }
 
@@ -374,6 +412,7 @@ struct Slot {  // pinned host + device buffers of one in-flight batch
     size_t cap_qtext = 0;
     hipEvent_t qev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around k_qmask
     hipEvent_t rev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around k_rstats (runs with read statistics)
+    hipEvent_t mev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around k_mdata_mark (runs with minimizer data)
 };
 
 // what a buffer that must hold `need` is allocated with: some room, so that batches a little larger do not reallocate
@@ -511,7 +550,7 @@ static void slot_free(Slot &s) {
         if (p) (void)hipFree(p);
     for (void *p : {s.d_qtext, (void *)s.d_qcnt})
         if (p) (void)hipFree(p);
-    for (hipEvent_t ev : {s.qev[0], s.qev[1], s.rev[0], s.rev[1]})
+    for (hipEvent_t ev : {s.qev[0], s.qev[1], s.rev[0], s.rev[1], s.mev[0], s.mev[1]})
         if (ev) (void)hipEventDestroy(ev);
     for (void *p : {(void *)s.h_off, (void *)s.h_len, (void *)s.h_res, (void *)s.h_taxa, (void *)s.h_taxa_off, (void *)s.h_flag})
         if (p) (void)hipHostFree(p);
@@ -593,6 +632,7 @@ struct RunState {
     bool paired, want_k;
     // results of the run
     uint64_t total = 0, classified = 0, total_bases = 0;
+    uint64_t hit_groups = 0;  // the fragments' nh_result.hit_groups summed: the checker of the minimizer data's count
     // split runs (NOHUMAN_TRACE): what the classified-out builder made, and the bytes of record text the run copied back to
     // the host -- classified-out text for host encoders, and batches of the reader on the GPU fetched for the other side
     uint64_t human_records = 0, human_bytes = 0;
@@ -615,6 +655,7 @@ struct RunState {
     std::vector<uint64_t> len_hist[2][2];
     std::map<uint64_t, uint64_t> len_long[2][2];
     double rstats_kernel_ms = 0;
+    double mdata_kernel_ms = 0;  // NOHUMAN_TRACE: k_mdata_mark, by events on the slots' streams
     std::atomic<uint64_t> text_fetched{0};
     std::vector<uint64_t> dev_counts;  // per device {fragments, classified, bases, 0} as the writer saw them (checker)
     std::vector<uint64_t *> d_run_counters;  // per device: the counters the classify kernels of THIS run add to (HBM)
@@ -894,7 +935,7 @@ static void format_batch(RunState *rs, const Batch &b, const Slot &s, OutFile &o
     const char *t1 = b.fetch1 ? b.fetch1.get() : b.h1->text.data();
     const char *t2 = !rs->paired ? nullptr : b.fetch2 ? b.fetch2.get() : b.h2->text.data();
     char tmp[128];
-    uint64_t bases = 0, classified = 0;
+    uint64_t bases = 0, classified = 0, hit_groups = 0;
     const RecRef *const R1 = b.h1->recs.data() + b.off1;
     const RecRef *const R2 = rs->paired ? b.h2->recs.data() + b.off2 : nullptr;
     for (size_t i = 0; i < b.n; i++) {
@@ -902,6 +943,7 @@ static void format_batch(RunState *rs, const Batch &b, const Slot &s, OutFile &o
         const uint32_t call = s.h_res[i].call;
         const bool is_class = call != 0;
         classified += is_class;
+        hit_groups += s.h_res[i].hit_groups;
         rs->call_counts[call] += is_class;
         bases += r1.slen + (rs->paired ? R2[i].slen : 0);
         if (emit && is_class == keep_class) {
@@ -949,6 +991,7 @@ static void format_batch(RunState *rs, const Batch &b, const Slot &s, OutFile &o
     if (rs->want_k) ok.add_scratch(0);
     rs->total += b.n;
     rs->classified += classified;
+    rs->hit_groups += hit_groups;
     rs->total_bases += bases;
     uint64_t *dc = &rs->dev_counts[4 * (size_t)b.dev_index];
     dc[0] += b.n;
@@ -1044,22 +1087,58 @@ static int check_list_args(const nh_run_args *a, const char *h1, const char *h2,
     return NH_OK;
 }
 
-// nh_run_rstats' table, checked before any device is touched: it names no input and no other output of the run
-static int check_rstats_args(const nh_run_args *a, const nh_run_extras *x, const char *path) {
-    if (!path) return NH_OK;
-    if (!a) return set_error(NH_EINVAL, "nh_run_rstats: null arguments");
-    if (!path[0]) return set_error(NH_EINVAL, "nh_run_rstats: read_stats_path is an empty path");
+// The file of a run that `path` names -- the same path, or the same device and inode: an input (*input set) or an output, among them
+// the read statistics table and the per-taxon files where given.  NULL: none.
+static const char *run_file_named(const nh_run_args *a, const nh_run_extras *x, const char *rs_path, const nh_taxon_out *outs, uint32_t n_outs,
+                                  const char *path, bool *input) {
     struct stat sl;
     const bool ls = stat(path, &sl) == 0 && S_ISREG(sl.st_mode);
     auto same = [&](const char *p) {
         struct stat sp;
         return p && p[0] && (!strcmp(p, path) || (ls && stat(p, &sp) == 0 && sp.st_dev == sl.st_dev && sp.st_ino == sl.st_ino));
     };
+    *input = true;
     for (const char *p : {a->in1, a->in2})
-        if (same(p)) return set_error(NH_EINVAL, "nh_run_rstats: the read statistics table %s is the input %s", path, p);
+        if (same(p)) return p;
+    *input = false;
     for (const char *p : {a->out1, a->out2, a->kraken_output, a->report, x ? x->human_out1 : nullptr, x ? x->human_out2 : nullptr,
-                          x ? x->calls : nullptr, x ? x->human_ids : nullptr})
-        if (same(p)) return set_error(NH_EINVAL, "nh_run_rstats: the read statistics table %s is also the output %s", path, p);
+                          x ? x->calls : nullptr, x ? x->human_ids : nullptr, rs_path})
+        if (same(p)) return p;
+    for (uint32_t i = 0; outs && i < n_outs; i++)
+        for (const char *p : {outs[i].out1, outs[i].out2})
+            if (same(p)) return p;
+    return nullptr;
+}
+
+// nh_run_rstats' table, checked before any device is touched: it names no input and no other output of the run
+static int check_rstats_args(const nh_run_args *a, const nh_run_extras *x, const char *path) {
+    if (!path) return NH_OK;
+    if (!a) return set_error(NH_EINVAL, "nh_run_rstats: null arguments");
+    if (!path[0]) return set_error(NH_EINVAL, "nh_run_rstats: read_stats_path is an empty path");
+    bool input = false;
+    if (const char *p = run_file_named(a, x, nullptr, nullptr, 0, path, &input))
+        return set_error(NH_EINVAL, input ? "nh_run_rstats: the read statistics table %s is the input %s" : "nh_run_rstats: the read statistics table %s is also the output %s",
+                         path, p);
+    return NH_OK;
+}
+
+// nh_run_mdata's own arguments, checked before any device is touched: the struct, and a table that names no input and no other
+// output of the run
+static int check_mdata_args(const nh_run_args *a, const nh_run_extras *x, const char *rs_path, const nh_taxon_out *outs, uint32_t n_outs,
+                            const nh_minimizer_data *md) {
+    if (!md) return NH_OK;
+    if (md->struct_size < sizeof(nh_minimizer_data))
+        return set_error(NH_EINVAL, "nh_run_mdata: struct_size %u is smaller than nh_minimizer_data (%zu bytes)", md->struct_size, sizeof(nh_minimizer_data));
+    if (!a) return set_error(NH_EINVAL, "nh_run_mdata: null arguments");
+    if (md->in_report && !(a->report && a->report[0])) return set_error(NH_EINVAL, "nh_run_mdata: in_report is set without a report (args->report)");
+    if (md->taxa && md->taxa_cap == 0) return set_error(NH_EINVAL, "nh_run_mdata: taxa is given with taxa_cap 0");
+    if (md->table) {
+        if (!md->table[0]) return set_error(NH_EINVAL, "nh_run_mdata: table is an empty path");
+        bool input = false;
+        if (const char *p = run_file_named(a, x, rs_path, outs, n_outs, md->table, &input))
+            return set_error(NH_EINVAL, input ? "nh_run_mdata: the minimizer table %s is the input %s" : "nh_run_mdata: the minimizer table %s is also the output %s",
+                             md->table, p);
+    }
     return NH_OK;
 }
 
@@ -1117,10 +1196,14 @@ static int check_taxon_args(const nh_run_args *a, const nh_run_extras *x, const 
 // rs_path / rs_out set (nh_run_rstats): read statistics -- k_rstats behind the classifier on the slot's stream adds every sequence
 // of the batch to the device's four accumulators (nh_rstats.hip), fetched once, at the end; the writer keeps the lengths by class
 // for median and N50.  Both NULL: nothing of this runs.
+// md asking for something (nh_run_mdata): minimizer data -- k_mdata_mark behind the classifier on the slot's stream marks the cell of
+// every hit group in the device's bitmap and counts the group for its taxon (nh_mdata.hip), on the text the classifier read;
+// k_mdata_count reads the bitmap once, at the end (several devices: the union of their bitmaps -- a minimizer hit on two devices is
+// one).  NULL, or nothing asked for: nothing of this runs.
 int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_stats *stats, const char *hout1 = nullptr,
                 const char *hout2 = nullptr, bool mask = false, const char *calls = nullptr, const char *ids = nullptr,
                 uint32_t minq = 0, const char *rs_path = nullptr, nh_read_stats *rs_out = nullptr, nh_taxon_out *touts = nullptr,
-                uint32_t n_touts = 0) {
+                uint32_t n_touts = 0, nh_minimizer_data *md = nullptr) {
     if (!a || !a->in1 || !a->out1) return set_error(NH_EINVAL, "nh_run: in1 and out1 are required");
     if (engines.empty()) return set_error(NH_EINVAL, "nh_run: no engine");
     const bool split = hout1 != nullptr;
@@ -1129,6 +1212,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
     const bool lists = calls || ids;
     const bool qm = minq > 0;
     const bool rst = rs_path || rs_out;
+    const bool mdt = md && (md->in_report || md->table || md->taxa);
     if (minq > 93) return set_error(NH_EINVAL, "nh_run: minimum base quality %u is not in 0..93 (Phred+33)", minq);
     if (lists) {
         const int vrc = check_list_args(a, hout1, hout2, calls, ids);
@@ -1175,6 +1259,13 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
             const uint32_t p = e0->parent[i];
             bin_of[i] = own[i] >= 0 ? (uint8_t)own[i] : (i > 1 && p >= 1 && p < i) ? bin_of[p] : other >= 0 ? (uint8_t)other : (uint8_t)0xFF;
         }
+    }
+    if (mdt) {  // (the database is open: before any input is read or any output created)
+        nh_run_extras x{};
+        x.human_out1 = hout1, x.human_out2 = hout2, x.calls = calls, x.human_ids = ids;
+        int vrc = check_mdata_args(a, &x, rs_path, touts, n_touts, md);
+        for (size_t g = 0; g < engines.size() && !vrc; g++) vrc = mdata_check_db(engines[g]);
+        if (vrc) return vrc;
     }
     if (split || lists || taxa)
         for (Engine *e : engines) {
@@ -1304,10 +1395,20 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
     // read statistics: one block of four accumulators per device of the run, zeroed with min_len all-ones
     std::vector<unsigned long long *> d_racc((size_t)G, nullptr);
     std::vector<nh_read_class> racc;  // the devices' blocks summed: [class][mate]
+    // minimizer data: one zeroed bitmap (a bit a cell) and one array of hit groups per node and device, for the whole run
+    std::vector<uint32_t *> d_marks((size_t)G, nullptr);
+    std::vector<unsigned long long *> d_groups((size_t)G, nullptr);
+    const size_t md_nodes = engines[0]->external.size();
+    const size_t md_mark_bytes = mdt ? (size_t)mdata_mark_words(engines[0]) * 4 : 0;
+    MdataNumbers mdn;  // [3] minimizers_own, [5] distinct_own, [7] db_cells_own, filled at the end of the run
+    double md_count_ms = 0;
     auto free_run_counters = [&] {
         for (int g = 0; g < G; g++) {
-            if (!rs.d_run_counters[g] && !d_racc[g] && !d_bin_of[g]) continue;
+            if (!rs.d_run_counters[g] && !d_racc[g] && !d_bin_of[g] && !d_marks[g] && !d_groups[g]) continue;
             (void)dev_set(engines[g]->device);
+            if (d_marks[g]) (void)hipFree(d_marks[g]);
+            if (d_groups[g]) (void)hipFree(d_groups[g]);
+            d_marks[g] = nullptr, d_groups[g] = nullptr;
             if (rs.d_run_counters[g]) (void)hipFree(rs.d_run_counters[g]);
             if (d_racc[g]) (void)hipFree(d_racc[g]);
             if (d_bin_of[g]) (void)hipFree(d_bin_of[g]);
@@ -1335,6 +1436,20 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 return set_error(NH_EDEVICE, "cannot allocate the read statistics' accumulators on device %d", engines[g]->device);
             }
         }
+        if (mdt) {
+            // (the slots' streams do not wait for the legacy stream: the zeroes are in place before the first batch)
+            if (dev_malloc((void **)&d_marks[g], std::max<size_t>(md_mark_bytes, 4)) != hipSuccess ||
+                dev_malloc((void **)&d_groups[g], std::max<size_t>(md_nodes, 1) * 8) != hipSuccess) {
+                free_run_counters();
+                return set_error(NH_EOOM, "minimizer data: cannot allocate the bitmap of %zu bytes and %zu counters on device %d", md_mark_bytes, md_nodes,
+                                 engines[g]->device);
+            }
+            if (hipMemset(d_marks[g], 0, std::max<size_t>(md_mark_bytes, 4)) != hipSuccess ||
+                hipMemset(d_groups[g], 0, std::max<size_t>(md_nodes, 1) * 8) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+                free_run_counters();
+                return set_error(NH_EDEVICE, "minimizer data: cannot clear the bitmap on device %d", engines[g]->device);
+            }
+        }
     }
     // stream slots a device: two keep the classifier busy; a third lets the copy of a batch's text back to the host (batches
     // born on the GPU, outputs written by the host) run while the writer is still busy with the batch before; a fourth is
@@ -1358,7 +1473,9 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
             (qm && getenv("NOHUMAN_TRACE") &&
              (hipEventCreate(&slots[i].qev[0]) != hipSuccess || hipEventCreate(&slots[i].qev[1]) != hipSuccess)) ||
             (rst && getenv("NOHUMAN_TRACE") &&
-             (hipEventCreate(&slots[i].rev[0]) != hipSuccess || hipEventCreate(&slots[i].rev[1]) != hipSuccess))) {
+             (hipEventCreate(&slots[i].rev[0]) != hipSuccess || hipEventCreate(&slots[i].rev[1]) != hipSuccess)) ||
+            (mdt && getenv("NOHUMAN_TRACE") &&
+             (hipEventCreate(&slots[i].mev[0]) != hipSuccess || hipEventCreate(&slots[i].mev[1]) != hipSuccess))) {
             for (auto &s : slots) slot_free(s);
             free_run_counters();
             return set_error(NH_EDEVICE, "cannot create streams");
@@ -1664,6 +1781,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                     add_event_ms(s.lists.ev, &rs.list_kernel_ms);
                     add_event_ms(s.qev, &rs.qmask_kernel_ms);
                     add_event_ms(s.rev, &rs.rstats_kernel_ms);
+                    add_event_ms(s.mev, &rs.mdata_kernel_ms);
                     // read statistics: every length of the batch, by the class of its fragment and its mate
                     for (size_t i = 0; rst && i < b.n; i++) {
                         const int c = s.h_res[i].call != 0;
@@ -1966,6 +2084,13 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 if (s.rev[1] && he == hipSuccess) he = hipEventRecord(s.rev[1], s.stream);
                 if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("read statistics: ") + hipGetErrorString(he));
             }
+            if (!rs.failed() && mdt) {  // minimizer data, marked behind the classifier on the same stream: the text the classifier read
+                if (s.mev[0]) (void)hipEventRecord(s.mev[0], s.stream);
+                he = launch_mdata_mark(s.e, qm ? s.d_qtext : s.d_text, ntext, s.d_off, s.d_len, b.n, mates, d_marks[(size_t)(si / NS)],
+                                       d_groups[(size_t)(si / NS)], s.stream);
+                if (s.mev[1] && he == hipSuccess) he = hipEventRecord(s.mev[1], s.stream);
+                if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("minimizer data: ") + hipGetErrorString(he));
+            }
             if (!rs.failed() && lists) {  // the calls table and the human ids, built behind the classifier on the same stream
                 CallsArgs ca{};
                 ca.text = (const char *)s.d_text;
@@ -2136,6 +2261,47 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
             }
         }
     }
+    if (mdt && rs.err_code == NH_OK) {
+        // (every stream has been synchronised.)  The hit groups of the devices are added; their bitmaps are NOT counted one by one
+        // -- a minimizer hit on two devices is one -- but ORed on the host and the union counted on the first engine.
+        Engine *e0 = engines[0];
+        const size_t words = md_mark_bytes / 4;
+        std::vector<unsigned long long> part(md_nodes), sum(md_nodes, 0);
+        hipError_t he = hipSuccess;
+        for (int g = 0; g < G && he == hipSuccess; g++) {
+            he = dev_set(engines[g]->device);
+            if (he == hipSuccess) he = hipMemcpy(part.data(), d_groups[g], md_nodes * 8, hipMemcpyDeviceToHost);
+            for (size_t i = 0; i < md_nodes; i++) sum[i] += part[i];
+        }
+        if (he == hipSuccess && G > 1) {
+            std::vector<uint32_t> all(words, 0), one(words);
+            for (int g = 0; g < G && he == hipSuccess; g++) {
+                he = dev_set(engines[g]->device);
+                if (he == hipSuccess) he = hipMemcpy(one.data(), d_marks[g], words * 4, hipMemcpyDeviceToHost);
+                for (size_t i = 0; i < words; i++) all[i] |= one[i];
+            }
+            if (he == hipSuccess) he = dev_set(e0->device);
+            if (he == hipSuccess) he = hipMemcpy(d_marks[0], all.data(), words * 4, hipMemcpyHostToDevice);
+        }
+        mdn.v[3].assign(sum.begin(), sum.end());
+        // two counts with the array of hit groups as their bins: the marked cells, then all cells
+        hipEvent_t cev[2] = {nullptr, nullptr};
+        if (he == hipSuccess) he = dev_set(e0->device);
+        if (he == hipSuccess && getenv("NOHUMAN_TRACE") && (hipEventCreate(&cev[0]) != hipSuccess || hipEventCreate(&cev[1]) != hipSuccess)) he = hipErrorUnknown;
+        for (int pass = 0; pass < 2 && he == hipSuccess; pass++) {
+            he = hipMemsetAsync(d_groups[0], 0, md_nodes * 8, e0->stream);
+            if (he == hipSuccess && cev[0]) he = hipEventRecord(cev[0], e0->stream);
+            if (he == hipSuccess) he = launch_mdata_count(e0, pass == 0 ? d_marks[0] : nullptr, d_groups[0], e0->stream);
+            if (he == hipSuccess && cev[1]) he = hipEventRecord(cev[1], e0->stream);
+            if (he == hipSuccess) he = hipStreamSynchronize(e0->stream);
+            if (he == hipSuccess) he = hipMemcpy(part.data(), d_groups[0], md_nodes * 8, hipMemcpyDeviceToHost);
+            mdn.v[pass == 0 ? 5 : 7].assign(part.begin(), part.end());
+            if (he == hipSuccess && pass == 0) add_event_ms(cev, &md_count_ms);
+        }
+        for (hipEvent_t ev : cev)
+            if (ev) (void)hipEventDestroy(ev);
+        if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("minimizer data, counting the bitmap: ") + hipGetErrorString(he));
+    }
     for (auto &s : slots) slot_free(s);
     if (const char *tr = getenv("NOHUMAN_TRACE")) {
         if (tr[0] == '1') {
@@ -2169,6 +2335,13 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
             if (rst && racc.size() == 4)
                 fprintf(stderr, "[nohuman trace] rstats: %llu bases, kernel %.3f ms\n",
                         (unsigned long long)(racc[0].bases + racc[1].bases + racc[2].bases + racc[3].bases), rs.rstats_kernel_ms);
+            if (mdt && rs.err_code == NH_OK) {
+                unsigned long long groups = 0, distinct = 0;
+                for (uint64_t v : mdn.v[3]) groups += v;
+                for (uint64_t v : mdn.v[5]) distinct += v;
+                fprintf(stderr, "[nohuman trace] minimizer data: %llu hit groups on %llu distinct minimizers, k_mdata_mark %.3f ms, k_mdata_count %.3f ms\n", groups,
+                        distinct, rs.mdata_kernel_ms, md_count_ms);
+            }
             if (g_pageable_batches.load())
                 fprintf(stderr, "[nohuman trace] %d batch buffers could not be page-locked (pageable memory used)\n",
                         g_pageable_batches.load());
@@ -2236,8 +2409,20 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
         if (crc) return crc;
     }
 
+    const TaxoView mdview = taxo_view(engines[0]);
+    if (mdt) {
+        mdn.v[1] = rs.call_counts;
+        mdata_clades(mdview, mdn);
+        // (the classifier's own count of hit groups, fragment by fragment, is the checker of what the pass counted)
+        uint64_t groups = 0;
+        for (uint64_t i = 1; i < mdview.n; i++) groups += mdn.v[3][i];
+        if (groups != rs.hit_groups)
+            return set_error(NH_EDEVICE, "minimizer data: the pass counted %llu hit groups, the classifier %llu", (unsigned long long)groups,
+                             (unsigned long long)rs.hit_groups);
+    }
+    const std::vector<uint64_t> md_report[2] = {mdn.v[2], mdn.v[4]};
     if (a->report && a->report[0] &&
-        (rc = write_report(engines[0], a->report, rs.call_counts, rs.total, rs.total - rs.classified)))
+        (rc = write_report(engines[0], a->report, rs.call_counts, rs.total, rs.total - rs.classified, mdt && md->in_report ? md_report : nullptr)))
         return rc;
     {  // (side by side as well: the last chunks of two GPU encoders, their buffers' release)
         int rc2 = NH_OK;
@@ -2311,6 +2496,16 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
         if (rs_out) *rs_out = out;
     }
     for (int k = 0; k < K; k++) touts[k].fragments = rs.taxon_frags[k];
+    if (mdt) {
+        if (md->table && (rc = write_mdata_table(mdview, mdn, md->table))) return rc;
+        md->n_taxa = mdview.n > 1 ? (uint32_t)(mdview.n - 1) : 0;
+        for (uint64_t i = 1; md->taxa && i < mdview.n && i - 1 < md->taxa_cap; i++) {
+            nh_taxon_minimizers &o = md->taxa[i - 1];
+            o.taxid = mdview.field(i, 5);
+            o.reads_clade = mdn.v[0][i], o.reads_own = mdn.v[1][i], o.minimizers_clade = mdn.v[2][i], o.minimizers_own = mdn.v[3][i];
+            o.distinct_clade = mdn.v[4][i], o.distinct_own = mdn.v[5][i], o.db_cells_clade = mdn.v[6][i], o.db_cells_own = mdn.v[7][i];
+        }
+    }
     if (stats) {
         nh_stats st;
         memset(&st, 0, sizeof st);
@@ -2326,9 +2521,10 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
 
 int run_engine(Engine *e, const nh_run_args *a, nh_stats *stats, const char *hout1 = nullptr, const char *hout2 = nullptr,
                bool mask = false, const char *calls = nullptr, const char *ids = nullptr, uint32_t minq = 0,
-               const char *rs_path = nullptr, nh_read_stats *rs_out = nullptr, nh_taxon_out *touts = nullptr, uint32_t n_touts = 0) {
+               const char *rs_path = nullptr, nh_read_stats *rs_out = nullptr, nh_taxon_out *touts = nullptr, uint32_t n_touts = 0,
+               nh_minimizer_data *md = nullptr) {
     std::vector<Engine *> v{e};
-    return run_engines(v, a, stats, hout1, hout2, mask, calls, ids, minq, rs_path, rs_out, touts, n_touts);
+    return run_engines(v, a, stats, hout1, hout2, mask, calls, ids, minq, rs_path, rs_out, touts, n_touts, md);
 }
 
 // nh_run_minq's own argument, checked before any device is touched: the highest printable quality is '~', Phred 93
@@ -2363,6 +2559,14 @@ int check_rstats(const nh_run_args *a, const nh_run_extras *x, uint32_t minq, co
 int check_taxa(const nh_run_args *a, const nh_run_extras *x, uint32_t minq, const char *rs_path, const nh_taxon_out *outs, uint32_t n) {
     int rc = check_rstats(a, x, minq, rs_path);
     if (!rc) rc = check_taxon_args(a, x, rs_path, outs, n);
+    return rc;
+}
+
+// nh_run_mdata's arguments, checked before any device is touched: nh_run_taxa's, then the struct and the table's path
+int check_mdata(const nh_run_args *a, const nh_run_extras *x, uint32_t minq, const char *rs_path, const nh_taxon_out *outs, uint32_t n,
+                const nh_minimizer_data *md) {
+    int rc = check_taxa(a, x, minq, rs_path, outs, n);
+    if (!rc) rc = check_mdata_args(a, x, rs_path, outs, n, md);
     return rc;
 }
 
@@ -2428,6 +2632,19 @@ int nh_run_engine_taxa(nh_engine *e, const nh_run_args *args, const nh_run_extra
                               outs, n_outs);
     return nh::run_engine((nh::Engine *)e, args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls,
                           extras->human_ids, min_base_quality, read_stats_path, read_stats, outs, n_outs);
+}
+
+int nh_run_engine_mdata(nh_engine *e, const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality,
+                        const char *read_stats_path, nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs, nh_minimizer_data *md,
+                        nh_stats *stats) {
+    const int rc = nh::check_mdata(args, extras, min_base_quality, read_stats_path, outs, n_outs, md);
+    if (rc) return rc;
+    if (!e) return nh::set_error(NH_EINVAL, "null engine");
+    if (!extras)
+        return nh::run_engine((nh::Engine *)e, args, stats, nullptr, nullptr, false, nullptr, nullptr, min_base_quality, read_stats_path, read_stats,
+                              outs, n_outs, md);
+    return nh::run_engine((nh::Engine *)e, args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls,
+                          extras->human_ids, min_base_quality, read_stats_path, read_stats, outs, n_outs, md);
 }
 
 int nh_fastx_scan(const char *path, uint64_t *n_records, uint64_t *n_bases, uint64_t *digest) {
@@ -2576,7 +2793,7 @@ int nh_debug_reader_dump(const char *path, int reader, int device, uint64_t batc
 // round-robin, outputs stay in input order, the counts are summed on the host.
 static int run_devices(const nh_run_args *args, nh_stats *stats, const char *hout1, const char *hout2, bool mask = false,
                        const char *calls = nullptr, const char *ids = nullptr, uint32_t minq = 0, const char *rs_path = nullptr,
-                       nh_read_stats *rs_out = nullptr, nh_taxon_out *touts = nullptr, uint32_t n_touts = 0) {
+                       nh_read_stats *rs_out = nullptr, nh_taxon_out *touts = nullptr, uint32_t n_touts = 0, nh_minimizer_data *md = nullptr) {
     if (!args || !args->db_dir) return nh::set_error(NH_EINVAL, "nh_run: db_dir is required");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -2612,7 +2829,7 @@ static int run_devices(const nh_run_args *args, nh_stats *stats, const char *hou
     }
     const double t_load = since(t_begin);
     const auto t_run = std::chrono::steady_clock::now();
-    if (!rc) rc = nh::run_engines(engines, args, stats, hout1, hout2, mask, calls, ids, minq, rs_path, rs_out, touts, n_touts);
+    if (!rc) rc = nh::run_engines(engines, args, stats, hout1, hout2, mask, calls, ids, minq, rs_path, rs_out, touts, n_touts, md);
     const double s_run = since(t_run);
     std::string keep = nh::g_last_error;
     const auto t_close = std::chrono::steady_clock::now();
@@ -2670,6 +2887,16 @@ int nh_run_taxa(const nh_run_args *args, const nh_run_extras *extras, uint32_t m
         return run_devices(args, stats, nullptr, nullptr, false, nullptr, nullptr, min_base_quality, read_stats_path, read_stats, outs, n_outs);
     return run_devices(args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls, extras->human_ids,
                        min_base_quality, read_stats_path, read_stats, outs, n_outs);
+}
+
+int nh_run_mdata(const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality, const char *read_stats_path,
+                 nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs, nh_minimizer_data *md, nh_stats *stats) {
+    const int rc = nh::check_mdata(args, extras, min_base_quality, read_stats_path, outs, n_outs, md);  // (before any device is touched)
+    if (rc) return rc;
+    if (!extras)
+        return run_devices(args, stats, nullptr, nullptr, false, nullptr, nullptr, min_base_quality, read_stats_path, read_stats, outs, n_outs, md);
+    return run_devices(args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls, extras->human_ids,
+                       min_base_quality, read_stats_path, read_stats, outs, n_outs, md);
 }
 
 }  // extern "C"

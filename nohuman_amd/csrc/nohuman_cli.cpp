@@ -221,6 +221,8 @@ struct Args {
     std::string calls, human_ids;  // read lists (nh_run_ex): a table line per read; the ids of the human reads
     unsigned min_base_quality = 0;  // kraken2's --minimum-base-quality (nh_run_minq); 0: off
     std::string read_stats;         // the read statistics table (nh_run_rstats)
+    bool report_minimizer_data = false;  // kraken2's flag: two more columns in the report (nh_run_mdata)
+    std::string minimizer_table;         // the minimizer table (nh_run_mdata)
     // per-taxon outputs (nh_run_taxa): the selectors in the order given -- taxid (0: `other`), the path as given ('#' in it: the mate)
     std::vector<std::pair<unsigned long long, std::string>> taxon_out;
     bool has_out1 = false, has_out2 = false, check = false, download = false, list = false, human = false;
@@ -263,6 +265,9 @@ static void usage(FILE *f) {
           "      --minimum-base-quality <INT>  Kraken2 minimum base quality: classify FASTQ bases with a lower Phred+33 quality as ambiguous (0-93; the reads written keep their bases) [default: 0]\n"
           "  -k, --kraken-output <FILE>   Write the Kraken2 read classification output to a file\n"
           "  -r, --kraken-report <FILE>   Write the Kraken2 report with aggregate counts/clade to file\n"
+          "      --report-minimizer-data  Report, per clade, the minimizer hits of the reads and how many distinct minimizers they were, as columns 4 and 5 of the Kraken2 report "
+          "(many reads on few distinct minimizers mark a false positive; counted exactly on the GPU); needs --kraken-report\n"
+          "      --minimizer-table <FILE> Write a table with, per taxon: reads, minimizer hits, distinct minimizers and cells of the database, own and clade, and the coverage in percent\n"
           "      --calls <FILE>           Write a table with one line per read: C/U, id, taxid, length(s), k-mers, clade hits (hits / k-mers is the confidence -C thresholds), hit groups\n"
           "      --read-stats <FILE>      Write a QC table of all, non-human and human reads per mate: reads, bases, min/mean/median/max length, N50, GC %, other bases, Q20 %, Q30 %, mean quality (counted on the GPU in the same pass)\n"
           "      --human-ids <FILE>       Write the ids of the human reads, one per line\n"
@@ -369,6 +374,8 @@ static Args parse_args(int argc, char **argv) {
         else if (s == "--calls") a.calls = val();
         else if (s == "--human-ids") a.human_ids = val();
         else if (s == "--read-stats") a.read_stats = val();
+        else if (s == "--report-minimizer-data") a.report_minimizer_data = true;
+        else if (s == "--minimizer-table") a.minimizer_table = val();
         else if (s == "--taxon-out") {
             const std::string t = val();
             const size_t colon = t.find(':');
@@ -430,7 +437,8 @@ static Args parse_args(int argc, char **argv) {
         if (!a.input.empty()) arg_error("the argument '--build-db <DIR>' cannot be used with read inputs ('%s'): the genome is given with '--reference <FILE>'", a.input[0].c_str());
         const char *out_flag = a.has_out1 ? "--out1" : a.has_out2 ? "--out2" : a.has_human_out1 ? "--human-out1" : a.has_human_out2 ? "--human-out2"
                              : !a.kraken_output.empty() ? "--kraken-output" : !a.kraken_report.empty() ? "--kraken-report" : !a.calls.empty() ? "--calls"
-                             : !a.human_ids.empty() ? "--human-ids" : !a.read_stats.empty() ? "--read-stats" : a.has_type ? "--output-type"
+                             : !a.human_ids.empty() ? "--human-ids" : !a.read_stats.empty() ? "--read-stats" : a.report_minimizer_data ? "--report-minimizer-data"
+                             : !a.minimizer_table.empty() ? "--minimizer-table" : a.has_type ? "--output-type"
                              : a.bgzf ? "--bgzf" : a.mask ? "--mask" : a.human ? "--human" : !a.taxon_out.empty() ? "--taxon-out" : nullptr;
         if (out_flag) arg_error("the argument '--build-db <DIR>' cannot be used with '%s'", out_flag);
         for (const std::string &r : a.reference)
@@ -475,7 +483,8 @@ static Args parse_args(int argc, char **argv) {
                 const char *other = (a.has_out1 && p == a.out1) ? "--out1" : (a.has_out2 && p == a.out2) ? "--out2"
                                   : (a.has_human_out1 && p == a.human_out1) ? "--human-out1" : (a.has_human_out2 && p == a.human_out2) ? "--human-out2"
                                   : p == a.kraken_output ? "--kraken-output" : p == a.kraken_report ? "--kraken-report" : p == a.calls ? "--calls"
-                                  : p == a.human_ids ? "--human-ids" : p == a.read_stats ? "--read-stats" : nullptr;
+                                  : p == a.human_ids ? "--human-ids" : p == a.read_stats ? "--read-stats"
+                                  : p == a.minimizer_table ? "--minimizer-table" : nullptr;
                 if (other) arg_error("the argument '--taxon-out <TAXID|other>:<PATH>' names the same file as '%s': %s", other, p.c_str());
                 for (const std::string &q : mine)
                     if (p == q) arg_error("the argument '--taxon-out <TAXID|other>:<PATH>' names the same file twice: %s", p.c_str());
@@ -491,6 +500,18 @@ static Args parse_args(int argc, char **argv) {
         if (!a.read_stats.empty() && a.read_stats == *o)
             arg_error("the argument '--read-stats <FILE>' names the same file as '%s <FILE>': %s", o == &a.calls ? "--calls" : "--human-ids",
                       a.read_stats.c_str());
+    if (a.report_minimizer_data && a.kraken_report.empty())
+        arg_error("the argument '--report-minimizer-data' needs '--kraken-report <FILE>': its two columns go into the report");
+    if (!a.minimizer_table.empty()) {
+        const std::string &p = a.minimizer_table;
+        const char *other = (a.has_out1 && p == a.out1) ? "--out1" : (a.has_out2 && p == a.out2) ? "--out2"
+                          : (a.has_human_out1 && p == a.human_out1) ? "--human-out1" : (a.has_human_out2 && p == a.human_out2) ? "--human-out2"
+                          : p == a.kraken_output ? "--kraken-output" : p == a.kraken_report ? "--kraken-report" : p == a.calls ? "--calls"
+                          : p == a.human_ids ? "--human-ids" : p == a.read_stats ? "--read-stats" : nullptr;
+        if (other) arg_error("the argument '--minimizer-table <FILE>' names the same file as '%s': %s", other, p.c_str());
+        for (const std::string &in : a.input)
+            if (p == in) arg_error("the argument '--minimizer-table <FILE>' names the input %s", p.c_str());
+    }
     return a;
 }
 
@@ -753,6 +774,8 @@ int main(int argc, char **argv) {
     if (!args.human_ids.empty()) staged_files.push_back({args.human_ids, ipart});
     const std::string spart = args.read_stats.empty() ? "" : staged(args.read_stats);
     if (!args.read_stats.empty()) staged_files.push_back({args.read_stats, spart});
+    const std::string mpart = args.minimizer_table.empty() ? "" : staged(args.minimizer_table);
+    if (!args.minimizer_table.empty()) staged_files.push_back({args.minimizer_table, mpart});
     // the per-taxon files: staged and renamed like the human outputs
     std::vector<std::string> tfinal, tpart;  // [2 * selector + mate]
     for (const auto &o : args.taxon_out)
@@ -802,7 +825,15 @@ int main(int argc, char **argv) {
     rx.human_out1 = hp1, rx.human_out2 = hp2;
     rx.calls = args.calls.empty() ? nullptr : cpart.c_str();
     rx.human_ids = args.human_ids.empty() ? nullptr : ipart.c_str();
-    const int run_rc = !touts.empty() ? nh_run_taxa(&ra, lists || args.mask || split ? &rx : nullptr, args.min_base_quality,
+    nh_minimizer_data md;
+    memset(&md, 0, sizeof md);
+    md.struct_size = (uint32_t)sizeof md;
+    md.in_report = args.report_minimizer_data ? 1 : 0;
+    md.table = args.minimizer_table.empty() ? nullptr : mpart.c_str();
+    const int run_rc = md.in_report || md.table ? nh_run_mdata(&ra, lists || args.mask || split ? &rx : nullptr, args.min_base_quality,
+                                                               args.read_stats.empty() ? nullptr : spart.c_str(), nullptr,
+                                                               touts.empty() ? nullptr : touts.data(), (uint32_t)touts.size(), &md, &st)
+                       : !touts.empty() ? nh_run_taxa(&ra, lists || args.mask || split ? &rx : nullptr, args.min_base_quality,
                                                     args.read_stats.empty() ? nullptr : spart.c_str(), nullptr, touts.data(), (uint32_t)touts.size(), &st)
                        : !args.read_stats.empty() ? nh_run_rstats(&ra, lists || args.mask || split ? &rx : nullptr, args.min_base_quality, spart.c_str(), nullptr, &st)
                        : args.min_base_quality ? nh_run_minq(&ra, lists || args.mask || split ? &rx : nullptr, args.min_base_quality, &st)
@@ -856,6 +887,7 @@ int main(int argc, char **argv) {
     if (!args.calls.empty()) INFO("Calls table written to: %s", quoted(args.calls).c_str());
     if (!args.human_ids.empty()) INFO("Human read ids written to: %s", quoted(args.human_ids).c_str());
     if (!args.read_stats.empty()) INFO("Read statistics written to: %s", quoted(args.read_stats).c_str());
+    if (!args.minimizer_table.empty()) INFO("Minimizer table written to: %s", quoted(args.minimizer_table).c_str());
     if (!args.kraken_report.empty()) INFO("Kraken report file written to: %s", quoted(args.kraken_report).c_str());
     INFO("Done.");
     return 0;

@@ -42,7 +42,8 @@ def probe() -> str:
 def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None, confidence: float = 0.0,
         threads: int = 1, keep_human: bool = False, device_ids=None, out_codec: int = 0,
         codec_threads: int = 0, human_out1=None, human_out2=None, mask: bool = False, calls=None,
-        human_ids=None, min_base_quality: int = 0, read_stats=None, taxon_outs=None) -> "_lib.nh_stats":
+        human_ids=None, min_base_quality: int = 0, read_stats=None, taxon_outs=None, report_minimizer_data: bool = False,
+        minimizer_table=None, minimizer_data=None) -> "_lib.nh_stats":
     """nh_run: whole run, database loaded into every listed device (default: all visible).  human_out1 (and, paired,
     human_out2) given: nh_run_split -- the non-human reads go to out1 / out2 and, in the same pass, the human reads to
     human_out1 / human_out2 exactly as a keep_human run would write them.  mask: nh_run_mask -- every read goes to
@@ -59,7 +60,13 @@ def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
     taxon_outs (nh_run_taxa; not with keep_human): up to 8 selectors [(taxid or "other", out1, out2 or None), ...] -- the
     classified reads sorted by clade on the GPU in the same pass, each to the deepest selected taxon that is its call or an
     ancestor of it ("other": in no selector's clade), written as a keep_human run writes them.  The stats returned then carry
-    taxon_fragments: the selectors' fragment counts, in the order given."""
+    taxon_fragments: the selectors' fragment counts, in the order given.
+    report_minimizer_data / minimizer_table / minimizer_data (nh_run_mdata; any kind of run): kraken2's --report-minimizer-data --
+    per taxon, the minimizer hit groups of the run's reads and how many DISTINCT database minimizers they were, counted exactly
+    on the GPU by a pass behind the classifier.  report_minimizer_data puts the two clade numbers into columns 4 and 5 of
+    `report`; minimizer_table is the path of the project's own table (with the cells of the table per taxon and the coverage);
+    minimizer_data is a list that receives a dict per node of the taxonomy, in internal-id order from the root (taxid,
+    reads_clade, reads_own, minimizers_clade, minimizers_own, distinct_clade, distinct_own, db_cells_clade, db_cells_own)."""
     a = _lib.nh_run_args()
     a.db_dir = os.fsencode(db_dir)
     a.in1 = os.fsencode(in1)
@@ -82,7 +89,17 @@ def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
         a.n_devices = 0
         a.device_ids = None
     s = _lib.nh_stats()
-    if taxon_outs:
+    if report_minimizer_data or minimizer_table is not None or minimizer_data is not None:
+        rs = _read_stats(read_stats) if read_stats is not None else None
+        t = _taxon_outs(taxon_outs or [])
+        md = _minimizer_data(report_minimizer_data, minimizer_table, minimizer_data, _taxo_nodes(os.fspath(db_dir)))
+        _check(_lib.lib().nh_run_mdata(C.byref(a), _extras_or_none(mask, human_out1, human_out2, calls, human_ids),
+                                       _minq(min_base_quality), _path_or_none(rs.path) if rs else None,
+                                       C.byref(rs.raw) if rs else None, t if len(t) else None, len(t), C.byref(md), C.byref(s)))
+        _minimizer_data_out(md, minimizer_data)
+        if taxon_outs:
+            s.taxon_fragments = [int(x.fragments) for x in t]
+    elif taxon_outs:
         rs = _read_stats(read_stats) if read_stats is not None else None
         t = _taxon_outs(taxon_outs)
         _check(_lib.lib().nh_run_taxa(C.byref(a), _extras_or_none(mask, human_out1, human_out2, calls, human_ids),
@@ -123,6 +140,41 @@ def _taxon_outs(sel):
         x.out1 = _path_or_none(out1)
         x.out2 = _path_or_none(out2)
     return t
+
+
+def _taxo_nodes(db_dir) -> int:
+    """nodes of the taxonomy in db_dir (or its db subdirectory), from taxo.k2d's header; 0 where it cannot be read"""
+    for d in (db_dir, os.path.join(db_dir, "db")):
+        try:
+            with open(os.path.join(d, "taxo.k2d"), "rb") as f:
+                head = f.read(16)
+            if len(head) == 16 and head[:8] == b"K2TAXDAT":
+                return int.from_bytes(head[8:16], "little")
+        except OSError:
+            pass
+    return 0
+
+
+def _minimizer_data(in_report, table, want_list, nodes) -> "_lib.nh_minimizer_data":
+    """run(report_minimizer_data=, minimizer_table=, minimizer_data=): the nh_minimizer_data of a run on a taxonomy of `nodes`"""
+    md = _lib.nh_minimizer_data()
+    md.struct_size = C.sizeof(_lib.nh_minimizer_data)
+    md.in_report = int(bool(in_report))
+    md.table = _path_or_none(table)
+    if want_list is not None:
+        cap = max(int(nodes), 1)
+        md._keep = (_lib.nh_taxon_minimizers * cap)()
+        md.taxa = md._keep
+        md.taxa_cap = cap
+    return md
+
+
+def _minimizer_data_out(md, want_list):
+    if want_list is None:
+        return
+    del want_list[:]
+    for i in range(min(int(md.n_taxa), int(md.taxa_cap))):
+        want_list.append({name: int(getattr(md.taxa[i], name)) for name, _ in _lib.nh_taxon_minimizers._fields_})
 
 
 def _extras(mask, human_out1, human_out2, calls, human_ids) -> "_lib.nh_run_extras":
@@ -440,6 +492,25 @@ class Engine:
         _check(self._L.nh_read_stats_device(self._h, d_text, text_len, d_seq_starts, d_seq_lens, d_qual_starts, d_results, n_frag,
                                             FLAG_PAIRED if paired else 0, d_acc, int(max_workgroups), stream or None))
 
+    def minimizer_marks_bytes(self) -> int:
+        """bytes of the bitmap minimizer_mark_device writes: one bit a cell of the table, 4 * ceil(capacity / 32)"""
+        n = C.c_uint64(0)
+        _check(self._L.nh_minimizer_marks_bytes(self._h, C.byref(n)))
+        return int(n.value)
+
+    def minimizer_mark_device(self, d_text: int, text_len: int, d_seq_starts: int, d_seq_lens: int, n_frag: int, d_marks: int,
+                              d_groups: int, paired: bool = False, stream: int = 0):
+        """The minimizer data's marking pass (nh_minimizer_mark_device), on the arrays of classify_records_device: every hit
+        group sets the bit of the cell where its key was found in d_marks (minimizer_marks_bytes() bytes) and adds 1 to
+        d_groups[taxon] (node_count uint64); the caller zeroes both.  Asynchronous on `stream`."""
+        _check(self._L.nh_minimizer_mark_device(self._h, d_text, text_len, d_seq_starts, d_seq_lens, n_frag,
+                                                FLAG_PAIRED if paired else 0, d_marks, d_groups, stream or None))
+
+    def minimizer_count_device(self, d_marks: int, d_counts: int, stream: int = 0):
+        """nh_minimizer_count_device: d_counts[taxon] (node_count uint64, zeroed by the caller) grows by the marked cells of
+        that taxon; d_marks 0: by all its cells.  Asynchronous on `stream`."""
+        _check(self._L.nh_minimizer_count_device(self._h, d_marks or None, d_counts, stream or None))
+
     def add_sequences(self, d_bases: int, d_seq_offsets: int, n_seq: int, value: int, stream: int = 0):
         """Bench/test support: insert the minimizers of device-resident sequences into the table."""
         _check(self._L.nh_synthetic_add_sequences(self._h, d_bases, d_seq_offsets, n_seq, value,
@@ -457,10 +528,12 @@ class Engine:
     def run(self, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
             confidence: float = 0.0, threads: int = 1, keep_human: bool = False, out_codec: int = 0,
             codec_threads: int = 0, human_out1=None, human_out2=None, mask: bool = False, calls=None,
-            human_ids=None, min_base_quality: int = 0, read_stats=None, taxon_outs=None) -> _lib.nh_stats:
+            human_ids=None, min_base_quality: int = 0, read_stats=None, taxon_outs=None, report_minimizer_data: bool = False,
+            minimizer_table=None, minimizer_data=None) -> _lib.nh_stats:
         """nh_run_engine; with human_out1 (and, paired, human_out2): nh_run_engine_split; mask: nh_run_engine_mask; with
         calls / human_ids: nh_run_engine_ex; with min_base_quality: nh_run_engine_minq; with read_stats:
-        nh_run_engine_rstats; with taxon_outs: nh_run_engine_taxa -- as run() above."""
+        nh_run_engine_rstats; with taxon_outs: nh_run_engine_taxa; with report_minimizer_data / minimizer_table / minimizer_data:
+        nh_run_engine_mdata -- as run() above."""
         a = _lib.nh_run_args()
         a.db_dir = None
         a.in1 = os.fsencode(in1)
@@ -477,7 +550,17 @@ class Engine:
         a.out_codec = int(out_codec)
         a.codec_threads = int(codec_threads)
         s = _lib.nh_stats()
-        if taxon_outs:
+        if report_minimizer_data or minimizer_table is not None or minimizer_data is not None:
+            rs = _read_stats(read_stats) if read_stats is not None else None
+            t = _taxon_outs(taxon_outs or [])
+            md = _minimizer_data(report_minimizer_data, minimizer_table, minimizer_data, self.info.node_count)
+            _check(self._L.nh_run_engine_mdata(self._h, C.byref(a), _extras_or_none(mask, human_out1, human_out2, calls, human_ids),
+                                               _minq(min_base_quality), _path_or_none(rs.path) if rs else None,
+                                               C.byref(rs.raw) if rs else None, t if len(t) else None, len(t), C.byref(md), C.byref(s)))
+            _minimizer_data_out(md, minimizer_data)
+            if taxon_outs:
+                s.taxon_fragments = [int(x.fragments) for x in t]
+        elif taxon_outs:
             rs = _read_stats(read_stats) if read_stats is not None else None
             t = _taxon_outs(taxon_outs)
             _check(self._L.nh_run_engine_taxa(self._h, C.byref(a), _extras_or_none(mask, human_out1, human_out2, calls, human_ids),

@@ -101,7 +101,8 @@ class CommandRunner:
         """The kraken2 options nohuman emits (src/main.rs:215-267) -> dict."""
         opts = {"threads": 1, "db": None, "output": None, "confidence": 0.0, "report": None,
                 "paired": False, "classified_out": None, "unclassified_out": None, "inputs": [],
-                "calls": None, "human_ids": None, "minimum_base_quality": 0, "read_stats": None}
+                "calls": None, "human_ids": None, "minimum_base_quality": 0, "read_stats": None,
+                "report_minimizer_data": False, "minimizer_table": None}
         it = iter(args)
         for a in it:
             if a == "--threads":
@@ -131,6 +132,10 @@ class CommandRunner:
                 opts["human_ids"] = next(it)
             elif a == "--read-stats":  # (the engine's own as well: nohuman --read-stats)
                 opts["read_stats"] = next(it)
+            elif a == "--report-minimizer-data":  # kraken2's own flag: two more columns in --report
+                opts["report_minimizer_data"] = True
+            elif a == "--minimizer-table":  # (the engine's own: nohuman --minimizer-table)
+                opts["minimizer_table"] = next(it)
             elif a.startswith("--"):
                 raise OSError("%s failed with stderr Unknown option: %s" % ("kraken2", a))
             else:
@@ -207,7 +212,13 @@ class CommandRunner:
                 x.struct_size = C.sizeof(_lib.nh_run_extras)
                 x.calls = os.fsencode(o["calls"]) if o["calls"] is not None else None
                 x.human_ids = os.fsencode(o["human_ids"]) if o["human_ids"] is not None else None
-            if rstats is not None:
+            if o["report_minimizer_data"] or o["minimizer_table"] is not None:
+                md = _lib.nh_minimizer_data()
+                md.struct_size = C.sizeof(_lib.nh_minimizer_data)
+                md.in_report = int(o["report_minimizer_data"])
+                md.table = os.fsencode(o["minimizer_table"]) if o["minimizer_table"] is not None else None
+                rc = L.nh_run_mdata(C.byref(a), C.byref(x) if x is not None else None, minq, rstats, None, None, 0, C.byref(md), C.byref(s))
+            elif rstats is not None:
                 rc = L.nh_run_rstats(C.byref(a), C.byref(x) if x is not None else None, minq, rstats, None, C.byref(s))
             elif x is not None:
                 if minq:
