@@ -535,6 +535,52 @@ int nh_minimizer_mark_device(nh_engine *e, const void *d_text, uint64_t text_len
 int nh_minimizer_count_device(nh_engine *e, const void *d_marks, void *d_counts, void *stream);
 
 /*
+ * Host selection (--host-taxid, --keep-taxid; nohuman_amd/csrc/nh_host.hip): which classified fragments count as
+ * HOST.  Without a selection every classified fragment does (call != 0) -- right while a database holds one taxon, wrong for a
+ * database of several (a manifest build with a spike-in or a decoy, a standard kraken2 database).  With one, there are two lists
+ * of external taxids, host and keep, and a classified fragment is a host fragment iff the DEEPEST listed taxon that is its call or
+ * an ancestor of its call is a host taxid (the rule of the per-taxon outputs above).  No listed ancestor: not host.  An unclassified
+ * fragment is never host.  A classified fragment that is not host is SPARED: every output treats it exactly as it treats an
+ * unclassified fragment.  host {1} is the behaviour without a selection.
+ * What follows the selection: out1 / out2 (the non-host fragments; keep_human: the host fragments, the suffix carrying the true
+ * call; a spared record is written as an unclassified one is, raw where the input allows, no " kraken:taxid" suffix), the human
+ * outputs, the mask (N over host fragments only), human_ids, the classes of the read statistics.  What does NOT: nh_result, the
+ * calls table, kraken_output, the report, nh_stats, the per-taxon outputs and the minimizer data report the true calls, byte for
+ * byte as the same run without a selection writes them.
+ * The pass is one kernel behind the classifier (k_host_filter: a second array of results with call = 0 where the fragment is not
+ * host), launched only when a selection is given; without one nothing is allocated or launched.
+ */
+#define NH_MAX_HOST_TAXA 16            /* host + keep together */
+typedef struct {
+    uint32_t struct_size;              /* sizeof(nh_host_filter) of the caller */
+    uint32_t n_host, n_keep, reserved;
+    const uint64_t *host_taxids, *keep_taxids;   /* external ids */
+    uint64_t host_fragments, spared_fragments;   /* out: host_fragments + spared_fragments == nh_stats.classified */
+} nh_host_filter;
+/* nh_run_mdata with a host selection; any kind of run (keep_human and per-taxon outputs included).  hf NULL, or n_host == 0 and
+ * n_keep == 0: exactly nh_run_mdata.  NH_EINVAL before any device is touched, nothing created: struct_size too small; n_keep > 0
+ * with n_host == 0; more than NH_MAX_HOST_TAXA taxids together; a NULL list with a non-zero count; taxid 0; a taxid given twice,
+ * within or across the lists; every check of nh_run_mdata.  A taxid that the opened database's taxonomy does not hold: NH_EINVAL
+ * with the taxid in the message, once the database is open, before any input is read or any output created. */
+int nh_run_host(const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality, const char *read_stats_path,
+                nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs, nh_minimizer_data *md, nh_host_filter *hf,
+                nh_stats *stats);
+int nh_run_engine_host(nh_engine *e, const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality,
+                       const char *read_stats_path, nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs,
+                       nh_minimizer_data *md, nh_host_filter *hf, nh_stats *stats);
+/* The host-node table of a selection from a taxo.k2d image; host only, no device needed: host_of[i] = 1 where node i (internal id)
+ * is host, else 0; entry 0 is 0.  *n_nodes receives the taxonomy's node count (sentinel included); cap: entries of host_of.
+ * NH_EINVAL: the selection's own errors (above), a taxid the taxonomy does not hold, cap below the node count.  NH_EDB: an image
+ * that is not a taxonomy, is truncated, or whose parents do not lie below their children. */
+int nh_host_table_image(const void *taxo, size_t taxo_len, const nh_host_filter *hf, uint8_t *host_of, uint64_t cap, uint64_t *n_nodes);
+/* The pass itself, asynchronous on `stream`, on the engine's device: d_res_out[i] = d_res_in[i] with call = 0 where
+ * d_host_of[call] is 0 (n nh_result each; d_res_out == d_res_in is allowed; d_host_of: n_nodes bytes).  d_counts (may be NULL): two
+ * uint64 {host, spared} the kernel ADDS to.  A call >= n_nodes is never used as an index: it becomes 0, is counted nowhere, and
+ * sets a sticky error bit (value 128) that fails the engine's next blocking call or run with NH_EDEVICE.  n == 0 launches nothing. */
+int nh_host_filter_device(nh_engine *e, const void *d_res_in, void *d_res_out, uint64_t n, const void *d_host_of, uint64_t n_nodes,
+                          void *d_counts, void *stream);
+
+/*
  * Database builder (--build-db; nohuman_amd/csrc/nh_build.hip): FASTA in, a kraken2 database directory out (hash.k2d, opts.k2d,
  * taxo.k2d), built on the GPU.  What kraken2-build does for ONE taxon at the default geometry, and nothing more: k = 35, l = 31,
  * the default spaced-seed and toggle masks, revcom_version 1, dna_db 1, minimum_acceptable_hash_value 0, linear probing -- the

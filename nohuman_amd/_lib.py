@@ -85,6 +85,15 @@ class nh_minimizer_data(C.Structure):
                 ("taxa", C.POINTER(nh_taxon_minimizers)), ("taxa_cap", C.c_uint32), ("n_taxa", C.c_uint32)]
 
 
+NH_MAX_HOST_TAXA = 16
+
+
+class nh_host_filter(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_host", C.c_uint32), ("n_keep", C.c_uint32), ("reserved", C.c_uint32),
+                ("host_taxids", C.POINTER(C.c_uint64)), ("keep_taxids", C.POINTER(C.c_uint64)),
+                ("host_fragments", C.c_uint64), ("spared_fragments", C.c_uint64)]
+
+
 class nh_build_args(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_fasta", C.c_uint32), ("fasta", C.POINTER(C.c_char_p)),
                 ("out_dir", C.c_char_p), ("taxid", C.c_uint64), ("taxon_name", C.c_char_p), ("load_factor", C.c_double),
@@ -189,6 +198,14 @@ SYMBOLS = {
     "nh_run_engine_mdata": (C.c_int, [_P, C.POINTER(nh_run_args), C.POINTER(nh_run_extras), C.c_uint32, C.c_char_p,
                                       C.POINTER(nh_read_stats), C.POINTER(nh_taxon_out), C.c_uint32, C.POINTER(nh_minimizer_data),
                                       C.POINTER(nh_stats)]),
+    "nh_run_host": (C.c_int, [C.POINTER(nh_run_args), C.POINTER(nh_run_extras), C.c_uint32, C.c_char_p, C.POINTER(nh_read_stats),
+                              C.POINTER(nh_taxon_out), C.c_uint32, C.POINTER(nh_minimizer_data), C.POINTER(nh_host_filter),
+                              C.POINTER(nh_stats)]),
+    "nh_run_engine_host": (C.c_int, [_P, C.POINTER(nh_run_args), C.POINTER(nh_run_extras), C.c_uint32, C.c_char_p,
+                                     C.POINTER(nh_read_stats), C.POINTER(nh_taxon_out), C.c_uint32, C.POINTER(nh_minimizer_data),
+                                     C.POINTER(nh_host_filter), C.POINTER(nh_stats)]),
+    "nh_host_table_image": (C.c_int, [_P, C.c_size_t, C.POINTER(nh_host_filter), _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "nh_host_filter_device": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint64, _P, _P]),
     "nh_minimizer_marks_bytes": (C.c_int, [_P, C.POINTER(C.c_uint64)]),
     "nh_minimizer_mark_device": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint64, C.c_uint32, _P, _P, _P]),
     "nh_minimizer_count_device": (C.c_int, [_P, _P, _P, _P]),

@@ -73,7 +73,7 @@ __device__ inline Line load_line(const CallsArgs &a, uint64_t f, bool report) {
         tail += L.nd[k] ? 1 + L.nd[k] : 0;
     }
     L.len[0] = a.want[0] ? 2ull + idl + tail + 1 : 0;
-    L.len[1] = a.want[1] && L.cls ? (uint64_t)idl + 1 : 0;
+    L.len[1] = a.want[1] && (a.res_ids ? a.res_ids[f].call != 0 : L.cls != 0) ? (uint64_t)idl + 1 : 0;
     return L;
 }
 

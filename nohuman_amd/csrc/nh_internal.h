@@ -184,6 +184,7 @@ struct CallsArgs {
     const uint32_t *rec;      // n * mates {header start (absolute), header length, qualities start (absolute), length}
     const uint32_t *idlen;    // n: the length of mate 1's id (RecRef::idlen)
     const nh_result *res;     // n results
+    const nh_result *res_ids; // NULL (= res), or the n results whose call != 0 decides the id list (a host selection: nh_host.hip)
     const uint64_t *ext;      // internal -> external taxon id, n_ext entries
     uint64_t n_ext, n, nblk;  // nblk = calls_blocks(n)
     int mates;
@@ -238,6 +239,15 @@ uint64_t mdata_mark_words(const Engine *e);
 hipError_t launch_mdata_mark(Engine *e, const void *d_text, uint64_t text_len, const void *d_seq_starts, const void *d_seq_lens, uint64_t n_frag,
                              int mates, void *d_marks, void *d_groups, hipStream_t stream);
 hipError_t launch_mdata_count(Engine *e, const void *d_marks, void *d_counts, hipStream_t stream);
+// The host selection (nh_host.hip; nh_run_host): the selection's own checks (NH_EINVAL, no device needed); host_of, one byte per
+// node of the engine's taxonomy, 1 where the deepest listed ancestor-or-self is a host taxid (NH_EINVAL: a taxid the taxonomy does
+// not hold); k_host_filter: out[i] = in[i] with call = 0 where host_of[call] is 0 (out == in allowed), counts (NULL or two words:
+// host, spared) added to, error: the engine's sticky error word (bit 128: a call >= n_nodes, written as 0, never an index).
+bool host_filter_given(const nh_host_filter *hf);  // not NULL and a taxid listed (or a struct too small to say: refused by the check)
+int check_host_filter(const nh_host_filter *hf);
+int host_table(const Engine *e, const nh_host_filter *hf, std::vector<uint8_t> &host_of);
+hipError_t launch_host_filter(const void *d_in, void *d_out, uint64_t n, const uint8_t *d_host_of, uint64_t n_nodes, unsigned long long *d_counts,
+                              int *d_error, hipStream_t stream);
 // buffers kept between the runs of a process (nh_run.hip: page-locked batch text; nh_gunzip.hip: the gzip reader's HBM and
 // staging): emptied when an engine is closed
 void run_cache_trim();

@@ -413,6 +413,15 @@ struct Slot {  // pinned host + device buffers of one in-flight batch
     hipEvent_t qev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around k_qmask
     hipEvent_t rev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around k_rstats (runs with read statistics)
     hipEvent_t mev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around k_mdata_mark (runs with minimizer data)
+    // runs with a host selection (nh_run_host): the results with call = 0 where the fragment is not host (nh_host.hip) -- what
+    // decides host-ness on the device (d_hres: the builders that remove, mask, list or count host reads) and on the host (h_hres:
+    // the writer); d_res / h_res keep the true calls.  NULL in a run without a selection: the host-ness is then h_res's call != 0
+    void *d_hres = nullptr;
+    nh_result *h_hres = nullptr;
+    size_t cap_hres = 0;
+    hipEvent_t hev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around k_host_filter
+    // the results that decide which fragments are host reads
+    const nh_result *host_res() const { return h_hres ? h_hres : h_res; }
 };
 
 // what a buffer that must hold `need` is allocated with: some room, so that batches a little larger do not reallocate
@@ -515,6 +524,19 @@ static int slot_reserve_idl(Slot &s, size_t n) {
     return NH_OK;
 }
 
+// the second results array of nfrag fragments of a slot (runs with a host selection)
+static int slot_reserve_hres(Slot &s, size_t nfrag) {
+    if (nfrag <= s.cap_hres) return NH_OK;
+    if (s.h_hres) (void)hipHostFree(s.h_hres);
+    if (s.d_hres) (void)hipFree(s.d_hres);
+    s.h_hres = nullptr, s.d_hres = nullptr;
+    s.cap_hres = grow(nfrag);
+    if (host_malloc((void **)&s.h_hres, s.cap_hres * sizeof(nh_result), hipHostMallocDefault) != hipSuccess ||
+        dev_malloc(&s.d_hres, s.cap_hres * sizeof(nh_result)) != hipSuccess)
+        return set_error(NH_EOOM, "cannot allocate batch buffers (%zu host-filtered results)", s.cap_hres);
+    return NH_OK;
+}
+
 // the quality mask's buffers of a slot: the record table of nrec sequences, ntext bytes of masked text, the counter
 static int slot_reserve_qmask(Slot &s, size_t ntext, size_t nrec) {
     const int rrc = slot_reserve_rec(s, nrec);
@@ -544,13 +566,13 @@ static void slot_free(Slot &s) {
         for (hipEvent_t ev : o->ev)
             if (ev) (void)hipEventDestroy(ev);
     }
-    for (void *p : {(void *)s.h_rec, (void *)s.h_idl})
+    for (void *p : {(void *)s.h_rec, (void *)s.h_idl, (void *)s.h_hres})
         if (p) (void)hipHostFree(p);
-    for (void *p : {s.d_rec, s.d_idl})
+    for (void *p : {s.d_rec, s.d_idl, s.d_hres})
         if (p) (void)hipFree(p);
     for (void *p : {s.d_qtext, (void *)s.d_qcnt})
         if (p) (void)hipFree(p);
-    for (hipEvent_t ev : {s.qev[0], s.qev[1], s.rev[0], s.rev[1], s.mev[0], s.mev[1]})
+    for (hipEvent_t ev : {s.qev[0], s.qev[1], s.rev[0], s.rev[1], s.mev[0], s.mev[1], s.hev[0], s.hev[1]})
         if (ev) (void)hipEventDestroy(ev);
     for (void *p : {(void *)s.h_off, (void *)s.h_len, (void *)s.h_res, (void *)s.h_taxa, (void *)s.h_taxa_off, (void *)s.h_flag})
         if (p) (void)hipHostFree(p);
@@ -656,6 +678,10 @@ struct RunState {
     std::map<uint64_t, uint64_t> len_long[2][2];
     double rstats_kernel_ms = 0;
     double mdata_kernel_ms = 0;  // NOHUMAN_TRACE: k_mdata_mark, by events on the slots' streams
+    // runs with a host selection: the classified fragments that are host / spared as the writer saw them (the checker of the
+    // devices' counters), k_host_filter's time
+    uint64_t host_frags = 0, spared_frags = 0;
+    double host_kernel_ms = 0;
     std::atomic<uint64_t> text_fetched{0};
     std::vector<uint64_t> dev_counts;  // per device {fragments, classified, bases, 0} as the writer saw them (checker)
     std::vector<uint64_t *> d_run_counters;  // per device: the counters the classify kernels of THIS run add to (HBM)
@@ -935,23 +961,28 @@ static void format_batch(RunState *rs, const Batch &b, const Slot &s, OutFile &o
     const char *t1 = b.fetch1 ? b.fetch1.get() : b.h1->text.data();
     const char *t2 = !rs->paired ? nullptr : b.fetch2 ? b.fetch2.get() : b.h2->text.data();
     char tmp[128];
-    uint64_t bases = 0, classified = 0, hit_groups = 0;
+    uint64_t bases = 0, classified = 0, hit_groups = 0, host = 0;
+    const nh_result *const hres = s.host_res();  // (a host selection: call = 0 where the fragment is not host; else h_res)
     const RecRef *const R1 = b.h1->recs.data() + b.off1;
     const RecRef *const R2 = rs->paired ? b.h2->recs.data() + b.off2 : nullptr;
     for (size_t i = 0; i < b.n; i++) {
         const RecRef &r1 = R1[i];
         const uint32_t call = s.h_res[i].call;
         const bool is_class = call != 0;
+        // host-ness decides what is emitted and how; the call what is reported (the counts, the -k line, the suffix): a spared
+        // fragment -- classified, not host -- is written exactly as an unclassified one is
+        const bool is_host = hres[i].call != 0;
         classified += is_class;
+        host += is_host;
         hit_groups += s.h_res[i].hit_groups;
         rs->call_counts[call] += is_class;
         bases += r1.slen + (rs->paired ? R2[i].slen : 0);
-        if (emit && is_class == keep_class) {
-            if (!is_class && r1.raw_end) {
+        if (emit && is_host == keep_class) {
+            if (!is_host && r1.raw_end) {
                 o1.add_raw(t1 + r1.h, r1.raw_end - r1.h);
             } else {
                 const char *suffix = nullptr;
-                if (is_class) {
+                if (is_host) {
                     snprintf(tmp, sizeof tmp, " kraken:taxid|%llu", (unsigned long long)e->external[call]);
                     suffix = tmp;
                 }
@@ -961,11 +992,11 @@ static void format_batch(RunState *rs, const Batch &b, const Slot &s, OutFile &o
             }
             if (rs->paired) {
                 const RecRef &r2 = R2[i];
-                if (!is_class && r2.raw_end) {
+                if (!is_host && r2.raw_end) {
                     o2.add_raw(t2 + r2.h, r2.raw_end - r2.h);
                 } else {
                     const size_t from = o2.scratch.size();
-                    put_record(o2.scratch, t2, b.h2->format, r2, is_class ? tmp : nullptr);
+                    put_record(o2.scratch, t2, b.h2->format, r2, is_host ? tmp : nullptr);
                     o2.add_scratch(from);
                 }
             }
@@ -991,6 +1022,8 @@ static void format_batch(RunState *rs, const Batch &b, const Slot &s, OutFile &o
     if (rs->want_k) ok.add_scratch(0);
     rs->total += b.n;
     rs->classified += classified;
+    rs->host_frags += host;
+    rs->spared_frags += classified - host;
     rs->hit_groups += hit_groups;
     rs->total_bases += bases;
     uint64_t *dc = &rs->dev_counts[4 * (size_t)b.dev_index];
@@ -1200,10 +1233,14 @@ static int check_taxon_args(const nh_run_args *a, const nh_run_extras *x, const 
 // every hit group in the device's bitmap and counts the group for its taxon (nh_mdata.hip), on the text the classifier read;
 // k_mdata_count reads the bitmap once, at the end (several devices: the union of their bitmaps -- a minimizer hit on two devices is
 // one).  NULL, or nothing asked for: nothing of this runs.
+// hf selecting something (nh_run_host): the host selection -- k_host_filter behind the classifier on the slot's stream writes the
+// batch's results a second time, call = 0 where the fragment is not a host fragment (nh_host.hip); everything that removes, keeps,
+// masks, lists or counts HOST reads then reads that array (the writer its copy), everything that reports the CALL the classifier's.
+// NULL, or no taxid: nothing of this runs.
 int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_stats *stats, const char *hout1 = nullptr,
                 const char *hout2 = nullptr, bool mask = false, const char *calls = nullptr, const char *ids = nullptr,
                 uint32_t minq = 0, const char *rs_path = nullptr, nh_read_stats *rs_out = nullptr, nh_taxon_out *touts = nullptr,
-                uint32_t n_touts = 0, nh_minimizer_data *md = nullptr) {
+                uint32_t n_touts = 0, nh_minimizer_data *md = nullptr, nh_host_filter *hf = nullptr) {
     if (!a || !a->in1 || !a->out1) return set_error(NH_EINVAL, "nh_run: in1 and out1 are required");
     if (engines.empty()) return set_error(NH_EINVAL, "nh_run: no engine");
     const bool split = hout1 != nullptr;
@@ -1213,6 +1250,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
     const bool qm = minq > 0;
     const bool rst = rs_path || rs_out;
     const bool mdt = md && (md->in_report || md->table || md->taxa);
+    const bool hsel = host_filter_given(hf);
     if (minq > 93) return set_error(NH_EINVAL, "nh_run: minimum base quality %u is not in 0..93 (Phred+33)", minq);
     if (lists) {
         const int vrc = check_list_args(a, hout1, hout2, calls, ids);
@@ -1266,6 +1304,14 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
         int vrc = check_mdata_args(a, &x, rs_path, touts, n_touts, md);
         for (size_t g = 0; g < engines.size() && !vrc; g++) vrc = mdata_check_db(engines[g]);
         if (vrc) return vrc;
+    }
+    // the host selection: which nodes of the taxonomy are host (the database is open: before any input is read or any output created)
+    std::vector<uint8_t> host_of;
+    if (hsel) {
+        int vrc = check_host_filter(hf);
+        if (!vrc) vrc = host_table(engines[0], hf, host_of);
+        if (vrc) return vrc;
+        hf->host_fragments = hf->spared_fragments = 0;
     }
     if (split || lists || taxa)
         for (Engine *e : engines) {
@@ -1392,6 +1438,9 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
 
     rs.d_run_counters.assign((size_t)G, nullptr);
     std::vector<uint8_t *> d_bin_of((size_t)G, nullptr);  // per device: bin_of in HBM for the run
+    // host selection: per device host_of in HBM for the run, and the pair of counters {host, spared} k_host_filter adds to
+    std::vector<uint8_t *> d_host_of((size_t)G, nullptr);
+    std::vector<unsigned long long *> d_hcnt((size_t)G, nullptr);
     // read statistics: one block of four accumulators per device of the run, zeroed with min_len all-ones
     std::vector<unsigned long long *> d_racc((size_t)G, nullptr);
     std::vector<nh_read_class> racc;  // the devices' blocks summed: [class][mate]
@@ -1404,8 +1453,11 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
     double md_count_ms = 0;
     auto free_run_counters = [&] {
         for (int g = 0; g < G; g++) {
-            if (!rs.d_run_counters[g] && !d_racc[g] && !d_bin_of[g] && !d_marks[g] && !d_groups[g]) continue;
+            if (!rs.d_run_counters[g] && !d_racc[g] && !d_bin_of[g] && !d_marks[g] && !d_groups[g] && !d_host_of[g] && !d_hcnt[g]) continue;
             (void)dev_set(engines[g]->device);
+            if (d_host_of[g]) (void)hipFree(d_host_of[g]);
+            if (d_hcnt[g]) (void)hipFree(d_hcnt[g]);
+            d_host_of[g] = nullptr, d_hcnt[g] = nullptr;
             if (d_marks[g]) (void)hipFree(d_marks[g]);
             if (d_groups[g]) (void)hipFree(d_groups[g]);
             d_marks[g] = nullptr, d_groups[g] = nullptr;
@@ -1426,6 +1478,14 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                      hipMemcpy(d_bin_of[g], bin_of.data(), bin_of.size(), hipMemcpyHostToDevice) != hipSuccess)) {
             free_run_counters();
             return set_error(NH_EDEVICE, "cannot copy the selectors' bins to device %d", engines[g]->device);
+        }
+        // (hipMemcpy / hipMemset block: the table and the zeroes are in place before the slots' streams, which do not wait for the
+        // legacy stream, carry the first batch)
+        if (hsel && (dev_malloc((void **)&d_host_of[g], host_of.size()) != hipSuccess || dev_malloc((void **)&d_hcnt[g], 16) != hipSuccess ||
+                     hipMemcpy(d_host_of[g], host_of.data(), host_of.size(), hipMemcpyHostToDevice) != hipSuccess ||
+                     hipMemset(d_hcnt[g], 0, 16) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) {
+            free_run_counters();
+            return set_error(NH_EDEVICE, "cannot copy the host selection's table to device %d", engines[g]->device);
         }
         if (rst) {
             nh_read_class init[4];
@@ -1475,7 +1535,9 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
             (rst && getenv("NOHUMAN_TRACE") &&
              (hipEventCreate(&slots[i].rev[0]) != hipSuccess || hipEventCreate(&slots[i].rev[1]) != hipSuccess)) ||
             (mdt && getenv("NOHUMAN_TRACE") &&
-             (hipEventCreate(&slots[i].mev[0]) != hipSuccess || hipEventCreate(&slots[i].mev[1]) != hipSuccess))) {
+             (hipEventCreate(&slots[i].mev[0]) != hipSuccess || hipEventCreate(&slots[i].mev[1]) != hipSuccess)) ||
+            (hsel && getenv("NOHUMAN_TRACE") &&
+             (hipEventCreate(&slots[i].hev[0]) != hipSuccess || hipEventCreate(&slots[i].hev[1]) != hipSuccess))) {
             for (auto &s : slots) slot_free(s);
             free_run_counters();
             return set_error(NH_EDEVICE, "cannot create streams");
@@ -1705,8 +1767,9 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                     auto need_fetch = [&](const HalfBatch &hb) {
                         if (hb.host_text_valid || mask) return false;
                         const size_t off = &hb == b.h1.get() ? b.off1 : b.off2;
+                        const nh_result *const hres = s.host_res();
                         for (size_t i = 0; i < b.n; i++)
-                            if (!hb.recs[off + i].raw_end && (s.h_res[i].call != 0) == (a->keep_human != 0)) return true;
+                            if (!hb.recs[off + i].raw_end && (hres[i].call != 0) == (a->keep_human != 0)) return true;
                         return false;
                     };
                     for (int m = 0; m < (rs.paired ? 2 : 1) && !wrc; m++) {
@@ -1737,7 +1800,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                         rs.mask_records += b.n * (size_t)mates;
                         rs.mask_nblk += mask_blocks(b.n) * (uint64_t)mates;
                         for (int m = 0; m < mates; m++) rs.mask_fast += s.mask.h_total[2 + m];
-                        for (size_t i = 0; i < b.n; i++) rs.mask_masked += (s.h_res[i].call != 0) * (uint64_t)mates;
+                        for (size_t i = 0; i < b.n; i++) rs.mask_masked += (s.host_res()[i].call != 0) * (uint64_t)mates;
                     }
                     // a split run's classified records: the text the builder made, one span a mate -- in HBM, or copied here
                     add_event_ms(s.human.ev, &rs.human_kernel_ms);
@@ -1751,7 +1814,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                         hs.is_scratch.push_back(0);
                     }
                     if (split)
-                        for (size_t i = 0; i < b.n; i++) rs.human_records += s.h_res[i].call != 0;
+                        for (size_t i = 0; i < b.n; i++) rs.human_records += s.host_res()[i].call != 0;
                     // the per-taxon records: a mate's buffer with the bins in it -- in HBM, or copied here as far as the last bin
                     // reaches -- and a span a bin that has bytes
                     add_event_ms(s.taxon.ev, &rs.taxon_kernel_ms);
@@ -1782,9 +1845,10 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                     add_event_ms(s.qev, &rs.qmask_kernel_ms);
                     add_event_ms(s.rev, &rs.rstats_kernel_ms);
                     add_event_ms(s.mev, &rs.mdata_kernel_ms);
-                    // read statistics: every length of the batch, by the class of its fragment and its mate
+                    add_event_ms(s.hev, &rs.host_kernel_ms);
+                    // read statistics: every length of the batch, by the class of its fragment (host or not) and its mate
                     for (size_t i = 0; rst && i < b.n; i++) {
-                        const int c = s.h_res[i].call != 0;
+                        const int c = s.host_res()[i].call != 0;
                         for (int m = 0; m < mates; m++) {
                             const uint64_t L = s.h_len[i * mates + m];
                             if (L >= (1u << 20)) {
@@ -1953,6 +2017,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
             }
             if (!rc && qm) rc = slot_reserve_qmask(s, ntext, b.n * (size_t)mates);
             if (!rc && rst) rc = slot_reserve_rec(s, b.n * (size_t)mates);
+            if (!rc && hsel) rc = slot_reserve_hres(s, b.n);
             // kraken2 ends a run at a FASTQ record whose quality line is not as long as its sequence when it masks by quality;
             // the read statistics count a base per quality as well
             for (size_t i = 0; (qm || rst) && !rc && i < b.n; i++)
@@ -2065,6 +2130,16 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                                      rs.d_run_counters[(size_t)(si / NS)], s.stream, s.d_len, ntext);
                 if (rc) rs.fail(rc, g_last_error);
             }
+            // the results that decide host-ness from here on: the classifier's, or -- a host selection -- their copy with call = 0
+            // where the fragment is not host, made right behind the classifier on the same stream
+            const nh_result *const d_host_res = (const nh_result *)(hsel ? s.d_hres : s.d_res);
+            if (!rs.failed() && hsel) {
+                if (s.hev[0]) (void)hipEventRecord(s.hev[0], s.stream);
+                he = launch_host_filter(s.d_res, s.d_hres, b.n, d_host_of[(size_t)(si / NS)], s.e->external.size(), d_hcnt[(size_t)(si / NS)],
+                                        s.e->d_error + LAUNCH_SLOTS, s.stream);
+                if (s.hev[1] && he == hipSuccess) he = hipEventRecord(s.hev[1], s.stream);
+                if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("host filter: ") + hipGetErrorString(he));
+            }
             if (!rs.failed() && rst) {  // the read statistics, counted behind the classifier on the same stream: the INPUT's bases
                 RstatsArgs ta{};
                 ta.text = (const char *)s.d_text;
@@ -2076,7 +2151,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 ta.mates = mates;
                 ta.fastq[0] = b.h1->format == FMT_FASTQ;
                 ta.fastq[1] = rs.paired && b.h2->format == FMT_FASTQ;
-                ta.res = (const nh_result *)s.d_res;
+                ta.res = d_host_res;
                 ta.acc = d_racc[(size_t)(si / NS)];
                 ta.error = s.e->d_error + LAUNCH_SLOTS;
                 if (s.rev[0]) (void)hipEventRecord(s.rev[0], s.stream);
@@ -2099,6 +2174,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 ca.rec = (const uint32_t *)s.d_rec;
                 ca.idlen = (const uint32_t *)s.d_idl;
                 ca.res = (const nh_result *)s.d_res;
+                ca.res_ids = hsel ? d_host_res : nullptr;  // (the table keeps the true calls; the id list is the host fragments')
                 ca.ext = s.e->d_external;
                 ca.n_ext = s.e->external.size();
                 ca.n = b.n;
@@ -2122,7 +2198,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 ha.seq_off = (const uint64_t *)s.d_off;
                 ha.seq_len = (const uint32_t *)s.d_len;
                 ha.rec = (const uint32_t *)s.d_rec;
-                ha.res = (const nh_result *)s.d_res;
+                ha.res = d_host_res;  // (the call of a host fragment is the true call: the suffix carries it)
                 ha.ext = s.e->d_external;
                 ha.n_ext = s.e->external.size();
                 ha.n = b.n;
@@ -2173,7 +2249,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 ma.seq_off = (const uint64_t *)s.d_off;
                 ma.seq_len = (const uint32_t *)s.d_len;
                 ma.rec = (const uint32_t *)s.d_rec;
-                ma.res = (const nh_result *)s.d_res;
+                ma.res = d_host_res;
                 ma.n = b.n;
                 ma.nblk = mask_blocks(b.n);
                 ma.mates = mates;
@@ -2191,6 +2267,8 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
             }
             if (!rs.failed()) {
                 he = hipMemcpyAsync(s.h_res, s.d_res, b.n * sizeof(nh_result), hipMemcpyDeviceToHost, s.stream);
+                if (he == hipSuccess && hsel)
+                    he = hipMemcpyAsync(s.h_hres, s.d_hres, b.n * sizeof(nh_result), hipMemcpyDeviceToHost, s.stream);
                 if (he == hipSuccess)
                     he = hipMemcpyAsync(s.h_flag, s.e->d_error + LAUNCH_SLOTS, sizeof(int), hipMemcpyDeviceToHost, s.stream);
                 if (he == hipSuccess && rs.want_k && toff)
@@ -2242,6 +2320,22 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
             unsigned long long c = 0;
             if (dev_set(s.e->device) == hipSuccess && hipMemcpy(&c, s.d_qcnt, 8, hipMemcpyDeviceToHost) == hipSuccess) rs.qmask_masked += c;
         }
+    uint64_t dev_host[2] = {0, 0};  // host selection: the devices' {host, spared} fragments summed
+    for (int g = 0; hsel && g < G && rs.err_code == NH_OK; g++) {
+        unsigned long long c[2] = {0, 0};
+        if (dev_set(engines[g]->device) != hipSuccess || hipMemcpy(c, d_hcnt[g], 16, hipMemcpyDeviceToHost) != hipSuccess) {
+            rs.fail(NH_EDEVICE, "reading the host filter's counters failed");
+            break;
+        }
+        dev_host[0] += c[0], dev_host[1] += c[1];
+    }
+    // (the fragments the writer saw as host and as spared are the checker of what the kernel counted, as for the run's counters)
+    if (hsel && rs.err_code == NH_OK && (dev_host[0] != rs.host_frags || dev_host[1] != rs.spared_frags)) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "host filter: the devices counted %llu host / %llu spared fragments, the writer %llu / %llu", (unsigned long long)dev_host[0],
+                 (unsigned long long)dev_host[1], (unsigned long long)rs.host_frags, (unsigned long long)rs.spared_frags);
+        rs.fail(NH_EDEVICE, msg);
+    }
     if (rst && rs.err_code == NH_OK) {  // the devices' accumulators, once: rows summed on the host
         racc.assign(4, nh_read_class{});
         for (nh_read_class &c : racc) c.min_len = ~0ull;
@@ -2342,6 +2436,9 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 fprintf(stderr, "[nohuman trace] minimizer data: %llu hit groups on %llu distinct minimizers, k_mdata_mark %.3f ms, k_mdata_count %.3f ms\n", groups,
                         distinct, rs.mdata_kernel_ms, md_count_ms);
             }
+            if (hsel && rs.err_code == NH_OK)
+                fprintf(stderr, "[nohuman trace] host-filter: %llu host, %llu spared fragments; kernel %.3f ms\n", (unsigned long long)dev_host[0],
+                        (unsigned long long)dev_host[1], rs.host_kernel_ms);
             if (g_pageable_batches.load())
                 fprintf(stderr, "[nohuman trace] %d batch buffers could not be page-locked (pageable memory used)\n",
                         g_pageable_batches.load());
@@ -2496,6 +2593,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
         if (rs_out) *rs_out = out;
     }
     for (int k = 0; k < K; k++) touts[k].fragments = rs.taxon_frags[k];
+    if (hsel) hf->host_fragments = rs.host_frags, hf->spared_fragments = rs.spared_frags;
     if (mdt) {
         if (md->table && (rc = write_mdata_table(mdview, mdn, md->table))) return rc;
         md->n_taxa = mdview.n > 1 ? (uint32_t)(mdview.n - 1) : 0;
@@ -2522,9 +2620,9 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
 int run_engine(Engine *e, const nh_run_args *a, nh_stats *stats, const char *hout1 = nullptr, const char *hout2 = nullptr,
                bool mask = false, const char *calls = nullptr, const char *ids = nullptr, uint32_t minq = 0,
                const char *rs_path = nullptr, nh_read_stats *rs_out = nullptr, nh_taxon_out *touts = nullptr, uint32_t n_touts = 0,
-               nh_minimizer_data *md = nullptr) {
+               nh_minimizer_data *md = nullptr, nh_host_filter *hf = nullptr) {
     std::vector<Engine *> v{e};
-    return run_engines(v, a, stats, hout1, hout2, mask, calls, ids, minq, rs_path, rs_out, touts, n_touts, md);
+    return run_engines(v, a, stats, hout1, hout2, mask, calls, ids, minq, rs_path, rs_out, touts, n_touts, md, hf);
 }
 
 // nh_run_minq's own argument, checked before any device is touched: the highest printable quality is '~', Phred 93
@@ -2567,6 +2665,14 @@ int check_mdata(const nh_run_args *a, const nh_run_extras *x, uint32_t minq, con
                 const nh_minimizer_data *md) {
     int rc = check_taxa(a, x, minq, rs_path, outs, n);
     if (!rc) rc = check_mdata_args(a, x, rs_path, outs, n, md);
+    return rc;
+}
+
+// nh_run_host's arguments, checked before any device is touched: the selection's own, then nh_run_mdata's
+int check_host(const nh_run_args *a, const nh_run_extras *x, uint32_t minq, const char *rs_path, const nh_taxon_out *outs, uint32_t n,
+               const nh_minimizer_data *md, const nh_host_filter *hf) {
+    int rc = check_host_filter(hf);
+    if (!rc) rc = check_mdata(a, x, minq, rs_path, outs, n, md);
     return rc;
 }
 
@@ -2645,6 +2751,21 @@ int nh_run_engine_mdata(nh_engine *e, const nh_run_args *args, const nh_run_extr
                               outs, n_outs, md);
     return nh::run_engine((nh::Engine *)e, args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls,
                           extras->human_ids, min_base_quality, read_stats_path, read_stats, outs, n_outs, md);
+}
+
+int nh_run_engine_host(nh_engine *e, const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality,
+                       const char *read_stats_path, nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs, nh_minimizer_data *md,
+                       nh_host_filter *hf, nh_stats *stats) {
+    if (!nh::host_filter_given(hf))  // (exactly nh_run_engine_mdata)
+        return nh_run_engine_mdata(e, args, extras, min_base_quality, read_stats_path, read_stats, outs, n_outs, md, stats);
+    const int rc = nh::check_host(args, extras, min_base_quality, read_stats_path, outs, n_outs, md, hf);
+    if (rc) return rc;
+    if (!e) return nh::set_error(NH_EINVAL, "null engine");
+    if (!extras)
+        return nh::run_engine((nh::Engine *)e, args, stats, nullptr, nullptr, false, nullptr, nullptr, min_base_quality, read_stats_path, read_stats,
+                              outs, n_outs, md, hf);
+    return nh::run_engine((nh::Engine *)e, args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls,
+                          extras->human_ids, min_base_quality, read_stats_path, read_stats, outs, n_outs, md, hf);
 }
 
 int nh_fastx_scan(const char *path, uint64_t *n_records, uint64_t *n_bases, uint64_t *digest) {
@@ -2793,7 +2914,8 @@ int nh_debug_reader_dump(const char *path, int reader, int device, uint64_t batc
 // round-robin, outputs stay in input order, the counts are summed on the host.
 static int run_devices(const nh_run_args *args, nh_stats *stats, const char *hout1, const char *hout2, bool mask = false,
                        const char *calls = nullptr, const char *ids = nullptr, uint32_t minq = 0, const char *rs_path = nullptr,
-                       nh_read_stats *rs_out = nullptr, nh_taxon_out *touts = nullptr, uint32_t n_touts = 0, nh_minimizer_data *md = nullptr) {
+                       nh_read_stats *rs_out = nullptr, nh_taxon_out *touts = nullptr, uint32_t n_touts = 0, nh_minimizer_data *md = nullptr,
+                       nh_host_filter *hf = nullptr) {
     if (!args || !args->db_dir) return nh::set_error(NH_EINVAL, "nh_run: db_dir is required");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -2829,7 +2951,7 @@ static int run_devices(const nh_run_args *args, nh_stats *stats, const char *hou
     }
     const double t_load = since(t_begin);
     const auto t_run = std::chrono::steady_clock::now();
-    if (!rc) rc = nh::run_engines(engines, args, stats, hout1, hout2, mask, calls, ids, minq, rs_path, rs_out, touts, n_touts, md);
+    if (!rc) rc = nh::run_engines(engines, args, stats, hout1, hout2, mask, calls, ids, minq, rs_path, rs_out, touts, n_touts, md, hf);
     const double s_run = since(t_run);
     std::string keep = nh::g_last_error;
     const auto t_close = std::chrono::steady_clock::now();
@@ -2897,6 +3019,17 @@ int nh_run_mdata(const nh_run_args *args, const nh_run_extras *extras, uint32_t 
         return run_devices(args, stats, nullptr, nullptr, false, nullptr, nullptr, min_base_quality, read_stats_path, read_stats, outs, n_outs, md);
     return run_devices(args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls, extras->human_ids,
                        min_base_quality, read_stats_path, read_stats, outs, n_outs, md);
+}
+
+int nh_run_host(const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality, const char *read_stats_path,
+                nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs, nh_minimizer_data *md, nh_host_filter *hf, nh_stats *stats) {
+    if (!nh::host_filter_given(hf)) return nh_run_mdata(args, extras, min_base_quality, read_stats_path, read_stats, outs, n_outs, md, stats);
+    const int rc = nh::check_host(args, extras, min_base_quality, read_stats_path, outs, n_outs, md, hf);  // (before any device is touched)
+    if (rc) return rc;
+    if (!extras)
+        return run_devices(args, stats, nullptr, nullptr, false, nullptr, nullptr, min_base_quality, read_stats_path, read_stats, outs, n_outs, md, hf);
+    return run_devices(args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls, extras->human_ids,
+                       min_base_quality, read_stats_path, read_stats, outs, n_outs, md, hf);
 }
 
 }  // extern "C"

@@ -225,6 +225,8 @@ struct Args {
     std::string minimizer_table;         // the minimizer table (nh_run_mdata)
     // per-taxon outputs (nh_run_taxa): the selectors in the order given -- taxid (0: `other`), the path as given ('#' in it: the mate)
     std::vector<std::pair<unsigned long long, std::string>> taxon_out;
+    // the host selection (nh_run_host): the clades whose reads count as host, and the clades inside them that do not
+    std::vector<unsigned long long> host_taxids, keep_taxids;
     bool has_out1 = false, has_out2 = false, check = false, download = false, list = false, human = false;
     bool has_type = false;
     Codec type = C_NONE;
@@ -274,6 +276,11 @@ static void usage(FILE *f) {
           "      --taxon-out <TAXID|other>:<PATH>  Also write the classified reads of this taxon's clade to PATH, in the same run (as -H would write them); "
           "may be given up to 8 times: a read goes to the deepest selected taxon that is its call or an ancestor of it, `other` takes the "
           "classified reads in no selected clade. With two inputs PATH must contain '#', which becomes _1 / _2\n"
+          "      --host-taxid <TAXID>     Count only the reads classified into this taxon's clade as host (removed, written by -H / --human-out1, masked, listed by "
+          "--human-ids); may be given more than once, 16 times together with --keep-taxid. Without it every classified read is host, which is "
+          "--host-taxid 1. A classified read outside the host clades is kept and written as an unclassified one; -k, -r, --calls and --taxon-out report the true calls\n"
+          "      --keep-taxid <TAXID>     Do not count the reads of this taxon's clade as host although a --host-taxid clade contains it (the deepest of the "
+          "listed taxa above a read's call decides); needs --host-taxid\n"
           "      --build-db <DIR>         Build a database (hash.k2d, opts.k2d, taxo.k2d) in DIR from the --reference files, on the GPU, and exit\n"
           "      --reference <FILE>       FASTA file (plain or gzip) of the host genome for --build-db; may be given more than once\n"
           "      --taxid <INT>            Taxonomy id of the host for --build-db [default: 9606]\n"
@@ -395,6 +402,21 @@ static Args parse_args(int argc, char **argv) {
             if (a.taxon_out.size() == NH_MAX_TAXON_OUTS) arg_error("the argument '--taxon-out <TAXID|other>:<PATH>' cannot be used more than %d times", NH_MAX_TAXON_OUTS);
             a.taxon_out.push_back({id, t.substr(colon + 1)});
         }
+        else if (s == "--host-taxid" || s == "--keep-taxid") {
+            const std::string t = val();
+            char *end;
+            errno = 0;
+            const unsigned long long id = strtoull(t.c_str(), &end, 10);
+            if (*end || t.empty() || t[0] < '0' || t[0] > '9' || errno)
+                arg_error("invalid value '%s' for '%s <TAXID>': invalid digit found in string", t.c_str(), s.c_str());
+            if (id == 0) arg_error("invalid value '%s' for '%s <TAXID>': 0 is not a taxon", t.c_str(), s.c_str());
+            for (const std::vector<unsigned long long> *l : {&a.host_taxids, &a.keep_taxids})
+                for (unsigned long long o : *l)
+                    if (o == id) arg_error("the arguments '--host-taxid <TAXID>' and '--keep-taxid <TAXID>' name taxon %llu more than once", id);
+            if (a.host_taxids.size() + a.keep_taxids.size() == NH_MAX_HOST_TAXA)
+                arg_error("the arguments '--host-taxid <TAXID>' and '--keep-taxid <TAXID>' cannot be used more than %d times together", NH_MAX_HOST_TAXA);
+            (s == "--host-taxid" ? a.host_taxids : a.keep_taxids).push_back(id);
+        }
         else if (s == "--build-db") { a.build_db = val(); a.has_build_db = true; }
         else if (s == "--reference") a.reference.push_back(val());
         else if (s == "--taxid" || s == "--capacity") {
@@ -439,7 +461,8 @@ static Args parse_args(int argc, char **argv) {
                              : !a.kraken_output.empty() ? "--kraken-output" : !a.kraken_report.empty() ? "--kraken-report" : !a.calls.empty() ? "--calls"
                              : !a.human_ids.empty() ? "--human-ids" : !a.read_stats.empty() ? "--read-stats" : a.report_minimizer_data ? "--report-minimizer-data"
                              : !a.minimizer_table.empty() ? "--minimizer-table" : a.has_type ? "--output-type"
-                             : a.bgzf ? "--bgzf" : a.mask ? "--mask" : a.human ? "--human" : !a.taxon_out.empty() ? "--taxon-out" : nullptr;
+                             : a.bgzf ? "--bgzf" : a.mask ? "--mask" : a.human ? "--human" : !a.taxon_out.empty() ? "--taxon-out"
+                             : !a.host_taxids.empty() ? "--host-taxid" : !a.keep_taxids.empty() ? "--keep-taxid" : nullptr;
         if (out_flag) arg_error("the argument '--build-db <DIR>' cannot be used with '%s'", out_flag);
         for (const std::string &r : a.reference)
             if (!exists(r)) arg_error("invalid value '%s' for '--reference <FILE>': %s does not exist", r.c_str(), quoted(r).c_str());
@@ -452,6 +475,8 @@ static Args parse_args(int argc, char **argv) {
     if (a.input.empty() && !a.check && !a.download && !a.list)
         arg_error("the following required arguments were not provided:\n  <INPUT>...");
     if (a.mask && a.human) arg_error("the argument '--mask' cannot be used with '--human'");
+    if (!a.keep_taxids.empty() && a.host_taxids.empty())
+        arg_error("the argument '--keep-taxid <TAXID>' needs '--host-taxid <TAXID>': it keeps a clade inside a host clade");
     // split run (--human-out1 / --human-out2): the non-human reads to -o / -O, the human ones to these, in one pass
     if (a.has_human_out1 || a.has_human_out2) {
         const bool paired = a.input.size() == 2;
@@ -830,7 +855,31 @@ int main(int argc, char **argv) {
     md.struct_size = (uint32_t)sizeof md;
     md.in_report = args.report_minimizer_data ? 1 : 0;
     md.table = args.minimizer_table.empty() ? nullptr : mpart.c_str();
-    const int run_rc = md.in_report || md.table ? nh_run_mdata(&ra, lists || args.mask || split ? &rx : nullptr, args.min_base_quality,
+    nh_host_filter hf;
+    memset(&hf, 0, sizeof hf);
+    hf.struct_size = (uint32_t)sizeof hf;
+    hf.n_host = (uint32_t)args.host_taxids.size(), hf.n_keep = (uint32_t)args.keep_taxids.size();
+    std::vector<uint64_t> host_ids(args.host_taxids.begin(), args.host_taxids.end()), keep_ids(args.keep_taxids.begin(), args.keep_taxids.end());
+    hf.host_taxids = host_ids.empty() ? nullptr : host_ids.data();
+    hf.keep_taxids = keep_ids.empty() ? nullptr : keep_ids.data();
+    const bool hsel = hf.n_host != 0;
+    if (hsel) {  // the host selection by name, before the run
+        auto named = [&](const std::vector<unsigned long long> &ids) {
+            std::string out;
+            for (unsigned long long id : ids) {
+                char b[32];
+                snprintf(b, sizeof b, "%llu (", id);
+                out += (out.empty() ? "" : ", ") + std::string(b) + taxon_name_of(db_path, id) + ")";
+            }
+            return out;
+        };
+        if (args.keep_taxids.empty()) INFO("Host clades: %s", named(args.host_taxids).c_str());
+        else INFO("Host clades: %s; kept clades: %s", named(args.host_taxids).c_str(), named(args.keep_taxids).c_str());
+    }
+    const int run_rc = hsel ? nh_run_host(&ra, lists || args.mask || split ? &rx : nullptr, args.min_base_quality,
+                                          args.read_stats.empty() ? nullptr : spart.c_str(), nullptr, touts.empty() ? nullptr : touts.data(),
+                                          (uint32_t)touts.size(), md.in_report || md.table ? &md : nullptr, &hf, &st)
+                       : md.in_report || md.table ? nh_run_mdata(&ra, lists || args.mask || split ? &rx : nullptr, args.min_base_quality,
                                                                args.read_stats.empty() ? nullptr : spart.c_str(), nullptr,
                                                                touts.empty() ? nullptr : touts.data(), (uint32_t)touts.size(), &md, &st)
                        : !touts.empty() ? nh_run_taxa(&ra, lists || args.mask || split ? &rx : nullptr, args.min_base_quality,
@@ -863,6 +912,9 @@ int main(int argc, char **argv) {
     INFO("%llu / %llu (%s%%) sequences classified as human; %llu (%s%%) as non-human",
          (unsigned long long)st.classified, (unsigned long long)st.total_sequences, pct(st.classified).c_str(),
          (unsigned long long)st.unclassified, pct(st.unclassified).c_str());
+    if (hsel)
+        INFO("%llu host sequences removed; %llu classified sequences outside the host clades kept", (unsigned long long)hf.host_fragments,
+             (unsigned long long)hf.spared_fragments);
     INFO("Kraken2 finished. Organising output...");
 
     if (paired && args.threads / 2 > 1) {  // the reference announces both files before its two compress threads run

@@ -43,7 +43,7 @@ def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
         threads: int = 1, keep_human: bool = False, device_ids=None, out_codec: int = 0,
         codec_threads: int = 0, human_out1=None, human_out2=None, mask: bool = False, calls=None,
         human_ids=None, min_base_quality: int = 0, read_stats=None, taxon_outs=None, report_minimizer_data: bool = False,
-        minimizer_table=None, minimizer_data=None) -> "_lib.nh_stats":
+        minimizer_table=None, minimizer_data=None, host_taxids=None, keep_taxids=None) -> "_lib.nh_stats":
     """nh_run: whole run, database loaded into every listed device (default: all visible).  human_out1 (and, paired,
     human_out2) given: nh_run_split -- the non-human reads go to out1 / out2 and, in the same pass, the human reads to
     human_out1 / human_out2 exactly as a keep_human run would write them.  mask: nh_run_mask -- every read goes to
@@ -66,7 +66,14 @@ def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
     on the GPU by a pass behind the classifier.  report_minimizer_data puts the two clade numbers into columns 4 and 5 of
     `report`; minimizer_table is the path of the project's own table (with the cells of the table per taxon and the coverage);
     minimizer_data is a list that receives a dict per node of the taxonomy, in internal-id order from the root (taxid,
-    reads_clade, reads_own, minimizers_clade, minimizers_own, distinct_clade, distinct_own, db_cells_clade, db_cells_own)."""
+    reads_clade, reads_own, minimizers_clade, minimizers_own, distinct_clade, distinct_own, db_cells_clade, db_cells_own).
+    host_taxids / keep_taxids (nh_run_host; any kind of run): the host selection -- two lists of taxids, 16 together at most.  A
+    classified fragment is a HOST fragment iff the deepest listed taxon that is its call or an ancestor of its call is a host
+    taxid; a classified fragment that is not is SPARED and every output treats it as it treats an unclassified one: out1 / out2,
+    the human outputs, the mask, human_ids and the classes of read_stats follow the selection, while calls, kraken_output,
+    report, taxon_outs, the minimizer data and the stats' three totals keep the true calls.  host_taxids=[1] is the run without a
+    selection; [9606] on a standard database removes only human reads; [1] with keep_taxids=[10239] everything but viruses.  The
+    stats returned then carry host_fragments and spared_fragments (their sum is `classified`)."""
     a = _lib.nh_run_args()
     a.db_dir = os.fsencode(db_dir)
     a.in1 = os.fsencode(in1)
@@ -89,7 +96,22 @@ def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
         a.n_devices = 0
         a.device_ids = None
     s = _lib.nh_stats()
-    if report_minimizer_data or minimizer_table is not None or minimizer_data is not None:
+    if host_taxids or keep_taxids:
+        rs = _read_stats(read_stats) if read_stats is not None else None
+        t = _taxon_outs(taxon_outs or [])
+        want_md = report_minimizer_data or minimizer_table is not None or minimizer_data is not None
+        md = _minimizer_data(report_minimizer_data, minimizer_table, minimizer_data, _taxo_nodes(os.fspath(db_dir))) if want_md else None
+        hf = _host_filter(host_taxids, keep_taxids)
+        _check(_lib.lib().nh_run_host(C.byref(a), _extras_or_none(mask, human_out1, human_out2, calls, human_ids),
+                                      _minq(min_base_quality), _path_or_none(rs.path) if rs else None,
+                                      C.byref(rs.raw) if rs else None, t if len(t) else None, len(t),
+                                      C.byref(md) if md is not None else None, C.byref(hf), C.byref(s)))
+        if md is not None:
+            _minimizer_data_out(md, minimizer_data)
+        if taxon_outs:
+            s.taxon_fragments = [int(x.fragments) for x in t]
+        s.host_fragments, s.spared_fragments = int(hf.host_fragments), int(hf.spared_fragments)
+    elif report_minimizer_data or minimizer_table is not None or minimizer_data is not None:
         rs = _read_stats(read_stats) if read_stats is not None else None
         t = _taxon_outs(taxon_outs or [])
         md = _minimizer_data(report_minimizer_data, minimizer_table, minimizer_data, _taxo_nodes(os.fspath(db_dir)))
@@ -175,6 +197,34 @@ def _minimizer_data_out(md, want_list):
     del want_list[:]
     for i in range(min(int(md.n_taxa), int(md.taxa_cap))):
         want_list.append({name: int(getattr(md.taxa[i], name)) for name, _ in _lib.nh_taxon_minimizers._fields_})
+
+
+def _host_filter(host_taxids, keep_taxids) -> "_lib.nh_host_filter":
+    """run(host_taxids=, keep_taxids=): the nh_host_filter of two lists of taxids (the library checks them)"""
+    hf = _lib.nh_host_filter()
+    hf.struct_size = C.sizeof(_lib.nh_host_filter)
+    for name, ids in (("host", host_taxids), ("keep", keep_taxids)):
+        ids = [int(x) for x in (ids or [])]
+        if any(x < 0 or x >= 2 ** 64 for x in ids):
+            raise EngineError(-1, "%s_taxids: a taxid is a number in 0 .. 2^64 - 1" % name)
+        arr = (C.c_uint64 * max(len(ids), 1))(*ids)
+        setattr(hf, "_keep_" + name, arr)  # (the struct borrows the arrays)
+        setattr(hf, "n_" + name, len(ids))
+        setattr(hf, name + "_taxids", arr)
+    return hf
+
+
+def host_table(taxo_bytes, host_taxids=None, keep_taxids=None) -> bytes:
+    """nh_host_table_image: the host-node table of a selection on a taxo.k2d image, one byte per node in internal-id order (entry
+    0 is 0): 1 where the deepest listed taxon that is the node or an ancestor of it is a host taxid.  No GPU needed."""
+    taxo_bytes = bytes(taxo_bytes)
+    hf = _host_filter(host_taxids, keep_taxids)
+    n = C.c_uint64(0)
+    cap = int.from_bytes(taxo_bytes[8:16], "little") if len(taxo_bytes) >= 16 else 0
+    cap = min(max(cap, 1), max(len(taxo_bytes), 1))  # (a node takes 56 bytes: a count above the image's bytes is refused anyway)
+    buf = (C.c_uint8 * cap)()
+    _check(_lib.lib().nh_host_table_image(taxo_bytes, len(taxo_bytes), C.byref(hf), buf, cap, C.byref(n)))
+    return bytes(buf[:int(n.value)])
 
 
 def _extras(mask, human_out1, human_out2, calls, human_ids) -> "_lib.nh_run_extras":
@@ -492,6 +542,14 @@ class Engine:
         _check(self._L.nh_read_stats_device(self._h, d_text, text_len, d_seq_starts, d_seq_lens, d_qual_starts, d_results, n_frag,
                                             FLAG_PAIRED if paired else 0, d_acc, int(max_workgroups), stream or None))
 
+    def host_filter_device(self, d_res_in: int, d_res_out: int, n: int, d_host_of: int, n_nodes: int, d_counts: int = 0, stream: int = 0):
+        """The host selection's pass behind classify_*_device (nh_host_filter_device): d_res_out[i] = d_res_in[i] (n nh_result, 16-byte
+        aligned; the same array is allowed) with call = 0 where d_host_of[call] is 0 (n_nodes bytes, what host_table() returns).
+        d_counts: two uint64 {host, spared} the kernel adds to.  A call >= n_nodes becomes 0 and fails the engine's next blocking
+        call.  Asynchronous on `stream`."""
+        _check(self._L.nh_host_filter_device(self._h, d_res_in or None, d_res_out or None, int(n), d_host_of or None, int(n_nodes),
+                                             d_counts or None, stream or None))
+
     def minimizer_marks_bytes(self) -> int:
         """bytes of the bitmap minimizer_mark_device writes: one bit a cell of the table, 4 * ceil(capacity / 32)"""
         n = C.c_uint64(0)
@@ -529,11 +587,11 @@ class Engine:
             confidence: float = 0.0, threads: int = 1, keep_human: bool = False, out_codec: int = 0,
             codec_threads: int = 0, human_out1=None, human_out2=None, mask: bool = False, calls=None,
             human_ids=None, min_base_quality: int = 0, read_stats=None, taxon_outs=None, report_minimizer_data: bool = False,
-            minimizer_table=None, minimizer_data=None) -> _lib.nh_stats:
+            minimizer_table=None, minimizer_data=None, host_taxids=None, keep_taxids=None) -> _lib.nh_stats:
         """nh_run_engine; with human_out1 (and, paired, human_out2): nh_run_engine_split; mask: nh_run_engine_mask; with
         calls / human_ids: nh_run_engine_ex; with min_base_quality: nh_run_engine_minq; with read_stats:
         nh_run_engine_rstats; with taxon_outs: nh_run_engine_taxa; with report_minimizer_data / minimizer_table / minimizer_data:
-        nh_run_engine_mdata -- as run() above."""
+        nh_run_engine_mdata; with host_taxids / keep_taxids: nh_run_engine_host -- as run() above."""
         a = _lib.nh_run_args()
         a.db_dir = None
         a.in1 = os.fsencode(in1)
@@ -550,7 +608,22 @@ class Engine:
         a.out_codec = int(out_codec)
         a.codec_threads = int(codec_threads)
         s = _lib.nh_stats()
-        if report_minimizer_data or minimizer_table is not None or minimizer_data is not None:
+        if host_taxids or keep_taxids:
+            rs = _read_stats(read_stats) if read_stats is not None else None
+            t = _taxon_outs(taxon_outs or [])
+            want_md = report_minimizer_data or minimizer_table is not None or minimizer_data is not None
+            md = _minimizer_data(report_minimizer_data, minimizer_table, minimizer_data, self.info.node_count) if want_md else None
+            hf = _host_filter(host_taxids, keep_taxids)
+            _check(self._L.nh_run_engine_host(self._h, C.byref(a), _extras_or_none(mask, human_out1, human_out2, calls, human_ids),
+                                              _minq(min_base_quality), _path_or_none(rs.path) if rs else None,
+                                              C.byref(rs.raw) if rs else None, t if len(t) else None, len(t),
+                                              C.byref(md) if md is not None else None, C.byref(hf), C.byref(s)))
+            if md is not None:
+                _minimizer_data_out(md, minimizer_data)
+            if taxon_outs:
+                s.taxon_fragments = [int(x.fragments) for x in t]
+            s.host_fragments, s.spared_fragments = int(hf.host_fragments), int(hf.spared_fragments)
+        elif report_minimizer_data or minimizer_table is not None or minimizer_data is not None:
             rs = _read_stats(read_stats) if read_stats is not None else None
             t = _taxon_outs(taxon_outs or [])
             md = _minimizer_data(report_minimizer_data, minimizer_table, minimizer_data, self.info.node_count)

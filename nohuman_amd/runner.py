@@ -102,7 +102,7 @@ class CommandRunner:
         opts = {"threads": 1, "db": None, "output": None, "confidence": 0.0, "report": None,
                 "paired": False, "classified_out": None, "unclassified_out": None, "inputs": [],
                 "calls": None, "human_ids": None, "minimum_base_quality": 0, "read_stats": None,
-                "report_minimizer_data": False, "minimizer_table": None}
+                "report_minimizer_data": False, "minimizer_table": None, "host_taxids": [], "keep_taxids": []}
         it = iter(args)
         for a in it:
             if a == "--threads":
@@ -136,6 +136,11 @@ class CommandRunner:
                 opts["report_minimizer_data"] = True
             elif a == "--minimizer-table":  # (the engine's own: nohuman --minimizer-table)
                 opts["minimizer_table"] = next(it)
+            elif a in ("--host-taxid", "--keep-taxid"):  # (the engine's own: nohuman --host-taxid / --keep-taxid, repeatable)
+                v = next(it)
+                if not (v.isascii() and v.isdigit() and 0 < int(v) < 2 ** 64):
+                    raise OSError("%s failed with stderr %s must be a taxid (a positive integer): %s" % ("kraken2", a, v))
+                opts["host_taxids" if a == "--host-taxid" else "keep_taxids"].append(int(v))
             elif a.startswith("--"):
                 raise OSError("%s failed with stderr Unknown option: %s" % ("kraken2", a))
             else:
@@ -212,11 +217,20 @@ class CommandRunner:
                 x.struct_size = C.sizeof(_lib.nh_run_extras)
                 x.calls = os.fsencode(o["calls"]) if o["calls"] is not None else None
                 x.human_ids = os.fsencode(o["human_ids"]) if o["human_ids"] is not None else None
+            md = None
             if o["report_minimizer_data"] or o["minimizer_table"] is not None:
                 md = _lib.nh_minimizer_data()
                 md.struct_size = C.sizeof(_lib.nh_minimizer_data)
                 md.in_report = int(o["report_minimizer_data"])
                 md.table = os.fsencode(o["minimizer_table"]) if o["minimizer_table"] is not None else None
+            if o["host_taxids"] or o["keep_taxids"]:
+                from .engine import _host_filter
+                hf = _host_filter(o["host_taxids"], o["keep_taxids"])
+                rc = L.nh_run_host(C.byref(a), C.byref(x) if x is not None else None, minq, rstats, None, None, 0,
+                                   C.byref(md) if md is not None else None, C.byref(hf), C.byref(s))
+                if rc == 0:
+                    s.host_fragments, s.spared_fragments = int(hf.host_fragments), int(hf.spared_fragments)
+            elif md is not None:
                 rc = L.nh_run_mdata(C.byref(a), C.byref(x) if x is not None else None, minq, rstats, None, None, 0, C.byref(md), C.byref(s))
             elif rstats is not None:
                 rc = L.nh_run_rstats(C.byref(a), C.byref(x) if x is not None else None, minq, rstats, None, C.byref(s))
