@@ -678,6 +678,51 @@ int nh_build_db(const nh_build_args *args, nh_build_stats *stats);
 int nh_build_check(const nh_build_args *args, nh_build_stats *stats);
 
 /*
+ * Extension of an existing database (--build-db OUT --extend-db BASE; nh_build.hip, nh_extend.hip): the taxa of
+ * `b` (a taxa_file, or the one-taxon form fasta / taxid / taxon_name) are added to the database in x->base_dir and the result is
+ * written to b->out_dir.  Only the three .k2d files of the base are needed, not the sequences it was made from: the table is
+ * loaded, re-keyed in place for the merged taxonomy and the new minimizers are inserted into its free cells.
+ * The 64-bit hash of a stored minimizer is not in hash.k2d, so the capacity cannot change: b->capacity must be 0, and
+ * b->load_factor is the highest load the RESULT may have (0 = 0.95).  out_dir, force, mask_low_complexity, piece_kmers, device,
+ * threads and taxon_stats mean what they mean to nh_build_db.
+ * Taxonomy: a manifest line's parent may be 1, another line or an external id of the base; a line whose taxid the base holds adds
+ * its FASTA files to that node (its parent field must name the base's parent; the base's name stays); the one-taxon form is a
+ * child of the root or the existing node of that taxid.  The merged tree is numbered as nh_build_db numbers any tree, value_bits
+ * is the larger of the base's and what the merged nodes need, names are written in internal-id order and the rank strings of the
+ * base are kept ("no rank" for added nodes).  opts.k2d is the base's, byte for byte.  Extending a database made by nh_build_db
+ * gives the taxo.k2d and opts.k2d of a build of all taxa in one go, and the same table (occupied cells, sorted cell words).
+ * Where the value field widens by d bits every stored key loses its low d bits.  Two cells of one probe run whose keys become
+ * equal that way both receive the lowest common ancestor of their values; the later one can no longer be reached by a look-up
+ * and cannot be deleted: shadowed_cells counts such cells, which stay in the table and in `size`.
+ * NH_EINVAL before any device is touched, out_dir as it was: what nh_build_db refuses; base_dir NULL or without one of the three
+ * files; out_dir the same directory as base_dir; capacity not 0; a parent that is neither 1, a line nor in the base; an existing
+ * taxid under another parent; more than 4096 merged nodes.  NH_EDB: a base file with a bad magic or truncated; key_bits +
+ * value_bits not 32; capacity 2^33 or more; an opts.k2d of another geometry than nh_build_db's; a base taxonomy with one
+ * external id twice; on the device, a cell whose value is no node of the base or a count of non-empty cells other than the
+ * header's size.  NH_ECAPACITY, nothing written: the table fills, or size / capacity of the result exceeds the ceiling.
+ * The base directory is never opened for writing.
+ */
+typedef struct {
+    uint32_t struct_size;      /* sizeof(nh_extend_args) of the caller */
+    uint32_t base_cells_cap;   /* entries of base_cells */
+    const char *base_dir;      /* the database to extend: read, never written */
+    uint64_t *base_cells;      /* NULL, or per node of the NEW taxonomy in internal-id order from the root: cells of the
+                                * base table that held it before anything was added (0 for an added node) */
+} nh_extend_args;
+typedef struct {
+    uint32_t struct_size, reserved; /* struct_size: sizeof(nh_extend_stats) of the caller */
+    uint64_t base_size, base_nodes, base_value_bits; /* base_nodes: nodes of the base's taxonomy, the sentinel included */
+    uint64_t nodes_added, cells_added;  /* cells_added = size - base_size */
+    uint64_t shadowed_cells;            /* cells that are not the first of their key in their probe run (above) */
+    double load;                        /* size / capacity of the result */
+    double seconds_load, seconds_rekey; /* base table to the device; the re-key passes alone (events) */
+} nh_extend_stats;
+int nh_extend_db(const nh_build_args *b, const nh_extend_args *x, nh_build_stats *bs, nh_extend_stats *xs);
+/* Every check nh_extend_db makes before it touches a device: the same codes and messages, nothing created.  bs->taxa, the taxid
+ * of every taxon_stats entry (the new internal-id order) and xs->base_nodes, nodes_added and base_value_bits are written. */
+int nh_extend_check(const nh_build_args *b, const nh_extend_args *x, nh_build_stats *bs, nh_extend_stats *xs);
+
+/*
  * Low-complexity masking of a host buffer in place, by the kernel and the launch code the builder uses (nh_dust.hip): symmetric
  * DUST (Morgulis et al. 2006) at dustmasker's defaults, window 64 bases and score threshold 2.0, neither an option.  Each segment
  * [seg_start[i], +seg_len[i]) of text is one sequence: it is split into maximal runs of ACGTacgt (case carries no meaning; any

@@ -133,6 +133,17 @@ class nh_build_stats_v3(nh_build_stats_v2):
     _fields_ = [("taxa", C.c_uint64)]
 
 
+class nh_extend_args(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("base_cells_cap", C.c_uint32), ("base_dir", C.c_char_p),
+                ("base_cells", C.POINTER(C.c_uint64))]
+
+
+class nh_extend_stats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("base_size", C.c_uint64), ("base_nodes", C.c_uint64),
+                ("base_value_bits", C.c_uint64), ("nodes_added", C.c_uint64), ("cells_added", C.c_uint64),
+                ("shadowed_cells", C.c_uint64), ("load", C.c_double), ("seconds_load", C.c_double), ("seconds_rekey", C.c_double)]
+
+
 # every symbol include/nohuman_engine.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -212,6 +223,10 @@ SYMBOLS = {
     "nh_read_stats_write": (C.c_int, [C.POINTER(nh_read_stats), C.c_char_p]),
     "nh_build_db": (C.c_int, [C.POINTER(nh_build_args), C.POINTER(nh_build_stats)]),  # (or their _v2 / _v3 subclasses)
     "nh_build_check": (C.c_int, [C.POINTER(nh_build_args), C.POINTER(nh_build_stats)]),
+    "nh_extend_db": (C.c_int, [C.POINTER(nh_build_args), C.POINTER(nh_extend_args), C.POINTER(nh_build_stats),
+                               C.POINTER(nh_extend_stats)]),
+    "nh_extend_check": (C.c_int, [C.POINTER(nh_build_args), C.POINTER(nh_extend_args), C.POINTER(nh_build_stats),
+                                  C.POINTER(nh_extend_stats)]),
     "nh_dust_mask": (C.c_int, [C.c_int32, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint64,
                                C.POINTER(C.c_uint64)]),
     "nh_allreduce_counters": (C.c_int, [C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_uint64), C.c_char_p,

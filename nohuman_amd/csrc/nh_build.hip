@@ -36,6 +36,10 @@
 // node table (parent) is read from global memory: it is at most 16 KB, shared by every wave and looked at only on that path -- and
 // k_value_cells counts the cells per node of the finished table.  COUNT knows no taxon.  A build of one taxon launches the kernels
 // it always did (MULTI = false).
+//
+// Extension (nh_extend_db; nh_extend.hip): the table is not zeroed but loaded from the base database's hash.k2d and
+// re-keyed in place for the merged taxonomy; INSERT then runs as for several taxa (MULTI even for one added taxon: it merges with
+// values of the base), there is no COUNT, and the capacity is the base's.
 #include <errno.h>
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -54,6 +58,7 @@
 
 #include "nh_device.h"
 #include "nh_dust.h"
+#include "nh_extend.h"
 #include "nh_fastx.h"
 #include "nh_internal.h"
 #include "nh_scan.h"
@@ -731,14 +736,24 @@ std::vector<uint8_t> opts_image() {
 }
 
 // "K2TAXDAT", node count, bytes of the name and the rank strings, 56-byte nodes {parent, first child, child count,
-// name offset, rank offset, external id, godparent}, the two string tables.  The sentinel shares the root's name, "root".
+// name offset, rank offset, external id, godparent}, the two string tables.  The sentinel shares the root's name, "root".  The
+// rank table holds the distinct rank strings in the order of their first use: "no rank" alone unless an extended base had others.
 std::vector<uint8_t> taxo_image(const std::vector<TaxaNode> &nodes) {
-    std::string names = std::string("root") + '\0';
-    const std::string ranks = std::string("no rank") + '\0';
+    std::string names = nodes[1].name + '\0';
+    std::string ranks;
+    std::vector<std::pair<std::string, uint64_t>> rank_at;
     std::vector<uint64_t> recs(nodes.size() * 7, 0);
     for (size_t i = 1; i < nodes.size(); i++) {
         uint64_t *r = &recs[i * 7];
         r[0] = nodes[i].parent, r[1] = nodes[i].first_child, r[2] = nodes[i].children, r[5] = nodes[i].taxid;
+        size_t k = 0;
+        while (k < rank_at.size() && rank_at[k].first != nodes[i].rank) k++;
+        if (k == rank_at.size()) {
+            rank_at.push_back({nodes[i].rank, ranks.size()});
+            ranks += nodes[i].rank;
+            ranks += '\0';
+        }
+        r[4] = rank_at[k].second;
         if (i >= 2) {
             r[3] = names.size();
             names += nodes[i].name;
@@ -765,7 +780,7 @@ bool write_file(const std::string &path, const std::vector<uint8_t> &img) {
 }
 
 // the three files under temporary names, then renamed into place; on any failure nothing of this call stays behind
-int write_database(Builder &B, const nh_build_args *a, const std::vector<TaxaNode> &nodes, uint64_t size) {
+int write_database(Builder &B, const nh_build_args *a, const std::vector<TaxaNode> &nodes, uint64_t size, const std::vector<uint8_t> *opts = nullptr) {
     const std::string dir = a->out_dir;
     bool made_dir = false;
     struct stat st;
@@ -800,7 +815,7 @@ int write_database(Builder &B, const nh_build_args *a, const std::vector<TaxaNod
         if (he != hipSuccess) return fail(NH_EDEVICE, std::string("fetching the table: ") + hipGetErrorString(he));
         if (!ok) return fail(NH_EIO, "cannot write " + tmp[0]);
     }
-    if (!write_file(tmp[1], opts_image())) return fail(NH_EIO, "cannot write " + tmp[1]);
+    if (!write_file(tmp[1], opts ? *opts : opts_image())) return fail(NH_EIO, "cannot write " + tmp[1]);
     if (!write_file(tmp[2], taxo_image(nodes))) return fail(NH_EIO, "cannot write " + tmp[2]);
     for (int i = 0; i < 3; i++)
         if (rename(tmp[i].c_str(), fin[i].c_str()) != 0) return fail(NH_EIO, "cannot move " + tmp[i] + " into place: " + strerror(errno));
@@ -816,6 +831,15 @@ struct BuildPlan {
     std::vector<BuildInput> inputs;  // in the order they are read: by node, a node's files as given
 };
 
+// the database an extension starts from (nh_extend_db), as far as the host reads it
+struct BasePlan {
+    std::string dir;
+    uint64_t capacity = 0, size = 0, old_vb = 0;
+    std::vector<uint8_t> opts;    // opts.k2d as it is
+    BaseTaxo taxo;
+    std::vector<uint32_t> remap;  // internal id of the base -> internal id of the merged tree
+};
+
 // (the caller's layout is told by struct_size: one of an earlier layout gets that layout's stats and no more)
 void layout_of(const nh_build_args *a, BuildPlan &P) {
     P.grown = a && a->struct_size >= NH_BUILD_ARGS_SIZE_V2;
@@ -824,7 +848,7 @@ void layout_of(const nh_build_args *a, BuildPlan &P) {
 }
 
 // ---- arguments: everything refused here is refused before any device is touched and before anything is created
-int plan_build(const nh_build_args *a, BuildPlan &P) {
+int plan_build(const nh_build_args *a, BuildPlan &P, BasePlan *base = nullptr) {
     if (!a) return set_error(NH_EINVAL, "nh_build_db: null arguments");
     if (a->struct_size < NH_BUILD_ARGS_SIZE_V1)
         return set_error(NH_EINVAL, "nh_build_db: struct_size %u is smaller than nh_build_args (%u)", a->struct_size, NH_BUILD_ARGS_SIZE_V1);
@@ -840,7 +864,7 @@ int plan_build(const nh_build_args *a, BuildPlan &P) {
             if (!a->fasta[i]) return set_error(NH_EINVAL, "nh_build_db: input %u is a null path", i);
     }
     if (!a->out_dir || !*a->out_dir) return set_error(NH_EINVAL, "nh_build_db: no output directory");
-    P.lf = a->load_factor == 0 ? 0.7 : a->load_factor;
+    P.lf = a->load_factor == 0 ? (base ? 0.95 : 0.7) : a->load_factor;
     if (!(P.lf > 0 && P.lf <= 0.95)) return set_error(NH_EINVAL, "nh_build_db: load factor %g is not in (0, 0.95]", a->load_factor);
     if (a->taxid == 1) return set_error(NH_EINVAL, "nh_build_db: taxid 1 is the root of the taxonomy, not a taxon to build");
     // (a probe-queue entry of the classifier packs the home cell and the 30-bit key into 63 bits)
@@ -852,7 +876,7 @@ int plan_build(const nh_build_args *a, BuildPlan &P) {
         if (input_is_output(taxa_file, dir))
             return set_error(NH_EINVAL, "nh_build_db: the taxa manifest %s is a database file of the output directory %s", taxa_file, dir.c_str());
         std::string err;
-        const int rc = parse_taxa(taxa_file, P.nodes, err);
+        const int rc = base ? merge_taxa(taxa_file, base->taxo, P.nodes, base->remap, err) : parse_taxa(taxa_file, P.nodes, err);
         if (rc) return set_error(rc, "%s", err.c_str());
         for (size_t i = 2; i < P.nodes.size(); i++)
             for (const std::string &f : P.nodes[i].files) {
@@ -870,7 +894,15 @@ int plan_build(const nh_build_args *a, BuildPlan &P) {
         for (const char *name : DB_FILES)
             if (file_there(dir + "/" + name))
                 return set_error(NH_EINVAL, "nh_build_db: %s already holds %s (`force` replaces a database)", dir.c_str(), name);
-    if (!taxa_file) {  // one taxon: the three nodes it always had
+    if (!taxa_file && base) {  // one taxon on a base: a child of the root, or the node the base has for it
+        const uint64_t taxid = a->taxid ? a->taxid : 9606;
+        const std::string name = a->taxon_name ? a->taxon_name : taxid == 9606 ? "Homo sapiens" : "taxon" + std::to_string(taxid);
+        std::string err;
+        const int rc = merge_taxon(taxid, name, std::vector<std::string>(a->fasta, a->fasta + a->n_fasta), base->taxo, P.nodes, base->remap, err);
+        if (rc) return set_error(rc, "%s", err.c_str());
+        for (size_t i = 2; i < P.nodes.size(); i++)
+            for (const std::string &f : P.nodes[i].files) P.inputs.push_back({f, (uint32_t)i});
+    } else if (!taxa_file) {  // one taxon: the three nodes it always had
         const uint64_t taxid = a->taxid ? a->taxid : 9606;
         P.nodes.resize(3);
         P.nodes[1].taxid = 1, P.nodes[1].name = "root", P.nodes[1].first_child = 2, P.nodes[1].children = 1;
@@ -1003,6 +1035,229 @@ int build_db(const nh_build_args *a, nh_build_stats *stats) {
     return NH_OK;
 }
 
+// ---- nh_extend_db: the taxa of a build added to an existing database (nh_extend.hip) ---------------------------
+bool read_whole(const std::string &path, std::vector<uint8_t> &out, size_t at_most) {
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) return false;
+    out.resize(at_most);
+    const size_t n = fread(out.data(), 1, at_most, f);
+    out.resize(n);
+    fclose(f);
+    return true;
+}
+
+// every check of an extension that needs no device; P.nodes is the merged tree, X.remap the way there from the base's ids
+int plan_extend(const nh_build_args *a, const nh_extend_args *x, const nh_extend_stats *xs, BuildPlan &P, BasePlan &X) {
+    if (!a || !x) return set_error(NH_EINVAL, "nh_extend_db: null arguments");
+    if (a->struct_size < sizeof(nh_build_args))
+        return set_error(NH_EINVAL, "nh_extend_db: struct_size %u is smaller than nh_build_args (%u)", a->struct_size, (unsigned)sizeof(nh_build_args));
+    if (x->struct_size < sizeof(nh_extend_args))
+        return set_error(NH_EINVAL, "nh_extend_db: struct_size %u is smaller than nh_extend_args (%u)", x->struct_size, (unsigned)sizeof(nh_extend_args));
+    if (xs && xs->struct_size < sizeof(nh_extend_stats))
+        return set_error(NH_EINVAL, "nh_extend_db: struct_size %u is smaller than nh_extend_stats (%u)", xs->struct_size, (unsigned)sizeof(nh_extend_stats));
+    if (!x->base_dir || !*x->base_dir) return set_error(NH_EINVAL, "nh_extend_db: no base database (base_dir)");
+    if (a->capacity != 0)
+        return set_error(NH_EINVAL, "nh_extend_db: capacity %llu cannot be given: an extension keeps the capacity of its base (the 64-bit hashes that "
+                         "another capacity would need are not in hash.k2d)", (unsigned long long)a->capacity);
+    X.dir = x->base_dir;
+    for (const char *name : DB_FILES) {
+        struct stat st;
+        if (stat((X.dir + "/" + name).c_str(), &st) != 0 || !S_ISREG(st.st_mode))
+            return set_error(NH_EINVAL, "nh_extend_db: the base database %s holds no %s", X.dir.c_str(), name);
+    }
+    if (a->out_dir && *a->out_dir) {
+        const std::string o = real_of(a->out_dir), b = real_of(X.dir);
+        if (!o.empty() && o == b)
+            return set_error(NH_EINVAL, "nh_extend_db: the output directory %s is the base database itself: an extension is written to a directory of its own", a->out_dir);
+    }
+    {   // hash.k2d: the header, and a file as long as it says
+        const std::string path = X.dir + "/hash.k2d";
+        std::vector<uint8_t> h;
+        struct stat st;
+        if (!read_whole(path, h, 32) || stat(path.c_str(), &st) != 0) return set_error(NH_EIO, "nh_extend_db: cannot read %s: %s", path.c_str(), strerror(errno));
+        if (h.size() < 32) return set_error(NH_EDB, "nh_extend_db: %s is truncated: %llu bytes hold no header", path.c_str(), (unsigned long long)h.size());
+        uint64_t hdr[4];
+        memcpy(hdr, h.data(), 32);
+        if (hdr[2] + hdr[3] != 32 || hdr[3] == 0 || hdr[3] > 31)
+            return set_error(NH_EDB, "nh_extend_db: %s: key_bits %llu + value_bits %llu is not 32", path.c_str(), (unsigned long long)hdr[2], (unsigned long long)hdr[3]);
+        if (hdr[0] == 0 || hdr[0] >> 33) return set_error(NH_EDB, "nh_extend_db: %s: capacity %llu is not in [1, 2^33)", path.c_str(), (unsigned long long)hdr[0]);
+        if ((uint64_t)st.st_size != 32 + 4 * hdr[0])
+            return set_error(NH_EDB, "nh_extend_db: %s is truncated: %llu bytes, but its %llu cells take %llu", path.c_str(), (unsigned long long)st.st_size,
+                             (unsigned long long)hdr[0], (unsigned long long)(32 + 4 * hdr[0]));
+        if (hdr[1] >= hdr[0]) return set_error(NH_EDB, "nh_extend_db: %s: size %llu leaves no empty cell in %llu", path.c_str(), (unsigned long long)hdr[1], (unsigned long long)hdr[0]);
+        X.capacity = hdr[0], X.size = hdr[1], X.old_vb = hdr[3];
+    }
+    {   // opts.k2d: the geometry this builder writes, and no other
+        const std::string path = X.dir + "/opts.k2d";
+        if (!read_whole(path, X.opts, 4096)) return set_error(NH_EIO, "nh_extend_db: cannot read %s: %s", path.c_str(), strerror(errno));
+        if (X.opts.size() < 52) return set_error(NH_EDB, "nh_extend_db: %s is truncated: %llu bytes", path.c_str(), (unsigned long long)X.opts.size());
+        const std::vector<uint8_t> want = opts_image();
+        const char *field = memcmp(X.opts.data(), want.data(), 8)             ? "k"
+                            : memcmp(X.opts.data() + 8, want.data() + 8, 8)   ? "l"
+                            : memcmp(X.opts.data() + 16, want.data() + 16, 8) ? "spaced_seed_mask"
+                            : memcmp(X.opts.data() + 24, want.data() + 24, 8) ? "toggle_mask"
+                            : X.opts[32] != want[32]                          ? "dna_db"
+                            : memcmp(X.opts.data() + 40, want.data() + 40, 8) ? "minimum_acceptable_hash_value"
+                            : memcmp(X.opts.data() + 48, want.data() + 48, 4) ? "revcom_version"
+                                                                              : nullptr;
+        if (field)
+            return set_error(NH_EDB, "nh_extend_db: %s: %s is not that of the default geometry (k = 35, l = 31, the default masks, a DNA database, "
+                             "revcom_version 1, minimum hash 0), the only one that can be extended", path.c_str(), field);
+    }
+    {
+        std::string err;
+        const int rc = read_base_taxo((X.dir + "/taxo.k2d").c_str(), X.taxo, err);
+        if (rc) return set_error(rc, "%s", err.c_str());
+    }
+    return plan_build(a, P, &X);
+}
+
+void extend_plan_stats(const BuildPlan &P, const BasePlan &X, nh_extend_stats &xs) {
+    xs.base_size = X.size;
+    xs.base_nodes = X.taxo.taxid.size();
+    xs.base_value_bits = X.old_vb;
+    xs.nodes_added = P.nodes.size() - X.taxo.taxid.size();
+}
+
+void give_extend_stats(nh_extend_stats *xs, const nh_extend_stats &v) {
+    if (!xs) return;
+    const uint32_t size = xs->struct_size;
+    *xs = v;
+    xs->struct_size = size, xs->reserved = 0;
+}
+
+int extend_check(const nh_build_args *a, const nh_extend_args *x, nh_build_stats *stats, nh_extend_stats *xs) {
+    BuildPlan P;
+    BasePlan X;
+    layout_of(a, P);
+    const int rc = plan_extend(a, x, xs, P, X);
+    if (rc) return rc;
+    if (stats) memset(stats, 0, sizeof *stats);
+    std::vector<nh_build_taxon_stats> per_node(P.nodes.size());
+    for (size_t i = 0; i < P.nodes.size(); i++) memset(&per_node[i], 0, sizeof per_node[i]), per_node[i].taxid = P.nodes[i].taxid;
+    give_taxon_stats(a, P, per_node);
+    if (stats) stats->taxa = P.nodes.size() - 1;
+    nh_extend_stats v;
+    memset(&v, 0, sizeof v);
+    extend_plan_stats(P, X, v);
+    give_extend_stats(xs, v);
+    return NH_OK;
+}
+
+int extend_db(const nh_build_args *a, const nh_extend_args *x, nh_build_stats *stats, nh_extend_stats *xs) {
+    BuildPlan P;
+    BasePlan X;
+    layout_of(a, P);
+    int rc = plan_extend(a, x, xs, P, X);
+    if (rc) return rc;
+    if (stats) memset(stats, 0, sizeof *stats);
+    rc = check_device(a->device);
+    if (rc) return rc;
+    Builder B;
+    B.device = a->device;
+    B.threads = a->threads;
+    B.mask = a->mask_low_complexity != 0;
+    B.node_count = (uint32_t)P.nodes.size();
+    B.multi = true;  // (one added taxon too: its minimizers merge with the values of the base)
+    B.vbits = value_bits_for(B.node_count);
+    if (B.vbits < X.old_vb) B.vbits = (uint32_t)X.old_vb;  // (the value field never shrinks)
+    B.parent.assign((size_t)1 << B.vbits, 0);
+    B.per_node.resize(B.node_count);
+    for (uint32_t i = 0; i < B.node_count; i++) {
+        B.parent[i] = P.nodes[i].parent;
+        memset(&B.per_node[i], 0, sizeof B.per_node[i]);
+        B.per_node[i].taxid = P.nodes[i].taxid;
+    }
+    if (a->piece_kmers) B.piece = a->piece_kmers < (1ull << 31) ? a->piece_kmers : (1ull << 31);
+    if (const char *env = getenv("NOHUMAN_BUILD_BATCH")) {
+        const long long v = atoll(env);
+        if (v > 0) B.batch_cap = (uint64_t)v < 64 ? 64 : (uint64_t)v;
+    }
+    if (const char *env = getenv("NOHUMAN_OPT_AMBIGUITY_RULE")) B.ambig_rule = atoi(env) != 0 ? 1 : 0;
+    else B.ambig_rule = NH_AMBIGUITY_DEFAULT == NH_AMBIGUITY_LAST_LMER ? 0 : 1;
+    rc = B.init();
+    if (rc) return rc;
+
+    nh_extend_stats v;
+    memset(&v, 0, sizeof v);
+    extend_plan_stats(P, X, v);
+    // the base table into the one table-sized buffer there ever is, then re-keyed where it lies
+    rc = B.alloc_table(X.capacity);
+    if (rc) return rc;
+    auto t0 = std::chrono::steady_clock::now();
+    rc = ext_load_table((X.dir + "/hash.k2d").c_str(), B.d_table, X.capacity, B.stream);
+    if (rc) return rc;
+    v.seconds_load = since(t0);
+    ExtendTable T;
+    T.d_table = B.d_table, T.capacity = X.capacity, T.old_vb = (uint32_t)X.old_vb, T.new_vb = B.vbits;
+    T.remap.assign(X.remap.begin(), X.remap.end());
+    T.d_parent = B.d_parent, T.grid_max = B.grid_max, T.stream = B.stream;
+    rc = ext_rekey(T);
+    if (rc) return rc;
+    const std::string hash_path = X.dir + "/hash.k2d";
+    if (T.bad_value)
+        return set_error(NH_EDB, "nh_extend_db: %s holds a cell whose value is no node of its taxonomy (%llu nodes)", hash_path.c_str(),
+                         (unsigned long long)X.taxo.taxid.size());
+    if (T.non_empty != X.size)
+        return set_error(NH_EDB, "nh_extend_db: %s holds %llu non-empty cells, but its header gives the size %llu", hash_path.c_str(),
+                         (unsigned long long)T.non_empty, (unsigned long long)X.size);
+    v.seconds_rekey = T.seconds_rekey;
+    v.shadowed_cells = T.shadowed;
+    rc = B.count_cells();
+    if (rc) return rc;
+    std::vector<uint64_t> base_cells(B.node_count, 0);
+    for (uint32_t i = 1; i < B.node_count; i++) base_cells[i] = B.per_node[i].cells;
+
+    const uint64_t free_cells = X.capacity - X.size;
+    rc = B.pass(P.inputs, false, true);
+    if (rc == NH_ECAPACITY)
+        return set_error(NH_ECAPACITY, "nh_extend_db: the base table has %llu free cells of %llu and the addition needs more than that: the capacity of "
+                         "an extension is its base's", (unsigned long long)free_cells, (unsigned long long)X.capacity);
+    if (rc) return rc;
+    nh_build_stats s;
+    memset(&s, 0, sizeof s);
+    s.seconds_insert = B.t_gpu;
+    s.seconds_read = B.t_read;
+    s.sequences = B.sequences;
+    s.bases = B.bases;
+    s.kmers = B.kmers;
+    s.ambiguous_kmers = B.kmers - B.clean;
+    s.capacity = X.capacity;
+    s.size = X.size + B.claimed;
+    s.masked_bases = B.masked;
+    s.seconds_mask = B.t_mask;
+    s.taxa = B.node_count - 1;
+    v.cells_added = B.claimed;
+    v.load = (double)s.size / (double)s.capacity;
+    if (s.size >= X.capacity)
+        return set_error(NH_ECAPACITY, "nh_extend_db: the base table has %llu free cells of %llu and the addition needs %llu, which leaves no empty "
+                         "cell: the capacity of an extension is its base's", (unsigned long long)free_cells, (unsigned long long)X.capacity,
+                         (unsigned long long)B.claimed);
+    if (v.load > P.lf)
+        return set_error(NH_ECAPACITY, "nh_extend_db: the base table has %llu free cells of %llu and the addition needs %llu: the load would be %.4f, "
+                         "above the ceiling of %.4f (load_factor)", (unsigned long long)free_cells, (unsigned long long)X.capacity,
+                         (unsigned long long)B.claimed, v.load, P.lf);
+    BUILD_TRY(hipMemsetAsync(B.d_cells, 0, (size_t)B.node_count * sizeof(unsigned long long), B.stream));
+    rc = B.count_cells();
+    if (rc) return rc;
+    t0 = std::chrono::steady_clock::now();
+    rc = write_database(B, a, P.nodes, s.size, &X.opts);
+    if (rc) return rc;
+    s.seconds_write = since(t0);
+    if (getenv("NOHUMAN_TRACE"))
+        fprintf(stderr, "[nohuman trace] extend: base %llu cells of %llu at %llu value bits, %llu nodes; now %u value bits, %u nodes, table %s; "
+                        "%llu shadowed; %llu cells added; load %.4f s, re-key %.6f s (the streaming pass alone %.6f s), insert kernels %.4f s\n",
+                (unsigned long long)X.size, (unsigned long long)X.capacity, (unsigned long long)X.old_vb, (unsigned long long)X.taxo.taxid.size(),
+                B.vbits, B.node_count, T.rekeyed ? "rewritten" : "as it was", (unsigned long long)T.shadowed, (unsigned long long)B.claimed,
+                v.seconds_load, v.seconds_rekey, T.seconds_pass, B.t_kernel);
+    give_taxon_stats(a, P, B.per_node);
+    if (x->base_cells)
+        for (uint32_t i = 1; i < B.node_count && i - 1 < x->base_cells_cap; i++) x->base_cells[i - 1] = base_cells[i];
+    if (stats) memcpy(stats, &s, sizeof s);
+    give_extend_stats(xs, v);
+    return NH_OK;
+}
+
 }  // namespace
 }  // namespace nh
 
@@ -1023,5 +1278,25 @@ extern "C" int nh_build_db(const nh_build_args *args, nh_build_stats *stats) {
         return nh::set_error(NH_EOOM, "nh_build_db: out of host memory");
     } catch (const std::exception &e) {
         return nh::set_error(NH_EIO, "nh_build_db: %s", e.what());
+    }
+}
+
+extern "C" int nh_extend_check(const nh_build_args *b, const nh_extend_args *x, nh_build_stats *bs, nh_extend_stats *xs) {
+    try {
+        return nh::extend_check(b, x, bs, xs);
+    } catch (const std::bad_alloc &) {
+        return nh::set_error(NH_EOOM, "nh_extend_check: out of host memory");
+    } catch (const std::exception &e) {
+        return nh::set_error(NH_EIO, "nh_extend_check: %s", e.what());
+    }
+}
+
+extern "C" int nh_extend_db(const nh_build_args *b, const nh_extend_args *x, nh_build_stats *bs, nh_extend_stats *xs) {
+    try {
+        return nh::extend_db(b, x, bs, xs);
+    } catch (const std::bad_alloc &) {
+        return nh::set_error(NH_EOOM, "nh_extend_db: out of host memory");
+    } catch (const std::exception &e) {
+        return nh::set_error(NH_EIO, "nh_extend_db: %s", e.what());
     }
 }

@@ -231,6 +231,8 @@ struct Args {
     bool has_type = false;
     Codec type = C_NONE;
     // --build-db: make a database from FASTA instead of running on reads (nh_build_db)
+    std::string extend_db;  // --extend-db: the database that --build-db adds its taxa to (nh_extend_db)
+    bool has_extend_db = false;
     std::string build_db, taxon_name, taxa;  // taxa: the manifest of a build of several taxa (nh_build_args.taxa_file)
     bool has_taxa = false, has_taxid = false;
     bool has_build_db = false, has_taxon_name = false, has_build_opt = false, force = false, mask_low_complexity = false;
@@ -287,6 +289,9 @@ static void usage(FILE *f) {
           "      --taxon-name <NAME>      Name of the host in the database's taxonomy for --build-db\n"
           "      --taxa <FILE>            Build a database of several taxa from a manifest, one taxon per line, tab-separated: taxid, parent taxid (1 is the root), name, "
           "FASTA files; a minimizer shared by two taxa is stored as their lowest common ancestor\n"
+          "      --extend-db <DIR>        With a database build: add the taxa given to the existing database in DIR (its three .k2d files are enough, not the "
+          "genomes it was made from) and write the result to the build's directory; the table keeps its size, a load factor given is the highest load "
+          "the result may have [default: 0.95], a fixed number of cells cannot be asked for\n"
           "      --load-factor <FLOAT>    Load factor of the hash table for --build-db, in (0, 0.95] [default: 0.7]\n"
           "      --capacity <INT>         Cells of the hash table for --build-db; skips the counting pass [default: distinct minimizers / load factor]\n"
           "      --force                  Let --build-db replace a database that DIR already holds\n"
@@ -418,6 +423,7 @@ static Args parse_args(int argc, char **argv) {
             (s == "--host-taxid" ? a.host_taxids : a.keep_taxids).push_back(id);
         }
         else if (s == "--build-db") { a.build_db = val(); a.has_build_db = true; }
+        else if (s == "--extend-db") { a.extend_db = val(); a.has_extend_db = true; }
         else if (s == "--reference") a.reference.push_back(val());
         else if (s == "--taxid" || s == "--capacity") {
             std::string t = val();
@@ -464,6 +470,10 @@ static Args parse_args(int argc, char **argv) {
                              : a.bgzf ? "--bgzf" : a.mask ? "--mask" : a.human ? "--human" : !a.taxon_out.empty() ? "--taxon-out"
                              : !a.host_taxids.empty() ? "--host-taxid" : !a.keep_taxids.empty() ? "--keep-taxid" : nullptr;
         if (out_flag) arg_error("the argument '--build-db <DIR>' cannot be used with '%s'", out_flag);
+        if (a.has_extend_db) {
+            if (a.capacity) arg_error("the argument '--extend-db <DIR>' cannot be used with '--capacity <INT>': an extension keeps the capacity of its base");
+            if (!exists(a.extend_db)) arg_error("invalid value '%s' for '--extend-db <DIR>': %s does not exist", a.extend_db.c_str(), quoted(a.extend_db).c_str());
+        }
         for (const std::string &r : a.reference)
             if (!exists(r)) arg_error("invalid value '%s' for '--reference <FILE>': %s does not exist", r.c_str(), quoted(r).c_str());
         return a;
@@ -471,6 +481,7 @@ static Args parse_args(int argc, char **argv) {
     if (a.mask_low_complexity) arg_error("the argument '--mask-low-complexity' needs '--build-db <DIR>': it masks the genome a database is built from, not reads");
     if (!a.reference.empty()) arg_error("the argument '--reference <FILE>' needs '--build-db <DIR>'");
     if (a.has_taxa) arg_error("the argument '--taxa <FILE>' needs '--build-db <DIR>'");
+    if (a.has_extend_db) arg_error("the argument '--extend-db <DIR>' needs '--build-db <DIR>': it names the database that the build adds its taxa to");
     if (a.has_build_opt) arg_error("the arguments '--taxid', '--taxon-name', '--load-factor', '--capacity' and '--force' need '--build-db <DIR>'");
     if (a.input.empty() && !a.check && !a.download && !a.list)
         arg_error("the following required arguments were not provided:\n  <INPUT>...");
@@ -632,7 +643,18 @@ static void fill_build_args(const Args &args, std::vector<const char *> &refs, n
 
 int main(int argc, char **argv) {
     Args args = parse_args(argc, argv);
-    if (args.has_build_db && args.has_taxa) {  // what the manifest says wrongly is an argument error too: read before any device is asked for
+    if (args.has_build_db && args.has_extend_db) {  // the base, the taxa and how they fit together: checked before any device is asked for
+        std::vector<const char *> refs;
+        nh_build_args ba;
+        fill_build_args(args, refs, ba);
+        nh_extend_args xa;
+        memset(&xa, 0, sizeof xa);
+        xa.struct_size = (uint32_t)sizeof xa;
+        xa.base_dir = args.extend_db.c_str();
+        const int rc = nh_extend_check(&ba, &xa, nullptr, nullptr);
+        if (rc == NH_EINVAL) arg_error("invalid value '%s' for '--extend-db <DIR>': %s", args.extend_db.c_str(), nh_last_error());
+        if (rc != 0) die("Failed to extend the database\n\nCaused by:\n    %s", nh_last_error());
+    } else if (args.has_build_db && args.has_taxa) {  // what the manifest says wrongly is an argument error too: read before any device is asked for
         std::vector<const char *> refs;
         nh_build_args ba;
         fill_build_args(args, refs, ba);
@@ -681,6 +703,45 @@ int main(int argc, char **argv) {
     DEBUG("kraken2 is executable (in-process engine: %s)", probe);
     if (args.check) {
         INFO("All dependencies are available");
+        return 0;
+    }
+    if (args.has_build_db && args.has_extend_db) {
+        INFO("Extending database %s into %s...", quoted(args.extend_db).c_str(), quoted(args.build_db).c_str());
+        std::vector<const char *> refs;
+        nh_build_args ba;
+        fill_build_args(args, refs, ba);
+        std::vector<nh_build_taxon_stats> per_taxon(4096);
+        std::vector<uint64_t> base_cells(4096, 0);
+        ba.taxon_stats = per_taxon.data();
+        ba.taxon_stats_cap = (uint32_t)per_taxon.size();
+        nh_extend_args xa;
+        memset(&xa, 0, sizeof xa);
+        xa.struct_size = (uint32_t)sizeof xa;
+        xa.base_dir = args.extend_db.c_str();
+        xa.base_cells = base_cells.data();
+        xa.base_cells_cap = (uint32_t)base_cells.size();
+        nh_build_stats bs;
+        nh_extend_stats xs;
+        memset(&xs, 0, sizeof xs);
+        xs.struct_size = (uint32_t)sizeof xs;
+        if (nh_extend_db(&ba, &xa, &bs, &xs) != 0) die("Failed to extend the database\n\nCaused by:\n    %s", nh_last_error());
+        INFO("Base database: size %llu, capacity %llu, load %.4f, %llu nodes, %llu value bits", (unsigned long long)xs.base_size, (unsigned long long)bs.capacity,
+             bs.capacity ? (double)xs.base_size / (double)bs.capacity : 0.0, (unsigned long long)(xs.base_nodes - 1), (unsigned long long)xs.base_value_bits);
+        INFO("Database extended: %llu nodes added, %llu sequences, %llu bases, %llu cells added, %llu shadowed cells, size %llu, load %.4f; load %.2f s, "
+             "re-key %.4f s, read %.2f s, insert %.2f s, write %.2f s",
+             (unsigned long long)xs.nodes_added, (unsigned long long)bs.sequences, (unsigned long long)bs.bases, (unsigned long long)xs.cells_added,
+             (unsigned long long)xs.shadowed_cells, (unsigned long long)bs.size, xs.load, xs.seconds_load, xs.seconds_rekey, bs.seconds_read, bs.seconds_insert,
+             bs.seconds_write);
+        if (args.mask_low_complexity)
+            INFO("%llu low-complexity bases masked (%.2f %% of the bases), mask %.2f s", (unsigned long long)bs.masked_bases,
+                 bs.bases ? 100.0 * (double)bs.masked_bases / (double)bs.bases : 0.0, bs.seconds_mask);
+        const std::vector<std::string> taxon_names = node_names(args.build_db);
+        for (uint64_t i = 0; i < bs.taxa && i < per_taxon.size(); i++)  // (how many minimizers of the base an added taxon moved up the tree)
+            if (per_taxon[i].cells != base_cells[i])
+                DEBUG("  %s (taxid %llu): %llu cells before, %llu after", taxon_names.size() > i ? taxon_names[i].c_str() : "?",
+                      (unsigned long long)per_taxon[i].taxid, (unsigned long long)base_cells[i], (unsigned long long)per_taxon[i].cells);
+        INFO("Database written to: %s", quoted(args.build_db).c_str());
+        INFO("Done.");
         return 0;
     }
     if (args.has_build_db) {

@@ -324,6 +324,59 @@ def build_db(fasta_paths=None, out_dir=None, *, taxid: int = 0, taxon_name=None,
     return out
 
 
+def extend_db(base_dir, out_dir, fasta_paths=None, *, taxa=None, taxid: int = 0, taxon_name=None, max_load: float = 0.0,
+              mask_low_complexity: bool = False, force: bool = False, device: int = 0, threads: int = 1, piece_kmers: int = 0) -> dict:
+    """nh_extend_db: the database in base_dir with taxa added, written to out_dir -- only the three .k2d files of the base are
+    needed, not the sequences it was made from.  The taxa are one taxon (fasta_paths, taxid, taxon_name: a child of the root, or
+    the base's node of that taxid) or a manifest as build_db(taxa=...) reads it, whose parents may also be taxids of the base and
+    whose lines may name a taxon of the base to add sequences to it.  The table keeps the capacity of the base (its free cells
+    are the room there is); max_load is the highest load the result may have (0 = 0.95) -- EngineError with code -6
+    (NH_ECAPACITY) and nothing written where the addition does not fit.  Returns nh_build_stats and nh_extend_stats as one
+    dict (base_size, base_nodes, base_value_bits, nodes_added, cells_added, shadowed_cells, load, seconds_load, seconds_rekey
+    beside build_db's keys) with taxon_stats, a list of dicts (taxid, sequences, bases, kmers, cells, base_cells: the cells
+    the node held in the base, after renumbering) a node of the merged taxonomy in internal-id order from the root on."""
+    if fasta_paths is None:
+        fasta_paths = []
+    if isinstance(fasta_paths, (str, bytes, os.PathLike)):
+        fasta_paths = [fasta_paths]
+    paths = [os.fsencode(p) for p in fasta_paths]
+    a = _lib.nh_build_args_v3()
+    a.struct_size = C.sizeof(_lib.nh_build_args_v3)
+    a.mask_low_complexity = int(bool(mask_low_complexity))
+    a.n_fasta = len(paths)
+    arr = (C.c_char_p * max(len(paths), 1))(*paths)
+    if paths or taxa is None:
+        a.fasta = arr
+    if taxa is not None:
+        a.taxa_file = os.fsencode(taxa)
+    per_node = (_lib.nh_build_taxon_stats * MAX_TAXA_NODES)()
+    a.taxon_stats = per_node
+    a.taxon_stats_cap = MAX_TAXA_NODES
+    a.out_dir = os.fsencode(out_dir) if out_dir is not None else None
+    a.taxid = int(taxid)
+    a.taxon_name = taxon_name.encode() if isinstance(taxon_name, str) else taxon_name
+    a.load_factor = float(max_load)
+    a.piece_kmers = int(piece_kmers)
+    a.device = int(device)
+    a.threads = int(threads)
+    a.force = int(bool(force))
+    x = _lib.nh_extend_args()
+    x.struct_size = C.sizeof(_lib.nh_extend_args)
+    x.base_dir = os.fsencode(base_dir) if base_dir is not None else None
+    base_cells = (C.c_uint64 * MAX_TAXA_NODES)()
+    x.base_cells = base_cells
+    x.base_cells_cap = MAX_TAXA_NODES
+    s = _lib.nh_build_stats_v3()
+    xs = _lib.nh_extend_stats()
+    xs.struct_size = C.sizeof(_lib.nh_extend_stats)
+    _check(_lib.lib().nh_extend_db(C.byref(a), C.byref(x), C.byref(s), C.byref(xs)))
+    out = {name: getattr(s, name) for name, _ in _lib.nh_build_stats._fields_ + _lib.nh_build_stats_v2._fields_ + _lib.nh_build_stats_v3._fields_}
+    out.update({name: getattr(xs, name) for name, _ in _lib.nh_extend_stats._fields_ if name not in ("struct_size", "reserved")})
+    out["taxon_stats"] = [dict({name: getattr(per_node[i], name) for name, _ in _lib.nh_build_taxon_stats._fields_}, base_cells=int(base_cells[i]))
+                          for i in range(min(int(s.taxa), MAX_TAXA_NODES))]
+    return out
+
+
 def dust_mask(seqs, device: int = 0):
     """nh_dust_mask: low-complexity masking of sequences on the GPU -- symmetric DUST at dustmasker's defaults (window 64,
     threshold 2.0), the kernel build_db(mask_low_complexity=True) runs.  seqs: bytes objects (one alone is taken as a list of
