@@ -260,6 +260,40 @@ int nh_run(const nh_run_args *args, nh_stats *stats);
  * over every record's header line, sequence and qualities (each followed by one 0 byte).
  * Needs no GPU. */
 int nh_fastx_scan(const char *path, uint64_t *n_records, uint64_t *n_bases, uint64_t *digest);
+/*
+ * BAM input.  in1 of every nh_run* may be a BAM file -- unaligned (ONT, PacBio HiFi, uBAM) or aligned, single-end: a file whose
+ * first gzip member carries the BGZF extra field and whose inflated stream begins "BAM\1"; anything else is read as before.  Its
+ * records are transcoded on the GPU to the canonical FASTQ `samtools fastq` would write (as far as that is recalled: DESIGN.md
+ * 6.16) and everything behind the reader runs on that text: "@name\nSEQ\n+\nQUAL\n", bases from "=ACMGRSVTWYHKDBN", qualities
+ * + 33 (absent qualities, first byte 0xFF: every quality '"'), reverse-strand records (flag 0x10) reverse-complemented with their
+ * qualities reversed, no tags in the header.  Secondary and supplementary records (0x100, 0x800) and records without bases are
+ * skipped; a paired record (0x1) fails the run with NH_EIO, as every malformed record does, with the record's ordinal in the
+ * message.  A BAM in1 with an in2, or a BAM in2, is NH_EINVAL before any device is touched.
+ *
+ * nh_bam_scan: the host side alone, no device -- the counts of a BAM file and nh_fastx_scan's digest of the FASTQ it transcodes
+ * to.  NH_EINVAL: a null argument, a struct_size below the struct's, a file that is no BAM; NH_EIO: a malformed one.
+ */
+typedef struct nh_bam_info {
+    uint32_t struct_size;          /* sizeof(nh_bam_info), set by the caller */
+    uint32_t reserved;
+    uint64_t records;              /* all records of the file */
+    uint64_t reads;                /* records kept */
+    uint64_t bases;                /* bases of the kept records */
+    uint64_t skipped_secondary;    /* flag 0x100 or 0x800 */
+    uint64_t skipped_empty;        /* l_seq == 0 */
+    uint64_t reverse_complemented; /* kept records with flag 0x10 */
+    uint64_t missing_qualities;    /* kept records whose qualities are absent */
+    uint64_t digest;
+} nh_bam_info;
+int nh_bam_scan(const char *path, uint32_t threads, nh_bam_info *info);
+/* The kernel alone, asynchronous on `stream`, on the engine's device.  d_bam: bam_len BAM bytes (4-byte aligned, readable up to
+ * bam_len rounded up to a multiple of 4); d_table: two uint64 a record -- the offset of its block_size field in d_bam and the
+ * offset of its '@' in d_text, the latter ascending; d_text: text_cap bytes (4-byte aligned) of which [0, text_len) is the text.
+ * error_bits: one int in device memory, zeroed by the caller.  A record whose fields, as its own fixed part states them, do not
+ * lie inside d_bam sets bit 1 there, one whose text does not lie inside [0, text_len) bit 2; nothing of such a record is written
+ * and the others are.  NOHUMAN_BAM_SPAN: the bytes of text one wave writes of a long record (a test and tuning knob). */
+int nh_bam_to_fastq_device(nh_engine *e, const void *d_bam, uint64_t bam_len, const void *d_table, uint64_t n_records,
+                           void *d_text, uint64_t text_cap, uint64_t text_len, int *error_bits, void *stream);
 /* Output compression stage: replaces CompressionFormat::compress
  * (/root/reference/src/compression.rs:182-200, called from src/main.rs:342-368).  Compresses file
  * `in` to file `out`; gzip runs block-parallel on `threads` workers like the reference's gzp

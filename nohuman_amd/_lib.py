@@ -144,6 +144,12 @@ class nh_extend_stats(C.Structure):
                 ("shadowed_cells", C.c_uint64), ("load", C.c_double), ("seconds_load", C.c_double), ("seconds_rekey", C.c_double)]
 
 
+class nh_bam_info(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("records", C.c_uint64), ("reads", C.c_uint64),
+                ("bases", C.c_uint64), ("skipped_secondary", C.c_uint64), ("skipped_empty", C.c_uint64),
+                ("reverse_complemented", C.c_uint64), ("missing_qualities", C.c_uint64), ("digest", C.c_uint64)]
+
+
 # every symbol include/nohuman_engine.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -184,8 +190,10 @@ SYMBOLS = {
     "nh_gunzip_device_file": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int32, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
     "nh_fastx_scan": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                 C.POINTER(C.c_uint64)]),
+    "nh_bam_scan": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(nh_bam_info)]),
+    "nh_bam_to_fastq_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, _P, C.c_uint64, C.c_uint64, _P, _P]),
     "nh_run": (C.c_int, [C.POINTER(nh_run_args), C.POINTER(nh_stats)]),
-    "nh_run_engine": (C.c_int, [_P, C.POINTER(nh_run_args), C.POINTER(nh_stats)]),
+    "nh_run_engine":(C.c_int, [_P, C.POINTER(nh_run_args), C.POINTER(nh_stats)]),
     "nh_run_split": (C.c_int, [C.POINTER(nh_run_args), C.c_char_p, C.c_char_p, C.POINTER(nh_stats)]),
     "nh_run_engine_split": (C.c_int, [_P, C.POINTER(nh_run_args), C.c_char_p, C.c_char_p, C.POINTER(nh_stats)]),
     "nh_run_mask": (C.c_int, [C.POINTER(nh_run_args), C.c_char_p, C.c_char_p, C.POINTER(nh_stats)]),

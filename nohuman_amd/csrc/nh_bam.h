@@ -1,0 +1,127 @@
+// nh_bam.h -- BAM input: unaligned or aligned single-end reads, transcoded to canonical FASTQ text.
+//
+// The BGZF stream is inflated on the host (ByteSource: BGZF is multi-member gzip), the records are chained by their
+// block_size and validated there (BamStream), and the per-base work -- 4-bit bases to ASCII, qualities + 33, the reverse
+// complement of reverse-strand records, "@name\nSEQ\n+\nQUAL\n" -- is done by k_bam_fastq (nh_bam.hip) on the batch's BAM bytes in
+// HBM.  What leaves BamReader is what DevFastqReader hands out: a FASTQ text in device memory and its record table.
+// tests/bam_model.py is the specification; DESIGN.md 6.16.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include <stdlib.h>
+
+#include <functional>
+#include <string>
+#include <vector>
+
+#include "nh_fastx.h"
+#ifndef NH_BAM_HOST_ONLY
+#include <hip/hip_runtime.h>
+#endif
+
+namespace nh {
+
+// the FASTQ text one kept record transcodes to: '@' name '\n' bases "\n+\n" qualities '\n'
+inline uint64_t bam_text_len(uint32_t name_len, uint32_t l_seq) { return (uint64_t)name_len + 2ull * l_seq + 6; }
+
+struct BamRec {  // one record as chained on the host; offsets into the window it was chained in
+    size_t off;          // its block_size field
+    uint32_t block_size, l_read_name, n_cigar, flag, l_seq;
+    uint64_t ordinal;    // 1-based, all records of the file counted
+    size_t name() const { return off + 36; }
+    size_t seq() const { return off + 36 + l_read_name + 4 * (size_t)n_cigar; }
+    size_t qual() const { return seq() + ((size_t)l_seq + 1) / 2; }
+    uint32_t name_len() const { return l_read_name - 1; }
+    uint64_t text_len() const { return bam_text_len(name_len(), l_seq); }
+};
+
+struct BamCounts {
+    uint64_t records = 0, reads = 0, bases = 0, skipped_secondary = 0, skipped_empty = 0, reverse_complemented = 0, missing_qualities = 0;
+};
+
+// The inflated BAM stream as a window of bytes and a cursor: header, then record by record.  The source is any function that
+// fills a buffer (ByteSource::read; the stand-alone scan of the sanitizer build reads with zlib).
+class BamStream {
+public:
+    typedef std::function<long(uint8_t *, size_t)> ReadFn;  // bytes read, 0 at the end, -1 on error
+    void open(ReadFn read, const std::string &name) {
+        read_ = std::move(read);
+        name_ = name;
+        if (const char *env = getenv("NOHUMAN_BAM_CHUNK")) {  // test knob: records and fixed parts cut at every offset
+            const long v = atol(env);
+            if (v > 0) chunk = (size_t)v;
+        }
+    }
+    // the magic, the text and the references: 0, or -1 with err set
+    int read_header(std::string &err);
+    // The next KEPT record (secondary, supplementary and empty ones are counted and stepped over): 1 and *r (offsets into
+    // data(), valid until the next compact()), 0 at the end of the stream, -1 malformed (err set: the record's ordinal).
+    int next(BamRec *r, std::string &err);
+    const uint8_t *data() const { return win_.data(); }
+    size_t cursor() const { return pos_; }
+    // drops the bytes in front of the cursor (the records handed out so far are gone)
+    void compact();
+    const BamCounts &counts() const { return cnt_; }
+    size_t chunk = 4u << 20;  // bytes per read of the source
+    bool holding = false;     // the caller keeps records of this window: next() does not compact it over skipped ones
+
+private:
+    int ensure(size_t n, std::string &err);  // n bytes at the cursor: 1, 0 the stream ends before, -1 read error
+    ReadFn read_;
+    std::string name_;
+    std::vector<uint8_t> win_;
+    size_t pos_ = 0, len_ = 0;
+    bool eof_ = false;
+    BamCounts cnt_;
+};
+
+// One record's FASTQ text in plain C++ (the rules of the kernel): text_len() bytes at out.  bam: the window r points into.
+void bam_transcode(const uint8_t *bam, const BamRec &r, char *out);
+// header / id of a kept record as every reader here states them: hlen without trailing white space, the id up to the first
+// blank; false: the name cannot stand in a FASTQ header line (a line feed in it, nothing but white space)
+bool bam_name_fields(const uint8_t *name, uint32_t name_len, uint32_t *hlen, uint32_t *idlen);
+
+// the scan behind nh_bam_scan on any source: counts and nh_fastx_scan's digest of the FASTQ the stream transcodes to
+int bam_scan_stream(BamStream &s, BamCounts *counts, uint64_t *digest, std::string &err);
+
+// Is the file a BAM: its first gzip member carries the BGZF extra field and inflates to a stream that begins "BAM\1"
+bool bam_wants(const char *path);
+
+#ifndef NH_BAM_HOST_ONLY
+class BamReaderImpl;
+// BlockReader's shape on a BAM file; the batches are born on a device (DevFastqReader's hand-over).
+class BamReader {
+public:
+    BamReader();
+    ~BamReader();
+    BamReader(const BamReader &) = delete;
+    BamReader &operator=(const BamReader &) = delete;
+    // devices: the GPUs of the run -- batch b is transcoded on devices[b mod n] and says so (HalfBatch::dev_device)
+    int open(const char *path, const int *devices, int n_devices, std::string &err, unsigned gz_threads = 0);
+    // up to max_recs records, cut after the record that reaches max_text bytes of FASTQ text (BlockReader::next_batch's rule);
+    // hb.eof at the end of the input, hb.error on malformed input or a device failure
+    void next_batch(HalfBatch &hb, size_t max_recs, size_t max_text);
+    const BamCounts &counts() const;
+    void close();  // waits until every batch handed out has been released
+
+private:
+    BamReaderImpl *impl_;
+};
+
+// k_bam_fastq (nh_bam.hip).  table: two uint64 a record -- where its block_size field lies in bam, where its '@' lies in text.
+// error: one word, BAM_ERR_* are set in it.  span 0: NOHUMAN_BAM_SPAN, else the default.
+enum { BAM_ERR_FIELDS = 1, BAM_ERR_TEXT = 2 };
+struct BamFastqArgs {
+    const uint8_t *bam;
+    uint64_t bam_len;
+    const uint64_t *table;
+    uint64_t n;
+    char *text;
+    uint64_t text_cap, text_len;
+    int *error;
+    uint32_t span;
+};
+hipError_t launch_bam_fastq(const BamFastqArgs &a, hipStream_t stream);
+#endif
+
+}  // namespace nh

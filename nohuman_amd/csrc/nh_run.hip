@@ -28,6 +28,7 @@
 #include <string>
 #include <vector>
 
+#include "nh_bam.h"
 #include "nh_codec.h"
 #include "nh_fastx.h"
 #include "nh_gunzip.h"
@@ -290,12 +291,30 @@ static int write_mdata_table(const TaxoView &t, const MdataNumbers &m, const cha
 //                   b mod G, database replicated per device: SURVEY.md section 8e)
 // writer thread:    format and write the outputs of finished batches in input order
 static size_t estimate_batch_frags(const char *path, size_t *mean_record_bytes) {
-    BlockReader r;
     std::string err;
     *mean_record_bytes = 0;
-    if (r.open(path, err) != 0) return 1u << 18;
     HalfBatch hb;
-    r.next_batch(hb, 256, 64u << 20);
+    if (bam_wants(path)) {  // the first kept records of a BAM: their lengths as the FASTQ text they become
+        ByteSource src;
+        if (src.open(path, err) != 0) return 1u << 18;
+        BamStream bs;
+        bs.open([&](uint8_t *b, size_t n) { return src.read(b, n); }, path);
+        bs.chunk = 1u << 20;
+        if (bs.read_header(err) != 0) return 1u << 18;
+        bs.holding = true;
+        BamRec br;
+        uint32_t t = 0;
+        while (hb.recs.size() < 256 && t < (64u << 20) && bs.next(&br, err) == 1) {
+            RecRef x{};
+            x.s = t + br.name_len() + 2, x.slen = x.qlen = br.l_seq, x.q = x.s + br.l_seq + 3;
+            t += (uint32_t)br.text_len();
+            hb.recs.push_back(x);
+        }
+    } else {
+        BlockReader r;
+        if (r.open(path, err) != 0) return 1u << 18;
+        r.next_batch(hb, 256, 64u << 20);
+    }
     if (hb.recs.empty()) return 1u << 18;
     uint64_t sum = 0;
     for (const RecRef &x : hb.recs) sum += x.slen;
@@ -784,9 +803,10 @@ struct StageClock {  // NOHUMAN_TRACE=1: where the wall time of a run goes, per 
 };
 enum { ST_READ1 = 0, ST_READ2, ST_RPUSH1, ST_RPUSH2, ST_MPOP, ST_MSLOT, ST_MGATHER, ST_MLAUNCH, ST_WPOP, ST_WSYNC, ST_WFORMAT, ST_WWRITE };
 
-// the host reader's loop: batches of an opened BlockReader into the queue, behind `skip` records that are read and dropped
-// (the reader on the GPU handed them out before it handed the file over)
-static void host_read(BlockReader &r, BoundedQueue<std::unique_ptr<HalfBatch>> *out, RunState *rs, BatchPool *pool, StageClock *clk, int which,
+// the host reader's loop: batches of an opened BlockReader (or BamReader: the same next_batch) into the queue, behind `skip`
+// records that are read and dropped (the reader on the GPU handed them out before it handed the file over)
+template <class Reader>
+static void host_read(Reader &r, BoundedQueue<std::unique_ptr<HalfBatch>> *out, RunState *rs, BatchPool *pool, StageClock *clk, int which,
                       size_t batch_frags, size_t batch_text, uint64_t skip) {
     while (skip) {
         std::unique_ptr<HalfBatch> hb = pool->get();
@@ -848,6 +868,26 @@ static void reader_main(const char *path, BoundedQueue<std::unique_ptr<HalfBatch
                         BatchPool *pool, StageClock *clk, int which, size_t batch_frags, size_t batch_text,
                         unsigned gz_threads, std::vector<int> gz_devices, bool device_reader, unsigned hybrid_threads) {
     const int gz_device = gz_devices.empty() ? -1 : gz_devices[0];
+    // BAM: inflated and chained on the host, transcoded to FASTQ text on the GPU (nh_bam.h); the batches are born there
+    if (bam_wants(path)) {
+        BamReader br;
+        std::string err;
+        if (gz_devices.empty() || br.open(path, gz_devices.data(), (int)gz_devices.size(), err, gz_threads) != 0) {
+            rs->fail(NH_EIO, gz_devices.empty() ? std::string(path) + ": BAM input needs a device" : err);
+            out->close();
+            return;
+        }
+        host_read(br, out, rs, pool, clk, which, batch_frags, batch_text, 0);
+        if (getenv("NOHUMAN_TRACE")) {
+            const BamCounts &c = br.counts();
+            fprintf(stderr, "[nohuman trace] BAM reader: %llu records, %llu kept, %llu secondary or supplementary and %llu empty skipped, %llu reverse-complemented\n",
+                    (unsigned long long)c.records, (unsigned long long)c.reads, (unsigned long long)c.skipped_secondary,
+                    (unsigned long long)c.skipped_empty, (unsigned long long)c.reverse_complemented);
+        }
+        out->close();
+        br.close();  // (waits for the batches still in the pipeline: they point into its buffers)
+        return;
+    }
     // gzip FASTQ: the whole reader on the GPU (inflate, record index; the text stays in HBM) where that pays (the caller
     // decides: device_reader) or NOHUMAN_GZ_READER says "device"; "host": the host decoders; "device-text": inflate on the
     // GPU, records parsed on the host (BlockReader)
@@ -1237,11 +1277,21 @@ static int check_taxon_args(const nh_run_args *a, const nh_run_extras *x, const 
 // batch's results a second time, call = 0 where the fragment is not a host fragment (nh_host.hip); everything that removes, keeps,
 // masks, lists or counts HOST reads then reads that array (the writer its copy), everything that reports the CALL the classifier's.
 // NULL, or no taxid: nothing of this runs.
+// BAM input is single-end: NH_EINVAL -- before any device is touched -- for a BAM in1 beside an in2, and for a BAM in2
+int check_bam_inputs(const nh_run_args *a) {
+    if (!a || !a->in2) return NH_OK;
+    if (bam_wants(a->in2)) return set_error(NH_EINVAL, "nh_run: in2 %s is a BAM file: BAM input is single-end, give it alone as in1", a->in2);
+    if (a->in1 && bam_wants(a->in1))
+        return set_error(NH_EINVAL, "nh_run: in1 %s is a BAM file and in2 is given: BAM input is single-end (split a paired BAM with `samtools fastq -1 -2`)", a->in1);
+    return NH_OK;
+}
+
 int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_stats *stats, const char *hout1 = nullptr,
                 const char *hout2 = nullptr, bool mask = false, const char *calls = nullptr, const char *ids = nullptr,
                 uint32_t minq = 0, const char *rs_path = nullptr, nh_read_stats *rs_out = nullptr, nh_taxon_out *touts = nullptr,
                 uint32_t n_touts = 0, nh_minimizer_data *md = nullptr, nh_host_filter *hf = nullptr) {
     if (!a || !a->in1 || !a->out1) return set_error(NH_EINVAL, "nh_run: in1 and out1 are required");
+    if (const int brc = check_bam_inputs(a)) return brc;
     if (engines.empty()) return set_error(NH_EINVAL, "nh_run: no engine");
     const bool split = hout1 != nullptr;
     const int K = (int)n_touts;  // per-taxon outputs: the selectors
@@ -1583,6 +1633,10 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
         // the host's inflate workers (round 6: the GPU's codec kernels and the host's cores idle in turn otherwise)
         split_readers = rs.paired && how && !strcmp(how, "split") && dev_gunzip_wants(a->in1) && dev_gunzip_wants(a->in2);
         if (split_readers) dev_reader1 = true, dev_reader2 = false;
+        if (bam_wants(a->in1)) {  // (its own reader, whatever NOHUMAN_GZ_READER says; its batches are born on the GPU as well)
+            dev_reader1 = false;
+            if (!host_text_wanted) pool1.first_reserve = 0, prefill1 = 0;
+        }
         if (getenv("NOHUMAN_TRACE"))
             fprintf(stderr, "[nohuman trace] gzip reader: %s%s%s\n", dev_reader1 ? "GPU" : "host", rs.paired ? (dev_reader2 ? " / GPU" : " / host") : "",
                     how ? " (NOHUMAN_GZ_READER)" : "");
@@ -2804,7 +2858,7 @@ int nh_fastx_scan(const char *path, uint64_t *n_records, uint64_t *n_bases, uint
 
 // Test hook (not part of the ABI in include/nohuman_engine.h, like nh_debug_sched): one reader driven alone -- no engine, no
 // classification, no outputs -- and what it handed out, record by record.  reader 0: the host's BlockReader; 1: DevFastqReader
-// on `device` (the batches' bytes are copied back from HalfBatch::dev_text; every batch is released).  next_batch() is called
+// on `device`; 2: BamReader on `device` (the batches' bytes are copied back from HalfBatch::dev_text; every batch is released).  next_batch() is called
 // until the reader reports the end of the input, hands the file over to the host reader (reported, not followed) or fails.
 //   recs     NH_DUMP_REC_WORDS words a record, in input order: hlen, idlen, slen, qlen, canonical (raw_end != 0), raw length
 //            (raw_end - h), index of its batch, digest of header / sequence / qualities (mixed like nh_fastx_scan, from the
@@ -2817,7 +2871,7 @@ enum { NH_DUMP_REC_WORDS = 9 };
 int nh_debug_reader_dump(const char *path, int reader, int device, uint64_t batch_recs, uint64_t max_text, uint64_t *recs, uint64_t rec_cap,
                          uint64_t *n_recs, uint64_t *batches, uint64_t batch_cap, uint64_t *n_batches, uint64_t *pieces, uint64_t piece_cap,
                          uint64_t *n_pieces, int *end, char *msg, uint64_t msg_cap) {
-    if (!path || !recs || !n_recs || !batches || !n_batches || !pieces || !n_pieces || !end || !msg || !msg_cap || !batch_recs || (reader != 0 && reader != 1))
+    if (!path || !recs || !n_recs || !batches || !n_batches || !pieces || !n_pieces || !end || !msg || !msg_cap || !batch_recs || reader < 0 || reader > 2)
         return nh::set_error(NH_EINVAL, "nh_debug_reader_dump: bad argument");
     auto fnv = [](const uint8_t *p, size_t len, uint64_t h) {
         for (size_t i = 0; i < len; i++) h = (h ^ p[i]) * 0x100000001b3ull;
@@ -2870,6 +2924,28 @@ int nh_debug_reader_dump(const char *path, int reader, int device, uint64_t batc
             if (!hb.recs.empty() || !hb.eof) (void)take(hb);
             if (hb.eof) break;
         }
+    } else if (reader == 2) {
+        nh::BamReader br;
+        if (!nh::bam_wants(path)) return nh::set_error(NH_EINVAL, "nh_debug_reader_dump: %s is no BAM file", path);
+        if (br.open(path, &device, 1, err, 1) != 0) return nh::set_error(NH_EIO, "%s", err.c_str());
+        for (;;) {
+            br.next_batch(hb, (size_t)batch_recs, (size_t)max_text);
+            if (!hb.error.empty()) {
+                *end = 2;
+                text = hb.error;
+                break;
+            }
+            if ((!hb.recs.empty() || !hb.eof) && !take(hb)) {
+                hb.reset();
+                br.close();
+                return nh::set_error(NH_EDEVICE, "nh_debug_reader_dump: a batch's text could not be copied back");
+            }
+            const bool eof = hb.eof;
+            hb.reset();  // (releases the batch: the reader's close() waits for every batch it handed out)
+            if (eof) break;
+        }
+        hb.reset();
+        br.close();
     } else {
         nh::DevFastqReader dr;
         const int orc = dr.open(path, device, err);
@@ -2917,6 +2993,7 @@ static int run_devices(const nh_run_args *args, nh_stats *stats, const char *hou
                        nh_read_stats *rs_out = nullptr, nh_taxon_out *touts = nullptr, uint32_t n_touts = 0, nh_minimizer_data *md = nullptr,
                        nh_host_filter *hf = nullptr) {
     if (!args || !args->db_dir) return nh::set_error(NH_EINVAL, "nh_run: db_dir is required");
+    if (const int brc = nh::check_bam_inputs(args)) return brc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return nh::set_error(NH_EDEVICE, "no HIP device available");

@@ -246,7 +246,7 @@ struct Args {
 
 static void usage(FILE *f) {
     fputs("Usage: nohuman [OPTIONS] [INPUT]...\n\n"
-          "Arguments:\n  [INPUT]...  Input file(s) to remove human reads from\n\n"
+          "Arguments:\n  [INPUT]...  Input file(s) to remove human reads from (FASTA or FASTQ, plain, gzip or bzip2; or one BAM file of single-end reads)\n\n"
           "Options:\n"
           "  -o, --out1 <OUTPUT_1>        First output file\n"
           "  -O, --out2 <OUTPUT_2>        Second output file\n"
@@ -976,6 +976,15 @@ int main(int argc, char **argv) {
     if (hsel)
         INFO("%llu host sequences removed; %llu classified sequences outside the host clades kept", (unsigned long long)hf.host_fragments,
              (unsigned long long)hf.spared_fragments);
+    if (g_verbose) {  // a BAM input: what the reader made of its records (the host side of the reader once more: nh_bam_scan)
+        nh_bam_info bi;
+        memset(&bi, 0, sizeof bi);
+        bi.struct_size = (uint32_t)sizeof bi;
+        if (nh_bam_scan(args.input[0].c_str(), args.threads, &bi) == 0)
+            DEBUG("BAM input: %llu records, %llu kept, %llu secondary or supplementary and %llu without bases skipped, %llu reverse-complemented",
+                  (unsigned long long)bi.records, (unsigned long long)bi.reads, (unsigned long long)bi.skipped_secondary,
+                  (unsigned long long)bi.skipped_empty, (unsigned long long)bi.reverse_complemented);
+    }
     INFO("Kraken2 finished. Organising output...");
 
     if (paired && args.threads / 2 > 1) {  // the reference announces both files before its two compress threads run

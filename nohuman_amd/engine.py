@@ -1,6 +1,7 @@
 """Engine: Python view of the C ABI (include/nohuman_engine.h).  numpy in, numpy out."""
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 
@@ -399,6 +400,18 @@ def dust_mask(seqs, device: int = 0):
     return [raw[int(a):int(a) + int(n)] for a, n in zip(starts, lens)], int(masked.value)
 
 
+BamInfo = collections.namedtuple("BamInfo", "records reads bases skipped_secondary skipped_empty reverse_complemented missing_qualities digest")
+
+
+def bam_scan(path, threads: int = 1) -> BamInfo:
+    """nh_bam_scan: the counts of a BAM file and the digest (nh_fastx_scan's) of the FASTQ it transcodes to -- the host side of the
+    BAM reader alone, no GPU.  EngineError -1 for a file that is no BAM, -2 for a malformed one (the message names the record)."""
+    info = _lib.nh_bam_info()
+    info.struct_size = C.sizeof(info)
+    _check(_lib.lib().nh_bam_scan(os.fsencode(path), int(threads), C.byref(info)))
+    return BamInfo(*(int(getattr(info, f)) for f in BamInfo._fields))
+
+
 def device_count() -> int:
     n = C.c_int(0)
     _check(_lib.lib().nh_device_count(C.byref(n)))
@@ -585,6 +598,16 @@ class Engine:
         kernel adds its masked bases to.  Asynchronous on `stream`."""
         _check(self._L.nh_quality_mask_device(self._h, d_text, text_len, d_seq_starts, d_seq_lens, d_qual_starts, n_seq,
                                               _minq(min_base_quality), d_out, d_masked or None, stream or None))
+
+    def bam_to_fastq_device(self, d_bam: int, bam_len: int, d_table: int, n_records: int, d_text: int, text_cap: int, text_len: int,
+                            d_error_bits: int, stream: int = 0):
+        """The BAM reader's kernel alone (nh_bam_to_fastq_device): the records of d_bam (bam_len bytes, 4-byte aligned) that
+        d_table names -- two uint64 a record: where its block_size field lies in d_bam, where its '@' lies in d_text, ascending --
+        are written as "@name\\nSEQ\\n+\\nQUAL\\n" into d_text[0, text_len) (text_cap bytes, 4-byte aligned).  d_error_bits: one
+        int32 the caller zeroed; bit 1: a record outside d_bam, bit 2: a record's text outside the text -- such a record is not
+        written, the others are.  Asynchronous on `stream`."""
+        _check(self._L.nh_bam_to_fastq_device(self._h, d_bam or None, int(bam_len), d_table or None, int(n_records), d_text or None,
+                                              int(text_cap), int(text_len), d_error_bits or None, stream or None))
 
     def read_stats_device(self, d_text: int, text_len: int, d_seq_starts: int, d_seq_lens: int, d_qual_starts: int,
                           d_results: int, n_frag: int, d_acc: int, paired: bool = False, max_workgroups: int = 0, stream: int = 0):
