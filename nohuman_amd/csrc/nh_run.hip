@@ -1088,136 +1088,198 @@ static int ensure_device_external(Engine *e) {
     return NH_OK;
 }
 
-// nh_run_split's own arguments, checked before any device is touched
-static int check_split_args(const nh_run_args *a, const char *h1, const char *h2, const char *who = "nh_run_split") {
-    if (!a) return set_error(NH_EINVAL, "%s: null arguments", who);
+// ---- the request of a whole run ------------------------------------------------------------------
+// What an nh_run* entry was asked for, in one place: make_request fills it from the entry's arguments, check_request refuses a
+// bad one before any device is touched, run_devices / run_engine / run_engines carry it out.
+struct RunRequest {
+    // the entry: nh_run_split and nh_run_mask take the human outputs as bare paths and always check them, nh_run_ex wants its
+    // extras; RUN is nh_run and every entry from nh_run_minq upwards without extras (with extras they ask what nh_run_ex asks: EX)
+    enum Form { RUN, SPLIT, MASK, EX } form = RUN;
+    const char *who = "nh_run";  // the entry's name, for messages
+    const nh_run_args *a = nullptr;
+    const nh_run_extras *x = nullptr;  // the caller's extras as given: what is wrong with the struct itself is said in check_request's order
+    // hout1 set: a split run (nh_run_split) -- a->keep_human is 0, hout1 / hout2 receive the classified records
+    const char *hout1 = nullptr, *hout2 = nullptr;
+    // a masked run (nh_run_mask) -- a->keep_human is 0, out1 / out2 receive every record, a classified one's bases as 'N'
+    bool mask = false;
+    // set (nh_run_ex): the calls table / the human read ids, built in HBM beside whatever else the run writes
+    const char *calls = nullptr, *ids = nullptr;
+    // > 0 (nh_run_minq): kraken2's --minimum-base-quality -- the classifier reads a copy of each batch's sequences in which the
+    // bases of a FASTQ record with a quality below minq are 'N' (k_qmask, in front of it on the slot's stream); every output is made
+    // from the batch's text as before, so the records written keep their bases.  0: nothing of this runs.
+    uint32_t minq = 0;
+    // either set (nh_run_rstats): read statistics -- k_rstats behind the classifier on the slot's stream adds every sequence of the
+    // batch to the device's four accumulators (nh_rstats.hip), fetched once, at the end; the writer keeps the lengths by class for
+    // median and N50.  Both NULL: nothing of this runs.
+    const char *rs_path = nullptr;
+    nh_read_stats *rs_out = nullptr;
+    // n_touts > 0 (nh_run_taxa): per-taxon outputs -- k_tout_* behind the classifier on the slot's stream sort the classified
+    // records of the batch into the selectors' bins (nh_split.hip), a span a bin and mate goes to the selector's file.  0: nothing runs.
+    nh_taxon_out *touts = nullptr;
+    uint32_t n_touts = 0;
+    // asking for something (nh_run_mdata): minimizer data -- k_mdata_mark behind the classifier on the slot's stream marks the cell
+    // of every hit group in the device's bitmap and counts the group for its taxon (nh_mdata.hip), on the text the classifier read;
+    // k_mdata_count reads the bitmap once, at the end (several devices: the union of their bitmaps -- a minimizer hit on two devices
+    // is one).  NULL, or nothing asked for: nothing of this runs.
+    nh_minimizer_data *md = nullptr;
+    // set (nh_run_host with a taxid): the host selection -- k_host_filter behind the classifier on the slot's stream writes the
+    // batch's results a second time, call = 0 where the fragment is not a host fragment (nh_host.hip); everything that removes, keeps,
+    // masks, lists or counts HOST reads then reads that array (the writer its copy), everything that reports the CALL the
+    // classifier's.  NULL: nothing of this runs.
+    nh_host_filter *hf = nullptr;
+};
+
+// The request of an entry: its args, its extras (NULL where it has none, or was given none) or the bare human paths of
+// nh_run_split / nh_run_mask, and as much of nh_run_host's tail as the entry has
+RunRequest make_request(RunRequest::Form form, const nh_run_args *a, const nh_run_extras *x, const char *h1 = nullptr, const char *h2 = nullptr,
+                        uint32_t minq = 0, const char *rs_path = nullptr, nh_read_stats *rs_out = nullptr, nh_taxon_out *touts = nullptr,
+                        uint32_t n_touts = 0, nh_minimizer_data *md = nullptr, nh_host_filter *hf = nullptr) {
+    static const char *const names[] = {"nh_run", "nh_run_split", "nh_run_mask", "nh_run_ex"};
+    RunRequest r;
+    r.form = form == RunRequest::RUN && x ? RunRequest::EX : form;
+    r.who = names[r.form];
+    r.a = a, r.x = x;
+    r.hout1 = h1, r.hout2 = h2, r.mask = form == RunRequest::MASK;
+    if (x && x->struct_size >= sizeof(nh_run_extras))  // (a smaller struct: check_request refuses it, nothing else of it is read)
+        r.hout1 = x->human_out1, r.hout2 = x->human_out2, r.mask = x->mask != 0, r.calls = x->calls, r.ids = x->human_ids;
+    r.minq = minq, r.rs_path = rs_path, r.rs_out = rs_out, r.touts = touts, r.n_touts = n_touts, r.md = md;
+    r.hf = host_filter_given(hf) ? hf : nullptr;  // (no taxid listed: the run of nh_run_mdata, and the struct is not looked at again)
+    return r;
+}
+
+// ---- the files a request names ----------------------------------------------------------------------
+// `candidate` names the file `other` names: the same string, or candidate is an existing regular file and other has its device and
+// inode.  (Which of the two is tested for being regular cannot be seen: two names of one inode have one mode.)
+static bool same_file(const char *candidate, const char *other) {
+    if (!strcmp(candidate, other)) return true;
+    struct stat sc, so;
+    return stat(candidate, &sc) == 0 && S_ISREG(sc.st_mode) && stat(other, &so) == 0 && so.st_dev == sc.st_dev && so.st_ino == sc.st_ino;
+}
+
+// One file of a request.  The kinds are in the order of the checks: a feature's files are checked against the files of the kinds
+// before it (and the read lists and the selectors' files among themselves).
+enum FileKind { F_INPUT, F_OUTPUT, F_HUMAN, F_LIST, F_RSTATS, F_TAXON, F_MDATA };
+struct RunFile {
+    const char *path;   // never NULL; may be empty
+    FileKind kind;
+    const char *who;    // the words of a message about it: "<who>: <words> <path> is the input ..."
+    std::string words;
+};
+
+// The files r names, inputs first, of the kinds up to `last` -- what is behind it may not have been checked yet (r.a is not NULL)
+static std::vector<RunFile> request_files(const RunRequest &r, FileKind last) {
+    std::vector<RunFile> f;
+    auto add = [&](const char *p, FileKind k, const char *who, std::string words) {
+        if (p && k <= last) f.push_back({p, k, who, std::move(words)});
+    };
+    const nh_run_args *a = r.a;
+    for (const char *p : {a->in1, a->in2}) add(p, F_INPUT, "nh_run", "input");
+    for (const char *p : {a->out1, a->out2, a->kraken_output, a->report}) add(p, F_OUTPUT, r.mask ? "nh_run_mask" : "nh_run", "output");
+    for (const char *p : {r.hout1, r.hout2}) add(p, F_HUMAN, r.mask ? "nh_run_mask" : "nh_run_split", "human output");
+    add(r.calls, F_LIST, "nh_run_ex", "calls");
+    add(r.ids, F_LIST, "nh_run_ex", "human_ids");
+    add(r.rs_path, F_RSTATS, "nh_run_rstats", "the read statistics table");
+    for (uint32_t i = 0; last >= F_TAXON && r.touts && i < r.n_touts; i++)
+        for (int m = 0; m < 2; m++) add(m ? r.touts[i].out2 : r.touts[i].out1, F_TAXON, "nh_run_taxa", "outs[" + std::to_string(i) + "].out" + std::to_string(m + 1));
+    if (last >= F_MDATA && r.md) add(r.md->table, F_MDATA, "nh_run_mdata", "the minimizer table");
+    return f;
+}
+
+// files[c] against the `upto` files in front: NH_EINVAL, with c's words, for the first that it also names.  (An output given as
+// an empty path is not written: it collides with nothing.  An input is compared as it is.)
+static int check_collision(const std::vector<RunFile> &files, size_t c, size_t upto) {
+    const RunFile &f = files[c];
+    for (size_t i = 0; i < upto; i++) {
+        const RunFile &o = files[i];
+        if ((o.kind != F_INPUT && !o.path[0]) || !same_file(f.path, o.path)) continue;
+        if (o.kind == F_INPUT) return set_error(NH_EINVAL, "%s: %s %s is the input %s", f.who, f.words.c_str(), f.path, o.path);
+        if (o.kind == F_LIST && f.kind == F_LIST) return set_error(NH_EINVAL, "nh_run_ex: calls and human_ids are the same file %s", f.path);
+        if (o.kind == F_TAXON && f.kind == F_TAXON) return set_error(NH_EINVAL, "%s: %s %s is also %s", f.who, f.words.c_str(), f.path, o.words.c_str());
+        return set_error(NH_EINVAL, "%s: %s %s is also the output %s", f.who, f.words.c_str(), f.path, o.path);
+    }
+    return NH_OK;
+}
+
+// every file of `kind` against the files of the kinds before it; the read lists and the selectors' files also against the earlier
+// ones of their own kind (human_out1 against human_out2 is check_split_args' own test, by name only)
+static int check_files(const RunRequest &r, FileKind kind) {
+    const std::vector<RunFile> files = request_files(r, kind);
+    size_t first = 0;
+    while (first < files.size() && files[first].kind != kind) first++;
+    for (size_t c = first; c < files.size(); c++)
+        if (const int rc = check_collision(files, c, kind == F_LIST || kind == F_TAXON ? c : first)) return rc;
+    return NH_OK;
+}
+
+// ---- check_request: what is wrong with a request, said before any device is touched -----------------
+// the human outputs of a split run, and of a masked run that has them
+static int check_split_args(const RunRequest &r) {
+    const nh_run_args *a = r.a;
+    const char *h1 = r.hout1, *h2 = r.hout2, *who = r.mask ? "nh_run_mask" : "nh_run_split";
     if (!h1 || !h1[0]) return set_error(NH_EINVAL, "%s: human_out1 is required", who);
     if (a->keep_human != 0) return set_error(NH_EINVAL, "%s: keep_human must be 0 (the human reads go to human_out1 / human_out2)", who);
     if (a->in2 && !h2) return set_error(NH_EINVAL, "%s: paired input needs human_out2", who);
     if (!a->in2 && h2) return set_error(NH_EINVAL, "%s: human_out2 is given without in2", who);
     if (h2 && !strcmp(h1, h2)) return set_error(NH_EINVAL, "%s: human_out1 and human_out2 are the same file", who);
-    for (const char *h : {h1, h2}) {
-        if (!h) continue;
-        struct stat sh;
-        const bool hs = stat(h, &sh) == 0 && S_ISREG(sh.st_mode);
-        for (const char *p : {a->in1, a->in2}) {
-            struct stat si;
-            if (p && (!strcmp(p, h) || (hs && stat(p, &si) == 0 && si.st_dev == sh.st_dev && si.st_ino == sh.st_ino)))
-                return set_error(NH_EINVAL, "%s: human output %s is the input %s", who, h, p);
-        }
-        for (const char *o : {a->out1, a->out2, a->kraken_output, a->report}) {
-            struct stat so;
-            if (o && o[0] && (!strcmp(o, h) || (hs && stat(o, &so) == 0 && so.st_dev == sh.st_dev && so.st_ino == sh.st_ino)))
-                return set_error(NH_EINVAL, "%s: human output %s is also the output %s", who, h, o);
-        }
-    }
-    return NH_OK;
+    return check_files(r, F_HUMAN);
 }
 
-// nh_run_mask's own arguments, checked before any device is touched
-static int check_mask_args(const nh_run_args *a, const char *h1, const char *h2) {
-    if (!a) return set_error(NH_EINVAL, "nh_run_mask: null arguments");
-    if (a->keep_human != 0) return set_error(NH_EINVAL, "nh_run_mask: keep_human must be 0 (the human reads are masked, not kept)");
-    if (h1 || h2) {
-        const int rc = check_split_args(a, h1, h2, "nh_run_mask");
+// a masked run: out1 / out2 receive every record, so none of the run's own outputs may be an input
+static int check_mask_args(const RunRequest &r) {
+    if (r.a->keep_human != 0) return set_error(NH_EINVAL, "nh_run_mask: keep_human must be 0 (the human reads are masked, not kept)");
+    if (r.hout1 || r.hout2) {
+        const int rc = check_split_args(r);
         if (rc) return rc;
     }
-    for (const char *o : {a->out1, a->out2, a->kraken_output, a->report}) {
-        if (!o || !o[0]) continue;
-        struct stat so;
-        const bool oreg = stat(o, &so) == 0 && S_ISREG(so.st_mode);
-        for (const char *p : {a->in1, a->in2}) {
-            struct stat si;
-            if (p && (!strcmp(p, o) || (oreg && stat(p, &si) == 0 && si.st_dev == so.st_dev && si.st_ino == so.st_ino)))
-                return set_error(NH_EINVAL, "nh_run_mask: output %s is the input %s", o, p);
-        }
+    const std::vector<RunFile> files = request_files(r, F_OUTPUT);
+    size_t inputs = 0;
+    while (inputs < files.size() && files[inputs].kind == F_INPUT) inputs++;
+    for (size_t c = inputs; c < files.size(); c++)
+        if (files[c].path[0])
+            if (const int rc = check_collision(files, c, inputs)) return rc;
+    return NH_OK;
+}
+
+// the read lists (the calls table, the human ids): a list names no input and no other output of the run
+static int check_list_args(const RunRequest &r) {
+    const std::vector<RunFile> files = request_files(r, F_LIST);
+    for (size_t c = 0; c < files.size(); c++) {
+        if (files[c].kind != F_LIST) continue;
+        if (!files[c].path[0]) return set_error(NH_EINVAL, "nh_run_ex: %s is an empty path", files[c].words.c_str());
+        if (const int rc = check_collision(files, c, c)) return rc;
     }
     return NH_OK;
 }
 
-// nh_run_ex's read lists (the calls table, the human ids), checked before any device is touched: a list names no input and no
-// other output of the run (the same path, or the same device and inode)
-static int check_list_args(const nh_run_args *a, const char *h1, const char *h2, const char *calls, const char *ids) {
-    if (!a) return set_error(NH_EINVAL, "nh_run_ex: null arguments");
-    const char *const what[2] = {"calls", "human_ids"};
-    const char *const list[2] = {calls, ids};
-    for (int o = 0; o < 2; o++) {
-        const char *l = list[o];
-        if (!l) continue;
-        if (!l[0]) return set_error(NH_EINVAL, "nh_run_ex: %s is an empty path", what[o]);
-        struct stat sl;
-        const bool ls = stat(l, &sl) == 0 && S_ISREG(sl.st_mode);
-        auto same = [&](const char *p) {
-            struct stat sp;
-            return p && p[0] && (!strcmp(p, l) || (ls && stat(p, &sp) == 0 && sp.st_dev == sl.st_dev && sp.st_ino == sl.st_ino));
-        };
-        for (const char *p : {a->in1, a->in2})
-            if (same(p)) return set_error(NH_EINVAL, "nh_run_ex: %s %s is the input %s", what[o], l, p);
-        for (const char *p : {a->out1, a->out2, a->kraken_output, a->report, h1, h2})
-            if (same(p)) return set_error(NH_EINVAL, "nh_run_ex: %s %s is also the output %s", what[o], l, p);
-        if (o == 1 && same(calls)) return set_error(NH_EINVAL, "nh_run_ex: calls and human_ids are the same file %s", l);
+// what nh_run_ex checks, and nh_run_split / nh_run_mask for the fields they share with it: the struct, the human outputs or the
+// mask, the read lists
+static int check_extras(const RunRequest &r) {
+    if (!r.a) return set_error(NH_EINVAL, "%s: null arguments", r.who);
+    if (r.form == RunRequest::EX) {
+        if (!r.x) return set_error(NH_EINVAL, "nh_run_ex: null extras");
+        if (r.x->struct_size < sizeof(nh_run_extras))
+            return set_error(NH_EINVAL, "nh_run_ex: struct_size %u is smaller than nh_run_extras (%zu bytes)", r.x->struct_size, sizeof(nh_run_extras));
     }
-    return NH_OK;
+    int rc = NH_OK;
+    if (r.mask) rc = check_mask_args(r);
+    else if (r.hout1 || r.hout2 || r.form == RunRequest::SPLIT) rc = check_split_args(r);
+    if (rc) return rc;
+    return check_list_args(r);
 }
 
-// The file of a run that `path` names -- the same path, or the same device and inode: an input (*input set) or an output, among them
-// the read statistics table and the per-taxon files where given.  NULL: none.
-static const char *run_file_named(const nh_run_args *a, const nh_run_extras *x, const char *rs_path, const nh_taxon_out *outs, uint32_t n_outs,
-                                  const char *path, bool *input) {
-    struct stat sl;
-    const bool ls = stat(path, &sl) == 0 && S_ISREG(sl.st_mode);
-    auto same = [&](const char *p) {
-        struct stat sp;
-        return p && p[0] && (!strcmp(p, path) || (ls && stat(p, &sp) == 0 && sp.st_dev == sl.st_dev && sp.st_ino == sl.st_ino));
-    };
-    *input = true;
-    for (const char *p : {a->in1, a->in2})
-        if (same(p)) return p;
-    *input = false;
-    for (const char *p : {a->out1, a->out2, a->kraken_output, a->report, x ? x->human_out1 : nullptr, x ? x->human_out2 : nullptr,
-                          x ? x->calls : nullptr, x ? x->human_ids : nullptr, rs_path})
-        if (same(p)) return p;
-    for (uint32_t i = 0; outs && i < n_outs; i++)
-        for (const char *p : {outs[i].out1, outs[i].out2})
-            if (same(p)) return p;
-    return nullptr;
+// nh_run_rstats' table: it names no input and no other output of the run
+static int check_rstats_args(const RunRequest &r) {
+    if (!r.rs_path) return NH_OK;
+    if (!r.a) return set_error(NH_EINVAL, "nh_run_rstats: null arguments");
+    if (!r.rs_path[0]) return set_error(NH_EINVAL, "nh_run_rstats: read_stats_path is an empty path");
+    return check_files(r, F_RSTATS);
 }
 
-// nh_run_rstats' table, checked before any device is touched: it names no input and no other output of the run
-static int check_rstats_args(const nh_run_args *a, const nh_run_extras *x, const char *path) {
-    if (!path) return NH_OK;
-    if (!a) return set_error(NH_EINVAL, "nh_run_rstats: null arguments");
-    if (!path[0]) return set_error(NH_EINVAL, "nh_run_rstats: read_stats_path is an empty path");
-    bool input = false;
-    if (const char *p = run_file_named(a, x, nullptr, nullptr, 0, path, &input))
-        return set_error(NH_EINVAL, input ? "nh_run_rstats: the read statistics table %s is the input %s" : "nh_run_rstats: the read statistics table %s is also the output %s",
-                         path, p);
-    return NH_OK;
-}
-
-// nh_run_mdata's own arguments, checked before any device is touched: the struct, and a table that names no input and no other
-// output of the run
-static int check_mdata_args(const nh_run_args *a, const nh_run_extras *x, const char *rs_path, const nh_taxon_out *outs, uint32_t n_outs,
-                            const nh_minimizer_data *md) {
-    if (!md) return NH_OK;
-    if (md->struct_size < sizeof(nh_minimizer_data))
-        return set_error(NH_EINVAL, "nh_run_mdata: struct_size %u is smaller than nh_minimizer_data (%zu bytes)", md->struct_size, sizeof(nh_minimizer_data));
-    if (!a) return set_error(NH_EINVAL, "nh_run_mdata: null arguments");
-    if (md->in_report && !(a->report && a->report[0])) return set_error(NH_EINVAL, "nh_run_mdata: in_report is set without a report (args->report)");
-    if (md->taxa && md->taxa_cap == 0) return set_error(NH_EINVAL, "nh_run_mdata: taxa is given with taxa_cap 0");
-    if (md->table) {
-        if (!md->table[0]) return set_error(NH_EINVAL, "nh_run_mdata: table is an empty path");
-        bool input = false;
-        if (const char *p = run_file_named(a, x, rs_path, outs, n_outs, md->table, &input))
-            return set_error(NH_EINVAL, input ? "nh_run_mdata: the minimizer table %s is the input %s" : "nh_run_mdata: the minimizer table %s is also the output %s",
-                             md->table, p);
-    }
-    return NH_OK;
-}
-
-// nh_run_taxa's selectors, checked before any device is touched: their number, their taxids, their files -- a per-taxon file
-// names no input and no other output of the run (the same path, or the same device and inode)
-static int check_taxon_args(const nh_run_args *a, const nh_run_extras *x, const char *rs_path, const nh_taxon_out *outs, uint32_t n) {
+// nh_run_taxa's selectors: their number, their taxids, their files -- a per-taxon file names no input and no other output of the run
+static int check_taxon_args(const RunRequest &r) {
+    const nh_run_args *a = r.a;
+    const nh_taxon_out *outs = r.touts;
+    const uint32_t n = r.n_touts;
     if (n == 0) return NH_OK;
     if (!a) return set_error(NH_EINVAL, "nh_run_taxa: null arguments");
     if (n > NH_MAX_TAXON_OUTS) return set_error(NH_EINVAL, "nh_run_taxa: n_outs %u is above NH_MAX_TAXON_OUTS (%d)", n, NH_MAX_TAXON_OUTS);
@@ -1235,48 +1297,34 @@ static int check_taxon_args(const nh_run_args *a, const nh_run_extras *x, const 
                 return set_error(NH_EINVAL, "nh_run_taxa: outs[%u].taxid %llu is given twice", i, (unsigned long long)t.taxid);
             }
     }
-    for (uint32_t i = 0; i < n; i++)
-        for (int m = 0; m < 2; m++) {
-            const char *l = m ? outs[i].out2 : outs[i].out1;
-            if (!l) continue;
-            struct stat sl;
-            const bool ls = stat(l, &sl) == 0 && S_ISREG(sl.st_mode);
-            auto same = [&](const char *p) {
-                struct stat sp;
-                return p && p[0] && (!strcmp(p, l) || (ls && stat(p, &sp) == 0 && sp.st_dev == sl.st_dev && sp.st_ino == sl.st_ino));
-            };
-            for (const char *p : {a->in1, a->in2})
-                if (same(p)) return set_error(NH_EINVAL, "nh_run_taxa: outs[%u].out%d %s is the input %s", i, m + 1, l, p);
-            for (const char *p : {a->out1, a->out2, a->kraken_output, a->report, x ? x->human_out1 : nullptr, x ? x->human_out2 : nullptr,
-                                  x ? x->calls : nullptr, x ? x->human_ids : nullptr, rs_path})
-                if (same(p)) return set_error(NH_EINVAL, "nh_run_taxa: outs[%u].out%d %s is also the output %s", i, m + 1, l, p);
-            for (uint32_t j = 0; j <= i; j++)
-                for (int mj = 0; mj < (j < i ? 2 : m); mj++)
-                    if (same(mj ? outs[j].out2 : outs[j].out1))
-                        return set_error(NH_EINVAL, "nh_run_taxa: outs[%u].out%d %s is also outs[%u].out%d", i, m + 1, l, j, mj + 1);
-        }
-    return NH_OK;
+    return check_files(r, F_TAXON);
 }
 
-// hout1 set: a split run (nh_run_split) -- a->keep_human is 0, hout1 / hout2 receive the classified records
-// mask: a masked run (nh_run_mask) -- a->keep_human is 0, out1 / out2 receive every record, a classified one's bases as 'N'
-// calls / ids set (nh_run_ex): the calls table / the human read ids, built in HBM beside whatever else the run writes
-// minq > 0 (nh_run_minq): kraken2's --minimum-base-quality -- the classifier reads a copy of each batch's sequences in which the
-// bases of a FASTQ record with a quality below minq are 'N' (k_qmask, in front of it on the slot's stream); every output is made
-// from the batch's text as before, so the records written keep their bases.  0: nothing of this runs.
-// touts / n_touts (nh_run_taxa): per-taxon outputs -- k_tout_* behind the classifier on the slot's stream sort the classified
-// records of the batch into the selectors' bins (nh_split.hip), a span a bin and mate goes to the selector's file.  0: nothing runs.
-// rs_path / rs_out set (nh_run_rstats): read statistics -- k_rstats behind the classifier on the slot's stream adds every sequence
-// of the batch to the device's four accumulators (nh_rstats.hip), fetched once, at the end; the writer keeps the lengths by class
-// for median and N50.  Both NULL: nothing of this runs.
-// md asking for something (nh_run_mdata): minimizer data -- k_mdata_mark behind the classifier on the slot's stream marks the cell of
-// every hit group in the device's bitmap and counts the group for its taxon (nh_mdata.hip), on the text the classifier read;
-// k_mdata_count reads the bitmap once, at the end (several devices: the union of their bitmaps -- a minimizer hit on two devices is
-// one).  NULL, or nothing asked for: nothing of this runs.
-// hf selecting something (nh_run_host): the host selection -- k_host_filter behind the classifier on the slot's stream writes the
-// batch's results a second time, call = 0 where the fragment is not a host fragment (nh_host.hip); everything that removes, keeps,
-// masks, lists or counts HOST reads then reads that array (the writer its copy), everything that reports the CALL the classifier's.
-// NULL, or no taxid: nothing of this runs.
+// nh_run_mdata's own arguments: the struct, and a table that names no input and no other output of the run
+static int check_mdata_args(const RunRequest &r) {
+    const nh_minimizer_data *md = r.md;
+    if (!md) return NH_OK;
+    if (md->struct_size < sizeof(nh_minimizer_data))
+        return set_error(NH_EINVAL, "nh_run_mdata: struct_size %u is smaller than nh_minimizer_data (%zu bytes)", md->struct_size, sizeof(nh_minimizer_data));
+    if (!r.a) return set_error(NH_EINVAL, "nh_run_mdata: null arguments");
+    if (md->in_report && !(r.a->report && r.a->report[0])) return set_error(NH_EINVAL, "nh_run_mdata: in_report is set without a report (args->report)");
+    if (md->taxa && md->taxa_cap == 0) return set_error(NH_EINVAL, "nh_run_mdata: taxa is given with taxa_cap 0");
+    if (md->table && !md->table[0]) return set_error(NH_EINVAL, "nh_run_mdata: table is an empty path");
+    return check_files(r, F_MDATA);
+}
+
+// Every entry's checks, in one order: the host selection's own, the minimum base quality (the highest printable quality is '~',
+// Phred 93), the extras (the mask or the human outputs, then the read lists), the read statistics' table, the selectors, the
+// minimizer data.  What an entry cannot ask for is not set in its request and checks nothing.
+int check_request(const RunRequest &r) {
+    int rc = check_host_filter(r.hf);
+    if (!rc && r.minq > 93) rc = set_error(NH_EINVAL, "minimum base quality %u is not in 0..93 (Phred+33)", r.minq);
+    if (!rc && r.form != RunRequest::RUN) rc = check_extras(r);
+    if (!rc) rc = check_rstats_args(r);
+    if (!rc) rc = check_taxon_args(r);
+    if (!rc) rc = check_mdata_args(r);
+    return rc;
+}
 // BAM input is single-end: NH_EINVAL -- before any device is touched -- for a BAM in1 beside an in2, and for a BAM in2
 int check_bam_inputs(const nh_run_args *a) {
     if (!a || !a->in2) return NH_OK;
@@ -1286,81 +1334,313 @@ int check_bam_inputs(const nh_run_args *a) {
     return NH_OK;
 }
 
-int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_stats *stats, const char *hout1 = nullptr,
-                const char *hout2 = nullptr, bool mask = false, const char *calls = nullptr, const char *ids = nullptr,
-                uint32_t minq = 0, const char *rs_path = nullptr, nh_read_stats *rs_out = nullptr, nh_taxon_out *touts = nullptr,
-                uint32_t n_touts = 0, nh_minimizer_data *md = nullptr, nh_host_filter *hf = nullptr) {
+// ---- the parts of a run that happen once, before the first batch or after the last ------------------
+// The output files of a run
+struct RunFiles {
+    OutFile o1, o2, ok;  // the kept records of mate 1 / mate 2, the per-read kraken output
+    OutFile h1, h2;      // the classified records of a split run
+    OutFile oc, oi;      // the read lists (calls, human ids): plain text whatever the codec of the records
+    OutFile tx[2][NH_MAX_TAXON_OUTS];  // the selectors' files, [mate][selector]
+};
+
+// Creates them.  gzip output is encoded on the GPU (nh_deflate.hip); with two devices each mate file has its own: mate 1's files on
+// the first device, mate 2's on the second.  Mate 2's file and the human outputs are opened side by side with out1: a GPU encoder
+// takes 70 ms to set up -- page-locked buffers, a trial of its prices.
+static int open_run_files(RunFiles &f, const RunRequest &r, const std::vector<Engine *> &engines, bool paired, bool want_k) {
+    const nh_run_args *a = r.a;
+    const int dev1 = engines[0]->device, dev2 = engines[engines.size() > 1 ? 1 : 0]->device;
+    int rc, rc2 = NH_OK, rch1 = NH_OK, rch2 = NH_OK;
+    std::string err2, errh1, errh2;
+    std::thread t2, th1, th2;
+    if (paired)
+        t2 = std::thread([&] {
+            rc2 = f.o2.open(a->out2, a->out_codec, a->codec_threads, dev2);
+            if (rc2) err2 = g_last_error;
+        });
+    if (r.hout1) {
+        th1 = std::thread([&] {
+            rch1 = f.h1.open(r.hout1, a->out_codec, a->codec_threads, dev1);
+            if (rch1) errh1 = g_last_error;
+        });
+        if (paired)
+            th2 = std::thread([&] {
+                rch2 = f.h2.open(r.hout2, a->out_codec, a->codec_threads, dev2);
+                if (rch2) errh2 = g_last_error;
+            });
+    }
+    rc = f.o1.open(a->out1, a->out_codec, a->codec_threads, dev1);
+    if (t2.joinable()) t2.join();
+    if (th1.joinable()) th1.join();
+    if (th2.joinable()) th2.join();
+    if (rc) return rc;
+    if (rc2) return set_error(rc2, "%s", err2.c_str());
+    if (rch1) return set_error(rch1, "%s", errh1.c_str());
+    if (rch2) return set_error(rch2, "%s", errh2.c_str());
+    for (uint32_t k = 0; k < r.n_touts; k++)
+        for (int m = 0; m < (paired ? 2 : 1); m++)
+            if ((rc = f.tx[m][k].open(m ? r.touts[k].out2 : r.touts[k].out1, a->out_codec, a->codec_threads, m ? dev2 : dev1))) return rc;
+    if (want_k && (rc = f.ok.open(a->kraken_output))) return rc;
+    if (r.calls && (rc = f.oc.open(r.calls))) return rc;
+    if (r.ids && (rc = f.oi.open(r.ids))) return rc;
+    return NH_OK;
+}
+
+// per-taxon outputs: the bin of every node of the taxonomy -- its deepest selected ancestor-or-self, else `other`'s, else none
+static int selector_bins(const Engine *e0, const RunRequest &r, std::vector<uint8_t> &bin_of) {
+    const size_t nn = e0->external.size();
+    bin_of.assign(std::max<size_t>(nn, 1), 0xFF);
+    std::vector<int> own(nn, -1);
+    int other = -1;
+    for (int k = 0; k < (int)r.n_touts; k++) {
+        if (r.touts[k].taxid == NH_TAXON_OTHER) {
+            other = k;
+            continue;
+        }
+        size_t at = 0;
+        for (size_t i = 1; i < nn && !at; i++)
+            if (e0->external[i] == r.touts[k].taxid) at = i;
+        if (!at) return set_error(NH_EINVAL, "nh_run_taxa: taxid %llu is not in the database's taxonomy", (unsigned long long)r.touts[k].taxid);
+        own[at] = k;
+    }
+    for (size_t i = 1; i < nn; i++) {  // (parents have smaller ids than their children: nh_open checked)
+        const uint32_t p = e0->parent[i];
+        bin_of[i] = own[i] >= 0 ? (uint8_t)own[i] : (i > 1 && p >= 1 && p < i) ? bin_of[p] : other >= 0 ? (uint8_t)other : (uint8_t)0xFF;
+    }
+    return NH_OK;
+}
+
+// What one device holds for the whole run, given back when the run's scope ends
+struct RunBuffers {
+    int device = -1;
+    uint64_t *counters = nullptr;  // the counters the classify kernels of this run add to (RunState::d_run_counters points here)
+    uint8_t *bin_of = nullptr;     // per-taxon outputs: the selectors' bins
+    // host selection: host_of, and the pair of counters {host, spared} k_host_filter adds to
+    uint8_t *host_of = nullptr;
+    unsigned long long *hcnt = nullptr;
+    unsigned long long *racc = nullptr;  // read statistics: one block of four accumulators, zeroed with min_len all-ones
+    // minimizer data: one zeroed bitmap (a bit a cell) and one array of hit groups per node
+    uint32_t *marks = nullptr;
+    unsigned long long *groups = nullptr;
+    RunBuffers() = default;
+    RunBuffers(const RunBuffers &) = delete;
+    RunBuffers &operator=(const RunBuffers &) = delete;
+    ~RunBuffers() {
+        if (!counters && !bin_of && !host_of && !hcnt && !racc && !marks && !groups) return;
+        (void)dev_set(device);
+        for (void *p : {(void *)host_of, (void *)hcnt, (void *)marks, (void *)groups, (void *)counters, (void *)racc, (void *)bin_of})
+            if (p) (void)hipFree(p);
+    }
+};
+
+// (hipMemcpy / hipMemset block: the tables and the zeroes are in place before the slots' streams, which do not wait for the legacy
+// stream, carry the first batch)
+static int alloc_run_buffers(RunBuffers &b, const Engine *e, const std::vector<uint8_t> &bin_of, const std::vector<uint8_t> &host_of, bool rst,
+                             size_t md_mark_bytes, size_t md_nodes, bool mdt) {
+    b.device = e->device;
+    const size_t nb = (CNT_N + 12) * sizeof(uint64_t);  // (+12: the words of the instrumented kernel variant)
+    if (dev_set(e->device) != hipSuccess || dev_malloc((void **)&b.counters, nb) != hipSuccess || hipMemset(b.counters, 0, nb) != hipSuccess)
+        return set_error(NH_EDEVICE, "cannot allocate the run's counters on device %d", e->device);
+    if (!bin_of.empty() && (dev_malloc((void **)&b.bin_of, bin_of.size()) != hipSuccess ||
+                            hipMemcpy(b.bin_of, bin_of.data(), bin_of.size(), hipMemcpyHostToDevice) != hipSuccess))
+        return set_error(NH_EDEVICE, "cannot copy the selectors' bins to device %d", e->device);
+    if (!host_of.empty() && (dev_malloc((void **)&b.host_of, host_of.size()) != hipSuccess || dev_malloc((void **)&b.hcnt, 16) != hipSuccess ||
+                             hipMemcpy(b.host_of, host_of.data(), host_of.size(), hipMemcpyHostToDevice) != hipSuccess ||
+                             hipMemset(b.hcnt, 0, 16) != hipSuccess || hipDeviceSynchronize() != hipSuccess))
+        return set_error(NH_EDEVICE, "cannot copy the host selection's table to device %d", e->device);
+    if (rst) {
+        nh_read_class init[4];
+        memset(init, 0, sizeof init);
+        for (nh_read_class &c : init) c.min_len = ~0ull;
+        if (dev_malloc((void **)&b.racc, sizeof init) != hipSuccess || hipMemcpy(b.racc, init, sizeof init, hipMemcpyHostToDevice) != hipSuccess)
+            return set_error(NH_EDEVICE, "cannot allocate the read statistics' accumulators on device %d", e->device);
+    }
+    if (mdt) {
+        if (dev_malloc((void **)&b.marks, std::max<size_t>(md_mark_bytes, 4)) != hipSuccess ||
+            dev_malloc((void **)&b.groups, std::max<size_t>(md_nodes, 1) * 8) != hipSuccess)
+            return set_error(NH_EOOM, "minimizer data: cannot allocate the bitmap of %zu bytes and %zu counters on device %d", md_mark_bytes, md_nodes,
+                             e->device);
+        if (hipMemset(b.marks, 0, std::max<size_t>(md_mark_bytes, 4)) != hipSuccess ||
+            hipMemset(b.groups, 0, std::max<size_t>(md_nodes, 1) * 8) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+            return set_error(NH_EDEVICE, "minimizer data: cannot clear the bitmap on device %d", e->device);
+    }
+    return NH_OK;
+}
+
+// ---- after the writer threads are joined: what the devices counted over the whole run, fetched once.  (Every stream has been
+// synchronised by the writer, or the run has failed: each step runs only while it has not, and fails it with its own words.)
+// the bases k_qmask replaced
+static void collect_qmask(std::vector<Slot> &slots, RunState &rs) {
+    for (auto &s : slots)
+        if (s.d_qcnt && rs.err_code == NH_OK) {
+            unsigned long long c = 0;
+            if (dev_set(s.e->device) == hipSuccess && hipMemcpy(&c, s.d_qcnt, 8, hipMemcpyDeviceToHost) == hipSuccess) rs.qmask_masked += c;
+        }
+}
+
+// host selection: the devices' {host, spared} fragments summed into dev_host
+static void collect_host_counts(const std::vector<RunBuffers> &dbuf, RunState &rs, uint64_t dev_host[2]) {
+    for (size_t g = 0; g < dbuf.size() && rs.err_code == NH_OK; g++) {
+        unsigned long long c[2] = {0, 0};
+        if (dev_set(dbuf[g].device) != hipSuccess || hipMemcpy(c, dbuf[g].hcnt, 16, hipMemcpyDeviceToHost) != hipSuccess) {
+            rs.fail(NH_EDEVICE, "reading the host filter's counters failed");
+            break;
+        }
+        dev_host[0] += c[0], dev_host[1] += c[1];
+    }
+    // (the fragments the writer saw as host and as spared are the checker of what the kernel counted, as for the run's counters)
+    if (rs.err_code == NH_OK && (dev_host[0] != rs.host_frags || dev_host[1] != rs.spared_frags)) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "host filter: the devices counted %llu host / %llu spared fragments, the writer %llu / %llu", (unsigned long long)dev_host[0],
+                 (unsigned long long)dev_host[1], (unsigned long long)rs.host_frags, (unsigned long long)rs.spared_frags);
+        rs.fail(NH_EDEVICE, msg);
+    }
+}
+
+// read statistics: the devices' accumulators, rows summed on the host into racc: [class][mate]
+static void collect_rstats(const std::vector<RunBuffers> &dbuf, RunState &rs, std::vector<nh_read_class> &racc) {
+    if (rs.err_code != NH_OK) return;
+    racc.assign(4, nh_read_class{});
+    for (nh_read_class &c : racc) c.min_len = ~0ull;
+    for (size_t g = 0; g < dbuf.size() && rs.err_code == NH_OK; g++) {
+        nh_read_class part[4];
+        if (dev_set(dbuf[g].device) != hipSuccess || hipMemcpy(part, dbuf[g].racc, sizeof part, hipMemcpyDeviceToHost) != hipSuccess) {
+            rs.fail(NH_EDEVICE, "reading the read statistics' accumulators failed");
+            break;
+        }
+        for (int k = 0; k < 4; k++) {
+            const uint64_t *src = (const uint64_t *)&part[k];
+            uint64_t *dst = (uint64_t *)&racc[k];
+            for (size_t w = 0; w < sizeof(nh_read_class) / 8; w++)
+                if (w == 2) dst[w] = std::min(dst[w], src[w]);
+                else if (w == 3) dst[w] = std::max(dst[w], src[w]);
+                else dst[w] += src[w];
+        }
+    }
+}
+
+// minimizer data: the hit groups of the devices are added; their bitmaps are NOT counted one by one -- a minimizer hit on two
+// devices is one -- but ORed on the host and the union counted on the first engine.  mdn: [3] minimizers_own, [5] distinct_own,
+// [7] db_cells_own
+static void collect_mdata(const std::vector<RunBuffers> &dbuf, RunState &rs, size_t md_mark_bytes, MdataNumbers &mdn, double *md_count_ms) {
+    if (rs.err_code != NH_OK) return;
+    const int G = (int)dbuf.size();
+    Engine *e0 = rs.engines[0];
+    const size_t md_nodes = e0->external.size();
+    const size_t words = md_mark_bytes / 4;
+    std::vector<unsigned long long> part(md_nodes), sum(md_nodes, 0);
+    hipError_t he = hipSuccess;
+    for (int g = 0; g < G && he == hipSuccess; g++) {
+        he = dev_set(dbuf[g].device);
+        if (he == hipSuccess) he = hipMemcpy(part.data(), dbuf[g].groups, md_nodes * 8, hipMemcpyDeviceToHost);
+        for (size_t i = 0; i < md_nodes; i++) sum[i] += part[i];
+    }
+    if (he == hipSuccess && G > 1) {
+        std::vector<uint32_t> all(words, 0), one(words);
+        for (int g = 0; g < G && he == hipSuccess; g++) {
+            he = dev_set(dbuf[g].device);
+            if (he == hipSuccess) he = hipMemcpy(one.data(), dbuf[g].marks, words * 4, hipMemcpyDeviceToHost);
+            for (size_t i = 0; i < words; i++) all[i] |= one[i];
+        }
+        if (he == hipSuccess) he = dev_set(e0->device);
+        if (he == hipSuccess) he = hipMemcpy(dbuf[0].marks, all.data(), words * 4, hipMemcpyHostToDevice);
+    }
+    mdn.v[3].assign(sum.begin(), sum.end());
+    // two counts with the array of hit groups as their bins: the marked cells, then all cells
+    hipEvent_t cev[2] = {nullptr, nullptr};
+    if (he == hipSuccess) he = dev_set(e0->device);
+    if (he == hipSuccess && getenv("NOHUMAN_TRACE") && (hipEventCreate(&cev[0]) != hipSuccess || hipEventCreate(&cev[1]) != hipSuccess)) he = hipErrorUnknown;
+    for (int pass = 0; pass < 2 && he == hipSuccess; pass++) {
+        he = hipMemsetAsync(dbuf[0].groups, 0, md_nodes * 8, e0->stream);
+        if (he == hipSuccess && cev[0]) he = hipEventRecord(cev[0], e0->stream);
+        if (he == hipSuccess) he = launch_mdata_count(e0, pass == 0 ? dbuf[0].marks : nullptr, dbuf[0].groups, e0->stream);
+        if (he == hipSuccess && cev[1]) he = hipEventRecord(cev[1], e0->stream);
+        if (he == hipSuccess) he = hipStreamSynchronize(e0->stream);
+        if (he == hipSuccess) he = hipMemcpy(part.data(), dbuf[0].groups, md_nodes * 8, hipMemcpyDeviceToHost);
+        mdn.v[pass == 0 ? 5 : 7].assign(part.begin(), part.end());
+        if (he == hipSuccess && pass == 0) add_event_ms(cev, md_count_ms);
+    }
+    for (hipEvent_t ev : cev)
+        if (ev) (void)hipEventDestroy(ev);
+    if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("minimizer data, counting the bitmap: ") + hipGetErrorString(he));
+}
+
+// The run's only exchange step: the counters the classify kernels kept in each
+// device's HBM are summed by ONE all-reduce over RCCL, reduced where they lie.  The sums the writer kept
+// on the host are the checker.  A collective that cannot run at G > 1 is reported on stderr (one WARN
+// line; the host sums stand) and fails the run under NOHUMAN_RCCL=strict; NOHUMAN_RCCL=0 skips the
+// collective, =1 also runs it for a single device.
+static int reduce_run_counters(RunState &rs) {
+    const std::vector<Engine *> &engines = rs.engines;
+    const int G = (int)engines.size();
+    std::vector<uint64_t> rows(4 * (size_t)G, 0);
+    uint64_t dsum[4] = {0, 0, 0, 0};
+    hipError_t he = hipSuccess;
+    for (int g = 0; g < G && he == hipSuccess; g++) {
+        he = dev_set(engines[g]->device);
+        if (he == hipSuccess) he = hipMemcpy(&rows[4 * g], rs.d_run_counters[g], 32, hipMemcpyDeviceToHost);
+        for (int i = 0; i < 4; i++) dsum[i] += rows[4 * g + i];
+        if (he == hipSuccess) {  // the engine's running totals (nh_stats_get) include this run
+            hipLaunchKernelGGL(k_add_counters, dim3(1), dim3(4), 0, engines[g]->stream,
+                               (unsigned long long *)engines[g]->d_counters, (const unsigned long long *)rs.d_run_counters[g]);
+            he = hipStreamSynchronize(engines[g]->stream);
+        }
+    }
+    int crc = NH_OK;
+    if (he != hipSuccess) crc = set_error(NH_EDEVICE, "reading the run's counters: %s", hipGetErrorString(he));
+    else if (dsum[CNT_FRAGMENTS] != rs.total || dsum[CNT_CLASSIFIED] != rs.classified || dsum[CNT_BASES] != rs.total_bases)
+        crc = set_error(NH_EDEVICE, "the devices counted %llu fragments / %llu classified / %llu bases, the writer %llu / %llu / %llu",
+                        (unsigned long long)dsum[0], (unsigned long long)dsum[1], (unsigned long long)dsum[2],
+                        (unsigned long long)rs.total, (unsigned long long)rs.classified, (unsigned long long)rs.total_bases);
+    const char *env = getenv("NOHUMAN_RCCL");
+    const bool strict = env && strcmp(env, "strict") == 0;
+    const bool want = env ? env[0] != '0' : G > 1;
+    if (!crc && want && (G > 1 || env)) {
+        std::vector<int> ids;
+        for (Engine *e : engines) ids.push_back(e->device);
+        std::vector<const uint64_t *> src(rs.d_run_counters.begin(), rs.d_run_counters.end());
+        std::string backend;
+        const int arc = allreduce_counters(ids.data(), G, rows.data(), backend, src.data());
+        if (arc == NH_OK) {
+            for (int g = 0; g < G && !crc; g++)
+                if (rows[4 * g] != rs.total || rows[4 * g + 1] != rs.classified || rows[4 * g + 2] != rs.total_bases)
+                    crc = set_error(NH_EDEVICE, "count all-reduce disagrees with the host-side sum on device %d", ids[g]);
+            if (getenv("NOHUMAN_TRACE")) fprintf(stderr, "[nohuman trace] counters reduced by %s\n", backend.c_str());
+        } else if (strict) {
+            crc = arc;
+        } else {
+            fprintf(stderr, "nohuman: WARN count all-reduce over %d devices did not run (%s); the counts were summed on the host\n",
+                    G, g_last_error.c_str());
+        }
+    }
+    return crc;
+}
+int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_stats *stats) {
+    const nh_run_args *a = r.a;
     if (!a || !a->in1 || !a->out1) return set_error(NH_EINVAL, "nh_run: in1 and out1 are required");
     if (const int brc = check_bam_inputs(a)) return brc;
     if (engines.empty()) return set_error(NH_EINVAL, "nh_run: no engine");
-    const bool split = hout1 != nullptr;
-    const int K = (int)n_touts;  // per-taxon outputs: the selectors
+    // the request (check_request has passed it) under the names the pipeline uses
+    const bool mask = r.mask;
+    const char *const calls = r.calls, *const ids = r.ids;
+    const uint32_t minq = r.minq;
+    nh_minimizer_data *const md = r.md;
+    nh_host_filter *const hf = r.hf;
+    const bool split = r.hout1 != nullptr;
+    const int K = (int)r.n_touts;  // per-taxon outputs: the selectors
     const bool taxa = K > 0;
     const bool lists = calls || ids;
     const bool qm = minq > 0;
-    const bool rst = rs_path || rs_out;
+    const bool rst = r.rs_path || r.rs_out;
     const bool mdt = md && (md->in_report || md->table || md->taxa);
-    const bool hsel = host_filter_given(hf);
-    if (minq > 93) return set_error(NH_EINVAL, "nh_run: minimum base quality %u is not in 0..93 (Phred+33)", minq);
-    if (lists) {
-        const int vrc = check_list_args(a, hout1, hout2, calls, ids);
-        if (vrc) return vrc;
-    }
-    if (rs_path) {
-        nh_run_extras x{};
-        x.human_out1 = hout1, x.human_out2 = hout2, x.calls = calls, x.human_ids = ids;
-        const int vrc = check_rstats_args(a, &x, rs_path);
-        if (vrc) return vrc;
-    }
-    if (mask) {
-        const int vrc = check_mask_args(a, hout1, hout2);
-        if (vrc) return vrc;
-    }
-    if (split) {
-        const int vrc = check_split_args(a, hout1, hout2, mask ? "nh_run_mask" : "nh_run_split");
-        if (vrc) return vrc;
-    }
-    // per-taxon outputs: the bin of every node of the taxonomy -- its deepest selected ancestor-or-self, else `other`'s, else none
-    std::vector<uint8_t> bin_of;
-    if (taxa) {
-        nh_run_extras x{};
-        x.human_out1 = hout1, x.human_out2 = hout2, x.calls = calls, x.human_ids = ids;
-        const int vrc = check_taxon_args(a, &x, rs_path, touts, n_touts);
-        if (vrc) return vrc;
-        const Engine *e0 = engines[0];
-        const size_t nn = e0->external.size();
-        bin_of.assign(std::max<size_t>(nn, 1), 0xFF);
-        std::vector<int> own(nn, -1);
-        int other = -1;
-        for (int k = 0; k < K; k++) {
-            if (touts[k].taxid == NH_TAXON_OTHER) {
-                other = k;
-                continue;
-            }
-            size_t at = 0;
-            for (size_t i = 1; i < nn && !at; i++)
-                if (e0->external[i] == touts[k].taxid) at = i;
-            if (!at) return set_error(NH_EINVAL, "nh_run_taxa: taxid %llu is not in the database's taxonomy", (unsigned long long)touts[k].taxid);
-            own[at] = k;
-        }
-        for (size_t i = 1; i < nn; i++) {  // (parents have smaller ids than their children: nh_open checked)
-            const uint32_t p = e0->parent[i];
-            bin_of[i] = own[i] >= 0 ? (uint8_t)own[i] : (i > 1 && p >= 1 && p < i) ? bin_of[p] : other >= 0 ? (uint8_t)other : (uint8_t)0xFF;
-        }
-    }
-    if (mdt) {  // (the database is open: before any input is read or any output created)
-        nh_run_extras x{};
-        x.human_out1 = hout1, x.human_out2 = hout2, x.calls = calls, x.human_ids = ids;
-        int vrc = check_mdata_args(a, &x, rs_path, touts, n_touts, md);
-        for (size_t g = 0; g < engines.size() && !vrc; g++) vrc = mdata_check_db(engines[g]);
-        if (vrc) return vrc;
-    }
-    // the host selection: which nodes of the taxonomy are host (the database is open: before any input is read or any output created)
-    std::vector<uint8_t> host_of;
+    const bool hsel = hf != nullptr;
+    // the features' tables, and what they ask of the database (it is open: before any input is read or any output created)
+    int rc;
+    std::vector<uint8_t> bin_of, host_of;  // per node of the taxonomy: the selector's bin, host or not
+    if (taxa && (rc = selector_bins(engines[0], r, bin_of))) return rc;
+    for (size_t g = 0; mdt && g < engines.size(); g++)
+        if ((rc = mdata_check_db(engines[g]))) return rc;
     if (hsel) {
-        int vrc = check_host_filter(hf);
-        if (!vrc) vrc = host_table(engines[0], hf, host_of);
-        if (vrc) return vrc;
+        if ((rc = host_table(engines[0], hf, host_of))) return rc;
         hf->host_fragments = hf->spared_fragments = 0;
     }
     if (split || lists || taxa)
@@ -1385,67 +1665,25 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
         fclose(f);
     }
     // outputs are created with O_TRUNC before the first input byte is read: an output that IS an input
-    // (same device and inode) would be emptied -- refuse (the CLI host stages its outputs and renames)
-    std::vector<const char *> outputs{a->out1, a->out2, rs.want_k ? a->kraken_output : nullptr, a->report, hout1, hout2, calls, ids};
-    for (int k = 0; k < K; k++) outputs.push_back(touts[k].out1), outputs.push_back(touts[k].out2);
-    for (const char *o : outputs) {
-        struct stat so;
-        if (!o || !o[0] || stat(o, &so) != 0 || !S_ISREG(so.st_mode)) continue;
-        for (const char *p : {a->in1, a->in2}) {
-            struct stat si;
-            if (p && stat(p, &si) == 0 && si.st_dev == so.st_dev && si.st_ino == so.st_ino)
-                return set_error(NH_EINVAL, "nh_run: output %s is the input %s", o, p);
+    // (same device and inode) would be emptied -- refuse (the CLI host stages its outputs and renames).  Only an output that is
+    // there, as a regular file, is looked at; for a plain nh_run this is the only such check.
+    {
+        const std::vector<RunFile> files = request_files(r, F_MDATA);
+        size_t inputs = 0;
+        while (inputs < files.size() && files[inputs].kind == F_INPUT) inputs++;
+        for (size_t c = inputs; c < files.size(); c++) {
+            struct stat so;
+            if (!files[c].path[0] || stat(files[c].path, &so) != 0 || !S_ISREG(so.st_mode)) continue;
+            if ((rc = check_collision(files, c, inputs))) return rc;
         }
     }
-    OutFile o1, o2, ok, h1, h2;  // (h1, h2: the classified records of a split run)
-    int rc;
     const bool gzip_family = a->out_codec == NH_CODEC_GZIP || a->out_codec == NH_CODEC_BGZF;  // the codecs the GPU encodes
     if (a->out_codec < NH_CODEC_NONE || a->out_codec > NH_CODEC_BGZF)
         return set_error(NH_EINVAL, "nh_run: unknown out_codec %d", a->out_codec);
-    // gzip output is encoded on the GPU (nh_deflate.hip); with two devices each mate file has its own
-    // (the two are opened side by side: a GPU encoder takes 70 ms to set up -- page-locked buffers, a trial of its prices)
-    {
-        int rc2 = NH_OK;
-        std::string err2;
-        std::thread t2;
-        if (rs.paired)
-            t2 = std::thread([&] {
-                rc2 = o2.open(a->out2, a->out_codec, a->codec_threads, engines[engines.size() > 1 ? 1 : 0]->device);
-                if (rc2) err2 = g_last_error;
-            });
-        int rch1 = NH_OK, rch2 = NH_OK;
-        std::string errh1, errh2;
-        std::thread th1, th2;
-        if (split) {
-            th1 = std::thread([&] {
-                rch1 = h1.open(hout1, a->out_codec, a->codec_threads, engines[0]->device);
-                if (rch1) errh1 = g_last_error;
-            });
-            if (rs.paired)
-                th2 = std::thread([&] {
-                    rch2 = h2.open(hout2, a->out_codec, a->codec_threads, engines[engines.size() > 1 ? 1 : 0]->device);
-                    if (rch2) errh2 = g_last_error;
-                });
-        }
-        rc = o1.open(a->out1, a->out_codec, a->codec_threads, engines[0]->device);
-        if (t2.joinable()) t2.join();
-        if (th1.joinable()) th1.join();
-        if (th2.joinable()) th2.join();
-        if (rc) return rc;
-        if (rc2) return set_error(rc2, "%s", err2.c_str());
-        if (rch1) return set_error(rch1, "%s", errh1.c_str());
-        if (rch2) return set_error(rch2, "%s", errh2.c_str());
-    }
-    // the selectors' files, [mate][selector]: like the human outputs, mate 1's on the first device, mate 2's on the second
-    OutFile tx[2][NH_MAX_TAXON_OUTS];
-    for (int k = 0; k < K; k++)
-        for (int m = 0; m < (rs.paired ? 2 : 1); m++)
-            if ((rc = tx[m][k].open(m ? touts[k].out2 : touts[k].out1, a->out_codec, a->codec_threads, engines[m && engines.size() > 1 ? 1 : 0]->device)))
-                return rc;
-    if (rs.want_k && (rc = ok.open(a->kraken_output))) return rc;
-    OutFile oc, oi;  // the read lists: plain text whatever the codec of the records
-    if (calls && (rc = oc.open(calls))) return rc;
-    if (ids && (rc = oi.open(ids))) return rc;
+    RunFiles files;
+    if ((rc = open_run_files(files, r, engines, rs.paired, rs.want_k))) return rc;
+    OutFile &o1 = files.o1, &o2 = files.o2, &ok = files.ok, &h1 = files.h1, &h2 = files.h2, &oc = files.oc, &oi = files.oi;
+    OutFile(&tx)[2][NH_MAX_TAXON_OUTS] = files.tx;
 
     // fragments per batch: ~96 MB of sequence, at most 262144; both readers cut at the same record
     // count so that paired batches stay aligned (a byte budget only cuts single-end batches)
@@ -1486,80 +1724,15 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
         for (int m = 0; m < mates; m++) taxon_in_hbm = taxon_in_hbm && tx[m][k].enc && tx[m][k].enc->takes_device_spans();
     auto t0 = std::chrono::steady_clock::now();
 
-    rs.d_run_counters.assign((size_t)G, nullptr);
-    std::vector<uint8_t *> d_bin_of((size_t)G, nullptr);  // per device: bin_of in HBM for the run
-    // host selection: per device host_of in HBM for the run, and the pair of counters {host, spared} k_host_filter adds to
-    std::vector<uint8_t *> d_host_of((size_t)G, nullptr);
-    std::vector<unsigned long long *> d_hcnt((size_t)G, nullptr);
-    // read statistics: one block of four accumulators per device of the run, zeroed with min_len all-ones
-    std::vector<unsigned long long *> d_racc((size_t)G, nullptr);
-    std::vector<nh_read_class> racc;  // the devices' blocks summed: [class][mate]
-    // minimizer data: one zeroed bitmap (a bit a cell) and one array of hit groups per node and device, for the whole run
-    std::vector<uint32_t *> d_marks((size_t)G, nullptr);
-    std::vector<unsigned long long *> d_groups((size_t)G, nullptr);
-    const size_t md_nodes = engines[0]->external.size();
     const size_t md_mark_bytes = mdt ? (size_t)mdata_mark_words(engines[0]) * 4 : 0;
     MdataNumbers mdn;  // [3] minimizers_own, [5] distinct_own, [7] db_cells_own, filled at the end of the run
     double md_count_ms = 0;
-    auto free_run_counters = [&] {
-        for (int g = 0; g < G; g++) {
-            if (!rs.d_run_counters[g] && !d_racc[g] && !d_bin_of[g] && !d_marks[g] && !d_groups[g] && !d_host_of[g] && !d_hcnt[g]) continue;
-            (void)dev_set(engines[g]->device);
-            if (d_host_of[g]) (void)hipFree(d_host_of[g]);
-            if (d_hcnt[g]) (void)hipFree(d_hcnt[g]);
-            d_host_of[g] = nullptr, d_hcnt[g] = nullptr;
-            if (d_marks[g]) (void)hipFree(d_marks[g]);
-            if (d_groups[g]) (void)hipFree(d_groups[g]);
-            d_marks[g] = nullptr, d_groups[g] = nullptr;
-            if (rs.d_run_counters[g]) (void)hipFree(rs.d_run_counters[g]);
-            if (d_racc[g]) (void)hipFree(d_racc[g]);
-            if (d_bin_of[g]) (void)hipFree(d_bin_of[g]);
-            rs.d_run_counters[g] = nullptr, d_racc[g] = nullptr, d_bin_of[g] = nullptr;
-        }
-    };
+    std::vector<nh_read_class> racc;  // read statistics: the devices' blocks summed: [class][mate]
+    std::vector<RunBuffers> dbuf((size_t)G);  // per device, for the run
+    rs.d_run_counters.assign((size_t)G, nullptr);
     for (int g = 0; g < G; g++) {
-        const size_t nb = (CNT_N + 12) * sizeof(uint64_t);  // (+12: the words of the instrumented kernel variant)
-        if (dev_set(engines[g]->device) != hipSuccess || dev_malloc((void **)&rs.d_run_counters[g], nb) != hipSuccess ||
-            hipMemset(rs.d_run_counters[g], 0, nb) != hipSuccess) {
-            free_run_counters();
-            return set_error(NH_EDEVICE, "cannot allocate the run's counters on device %d", engines[g]->device);
-        }
-        if (taxa && (dev_malloc((void **)&d_bin_of[g], bin_of.size()) != hipSuccess ||
-                     hipMemcpy(d_bin_of[g], bin_of.data(), bin_of.size(), hipMemcpyHostToDevice) != hipSuccess)) {
-            free_run_counters();
-            return set_error(NH_EDEVICE, "cannot copy the selectors' bins to device %d", engines[g]->device);
-        }
-        // (hipMemcpy / hipMemset block: the table and the zeroes are in place before the slots' streams, which do not wait for the
-        // legacy stream, carry the first batch)
-        if (hsel && (dev_malloc((void **)&d_host_of[g], host_of.size()) != hipSuccess || dev_malloc((void **)&d_hcnt[g], 16) != hipSuccess ||
-                     hipMemcpy(d_host_of[g], host_of.data(), host_of.size(), hipMemcpyHostToDevice) != hipSuccess ||
-                     hipMemset(d_hcnt[g], 0, 16) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) {
-            free_run_counters();
-            return set_error(NH_EDEVICE, "cannot copy the host selection's table to device %d", engines[g]->device);
-        }
-        if (rst) {
-            nh_read_class init[4];
-            memset(init, 0, sizeof init);
-            for (nh_read_class &c : init) c.min_len = ~0ull;
-            if (dev_malloc((void **)&d_racc[g], sizeof init) != hipSuccess || hipMemcpy(d_racc[g], init, sizeof init, hipMemcpyHostToDevice) != hipSuccess) {
-                free_run_counters();
-                return set_error(NH_EDEVICE, "cannot allocate the read statistics' accumulators on device %d", engines[g]->device);
-            }
-        }
-        if (mdt) {
-            // (the slots' streams do not wait for the legacy stream: the zeroes are in place before the first batch)
-            if (dev_malloc((void **)&d_marks[g], std::max<size_t>(md_mark_bytes, 4)) != hipSuccess ||
-                dev_malloc((void **)&d_groups[g], std::max<size_t>(md_nodes, 1) * 8) != hipSuccess) {
-                free_run_counters();
-                return set_error(NH_EOOM, "minimizer data: cannot allocate the bitmap of %zu bytes and %zu counters on device %d", md_mark_bytes, md_nodes,
-                                 engines[g]->device);
-            }
-            if (hipMemset(d_marks[g], 0, std::max<size_t>(md_mark_bytes, 4)) != hipSuccess ||
-                hipMemset(d_groups[g], 0, std::max<size_t>(md_nodes, 1) * 8) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-                free_run_counters();
-                return set_error(NH_EDEVICE, "minimizer data: cannot clear the bitmap on device %d", engines[g]->device);
-            }
-        }
+        if ((rc = alloc_run_buffers(dbuf[g], engines[g], bin_of, host_of, rst, md_mark_bytes, engines[0]->external.size(), mdt))) return rc;
+        rs.d_run_counters[g] = dbuf[g].counters;
     }
     // stream slots a device: two keep the classifier busy; a third lets the copy of a batch's text back to the host (batches
     // born on the GPU, outputs written by the host) run while the writer is still busy with the batch before; a fourth is
@@ -1589,7 +1762,6 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
             (hsel && getenv("NOHUMAN_TRACE") &&
              (hipEventCreate(&slots[i].hev[0]) != hipSuccess || hipEventCreate(&slots[i].hev[1]) != hipSuccess))) {
             for (auto &s : slots) slot_free(s);
-            free_run_counters();
             return set_error(NH_EDEVICE, "cannot create streams");
         }
     }
@@ -2189,7 +2361,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
             const nh_result *const d_host_res = (const nh_result *)(hsel ? s.d_hres : s.d_res);
             if (!rs.failed() && hsel) {
                 if (s.hev[0]) (void)hipEventRecord(s.hev[0], s.stream);
-                he = launch_host_filter(s.d_res, s.d_hres, b.n, d_host_of[(size_t)(si / NS)], s.e->external.size(), d_hcnt[(size_t)(si / NS)],
+                he = launch_host_filter(s.d_res, s.d_hres, b.n, dbuf[(size_t)(si / NS)].host_of, s.e->external.size(), dbuf[(size_t)(si / NS)].hcnt,
                                         s.e->d_error + LAUNCH_SLOTS, s.stream);
                 if (s.hev[1] && he == hipSuccess) he = hipEventRecord(s.hev[1], s.stream);
                 if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("host filter: ") + hipGetErrorString(he));
@@ -2206,7 +2378,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 ta.fastq[0] = b.h1->format == FMT_FASTQ;
                 ta.fastq[1] = rs.paired && b.h2->format == FMT_FASTQ;
                 ta.res = d_host_res;
-                ta.acc = d_racc[(size_t)(si / NS)];
+                ta.acc = dbuf[(size_t)(si / NS)].racc;
                 ta.error = s.e->d_error + LAUNCH_SLOTS;
                 if (s.rev[0]) (void)hipEventRecord(s.rev[0], s.stream);
                 he = launch_rstats(ta, s.e->n_cu, 0, s.stream);
@@ -2215,8 +2387,8 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
             }
             if (!rs.failed() && mdt) {  // minimizer data, marked behind the classifier on the same stream: the text the classifier read
                 if (s.mev[0]) (void)hipEventRecord(s.mev[0], s.stream);
-                he = launch_mdata_mark(s.e, qm ? s.d_qtext : s.d_text, ntext, s.d_off, s.d_len, b.n, mates, d_marks[(size_t)(si / NS)],
-                                       d_groups[(size_t)(si / NS)], s.stream);
+                he = launch_mdata_mark(s.e, qm ? s.d_qtext : s.d_text, ntext, s.d_off, s.d_len, b.n, mates, dbuf[(size_t)(si / NS)].marks,
+                                       dbuf[(size_t)(si / NS)].groups, s.stream);
                 if (s.mev[1] && he == hipSuccess) he = hipEventRecord(s.mev[1], s.stream);
                 if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("minimizer data: ") + hipGetErrorString(he));
             }
@@ -2286,7 +2458,7 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                 ta.fastq[1] = rs.paired && b.h2->format == FMT_FASTQ;
                 for (int m = 0; m < mates; m++) ta.out[m] = s.taxon.d_out[m], ta.cap[m] = s.taxon.cap_out[m];
                 ta.blk = (uint64_t *)s.taxon.d_blk;
-                ta.bin_of = d_bin_of[(size_t)(si / NS)];
+                ta.bin_of = dbuf[(size_t)(si / NS)].bin_of;
                 ta.K = K;
                 ta.start = s.taxon.d_total = ta.blk + 2 * (uint64_t)K * ta.nblk;
                 ta.total = ta.start + 2 * K;
@@ -2369,87 +2541,11 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
         w2_cv.notify_all();
         tw2.join();
     }
-    for (auto &s : slots)  // (every stream has been synchronised by the writer, or the run has failed)
-        if (s.d_qcnt && rs.err_code == NH_OK) {
-            unsigned long long c = 0;
-            if (dev_set(s.e->device) == hipSuccess && hipMemcpy(&c, s.d_qcnt, 8, hipMemcpyDeviceToHost) == hipSuccess) rs.qmask_masked += c;
-        }
+    collect_qmask(slots, rs);
     uint64_t dev_host[2] = {0, 0};  // host selection: the devices' {host, spared} fragments summed
-    for (int g = 0; hsel && g < G && rs.err_code == NH_OK; g++) {
-        unsigned long long c[2] = {0, 0};
-        if (dev_set(engines[g]->device) != hipSuccess || hipMemcpy(c, d_hcnt[g], 16, hipMemcpyDeviceToHost) != hipSuccess) {
-            rs.fail(NH_EDEVICE, "reading the host filter's counters failed");
-            break;
-        }
-        dev_host[0] += c[0], dev_host[1] += c[1];
-    }
-    // (the fragments the writer saw as host and as spared are the checker of what the kernel counted, as for the run's counters)
-    if (hsel && rs.err_code == NH_OK && (dev_host[0] != rs.host_frags || dev_host[1] != rs.spared_frags)) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "host filter: the devices counted %llu host / %llu spared fragments, the writer %llu / %llu", (unsigned long long)dev_host[0],
-                 (unsigned long long)dev_host[1], (unsigned long long)rs.host_frags, (unsigned long long)rs.spared_frags);
-        rs.fail(NH_EDEVICE, msg);
-    }
-    if (rst && rs.err_code == NH_OK) {  // the devices' accumulators, once: rows summed on the host
-        racc.assign(4, nh_read_class{});
-        for (nh_read_class &c : racc) c.min_len = ~0ull;
-        for (int g = 0; g < G && rs.err_code == NH_OK; g++) {
-            nh_read_class part[4];
-            if (dev_set(engines[g]->device) != hipSuccess || hipMemcpy(part, d_racc[g], sizeof part, hipMemcpyDeviceToHost) != hipSuccess) {
-                rs.fail(NH_EDEVICE, "reading the read statistics' accumulators failed");
-                break;
-            }
-            for (int k = 0; k < 4; k++) {
-                const uint64_t *src = (const uint64_t *)&part[k];
-                uint64_t *dst = (uint64_t *)&racc[k];
-                for (size_t w = 0; w < sizeof(nh_read_class) / 8; w++)
-                    if (w == 2) dst[w] = std::min(dst[w], src[w]);
-                    else if (w == 3) dst[w] = std::max(dst[w], src[w]);
-                    else dst[w] += src[w];
-            }
-        }
-    }
-    if (mdt && rs.err_code == NH_OK) {
-        // (every stream has been synchronised.)  The hit groups of the devices are added; their bitmaps are NOT counted one by one
-        // -- a minimizer hit on two devices is one -- but ORed on the host and the union counted on the first engine.
-        Engine *e0 = engines[0];
-        const size_t words = md_mark_bytes / 4;
-        std::vector<unsigned long long> part(md_nodes), sum(md_nodes, 0);
-        hipError_t he = hipSuccess;
-        for (int g = 0; g < G && he == hipSuccess; g++) {
-            he = dev_set(engines[g]->device);
-            if (he == hipSuccess) he = hipMemcpy(part.data(), d_groups[g], md_nodes * 8, hipMemcpyDeviceToHost);
-            for (size_t i = 0; i < md_nodes; i++) sum[i] += part[i];
-        }
-        if (he == hipSuccess && G > 1) {
-            std::vector<uint32_t> all(words, 0), one(words);
-            for (int g = 0; g < G && he == hipSuccess; g++) {
-                he = dev_set(engines[g]->device);
-                if (he == hipSuccess) he = hipMemcpy(one.data(), d_marks[g], words * 4, hipMemcpyDeviceToHost);
-                for (size_t i = 0; i < words; i++) all[i] |= one[i];
-            }
-            if (he == hipSuccess) he = dev_set(e0->device);
-            if (he == hipSuccess) he = hipMemcpy(d_marks[0], all.data(), words * 4, hipMemcpyHostToDevice);
-        }
-        mdn.v[3].assign(sum.begin(), sum.end());
-        // two counts with the array of hit groups as their bins: the marked cells, then all cells
-        hipEvent_t cev[2] = {nullptr, nullptr};
-        if (he == hipSuccess) he = dev_set(e0->device);
-        if (he == hipSuccess && getenv("NOHUMAN_TRACE") && (hipEventCreate(&cev[0]) != hipSuccess || hipEventCreate(&cev[1]) != hipSuccess)) he = hipErrorUnknown;
-        for (int pass = 0; pass < 2 && he == hipSuccess; pass++) {
-            he = hipMemsetAsync(d_groups[0], 0, md_nodes * 8, e0->stream);
-            if (he == hipSuccess && cev[0]) he = hipEventRecord(cev[0], e0->stream);
-            if (he == hipSuccess) he = launch_mdata_count(e0, pass == 0 ? d_marks[0] : nullptr, d_groups[0], e0->stream);
-            if (he == hipSuccess && cev[1]) he = hipEventRecord(cev[1], e0->stream);
-            if (he == hipSuccess) he = hipStreamSynchronize(e0->stream);
-            if (he == hipSuccess) he = hipMemcpy(part.data(), d_groups[0], md_nodes * 8, hipMemcpyDeviceToHost);
-            mdn.v[pass == 0 ? 5 : 7].assign(part.begin(), part.end());
-            if (he == hipSuccess && pass == 0) add_event_ms(cev, &md_count_ms);
-        }
-        for (hipEvent_t ev : cev)
-            if (ev) (void)hipEventDestroy(ev);
-        if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("minimizer data, counting the bitmap: ") + hipGetErrorString(he));
-    }
+    if (hsel) collect_host_counts(dbuf, rs, dev_host);
+    if (rst) collect_rstats(dbuf, rs, racc);
+    if (mdt) collect_mdata(dbuf, rs, md_mark_bytes, mdn, &md_count_ms);
     for (auto &s : slots) slot_free(s);
     if (const char *tr = getenv("NOHUMAN_TRACE")) {
         if (tr[0] == '1') {
@@ -2498,67 +2594,14 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
                         g_pageable_batches.load());
         }
     }
-    if (rs.err_code != NH_OK) {
-        free_run_counters();
-        return set_error(rs.err_code, "%s", rs.err_msg.c_str());
-    }
+    if (rs.err_code != NH_OK) return set_error(rs.err_code, "%s", rs.err_msg.c_str());
     if (dev_debug()) {  // NOHUMAN_DEBUG_DEVICE: a launch, copy or allocation under the wrong device fails the run that met it
         const std::string v = dev_violation(true);
-        if (!v.empty()) {
-            free_run_counters();
-            return set_error(NH_EDEVICE, "device discipline: %s", v.c_str());
-        }
+        if (!v.empty()) return set_error(NH_EDEVICE, "device discipline: %s", v.c_str());
     }
-
-    // The run's only exchange step: the counters the classify kernels kept in each
-    // device's HBM are summed by ONE all-reduce over RCCL, reduced where they lie.  The sums the writer kept
-    // on the host are the checker.  A collective that cannot run at G > 1 is reported on stderr (one WARN
-    // line; the host sums stand) and fails the run under NOHUMAN_RCCL=strict; NOHUMAN_RCCL=0 skips the
-    // collective, =1 also runs it for a single device.
-    {
-        std::vector<uint64_t> rows(4 * (size_t)G, 0);
-        uint64_t dsum[4] = {0, 0, 0, 0};
-        hipError_t he = hipSuccess;
-        for (int g = 0; g < G && he == hipSuccess; g++) {
-            he = dev_set(engines[g]->device);
-            if (he == hipSuccess) he = hipMemcpy(&rows[4 * g], rs.d_run_counters[g], 32, hipMemcpyDeviceToHost);
-            for (int i = 0; i < 4; i++) dsum[i] += rows[4 * g + i];
-            if (he == hipSuccess) {  // the engine's running totals (nh_stats_get) include this run
-                hipLaunchKernelGGL(k_add_counters, dim3(1), dim3(4), 0, engines[g]->stream,
-                                   (unsigned long long *)engines[g]->d_counters, (const unsigned long long *)rs.d_run_counters[g]);
-                he = hipStreamSynchronize(engines[g]->stream);
-            }
-        }
-        int crc = NH_OK;
-        if (he != hipSuccess) crc = set_error(NH_EDEVICE, "reading the run's counters: %s", hipGetErrorString(he));
-        else if (dsum[CNT_FRAGMENTS] != rs.total || dsum[CNT_CLASSIFIED] != rs.classified || dsum[CNT_BASES] != rs.total_bases)
-            crc = set_error(NH_EDEVICE, "the devices counted %llu fragments / %llu classified / %llu bases, the writer %llu / %llu / %llu",
-                            (unsigned long long)dsum[0], (unsigned long long)dsum[1], (unsigned long long)dsum[2],
-                            (unsigned long long)rs.total, (unsigned long long)rs.classified, (unsigned long long)rs.total_bases);
-        const char *env = getenv("NOHUMAN_RCCL");
-        const bool strict = env && strcmp(env, "strict") == 0;
-        const bool want = env ? env[0] != '0' : G > 1;
-        if (!crc && want && (G > 1 || env)) {
-            std::vector<int> ids;
-            for (Engine *e : engines) ids.push_back(e->device);
-            std::vector<const uint64_t *> src(rs.d_run_counters.begin(), rs.d_run_counters.end());
-            std::string backend;
-            const int arc = allreduce_counters(ids.data(), G, rows.data(), backend, src.data());
-            if (arc == NH_OK) {
-                for (int g = 0; g < G && !crc; g++)
-                    if (rows[4 * g] != rs.total || rows[4 * g + 1] != rs.classified || rows[4 * g + 2] != rs.total_bases)
-                        crc = set_error(NH_EDEVICE, "count all-reduce disagrees with the host-side sum on device %d", ids[g]);
-                if (getenv("NOHUMAN_TRACE")) fprintf(stderr, "[nohuman trace] counters reduced by %s\n", backend.c_str());
-            } else if (strict) {
-                crc = arc;
-            } else {
-                fprintf(stderr, "nohuman: WARN count all-reduce over %d devices did not run (%s); the counts were summed on the host\n",
-                        G, g_last_error.c_str());
-            }
-        }
-        free_run_counters();
-        if (crc) return crc;
-    }
+    rc = reduce_run_counters(rs);
+    dbuf.clear();  // (the run's device buffers go back before the reports are written)
+    if (rc) return rc;
 
     const TaxoView mdview = taxo_view(engines[0]);
     if (mdt) {
@@ -2643,10 +2686,10 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
             return set_error(NH_EDEVICE, "read statistics: the devices counted %llu reads / %llu bases, the writer %llu / %llu",
                              (unsigned long long)dev_reads, (unsigned long long)dev_bases, (unsigned long long)host_reads,
                              (unsigned long long)host_bases);
-        if (rs_path && (rc = nh_read_stats_write(&out, rs_path))) return rc;
-        if (rs_out) *rs_out = out;
+        if (r.rs_path && (rc = nh_read_stats_write(&out, r.rs_path))) return rc;
+        if (r.rs_out) *r.rs_out = out;
     }
-    for (int k = 0; k < K; k++) touts[k].fragments = rs.taxon_frags[k];
+    for (int k = 0; k < K; k++) r.touts[k].fragments = rs.taxon_frags[k];
     if (hsel) hf->host_fragments = rs.host_frags, hf->spared_fragments = rs.spared_frags;
     if (mdt) {
         if (md->table && (rc = write_mdata_table(mdview, mdn, md->table))) return rc;
@@ -2671,155 +2714,66 @@ int run_engines(const std::vector<Engine *> &engines, const nh_run_args *a, nh_s
     return NH_OK;
 }
 
-int run_engine(Engine *e, const nh_run_args *a, nh_stats *stats, const char *hout1 = nullptr, const char *hout2 = nullptr,
-               bool mask = false, const char *calls = nullptr, const char *ids = nullptr, uint32_t minq = 0,
-               const char *rs_path = nullptr, nh_read_stats *rs_out = nullptr, nh_taxon_out *touts = nullptr, uint32_t n_touts = 0,
-               nh_minimizer_data *md = nullptr, nh_host_filter *hf = nullptr) {
+int run_engine(Engine *e, const RunRequest &r, nh_stats *stats) {
     std::vector<Engine *> v{e};
-    return run_engines(v, a, stats, hout1, hout2, mask, calls, ids, minq, rs_path, rs_out, touts, n_touts, md, hf);
-}
-
-// nh_run_minq's own argument, checked before any device is touched: the highest printable quality is '~', Phred 93
-int check_minq(uint32_t minq) {
-    if (minq > 93) return set_error(NH_EINVAL, "minimum base quality %u is not in 0..93 (Phred+33)", minq);
-    return NH_OK;
-}
-
-// nh_run_ex's arguments, checked before any device is touched: the struct, what nh_run_split / nh_run_mask check for the fields
-// they share, and the read lists
-int check_extras(const nh_run_args *a, const nh_run_extras *x) {
-    if (!a) return set_error(NH_EINVAL, "nh_run_ex: null arguments");
-    if (!x) return set_error(NH_EINVAL, "nh_run_ex: null extras");
-    if (x->struct_size < sizeof(nh_run_extras))
-        return set_error(NH_EINVAL, "nh_run_ex: struct_size %u is smaller than nh_run_extras (%zu bytes)", x->struct_size, sizeof(nh_run_extras));
-    int rc = NH_OK;
-    if (x->mask) rc = check_mask_args(a, x->human_out1, x->human_out2);
-    else if (x->human_out1 || x->human_out2) rc = check_split_args(a, x->human_out1, x->human_out2);
-    if (rc) return rc;
-    return check_list_args(a, x->human_out1, x->human_out2, x->calls, x->human_ids);
-}
-
-// nh_run_rstats' arguments, checked before any device is touched: nh_run_minq's, then the table's path
-int check_rstats(const nh_run_args *a, const nh_run_extras *x, uint32_t minq, const char *rs_path) {
-    int rc = check_minq(minq);
-    if (!rc && x) rc = check_extras(a, x);
-    if (!rc) rc = check_rstats_args(a, x, rs_path);
-    return rc;
-}
-
-// nh_run_taxa's arguments, checked before any device is touched: nh_run_rstats', then the selectors
-int check_taxa(const nh_run_args *a, const nh_run_extras *x, uint32_t minq, const char *rs_path, const nh_taxon_out *outs, uint32_t n) {
-    int rc = check_rstats(a, x, minq, rs_path);
-    if (!rc) rc = check_taxon_args(a, x, rs_path, outs, n);
-    return rc;
-}
-
-// nh_run_mdata's arguments, checked before any device is touched: nh_run_taxa's, then the struct and the table's path
-int check_mdata(const nh_run_args *a, const nh_run_extras *x, uint32_t minq, const char *rs_path, const nh_taxon_out *outs, uint32_t n,
-                const nh_minimizer_data *md) {
-    int rc = check_taxa(a, x, minq, rs_path, outs, n);
-    if (!rc) rc = check_mdata_args(a, x, rs_path, outs, n, md);
-    return rc;
-}
-
-// nh_run_host's arguments, checked before any device is touched: the selection's own, then nh_run_mdata's
-int check_host(const nh_run_args *a, const nh_run_extras *x, uint32_t minq, const char *rs_path, const nh_taxon_out *outs, uint32_t n,
-               const nh_minimizer_data *md, const nh_host_filter *hf) {
-    int rc = check_host_filter(hf);
-    if (!rc) rc = check_mdata(a, x, minq, rs_path, outs, n, md);
-    return rc;
+    return run_engines(v, r, stats);
 }
 
 }  // namespace nh
 
 extern "C" {
 
-int nh_run_engine(nh_engine *e, const nh_run_args *args, nh_stats *stats) {
+// an engine entry: the request's own checks (before any device is touched), then the run on the caller's engine
+static int run_on_engine(nh_engine *e, const nh::RunRequest &r, nh_stats *stats) {
+    if (const int rc = nh::check_request(r)) return rc;
     if (!e) return nh::set_error(NH_EINVAL, "null engine");
-    return nh::run_engine((nh::Engine *)e, args, stats);
+    return nh::run_engine((nh::Engine *)e, r, stats);
+}
+
+int nh_run_engine(nh_engine *e, const nh_run_args *args, nh_stats *stats) {
+    return run_on_engine(e, nh::make_request(nh::RunRequest::RUN, args, nullptr), stats);
 }
 
 int nh_run_engine_split(nh_engine *e, const nh_run_args *args, const char *human_out1, const char *human_out2, nh_stats *stats) {
-    const int rc = nh::check_split_args(args, human_out1, human_out2);
-    if (rc) return rc;
-    if (!e) return nh::set_error(NH_EINVAL, "null engine");
-    return nh::run_engine((nh::Engine *)e, args, stats, human_out1, human_out2);
+    return run_on_engine(e, nh::make_request(nh::RunRequest::SPLIT, args, nullptr, human_out1, human_out2), stats);
 }
 
 int nh_run_engine_mask(nh_engine *e, const nh_run_args *args, const char *human_out1, const char *human_out2, nh_stats *stats) {
-    const int rc = nh::check_mask_args(args, human_out1, human_out2);
-    if (rc) return rc;
-    if (!e) return nh::set_error(NH_EINVAL, "null engine");
-    return nh::run_engine((nh::Engine *)e, args, stats, human_out1, human_out2, true);
+    return run_on_engine(e, nh::make_request(nh::RunRequest::MASK, args, nullptr, human_out1, human_out2), stats);
 }
 
 int nh_run_engine_ex(nh_engine *e, const nh_run_args *args, const nh_run_extras *extras, nh_stats *stats) {
-    const int rc = nh::check_extras(args, extras);
-    if (rc) return rc;
-    if (!e) return nh::set_error(NH_EINVAL, "null engine");
-    return nh::run_engine((nh::Engine *)e, args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls,
-                          extras->human_ids);
+    return run_on_engine(e, nh::make_request(nh::RunRequest::EX, args, extras), stats);
 }
 
 int nh_run_engine_minq(nh_engine *e, const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality, nh_stats *stats) {
-    int rc = nh::check_minq(min_base_quality);
-    if (!rc && extras) rc = nh::check_extras(args, extras);
-    if (rc) return rc;
-    if (!e) return nh::set_error(NH_EINVAL, "null engine");
-    if (!extras) return nh::run_engine((nh::Engine *)e, args, stats, nullptr, nullptr, false, nullptr, nullptr, min_base_quality);
-    return nh::run_engine((nh::Engine *)e, args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls,
-                          extras->human_ids, min_base_quality);
+    return run_on_engine(e, nh::make_request(nh::RunRequest::RUN, args, extras, nullptr, nullptr, min_base_quality), stats);
 }
 
 int nh_run_engine_rstats(nh_engine *e, const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality,
                          const char *read_stats_path, nh_read_stats *out, nh_stats *stats) {
-    const int rc = nh::check_rstats(args, extras, min_base_quality, read_stats_path);
-    if (rc) return rc;
-    if (!e) return nh::set_error(NH_EINVAL, "null engine");
-    if (!extras)
-        return nh::run_engine((nh::Engine *)e, args, stats, nullptr, nullptr, false, nullptr, nullptr, min_base_quality, read_stats_path, out);
-    return nh::run_engine((nh::Engine *)e, args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls,
-                          extras->human_ids, min_base_quality, read_stats_path, out);
+    return run_on_engine(e, nh::make_request(nh::RunRequest::RUN, args, extras, nullptr, nullptr, min_base_quality, read_stats_path, out), stats);
 }
 
 int nh_run_engine_taxa(nh_engine *e, const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality,
                        const char *read_stats_path, nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs, nh_stats *stats) {
-    const int rc = nh::check_taxa(args, extras, min_base_quality, read_stats_path, outs, n_outs);
-    if (rc) return rc;
-    if (!e) return nh::set_error(NH_EINVAL, "null engine");
-    if (!extras)
-        return nh::run_engine((nh::Engine *)e, args, stats, nullptr, nullptr, false, nullptr, nullptr, min_base_quality, read_stats_path, read_stats,
-                              outs, n_outs);
-    return nh::run_engine((nh::Engine *)e, args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls,
-                          extras->human_ids, min_base_quality, read_stats_path, read_stats, outs, n_outs);
+    return run_on_engine(e, nh::make_request(nh::RunRequest::RUN, args, extras, nullptr, nullptr, min_base_quality, read_stats_path, read_stats, outs, n_outs),
+                         stats);
 }
 
 int nh_run_engine_mdata(nh_engine *e, const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality,
                         const char *read_stats_path, nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs, nh_minimizer_data *md,
                         nh_stats *stats) {
-    const int rc = nh::check_mdata(args, extras, min_base_quality, read_stats_path, outs, n_outs, md);
-    if (rc) return rc;
-    if (!e) return nh::set_error(NH_EINVAL, "null engine");
-    if (!extras)
-        return nh::run_engine((nh::Engine *)e, args, stats, nullptr, nullptr, false, nullptr, nullptr, min_base_quality, read_stats_path, read_stats,
-                              outs, n_outs, md);
-    return nh::run_engine((nh::Engine *)e, args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls,
-                          extras->human_ids, min_base_quality, read_stats_path, read_stats, outs, n_outs, md);
+    return run_on_engine(e, nh::make_request(nh::RunRequest::RUN, args, extras, nullptr, nullptr, min_base_quality, read_stats_path, read_stats, outs, n_outs, md),
+                         stats);
 }
 
+// (without a selection -- hf NULL, or no taxid in it -- the request is nh_run_engine_mdata's: make_request drops such an hf)
 int nh_run_engine_host(nh_engine *e, const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality,
                        const char *read_stats_path, nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs, nh_minimizer_data *md,
                        nh_host_filter *hf, nh_stats *stats) {
-    if (!nh::host_filter_given(hf))  // (exactly nh_run_engine_mdata)
-        return nh_run_engine_mdata(e, args, extras, min_base_quality, read_stats_path, read_stats, outs, n_outs, md, stats);
-    const int rc = nh::check_host(args, extras, min_base_quality, read_stats_path, outs, n_outs, md, hf);
-    if (rc) return rc;
-    if (!e) return nh::set_error(NH_EINVAL, "null engine");
-    if (!extras)
-        return nh::run_engine((nh::Engine *)e, args, stats, nullptr, nullptr, false, nullptr, nullptr, min_base_quality, read_stats_path, read_stats,
-                              outs, n_outs, md, hf);
-    return nh::run_engine((nh::Engine *)e, args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls,
-                          extras->human_ids, min_base_quality, read_stats_path, read_stats, outs, n_outs, md, hf);
+    return run_on_engine(
+        e, nh::make_request(nh::RunRequest::RUN, args, extras, nullptr, nullptr, min_base_quality, read_stats_path, read_stats, outs, n_outs, md, hf), stats);
 }
 
 int nh_fastx_scan(const char *path, uint64_t *n_records, uint64_t *n_bases, uint64_t *digest) {
@@ -2988,10 +2942,8 @@ int nh_debug_reader_dump(const char *path, int reader, int device, uint64_t batc
 
 // Whole run on one or several devices: the database is loaded into every device's HBM, batches go
 // round-robin, outputs stay in input order, the counts are summed on the host.
-static int run_devices(const nh_run_args *args, nh_stats *stats, const char *hout1, const char *hout2, bool mask = false,
-                       const char *calls = nullptr, const char *ids = nullptr, uint32_t minq = 0, const char *rs_path = nullptr,
-                       nh_read_stats *rs_out = nullptr, nh_taxon_out *touts = nullptr, uint32_t n_touts = 0, nh_minimizer_data *md = nullptr,
-                       nh_host_filter *hf = nullptr) {
+static int run_devices(const nh::RunRequest &r, nh_stats *stats) {
+    const nh_run_args *args = r.a;
     if (!args || !args->db_dir) return nh::set_error(NH_EINVAL, "nh_run: db_dir is required");
     if (const int brc = nh::check_bam_inputs(args)) return brc;
     int ndev = 0;
@@ -3028,7 +2980,7 @@ static int run_devices(const nh_run_args *args, nh_stats *stats, const char *hou
     }
     const double t_load = since(t_begin);
     const auto t_run = std::chrono::steady_clock::now();
-    if (!rc) rc = nh::run_engines(engines, args, stats, hout1, hout2, mask, calls, ids, minq, rs_path, rs_out, touts, n_touts, md, hf);
+    if (!rc) rc = nh::run_engines(engines, r, stats);
     const double s_run = since(t_run);
     std::string keep = nh::g_last_error;
     const auto t_close = std::chrono::steady_clock::now();
@@ -3040,73 +2992,52 @@ static int run_devices(const nh_run_args *args, nh_stats *stats, const char *hou
     return rc;
 }
 
-int nh_run(const nh_run_args *args, nh_stats *stats) { return run_devices(args, stats, nullptr, nullptr); }
+// a standalone entry: the request's own checks (before any device is touched), then the run on the devices it names
+static int run_standalone(const nh::RunRequest &r, nh_stats *stats) {
+    if (const int rc = nh::check_request(r)) return rc;
+    return run_devices(r, stats);
+}
+
+int nh_run(const nh_run_args *args, nh_stats *stats) { return run_standalone(nh::make_request(nh::RunRequest::RUN, args, nullptr), stats); }
 
 int nh_run_split(const nh_run_args *args, const char *human_out1, const char *human_out2, nh_stats *stats) {
-    const int rc = nh::check_split_args(args, human_out1, human_out2);  // (before any device is touched)
-    if (rc) return rc;
-    return run_devices(args, stats, human_out1, human_out2);
+    return run_standalone(nh::make_request(nh::RunRequest::SPLIT, args, nullptr, human_out1, human_out2), stats);
 }
 
 int nh_run_mask(const nh_run_args *args, const char *human_out1, const char *human_out2, nh_stats *stats) {
-    const int rc = nh::check_mask_args(args, human_out1, human_out2);  // (before any device is touched)
-    if (rc) return rc;
-    return run_devices(args, stats, human_out1, human_out2, true);
+    return run_standalone(nh::make_request(nh::RunRequest::MASK, args, nullptr, human_out1, human_out2), stats);
 }
 
 int nh_run_ex(const nh_run_args *args, const nh_run_extras *extras, nh_stats *stats) {
-    const int rc = nh::check_extras(args, extras);  // (before any device is touched)
-    if (rc) return rc;
-    return run_devices(args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls, extras->human_ids);
+    return run_standalone(nh::make_request(nh::RunRequest::EX, args, extras), stats);
 }
 
 int nh_run_minq(const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality, nh_stats *stats) {
-    int rc = nh::check_minq(min_base_quality);  // (before any device is touched)
-    if (!rc && extras) rc = nh::check_extras(args, extras);
-    if (rc) return rc;
-    if (!extras) return run_devices(args, stats, nullptr, nullptr, false, nullptr, nullptr, min_base_quality);
-    return run_devices(args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls, extras->human_ids,
-                       min_base_quality);
+    return run_standalone(nh::make_request(nh::RunRequest::RUN, args, extras, nullptr, nullptr, min_base_quality), stats);
 }
 
 int nh_run_rstats(const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality, const char *read_stats_path,
                   nh_read_stats *out, nh_stats *stats) {
-    const int rc = nh::check_rstats(args, extras, min_base_quality, read_stats_path);  // (before any device is touched)
-    if (rc) return rc;
-    if (!extras) return run_devices(args, stats, nullptr, nullptr, false, nullptr, nullptr, min_base_quality, read_stats_path, out);
-    return run_devices(args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls, extras->human_ids,
-                       min_base_quality, read_stats_path, out);
+    return run_standalone(nh::make_request(nh::RunRequest::RUN, args, extras, nullptr, nullptr, min_base_quality, read_stats_path, out), stats);
 }
 
 int nh_run_taxa(const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality, const char *read_stats_path,
                 nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs, nh_stats *stats) {
-    const int rc = nh::check_taxa(args, extras, min_base_quality, read_stats_path, outs, n_outs);  // (before any device is touched)
-    if (rc) return rc;
-    if (!extras)
-        return run_devices(args, stats, nullptr, nullptr, false, nullptr, nullptr, min_base_quality, read_stats_path, read_stats, outs, n_outs);
-    return run_devices(args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls, extras->human_ids,
-                       min_base_quality, read_stats_path, read_stats, outs, n_outs);
+    return run_standalone(nh::make_request(nh::RunRequest::RUN, args, extras, nullptr, nullptr, min_base_quality, read_stats_path, read_stats, outs, n_outs),
+                          stats);
 }
 
 int nh_run_mdata(const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality, const char *read_stats_path,
                  nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs, nh_minimizer_data *md, nh_stats *stats) {
-    const int rc = nh::check_mdata(args, extras, min_base_quality, read_stats_path, outs, n_outs, md);  // (before any device is touched)
-    if (rc) return rc;
-    if (!extras)
-        return run_devices(args, stats, nullptr, nullptr, false, nullptr, nullptr, min_base_quality, read_stats_path, read_stats, outs, n_outs, md);
-    return run_devices(args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls, extras->human_ids,
-                       min_base_quality, read_stats_path, read_stats, outs, n_outs, md);
+    return run_standalone(nh::make_request(nh::RunRequest::RUN, args, extras, nullptr, nullptr, min_base_quality, read_stats_path, read_stats, outs, n_outs, md),
+                          stats);
 }
 
+// (without a selection -- hf NULL, or no taxid in it -- the request is nh_run_mdata's: make_request drops such an hf)
 int nh_run_host(const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality, const char *read_stats_path,
                 nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs, nh_minimizer_data *md, nh_host_filter *hf, nh_stats *stats) {
-    if (!nh::host_filter_given(hf)) return nh_run_mdata(args, extras, min_base_quality, read_stats_path, read_stats, outs, n_outs, md, stats);
-    const int rc = nh::check_host(args, extras, min_base_quality, read_stats_path, outs, n_outs, md, hf);  // (before any device is touched)
-    if (rc) return rc;
-    if (!extras)
-        return run_devices(args, stats, nullptr, nullptr, false, nullptr, nullptr, min_base_quality, read_stats_path, read_stats, outs, n_outs, md, hf);
-    return run_devices(args, stats, extras->human_out1, extras->human_out2, extras->mask != 0, extras->calls, extras->human_ids,
-                       min_base_quality, read_stats_path, read_stats, outs, n_outs, md, hf);
+    return run_standalone(
+        nh::make_request(nh::RunRequest::RUN, args, extras, nullptr, nullptr, min_base_quality, read_stats_path, read_stats, outs, n_outs, md, hf), stats);
 }
 
 }  // extern "C"

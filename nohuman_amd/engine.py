@@ -96,55 +96,47 @@ def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
     else:
         a.n_devices = 0
         a.device_ids = None
+    return _run_entry("nh_run", (), lambda: _taxo_nodes(os.fspath(db_dir)), a, human_out1, human_out2, mask, calls, human_ids,
+                      min_base_quality, read_stats, taxon_outs, report_minimizer_data, minimizer_table, minimizer_data, host_taxids,
+                      keep_taxids)
+
+
+def _run_entry(prefix, lead, nodes, a, human_out1, human_out2, mask, calls, human_ids, min_base_quality, read_stats, taxon_outs,
+               report_minimizer_data, minimizer_table, minimizer_data, host_taxids, keep_taxids) -> "_lib.nh_stats":
+    """run() and Engine.run(): the entry of the family `prefix` (nh_run / nh_run_engine, behind the arguments `lead`: none / the
+    handle) that the options ask for -- the first of host, mdata, taxa, rstats, minq, ex, mask, split, none that has one -- and
+    what it hands back, on the stats.  nodes(): the nodes of the taxonomy, asked only where minimizer data wants a list."""
+    fn = lambda suffix: getattr(_lib.lib(), prefix + suffix)
     s = _lib.nh_stats()
-    if host_taxids or keep_taxids:
+    head = tuple(lead) + (C.byref(a),)
+    want_md = report_minimizer_data or minimizer_table is not None or minimizer_data is not None
+    if host_taxids or keep_taxids or want_md or taxon_outs or read_stats is not None or min_base_quality:
+        # the entries that take nh_run_minq's list and, each, one thing more: every one gets the list as far as its own last argument
+        x = _extras_or_none(mask, human_out1, human_out2, calls, human_ids)
         rs = _read_stats(read_stats) if read_stats is not None else None
         t = _taxon_outs(taxon_outs or [])
-        want_md = report_minimizer_data or minimizer_table is not None or minimizer_data is not None
-        md = _minimizer_data(report_minimizer_data, minimizer_table, minimizer_data, _taxo_nodes(os.fspath(db_dir))) if want_md else None
-        hf = _host_filter(host_taxids, keep_taxids)
-        _check(_lib.lib().nh_run_host(C.byref(a), _extras_or_none(mask, human_out1, human_out2, calls, human_ids),
-                                      _minq(min_base_quality), _path_or_none(rs.path) if rs else None,
-                                      C.byref(rs.raw) if rs else None, t if len(t) else None, len(t),
-                                      C.byref(md) if md is not None else None, C.byref(hf), C.byref(s)))
+        md = _minimizer_data(report_minimizer_data, minimizer_table, minimizer_data, nodes()) if want_md else None
+        hf = _host_filter(host_taxids, keep_taxids) if host_taxids or keep_taxids else None
+        tail = [x, _minq(min_base_quality), _path_or_none(rs.path) if rs else None, C.byref(rs.raw) if rs else None,
+                t if len(t) else None, len(t), C.byref(md) if md is not None else None, C.byref(hf) if hf is not None else None]
+        suffix, n = (("_host", 8) if hf is not None else ("_mdata", 7) if want_md else ("_taxa", 6) if taxon_outs else
+                     ("_rstats", 4) if rs is not None else ("_minq", 2))
+        _check(fn(suffix)(*head, *tail[:n], C.byref(s)))
         if md is not None:
             _minimizer_data_out(md, minimizer_data)
         if taxon_outs:
-            s.taxon_fragments = [int(x.fragments) for x in t]
-        s.host_fragments, s.spared_fragments = int(hf.host_fragments), int(hf.spared_fragments)
-    elif report_minimizer_data or minimizer_table is not None or minimizer_data is not None:
-        rs = _read_stats(read_stats) if read_stats is not None else None
-        t = _taxon_outs(taxon_outs or [])
-        md = _minimizer_data(report_minimizer_data, minimizer_table, minimizer_data, _taxo_nodes(os.fspath(db_dir)))
-        _check(_lib.lib().nh_run_mdata(C.byref(a), _extras_or_none(mask, human_out1, human_out2, calls, human_ids),
-                                       _minq(min_base_quality), _path_or_none(rs.path) if rs else None,
-                                       C.byref(rs.raw) if rs else None, t if len(t) else None, len(t), C.byref(md), C.byref(s)))
-        _minimizer_data_out(md, minimizer_data)
-        if taxon_outs:
-            s.taxon_fragments = [int(x.fragments) for x in t]
-    elif taxon_outs:
-        rs = _read_stats(read_stats) if read_stats is not None else None
-        t = _taxon_outs(taxon_outs)
-        _check(_lib.lib().nh_run_taxa(C.byref(a), _extras_or_none(mask, human_out1, human_out2, calls, human_ids),
-                                      _minq(min_base_quality), _path_or_none(rs.path) if rs else None,
-                                      C.byref(rs.raw) if rs else None, t, len(t), C.byref(s)))
-        s.taxon_fragments = [int(x.fragments) for x in t]
-    elif read_stats is not None:
-        rs = _read_stats(read_stats)
-        _check(_lib.lib().nh_run_rstats(C.byref(a), _extras_or_none(mask, human_out1, human_out2, calls, human_ids),
-                                        _minq(min_base_quality), _path_or_none(rs.path), C.byref(rs.raw), C.byref(s)))
-    elif min_base_quality:
-        _check(_lib.lib().nh_run_minq(C.byref(a), _extras_or_none(mask, human_out1, human_out2, calls, human_ids),
-                                      _minq(min_base_quality), C.byref(s)))
+            s.taxon_fragments = [int(o.fragments) for o in t]
+        if hf is not None:
+            s.host_fragments, s.spared_fragments = int(hf.host_fragments), int(hf.spared_fragments)
     elif calls is not None or human_ids is not None:
         x = _extras(mask, human_out1, human_out2, calls, human_ids)
-        _check(_lib.lib().nh_run_ex(C.byref(a), C.byref(x), C.byref(s)))
+        _check(fn("_ex")(*head, C.byref(x), C.byref(s)))
     elif mask:
-        _check(_lib.lib().nh_run_mask(C.byref(a), _path_or_none(human_out1), _path_or_none(human_out2), C.byref(s)))
+        _check(fn("_mask")(*head, _path_or_none(human_out1), _path_or_none(human_out2), C.byref(s)))
     elif human_out1 is not None or human_out2 is not None:
-        _check(_lib.lib().nh_run_split(C.byref(a), _path_or_none(human_out1), _path_or_none(human_out2), C.byref(s)))
+        _check(fn("_split")(*head, _path_or_none(human_out1), _path_or_none(human_out2), C.byref(s)))
     else:
-        _check(_lib.lib().nh_run(C.byref(a), C.byref(s)))
+        _check(fn("")(*head, C.byref(s)))
     return s
 
 
@@ -683,55 +675,6 @@ class Engine:
         a.device_ids = None
         a.out_codec = int(out_codec)
         a.codec_threads = int(codec_threads)
-        s = _lib.nh_stats()
-        if host_taxids or keep_taxids:
-            rs = _read_stats(read_stats) if read_stats is not None else None
-            t = _taxon_outs(taxon_outs or [])
-            want_md = report_minimizer_data or minimizer_table is not None or minimizer_data is not None
-            md = _minimizer_data(report_minimizer_data, minimizer_table, minimizer_data, self.info.node_count) if want_md else None
-            hf = _host_filter(host_taxids, keep_taxids)
-            _check(self._L.nh_run_engine_host(self._h, C.byref(a), _extras_or_none(mask, human_out1, human_out2, calls, human_ids),
-                                              _minq(min_base_quality), _path_or_none(rs.path) if rs else None,
-                                              C.byref(rs.raw) if rs else None, t if len(t) else None, len(t),
-                                              C.byref(md) if md is not None else None, C.byref(hf), C.byref(s)))
-            if md is not None:
-                _minimizer_data_out(md, minimizer_data)
-            if taxon_outs:
-                s.taxon_fragments = [int(x.fragments) for x in t]
-            s.host_fragments, s.spared_fragments = int(hf.host_fragments), int(hf.spared_fragments)
-        elif report_minimizer_data or minimizer_table is not None or minimizer_data is not None:
-            rs = _read_stats(read_stats) if read_stats is not None else None
-            t = _taxon_outs(taxon_outs or [])
-            md = _minimizer_data(report_minimizer_data, minimizer_table, minimizer_data, self.info.node_count)
-            _check(self._L.nh_run_engine_mdata(self._h, C.byref(a), _extras_or_none(mask, human_out1, human_out2, calls, human_ids),
-                                               _minq(min_base_quality), _path_or_none(rs.path) if rs else None,
-                                               C.byref(rs.raw) if rs else None, t if len(t) else None, len(t), C.byref(md), C.byref(s)))
-            _minimizer_data_out(md, minimizer_data)
-            if taxon_outs:
-                s.taxon_fragments = [int(x.fragments) for x in t]
-        elif taxon_outs:
-            rs = _read_stats(read_stats) if read_stats is not None else None
-            t = _taxon_outs(taxon_outs)
-            _check(self._L.nh_run_engine_taxa(self._h, C.byref(a), _extras_or_none(mask, human_out1, human_out2, calls, human_ids),
-                                              _minq(min_base_quality), _path_or_none(rs.path) if rs else None,
-                                              C.byref(rs.raw) if rs else None, t, len(t), C.byref(s)))
-            s.taxon_fragments = [int(x.fragments) for x in t]
-        elif read_stats is not None:
-            rs = _read_stats(read_stats)
-            _check(self._L.nh_run_engine_rstats(self._h, C.byref(a), _extras_or_none(mask, human_out1, human_out2, calls, human_ids),
-                                                _minq(min_base_quality), _path_or_none(rs.path), C.byref(rs.raw), C.byref(s)))
-        elif min_base_quality:
-            _check(self._L.nh_run_engine_minq(self._h, C.byref(a), _extras_or_none(mask, human_out1, human_out2, calls, human_ids),
-                                              _minq(min_base_quality), C.byref(s)))
-        elif calls is not None or human_ids is not None:
-            x = _extras(mask, human_out1, human_out2, calls, human_ids)
-            _check(self._L.nh_run_engine_ex(self._h, C.byref(a), C.byref(x), C.byref(s)))
-        elif mask:
-            _check(self._L.nh_run_engine_mask(self._h, C.byref(a), _path_or_none(human_out1), _path_or_none(human_out2),
-                                              C.byref(s)))
-        elif human_out1 is not None or human_out2 is not None:
-            _check(self._L.nh_run_engine_split(self._h, C.byref(a), _path_or_none(human_out1), _path_or_none(human_out2),
-                                               C.byref(s)))
-        else:
-            _check(self._L.nh_run_engine(self._h, C.byref(a), C.byref(s)))
-        return s
+        return _run_entry("nh_run_engine", (self._h,), lambda: self.info.node_count, a, human_out1, human_out2, mask, calls, human_ids,
+                          min_base_quality, read_stats, taxon_outs, report_minimizer_data, minimizer_table, minimizer_data, host_taxids,
+                          keep_taxids)
