@@ -224,7 +224,10 @@ typedef enum nh_codec {
      * 28-byte EOF member; an empty text is the EOF member alone.  Any gzip reader takes it; htslib tools seek in it, and
      * this library's GPU reader finds its chunks by the headers.  Encoded like NH_CODEC_GZIP: on the GPU where nh_run has one
      * (NOHUMAN_GZIP=host: zlib level 6 on `threads` workers), accepted wherever a codec is.  No .gzi index is written. */
-    NH_CODEC_BGZF = 5
+    NH_CODEC_BGZF = 5,
+    /* BAM output (nh_run* only; "BAM output" below): every record output of the run is a BAM file -- the input's header and the
+     * selected records of the input, byte for byte, in NH_CODEC_BGZF's framing.  in1 must be a BAM file. */
+    NH_CODEC_BAM = 6
 } nh_codec;
 
 /*
@@ -266,7 +269,7 @@ int nh_fastx_scan(const char *path, uint64_t *n_records, uint64_t *n_bases, uint
  * records are transcoded on the GPU to the canonical FASTQ `samtools fastq` would write (as far as that is recalled: DESIGN.md
  * 6.16) and everything behind the reader runs on that text: "@name\nSEQ\n+\nQUAL\n", bases from "=ACMGRSVTWYHKDBN", qualities
  * + 33 (absent qualities, first byte 0xFF: every quality '"'), reverse-strand records (flag 0x10) reverse-complemented with their
- * qualities reversed, no tags in the header.  Secondary and supplementary records (0x100, 0x800) and records without bases are
+ * qualities reversed, no tags in the header (the tags survive only in BAM output, NH_CODEC_BAM below).  Secondary and supplementary records (0x100, 0x800) and records without bases are
  * skipped; a paired record (0x1) fails the run with NH_EIO, as every malformed record does, with the record's ordinal in the
  * message.  A BAM in1 with an in2, or a BAM in2, is NH_EINVAL before any device is touched.
  *
@@ -294,12 +297,40 @@ int nh_bam_scan(const char *path, uint32_t threads, nh_bam_info *info);
  * and the others are.  NOHUMAN_BAM_SPAN: the bytes of text one wave writes of a long record (a test and tuning knob). */
 int nh_bam_to_fastq_device(nh_engine *e, const void *d_bam, uint64_t bam_len, const void *d_table, uint64_t n_records,
                            void *d_text, uint64_t text_cap, uint64_t text_len, int *error_bits, void *stream);
+/*
+ * BAM output.  With out_codec = NH_CODEC_BAM and a BAM in1, out1 (and human_out1 of a split run) is a BAM file: the input's
+ * header copied byte for byte (magic, l_text, text, n_ref, references; no @PG line is added), then the selected records of the
+ * input in input order, each copied byte for byte with its block_size field -- tags (MM / ML, mv, RG ...), CIGAR, flags and a
+ * reverse-strand record's orientation untouched -- framed as BGZF and closed by bgzip's EOF member.  Which records are selected
+ * is the FASTQ outputs' rule: out1 gets the non-host records (with keep_human the host records), human_out1 the host records; a
+ * host selection (nh_host_filter) is followed as the FASTQ outputs follow it.  No record selected: the header and the EOF
+ * member, still a valid BAM.  The records the reader skips -- secondary, supplementary, without bases -- are never classified
+ * and are written NOWHERE (nh_bam_scan counts them).  No call is added to a record: it is in `calls` and kraken_output.  Every
+ * other output (kraken_output, report, calls, human_ids, read statistics, minimizer data, nh_stats) is byte for byte what the
+ * same run with a FASTQ codec writes.  The records are selected and compacted on the GPU from the BAM bytes the reader holds
+ * there (nh_bamout.hip) and encoded by NH_CODEC_BGZF's encoders.
+ * NH_EINVAL, before any device is touched and with nothing created: NH_CODEC_BAM with an in1 that is not a BAM file, with in2,
+ * in a masked run, with per-taxon outputs (the last two: not built yet).  nh_compress_file* refuse it: a FASTQ file cannot be
+ * made a BAM.
+ *
+ * nh_bam_select_device: the select-and-compact kernels alone, on the engine's device and `stream`.  d_bam / bam_len as for
+ * nh_bam_to_fastq_device; d_table: the reader's table, two uint64 a record, of which the first -- the offset of the record's
+ * block_size field in d_bam -- is used; d_results: n_records nh_result; want: 0 selects the records with call == 0, 1 those with
+ * call != 0.  d_out (out_cap bytes, 4-byte aligned) receives the selected records, 4 + block_size bytes each, contiguous and in
+ * table order; *d_total (device memory) their bytes.  error_bits: one int in device memory, zeroed by the caller: a record whose
+ * block_size field or whose bytes [offset, offset + 4 + block_size) do not lie inside [0, bam_len) sets bit 1 and is not
+ * written (the others are); a total above out_cap sets bit 4, nothing is written and *d_total is 0.  The call waits for
+ * `stream` (its scratch is the call's own).  NOHUMAN_BAM_SPAN: the bytes one wave copies of a long record (test / tuning knob).
+ */
+int nh_bam_select_device(nh_engine *e, const void *d_bam, uint64_t bam_len, const void *d_table, uint64_t n_records,
+                         const void *d_results, int want, void *d_out, uint64_t out_cap, uint64_t *d_total, int *error_bits,
+                         void *stream);
 /* Output compression stage: replaces CompressionFormat::compress
  * (/root/reference/src/compression.rs:182-200, called from src/main.rs:342-368).  Compresses file
  * `in` to file `out`; gzip runs block-parallel on `threads` workers like the reference's gzp
  * encoder (compression.rs:214-233) and produces one ordinary gzip member at level 6; bzip2 and xz
  * go through libbz2.so.1 / liblzma.so.5 (one thread / `threads` workers, preset 6, CRC64), zstd through
- * libzstd.so.1; NH_CODEC_BGZF is zlib level 6 per 65280-byte member on `threads` workers; NH_CODEC_NONE copies.  Parity target is the decompressed content and
+ * libzstd.so.1; NH_CODEC_BGZF is zlib level 6 per 65280-byte member on `threads` workers; NH_CODEC_NONE copies; NH_CODEC_BAM is NH_EINVAL (a FASTQ file cannot be made a BAM).  Parity target is the decompressed content and
  * the container magic (compression.rs:282-288).  Needs no GPU. */
 int nh_compress_file(const char *in, const char *out, int codec, uint32_t threads);
 /* The gzip case of that stage on the GPU (nohuman_amd/csrc/nh_deflate.hip; replaces gzip_compress,

@@ -192,6 +192,7 @@ SYMBOLS = {
                                 C.POINTER(C.c_uint64)]),
     "nh_bam_scan": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(nh_bam_info)]),
     "nh_bam_to_fastq_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, _P, C.c_uint64, C.c_uint64, _P, _P]),
+    "nh_bam_select_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, _P, C.c_int, _P, C.c_uint64, _P, _P, _P]),
     "nh_run": (C.c_int, [C.POINTER(nh_run_args), C.POINTER(nh_stats)]),
     "nh_run_engine":(C.c_int, [_P, C.POINTER(nh_run_args), C.POINTER(nh_stats)]),
     "nh_run_split": (C.c_int, [C.POINTER(nh_run_args), C.c_char_p, C.c_char_p, C.POINTER(nh_stats)]),

@@ -55,6 +55,12 @@ void BamStream::compact() {
 }
 
 int BamStream::read_header(std::string &err) {
+    header_.clear();
+    size_t kept = pos_;  // the header's bytes up to here are in header_
+    auto keep = [&] {
+        header_.append((const char *)win_.data() + kept, pos_ - kept);
+        kept = pos_;
+    };
     auto need = [&](size_t n) -> int {
         const int rc = ensure(n, err);
         if (rc == 0) err = name_ + ": the BAM stream ends inside the header";
@@ -89,8 +95,13 @@ int BamStream::read_header(std::string &err) {
         pos_ += 4;
         if (need((size_t)l_name + 4)) return -1;
         pos_ += (size_t)l_name + 4;
-        if (pos_ > (8u << 20)) compact();
+        if (pos_ > (8u << 20)) {
+            keep();
+            compact();
+            kept = 0;
+        }
     }
+    keep();
     return 0;
 }
 
@@ -397,6 +408,9 @@ public:
         hb.text.set_size((size_t)text);
         hb.dev_text = (const uint8_t *)s.d_text;
         hb.dev_device = s.dev;
+        hb.dev_bam = s.d_bam;
+        hb.dev_bam_table = s.d_tab;
+        hb.bam_len = b1 - b0;
         hb.host_text_valid = false;
         {
             std::lock_guard<std::mutex> lk(mu_);
@@ -414,6 +428,7 @@ public:
     }
 
     const BamCounts &counts() const { return stream_.counts(); }
+    std::string take_header() { return stream_.take_header(); }
 
     void close() {
         if (!open_) return;
@@ -524,6 +539,7 @@ int BamReader::open(const char *path, const int *devices, int n_devices, std::st
 }
 void BamReader::next_batch(HalfBatch &hb, size_t max_recs, size_t max_text) { impl_->next_batch(hb, max_recs, max_text); }
 const BamCounts &BamReader::counts() const { return impl_->counts(); }
+std::string BamReader::take_header() { return impl_->take_header(); }
 void BamReader::close() { impl_->close(); }
 
 }  // namespace nh

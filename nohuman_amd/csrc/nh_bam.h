@@ -17,6 +17,8 @@
 #include "nh_fastx.h"
 #ifndef NH_BAM_HOST_ONLY
 #include <hip/hip_runtime.h>
+
+#include "nohuman_engine.h"
 #endif
 
 namespace nh {
@@ -54,6 +56,9 @@ public:
     }
     // the magic, the text and the references: 0, or -1 with err set
     int read_header(std::string &err);
+    // the header read_header() stepped over, byte for byte (BAM output copies it); take_header() moves it out
+    const std::string &header_bytes() const { return header_; }
+    std::string take_header() { return std::move(header_); }
     // The next KEPT record (secondary, supplementary and empty ones are counted and stepped over): 1 and *r (offsets into
     // data(), valid until the next compact()), 0 at the end of the stream, -1 malformed (err set: the record's ordinal).
     int next(BamRec *r, std::string &err);
@@ -70,6 +75,7 @@ private:
     ReadFn read_;
     std::string name_;
     std::vector<uint8_t> win_;
+    std::string header_;
     size_t pos_ = 0, len_ = 0;
     bool eof_ = false;
     BamCounts cnt_;
@@ -96,12 +102,15 @@ public:
     ~BamReader();
     BamReader(const BamReader &) = delete;
     BamReader &operator=(const BamReader &) = delete;
-    // devices: the GPUs of the run -- batch b is transcoded on devices[b mod n] and says so (HalfBatch::dev_device)
+    // devices: the GPUs of the run -- batch b is transcoded on devices[b mod n] and says so (HalfBatch::dev_device); its BAM bytes
+    // and its table stay there until the batch is released (HalfBatch::dev_bam, dev_bam_table, bam_len: BAM output reads them)
     int open(const char *path, const int *devices, int n_devices, std::string &err, unsigned gz_threads = 0);
     // up to max_recs records, cut after the record that reaches max_text bytes of FASTQ text (BlockReader::next_batch's rule);
     // hb.eof at the end of the input, hb.error on malformed input or a device failure
     void next_batch(HalfBatch &hb, size_t max_recs, size_t max_text);
     const BamCounts &counts() const;
+    // the input's header, byte for byte: handed out once (BAM output writes it in front of each file), empty from then on
+    std::string take_header();
     void close();  // waits until every batch handed out has been released
 
 private:
@@ -110,7 +119,7 @@ private:
 
 // k_bam_fastq (nh_bam.hip).  table: two uint64 a record -- where its block_size field lies in bam, where its '@' lies in text.
 // error: one word, BAM_ERR_* are set in it.  span 0: NOHUMAN_BAM_SPAN, else the default.
-enum { BAM_ERR_FIELDS = 1, BAM_ERR_TEXT = 2 };
+enum { BAM_ERR_FIELDS = 1, BAM_ERR_TEXT = 2, BAM_ERR_OUT = 4 };  // (BAM_ERR_OUT: nh_bam_select_device's total above its buffer)
 struct BamFastqArgs {
     const uint8_t *bam;
     uint64_t bam_len;
@@ -122,6 +131,30 @@ struct BamFastqArgs {
     uint32_t span;
 };
 hipError_t launch_bam_fastq(const BamFastqArgs &a, hipStream_t stream);
+
+// BAM output (nh_bamout.hip; NH_CODEC_BAM): the records of a batch's BAM bytes selected by their call and compacted, each copied
+// whole (4 + block_size bytes), in table order, for up to two outputs in one pass: output o takes the records whose host-ness
+// (res[i].call != 0) is want[o].  table: the reader's, two uint64 a record, the first -- where the record's block_size field
+// lies in bam -- is used.  A record whose block_size field or whose bytes do not lie inside [0, bam_len) sets err_fields in
+// *error and is written nowhere; an output whose total is above its cap sets err_total, gets nothing and total 0.
+struct BamOutArgs {
+    const uint8_t *bam;
+    uint64_t bam_len;
+    const uint64_t *table;
+    uint64_t n, nblk;         // nblk = bam_out_blocks(n)
+    const nh_result *res;     // n results
+    int n_out;                // 1 or 2
+    int want[2];
+    char *out[2];
+    uint64_t cap[2];
+    uint64_t *blk;            // n_out * nblk words of scratch
+    uint64_t *total;          // 2 words
+    int *error;
+    int err_fields, err_total;
+    uint32_t span;            // 0: NOHUMAN_BAM_SPAN, else the default
+};
+uint64_t bam_out_blocks(uint64_t n);
+hipError_t launch_bam_out(const BamOutArgs &a, hipStream_t stream);
 #endif
 
 }  // namespace nh

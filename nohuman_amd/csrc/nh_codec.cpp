@@ -653,8 +653,9 @@ StreamEncoder *make_encoder(int codec, int fd, unsigned threads, const char *nam
         case NH_CODEC_NONE:
             return new PlainEncoder(fd, name);
         case NH_CODEC_GZIP:
-        case NH_CODEC_BGZF: {  // (the same choice between the two encoders for both containers)
-            const bool bgzf = codec == NH_CODEC_BGZF;
+        case NH_CODEC_BGZF:
+        case NH_CODEC_BAM: {  // (the same choice between the two encoders for both containers; a BAM file is BGZF around BAM bytes)
+            const bool bgzf = codec != NH_CODEC_GZIP;
             const char *how = getenv("NOHUMAN_GZIP");
             if (device >= 0 && !(how && !strcmp(how, "host"))) {
                 StreamEncoder *e = make_gpu_gzip_encoder(fd, device, name, bgzf);
@@ -699,6 +700,7 @@ StreamEncoder *make_encoder(int codec, int fd, unsigned threads, const char *nam
 
 int compress_file(const char *in, const char *out, int codec, unsigned threads, int device = -1) {
     if (!in || !out) return set_error(NH_EINVAL, "nh_compress_file: null path");
+    if (codec == NH_CODEC_BAM) return set_error(NH_EINVAL, "nh_compress_file: codec %d (BAM) is an output of nh_run on a BAM input only: a FASTQ file cannot be made a BAM", codec);
     if (codec != NH_CODEC_NONE && codec != NH_CODEC_GZIP && codec != NH_CODEC_BZIP2 && codec != NH_CODEC_XZ &&
         codec != NH_CODEC_ZSTD && codec != NH_CODEC_BGZF)
         return set_error(NH_EINVAL, "nh_compress_file: unknown codec %d", codec);

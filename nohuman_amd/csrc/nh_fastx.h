@@ -154,6 +154,12 @@ struct HalfBatch {  // the records one input file contributes to a batch
     const uint8_t *dev_text = nullptr;
     int dev_device = -1;
     bool host_text_valid = true;
+    // A batch of the BAM reader (nh_bam.h) besides: the BAM bytes its records were transcoded from (bam_len of them) and the
+    // reader's table -- two uint64 a record of `recs`, the first where its block_size field lies in dev_bam -- in the memory of
+    // dev_device, valid until release().  Only BamReaderImpl sets them; BAM output (nh_bamout.hip) reads them.
+    const uint8_t *dev_bam = nullptr;
+    const uint64_t *dev_bam_table = nullptr;
+    size_t bam_len = 0;
     std::function<void()> release;
     void reset() {
         if (release) {
@@ -163,6 +169,9 @@ struct HalfBatch {  // the records one input file contributes to a batch
         dev_text = nullptr;
         dev_device = -1;
         host_text_valid = true;
+        dev_bam = nullptr;
+        dev_bam_table = nullptr;
+        bam_len = 0;
         text.clear();
         recs.clear();
         format = FMT_AUTO;

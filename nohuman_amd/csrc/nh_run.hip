@@ -423,6 +423,7 @@ struct Slot {  // pinned host + device buffers of one in-flight batch
     BuiltOut mask;   // masked runs (nh_run_mask): every record per mate; totals: bytes[2], FAST blocks[2]
     BuiltOut lists;  // read lists (nh_run_ex): the calls table [0] and the human ids [1]; totals: bytes[2], lines[2]
     BuiltOut taxon;  // per-taxon outputs (nh_run_taxa): one buffer a mate, K bins in it; totals: start[2][K], bytes[2][K]
+    BuiltOut bam;    // BAM output (NH_CODEC_BAM): the selected records of out1 [0] and, a split run, of human_out1 [1]; totals: bytes[2]
     // runs with a minimum base quality (nh_run_minq): the text-sized buffer the classifier reads instead of d_text -- the
     // sequences with 'N' where the quality is low (nh_qmask.hip; the record table tells where the qualities lie) -- allocated
     // when first needed, and the masked bases of the slot's batches, read once, at the end of the run
@@ -577,7 +578,7 @@ static int slot_reserve_qmask(Slot &s, size_t ntext, size_t nrec) {
 static void slot_free(Slot &s) {
     if (!s.e) return;
     (void)dev_set(s.e->device);
-    for (BuiltOut *o : {&s.human, &s.mask, &s.lists, &s.taxon}) {
+    for (BuiltOut *o : {&s.human, &s.mask, &s.lists, &s.taxon, &s.bam}) {
         for (void *p : {(void *)o->h_out[0], (void *)o->h_out[1], (void *)o->h_total})
             if (p) (void)hipHostFree(p);
         for (void *p : {o->d_blk, (void *)o->d_out[0], (void *)o->d_out[1]})
@@ -701,6 +702,23 @@ struct RunState {
     // devices' counters), k_host_filter's time
     uint64_t host_frags = 0, spared_frags = 0;
     double host_kernel_ms = 0;
+    // BAM output (NOHUMAN_TRACE): the records and bytes the builder selected per output, its kernel time
+    uint64_t bam_records[2] = {0, 0}, bam_bytes[2] = {0, 0};
+    double bam_kernel_ms = 0;
+    // in1's reader says once what it reads: a BAM's header, byte for byte (BamReader::take_header), or "" for anything else.  A run
+    // with BAM output waits for it and writes it in front of every record output
+    std::mutex hdr_mu;
+    std::condition_variable hdr_cv;
+    bool hdr_set = false;
+    std::string bam_header;
+    void set_bam_header(std::string h) {
+        {
+            std::lock_guard<std::mutex> lk(hdr_mu);
+            bam_header = std::move(h);
+            hdr_set = true;
+        }
+        hdr_cv.notify_all();
+    }
     std::atomic<uint64_t> text_fetched{0};
     std::vector<uint64_t> dev_counts;  // per device {fragments, classified, bases, 0} as the writer saw them (checker)
     std::vector<uint64_t *> d_run_counters;  // per device: the counters the classify kernels of THIS run add to (HBM)
@@ -869,14 +887,18 @@ static void reader_main(const char *path, BoundedQueue<std::unique_ptr<HalfBatch
                         unsigned gz_threads, std::vector<int> gz_devices, bool device_reader, unsigned hybrid_threads) {
     const int gz_device = gz_devices.empty() ? -1 : gz_devices[0];
     // BAM: inflated and chained on the host, transcoded to FASTQ text on the GPU (nh_bam.h); the batches are born there
-    if (bam_wants(path)) {
+    const bool is_bam = bam_wants(path);
+    if (which == 0 && !is_bam) rs->set_bam_header("");
+    if (is_bam) {
         BamReader br;
         std::string err;
         if (gz_devices.empty() || br.open(path, gz_devices.data(), (int)gz_devices.size(), err, gz_threads) != 0) {
             rs->fail(NH_EIO, gz_devices.empty() ? std::string(path) + ": BAM input needs a device" : err);
+            if (which == 0) rs->set_bam_header("");
             out->close();
             return;
         }
+        if (which == 0) rs->set_bam_header(br.take_header());
         host_read(br, out, rs, pool, clk, which, batch_frags, batch_text, 0);
         if (getenv("NOHUMAN_TRACE")) {
             const BamCounts &c = br.counts();
@@ -1313,9 +1335,26 @@ static int check_mdata_args(const RunRequest &r) {
     return check_files(r, F_MDATA);
 }
 
+// The container of the record outputs: a codec there is none of, and what BAM output (NH_CODEC_BAM: the selected records of a BAM
+// in1, copied) does not go with -- a second input, a masked run, per-taxon outputs (the last two: not built yet), an in1 that is
+// no BAM file.  (A request without arguments is refused by its entry.)
+static int check_out_codec(const RunRequest &r) {
+    const nh_run_args *a = r.a;
+    if (!a) return NH_OK;
+    if (a->out_codec < NH_CODEC_NONE || a->out_codec > NH_CODEC_BAM) return set_error(NH_EINVAL, "nh_run: unknown out_codec %d", a->out_codec);
+    if (a->out_codec != NH_CODEC_BAM) return NH_OK;
+    if (a->in2) return set_error(NH_EINVAL, "nh_run: BAM output (out_codec %d) with in2 %s: BAM input is single-end, so is BAM output", NH_CODEC_BAM, a->in2);
+    if (r.mask) return set_error(NH_EINVAL, "nh_run_mask: BAM output (out_codec %d) of a masked run is not supported: a masked record is not a record of the input", NH_CODEC_BAM);
+    if (r.n_touts) return set_error(NH_EINVAL, "nh_run_taxa: BAM output (out_codec %d) with per-taxon outputs is not supported", NH_CODEC_BAM);
+    if (!a->in1 || !bam_wants(a->in1))
+        return set_error(NH_EINVAL, "nh_run: BAM output (out_codec %d) needs a BAM in1: %s is not a BAM file, and a FASTQ record has no BAM record to copy",
+                         NH_CODEC_BAM, a->in1 ? a->in1 : "(null)");
+    return NH_OK;
+}
+
 // Every entry's checks, in one order: the host selection's own, the minimum base quality (the highest printable quality is '~',
 // Phred 93), the extras (the mask or the human outputs, then the read lists), the read statistics' table, the selectors, the
-// minimizer data.  What an entry cannot ask for is not set in its request and checks nothing.
+// minimizer data, the container.  What an entry cannot ask for is not set in its request and checks nothing.
 int check_request(const RunRequest &r) {
     int rc = check_host_filter(r.hf);
     if (!rc && r.minq > 93) rc = set_error(NH_EINVAL, "minimum base quality %u is not in 0..93 (Phred+33)", r.minq);
@@ -1323,6 +1362,7 @@ int check_request(const RunRequest &r) {
     if (!rc) rc = check_rstats_args(r);
     if (!rc) rc = check_taxon_args(r);
     if (!rc) rc = check_mdata_args(r);
+    if (!rc) rc = check_out_codec(r);
     return rc;
 }
 // BAM input is single-end: NH_EINVAL -- before any device is touched -- for a BAM in1 beside an in2, and for a BAM in2
@@ -1625,7 +1665,12 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
     const uint32_t minq = r.minq;
     nh_minimizer_data *const md = r.md;
     nh_host_filter *const hf = r.hf;
-    const bool split = r.hout1 != nullptr;
+    // BAM output (check_request has passed it: a BAM in1 alone, neither masked nor with selectors): out1 and, a split run, human_out1
+    // receive records of the input selected on the device (nh_bamout.hip); none of the FASTQ record builders runs
+    const bool bamout = a->out_codec == NH_CODEC_BAM;
+    const bool split_files = r.hout1 != nullptr;  // a split run: the human outputs are opened, flushed, closed
+    const bool split = split_files && !bamout;     // ... and their records built as FASTQ text (nh_split.hip)
+    const int n_bout = split_files ? 2 : 1;        // BAM output: the builder's outputs
     const int K = (int)r.n_touts;  // per-taxon outputs: the selectors
     const bool taxa = K > 0;
     const bool lists = calls || ids;
@@ -1677,8 +1722,8 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
             if ((rc = check_collision(files, c, inputs))) return rc;
         }
     }
-    const bool gzip_family = a->out_codec == NH_CODEC_GZIP || a->out_codec == NH_CODEC_BGZF;  // the codecs the GPU encodes
-    if (a->out_codec < NH_CODEC_NONE || a->out_codec > NH_CODEC_BGZF)
+    const bool gzip_family = a->out_codec == NH_CODEC_GZIP || a->out_codec == NH_CODEC_BGZF || bamout;  // the codecs the GPU encodes
+    if (a->out_codec < NH_CODEC_NONE || a->out_codec > NH_CODEC_BAM)
         return set_error(NH_EINVAL, "nh_run: unknown out_codec %d", a->out_codec);
     RunFiles files;
     if ((rc = open_run_files(files, r, engines, rs.paired, rs.want_k))) return rc;
@@ -1707,7 +1752,9 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
     // codecs, for the ids of --output lines and for the suffix of classified-out headers; gzip outputs encoded on the GPU
     // take the kept records from HBM (a record that needs reformatting -- CRLF, "+id" -- makes the writer fetch its batch).
     // A masked run builds every output record on the device (the split side as well): only --output lines need the bytes.
-    const bool host_text_wanted = mask ? rs.want_k || G > 1
+    // BAM output takes nothing from the text at all: its records are the input's BAM bytes, which the reader keeps in HBM.
+    const bool host_text_wanted = bamout ? rs.want_k
+                                  : mask ? rs.want_k || G > 1
                                        : !(gzip_family && o1.enc && o1.enc->takes_device_spans() &&
                                            (!rs.paired || (o2.enc && o2.enc->takes_device_spans()))) ||
                                              rs.want_k || a->keep_human != 0 || G > 1;  // (G > 1: a batch's slot and its file's encoder may sit on different GPUs)
@@ -1719,6 +1766,8 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
     // masked runs: the same for out1 / out2 -- one span a mate and batch, from HBM or copied to page-locked slot memory
     const bool mask_in_hbm = mask && G == 1 && o1.enc && o1.enc->takes_device_spans() &&
                              (!rs.paired || (o2.enc && o2.enc->takes_device_spans()));
+    // BAM output: the same for out1 / human_out1 -- one span an output and batch
+    const bool bam_in_hbm = bamout && G == 1 && o1.enc && o1.enc->takes_device_spans() && (!split_files || (h1.enc && h1.enc->takes_device_spans()));
     bool taxon_in_hbm = taxa && G == 1;
     for (int k = 0; k < K; k++)
         for (int m = 0; m < mates; m++) taxon_in_hbm = taxon_in_hbm && tx[m][k].enc && tx[m][k].enc->takes_device_spans();
@@ -1751,6 +1800,8 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
              (hipEventCreate(&slots[i].mask.ev[0]) != hipSuccess || hipEventCreate(&slots[i].mask.ev[1]) != hipSuccess)) ||
             (lists && getenv("NOHUMAN_TRACE") &&
              (hipEventCreate(&slots[i].lists.ev[0]) != hipSuccess || hipEventCreate(&slots[i].lists.ev[1]) != hipSuccess)) ||
+            (bamout && getenv("NOHUMAN_TRACE") &&
+             (hipEventCreate(&slots[i].bam.ev[0]) != hipSuccess || hipEventCreate(&slots[i].bam.ev[1]) != hipSuccess)) ||
             (taxa && getenv("NOHUMAN_TRACE") &&
              (hipEventCreate(&slots[i].taxon.ev[0]) != hipSuccess || hipEventCreate(&slots[i].taxon.ev[1]) != hipSuccess)) ||
             (qm && getenv("NOHUMAN_TRACE") &&
@@ -1857,6 +1908,23 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
     std::thread t2;
     if (rs.paired)
         t2 = std::thread(reader_main, a->in2, &q2, &rs, &pool2, &clk, 1, BATCH_FRAGS, BATCH_TEXT, gz_threads2, devs2, dev_reader2, hybrid_threads);
+    // BAM output: the input's header, as the reader found it, is the first thing in every record output (a host span: the
+    // encoder stages it), before the writer hands on the first batch's records
+    if (bamout) {
+        std::string hdr;
+        {
+            std::unique_lock<std::mutex> lk(rs.hdr_mu);
+            rs.hdr_cv.wait(lk, [&] { return rs.hdr_set; });
+            hdr.swap(rs.bam_header);
+        }
+        if (hdr.empty()) rs.fail(NH_EIO, std::string(a->in1) + ": no BAM header to copy (the file is not the BAM it was when the run was checked)");
+        for (OutFile *f : {&o1, split_files ? &h1 : (OutFile *)nullptr}) {
+            if (!f || rs.failed()) continue;
+            int hrc = f->enc->write(hdr.data(), hdr.size());
+            if (!hrc) hrc = f->enc->settle();
+            if (hrc) rs.fail(hrc, g_last_error);
+        }
+    }
 
     // writer: consumes batches in order; each arrives after its stream was synchronised.  Two stages: the WRITER
     // waits for the batch's stream, decides and formats (span lists, nothing is copied); the FLUSHER writes the spans
@@ -1914,13 +1982,18 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
                 // the kept records from there instead of a second trip over PCIe
                 // (a part that fetched its own host copy has its spans there: they are staged like any host memory)
                 // (a masked run's spans are the built text: in HBM, mapped here, or in the slot's page-locked copy)
-                if (o1.enc && !mask) o1.enc->map_device(b.h1->text.data(), b.len1, s.d_text, s.e->device, b.h1->host_text_valid);
+                if (o1.enc && !mask && !bamout) o1.enc->map_device(b.h1->text.data(), b.len1, s.d_text, s.e->device, b.h1->host_text_valid);
                 if (rs.paired && o2.enc && !mask)
                     o2.enc->map_device(b.h2->text.data(), b.len2, (const char *)s.d_text + base2w, s.e->device, b.h2->host_text_valid);
                 if (mask_in_hbm)
                     for (int m = 0; m < mates; m++) {
                         Spans &ms = m ? j->s2 : j->s1;
                         if (!ms.iov.empty()) (m ? o2 : o1).enc->map_device(ms.iov[0].iov_base, ms.iov[0].iov_len, s.mask.d_out[m], s.e->device, false);
+                    }
+                if (bam_in_hbm)  // (BAM output: the selected records of out1 in s1, of human_out1 in hs1, each one span)
+                    for (int o = 0; o < n_bout; o++) {
+                        Spans &bs = o ? j->hs1 : j->s1;
+                        if (!bs.iov.empty()) (o ? h1 : o1).enc->map_device(bs.iov[0].iov_base, bs.iov[0].iov_len, s.bam.d_out[o], s.e->device, false);
                     }
                 // the classified records that only exist in HBM: their span's address is the device buffer's, never read on the host
                 if (human_in_hbm)
@@ -1944,7 +2017,7 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
                 }
                 int wrc = o1.flush(j->s1);
                 if (!wrc && rs.want_k) wrc = ok.flush(j->sk);
-                if (!wrc && split) wrc = h1.flush(j->hs1);
+                if (!wrc && split_files) wrc = h1.flush(j->hs1);
                 for (int k = 0; k < K && !wrc; k++)
                     if (!j->ts[0][k].iov.empty()) wrc = tx[0][k].flush(j->ts[0][k]);
                 if (!wrc && calls) wrc = oc.flush(j->sc);
@@ -1991,7 +2064,7 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
                     // a batch whose text is only in HBM, and a kept record that must be rewritten (CRLF, "+id" line): fetch it
                     // (into a buffer of this part: the half itself may be in use by other parts -- Batch)
                     auto need_fetch = [&](const HalfBatch &hb) {
-                        if (hb.host_text_valid || mask) return false;
+                        if (hb.host_text_valid || mask || bamout) return false;
                         const size_t off = &hb == b.h1.get() ? b.off1 : b.off2;
                         const nh_result *const hres = s.host_res();
                         for (size_t i = 0; i < b.n; i++)
@@ -2012,7 +2085,26 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
                     }
                 }
                 if (!wrc) {
-                    format_batch(&rs, b, s, o1, o2, ok, !mask);
+                    format_batch(&rs, b, s, o1, o2, ok, !mask && !bamout);
+                    // BAM output: the records the builder selected, one span an output -- in HBM, or copied here
+                    add_event_ms(s.bam.ev, &rs.bam_kernel_ms);
+                    for (int o = 0; bamout && o < n_bout && !wrc; o++) {
+                        const size_t tot = (size_t)s.bam.h_total[o];
+                        rs.bam_bytes[o] += tot;
+                        const bool want_host = split_files ? o == 1 : a->keep_human != 0;
+                        for (size_t i = 0; i < b.n; i++) rs.bam_records[o] += (s.host_res()[i].call != 0) == want_host;
+                        if (!tot) continue;
+                        if (tot > s.bam.cap_out[o]) {
+                            wrc = set_error(NH_EDEVICE, "BAM-out builder: an output ends outside its buffer");
+                            break;
+                        }
+                        char *at = built_span(s.bam, o, tot, bam_in_hbm, rs, &wrc, "BAM-out buffers", "BAM records");
+                        if (o == 0) o1.add_raw(at, tot);
+                        else {
+                            j->hs1.iov.push_back({(void *)at, tot});
+                            j->hs1.is_scratch.push_back(0);
+                        }
+                    }
                     // a masked run's records: the text the builder made, one span a mate -- in HBM, or copied here
                     add_event_ms(s.mask.ev, &rs.mask_kernel_ms);
                     for (int m = 0; mask && m < mates && !wrc; m++) {
@@ -2173,7 +2265,7 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
                 std::unique_lock<std::mutex> lk(slot_mu);
                 if (home >= 0) {
                     si = home * NS + (int)(home_turn[(size_t)home]++ % (uint64_t)NS);
-                    if (slots[(size_t)si].busy)
+                    if (slots[(size_t)si].busy && !bamout)  // (BAM output: the builder reads the batch's BAM bytes where they lie)
                         for (int k = 0; k < NS * G; k++)
                             if (!slots[(size_t)k].busy) {
                                 si = k;
@@ -2229,6 +2321,13 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
                 rc = slot_reserve_rec(s, b.n * (size_t)mates);
                 // (the scratch: block offsets, totals and FAST counts, block flags: MaskArgs)
                 if (!rc) rc = built_reserve(s.mask, 3 * mask_blocks(b.n) + 4, out_cap, mates, "masked-out buffers");
+            }
+            if (!rc && bamout) {  // an output's records: the batch's BAM bytes at most
+                const size_t out_cap[2] = {b.h1->bam_len + 64, b.h1->bam_len + 64};
+                if (!b.h1->dev_bam || !b.h1->dev_bam_table || b.h1->dev_device != s.e->device)
+                    rc = set_error(NH_EDEVICE, "BAM output: a batch without its BAM bytes on the device that classifies it");
+                // (the scratch: block offsets of every output, totals: BamOutArgs)
+                if (!rc) rc = built_reserve(s.bam, (size_t)n_bout * bam_out_blocks(b.n) + 2, out_cap, n_bout, "BAM-out buffers");
             }
             if (!rc && lists) {
                 // a table line: "C\t", the id, then at most 1 + 20 + 1 + 21 + 1 + 3 * 11 bytes of numbers, separators and
@@ -2441,6 +2540,29 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
                 if (s.human.ev[1] && he == hipSuccess) he = hipEventRecord(s.human.ev[1], s.stream);
                 if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("classified-out builder: ") + hipGetErrorString(he));
             }
+            if (!rs.failed() && bamout) {  // the selected records of the input's BAM bytes, compacted behind the classifier on the same stream
+                BamOutArgs ba{};
+                ba.bam = b.h1->dev_bam;
+                ba.bam_len = b.h1->bam_len;
+                ba.table = b.h1->dev_bam_table + 2 * b.off1;  // (a part of a half: a range of its table)
+                ba.n = b.n;
+                ba.nblk = bam_out_blocks(b.n);
+                ba.res = d_host_res;
+                ba.n_out = n_bout;
+                ba.want[0] = split_files ? 0 : a->keep_human != 0;  // out1: the non-host records, with keep_human the host records
+                ba.want[1] = 1;                                      // human_out1: the host records
+                for (int o = 0; o < n_bout; o++) ba.out[o] = s.bam.d_out[o], ba.cap[o] = s.bam.cap_out[o];
+                ba.blk = (uint64_t *)s.bam.d_blk;
+                ba.total = s.bam.d_total = ba.blk + (uint64_t)n_bout * ba.nblk;
+                ba.error = s.e->d_error + LAUNCH_SLOTS;
+                ba.err_fields = ba.err_total = 256;
+                dev_check_ptr(ba.bam, s.e->device, "nh_run, a batch's BAM bytes");
+                dev_check_ptr(ba.table, s.e->device, "nh_run, a batch's BAM table");
+                if (s.bam.ev[0]) (void)hipEventRecord(s.bam.ev[0], s.stream);
+                he = launch_bam_out(ba, s.stream);
+                if (s.bam.ev[1] && he == hipSuccess) he = hipEventRecord(s.bam.ev[1], s.stream);
+                if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("BAM-out builder: ") + hipGetErrorString(he));
+            }
             if (!rs.failed() && taxa) {  // the classified records of both mates sorted into the selectors' bins, on the same stream
                 TaxonOutArgs ta{};
                 ta.text = (const char *)s.d_text;
@@ -2501,6 +2623,8 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
                     he = hipMemcpyAsync(s.h_taxa, s.d_taxa, toff * 4, hipMemcpyDeviceToHost, s.stream);
                 if (he == hipSuccess && split)
                     he = hipMemcpyAsync(s.human.h_total, s.human.d_total, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
+                if (he == hipSuccess && bamout)
+                    he = hipMemcpyAsync(s.bam.h_total, s.bam.d_total, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
                 if (he == hipSuccess && taxa)
                     he = hipMemcpyAsync(s.taxon.h_total, s.taxon.d_total, 4 * (size_t)K * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
                 if (he == hipSuccess && mask)
@@ -2559,6 +2683,11 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
                 fprintf(stderr, "[nohuman trace] human-out: %llu records, %llu bytes built on device; %llu fetched to host; builder kernels %.3f ms (%.1f GB/s of text)\n",
                         (unsigned long long)rs.human_records, (unsigned long long)rs.human_bytes, (unsigned long long)rs.text_fetched.load(),
                         rs.human_kernel_ms, rs.human_kernel_ms > 0 ? (double)rs.human_bytes / (rs.human_kernel_ms * 1e6) : 0.0);
+            if (bamout)
+                fprintf(stderr, "[nohuman trace] bam-out: %llu + %llu records, %llu + %llu bytes selected on device; %llu fetched to host; builder kernels %.3f ms (%.1f GB/s of records)\n",
+                        (unsigned long long)rs.bam_records[0], (unsigned long long)rs.bam_records[1], (unsigned long long)rs.bam_bytes[0],
+                        (unsigned long long)rs.bam_bytes[1], (unsigned long long)rs.text_fetched.load(), rs.bam_kernel_ms,
+                        rs.bam_kernel_ms > 0 ? (double)(rs.bam_bytes[0] + rs.bam_bytes[1]) / (rs.bam_kernel_ms * 1e6) : 0.0);
             if (mask)
                 fprintf(stderr, "[nohuman trace] mask: %llu records masked, %llu written, %llu bytes built on device; %llu fetched to host; builder kernels %.3f ms (%.1f GB/s of text); %llu of %llu blocks copied whole\n",
                         (unsigned long long)rs.mask_masked, (unsigned long long)rs.mask_records, (unsigned long long)rs.mask_bytes,
@@ -2630,7 +2759,7 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
         int rch1 = NH_OK, rch2 = NH_OK;
         std::string errh1, errh2;
         std::thread th1, th2;
-        if (split) {
+        if (split_files) {
             th1 = std::thread([&] {
                 rch1 = h1.close();
                 if (rch1) errh1 = g_last_error;

@@ -145,6 +145,36 @@ static Codec codec_from_magic(const std::string &p) {
     if (m[0] == 0xfd && m[1] == 0x37 && m[2] == 0x7a && m[3] == 0x58 && m[4] == 0x5a) return C_XZ;
     return C_NONE;
 }
+// Is the file a BAM: a first gzip member with the BGZF extra field that inflates to a stream beginning "BAM\1" (the library's test)
+static bool is_bam_file(const std::string &p) {
+    FILE *f = fopen(p.c_str(), "rb");
+    if (!f) return false;
+    std::vector<unsigned char> m(65536 + 64);
+    const size_t got = fread(m.data(), 1, m.size(), f);
+    fclose(f);
+    if (got < 18 || m[0] != 0x1f || m[1] != 0x8b || m[2] != 8 || m[3] != 4) return false;
+    const size_t xlen = m[10] | (size_t)m[11] << 8;
+    if (12 + xlen > got) return false;
+    bool bc = false;
+    for (size_t at = 12; at + 4 <= 12 + xlen;) {
+        const size_t slen = m[at + 2] | (size_t)m[at + 3] << 8;
+        if (m[at] == 'B' && m[at + 1] == 'C' && slen == 2) bc = true;
+        at += 4 + slen;
+    }
+    if (!bc) return false;
+    z_stream z;
+    memset(&z, 0, sizeof z);
+    if (inflateInit2(&z, -15) != Z_OK) return false;
+    unsigned char magic[4] = {0, 0, 0, 0};
+    z.next_in = m.data() + 12 + xlen;
+    z.avail_in = (uInt)(got - 12 - xlen);
+    z.next_out = magic;
+    z.avail_out = 4;
+    (void)inflate(&z, Z_SYNC_FLUSH);
+    const bool four = z.avail_out == 0;
+    inflateEnd(&z);
+    return four && memcmp(magic, "BAM\1", 4) == 0;
+}
 static std::string add_extension(Codec c, const std::string &p) {
     if (c == C_NONE) return p;
     return p + "." + codec_ext(c);  // "a.fq" -> "a.fq.gz", "a" -> "a.gz"
@@ -217,6 +247,7 @@ struct Args {
     std::string human_out1, human_out2;  // split run: the human reads in the same pass (nh_run_split)
     bool has_human_out1 = false, has_human_out2 = false;
     bool bgzf = false;  // gzip outputs in bgzip's blocked form (NH_CODEC_BGZF)
+    bool bam_out = false;  // a BAM input's kept records as BAM, tags intact (NH_CODEC_BAM)
     bool mask = false;  // masked run: every read written, the human ones' bases as N (nh_run_mask)
     std::string calls, human_ids;  // read lists (nh_run_ex): a table line per read; the ids of the human reads
     unsigned min_base_quality = 0;  // kraken2's --minimum-base-quality (nh_run_minq); 0: off
@@ -257,6 +288,9 @@ static void usage(FILE *f) {
           "      --list-db-versions       List available database versions and exit\n"
           "  -F, --output-type <FORMAT>   Output compression format. u: uncompressed; b: Bzip2; g: Gzip; x: Xz (Lzma); z: Zstd\n"
           "      --bgzf                   Write gzip outputs as BGZF (blocked gzip, as bgzip writes it); needs the output format g\n"
+          "      --bam-out                Write the kept records of a BAM input as BAM: the input's header (no @PG line is added) and records copied byte for byte, "
+          "tags (MM/ML, mv, RG ...) intact, BGZF framed [default output: <stem>.nohuman.bam]. Secondary, supplementary and empty records are written nowhere; the call "
+          "is not added to a record (see --calls, -k). Not with another output format or container, a masked run, per-taxon outputs, two inputs or an input that is not a BAM\n"
           "  -t, --threads <INT>          Number of threads to use [default: 1]\n"
           "  -H, --human                  Output human reads instead of removing them\n"
           "      --human-out1 <PATH>      Also write the human reads, in the same run, to this file (as -H would)\n"
@@ -365,6 +399,7 @@ static Args parse_args(int argc, char **argv) {
         else if (s == "--human-out2") { a.human_out2 = val(); a.has_human_out2 = true; }
         else if (s == "--mask") a.mask = true;
         else if (s == "--bgzf") a.bgzf = true;
+        else if (s == "--bam-out") a.bam_out = true;
         else if (s == "-C" || s == "--conf") {
             std::string t = val();
             char *end;
@@ -467,7 +502,7 @@ static Args parse_args(int argc, char **argv) {
                              : !a.kraken_output.empty() ? "--kraken-output" : !a.kraken_report.empty() ? "--kraken-report" : !a.calls.empty() ? "--calls"
                              : !a.human_ids.empty() ? "--human-ids" : !a.read_stats.empty() ? "--read-stats" : a.report_minimizer_data ? "--report-minimizer-data"
                              : !a.minimizer_table.empty() ? "--minimizer-table" : a.has_type ? "--output-type"
-                             : a.bgzf ? "--bgzf" : a.mask ? "--mask" : a.human ? "--human" : !a.taxon_out.empty() ? "--taxon-out"
+                             : a.bgzf ? "--bgzf" : a.bam_out ? "--bam-out" : a.mask ? "--mask" : a.human ? "--human" : !a.taxon_out.empty() ? "--taxon-out"
                              : !a.host_taxids.empty() ? "--host-taxid" : !a.keep_taxids.empty() ? "--keep-taxid" : nullptr;
         if (out_flag) arg_error("the argument '--build-db <DIR>' cannot be used with '%s'", out_flag);
         if (a.has_extend_db) {
@@ -486,6 +521,16 @@ static Args parse_args(int argc, char **argv) {
     if (a.input.empty() && !a.check && !a.download && !a.list)
         arg_error("the following required arguments were not provided:\n  <INPUT>...");
     if (a.mask && a.human) arg_error("the argument '--mask' cannot be used with '--human'");
+    // BAM output (--bam-out): the kept records of ONE BAM input, copied; its container is BGZF, whatever -F or the names say
+    if (a.bam_out) {
+        if (a.has_type) arg_error("the argument '--bam-out' cannot be used with '--output-type <FORMAT>': a BAM file is its own container");
+        if (a.bgzf) arg_error("the argument '--bam-out' cannot be used with '--bgzf': a BAM file is BGZF framed already");
+        if (a.mask) arg_error("the argument '--bam-out' cannot be used with '--mask'");
+        if (!a.taxon_out.empty()) arg_error("the argument '--bam-out' cannot be used with '--taxon-out <TAXID|other>:<PATH>'");
+        if (a.input.size() > 1) arg_error("the argument '--bam-out' cannot be used with two inputs: BAM input is single-end");
+        if (a.input.size() == 1 && !is_bam_file(a.input[0]))
+            arg_error("the argument '--bam-out' needs a BAM input: %s is not a BAM file", quoted(a.input[0]).c_str());
+    }
     if (!a.keep_taxids.empty() && a.host_taxids.empty())
         arg_error("the argument '--keep-taxid <TAXID>' needs '--host-taxid <TAXID>': it keeps a clade inside a host clade");
     // split run (--human-out1 / --human-out2): the non-human reads to -o / -O, the human ones to these, in one pass
@@ -560,6 +605,11 @@ static double confidence_as_kraken2_sees_it(float c, std::string &text) {
     }
     text = buf;
     return strtod(buf, nullptr);
+}
+
+// --bam-out: "<stem>.nohuman.bam" beside the input (the stem without a trailing ".bam")
+static std::string default_bam_out_name(const std::string &in) {
+    return join(parent_of(in), (extension(in) == "bam" ? file_stem(in) : file_name(in)) + ".nohuman.bam");
 }
 
 static std::string default_out_name(const std::string &in, Codec out_codec) {
@@ -670,7 +720,7 @@ int main(int argc, char **argv) {
     }
     if (args.has_human_out1 && !args.input.empty()) {  // a human output equal to a DEFAULT output name: an argument error as well
         const Codec c = args.has_type ? args.type : args.has_out1 ? codec_from_path(args.out1) : codec_from_magic(args.input[0]);
-        const std::string o1 = args.has_out1 ? args.out1 : default_out_name(args.input[0], c);
+        const std::string o1 = args.has_out1 ? args.out1 : args.bam_out ? default_bam_out_name(args.input[0]) : default_out_name(args.input[0], c);
         const std::string o2 = args.input.size() == 2 ? (args.has_out2 ? args.out2 : default_out_name(args.input[1], c)) : "";
         for (const std::string *h : {&args.human_out1, &args.human_out2})
             if (!h->empty() && (*h == o1 || *h == o2))
@@ -817,9 +867,9 @@ int main(int argc, char **argv) {
     // directory (src/main.rs:248-257) and compresses them to the output paths afterwards
     // (src/main.rs:342-368).  Here the engine's writer feeds the kept records straight into the output
     // encoder: no temporary file, one pass.
-    std::string out1 = args.has_out1 ? args.out1 : default_out_name(args.input[0], out_codec);
+    std::string out1 = args.has_out1 ? args.out1 : args.bam_out ? default_bam_out_name(args.input[0]) : default_out_name(args.input[0], out_codec);
     std::string out2 = paired ? (args.has_out2 ? args.out2 : default_out_name(args.input[1], out_codec)) : "";
-    const int codec = out_codec == C_GZ ? (args.bgzf ? NH_CODEC_BGZF : NH_CODEC_GZIP) : out_codec == C_BZ2 ? NH_CODEC_BZIP2 : out_codec == C_XZ ? NH_CODEC_XZ
+    const int codec = args.bam_out ? NH_CODEC_BAM : out_codec == C_GZ ? (args.bgzf ? NH_CODEC_BGZF : NH_CODEC_GZIP) : out_codec == C_BZ2 ? NH_CODEC_BZIP2 : out_codec == C_XZ ? NH_CODEC_XZ
                     : out_codec == C_ZST ? NH_CODEC_ZSTD : NH_CODEC_NONE;
     INFO(args.mask ? "Masking human reads..." : args.human ? "Keeping human reads..." : "Removing human reads...");
 

@@ -16,7 +16,7 @@ TAXON_MATE_BORDER = 0xFFFFFFFE
 FLAG_PAIRED = 1
 FLAG_LONG = 2
 # nh_codec of include/nohuman_engine.h: what out_codec takes
-CODEC_NONE, CODEC_BZIP2, CODEC_GZIP, CODEC_XZ, CODEC_ZSTD, CODEC_BGZF = 0, 1, 2, 3, 4, 5
+CODEC_NONE, CODEC_BZIP2, CODEC_GZIP, CODEC_XZ, CODEC_ZSTD, CODEC_BGZF, CODEC_BAM = 0, 1, 2, 3, 4, 5, 6
 
 
 class EngineError(RuntimeError):
@@ -50,6 +50,10 @@ def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
     human_out1 / human_out2 exactly as a keep_human run would write them.  mask: nh_run_mask -- every read goes to
     out1 / out2 in input order, a human read's bases replaced by N (with human_out1 / human_out2 as well, if given).
     out_codec: the container of every output, one of the CODEC_* numbers (CODEC_BGZF: gzip in bgzip's blocked form).
+    CODEC_BAM (in1 a BAM file, alone; not with mask or taxon_outs): out1 and human_out1 are BAM files -- the input's header (no
+    @PG line added) and the selected records of the input copied byte for byte, tags intact, BGZF framed; the records the
+    reader skips (secondary, supplementary, without bases) are written nowhere, and no call is added to a record (it is in
+    calls and kraken_output).  Every other output is what the same run with a FASTQ codec writes.
     calls / human_ids (nh_run_ex; any kind of run): two plain-text read lists built on the GPU in the same pass -- calls: a
     line per fragment, C/U, id, taxid, length(s), total_kmers, clade_hits, hit_groups, tab-separated (clade_hits /
     total_kmers is the confidence that `confidence` thresholds); human_ids: the id of every human fragment.
@@ -600,6 +604,17 @@ class Engine:
         written, the others are.  Asynchronous on `stream`."""
         _check(self._L.nh_bam_to_fastq_device(self._h, d_bam or None, int(bam_len), d_table or None, int(n_records), d_text or None,
                                               int(text_cap), int(text_len), d_error_bits or None, stream or None))
+
+    def bam_select_device(self, d_bam: int, bam_len: int, d_table: int, n_records: int, d_results: int, want: int, d_out: int, out_cap: int,
+                          d_total: int, d_error_bits: int, stream: int = 0):
+        """BAM output's kernels alone (nh_bam_select_device): of the records of d_bam (bam_len bytes, 4-byte aligned) that d_table
+        names -- the reader's table, two uint64 a record, the first where its block_size field lies in d_bam -- those whose
+        d_results[i].call is 0 (want 0) or not 0 (want 1) are copied whole, 4 + block_size bytes each, contiguous and in table
+        order, into d_out (out_cap bytes, 4-byte aligned); d_total (one uint64 in device memory) receives their bytes.
+        d_error_bits: one int32 the caller zeroed; bit 1: a record outside d_bam -- not written, the others are; bit 4: the
+        total is above out_cap -- nothing is written, the total is 0.  Waits for `stream`."""
+        _check(self._L.nh_bam_select_device(self._h, d_bam or None, int(bam_len), d_table or None, int(n_records), d_results or None,
+                                            int(want), d_out or None, int(out_cap), d_total or None, d_error_bits or None, stream or None))
 
     def read_stats_device(self, d_text: int, text_len: int, d_seq_starts: int, d_seq_lens: int, d_qual_starts: int,
                           d_results: int, n_frag: int, d_acc: int, paired: bool = False, max_workgroups: int = 0, stream: int = 0):
