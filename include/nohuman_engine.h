@@ -343,6 +343,28 @@ int nh_gzip_gpu_file(int32_t device, const void *in, uint64_t n, const char *out
 /* The same through the encoder's BGZF mode (NH_CODEC_BGZF): a member per 65280-byte region, framed on the GPU, then the EOF
  * member.  Arguments and stats as nh_gzip_gpu_file. */
 int nh_bgzf_gpu_file(int32_t device, const void *in, uint64_t n, const char *out, uint64_t *stats);
+/* Test / tool support for that encoder: its HOST MODEL (nohuman_amd/csrc/nh_deflate_model.h -- the kernel's own lane-level functions,
+ * nh_deflate_core.h, the 64 lanes run by a loop, with the host side's chunks, price pilot, price hand-over and framing).  Writes to
+ * `out` the file nh_gzip_gpu_file (bgzf = 0) or nh_bgzf_gpu_file (bgzf = 1) writes for the same text when the encoder runs with
+ * NOHUMAN_GZIP_WAYS = ways (4, 6, 8), NOHUMAN_GZIP_REGION = region_bytes (rounded as the encoder rounds it; BGZF: 65280 whatever it
+ * says), chunks of chunk_bytes (the encoder's: NOHUMAN_GZIP_CHUNK_MB << 20, 128 MiB by default; here anything from one region up, BGZF:
+ * cut down to whole regions) and NOHUMAN_GZIP_PRICES = prices (-1: unset, the pilot chooses).  The regions of a chunk run on `threads`
+ * threads (0: up to 16); the bytes do not depend on that.  region_sizes (may be NULL): region_sizes_cap entries that receive the bytes
+ * of every region's deflate stream, in order.  stats12 (may be NULL): {file bytes, regions, price set chosen, dynamic blocks, stored
+ * blocks, blocks with a literal/length or distance code repaired to 15 bits, blocks with the code-length code repaired to 7 bits,
+ * longest match, longest distance, matches extended beyond the scan cap, tokens, matches}.  Needs no GPU. */
+typedef struct nh_gzip_model_opts {
+    uint32_t ways;
+    uint32_t region_bytes;
+    uint64_t chunk_bytes;
+    int32_t prices;
+    int32_t bgzf;
+    uint32_t threads;
+    uint32_t reserved;
+    uint32_t *region_sizes;
+    uint64_t region_sizes_cap;
+} nh_gzip_model_opts;
+int nh_gzip_model_file(const void *in, uint64_t n, const char *out, const nh_gzip_model_opts *opts, uint64_t *stats12);
 /* nh_compress_file for a host that keeps the reference's two stages (kraken2-style temporary file, then compress,
  * src/main.rs:342-368) but has the GPU at hand: NH_CODEC_GZIP and NH_CODEC_BGZF are encoded on `device` as above, the other codecs as in
  * nh_compress_file. */

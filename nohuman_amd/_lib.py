@@ -94,6 +94,12 @@ class nh_host_filter(C.Structure):
                 ("host_fragments", C.c_uint64), ("spared_fragments", C.c_uint64)]
 
 
+class nh_gzip_model_opts(C.Structure):
+    _fields_ = [("ways", C.c_uint32), ("region_bytes", C.c_uint32), ("chunk_bytes", C.c_uint64), ("prices", C.c_int32),
+                ("bgzf", C.c_int32), ("threads", C.c_uint32), ("reserved", C.c_uint32),
+                ("region_sizes", C.POINTER(C.c_uint32)), ("region_sizes_cap", C.c_uint64)]
+
+
 class nh_build_args(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_fasta", C.c_uint32), ("fasta", C.POINTER(C.c_char_p)),
                 ("out_dir", C.c_char_p), ("taxid", C.c_uint64), ("taxon_name", C.c_char_p), ("load_factor", C.c_double),
@@ -185,6 +191,7 @@ SYMBOLS = {
     "nh_compress_file_device": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_uint32, C.c_int32]),
     "nh_gzip_gpu_file": (C.c_int, [C.c_int32, _P, C.c_uint64, C.c_char_p, C.POINTER(C.c_uint64)]),
     "nh_bgzf_gpu_file": (C.c_int, [C.c_int32, _P, C.c_uint64, C.c_char_p, C.POINTER(C.c_uint64)]),
+    "nh_gzip_model_file": (C.c_int, [_P, C.c_uint64, C.c_char_p, C.POINTER(nh_gzip_model_opts), C.POINTER(C.c_uint64)]),
     "nh_gunzip_file": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64)]),
     "nh_cache_bytes": (C.c_uint64, [C.c_int32, C.c_int32]),
     "nh_gunzip_device_file": (C.c_int, [C.c_char_p, C.c_char_p, C.c_int32, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),

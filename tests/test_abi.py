@@ -40,6 +40,8 @@ def test_struct_layouts_match_header():
     assert C.sizeof(_lib.nh_db_info) == 96
     assert C.sizeof(_lib.nh_db_check) == 32
     assert C.sizeof(_lib.nh_run_args) == 7 * 8 + 8 + 4 * 3 + 4 + 8 + 8
+    assert C.sizeof(_lib.nh_gzip_model_opts) == 4 + 4 + 8 + 4 * 4 + 8 + 8   # (nh_gzip_model_file: test / tool support, needs no GPU)
+    assert _lib.nh_gzip_model_opts.region_sizes.offset == 32 and _lib.nh_gzip_model_opts.chunk_bytes.offset == 8
 
 
 def _has_gpu():

@@ -9,7 +9,7 @@ import subprocess
 import pytest
 
 from nohuman_amd import _lib
-from tests import bgzf_util
+from tests import bgzf_util, deflate_pins
 from tests.test_bgzf_host import NAMES, host_bgzf
 
 pytestmark = pytest.mark.gpu
@@ -32,7 +32,11 @@ def gpu_bgzf(data, path):
     rc = L.nh_bgzf_gpu_file(0, buf, len(data), os.fsencode(str(path)), stats)
     assert rc == 0, L.nh_last_error().decode()
     assert os.path.getsize(path) == stats[0]
-    return open(path, "rb").read()
+    raw = open(path, "rb").read()
+    # the file is the one the encoder's host model writes in its BGZF mode (ways, price choice and chunk size from the environment)
+    deflate_pins.assert_equals_model(raw, data, os.environ.get("PYTEST_CURRENT_TEST", str(path)), "the environment's, BGZF",
+                                     **deflate_pins.encoder_options(bgzf=True))
+    return raw
 
 
 @pytest.mark.parametrize("name", NAMES)

@@ -1,6 +1,8 @@
 """gzip output encoded on the GPU (nohuman_amd/csrc/nh_deflate.hip; SURVEY.md 8f-4, the reference's stage is
 compression.rs:214-233).  Parity target is the decompressed content (compression.rs:282-288): every stream is
-inflated by zlib -- which also checks the member's CRC-32 and length -- and by this repo's own parallel reader."""
+inflated by zlib -- which also checks the member's CRC-32 and length -- and by this repo's own parallel reader.
+Every file check() sees is also compared byte for byte with the encoder's host model (nh_gzip_model_file through
+tests/deflate_pins.py) under the options the encoder read from the environment."""
 import ctypes as C
 import gzip
 import os
@@ -13,6 +15,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from nohuman_amd import _lib  # noqa: E402
+from tests import deflate_pins  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -49,6 +52,8 @@ def check(data, path):
     assert gzip.decompress(raw) == data          # zlib: content, CRC-32, ISIZE
     d = zlib.decompressobj(31)                    # one member, nothing behind it
     assert d.decompress(raw) == data and d.eof and d.unused_data == b""
+    # the file is the one the host model writes: ways, region, price choice and chunk size as the encoder read them
+    deflate_pins.assert_equals_model(raw, data, os.environ.get("PYTEST_CURRENT_TEST", path), "the environment's", **deflate_pins.encoder_options())
     return size
 
 
@@ -130,6 +135,9 @@ def test_run_takes_long_spans_from_the_device_copy_of_the_batch(tmp_path, monkey
         assert len(want) > 2_000_000
         assert gzip.decompress((tmp_path / ("g_%s.gz" % m)).read_bytes()) == want
         assert gzip.decompress((tmp_path / ("h_%s.gz" % m)).read_bytes()) == want
+        # mapped and staged spans, several batches: the stream is the one the plain text determines
+        deflate_pins.assert_equals_model((tmp_path / ("g_%s.gz" % m)).read_bytes(), want, "nh_run's g_%s.gz, %d fragments a batch" % (m, batch_frags),
+                                         "the environment's", **deflate_pins.encoder_options())
 
 
 def test_encoder_with_pageable_staging_buffers(tmp_path):
