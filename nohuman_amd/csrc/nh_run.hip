@@ -37,9 +37,6 @@
 
 namespace nh {
 
-// Output file written with writev(): a batch's output is a list of spans, either slices of the raw
-// input text (kept records that need no reformatting -- the common case, no copy) or pieces of a
-// scratch buffer (reformatted records, kraken output lines).
 // What one batch puts into one output file: slices of the batch's raw text (the normal case: nothing is copied) and of
 // a scratch string (reformatted records), in output order
 struct Spans {
@@ -91,7 +88,6 @@ struct OutFile {
         iov.push_back({(void *)from, n});
         sp.is_scratch.push_back(1);
     }
-    int flush() { return flush(sp); }
     int flush(Spans &x) {  // write all spans of x, then forget them
         std::vector<struct iovec> &iov = x.iov;
         for (size_t i = 0; i < iov.size(); i++)
@@ -380,6 +376,14 @@ struct Batch {
     size_t n = 0;
     int slot = -1;  // stream slot that carries its results
     int dev_index = 0;  // index of the slot's device among the run's engines
+    // the batch's text in the slot's device buffer: file 1's at byte 0, file 2's behind it at base2() (len2 is 0 without one)
+    size_t base2() const { return (len1 + 8 + 255) & ~(size_t)255; }
+    size_t ntext() const { return h2 ? base2() + len2 : len1; }
+    // the words of fragment i in the -k lines' taxa: one a k-mer of each mate, and the mates' border
+    uint64_t kmer_taxa(size_t i, uint64_t k) const {
+        const uint64_t l1 = h1->recs[off1 + i].slen, l2 = h2 ? h2->recs[off2 + i].slen : 0;
+        return (l1 >= k ? l1 - k + 1 : 0) + (h2 ? (l2 >= k ? l2 - k + 1 : 0) + 1 : 0);
+    }
 };
 
 // One builder's side of a slot: the texts (one a mate, or one a list) that nh_split / nh_mask / nh_calls.hip make in HBM behind
@@ -398,7 +402,6 @@ struct BuiltOut {
 struct Slot {  // pinned host + device buffers of one in-flight batch
     Engine *e = nullptr;
     hipStream_t stream = nullptr;
-    int work_slot = 0;
     // The sequences are classified IN PLACE: the raw text of the batch (both mate files' record text, as
     // read) is copied to the device as it is, and the kernel gets (start, length) of every sequence.
     uint64_t *h_off = nullptr;   // n_seq starts into d_text
@@ -520,42 +523,23 @@ static int built_reserve_host(BuiltOut &o, int i, size_t n, const char *what) {
     return NH_OK;
 }
 
+// a page-locked array of a slot and its twin in HBM: n elements of `elem` bytes (`what`: their name in the message)
+static int slot_reserve_pair(void **h, void **d, size_t *cap, size_t n, size_t elem, const char *what) {
+    if (n <= *cap) return NH_OK;
+    if (*h) (void)hipHostFree(*h);
+    if (*d) (void)hipFree(*d);
+    *h = nullptr, *d = nullptr;
+    *cap = grow(n);
+    if (host_malloc(h, *cap * elem, hipHostMallocDefault) != hipSuccess || dev_malloc(d, *cap * elem) != hipSuccess)
+        return set_error(NH_EOOM, "cannot allocate batch buffers (%zu %s)", *cap, what);
+    return NH_OK;
+}
 // the record table of nrec sequences of a slot (read statistics need nothing else)
-static int slot_reserve_rec(Slot &s, size_t nrec) {
-    if (nrec <= s.cap_rec) return NH_OK;
-    if (s.h_rec) (void)hipHostFree(s.h_rec);
-    if (s.d_rec) (void)hipFree(s.d_rec);
-    s.h_rec = nullptr, s.d_rec = nullptr;
-    s.cap_rec = grow(nrec);
-    if (host_malloc((void **)&s.h_rec, s.cap_rec * 16, hipHostMallocDefault) != hipSuccess || dev_malloc(&s.d_rec, s.cap_rec * 16) != hipSuccess)
-        return set_error(NH_EOOM, "cannot allocate batch buffers (%zu records)", s.cap_rec);
-    return NH_OK;
-}
-
+static int slot_reserve_rec(Slot &s, size_t nrec) { return slot_reserve_pair((void **)&s.h_rec, &s.d_rec, &s.cap_rec, nrec, 16, "records"); }
 // mate 1's id lengths of n fragments of a slot (read lists)
-static int slot_reserve_idl(Slot &s, size_t n) {
-    if (n <= s.cap_idl) return NH_OK;
-    if (s.h_idl) (void)hipHostFree(s.h_idl);
-    if (s.d_idl) (void)hipFree(s.d_idl);
-    s.h_idl = nullptr, s.d_idl = nullptr;
-    s.cap_idl = grow(n);
-    if (host_malloc((void **)&s.h_idl, s.cap_idl * 4, hipHostMallocDefault) != hipSuccess || dev_malloc(&s.d_idl, s.cap_idl * 4) != hipSuccess)
-        return set_error(NH_EOOM, "cannot allocate batch buffers (%zu id lengths)", s.cap_idl);
-    return NH_OK;
-}
-
+static int slot_reserve_idl(Slot &s, size_t n) { return slot_reserve_pair((void **)&s.h_idl, &s.d_idl, &s.cap_idl, n, 4, "id lengths"); }
 // the second results array of nfrag fragments of a slot (runs with a host selection)
-static int slot_reserve_hres(Slot &s, size_t nfrag) {
-    if (nfrag <= s.cap_hres) return NH_OK;
-    if (s.h_hres) (void)hipHostFree(s.h_hres);
-    if (s.d_hres) (void)hipFree(s.d_hres);
-    s.h_hres = nullptr, s.d_hres = nullptr;
-    s.cap_hres = grow(nfrag);
-    if (host_malloc((void **)&s.h_hres, s.cap_hres * sizeof(nh_result), hipHostMallocDefault) != hipSuccess ||
-        dev_malloc(&s.d_hres, s.cap_hres * sizeof(nh_result)) != hipSuccess)
-        return set_error(NH_EOOM, "cannot allocate batch buffers (%zu host-filtered results)", s.cap_hres);
-    return NH_OK;
-}
+static int slot_reserve_hres(Slot &s, size_t n) { return slot_reserve_pair((void **)&s.h_hres, &s.d_hres, &s.cap_hres, n, sizeof(nh_result), "host-filtered results"); }
 
 // the quality mask's buffers of a slot: the record table of nrec sequences, ntext bytes of masked text, the counter
 static int slot_reserve_qmask(Slot &s, size_t ntext, size_t nrec) {
@@ -1383,39 +1367,38 @@ struct RunFiles {
     OutFile tx[2][NH_MAX_TAXON_OUTS];  // the selectors' files, [mate][selector]
 };
 
+// fn(file, i) on out1 [0] and, side by side with it on threads of their own, on out2 [1] and the human outputs of a split run [2],
+// [3]: a GPU encoder takes 70 ms to set up -- page-locked buffers, a trial of its prices -- and its last chunks as long to finish.
+// The first error in that order.
+template <class F>
+static int record_files_side_by_side(RunFiles &f, bool paired, bool split_files, F fn) {
+    OutFile *const of[4] = {&f.o1, paired ? &f.o2 : nullptr, split_files ? &f.h1 : nullptr, split_files && paired ? &f.h2 : nullptr};
+    int rc[4] = {NH_OK, NH_OK, NH_OK, NH_OK};
+    std::string err[4];
+    std::thread t[4];
+    for (int i = 1; i < 4; i++)
+        if (of[i])
+            t[i] = std::thread([&, i] {
+                rc[i] = fn(*of[i], i);
+                if (rc[i]) err[i] = g_last_error;
+            });
+    rc[0] = fn(f.o1, 0);
+    for (std::thread &x : t)
+        if (x.joinable()) x.join();
+    for (int i = 1; i < 4 && !rc[0]; i++)
+        if (rc[i]) return set_error(rc[i], "%s", err[i].c_str());
+    return rc[0];
+}
+
 // Creates them.  gzip output is encoded on the GPU (nh_deflate.hip); with two devices each mate file has its own: mate 1's files on
-// the first device, mate 2's on the second.  Mate 2's file and the human outputs are opened side by side with out1: a GPU encoder
-// takes 70 ms to set up -- page-locked buffers, a trial of its prices.
+// the first device, mate 2's on the second.
 static int open_run_files(RunFiles &f, const RunRequest &r, const std::vector<Engine *> &engines, bool paired, bool want_k) {
     const nh_run_args *a = r.a;
     const int dev1 = engines[0]->device, dev2 = engines[engines.size() > 1 ? 1 : 0]->device;
-    int rc, rc2 = NH_OK, rch1 = NH_OK, rch2 = NH_OK;
-    std::string err2, errh1, errh2;
-    std::thread t2, th1, th2;
-    if (paired)
-        t2 = std::thread([&] {
-            rc2 = f.o2.open(a->out2, a->out_codec, a->codec_threads, dev2);
-            if (rc2) err2 = g_last_error;
-        });
-    if (r.hout1) {
-        th1 = std::thread([&] {
-            rch1 = f.h1.open(r.hout1, a->out_codec, a->codec_threads, dev1);
-            if (rch1) errh1 = g_last_error;
-        });
-        if (paired)
-            th2 = std::thread([&] {
-                rch2 = f.h2.open(r.hout2, a->out_codec, a->codec_threads, dev2);
-                if (rch2) errh2 = g_last_error;
-            });
-    }
-    rc = f.o1.open(a->out1, a->out_codec, a->codec_threads, dev1);
-    if (t2.joinable()) t2.join();
-    if (th1.joinable()) th1.join();
-    if (th2.joinable()) th2.join();
+    const char *const paths[4] = {a->out1, a->out2, r.hout1, r.hout2};
+    int rc = record_files_side_by_side(f, paired, r.hout1 != nullptr,
+                                       [&](OutFile &of, int i) { return of.open(paths[i], a->out_codec, a->codec_threads, i & 1 ? dev2 : dev1); });
     if (rc) return rc;
-    if (rc2) return set_error(rc2, "%s", err2.c_str());
-    if (rch1) return set_error(rch1, "%s", errh1.c_str());
-    if (rch2) return set_error(rch2, "%s", errh2.c_str());
     for (uint32_t k = 0; k < r.n_touts; k++)
         for (int m = 0; m < (paired ? 2 : 1); m++)
             if ((rc = f.tx[m][k].open(m ? r.touts[k].out2 : r.touts[k].out1, a->out_codec, a->codec_threads, m ? dev2 : dev1))) return rc;
@@ -1654,201 +1637,265 @@ static int reduce_run_counters(RunState &rs) {
     }
     return crc;
 }
-int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_stats *stats) {
-    const nh_run_args *a = r.a;
-    if (!a || !a->in1 || !a->out1) return set_error(NH_EINVAL, "nh_run: in1 and out1 are required");
-    if (const int brc = check_bam_inputs(a)) return brc;
-    if (engines.empty()) return set_error(NH_EINVAL, "nh_run: no engine");
-    // the request (check_request has passed it) under the names the pipeline uses
-    const bool mask = r.mask;
-    const char *const calls = r.calls, *const ids = r.ids;
-    const uint32_t minq = r.minq;
-    nh_minimizer_data *const md = r.md;
-    nh_host_filter *const hf = r.hf;
-    // BAM output (check_request has passed it: a BAM in1 alone, neither masked nor with selectors): out1 and, a split run, human_out1
-    // receive records of the input selected on the device (nh_bamout.hip); none of the FASTQ record builders runs
-    const bool bamout = a->out_codec == NH_CODEC_BAM;
-    const bool split_files = r.hout1 != nullptr;  // a split run: the human outputs are opened, flushed, closed
-    const bool split = split_files && !bamout;     // ... and their records built as FASTQ text (nh_split.hip)
-    const int n_bout = split_files ? 2 : 1;        // BAM output: the builder's outputs
-    const int K = (int)r.n_touts;  // per-taxon outputs: the selectors
-    const bool taxa = K > 0;
-    const bool lists = calls || ids;
-    const bool qm = minq > 0;
-    const bool rst = r.rs_path || r.rs_out;
-    const bool mdt = md && (md->in_report || md->table || md->taxa);
-    const bool hsel = hf != nullptr;
-    // the features' tables, and what they ask of the database (it is open: before any input is read or any output created)
-    int rc;
-    std::vector<uint8_t> bin_of, host_of;  // per node of the taxonomy: the selector's bin, host or not
-    if (taxa && (rc = selector_bins(engines[0], r, bin_of))) return rc;
-    for (size_t g = 0; mdt && g < engines.size(); g++)
-        if ((rc = mdata_check_db(engines[g]))) return rc;
-    if (hsel) {
-        if ((rc = host_table(engines[0], hf, host_of))) return rc;
-        hf->host_fragments = hf->spared_fragments = 0;
+
+// ---- the run's shape ----------------------------------------------------------------------------------
+// What kind of run a request asks for, computed once and const from then on: the constructor reads the request (check_request has
+// passed it) and the environment -- the features' tables are checked with these flags before any output is created --,
+// set_outputs() adds what the opened files decide.  Nothing else derives these values a second time.
+namespace {  // (the pipeline's own types: this file's alone)
+struct RunShape {
+    bool mask, calls, ids, lists;
+    uint32_t minq;
+    // BAM output (a BAM in1 alone, neither masked nor with selectors): out1 and, a split run, human_out1 receive records of the
+    // input selected on the device (nh_bamout.hip); none of the FASTQ record builders runs
+    bool bamout;
+    bool split_files;  // a split run: the human outputs are opened, flushed, closed
+    bool split;        // ... and their records built as FASTQ text (nh_split.hip)
+    int n_bout, K;     // BAM output: the builder's outputs; per-taxon outputs: the selectors
+    bool taxa, qm, rst, mdt, hsel;
+    bool want_rec;     // a kernel of the run reads the record table
+    bool gzip_family;  // the codecs the GPU encodes
+    int G, NS;         // devices, stream slots a device
+    bool trace, trace_run;  // NOHUMAN_TRACE is set: events around the launches, the trace lines; it begins with 1: the run's own lines at its end
+    // set_outputs() (outs_take_hbm: out1 / out2 are gzip-family encoders on the GPU that take device spans):
+    int mates = 1;
+    uint32_t flags = 0;
+    bool outs_take_hbm = false, host_text_wanted = false, human_in_hbm = false, mask_in_hbm = false, bam_in_hbm = false, taxon_in_hbm = false;
+
+    RunShape(const RunRequest &r, size_t n_engines) {
+        const nh_run_args *a = r.a;
+        mask = r.mask, calls = r.calls != nullptr, ids = r.ids != nullptr, lists = calls || ids, minq = r.minq;
+        bamout = a->out_codec == NH_CODEC_BAM;
+        split_files = r.hout1 != nullptr, split = split_files && !bamout, n_bout = split_files ? 2 : 1;
+        K = (int)r.n_touts, taxa = K > 0;
+        qm = minq > 0, rst = r.rs_path || r.rs_out, hsel = r.hf != nullptr;
+        mdt = r.md && (r.md->in_report || r.md->table || r.md->taxa);
+        want_rec = split || mask || lists || qm || rst || taxa;
+        gzip_family = a->out_codec == NH_CODEC_GZIP || a->out_codec == NH_CODEC_BGZF || bamout;
+        G = (int)n_engines;
+        // stream slots a device: two keep the classifier busy; a third lets the copy of a batch's text back to the host (batches
+        // born on the GPU, outputs written by the host) run while the writer is still busy with the batch before; a fourth is
+        // held by the batch the flusher is writing
+        NS = 4;
+        if (const char *env = getenv("NOHUMAN_SLOTS")) NS = std::max(1, std::min(8, atoi(env)));
+        const char *tr = getenv("NOHUMAN_TRACE");
+        trace = tr != nullptr, trace_run = tr && tr[0] == '1';
     }
-    if (split || lists || taxa)
-        for (Engine *e : engines) {
-            const int erc = ensure_device_external(e);
-            if (erc) return erc;
-        }
-    RunState rs;
-    rs.a = a;
-    rs.engines = engines;
-    rs.paired = a->in2 != nullptr;
-    if (rs.paired && !a->out2) return set_error(NH_EINVAL, "nh_run: paired input needs out2");
-    if (!(a->confidence >= 0.0 && a->confidence <= 1.0))
-        return set_error(NH_EINVAL, "Confidence score must be in the closed interval [0, 1]");
-    rs.want_k = a->kraken_output && a->kraken_output[0] && strcmp(a->kraken_output, "/dev/null") != 0;
-    rs.call_counts.assign(engines[0]->external.size(), 0);
-    rs.dev_counts.assign(4 * engines.size(), 0);
-    for (const char *p : {a->in1, a->in2}) {  // fail on unreadable inputs before creating outputs
-        if (!p) continue;
-        FILE *f = fopen(p, "rb");
-        if (!f) return set_error(NH_EIO, "cannot open %s", p);
-        fclose(f);
+    void set_outputs(const nh_run_args *a, const RunState &rs, RunFiles &f) {
+        auto takes = [](const OutFile &o) { return o.enc && o.enc->takes_device_spans(); };
+        mates = rs.paired ? 2 : 1;
+        flags = rs.paired ? NH_FLAG_PAIRED : 0;
+        outs_take_hbm = gzip_family && takes(f.o1) && (!rs.paired || takes(f.o2));
+        // Batches of the reader on the GPU keep their text in HBM.  The host needs the bytes for plain outputs and the host's
+        // codecs, for the ids of --output lines and for the suffix of classified-out headers; gzip outputs encoded on the GPU
+        // take the kept records from HBM (a record that needs reformatting -- CRLF, "+id" -- makes the writer fetch its batch).
+        // A masked run builds every output record on the device (the split side as well): only --output lines need the bytes.
+        // BAM output takes nothing from the text at all: its records are the input's BAM bytes, which the reader keeps in HBM.
+        host_text_wanted = bamout ? rs.want_k
+                           : mask ? rs.want_k || G > 1
+                                  : !outs_take_hbm || rs.want_k || a->keep_human != 0 || G > 1;  // (G > 1: a batch's slot and its file's encoder may sit on different GPUs)
+        // split runs: the classified-out text is built in HBM; an encoder on the slot's GPU takes it from there, any other output
+        // gets exactly the built bytes copied to the host (G > 1: a batch's slot and its file's encoder may sit on different GPUs)
+        human_in_hbm = split && G == 1 && takes(f.h1) && (!rs.paired || takes(f.h2));
+        // masked runs: the same for out1 / out2 -- one span a mate and batch, from HBM or copied to page-locked slot memory
+        mask_in_hbm = mask && G == 1 && takes(f.o1) && (!rs.paired || takes(f.o2));
+        // BAM output: the same for out1 / human_out1 -- one span an output and batch
+        bam_in_hbm = bamout && G == 1 && takes(f.o1) && (!split_files || takes(f.h1));
+        taxon_in_hbm = taxa && G == 1;
+        for (int k = 0; k < K; k++)
+            for (int m = 0; m < mates; m++) taxon_in_hbm = taxon_in_hbm && takes(f.tx[m][k]);
     }
-    // outputs are created with O_TRUNC before the first input byte is read: an output that IS an input
-    // (same device and inode) would be emptied -- refuse (the CLI host stages its outputs and renames).  Only an output that is
-    // there, as a regular file, is looked at; for a plain nh_run this is the only such check.
-    {
-        const std::vector<RunFile> files = request_files(r, F_MDATA);
-        size_t inputs = 0;
-        while (inputs < files.size() && files[inputs].kind == F_INPUT) inputs++;
-        for (size_t c = inputs; c < files.size(); c++) {
-            struct stat so;
-            if (!files[c].path[0] || stat(files[c].path, &so) != 0 || !S_ISREG(so.st_mode)) continue;
-            if ((rc = check_collision(files, c, inputs))) return rc;
-        }
+};
+
+// What the writer hands the flusher for one batch
+struct FlushJob {
+    Batch b;
+    Spans s1, s2, sk, hs1, hs2;  // (hs1, hs2: a split run's classified records, one span a mate)
+    Spans sc, si;                // (the batch's part of the calls table and of the human ids, one span each)
+    Spans ts[2][NH_MAX_TAXON_OUTS];  // (per-taxon outputs: a span a mate and selector with records in the batch)
+    // the built spans that only exist in HBM (an address there, never read on the host): the flusher maps them for the file's encoder
+    std::vector<std::pair<OutFile *, struct iovec>> dev;
+    bool valid = false;  // (false: the run had failed when the batch arrived -- only its buffers go back)
+};
+
+// One active output builder of a run: which BuiltOut of the slot, how many words of totals come back with the results, where its
+// kernel time is summed.  One pass in front of or behind the classifier: its pair of events, where its kernel time is summed.
+struct Builder { BuiltOut Slot::*out; size_t total_words; double RunState::*ms; };
+struct Pass { hipEvent_t (Slot::*ev)[2]; double RunState::*ms; };
+
+// a launch on the slot's stream between a pair of events (NOHUMAN_TRACE; none without it); a failure fails the run under `name`
+template <class F>
+static void timed_launch(RunState &rs, hipStream_t stream, const hipEvent_t ev[2], const char *name, F launch) {
+    if (ev[0]) (void)hipEventRecord(ev[0], stream);
+    hipError_t he = launch();
+    if (ev[1] && he == hipSuccess) he = hipEventRecord(ev[1], stream);
+    if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string(name) + ": " + hipGetErrorString(he));
+}
+
+// where a kernel finds the batch in the slot: the text, the sequences' lengths, the record table (CallsArgs takes no more) ...
+template <class A>
+static void batch_records(A &x, const Slot &s, const Batch &b) {
+    x.text = (const char *)s.d_text, x.ntext = b.ntext();
+    x.seq_len = (const uint32_t *)s.d_len;
+    x.rec = (const uint32_t *)s.d_rec;
+    x.mates = b.h2 ? 2 : 1;
+}
+// ... the sequences' starts and which mate is FASTQ (HumanOutArgs, TaxonOutArgs, MaskArgs, QmaskArgs, RstatsArgs)
+template <class A>
+static void batch_source(A &x, const Slot &s, const Batch &b) {
+    batch_records(x, s, b);
+    x.seq_off = (const uint64_t *)s.d_off;
+    x.fastq[0] = b.h1->format == FMT_FASTQ, x.fastq[1] = b.h2 && b.h2->format == FMT_FASTQ;
+}
+// where a builder's kernels write: its n_out outputs, its scratch, the engine's error word
+template <class A>
+static void built_sink(A &x, const BuiltOut &o, int n_out, const Slot &s) {
+    for (int i = 0; i < n_out; i++) x.out[i] = o.d_out[i], x.cap[i] = o.cap_out[i];
+    x.blk = (uint64_t *)o.d_blk;
+    x.error = s.e->d_error + LAUNCH_SLOTS;
+}
+
+// ---- the pipeline: readers -> main (pair, stage, launch) -> writer -> flusher ---------------------------
+// The state the threads of one run share, and their bodies.  start() sets the readers, the writer and the flusher going, run()
+// is the main thread's loop -- every batch through pick_slot, reserve, gather, stage_text, launch, queue_results --, shutdown()
+// unblocks and joins them, also after an error.
+struct Pipeline {
+    const nh_run_args *const a;
+    const RunShape &sh;
+    RunState &rs;
+    RunFiles &f;
+    const std::vector<Engine *> &engines;
+    std::vector<RunBuffers> &dbuf;
+    const std::vector<uint8_t> &bin_of;
+    size_t batch_frags = 0, batch_text = 0, mean_rec = 0;  // batch_limits()
+    std::vector<Builder> builders;  // the run's active builders, in the order their totals are copied back
+    std::vector<Pass> passes;
+    std::vector<Slot> slots;
+    BoundedQueue<std::unique_ptr<HalfBatch>> q1{3}, q2{3};
+    BatchPool pool1, pool2;
+    BoundedQueue<Batch> wq;
+    BoundedQueue<std::unique_ptr<FlushJob>> fq{1};
+    std::mutex slot_mu, w2_mu;  // (w2: the hand-shake between the flusher and its helper for the second mate's files)
+    std::condition_variable slot_cv, w2_cv;
+    int w2_state = 0, w2_rc = NH_OK;  // 0 idle, 1 flush requested, 2 done, -1 quit
+    Spans *w2_spans = nullptr, *w2_hspans = nullptr, *w2_tspans = nullptr;
+    std::string w2_err;
+    StageClock clk;
+    std::thread t1, t2, tw, tf, tw2;
+    // the main loop: the half of each file in hand and how many of its records have gone out (a half is normally used whole: Batch)
+    std::shared_ptr<HalfBatch> c1, c2;
+    size_t p1 = 0, p2 = 0, cl1 = 0, cl2 = 0;  // (cl: the half's bytes of text, read once, when it arrives)
+    uint64_t batch_no = 0, frags_out = 0;      // (frags_out: the fragments of the batches before this one)
+    std::vector<uint64_t> home_turn;
+
+    Pipeline(const RunShape &sh_, RunState &rs_, RunFiles &f_, std::vector<RunBuffers> &dbuf_, const std::vector<uint8_t> &bin_of_)
+        : a(rs_.a), sh(sh_), rs(rs_), f(f_), engines(rs_.engines), dbuf(dbuf_), bin_of(bin_of_), wq((size_t)(sh_.NS * sh_.G)),
+          home_turn((size_t)sh_.G, 0) {
+        if (sh.split) builders.push_back({&Slot::human, 2, &RunState::human_kernel_ms});
+        if (sh.bamout) builders.push_back({&Slot::bam, 2, &RunState::bam_kernel_ms});
+        if (sh.taxa) builders.push_back({&Slot::taxon, 4 * (size_t)sh.K, &RunState::taxon_kernel_ms});
+        if (sh.mask) builders.push_back({&Slot::mask, 4, &RunState::mask_kernel_ms});
+        if (sh.lists) builders.push_back({&Slot::lists, 4, &RunState::list_kernel_ms});
+        if (sh.qm) passes.push_back({&Slot::qev, &RunState::qmask_kernel_ms});
+        if (sh.rst) passes.push_back({&Slot::rev, &RunState::rstats_kernel_ms});
+        if (sh.mdt) passes.push_back({&Slot::mev, &RunState::mdata_kernel_ms});
+        if (sh.hsel) passes.push_back({&Slot::hev, &RunState::host_kernel_ms});
     }
-    const bool gzip_family = a->out_codec == NH_CODEC_GZIP || a->out_codec == NH_CODEC_BGZF || bamout;  // the codecs the GPU encodes
-    if (a->out_codec < NH_CODEC_NONE || a->out_codec > NH_CODEC_BAM)
-        return set_error(NH_EINVAL, "nh_run: unknown out_codec %d", a->out_codec);
-    RunFiles files;
-    if ((rc = open_run_files(files, r, engines, rs.paired, rs.want_k))) return rc;
-    OutFile &o1 = files.o1, &o2 = files.o2, &ok = files.ok, &h1 = files.h1, &h2 = files.h2, &oc = files.oc, &oi = files.oi;
-    OutFile(&tx)[2][NH_MAX_TAXON_OUTS] = files.tx;
 
     // fragments per batch: ~96 MB of sequence, at most 262144; both readers cut at the same record
     // count so that paired batches stay aligned (a byte budget only cuts single-end batches)
-    size_t mean_rec = 0;
-    size_t BATCH_FRAGS = estimate_batch_frags(a->in1, &mean_rec);
-    if (const char *env = getenv("NOHUMAN_BATCH_FRAGS")) {  // tuning / test knob
-        const long v = atol(env);
-        if (v > 0) BATCH_FRAGS = (size_t)v;
-    }
-    // byte budget of one reader's batch: single-end batches are cut by it; paired batches are cut by record
-    // count (both readers at the same count), and their budget only keeps the text of the two halves together
-    // below the 4 GB a batch's 32-bit sequence positions can address
-    size_t BATCH_TEXT = rs.paired ? (size_t)0x7F000000u : (size_t)(512u << 20);
-    if (const char *env = getenv("NOHUMAN_BATCH_TEXT")) {  // test knob: batches cut by text at small scale (paired: the halves then differ in length)
-        const long v = atol(env);
-        if (v > 0) BATCH_TEXT = (size_t)v;
-    }
-    const int G = (int)engines.size();
-    const int mates = rs.paired ? 2 : 1;
-    // Batches of the reader on the GPU keep their text in HBM.  The host needs the bytes for plain outputs and the host's
-    // codecs, for the ids of --output lines and for the suffix of classified-out headers; gzip outputs encoded on the GPU
-    // take the kept records from HBM (a record that needs reformatting -- CRLF, "+id" -- makes the writer fetch its batch).
-    // A masked run builds every output record on the device (the split side as well): only --output lines need the bytes.
-    // BAM output takes nothing from the text at all: its records are the input's BAM bytes, which the reader keeps in HBM.
-    const bool host_text_wanted = bamout ? rs.want_k
-                                  : mask ? rs.want_k || G > 1
-                                       : !(gzip_family && o1.enc && o1.enc->takes_device_spans() &&
-                                           (!rs.paired || (o2.enc && o2.enc->takes_device_spans()))) ||
-                                             rs.want_k || a->keep_human != 0 || G > 1;  // (G > 1: a batch's slot and its file's encoder may sit on different GPUs)
-    const uint32_t flags = rs.paired ? NH_FLAG_PAIRED : 0;
-    // split runs: the classified-out text is built in HBM; an encoder on the slot's GPU takes it from there, any other output
-    // gets exactly the built bytes copied to the host (G > 1: a batch's slot and its file's encoder may sit on different GPUs)
-    const bool human_in_hbm = split && G == 1 && h1.enc && h1.enc->takes_device_spans() &&
-                              (!rs.paired || (h2.enc && h2.enc->takes_device_spans()));
-    // masked runs: the same for out1 / out2 -- one span a mate and batch, from HBM or copied to page-locked slot memory
-    const bool mask_in_hbm = mask && G == 1 && o1.enc && o1.enc->takes_device_spans() &&
-                             (!rs.paired || (o2.enc && o2.enc->takes_device_spans()));
-    // BAM output: the same for out1 / human_out1 -- one span an output and batch
-    const bool bam_in_hbm = bamout && G == 1 && o1.enc && o1.enc->takes_device_spans() && (!split_files || (h1.enc && h1.enc->takes_device_spans()));
-    bool taxon_in_hbm = taxa && G == 1;
-    for (int k = 0; k < K; k++)
-        for (int m = 0; m < mates; m++) taxon_in_hbm = taxon_in_hbm && tx[m][k].enc && tx[m][k].enc->takes_device_spans();
-    auto t0 = std::chrono::steady_clock::now();
-
-    const size_t md_mark_bytes = mdt ? (size_t)mdata_mark_words(engines[0]) * 4 : 0;
-    MdataNumbers mdn;  // [3] minimizers_own, [5] distinct_own, [7] db_cells_own, filled at the end of the run
-    double md_count_ms = 0;
-    std::vector<nh_read_class> racc;  // read statistics: the devices' blocks summed: [class][mate]
-    std::vector<RunBuffers> dbuf((size_t)G);  // per device, for the run
-    rs.d_run_counters.assign((size_t)G, nullptr);
-    for (int g = 0; g < G; g++) {
-        if ((rc = alloc_run_buffers(dbuf[g], engines[g], bin_of, host_of, rst, md_mark_bytes, engines[0]->external.size(), mdt))) return rc;
-        rs.d_run_counters[g] = dbuf[g].counters;
-    }
-    // stream slots a device: two keep the classifier busy; a third lets the copy of a batch's text back to the host (batches
-    // born on the GPU, outputs written by the host) run while the writer is still busy with the batch before; a fourth is
-    // held by the batch the flusher is writing
-    int NS = 4;
-    if (const char *env = getenv("NOHUMAN_SLOTS")) NS = std::max(1, std::min(8, atoi(env)));
-    std::vector<Slot> slots((size_t)NS * G);
-    for (int i = 0; i < NS * G; i++) {
-        slots[i].e = engines[i / NS];
-        slots[i].work_slot = i % NS;
-        if (dev_set(slots[i].e->device) != hipSuccess ||
-            hipStreamCreateWithFlags(&slots[i].stream, hipStreamNonBlocking) != hipSuccess ||
-            (split && getenv("NOHUMAN_TRACE") &&
-             (hipEventCreate(&slots[i].human.ev[0]) != hipSuccess || hipEventCreate(&slots[i].human.ev[1]) != hipSuccess)) ||
-            (mask && getenv("NOHUMAN_TRACE") &&
-             (hipEventCreate(&slots[i].mask.ev[0]) != hipSuccess || hipEventCreate(&slots[i].mask.ev[1]) != hipSuccess)) ||
-            (lists && getenv("NOHUMAN_TRACE") &&
-             (hipEventCreate(&slots[i].lists.ev[0]) != hipSuccess || hipEventCreate(&slots[i].lists.ev[1]) != hipSuccess)) ||
-            (bamout && getenv("NOHUMAN_TRACE") &&
-             (hipEventCreate(&slots[i].bam.ev[0]) != hipSuccess || hipEventCreate(&slots[i].bam.ev[1]) != hipSuccess)) ||
-            (taxa && getenv("NOHUMAN_TRACE") &&
-             (hipEventCreate(&slots[i].taxon.ev[0]) != hipSuccess || hipEventCreate(&slots[i].taxon.ev[1]) != hipSuccess)) ||
-            (qm && getenv("NOHUMAN_TRACE") &&
-             (hipEventCreate(&slots[i].qev[0]) != hipSuccess || hipEventCreate(&slots[i].qev[1]) != hipSuccess)) ||
-            (rst && getenv("NOHUMAN_TRACE") &&
-             (hipEventCreate(&slots[i].rev[0]) != hipSuccess || hipEventCreate(&slots[i].rev[1]) != hipSuccess)) ||
-            (mdt && getenv("NOHUMAN_TRACE") &&
-             (hipEventCreate(&slots[i].mev[0]) != hipSuccess || hipEventCreate(&slots[i].mev[1]) != hipSuccess)) ||
-            (hsel && getenv("NOHUMAN_TRACE") &&
-             (hipEventCreate(&slots[i].hev[0]) != hipSuccess || hipEventCreate(&slots[i].hev[1]) != hipSuccess))) {
-            for (auto &s : slots) slot_free(s);
-            return set_error(NH_EDEVICE, "cannot create streams");
+    void batch_limits() {
+        batch_frags = estimate_batch_frags(a->in1, &mean_rec);
+        if (const char *env = getenv("NOHUMAN_BATCH_FRAGS")) {  // tuning / test knob
+            const long v = atol(env);
+            if (v > 0) batch_frags = (size_t)v;
+        }
+        // byte budget of one reader's batch: single-end batches are cut by it; paired batches are cut by record
+        // count (both readers at the same count), and their budget only keeps the text of the two halves together
+        // below the 4 GB a batch's 32-bit sequence positions can address
+        batch_text = rs.paired ? (size_t)0x7F000000u : (size_t)(512u << 20);
+        if (const char *env = getenv("NOHUMAN_BATCH_TEXT")) {  // test knob: batches cut by text at small scale (paired: the halves then differ in length)
+            const long v = atol(env);
+            if (v > 0) batch_text = (size_t)v;
         }
     }
 
-    BoundedQueue<std::unique_ptr<HalfBatch>> q1(3), q2(3);
-    BatchPool pool1, pool2;
-    int prefill = 4 + 2 * G;
-    if (mean_rec) {  // size the page-locked text buffers once: a batch of records plus one read chunk
-        size_t want = BATCH_FRAGS * mean_rec + BATCH_FRAGS * mean_rec / 8 + (8u << 20);
-        if (want > BATCH_TEXT + (8u << 20)) want = BATCH_TEXT + (8u << 20);
-        // small inputs: no more (and no larger) buffers than the text they can hold, compressed 12:1 at most
-        struct stat st1;
-        if (stat(a->in1, &st1) == 0 && S_ISREG(st1.st_mode)) {
-            const uint64_t est = (uint64_t)st1.st_size * 12 + (1u << 20);
-            if (est < want) want = (size_t)est;
-            const uint64_t nb = est / want + 1;
-            if (nb < (uint64_t)prefill) prefill = (int)nb;
+    // the stream and, under NOHUMAN_TRACE, the events of every slot
+    int create_slots() {
+        slots.resize((size_t)sh.NS * sh.G);
+        for (int i = 0; i < sh.NS * sh.G; i++) {
+            Slot &s = slots[i];
+            s.e = engines[i / sh.NS];
+            bool ok = dev_set(s.e->device) == hipSuccess && hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) == hipSuccess;
+            for (const Builder &bd : builders)
+                for (hipEvent_t &ev : (s.*bd.out).ev) ok = ok && (!sh.trace || hipEventCreate(&ev) == hipSuccess);
+            for (const Pass &ps : passes)
+                for (hipEvent_t &ev : s.*ps.ev) ok = ok && (!sh.trace || hipEventCreate(&ev) == hipSuccess);
+            if (!ok) {
+                for (auto &x : slots) slot_free(x);
+                return set_error(NH_EDEVICE, "cannot create streams");
+            }
         }
-        if (want < (1ull << 31)) pool1.first_reserve = pool2.first_reserve = want;
-        if (getenv("NOHUMAN_TRACE"))
-            fprintf(stderr, "[nohuman trace] batch: %zu fragments, text buffers of %zu bytes reserved at once, %d prefilled per file\n",
-                    BATCH_FRAGS, pool1.first_reserve, prefill);
+        return NH_OK;
     }
-    int prefill1 = prefill, prefill2 = prefill;
-    // which reader takes a gzip input: NOHUMAN_GZ_READER by name ("device", "host", "device-text"), else by the input
-    // (device_reader_pays); paired files go the same way (the smaller file decides)
-    bool dev_reader1 = false, dev_reader2 = false, split_readers = false;
-    {
+
+    // the builders, a function each with three steps: RESERVE (main thread, before the record table is gathered), LAUNCH (main
+    // thread, behind the classifier on the slot's stream), SPANS (writer thread: the totals that came back into spans of the
+    // flusher's job).  *rc: the stage's error so far -- a reserve or a span is not made behind one -- and this step's
+    enum BuildStep { RESERVE, LAUNCH, SPANS };
+    // a span of built text for file `of`, kept in `sp`; in HBM: also noted for the flusher to map
+    void add_built(FlushJob *j, OutFile &of, Spans &sp, char *at, size_t len, bool in_hbm) {
+        sp.iov.push_back({(void *)at, len});
+        sp.is_scratch.push_back(0);
+        if (in_hbm) j->dev.push_back({&of, {(void *)at, len}});
+    }
+    // output i of a builder that makes one span an output: its total, added to *bytes, as a span of `of` kept in `sp`
+    void one_span(FlushJob *j, BuiltOut &o, int i, bool in_hbm, OutFile &of, Spans &sp, uint64_t *bytes, int *rc, const char *what, const char *item) {
+        const size_t tot = (size_t)o.h_total[i];
+        *bytes += tot;
+        if (tot) add_built(j, of, sp, built_span(o, i, tot, in_hbm, rs, rc, what, item), tot, in_hbm);
+    }
+
+    void start() {
+        start_readers();
+        if (sh.bamout) write_bam_header();
+        if (rs.paired) tw2 = std::thread([this] { mate2_flusher_main(); });
+        tf = std::thread([this] { flusher_main(); });
+        tw = std::thread([this] { writer_main(); });
+    }
+
+    // sizes the pools' page-locked text buffers, chooses each input's reader and starts the reader threads
+    void start_readers() {
+        const int G = sh.G, mates = sh.mates;
+        const bool host_text_wanted = sh.host_text_wanted;
+        int prefill = 4 + 2 * G;
+        if (mean_rec) {  // size the page-locked text buffers once: a batch of records plus one read chunk
+            size_t want = batch_frags * mean_rec + batch_frags * mean_rec / 8 + (8u << 20);
+            if (want > batch_text + (8u << 20)) want = batch_text + (8u << 20);
+            // small inputs: no more (and no larger) buffers than the text they can hold, compressed 12:1 at most
+            struct stat st1;
+            if (stat(a->in1, &st1) == 0 && S_ISREG(st1.st_mode)) {
+                const uint64_t est = (uint64_t)st1.st_size * 12 + (1u << 20);
+                if (est < want) want = (size_t)est;
+                const uint64_t nb = est / want + 1;
+                if (nb < (uint64_t)prefill) prefill = (int)nb;
+            }
+            if (want < (1ull << 31)) pool1.first_reserve = pool2.first_reserve = want;
+            if (sh.trace)
+                fprintf(stderr, "[nohuman trace] batch: %zu fragments, text buffers of %zu bytes reserved at once, %d prefilled per file\n",
+                        batch_frags, pool1.first_reserve, prefill);
+        }
+        int prefill1 = prefill, prefill2 = prefill;
+        // which reader takes a gzip input: NOHUMAN_GZ_READER by name ("device", "host", "device-text"), else by the input
+        // (device_reader_pays); paired files go the same way (the smaller file decides)
+        bool dev_reader1 = false, dev_reader2 = false, split_readers = false;
         const char *how = getenv("NOHUMAN_GZ_READER");
         const bool off = how && (!strcmp(how, "host") || !strcmp(how, "device-text"));
         const bool named = how && !strcmp(how, "device");
-        const bool by_host = a->keep_human == 0 && !(gzip_family && o1.enc && o1.enc->takes_device_spans() &&
-                                                     (!rs.paired || (o2.enc && o2.enc->takes_device_spans())));
+        const bool by_host = a->keep_human == 0 && !sh.outs_take_hbm;
         // (a masked run whose outputs are written by the host: every byte leaves through it, as the kept reads of a normal run
         // do -- the same choice; with GPU gzip outputs nothing does and the reader on the GPU is taken, profiles/mask_e2e.txt)
-        const bool text_to_host = host_text_wanted || (mask && !mask_in_hbm);
+        const bool text_to_host = host_text_wanted || (sh.mask && !sh.mask_in_hbm);
         dev_reader1 = !off && dev_gunzip_wants(a->in1) && (named || device_reader_pays(a->in1, mean_rec, text_to_host, by_host));
         dev_reader2 = rs.paired && !off && dev_gunzip_wants(a->in2) && (named || device_reader_pays(a->in2, mean_rec, text_to_host, by_host));
         if (rs.paired && !named && dev_reader1 != dev_reader2 && dev_gunzip_wants(a->in1) && dev_gunzip_wants(a->in2)) dev_reader1 = dev_reader2 = false;
@@ -1860,57 +1907,56 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
             dev_reader1 = false;
             if (!host_text_wanted) pool1.first_reserve = 0, prefill1 = 0;
         }
-        if (getenv("NOHUMAN_TRACE"))
+        if (sh.trace)
             fprintf(stderr, "[nohuman trace] gzip reader: %s%s%s\n", dev_reader1 ? "GPU" : "host", rs.paired ? (dev_reader2 ? " / GPU" : " / host") : "",
                     how ? " (NOHUMAN_GZ_READER)" : "");
         // batches of the reader on the GPU carry no host text unless an output needs it: no page-locked buffers made ahead for them
         if (dev_reader1 && !host_text_wanted) pool1.first_reserve = 0, prefill1 = 0;
         if (dev_reader2 && !host_text_wanted) pool2.first_reserve = 0, prefill2 = 0;
+        if (prefill1) pool1.start_prefill(prefill1);
+        if (rs.paired && prefill2) pool2.start_prefill(prefill2);
+        // gzip inputs are inflated by `threads` workers in all, shared between the files
+        unsigned gz_threads = (a->threads ? a->threads : 1) / (unsigned)mates;
+        if (gz_threads < 1) gz_threads = 1;
+        if (gz_threads > 16) gz_threads = 16;  // beyond that the record parser of the file is the limit
+        unsigned gz_threads2 = gz_threads;
+        if (split_readers) gz_threads2 = std::min(16u, std::max(1u, a->threads ? a->threads : 1u));  // (file 1's reader is on the GPU: every worker to file 2)
+        // gzip inputs are read on the GPU (nh_gunzip.hip): file 1 on the first device, file 2 on the second where there is one
+        // ... piece by piece over the run's devices (the compressed ranges are the shards): file 1 starts on the
+        // first device, file 2 on the second, so the two files' pieces of the same moment sit on different GPUs
+        std::vector<int> devs1, devs2;
+        for (int g = 0; g < G; g++) {
+            devs1.push_back(engines[(size_t)g]->device);
+            devs2.push_back(engines[(size_t)((g + 1) % G)]->device);
+        }
+        if (getenv("NOHUMAN_GZ_SHARD") && getenv("NOHUMAN_GZ_SHARD")[0] == '0') devs1.resize(1), devs2.resize(1);  // (A / B: a file's reader on one device)
+        if (const char *e = getenv("NOHUMAN_GZ_LANES")) {  // tuning knob: several lanes of the reader on ONE device (pieces decoded ahead there)
+            const int n = atoi(e);
+            while (G == 1 && (int)devs1.size() < n && n <= 4) devs1.push_back(devs1[0]), devs2.push_back(devs2[0]);
+        }
+        // The hybrid reader (round 6, nh_gunzip.hip): the odd cells of each input's (then alternating) piece grid inflated by host workers
+        // beside the GPU's.  OFF unless asked for (NOHUMAN_GZ_HYBRID=n: n workers per file; 1: the run's threads less four, shared between
+        // the files): built for the runs whose kept text is re-encoded on the GPU -- there the chip's codec kernels, inflate and deflate in
+        // turn, are what the run waits for -- and measured there: 30.8 -> 24.7 Mreads/s on 40 M pairs (profiles/r06_hybrid.txt): a host
+        // piece's in-order part (stitching, CRC, copy, upload: 0.2 s) holds the file's stream up five times a file, and pieces decoded
+        // ahead lose the in-order reader's staged input.  Correct and covered; what would make it pay is written down there.
+        unsigned hybrid_threads = 0;
+        if (const char *e = getenv("NOHUMAN_GZ_HYBRID")) {
+            const int v = atoi(e);
+            const unsigned T = a->threads ? a->threads : 1;
+            const unsigned want = v <= 0 ? 0u : v == 1 ? std::max(1u, (T > 4 ? T - 4 : 1u) / (unsigned)mates) : (unsigned)v;
+            hybrid_threads = G == 1 ? std::min(16u, want) : 0u;  // (one device: the reader's lanes over several are untested with it)
+            if (sh.trace && (dev_reader1 || dev_reader2))
+                fprintf(stderr, "[nohuman trace] gzip reader: hybrid %s (%u host workers per file)\n", hybrid_threads ? "on" : "off", hybrid_threads);
+        }
+        t1 = std::thread(reader_main, a->in1, &q1, &rs, &pool1, &clk, 0, batch_frags, batch_text, gz_threads, devs1, dev_reader1, hybrid_threads);
+        if (rs.paired)
+            t2 = std::thread(reader_main, a->in2, &q2, &rs, &pool2, &clk, 1, batch_frags, batch_text, gz_threads2, devs2, dev_reader2, hybrid_threads);
     }
-    if (prefill1) pool1.start_prefill(prefill1);
-    if (rs.paired && prefill2) pool2.start_prefill(prefill2);
-    StageClock clk;
-    // gzip inputs are inflated by `threads` workers in all, shared between the files
-    unsigned gz_threads = (a->threads ? a->threads : 1) / (unsigned)mates;
-    if (gz_threads < 1) gz_threads = 1;
-    if (gz_threads > 16) gz_threads = 16;  // beyond that the record parser of the file is the limit
-    unsigned gz_threads2 = gz_threads;
-    if (split_readers) gz_threads2 = std::min(16u, std::max(1u, a->threads ? a->threads : 1u));  // (file 1's reader is on the GPU: every worker to file 2)
-    // gzip inputs are read on the GPU (nh_gunzip.hip): file 1 on the first device, file 2 on the second where there is one
-    // ... piece by piece over the run's devices (the compressed ranges are the shards): file 1 starts on the
-    // first device, file 2 on the second, so the two files' pieces of the same moment sit on different GPUs
-    std::vector<int> devs1, devs2;
-    for (int g = 0; g < G; g++) {
-        devs1.push_back(engines[(size_t)g]->device);
-        devs2.push_back(engines[(size_t)((g + 1) % G)]->device);
-    }
-    if (getenv("NOHUMAN_GZ_SHARD") && getenv("NOHUMAN_GZ_SHARD")[0] == '0') devs1.resize(1), devs2.resize(1);  // (A / B: a file's reader on one device)
-    if (const char *e = getenv("NOHUMAN_GZ_LANES")) {  // tuning knob: several lanes of the reader on ONE device (pieces decoded ahead there)
-        const int n = atoi(e);
-        while (G == 1 && (int)devs1.size() < n && n <= 4) devs1.push_back(devs1[0]), devs2.push_back(devs2[0]);
-    }
-    // The hybrid reader (round 6, nh_gunzip.hip): the odd cells of each input's (then alternating) piece grid inflated by host workers
-    // beside the GPU's.  OFF unless asked for (NOHUMAN_GZ_HYBRID=n: n workers per file; 1: the run's threads less four, shared between
-    // the files): built for the runs whose kept text is re-encoded on the GPU -- there the chip's codec kernels, inflate and deflate in
-    // turn, are what the run waits for -- and measured there: 30.8 -> 24.7 Mreads/s on 40 M pairs (profiles/r06_hybrid.txt): a host
-    // piece's in-order part (stitching, CRC, copy, upload: 0.2 s) holds the file's stream up five times a file, and pieces decoded
-    // ahead lose the in-order reader's staged input.  Correct and covered; what would make it pay is written down there.
-    unsigned hybrid_threads = 0;
-    if (const char *e = getenv("NOHUMAN_GZ_HYBRID")) {
-        const int v = atoi(e);
-        const unsigned T = a->threads ? a->threads : 1;
-        const unsigned want = v <= 0 ? 0u : v == 1 ? std::max(1u, (T > 4 ? T - 4 : 1u) / (unsigned)mates) : (unsigned)v;
-        hybrid_threads = G == 1 ? std::min(16u, want) : 0u;  // (one device: the reader's lanes over several are untested with it)
-        if (getenv("NOHUMAN_TRACE") && (dev_reader1 || dev_reader2))
-            fprintf(stderr, "[nohuman trace] gzip reader: hybrid %s (%u host workers per file)\n", hybrid_threads ? "on" : "off", hybrid_threads);
-    }
-    std::thread t1(reader_main, a->in1, &q1, &rs, &pool1, &clk, 0, BATCH_FRAGS, BATCH_TEXT, gz_threads, devs1, dev_reader1, hybrid_threads);
-    std::thread t2;
-    if (rs.paired)
-        t2 = std::thread(reader_main, a->in2, &q2, &rs, &pool2, &clk, 1, BATCH_FRAGS, BATCH_TEXT, gz_threads2, devs2, dev_reader2, hybrid_threads);
+
     // BAM output: the input's header, as the reader found it, is the first thing in every record output (a host span: the
     // encoder stages it), before the writer hands on the first batch's records
-    if (bamout) {
+    void write_bam_header() {
         std::string hdr;
         {
             std::unique_lock<std::mutex> lk(rs.hdr_mu);
@@ -1918,58 +1964,39 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
             hdr.swap(rs.bam_header);
         }
         if (hdr.empty()) rs.fail(NH_EIO, std::string(a->in1) + ": no BAM header to copy (the file is not the BAM it was when the run was checked)");
-        for (OutFile *f : {&o1, split_files ? &h1 : (OutFile *)nullptr}) {
-            if (!f || rs.failed()) continue;
-            int hrc = f->enc->write(hdr.data(), hdr.size());
-            if (!hrc) hrc = f->enc->settle();
+        for (OutFile *of : {&f.o1, sh.split_files ? &f.h1 : (OutFile *)nullptr}) {
+            if (!of || rs.failed()) continue;
+            int hrc = of->enc->write(hdr.data(), hdr.size());
+            if (!hrc) hrc = of->enc->settle();
             if (hrc) rs.fail(hrc, g_last_error);
         }
     }
 
-    // writer: consumes batches in order; each arrives after its stream was synchronised.  Two stages: the WRITER
-    // waits for the batch's stream, decides and formats (span lists, nothing is copied); the FLUSHER writes the spans
-    // of the batch before while the writer is on the next one -- a helper takes the second mate file, so that both files
-    // are written at the same time -- and only then gives the batch's buffers and its stream slot back.  (One thread did
-    // both in round 3: 35.5 GB of kept text leave through writev() at 12 GB/s, 2.9 s, and the 1.3 s of waiting and
-    // formatting came on top, profiles/r04_e2e.txt.)
-    struct FlushJob {
-        Batch b;
-        Spans s1, s2, sk, hs1, hs2;  // (hs1, hs2: a split run's classified records, one span a mate)
-        Spans sc, si;                // (the batch's part of the calls table and of the human ids, one span each)
-        Spans ts[2][NH_MAX_TAXON_OUTS];  // (per-taxon outputs: a span a mate and selector with records in the batch)
-        bool valid = false;  // (false: the run had failed when the batch arrived -- only its buffers go back)
-    };
-    BoundedQueue<Batch> wq((size_t)(NS * G));
-    BoundedQueue<std::unique_ptr<FlushJob>> fq(1);
-    std::mutex slot_mu;
-    std::condition_variable slot_cv;
-    std::mutex w2_mu;
-    std::condition_variable w2_cv;
-    int w2_state = 0;  // 0 idle, 1 flush requested, 2 done, -1 quit
-    Spans *w2_spans = nullptr, *w2_hspans = nullptr, *w2_tspans = nullptr;
-    int w2_rc = NH_OK;
-    std::string w2_err;
-    std::thread tw2;
-    if (rs.paired)
-        tw2 = std::thread([&] {
-            for (;;) {
-                std::unique_lock<std::mutex> lk(w2_mu);
-                w2_cv.wait(lk, [&] { return w2_state == 1 || w2_state == -1; });
-                if (w2_state == -1) return;
-                Spans *sp2 = w2_spans, *hsp2 = w2_hspans, *tsp2 = w2_tspans;
-                lk.unlock();
-                int frc = o2.flush(*sp2);
-                if (!frc && hsp2) frc = h2.flush(*hsp2);
-                for (int k = 0; k < K && !frc; k++)
-                    if (!tsp2[k].iov.empty()) frc = tx[1][k].flush(tsp2[k]);
-                lk.lock();
-                w2_rc = frc;
-                if (frc) w2_err = g_last_error;
-                w2_state = 2;
-                w2_cv.notify_all();
-            }
-        });
-    std::thread tf([&] {
+    // the flusher's helper: the second mate's files, written while the flusher writes the first's
+    void mate2_flusher_main() {
+        for (;;) {
+            std::unique_lock<std::mutex> lk(w2_mu);
+            w2_cv.wait(lk, [&] { return w2_state == 1 || w2_state == -1; });
+            if (w2_state == -1) return;
+            Spans *sp2 = w2_spans, *hsp2 = w2_hspans, *tsp2 = w2_tspans;
+            lk.unlock();
+            int frc = f.o2.flush(*sp2);
+            if (!frc && hsp2) frc = f.h2.flush(*hsp2);
+            for (int k = 0; k < sh.K && !frc; k++)
+                if (!tsp2[k].iov.empty()) frc = f.tx[1][k].flush(tsp2[k]);
+            lk.lock();
+            w2_rc = frc;
+            if (frc) w2_err = g_last_error;
+            w2_state = 2;
+            w2_cv.notify_all();
+        }
+    }
+
+    // The FLUSHER writes the spans of the batch before while the writer is on the next one -- a helper takes the second mate file, so
+    // that both files are written at the same time -- and only then gives the batch's buffers and its stream slot back.  (One thread
+    // did both in round 3: 35.5 GB of kept text leave through writev() at 12 GB/s, 2.9 s, and the 1.3 s of waiting and formatting
+    // came on top, profiles/r04_e2e.txt.)
+    void flusher_main() {
         std::unique_ptr<FlushJob> j;
         while (fq.pop(j)) {
             Slot &s = slots[j->b.slot];
@@ -1977,51 +2004,29 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
                 uint64_t c3 = StageClock::now();
                 (void)dev_set(s.e->device);
                 const Batch &b = j->b;
-                const size_t base2w = (b.len1 + 8 + 255) & ~(size_t)255;
                 // the batch's raw text is still in the slot's device buffer: an encoder on that GPU takes
                 // the kept records from there instead of a second trip over PCIe
                 // (a part that fetched its own host copy has its spans there: they are staged like any host memory)
-                // (a masked run's spans are the built text: in HBM, mapped here, or in the slot's page-locked copy)
-                if (o1.enc && !mask && !bamout) o1.enc->map_device(b.h1->text.data(), b.len1, s.d_text, s.e->device, b.h1->host_text_valid);
-                if (rs.paired && o2.enc && !mask)
-                    o2.enc->map_device(b.h2->text.data(), b.len2, (const char *)s.d_text + base2w, s.e->device, b.h2->host_text_valid);
-                if (mask_in_hbm)
-                    for (int m = 0; m < mates; m++) {
-                        Spans &ms = m ? j->s2 : j->s1;
-                        if (!ms.iov.empty()) (m ? o2 : o1).enc->map_device(ms.iov[0].iov_base, ms.iov[0].iov_len, s.mask.d_out[m], s.e->device, false);
-                    }
-                if (bam_in_hbm)  // (BAM output: the selected records of out1 in s1, of human_out1 in hs1, each one span)
-                    for (int o = 0; o < n_bout; o++) {
-                        Spans &bs = o ? j->hs1 : j->s1;
-                        if (!bs.iov.empty()) (o ? h1 : o1).enc->map_device(bs.iov[0].iov_base, bs.iov[0].iov_len, s.bam.d_out[o], s.e->device, false);
-                    }
-                // the classified records that only exist in HBM: their span's address is the device buffer's, never read on the host
-                if (human_in_hbm)
-                    for (int m = 0; m < mates; m++) {
-                        Spans &hs = m ? j->hs2 : j->hs1;
-                        if (!hs.iov.empty()) (m ? h2 : h1).enc->map_device(hs.iov[0].iov_base, hs.iov[0].iov_len, s.human.d_out[m], s.e->device, false);
-                    }
-                if (taxon_in_hbm)
-                    for (int m = 0; m < mates; m++)
-                        for (int k = 0; k < K; k++) {
-                            Spans &t = j->ts[m][k];
-                            if (!t.iov.empty()) tx[m][k].enc->map_device(t.iov[0].iov_base, t.iov[0].iov_len, t.iov[0].iov_base, s.e->device, false);
-                        }
+                // (a masked run's spans are the built text: in HBM, mapped below, or in the slot's page-locked copy)
+                if (f.o1.enc && !sh.mask && !sh.bamout) f.o1.enc->map_device(b.h1->text.data(), b.len1, s.d_text, s.e->device, b.h1->host_text_valid);
+                if (rs.paired && f.o2.enc && !sh.mask)
+                    f.o2.enc->map_device(b.h2->text.data(), b.len2, (const char *)s.d_text + b.base2(), s.e->device, b.h2->host_text_valid);
+                for (const auto &d : j->dev) d.first->enc->map_device(d.second.iov_base, d.second.iov_len, d.second.iov_base, s.e->device, false);
                 if (rs.paired) {
                     std::lock_guard<std::mutex> lk(w2_mu);
                     w2_spans = &j->s2;
-                    w2_hspans = split ? &j->hs2 : nullptr;
+                    w2_hspans = sh.split ? &j->hs2 : nullptr;
                     w2_tspans = j->ts[1];
                     w2_state = 1;
                     w2_cv.notify_all();
                 }
-                int wrc = o1.flush(j->s1);
-                if (!wrc && rs.want_k) wrc = ok.flush(j->sk);
-                if (!wrc && split_files) wrc = h1.flush(j->hs1);
-                for (int k = 0; k < K && !wrc; k++)
-                    if (!j->ts[0][k].iov.empty()) wrc = tx[0][k].flush(j->ts[0][k]);
-                if (!wrc && calls) wrc = oc.flush(j->sc);
-                if (!wrc && ids) wrc = oi.flush(j->si);
+                int wrc = f.o1.flush(j->s1);
+                if (!wrc && rs.want_k) wrc = f.ok.flush(j->sk);
+                if (!wrc && sh.split_files) wrc = f.h1.flush(j->hs1);
+                for (int k = 0; k < sh.K && !wrc; k++)
+                    if (!j->ts[0][k].iov.empty()) wrc = f.tx[0][k].flush(j->ts[0][k]);
+                if (!wrc && sh.calls) wrc = f.oc.flush(j->sc);
+                if (!wrc && sh.ids) wrc = f.oi.flush(j->si);
                 if (rs.paired) {
                     std::unique_lock<std::mutex> lk(w2_mu);
                     w2_cv.wait(lk, [&] { return w2_state == 2; });
@@ -2031,7 +2036,7 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
                 clk.ns[ST_WWRITE] += StageClock::now() - c3;
                 if (wrc) rs.fail(wrc, g_last_error);
             }
-            j->b.h1.reset();  // (the last part of a half gives it back to its pool: the deleter of take())
+            j->b.h1.reset();  // (the last part of a half gives it back to its pool: the deleter of next_batch's take)
             j->b.h2.reset();
             {
                 std::lock_guard<std::mutex> lk(slot_mu);
@@ -2039,8 +2044,55 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
             }
             slot_cv.notify_all();
         }
-    });
-    std::thread tw([&] {
+    }
+
+    // a batch whose text is only in HBM, and a kept record that must be rewritten (CRLF, "+id" line): fetch it
+    // (into a buffer of this part: the half itself may be in use by other parts -- Batch)
+    int fetch_text(Slot &s, Batch &b) {
+        int wrc = NH_OK;
+        auto need_fetch = [&](const HalfBatch &hb) {
+            if (hb.host_text_valid || sh.mask || sh.bamout) return false;
+            const size_t off = &hb == b.h1.get() ? b.off1 : b.off2;
+            const nh_result *const hres = s.host_res();
+            for (size_t i = 0; i < b.n; i++)
+                if (!hb.recs[off + i].raw_end && (hres[i].call != 0) == (a->keep_human != 0)) return true;
+            return false;
+        };
+        for (int m = 0; m < sh.mates && !wrc; m++) {
+            const HalfBatch &hb = m ? *b.h2 : *b.h1;
+            if (need_fetch(hb)) {
+                const size_t L = m ? b.len2 : b.len1;
+                std::unique_ptr<char[]> &dst = m ? b.fetch2 : b.fetch1;
+                dst.reset(new (std::nothrow) char[L + 64]);
+                if (!dst) wrc = set_error(NH_EOOM, "out of memory");
+                if (!wrc && hipMemcpy(dst.get(), (const char *)s.d_text + (m ? b.base2() : 0), L, hipMemcpyDeviceToHost) != hipSuccess)
+                    wrc = set_error(NH_EDEVICE, "fetching a batch's text from the device failed");
+                rs.text_fetched += L;
+            }
+        }
+        return wrc;
+    }
+
+    // read statistics: every length of the batch, by the class of its fragment (host or not) and its mate
+    void note_lengths(const Slot &s, const Batch &b) {
+        for (size_t i = 0; i < b.n; i++) {
+            const int c = s.host_res()[i].call != 0;
+            for (int m = 0; m < sh.mates; m++) {
+                const uint64_t L = s.h_len[i * sh.mates + m];
+                if (L >= (1u << 20)) {
+                    rs.len_long[c][m][L]++;
+                    continue;
+                }
+                std::vector<uint64_t> &h = rs.len_hist[c][m];
+                if (L >= h.size()) h.resize(std::max<size_t>(L + 1, std::min<size_t>(2 * h.size(), 1u << 20)), 0);
+                h[L]++;
+            }
+        }
+    }
+
+    // The WRITER consumes batches in order: it waits for the batch's stream, decides and formats (span lists, nothing is copied),
+    // turns the builders' totals into spans and hands the job to the flusher.
+    void writer_main() {
         Batch b;
         for (;;) {
             uint64_t c0 = StageClock::now();
@@ -2059,143 +2111,20 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
                 // (the error bits came with the results on the slot's stream: a copy of their own here would queue behind
                 // whatever else the device is running -- the gzip reader's kernels -- once a batch)
                 if (!wrc && *s.h_flag) wrc = check_error_flag(s.e);
+                if (!wrc) wrc = fetch_text(s, b);
                 if (!wrc) {
-                    const size_t base2w = (b.len1 + 8 + 255) & ~(size_t)255;
-                    // a batch whose text is only in HBM, and a kept record that must be rewritten (CRLF, "+id" line): fetch it
-                    // (into a buffer of this part: the half itself may be in use by other parts -- Batch)
-                    auto need_fetch = [&](const HalfBatch &hb) {
-                        if (hb.host_text_valid || mask || bamout) return false;
-                        const size_t off = &hb == b.h1.get() ? b.off1 : b.off2;
-                        const nh_result *const hres = s.host_res();
-                        for (size_t i = 0; i < b.n; i++)
-                            if (!hb.recs[off + i].raw_end && (hres[i].call != 0) == (a->keep_human != 0)) return true;
-                        return false;
-                    };
-                    for (int m = 0; m < (rs.paired ? 2 : 1) && !wrc; m++) {
-                        const HalfBatch &hb = m ? *b.h2 : *b.h1;
-                        if (need_fetch(hb)) {
-                            const size_t L = m ? b.len2 : b.len1;
-                            std::unique_ptr<char[]> &dst = m ? b.fetch2 : b.fetch1;
-                            dst.reset(new (std::nothrow) char[L + 64]);
-                            if (!dst) wrc = set_error(NH_EOOM, "out of memory");
-                            if (!wrc && hipMemcpy(dst.get(), (const char *)s.d_text + (m ? base2w : 0), L, hipMemcpyDeviceToHost) != hipSuccess)
-                                wrc = set_error(NH_EDEVICE, "fetching a batch's text from the device failed");
-                            rs.text_fetched += L;
-                        }
-                    }
-                }
-                if (!wrc) {
-                    format_batch(&rs, b, s, o1, o2, ok, !mask && !bamout);
-                    // BAM output: the records the builder selected, one span an output -- in HBM, or copied here
-                    add_event_ms(s.bam.ev, &rs.bam_kernel_ms);
-                    for (int o = 0; bamout && o < n_bout && !wrc; o++) {
-                        const size_t tot = (size_t)s.bam.h_total[o];
-                        rs.bam_bytes[o] += tot;
-                        const bool want_host = split_files ? o == 1 : a->keep_human != 0;
-                        for (size_t i = 0; i < b.n; i++) rs.bam_records[o] += (s.host_res()[i].call != 0) == want_host;
-                        if (!tot) continue;
-                        if (tot > s.bam.cap_out[o]) {
-                            wrc = set_error(NH_EDEVICE, "BAM-out builder: an output ends outside its buffer");
-                            break;
-                        }
-                        char *at = built_span(s.bam, o, tot, bam_in_hbm, rs, &wrc, "BAM-out buffers", "BAM records");
-                        if (o == 0) o1.add_raw(at, tot);
-                        else {
-                            j->hs1.iov.push_back({(void *)at, tot});
-                            j->hs1.is_scratch.push_back(0);
-                        }
-                    }
-                    // a masked run's records: the text the builder made, one span a mate -- in HBM, or copied here
-                    add_event_ms(s.mask.ev, &rs.mask_kernel_ms);
-                    for (int m = 0; mask && m < mates && !wrc; m++) {
-                        const size_t tot = (size_t)s.mask.h_total[m];
-                        rs.mask_bytes += tot;
-                        if (!tot) continue;
-                        char *at = built_span(s.mask, m, tot, mask_in_hbm, rs, &wrc, "masked-out buffers", "masked records");
-                        (m ? o2 : o1).add_raw(at, tot);
-                    }
-                    if (mask) {
-                        rs.mask_records += b.n * (size_t)mates;
-                        rs.mask_nblk += mask_blocks(b.n) * (uint64_t)mates;
-                        for (int m = 0; m < mates; m++) rs.mask_fast += s.mask.h_total[2 + m];
-                        for (size_t i = 0; i < b.n; i++) rs.mask_masked += (s.host_res()[i].call != 0) * (uint64_t)mates;
-                    }
-                    // a split run's classified records: the text the builder made, one span a mate -- in HBM, or copied here
-                    add_event_ms(s.human.ev, &rs.human_kernel_ms);
-                    for (int m = 0; split && m < mates && !wrc; m++) {
-                        const size_t tot = (size_t)s.human.h_total[m];
-                        rs.human_bytes += tot;
-                        if (!tot) continue;
-                        char *at = built_span(s.human, m, tot, human_in_hbm, rs, &wrc, "classified-out buffers", "classified records");
-                        Spans &hs = m ? j->hs2 : j->hs1;
-                        hs.iov.push_back({(void *)at, tot});
-                        hs.is_scratch.push_back(0);
-                    }
-                    if (split)
-                        for (size_t i = 0; i < b.n; i++) rs.human_records += s.host_res()[i].call != 0;
-                    // the per-taxon records: a mate's buffer with the bins in it -- in HBM, or copied here as far as the last bin
-                    // reaches -- and a span a bin that has bytes
-                    add_event_ms(s.taxon.ev, &rs.taxon_kernel_ms);
-                    for (int m = 0; taxa && m < mates && !wrc; m++) {
-                        const uint64_t *start = s.taxon.h_total + m * K, *bytes = s.taxon.h_total + 2 * K + m * K;
-                        size_t end = 0;
-                        for (int k = 0; k < K; k++)
-                            if (bytes[k]) end = (size_t)(start[k] + bytes[k]);
-                        if (!end) continue;
-                        if (end > s.taxon.cap_out[m]) {
-                            wrc = set_error(NH_EDEVICE, "per-taxon builder: a bin ends outside its buffer");
-                            break;
-                        }
-                        char *at = built_span(s.taxon, m, end, taxon_in_hbm, rs, &wrc, "per-taxon buffers", "per-taxon records");
-                        for (int k = 0; k < K; k++) {
-                            if (!bytes[k]) continue;
-                            rs.taxon_bytes += bytes[k];
-                            j->ts[m][k].iov.push_back({(void *)(at + start[k]), (size_t)bytes[k]});
-                            j->ts[m][k].is_scratch.push_back(0);
-                        }
-                    }
-                    for (size_t i = 0; taxa && i < b.n; i++) {
-                        const uint32_t call = s.h_res[i].call;
-                        const uint8_t bin = call && call < bin_of.size() ? bin_of[call] : 0xFF;
-                        if (bin < K) rs.taxon_frags[bin]++, rs.taxon_records++;
-                    }
-                    add_event_ms(s.lists.ev, &rs.list_kernel_ms);
-                    add_event_ms(s.qev, &rs.qmask_kernel_ms);
-                    add_event_ms(s.rev, &rs.rstats_kernel_ms);
-                    add_event_ms(s.mev, &rs.mdata_kernel_ms);
-                    add_event_ms(s.hev, &rs.host_kernel_ms);
-                    // read statistics: every length of the batch, by the class of its fragment (host or not) and its mate
-                    for (size_t i = 0; rst && i < b.n; i++) {
-                        const int c = s.host_res()[i].call != 0;
-                        for (int m = 0; m < mates; m++) {
-                            const uint64_t L = s.h_len[i * mates + m];
-                            if (L >= (1u << 20)) {
-                                rs.len_long[c][m][L]++;
-                                continue;
-                            }
-                            std::vector<uint64_t> &h = rs.len_hist[c][m];
-                            if (L >= h.size()) h.resize(std::max<size_t>(L + 1, std::min<size_t>(2 * h.size(), 1u << 20)), 0);
-                            h[L]++;
-                        }
-                    }
-                    // the read lists: exactly the built bytes, copied to the slot's page-locked memory, one span a file
-                    for (int o = 0; lists && o < 2 && !wrc; o++) {
-                        const size_t tot = (size_t)s.lists.h_total[o];
-                        rs.list_bytes[o] += tot;
-                        rs.list_lines[o] += s.lists.h_total[2 + o];
-                        if (!tot) continue;
-                        char *at = built_span(s.lists, o, tot, false, rs, &wrc, "read-list buffers", "read list");
-                        Spans &ls = o ? j->si : j->sc;
-                        ls.iov.push_back({(void *)at, tot});
-                        ls.is_scratch.push_back(0);
-                    }
+                    format_batch(&rs, b, s, f.o1, f.o2, f.ok, !sh.mask && !sh.bamout);
+                    for (const Builder &bd : builders) add_event_ms((s.*bd.out).ev, &(rs.*bd.ms));
+                    for (const Pass &ps : passes) add_event_ms(s.*ps.ev, &(rs.*ps.ms));
+                    if (sh.bamout) build_bam(SPANS, s, b, j.get(), &wrc);
+                    if (sh.mask) build_mask(SPANS, s, b, j.get(), &wrc);
+                    if (sh.split) build_human(SPANS, s, b, j.get(), &wrc);
+                    if (sh.taxa) build_taxon(SPANS, s, b, j.get(), &wrc);
+                    if (sh.rst) note_lengths(s, b);
+                    if (sh.lists) build_lists(SPANS, s, b, j.get(), &wrc);
                     clk.ns[ST_WFORMAT] += StageClock::now() - c2;
-                    j->s1 = std::move(o1.sp);
-                    j->s2 = std::move(o2.sp);
-                    j->sk = std::move(ok.sp);
-                    o1.sp.clear();
-                    o2.sp.clear();
-                    ok.sp.clear();
+                    j->s1 = std::move(f.o1.sp), j->s2 = std::move(f.o2.sp), j->sk = std::move(f.ok.sp);
+                    f.o1.sp.clear(), f.o2.sp.clear(), f.ok.sp.clear();
                     j->valid = true;
                 }
                 if (wrc) rs.fail(wrc, g_last_error);
@@ -2204,39 +2133,212 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
             fq.push(std::move(j));
         }
         fq.close();
-    });
+    }
+
+    // a split run's classified records (nh_split.hip): the text of both mates, one span a mate -- in HBM, or copied by the writer
+    void build_human(BuildStep step, Slot &s, const Batch &b, FlushJob *j, int *rc) {
+        const int mates = sh.mates;
+        if (step == RESERVE) {  // a mate's classified-out text: its records less what normalisation drops, plus 36 bytes a suffix
+            const size_t out_cap[2] = {b.len1 + b.n * 36 + 64, b.len2 + b.n * 36 + 64};
+            if (!*rc) *rc = slot_reserve_rec(s, b.n * (size_t)mates);
+            if (!*rc) *rc = built_reserve(s.human, 2 * human_out_blocks(b.n) + 2, out_cap, mates, "classified-out buffers");
+        } else if (step == LAUNCH) {
+            HumanOutArgs ha{};
+            batch_source(ha, s, b);
+            ha.res = (const nh_result *)(sh.hsel ? s.d_hres : s.d_res);  // (the call of a host fragment is the true call: the suffix carries it)
+            ha.ext = s.e->d_external, ha.n_ext = s.e->external.size();
+            ha.n = b.n, ha.nblk = human_out_blocks(b.n);
+            built_sink(ha, s.human, mates, s);
+            ha.total = s.human.d_total = ha.blk + 2 * ha.nblk;
+            timed_launch(rs, s.stream, s.human.ev, "classified-out builder", [&] { return launch_human_out(ha, s.stream); });
+        } else {
+            for (int m = 0; m < mates && !*rc; m++)
+                one_span(j, s.human, m, sh.human_in_hbm, m ? f.h2 : f.h1, m ? j->hs2 : j->hs1, &rs.human_bytes, rc, "classified-out buffers", "classified records");
+            for (size_t i = 0; i < b.n; i++) rs.human_records += s.host_res()[i].call != 0;
+        }
+    }
+
+    // the per-taxon records (nh_split.hip, k_tout_*): the classified records of both mates sorted into the selectors' bins -- a mate's
+    // buffer with the bins in it, in HBM or copied by the writer as far as the last bin reaches, and a span a bin that has bytes
+    void build_taxon(BuildStep step, Slot &s, const Batch &b, FlushJob *j, int *rc) {
+        const int mates = sh.mates, K = sh.K;
+        if (step == RESERVE) {  // a mate's bins: the classified-out text at most, and the bins' alignment
+            const size_t out_cap[2] = {b.len1 + b.n * 36 + 64 + 256 * (size_t)K, b.len2 + b.n * 36 + 64 + 256 * (size_t)K};
+            if (!*rc) *rc = slot_reserve_rec(s, b.n * (size_t)mates);
+            if (!*rc && !s.taxon.h_total && host_malloc((void **)&s.taxon.h_total, 4 * NH_MAX_TAXON_OUTS * sizeof(uint64_t), hipHostMallocDefault) != hipSuccess)
+                *rc = set_error(NH_EOOM, "cannot allocate batch buffers");
+            // (the scratch: block sums of every mate and bin, then start[2][K] and total[2][K]: TaxonOutArgs)
+            if (!*rc) *rc = built_reserve(s.taxon, 2 * (size_t)K * human_out_blocks(b.n) + 4 * (size_t)K, out_cap, mates, "per-taxon buffers");
+        } else if (step == LAUNCH) {
+            TaxonOutArgs ta{};
+            batch_source(ta, s, b);
+            ta.res = (const nh_result *)s.d_res;
+            ta.ext = s.e->d_external, ta.n_ext = s.e->external.size();
+            ta.n = b.n, ta.nblk = human_out_blocks(b.n);
+            built_sink(ta, s.taxon, mates, s);
+            ta.bin_of = dbuf[(size_t)b.dev_index].bin_of, ta.K = K;
+            ta.start = s.taxon.d_total = ta.blk + 2 * (uint64_t)K * ta.nblk;
+            ta.total = ta.start + 2 * K;
+            timed_launch(rs, s.stream, s.taxon.ev, "per-taxon builder", [&] { return launch_taxon_out(ta, s.stream); });
+        } else {
+            for (int m = 0; m < mates && !*rc; m++) {
+                const uint64_t *start = s.taxon.h_total + m * K, *bytes = s.taxon.h_total + 2 * K + m * K;
+                size_t end = 0;
+                for (int k = 0; k < K; k++)
+                    if (bytes[k]) end = (size_t)(start[k] + bytes[k]);
+                if (!end) continue;
+                if (end > s.taxon.cap_out[m]) {
+                    *rc = set_error(NH_EDEVICE, "per-taxon builder: a bin ends outside its buffer");
+                    break;
+                }
+                char *at = built_span(s.taxon, m, end, sh.taxon_in_hbm, rs, rc, "per-taxon buffers", "per-taxon records");
+                for (int k = 0; k < K; k++) {
+                    if (!bytes[k]) continue;
+                    rs.taxon_bytes += bytes[k];
+                    add_built(j, f.tx[m][k], j->ts[m][k], at + start[k], (size_t)bytes[k], sh.taxon_in_hbm);
+                }
+            }
+            for (size_t i = 0; i < b.n; i++) {
+                const uint32_t call = s.h_res[i].call;
+                const uint8_t bin = call && call < bin_of.size() ? bin_of[call] : 0xFF;
+                if (bin < K) rs.taxon_frags[bin]++, rs.taxon_records++;
+            }
+        }
+    }
+
+    // a masked run's records (nh_mask.hip): every record of both mates, masked, one span a mate -- in HBM, or copied by the writer
+    void build_mask(BuildStep step, Slot &s, const Batch &b, FlushJob *j, int *rc) {
+        const int mates = sh.mates;
+        if (step == RESERVE) {  // a mate's masked text: its records less what normalisation drops, plus a final newline each
+            const size_t out_cap[2] = {b.len1 + b.n + 64, b.len2 + b.n + 64};
+            if (!*rc) *rc = slot_reserve_rec(s, b.n * (size_t)mates);
+            // (the scratch: block offsets, totals and FAST counts, block flags: MaskArgs)
+            if (!*rc) *rc = built_reserve(s.mask, 3 * mask_blocks(b.n) + 4, out_cap, mates, "masked-out buffers");
+        } else if (step == LAUNCH) {
+            MaskArgs ma{};
+            batch_source(ma, s, b);
+            ma.res = (const nh_result *)(sh.hsel ? s.d_hres : s.d_res);
+            ma.n = b.n, ma.nblk = mask_blocks(b.n);
+            built_sink(ma, s.mask, mates, s);
+            ma.total = s.mask.d_total = ma.blk + 2 * ma.nblk;
+            ma.fast = (uint32_t *)(ma.total + 4);
+            timed_launch(rs, s.stream, s.mask.ev, "mask builder", [&] { return launch_mask(ma, s.stream); });
+        } else {
+            for (int m = 0; m < mates && !*rc; m++) {
+                OutFile &of = m ? f.o2 : f.o1;  // (its span list is the batch's, empty in such a run: the writer moves it into the job)
+                one_span(j, s.mask, m, sh.mask_in_hbm, of, of.sp, &rs.mask_bytes, rc, "masked-out buffers", "masked records");
+            }
+            rs.mask_records += b.n * (size_t)mates;
+            rs.mask_nblk += mask_blocks(b.n) * (uint64_t)mates;
+            for (int m = 0; m < mates; m++) rs.mask_fast += s.mask.h_total[2 + m];
+            for (size_t i = 0; i < b.n; i++) rs.mask_masked += (s.host_res()[i].call != 0) * (uint64_t)mates;
+        }
+    }
+
+    // BAM output (nh_bamout.hip): the selected records of the input's BAM bytes, compacted -- out1's [0] and, a split run, human_out1's
+    // [1], one span an output, in HBM or copied by the writer
+    void build_bam(BuildStep step, Slot &s, const Batch &b, FlushJob *j, int *rc) {
+        const int n_bout = sh.n_bout;
+        if (step == RESERVE) {  // an output's records: the batch's BAM bytes at most
+            const size_t out_cap[2] = {b.h1->bam_len + 64, b.h1->bam_len + 64};
+            if (!*rc && (!b.h1->dev_bam || !b.h1->dev_bam_table || b.h1->dev_device != s.e->device))
+                *rc = set_error(NH_EDEVICE, "BAM output: a batch without its BAM bytes on the device that classifies it");
+            // (the scratch: block offsets of every output, totals: BamOutArgs)
+            if (!*rc) *rc = built_reserve(s.bam, (size_t)n_bout * bam_out_blocks(b.n) + 2, out_cap, n_bout, "BAM-out buffers");
+        } else if (step == LAUNCH) {
+            BamOutArgs ba{};
+            ba.bam = b.h1->dev_bam, ba.bam_len = b.h1->bam_len;
+            ba.table = b.h1->dev_bam_table + 2 * b.off1;  // (a part of a half: a range of its table)
+            ba.n = b.n, ba.nblk = bam_out_blocks(b.n);
+            ba.res = (const nh_result *)(sh.hsel ? s.d_hres : s.d_res);
+            ba.n_out = n_bout;
+            ba.want[0] = sh.split_files ? 0 : a->keep_human != 0;  // out1: the non-host records, with keep_human the host records
+            ba.want[1] = 1;                                         // human_out1: the host records
+            built_sink(ba, s.bam, n_bout, s);
+            ba.total = s.bam.d_total = ba.blk + (uint64_t)n_bout * ba.nblk;
+            ba.err_fields = ba.err_total = 256;
+            dev_check_ptr(ba.bam, s.e->device, "nh_run, a batch's BAM bytes");
+            dev_check_ptr(ba.table, s.e->device, "nh_run, a batch's BAM table");
+            timed_launch(rs, s.stream, s.bam.ev, "BAM-out builder", [&] { return launch_bam_out(ba, s.stream); });
+        } else {
+            for (int o = 0; o < n_bout && !*rc; o++) {
+                const size_t tot = (size_t)s.bam.h_total[o];
+                rs.bam_bytes[o] += tot;
+                const bool want_host = sh.split_files ? o == 1 : a->keep_human != 0;
+                for (size_t i = 0; i < b.n; i++) rs.bam_records[o] += (s.host_res()[i].call != 0) == want_host;
+                if (!tot) continue;
+                if (tot > s.bam.cap_out[o]) {
+                    *rc = set_error(NH_EDEVICE, "BAM-out builder: an output ends outside its buffer");
+                    break;
+                }
+                char *at = built_span(s.bam, o, tot, sh.bam_in_hbm, rs, rc, "BAM-out buffers", "BAM records");
+                // (out1's span list is the batch's, empty in such a run: the writer moves it into the job)
+                add_built(j, o ? f.h1 : f.o1, o ? j->hs1 : f.o1.sp, at, tot, sh.bam_in_hbm);
+            }
+        }
+    }
+
+    // the read lists (nh_calls.hip): the calls table [0] and the human ids [1] -- exactly the built bytes, copied to the slot's
+    // page-locked memory, one span a file
+    void build_lists(BuildStep step, Slot &s, const Batch &b, FlushJob *j, int *rc) {
+        if (step == RESERVE) {
+            // a table line: "C\t", the id, then at most 1 + 20 + 1 + 21 + 1 + 3 * 11 bytes of numbers, separators and
+            // the newline; an id line: the id and a newline
+            uint64_t idsum = 0;
+            for (size_t i = 0; i < b.n; i++) idsum += b.h1->recs[b.off1 + i].idlen;
+            const size_t out_cap[2] = {sh.calls ? (size_t)idsum + b.n * 79 + 64 : 0, sh.ids ? (size_t)idsum + b.n + 64 : 0};
+            if (!*rc) *rc = slot_reserve_rec(s, b.n * (size_t)sh.mates);
+            if (!*rc) *rc = slot_reserve_idl(s, b.n);
+            // (the scratch: block offsets and line counts of both outputs, totals: CallsArgs)
+            if (!*rc) *rc = built_reserve(s.lists, 4 * calls_blocks(b.n) + 4, out_cap, 2, "read-list buffers");
+        } else if (step == LAUNCH) {
+            CallsArgs ca{};
+            batch_records(ca, s, b);
+            ca.idlen = (const uint32_t *)s.d_idl;
+            ca.res = (const nh_result *)s.d_res;
+            ca.res_ids = sh.hsel ? (const nh_result *)s.d_hres : nullptr;  // (the table keeps the true calls; the id list is the host fragments')
+            ca.ext = s.e->d_external, ca.n_ext = s.e->external.size();
+            ca.n = b.n, ca.nblk = calls_blocks(b.n);
+            ca.want[0] = sh.calls, ca.want[1] = sh.ids;
+            built_sink(ca, s.lists, 2, s);
+            ca.total = s.lists.d_total = ca.blk + 4 * ca.nblk;
+            timed_launch(rs, s.stream, s.lists.ev, "read-list builder", [&] { return launch_calls(ca, s.stream); });
+        } else {
+            for (int o = 0; o < 2 && !*rc; o++) {
+                rs.list_lines[o] += s.lists.h_total[2 + o];
+                one_span(j, s.lists, o, false, o ? f.oi : f.oc, o ? j->si : j->sc, &rs.list_bytes[o], rc, "read-list buffers", "read list");
+            }
+        }
+    }
 
     // main: pair halves, stage, launch
-    uint64_t batch_no = 0, frags_out = 0;  // (frags_out: the fragments of the batches before this one)
-    std::vector<uint64_t> home_turn((size_t)G, 0);
-    // the half of each file in hand and how many of its records have gone out (a half is normally used whole: Batch)
-    std::shared_ptr<HalfBatch> c1, c2;
-    size_t p1 = 0, p2 = 0, cl1 = 0, cl2 = 0;  // (cl: the half's bytes of text, read once, when it arrives)
-    auto take = [](BoundedQueue<std::unique_ptr<HalfBatch>> &q, BatchPool *pool, std::shared_ptr<HalfBatch> &c, size_t &pos, size_t &len) {
-        std::unique_ptr<HalfBatch> u;
-        if (!q.pop(u)) return false;
-        c = std::shared_ptr<HalfBatch>(u.release(), [pool](HalfBatch *h) { pool->put(std::unique_ptr<HalfBatch>(h)); });
-        pos = 0;
-        len = c->text.size();
-        return true;
-    };
-    for (;;) {
-        if (rs.failed()) break;
-        Batch b;
-        uint64_t m0 = StageClock::now();
-        if (!c1 && !take(q1, &pool1, c1, p1, cl1)) break;
-        if (rs.paired && !c2 && !take(q2, &pool2, c2, p2, cl2)) break;
+    void run() {
+        for (bool last = false; !last && !rs.failed();) {
+            Batch b;
+            const uint64_t m0 = StageClock::now();
+            if (!next_batch(b, &last) || (b.n > 0 && !submit(b, m0))) break;
+        }
+    }
+
+    // the next batch of the two files' halves; false: an input has ended (or the run was shut down)
+    bool next_batch(Batch &b, bool *last) {
+        auto take = [](BoundedQueue<std::unique_ptr<HalfBatch>> &q, BatchPool *pool, std::shared_ptr<HalfBatch> &c, size_t &pos, size_t &len) {
+            std::unique_ptr<HalfBatch> u;
+            if (!q.pop(u)) return false;
+            c = std::shared_ptr<HalfBatch>(u.release(), [pool](HalfBatch *h) { pool->put(std::unique_ptr<HalfBatch>(h)); });
+            pos = 0;
+            len = c->text.size();
+            return true;
+        };
+        if (!c1 && !take(q1, &pool1, c1, p1, cl1)) return false;
+        if (rs.paired && !c2 && !take(q2, &pool2, c2, p2, cl2)) return false;
         // kraken2 reads the files in lockstep and stops at the shorter one.  Both readers cut batches at the same record
         // counts, so the halves normally pair up whole; where they do not (see Batch) the shorter one decides and the rest of
         // the longer one pairs with the other file's next half -- no read is dropped, no run stopped
-        b.h1 = c1;
-        b.off1 = p1;
-        b.len1 = cl1;
+        b.h1 = c1, b.off1 = p1, b.len1 = cl1;
         b.n = c1->recs.size() - p1;
         if (rs.paired) {
-            b.h2 = c2;
-            b.off2 = p2;
-            b.len2 = cl2;
+            b.h2 = c2, b.off2 = p2, b.len2 = cl2;
             b.n = std::min(b.n, c2->recs.size() - p2);
             p2 += b.n;
         }
@@ -2244,485 +2346,472 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
         // a half that is used up is let go of HERE, not when the next one arrives: a reader on the GPU may need its buffer to
         // produce that next one (a piece smaller than a batch hands out nothing until the piece behind it is decoded)
         const bool done1 = p1 == c1->recs.size(), done2 = rs.paired && p2 == c2->recs.size();
-        const bool last = (done1 && c1->eof) || (done2 && c2->eof);
+        *last = (done1 && c1->eof) || (done2 && c2->eof);
         if (done1) c1.reset();
         if (done2) c2.reset();
-        if (b.n > 0) {
-            // the slot: in turn over all devices' slots -- but a batch born on a GPU (the gzip reader there) is classified
-            // on THAT device, in that device's slots in turn, unless they are all busy and another device has a free one
-            // (then its text crosses xGMI once); the writer takes the batches in the order they are pushed, whatever the slot
-            int si = (int)(batch_no % (uint64_t)(NS * G));
-            uint64_t m1 = StageClock::now();
-            clk.ns[ST_MPOP] += m1 - m0;
-            {
-                int home = -1;
-                if (G > 1 && b.h1->dev_text)
-                    for (int g = 0; g < G; g++)
-                        if (engines[(size_t)g]->device == b.h1->dev_device) {
-                            home = g;
+        return true;
+    }
+
+    // one batch through the stages; false: the run has failed in a way that ends the loop (the batch still goes to the writer,
+    // which gives its buffers back)
+    bool submit(Batch &b, uint64_t m0) {
+        const uint64_t m1 = StageClock::now();
+        clk.ns[ST_MPOP] += m1 - m0;
+        Slot &s = pick_slot(b);
+        const uint64_t m2 = StageClock::now();
+        clk.ns[ST_MSLOT] += m2 - m1;
+        int rc;
+        if (b.ntext() >= (1ull << 32))
+            rc = set_error(NH_EINVAL, "a batch of more than 4 GB of record text (its offsets are 32-bit): paired records of several kilobases each are not supported");
+        else rc = reserve(s, b);
+        if (rc) {
+            rs.fail(rc, g_last_error);
+            wq.push(std::move(b));
+            return false;
+        }
+        dev_check_ptr(s.d_text, s.e->device, "nh_run, a slot's text buffer");
+        const uint64_t nbases = gather(s, b);
+        // H2D, classify, D2H: all asynchronous on the slot's stream
+        const uint64_t m3 = StageClock::now();
+        clk.ns[ST_MGATHER] += m3 - m2;
+        const bool staged = stage_text(s, b);
+        launch(s, b, nbases, staged);
+        queue_results(s, b);
+        batch_no++;
+        frags_out += b.n;
+        wq.push(std::move(b));
+        clk.ns[ST_MLAUNCH] += StageClock::now() - m3;
+        return true;
+    }
+
+    // the slot: in turn over all devices' slots -- but a batch born on a GPU (the gzip reader there) is classified
+    // on THAT device, in that device's slots in turn, unless they are all busy and another device has a free one
+    // (then its text crosses xGMI once); the writer takes the batches in the order they are pushed, whatever the slot
+    Slot &pick_slot(Batch &b) {
+        const int G = sh.G, NS = sh.NS;
+        int si = (int)(batch_no % (uint64_t)(NS * G));
+        {
+            int home = -1;
+            if (G > 1 && b.h1->dev_text)
+                for (int g = 0; g < G; g++)
+                    if (engines[(size_t)g]->device == b.h1->dev_device) {
+                        home = g;
+                        break;
+                    }
+            std::unique_lock<std::mutex> lk(slot_mu);
+            if (home >= 0) {
+                si = home * NS + (int)(home_turn[(size_t)home]++ % (uint64_t)NS);
+                if (slots[(size_t)si].busy && !sh.bamout)  // (BAM output: the builder reads the batch's BAM bytes where they lie)
+                    for (int i = 0; i < NS * G; i++)
+                        if (!slots[(size_t)i].busy) {
+                            si = i;
                             break;
                         }
-                std::unique_lock<std::mutex> lk(slot_mu);
-                if (home >= 0) {
-                    si = home * NS + (int)(home_turn[(size_t)home]++ % (uint64_t)NS);
-                    if (slots[(size_t)si].busy && !bamout)  // (BAM output: the builder reads the batch's BAM bytes where they lie)
-                        for (int k = 0; k < NS * G; k++)
-                            if (!slots[(size_t)k].busy) {
-                                si = k;
-                                break;
-                            }
-                }
-                slot_cv.wait(lk, [&] { return !slots[(size_t)si].busy; });
-                slots[(size_t)si].busy = true;
             }
-            Slot &s = slots[si];
-            uint64_t m2 = StageClock::now();
-            clk.ns[ST_MSLOT] += m2 - m1;
-            b.slot = si;
-            b.dev_index = si / NS;
-            // (start, length) of every sequence inside the raw text: text of file 1 at byte 0 of the device
-            // buffer, text of file 2 behind it
-            const size_t len1 = b.len1, len2 = rs.paired ? b.len2 : 0;
-            const size_t base2 = (len1 + 8 + 255) & ~(size_t)255;
-            const size_t ntext = rs.paired ? base2 + len2 : len1;
-            if (ntext >= (1ull << 32)) {
-                rs.fail(NH_EINVAL, "a batch of more than 4 GB of record text (its offsets are 32-bit): paired records of several kilobases each are not supported");
-                wq.push(std::move(b));
-                break;
+            slot_cv.wait(lk, [&] { return !slots[(size_t)si].busy; });
+            slots[(size_t)si].busy = true;
+        }
+        b.slot = si;
+        b.dev_index = si / NS;
+        return slots[(size_t)si];
+    }
+
+    // the slot's buffers for this batch, every active feature's; then the refusal of a record the quality passes cannot read
+    int reserve(Slot &s, const Batch &b) {
+        uint64_t ntaxa = 0;
+        for (size_t i = 0; rs.want_k && i < b.n; i++) ntaxa += b.kmer_taxa(i, s.e->info.k);
+        int rc = slot_reserve(s, b.ntext(), b.n, ntaxa + 1);
+        if (sh.split) build_human(RESERVE, s, b, nullptr, &rc);
+        if (sh.taxa) build_taxon(RESERVE, s, b, nullptr, &rc);
+        if (sh.mask) build_mask(RESERVE, s, b, nullptr, &rc);
+        if (sh.bamout) build_bam(RESERVE, s, b, nullptr, &rc);
+        if (sh.lists) build_lists(RESERVE, s, b, nullptr, &rc);
+        if (!rc && sh.qm) rc = slot_reserve_qmask(s, b.ntext(), b.n * (size_t)sh.mates);
+        if (!rc && sh.rst) rc = slot_reserve_rec(s, b.n * (size_t)sh.mates);
+        if (!rc && sh.hsel) rc = slot_reserve_hres(s, b.n);
+        if (!rc && (sh.qm || sh.rst)) rc = check_quality_lengths(b);
+        return rc;
+    }
+
+    // kraken2 ends a run at a FASTQ record whose quality line is not as long as its sequence when it masks by quality;
+    // the read statistics count a base per quality as well
+    int check_quality_lengths(const Batch &b) {
+        for (size_t i = 0; i < b.n; i++)
+            for (int m = 0; m < sh.mates; m++) {
+                const HalfBatch &hb = m ? *b.h2 : *b.h1;
+                const RecRef &rr = hb.recs[(m ? b.off2 : b.off1) + i];
+                if (hb.format == FMT_FASTQ && rr.qlen != rr.slen)
+                    return set_error(NH_EIO, "%s, read %llu: sequence length (%u) != quality string length (%u), which %s", m ? a->in2 : a->in1,
+                                     (unsigned long long)(frags_out + i + 1), rr.slen, rr.qlen,
+                                     sh.qm ? "--minimum-base-quality cannot mask" : "--read-stats cannot count");
             }
-            uint64_t ntaxa = 0;
-            const uint64_t k = s.e->info.k;
-            if (rs.want_k) {
-                for (size_t i = 0; i < b.n; i++) {
-                    const uint64_t l1 = b.h1->recs[b.off1 + i].slen;
-                    ntaxa += l1 >= k ? l1 - k + 1 : 0;
-                    if (rs.paired) {
-                        const uint64_t l2 = b.h2->recs[b.off2 + i].slen;
-                        ntaxa += (l2 >= k ? l2 - k + 1 : 0) + 1;
-                    }
-                }
-            }
-            rc = slot_reserve(s, ntext, b.n, ntaxa + 1);
-            if (!rc && split) {  // a mate's classified-out text: its records less what normalisation drops, plus 36 bytes a suffix
-                const size_t out_cap[2] = {len1 + b.n * 36 + 64, len2 + b.n * 36 + 64};
-                rc = slot_reserve_rec(s, b.n * (size_t)mates);
-                if (!rc) rc = built_reserve(s.human, 2 * human_out_blocks(b.n) + 2, out_cap, mates, "classified-out buffers");
-            }
-            if (!rc && taxa) {  // a mate's bins: the classified-out text at most, and the bins' alignment
-                const size_t out_cap[2] = {len1 + b.n * 36 + 64 + 256 * (size_t)K, len2 + b.n * 36 + 64 + 256 * (size_t)K};
-                rc = slot_reserve_rec(s, b.n * (size_t)mates);
-                if (!rc && !s.taxon.h_total && host_malloc((void **)&s.taxon.h_total, 4 * NH_MAX_TAXON_OUTS * sizeof(uint64_t), hipHostMallocDefault) != hipSuccess)
-                    rc = set_error(NH_EOOM, "cannot allocate batch buffers");
-                // (the scratch: block sums of every mate and bin, then start[2][K] and total[2][K]: TaxonOutArgs)
-                if (!rc) rc = built_reserve(s.taxon, 2 * (size_t)K * human_out_blocks(b.n) + 4 * (size_t)K, out_cap, mates, "per-taxon buffers");
-            }
-            if (!rc && mask) {  // a mate's masked text: its records less what normalisation drops, plus a final newline each
-                const size_t out_cap[2] = {len1 + b.n + 64, len2 + b.n + 64};
-                rc = slot_reserve_rec(s, b.n * (size_t)mates);
-                // (the scratch: block offsets, totals and FAST counts, block flags: MaskArgs)
-                if (!rc) rc = built_reserve(s.mask, 3 * mask_blocks(b.n) + 4, out_cap, mates, "masked-out buffers");
-            }
-            if (!rc && bamout) {  // an output's records: the batch's BAM bytes at most
-                const size_t out_cap[2] = {b.h1->bam_len + 64, b.h1->bam_len + 64};
-                if (!b.h1->dev_bam || !b.h1->dev_bam_table || b.h1->dev_device != s.e->device)
-                    rc = set_error(NH_EDEVICE, "BAM output: a batch without its BAM bytes on the device that classifies it");
-                // (the scratch: block offsets of every output, totals: BamOutArgs)
-                if (!rc) rc = built_reserve(s.bam, (size_t)n_bout * bam_out_blocks(b.n) + 2, out_cap, n_bout, "BAM-out buffers");
-            }
-            if (!rc && lists) {
-                // a table line: "C\t", the id, then at most 1 + 20 + 1 + 21 + 1 + 3 * 11 bytes of numbers, separators and
-                // the newline; an id line: the id and a newline
-                uint64_t idsum = 0;
-                for (size_t i = 0; i < b.n; i++) idsum += b.h1->recs[b.off1 + i].idlen;
-                const size_t out_cap[2] = {calls ? (size_t)idsum + b.n * 79 + 64 : 0, ids ? (size_t)idsum + b.n + 64 : 0};
-                rc = slot_reserve_rec(s, b.n * (size_t)mates);
-                if (!rc) rc = slot_reserve_idl(s, b.n);
-                // (the scratch: block offsets and line counts of both outputs, totals: CallsArgs)
-                if (!rc) rc = built_reserve(s.lists, 4 * calls_blocks(b.n) + 4, out_cap, 2, "read-list buffers");
-            }
-            if (!rc && qm) rc = slot_reserve_qmask(s, ntext, b.n * (size_t)mates);
-            if (!rc && rst) rc = slot_reserve_rec(s, b.n * (size_t)mates);
-            if (!rc && hsel) rc = slot_reserve_hres(s, b.n);
-            // kraken2 ends a run at a FASTQ record whose quality line is not as long as its sequence when it masks by quality;
-            // the read statistics count a base per quality as well
-            for (size_t i = 0; (qm || rst) && !rc && i < b.n; i++)
-                for (int m = 0; m < mates && !rc; m++) {
-                    const HalfBatch &hb = m ? *b.h2 : *b.h1;
-                    const RecRef &r = hb.recs[(m ? b.off2 : b.off1) + i];
-                    if (hb.format == FMT_FASTQ && r.qlen != r.slen)
-                        rc = set_error(NH_EIO, "%s, read %llu: sequence length (%u) != quality string length (%u), which %s",
-                                       m ? a->in2 : a->in1, (unsigned long long)(frags_out + i + 1), r.slen, r.qlen,
-                                       qm ? "--minimum-base-quality cannot mask" : "--read-stats cannot count");
-                }
-            if (rc) {
-                rs.fail(rc, g_last_error);
-                wq.push(std::move(b));
-                break;
-            }
-            dev_check_ptr(s.d_text, s.e->device, "nh_run, a slot's text buffer");
-            uint64_t nbases = 0, toff = 0;
-            for (size_t i = 0; i < b.n; i++) {
-                const RecRef &r1 = b.h1->recs[b.off1 + i];
-                s.h_off[i * mates] = r1.s;
-                s.h_len[i * mates] = r1.slen;
-                nbases += r1.slen;
-                if (lists) s.h_idl[i] = r1.idlen;
-                if (split || mask || lists || qm || rst || taxa) {
-                    uint32_t *hr = s.h_rec + 4 * i * mates;
-                    hr[0] = r1.h, hr[1] = r1.hlen, hr[2] = r1.q, hr[3] = r1.qlen;
-                    if (rs.paired) {
-                        const RecRef &r2 = b.h2->recs[b.off2 + i];
-                        hr[4] = (uint32_t)(base2 + r2.h), hr[5] = r2.hlen, hr[6] = (uint32_t)(base2 + r2.q), hr[7] = r2.qlen;
-                    }
-                }
-                if (rs.want_k) {
-                    s.h_taxa_off[i] = toff;
-                    toff += r1.slen >= k ? r1.slen - k + 1 : 0;
-                }
+        return NH_OK;
+    }
+
+    // (start, length) of every sequence inside the raw text -- text of file 1 at byte 0 of the device buffer, text of file 2
+    // behind it --, the record table, the id lengths, where each fragment's k-mer taxa go; returns the batch's bases
+    uint64_t gather(Slot &s, const Batch &b) {
+        const int mates = sh.mates;
+        const size_t base2 = b.base2();
+        uint64_t nbases = 0, toff = 0;
+        for (size_t i = 0; i < b.n; i++) {
+            const RecRef &r1 = b.h1->recs[b.off1 + i];
+            s.h_off[i * mates] = r1.s;
+            s.h_len[i * mates] = r1.slen;
+            nbases += r1.slen;
+            if (sh.lists) s.h_idl[i] = r1.idlen;
+            if (sh.want_rec) {
+                uint32_t *hr = s.h_rec + 4 * i * mates;
+                hr[0] = r1.h, hr[1] = r1.hlen, hr[2] = r1.q, hr[3] = r1.qlen;
                 if (rs.paired) {
                     const RecRef &r2 = b.h2->recs[b.off2 + i];
-                    s.h_off[i * mates + 1] = base2 + r2.s;
-                    s.h_len[i * mates + 1] = r2.slen;
-                    nbases += r2.slen;
-                    if (rs.want_k) toff += (r2.slen >= k ? r2.slen - k + 1 : 0) + 1;
+                    hr[4] = (uint32_t)(base2 + r2.h), hr[5] = r2.hlen, hr[6] = (uint32_t)(base2 + r2.q), hr[7] = r2.qlen;
                 }
             }
-            if (rs.want_k) s.h_taxa_off[b.n] = toff;
-            s.n_taxa = toff;
-            // H2D, classify, D2H: all asynchronous on the slot's stream
-            uint64_t m3 = StageClock::now();
-            clk.ns[ST_MGATHER] += m3 - m2;
-            hipError_t he = dev_set(s.e->device);
-            {   // test knob of the checker itself: the launch goes out under the run's FIRST device whatever slot carries it
-                static const bool brk = getenv("NOHUMAN_DEBUG_DEVICE_BREAK") != nullptr;
-                if (brk) he = dev_set(engines[0]->device);
+            if (rs.want_k) s.h_taxa_off[i] = toff, toff += b.kmer_taxa(i, s.e->info.k);
+            if (rs.paired) {
+                const RecRef &r2 = b.h2->recs[b.off2 + i];
+                s.h_off[i * mates + 1] = base2 + r2.s;
+                s.h_len[i * mates + 1] = r2.slen;
+                nbases += r2.slen;
             }
-            // the batch's text: from the host as it was read, or -- a batch of the reader on the GPU -- from HBM to HBM (from
-            // another device's memory: over xGMI); the bytes then go to the host only if an output written there needs them
-            auto stage_text = [&](HalfBatch &hb, size_t at, size_t len) -> hipError_t {
-                if (!len) return hipSuccess;
-                if (!hb.dev_text) return hipMemcpyAsync((char *)s.d_text + at, hb.text.data(), len, hipMemcpyHostToDevice, s.stream);
-                hipError_t e2 = dev_copy_between((char *)s.d_text + at, s.e->device, hb.dev_text, hb.dev_device, len, s.stream);
-                if (e2 == hipSuccess && host_text_wanted && !hb.host_text_valid) {  // (a half used in parts is fetched by its first)
-                    hb.text.clear();  // (a batch born on the GPU comes with a token buffer: the real one only where it is needed)
-                    if (!hb.text.reserve(len + 64)) return hipErrorOutOfMemory;
-                    hb.text.set_size(len);
-                    e2 = hipMemcpyAsync(hb.text.data(), (char *)s.d_text + at, len, hipMemcpyDeviceToHost, s.stream);
-                    rs.text_fetched += len;
-                    hb.host_text_valid = true;  // (once the stream has been synchronised: the writer does that first)
-                }
-                return e2;
-            };
-            if (he == hipSuccess) he = stage_text(*b.h1, 0, len1);
-            if (he == hipSuccess && rs.paired) he = stage_text(*b.h2, base2, len2);
-            if (he == hipSuccess)
-                he = hipMemcpyAsync(s.d_off, s.h_off, b.n * mates * 8, hipMemcpyHostToDevice, s.stream);
-            if (he == hipSuccess)
-                he = hipMemcpyAsync(s.d_len, s.h_len, b.n * mates * 4, hipMemcpyHostToDevice, s.stream);
-            if (he == hipSuccess && rs.want_k)
-                he = hipMemcpyAsync(s.d_taxa_off, s.h_taxa_off, (b.n + 1) * 8, hipMemcpyHostToDevice, s.stream);
-            if (he == hipSuccess && (split || mask || lists || qm || rst || taxa))
-                he = hipMemcpyAsync(s.d_rec, s.h_rec, b.n * mates * 16, hipMemcpyHostToDevice, s.stream);
-            if (he == hipSuccess && lists)
-                he = hipMemcpyAsync(s.d_idl, s.h_idl, b.n * 4, hipMemcpyHostToDevice, s.stream);
-            if (he != hipSuccess) {
-                rs.fail(NH_EDEVICE, std::string("H2D: ") + hipGetErrorString(he));
-            } else if (qm) {  // the sequences the classifier reads: a copy with 'N' where the quality is below minq
-                dev_check_ptr(s.d_qtext, s.e->device, "nh_run, a slot's quality-masked text");
-                QmaskArgs qa{};
-                qa.text = (const char *)s.d_text;
-                qa.ntext = ntext;
-                qa.seq_off = (const uint64_t *)s.d_off;
-                qa.seq_len = (const uint32_t *)s.d_len;
-                qa.rec = (const uint32_t *)s.d_rec;
-                qa.n = b.n * (uint64_t)mates;
-                qa.mates = mates;
-                qa.fastq[0] = b.h1->format == FMT_FASTQ;
-                qa.fastq[1] = rs.paired && b.h2->format == FMT_FASTQ;
-                qa.thresh = minq + 33;
-                qa.out = (char *)s.d_qtext;
-                qa.masked = s.d_qcnt;
-                qa.error = s.e->d_error + LAUNCH_SLOTS;
-                if (s.qev[0]) (void)hipEventRecord(s.qev[0], s.stream);
-                he = launch_qmask(qa, s.stream);
-                if (s.qev[1] && he == hipSuccess) he = hipEventRecord(s.qev[1], s.stream);
-                if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("quality mask: ") + hipGetErrorString(he));
-            }
-            if (!rs.failed()) {
-                rc = classify_device(s.e, qm ? s.d_qtext : s.d_text, s.d_off, b.n,
-                                     flags | (nbases / b.n > 2000 ? NH_FLAG_LONG : 0u), a->confidence, s.d_res,
-                                     rs.want_k ? s.d_taxa : nullptr, rs.want_k ? s.d_taxa_off : nullptr,
-                                     rs.d_run_counters[(size_t)(si / NS)], s.stream, s.d_len, ntext);
-                if (rc) rs.fail(rc, g_last_error);
-            }
-            // the results that decide host-ness from here on: the classifier's, or -- a host selection -- their copy with call = 0
-            // where the fragment is not host, made right behind the classifier on the same stream
-            const nh_result *const d_host_res = (const nh_result *)(hsel ? s.d_hres : s.d_res);
-            if (!rs.failed() && hsel) {
-                if (s.hev[0]) (void)hipEventRecord(s.hev[0], s.stream);
-                he = launch_host_filter(s.d_res, s.d_hres, b.n, dbuf[(size_t)(si / NS)].host_of, s.e->external.size(), dbuf[(size_t)(si / NS)].hcnt,
-                                        s.e->d_error + LAUNCH_SLOTS, s.stream);
-                if (s.hev[1] && he == hipSuccess) he = hipEventRecord(s.hev[1], s.stream);
-                if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("host filter: ") + hipGetErrorString(he));
-            }
-            if (!rs.failed() && rst) {  // the read statistics, counted behind the classifier on the same stream: the INPUT's bases
-                RstatsArgs ta{};
-                ta.text = (const char *)s.d_text;
-                ta.ntext = ntext;
-                ta.seq_off = (const uint64_t *)s.d_off;
-                ta.seq_len = (const uint32_t *)s.d_len;
-                ta.rec = (const uint32_t *)s.d_rec;
-                ta.n = b.n * (uint64_t)mates;
-                ta.mates = mates;
-                ta.fastq[0] = b.h1->format == FMT_FASTQ;
-                ta.fastq[1] = rs.paired && b.h2->format == FMT_FASTQ;
-                ta.res = d_host_res;
-                ta.acc = dbuf[(size_t)(si / NS)].racc;
-                ta.error = s.e->d_error + LAUNCH_SLOTS;
-                if (s.rev[0]) (void)hipEventRecord(s.rev[0], s.stream);
-                he = launch_rstats(ta, s.e->n_cu, 0, s.stream);
-                if (s.rev[1] && he == hipSuccess) he = hipEventRecord(s.rev[1], s.stream);
-                if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("read statistics: ") + hipGetErrorString(he));
-            }
-            if (!rs.failed() && mdt) {  // minimizer data, marked behind the classifier on the same stream: the text the classifier read
-                if (s.mev[0]) (void)hipEventRecord(s.mev[0], s.stream);
-                he = launch_mdata_mark(s.e, qm ? s.d_qtext : s.d_text, ntext, s.d_off, s.d_len, b.n, mates, dbuf[(size_t)(si / NS)].marks,
-                                       dbuf[(size_t)(si / NS)].groups, s.stream);
-                if (s.mev[1] && he == hipSuccess) he = hipEventRecord(s.mev[1], s.stream);
-                if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("minimizer data: ") + hipGetErrorString(he));
-            }
-            if (!rs.failed() && lists) {  // the calls table and the human ids, built behind the classifier on the same stream
-                CallsArgs ca{};
-                ca.text = (const char *)s.d_text;
-                ca.ntext = ntext;
-                ca.seq_len = (const uint32_t *)s.d_len;
-                ca.rec = (const uint32_t *)s.d_rec;
-                ca.idlen = (const uint32_t *)s.d_idl;
-                ca.res = (const nh_result *)s.d_res;
-                ca.res_ids = hsel ? d_host_res : nullptr;  // (the table keeps the true calls; the id list is the host fragments')
-                ca.ext = s.e->d_external;
-                ca.n_ext = s.e->external.size();
-                ca.n = b.n;
-                ca.nblk = calls_blocks(b.n);
-                ca.mates = mates;
-                ca.want[0] = calls != nullptr;
-                ca.want[1] = ids != nullptr;
-                for (int o = 0; o < 2; o++) ca.out[o] = s.lists.d_out[o], ca.cap[o] = s.lists.cap_out[o];
-                ca.blk = (uint64_t *)s.lists.d_blk;
-                ca.total = s.lists.d_total = ca.blk + 4 * ca.nblk;
-                ca.error = s.e->d_error + LAUNCH_SLOTS;
-                if (s.lists.ev[0]) (void)hipEventRecord(s.lists.ev[0], s.stream);
-                he = launch_calls(ca, s.stream);
-                if (s.lists.ev[1] && he == hipSuccess) he = hipEventRecord(s.lists.ev[1], s.stream);
-                if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("read-list builder: ") + hipGetErrorString(he));
-            }
-            if (!rs.failed() && split) {  // the classified records of both mates, built behind the classifier on the same stream
-                HumanOutArgs ha{};
-                ha.text = (const char *)s.d_text;
-                ha.ntext = ntext;
-                ha.seq_off = (const uint64_t *)s.d_off;
-                ha.seq_len = (const uint32_t *)s.d_len;
-                ha.rec = (const uint32_t *)s.d_rec;
-                ha.res = d_host_res;  // (the call of a host fragment is the true call: the suffix carries it)
-                ha.ext = s.e->d_external;
-                ha.n_ext = s.e->external.size();
-                ha.n = b.n;
-                ha.nblk = human_out_blocks(b.n);
-                ha.mates = mates;
-                ha.fastq[0] = b.h1->format == FMT_FASTQ;
-                ha.fastq[1] = rs.paired && b.h2->format == FMT_FASTQ;
-                for (int m = 0; m < mates; m++) ha.out[m] = s.human.d_out[m], ha.cap[m] = s.human.cap_out[m];
-                ha.blk = (uint64_t *)s.human.d_blk;
-                ha.total = s.human.d_total = ha.blk + 2 * ha.nblk;
-                ha.error = s.e->d_error + LAUNCH_SLOTS;
-                if (s.human.ev[0]) (void)hipEventRecord(s.human.ev[0], s.stream);
-                he = launch_human_out(ha, s.stream);
-                if (s.human.ev[1] && he == hipSuccess) he = hipEventRecord(s.human.ev[1], s.stream);
-                if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("classified-out builder: ") + hipGetErrorString(he));
-            }
-            if (!rs.failed() && bamout) {  // the selected records of the input's BAM bytes, compacted behind the classifier on the same stream
-                BamOutArgs ba{};
-                ba.bam = b.h1->dev_bam;
-                ba.bam_len = b.h1->bam_len;
-                ba.table = b.h1->dev_bam_table + 2 * b.off1;  // (a part of a half: a range of its table)
-                ba.n = b.n;
-                ba.nblk = bam_out_blocks(b.n);
-                ba.res = d_host_res;
-                ba.n_out = n_bout;
-                ba.want[0] = split_files ? 0 : a->keep_human != 0;  // out1: the non-host records, with keep_human the host records
-                ba.want[1] = 1;                                      // human_out1: the host records
-                for (int o = 0; o < n_bout; o++) ba.out[o] = s.bam.d_out[o], ba.cap[o] = s.bam.cap_out[o];
-                ba.blk = (uint64_t *)s.bam.d_blk;
-                ba.total = s.bam.d_total = ba.blk + (uint64_t)n_bout * ba.nblk;
-                ba.error = s.e->d_error + LAUNCH_SLOTS;
-                ba.err_fields = ba.err_total = 256;
-                dev_check_ptr(ba.bam, s.e->device, "nh_run, a batch's BAM bytes");
-                dev_check_ptr(ba.table, s.e->device, "nh_run, a batch's BAM table");
-                if (s.bam.ev[0]) (void)hipEventRecord(s.bam.ev[0], s.stream);
-                he = launch_bam_out(ba, s.stream);
-                if (s.bam.ev[1] && he == hipSuccess) he = hipEventRecord(s.bam.ev[1], s.stream);
-                if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("BAM-out builder: ") + hipGetErrorString(he));
-            }
-            if (!rs.failed() && taxa) {  // the classified records of both mates sorted into the selectors' bins, on the same stream
-                TaxonOutArgs ta{};
-                ta.text = (const char *)s.d_text;
-                ta.ntext = ntext;
-                ta.seq_off = (const uint64_t *)s.d_off;
-                ta.seq_len = (const uint32_t *)s.d_len;
-                ta.rec = (const uint32_t *)s.d_rec;
-                ta.res = (const nh_result *)s.d_res;
-                ta.ext = s.e->d_external;
-                ta.n_ext = s.e->external.size();
-                ta.n = b.n;
-                ta.nblk = human_out_blocks(b.n);
-                ta.mates = mates;
-                ta.fastq[0] = b.h1->format == FMT_FASTQ;
-                ta.fastq[1] = rs.paired && b.h2->format == FMT_FASTQ;
-                for (int m = 0; m < mates; m++) ta.out[m] = s.taxon.d_out[m], ta.cap[m] = s.taxon.cap_out[m];
-                ta.blk = (uint64_t *)s.taxon.d_blk;
-                ta.bin_of = dbuf[(size_t)(si / NS)].bin_of;
-                ta.K = K;
-                ta.start = s.taxon.d_total = ta.blk + 2 * (uint64_t)K * ta.nblk;
-                ta.total = ta.start + 2 * K;
-                ta.error = s.e->d_error + LAUNCH_SLOTS;
-                if (s.taxon.ev[0]) (void)hipEventRecord(s.taxon.ev[0], s.stream);
-                he = launch_taxon_out(ta, s.stream);
-                if (s.taxon.ev[1] && he == hipSuccess) he = hipEventRecord(s.taxon.ev[1], s.stream);
-                if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("per-taxon builder: ") + hipGetErrorString(he));
-            }
-            if (!rs.failed() && mask) {  // every record of both mates, masked, built behind the classifier on the same stream
-                MaskArgs ma{};
-                ma.text = (const char *)s.d_text;
-                ma.ntext = ntext;
-                ma.seq_off = (const uint64_t *)s.d_off;
-                ma.seq_len = (const uint32_t *)s.d_len;
-                ma.rec = (const uint32_t *)s.d_rec;
-                ma.res = d_host_res;
-                ma.n = b.n;
-                ma.nblk = mask_blocks(b.n);
-                ma.mates = mates;
-                ma.fastq[0] = b.h1->format == FMT_FASTQ;
-                ma.fastq[1] = rs.paired && b.h2->format == FMT_FASTQ;
-                for (int m = 0; m < mates; m++) ma.out[m] = s.mask.d_out[m], ma.cap[m] = s.mask.cap_out[m];
-                ma.blk = (uint64_t *)s.mask.d_blk;
-                ma.total = s.mask.d_total = ma.blk + 2 * ma.nblk;
-                ma.fast = (uint32_t *)(ma.total + 4);
-                ma.error = s.e->d_error + LAUNCH_SLOTS;
-                if (s.mask.ev[0]) (void)hipEventRecord(s.mask.ev[0], s.stream);
-                he = launch_mask(ma, s.stream);
-                if (s.mask.ev[1] && he == hipSuccess) he = hipEventRecord(s.mask.ev[1], s.stream);
-                if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("mask builder: ") + hipGetErrorString(he));
-            }
-            if (!rs.failed()) {
-                he = hipMemcpyAsync(s.h_res, s.d_res, b.n * sizeof(nh_result), hipMemcpyDeviceToHost, s.stream);
-                if (he == hipSuccess && hsel)
-                    he = hipMemcpyAsync(s.h_hres, s.d_hres, b.n * sizeof(nh_result), hipMemcpyDeviceToHost, s.stream);
-                if (he == hipSuccess)
-                    he = hipMemcpyAsync(s.h_flag, s.e->d_error + LAUNCH_SLOTS, sizeof(int), hipMemcpyDeviceToHost, s.stream);
-                if (he == hipSuccess && rs.want_k && toff)
-                    he = hipMemcpyAsync(s.h_taxa, s.d_taxa, toff * 4, hipMemcpyDeviceToHost, s.stream);
-                if (he == hipSuccess && split)
-                    he = hipMemcpyAsync(s.human.h_total, s.human.d_total, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
-                if (he == hipSuccess && bamout)
-                    he = hipMemcpyAsync(s.bam.h_total, s.bam.d_total, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
-                if (he == hipSuccess && taxa)
-                    he = hipMemcpyAsync(s.taxon.h_total, s.taxon.d_total, 4 * (size_t)K * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
-                if (he == hipSuccess && mask)
-                    he = hipMemcpyAsync(s.mask.h_total, s.mask.d_total, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
-                if (he == hipSuccess && lists)
-                    he = hipMemcpyAsync(s.lists.h_total, s.lists.d_total, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
-                if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("D2H: ") + hipGetErrorString(he));
-            }
-            batch_no++;
-            frags_out += b.n;
-            wq.push(std::move(b));
-            clk.ns[ST_MLAUNCH] += StageClock::now() - m3;
         }
-        if (last) break;
+        if (rs.want_k) s.h_taxa_off[b.n] = toff;
+        s.n_taxa = toff;
+        return nbases;
     }
-    // shut the pipeline down (also on errors): unblock readers, drain the writer
-    c1.reset();  // (a reader on the GPU waits in close() for every batch it handed out)
-    c2.reset();
-    pool1.stop();
-    pool2.stop();
-    q1.close();
-    q2.close();
-    wq.close();
-    {   // what the readers had queued is dropped (a batch born on the GPU gives its text buffer back: its reader waits for that)
-        std::unique_ptr<HalfBatch> drop;
-        while (q1.pop(drop)) drop.reset();
-        while (q2.pop(drop)) drop.reset();
+
+    // the batch's text and its tables onto the slot's stream; false: a copy failed (and failed the run)
+    bool stage_text(Slot &s, Batch &b) {
+        const int mates = sh.mates;
+        hipError_t he = dev_set(s.e->device);
+        // test knob of the checker itself: the launch goes out under the run's FIRST device whatever slot carries it
+        static const bool brk = getenv("NOHUMAN_DEBUG_DEVICE_BREAK") != nullptr;
+        if (brk) he = dev_set(engines[0]->device);
+        // the batch's text: from the host as it was read, or -- a batch of the reader on the GPU -- from HBM to HBM (from
+        // another device's memory: over xGMI); the bytes then go to the host only if an output written there needs them
+        auto half = [&](HalfBatch &hb, size_t at, size_t len) -> hipError_t {
+            if (!len) return hipSuccess;
+            if (!hb.dev_text) return hipMemcpyAsync((char *)s.d_text + at, hb.text.data(), len, hipMemcpyHostToDevice, s.stream);
+            hipError_t e2 = dev_copy_between((char *)s.d_text + at, s.e->device, hb.dev_text, hb.dev_device, len, s.stream);
+            if (e2 == hipSuccess && sh.host_text_wanted && !hb.host_text_valid) {  // (a half used in parts is fetched by its first)
+                hb.text.clear();  // (a batch born on the GPU comes with a token buffer: the real one only where it is needed)
+                if (!hb.text.reserve(len + 64)) return hipErrorOutOfMemory;
+                hb.text.set_size(len);
+                e2 = hipMemcpyAsync(hb.text.data(), (char *)s.d_text + at, len, hipMemcpyDeviceToHost, s.stream);
+                rs.text_fetched += len;
+                hb.host_text_valid = true;  // (once the stream has been synchronised: the writer does that first)
+            }
+            return e2;
+        };
+        if (he == hipSuccess) he = half(*b.h1, 0, b.len1);
+        if (he == hipSuccess && rs.paired) he = half(*b.h2, b.base2(), b.len2);
+        if (he == hipSuccess) he = hipMemcpyAsync(s.d_off, s.h_off, b.n * mates * 8, hipMemcpyHostToDevice, s.stream);
+        if (he == hipSuccess) he = hipMemcpyAsync(s.d_len, s.h_len, b.n * mates * 4, hipMemcpyHostToDevice, s.stream);
+        if (he == hipSuccess && rs.want_k) he = hipMemcpyAsync(s.d_taxa_off, s.h_taxa_off, (b.n + 1) * 8, hipMemcpyHostToDevice, s.stream);
+        if (he == hipSuccess && sh.want_rec) he = hipMemcpyAsync(s.d_rec, s.h_rec, b.n * mates * 16, hipMemcpyHostToDevice, s.stream);
+        if (he == hipSuccess && sh.lists) he = hipMemcpyAsync(s.d_idl, s.h_idl, b.n * 4, hipMemcpyHostToDevice, s.stream);
+        if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("H2D: ") + hipGetErrorString(he));
+        return he == hipSuccess;
     }
-    t1.join();
-    if (t2.joinable()) t2.join();
-    tw.join();
-    tf.join();
-    if (tw2.joinable()) {
-        {
-            std::lock_guard<std::mutex> lk(w2_mu);
-            w2_state = -1;
+
+    // the batch's launches on the slot's stream, in this order: the quality mask, the classifier, the host filter, the read
+    // statistics, the minimizer data's marks, then the builders -- lists, split, BAM out, per-taxon, mask.  Each goes out only
+    // while the run has not failed.
+    void launch(Slot &s, const Batch &b, uint64_t nbases, bool staged) {
+        const int mates = sh.mates;
+        const uint64_t ntext = b.ntext();
+        RunBuffers &db = dbuf[(size_t)b.dev_index];
+        int *const d_error = s.e->d_error + LAUNCH_SLOTS;
+        if (staged && sh.qm) {  // the sequences the classifier reads: a copy with 'N' where the quality is below minq
+            dev_check_ptr(s.d_qtext, s.e->device, "nh_run, a slot's quality-masked text");
+            QmaskArgs qa{};
+            batch_source(qa, s, b);
+            qa.n = b.n * (uint64_t)mates;
+            qa.thresh = sh.minq + 33;
+            qa.out = (char *)s.d_qtext, qa.masked = s.d_qcnt, qa.error = d_error;
+            timed_launch(rs, s.stream, s.qev, "quality mask", [&] { return launch_qmask(qa, s.stream); });
         }
-        w2_cv.notify_all();
-        tw2.join();
+        if (!rs.failed()) {
+            const int rc = classify_device(s.e, sh.qm ? s.d_qtext : s.d_text, s.d_off, b.n, sh.flags | (nbases / b.n > 2000 ? NH_FLAG_LONG : 0u),
+                                           a->confidence, s.d_res, rs.want_k ? s.d_taxa : nullptr, rs.want_k ? s.d_taxa_off : nullptr,
+                                           rs.d_run_counters[(size_t)b.dev_index], s.stream, s.d_len, ntext);
+            if (rc) rs.fail(rc, g_last_error);
+        }
+        // the results that decide host-ness from here on: the classifier's, or -- a host selection -- their copy with call = 0
+        // where the fragment is not host, made right behind the classifier on the same stream
+        if (!rs.failed() && sh.hsel)
+            timed_launch(rs, s.stream, s.hev, "host filter",
+                         [&] { return launch_host_filter(s.d_res, s.d_hres, b.n, db.host_of, s.e->external.size(), db.hcnt, d_error, s.stream); });
+        if (!rs.failed() && sh.rst) {  // the read statistics, counted behind the classifier on the same stream: the INPUT's bases
+            RstatsArgs ta{};
+            batch_source(ta, s, b);
+            ta.n = b.n * (uint64_t)mates;
+            ta.res = (const nh_result *)(sh.hsel ? s.d_hres : s.d_res);
+            ta.acc = db.racc, ta.error = d_error;
+            timed_launch(rs, s.stream, s.rev, "read statistics", [&] { return launch_rstats(ta, s.e->n_cu, 0, s.stream); });
+        }
+        if (!rs.failed() && sh.mdt)  // minimizer data, marked behind the classifier on the same stream: the text the classifier read
+            timed_launch(rs, s.stream, s.mev, "minimizer data", [&] {
+                return launch_mdata_mark(s.e, sh.qm ? s.d_qtext : s.d_text, ntext, s.d_off, s.d_len, b.n, mates, db.marks, db.groups, s.stream);
+            });
+        int none = NH_OK;  // (a launch fails the run itself)
+        if (!rs.failed() && sh.lists) build_lists(LAUNCH, s, b, nullptr, &none);
+        if (!rs.failed() && sh.split) build_human(LAUNCH, s, b, nullptr, &none);
+        if (!rs.failed() && sh.bamout) build_bam(LAUNCH, s, b, nullptr, &none);
+        if (!rs.failed() && sh.taxa) build_taxon(LAUNCH, s, b, nullptr, &none);
+        if (!rs.failed() && sh.mask) build_mask(LAUNCH, s, b, nullptr, &none);
     }
-    collect_qmask(slots, rs);
+
+    // the copies of the batch's results back to the host, behind its launches on the slot's stream
+    void queue_results(Slot &s, const Batch &b) {
+        if (rs.failed()) return;
+        hipError_t he = hipMemcpyAsync(s.h_res, s.d_res, b.n * sizeof(nh_result), hipMemcpyDeviceToHost, s.stream);
+        if (he == hipSuccess && sh.hsel) he = hipMemcpyAsync(s.h_hres, s.d_hres, b.n * sizeof(nh_result), hipMemcpyDeviceToHost, s.stream);
+        if (he == hipSuccess) he = hipMemcpyAsync(s.h_flag, s.e->d_error + LAUNCH_SLOTS, sizeof(int), hipMemcpyDeviceToHost, s.stream);
+        if (he == hipSuccess && rs.want_k && s.n_taxa) he = hipMemcpyAsync(s.h_taxa, s.d_taxa, s.n_taxa * 4, hipMemcpyDeviceToHost, s.stream);
+        for (const Builder &bd : builders) {
+            BuiltOut &o = s.*bd.out;
+            if (he == hipSuccess) he = hipMemcpyAsync(o.h_total, o.d_total, bd.total_words * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
+        }
+        if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("D2H: ") + hipGetErrorString(he));
+    }
+
+    // shuts the pipeline down (also on errors): unblocks the readers, drains the writer, joins every thread
+    void shutdown() {
+        c1.reset(), c2.reset();  // (a reader on the GPU waits in close() for every batch it handed out)
+        pool1.stop(), pool2.stop();
+        q1.close(), q2.close(), wq.close();
+        {   // what the readers had queued is dropped (a batch born on the GPU gives its text buffer back: its reader waits for that)
+            std::unique_ptr<HalfBatch> drop;
+            while (q1.pop(drop)) drop.reset();
+            while (q2.pop(drop)) drop.reset();
+        }
+        t1.join();
+        if (t2.joinable()) t2.join();
+        tw.join(), tf.join();
+        if (tw2.joinable()) {
+            {
+                std::lock_guard<std::mutex> lk(w2_mu);
+                w2_state = -1;
+            }
+            w2_cv.notify_all();
+            tw2.join();
+        }
+    }
+};
+}  // namespace
+
+// ---- after the pipeline -------------------------------------------------------------------------------
+// NOHUMAN_TRACE=1: where the wall time went, and a line a feature of the run
+static void print_run_trace(const RunShape &sh, RunState &rs, const StageClock &clk, double wall, const std::vector<nh_read_class> &racc,
+                            const MdataNumbers &mdn, double md_count_ms, const uint64_t dev_host[2]) {
+    static const char *names[] = {"read1", "read2", "rpush1", "rpush2", "main.pop", "main.slot", "main.gather",
+                                  "main.launch", "wr.pop", "wr.sync", "wr.format", "wr.write"};
+    const unsigned long long fetched = rs.text_fetched.load();
+    fprintf(stderr, "[nohuman trace] wall %.3fs |", wall);
+    for (int i = 0; i < 12; i++) fprintf(stderr, " %s %.3f", names[i], (double)clk.ns[i].load() * 1e-9);
+    fprintf(stderr, "\n");
+    if (sh.split)
+        fprintf(stderr, "[nohuman trace] human-out: %llu records, %llu bytes built on device; %llu fetched to host; builder kernels %.3f ms (%.1f GB/s of text)\n",
+                (unsigned long long)rs.human_records, (unsigned long long)rs.human_bytes, fetched,
+                rs.human_kernel_ms, rs.human_kernel_ms > 0 ? (double)rs.human_bytes / (rs.human_kernel_ms * 1e6) : 0.0);
+    if (sh.bamout)
+        fprintf(stderr, "[nohuman trace] bam-out: %llu + %llu records, %llu + %llu bytes selected on device; %llu fetched to host; builder kernels %.3f ms (%.1f GB/s of records)\n",
+                (unsigned long long)rs.bam_records[0], (unsigned long long)rs.bam_records[1], (unsigned long long)rs.bam_bytes[0],
+                (unsigned long long)rs.bam_bytes[1], fetched, rs.bam_kernel_ms,
+                rs.bam_kernel_ms > 0 ? (double)(rs.bam_bytes[0] + rs.bam_bytes[1]) / (rs.bam_kernel_ms * 1e6) : 0.0);
+    if (sh.mask)
+        fprintf(stderr, "[nohuman trace] mask: %llu records masked, %llu written, %llu bytes built on device; %llu fetched to host; builder kernels %.3f ms (%.1f GB/s of text); %llu of %llu blocks copied whole\n",
+                (unsigned long long)rs.mask_masked, (unsigned long long)rs.mask_records, (unsigned long long)rs.mask_bytes,
+                fetched, rs.mask_kernel_ms, rs.mask_kernel_ms > 0 ? (double)rs.mask_bytes / (rs.mask_kernel_ms * 1e6) : 0.0,
+                (unsigned long long)rs.mask_fast, (unsigned long long)rs.mask_nblk);
+    if (sh.taxa)
+        fprintf(stderr, "[nohuman trace] taxon-out: %llu records, %llu bytes built on device; %llu fetched to host; kernel %.3f ms\n",
+                (unsigned long long)rs.taxon_records, (unsigned long long)rs.taxon_bytes, fetched, rs.taxon_kernel_ms);
+    if (sh.lists)
+        fprintf(stderr, "[nohuman trace] calls: %llu lines, %llu bytes; ids: %llu lines, %llu bytes built on device; %llu fetched to host; builder kernels %.3f ms\n",
+                (unsigned long long)rs.list_lines[0], (unsigned long long)rs.list_bytes[0], (unsigned long long)rs.list_lines[1],
+                (unsigned long long)rs.list_bytes[1], fetched, rs.list_kernel_ms);
+    if (sh.qm)
+        fprintf(stderr, "[nohuman trace] qmask: Q %u, %llu of %llu bases masked, kernel %.3f ms\n", sh.minq,
+                (unsigned long long)rs.qmask_masked, (unsigned long long)rs.total_bases, rs.qmask_kernel_ms);
+    if (sh.rst && racc.size() == 4)
+        fprintf(stderr, "[nohuman trace] rstats: %llu bases, kernel %.3f ms\n",
+                (unsigned long long)(racc[0].bases + racc[1].bases + racc[2].bases + racc[3].bases), rs.rstats_kernel_ms);
+    if (sh.mdt && rs.err_code == NH_OK) {
+        unsigned long long groups = 0, distinct = 0;
+        for (uint64_t v : mdn.v[3]) groups += v;
+        for (uint64_t v : mdn.v[5]) distinct += v;
+        fprintf(stderr, "[nohuman trace] minimizer data: %llu hit groups on %llu distinct minimizers, k_mdata_mark %.3f ms, k_mdata_count %.3f ms\n", groups,
+                distinct, rs.mdata_kernel_ms, md_count_ms);
+    }
+    if (sh.hsel && rs.err_code == NH_OK)
+        fprintf(stderr, "[nohuman trace] host-filter: %llu host, %llu spared fragments; kernel %.3f ms\n", (unsigned long long)dev_host[0],
+                (unsigned long long)dev_host[1], rs.host_kernel_ms);
+    if (g_pageable_batches.load())
+        fprintf(stderr, "[nohuman trace] %d batch buffers could not be page-locked (pageable memory used)\n", g_pageable_batches.load());
+}
+
+// closes the outputs: the record files side by side (the last chunks of two GPU encoders, their buffers' release), then the
+// selectors' files, the -k file and the read lists one after the other
+static int close_run_files(RunFiles &f, const RunShape &sh, const RunState &rs) {
+    int rc = record_files_side_by_side(f, rs.paired, sh.split_files, [](OutFile &of, int) { return of.close(); });
+    if (rc) return rc;
+    for (int k = 0; k < sh.K; k++)
+        for (int m = 0; m < sh.mates; m++)
+            if ((rc = f.tx[m][k].close())) return rc;
+    if (rs.want_k && (rc = f.ok.close())) return rc;
+    if (sh.calls && (rc = f.oc.close())) return rc;
+    if (sh.ids && (rc = f.oi.close())) return rc;
+    return NH_OK;
+}
+
+// read statistics: the devices' sums and the writer's lengths into the run's nh_read_stats -- median and N50 from every length --,
+// checked against each other, written to the table and to the caller's struct
+static int finish_read_stats(const RunRequest &r, const RunState &rs, int mates, const std::vector<nh_read_class> &racc) {
+    nh_read_stats out;
+    memset(&out, 0, sizeof out);
+    out.mates = mates;
+    uint64_t dev_reads = 0, dev_bases = 0, host_reads = 0, host_bases = 0;
+    for (int m = 0; m < mates; m++) {
+        std::vector<std::pair<uint64_t, uint64_t>> lens[3];  // (length, reads) ascending: input, non-human, human
+        for (int c = 0; c < 2; c++) {
+            nh_read_class &k = out.cls[c][m];
+            k = racc[(size_t)(2 * c + m)];
+            if (!k.reads) k.min_len = 0;
+            dev_reads += k.reads, dev_bases += k.bases;
+            const std::vector<uint64_t> &h = rs.len_hist[c][m];
+            for (size_t L = 0; L < h.size(); L++)
+                if (h[L]) lens[1 + c].push_back({L, h[L]});
+            for (const auto &p : rs.len_long[c][m]) lens[1 + c].push_back(p);
+            for (const auto &p : lens[1 + c]) host_reads += p.second, host_bases += p.first * p.second;
+        }
+        // the input: the union of the two classes (both ascending)
+        std::map<uint64_t, uint64_t> all;
+        for (int c = 1; c < 3; c++)
+            for (const auto &p : lens[c]) all[p.first] += p.second;
+        lens[0].assign(all.begin(), all.end());
+        for (int set = 0; set < 3; set++) length_summary(lens[set], &out.median_len[set][m], &out.n50[set][m]);
+    }
+    // (the lengths the writer kept are the checker of what the devices counted, as for the run's counters)
+    if (dev_reads != host_reads || dev_bases != host_bases || dev_reads != rs.total * (uint64_t)mates)
+        return set_error(NH_EDEVICE, "read statistics: the devices counted %llu reads / %llu bases, the writer %llu / %llu",
+                         (unsigned long long)dev_reads, (unsigned long long)dev_bases, (unsigned long long)host_reads,
+                         (unsigned long long)host_bases);
+    if (r.rs_path)
+        if (const int rc = nh_read_stats_write(&out, r.rs_path)) return rc;
+    if (r.rs_out) *r.rs_out = out;
+    return NH_OK;
+}
+
+// minimizer data: the clade sums, checked against the classifier's own count of hit groups, fragment by fragment
+static int finish_mdata(const TaxoView &view, const RunState &rs, MdataNumbers &mdn) {
+    mdn.v[1] = rs.call_counts;
+    mdata_clades(view, mdn);
+    uint64_t groups = 0;
+    for (uint64_t i = 1; i < view.n; i++) groups += mdn.v[3][i];
+    if (groups != rs.hit_groups)
+        return set_error(NH_EDEVICE, "minimizer data: the pass counted %llu hit groups, the classifier %llu", (unsigned long long)groups,
+                         (unsigned long long)rs.hit_groups);
+    return NH_OK;
+}
+// ... and handed out: the table, the caller's array
+static int report_mdata(const TaxoView &view, const MdataNumbers &mdn, nh_minimizer_data *md) {
+    if (md->table)
+        if (const int rc = write_mdata_table(view, mdn, md->table)) return rc;
+    md->n_taxa = view.n > 1 ? (uint32_t)(view.n - 1) : 0;
+    for (uint64_t i = 1; md->taxa && i < view.n && i - 1 < md->taxa_cap; i++) {
+        nh_taxon_minimizers &o = md->taxa[i - 1];
+        o.taxid = view.field(i, 5);
+        o.reads_clade = mdn.v[0][i], o.reads_own = mdn.v[1][i], o.minimizers_clade = mdn.v[2][i], o.minimizers_own = mdn.v[3][i];
+        o.distinct_clade = mdn.v[4][i], o.distinct_own = mdn.v[5][i], o.db_cells_clade = mdn.v[6][i], o.db_cells_own = mdn.v[7][i];
+    }
+    return NH_OK;
+}
+
+// what run_engines refuses before it touches a device or a file: the arguments, unreadable inputs, an output that is an input
+static int check_run_files(const RunRequest &r, const RunState &rs) {
+    const nh_run_args *a = r.a;
+    if (rs.paired && !a->out2) return set_error(NH_EINVAL, "nh_run: paired input needs out2");
+    if (!(a->confidence >= 0.0 && a->confidence <= 1.0)) return set_error(NH_EINVAL, "Confidence score must be in the closed interval [0, 1]");
+    for (const char *p : {a->in1, a->in2}) {  // fail on unreadable inputs before creating outputs
+        if (!p) continue;
+        FILE *f = fopen(p, "rb");
+        if (!f) return set_error(NH_EIO, "cannot open %s", p);
+        fclose(f);
+    }
+    // outputs are created with O_TRUNC before the first input byte is read: an output that IS an input
+    // (same device and inode) would be emptied -- refuse (the CLI host stages its outputs and renames).  Only an output that is
+    // there, as a regular file, is looked at; for a plain nh_run this is the only such check.
+    const std::vector<RunFile> files = request_files(r, F_MDATA);
+    size_t inputs = 0;
+    while (inputs < files.size() && files[inputs].kind == F_INPUT) inputs++;
+    for (size_t c = inputs; c < files.size(); c++) {
+        struct stat so;
+        if (!files[c].path[0] || stat(files[c].path, &so) != 0 || !S_ISREG(so.st_mode)) continue;
+        if (const int rc = check_collision(files, c, inputs)) return rc;
+    }
+    if (a->out_codec < NH_CODEC_NONE || a->out_codec > NH_CODEC_BAM) return set_error(NH_EINVAL, "nh_run: unknown out_codec %d", a->out_codec);
+    return NH_OK;
+}
+
+int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_stats *stats) {
+    const nh_run_args *a = r.a;
+    if (!a || !a->in1 || !a->out1) return set_error(NH_EINVAL, "nh_run: in1 and out1 are required");
+    if (const int brc = check_bam_inputs(a)) return brc;
+    if (engines.empty()) return set_error(NH_EINVAL, "nh_run: no engine");
+    RunShape sh(r, engines.size());
+    // the features' tables, and what they ask of the database (it is open: before any input is read or any output created)
+    int rc;
+    std::vector<uint8_t> bin_of, host_of;  // per node of the taxonomy: the selector's bin, host or not
+    if (sh.taxa && (rc = selector_bins(engines[0], r, bin_of))) return rc;
+    for (size_t g = 0; sh.mdt && g < engines.size(); g++)
+        if ((rc = mdata_check_db(engines[g]))) return rc;
+    if (sh.hsel) {
+        if ((rc = host_table(engines[0], r.hf, host_of))) return rc;
+        r.hf->host_fragments = r.hf->spared_fragments = 0;
+    }
+    if (sh.split || sh.lists || sh.taxa)
+        for (Engine *e : engines)
+            if ((rc = ensure_device_external(e))) return rc;
+    RunState rs;
+    rs.a = a, rs.engines = engines;
+    rs.paired = a->in2 != nullptr;
+    rs.want_k = a->kraken_output && a->kraken_output[0] && strcmp(a->kraken_output, "/dev/null") != 0;
+    rs.call_counts.assign(engines[0]->external.size(), 0);
+    rs.dev_counts.assign(4 * engines.size(), 0);
+    if ((rc = check_run_files(r, rs))) return rc;
+    RunFiles files;
+    if ((rc = open_run_files(files, r, engines, rs.paired, rs.want_k))) return rc;
+    std::vector<RunBuffers> dbuf((size_t)sh.G);  // per device, for the run
+    Pipeline p(sh, rs, files, dbuf, bin_of);
+    p.batch_limits();
+    sh.set_outputs(a, rs, files);
+    auto t0 = std::chrono::steady_clock::now();
+
+    const size_t md_mark_bytes = sh.mdt ? (size_t)mdata_mark_words(engines[0]) * 4 : 0;
+    MdataNumbers mdn;  // [3] minimizers_own, [5] distinct_own, [7] db_cells_own, filled at the end of the run
+    double md_count_ms = 0;
+    std::vector<nh_read_class> racc;  // read statistics: the devices' blocks summed: [class][mate]
+    rs.d_run_counters.assign((size_t)sh.G, nullptr);
+    for (int g = 0; g < sh.G; g++) {
+        if ((rc = alloc_run_buffers(dbuf[g], engines[g], bin_of, host_of, sh.rst, md_mark_bytes, engines[0]->external.size(), sh.mdt))) return rc;
+        rs.d_run_counters[g] = dbuf[g].counters;
+    }
+    if ((rc = p.create_slots())) return rc;
+    p.start();
+    p.run();
+    p.shutdown();
+
+    collect_qmask(p.slots, rs);
     uint64_t dev_host[2] = {0, 0};  // host selection: the devices' {host, spared} fragments summed
-    if (hsel) collect_host_counts(dbuf, rs, dev_host);
-    if (rst) collect_rstats(dbuf, rs, racc);
-    if (mdt) collect_mdata(dbuf, rs, md_mark_bytes, mdn, &md_count_ms);
-    for (auto &s : slots) slot_free(s);
-    if (const char *tr = getenv("NOHUMAN_TRACE")) {
-        if (tr[0] == '1') {
-            static const char *names[] = {"read1", "read2", "rpush1", "rpush2", "main.pop", "main.slot", "main.gather",
-                                          "main.launch", "wr.pop", "wr.sync", "wr.format", "wr.write"};
-            fprintf(stderr, "[nohuman trace] wall %.3fs |",
-                    std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
-            for (int i = 0; i < 12; i++) fprintf(stderr, " %s %.3f", names[i], (double)clk.ns[i].load() * 1e-9);
-            fprintf(stderr, "\n");
-            if (split)
-                fprintf(stderr, "[nohuman trace] human-out: %llu records, %llu bytes built on device; %llu fetched to host; builder kernels %.3f ms (%.1f GB/s of text)\n",
-                        (unsigned long long)rs.human_records, (unsigned long long)rs.human_bytes, (unsigned long long)rs.text_fetched.load(),
-                        rs.human_kernel_ms, rs.human_kernel_ms > 0 ? (double)rs.human_bytes / (rs.human_kernel_ms * 1e6) : 0.0);
-            if (bamout)
-                fprintf(stderr, "[nohuman trace] bam-out: %llu + %llu records, %llu + %llu bytes selected on device; %llu fetched to host; builder kernels %.3f ms (%.1f GB/s of records)\n",
-                        (unsigned long long)rs.bam_records[0], (unsigned long long)rs.bam_records[1], (unsigned long long)rs.bam_bytes[0],
-                        (unsigned long long)rs.bam_bytes[1], (unsigned long long)rs.text_fetched.load(), rs.bam_kernel_ms,
-                        rs.bam_kernel_ms > 0 ? (double)(rs.bam_bytes[0] + rs.bam_bytes[1]) / (rs.bam_kernel_ms * 1e6) : 0.0);
-            if (mask)
-                fprintf(stderr, "[nohuman trace] mask: %llu records masked, %llu written, %llu bytes built on device; %llu fetched to host; builder kernels %.3f ms (%.1f GB/s of text); %llu of %llu blocks copied whole\n",
-                        (unsigned long long)rs.mask_masked, (unsigned long long)rs.mask_records, (unsigned long long)rs.mask_bytes,
-                        (unsigned long long)rs.text_fetched.load(), rs.mask_kernel_ms,
-                        rs.mask_kernel_ms > 0 ? (double)rs.mask_bytes / (rs.mask_kernel_ms * 1e6) : 0.0,
-                        (unsigned long long)rs.mask_fast, (unsigned long long)rs.mask_nblk);
-            if (taxa)
-                fprintf(stderr, "[nohuman trace] taxon-out: %llu records, %llu bytes built on device; %llu fetched to host; kernel %.3f ms\n",
-                        (unsigned long long)rs.taxon_records, (unsigned long long)rs.taxon_bytes, (unsigned long long)rs.text_fetched.load(),
-                        rs.taxon_kernel_ms);
-            if (lists)
-                fprintf(stderr, "[nohuman trace] calls: %llu lines, %llu bytes; ids: %llu lines, %llu bytes built on device; %llu fetched to host; builder kernels %.3f ms\n",
-                        (unsigned long long)rs.list_lines[0], (unsigned long long)rs.list_bytes[0], (unsigned long long)rs.list_lines[1],
-                        (unsigned long long)rs.list_bytes[1], (unsigned long long)rs.text_fetched.load(), rs.list_kernel_ms);
-            if (qm)
-                fprintf(stderr, "[nohuman trace] qmask: Q %u, %llu of %llu bases masked, kernel %.3f ms\n", minq,
-                        (unsigned long long)rs.qmask_masked, (unsigned long long)rs.total_bases, rs.qmask_kernel_ms);
-            if (rst && racc.size() == 4)
-                fprintf(stderr, "[nohuman trace] rstats: %llu bases, kernel %.3f ms\n",
-                        (unsigned long long)(racc[0].bases + racc[1].bases + racc[2].bases + racc[3].bases), rs.rstats_kernel_ms);
-            if (mdt && rs.err_code == NH_OK) {
-                unsigned long long groups = 0, distinct = 0;
-                for (uint64_t v : mdn.v[3]) groups += v;
-                for (uint64_t v : mdn.v[5]) distinct += v;
-                fprintf(stderr, "[nohuman trace] minimizer data: %llu hit groups on %llu distinct minimizers, k_mdata_mark %.3f ms, k_mdata_count %.3f ms\n", groups,
-                        distinct, rs.mdata_kernel_ms, md_count_ms);
-            }
-            if (hsel && rs.err_code == NH_OK)
-                fprintf(stderr, "[nohuman trace] host-filter: %llu host, %llu spared fragments; kernel %.3f ms\n", (unsigned long long)dev_host[0],
-                        (unsigned long long)dev_host[1], rs.host_kernel_ms);
-            if (g_pageable_batches.load())
-                fprintf(stderr, "[nohuman trace] %d batch buffers could not be page-locked (pageable memory used)\n",
-                        g_pageable_batches.load());
-        }
-    }
+    if (sh.hsel) collect_host_counts(dbuf, rs, dev_host);
+    if (sh.rst) collect_rstats(dbuf, rs, racc);
+    if (sh.mdt) collect_mdata(dbuf, rs, md_mark_bytes, mdn, &md_count_ms);
+    for (auto &s : p.slots) slot_free(s);
+    if (sh.trace_run)
+        print_run_trace(sh, rs, p.clk, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), racc, mdn, md_count_ms, dev_host);
     if (rs.err_code != NH_OK) return set_error(rs.err_code, "%s", rs.err_msg.c_str());
     if (dev_debug()) {  // NOHUMAN_DEBUG_DEVICE: a launch, copy or allocation under the wrong device fails the run that met it
         const std::string v = dev_violation(true);
@@ -2733,109 +2822,20 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
     if (rc) return rc;
 
     const TaxoView mdview = taxo_view(engines[0]);
-    if (mdt) {
-        mdn.v[1] = rs.call_counts;
-        mdata_clades(mdview, mdn);
-        // (the classifier's own count of hit groups, fragment by fragment, is the checker of what the pass counted)
-        uint64_t groups = 0;
-        for (uint64_t i = 1; i < mdview.n; i++) groups += mdn.v[3][i];
-        if (groups != rs.hit_groups)
-            return set_error(NH_EDEVICE, "minimizer data: the pass counted %llu hit groups, the classifier %llu", (unsigned long long)groups,
-                             (unsigned long long)rs.hit_groups);
-    }
+    if (sh.mdt && (rc = finish_mdata(mdview, rs, mdn))) return rc;
     const std::vector<uint64_t> md_report[2] = {mdn.v[2], mdn.v[4]};
     if (a->report && a->report[0] &&
-        (rc = write_report(engines[0], a->report, rs.call_counts, rs.total, rs.total - rs.classified, mdt && md->in_report ? md_report : nullptr)))
+        (rc = write_report(engines[0], a->report, rs.call_counts, rs.total, rs.total - rs.classified, sh.mdt && r.md->in_report ? md_report : nullptr)))
         return rc;
-    {  // (side by side as well: the last chunks of two GPU encoders, their buffers' release)
-        int rc2 = NH_OK;
-        std::string err2;
-        std::thread t2;
-        if (rs.paired)
-            t2 = std::thread([&] {
-                rc2 = o2.close();
-                if (rc2) err2 = g_last_error;
-            });
-        int rch1 = NH_OK, rch2 = NH_OK;
-        std::string errh1, errh2;
-        std::thread th1, th2;
-        if (split_files) {
-            th1 = std::thread([&] {
-                rch1 = h1.close();
-                if (rch1) errh1 = g_last_error;
-            });
-            if (rs.paired)
-                th2 = std::thread([&] {
-                    rch2 = h2.close();
-                    if (rch2) errh2 = g_last_error;
-                });
-        }
-        rc = o1.close();
-        if (t2.joinable()) t2.join();
-        if (th1.joinable()) th1.join();
-        if (th2.joinable()) th2.join();
-        if (rc) return rc;
-        if (rc2) return set_error(rc2, "%s", err2.c_str());
-        if (rch1) return set_error(rch1, "%s", errh1.c_str());
-        if (rch2) return set_error(rch2, "%s", errh2.c_str());
-    }
-    for (int k = 0; k < K; k++)
-        for (int m = 0; m < mates; m++)
-            if ((rc = tx[m][k].close())) return rc;
-    if (rs.want_k && (rc = ok.close())) return rc;
-    if (calls && (rc = oc.close())) return rc;
-    if (ids && (rc = oi.close())) return rc;
-    if (rst) {
-        nh_read_stats out;
-        memset(&out, 0, sizeof out);
-        out.mates = mates;
-        uint64_t dev_reads = 0, dev_bases = 0, host_reads = 0, host_bases = 0;
-        for (int m = 0; m < mates; m++) {
-            std::vector<std::pair<uint64_t, uint64_t>> lens[3];  // (length, reads) ascending: input, non-human, human
-            for (int c = 0; c < 2; c++) {
-                nh_read_class &k = out.cls[c][m];
-                k = racc[(size_t)(2 * c + m)];
-                if (!k.reads) k.min_len = 0;
-                dev_reads += k.reads, dev_bases += k.bases;
-                const std::vector<uint64_t> &h = rs.len_hist[c][m];
-                for (size_t L = 0; L < h.size(); L++)
-                    if (h[L]) lens[1 + c].push_back({L, h[L]});
-                for (const auto &p : rs.len_long[c][m]) lens[1 + c].push_back(p);
-                for (const auto &p : lens[1 + c]) host_reads += p.second, host_bases += p.first * p.second;
-            }
-            // the input: the union of the two classes (both ascending)
-            std::map<uint64_t, uint64_t> all;
-            for (int c = 1; c < 3; c++)
-                for (const auto &p : lens[c]) all[p.first] += p.second;
-            lens[0].assign(all.begin(), all.end());
-            for (int set = 0; set < 3; set++) length_summary(lens[set], &out.median_len[set][m], &out.n50[set][m]);
-        }
-        // (the lengths the writer kept are the checker of what the devices counted, as for the run's counters)
-        if (dev_reads != host_reads || dev_bases != host_bases || dev_reads != rs.total * (uint64_t)mates)
-            return set_error(NH_EDEVICE, "read statistics: the devices counted %llu reads / %llu bases, the writer %llu / %llu",
-                             (unsigned long long)dev_reads, (unsigned long long)dev_bases, (unsigned long long)host_reads,
-                             (unsigned long long)host_bases);
-        if (r.rs_path && (rc = nh_read_stats_write(&out, r.rs_path))) return rc;
-        if (r.rs_out) *r.rs_out = out;
-    }
-    for (int k = 0; k < K; k++) r.touts[k].fragments = rs.taxon_frags[k];
-    if (hsel) hf->host_fragments = rs.host_frags, hf->spared_fragments = rs.spared_frags;
-    if (mdt) {
-        if (md->table && (rc = write_mdata_table(mdview, mdn, md->table))) return rc;
-        md->n_taxa = mdview.n > 1 ? (uint32_t)(mdview.n - 1) : 0;
-        for (uint64_t i = 1; md->taxa && i < mdview.n && i - 1 < md->taxa_cap; i++) {
-            nh_taxon_minimizers &o = md->taxa[i - 1];
-            o.taxid = mdview.field(i, 5);
-            o.reads_clade = mdn.v[0][i], o.reads_own = mdn.v[1][i], o.minimizers_clade = mdn.v[2][i], o.minimizers_own = mdn.v[3][i];
-            o.distinct_clade = mdn.v[4][i], o.distinct_own = mdn.v[5][i], o.db_cells_clade = mdn.v[6][i], o.db_cells_own = mdn.v[7][i];
-        }
-    }
+    if ((rc = close_run_files(files, sh, rs))) return rc;
+    if (sh.rst && (rc = finish_read_stats(r, rs, sh.mates, racc))) return rc;
+    for (int k = 0; k < sh.K; k++) r.touts[k].fragments = rs.taxon_frags[k];
+    if (sh.hsel) r.hf->host_fragments = rs.host_frags, r.hf->spared_fragments = rs.spared_frags;
+    if (sh.mdt && (rc = report_mdata(mdview, mdn, r.md))) return rc;
     if (stats) {
         nh_stats st;
         memset(&st, 0, sizeof st);
-        st.total_sequences = rs.total;
-        st.classified = rs.classified;
-        st.unclassified = rs.total - rs.classified;
+        st.total_sequences = rs.total, st.classified = rs.classified, st.unclassified = rs.total - rs.classified;
         st.total_bases = rs.total_bases;
         st.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         *stats = st;
