@@ -827,6 +827,46 @@ int nh_extend_check(const nh_build_args *b, const nh_extend_args *x, nh_build_st
 int nh_dust_mask(int32_t device, char *text, uint64_t n_bytes, const uint64_t *seg_start, const uint64_t *seg_len, uint64_t n_seg,
                  uint64_t *masked_bases);
 
+/*
+ * Reads classified with their low-complexity stretches masked (--dust-reads; nh_dust.hip).  A table that holds the
+ * minimizers of poly-A tails or of (AC)n / (CAG)n microsatellites -- any database built without masking, of which the user may
+ * only have the three .k2d files -- calls a microbial read that carries such a stretch host.  With the pass enabled EVERY
+ * sequence of every batch, both mates, FASTA as well as FASTQ, is masked by the symmetric DUST of nh_dust_mask above, each sequence
+ * ON ITS OWN (one segment: no triplet spans two sequences), window 64 and threshold 2.0 fixed, and the classifier and the minimizer
+ * data's marks read the masked copy, in which a masked base is 'N', an ambiguous base to the scanner.
+ * Only classification changes: nh_result, the hit list of kraken_output (a masked stretch shows as "A:n"), the calls table, the
+ * report, the three totals, and what follows from the calls; total_kmers, the lengths and total_bases do not.
+ * THE DEVIATION OF nh_run_minq, FOR THE SAME REASON: EVERY RECORD WRITTEN KEEPS THE INPUT'S BASES, in every output -- a
+ * decontamination tool does not alter the reads it returns.  With a minimum base quality as well the classifier sees the union of
+ * the two masks; DUST is computed on the input's bases, not on the quality-masked ones.  Not enabled: nothing is allocated, copied
+ * or launched, and every output is byte for byte that of nh_run_host.
+ *
+ * nh_run_dust / nh_run_engine_dust: nh_run_host with the pass.  rd NULL or rd->enable == 0: exactly nh_run_host.  A struct_size
+ * smaller than the struct: NH_EINVAL before any device is touched, nothing created.  masked_bases receives the bases masked over
+ * the whole run, all devices summed (0 where the run fails after its arguments and its database were accepted; untouched before).
+ *
+ * nh_dust_reads_device: the pass itself on the engine's device, on `stream`.  Sequence i is d_text[d_seq_starts[i],
+ * +d_seq_lens[i]) (uint64 / uint32, the arrays of nh_classify_records_device, in any order).  d_out (text_len bytes) ALREADY HOLDS
+ * the sequences at the same offsets -- a copy of the text, or nh_quality_mask_device's output; every masked base becomes 'N' there
+ * and no other byte of it is written; d_text is only read.  d_masked (may be NULL): one uint64 the kernel adds to.  The entry
+ * allocates its scratch (8 bytes a sequence), waits for the stream and frees it.  n_seq == 0 launches nothing.  A sequence that
+ * leaves [0, text_len) is skipped -- nothing of it is read or written, the others are masked -- and sets a sticky error bit
+ * (value 512) that fails the engine's next blocking call or run with NH_EDEVICE.
+ */
+typedef struct {
+    uint32_t struct_size;   /* sizeof(nh_read_dust) of the caller */
+    uint32_t enable;        /* not 0: mask */
+    uint64_t masked_bases;  /* out */
+} nh_read_dust;
+int nh_run_dust(const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality, const char *read_stats_path,
+                nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs, nh_minimizer_data *md, nh_host_filter *hf,
+                nh_read_dust *rd, nh_stats *stats);
+int nh_run_engine_dust(nh_engine *e, const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality,
+                       const char *read_stats_path, nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs,
+                       nh_minimizer_data *md, nh_host_filter *hf, nh_read_dust *rd, nh_stats *stats);
+int nh_dust_reads_device(nh_engine *e, const void *d_text, uint64_t text_len, const void *d_seq_starts, const void *d_seq_lens,
+                         uint64_t n_seq, void *d_out, void *d_masked, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,6 @@
 // nh_dust.h -- low-complexity masking (symmetric DUST, window 64, threshold 2.0) on the device: what nh_dust.hip gives the
-// builder (nh_build.hip) and nh_dust_mask.  The definition: DESIGN.md 6.10; the model: tests/dust_model.py.
+// builder (nh_build.hip) and nh_dust_mask, and the runs with --dust-reads (nh_run.hip) and nh_dust_reads_device.  The definition:
+// DESIGN.md 6.10 and 6.18; the model: tests/dust_model.py.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -35,5 +36,27 @@ int dust_grid_max();
 // src is only read, so no tile sees what another one wrote.  A tile that leaves [0, text_len) is skipped.
 hipError_t launch_dust(const char *src, char *dst, uint64_t text_len, const DustTile *d_tiles, uint64_t n_tiles,
                        unsigned long long *d_count, int grid_max, hipStream_t stream);
+
+
+// The reads of one batch masked each on its own (k_rdust; nh_run_dust, nh_dust_reads_device): `out`, a buffer with the layout of
+// the text that already holds the sequences (a copy of the text, or the quality mask's output), gets 'N' at every masked base
+// of every sequence text[seq_off[i], +seq_len[i]); nothing else of it is written, the text is only read.
+struct ReadDustArgs {
+    const char *text;         // the batch's text (d_text), ntext bytes
+    uint64_t ntext;
+    const uint64_t *seq_off;  // n sequence starts (absolute), in any order
+    const uint32_t *seq_len;  // n sequence lengths
+    uint64_t n;               // sequences, at most 2^31
+    char *out;                // ntext bytes
+    unsigned long long *masked;  // NULL or one counter the waves add their masked bases to
+    int *error;               // the engine's sticky error word (bit 512: a sequence that leaves the text; it is skipped)
+    uint64_t nblk, *blk, *loc;   // (launch_read_dust's: the scratch, cut)
+};
+// words of scratch a launch over n sequences needs
+uint64_t read_dust_scratch_words(uint64_t n);
+// blocks of k_rdust that fill the current device once
+int read_dust_grid_max();
+// three launches on `stream`: the offsets of the sequences in the virtual text (two), the mask
+hipError_t launch_read_dust(ReadDustArgs a, uint64_t *scratch, int grid_max, hipStream_t stream);
 
 }  // namespace nh

@@ -994,6 +994,8 @@ int check_error_flag(Engine *e) {
             return set_error(NH_EDEVICE, "host filter: a fragment's call lies outside the taxonomy (written as unclassified, never used as an index)");
         if (flag & 256)
             return set_error(NH_EDEVICE, "BAM-out builder: a record lies outside its batch's BAM bytes or output buffer");
+        if (flag & 512)
+            return set_error(NH_EDEVICE, "read DUST: a sequence lies outside its batch's text (it was skipped: nothing of it was read or masked)");
         if (flag & 32)
             return set_error(NH_EIO,"quality mask / read statistics: a record's quality line is not as long as its sequence, or the record lies outside its batch's text");
         return set_error(NH_ECAPACITY, "a fragment hit more than 2048 distinct taxa");

@@ -30,6 +30,7 @@
 
 #include "nh_bam.h"
 #include "nh_codec.h"
+#include "nh_dust.h"
 #include "nh_fastx.h"
 #include "nh_gunzip.h"
 #include "nh_internal.h"
@@ -434,6 +435,14 @@ struct Slot {  // pinned host + device buffers of one in-flight batch
     unsigned long long *d_qcnt = nullptr;
     size_t cap_qtext = 0;
     hipEvent_t qev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around k_qmask
+    // runs that mask the reads' low-complexity stretches (nh_run_dust): d_qtext is reserved for them as well -- a copy of the text,
+    // or the quality mask's output, in which k_rdust (nh_dust.hip) writes 'N' --, the scratch of its scan, the masked bases of the
+    // slot's batches, the blocks that fill the slot's device once
+    uint64_t *d_dscr = nullptr;
+    size_t cap_dscr = 0;
+    unsigned long long *d_dcnt = nullptr;
+    int dust_grid = 0;
+    hipEvent_t duev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around the three launches of the read DUST
     hipEvent_t rev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around k_rstats (runs with read statistics)
     hipEvent_t mev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around k_mdata_mark (runs with minimizer data)
     // runs with a host selection (nh_run_host): the results with call = 0 where the fragment is not host (nh_host.hip) -- what
@@ -541,17 +550,43 @@ static int slot_reserve_idl(Slot &s, size_t n) { return slot_reserve_pair((void 
 // the second results array of nfrag fragments of a slot (runs with a host selection)
 static int slot_reserve_hres(Slot &s, size_t n) { return slot_reserve_pair((void **)&s.h_hres, &s.d_hres, &s.cap_hres, n, sizeof(nh_result), "host-filtered results"); }
 
-// the quality mask's buffers of a slot: the record table of nrec sequences, ntext bytes of masked text, the counter
-static int slot_reserve_qmask(Slot &s, size_t ntext, size_t nrec) {
-    const int rrc = slot_reserve_rec(s, nrec);
-    if (rrc) return rrc;
+// ntext bytes of masked text of a slot: what the classifier reads in a run with a minimum base quality or with --dust-reads
+static int slot_reserve_qtext(Slot &s, size_t ntext) {
     if (ntext + 64 > s.cap_qtext) {
         if (s.d_qtext) (void)hipFree(s.d_qtext);
         s.d_qtext = nullptr;
         s.cap_qtext = grow(ntext + 64);
         if (dev_malloc(&s.d_qtext, s.cap_qtext) != hipSuccess)
-            return set_error(NH_EOOM, "cannot allocate quality-mask buffers (%zu bytes)", s.cap_qtext);
+            return set_error(NH_EOOM, "cannot allocate the masked text (%zu bytes)", s.cap_qtext);
     }
+    return NH_OK;
+}
+
+// the read DUST's buffers of a slot: ntext bytes of masked text, the scan's scratch for nseq sequences, the counter
+static int slot_reserve_dust(Slot &s, size_t ntext, size_t nseq) {
+    const int trc = slot_reserve_qtext(s, ntext);
+    if (trc) return trc;
+    const size_t words = (size_t)read_dust_scratch_words(nseq);
+    if (words > s.cap_dscr) {
+        if (s.d_dscr) (void)hipFree(s.d_dscr);
+        s.d_dscr = nullptr;
+        s.cap_dscr = grow(words);
+        if (dev_malloc(&s.d_dscr, s.cap_dscr * 8) != hipSuccess) return set_error(NH_EOOM, "cannot allocate the read DUST's scratch (%zu words)", s.cap_dscr);
+    }
+    if (!s.d_dcnt) {
+        if (dev_malloc((void **)&s.d_dcnt, 8) != hipSuccess) return set_error(NH_EOOM, "cannot allocate batch buffers");
+        if (hipMemsetAsync(s.d_dcnt, 0, 8, s.stream) != hipSuccess) return set_error(NH_EDEVICE, "cannot clear the read DUST's counter");
+        s.dust_grid = read_dust_grid_max();
+    }
+    return NH_OK;
+}
+
+// the quality mask's buffers of a slot: the record table of nrec sequences, ntext bytes of masked text, the counter
+static int slot_reserve_qmask(Slot &s, size_t ntext, size_t nrec) {
+    const int rrc = slot_reserve_rec(s, nrec);
+    if (rrc) return rrc;
+    const int trc = slot_reserve_qtext(s, ntext);
+    if (trc) return trc;
     if (!s.d_qcnt) {
         if (dev_malloc((void **)&s.d_qcnt, 8) != hipSuccess) return set_error(NH_EOOM, "cannot allocate batch buffers");
         if (hipMemsetAsync(s.d_qcnt, 0, 8, s.stream) != hipSuccess) return set_error(NH_EDEVICE, "cannot clear the quality mask's counter");
@@ -574,9 +609,9 @@ static void slot_free(Slot &s) {
         if (p) (void)hipHostFree(p);
     for (void *p : {s.d_rec, s.d_idl, s.d_hres})
         if (p) (void)hipFree(p);
-    for (void *p : {s.d_qtext, (void *)s.d_qcnt})
+    for (void *p : {s.d_qtext, (void *)s.d_qcnt, (void *)s.d_dscr, (void *)s.d_dcnt})
         if (p) (void)hipFree(p);
-    for (hipEvent_t ev : {s.qev[0], s.qev[1], s.rev[0], s.rev[1], s.mev[0], s.mev[1], s.hev[0], s.hev[1]})
+    for (hipEvent_t ev : {s.duev[0], s.duev[1], s.qev[0], s.qev[1], s.rev[0], s.rev[1], s.mev[0], s.mev[1], s.hev[0], s.hev[1]})
         if (ev) (void)hipEventDestroy(ev);
     for (void *p : {(void *)s.h_off, (void *)s.h_len, (void *)s.h_res, (void *)s.h_taxa, (void *)s.h_taxa_off, (void *)s.h_flag})
         if (p) (void)hipHostFree(p);
@@ -676,6 +711,9 @@ struct RunState {
     // runs with a minimum base quality (NOHUMAN_TRACE): the bases k_qmask replaced, its kernel time
     uint64_t qmask_masked = 0;
     double qmask_kernel_ms = 0;
+    // runs with --dust-reads: the bases k_rdust masked (nh_read_dust.masked_bases), the kernel time of its three launches
+    uint64_t dust_masked = 0;
+    double dust_kernel_ms = 0;
     // runs with read statistics: the exact length histogram of each [class][mate] -- a vector for the lengths below 2^20, a map
     // above -- that the writer keeps from the batch's lengths and calls (median and N50 need every length), k_rstats' time
     std::vector<uint64_t> len_hist[2][2];
@@ -1133,13 +1171,19 @@ struct RunRequest {
     // masks, lists or counts HOST reads then reads that array (the writer its copy), everything that reports the CALL the
     // classifier's.  NULL: nothing of this runs.
     nh_host_filter *hf = nullptr;
+    // given (nh_run_dust): the struct as the caller gave it -- check_request looks at its size --, and `dust` where it enables the
+    // pass: every sequence of every batch is masked by symmetric DUST on its own (k_rdust in front of the classifier on the slot's
+    // stream, behind the quality mask) in the copy the classifier and the minimizer data's marks read; the outputs keep the
+    // input's bases, as with minq.  Not enabled: nothing of this runs.
+    nh_read_dust *rd = nullptr;
+    bool dust = false;
 };
 
 // The request of an entry: its args, its extras (NULL where it has none, or was given none) or the bare human paths of
 // nh_run_split / nh_run_mask, and as much of nh_run_host's tail as the entry has
 RunRequest make_request(RunRequest::Form form, const nh_run_args *a, const nh_run_extras *x, const char *h1 = nullptr, const char *h2 = nullptr,
                         uint32_t minq = 0, const char *rs_path = nullptr, nh_read_stats *rs_out = nullptr, nh_taxon_out *touts = nullptr,
-                        uint32_t n_touts = 0, nh_minimizer_data *md = nullptr, nh_host_filter *hf = nullptr) {
+                        uint32_t n_touts = 0, nh_minimizer_data *md = nullptr, nh_host_filter *hf = nullptr, nh_read_dust *rd = nullptr) {
     static const char *const names[] = {"nh_run", "nh_run_split", "nh_run_mask", "nh_run_ex"};
     RunRequest r;
     r.form = form == RunRequest::RUN && x ? RunRequest::EX : form;
@@ -1150,6 +1194,7 @@ RunRequest make_request(RunRequest::Form form, const nh_run_args *a, const nh_ru
         r.hout1 = x->human_out1, r.hout2 = x->human_out2, r.mask = x->mask != 0, r.calls = x->calls, r.ids = x->human_ids;
     r.minq = minq, r.rs_path = rs_path, r.rs_out = rs_out, r.touts = touts, r.n_touts = n_touts, r.md = md;
     r.hf = host_filter_given(hf) ? hf : nullptr;  // (no taxid listed: the run of nh_run_mdata, and the struct is not looked at again)
+    r.rd = rd, r.dust = rd && rd->struct_size >= sizeof(nh_read_dust) && rd->enable != 0;
     return r;
 }
 
@@ -1337,11 +1382,13 @@ static int check_out_codec(const RunRequest &r) {
 }
 
 // Every entry's checks, in one order: the host selection's own, the minimum base quality (the highest printable quality is '~',
-// Phred 93), the extras (the mask or the human outputs, then the read lists), the read statistics' table, the selectors, the
+// Phred 93), the read DUST's struct, the extras (the mask or the human outputs, then the read lists), the read statistics' table, the selectors, the
 // minimizer data, the container.  What an entry cannot ask for is not set in its request and checks nothing.
 int check_request(const RunRequest &r) {
     int rc = check_host_filter(r.hf);
     if (!rc && r.minq > 93) rc = set_error(NH_EINVAL, "minimum base quality %u is not in 0..93 (Phred+33)", r.minq);
+    if (!rc && r.rd && r.rd->struct_size < sizeof(nh_read_dust))
+        rc = set_error(NH_EINVAL, "nh_run_dust: struct_size %u is smaller than nh_read_dust (%zu bytes)", r.rd->struct_size, sizeof(nh_read_dust));
     if (!rc && r.form != RunRequest::RUN) rc = check_extras(r);
     if (!rc) rc = check_rstats_args(r);
     if (!rc) rc = check_taxon_args(r);
@@ -1500,6 +1547,16 @@ static void collect_qmask(std::vector<Slot> &slots, RunState &rs) {
         }
 }
 
+// the bases k_rdust masked
+static void collect_dust(std::vector<Slot> &slots, RunState &rs) {
+    for (auto &s : slots)
+        if (s.d_dcnt && rs.err_code == NH_OK) {
+            unsigned long long c = 0;
+            if (dev_set(s.e->device) == hipSuccess && hipMemcpy(&c, s.d_dcnt, 8, hipMemcpyDeviceToHost) == hipSuccess) rs.dust_masked += c;
+            else rs.fail(NH_EDEVICE, "reading the read DUST's counter failed");
+        }
+}
+
 // host selection: the devices' {host, spared} fragments summed into dev_host
 static void collect_host_counts(const std::vector<RunBuffers> &dbuf, RunState &rs, uint64_t dev_host[2]) {
     for (size_t g = 0; g < dbuf.size() && rs.err_code == NH_OK; g++) {
@@ -1653,6 +1710,8 @@ struct RunShape {
     bool split;        // ... and their records built as FASTQ text (nh_split.hip)
     int n_bout, K;     // BAM output: the builder's outputs; per-taxon outputs: the selectors
     bool taxa, qm, rst, mdt, hsel;
+    bool dust;         // --dust-reads: k_rdust in front of the classifier
+    bool qtext;        // the classifier and the minimizer data's marks read the slot's masked text, not the batch's (qm or dust)
     bool want_rec;     // a kernel of the run reads the record table
     bool gzip_family;  // the codecs the GPU encodes
     int G, NS;         // devices, stream slots a device
@@ -1669,6 +1728,7 @@ struct RunShape {
         split_files = r.hout1 != nullptr, split = split_files && !bamout, n_bout = split_files ? 2 : 1;
         K = (int)r.n_touts, taxa = K > 0;
         qm = minq > 0, rst = r.rs_path || r.rs_out, hsel = r.hf != nullptr;
+        dust = r.dust, qtext = qm || dust;
         mdt = r.md && (r.md->in_report || r.md->table || r.md->taxa);
         want_rec = split || mask || lists || qm || rst || taxa;
         gzip_family = a->out_codec == NH_CODEC_GZIP || a->out_codec == NH_CODEC_BGZF || bamout;
@@ -1797,6 +1857,7 @@ struct Pipeline {
         if (sh.mask) builders.push_back({&Slot::mask, 4, &RunState::mask_kernel_ms});
         if (sh.lists) builders.push_back({&Slot::lists, 4, &RunState::list_kernel_ms});
         if (sh.qm) passes.push_back({&Slot::qev, &RunState::qmask_kernel_ms});
+        if (sh.dust) passes.push_back({&Slot::duev, &RunState::dust_kernel_ms});
         if (sh.rst) passes.push_back({&Slot::rev, &RunState::rstats_kernel_ms});
         if (sh.mdt) passes.push_back({&Slot::mev, &RunState::mdata_kernel_ms});
         if (sh.hsel) passes.push_back({&Slot::hev, &RunState::host_kernel_ms});
@@ -2427,6 +2488,7 @@ struct Pipeline {
         if (sh.bamout) build_bam(RESERVE, s, b, nullptr, &rc);
         if (sh.lists) build_lists(RESERVE, s, b, nullptr, &rc);
         if (!rc && sh.qm) rc = slot_reserve_qmask(s, b.ntext(), b.n * (size_t)sh.mates);
+        if (!rc && sh.dust) rc = slot_reserve_dust(s, b.ntext(), b.n * (size_t)sh.mates);
         if (!rc && sh.rst) rc = slot_reserve_rec(s, b.n * (size_t)sh.mates);
         if (!rc && sh.hsel) rc = slot_reserve_hres(s, b.n);
         if (!rc && (sh.qm || sh.rst)) rc = check_quality_lengths(b);
@@ -2515,7 +2577,8 @@ struct Pipeline {
         return he == hipSuccess;
     }
 
-    // the batch's launches on the slot's stream, in this order: the quality mask, the classifier, the host filter, the read
+    // the batch's launches on the slot's stream, in this order: the quality mask, the read DUST (on a copy of the text where no
+    // quality mask has written the sequences), the classifier, the host filter, the read
     // statistics, the minimizer data's marks, then the builders -- lists, split, BAM out, per-taxon, mask.  Each goes out only
     // while the run has not failed.
     void launch(Slot &s, const Batch &b, uint64_t nbases, bool staged) {
@@ -2532,8 +2595,18 @@ struct Pipeline {
             qa.out = (char *)s.d_qtext, qa.masked = s.d_qcnt, qa.error = d_error;
             timed_launch(rs, s.stream, s.qev, "quality mask", [&] { return launch_qmask(qa, s.stream); });
         }
+        if (staged && sh.dust && !rs.failed()) {  // ... and 'N' over the low-complexity stretches of every sequence: the union of the masks
+            dev_check_ptr(s.d_qtext, s.e->device, "nh_run, a slot's DUST-masked text");
+            if (!sh.qm && hipMemcpyAsync(s.d_qtext, s.d_text, ntext, hipMemcpyDeviceToDevice, s.stream) != hipSuccess)
+                rs.fail(NH_EDEVICE, "read DUST: the copy of the batch's text failed");
+            ReadDustArgs da{};
+            da.text = (const char *)s.d_text, da.ntext = ntext;  // (DUST reads the input's bases, not the quality-masked ones)
+            da.seq_off = (const uint64_t *)s.d_off, da.seq_len = (const uint32_t *)s.d_len, da.n = b.n * (uint64_t)mates;
+            da.out = (char *)s.d_qtext, da.masked = s.d_dcnt, da.error = d_error;
+            if (!rs.failed()) timed_launch(rs, s.stream, s.duev, "read DUST", [&] { return launch_read_dust(da, s.d_dscr, s.dust_grid, s.stream); });
+        }
         if (!rs.failed()) {
-            const int rc = classify_device(s.e, sh.qm ? s.d_qtext : s.d_text, s.d_off, b.n, sh.flags | (nbases / b.n > 2000 ? NH_FLAG_LONG : 0u),
+            const int rc = classify_device(s.e, sh.qtext ? s.d_qtext : s.d_text, s.d_off, b.n, sh.flags | (nbases / b.n > 2000 ? NH_FLAG_LONG : 0u),
                                            a->confidence, s.d_res, rs.want_k ? s.d_taxa : nullptr, rs.want_k ? s.d_taxa_off : nullptr,
                                            rs.d_run_counters[(size_t)b.dev_index], s.stream, s.d_len, ntext);
             if (rc) rs.fail(rc, g_last_error);
@@ -2553,7 +2626,7 @@ struct Pipeline {
         }
         if (!rs.failed() && sh.mdt)  // minimizer data, marked behind the classifier on the same stream: the text the classifier read
             timed_launch(rs, s.stream, s.mev, "minimizer data", [&] {
-                return launch_mdata_mark(s.e, sh.qm ? s.d_qtext : s.d_text, ntext, s.d_off, s.d_len, b.n, mates, db.marks, db.groups, s.stream);
+                return launch_mdata_mark(s.e, sh.qtext ? s.d_qtext : s.d_text, ntext, s.d_off, s.d_len, b.n, mates, db.marks, db.groups, s.stream);
             });
         int none = NH_OK;  // (a launch fails the run itself)
         if (!rs.failed() && sh.lists) build_lists(LAUNCH, s, b, nullptr, &none);
@@ -2636,6 +2709,9 @@ static void print_run_trace(const RunShape &sh, RunState &rs, const StageClock &
     if (sh.qm)
         fprintf(stderr, "[nohuman trace] qmask: Q %u, %llu of %llu bases masked, kernel %.3f ms\n", sh.minq,
                 (unsigned long long)rs.qmask_masked, (unsigned long long)rs.total_bases, rs.qmask_kernel_ms);
+    if (sh.dust)
+        fprintf(stderr, "[nohuman trace] dust-reads: %llu of %llu bases masked, kernel %.3f ms\n", (unsigned long long)rs.dust_masked,
+                (unsigned long long)rs.total_bases, rs.dust_kernel_ms);
     if (sh.rst && racc.size() == 4)
         fprintf(stderr, "[nohuman trace] rstats: %llu bases, kernel %.3f ms\n",
                 (unsigned long long)(racc[0].bases + racc[1].bases + racc[2].bases + racc[3].bases), rs.rstats_kernel_ms);
@@ -2772,6 +2848,7 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
         if ((rc = host_table(engines[0], r.hf, host_of))) return rc;
         r.hf->host_fragments = r.hf->spared_fragments = 0;
     }
+    if (r.rd) r.rd->masked_bases = 0;
     if (sh.split || sh.lists || sh.taxa)
         for (Engine *e : engines)
             if ((rc = ensure_device_external(e))) return rc;
@@ -2805,6 +2882,7 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
     p.shutdown();
 
     collect_qmask(p.slots, rs);
+    if (sh.dust) collect_dust(p.slots, rs);
     uint64_t dev_host[2] = {0, 0};  // host selection: the devices' {host, spared} fragments summed
     if (sh.hsel) collect_host_counts(dbuf, rs, dev_host);
     if (sh.rst) collect_rstats(dbuf, rs, racc);
@@ -2831,6 +2909,7 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
     if (sh.rst && (rc = finish_read_stats(r, rs, sh.mates, racc))) return rc;
     for (int k = 0; k < sh.K; k++) r.touts[k].fragments = rs.taxon_frags[k];
     if (sh.hsel) r.hf->host_fragments = rs.host_frags, r.hf->spared_fragments = rs.spared_frags;
+    if (sh.dust) r.rd->masked_bases = rs.dust_masked;
     if (sh.mdt && (rc = report_mdata(mdview, mdn, r.md))) return rc;
     if (stats) {
         nh_stats st;
@@ -2903,6 +2982,15 @@ int nh_run_engine_host(nh_engine *e, const nh_run_args *args, const nh_run_extra
                        nh_host_filter *hf, nh_stats *stats) {
     return run_on_engine(
         e, nh::make_request(nh::RunRequest::RUN, args, extras, nullptr, nullptr, min_base_quality, read_stats_path, read_stats, outs, n_outs, md, hf), stats);
+}
+
+// (rd NULL, or its enable 0: the request is nh_run_engine_host's)
+int nh_run_engine_dust(nh_engine *e, const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality,
+                       const char *read_stats_path, nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs, nh_minimizer_data *md,
+                       nh_host_filter *hf, nh_read_dust *rd, nh_stats *stats) {
+    return run_on_engine(
+        e, nh::make_request(nh::RunRequest::RUN, args, extras, nullptr, nullptr, min_base_quality, read_stats_path, read_stats, outs, n_outs, md, hf, rd),
+        stats);
 }
 
 int nh_fastx_scan(const char *path, uint64_t *n_records, uint64_t *n_bases, uint64_t *digest) {
@@ -3167,6 +3255,15 @@ int nh_run_host(const nh_run_args *args, const nh_run_extras *extras, uint32_t m
                 nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs, nh_minimizer_data *md, nh_host_filter *hf, nh_stats *stats) {
     return run_standalone(
         nh::make_request(nh::RunRequest::RUN, args, extras, nullptr, nullptr, min_base_quality, read_stats_path, read_stats, outs, n_outs, md, hf), stats);
+}
+
+// (rd NULL, or its enable 0: the request is nh_run_host's)
+int nh_run_dust(const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality, const char *read_stats_path,
+                nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs, nh_minimizer_data *md, nh_host_filter *hf, nh_read_dust *rd,
+                nh_stats *stats) {
+    return run_standalone(
+        nh::make_request(nh::RunRequest::RUN, args, extras, nullptr, nullptr, min_base_quality, read_stats_path, read_stats, outs, n_outs, md, hf, rd),
+        stats);
 }
 
 }  // extern "C"

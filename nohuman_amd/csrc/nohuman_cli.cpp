@@ -251,6 +251,7 @@ struct Args {
     bool mask = false;  // masked run: every read written, the human ones' bases as N (nh_run_mask)
     std::string calls, human_ids;  // read lists (nh_run_ex): a table line per read; the ids of the human reads
     unsigned min_base_quality = 0;  // kraken2's --minimum-base-quality (nh_run_minq); 0: off
+    bool dust_reads = false;        // classify every read with its low-complexity stretches as ambiguous bases (nh_run_dust)
     std::string read_stats;         // the read statistics table (nh_run_rstats)
     bool report_minimizer_data = false;  // kraken2's flag: two more columns in the report (nh_run_mdata)
     std::string minimizer_table;         // the minimizer table (nh_run_mdata)
@@ -301,6 +302,8 @@ static void usage(FILE *f) {
           "minimizers are taken [recommended for real genomes]\n"
           "  -C, --conf <[0, 1]>          Kraken2 minimum confidence score [default: 0.0]\n"
           "      --minimum-base-quality <INT>  Kraken2 minimum base quality: classify FASTQ bases with a lower Phred+33 quality as ambiguous (0-93; the reads written keep their bases) [default: 0]\n"
+          "      --dust-reads             Classify every read with its low-complexity stretches (poly-A, microsatellites: symmetric DUST, window 64, level 20) "
+          "as ambiguous bases, so that a database built without low-complexity filtering does not call them human (the reads written keep their bases)\n"
           "  -k, --kraken-output <FILE>   Write the Kraken2 read classification output to a file\n"
           "  -r, --kraken-report <FILE>   Write the Kraken2 report with aggregate counts/clade to file\n"
           "      --report-minimizer-data  Report, per clade, the minimizer hits of the reads and how many distinct minimizers they were, as columns 4 and 5 of the Kraken2 report "
@@ -480,6 +483,7 @@ static Args parse_args(int argc, char **argv) {
             a.has_build_opt = true;
         } else if (s == "--force") a.force = a.has_build_opt = true;
         else if (s == "--mask-low-complexity") a.mask_low_complexity = true;
+        else if (s == "--dust-reads") a.dust_reads = true;
         else if (s == "--taxa") { a.taxa = val(); a.has_taxa = true; }
         else if (s == "-v" || s == "--verbose") g_verbose = true;
         else if (s == "-h" || s == "--help") { usage(stdout); exit(0); }
@@ -503,7 +507,7 @@ static Args parse_args(int argc, char **argv) {
                              : !a.human_ids.empty() ? "--human-ids" : !a.read_stats.empty() ? "--read-stats" : a.report_minimizer_data ? "--report-minimizer-data"
                              : !a.minimizer_table.empty() ? "--minimizer-table" : a.has_type ? "--output-type"
                              : a.bgzf ? "--bgzf" : a.bam_out ? "--bam-out" : a.mask ? "--mask" : a.human ? "--human" : !a.taxon_out.empty() ? "--taxon-out"
-                             : !a.host_taxids.empty() ? "--host-taxid" : !a.keep_taxids.empty() ? "--keep-taxid" : nullptr;
+                             : !a.host_taxids.empty() ? "--host-taxid" : !a.keep_taxids.empty() ? "--keep-taxid" : a.dust_reads ? "--dust-reads" : nullptr;
         if (out_flag) arg_error("the argument '--build-db <DIR>' cannot be used with '%s'", out_flag);
         if (a.has_extend_db) {
             if (a.capacity) arg_error("the argument '--extend-db <DIR>' cannot be used with '--capacity <INT>': an extension keeps the capacity of its base");
@@ -987,7 +991,14 @@ int main(int argc, char **argv) {
         if (args.keep_taxids.empty()) INFO("Host clades: %s", named(args.host_taxids).c_str());
         else INFO("Host clades: %s; kept clades: %s", named(args.host_taxids).c_str(), named(args.keep_taxids).c_str());
     }
-    const int run_rc = hsel ? nh_run_host(&ra, lists || args.mask || split ? &rx : nullptr, args.min_base_quality,
+    nh_read_dust rd;
+    memset(&rd, 0, sizeof rd);
+    rd.struct_size = (uint32_t)sizeof rd;
+    rd.enable = args.dust_reads ? 1 : 0;
+    const int run_rc = args.dust_reads ? nh_run_dust(&ra, lists || args.mask || split ? &rx : nullptr, args.min_base_quality,
+                                                     args.read_stats.empty() ? nullptr : spart.c_str(), nullptr, touts.empty() ? nullptr : touts.data(),
+                                                     (uint32_t)touts.size(), md.in_report || md.table ? &md : nullptr, hsel ? &hf : nullptr, &rd, &st)
+                       : hsel ? nh_run_host(&ra, lists || args.mask || split ? &rx : nullptr, args.min_base_quality,
                                           args.read_stats.empty() ? nullptr : spart.c_str(), nullptr, touts.empty() ? nullptr : touts.data(),
                                           (uint32_t)touts.size(), md.in_report || md.table ? &md : nullptr, &hf, &st)
                        : md.in_report || md.table ? nh_run_mdata(&ra, lists || args.mask || split ? &rx : nullptr, args.min_base_quality,
@@ -1026,6 +1037,9 @@ int main(int argc, char **argv) {
     if (hsel)
         INFO("%llu host sequences removed; %llu classified sequences outside the host clades kept", (unsigned long long)hf.host_fragments,
              (unsigned long long)hf.spared_fragments);
+    if (args.dust_reads)
+        DEBUG("%llu low-complexity bases of the reads masked for classification (%.2f %% of the bases)", (unsigned long long)rd.masked_bases,
+              st.total_bases ? 100.0 * (double)rd.masked_bases / (double)st.total_bases : 0.0);
     if (g_verbose) {  // a BAM input: what the reader made of its records (the host side of the reader once more: nh_bam_scan)
         nh_bam_info bi;
         memset(&bi, 0, sizeof bi);

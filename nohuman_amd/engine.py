@@ -44,7 +44,7 @@ def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
         threads: int = 1, keep_human: bool = False, device_ids=None, out_codec: int = 0,
         codec_threads: int = 0, human_out1=None, human_out2=None, mask: bool = False, calls=None,
         human_ids=None, min_base_quality: int = 0, read_stats=None, taxon_outs=None, report_minimizer_data: bool = False,
-        minimizer_table=None, minimizer_data=None, host_taxids=None, keep_taxids=None) -> "_lib.nh_stats":
+        minimizer_table=None, minimizer_data=None, host_taxids=None, keep_taxids=None, dust_reads: bool = False) -> "_lib.nh_stats":
     """nh_run: whole run, database loaded into every listed device (default: all visible).  human_out1 (and, paired,
     human_out2) given: nh_run_split -- the non-human reads go to out1 / out2 and, in the same pass, the human reads to
     human_out1 / human_out2 exactly as a keep_human run would write them.  mask: nh_run_mask -- every read goes to
@@ -78,7 +78,11 @@ def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
     the human outputs, the mask, human_ids and the classes of read_stats follow the selection, while calls, kraken_output,
     report, taxon_outs, the minimizer data and the stats' three totals keep the true calls.  host_taxids=[1] is the run without a
     selection; [9606] on a standard database removes only human reads; [1] with keep_taxids=[10239] everything but viruses.  The
-    stats returned then carry host_fragments and spared_fragments (their sum is `classified`)."""
+    stats returned then carry host_fragments and spared_fragments (their sum is `classified`).
+    dust_reads (nh_run_dust; any kind of run): every sequence, both mates, FASTA as FASTQ, is classified with its low-complexity
+    stretches (symmetric DUST, window 64, level 20, each sequence on its own) as ambiguous bases -- what cures the false positives
+    of a database built without low-complexity masking; every record written keeps its bases.  With min_base_quality the
+    classifier sees the union of the two masks.  The stats returned then carry dust_masked_bases."""
     a = _lib.nh_run_args()
     a.db_dir = os.fsencode(db_dir)
     a.in1 = os.fsencode(in1)
@@ -102,28 +106,30 @@ def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
         a.device_ids = None
     return _run_entry("nh_run", (), lambda: _taxo_nodes(os.fspath(db_dir)), a, human_out1, human_out2, mask, calls, human_ids,
                       min_base_quality, read_stats, taxon_outs, report_minimizer_data, minimizer_table, minimizer_data, host_taxids,
-                      keep_taxids)
+                      keep_taxids, dust_reads)
 
 
 def _run_entry(prefix, lead, nodes, a, human_out1, human_out2, mask, calls, human_ids, min_base_quality, read_stats, taxon_outs,
-               report_minimizer_data, minimizer_table, minimizer_data, host_taxids, keep_taxids) -> "_lib.nh_stats":
+               report_minimizer_data, minimizer_table, minimizer_data, host_taxids, keep_taxids, dust_reads=False) -> "_lib.nh_stats":
     """run() and Engine.run(): the entry of the family `prefix` (nh_run / nh_run_engine, behind the arguments `lead`: none / the
-    handle) that the options ask for -- the first of host, mdata, taxa, rstats, minq, ex, mask, split, none that has one -- and
+    handle) that the options ask for -- the first of dust, host, mdata, taxa, rstats, minq, ex, mask, split, none that has one -- and
     what it hands back, on the stats.  nodes(): the nodes of the taxonomy, asked only where minimizer data wants a list."""
     fn = lambda suffix: getattr(_lib.lib(), prefix + suffix)
     s = _lib.nh_stats()
     head = tuple(lead) + (C.byref(a),)
     want_md = report_minimizer_data or minimizer_table is not None or minimizer_data is not None
-    if host_taxids or keep_taxids or want_md or taxon_outs or read_stats is not None or min_base_quality:
+    if dust_reads or host_taxids or keep_taxids or want_md or taxon_outs or read_stats is not None or min_base_quality:
         # the entries that take nh_run_minq's list and, each, one thing more: every one gets the list as far as its own last argument
         x = _extras_or_none(mask, human_out1, human_out2, calls, human_ids)
         rs = _read_stats(read_stats) if read_stats is not None else None
         t = _taxon_outs(taxon_outs or [])
         md = _minimizer_data(report_minimizer_data, minimizer_table, minimizer_data, nodes()) if want_md else None
         hf = _host_filter(host_taxids, keep_taxids) if host_taxids or keep_taxids else None
+        rd = _lib.nh_read_dust(C.sizeof(_lib.nh_read_dust), 1, 0) if dust_reads else None
         tail = [x, _minq(min_base_quality), _path_or_none(rs.path) if rs else None, C.byref(rs.raw) if rs else None,
-                t if len(t) else None, len(t), C.byref(md) if md is not None else None, C.byref(hf) if hf is not None else None]
-        suffix, n = (("_host", 8) if hf is not None else ("_mdata", 7) if want_md else ("_taxa", 6) if taxon_outs else
+                t if len(t) else None, len(t), C.byref(md) if md is not None else None, C.byref(hf) if hf is not None else None,
+                C.byref(rd) if rd is not None else None]
+        suffix, n = (("_dust", 9) if rd is not None else ("_host", 8) if hf is not None else ("_mdata", 7) if want_md else ("_taxa", 6) if taxon_outs else
                      ("_rstats", 4) if rs is not None else ("_minq", 2))
         _check(fn(suffix)(*head, *tail[:n], C.byref(s)))
         if md is not None:
@@ -132,6 +138,8 @@ def _run_entry(prefix, lead, nodes, a, human_out1, human_out2, mask, calls, huma
             s.taxon_fragments = [int(o.fragments) for o in t]
         if hf is not None:
             s.host_fragments, s.spared_fragments = int(hf.host_fragments), int(hf.spared_fragments)
+        if rd is not None:
+            s.dust_masked_bases = int(rd.masked_bases)
     elif calls is not None or human_ids is not None:
         x = _extras(mask, human_out1, human_out2, calls, human_ids)
         _check(fn("_ex")(*head, C.byref(x), C.byref(s)))
@@ -595,6 +603,16 @@ class Engine:
         _check(self._L.nh_quality_mask_device(self._h, d_text, text_len, d_seq_starts, d_seq_lens, d_qual_starts, n_seq,
                                               _minq(min_base_quality), d_out, d_masked or None, stream or None))
 
+    def dust_reads_device(self, d_text: int, text_len: int, d_seq_starts: int, d_seq_lens: int, n_seq: int, d_out: int,
+                          d_masked: int = 0, stream: int = 0):
+        """--dust-reads as a pass in front of classify_records_device (nh_dust_reads_device): d_out (text_len bytes, the layout
+        of d_text) already holds the sequences -- a copy of the text, or quality_mask_device's output -- and gets N at every base
+        that symmetric DUST (window 64, level 20) masks in the sequence d_text[start, +len) taken on its own; nothing else of d_out
+        is written.  d_masked: one uint64 the kernel adds its masked bases to.  A sequence that leaves the text is skipped and
+        fails the engine's next blocking call.  Waits for `stream`."""
+        _check(self._L.nh_dust_reads_device(self._h, d_text or None, int(text_len), d_seq_starts or None, d_seq_lens or None, int(n_seq),
+                                            d_out or None, d_masked or None, stream or None))
+
     def bam_to_fastq_device(self, d_bam: int, bam_len: int, d_table: int, n_records: int, d_text: int, text_cap: int, text_len: int,
                             d_error_bits: int, stream: int = 0):
         """The BAM reader's kernel alone (nh_bam_to_fastq_device): the records of d_bam (bam_len bytes, 4-byte aligned) that
@@ -670,11 +688,12 @@ class Engine:
             confidence: float = 0.0, threads: int = 1, keep_human: bool = False, out_codec: int = 0,
             codec_threads: int = 0, human_out1=None, human_out2=None, mask: bool = False, calls=None,
             human_ids=None, min_base_quality: int = 0, read_stats=None, taxon_outs=None, report_minimizer_data: bool = False,
-            minimizer_table=None, minimizer_data=None, host_taxids=None, keep_taxids=None) -> _lib.nh_stats:
+            minimizer_table=None, minimizer_data=None, host_taxids=None, keep_taxids=None, dust_reads: bool = False) -> _lib.nh_stats:
         """nh_run_engine; with human_out1 (and, paired, human_out2): nh_run_engine_split; mask: nh_run_engine_mask; with
         calls / human_ids: nh_run_engine_ex; with min_base_quality: nh_run_engine_minq; with read_stats:
         nh_run_engine_rstats; with taxon_outs: nh_run_engine_taxa; with report_minimizer_data / minimizer_table / minimizer_data:
-        nh_run_engine_mdata; with host_taxids / keep_taxids: nh_run_engine_host -- as run() above."""
+        nh_run_engine_mdata; with host_taxids / keep_taxids: nh_run_engine_host; with dust_reads: nh_run_engine_dust -- as run()
+        above."""
         a = _lib.nh_run_args()
         a.db_dir = None
         a.in1 = os.fsencode(in1)
@@ -692,4 +711,4 @@ class Engine:
         a.codec_threads = int(codec_threads)
         return _run_entry("nh_run_engine", (self._h,), lambda: self.info.node_count, a, human_out1, human_out2, mask, calls, human_ids,
                           min_base_quality, read_stats, taxon_outs, report_minimizer_data, minimizer_table, minimizer_data, host_taxids,
-                          keep_taxids)
+                          keep_taxids, dust_reads)
