@@ -867,6 +867,72 @@ int nh_run_engine_dust(nh_engine *e, const nh_run_args *args, const nh_run_extra
 int nh_dust_reads_device(nh_engine *e, const void *d_text, uint64_t text_len, const void *d_seq_starts, const void *d_seq_lens,
                          uint64_t n_seq, void *d_out, void *d_masked, void *stream);
 
+/*
+ * Host intervals (--host-intervals; nh_cover.hip): WHERE in each read the host k-mers lie, as BED.  Every other
+ * answer of a run is about a whole read; a 40 kb read that is half viral and half human, or a microbial read with one 300-base
+ * stretch of human-like minimizers, is host as a whole.  This report alters nothing -- a decontamination tool does not alter the
+ * reads it returns -- and lets `bedtools maskfasta`, `seqkit subseq --bed` or a trimmer act on it.
+ *
+ * HOST K-MERS.  Every sequence of the batch, both mates, FASTA as FASTQ, in the copy the classifier reads (with a minimum base
+ * quality or the read DUST: the masked copy, so the intervals agree with the calls).  k-mer i (0-based, bases [i, i + k)) is a
+ * host k-mer when it is not ambiguous under the ambiguity rule in force, its minimizer is looked up (a minimizer below
+ * minimum_acceptable_hash_value is not, as in the classifier), the look-up finds a non-zero value v and -- a run with a host
+ * selection (nh_host_filter) -- the one-byte-a-node table of that selection says v is host; without a selection every non-zero
+ * value is host.
+ * INTERVALS.  A base is covered when a host k-mer contains it; a sequence's intervals are its maximal runs of covered bases,
+ * 0-based and half-open.  Host k-mers i < j with j <= i + k share an interval; an interval never crosses a sequence's end.  An
+ * ambiguous base p splits a host stretch into [.., p) and [p + 1, ..) where no unambiguous k-mer contains it.  Under the default
+ * ambiguity rule (1, kraken2's: an N costs the k - 1 k-mers that hold it in their last k - 1 bases) the k-mer that BEGINS with
+ * the N is looked up like any other, so ONE N INSIDE A HOST STRETCH USUALLY STAYS COVERED and two in a row leave the first
+ * uncovered; under rule 0 it takes k - l + 1.  The intervals are what the classifier's own hit list (kraken_output's fifth
+ * column) says, k-mer for k-mer.  They do not depend on reset_per_mate, on the confidence, on minimum_hit_groups or on the call.
+ * THE FILE is plain text, never compressed, without a header line: one line an interval,
+ *     <id> \t <start> \t <end> \t <mate: 1|2> \t <external taxid of the fragment's call, 0 if unclassified> \n
+ * in input order: fragment, then mate, then start.  <id> is exactly the calls table's id (a paired run drops a trailing /1 or /2).
+ * A fragment without a covered base has no line, classified or not; an unclassified read with one hit group has one.  The taxid
+ * is the true call, as in the calls table, not the host-filtered one.  BAM INPUT: THE COORDINATES ARE THOSE OF THE FASTQ TEXT THE
+ * READER TRANSCODES TO, SO A REVERSE-STRAND RECORD IS COUNTED ON ITS REVERSE COMPLEMENT (the read as the sequencer gave it).
+ * Every other output and the three totals are byte for byte what the same run writes without the file; without it nothing is
+ * allocated or launched.  The pass supports the default geometry (k 35, l 31, the default masks, revcom_version 1) and linear
+ * probing only: another database is refused with NH_EINVAL, the reason named, once it is open and before any input is read or any
+ * output created.
+ *
+ * nh_run_intervals / nh_run_engine_intervals: nh_run_dust with the report.  hi NULL or hi->path NULL: exactly nh_run_dust.  A
+ * struct_size smaller than the struct, an empty path, a path that names an input or any other output of the run (a per-taxon file
+ * and the read statistics' table included): NH_EINVAL before any device is touched, nothing created.  fragments (those with a
+ * line), intervals and covered_bases are summed over the run's devices (0 where the run fails after its arguments were accepted).
+ *
+ * nh_host_cover_device: the mark pass on the engine's device, on `stream`.  Sequence i is d_text[d_seq_starts[i], +d_seq_lens[i])
+ * (uint64 / uint32, the arrays of nh_classify_records_device, in any order); d_text is 4-byte aligned and only read, no byte
+ * behind the dword of its last byte.  d_host_of: NULL, or n_nodes bytes (nh_host_table_image).  d_cover, ceil(text_len / 32)
+ * uint32 zeroed by the caller, gets bit (p & 31) of word p / 32 set for every covered byte p of the text; a word without a new
+ * bit is not written.  A sequence that leaves [0, text_len) is skipped -- nothing of it is read or written -- and sets a sticky
+ * error bit (value 1024) that fails the engine's next blocking call or run with NH_EDEVICE.
+ * nh_cover_intervals_device: the bitmap into records {uint32 seq, start, end}, in the order of the sequence table, then by start,
+ * every interval clipped to its sequence (two sequences back to back give two records).  *d_total (uint64) receives the records;
+ * more than cap_records: bit 2048 is set in *error_bits (an int32 of the caller's in device memory), the total is 0 and nothing is
+ * written; a sequence outside the text has no record and sets bit 1024 there.
+ * Both entries allocate their scratch (8 and 4 bytes a sequence), wait for the stream and free it; n_seq == 0 launches nothing.
+ */
+typedef struct {
+    uint32_t struct_size;    /* sizeof(nh_host_intervals) of the caller */
+    uint32_t reserved;       /* 0 */
+    const char *path;        /* the BED file; NULL: no report */
+    uint64_t fragments;      /* out: fragments with an interval */
+    uint64_t intervals;      /* out */
+    uint64_t covered_bases;  /* out */
+} nh_host_intervals;
+int nh_run_intervals(const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality, const char *read_stats_path,
+                     nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs, nh_minimizer_data *md, nh_host_filter *hf,
+                     nh_read_dust *rd, nh_host_intervals *hi, nh_stats *stats);
+int nh_run_engine_intervals(nh_engine *e, const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality,
+                            const char *read_stats_path, nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs,
+                            nh_minimizer_data *md, nh_host_filter *hf, nh_read_dust *rd, nh_host_intervals *hi, nh_stats *stats);
+int nh_host_cover_device(nh_engine *e, const void *d_text, uint64_t text_len, const void *d_seq_starts, const void *d_seq_lens,
+                         uint64_t n_seq, const void *d_host_of, uint64_t n_nodes, void *d_cover, void *stream);
+int nh_cover_intervals_device(nh_engine *e, const void *d_cover, uint64_t text_len, const void *d_seq_starts, const void *d_seq_lens,
+                              uint64_t n_seq, void *d_intervals, uint64_t cap_records, void *d_total, void *error_bits, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

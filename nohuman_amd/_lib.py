@@ -98,6 +98,11 @@ class nh_read_dust(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("enable", C.c_uint32), ("masked_bases", C.c_uint64)]
 
 
+class nh_host_intervals(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("path", C.c_char_p),
+                ("fragments", C.c_uint64), ("intervals", C.c_uint64), ("covered_bases", C.c_uint64)]
+
+
 class nh_gzip_model_opts(C.Structure):
     _fields_ = [("ways", C.c_uint32), ("region_bytes", C.c_uint32), ("chunk_bytes", C.c_uint64), ("prices", C.c_int32),
                 ("bgzf", C.c_int32), ("threads", C.c_uint32), ("reserved", C.c_uint32),
@@ -242,6 +247,15 @@ SYMBOLS = {
                                      C.POINTER(nh_read_stats), C.POINTER(nh_taxon_out), C.c_uint32, C.POINTER(nh_minimizer_data),
                                      C.POINTER(nh_host_filter), C.POINTER(nh_read_dust), C.POINTER(nh_stats)]),
     "nh_dust_reads_device": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint64, _P, _P, _P]),
+    "nh_run_intervals": (C.c_int, [C.POINTER(nh_run_args), C.POINTER(nh_run_extras), C.c_uint32, C.c_char_p, C.POINTER(nh_read_stats),
+                                   C.POINTER(nh_taxon_out), C.c_uint32, C.POINTER(nh_minimizer_data), C.POINTER(nh_host_filter),
+                                   C.POINTER(nh_read_dust), C.POINTER(nh_host_intervals), C.POINTER(nh_stats)]),
+    "nh_run_engine_intervals": (C.c_int, [_P, C.POINTER(nh_run_args), C.POINTER(nh_run_extras), C.c_uint32, C.c_char_p,
+                                          C.POINTER(nh_read_stats), C.POINTER(nh_taxon_out), C.c_uint32, C.POINTER(nh_minimizer_data),
+                                          C.POINTER(nh_host_filter), C.POINTER(nh_read_dust), C.POINTER(nh_host_intervals),
+                                          C.POINTER(nh_stats)]),
+    "nh_host_cover_device": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint64, _P, C.c_uint64, _P, _P]),
+    "nh_cover_intervals_device": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint64, _P, C.c_uint64, _P, _P, _P]),
     "nh_host_table_image": (C.c_int, [_P, C.c_size_t, C.POINTER(nh_host_filter), _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     "nh_host_filter_device": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint64, _P, _P]),
     "nh_minimizer_marks_bytes": (C.c_int, [_P, C.POINTER(C.c_uint64)]),

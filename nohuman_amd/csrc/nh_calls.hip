@@ -48,16 +48,12 @@ __device__ inline Line load_line(const CallsArgs &a, uint64_t f, bool report) {
     if (f >= a.n) return L;
     const nh_result r = a.res[f];
     const uint64_t i = f * (uint64_t)a.mates;
-    const uint2 hr = reinterpret_cast<const uint2 *>(a.rec)[2 * i];  // {header start, header length} of mate 1
-    const uint64_t h = hr.x, hlen = hr.y;
-    uint32_t idl = a.idlen[f];
-    if (!(r.call < a.n_ext && h + hlen <= a.ntext && (uint64_t)idl + 1 <= hlen)) {
+    uint32_t idl = 0;
+    if (!(r.call < a.n_ext && read_id(a.text, a.ntext, a.rec, a.idlen, f, a.mates, &L.id, &idl))) {  // (the id: nh_outbuild.h, shared with nh_cover.hip)
         if (report) atomicOr(a.error, ERR_CALLS);
+        L.id = 0;
         return L;
     }
-    L.id = h + 1;
-    if (a.mates == 2 && idl > 2 && a.text[L.id + idl - 2] == '/' && (a.text[L.id + idl - 1] == '1' || a.text[L.id + idl - 1] == '2'))
-        idl -= 2;
     L.idlen = idl;
     L.cls = r.call != 0;
     L.v[0] = L.cls ? a.ext[r.call] : 0;

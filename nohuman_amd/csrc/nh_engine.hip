@@ -996,6 +996,10 @@ int check_error_flag(Engine *e) {
             return set_error(NH_EDEVICE, "BAM-out builder: a record lies outside its batch's BAM bytes or output buffer");
         if (flag & 512)
             return set_error(NH_EDEVICE, "read DUST: a sequence lies outside its batch's text (it was skipped: nothing of it was read or masked)");
+        if (flag & NH_ERR_COVER)
+            return set_error(NH_EDEVICE, "host intervals: a sequence or a record's header lies outside its batch's text (it was skipped: nothing of it was read or marked)");
+        if (flag & NH_ERR_COVER_CAP)
+            return set_error(NH_EDEVICE, "host intervals: the intervals of a batch do not fit their buffer (nothing of them was written)");
         if (flag & 32)
             return set_error(NH_EIO,"quality mask / read statistics: a record's quality line is not as long as its sequence, or the record lies outside its batch's text");
         return set_error(NH_ECAPACITY, "a fragment hit more than 2048 distinct taxa");

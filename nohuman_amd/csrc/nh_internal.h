@@ -248,6 +248,64 @@ int check_host_filter(const nh_host_filter *hf);
 int host_table(const Engine *e, const nh_host_filter *hf, std::vector<uint8_t> &host_of);
 hipError_t launch_host_filter(const void *d_in, void *d_out, uint64_t n, const uint8_t *d_host_of, uint64_t n_nodes, unsigned long long *d_counts,
                               int *d_error, hipStream_t stream);
+// Host intervals (nh_cover.hip; nh_run_intervals): k_cover_mark behind the classifier ORs the bases that host k-mers cover into
+// `cover`, one bit a byte of the text (cover_words() uint32, zeroed by the caller); k_cover_ivl_* turn the bitmap into records
+// {seq, start, end}; k_cover_line_* the records into BED lines.  The engine's sticky error word: NH_ERR_COVER, a sequence (or a
+// record's header) outside the text, skipped; NH_ERR_COVER_CAP, a list or a text above its capacity, total 0 and nothing written.
+constexpr int NH_ERR_COVER = 1024, NH_ERR_COVER_CAP = 2048;
+struct CoverArgs {
+    const char *text;         // the text the classifier read, ntext bytes, 4-byte aligned
+    uint64_t ntext;
+    const uint64_t *seq_off;  // n_seq sequence starts (absolute)
+    const uint32_t *seq_len;  // n_seq sequence lengths
+    uint64_t n_seq;
+    const uint8_t *host_of;   // NULL (every non-zero value is host), or n_nodes bytes: host_table()'s
+    uint64_t n_nodes;
+    uint32_t *cover;          // cover_words(ntext) words, ORed into
+    uint64_t *scratch;        // cover_mark_scratch_words(n_seq) words
+    int *error;
+};
+struct CoverIvlArgs {
+    const uint32_t *cover;    // cover_words(ntext) words
+    uint64_t ntext;
+    const uint64_t *seq_off;
+    const uint32_t *seq_len;
+    uint64_t n_seq;
+    uint32_t *rec;            // cap records of three words: sequence, start, end
+    uint64_t cap;
+    uint64_t *total;          // one word: the records written
+    uint64_t *scratch;        // cover_intervals_scratch_words(n_seq) words
+    int *error;
+    uint32_t *cnt;            // (the launcher's: where in the scratch the counts and the block sums lie)
+    uint64_t *blk, nblk;
+};
+struct CoverLinesArgs {
+    const char *text;         // the batch's text (the ids), ntext bytes
+    uint64_t ntext;
+    const uint32_t *rec;      // n * mates {header start (absolute), header length, ...}: the run's record table
+    const uint32_t *idlen;    // n: the length of mate 1's id
+    const nh_result *res;     // n results (the true calls)
+    const uint64_t *ext;      // internal -> external taxon id, n_ext entries
+    uint64_t n_ext, n;        // n: fragments
+    int mates;
+    const uint32_t *ivl;      // the records, *n_ivl of them (a number above cap_ivl: none)
+    const uint64_t *n_ivl;
+    uint64_t cap_ivl;
+    char *out;                // cap bytes
+    uint64_t cap;
+    uint64_t *blk;            // 3 * nblk words of scratch, nblk = cover_line_blocks(cap_ivl)
+    uint64_t nblk;
+    uint64_t *total;          // 4 words: bytes, lines, fragments with a line, covered bases
+    int *error;
+};
+int cover_check_db(const Engine *e);  // NH_OK, or NH_EINVAL: a geometry or a probing the pass does not support, named
+uint64_t cover_words(uint64_t ntext);
+uint64_t cover_mark_scratch_words(uint64_t n_seq);
+uint64_t cover_intervals_scratch_words(uint64_t n_seq);
+uint64_t cover_line_blocks(uint64_t cap_ivl);
+hipError_t launch_cover_mark(Engine *e, const CoverArgs &c, hipStream_t stream);
+hipError_t launch_cover_intervals(const CoverIvlArgs &a, hipStream_t stream);
+hipError_t launch_cover_lines(const CoverLinesArgs &a, hipStream_t stream);
 // buffers kept between the runs of a process (nh_run.hip: page-locked batch text; nh_gunzip.hip: the gzip reader's HBM and
 // staging): emptied when an engine is closed
 void run_cache_trim();

@@ -1,4 +1,4 @@
-// nh_outbuild.h -- what the builders of output text in HBM share (device only): nh_split.hip, nh_mask.hip, nh_calls.hip.
+// nh_outbuild.h -- what the builders of output text in HBM share (device only): nh_split.hip, nh_mask.hip, nh_calls.hip, nh_cover.hip.
 //
 // Each builder makes, per output (a mate's records, a list), one contiguous text out of pieces (records, lines) whose
 // lengths are only known on the device, in three steps that are three launches on the batch's stream:
@@ -98,6 +98,22 @@ __device__ __forceinline__ uint32_t text_dword(const char *text, uint64_t src) {
     const uint32_t lo = w[0];
     if (sh == 0) return lo;
     return __builtin_amdgcn_alignbyte(w[1], lo, sh);
+}
+
+// Mate 1's id of fragment f, as every read list prints it: from the byte behind '@' / '>' of the header (rec: the run's record table,
+// {header start, header length, ...} a sequence; mates sequences a fragment) for the id length the reader found (idlen[f]: up to the
+// first space, tab or '\r'); a paired run drops a trailing "/1" or "/2" from an id longer than two bytes (kraken2 TrimPairInfo).
+// false: the header lies outside the text, or the id is longer than its header -- nothing of the text is read then
+__device__ __forceinline__ bool read_id(const char *text, uint64_t ntext, const uint32_t *rec, const uint32_t *idlen, uint64_t f, int mates, uint64_t *id,
+                                        uint32_t *idl_out) {
+    const uint2 hr = reinterpret_cast<const uint2 *>(rec)[2 * f * (uint64_t)mates];  // {header start, header length} of mate 1
+    const uint64_t h = hr.x, hlen = hr.y;
+    uint32_t idl = idlen[f];
+    if (!(h + hlen <= ntext && (uint64_t)idl + 1 <= hlen)) return false;
+    const uint64_t at = h + 1;
+    if (mates == 2 && idl > 2 && text[at + idl - 2] == '/' && (text[at + idl - 1] == '1' || text[at + idl - 1] == '2')) idl -= 2;
+    *id = at, *idl_out = idl;
+    return true;
 }
 
 // One wave writes the piece out[o, o + len) (inside the buffer: the caller checked).  byte_at(p): byte p of the piece;

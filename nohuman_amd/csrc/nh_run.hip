@@ -428,6 +428,11 @@ struct Slot {  // pinned host + device buffers of one in-flight batch
     BuiltOut lists;  // read lists (nh_run_ex): the calls table [0] and the human ids [1]; totals: bytes[2], lines[2]
     BuiltOut taxon;  // per-taxon outputs (nh_run_taxa): one buffer a mate, K bins in it; totals: start[2][K], bytes[2][K]
     BuiltOut bam;    // BAM output (NH_CODEC_BAM): the selected records of out1 [0] and, a split run, of human_out1 [1]; totals: bytes[2]
+    // host intervals (nh_run_intervals): the BED lines [0] and the interval records they are made from [1]; totals: bytes, lines,
+    // fragments, covered bases -- and the bitmap k_cover_mark ORs into, one bit a byte of the batch's text, zeroed per batch
+    BuiltOut cover;
+    uint32_t *d_cover = nullptr;
+    size_t cap_cover = 0;  // in words
     // runs with a minimum base quality (nh_run_minq): the text-sized buffer the classifier reads instead of d_text -- the
     // sequences with 'N' where the quality is low (nh_qmask.hip; the record table tells where the qualities lie) -- allocated
     // when first needed, and the masked bases of the slot's batches, read once, at the end of the run
@@ -597,7 +602,7 @@ static int slot_reserve_qmask(Slot &s, size_t ntext, size_t nrec) {
 static void slot_free(Slot &s) {
     if (!s.e) return;
     (void)dev_set(s.e->device);
-    for (BuiltOut *o : {&s.human, &s.mask, &s.lists, &s.taxon, &s.bam}) {
+    for (BuiltOut *o : {&s.human, &s.mask, &s.lists, &s.taxon, &s.bam, &s.cover}) {
         for (void *p : {(void *)o->h_out[0], (void *)o->h_out[1], (void *)o->h_total})
             if (p) (void)hipHostFree(p);
         for (void *p : {o->d_blk, (void *)o->d_out[0], (void *)o->d_out[1]})
@@ -609,7 +614,7 @@ static void slot_free(Slot &s) {
         if (p) (void)hipHostFree(p);
     for (void *p : {s.d_rec, s.d_idl, s.d_hres})
         if (p) (void)hipFree(p);
-    for (void *p : {s.d_qtext, (void *)s.d_qcnt, (void *)s.d_dscr, (void *)s.d_dcnt})
+    for (void *p : {s.d_qtext, (void *)s.d_qcnt, (void *)s.d_dscr, (void *)s.d_dcnt, (void *)s.d_cover})
         if (p) (void)hipFree(p);
     for (hipEvent_t ev : {s.duev[0], s.duev[1], s.qev[0], s.qev[1], s.rev[0], s.rev[1], s.mev[0], s.mev[1], s.hev[0], s.hev[1]})
         if (ev) (void)hipEventDestroy(ev);
@@ -724,6 +729,10 @@ struct RunState {
     // devices' counters), k_host_filter's time
     uint64_t host_frags = 0, spared_frags = 0;
     double host_kernel_ms = 0;
+    // host intervals: the fragments with a line, the lines and the covered bases as the devices counted them (nh_host_intervals),
+    // the bytes of the lines, the kernel time of the mark pass and the two builders
+    uint64_t cover_frags = 0, cover_ivls = 0, cover_bases = 0, cover_bytes = 0;
+    double cover_kernel_ms = 0;
     // BAM output (NOHUMAN_TRACE): the records and bytes the builder selected per output, its kernel time
     uint64_t bam_records[2] = {0, 0}, bam_bytes[2] = {0, 0};
     double bam_kernel_ms = 0;
@@ -1177,13 +1186,20 @@ struct RunRequest {
     // input's bases, as with minq.  Not enabled: nothing of this runs.
     nh_read_dust *rd = nullptr;
     bool dust = false;
+    // given (nh_run_intervals): the struct as the caller gave it -- check_request looks at its size --, and `hi_path` where it asks
+    // for the report: k_cover_mark behind the classifier (and the host filter's table) on the slot's stream marks the bases that host
+    // k-mers cover in the text the classifier read, k_cover_ivl_* / k_cover_line_* make the BED lines of the batch (nh_cover.hip).
+    // No path: nothing of this runs.
+    nh_host_intervals *hi = nullptr;
+    const char *hi_path = nullptr;
 };
 
 // The request of an entry: its args, its extras (NULL where it has none, or was given none) or the bare human paths of
 // nh_run_split / nh_run_mask, and as much of nh_run_host's tail as the entry has
 RunRequest make_request(RunRequest::Form form, const nh_run_args *a, const nh_run_extras *x, const char *h1 = nullptr, const char *h2 = nullptr,
                         uint32_t minq = 0, const char *rs_path = nullptr, nh_read_stats *rs_out = nullptr, nh_taxon_out *touts = nullptr,
-                        uint32_t n_touts = 0, nh_minimizer_data *md = nullptr, nh_host_filter *hf = nullptr, nh_read_dust *rd = nullptr) {
+                        uint32_t n_touts = 0, nh_minimizer_data *md = nullptr, nh_host_filter *hf = nullptr, nh_read_dust *rd = nullptr,
+                        nh_host_intervals *hi = nullptr) {
     static const char *const names[] = {"nh_run", "nh_run_split", "nh_run_mask", "nh_run_ex"};
     RunRequest r;
     r.form = form == RunRequest::RUN && x ? RunRequest::EX : form;
@@ -1195,6 +1211,7 @@ RunRequest make_request(RunRequest::Form form, const nh_run_args *a, const nh_ru
     r.minq = minq, r.rs_path = rs_path, r.rs_out = rs_out, r.touts = touts, r.n_touts = n_touts, r.md = md;
     r.hf = host_filter_given(hf) ? hf : nullptr;  // (no taxid listed: the run of nh_run_mdata, and the struct is not looked at again)
     r.rd = rd, r.dust = rd && rd->struct_size >= sizeof(nh_read_dust) && rd->enable != 0;
+    r.hi = hi, r.hi_path = hi && hi->struct_size >= sizeof(nh_host_intervals) ? hi->path : nullptr;
     return r;
 }
 
@@ -1209,7 +1226,7 @@ static bool same_file(const char *candidate, const char *other) {
 
 // One file of a request.  The kinds are in the order of the checks: a feature's files are checked against the files of the kinds
 // before it (and the read lists and the selectors' files among themselves).
-enum FileKind { F_INPUT, F_OUTPUT, F_HUMAN, F_LIST, F_RSTATS, F_TAXON, F_MDATA };
+enum FileKind { F_INPUT, F_OUTPUT, F_HUMAN, F_LIST, F_RSTATS, F_TAXON, F_MDATA, F_COVER };
 struct RunFile {
     const char *path;   // never NULL; may be empty
     FileKind kind;
@@ -1233,6 +1250,7 @@ static std::vector<RunFile> request_files(const RunRequest &r, FileKind last) {
     for (uint32_t i = 0; last >= F_TAXON && r.touts && i < r.n_touts; i++)
         for (int m = 0; m < 2; m++) add(m ? r.touts[i].out2 : r.touts[i].out1, F_TAXON, "nh_run_taxa", "outs[" + std::to_string(i) + "].out" + std::to_string(m + 1));
     if (last >= F_MDATA && r.md) add(r.md->table, F_MDATA, "nh_run_mdata", "the minimizer table");
+    add(r.hi_path, F_COVER, "nh_run_intervals", "the host intervals' file");
     return f;
 }
 
@@ -1364,6 +1382,18 @@ static int check_mdata_args(const RunRequest &r) {
     return check_files(r, F_MDATA);
 }
 
+// nh_run_intervals' own arguments: the struct, and a file that names no input and no other output of the run
+static int check_cover_args(const RunRequest &r) {
+    const nh_host_intervals *hi = r.hi;
+    if (!hi) return NH_OK;
+    if (hi->struct_size < sizeof(nh_host_intervals))
+        return set_error(NH_EINVAL, "nh_run_intervals: struct_size %u is smaller than nh_host_intervals (%zu bytes)", hi->struct_size, sizeof(nh_host_intervals));
+    if (!r.hi_path) return NH_OK;
+    if (!r.a) return set_error(NH_EINVAL, "nh_run_intervals: null arguments");
+    if (!r.hi_path[0]) return set_error(NH_EINVAL, "nh_run_intervals: path is an empty path");
+    return check_files(r, F_COVER);
+}
+
 // The container of the record outputs: a codec there is none of, and what BAM output (NH_CODEC_BAM: the selected records of a BAM
 // in1, copied) does not go with -- a second input, a masked run, per-taxon outputs (the last two: not built yet), an in1 that is
 // no BAM file.  (A request without arguments is refused by its entry.)
@@ -1383,7 +1413,7 @@ static int check_out_codec(const RunRequest &r) {
 
 // Every entry's checks, in one order: the host selection's own, the minimum base quality (the highest printable quality is '~',
 // Phred 93), the read DUST's struct, the extras (the mask or the human outputs, then the read lists), the read statistics' table, the selectors, the
-// minimizer data, the container.  What an entry cannot ask for is not set in its request and checks nothing.
+// minimizer data, the host intervals, the container.  What an entry cannot ask for is not set in its request and checks nothing.
 int check_request(const RunRequest &r) {
     int rc = check_host_filter(r.hf);
     if (!rc && r.minq > 93) rc = set_error(NH_EINVAL, "minimum base quality %u is not in 0..93 (Phred+33)", r.minq);
@@ -1393,6 +1423,7 @@ int check_request(const RunRequest &r) {
     if (!rc) rc = check_rstats_args(r);
     if (!rc) rc = check_taxon_args(r);
     if (!rc) rc = check_mdata_args(r);
+    if (!rc) rc = check_cover_args(r);
     if (!rc) rc = check_out_codec(r);
     return rc;
 }
@@ -1411,6 +1442,7 @@ struct RunFiles {
     OutFile o1, o2, ok;  // the kept records of mate 1 / mate 2, the per-read kraken output
     OutFile h1, h2;      // the classified records of a split run
     OutFile oc, oi;      // the read lists (calls, human ids): plain text whatever the codec of the records
+    OutFile ohi;         // the host intervals: plain text as well
     OutFile tx[2][NH_MAX_TAXON_OUTS];  // the selectors' files, [mate][selector]
 };
 
@@ -1452,6 +1484,7 @@ static int open_run_files(RunFiles &f, const RunRequest &r, const std::vector<En
     if (want_k && (rc = f.ok.open(a->kraken_output))) return rc;
     if (r.calls && (rc = f.oc.open(r.calls))) return rc;
     if (r.ids && (rc = f.oi.open(r.ids))) return rc;
+    if (r.hi_path && (rc = f.ohi.open(r.hi_path))) return rc;
     return NH_OK;
 }
 
@@ -1711,6 +1744,8 @@ struct RunShape {
     int n_bout, K;     // BAM output: the builder's outputs; per-taxon outputs: the selectors
     bool taxa, qm, rst, mdt, hsel;
     bool dust;         // --dust-reads: k_rdust in front of the classifier
+    bool cover;        // --host-intervals: k_cover_mark and the two builders behind the classifier
+    bool idl;          // a builder prints mate 1's id: the id lengths go to the device (the read lists, the host intervals)
     bool qtext;        // the classifier and the minimizer data's marks read the slot's masked text, not the batch's (qm or dust)
     bool want_rec;     // a kernel of the run reads the record table
     bool gzip_family;  // the codecs the GPU encodes
@@ -1730,7 +1765,8 @@ struct RunShape {
         qm = minq > 0, rst = r.rs_path || r.rs_out, hsel = r.hf != nullptr;
         dust = r.dust, qtext = qm || dust;
         mdt = r.md && (r.md->in_report || r.md->table || r.md->taxa);
-        want_rec = split || mask || lists || qm || rst || taxa;
+        cover = r.hi_path != nullptr, idl = lists || cover;
+        want_rec = split || mask || lists || qm || rst || taxa || cover;
         gzip_family = a->out_codec == NH_CODEC_GZIP || a->out_codec == NH_CODEC_BGZF || bamout;
         G = (int)n_engines;
         // stream slots a device: two keep the classifier busy; a third lets the copy of a batch's text back to the host (batches
@@ -1772,6 +1808,7 @@ struct FlushJob {
     Batch b;
     Spans s1, s2, sk, hs1, hs2;  // (hs1, hs2: a split run's classified records, one span a mate)
     Spans sc, si;                // (the batch's part of the calls table and of the human ids, one span each)
+    Spans shi;                   // (... and of the host intervals)
     Spans ts[2][NH_MAX_TAXON_OUTS];  // (per-taxon outputs: a span a mate and selector with records in the batch)
     // the built spans that only exist in HBM (an address there, never read on the host): the flusher maps them for the file's encoder
     std::vector<std::pair<OutFile *, struct iovec>> dev;
@@ -1856,6 +1893,7 @@ struct Pipeline {
         if (sh.taxa) builders.push_back({&Slot::taxon, 4 * (size_t)sh.K, &RunState::taxon_kernel_ms});
         if (sh.mask) builders.push_back({&Slot::mask, 4, &RunState::mask_kernel_ms});
         if (sh.lists) builders.push_back({&Slot::lists, 4, &RunState::list_kernel_ms});
+        if (sh.cover) builders.push_back({&Slot::cover, 4, &RunState::cover_kernel_ms});
         if (sh.qm) passes.push_back({&Slot::qev, &RunState::qmask_kernel_ms});
         if (sh.dust) passes.push_back({&Slot::duev, &RunState::dust_kernel_ms});
         if (sh.rst) passes.push_back({&Slot::rev, &RunState::rstats_kernel_ms});
@@ -2088,6 +2126,7 @@ struct Pipeline {
                     if (!j->ts[0][k].iov.empty()) wrc = f.tx[0][k].flush(j->ts[0][k]);
                 if (!wrc && sh.calls) wrc = f.oc.flush(j->sc);
                 if (!wrc && sh.ids) wrc = f.oi.flush(j->si);
+                if (!wrc && sh.cover) wrc = f.ohi.flush(j->shi);
                 if (rs.paired) {
                     std::unique_lock<std::mutex> lk(w2_mu);
                     w2_cv.wait(lk, [&] { return w2_state == 2; });
@@ -2183,6 +2222,7 @@ struct Pipeline {
                     if (sh.taxa) build_taxon(SPANS, s, b, j.get(), &wrc);
                     if (sh.rst) note_lengths(s, b);
                     if (sh.lists) build_lists(SPANS, s, b, j.get(), &wrc);
+                    if (sh.cover) build_cover(SPANS, s, b, j.get(), &wrc);
                     clk.ns[ST_WFORMAT] += StageClock::now() - c2;
                     j->s1 = std::move(f.o1.sp), j->s2 = std::move(f.o2.sp), j->sk = std::move(f.ok.sp);
                     f.o1.sp.clear(), f.o2.sp.clear(), f.ok.sp.clear();
@@ -2372,6 +2412,76 @@ struct Pipeline {
         }
     }
 
+    // the host intervals (nh_cover.hip): the bitmap zeroed, the mark pass on the text the classifier read, the bitmap into records,
+    // the records into BED lines -- exactly the built bytes, copied to the slot's page-locked memory, one span.  An interval holds
+    // k = 35 bases at least and a base that is not covered lies between two of a sequence: (len + 1) / 36 of them at the most
+    static size_t cover_max_intervals(size_t len) { return (len + 1) / 36; }
+    size_t cover_max_records(const Batch &b, size_t *line_bytes) const {
+        size_t nrec = 0, nbytes = 0;
+        for (size_t i = 0; i < b.n; i++) {
+            size_t m = cover_max_intervals(b.h1->recs[b.off1 + i].slen);
+            if (b.h2) m += cover_max_intervals(b.h2->recs[b.off2 + i].slen);
+            // a line: the id, then at most 1 + 10 + 1 + 10 + 2 + 1 + 20 + 1 bytes of numbers, separators and the newline
+            nrec += m, nbytes += m * ((size_t)b.h1->recs[b.off1 + i].idlen + 46);
+        }
+        if (line_bytes) *line_bytes = nbytes;
+        return nrec;
+    }
+    void build_cover(BuildStep step, Slot &s, const Batch &b, FlushJob *j, int *rc) {
+        const int mates = sh.mates;
+        const size_t nseq = b.n * (size_t)mates;
+        const size_t pass_words = (size_t)std::max(cover_mark_scratch_words(nseq), cover_intervals_scratch_words(nseq));
+        if (step == RESERVE) {
+            size_t nbytes = 0;
+            const size_t nrec = cover_max_records(b, &nbytes);
+            const size_t out_cap[2] = {nbytes + 64, (nrec + 1) * 12};
+            if (!*rc) *rc = slot_reserve_rec(s, nseq);
+            if (!*rc) *rc = slot_reserve_idl(s, b.n);
+            // (the scratch: the larger of the mark pass's and the interval builder's, the records' total, the line builder's block sums and totals)
+            if (!*rc) *rc = built_reserve(s.cover, pass_words + 1 + 3 * (size_t)cover_line_blocks(nrec) + 4, out_cap, 2, "host-interval buffers");
+            const size_t cw = (size_t)cover_words(b.ntext());
+            if (!*rc && cw > s.cap_cover) {
+                if (s.d_cover) (void)hipFree(s.d_cover);
+                s.d_cover = nullptr;
+                s.cap_cover = grow(cw);
+                if (dev_malloc((void **)&s.d_cover, s.cap_cover * 4) != hipSuccess) *rc = set_error(NH_EOOM, "cannot allocate the host intervals' bitmap (%zu words)", s.cap_cover);
+            }
+        } else if (step == LAUNCH) {
+            const uint64_t ntext = b.ntext();
+            const size_t nrec = cover_max_records(b, nullptr);
+            int *const d_error = s.e->d_error + LAUNCH_SLOTS;
+            uint64_t *const scratch = (uint64_t *)s.cover.d_blk;
+            uint64_t *const n_ivl = scratch + pass_words;
+            CoverArgs ca{};
+            ca.text = (const char *)(sh.qtext ? s.d_qtext : s.d_text), ca.ntext = ntext;
+            ca.seq_off = (const uint64_t *)s.d_off, ca.seq_len = (const uint32_t *)s.d_len, ca.n_seq = nseq;
+            ca.host_of = sh.hsel ? dbuf[(size_t)b.dev_index].host_of : nullptr, ca.n_nodes = s.e->external.size();
+            ca.cover = s.d_cover, ca.scratch = scratch, ca.error = d_error;
+            CoverIvlArgs ia{};
+            ia.cover = s.d_cover, ia.ntext = ntext, ia.seq_off = ca.seq_off, ia.seq_len = ca.seq_len, ia.n_seq = nseq;
+            ia.rec = (uint32_t *)s.cover.d_out[1], ia.cap = nrec, ia.total = n_ivl, ia.scratch = scratch, ia.error = d_error;
+            CoverLinesArgs la{};
+            la.text = (const char *)s.d_text, la.ntext = ntext;
+            la.rec = (const uint32_t *)s.d_rec, la.idlen = (const uint32_t *)s.d_idl, la.res = (const nh_result *)s.d_res;
+            la.ext = s.e->d_external, la.n_ext = s.e->external.size(), la.n = b.n, la.mates = mates;
+            la.ivl = ia.rec, la.n_ivl = n_ivl, la.cap_ivl = nrec;
+            la.out = s.cover.d_out[0], la.cap = s.cover.cap_out[0];
+            la.blk = n_ivl + 1, la.nblk = cover_line_blocks(nrec);
+            la.total = s.cover.d_total = la.blk + 3 * la.nblk;
+            la.error = d_error;
+            timed_launch(rs, s.stream, s.cover.ev, "host intervals", [&] {
+                hipError_t he = hipMemsetAsync(s.d_cover, 0, (size_t)cover_words(ntext) * 4, s.stream);
+                if (he == hipSuccess) he = launch_cover_mark(s.e, ca, s.stream);
+                if (he == hipSuccess) he = launch_cover_intervals(ia, s.stream);
+                if (he == hipSuccess) he = launch_cover_lines(la, s.stream);
+                return he;
+            });
+        } else {
+            rs.cover_ivls += s.cover.h_total[1], rs.cover_frags += s.cover.h_total[2], rs.cover_bases += s.cover.h_total[3];
+            one_span(j, s.cover, 0, false, f.ohi, j->shi, &rs.cover_bytes, rc, "host-interval buffers", "host intervals");
+        }
+    }
+
     // main: pair halves, stage, launch
     void run() {
         for (bool last = false; !last && !rs.failed();) {
@@ -2487,6 +2597,7 @@ struct Pipeline {
         if (sh.mask) build_mask(RESERVE, s, b, nullptr, &rc);
         if (sh.bamout) build_bam(RESERVE, s, b, nullptr, &rc);
         if (sh.lists) build_lists(RESERVE, s, b, nullptr, &rc);
+        if (sh.cover) build_cover(RESERVE, s, b, nullptr, &rc);
         if (!rc && sh.qm) rc = slot_reserve_qmask(s, b.ntext(), b.n * (size_t)sh.mates);
         if (!rc && sh.dust) rc = slot_reserve_dust(s, b.ntext(), b.n * (size_t)sh.mates);
         if (!rc && sh.rst) rc = slot_reserve_rec(s, b.n * (size_t)sh.mates);
@@ -2521,7 +2632,7 @@ struct Pipeline {
             s.h_off[i * mates] = r1.s;
             s.h_len[i * mates] = r1.slen;
             nbases += r1.slen;
-            if (sh.lists) s.h_idl[i] = r1.idlen;
+            if (sh.idl) s.h_idl[i] = r1.idlen;
             if (sh.want_rec) {
                 uint32_t *hr = s.h_rec + 4 * i * mates;
                 hr[0] = r1.h, hr[1] = r1.hlen, hr[2] = r1.q, hr[3] = r1.qlen;
@@ -2572,14 +2683,14 @@ struct Pipeline {
         if (he == hipSuccess) he = hipMemcpyAsync(s.d_len, s.h_len, b.n * mates * 4, hipMemcpyHostToDevice, s.stream);
         if (he == hipSuccess && rs.want_k) he = hipMemcpyAsync(s.d_taxa_off, s.h_taxa_off, (b.n + 1) * 8, hipMemcpyHostToDevice, s.stream);
         if (he == hipSuccess && sh.want_rec) he = hipMemcpyAsync(s.d_rec, s.h_rec, b.n * mates * 16, hipMemcpyHostToDevice, s.stream);
-        if (he == hipSuccess && sh.lists) he = hipMemcpyAsync(s.d_idl, s.h_idl, b.n * 4, hipMemcpyHostToDevice, s.stream);
+        if (he == hipSuccess && sh.idl) he = hipMemcpyAsync(s.d_idl, s.h_idl, b.n * 4, hipMemcpyHostToDevice, s.stream);
         if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("H2D: ") + hipGetErrorString(he));
         return he == hipSuccess;
     }
 
     // the batch's launches on the slot's stream, in this order: the quality mask, the read DUST (on a copy of the text where no
     // quality mask has written the sequences), the classifier, the host filter, the read
-    // statistics, the minimizer data's marks, then the builders -- lists, split, BAM out, per-taxon, mask.  Each goes out only
+    // statistics, the minimizer data's marks, then the builders -- lists, host intervals, split, BAM out, per-taxon, mask.  Each goes out only
     // while the run has not failed.
     void launch(Slot &s, const Batch &b, uint64_t nbases, bool staged) {
         const int mates = sh.mates;
@@ -2630,6 +2741,7 @@ struct Pipeline {
             });
         int none = NH_OK;  // (a launch fails the run itself)
         if (!rs.failed() && sh.lists) build_lists(LAUNCH, s, b, nullptr, &none);
+        if (!rs.failed() && sh.cover) build_cover(LAUNCH, s, b, nullptr, &none);
         if (!rs.failed() && sh.split) build_human(LAUNCH, s, b, nullptr, &none);
         if (!rs.failed() && sh.bamout) build_bam(LAUNCH, s, b, nullptr, &none);
         if (!rs.failed() && sh.taxa) build_taxon(LAUNCH, s, b, nullptr, &none);
@@ -2706,6 +2818,10 @@ static void print_run_trace(const RunShape &sh, RunState &rs, const StageClock &
         fprintf(stderr, "[nohuman trace] calls: %llu lines, %llu bytes; ids: %llu lines, %llu bytes built on device; %llu fetched to host; builder kernels %.3f ms\n",
                 (unsigned long long)rs.list_lines[0], (unsigned long long)rs.list_bytes[0], (unsigned long long)rs.list_lines[1],
                 (unsigned long long)rs.list_bytes[1], fetched, rs.list_kernel_ms);
+    if (sh.cover)
+        fprintf(stderr, "[nohuman trace] host-intervals: %llu intervals in %llu fragments, %llu bases covered, %llu bytes built on device; kernels %.3f ms\n",
+                (unsigned long long)rs.cover_ivls, (unsigned long long)rs.cover_frags, (unsigned long long)rs.cover_bases,
+                (unsigned long long)rs.cover_bytes, rs.cover_kernel_ms);
     if (sh.qm)
         fprintf(stderr, "[nohuman trace] qmask: Q %u, %llu of %llu bases masked, kernel %.3f ms\n", sh.minq,
                 (unsigned long long)rs.qmask_masked, (unsigned long long)rs.total_bases, rs.qmask_kernel_ms);
@@ -2740,6 +2856,7 @@ static int close_run_files(RunFiles &f, const RunShape &sh, const RunState &rs) 
     if (rs.want_k && (rc = f.ok.close())) return rc;
     if (sh.calls && (rc = f.oc.close())) return rc;
     if (sh.ids && (rc = f.oi.close())) return rc;
+    if (sh.cover && (rc = f.ohi.close())) return rc;
     return NH_OK;
 }
 
@@ -2820,7 +2937,7 @@ static int check_run_files(const RunRequest &r, const RunState &rs) {
     // outputs are created with O_TRUNC before the first input byte is read: an output that IS an input
     // (same device and inode) would be emptied -- refuse (the CLI host stages its outputs and renames).  Only an output that is
     // there, as a regular file, is looked at; for a plain nh_run this is the only such check.
-    const std::vector<RunFile> files = request_files(r, F_MDATA);
+    const std::vector<RunFile> files = request_files(r, F_COVER);
     size_t inputs = 0;
     while (inputs < files.size() && files[inputs].kind == F_INPUT) inputs++;
     for (size_t c = inputs; c < files.size(); c++) {
@@ -2848,8 +2965,11 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
         if ((rc = host_table(engines[0], r.hf, host_of))) return rc;
         r.hf->host_fragments = r.hf->spared_fragments = 0;
     }
+    for (size_t g = 0; sh.cover && g < engines.size(); g++)
+        if ((rc = cover_check_db(engines[g]))) return rc;
     if (r.rd) r.rd->masked_bases = 0;
-    if (sh.split || sh.lists || sh.taxa)
+    if (sh.cover) r.hi->fragments = r.hi->intervals = r.hi->covered_bases = 0;
+    if (sh.split || sh.lists || sh.taxa || sh.cover)
         for (Engine *e : engines)
             if ((rc = ensure_device_external(e))) return rc;
     RunState rs;
@@ -2910,6 +3030,7 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
     for (int k = 0; k < sh.K; k++) r.touts[k].fragments = rs.taxon_frags[k];
     if (sh.hsel) r.hf->host_fragments = rs.host_frags, r.hf->spared_fragments = rs.spared_frags;
     if (sh.dust) r.rd->masked_bases = rs.dust_masked;
+    if (sh.cover) r.hi->fragments = rs.cover_frags, r.hi->intervals = rs.cover_ivls, r.hi->covered_bases = rs.cover_bases;
     if (sh.mdt && (rc = report_mdata(mdview, mdn, r.md))) return rc;
     if (stats) {
         nh_stats st;
@@ -2990,6 +3111,15 @@ int nh_run_engine_dust(nh_engine *e, const nh_run_args *args, const nh_run_extra
                        nh_host_filter *hf, nh_read_dust *rd, nh_stats *stats) {
     return run_on_engine(
         e, nh::make_request(nh::RunRequest::RUN, args, extras, nullptr, nullptr, min_base_quality, read_stats_path, read_stats, outs, n_outs, md, hf, rd),
+        stats);
+}
+
+// (hi NULL, or its path NULL: the request is nh_run_engine_dust's)
+int nh_run_engine_intervals(nh_engine *e, const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality,
+                            const char *read_stats_path, nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs, nh_minimizer_data *md,
+                            nh_host_filter *hf, nh_read_dust *rd, nh_host_intervals *hi, nh_stats *stats) {
+    return run_on_engine(
+        e, nh::make_request(nh::RunRequest::RUN, args, extras, nullptr, nullptr, min_base_quality, read_stats_path, read_stats, outs, n_outs, md, hf, rd, hi),
         stats);
 }
 
@@ -3263,6 +3393,15 @@ int nh_run_dust(const nh_run_args *args, const nh_run_extras *extras, uint32_t m
                 nh_stats *stats) {
     return run_standalone(
         nh::make_request(nh::RunRequest::RUN, args, extras, nullptr, nullptr, min_base_quality, read_stats_path, read_stats, outs, n_outs, md, hf, rd),
+        stats);
+}
+
+// (hi NULL, or its path NULL: the request is nh_run_dust's)
+int nh_run_intervals(const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality, const char *read_stats_path,
+                     nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs, nh_minimizer_data *md, nh_host_filter *hf, nh_read_dust *rd,
+                     nh_host_intervals *hi, nh_stats *stats) {
+    return run_standalone(
+        nh::make_request(nh::RunRequest::RUN, args, extras, nullptr, nullptr, min_base_quality, read_stats_path, read_stats, outs, n_outs, md, hf, rd, hi),
         stats);
 }
 

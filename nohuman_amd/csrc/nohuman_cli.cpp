@@ -253,6 +253,7 @@ struct Args {
     unsigned min_base_quality = 0;  // kraken2's --minimum-base-quality (nh_run_minq); 0: off
     bool dust_reads = false;        // classify every read with its low-complexity stretches as ambiguous bases (nh_run_dust)
     std::string read_stats;         // the read statistics table (nh_run_rstats)
+    std::string host_intervals;     // the BED file of the bases that host k-mers cover (nh_run_intervals)
     bool report_minimizer_data = false;  // kraken2's flag: two more columns in the report (nh_run_mdata)
     std::string minimizer_table;         // the minimizer table (nh_run_mdata)
     // per-taxon outputs (nh_run_taxa): the selectors in the order given -- taxid (0: `other`), the path as given ('#' in it: the mate)
@@ -304,6 +305,10 @@ static void usage(FILE *f) {
           "      --minimum-base-quality <INT>  Kraken2 minimum base quality: classify FASTQ bases with a lower Phred+33 quality as ambiguous (0-93; the reads written keep their bases) [default: 0]\n"
           "      --dust-reads             Classify every read with its low-complexity stretches (poly-A, microsatellites: symmetric DUST, window 64, level 20) "
           "as ambiguous bases, so that a database built without low-complexity filtering does not call them human (the reads written keep their bases)\n"
+          "      --host-intervals <FILE>  Write where in each read the host k-mers lie, as BED without a header: one line 'id, start, end, mate (1|2), taxid of the read's call' for every "
+          "maximal run of bases covered by k-mers whose minimizer is in the database (with --host-taxid: in the host clades), 0-based and half-open, in input order. Plain text, never "
+          "compressed; no other output changes. With --minimum-base-quality / --dust-reads the masked bases are not covered. For BAM input the coordinates are those of the FASTQ "
+          "record the read is transcoded to: a reverse-strand record is counted on its reverse complement\n"
           "  -k, --kraken-output <FILE>   Write the Kraken2 read classification output to a file\n"
           "  -r, --kraken-report <FILE>   Write the Kraken2 report with aggregate counts/clade to file\n"
           "      --report-minimizer-data  Report, per clade, the minimizer hits of the reads and how many distinct minimizers they were, as columns 4 and 5 of the Kraken2 report "
@@ -424,6 +429,7 @@ static Args parse_args(int argc, char **argv) {
         else if (s == "--calls") a.calls = val();
         else if (s == "--human-ids") a.human_ids = val();
         else if (s == "--read-stats") a.read_stats = val();
+        else if (s == "--host-intervals") a.host_intervals = val();
         else if (s == "--report-minimizer-data") a.report_minimizer_data = true;
         else if (s == "--minimizer-table") a.minimizer_table = val();
         else if (s == "--taxon-out") {
@@ -507,7 +513,8 @@ static Args parse_args(int argc, char **argv) {
                              : !a.human_ids.empty() ? "--human-ids" : !a.read_stats.empty() ? "--read-stats" : a.report_minimizer_data ? "--report-minimizer-data"
                              : !a.minimizer_table.empty() ? "--minimizer-table" : a.has_type ? "--output-type"
                              : a.bgzf ? "--bgzf" : a.bam_out ? "--bam-out" : a.mask ? "--mask" : a.human ? "--human" : !a.taxon_out.empty() ? "--taxon-out"
-                             : !a.host_taxids.empty() ? "--host-taxid" : !a.keep_taxids.empty() ? "--keep-taxid" : a.dust_reads ? "--dust-reads" : nullptr;
+                             : !a.host_taxids.empty() ? "--host-taxid" : !a.keep_taxids.empty() ? "--keep-taxid" : a.dust_reads ? "--dust-reads"
+                             : !a.host_intervals.empty() ? "--host-intervals" : nullptr;
         if (out_flag) arg_error("the argument '--build-db <DIR>' cannot be used with '%s'", out_flag);
         if (a.has_extend_db) {
             if (a.capacity) arg_error("the argument '--extend-db <DIR>' cannot be used with '--capacity <INT>': an extension keeps the capacity of its base");
@@ -596,6 +603,16 @@ static Args parse_args(int argc, char **argv) {
         if (other) arg_error("the argument '--minimizer-table <FILE>' names the same file as '%s': %s", other, p.c_str());
         for (const std::string &in : a.input)
             if (p == in) arg_error("the argument '--minimizer-table <FILE>' names the input %s", p.c_str());
+    }
+    if (!a.host_intervals.empty()) {
+        const std::string &p = a.host_intervals;
+        const char *other = (a.has_out1 && p == a.out1) ? "--out1" : (a.has_out2 && p == a.out2) ? "--out2"
+                          : (a.has_human_out1 && p == a.human_out1) ? "--human-out1" : (a.has_human_out2 && p == a.human_out2) ? "--human-out2"
+                          : p == a.kraken_output ? "--kraken-output" : p == a.kraken_report ? "--kraken-report" : p == a.calls ? "--calls"
+                          : p == a.human_ids ? "--human-ids" : p == a.read_stats ? "--read-stats" : p == a.minimizer_table ? "--minimizer-table" : nullptr;
+        if (other) arg_error("the argument '--host-intervals <FILE>' names the same file as '%s': %s", other, p.c_str());
+        for (const std::string &in : a.input)
+            if (p == in) arg_error("the argument '--host-intervals <FILE>' names the input %s", p.c_str());
     }
     return a;
 }
@@ -914,6 +931,8 @@ int main(int argc, char **argv) {
     if (!args.human_ids.empty()) staged_files.push_back({args.human_ids, ipart});
     const std::string spart = args.read_stats.empty() ? "" : staged(args.read_stats);
     if (!args.read_stats.empty()) staged_files.push_back({args.read_stats, spart});
+    const std::string bpart = args.host_intervals.empty() ? "" : staged(args.host_intervals);
+    if (!args.host_intervals.empty()) staged_files.push_back({args.host_intervals, bpart});
     const std::string mpart = args.minimizer_table.empty() ? "" : staged(args.minimizer_table);
     if (!args.minimizer_table.empty()) staged_files.push_back({args.minimizer_table, mpart});
     // the per-taxon files: staged and renamed like the human outputs
@@ -995,7 +1014,14 @@ int main(int argc, char **argv) {
     memset(&rd, 0, sizeof rd);
     rd.struct_size = (uint32_t)sizeof rd;
     rd.enable = args.dust_reads ? 1 : 0;
-    const int run_rc = args.dust_reads ? nh_run_dust(&ra, lists || args.mask || split ? &rx : nullptr, args.min_base_quality,
+    nh_host_intervals hi;
+    memset(&hi, 0, sizeof hi);
+    hi.struct_size = (uint32_t)sizeof hi;
+    hi.path = args.host_intervals.empty() ? nullptr : bpart.c_str();
+    const int run_rc = hi.path ? nh_run_intervals(&ra, lists || args.mask || split ? &rx : nullptr, args.min_base_quality,
+                                                  args.read_stats.empty() ? nullptr : spart.c_str(), nullptr, touts.empty() ? nullptr : touts.data(),
+                                                  (uint32_t)touts.size(), md.in_report || md.table ? &md : nullptr, hsel ? &hf : nullptr, &rd, &hi, &st)
+                       : args.dust_reads ? nh_run_dust(&ra, lists || args.mask || split ? &rx : nullptr, args.min_base_quality,
                                                      args.read_stats.empty() ? nullptr : spart.c_str(), nullptr, touts.empty() ? nullptr : touts.data(),
                                                      (uint32_t)touts.size(), md.in_report || md.table ? &md : nullptr, hsel ? &hf : nullptr, &rd, &st)
                        : hsel ? nh_run_host(&ra, lists || args.mask || split ? &rx : nullptr, args.min_base_quality,
@@ -1040,6 +1066,10 @@ int main(int argc, char **argv) {
     if (args.dust_reads)
         DEBUG("%llu low-complexity bases of the reads masked for classification (%.2f %% of the bases)", (unsigned long long)rd.masked_bases,
               st.total_bases ? 100.0 * (double)rd.masked_bases / (double)st.total_bases : 0.0);
+    if (hi.path)
+        DEBUG("Host intervals: %llu intervals in %llu reads, %llu bases covered by host k-mers (%.2f %% of the bases)", (unsigned long long)hi.intervals,
+              (unsigned long long)hi.fragments, (unsigned long long)hi.covered_bases,
+              st.total_bases ? 100.0 * (double)hi.covered_bases / (double)st.total_bases : 0.0);
     if (g_verbose) {  // a BAM input: what the reader made of its records (the host side of the reader once more: nh_bam_scan)
         nh_bam_info bi;
         memset(&bi, 0, sizeof bi);
@@ -1073,6 +1103,7 @@ int main(int argc, char **argv) {
     if (!args.calls.empty()) INFO("Calls table written to: %s", quoted(args.calls).c_str());
     if (!args.human_ids.empty()) INFO("Human read ids written to: %s", quoted(args.human_ids).c_str());
     if (!args.read_stats.empty()) INFO("Read statistics written to: %s", quoted(args.read_stats).c_str());
+    if (!args.host_intervals.empty()) INFO("Host intervals written to: %s", quoted(args.host_intervals).c_str());
     if (!args.minimizer_table.empty()) INFO("Minimizer table written to: %s", quoted(args.minimizer_table).c_str());
     if (!args.kraken_report.empty()) INFO("Kraken report file written to: %s", quoted(args.kraken_report).c_str());
     INFO("Done.");

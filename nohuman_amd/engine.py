@@ -44,7 +44,8 @@ def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
         threads: int = 1, keep_human: bool = False, device_ids=None, out_codec: int = 0,
         codec_threads: int = 0, human_out1=None, human_out2=None, mask: bool = False, calls=None,
         human_ids=None, min_base_quality: int = 0, read_stats=None, taxon_outs=None, report_minimizer_data: bool = False,
-        minimizer_table=None, minimizer_data=None, host_taxids=None, keep_taxids=None, dust_reads: bool = False) -> "_lib.nh_stats":
+        minimizer_table=None, minimizer_data=None, host_taxids=None, keep_taxids=None, dust_reads: bool = False,
+        host_intervals=None) -> "_lib.nh_stats":
     """nh_run: whole run, database loaded into every listed device (default: all visible).  human_out1 (and, paired,
     human_out2) given: nh_run_split -- the non-human reads go to out1 / out2 and, in the same pass, the human reads to
     human_out1 / human_out2 exactly as a keep_human run would write them.  mask: nh_run_mask -- every read goes to
@@ -82,7 +83,13 @@ def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
     dust_reads (nh_run_dust; any kind of run): every sequence, both mates, FASTA as FASTQ, is classified with its low-complexity
     stretches (symmetric DUST, window 64, level 20, each sequence on its own) as ambiguous bases -- what cures the false positives
     of a database built without low-complexity masking; every record written keeps its bases.  With min_base_quality the
-    classifier sees the union of the two masks.  The stats returned then carry dust_masked_bases."""
+    classifier sees the union of the two masks.  The stats returned then carry dust_masked_bases.
+    host_intervals (nh_run_intervals; any kind of run): a BED file, plain text, of where in each read the host k-mers lie -- a line
+    `id, start, end, mate (1|2), taxid of the call` for every maximal run of bases that host k-mers cover (0-based, half-open), in
+    input order; a k-mer is host when its minimizer is found in the table and, with host_taxids / keep_taxids, its value lies in
+    the host clades.  Nothing else the run writes changes.  A BAM input's coordinates are those of the FASTQ text the reader
+    transcodes to: a reverse-strand record is counted on its reverse complement.  The stats returned then carry
+    interval_fragments, intervals and covered_bases."""
     a = _lib.nh_run_args()
     a.db_dir = os.fsencode(db_dir)
     a.in1 = os.fsencode(in1)
@@ -106,19 +113,20 @@ def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
         a.device_ids = None
     return _run_entry("nh_run", (), lambda: _taxo_nodes(os.fspath(db_dir)), a, human_out1, human_out2, mask, calls, human_ids,
                       min_base_quality, read_stats, taxon_outs, report_minimizer_data, minimizer_table, minimizer_data, host_taxids,
-                      keep_taxids, dust_reads)
+                      keep_taxids, dust_reads, host_intervals)
 
 
 def _run_entry(prefix, lead, nodes, a, human_out1, human_out2, mask, calls, human_ids, min_base_quality, read_stats, taxon_outs,
-               report_minimizer_data, minimizer_table, minimizer_data, host_taxids, keep_taxids, dust_reads=False) -> "_lib.nh_stats":
+               report_minimizer_data, minimizer_table, minimizer_data, host_taxids, keep_taxids, dust_reads=False,
+               host_intervals=None) -> "_lib.nh_stats":
     """run() and Engine.run(): the entry of the family `prefix` (nh_run / nh_run_engine, behind the arguments `lead`: none / the
-    handle) that the options ask for -- the first of dust, host, mdata, taxa, rstats, minq, ex, mask, split, none that has one -- and
+    handle) that the options ask for -- the first of intervals, dust, host, mdata, taxa, rstats, minq, ex, mask, split, none that has one -- and
     what it hands back, on the stats.  nodes(): the nodes of the taxonomy, asked only where minimizer data wants a list."""
     fn = lambda suffix: getattr(_lib.lib(), prefix + suffix)
     s = _lib.nh_stats()
     head = tuple(lead) + (C.byref(a),)
     want_md = report_minimizer_data or minimizer_table is not None or minimizer_data is not None
-    if dust_reads or host_taxids or keep_taxids or want_md or taxon_outs or read_stats is not None or min_base_quality:
+    if host_intervals is not None or dust_reads or host_taxids or keep_taxids or want_md or taxon_outs or read_stats is not None or min_base_quality:
         # the entries that take nh_run_minq's list and, each, one thing more: every one gets the list as far as its own last argument
         x = _extras_or_none(mask, human_out1, human_out2, calls, human_ids)
         rs = _read_stats(read_stats) if read_stats is not None else None
@@ -126,10 +134,12 @@ def _run_entry(prefix, lead, nodes, a, human_out1, human_out2, mask, calls, huma
         md = _minimizer_data(report_minimizer_data, minimizer_table, minimizer_data, nodes()) if want_md else None
         hf = _host_filter(host_taxids, keep_taxids) if host_taxids or keep_taxids else None
         rd = _lib.nh_read_dust(C.sizeof(_lib.nh_read_dust), 1, 0) if dust_reads else None
+        hi = (_lib.nh_host_intervals(C.sizeof(_lib.nh_host_intervals), 0, os.fsencode(host_intervals), 0, 0, 0)
+              if host_intervals is not None else None)
         tail = [x, _minq(min_base_quality), _path_or_none(rs.path) if rs else None, C.byref(rs.raw) if rs else None,
                 t if len(t) else None, len(t), C.byref(md) if md is not None else None, C.byref(hf) if hf is not None else None,
-                C.byref(rd) if rd is not None else None]
-        suffix, n = (("_dust", 9) if rd is not None else ("_host", 8) if hf is not None else ("_mdata", 7) if want_md else ("_taxa", 6) if taxon_outs else
+                C.byref(rd) if rd is not None else None, C.byref(hi) if hi is not None else None]
+        suffix, n = (("_intervals", 10) if hi is not None else ("_dust", 9) if rd is not None else ("_host", 8) if hf is not None else ("_mdata", 7) if want_md else ("_taxa", 6) if taxon_outs else
                      ("_rstats", 4) if rs is not None else ("_minq", 2))
         _check(fn(suffix)(*head, *tail[:n], C.byref(s)))
         if md is not None:
@@ -140,6 +150,8 @@ def _run_entry(prefix, lead, nodes, a, human_out1, human_out2, mask, calls, huma
             s.host_fragments, s.spared_fragments = int(hf.host_fragments), int(hf.spared_fragments)
         if rd is not None:
             s.dust_masked_bases = int(rd.masked_bases)
+        if hi is not None:
+            s.interval_fragments, s.intervals, s.covered_bases = int(hi.fragments), int(hi.intervals), int(hi.covered_bases)
     elif calls is not None or human_ids is not None:
         x = _extras(mask, human_out1, human_out2, calls, human_ids)
         _check(fn("_ex")(*head, C.byref(x), C.byref(s)))
@@ -613,6 +625,25 @@ class Engine:
         _check(self._L.nh_dust_reads_device(self._h, d_text or None, int(text_len), d_seq_starts or None, d_seq_lens or None, int(n_seq),
                                             d_out or None, d_masked or None, stream or None))
 
+    def host_cover_device(self, d_text: int, text_len: int, d_seq_starts: int, d_seq_lens: int, n_seq: int, d_cover: int,
+                          d_host_of: int = 0, n_nodes: int = 0, stream: int = 0):
+        """--host-intervals' mark pass behind classify_records_device (nh_host_cover_device): d_cover, ceil(text_len / 32) uint32
+        zeroed by the caller, gets a bit set for every byte of d_text (4-byte aligned) that a host k-mer of the sequences
+        d_text[start, +len) covers; a k-mer is host when its minimizer is found with a non-zero value v and -- d_host_of given,
+        n_nodes bytes -- d_host_of[v] is not 0.  A word without a new bit is not written.  A sequence that leaves the text is
+        skipped and fails the engine's next blocking call.  Waits for `stream`."""
+        _check(self._L.nh_host_cover_device(self._h, d_text or None, int(text_len), d_seq_starts or None, d_seq_lens or None, int(n_seq),
+                                            d_host_of or None, int(n_nodes), d_cover or None, stream or None))
+
+    def cover_intervals_device(self, d_cover: int, text_len: int, d_seq_starts: int, d_seq_lens: int, n_seq: int, d_intervals: int,
+                               cap_records: int, d_total: int, d_error_bits: int, stream: int = 0):
+        """host_cover_device's bitmap into records (nh_cover_intervals_device): d_intervals receives {uint32 seq, start, end} for
+        every maximal run of set bits inside a sequence, in the order of the sequence table, then by start; d_total (uint64) their
+        number.  More than cap_records: bit 2048 in d_error_bits (int32), total 0, nothing written; a sequence outside the text:
+        bit 1024 there and no record.  Waits for `stream`."""
+        _check(self._L.nh_cover_intervals_device(self._h, d_cover or None, int(text_len), d_seq_starts or None, d_seq_lens or None, int(n_seq),
+                                                 d_intervals or None, int(cap_records), d_total or None, d_error_bits or None, stream or None))
+
     def bam_to_fastq_device(self, d_bam: int, bam_len: int, d_table: int, n_records: int, d_text: int, text_cap: int, text_len: int,
                             d_error_bits: int, stream: int = 0):
         """The BAM reader's kernel alone (nh_bam_to_fastq_device): the records of d_bam (bam_len bytes, 4-byte aligned) that
@@ -688,12 +719,13 @@ class Engine:
             confidence: float = 0.0, threads: int = 1, keep_human: bool = False, out_codec: int = 0,
             codec_threads: int = 0, human_out1=None, human_out2=None, mask: bool = False, calls=None,
             human_ids=None, min_base_quality: int = 0, read_stats=None, taxon_outs=None, report_minimizer_data: bool = False,
-            minimizer_table=None, minimizer_data=None, host_taxids=None, keep_taxids=None, dust_reads: bool = False) -> _lib.nh_stats:
+            minimizer_table=None, minimizer_data=None, host_taxids=None, keep_taxids=None, dust_reads: bool = False,
+            host_intervals=None) -> _lib.nh_stats:
         """nh_run_engine; with human_out1 (and, paired, human_out2): nh_run_engine_split; mask: nh_run_engine_mask; with
         calls / human_ids: nh_run_engine_ex; with min_base_quality: nh_run_engine_minq; with read_stats:
         nh_run_engine_rstats; with taxon_outs: nh_run_engine_taxa; with report_minimizer_data / minimizer_table / minimizer_data:
-        nh_run_engine_mdata; with host_taxids / keep_taxids: nh_run_engine_host; with dust_reads: nh_run_engine_dust -- as run()
-        above."""
+        nh_run_engine_mdata; with host_taxids / keep_taxids: nh_run_engine_host; with dust_reads: nh_run_engine_dust; with host_intervals:
+        nh_run_engine_intervals -- as run() above."""
         a = _lib.nh_run_args()
         a.db_dir = None
         a.in1 = os.fsencode(in1)
@@ -711,4 +743,4 @@ class Engine:
         a.codec_threads = int(codec_threads)
         return _run_entry("nh_run_engine", (self._h,), lambda: self.info.node_count, a, human_out1, human_out2, mask, calls, human_ids,
                           min_base_quality, read_stats, taxon_outs, report_minimizer_data, minimizer_table, minimizer_data, host_taxids,
-                          keep_taxids, dust_reads)
+                          keep_taxids, dust_reads, host_intervals)

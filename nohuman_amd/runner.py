@@ -102,7 +102,8 @@ class CommandRunner:
         opts = {"threads": 1, "db": None, "output": None, "confidence": 0.0, "report": None,
                 "paired": False, "classified_out": None, "unclassified_out": None, "inputs": [],
                 "calls": None, "human_ids": None, "minimum_base_quality": 0, "read_stats": None,
-                "report_minimizer_data": False, "minimizer_table": None, "host_taxids": [], "keep_taxids": []}
+                "report_minimizer_data": False, "minimizer_table": None, "host_taxids": [], "keep_taxids": [],
+                "host_intervals": None}
         it = iter(args)
         for a in it:
             if a == "--threads":
@@ -136,6 +137,8 @@ class CommandRunner:
                 opts["report_minimizer_data"] = True
             elif a == "--minimizer-table":  # (the engine's own: nohuman --minimizer-table)
                 opts["minimizer_table"] = next(it)
+            elif a == "--host-intervals":  # (the engine's own: nohuman --host-intervals)
+                opts["host_intervals"] = next(it)
             elif a in ("--host-taxid", "--keep-taxid"):  # (the engine's own: nohuman --host-taxid / --keep-taxid, repeatable)
                 v = next(it)
                 if not (v.isascii() and v.isdigit() and 0 < int(v) < 2 ** 64):
@@ -223,9 +226,20 @@ class CommandRunner:
                 md.struct_size = C.sizeof(_lib.nh_minimizer_data)
                 md.in_report = int(o["report_minimizer_data"])
                 md.table = os.fsencode(o["minimizer_table"]) if o["minimizer_table"] is not None else None
+            hf = None
             if o["host_taxids"] or o["keep_taxids"]:
                 from .engine import _host_filter
                 hf = _host_filter(o["host_taxids"], o["keep_taxids"])
+            if o["host_intervals"] is not None:
+                hi = _lib.nh_host_intervals(C.sizeof(_lib.nh_host_intervals), 0, os.fsencode(o["host_intervals"]), 0, 0, 0)
+                rc = L.nh_run_intervals(C.byref(a), C.byref(x) if x is not None else None, minq, rstats, None, None, 0,
+                                        C.byref(md) if md is not None else None, C.byref(hf) if hf is not None else None, None,
+                                        C.byref(hi), C.byref(s))
+                if rc == 0:
+                    s.interval_fragments, s.intervals, s.covered_bases = int(hi.fragments), int(hi.intervals), int(hi.covered_bases)
+                    if hf is not None:
+                        s.host_fragments, s.spared_fragments = int(hf.host_fragments), int(hf.spared_fragments)
+            elif hf is not None:
                 rc = L.nh_run_host(C.byref(a), C.byref(x) if x is not None else None, minq, rstats, None, None, 0,
                                    C.byref(md) if md is not None else None, C.byref(hf), C.byref(s))
                 if rc == 0:
