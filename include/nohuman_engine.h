@@ -810,6 +810,41 @@ int nh_extend_db(const nh_build_args *b, const nh_extend_args *x, nh_build_stats
 int nh_extend_check(const nh_build_args *b, const nh_extend_args *x, nh_build_stats *bs, nh_extend_stats *xs);
 
 /*
+ * A build that leaves out the minimizers other sequences carry too (--build-db OUT --exclude FILE; nh_build.hip):
+ * with H the distinct minimizers of the host inputs of `b` (of the masked sequences where mask_low_complexity is set) and X those of
+ * the files of `x` -- read by the same parser, plain or gzip, FASTA or FASTQ, any number of records, scanned under the same
+ * ambiguity rule and never masked -- the database written is the one nh_build_db would make of a host whose minimizer set is
+ * H \ X.  Nothing of the exclusion input is stored, so it may be of any size, and the result is an ordinary database that needs no
+ * flag where it is used.  Exclusion works on the 62-bit minimizers; the table keeps 30-bit keys (fewer with many taxa), so a
+ * look-up of an excluded minimizer still finds a kept one of the same key on its probe path, as in any kraken2 table.
+ * The counting pass runs even where b->capacity is given (the exclusion pass flags what it finds in that pass's set; a given
+ * capacity is then used as it is, NH_ECAPACITY as ever), bs->distinct_minimizers is |H|, bs->capacity is
+ * ceil(|H \ X| / load_factor) unless given, xs->excluded_minimizers is |H and X|, exact whatever the order, batching or repetition
+ * of the exclusion input, and kept_minimizers = distinct_minimizers - excluded_minimizers.  With a taxa_file H is the union over
+ * the taxa: a minimizer in X is stored under no taxon.  x == NULL or x->n_fasta == 0 is nh_build_db(b, bs), to the byte.
+ * NH_EINVAL before any device is touched, nothing created: what nh_build_db refuses; a struct_size below nh_exclude_args' or
+ * nh_exclude_stats'; a NULL path; an exclusion file that is one of out_dir's three files, that is also a host input or a FASTA of
+ * the manifest (by real path), or that is given twice.  NH_EIO, out_dir as it was: an exclusion file that cannot be read or
+ * parsed (the message names it).  NH_EDB, nothing written: H \ X is empty.  Not available to nh_extend_db, which has no counting set.
+ */
+typedef struct {
+    uint32_t struct_size;      /* sizeof(nh_exclude_args) of the caller */
+    uint32_t n_fasta;
+    const char *const *fasta;  /* the exclusion files */
+} nh_exclude_args;
+typedef struct {
+    uint32_t struct_size, reserved;  /* struct_size: sizeof(nh_exclude_stats) of the caller */
+    uint64_t sequences, bases, kmers, ambiguous_kmers; /* of the exclusion input */
+    uint64_t lookups;                /* run-start minimizers of the exclusion input looked up in the set */
+    uint64_t excluded_minimizers, kept_minimizers;
+    double seconds_read, seconds_exclude; /* reading the exclusion files; the pass on the device (copies, kernels, waits) */
+} nh_exclude_stats;
+int nh_build_db_exclude(const nh_build_args *b, const nh_exclude_args *x, nh_build_stats *bs, nh_exclude_stats *xs);
+/* Every check nh_build_db_exclude makes before it touches a device: the same codes and messages, nothing created.  With x == NULL
+ * or x->n_fasta == 0 it is nh_build_check(b, bs). */
+int nh_exclude_check(const nh_build_args *b, const nh_exclude_args *x, nh_build_stats *bs, nh_exclude_stats *xs);
+
+/*
  * Low-complexity masking of a host buffer in place, by the kernel and the launch code the builder uses (nh_dust.hip): symmetric
  * DUST (Morgulis et al. 2006) at dustmasker's defaults, window 64 bases and score threshold 2.0, neither an option.  Each segment
  * [seg_start[i], +seg_len[i]) of text is one sequence: it is split into maximal runs of ACGTacgt (case carries no meaning; any

@@ -159,6 +159,17 @@ class nh_extend_stats(C.Structure):
                 ("shadowed_cells", C.c_uint64), ("load", C.c_double), ("seconds_load", C.c_double), ("seconds_rekey", C.c_double)]
 
 
+class nh_exclude_args(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_fasta", C.c_uint32), ("fasta", C.POINTER(C.c_char_p))]
+
+
+class nh_exclude_stats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("sequences", C.c_uint64), ("bases", C.c_uint64),
+                ("kmers", C.c_uint64), ("ambiguous_kmers", C.c_uint64), ("lookups", C.c_uint64),
+                ("excluded_minimizers", C.c_uint64), ("kept_minimizers", C.c_uint64), ("seconds_read", C.c_double),
+                ("seconds_exclude", C.c_double)]
+
+
 class nh_bam_info(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("records", C.c_uint64), ("reads", C.c_uint64),
                 ("bases", C.c_uint64), ("skipped_secondary", C.c_uint64), ("skipped_empty", C.c_uint64),
@@ -268,6 +279,10 @@ SYMBOLS = {
                                C.POINTER(nh_extend_stats)]),
     "nh_extend_check": (C.c_int, [C.POINTER(nh_build_args), C.POINTER(nh_extend_args), C.POINTER(nh_build_stats),
                                   C.POINTER(nh_extend_stats)]),
+    "nh_build_db_exclude": (C.c_int, [C.POINTER(nh_build_args), C.POINTER(nh_exclude_args), C.POINTER(nh_build_stats),
+                                      C.POINTER(nh_exclude_stats)]),
+    "nh_exclude_check": (C.c_int, [C.POINTER(nh_build_args), C.POINTER(nh_exclude_args), C.POINTER(nh_build_stats),
+                                   C.POINTER(nh_exclude_stats)]),
     "nh_dust_mask": (C.c_int, [C.c_int32, _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint64,
                                C.POINTER(C.c_uint64)]),
     "nh_allreduce_counters": (C.c_int, [C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_uint64), C.c_char_p,

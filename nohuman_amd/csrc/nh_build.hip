@@ -40,6 +40,15 @@
 // Extension (nh_extend_db; nh_extend.hip): the table is not zeroed but loaded from the base database's hash.k2d and
 // re-keyed in place for the merged taxonomy; INSERT then runs as for several taxa (MULTI even for one added taxon: it merges with
 // values of the base), there is no COUNT, and the capacity is the base's.
+//
+// Exclusion (nh_build_db_exclude): the host's minimizers that a set of other sequences also carries are left out.
+// The set of COUNT stays on the device (COUNT runs even where `capacity` is given), then a third pass, EXCLUDE, streams the
+// exclusion sequences through the same batches, pieces and scanner (never masked) and looks every run-start minimizer up in the
+// set, find-only: a key that is there gets bit 63 of its slot set (keys are below 2^62 + 1) by atomicOr, and the lane that saw
+// the bit clear counts it, so the count is |H and X| whatever the order, the batches or the repeats of the exclusion input; a miss
+// writes nothing.  INSERT then runs as k_build_pieces<false, MULTI, true>: it finds each minimizer's slot again and skips a
+// flagged one.  The capacity comes from what is kept.  Nothing of the exclusion input is stored and the set is not larger
+// for it.  A build without an exclusion list launches the kernels it always did (FILTER = false) and frees the set before INSERT.
 #include <errno.h>
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -70,9 +79,9 @@ namespace {
 
 // second kernel argument of k_build_pieces (the first is the classifier's KArgs: scan_tile reads the geometry from it)
 struct BuildDev {
-    unsigned long long *set;       // COUNT: slots of the key set
+    unsigned long long *set;       // COUNT, EXCLUDE, INSERT with FILTER: slots of the key set
     uint64_t set_cap, set_magic;   // slots, floor((2^64 - 1) / slots)
-    unsigned long long *counters;  // [0] slots / cells claimed, [1] k-mers that are not ambiguous
+    unsigned long long *counters;  // [0] slots / cells claimed (EXCLUDE: look-ups), [1] k-mers that are not ambiguous, [7] EXCLUDE: slots flagged
     int *full;                     // raised by a lane whose probe saw every slot / cell
     uint32_t value, pad;           // INSERT: the value field of every cell (one taxon)
     // INSERT of several taxa (MULTI)
@@ -81,11 +90,34 @@ struct BuildDev {
 };
 
 constexpr uint32_t FULL_POLL = 1023;  // a probing lane looks at `full` every 1024 cells
+constexpr unsigned long long SET_EXCLUDED = 1ull << 63;  // a slot of the set whose minimizer the exclusion input carries too (a key is below 2^63)
+
+// The slot of minimizer mz in the set, find-only: plain loads from its home on, the index wrapping at the set's end, until an empty
+// slot or the key (whatever its flag); at most `cap` slots are looked at.  -> the slot's index and its word in `word`, or `cap`.
+// Only for a set that no longer grows: slots change by their flag alone.
+__device__ __forceinline__ uint64_t set_find(const unsigned long long *set, const uint64_t cap, const uint64_t magic, const uint64_t mz,
+                                             unsigned long long &word) {
+    const unsigned long long key = mz + 1;
+    uint64_t idx = mod_capacity(fmix64(mz), cap, magic);
+    for (uint64_t tries = 0; tries < cap; tries++) {
+        const unsigned long long cur = set[idx];
+        if (cur == 0) break;
+        if ((cur & ~SET_EXCLUDED) == key) {
+            word = cur;
+            return idx;
+        }
+        idx++;
+        if (idx >= cap) idx = 0;
+    }
+    word = 0;
+    return cap;
+}
 
 // One wave per piece: sequence text[seq_off[p], +seq_len[p]) (starts and lengths, so that pieces may overlap).
 // MULTI (INSERT only): the value of a piece is its taxon's, and a cell that already holds the key under another value becomes the
 // lowest common ancestor of the two.
-template <bool COUNT, bool MULTI>
+// FILTER (INSERT only, builds with an exclusion list): a minimizer whose slot of the set is flagged is not inserted.
+template <bool COUNT, bool MULTI, bool FILTER = false>
 __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_build_pieces(const KArgs args_by_kernarg_pointer, const BuildDev b) {
     KArgsP ap = (KArgsP)__builtin_amdgcn_kernarg_segment_ptr();
     typedef WaveLdsT<true, 1, QCAP_GENERIC> WL;
@@ -144,6 +176,11 @@ __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_build_pieces(const K
             wave_sync();
             for (uint32_t r = lane; r < nruns && !gave_up; r += 64) {
                 const uint64_t mz = S.q[0][r];
+                if (FILTER) {  // (every minimizer of the host is in the set: COUNT put it there)
+                    unsigned long long word;
+                    (void)set_find(b.set, b.set_cap, b.set_magic, mz, word);
+                    if (word & SET_EXCLUDED) continue;
+                }
                 if (MULTI) inserts++;
                 const uint64_t hc = fmix64(mz);
                 uint64_t idx = mod_capacity(hc, cap, magic);
@@ -240,6 +277,78 @@ __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_build_pieces(const K
     }
 }
 
+// EXCLUDE: the pieces of the exclusion text, scanned as COUNT scans the host's (the same bounds: a piece that leaves the text is
+// skipped, text loads are clamped to the readable tail); every run-start minimizer is looked up in the finished set and flagged
+// where it is found.  A miss -- nearly every minimizer of another genome -- writes nothing.
+__global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_exclude_pieces(const KArgs args_by_kernarg_pointer, const BuildDev b) {
+    KArgsP ap = (KArgsP)__builtin_amdgcn_kernarg_segment_ptr();
+    typedef WaveLdsT<true, 1, QCAP_GENERIC> WL;
+    __shared__ WL lds_all[WAVES_PER_BLOCK];
+    const int lane = threadIdx.x & 63;
+    const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    WL &S = lds_all[wib];
+    init_wave_lds<true>(S, lane);
+    const uint32_t TQ = TL - 4u;  // k-mers of a full tile
+    const uint64_t n_piece = ap->n_frag;
+    const uint64_t *const start = ap->seq_off;
+    const uint32_t *const len = ap->seq_len;
+    const uint64_t text_len = ap->bases_end;
+    const uint64_t last_dw = (text_len + 4) >> 2;  // the text is readable for 8 bytes behind its end
+    const uint32_t *const text = reinterpret_cast<const uint32_t *>(ap->bases);
+    const uint32_t pl = (uint32_t)lane < PREF_LANES ? (uint32_t)lane : PREF_LANES - 1;
+    const uint64_t cap = b.set_cap, magic = b.set_magic;
+    uint64_t prof[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    uint64_t tprev = 0;
+    unsigned long long flagged = 0, lookups = 0;  // per lane
+    unsigned long long clean = 0;                 // wave-uniform
+    const uint64_t n_waves = (uint64_t)gridDim.x * WAVES_PER_BLOCK;
+    for (uint64_t p = (uint64_t)blockIdx.x * WAVES_PER_BLOCK + wib; p < n_piece; p += n_waves) {
+        const uint64_t o0 = start[p];
+        const uint32_t n = len[p];
+        if (n < 35u || o0 > text_len || text_len - o0 < n) continue;  // (wave-uniform; the host makes no such piece)
+        const uint32_t nk = n - 34u;
+        uint64_t carry_min = NH_FULL;
+        uint32_t w;
+        {
+            uint64_t dw = (o0 >> 2) + pl;
+            dw = dw < last_dw ? dw : last_dw;
+            w = text[dw];
+        }
+        for (uint32_t q0 = 0; q0 < nk; q0 += TQ) {
+            const uint64_t g0 = o0 + q0;
+            const uint32_t nl_left = (n - 31u + 1) - q0;
+            const uint32_t nlt = nl_left < (uint32_t)TL ? nl_left : (uint32_t)TL;
+            const uint32_t nq_left = nk - q0;
+            const uint32_t nqt = nq_left < TQ ? nq_left : TQ;
+            // the next tile's dword is loaded while this one is scanned
+            const bool more = nq_left > TQ;
+            uint64_t dwn = ((g0 + TQ) >> 2) + pl;
+            dwn = dwn < last_dw ? dwn : last_dw;
+            uint32_t ps, w_next = 0;
+            int last_lane;
+            const uint32_t nruns = scan_tile<true, false>(ap, S, lane, w, (uint32_t)g0 & 3u, nlt, nqt, 0u, 0u, carry_min, ps, last_lane,
+                                                          text + dwn, more, w_next, prof, tprev);
+            clean += (unsigned long long)(__popcll(__ballot(ps & 1u)) + __popcll(__ballot(ps & 2u)));
+            wave_sync();
+            for (uint32_t r = lane; r < nruns; r += 64) {
+                unsigned long long word;
+                const uint64_t idx = set_find(b.set, cap, magic, S.q[0][r], word);
+                lookups++;
+                // (several lanes may find one slot unflagged: the one whose atomicOr saw it so counts it)
+                if (idx < cap && !(word & SET_EXCLUDED) && !(atomicOr(&b.set[idx], SET_EXCLUDED) & SET_EXCLUDED)) flagged++;
+            }
+            wave_sync();
+            w = w_next;
+        }
+    }
+    for (int d = 32; d >= 1; d >>= 1) flagged += __shfl_xor(flagged, d, 64), lookups += __shfl_xor(lookups, d, 64);
+    if (lane == 0) {
+        if (flagged) atomicAdd(&b.counters[7], flagged);
+        if (lookups) atomicAdd(&b.counters[0], lookups);
+        if (clean) atomicAdd(&b.counters[1], clean);
+    }
+}
+
 // Cells per node of the finished table (several taxa): bins in LDS, one global atomic per non-zero bin and workgroup.  No occupied
 // cell holds the value 0, so bin i counts the value i + 1: VALUE_BINS bins hold every node of the largest taxonomy.  The table is
 // read four cells a lane; it is allocated, and zero, through the next multiple of four behind `cap`.
@@ -299,7 +408,7 @@ constexpr uint64_t DEFAULT_BATCH_BYTES = 128ull << 20;
 constexpr uint64_t TOGGLE_MASK = 0xe37e28c4271b5a2dull;
 constexpr uint64_t SPACED_MASK = 0x3FFFFFFFF3333333ull;  // "1" x 17 + "01" x 7, two bits a base
 constexpr uint32_t TAXON_NODE = 2;                       // one taxon: three nodes, 0 the null sentinel, 1 root, 2 the taxon
-constexpr int N_COUNTERS = 7;  // claimed, clean, `full` (an int), masked bases, then of several taxa: LCA merges, values replaced, insertions
+constexpr int N_COUNTERS = 8;  // claimed, clean, `full` (an int), masked bases, then of several taxa: LCA merges, values replaced, insertions; EXCLUDE: slots flagged
 const char *const DB_FILES[3] = {"hash.k2d", "opts.k2d", "taxo.k2d"};
 
 double since(std::chrono::steady_clock::time_point t0) {
@@ -355,6 +464,10 @@ struct Builder {
     uint64_t capacity = 0;
     // results
     bool counting = false;
+    bool excluding = false;  // the EXCLUDE pass: the text is the exclusion input's, `claimed` its look-ups
+    bool filter = false;     // INSERT skips what EXCLUDE flagged in the set
+    unsigned long long flagged = 0;
+    uint64_t x_sequences = 0, x_bases = 0, x_kmers = 0;  // of the exclusion input
     unsigned long long claimed = 0, clean = 0;
     bool full = false;
     double t_read = 0, t_gpu = 0;
@@ -410,7 +523,7 @@ struct Builder {
     int reset_counters() {
         BUILD_TRY(hipMemsetAsync(d_counters, 0, N_COUNTERS * sizeof(unsigned long long), stream));
         BUILD_TRY(hipStreamSynchronize(stream));
-        claimed = clean = masked = merges = swaps = inserts = 0;
+        claimed = clean = masked = merges = swaps = inserts = flagged = 0;
         full = false;
         return NH_OK;
     }
@@ -496,7 +609,7 @@ struct Builder {
         if (n_piece) {
             BUILD_TRY(hipMemcpyAsync(d_starts, starts.data(), n_piece * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
             BUILD_TRY(hipMemcpyAsync(d_lens, lens.data(), n_piece * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-            if (multi && !counting) BUILD_TRY(hipMemcpyAsync(d_values, values.data(), n_piece * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+            if (multi && !counting && !excluding) BUILD_TRY(hipMemcpyAsync(d_values, values.data(), n_piece * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
         }
         const bool masking = !tiles.empty();
         if (masking) {
@@ -519,7 +632,7 @@ struct Builder {
         d.table = d_table;
         d.n_copies = 1;
         d.copy_shift = 5;
-        d.capacity = counting ? 1 : capacity;
+        d.capacity = counting || excluding ? 1 : capacity;
         d.cap_magic = ~0ull / d.capacity;
         d.node_count = node_count;
         d.value_bits = vbits;
@@ -540,7 +653,7 @@ struct Builder {
         BuildDev b;
         memset(&b, 0, sizeof b);
         b.set = d_set;
-        b.set_cap = counting ? set_cap : 1;
+        b.set_cap = counting || excluding || filter ? set_cap : 1;
         b.set_magic = ~0ull / b.set_cap;
         b.counters = d_counters;
         b.full = d_full();
@@ -554,13 +667,19 @@ struct Builder {
             ;  // (masking: a batch of sequences too short for a k-mer)
         else if (counting)
             hipLaunchKernelGGL((k_build_pieces<true, false>), dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, stream, ka, b);
+        else if (excluding)
+            hipLaunchKernelGGL(k_exclude_pieces, dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, stream, ka, b);
+        else if (filter && multi)
+            hipLaunchKernelGGL((k_build_pieces<false, true, true>), dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, stream, ka, b);
+        else if (filter)
+            hipLaunchKernelGGL((k_build_pieces<false, false, true>), dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, stream, ka, b);
         else if (multi)
             hipLaunchKernelGGL((k_build_pieces<false, true>), dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, stream, ka, b);
         else
             hipLaunchKernelGGL((k_build_pieces<false, false>), dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, stream, ka, b);
         BUILD_TRY(hipGetLastError());
         BUILD_TRY(hipEventRecord(ev[1], stream));
-        unsigned long long out[N_COUNTERS] = {0, 0, 0, 0, 0, 0, 0};
+        unsigned long long out[N_COUNTERS] = {0, 0, 0, 0, 0, 0, 0, 0};
         BUILD_TRY(hipMemcpyAsync(out, d_counters, sizeof out, hipMemcpyDeviceToHost, stream));
         BUILD_TRY(hipStreamSynchronize(stream));
         float ms = 0;
@@ -576,6 +695,7 @@ struct Builder {
         merges = out[4];
         swaps = out[5];
         inserts = out[6];
+        flagged = out[7];
         int f;
         memcpy(&f, &out[2], sizeof f);
         full = f != 0;
@@ -679,7 +799,11 @@ struct Builder {
                 if (got < 0) return set_error(NH_EIO, "%s: %s", in.path.c_str(), err.c_str());
                 if (got == 0) break;
                 t_read += since(t0);
-                if (totals) {
+                if (excluding) {
+                    x_sequences++;
+                    x_bases += rec.seq.size();
+                    if (rec.seq.size() >= 35) x_kmers += rec.seq.size() - 34;
+                } else if (totals) {
                     sequences++;
                     bases += rec.seq.size();
                     pn.sequences++;
@@ -934,14 +1058,100 @@ int build_check(const nh_build_args *a, nh_build_stats *stats) {
     return NH_OK;
 }
 
-int build_db(const nh_build_args *a, nh_build_stats *stats) {
+// ---- nh_build_db_exclude: the checks of the exclusion list that need no device -----------------------------------
+// (an exclusion list is in force only where x is there and names a file: without one the call is nh_build_db)
+bool excluding_with(const nh_exclude_args *x) { return x && x->struct_size >= sizeof(nh_exclude_args) && x->n_fasta != 0; }
+
+// the struct sizes: looked at even where the list is empty
+int check_exclude_layout(const nh_exclude_args *x, const nh_exclude_stats *xs) {
+    if (x && x->struct_size < sizeof(nh_exclude_args))
+        return set_error(NH_EINVAL, "nh_build_db_exclude: struct_size %u is smaller than nh_exclude_args (%u)", x->struct_size, (unsigned)sizeof(nh_exclude_args));
+    if (xs && xs->struct_size < sizeof(nh_exclude_stats))
+        return set_error(NH_EINVAL, "nh_build_db_exclude: struct_size %u is smaller than nh_exclude_stats (%u)", xs->struct_size, (unsigned)sizeof(nh_exclude_stats));
+    return NH_OK;
+}
+
+// the files of the list against out_dir, the host's inputs (P.inputs: plan_build has passed) and each other -> `files`
+int plan_exclude(const nh_build_args *a, const nh_exclude_args *x, const BuildPlan &P, std::vector<BuildInput> &files) {
+    if (!x->fasta) return set_error(NH_EINVAL, "nh_build_db_exclude: n_fasta is %u but fasta is null", x->n_fasta);
+    for (uint32_t i = 0; i < x->n_fasta; i++)
+        if (!x->fasta[i]) return set_error(NH_EINVAL, "nh_build_db_exclude: exclusion file %u is a null path", i);
+    const std::string dir = a->out_dir;
+    // (a file that does not exist has no real path: it is compared by its name and fails as unreadable later)
+    auto id_of = [](const std::string &p) {
+        const std::string r = real_of(p);
+        return r.empty() ? p : r;
+    };
+    std::vector<std::string> host;
+    for (const BuildInput &in : P.inputs) host.push_back(id_of(in.path));
+    std::vector<std::string> seen;
+    for (uint32_t i = 0; i < x->n_fasta; i++) {
+        const char *f = x->fasta[i];
+        if (input_is_output(f, dir))
+            return set_error(NH_EINVAL, "nh_build_db_exclude: the exclusion file %s is a database file of the output directory %s", f, dir.c_str());
+        const std::string id = id_of(f);
+        for (size_t h = 0; h < host.size(); h++)
+            if (host[h] == id)
+                return set_error(NH_EINVAL, "nh_build_db_exclude: the exclusion file %s is also an input of the build (%s): every minimizer would be "
+                                 "excluded", f, P.inputs[h].path.c_str());
+        for (const std::string &s : seen)
+            if (s == id) return set_error(NH_EINVAL, "nh_build_db_exclude: the exclusion file %s is given twice", f);
+        seen.push_back(id);
+        files.push_back({f, 0});
+    }
+    return NH_OK;
+}
+
+void give_exclude_stats(nh_exclude_stats *xs, const nh_exclude_stats &v) {
+    if (!xs) return;
+    const uint32_t size = xs->struct_size;
+    *xs = v;
+    xs->struct_size = size, xs->reserved = 0;
+}
+
+int exclude_check(const nh_build_args *a, const nh_exclude_args *x, nh_build_stats *stats, nh_exclude_stats *xs) {
+    int rc = check_exclude_layout(x, xs);
+    if (rc) return rc;
+    if (!excluding_with(x)) return build_check(a, stats);
+    BuildPlan P;
+    layout_of(a, P);
+    if (stats) memset(stats, 0, P.stats_size);
+    rc = plan_build(a, P);
+    if (rc) return rc;
+    std::vector<BuildInput> files;
+    rc = plan_exclude(a, x, P, files);
+    if (rc) return rc;
+    std::vector<nh_build_taxon_stats> per_node(P.nodes.size());
+    for (size_t i = 0; i < P.nodes.size(); i++) memset(&per_node[i], 0, sizeof per_node[i]), per_node[i].taxid = P.nodes[i].taxid;
+    give_taxon_stats(a, P, per_node);
+    if (stats && P.v3) stats->taxa = P.nodes.size() - 1;
+    nh_exclude_stats v;
+    memset(&v, 0, sizeof v);
+    give_exclude_stats(xs, v);
+    return NH_OK;
+}
+
+int build_db(const nh_build_args *a, nh_build_stats *stats, const nh_exclude_args *x = nullptr, nh_exclude_stats *xs = nullptr) {
+    int rc = check_exclude_layout(x, xs);
+    if (rc) return rc;
     BuildPlan P;
     layout_of(a, P);
     const size_t stats_size = P.stats_size;
     if (stats) memset(stats, 0, stats_size);
-    int rc = plan_build(a, P);
+    rc = plan_build(a, P);
     if (rc) return rc;
     const double lf = P.lf;
+    std::vector<BuildInput> x_files;  // empty: a build as it ever was
+    if (excluding_with(x)) {
+        rc = plan_exclude(a, x, P, x_files);
+        if (rc) return rc;
+    }
+    const bool excluding = !x_files.empty();
+    // (an exclusion file that is not there should not cost a counting pass over the host first)
+    for (const BuildInput &f : x_files)
+        if (access(f.path.c_str(), R_OK) != 0) return set_error(NH_EIO, "cannot read the exclusion file %s: %s", f.path.c_str(), strerror(errno));
+    nh_exclude_stats xv;
+    memset(&xv, 0, sizeof xv);
 
     rc = check_device(a->device);
     if (rc) return rc;
@@ -973,23 +1183,48 @@ int build_db(const nh_build_args *a, nh_build_stats *stats) {
     memset(&s, 0, sizeof s);
     uint64_t capacity = a->capacity;
     double count_kernel = 0;
-    if (!capacity) {
+    double exclude_kernel = 0;
+    const bool counted = !capacity || excluding;  // (an exclusion needs the set: the counting pass runs whatever the capacity)
+    if (counted) {
         rc = B.pass(P.inputs, true, true);
         if (rc) return rc;
         s.distinct_minimizers = B.claimed;
         s.seconds_count = B.t_gpu;
         count_kernel = B.t_kernel;
         B.t_gpu = B.t_kernel = 0;
-        B.free_set();
+        if (!excluding) B.free_set();
         if (s.distinct_minimizers == 0)
             return set_error(NH_EDB, "the input holds no k-mer to build from: %llu sequences, %llu bases, every sequence shorter than 35 bases or "
                              "ambiguous throughout", (unsigned long long)B.sequences, (unsigned long long)B.bases);
-        capacity = (uint64_t)ceil((double)s.distinct_minimizers / lf);
-        if (capacity >> 33) return set_error(NH_ECAPACITY, "%llu distinct minimizers need a table of 2^33 cells or more", (unsigned long long)s.distinct_minimizers);
+        uint64_t kept = s.distinct_minimizers;
+        if (excluding) {  // EXCLUDE: the exclusion input against the set, never masked
+            const bool mask = B.mask;
+            const double t_read = B.t_read, t_mask = B.t_mask;
+            B.mask = false, B.excluding = true;
+            rc = B.pass(x_files, false, false);
+            B.mask = mask, B.excluding = false;
+            if (rc) return rc;
+            xv.sequences = B.x_sequences, xv.bases = B.x_bases, xv.kmers = B.x_kmers;
+            xv.ambiguous_kmers = B.x_kmers - B.clean;
+            xv.lookups = B.claimed;
+            xv.excluded_minimizers = B.flagged;
+            xv.kept_minimizers = kept = s.distinct_minimizers - B.flagged;
+            xv.seconds_read = B.t_read - t_read;
+            xv.seconds_exclude = B.t_gpu;
+            exclude_kernel = B.t_kernel;
+            B.t_read = t_read, B.t_mask = t_mask, B.t_gpu = B.t_kernel = 0;
+            if (kept == 0)
+                return set_error(NH_EDB, "every minimizer of the input is excluded: all %llu distinct minimizers are also in the exclusion input "
+                                 "(%llu sequences, %llu bases)", (unsigned long long)s.distinct_minimizers, (unsigned long long)xv.sequences,
+                                 (unsigned long long)xv.bases);
+            B.filter = true;
+        }
+        if (!capacity) capacity = (uint64_t)ceil((double)kept / lf);
+        if (capacity >> 33) return set_error(NH_ECAPACITY, "%llu distinct minimizers need a table of 2^33 cells or more", (unsigned long long)kept);
     }
     rc = B.alloc_table(capacity);
     if (rc) return rc;
-    rc = B.pass(P.inputs, false, a->capacity != 0);
+    rc = B.pass(P.inputs, false, !counted);
     if (rc) return rc;
     s.seconds_insert = B.t_gpu;
     s.seconds_read = B.t_read;
@@ -1030,8 +1265,13 @@ int build_db(const nh_build_args *a, nh_build_stats *stats) {
         fprintf(stderr, "[nohuman trace] build taxa: %u nodes, value_bits %u; insertions %llu, of them %llu found their key under another "
                         "value (the LCA path), values replaced %llu; cells per node %.6f s\n", B.node_count - 1, B.vbits, B.inserts, B.merges,
                 B.swaps, B.t_cells);
+    if (getenv("NOHUMAN_TRACE") && excluding)
+        fprintf(stderr, "[nohuman trace] build exclude: %llu k-mers of the exclusion input, %llu look-ups, %llu of %llu distinct minimizers excluded; "
+                        "kernels alone: exclude %.4f s (set of %llu slots)\n", (unsigned long long)xv.kmers, (unsigned long long)xv.lookups,
+                (unsigned long long)xv.excluded_minimizers, (unsigned long long)s.distinct_minimizers, exclude_kernel, (unsigned long long)B.set_cap);
     give_taxon_stats(a, P, B.per_node);
     if (stats) memcpy(stats, &s, stats_size);
+    give_exclude_stats(xs, xv);
     return NH_OK;
 }
 
@@ -1278,6 +1518,26 @@ extern "C" int nh_build_db(const nh_build_args *args, nh_build_stats *stats) {
         return nh::set_error(NH_EOOM, "nh_build_db: out of host memory");
     } catch (const std::exception &e) {
         return nh::set_error(NH_EIO, "nh_build_db: %s", e.what());
+    }
+}
+
+extern "C" int nh_exclude_check(const nh_build_args *b, const nh_exclude_args *x, nh_build_stats *bs, nh_exclude_stats *xs) {
+    try {
+        return nh::exclude_check(b, x, bs, xs);
+    } catch (const std::bad_alloc &) {
+        return nh::set_error(NH_EOOM, "nh_exclude_check: out of host memory");
+    } catch (const std::exception &e) {
+        return nh::set_error(NH_EIO, "nh_exclude_check: %s", e.what());
+    }
+}
+
+extern "C" int nh_build_db_exclude(const nh_build_args *b, const nh_exclude_args *x, nh_build_stats *bs, nh_exclude_stats *xs) {
+    try {
+        return nh::build_db(b, bs, x, xs);
+    } catch (const std::bad_alloc &) {
+        return nh::set_error(NH_EOOM, "nh_build_db_exclude: out of host memory");
+    } catch (const std::exception &e) {
+        return nh::set_error(NH_EIO, "nh_build_db_exclude: %s", e.what());
     }
 }
 

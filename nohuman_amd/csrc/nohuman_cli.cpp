@@ -270,6 +270,7 @@ struct Args {
     bool has_taxa = false, has_taxid = false;
     bool has_build_db = false, has_taxon_name = false, has_build_opt = false, force = false, mask_low_complexity = false;
     std::vector<std::string> reference;
+    std::vector<std::string> exclude;  // --exclude: files whose minimizers --build-db leaves out of the database (nh_build_db_exclude)
     unsigned long long taxid = 0, capacity = 0;
     double load_factor = 0;
     unsigned threads = 1;
@@ -334,6 +335,8 @@ static void usage(FILE *f) {
           "      --extend-db <DIR>        With a database build: add the taxa given to the existing database in DIR (its three .k2d files are enough, not the "
           "genomes it was made from) and write the result to the build's directory; the table keeps its size, a load factor given is the highest load "
           "the result may have [default: 0.95], a fixed number of cells cannot be asked for\n"
+          "      --exclude <FILE>         With a database build from genomes alone: leave out every minimizer that the sequences of FILE (FASTA or FASTQ, plain or "
+          "gzip; bacterial and viral genomes, say) carry too; nothing of FILE is stored; may be given more than once\n"
           "      --load-factor <FLOAT>    Load factor of the hash table for --build-db, in (0, 0.95] [default: 0.7]\n"
           "      --capacity <INT>         Cells of the hash table for --build-db; skips the counting pass [default: distinct minimizers / load factor]\n"
           "      --force                  Let --build-db replace a database that DIR already holds\n"
@@ -469,6 +472,7 @@ static Args parse_args(int argc, char **argv) {
         else if (s == "--build-db") { a.build_db = val(); a.has_build_db = true; }
         else if (s == "--extend-db") { a.extend_db = val(); a.has_extend_db = true; }
         else if (s == "--reference") a.reference.push_back(val());
+        else if (s == "--exclude") a.exclude.push_back(val());
         else if (s == "--taxid" || s == "--capacity") {
             std::string t = val();
             char *end;
@@ -520,13 +524,19 @@ static Args parse_args(int argc, char **argv) {
             if (a.capacity) arg_error("the argument '--extend-db <DIR>' cannot be used with '--capacity <INT>': an extension keeps the capacity of its base");
             if (!exists(a.extend_db)) arg_error("invalid value '%s' for '--extend-db <DIR>': %s does not exist", a.extend_db.c_str(), quoted(a.extend_db).c_str());
         }
+        if (!a.exclude.empty() && a.has_extend_db)
+            arg_error("the argument '--exclude <FILE>' cannot be used with '--extend-db <DIR>': an extension has no counting pass whose set the "
+                      "exclusion could be held against");
         for (const std::string &r : a.reference)
             if (!exists(r)) arg_error("invalid value '%s' for '--reference <FILE>': %s does not exist", r.c_str(), quoted(r).c_str());
+        for (const std::string &r : a.exclude)
+            if (!exists(r)) arg_error("invalid value '%s' for '--exclude <FILE>': %s does not exist", r.c_str(), quoted(r).c_str());
         return a;
     }
     if (a.mask_low_complexity) arg_error("the argument '--mask-low-complexity' needs '--build-db <DIR>': it masks the genome a database is built from, not reads");
     if (!a.reference.empty()) arg_error("the argument '--reference <FILE>' needs '--build-db <DIR>'");
     if (a.has_taxa) arg_error("the argument '--taxa <FILE>' needs '--build-db <DIR>'");
+    if (!a.exclude.empty()) arg_error("the argument '--exclude <FILE>' needs '--build-db <DIR>': it names sequences whose minimizers a database build leaves out");
     if (a.has_extend_db) arg_error("the argument '--extend-db <DIR>' needs '--build-db <DIR>': it names the database that the build adds its taxa to");
     if (a.has_build_opt) arg_error("the arguments '--taxid', '--taxon-name', '--load-factor', '--capacity' and '--force' need '--build-db <DIR>'");
     if (a.input.empty() && !a.check && !a.download && !a.list)
@@ -712,6 +722,15 @@ static void fill_build_args(const Args &args, std::vector<const char *> &refs, n
     if (const char *dv = getenv("NOHUMAN_DEVICES")) ba.device = (int32_t)strtol(dv, nullptr, 10);  // (one device: the first listed)
 }
 
+// --exclude: the list as nh_build_db_exclude takes it (empty: the call is nh_build_db)
+static void fill_exclude_args(const Args &args, std::vector<const char *> &files, nh_exclude_args &xa) {
+    for (const std::string &f : args.exclude) files.push_back(f.c_str());
+    memset(&xa, 0, sizeof xa);
+    xa.struct_size = (uint32_t)sizeof xa;
+    xa.n_fasta = (uint32_t)files.size();
+    xa.fasta = files.empty() ? nullptr : files.data();
+}
+
 int main(int argc, char **argv) {
     Args args = parse_args(argc, argv);
     if (args.has_build_db && args.has_extend_db) {  // the base, the taxa and how they fit together: checked before any device is asked for
@@ -725,6 +744,18 @@ int main(int argc, char **argv) {
         const int rc = nh_extend_check(&ba, &xa, nullptr, nullptr);
         if (rc == NH_EINVAL) arg_error("invalid value '%s' for '--extend-db <DIR>': %s", args.extend_db.c_str(), nh_last_error());
         if (rc != 0) die("Failed to extend the database\n\nCaused by:\n    %s", nh_last_error());
+    } else if (args.has_build_db && !args.exclude.empty()) {  // the exclusion list against the inputs and the output, and the manifest if there is one
+        std::vector<const char *> refs, files;
+        nh_build_args ba;
+        nh_exclude_args xa;
+        fill_build_args(args, refs, ba);
+        fill_exclude_args(args, files, xa);
+        const int rc = nh_exclude_check(&ba, &xa, nullptr, nullptr);
+        if (rc == NH_EINVAL && strstr(nh_last_error(), "nh_build_db_exclude:"))
+            arg_error("invalid value '%s' for '--exclude <FILE>': %s", args.exclude[0].c_str(), nh_last_error());
+        if (rc == NH_EINVAL && args.has_taxa) arg_error("invalid value '%s' for '--taxa <FILE>': %s", args.taxa.c_str(), nh_last_error());
+        if (rc == NH_EINVAL) arg_error("%s", nh_last_error());
+        if (rc != 0) die("Failed to build the database\n\nCaused by:\n    %s", nh_last_error());
     } else if (args.has_build_db && args.has_taxa) {  // what the manifest says wrongly is an argument error too: read before any device is asked for
         std::vector<const char *> refs;
         nh_build_args ba;
@@ -824,7 +855,17 @@ int main(int argc, char **argv) {
         ba.taxon_stats = per_taxon.data();
         ba.taxon_stats_cap = (uint32_t)per_taxon.size();
         nh_build_stats bs;
-        if (nh_build_db(&ba, &bs) != 0) die("Failed to build the database\n\nCaused by:\n    %s", nh_last_error());
+        std::vector<const char *> x_files;
+        nh_exclude_args xa;
+        fill_exclude_args(args, x_files, xa);
+        nh_exclude_stats xs;
+        memset(&xs, 0, sizeof xs);
+        xs.struct_size = (uint32_t)sizeof xs;
+        if (nh_build_db_exclude(&ba, &xa, &bs, &xs) != 0) die("Failed to build the database\n\nCaused by:\n    %s", nh_last_error());
+        if (!args.exclude.empty())
+            INFO("Exclusion: %llu sequences, %llu bases; %llu of %llu distinct minimizers excluded, %llu kept; read %.2f s, exclude %.2f s",
+                 (unsigned long long)xs.sequences, (unsigned long long)xs.bases, (unsigned long long)xs.excluded_minimizers,
+                 (unsigned long long)bs.distinct_minimizers, (unsigned long long)xs.kept_minimizers, xs.seconds_read, xs.seconds_exclude);
         char masked[128] = "";
         if (args.mask_low_complexity)
             snprintf(masked, sizeof masked, "; %llu low-complexity bases masked (%.2f %% of the bases), mask %.2f s", (unsigned long long)bs.masked_bases,

@@ -294,7 +294,7 @@ MAX_TAXA_NODES = 4096  # nodes of a taxa manifest with the root (include/nohuman
 
 def build_db(fasta_paths=None, out_dir=None, *, taxid: int = 0, taxon_name=None, load_factor: float = 0.0, capacity: int = 0,
              piece_kmers: int = 0, device: int = 0, threads: int = 1, force: bool = False,
-             mask_low_complexity: bool = False, taxa=None) -> dict:
+             mask_low_complexity: bool = False, taxa=None, exclude=None) -> dict:
     """nh_build_db: a kraken2 database directory (hash.k2d, opts.k2d, taxo.k2d) built on the GPU from FASTA files (plain or
     gzip, wrapped lines, any number of records; one path or a list).  One taxon (taxid, 0 = 9606; taxon_name), or several:
     taxa is the path of a manifest with a line `taxid <TAB> parent taxid <TAB> name [<TAB> FASTA path]...` per taxon (parent 1
@@ -306,7 +306,17 @@ def build_db(fasta_paths=None, out_dir=None, *, taxid: int = 0, taxon_name=None,
     threshold 2.0 -- what kraken2-build's dustmasker step is for; see dust_mask).  Returns nh_build_stats as a dict
     (sequences, bases, kmers, ambiguous_kmers, distinct_minimizers, capacity, size, seconds_read / _count / _insert / _write,
     masked_bases, seconds_mask, taxa) with taxon_stats, a list of dicts (taxid, sequences, bases, kmers, cells), one a node
-    in internal-id order from the root on; Engine.open(out_dir) and run(out_dir, ...) work on the result."""
+    in internal-id order from the root on; Engine.open(out_dir) and run(out_dir, ...) work on the result.
+    exclude: a path or a list of paths (FASTA or FASTQ, plain or gzip) whose minimizers are left out of the database
+    (nh_build_db_exclude): the table is built from the host's distinct minimizers that none of these sequences carries, nothing
+    of them is stored, the counting pass runs even with a capacity given, and the dict gains exclude_sequences, exclude_bases,
+    exclude_kmers, exclude_ambiguous_kmers, exclude_lookups, excluded_minimizers, kept_minimizers, seconds_exclude_read and
+    seconds_exclude.  None or an empty list is a build without the feature."""
+    if exclude is None:
+        exclude = []
+    if isinstance(exclude, (str, bytes, os.PathLike)):
+        exclude = [exclude]
+    x_paths = [os.fsencode(p) for p in exclude]
     if fasta_paths is None:  # (the library refuses taxa together with fasta_paths, taxid or taxon_name, and neither of them)
         fasta_paths = []
     if isinstance(fasta_paths, (str, bytes, os.PathLike)):
@@ -334,8 +344,23 @@ def build_db(fasta_paths=None, out_dir=None, *, taxid: int = 0, taxon_name=None,
     a.threads = int(threads)
     a.force = int(bool(force))
     s = _lib.nh_build_stats_v3()
-    _check(_lib.lib().nh_build_db(C.byref(a), C.byref(s)))
+    if x_paths:
+        x = _lib.nh_exclude_args()
+        x.struct_size = C.sizeof(_lib.nh_exclude_args)
+        x.n_fasta = len(x_paths)
+        x_arr = (C.c_char_p * len(x_paths))(*x_paths)
+        x.fasta = x_arr
+        xs = _lib.nh_exclude_stats()
+        xs.struct_size = C.sizeof(_lib.nh_exclude_stats)
+        _check(_lib.lib().nh_build_db_exclude(C.byref(a), C.byref(x), C.byref(s), C.byref(xs)))
+    else:
+        _check(_lib.lib().nh_build_db(C.byref(a), C.byref(s)))
     out = {name: getattr(s, name) for name, _ in _lib.nh_build_stats._fields_ + _lib.nh_build_stats_v2._fields_ + _lib.nh_build_stats_v3._fields_}
+    if x_paths:
+        out.update(exclude_sequences=xs.sequences, exclude_bases=xs.bases, exclude_kmers=xs.kmers,
+                   exclude_ambiguous_kmers=xs.ambiguous_kmers, exclude_lookups=xs.lookups,
+                   excluded_minimizers=xs.excluded_minimizers, kept_minimizers=xs.kept_minimizers,
+                   seconds_exclude_read=xs.seconds_read, seconds_exclude=xs.seconds_exclude)
     out["taxon_stats"] = [{name: getattr(per_node[i], name) for name, _ in _lib.nh_build_taxon_stats._fields_}
                           for i in range(min(int(s.taxa), MAX_TAXA_NODES))]
     return out

@@ -103,7 +103,7 @@ class CommandRunner:
                 "paired": False, "classified_out": None, "unclassified_out": None, "inputs": [],
                 "calls": None, "human_ids": None, "minimum_base_quality": 0, "read_stats": None,
                 "report_minimizer_data": False, "minimizer_table": None, "host_taxids": [], "keep_taxids": [],
-                "host_intervals": None}
+                "host_intervals": None, "exclude": []}
         it = iter(args)
         for a in it:
             if a == "--threads":
@@ -139,6 +139,8 @@ class CommandRunner:
                 opts["minimizer_table"] = next(it)
             elif a == "--host-intervals":  # (the engine's own: nohuman --host-intervals)
                 opts["host_intervals"] = next(it)
+            elif a == "--exclude":  # (the builder's own: nohuman --build-db --exclude, repeatable; run() refuses it as the CLI does)
+                opts["exclude"].append(next(it))
             elif a in ("--host-taxid", "--keep-taxid"):  # (the engine's own: nohuman --host-taxid / --keep-taxid, repeatable)
                 v = next(it)
                 if not (v.isascii() and v.isdigit() and 0 < int(v) < 2 ** 64):
@@ -179,6 +181,9 @@ class CommandRunner:
             return self.run_stock(args)
         o = self.parse_argv(args)
         try:
+            if o["exclude"]:
+                raise EngineError(-1, "--exclude needs --build-db: it names sequences whose minimizers a database build leaves out "
+                                  "(build_db(exclude=...)), not a run on reads")
             if o["db"] is None:
                 raise EngineError(-1, "--db is required")
             n_in = len(o["inputs"])
