@@ -9,7 +9,8 @@
 // consecutive pieces overlap by k - 1 bases and every k-mer belongs to exactly one piece.  A k-mer's minimizer and its ambiguity
 // depend only on that k-mer's own 35 bases, so the union over the pieces is the set of the whole sequence; a sequence that does not
 // fit what is left of a batch is cut the same way at the batch's end.  One wave scans one piece with the classifier's own scanner
-// (nh_scan.h: scan_tile) -- the builder skips a k-mer exactly when the classifier would not look it up.
+// (nh_scan.h: scan_tile) -- the builder skips a k-mer exactly when the classifier would not look it up.  The walk over the pieces
+// is written once (walk_pieces); the kernel of a pass gives it what to do with a tile's minimizers and when to stop.
 //
 // Two passes over the text:
 //   COUNT   every run-start minimizer goes into a device open-addressing set of 64-bit keys (key = minimizer + 1, 0 = empty; the
@@ -113,19 +114,17 @@ __device__ __forceinline__ uint64_t set_find(const unsigned long long *set, cons
     return cap;
 }
 
-// One wave per piece: sequence text[seq_off[p], +seq_len[p]) (starts and lengths, so that pieces may overlap).
-// MULTI (INSERT only): the value of a piece is its taxon's, and a cell that already holds the key under another value becomes the
-// lowest common ancestor of the two.
-// FILTER (INSERT only, builds with an exclusion list): a minimizer whose slot of the set is flagged is not inserted.
-template <bool COUNT, bool MULTI, bool FILTER = false>
-__global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_build_pieces(const KArgs args_by_kernarg_pointer, const BuildDev b) {
-    KArgsP ap = (KArgsP)__builtin_amdgcn_kernarg_segment_ptr();
-    typedef WaveLdsT<true, 1, QCAP_GENERIC> WL;
-    __shared__ WL lds_all[WAVES_PER_BLOCK];
-    const int lane = threadIdx.x & 63;
-    const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    WL &S = lds_all[wib];
-    init_wave_lds<true>(S, lane);
+// The walk over the pieces that every pass makes: one wave per piece, sequence text[seq_off[p], +seq_len[p]) (starts and lengths, so
+// that pieces may overlap), a piece a tile at a time through scan_tile.  The bounds are kept here and nowhere else: the text is
+// readable for 8 bytes behind its end and every dword index is clamped to that tail, and a piece that leaves the text is skipped
+// by the whole wave (the host makes no such piece).  enter(p) is called once for a piece that is walked, before its text is read,
+// and what it returns goes to every per_tile(it, nruns) of the piece; that is called between two wave_sync() with the tile's
+// run-start minimizers in S.q[0][0 .. nruns): the caller's lanes take them r = lane, lane + 64, ...; stop() is asked behind every
+// piece and is wave-uniform.  -> CLEAN: the k-mers walked that are not ambiguous (wave-uniform); else 0.
+template <bool CLEAN, class WL, class Enter, class PerTile, class Stop>
+__device__ __forceinline__ unsigned long long walk_pieces(KArgsP ap, WL &S, const int lane, const int wib, Enter &&enter,
+                                                          PerTile &&per_tile, Stop &&stop) {
+    unsigned long long clean = 0;
     const uint32_t TQ = TL - 4u;  // k-mers of a full tile
     const uint64_t n_piece = ap->n_frag;
     const uint64_t *const start = ap->seq_off;
@@ -134,23 +133,15 @@ __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_build_pieces(const K
     const uint64_t last_dw = (text_len + 4) >> 2;  // the text is readable for 8 bytes behind its end
     const uint32_t *const text = reinterpret_cast<const uint32_t *>(ap->bases);
     const uint32_t pl = (uint32_t)lane < PREF_LANES ? (uint32_t)lane : PREF_LANES - 1;
-    uint32_t *const table = const_cast<uint32_t *>(ap->db.table);
-    const uint64_t cap = COUNT ? b.set_cap : ap->db.capacity;
-    const uint64_t magic = COUNT ? b.set_magic : ap->db.cap_magic;
-    const uint32_t vbits = ap->db.value_bits;
     uint64_t prof[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t tprev = 0;
-    unsigned long long claimed = 0;  // per lane
-    unsigned long long clean = 0;    // wave-uniform
-    unsigned long long merges = 0, swaps = 0, inserts = 0;  // per lane (MULTI): own key found under another value; values replaced; insertions
-    bool gave_up = false;
     const uint64_t n_waves = (uint64_t)gridDim.x * WAVES_PER_BLOCK;
     for (uint64_t p = (uint64_t)blockIdx.x * WAVES_PER_BLOCK + wib; p < n_piece; p += n_waves) {
         const uint64_t o0 = start[p];
         const uint32_t n = len[p];
         if (n < 35u || o0 > text_len || text_len - o0 < n) continue;  // (wave-uniform; the host makes no such piece)
         const uint32_t nk = n - 34u;
-        const uint32_t mine = MULTI ? b.piece_value[p] : b.value;  // (wave-uniform)
+        const auto of_piece = enter(p);
         uint64_t carry_min = NH_FULL;
         uint32_t w;
         {
@@ -172,16 +163,55 @@ __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_build_pieces(const K
             int last_lane;
             const uint32_t nruns = scan_tile<true, false>(ap, S, lane, w, (uint32_t)g0 & 3u, nlt, nqt, 0u, 0u, carry_min, ps, last_lane,
                                                           text + dwn, more, w_next, prof, tprev);
-            if (!COUNT) clean += (unsigned long long)(__popcll(__ballot(ps & 1u)) + __popcll(__ballot(ps & 2u)));
+            if (CLEAN) clean += (unsigned long long)(__popcll(__ballot(ps & 1u)) + __popcll(__ballot(ps & 2u)));
             wave_sync();
-            for (uint32_t r = lane; r < nruns && !gave_up; r += 64) {
+            per_tile(of_piece, nruns);
+            wave_sync();
+            w = w_next;
+        }
+        if (stop()) break;
+    }
+    return clean;
+}
+
+// COUNT and INSERT over the pieces of the host's text.
+// MULTI (INSERT only): the value of a piece is its taxon's, and a cell that already holds the key under another value becomes the
+// lowest common ancestor of the two.
+// FILTER (INSERT only, builds with an exclusion list): a minimizer whose slot of the set is flagged is not inserted.
+template <bool COUNT, bool MULTI, bool FILTER = false>
+__global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_build_pieces(const KArgs args_by_kernarg_pointer, const BuildDev b) {
+    KArgsP ap = (KArgsP)__builtin_amdgcn_kernarg_segment_ptr();
+    typedef WaveLdsT<true, 1, QCAP_GENERIC> WL;
+    __shared__ WL lds_all[WAVES_PER_BLOCK];
+    const int lane = threadIdx.x & 63;
+    const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    WL &S = lds_all[wib];
+    init_wave_lds<true>(S, lane);
+    uint32_t *const table = const_cast<uint32_t *>(ap->db.table);
+    const uint64_t cap = COUNT ? b.set_cap : ap->db.capacity;
+    const uint64_t magic = COUNT ? b.set_magic : ap->db.cap_magic;
+    const uint32_t vbits = ap->db.value_bits;
+    struct {  // per lane
+        unsigned long long claimed = 0;
+        unsigned long long merges = 0, swaps = 0, inserts = 0;  // (MULTI): own key found under another value; values replaced; insertions
+        bool gave_up = false;
+    } tally;
+    const unsigned long long clean = walk_pieces<!COUNT>(
+        ap, S, lane, wib,
+        [&](const uint64_t p) { return MULTI ? b.piece_value[p] : b.value; },  // the piece's value (wave-uniform)
+        [&](const uint32_t mine, const uint32_t nruns) {
+            // (the loop works on a copy of the lane's tally: updated through the closure's references the kernels compile with more
+            // SGPR spills than the walk written out in place had, and the one-taxon INSERT takes 5.7 ms where it took 5.6:
+            // profiles/build_refactor.txt)
+            auto t = tally;
+            for (uint32_t r = lane; r < nruns && !t.gave_up; r += 64) {
                 const uint64_t mz = S.q[0][r];
                 if (FILTER) {  // (every minimizer of the host is in the set: COUNT put it there)
                     unsigned long long word;
                     (void)set_find(b.set, b.set_cap, b.set_magic, mz, word);
                     if (word & SET_EXCLUDED) continue;
                 }
-                if (MULTI) inserts++;
+                if (MULTI) t.inserts++;
                 const uint64_t hc = fmix64(mz);
                 uint64_t idx = mod_capacity(hc, cap, magic);
                 bool placed = false;
@@ -193,7 +223,7 @@ __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_build_pieces(const K
                         if (cur == 0) {
                             cur = atomicCAS(&b.set[idx], 0ull, key);
                             if (cur == 0) {
-                                claimed++;
+                                t.claimed++;
                                 placed = true;
                                 break;
                             }
@@ -214,7 +244,7 @@ __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_build_pieces(const K
                         if (cur == 0) {
                             cur = atomicCAS(&table[idx], 0u, cell);
                             if (cur == 0) {
-                                claimed++;
+                                t.claimed++;
                                 placed = true;
                                 break;
                             }
@@ -233,12 +263,12 @@ __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_build_pieces(const K
                                         if (x > y) x = b.parent[x];
                                         else y = b.parent[y];
                                     }
-                                    if (first && v != mine) merges++;
+                                    if (first && v != mine) t.merges++;
                                     first = false;
                                     if (x == v) break;
                                     const uint32_t seen = atomicCAS(&table[idx], cur, (compacted << vbits) | x);
                                     if (seen == cur) {
-                                        swaps++;
+                                        t.swaps++;
                                         break;
                                     }
                                     cur = seen;
@@ -254,15 +284,14 @@ __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_build_pieces(const K
                 }
                 if (!placed) {
                     __hip_atomic_store(b.full, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    gave_up = true;
+                    t.gave_up = true;
                 }
             }
-            wave_sync();
-            w = w_next;
-        }
+            tally = t;
+        },
         // a full table: no piece after this one can do anything but find it full again
-        if (__hip_atomic_load(b.full, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;
-    }
+        [&]() { return __hip_atomic_load(b.full, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0; });
+    unsigned long long &claimed = tally.claimed, &merges = tally.merges, &swaps = tally.swaps, &inserts = tally.inserts;
     for (int d = 32; d >= 1; d >>= 1) claimed += __shfl_xor(claimed, d, 64);
     if (lane == 0) {
         if (claimed) atomicAdd(&b.counters[0], claimed);
@@ -277,9 +306,8 @@ __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_build_pieces(const K
     }
 }
 
-// EXCLUDE: the pieces of the exclusion text, scanned as COUNT scans the host's (the same bounds: a piece that leaves the text is
-// skipped, text loads are clamped to the readable tail); every run-start minimizer is looked up in the finished set and flagged
-// where it is found.  A miss -- nearly every minimizer of another genome -- writes nothing.
+// EXCLUDE: the pieces of the exclusion text, walked as COUNT walks the host's; every run-start minimizer is looked up in the
+// finished set and flagged where it is found.  A miss -- nearly every minimizer of another genome -- writes nothing.
 __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_exclude_pieces(const KArgs args_by_kernarg_pointer, const BuildDev b) {
     KArgsP ap = (KArgsP)__builtin_amdgcn_kernarg_segment_ptr();
     typedef WaveLdsT<true, 1, QCAP_GENERIC> WL;
@@ -288,48 +316,11 @@ __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_exclude_pieces(const
     const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     WL &S = lds_all[wib];
     init_wave_lds<true>(S, lane);
-    const uint32_t TQ = TL - 4u;  // k-mers of a full tile
-    const uint64_t n_piece = ap->n_frag;
-    const uint64_t *const start = ap->seq_off;
-    const uint32_t *const len = ap->seq_len;
-    const uint64_t text_len = ap->bases_end;
-    const uint64_t last_dw = (text_len + 4) >> 2;  // the text is readable for 8 bytes behind its end
-    const uint32_t *const text = reinterpret_cast<const uint32_t *>(ap->bases);
-    const uint32_t pl = (uint32_t)lane < PREF_LANES ? (uint32_t)lane : PREF_LANES - 1;
     const uint64_t cap = b.set_cap, magic = b.set_magic;
-    uint64_t prof[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t tprev = 0;
     unsigned long long flagged = 0, lookups = 0;  // per lane
-    unsigned long long clean = 0;                 // wave-uniform
-    const uint64_t n_waves = (uint64_t)gridDim.x * WAVES_PER_BLOCK;
-    for (uint64_t p = (uint64_t)blockIdx.x * WAVES_PER_BLOCK + wib; p < n_piece; p += n_waves) {
-        const uint64_t o0 = start[p];
-        const uint32_t n = len[p];
-        if (n < 35u || o0 > text_len || text_len - o0 < n) continue;  // (wave-uniform; the host makes no such piece)
-        const uint32_t nk = n - 34u;
-        uint64_t carry_min = NH_FULL;
-        uint32_t w;
-        {
-            uint64_t dw = (o0 >> 2) + pl;
-            dw = dw < last_dw ? dw : last_dw;
-            w = text[dw];
-        }
-        for (uint32_t q0 = 0; q0 < nk; q0 += TQ) {
-            const uint64_t g0 = o0 + q0;
-            const uint32_t nl_left = (n - 31u + 1) - q0;
-            const uint32_t nlt = nl_left < (uint32_t)TL ? nl_left : (uint32_t)TL;
-            const uint32_t nq_left = nk - q0;
-            const uint32_t nqt = nq_left < TQ ? nq_left : TQ;
-            // the next tile's dword is loaded while this one is scanned
-            const bool more = nq_left > TQ;
-            uint64_t dwn = ((g0 + TQ) >> 2) + pl;
-            dwn = dwn < last_dw ? dwn : last_dw;
-            uint32_t ps, w_next = 0;
-            int last_lane;
-            const uint32_t nruns = scan_tile<true, false>(ap, S, lane, w, (uint32_t)g0 & 3u, nlt, nqt, 0u, 0u, carry_min, ps, last_lane,
-                                                          text + dwn, more, w_next, prof, tprev);
-            clean += (unsigned long long)(__popcll(__ballot(ps & 1u)) + __popcll(__ballot(ps & 2u)));
-            wave_sync();
+    const unsigned long long clean = walk_pieces<true>(
+        ap, S, lane, wib, [](const uint64_t) { return 0; },
+        [&](int, const uint32_t nruns) {
             for (uint32_t r = lane; r < nruns; r += 64) {
                 unsigned long long word;
                 const uint64_t idx = set_find(b.set, cap, magic, S.q[0][r], word);
@@ -337,10 +328,8 @@ __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_exclude_pieces(const
                 // (several lanes may find one slot unflagged: the one whose atomicOr saw it so counts it)
                 if (idx < cap && !(word & SET_EXCLUDED) && !(atomicOr(&b.set[idx], SET_EXCLUDED) & SET_EXCLUDED)) flagged++;
             }
-            wave_sync();
-            w = w_next;
-        }
-    }
+        },
+        []() { return false; });
     for (int d = 32; d >= 1; d >>= 1) flagged += __shfl_xor(flagged, d, 64), lookups += __shfl_xor(lookups, d, 64);
     if (lane == 0) {
         if (flagged) atomicAdd(&b.counters[7], flagged);
@@ -421,6 +410,22 @@ struct BuildInput {
     uint32_t node;
 };
 
+// COUNT and INSERT read the host's inputs; EXCLUDE reads the exclusion list against the set of COUNT and is never masked
+enum class Pass { COUNT, EXCLUDE, INSERT };
+
+// what one pass found, every field from zero at its start
+struct PassResult {
+    unsigned long long claimed = 0;  // COUNT: slots, INSERT: cells, EXCLUDE: look-ups
+    unsigned long long clean = 0;    // k-mers that are not ambiguous (INSERT, EXCLUDE)
+    unsigned long long flagged = 0;  // EXCLUDE: slots flagged
+    unsigned long long masked = 0;
+    unsigned long long merges = 0, swaps = 0, inserts = 0;  // INSERT of several taxa
+    uint64_t sequences = 0, bases = 0, kmers = 0;           // of the inputs read
+    double seconds_read = 0, seconds_gpu = 0;
+    double seconds_kernel = 0;  // of seconds_gpu: the pass's kernel alone (HIP events; the rest is copies, set growth and waits)
+    double seconds_mask = 0;    // the mask kernel alone
+};
+
 struct Builder {
     // arguments
     uint64_t piece = DEFAULT_PIECE_KMERS, batch_cap = DEFAULT_BATCH_BYTES;
@@ -451,7 +456,6 @@ struct Builder {
     std::vector<uint32_t> parent;  // 2^vbits entries
     uint32_t *d_parent = nullptr;
     unsigned long long *d_cells = nullptr;
-    unsigned long long merges = 0, swaps = 0, inserts = 0;
     double t_cells = 0;  // k_value_cells alone
     char *d_raw = nullptr;  // masking: the batch as it was uploaded, which the mask kernel reads while it writes d_text
     DustTile *d_tiles = nullptr;
@@ -462,21 +466,14 @@ struct Builder {
     uint64_t set_cap = 0;
     uint32_t *d_table = nullptr;
     uint64_t capacity = 0;
-    // results
-    bool counting = false;
-    bool excluding = false;  // the EXCLUDE pass: the text is the exclusion input's, `claimed` its look-ups
-    bool filter = false;     // INSERT skips what EXCLUDE flagged in the set
-    unsigned long long flagged = 0;
-    uint64_t x_sequences = 0, x_bases = 0, x_kmers = 0;  // of the exclusion input
-    unsigned long long claimed = 0, clean = 0;
-    bool full = false;
-    double t_read = 0, t_gpu = 0;
-    double t_kernel = 0;  // of t_gpu: the pass's kernel alone (HIP events; the rest is copies, set growth and waits)
-    double t_mask = 0;    // the mask kernel alone, all passes
-    unsigned long long masked = 0;
+    bool filter = false;  // the set carries the flags of an EXCLUDE pass: INSERT skips what is flagged
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    uint64_t sequences = 0, bases = 0, kmers = 0;
-    std::vector<nh_build_taxon_stats> per_node;  // by internal id
+    // the pass that is running, and what it has found so far
+    Pass kind = Pass::INSERT;
+    bool dust = false;  // it masks its text: `mask`, but never EXCLUDE
+    PassResult res;
+    std::vector<nh_build_taxon_stats> per_node;  // by internal id: sequences, bases and k-mers from the first pass over the host's inputs
+    bool tallied = false;                        // that pass is over
 
     ~Builder() {
         if (device >= 0 && stream) (void)dev_set(device);
@@ -517,14 +514,6 @@ struct Builder {
             BUILD_TRY(hipStreamSynchronize(stream));
         }
         text.reserve(batch_cap);
-        return NH_OK;
-    }
-
-    int reset_counters() {
-        BUILD_TRY(hipMemsetAsync(d_counters, 0, N_COUNTERS * sizeof(unsigned long long), stream));
-        BUILD_TRY(hipStreamSynchronize(stream));
-        claimed = clean = masked = merges = swaps = inserts = flagged = 0;
-        full = false;
         return NH_OK;
     }
 
@@ -589,8 +578,8 @@ struct Builder {
         }
         auto t0 = std::chrono::steady_clock::now();
         const uint64_t n_piece = starts.size();
-        if (counting) {
-            int rc = grow_set(claimed + batch_kmers);
+        if (kind == Pass::COUNT) {
+            int rc = grow_set(res.claimed + batch_kmers);
             if (rc) return rc;
         }
         if (n_piece > piece_cap) {
@@ -609,7 +598,7 @@ struct Builder {
         if (n_piece) {
             BUILD_TRY(hipMemcpyAsync(d_starts, starts.data(), n_piece * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
             BUILD_TRY(hipMemcpyAsync(d_lens, lens.data(), n_piece * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-            if (multi && !counting && !excluding) BUILD_TRY(hipMemcpyAsync(d_values, values.data(), n_piece * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+            if (multi && kind == Pass::INSERT) BUILD_TRY(hipMemcpyAsync(d_values, values.data(), n_piece * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
         }
         const bool masking = !tiles.empty();
         if (masking) {
@@ -632,7 +621,7 @@ struct Builder {
         d.table = d_table;
         d.n_copies = 1;
         d.copy_shift = 5;
-        d.capacity = counting || excluding ? 1 : capacity;
+        d.capacity = kind == Pass::INSERT ? capacity : 1;
         d.cap_magic = ~0ull / d.capacity;
         d.node_count = node_count;
         d.value_bits = vbits;
@@ -653,7 +642,7 @@ struct Builder {
         BuildDev b;
         memset(&b, 0, sizeof b);
         b.set = d_set;
-        b.set_cap = counting || excluding || filter ? set_cap : 1;
+        b.set_cap = kind != Pass::INSERT || filter ? set_cap : 1;
         b.set_magic = ~0ull / b.set_cap;
         b.counters = d_counters;
         b.full = d_full();
@@ -662,51 +651,47 @@ struct Builder {
         b.parent = d_parent;
         const uint64_t want = (n_piece + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
         const unsigned grid = (unsigned)(want < (uint64_t)grid_max ? want : (uint64_t)grid_max);
+        void (*kernel)(KArgs, BuildDev) = nullptr;
+        switch (kind) {
+        case Pass::COUNT: kernel = k_build_pieces<true, false>; break;
+        case Pass::EXCLUDE: kernel = k_exclude_pieces; break;
+        case Pass::INSERT:
+            kernel = multi ? (filter ? k_build_pieces<false, true, true> : k_build_pieces<false, true>)
+                           : (filter ? k_build_pieces<false, false, true> : k_build_pieces<false, false>);
+            break;
+        }
         BUILD_TRY(hipEventRecord(ev[0], stream));
-        if (n_piece == 0)
-            ;  // (masking: a batch of sequences too short for a k-mer)
-        else if (counting)
-            hipLaunchKernelGGL((k_build_pieces<true, false>), dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, stream, ka, b);
-        else if (excluding)
-            hipLaunchKernelGGL(k_exclude_pieces, dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, stream, ka, b);
-        else if (filter && multi)
-            hipLaunchKernelGGL((k_build_pieces<false, true, true>), dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, stream, ka, b);
-        else if (filter)
-            hipLaunchKernelGGL((k_build_pieces<false, false, true>), dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, stream, ka, b);
-        else if (multi)
-            hipLaunchKernelGGL((k_build_pieces<false, true>), dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, stream, ka, b);
-        else
-            hipLaunchKernelGGL((k_build_pieces<false, false>), dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, stream, ka, b);
+        // (no piece, masking: a batch of sequences too short for a k-mer)
+        if (n_piece) hipLaunchKernelGGL(kernel, dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, stream, ka, b);
         BUILD_TRY(hipGetLastError());
         BUILD_TRY(hipEventRecord(ev[1], stream));
         unsigned long long out[N_COUNTERS] = {0, 0, 0, 0, 0, 0, 0, 0};
         BUILD_TRY(hipMemcpyAsync(out, d_counters, sizeof out, hipMemcpyDeviceToHost, stream));
         BUILD_TRY(hipStreamSynchronize(stream));
         float ms = 0;
-        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) t_kernel += ms * 1e-3;
+        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) res.seconds_kernel += ms * 1e-3;
         else (void)hipGetLastError();
         if (masking) {
-            if (hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) t_mask += ms * 1e-3;
+            if (hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) res.seconds_mask += ms * 1e-3;
             else (void)hipGetLastError();
         }
-        claimed = out[0];
-        clean = out[1];
-        masked = out[3];
-        merges = out[4];
-        swaps = out[5];
-        inserts = out[6];
-        flagged = out[7];
-        int f;
-        memcpy(&f, &out[2], sizeof f);
-        full = f != 0;
+        res.claimed = out[0];
+        res.clean = out[1];
+        res.masked = out[3];
+        res.merges = out[4];
+        res.swaps = out[5];
+        res.inserts = out[6];
+        res.flagged = out[7];
+        int full;
+        memcpy(&full, &out[2], sizeof full);
         text.clear();
         starts.clear();
         lens.clear();
         values.clear();
         tiles.clear();
         batch_kmers = ctx_bytes = 0;
-        t_gpu += since(t0);
-        if (full && counting) return set_error(NH_EDEVICE, "the counting set of the build overflowed (%llu slots): this is a bug", (unsigned long long)set_cap);
+        res.seconds_gpu += since(t0);
+        if (full && kind == Pass::COUNT) return set_error(NH_EDEVICE, "the counting set of the build overflowed (%llu slots): this is a bug", (unsigned long long)set_cap);
         if (full)
             return set_error(NH_ECAPACITY, "the table of %llu cells is full: the input has more distinct minimizers than `capacity` holds "
                              "(leave capacity 0 and it is counted)", (unsigned long long)capacity);
@@ -715,7 +700,7 @@ struct Builder {
 
     // one sequence into the batches: pieces of `piece` k-mers, the batch's end a cut like any other
     int add_sequence(const char *s, size_t n) {
-        if (n < 35) return mask ? add_short(s, n) : NH_OK;
+        if (n < 35) return dust ? add_short(s, n) : NH_OK;
         const size_t nk = n - 34;
         size_t pos = 0;  // the first k-mer not yet in a piece (= its first base)
         while (pos < nk) {
@@ -730,12 +715,12 @@ struct Builder {
             const size_t mk = take - 34;                     // their k-mers
             // masking: the chunk with up to 63 bases of the sequence on either side; its masked bases are counted where they are
             // k-mer starts of this chunk, and through the sequence's end in its last chunk
-            const size_t cl = !mask ? 0 : pos < DUST_CONTEXT ? pos : (size_t)DUST_CONTEXT;
+            const size_t cl = !dust ? 0 : pos < DUST_CONTEXT ? pos : (size_t)DUST_CONTEXT;
             const size_t behind = n - (pos + take);
-            const size_t cr = !mask ? 0 : behind < DUST_CONTEXT ? behind : (size_t)DUST_CONTEXT;
+            const size_t cr = !dust ? 0 : behind < DUST_CONTEXT ? behind : (size_t)DUST_CONTEXT;
             const uint64_t t = text.size() + cl;
             text.insert(text.end(), s + pos - cl, s + pos + take + cr);
-            if (mask) {
+            if (dust) {
                 dust_tiles(tiles, t - cl, cl + take + cr, cl, cl + (behind ? mk : take));
                 ctx_bytes += cl + cr;
             }
@@ -781,11 +766,15 @@ struct Builder {
         return NH_OK;
     }
 
-    // every record of every input through add_sequence
-    int pass(const std::vector<BuildInput> &inputs, bool count, bool totals) {
-        counting = count;
-        int rc = reset_counters();
-        if (rc) return rc;
+    // every record of every input through add_sequence -> what the pass found
+    int pass(const std::vector<BuildInput> &inputs, Pass k, PassResult &out) {
+        kind = k;
+        dust = mask && kind != Pass::EXCLUDE;
+        res = PassResult();
+        BUILD_TRY(hipMemsetAsync(d_counters, 0, N_COUNTERS * sizeof(unsigned long long), stream));
+        BUILD_TRY(hipStreamSynchronize(stream));
+        const bool tally = kind != Pass::EXCLUDE && !tallied;
+        int rc;
         SeqRecord rec;
         for (const BuildInput &in : inputs) {
             FastxReader rd;
@@ -798,25 +787,20 @@ struct Builder {
                 const int got = rd.next(rec, err);
                 if (got < 0) return set_error(NH_EIO, "%s: %s", in.path.c_str(), err.c_str());
                 if (got == 0) break;
-                t_read += since(t0);
-                if (excluding) {
-                    x_sequences++;
-                    x_bases += rec.seq.size();
-                    if (rec.seq.size() >= 35) x_kmers += rec.seq.size() - 34;
-                } else if (totals) {
-                    sequences++;
-                    bases += rec.seq.size();
-                    pn.sequences++;
-                    pn.bases += rec.seq.size();
-                    if (rec.seq.size() >= 35) kmers += rec.seq.size() - 34, pn.kmers += rec.seq.size() - 34;
-                }
+                res.seconds_read += since(t0);
+                const uint64_t n = rec.seq.size(), nk = n >= 35 ? n - 34 : 0;
+                res.sequences++, res.bases += n, res.kmers += nk;
+                if (tally) pn.sequences++, pn.bases += n, pn.kmers += nk;
                 rc = add_sequence(rec.seq.data(), rec.seq.size());
                 if (rc) return rc;
                 t0 = std::chrono::steady_clock::now();
             }
-            t_read += since(t0);
+            res.seconds_read += since(t0);
         }
-        return flush();
+        rc = flush();
+        tallied = tallied || tally;
+        out = res;
+        return rc;
     }
 };
 
@@ -1045,16 +1029,35 @@ void give_taxon_stats(const nh_build_args *a, const BuildPlan &P, const std::vec
     for (uint32_t i = 1; i < per_node.size() && i - 1 < a->taxon_stats_cap; i++) a->taxon_stats[i - 1] = per_node[i];
 }
 
+// the per-node table of a plan before anything is read: the taxids, every count zero
+std::vector<nh_build_taxon_stats> zero_per_node(const std::vector<TaxaNode> &nodes) {
+    std::vector<nh_build_taxon_stats> per_node(nodes.size());
+    for (size_t i = 0; i < nodes.size(); i++) memset(&per_node[i], 0, sizeof per_node[i]), per_node[i].taxid = nodes[i].taxid;
+    return per_node;
+}
+
+// what a *_check call hands back of a plan that passed: the taxa and their zeroed table
+void give_plan(const nh_build_args *a, const BuildPlan &P, nh_build_stats *stats) {
+    give_taxon_stats(a, P, zero_per_node(P.nodes));
+    if (stats && P.v3) stats->taxa = P.nodes.size() - 1;
+}
+
+// a caller's nh_exclude_stats or nh_extend_stats filled from v, its struct_size kept
+template <class T>
+void give_stats(T *xs, const T &v) {
+    if (!xs) return;
+    const uint32_t size = xs->struct_size;
+    *xs = v;
+    xs->struct_size = size, xs->reserved = 0;
+}
+
 int build_check(const nh_build_args *a, nh_build_stats *stats) {
     BuildPlan P;
     layout_of(a, P);
     if (stats) memset(stats, 0, P.stats_size);
     const int rc = plan_build(a, P);
     if (rc) return rc;
-    std::vector<nh_build_taxon_stats> per_node(P.nodes.size());
-    for (size_t i = 0; i < P.nodes.size(); i++) memset(&per_node[i], 0, sizeof per_node[i]), per_node[i].taxid = P.nodes[i].taxid;
-    give_taxon_stats(a, P, per_node);
-    if (stats && P.v3) stats->taxa = P.nodes.size() - 1;
+    give_plan(a, P, stats);
     return NH_OK;
 }
 
@@ -1102,13 +1105,6 @@ int plan_exclude(const nh_build_args *a, const nh_exclude_args *x, const BuildPl
     return NH_OK;
 }
 
-void give_exclude_stats(nh_exclude_stats *xs, const nh_exclude_stats &v) {
-    if (!xs) return;
-    const uint32_t size = xs->struct_size;
-    *xs = v;
-    xs->struct_size = size, xs->reserved = 0;
-}
-
 int exclude_check(const nh_build_args *a, const nh_exclude_args *x, nh_build_stats *stats, nh_exclude_stats *xs) {
     int rc = check_exclude_layout(x, xs);
     if (rc) return rc;
@@ -1121,14 +1117,56 @@ int exclude_check(const nh_build_args *a, const nh_exclude_args *x, nh_build_sta
     std::vector<BuildInput> files;
     rc = plan_exclude(a, x, P, files);
     if (rc) return rc;
-    std::vector<nh_build_taxon_stats> per_node(P.nodes.size());
-    for (size_t i = 0; i < P.nodes.size(); i++) memset(&per_node[i], 0, sizeof per_node[i]), per_node[i].taxid = P.nodes[i].taxid;
-    give_taxon_stats(a, P, per_node);
-    if (stats && P.v3) stats->taxa = P.nodes.size() - 1;
+    give_plan(a, P, stats);
     nh_exclude_stats v;
     memset(&v, 0, sizeof v);
-    give_exclude_stats(xs, v);
+    give_stats(xs, v);
     return NH_OK;
+}
+
+// The builder of a build or an extension, from the arguments and a plan that passed: the taxonomy's tables (value fields of at least
+// min_vbits bits), the sizes of pieces and batches -- the environment knobs are read here -- and then the device.
+int configure(Builder &B, const nh_build_args *a, const BuildPlan &P, bool multi, uint32_t min_vbits) {
+    B.device = a->device;
+    B.threads = a->threads;
+    B.mask = P.grown && a->mask_low_complexity != 0;
+    B.node_count = (uint32_t)P.nodes.size();
+    B.multi = multi;
+    B.vbits = value_bits_for(B.node_count);
+    if (B.vbits < min_vbits) B.vbits = min_vbits;
+    B.parent.assign((size_t)1 << B.vbits, 0);
+    for (uint32_t i = 0; i < B.node_count; i++) B.parent[i] = P.nodes[i].parent;
+    B.per_node = zero_per_node(P.nodes);
+    if (a->piece_kmers) B.piece = a->piece_kmers < (1ull << 31) ? a->piece_kmers : (1ull << 31);
+    if (const char *env = getenv("NOHUMAN_BUILD_BATCH")) {  // test knob: bytes of text per batch (sequences cut at the batches' ends)
+        const long long v = atoll(env);
+        if (v > 0) B.batch_cap = (uint64_t)v < 64 ? 64 : (uint64_t)v;
+    }
+    if (const char *env = getenv("NOHUMAN_OPT_AMBIGUITY_RULE")) B.ambig_rule = atoi(env) != 0 ? 1 : 0;  // as the classifier reads it
+    else B.ambig_rule = NH_AMBIGUITY_DEFAULT == NH_AMBIGUITY_LAST_LMER ? 0 : 1;
+    return B.init();
+}
+
+// the fields of nh_build_stats that a build and an extension fill alike.  `count` is null where no COUNT pass ran; the totals of the
+// host's inputs are those of the first pass over them, as the per-node counts are, and the host's clocks cover both passes.
+void fill_build_stats(nh_build_stats &s, const Builder &B, const PassResult *count, const PassResult &insert, uint64_t capacity, uint64_t size) {
+    const PassResult &first = count ? *count : insert;
+    s.seconds_insert = insert.seconds_gpu;
+    s.seconds_read = insert.seconds_read + (count ? count->seconds_read : 0);
+    s.sequences = first.sequences;
+    s.bases = first.bases;
+    s.kmers = first.kmers;
+    s.ambiguous_kmers = first.kmers - insert.clean;
+    s.capacity = capacity;
+    s.size = size;
+    s.masked_bases = insert.masked;
+    s.seconds_mask = insert.seconds_mask + (count ? count->seconds_mask : 0);
+    s.taxa = B.node_count - 1;
+}
+
+int no_kmer(const PassResult &r) {
+    return set_error(NH_EDB, "the input holds no k-mer to build from: %llu sequences, %llu bases, every sequence shorter than 35 bases or "
+                     "ambiguous throughout", (unsigned long long)r.sequences, (unsigned long long)r.bases);
 }
 
 int build_db(const nh_build_args *a, nh_build_stats *stats, const nh_exclude_args *x = nullptr, nh_exclude_stats *xs = nullptr) {
@@ -1156,63 +1194,32 @@ int build_db(const nh_build_args *a, nh_build_stats *stats, const nh_exclude_arg
     rc = check_device(a->device);
     if (rc) return rc;
     Builder B;
-    B.device = a->device;
-    B.threads = a->threads;
-    B.mask = P.grown && a->mask_low_complexity != 0;
-    B.node_count = (uint32_t)P.nodes.size();
-    B.multi = B.node_count > 3;  // (a manifest of one taxon is the one-taxon build)
-    B.vbits = value_bits_for(B.node_count);
-    B.parent.assign((size_t)1 << B.vbits, 0);
-    B.per_node.resize(B.node_count);
-    for (uint32_t i = 0; i < B.node_count; i++) {
-        B.parent[i] = P.nodes[i].parent;
-        memset(&B.per_node[i], 0, sizeof B.per_node[i]);
-        B.per_node[i].taxid = P.nodes[i].taxid;
-    }
-    if (a->piece_kmers) B.piece = a->piece_kmers < (1ull << 31) ? a->piece_kmers : (1ull << 31);
-    if (const char *env = getenv("NOHUMAN_BUILD_BATCH")) {  // test knob: bytes of text per batch (sequences cut at the batches' ends)
-        const long long v = atoll(env);
-        if (v > 0) B.batch_cap = (uint64_t)v < 64 ? 64 : (uint64_t)v;
-    }
-    if (const char *env = getenv("NOHUMAN_OPT_AMBIGUITY_RULE")) B.ambig_rule = atoi(env) != 0 ? 1 : 0;  // as the classifier reads it
-    else B.ambig_rule = NH_AMBIGUITY_DEFAULT == NH_AMBIGUITY_LAST_LMER ? 0 : 1;
-    rc = B.init();
+    rc = configure(B, a, P, P.nodes.size() > 3, 0);  // (a manifest of one taxon is the one-taxon build)
     if (rc) return rc;
 
     nh_build_stats s;
     memset(&s, 0, sizeof s);
     uint64_t capacity = a->capacity;
-    double count_kernel = 0;
-    double exclude_kernel = 0;
+    PassResult count, excl, insert;
     const bool counted = !capacity || excluding;  // (an exclusion needs the set: the counting pass runs whatever the capacity)
     if (counted) {
-        rc = B.pass(P.inputs, true, true);
+        rc = B.pass(P.inputs, Pass::COUNT, count);
         if (rc) return rc;
-        s.distinct_minimizers = B.claimed;
-        s.seconds_count = B.t_gpu;
-        count_kernel = B.t_kernel;
-        B.t_gpu = B.t_kernel = 0;
+        s.distinct_minimizers = count.claimed;
+        s.seconds_count = count.seconds_gpu;
         if (!excluding) B.free_set();
-        if (s.distinct_minimizers == 0)
-            return set_error(NH_EDB, "the input holds no k-mer to build from: %llu sequences, %llu bases, every sequence shorter than 35 bases or "
-                             "ambiguous throughout", (unsigned long long)B.sequences, (unsigned long long)B.bases);
+        if (s.distinct_minimizers == 0) return no_kmer(count);
         uint64_t kept = s.distinct_minimizers;
-        if (excluding) {  // EXCLUDE: the exclusion input against the set, never masked
-            const bool mask = B.mask;
-            const double t_read = B.t_read, t_mask = B.t_mask;
-            B.mask = false, B.excluding = true;
-            rc = B.pass(x_files, false, false);
-            B.mask = mask, B.excluding = false;
+        if (excluding) {  // the exclusion input against the set
+            rc = B.pass(x_files, Pass::EXCLUDE, excl);
             if (rc) return rc;
-            xv.sequences = B.x_sequences, xv.bases = B.x_bases, xv.kmers = B.x_kmers;
-            xv.ambiguous_kmers = B.x_kmers - B.clean;
-            xv.lookups = B.claimed;
-            xv.excluded_minimizers = B.flagged;
-            xv.kept_minimizers = kept = s.distinct_minimizers - B.flagged;
-            xv.seconds_read = B.t_read - t_read;
-            xv.seconds_exclude = B.t_gpu;
-            exclude_kernel = B.t_kernel;
-            B.t_read = t_read, B.t_mask = t_mask, B.t_gpu = B.t_kernel = 0;
+            xv.sequences = excl.sequences, xv.bases = excl.bases, xv.kmers = excl.kmers;
+            xv.ambiguous_kmers = excl.kmers - excl.clean;
+            xv.lookups = excl.claimed;
+            xv.excluded_minimizers = excl.flagged;
+            xv.kept_minimizers = kept = s.distinct_minimizers - excl.flagged;
+            xv.seconds_read = excl.seconds_read;
+            xv.seconds_exclude = excl.seconds_gpu;
             if (kept == 0)
                 return set_error(NH_EDB, "every minimizer of the input is excluded: all %llu distinct minimizers are also in the exclusion input "
                                  "(%llu sequences, %llu bases)", (unsigned long long)s.distinct_minimizers, (unsigned long long)xv.sequences,
@@ -1224,26 +1231,14 @@ int build_db(const nh_build_args *a, nh_build_stats *stats, const nh_exclude_arg
     }
     rc = B.alloc_table(capacity);
     if (rc) return rc;
-    rc = B.pass(P.inputs, false, !counted);
+    rc = B.pass(P.inputs, Pass::INSERT, insert);
     if (rc) return rc;
-    s.seconds_insert = B.t_gpu;
-    s.seconds_read = B.t_read;
-    s.sequences = B.sequences;
-    s.bases = B.bases;
-    s.kmers = B.kmers;
-    s.ambiguous_kmers = B.kmers - B.clean;
-    s.capacity = capacity;
-    s.size = B.claimed;
-    s.masked_bases = B.masked;
-    s.seconds_mask = B.t_mask;
-    if (s.size == 0)
-        return set_error(NH_EDB, "the input holds no k-mer to build from: %llu sequences, %llu bases, every sequence shorter than 35 bases or "
-                         "ambiguous throughout", (unsigned long long)B.sequences, (unsigned long long)B.bases);
+    fill_build_stats(s, B, counted ? &count : nullptr, insert, capacity, insert.claimed);
+    if (s.size == 0) return no_kmer(counted ? count : insert);
     // (a table without one empty cell is no kraken2 table: a look-up of an absent key would never end there)
     if (s.size >= capacity)
         return set_error(NH_ECAPACITY, "the table of %llu cells is full: the input has more distinct minimizers than `capacity` holds "
                          "(leave capacity 0 and it is counted)", (unsigned long long)capacity);
-    s.taxa = B.node_count - 1;
     if (B.multi) {
         rc = B.count_cells();
         if (rc) return rc;
@@ -1258,20 +1253,20 @@ int build_db(const nh_build_args *a, nh_build_stats *stats, const nh_exclude_arg
         fprintf(stderr, "[nohuman trace] build: %llu k-mers, %llu ambiguous, %llu distinct minimizers, %llu cells of %llu; kernels alone: count %.4f s, "
                         "insert %.4f s, mask %.4f s for %llu masked bases (batches of %llu bytes, pieces of %llu k-mers)\n",
                 (unsigned long long)s.kmers, (unsigned long long)s.ambiguous_kmers, (unsigned long long)s.distinct_minimizers,
-                (unsigned long long)s.size, (unsigned long long)s.capacity, count_kernel, B.t_kernel, B.t_mask,
+                (unsigned long long)s.size, (unsigned long long)s.capacity, count.seconds_kernel, insert.seconds_kernel, s.seconds_mask,
                 (unsigned long long)s.masked_bases, (unsigned long long)B.batch_cap,
                 (unsigned long long)B.piece);
     if (getenv("NOHUMAN_TRACE") && B.multi)
         fprintf(stderr, "[nohuman trace] build taxa: %u nodes, value_bits %u; insertions %llu, of them %llu found their key under another "
-                        "value (the LCA path), values replaced %llu; cells per node %.6f s\n", B.node_count - 1, B.vbits, B.inserts, B.merges,
-                B.swaps, B.t_cells);
+                        "value (the LCA path), values replaced %llu; cells per node %.6f s\n", B.node_count - 1, B.vbits, insert.inserts, insert.merges,
+                insert.swaps, B.t_cells);
     if (getenv("NOHUMAN_TRACE") && excluding)
         fprintf(stderr, "[nohuman trace] build exclude: %llu k-mers of the exclusion input, %llu look-ups, %llu of %llu distinct minimizers excluded; "
                         "kernels alone: exclude %.4f s (set of %llu slots)\n", (unsigned long long)xv.kmers, (unsigned long long)xv.lookups,
-                (unsigned long long)xv.excluded_minimizers, (unsigned long long)s.distinct_minimizers, exclude_kernel, (unsigned long long)B.set_cap);
+                (unsigned long long)xv.excluded_minimizers, (unsigned long long)s.distinct_minimizers, excl.seconds_kernel, (unsigned long long)B.set_cap);
     give_taxon_stats(a, P, B.per_node);
     if (stats) memcpy(stats, &s, stats_size);
-    give_exclude_stats(xs, xv);
+    give_stats(xs, xv);
     return NH_OK;
 }
 
@@ -1359,13 +1354,6 @@ void extend_plan_stats(const BuildPlan &P, const BasePlan &X, nh_extend_stats &x
     xs.nodes_added = P.nodes.size() - X.taxo.taxid.size();
 }
 
-void give_extend_stats(nh_extend_stats *xs, const nh_extend_stats &v) {
-    if (!xs) return;
-    const uint32_t size = xs->struct_size;
-    *xs = v;
-    xs->struct_size = size, xs->reserved = 0;
-}
-
 int extend_check(const nh_build_args *a, const nh_extend_args *x, nh_build_stats *stats, nh_extend_stats *xs) {
     BuildPlan P;
     BasePlan X;
@@ -1373,14 +1361,11 @@ int extend_check(const nh_build_args *a, const nh_extend_args *x, nh_build_stats
     const int rc = plan_extend(a, x, xs, P, X);
     if (rc) return rc;
     if (stats) memset(stats, 0, sizeof *stats);
-    std::vector<nh_build_taxon_stats> per_node(P.nodes.size());
-    for (size_t i = 0; i < P.nodes.size(); i++) memset(&per_node[i], 0, sizeof per_node[i]), per_node[i].taxid = P.nodes[i].taxid;
-    give_taxon_stats(a, P, per_node);
-    if (stats) stats->taxa = P.nodes.size() - 1;
+    give_plan(a, P, stats);
     nh_extend_stats v;
     memset(&v, 0, sizeof v);
     extend_plan_stats(P, X, v);
-    give_extend_stats(xs, v);
+    give_stats(xs, v);
     return NH_OK;
 }
 
@@ -1394,28 +1379,8 @@ int extend_db(const nh_build_args *a, const nh_extend_args *x, nh_build_stats *s
     rc = check_device(a->device);
     if (rc) return rc;
     Builder B;
-    B.device = a->device;
-    B.threads = a->threads;
-    B.mask = a->mask_low_complexity != 0;
-    B.node_count = (uint32_t)P.nodes.size();
-    B.multi = true;  // (one added taxon too: its minimizers merge with the values of the base)
-    B.vbits = value_bits_for(B.node_count);
-    if (B.vbits < X.old_vb) B.vbits = (uint32_t)X.old_vb;  // (the value field never shrinks)
-    B.parent.assign((size_t)1 << B.vbits, 0);
-    B.per_node.resize(B.node_count);
-    for (uint32_t i = 0; i < B.node_count; i++) {
-        B.parent[i] = P.nodes[i].parent;
-        memset(&B.per_node[i], 0, sizeof B.per_node[i]);
-        B.per_node[i].taxid = P.nodes[i].taxid;
-    }
-    if (a->piece_kmers) B.piece = a->piece_kmers < (1ull << 31) ? a->piece_kmers : (1ull << 31);
-    if (const char *env = getenv("NOHUMAN_BUILD_BATCH")) {
-        const long long v = atoll(env);
-        if (v > 0) B.batch_cap = (uint64_t)v < 64 ? 64 : (uint64_t)v;
-    }
-    if (const char *env = getenv("NOHUMAN_OPT_AMBIGUITY_RULE")) B.ambig_rule = atoi(env) != 0 ? 1 : 0;
-    else B.ambig_rule = NH_AMBIGUITY_DEFAULT == NH_AMBIGUITY_LAST_LMER ? 0 : 1;
-    rc = B.init();
+    // (MULTI for one added taxon too: its minimizers merge with the values of the base; the value field never shrinks)
+    rc = configure(B, a, P, true, (uint32_t)X.old_vb);
     if (rc) return rc;
 
     nh_extend_stats v;
@@ -1449,34 +1414,25 @@ int extend_db(const nh_build_args *a, const nh_extend_args *x, nh_build_stats *s
     for (uint32_t i = 1; i < B.node_count; i++) base_cells[i] = B.per_node[i].cells;
 
     const uint64_t free_cells = X.capacity - X.size;
-    rc = B.pass(P.inputs, false, true);
+    PassResult insert;
+    rc = B.pass(P.inputs, Pass::INSERT, insert);
     if (rc == NH_ECAPACITY)
         return set_error(NH_ECAPACITY, "nh_extend_db: the base table has %llu free cells of %llu and the addition needs more than that: the capacity of "
                          "an extension is its base's", (unsigned long long)free_cells, (unsigned long long)X.capacity);
     if (rc) return rc;
     nh_build_stats s;
     memset(&s, 0, sizeof s);
-    s.seconds_insert = B.t_gpu;
-    s.seconds_read = B.t_read;
-    s.sequences = B.sequences;
-    s.bases = B.bases;
-    s.kmers = B.kmers;
-    s.ambiguous_kmers = B.kmers - B.clean;
-    s.capacity = X.capacity;
-    s.size = X.size + B.claimed;
-    s.masked_bases = B.masked;
-    s.seconds_mask = B.t_mask;
-    s.taxa = B.node_count - 1;
-    v.cells_added = B.claimed;
+    fill_build_stats(s, B, nullptr, insert, X.capacity, X.size + insert.claimed);
+    v.cells_added = insert.claimed;
     v.load = (double)s.size / (double)s.capacity;
     if (s.size >= X.capacity)
         return set_error(NH_ECAPACITY, "nh_extend_db: the base table has %llu free cells of %llu and the addition needs %llu, which leaves no empty "
                          "cell: the capacity of an extension is its base's", (unsigned long long)free_cells, (unsigned long long)X.capacity,
-                         (unsigned long long)B.claimed);
+                         (unsigned long long)insert.claimed);
     if (v.load > P.lf)
         return set_error(NH_ECAPACITY, "nh_extend_db: the base table has %llu free cells of %llu and the addition needs %llu: the load would be %.4f, "
                          "above the ceiling of %.4f (load_factor)", (unsigned long long)free_cells, (unsigned long long)X.capacity,
-                         (unsigned long long)B.claimed, v.load, P.lf);
+                         (unsigned long long)insert.claimed, v.load, P.lf);
     BUILD_TRY(hipMemsetAsync(B.d_cells, 0, (size_t)B.node_count * sizeof(unsigned long long), B.stream));
     rc = B.count_cells();
     if (rc) return rc;
@@ -1488,75 +1444,51 @@ int extend_db(const nh_build_args *a, const nh_extend_args *x, nh_build_stats *s
         fprintf(stderr, "[nohuman trace] extend: base %llu cells of %llu at %llu value bits, %llu nodes; now %u value bits, %u nodes, table %s; "
                         "%llu shadowed; %llu cells added; load %.4f s, re-key %.6f s (the streaming pass alone %.6f s), insert kernels %.4f s\n",
                 (unsigned long long)X.size, (unsigned long long)X.capacity, (unsigned long long)X.old_vb, (unsigned long long)X.taxo.taxid.size(),
-                B.vbits, B.node_count, T.rekeyed ? "rewritten" : "as it was", (unsigned long long)T.shadowed, (unsigned long long)B.claimed,
-                v.seconds_load, v.seconds_rekey, T.seconds_pass, B.t_kernel);
+                B.vbits, B.node_count, T.rekeyed ? "rewritten" : "as it was", (unsigned long long)T.shadowed, (unsigned long long)insert.claimed,
+                v.seconds_load, v.seconds_rekey, T.seconds_pass, insert.seconds_kernel);
     give_taxon_stats(a, P, B.per_node);
     if (x->base_cells)
         for (uint32_t i = 1; i < B.node_count && i - 1 < x->base_cells_cap; i++) x->base_cells[i - 1] = base_cells[i];
     if (stats) memcpy(stats, &s, sizeof s);
-    give_extend_stats(xs, v);
+    give_stats(xs, v);
     return NH_OK;
+}
+
+// an exported entry: no exception leaves the library
+template <class F>
+int guarded(const char *name, F &&f) {
+    try {
+        return f();
+    } catch (const std::bad_alloc &) {
+        return set_error(NH_EOOM, "%s: out of host memory", name);
+    } catch (const std::exception &e) {
+        return set_error(NH_EIO, "%s: %s", name, e.what());
+    }
 }
 
 }  // namespace
 }  // namespace nh
 
 extern "C" int nh_build_check(const nh_build_args *args, nh_build_stats *stats) {
-    try {
-        return nh::build_check(args, stats);
-    } catch (const std::bad_alloc &) {
-        return nh::set_error(NH_EOOM, "nh_build_check: out of host memory");
-    } catch (const std::exception &e) {
-        return nh::set_error(NH_EIO, "nh_build_check: %s", e.what());
-    }
+    return nh::guarded("nh_build_check", [&] { return nh::build_check(args, stats); });
 }
 
 extern "C" int nh_build_db(const nh_build_args *args, nh_build_stats *stats) {
-    try {
-        return nh::build_db(args, stats);
-    } catch (const std::bad_alloc &) {
-        return nh::set_error(NH_EOOM, "nh_build_db: out of host memory");
-    } catch (const std::exception &e) {
-        return nh::set_error(NH_EIO, "nh_build_db: %s", e.what());
-    }
+    return nh::guarded("nh_build_db", [&] { return nh::build_db(args, stats); });
 }
 
 extern "C" int nh_exclude_check(const nh_build_args *b, const nh_exclude_args *x, nh_build_stats *bs, nh_exclude_stats *xs) {
-    try {
-        return nh::exclude_check(b, x, bs, xs);
-    } catch (const std::bad_alloc &) {
-        return nh::set_error(NH_EOOM, "nh_exclude_check: out of host memory");
-    } catch (const std::exception &e) {
-        return nh::set_error(NH_EIO, "nh_exclude_check: %s", e.what());
-    }
+    return nh::guarded("nh_exclude_check", [&] { return nh::exclude_check(b, x, bs, xs); });
 }
 
 extern "C" int nh_build_db_exclude(const nh_build_args *b, const nh_exclude_args *x, nh_build_stats *bs, nh_exclude_stats *xs) {
-    try {
-        return nh::build_db(b, bs, x, xs);
-    } catch (const std::bad_alloc &) {
-        return nh::set_error(NH_EOOM, "nh_build_db_exclude: out of host memory");
-    } catch (const std::exception &e) {
-        return nh::set_error(NH_EIO, "nh_build_db_exclude: %s", e.what());
-    }
+    return nh::guarded("nh_build_db_exclude", [&] { return nh::build_db(b, bs, x, xs); });
 }
 
 extern "C" int nh_extend_check(const nh_build_args *b, const nh_extend_args *x, nh_build_stats *bs, nh_extend_stats *xs) {
-    try {
-        return nh::extend_check(b, x, bs, xs);
-    } catch (const std::bad_alloc &) {
-        return nh::set_error(NH_EOOM, "nh_extend_check: out of host memory");
-    } catch (const std::exception &e) {
-        return nh::set_error(NH_EIO, "nh_extend_check: %s", e.what());
-    }
+    return nh::guarded("nh_extend_check", [&] { return nh::extend_check(b, x, bs, xs); });
 }
 
 extern "C" int nh_extend_db(const nh_build_args *b, const nh_extend_args *x, nh_build_stats *bs, nh_extend_stats *xs) {
-    try {
-        return nh::extend_db(b, x, bs, xs);
-    } catch (const std::bad_alloc &) {
-        return nh::set_error(NH_EOOM, "nh_extend_db: out of host memory");
-    } catch (const std::exception &e) {
-        return nh::set_error(NH_EIO, "nh_extend_db: %s", e.what());
-    }
+    return nh::guarded("nh_extend_db", [&] { return nh::extend_db(b, x, bs, xs); });
 }

@@ -292,6 +292,49 @@ def _read_stats(v) -> "ReadStats":
 MAX_TAXA_NODES = 4096  # nodes of a taxa manifest with the root (include/nohuman_engine.h)
 
 
+def _build_args(fasta_paths, out_dir, taxa, taxid, taxon_name, load_factor, capacity, piece_kmers, device, threads, force,
+                mask_low_complexity):
+    """build_db and extend_db: their nh_build_args (present layout) and the per-node array it points to, which the caller keeps
+    (the library refuses taxa together with fasta_paths, taxid or taxon_name, and neither of them)"""
+    if fasta_paths is None:
+        fasta_paths = []
+    if isinstance(fasta_paths, (str, bytes, os.PathLike)):
+        fasta_paths = [fasta_paths]
+    paths = [os.fsencode(p) for p in fasta_paths]
+    a = _lib.nh_build_args_v3()
+    a.struct_size = C.sizeof(_lib.nh_build_args_v3)
+    a.mask_low_complexity = int(bool(mask_low_complexity))
+    a.n_fasta = len(paths)
+    if paths or taxa is None:
+        a.fasta = (C.c_char_p * max(len(paths), 1))(*paths)
+    if taxa is not None:
+        a.taxa_file = os.fsencode(taxa)
+    per_node = (_lib.nh_build_taxon_stats * MAX_TAXA_NODES)()
+    a.taxon_stats = per_node
+    a.taxon_stats_cap = MAX_TAXA_NODES
+    a.out_dir = os.fsencode(out_dir) if out_dir is not None else None
+    a.taxid = int(taxid)
+    a.taxon_name = taxon_name.encode() if isinstance(taxon_name, str) else taxon_name
+    a.load_factor = float(load_factor)
+    a.capacity = int(capacity)
+    a.piece_kmers = int(piece_kmers)
+    a.device = int(device)
+    a.threads = int(threads)
+    a.force = int(bool(force))
+    return a, per_node
+
+
+def _build_stats_dict(s) -> dict:
+    """nh_build_stats (present layout) as a dict, in the struct's order"""
+    return {name: getattr(s, name) for name, _ in _lib.nh_build_stats._fields_ + _lib.nh_build_stats_v2._fields_ + _lib.nh_build_stats_v3._fields_}
+
+
+def _taxon_stats(s, per_node) -> list:
+    """the per-node array of a call that gave the stats s: a dict a node"""
+    return [{name: getattr(per_node[i], name) for name, _ in _lib.nh_build_taxon_stats._fields_}
+            for i in range(min(int(s.taxa), MAX_TAXA_NODES))]
+
+
 def build_db(fasta_paths=None, out_dir=None, *, taxid: int = 0, taxon_name=None, load_factor: float = 0.0, capacity: int = 0,
              piece_kmers: int = 0, device: int = 0, threads: int = 1, force: bool = False,
              mask_low_complexity: bool = False, taxa=None, exclude=None) -> dict:
@@ -317,32 +360,8 @@ def build_db(fasta_paths=None, out_dir=None, *, taxid: int = 0, taxon_name=None,
     if isinstance(exclude, (str, bytes, os.PathLike)):
         exclude = [exclude]
     x_paths = [os.fsencode(p) for p in exclude]
-    if fasta_paths is None:  # (the library refuses taxa together with fasta_paths, taxid or taxon_name, and neither of them)
-        fasta_paths = []
-    if isinstance(fasta_paths, (str, bytes, os.PathLike)):
-        fasta_paths = [fasta_paths]
-    paths = [os.fsencode(p) for p in fasta_paths]
-    a = _lib.nh_build_args_v3()
-    a.struct_size = C.sizeof(_lib.nh_build_args_v3)
-    a.mask_low_complexity = int(bool(mask_low_complexity))
-    a.n_fasta = len(paths)
-    arr = (C.c_char_p * max(len(paths), 1))(*paths)
-    if paths or taxa is None:
-        a.fasta = arr
-    if taxa is not None:
-        a.taxa_file = os.fsencode(taxa)
-    per_node = (_lib.nh_build_taxon_stats * MAX_TAXA_NODES)()
-    a.taxon_stats = per_node
-    a.taxon_stats_cap = MAX_TAXA_NODES
-    a.out_dir = os.fsencode(out_dir) if out_dir is not None else None
-    a.taxid = int(taxid)
-    a.taxon_name = taxon_name.encode() if isinstance(taxon_name, str) else taxon_name
-    a.load_factor = float(load_factor)
-    a.capacity = int(capacity)
-    a.piece_kmers = int(piece_kmers)
-    a.device = int(device)
-    a.threads = int(threads)
-    a.force = int(bool(force))
+    a, per_node = _build_args(fasta_paths, out_dir, taxa, taxid, taxon_name, load_factor, capacity, piece_kmers, device, threads, force,
+                              mask_low_complexity)
     s = _lib.nh_build_stats_v3()
     if x_paths:
         x = _lib.nh_exclude_args()
@@ -355,14 +374,13 @@ def build_db(fasta_paths=None, out_dir=None, *, taxid: int = 0, taxon_name=None,
         _check(_lib.lib().nh_build_db_exclude(C.byref(a), C.byref(x), C.byref(s), C.byref(xs)))
     else:
         _check(_lib.lib().nh_build_db(C.byref(a), C.byref(s)))
-    out = {name: getattr(s, name) for name, _ in _lib.nh_build_stats._fields_ + _lib.nh_build_stats_v2._fields_ + _lib.nh_build_stats_v3._fields_}
+    out = _build_stats_dict(s)
     if x_paths:
         out.update(exclude_sequences=xs.sequences, exclude_bases=xs.bases, exclude_kmers=xs.kmers,
                    exclude_ambiguous_kmers=xs.ambiguous_kmers, exclude_lookups=xs.lookups,
                    excluded_minimizers=xs.excluded_minimizers, kept_minimizers=xs.kept_minimizers,
                    seconds_exclude_read=xs.seconds_read, seconds_exclude=xs.seconds_exclude)
-    out["taxon_stats"] = [{name: getattr(per_node[i], name) for name, _ in _lib.nh_build_taxon_stats._fields_}
-                          for i in range(min(int(s.taxa), MAX_TAXA_NODES))]
+    out["taxon_stats"] = _taxon_stats(s, per_node)
     return out
 
 
@@ -377,31 +395,8 @@ def extend_db(base_dir, out_dir, fasta_paths=None, *, taxa=None, taxid: int = 0,
     dict (base_size, base_nodes, base_value_bits, nodes_added, cells_added, shadowed_cells, load, seconds_load, seconds_rekey
     beside build_db's keys) with taxon_stats, a list of dicts (taxid, sequences, bases, kmers, cells, base_cells: the cells
     the node held in the base, after renumbering) a node of the merged taxonomy in internal-id order from the root on."""
-    if fasta_paths is None:
-        fasta_paths = []
-    if isinstance(fasta_paths, (str, bytes, os.PathLike)):
-        fasta_paths = [fasta_paths]
-    paths = [os.fsencode(p) for p in fasta_paths]
-    a = _lib.nh_build_args_v3()
-    a.struct_size = C.sizeof(_lib.nh_build_args_v3)
-    a.mask_low_complexity = int(bool(mask_low_complexity))
-    a.n_fasta = len(paths)
-    arr = (C.c_char_p * max(len(paths), 1))(*paths)
-    if paths or taxa is None:
-        a.fasta = arr
-    if taxa is not None:
-        a.taxa_file = os.fsencode(taxa)
-    per_node = (_lib.nh_build_taxon_stats * MAX_TAXA_NODES)()
-    a.taxon_stats = per_node
-    a.taxon_stats_cap = MAX_TAXA_NODES
-    a.out_dir = os.fsencode(out_dir) if out_dir is not None else None
-    a.taxid = int(taxid)
-    a.taxon_name = taxon_name.encode() if isinstance(taxon_name, str) else taxon_name
-    a.load_factor = float(max_load)
-    a.piece_kmers = int(piece_kmers)
-    a.device = int(device)
-    a.threads = int(threads)
-    a.force = int(bool(force))
+    a, per_node = _build_args(fasta_paths, out_dir, taxa, taxid, taxon_name, max_load, 0, piece_kmers, device, threads, force,
+                              mask_low_complexity)
     x = _lib.nh_extend_args()
     x.struct_size = C.sizeof(_lib.nh_extend_args)
     x.base_dir = os.fsencode(base_dir) if base_dir is not None else None
@@ -412,10 +407,9 @@ def extend_db(base_dir, out_dir, fasta_paths=None, *, taxa=None, taxid: int = 0,
     xs = _lib.nh_extend_stats()
     xs.struct_size = C.sizeof(_lib.nh_extend_stats)
     _check(_lib.lib().nh_extend_db(C.byref(a), C.byref(x), C.byref(s), C.byref(xs)))
-    out = {name: getattr(s, name) for name, _ in _lib.nh_build_stats._fields_ + _lib.nh_build_stats_v2._fields_ + _lib.nh_build_stats_v3._fields_}
+    out = _build_stats_dict(s)
     out.update({name: getattr(xs, name) for name, _ in _lib.nh_extend_stats._fields_ if name not in ("struct_size", "reserved")})
-    out["taxon_stats"] = [dict({name: getattr(per_node[i], name) for name, _ in _lib.nh_build_taxon_stats._fields_}, base_cells=int(base_cells[i]))
-                          for i in range(min(int(s.taxa), MAX_TAXA_NODES))]
+    out["taxon_stats"] = [dict(node, base_cells=int(base_cells[i])) for i, node in enumerate(_taxon_stats(s, per_node))]
     return out
 
 

@@ -277,9 +277,10 @@ def test_given_capacity(case, tmp_path):
     assert ei.value.code == NH_ECAPACITY and "capacity" in ei.value.message and not (tmp_path / "full").exists()
 
 
-def test_manifest_build(tmp_path):
-    """the tree of the taxa tests with a list that carries the stretch A and B share and a stretch of A alone: both are stored
-    under no taxon, the stretch A and G share stays at G, the one A, B and C share at the root"""
+@pytest.fixture(scope="module")
+def manifest_inputs():
+    """the tree of the taxa tests with a list that carries the stretch A and B share and a stretch of A alone, and the model's
+    table of it (computed once)"""
     from oracle import minidb
     from tests import build_taxa_util as t
     c = t.tree_case()
@@ -295,8 +296,17 @@ def test_manifest_build(tmp_path):
     vb = minidb.value_bits_for(tax.node_count)
     blob, size = xm.build_hash_fast(tax, c["pairs"], X, cap)
     assert size == len(kept)
+    return dict(c=c, excl=excl, mins=mins, X=X, H=H, kept=kept, cap=cap, vb=vb, blob=blob, size=size)
+
+
+def manifest_build(tmp_path, mi, **kw):
+    """the manifest build with the list against the model: the table as a set, the cells per node, the statistics"""
+    from oracle import minidb
+    from tests import build_taxa_util as t
+    c, X, H, kept, cap, vb, blob, size, mins = (mi[k] for k in ("c", "X", "H", "kept", "cap", "vb", "blob", "size", "mins"))
+    tax, st_ = c["tax"], c["stretches"]
     m = t.write_case(tmp_path, c["lines"], c["records"])
-    st = build(None, tmp_path / "db", taxa=m, piece_kmers=500, exclude=[u.write_fasta(tmp_path / "x.fa", excl)])
+    st = build(None, tmp_path / "db", taxa=m, exclude=[u.write_fasta(tmp_path / "x.fa", mi["excl"])], **kw)
     assert (st["distinct_minimizers"], st["excluded_minimizers"], st["kept_minimizers"]) == (len(H), len(H & X), len(kept))
     assert (st["capacity"], st["size"], st["taxa"]) == (cap, size, tax.node_count - 1)
     hdr, cells = table(tmp_path / "db")
@@ -307,6 +317,23 @@ def test_manifest_build(tmp_path):
     assert all(db.get(x) == 0 for x in H & X)
     assert {db.get(x) for x in mins(st_["ag"])} == {tax.internal[t.G]}
     assert {db.get(x) for x in mins(st_["abc"])} == {1}
+    return st
+
+
+def test_manifest_build(tmp_path, manifest_inputs):
+    """the tree of the taxa tests with a list that carries the stretch A and B share and a stretch of A alone: both are stored
+    under no taxon, the stretch A and G share stays at G, the one A, B and C share at the root"""
+    manifest_build(tmp_path, manifest_inputs, piece_kmers=500)
+
+
+def test_manifest_build_cut(tmp_path, manifest_inputs):
+    """the same build (k_build_pieces<false, true, true>) with batches of 4096 bytes and pieces of 64 k-mers: records are cut at
+    the batches' ends, a piece is shorter than a tile, and the result is the model's all the same"""
+    seqs = [s for _, s in manifest_inputs["c"]["pairs"]]
+    cut = bf.batches_of(seqs, 4096)
+    assert len(cut) >= 16 and sum(1 for j in range(len(seqs)) if sum(any(i == j for i, _ in b) for b in cut) >= 2) >= 12
+    st = manifest_build(tmp_path, manifest_inputs, batch=4096, piece_kmers=64)
+    assert st["exclude_kmers"] == sum(len(s) - 34 for _, s in manifest_inputs["excl"])
 
 
 def test_mask_low_complexity(tmp_path):
