@@ -115,60 +115,33 @@ __device__ __forceinline__ uint64_t set_find(const unsigned long long *set, cons
 }
 
 // The walk over the pieces that every pass makes: one wave per piece, sequence text[seq_off[p], +seq_len[p]) (starts and lengths, so
-// that pieces may overlap), a piece a tile at a time through scan_tile.  The bounds are kept here and nowhere else: the text is
-// readable for 8 bytes behind its end and every dword index is clamped to that tail, and a piece that leaves the text is skipped
-// by the whole wave (the host makes no such piece).  enter(p) is called once for a piece that is walked, before its text is read,
-// and what it returns goes to every per_tile(it, nruns) of the piece; that is called between two wave_sync() with the tile's
-// run-start minimizers in S.q[0][0 .. nruns): the caller's lanes take them r = lane, lane + 64, ...; stop() is asked behind every
-// piece and is wave-uniform.  -> CLEAN: the k-mers walked that are not ambiguous (wave-uniform); else 0.
+// that pieces may overlap), a piece a tile at a time through walk_tiles (nh_scan.h) with no minimizer carried into it.  The text
+// is readable for 8 bytes behind its end, which is the tail the walk's loads are clamped to, and a piece that leaves the text is
+// skipped by the whole wave (the host makes no such piece).  enter(p) is called once for a piece that is walked, before its text
+// is read, and what it returns goes to every per_tile(it, nruns) of the piece; that is called between two wave_sync() with the
+// tile's run-start minimizers in S.q[0][0 .. nruns): the caller's lanes take them r = lane, lane + 64, ...; stop() is asked behind
+// every piece and is wave-uniform.  -> CLEAN: the k-mers walked that are not ambiguous (wave-uniform); else 0.
 template <bool CLEAN, class WL, class Enter, class PerTile, class Stop>
 __device__ __forceinline__ unsigned long long walk_pieces(KArgsP ap, WL &S, const int lane, const int wib, Enter &&enter,
                                                           PerTile &&per_tile, Stop &&stop) {
     unsigned long long clean = 0;
-    const uint32_t TQ = TL - 4u;  // k-mers of a full tile
     const uint64_t n_piece = ap->n_frag;
     const uint64_t *const start = ap->seq_off;
     const uint32_t *const len = ap->seq_len;
     const uint64_t text_len = ap->bases_end;
     const uint64_t last_dw = (text_len + 4) >> 2;  // the text is readable for 8 bytes behind its end
     const uint32_t *const text = reinterpret_cast<const uint32_t *>(ap->bases);
-    const uint32_t pl = (uint32_t)lane < PREF_LANES ? (uint32_t)lane : PREF_LANES - 1;
-    uint64_t prof[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t tprev = 0;
     const uint64_t n_waves = (uint64_t)gridDim.x * WAVES_PER_BLOCK;
     for (uint64_t p = (uint64_t)blockIdx.x * WAVES_PER_BLOCK + wib; p < n_piece; p += n_waves) {
         const uint64_t o0 = start[p];
         const uint32_t n = len[p];
         if (n < 35u || o0 > text_len || text_len - o0 < n) continue;  // (wave-uniform; the host makes no such piece)
-        const uint32_t nk = n - 34u;
         const auto of_piece = enter(p);
         uint64_t carry_min = NH_FULL;
-        uint32_t w;
-        {
-            uint64_t dw = (o0 >> 2) + pl;
-            dw = dw < last_dw ? dw : last_dw;
-            w = text[dw];
-        }
-        for (uint32_t q0 = 0; q0 < nk; q0 += TQ) {
-            const uint64_t g0 = o0 + q0;
-            const uint32_t nl_left = (n - 31u + 1) - q0;
-            const uint32_t nlt = nl_left < (uint32_t)TL ? nl_left : (uint32_t)TL;
-            const uint32_t nq_left = nk - q0;
-            const uint32_t nqt = nq_left < TQ ? nq_left : TQ;
-            // the next tile's dword is loaded while this one is scanned
-            const bool more = nq_left > TQ;
-            uint64_t dwn = ((g0 + TQ) >> 2) + pl;
-            dwn = dwn < last_dw ? dwn : last_dw;
-            uint32_t ps, w_next = 0;
-            int last_lane;
-            const uint32_t nruns = scan_tile<true, false>(ap, S, lane, w, (uint32_t)g0 & 3u, nlt, nqt, 0u, 0u, carry_min, ps, last_lane,
-                                                          text + dwn, more, w_next, prof, tprev);
+        walk_tiles(ap, S, lane, text, last_dw, o0, n, carry_min, [&](const uint32_t nruns, const uint32_t ps) {
             if (CLEAN) clean += (unsigned long long)(__popcll(__ballot(ps & 1u)) + __popcll(__ballot(ps & 2u)));
-            wave_sync();
             per_tile(of_piece, nruns);
-            wave_sync();
-            w = w_next;
-        }
+        });
         if (stop()) break;
     }
     return clean;
@@ -394,8 +367,6 @@ __global__ __launch_bounds__(256) void k_set_rehash(const unsigned long long *ol
 
 constexpr uint64_t DEFAULT_PIECE_KMERS = 16 * (TL - 4);  // 1984: 16 tiles, 1.7 % of the text read twice
 constexpr uint64_t DEFAULT_BATCH_BYTES = 128ull << 20;
-constexpr uint64_t TOGGLE_MASK = 0xe37e28c4271b5a2dull;
-constexpr uint64_t SPACED_MASK = 0x3FFFFFFFF3333333ull;  // "1" x 17 + "01" x 7, two bits a base
 constexpr uint32_t TAXON_NODE = 2;                       // one taxon: three nodes, 0 the null sentinel, 1 root, 2 the taxon
 constexpr int N_COUNTERS = 8;  // claimed, clean, `full` (an int), masked bases, then of several taxa: LCA merges, values replaced, insertions; EXCLUDE: slots flagged
 const char *const DB_FILES[3] = {"hash.k2d", "opts.k2d", "taxo.k2d"};

@@ -9,9 +9,11 @@
 // k_cover_mark      a sequence is cut into pieces of `piece` k-mers (COVER_PIECE, NOHUMAN_COVER_PIECE) that overlap by k - 1 bases;
 //                   the pieces of a batch are numbered by an exclusive scan of the sequences' piece counts (k_cover_piece_sizes,
 //                   _scan, _starts: nh_outbuild.h's scheme) and a wave takes COVER_CHUNK consecutive pieces: one binary search, then a
-//                   walk.  A piece is scanned tile by tile exactly as k_mdata_mark scans a mate (scan_tile<true, false>, the next
-//                   tile's dword prefetched, the carried minimizer from tile to tile) with no carry INTO it: the first unambiguous
-//                   k-mer of a piece starts a run whatever lay before, and a run start is one find-only look-up.  `ps` says which run
+//                   walk.  A piece is scanned a tile at a time with no carry INTO it: the first unambiguous k-mer of a piece
+//                   starts a run whatever lay before, and a run start is one find-only look-up (nh_scan.h: find_cell).  The
+//                   tile loop is walk_tiles' (nh_scan.h), written out: with its per-tile code in a closure this kernel reloads
+//                   its arguments inside the loop and measured 0.6 % slower on long reads (profiles/tile_walk_refactor.txt);
+//                   what differs from walk_tiles is the clamp alone, the last dword that holds a byte of the text.  `ps` says which run
 //                   covers each k-mer; the tile's host k-mers, two ballots, are spread to a 128-bit mask, dilated by k (shifts and
 //                   ORs of a 256-bit value the whole wave holds), shifted to the bit of the tile's first base and ORed into the
 //                   bitmap, one bit a byte of the text: eight words at the most, a lane each.  A word whose new bits are zero is
@@ -47,8 +49,6 @@ namespace {
 constexpr uint32_t COVER_PIECE = 32 * (TL - 4);  // k-mers of a piece: 32 tiles, the classifier's segment (nh_device.h SEG_TILES)
 constexpr uint32_t COVER_CHUNK = 8;              // consecutive pieces a wave claims: one binary search for all of them
 constexpr uint32_t CK = 35;                      // k of the default geometry (cover_check_db)
-constexpr uint64_t CV_SPACED_MASK = 0x3FFFFFFFF3333333ull;  // kraken2's defaults (nh_build.hip writes them)
-constexpr uint64_t CV_TOGGLE_MASK = 0xe37e28c4271b5a2dull;
 
 // ---- the pieces ------------------------------------------------------------------------------------------------------------------
 struct PieceArgs {
@@ -105,24 +105,6 @@ struct CoverDev {
     uint32_t *cover;         // ceil(ntext / 32) words
     uint64_t n_words;
 };
-
-// find-only look-up of one minimizer (find_cell's scheme in nh_mdata.hip, without the cell): the value found, 0 for a miss
-__device__ __forceinline__ uint32_t find_value(const uint32_t *table, const uint64_t cap, const uint64_t magic, const uint32_t vbits,
-                                               const uint32_t vmask, const uint64_t min_hash, const uint64_t mz) {
-    const uint64_t hc = fmix64(mz);
-    if (min_hash != 0 && hc < min_hash) return 0;  // (the classifier does not look such a minimizer up: taxon 0)
-    const uint32_t compacted = (uint32_t)(hc >> (32 + vbits));
-    uint64_t idx = mod_capacity(hc, cap, magic);
-    for (uint64_t tries = 0; tries < cap; tries++) {
-        const uint32_t cell = table[idx];
-        const uint32_t v = cell & vmask;
-        if (v == 0) return 0;  // an empty cell ends the probe run
-        if ((cell >> vbits) == compacted) return v;
-        idx++;
-        if (idx >= cap) idx = 0;
-    }
-    return 0;
-}
 
 // bit i of x -> bit 2 i
 __device__ __forceinline__ uint64_t spread_bits(uint32_t v) {
@@ -223,7 +205,12 @@ __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_cover_mark(const KAr
                 for (int t = 0; t < 2; t++) {
                     const uint32_t r = (uint32_t)lane + 64u * t;
                     if (r >= nruns) continue;
-                    const uint32_t v = find_value(table, cap, magic, vbits, vmask, min_hash, S.q[0][r]);
+                    const uint64_t mz = S.q[0][r];
+                    // minimum_acceptable_hash_value: the classifier does not look such a minimizer up (taxon 0).  The hash is
+                    // taken in front of the test, so that find_cell's own merges with it: one fmix64 a look-up, as before
+                    const uint64_t hc = fmix64(mz);
+                    uint64_t at;  // (the cell is of no use here)
+                    const uint32_t v = min_hash != 0 && hc < min_hash ? 0u : find_cell(table, cap, magic, vbits, vmask, mz, at);
                     hit[t] = v != 0 && (m.host_of == nullptr || ((uint64_t)v < m.n_nodes && m.host_of[v] != 0));
                 }
                 const uint64_t hb0 = __ballot(hit[0]), hb1 = __ballot(hit[1]);
@@ -262,20 +249,6 @@ __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_cover_mark(const KAr
             }
         }
     }
-}
-
-int mark_blocks_per_cu() {
-    static const int n = [] {
-        int v = 0;
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, k_cover_mark, WAVE * WAVES_PER_BLOCK, 0) == hipSuccess && v > 0 ? v : 4;
-    }();
-    return n;
-}
-
-DevDB devdb_now(Engine *e) {  // options may be set from another thread: this launch's parameter block under the lock
-    std::lock_guard<std::mutex> lock(e->db_mu);
-    finish_devdb_public(e);
-    return e->dev;
 }
 
 uint32_t cover_piece() {  // k-mers of a piece: tuning / test knob, read at every launch
@@ -552,10 +525,10 @@ int cover_check_db(const Engine *e) {
     const char *const what = "host intervals: the pass supports the default geometry and linear probing only";
     if (i.k != 35) return set_error(NH_EINVAL, "%s: k is %llu, not 35", what, (unsigned long long)i.k);
     if (i.l != 31) return set_error(NH_EINVAL, "%s: l is %llu, not 31", what, (unsigned long long)i.l);
-    if (i.spaced_seed_mask != CV_SPACED_MASK)
-        return set_error(NH_EINVAL, "%s: spaced_seed_mask is 0x%llx, not 0x%llx", what, (unsigned long long)i.spaced_seed_mask, (unsigned long long)CV_SPACED_MASK);
-    if (i.toggle_mask != CV_TOGGLE_MASK)
-        return set_error(NH_EINVAL, "%s: toggle_mask is 0x%llx, not 0x%llx", what, (unsigned long long)i.toggle_mask, (unsigned long long)CV_TOGGLE_MASK);
+    if (i.spaced_seed_mask != SPACED_MASK)
+        return set_error(NH_EINVAL, "%s: spaced_seed_mask is 0x%llx, not 0x%llx", what, (unsigned long long)i.spaced_seed_mask, (unsigned long long)SPACED_MASK);
+    if (i.toggle_mask != TOGGLE_MASK)
+        return set_error(NH_EINVAL, "%s: toggle_mask is 0x%llx, not 0x%llx", what, (unsigned long long)i.toggle_mask, (unsigned long long)TOGGLE_MASK);
     if (i.revcom_version == 0) return set_error(NH_EINVAL, "%s: revcom_version is 0 (a legacy database)", what);
     if (!e->options.linear_probing) return set_error(NH_EINVAL, "%s: linear_probing is 0 in the engine's options", what);
     return NH_OK;
@@ -593,7 +566,8 @@ hipError_t launch_cover_mark(Engine *e, const CoverArgs &c, hipStream_t stream) 
     // the pieces there are is known on the device only: at least a piece a sequence's worth of waves, bounded by what the device holds
     const uint64_t by_text = c.ntext / ((uint64_t)pa.piece * COVER_CHUNK) + 1;
     const uint64_t want = (std::max<uint64_t>(by_text, (c.n_seq + COVER_CHUNK - 1) / COVER_CHUNK) + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-    const unsigned grid = (unsigned)std::min<uint64_t>(want, (uint64_t)std::max(1, e->n_cu) * mark_blocks_per_cu());
+    static const int per_cu = blocks_per_cu(k_cover_mark, WAVE * WAVES_PER_BLOCK, 4);
+    const unsigned grid = (unsigned)std::min<uint64_t>(want, (uint64_t)std::max(1, e->n_cu) * per_cu);
     hipLaunchKernelGGL(k_cover_mark, dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, stream, ka, m);
     return hipGetLastError();
 }

@@ -330,6 +330,12 @@ static void finish_devdb(Engine *e) {
 
 void finish_devdb_public(Engine *e) { finish_devdb(e); }
 
+DevDB devdb_now(Engine *e) {
+    std::lock_guard<std::mutex> lock(e->db_mu);
+    finish_devdb(e);
+    return e->dev;
+}
+
 static int alloc_table(Engine *e, uint64_t capacity) {
     // padded so that 16-byte chunk loads at the end of the table stay in bounds
     e->table_cells_alloc = ((capacity + 3) & ~3ull) + 32;

@@ -15,6 +15,17 @@
 namespace nh {
 constexpr unsigned LAUNCH_SLOTS = 16;  // launches of one engine that may be in flight at once
 constexpr uint64_t DEFER_WORDS = 1u << 15;  // 1 Mi chunks per launch (24 M pairs); larger launches skip the short-read kernel
+// kraken2's default masks: what the builder writes, and what the passes that scan at the default geometry ask of a database
+constexpr uint64_t TOGGLE_MASK = 0xe37e28c4271b5a2dull;
+constexpr uint64_t SPACED_MASK = 0x3FFFFFFFF3333333ull;  // "1" x 17 + "01" x 7, two bits a base
+
+// blocks of `kernel` (`threads` a block, no dynamic LDS) that a CU holds, `fallback` where the runtime does not say: a launcher
+// asks once and keeps the answer in a static
+template <class Kernel>
+int blocks_per_cu(Kernel kernel, int threads, int fallback) {
+    int v = 0;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, kernel, threads, 0) == hipSuccess && v > 0 ? v : fallback;
+}
 }
 
 namespace nh {
@@ -114,6 +125,7 @@ int open_synthetic(uint64_t capacity, uint64_t n_keys, uint32_t depth, uint64_t 
                    Engine **out);
 void destroy(Engine *e);
 void finish_devdb_public(Engine *e);
+DevDB devdb_now(Engine *e);  // the parameter block of a launch made now, taken under db_mu: options may be set from another thread
 int refresh_table_copies(Engine *e);  // after the cells of copy 0 changed (load, inserts): device-wide sync + re-copy
 int resolve_db_dir(const char *db_dir, std::string &resolved);
 int classify_device(Engine *e, const void *d_bases, const void *d_seq_off, uint64_t n_frag,

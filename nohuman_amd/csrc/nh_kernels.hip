@@ -1837,30 +1837,14 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
     return x ^ (x >> 31);
 }
 
-// kraken2 CompactHashTable::CompareAndSet with a constant value: claim the first empty cell of
-// the probe sequence, or stop at a cell that already holds this compacted key.
+// n_keys pseudo-random minimizers, each put into the table with a constant value (nh_scan.h: claim_cell)
 __global__ void k_synth_insert(uint32_t *table, uint64_t capacity, uint64_t cap_magic,
                                uint32_t value_bits, uint32_t value, uint64_t n_keys, uint64_t seed,
                                uint64_t key_mask, unsigned long long *size_counter) {
     uint64_t inserted = 0;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_keys; i += stride) {
-        const uint64_t mz = splitmix64(seed + i) & key_mask;
-        const uint64_t hc = fmix64(mz);
-        const uint32_t compacted = (uint32_t)(hc >> (32 + value_bits));
-        const uint32_t cell = (compacted << value_bits) | value;
-        uint64_t idx = mod_capacity(hc, capacity, cap_magic);
-        for (uint64_t tries = 0; tries < capacity; tries++) {
-            const uint32_t old = atomicCAS(&table[idx], 0u, cell);
-            if (old == 0) {
-                inserted++;
-                break;
-            }
-            if ((old >> value_bits) == compacted) break;
-            idx++;
-            if (idx >= capacity) idx = 0;
-        }
-    }
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_keys; i += stride)
+        if (claim_cell(table, capacity, cap_magic, value_bits, value, splitmix64(seed + i) & key_mask)) inserted++;
     // one atomic per wave
     for (int d = 32; d >= 1; d >>= 1) inserted += __shfl_xor(inserted, d, 64);
     if ((threadIdx.x & 63) == 0 && inserted) atomicAdd(size_counter, (unsigned long long)inserted);
@@ -1868,7 +1852,8 @@ __global__ void k_synth_insert(uint32_t *table, uint64_t capacity, uint64_t cap_
 
 // Inserts every minimizer of the given sequences into the table with a constant value (kraken2
 // build_db.cc ProcessSequence + CompareAndSet, linear probing): lets the bench put "human" reads
-// into the synthetic table so that the hit path is measured too.  Default geometry (STD) only.
+// into the synthetic table so that the hit path is measured too.  Default geometry (STD) only: one wave a sequence, through
+// walk_tiles and claim_cell (nh_scan.h).
 __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_insert_sequences(const KArgs args_by_kernarg_pointer,
                                                                             const uint32_t value) {
     KArgsP ap = (KArgsP)__builtin_amdgcn_kernarg_segment_ptr();
@@ -1878,56 +1863,26 @@ __global__ __launch_bounds__(WAVE * WAVES_PER_BLOCK) void k_insert_sequences(con
     const int wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     WL &S = lds_all[wib];
     init_wave_lds<true>(S, lane);
-    const uint32_t TQ = TL - 4u;
     const uint64_t n_seq = ap->n_frag;
     const uint64_t *const seq_off = ap->seq_off;
-    const uint64_t last_dw = (seq_off[n_seq] + 4) >> 2;
+    const uint64_t last_dw = (seq_off[n_seq] + 4) >> 2;  // the bases are readable for 8 bytes behind the last sequence
+    const uint32_t *const text = reinterpret_cast<const uint32_t *>(ap->bases);
     uint32_t *const table = const_cast<uint32_t *>(ap->db.table);
     const uint64_t cap = ap->db.capacity, magic = ap->db.cap_magic;
     const uint32_t vbits = ap->db.value_bits;
-    uint64_t prof[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t tprev = 0;
     unsigned long long inserted = 0;
     const uint64_t n_waves = (uint64_t)gridDim.x * WAVES_PER_BLOCK;
     for (uint64_t s = (uint64_t)blockIdx.x * WAVES_PER_BLOCK + wib; s < n_seq; s += n_waves) {
         const uint64_t o0 = seq_off[s];
         const uint32_t n = (uint32_t)(seq_off[s + 1] - o0);
-        const uint32_t nk = n >= 35u ? n - 34u : 0;
+        if (n < 35u) continue;  // (wave-uniform) no k-mer; the offsets ascend, so a sequence ends where the bases do at the latest
         uint64_t carry_min = NH_FULL;
-        for (uint32_t q0 = 0; q0 < nk; q0 += TQ) {
-            const uint64_t g0 = o0 + q0;
-            uint64_t dw = (g0 >> 2) + ((uint32_t)lane < PREF_LANES ? (uint32_t)lane : PREF_LANES - 1);
-            dw = dw < last_dw ? dw : last_dw;
-            const uint32_t *wp = reinterpret_cast<const uint32_t *>(ap->bases) + dw;
-            const uint32_t w = *wp;
-            const uint32_t nl_left = (n - 31u + 1) - q0;
-            const uint32_t nlt = nl_left < (uint32_t)TL ? nl_left : (uint32_t)TL;
-            const uint32_t nq_left = nk - q0;
-            const uint32_t nqt = nq_left < TQ ? nq_left : TQ;
-            uint32_t ps, wdummy = 0;
-            int last_lane;
-            const uint32_t nruns = scan_tile<true, false>(ap, S, lane, w, (uint32_t)g0 & 3u, nlt, nqt, 0u, 0u,
-                                                          carry_min, ps, last_lane, wp, false, wdummy, prof,
-                                                          tprev);
-            wave_sync();
-            for (uint32_t r = lane; r < nruns; r += 64) {
-                const uint64_t hc = fmix64(S.q[0][r]);
-                const uint32_t compacted = (uint32_t)(hc >> (32 + vbits));
-                const uint32_t cell = (compacted << vbits) | value;
-                uint64_t idx = mod_capacity(hc, cap, magic);
-                for (uint64_t tries = 0; tries < cap; tries++) {
-                    const uint32_t old = atomicCAS(&table[idx], 0u, cell);
-                    if (old == 0) {
-                        inserted++;
-                        break;
-                    }
-                    if ((old >> vbits) == compacted) break;
-                    idx++;
-                    if (idx >= cap) idx = 0;
-                }
-            }
-            wave_sync();
-        }
+        walk_tiles(ap, S, lane, text, last_dw, o0, n, carry_min, [&](const uint32_t nruns, uint32_t) {
+            unsigned long long ins = inserted;  // (a local copy: see k_build_pieces)
+            for (uint32_t r = lane; r < nruns; r += 64)
+                if (claim_cell(table, cap, magic, vbits, value, S.q[0][r])) ins++;
+            inserted = ins;
+        });
     }
     for (int d = 32; d >= 1; d >>= 1) inserted += __shfl_xor(inserted, d, 64);
     if (lane == 0 && inserted) atomicAdd(&ap->counters[0], inserted);

@@ -7,11 +7,13 @@
 // HyperLogLog, no sketches to merge, the same numbers whatever the batches, streams and devices, and clades that sum.
 //
 // k_mdata_mark, a pass of its own behind the classifier (which is not touched): one wave per fragment, both mates by the same
-// wave (reset_per_mate = 0 carries the last minimizer across the mate border), the tiles scanned by the classifier's own scanner
-// exactly as the builder's k_build_pieces does it (nh_scan.h: scan_tile<true, false>, the next tile's dword prefetched, carry_min
-// from tile to tile within a mate) -- a run start here is a run start there.  Every run start is looked up with a find-only linear
-// probe over copy 0 of the resident table (64-bit cell indices, bounded by the capacity); a hit sets the bit of the cell WHERE THE
-// KEY WAS FOUND and counts one hit group for the cell's value.
+// wave (reset_per_mate = 0 carries the last minimizer across the mate border), a mate a tile at a time through the classifier's
+// own scanner, carry_min from tile to tile and across the mate border -- a run start here is a run start there.  The tile loop
+// is walk_tiles' (nh_scan.h), written out: with its per-tile code in a closure the kernel compiled with more exec-mask
+// bookkeeping and missed the parent's timing in some legs (profiles/tile_walk_refactor.txt); as it stands it compiles to the
+// code it had.  Every run start is looked up with a find-only linear probe over copy 0 of the resident table (nh_scan.h: find_cell; 64-bit cell
+// indices, bounded by the capacity); a hit sets the bit of the cell WHERE THE KEY WAS FOUND and counts one hit group for the
+// cell's value.
 //   the bit      the word is read with a plain load first and the atomic OR issued only when the bit is clear: bits only go from 0
 //                to 1, so a stale read costs one redundant atomic and nothing else.  In a host-heavy sample almost every hit is a
 //                repeat, and a device atomic drops its line from L2 where a load keeps it (NOHUMAN_MDATA_ATOMIC=always disables
@@ -45,33 +47,11 @@ namespace nh {
 namespace {
 
 constexpr uint32_t MD_LDS_BINS = 4096;  // nodes up to which k_mdata_count keeps its bins in LDS (16 KB)
-constexpr uint64_t MD_SPACED_MASK = 0x3FFFFFFFF3333333ull;  // kraken2's defaults (nh_build.hip writes them)
-constexpr uint64_t MD_TOGGLE_MASK = 0xe37e28c4271b5a2dull;
 
 struct MarkDev {
     uint32_t *marks;             // one bit per cell, ceil(capacity / 32) words
     unsigned long long *groups;  // node_count counters
 };
-
-// find-only look-up of one minimizer: the value found (0: a miss) and, with it, the cell where the key matched
-__device__ __forceinline__ uint32_t find_cell(const uint32_t *table, const uint64_t cap, const uint64_t magic, const uint32_t vbits,
-                                              const uint32_t vmask, const uint64_t mz, uint64_t &at) {
-    const uint64_t hc = fmix64(mz);
-    const uint32_t compacted = (uint32_t)(hc >> (32 + vbits));
-    uint64_t idx = mod_capacity(hc, cap, magic);
-    for (uint64_t tries = 0; tries < cap; tries++) {
-        const uint32_t cell = table[idx];
-        const uint32_t v = cell & vmask;
-        if (v == 0) return 0;  // an empty cell ends the probe run
-        if ((cell >> vbits) == compacted) {
-            at = idx;
-            return v;
-        }
-        idx++;
-        if (idx >= cap) idx = 0;
-    }
-    return 0;
-}
 
 // One wave per fragment; TEST: look at the bitmap's word before the atomic.
 template <bool TEST>
@@ -243,12 +223,6 @@ __global__ __launch_bounds__(256) void k_mdata_count(const uint32_t *table, cons
     }
 }
 
-DevDB devdb_now(Engine *e) {  // options may be set from another thread: this launch's parameter block under the lock
-    std::lock_guard<std::mutex> lock(e->db_mu);
-    finish_devdb_public(e);
-    return e->dev;
-}
-
 bool mark_always_atomic() {
     static const bool v = [] {
         const char *env = getenv("NOHUMAN_MDATA_ATOMIC");
@@ -257,26 +231,18 @@ bool mark_always_atomic() {
     return v;
 }
 
-int mark_blocks_per_cu() {
-    static const int n = [] {
-        int v = 0;
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, k_mdata_mark<true>, WAVE * WAVES_PER_BLOCK, 0) == hipSuccess && v > 0 ? v : 4;
-    }();
-    return n;
-}
-
 }  // namespace
 
 int mdata_check_db(const Engine *e) {
     const nh_db_info &i = e->info;
     if (i.k != 35) return set_error(NH_EDB, "minimizer data: k is %llu; the pass supports the default geometry only (k = 35)", (unsigned long long)i.k);
     if (i.l != 31) return set_error(NH_EDB, "minimizer data: l is %llu; the pass supports the default geometry only (l = 31)", (unsigned long long)i.l);
-    if (i.spaced_seed_mask != MD_SPACED_MASK)
+    if (i.spaced_seed_mask != SPACED_MASK)
         return set_error(NH_EDB, "minimizer data: spaced_seed_mask is 0x%llx, not the default 0x%llx", (unsigned long long)i.spaced_seed_mask,
-                         (unsigned long long)MD_SPACED_MASK);
-    if (i.toggle_mask != MD_TOGGLE_MASK)
+                         (unsigned long long)SPACED_MASK);
+    if (i.toggle_mask != TOGGLE_MASK)
         return set_error(NH_EDB, "minimizer data: toggle_mask is 0x%llx, not the default 0x%llx", (unsigned long long)i.toggle_mask,
-                         (unsigned long long)MD_TOGGLE_MASK);
+                         (unsigned long long)TOGGLE_MASK);
     if (i.minimum_acceptable_hash_value != 0)
         return set_error(NH_EDB, "minimizer data: minimum_acceptable_hash_value is %llu, not 0", (unsigned long long)i.minimum_acceptable_hash_value);
     if (i.revcom_version == 0) return set_error(NH_EDB, "minimizer data: revcom_version is 0 (a legacy database)");
@@ -302,7 +268,8 @@ hipError_t launch_mdata_mark(Engine *e, const void *d_text, uint64_t text_len, c
     m.marks = (uint32_t *)d_marks;
     m.groups = (unsigned long long *)d_groups;
     const uint64_t want = (n_frag + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-    const unsigned grid = (unsigned)std::min<uint64_t>(want, (uint64_t)std::max(1, e->n_cu) * mark_blocks_per_cu());
+    static const int per_cu = blocks_per_cu(k_mdata_mark<true>, WAVE * WAVES_PER_BLOCK, 4);
+    const unsigned grid = (unsigned)std::min<uint64_t>(want, (uint64_t)std::max(1, e->n_cu) * per_cu);
     if (mark_always_atomic()) hipLaunchKernelGGL((k_mdata_mark<false>), dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, stream, ka, m);
     else hipLaunchKernelGGL((k_mdata_mark<true>), dim3(grid), dim3(WAVE * WAVES_PER_BLOCK), 0, stream, ka, m);
     return hipGetLastError();

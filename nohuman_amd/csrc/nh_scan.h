@@ -1,6 +1,8 @@
 // nh_scan.h -- the minimizer scanner of the gfx950 kernels: the per-wave LDS layout, the tile encoder and scan_tile, with
-// the hash helpers (fmix64, mod_capacity).  Device code shared by the classifier (nh_kernels.hip) and the database builder
-// (nh_build.hip): a k-mer is ambiguous, and has the minimizer it has, by ONE piece of code in both.
+// the hash helpers (fmix64, mod_capacity), and what the passes beside the classifier share: the walk over a stretch of text
+// (walk_tiles), the find-only probe (find_cell) and the constant-value claim (claim_cell).  Device code shared by the classifier
+// (nh_kernels.hip), the database builder (nh_build.hip), the minimizer data (nh_mdata.hip) and the host intervals
+// (nh_cover.hip): a k-mer is ambiguous, and has the minimizer it has, by ONE piece of code in all of them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -123,6 +125,46 @@ __device__ __forceinline__ uint64_t mod_capacity(uint64_t hc, uint64_t cap, uint
     if (r >= cap) r -= cap;
     if (r >= cap) r -= cap;
     return r;
+}
+
+// Find-only look-up of one minimizer by linear probing: plain loads from its home on, the index wrapping at the table's end, until
+// an empty cell or the compacted key; at most `cap` cells are looked at.  -> the value found (0: a miss) and, with it, in `at`
+// the cell where the key matched.
+__device__ __forceinline__ uint32_t find_cell(const uint32_t *table, const uint64_t cap, const uint64_t magic, const uint32_t vbits,
+                                              const uint32_t vmask, const uint64_t mz, uint64_t &at) {
+    const uint64_t hc = fmix64(mz);
+    const uint32_t compacted = (uint32_t)(hc >> (32 + vbits));
+    uint64_t idx = mod_capacity(hc, cap, magic);
+    for (uint64_t tries = 0; tries < cap; tries++) {
+        const uint32_t cell = table[idx];
+        const uint32_t v = cell & vmask;
+        if (v == 0) return 0;  // an empty cell ends the probe run
+        if ((cell >> vbits) == compacted) {
+            at = idx;
+            return v;
+        }
+        idx++;
+        if (idx >= cap) idx = 0;
+    }
+    return 0;
+}
+
+// kraken2 CompactHashTable::CompareAndSet with a constant value: claim the first empty cell of the probe sequence, or stop at a
+// cell that already holds this compacted key (or after `cap` cells).  -> this lane claimed an empty cell.
+__device__ __forceinline__ bool claim_cell(uint32_t *table, const uint64_t cap, const uint64_t magic, const uint32_t vbits,
+                                           const uint32_t value, const uint64_t mz) {
+    const uint64_t hc = fmix64(mz);
+    const uint32_t compacted = (uint32_t)(hc >> (32 + vbits));
+    const uint32_t cell = (compacted << vbits) | value;
+    uint64_t idx = mod_capacity(hc, cap, magic);
+    for (uint64_t tries = 0; tries < cap; tries++) {
+        const uint32_t old = atomicCAS(&table[idx], 0u, cell);
+        if (old == 0) return true;
+        if ((old >> vbits) == compacted) return false;
+        idx++;
+        if (idx >= cap) idx = 0;
+    }
+    return false;
 }
 
 // reverse the 32 two-bit groups of x and complement every base
@@ -472,5 +514,49 @@ __device__ __forceinline__ void init_wave_lds(WL &S, const int lane) {
 }
 
 constexpr uint32_t PREF_LANES = 42;  // dwords a tile can need: (3 + 128 + 30 + 3) / 4 <= 41
+
+// The tile walk of the passes beside the classifier that take a closure well -- the builder's walk_pieces and k_insert_sequences;
+// k_mdata_mark and k_cover_mark keep this loop written out (profiles/tile_walk_refactor.txt) -- at the default geometry, k = 35,
+// l = 31: ONE stretch text[o0, o0 + n) a tile of TL - 4 k-mers at a time through scan_tile<true, false>, the next tile's dword
+// loaded while this one is scanned.  The text is read as dwords and every dword index is clamped to `last_dw`, the last dword
+// the caller may read: no load leaves text[0 .. last_dw] whatever o0 and n are.  The caller sees to it that n >= 35, that the
+// stretch lies inside the text, and that both tests are wave-uniform: the whole wave walks, or none of it.  `carry_min` is the
+// minimizer of the last unambiguous k-mer before the stretch (NH_FULL: none) and, afterwards, of the last one in it.
+// per_tile(nruns, ps) is called between two wave_sync() with the tile's run-start minimizers in S.q[0][0 .. nruns), two a lane
+// at the most; `ps` is scan_body's.
+template <class WL, class PerTile>
+__device__ __forceinline__ void walk_tiles(KArgsP ap, WL &S, const int lane, const uint32_t *const text, const uint64_t last_dw,
+                                           const uint64_t o0, const uint32_t n, uint64_t &carry_min, PerTile &&per_tile) {
+    const uint32_t TQ = TL - 4u;  // k-mers of a full tile
+    const uint32_t pl = (uint32_t)lane < PREF_LANES ? (uint32_t)lane : PREF_LANES - 1;
+    const uint32_t nk = n - 34u;
+    uint64_t prof[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    uint64_t tprev = 0;
+    uint32_t w;
+    {
+        uint64_t dw = (o0 >> 2) + pl;
+        dw = dw < last_dw ? dw : last_dw;
+        w = text[dw];
+    }
+    for (uint32_t q0 = 0; q0 < nk; q0 += TQ) {
+        const uint64_t g0 = o0 + q0;
+        const uint32_t nl_left = (n - 31u + 1) - q0;
+        const uint32_t nlt = nl_left < (uint32_t)TL ? nl_left : (uint32_t)TL;
+        const uint32_t nq_left = nk - q0;
+        const uint32_t nqt = nq_left < TQ ? nq_left : TQ;
+        // the next tile's dword is loaded while this one is scanned
+        const bool more = nq_left > TQ;
+        uint64_t dwn = ((g0 + TQ) >> 2) + pl;
+        dwn = dwn < last_dw ? dwn : last_dw;
+        uint32_t ps, w_next = 0;
+        int last_lane;
+        const uint32_t nruns = scan_tile<true, false>(ap, S, lane, w, (uint32_t)g0 & 3u, nlt, nqt, 0u, 0u, carry_min, ps, last_lane,
+                                                      text + dwn, more, w_next, prof, tprev);
+        wave_sync();
+        per_tile(nruns, ps);
+        wave_sync();
+        w = w_next;
+    }
+}
 
 }  // namespace nh
