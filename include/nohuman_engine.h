@@ -968,6 +968,57 @@ int nh_host_cover_device(nh_engine *e, const void *d_text, uint64_t text_len, co
 int nh_cover_intervals_device(nh_engine *e, const void *d_cover, uint64_t text_len, const void *d_seq_starts, const void *d_seq_lens,
                               uint64_t n_seq, void *d_intervals, uint64_t cap_records, void *d_total, void *error_bits, void *stream);
 
+/*
+ * Host bases only (--host-bases-only, --host-gap; nh_cover.hip and nh_mask.hip; tests/hitmask_model.py is the
+ * specification): a masked run that writes 'N' only over the bases that host k-mers cover.  A masked run blanks a 40 kb bacterial
+ * read with one 300-base human-like stretch whole; this one removes the stretch and keeps the rest of the read, in the pass that
+ * already holds the text and the answer in HBM.
+ *
+ * COVERAGE is the host intervals' (above), bit for bit: the same mark pass, on the copy the classifier read, with the host
+ * selection where the run has one.  CLOSING, gap = G: a maximal run of uncovered bases [a, b) of one sequence with a covered base
+ * on each side in that sequence (a > 0, b < its length) and b - a <= G becomes covered; mates are closed separately, a run that
+ * touches an end of its sequence never is, G = 0 changes nothing.  An uncovered run shorter than k between two host k-mers holds
+ * no whole k-mer of its own, so nothing says it is not host: --host-gap 34 (k - 1) is the recommendation for noisy long reads.
+ * OUTPUT: the run is a masked run -- extras->mask is required --, every record in input order in the forms of nh_run_mask.  A
+ * HOST FRAGMENT is one whose call, after the host selection, is not 0: exactly the fragments a masked run blanks.  Byte p of each
+ * mate's sequence of a host fragment is 'N' where the closed coverage is set and the INPUT's own byte elsewhere (its case kept;
+ * never the quality- or DUST-masked copy); every other byte of every record is the masked run's.  Every other output, the three
+ * totals and a host intervals' file of the same run (the coverage BEFORE the closing) are byte for byte those of the masked run
+ * without it; not enabled, nothing is allocated or launched.
+ *
+ * nh_run_hostbases / nh_run_engine_hostbases: nh_run_intervals with the struct.  hb NULL or hb->enable 0: exactly
+ * nh_run_intervals.  A struct_size smaller than the struct, enable without extras->mask, gap above NH_HOST_GAP_MAX (a design cap:
+ * closing is for leftovers of k-mer size between error-broken stretches, not for deleting sequence): NH_EINVAL before any device is
+ * touched, nothing created.  The database must be one the mark pass supports (see above): NH_EINVAL, the reason named, once it is
+ * open.  host_bases (the sequence bases of host fragments, both mates), masked_bases (those written as 'N', whatever letter was
+ * there) and closed_bases (the masked ones that only the closing set) are exact, summed over the run's devices, and 0 where the
+ * run fails after its arguments were accepted.
+ *
+ * nh_cover_close_device: the closing on a bitmap laid out as nh_host_cover_device leaves it, on the engine's device, on `stream`.
+ * d_closed_bases: NULL, or a uint64 in device memory the kernel adds the bases it sets to.  It waits for the stream; n_seq == 0
+ * or gap == 0 launches nothing; a gap above NH_HOST_GAP_MAX is NH_EINVAL; a sequence that leaves [0, text_len) is skipped and
+ * sets the sticky error bit 1024, as in nh_host_cover_device.
+ */
+#define NH_HOST_GAP_MAX 4096
+typedef struct {
+    uint32_t struct_size;   /* sizeof(nh_host_bases) of the caller */
+    uint32_t enable;        /* 0: no such run */
+    uint32_t gap;           /* 0 .. NH_HOST_GAP_MAX */
+    uint32_t reserved;      /* 0 */
+    uint64_t host_bases;    /* out */
+    uint64_t masked_bases;  /* out */
+    uint64_t closed_bases;  /* out */
+} nh_host_bases;
+int nh_run_hostbases(const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality, const char *read_stats_path,
+                     nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs, nh_minimizer_data *md, nh_host_filter *hf,
+                     nh_read_dust *rd, nh_host_intervals *hi, nh_host_bases *hb, nh_stats *stats);
+int nh_run_engine_hostbases(nh_engine *e, const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality,
+                            const char *read_stats_path, nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs,
+                            nh_minimizer_data *md, nh_host_filter *hf, nh_read_dust *rd, nh_host_intervals *hi, nh_host_bases *hb,
+                            nh_stats *stats);
+int nh_cover_close_device(nh_engine *e, void *d_cover, uint64_t text_len, const void *d_seq_starts, const void *d_seq_lens,
+                          uint64_t n_seq, uint32_t gap, void *d_closed_bases, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

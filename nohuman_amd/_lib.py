@@ -103,6 +103,14 @@ class nh_host_intervals(C.Structure):
                 ("fragments", C.c_uint64), ("intervals", C.c_uint64), ("covered_bases", C.c_uint64)]
 
 
+class nh_host_bases(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("enable", C.c_uint32), ("gap", C.c_uint32), ("reserved", C.c_uint32),
+                ("host_bases", C.c_uint64), ("masked_bases", C.c_uint64), ("closed_bases", C.c_uint64)]
+
+
+NH_HOST_GAP_MAX = 4096
+
+
 class nh_gzip_model_opts(C.Structure):
     _fields_ = [("ways", C.c_uint32), ("region_bytes", C.c_uint32), ("chunk_bytes", C.c_uint64), ("prices", C.c_int32),
                 ("bgzf", C.c_int32), ("threads", C.c_uint32), ("reserved", C.c_uint32),
@@ -265,6 +273,14 @@ SYMBOLS = {
                                           C.POINTER(nh_read_stats), C.POINTER(nh_taxon_out), C.c_uint32, C.POINTER(nh_minimizer_data),
                                           C.POINTER(nh_host_filter), C.POINTER(nh_read_dust), C.POINTER(nh_host_intervals),
                                           C.POINTER(nh_stats)]),
+    "nh_run_hostbases": (C.c_int, [C.POINTER(nh_run_args), C.POINTER(nh_run_extras), C.c_uint32, C.c_char_p, C.POINTER(nh_read_stats),
+                                   C.POINTER(nh_taxon_out), C.c_uint32, C.POINTER(nh_minimizer_data), C.POINTER(nh_host_filter),
+                                   C.POINTER(nh_read_dust), C.POINTER(nh_host_intervals), C.POINTER(nh_host_bases), C.POINTER(nh_stats)]),
+    "nh_run_engine_hostbases": (C.c_int, [_P, C.POINTER(nh_run_args), C.POINTER(nh_run_extras), C.c_uint32, C.c_char_p,
+                                          C.POINTER(nh_read_stats), C.POINTER(nh_taxon_out), C.c_uint32, C.POINTER(nh_minimizer_data),
+                                          C.POINTER(nh_host_filter), C.POINTER(nh_read_dust), C.POINTER(nh_host_intervals),
+                                          C.POINTER(nh_host_bases), C.POINTER(nh_stats)]),
+    "nh_cover_close_device": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint64, C.c_uint32, _P, _P]),
     "nh_host_cover_device": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint64, _P, C.c_uint64, _P, _P]),
     "nh_cover_intervals_device": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint64, _P, C.c_uint64, _P, _P, _P]),
     "nh_host_table_image": (C.c_int, [_P, C.c_size_t, C.POINTER(nh_host_filter), _P, C.c_uint64, C.POINTER(C.c_uint64)]),

@@ -24,6 +24,14 @@
 //                   sequence (two sequences back to back give two records).  One wave a sequence at a time, 64 sequences a wave; a
 //                   lane takes a word: starts = w & ~(w << 1 | last bit of the word before), ends likewise, both with the words cut
 //                   to the sequence; the k-th start and the k-th end of a sequence make its k-th record (wave prefix sums).
+// k_cover_close     --host-bases-only's gap closing (tests/hitmask_model.py): an uncovered run of at most `gap` bases with a
+//                   covered base on each side in the same sequence becomes covered.  One wave a sequence, a lane a word, as the
+//                   interval builder; a lane takes the run ends of its word (covered, the next base not), looks for the sequence's
+//                   next covered base -- the rest of its word, then the words behind it as far as `gap` reaches -- and ORs the
+//                   bits between the two into the bitmap with atomicOr, a word at a time.  The uncovered runs are disjoint and a
+//                   run is closed by the lane that holds the base in front of it alone, so what other lanes set meanwhile (bits
+//                   in front of a covered base, never behind the last one a lane looks at) changes no lane's answer.  A run closes
+//                   the sequences of its host fragments alone (the mask builder reads no other), so the kernel's sum is closed_bases.
 // k_cover_line_*    sizes, scan, write on nh_outbuild.h: one line a record, <id> \t <start> \t <end> \t <mate> \t <taxid> \n, the
 //                   id as nh_calls.hip's (read_id), decimal digits by division; the sizes also count the fragments with a record
 //                   and the covered bases.
@@ -386,6 +394,58 @@ __global__ void __launch_bounds__(OB_THREADS) k_cover_ivl_write(CoverIvlArgs a) 
     }
 }
 
+// ---- the gap closing -------------------------------------------------------------------------------------------------------------
+constexpr unsigned CLOSE_MAX_BLOCKS = 1u << 16;
+
+__global__ void __launch_bounds__(OB_THREADS) k_cover_close(CoverCloseArgs a) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t n_waves = (uint64_t)gridDim.x * OB_WAVES;
+    uint64_t closed = 0;
+    for (uint64_t s = (uint64_t)blockIdx.x * OB_WAVES + (threadIdx.x >> 6); s < a.n_seq; s += n_waves) {  // (wave-uniform)
+        if (a.res != nullptr && a.res[s / (uint32_t)a.mates].call == 0) continue;  // (no host fragment: the mask builder does not ask)
+        const uint64_t o0 = a.seq_off[s];
+        const uint32_t n = a.seq_len[s];
+        if (!seq_in_text(o0, n, a.ntext)) {
+            if (lane == 0) atomicOr(a.error, NH_ERR_COVER);
+            continue;
+        }
+        if (n < 3) continue;  // (no base with a neighbour on each side)
+        const uint64_t end = o0 + n, w0 = o0 >> 5, w1 = (end - 1) >> 5;
+        for (uint64_t it = w0; it <= w1; it += 64) {
+            const uint64_t i = it + (uint64_t)lane;
+            const uint32_t w = seq_word(a.cover, i, w0, w1, o0, end);
+            if (!w) continue;
+            uint32_t en = w & ~((w >> 1) | (seq_word(a.cover, i + 1, w0, w1, o0, end) << 31));  // covered, the next base not
+            while (en) {
+                const uint32_t b = (uint32_t)__builtin_ctz(en);
+                en &= en - 1;
+                const uint64_t e = (i << 5) + b + 1;  // the run's first base; the sequence's next covered base is the run's end
+                const uint32_t rest = b == 31 ? 0u : w >> (b + 1);
+                uint64_t nx = ~0ull;
+                if (rest) nx = e + (uint32_t)__builtin_ctz(rest);
+                else
+                    for (uint64_t j = i + 1; j <= w1 && (j << 5) <= e + a.gap; j++) {
+                        const uint32_t x = seq_word(a.cover, j, w0, w1, o0, end);
+                        if (x) {
+                            nx = (j << 5) + (uint32_t)__builtin_ctz(x);
+                            break;
+                        }
+                    }
+                if (nx == ~0ull || nx - e > a.gap) continue;  // (it touches the sequence's end, or is longer than the gap)
+                for (uint64_t j = e >> 5; j <= (nx - 1) >> 5; j++) {  // (words of the sequence: e > o0, nx < end)
+                    const uint64_t b0 = j << 5;
+                    const uint32_t lo = e > b0 ? (uint32_t)(e - b0) : 0u, hi = nx < b0 + 32 ? (uint32_t)(nx - b0) : 32u;
+                    atomicOr(a.cover + j, (hi == 32 ? 0xFFFFFFFFu : (1u << hi) - 1u) & ~((1u << lo) - 1u));
+                }
+                closed += nx - e;
+            }
+        }
+    }
+    if (a.closed == nullptr) return;
+    const uint32_t lo = wave_sum((uint32_t)closed), hi = wave_sum((uint32_t)(closed >> 32));  // (a lane's sum is below 2^40: text_len)
+    if (lane == 0 && (lo | hi)) atomicAdd(a.closed, ((unsigned long long)hi << 32) + lo);
+}
+
 // ---- the records into lines ------------------------------------------------------------------------------------------------------
 constexpr int N_LFIELDS = 4;  // the numbers of a line: start, end, mate, taxid
 
@@ -584,6 +644,13 @@ hipError_t launch_cover_intervals(const CoverIvlArgs &a_, hipStream_t stream) {
     return hipGetLastError();
 }
 
+hipError_t launch_cover_close(const CoverCloseArgs &a, hipStream_t stream) {
+    if (a.n_seq == 0 || a.gap == 0) return hipSuccess;
+    const uint64_t want = (a.n_seq + OB_WAVES - 1) / OB_WAVES;
+    hipLaunchKernelGGL(k_cover_close, dim3((unsigned)std::min<uint64_t>(want, CLOSE_MAX_BLOCKS)), dim3(OB_THREADS), 0, stream, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_cover_lines(const CoverLinesArgs &a, hipStream_t stream) {
     if (a.n == 0 || a.nblk == 0) return hipMemsetAsync(a.total, 0, 4 * sizeof(uint64_t), stream);
     hipLaunchKernelGGL(k_cover_line_sizes, dim3((unsigned)a.nblk), dim3(OB_THREADS), 0, stream, a);
@@ -646,5 +713,27 @@ extern "C" int nh_cover_intervals_device(nh_engine *e_, const void *d_cover, uin
     if (he == hipSuccess) he = se;
     if (scratch) (void)hipFree(scratch);
     if (he != hipSuccess) return nh::set_error(NH_EDEVICE, "host intervals, interval launch: %s", hipGetErrorString(he));
+    return NH_OK;
+}
+
+extern "C" int nh_cover_close_device(nh_engine *e_, void *d_cover, uint64_t text_len, const void *d_seq_starts, const void *d_seq_lens, uint64_t n_seq,
+                                     uint32_t gap, void *d_closed_bases, void *stream) {
+    nh::Engine *e = (nh::Engine *)e_;
+    if (!e || !d_cover || (n_seq && (!d_seq_starts || !d_seq_lens))) return nh::set_error(NH_EINVAL, "nh_cover_close_device: null argument");
+    if (((uintptr_t)d_cover & 3) || ((uintptr_t)d_closed_bases & 7))
+        return nh::set_error(NH_EINVAL, "nh_cover_close_device: the bitmap must be 4-byte aligned, the counter 8-byte aligned");
+    if (gap > NH_HOST_GAP_MAX) return nh::set_error(NH_EINVAL, "nh_cover_close_device: gap %u is above NH_HOST_GAP_MAX (%d)", gap, NH_HOST_GAP_MAX);
+    if (n_seq > (1ull << 32) || text_len >= (1ull << 40)) return nh::set_error(NH_EINVAL, "nh_cover_close_device: too many sequences or too much text for one launch");
+    if (n_seq == 0 || gap == 0 || text_len == 0) return NH_OK;
+    if (nh::dev_set(e->device) != hipSuccess) return nh::set_error(NH_EDEVICE, "hipSetDevice failed");
+    nh::CoverCloseArgs a{};
+    a.cover = (uint32_t *)d_cover, a.ntext = text_len;
+    a.seq_off = (const uint64_t *)d_seq_starts, a.seq_len = (const uint32_t *)d_seq_lens, a.n_seq = n_seq;
+    a.gap = gap, a.res = nullptr, a.mates = 1, a.closed = (unsigned long long *)d_closed_bases;
+    a.error = e->d_error + nh::LAUNCH_SLOTS;
+    hipError_t he = nh::launch_cover_close(a, (hipStream_t)stream);
+    const hipError_t se = hipStreamSynchronize((hipStream_t)stream);
+    if (he == hipSuccess) he = se;
+    if (he != hipSuccess) return nh::set_error(NH_EDEVICE, "host bases only, closing launch: %s", hipGetErrorString(he));
     return NH_OK;
 }

@@ -184,6 +184,11 @@ struct MaskArgs {
     uint32_t *fast;           // 2 * nblk words of scratch
     uint64_t *total;          // 4 words: [m] the bytes of mate m's output, [2 + m] how many of its blocks are FAST
     int *error;               // the engine's sticky error word (bit 8: a record outside its text or buffer)
+    // --host-bases-only (NULL: the whole sequence of a classified fragment is 'N', as ever): the batch's cover bitmap after the
+    // closing, one bit a byte of the text (nh_cover.hip) -- a classified fragment's base is 'N' where its bit is set and the text's
+    // own byte elsewhere; hb: two counters the waves add to, the sequence bases of the classified fragments and those written as 'N'
+    const uint32_t *cover;
+    unsigned long long *hb;
 };
 uint64_t mask_blocks(uint64_t n);
 hipError_t launch_mask(const MaskArgs &a, hipStream_t stream);
@@ -310,6 +315,18 @@ struct CoverLinesArgs {
     uint64_t *total;          // 4 words: bytes, lines, fragments with a line, covered bases
     int *error;
 };
+struct CoverCloseArgs {       // --host-bases-only's gap closing: an uncovered run of at most gap bases between two covered ones of a sequence
+    uint32_t *cover;          // cover_words(ntext) words, ORed into
+    uint64_t ntext;
+    const uint64_t *seq_off;
+    const uint32_t *seq_len;
+    uint64_t n_seq;
+    uint32_t gap;
+    const nh_result *res;     // NULL (every sequence), or the results of the n_seq / mates fragments: a fragment whose call is 0 is left alone
+    int mates;
+    unsigned long long *closed;  // NULL or one counter the waves add the bases they set to
+    int *error;
+};
 int cover_check_db(const Engine *e);  // NH_OK, or NH_EINVAL: a geometry or a probing the pass does not support, named
 uint64_t cover_words(uint64_t ntext);
 uint64_t cover_mark_scratch_words(uint64_t n_seq);
@@ -318,6 +335,7 @@ uint64_t cover_line_blocks(uint64_t cap_ivl);
 hipError_t launch_cover_mark(Engine *e, const CoverArgs &c, hipStream_t stream);
 hipError_t launch_cover_intervals(const CoverIvlArgs &a, hipStream_t stream);
 hipError_t launch_cover_lines(const CoverLinesArgs &a, hipStream_t stream);
+hipError_t launch_cover_close(const CoverCloseArgs &a, hipStream_t stream);
 // buffers kept between the runs of a process (nh_run.hip: page-locked batch text; nh_gunzip.hip: the gzip reader's HBM and
 // staging): emptied when an engine is closed
 void run_cache_trim();

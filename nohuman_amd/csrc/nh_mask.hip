@@ -21,6 +21,12 @@
 //   k_mask_fill   FAST blocks only: 'N' over the sequence ranges of the classified fragments, written as pieces of one field
 // Every load stays inside the dwords that hold bytes of [0, ntext); every store inside [0, cap) of its mate's buffer.  A
 // record whose fields lie outside the text or a total above the buffer sets bit 8 of the engine's error word and writes nothing.
+//
+// --host-bases-only (MaskArgs::cover): k_mask_copy and k_mask_fill in their HB form.  A classified fragment's
+// sequence is the text's own, with 'N' where the bit of the SOURCE byte is set in the batch's cover bitmap: a sequence dword of
+// the output is text_dword() of its source position, whose four bits (not aligned with the output dword; they may lie in two words
+// of the bitmap) are expanded to a byte mask that selects 'N'.  The wave that writes a record counts its bits (popcount, one
+// reduction and two atomics a wave).  A bitmap load stays inside cover_words(ntext): a bit is read for a byte of the text alone.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -121,13 +127,64 @@ __global__ void __launch_bounds__(OB_THREADS) k_mask_scan(MaskArgs a) {
     }
 }
 
+// the cover bit of text byte p (p < ntext)
+__device__ __forceinline__ uint32_t cover_bit(const uint32_t *cover, uint64_t p) { return (cover[p >> 5] >> (uint32_t)(p & 31)) & 1u; }
+
+// the cover bits of the text bytes [src, src + 4), bit j: byte src + j (src + 3 < ntext: the second word holds the bit of src + 3)
+__device__ __forceinline__ uint32_t cover_bits4(const uint32_t *cover, uint64_t src) {
+    const uint64_t wi = src >> 5;
+    const uint32_t sh = (uint32_t)(src & 31);
+    uint32_t b = cover[wi] >> sh;
+    if (sh > 28) b |= cover[wi + 1] << (32 - sh);
+    return b & 0xFu;
+}
+
+// v with 'N' in the bytes whose bit of m (four bits) is set: bit j of m -> bit 8 j (the four shifted copies share no bit), -> byte j
+__device__ __forceinline__ uint32_t select_n(uint32_t v, uint32_t m) {
+    const uint32_t bytes = ((m * 0x00204081u) & 0x01010101u) * 0xFFu;
+    return (v & ~bytes) | (NNNN & bytes);
+}
+
+__device__ __forceinline__ uint32_t wave_total(uint32_t v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
+// base p of a classified fragment's sequence as it is written; HB: the lane's count of the bases written as 'N' goes up
+template <bool HB>
+__device__ __forceinline__ uint8_t masked_base(const MaskArgs &a, const MRec &r, uint64_t p, uint32_t &nmask) {
+    if (!HB) return (uint8_t)'N';
+    const uint32_t c = cover_bit(a.cover, r.s + p);
+    nmask += c;
+    return c ? (uint8_t)'N' : (uint8_t)a.text[r.s + p];
+}
+
+// ... and the four from p on (p + 4 <= r.slen)
+template <bool HB>
+__device__ __forceinline__ uint32_t masked_dword(const MaskArgs &a, const MRec &r, uint64_t p, uint32_t &nmask) {
+    if (!HB) return NNNN;
+    const uint32_t m = cover_bits4(a.cover, r.s + p);
+    nmask += (uint32_t)__popc(m);
+    return select_n(text_dword(a.text, r.s + p), m);
+}
+
+// HB: what the wave's records added -- the sequence bases of its classified fragments, those written as 'N' -- to the run's counters
+__device__ __forceinline__ void add_hb_counts(const MaskArgs &a, int lane, uint32_t host_bases, uint32_t nmask) {
+    const uint32_t n = wave_total(nmask);  // (a batch's text is below 4 GB: no sum here leaves 32 bits)
+    if (lane != 0) return;
+    if (host_bases) atomicAdd(a.hb, (unsigned long long)host_bases);
+    if (n) atomicAdd(a.hb + 1, (unsigned long long)n);
+}
+
 // byte p of the record's masked output (0 <= p < r.len)
-__device__ inline uint8_t mrec_byte(const MaskArgs &a, const MRec &r, bool fastq, uint64_t p) {
+template <bool HB>
+__device__ inline uint8_t mrec_byte(const MaskArgs &a, const MRec &r, bool fastq, uint64_t p, uint32_t &nmask) {
     if (p < r.hlen) return (uint8_t)a.text[r.h + p];
     p -= r.hlen;
     if (p == 0) return '\n';
     p -= 1;
-    if (p < r.slen) return r.cls ? (uint8_t)'N' : (uint8_t)a.text[r.s + p];
+    if (p < r.slen) return r.cls ? masked_base<HB>(a, r, p, nmask) : (uint8_t)a.text[r.s + p];
     p -= r.slen;
     if (!fastq) return '\n';
     if (p < 3) return p == 1 ? '+' : '\n';
@@ -158,6 +215,7 @@ __device__ inline bool fast_range(const MaskArgs &a, int m, uint64_t fb, uint64_
     return ok;
 }
 
+template <bool HB>
 __global__ void __launch_bounds__(OB_THREADS) k_mask_copy(MaskArgs a) {
     __shared__ uint64_t wsum[OB_WAVES];
     __shared__ uint64_t s_off[MB_FRAGS];
@@ -187,6 +245,7 @@ __global__ void __launch_bounds__(OB_THREADS) k_mask_copy(MaskArgs a) {
     block_offsets<MB_PER_THREAD>(s_off, wsum, [&](uint32_t fl) { return load_mrec(a, fb + fl, m, false).len; });
     const int lane = threadIdx.x & 63;
     const int gw = u * OB_WAVES + (threadIdx.x >> 6);
+    uint32_t host_bases = 0, nmask = 0;  // (HB: the wave's, the lane's)
     // wave gw of the block's MB_SUB * OB_WAVES writes the records gw, gw + MB_SUB * OB_WAVES, ... one after another
     for (int fl = gw; fl < MB_FRAGS; fl += MB_SUB * OB_WAVES) {
         const MRec r = load_mrec(a, fb + fl, m, false);
@@ -196,20 +255,24 @@ __global__ void __launch_bounds__(OB_THREADS) k_mask_copy(MaskArgs a) {
             if (lane == 0) atomicOr(a.error, ERR_MASK);
             continue;
         }
+        if (HB && r.cls) host_bases += r.slen;
         const uint64_t pB = (uint64_t)r.hlen + 1, pC = pB + r.slen + 3;
         wave_write(
-            out, o, r.len, lane, [&](uint64_t p) { return mrec_byte(a, r, fastq, p); },
+            out, o, r.len, lane, [&](uint64_t p) { return mrec_byte<HB>(a, r, fastq, p, nmask); },
             [&](uint64_t p, uint32_t *v) {
                 if (p + 4 <= r.hlen) *v = text_dword(a.text, r.h + p);
-                else if (p >= pB && p + 4 <= pB + r.slen) *v = r.cls ? NNNN : text_dword(a.text, r.s + (p - pB));
+                else if (p >= pB && p + 4 <= pB + r.slen) *v = r.cls ? masked_dword<HB>(a, r, p - pB, nmask) : text_dword(a.text, r.s + (p - pB));
                 else if (fastq && p >= pC && p + 4 <= pC + r.qlen) *v = text_dword(a.text, r.q + (p - pC));
                 else return false;
                 return true;
             });
     }
+    if (HB) add_hb_counts(a, lane, host_bases, nmask);
 }
 
-// FAST blocks: the copy wrote the raw text; 'N' over the sequences of the classified fragments
+// FAST blocks: the copy wrote the raw text; 'N' over the sequences of the classified fragments (HB: over their covered bases, the
+// others read from the text again)
+template <bool HB>
 __global__ void __launch_bounds__(OB_THREADS) k_mask_fill(MaskArgs a) {
     const int m = blockIdx.y;
     const uint64_t blk = blockIdx.x / MB_SUB;
@@ -222,19 +285,22 @@ __global__ void __launch_bounds__(OB_THREADS) k_mask_fill(MaskArgs a) {
     char *out = a.out[m];
     const int lane = threadIdx.x & 63;
     const int gw = u * OB_WAVES + (threadIdx.x >> 6);
+    uint32_t host_bases = 0, nmask = 0;  // (HB: the wave's, the lane's)
     for (int fl = gw; fl < MB_FRAGS; fl += MB_SUB * OB_WAVES) {
         const uint64_t f = fb + fl;
         if (f >= a.n || a.res[f].call == 0) continue;
         const MRec r = load_mrec(a, f, m, false);
         if (r.len == 0 || r.slen == 0 || r.h < h0 || r.h + r.len > h0 + L) continue;
+        if (HB) host_bases += r.slen;
         // (the sequence's first or last dword: the header's or the separator's bytes stay)
         wave_write(
-            out, base + (r.h - h0) + r.hlen + 1, r.slen, lane, [](uint64_t) { return (uint8_t)'N'; },
-            [](uint64_t, uint32_t *v) {
-                *v = NNNN;
+            out, base + (r.h - h0) + r.hlen + 1, r.slen, lane, [&](uint64_t p) { return masked_base<HB>(a, r, p, nmask); },
+            [&](uint64_t p, uint32_t *v) {
+                *v = masked_dword<HB>(a, r, p, nmask);
                 return true;
             });
     }
+    if (HB) add_hb_counts(a, lane, host_bases, nmask);
 }
 
 }  // namespace
@@ -246,8 +312,13 @@ hipError_t launch_mask(const MaskArgs &a, hipStream_t stream) {
     const dim3 grid((unsigned)a.nblk, (unsigned)a.mates), sub((unsigned)(a.nblk * MB_SUB), (unsigned)a.mates);
     hipLaunchKernelGGL(k_mask_sizes, grid, dim3(OB_THREADS), 0, stream, a);
     hipLaunchKernelGGL(k_mask_scan, dim3((unsigned)a.mates), dim3(OB_THREADS), 0, stream, a);
-    hipLaunchKernelGGL(k_mask_copy, sub, dim3(OB_THREADS), 0, stream, a);
-    hipLaunchKernelGGL(k_mask_fill, sub, dim3(OB_THREADS), 0, stream, a);
+    if (a.cover) {
+        hipLaunchKernelGGL(k_mask_copy<true>, sub, dim3(OB_THREADS), 0, stream, a);
+        hipLaunchKernelGGL(k_mask_fill<true>, sub, dim3(OB_THREADS), 0, stream, a);
+    } else {
+        hipLaunchKernelGGL(k_mask_copy<false>, sub, dim3(OB_THREADS), 0, stream, a);
+        hipLaunchKernelGGL(k_mask_fill<false>, sub, dim3(OB_THREADS), 0, stream, a);
+    }
     return hipGetLastError();
 }
 

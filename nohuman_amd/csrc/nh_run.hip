@@ -733,6 +733,9 @@ struct RunState {
     // the bytes of the lines, the kernel time of the mark pass and the two builders
     uint64_t cover_frags = 0, cover_ivls = 0, cover_bases = 0, cover_bytes = 0;
     double cover_kernel_ms = 0;
+    // host bases only: {host, masked, closed} bases as the devices counted them (nh_host_bases), fetched once at the end, and the
+    // sequence bases of the host fragments as the writer saw them
+    uint64_t hb_bases[3] = {0, 0, 0}, hb_host_written = 0;
     // BAM output (NOHUMAN_TRACE): the records and bytes the builder selected per output, its kernel time
     uint64_t bam_records[2] = {0, 0}, bam_bytes[2] = {0, 0};
     double bam_kernel_ms = 0;
@@ -1192,6 +1195,12 @@ struct RunRequest {
     // No path: nothing of this runs.
     nh_host_intervals *hi = nullptr;
     const char *hi_path = nullptr;
+    // given (nh_run_hostbases): the struct as the caller gave it -- check_request looks at its size --, and `hbo` where it enables the
+    // mode: a masked run whose mask builder reads the batch's cover bitmap -- the same mark pass as the host intervals', then the
+    // closing of the uncovered runs of at most hb->gap bases (nh_cover.hip) -- and writes 'N' over the covered bases of a host fragment
+    // alone (nh_mask.hip).  Not enabled: nothing of this runs.
+    nh_host_bases *hb = nullptr;
+    bool hbo = false;
 };
 
 // The request of an entry: its args, its extras (NULL where it has none, or was given none) or the bare human paths of
@@ -1199,7 +1208,7 @@ struct RunRequest {
 RunRequest make_request(RunRequest::Form form, const nh_run_args *a, const nh_run_extras *x, const char *h1 = nullptr, const char *h2 = nullptr,
                         uint32_t minq = 0, const char *rs_path = nullptr, nh_read_stats *rs_out = nullptr, nh_taxon_out *touts = nullptr,
                         uint32_t n_touts = 0, nh_minimizer_data *md = nullptr, nh_host_filter *hf = nullptr, nh_read_dust *rd = nullptr,
-                        nh_host_intervals *hi = nullptr) {
+                        nh_host_intervals *hi = nullptr, nh_host_bases *hb = nullptr) {
     static const char *const names[] = {"nh_run", "nh_run_split", "nh_run_mask", "nh_run_ex"};
     RunRequest r;
     r.form = form == RunRequest::RUN && x ? RunRequest::EX : form;
@@ -1212,6 +1221,7 @@ RunRequest make_request(RunRequest::Form form, const nh_run_args *a, const nh_ru
     r.hf = host_filter_given(hf) ? hf : nullptr;  // (no taxid listed: the run of nh_run_mdata, and the struct is not looked at again)
     r.rd = rd, r.dust = rd && rd->struct_size >= sizeof(nh_read_dust) && rd->enable != 0;
     r.hi = hi, r.hi_path = hi && hi->struct_size >= sizeof(nh_host_intervals) ? hi->path : nullptr;
+    r.hb = hb, r.hbo = hb && hb->struct_size >= sizeof(nh_host_bases) && hb->enable != 0;
     return r;
 }
 
@@ -1394,6 +1404,19 @@ static int check_cover_args(const RunRequest &r) {
     return check_files(r, F_COVER);
 }
 
+// nh_run_hostbases' own arguments: the struct, a masked run, the gap
+static int check_hostbases_args(const RunRequest &r) {
+    const nh_host_bases *hb = r.hb;
+    if (!hb) return NH_OK;
+    if (hb->struct_size < sizeof(nh_host_bases))
+        return set_error(NH_EINVAL, "nh_run_hostbases: struct_size %u is smaller than nh_host_bases (%zu bytes)", hb->struct_size, sizeof(nh_host_bases));
+    if (!r.hbo) return NH_OK;
+    if (!r.a) return set_error(NH_EINVAL, "nh_run_hostbases: null arguments");
+    if (!r.mask) return set_error(NH_EINVAL, "nh_run_hostbases: enable is set without a masked run (extras->mask): the mode writes every read, host bases as N");
+    if (hb->gap > NH_HOST_GAP_MAX) return set_error(NH_EINVAL, "nh_run_hostbases: gap %u is above NH_HOST_GAP_MAX (%d)", hb->gap, NH_HOST_GAP_MAX);
+    return NH_OK;
+}
+
 // The container of the record outputs: a codec there is none of, and what BAM output (NH_CODEC_BAM: the selected records of a BAM
 // in1, copied) does not go with -- a second input, a masked run, per-taxon outputs (the last two: not built yet), an in1 that is
 // no BAM file.  (A request without arguments is refused by its entry.)
@@ -1413,7 +1436,7 @@ static int check_out_codec(const RunRequest &r) {
 
 // Every entry's checks, in one order: the host selection's own, the minimum base quality (the highest printable quality is '~',
 // Phred 93), the read DUST's struct, the extras (the mask or the human outputs, then the read lists), the read statistics' table, the selectors, the
-// minimizer data, the host intervals, the container.  What an entry cannot ask for is not set in its request and checks nothing.
+// minimizer data, the host intervals, the host bases, the container.  What an entry cannot ask for is not set in its request and checks nothing.
 int check_request(const RunRequest &r) {
     int rc = check_host_filter(r.hf);
     if (!rc && r.minq > 93) rc = set_error(NH_EINVAL, "minimum base quality %u is not in 0..93 (Phred+33)", r.minq);
@@ -1424,6 +1447,7 @@ int check_request(const RunRequest &r) {
     if (!rc) rc = check_taxon_args(r);
     if (!rc) rc = check_mdata_args(r);
     if (!rc) rc = check_cover_args(r);
+    if (!rc) rc = check_hostbases_args(r);
     if (!rc) rc = check_out_codec(r);
     return rc;
 }
@@ -1521,6 +1545,7 @@ struct RunBuffers {
     uint8_t *host_of = nullptr;
     unsigned long long *hcnt = nullptr;
     unsigned long long *racc = nullptr;  // read statistics: one block of four accumulators, zeroed with min_len all-ones
+    unsigned long long *hbcnt = nullptr; // host bases only: {host, masked, closed} bases the mask builder and the closing add to
     // minimizer data: one zeroed bitmap (a bit a cell) and one array of hit groups per node
     uint32_t *marks = nullptr;
     unsigned long long *groups = nullptr;
@@ -1528,9 +1553,9 @@ struct RunBuffers {
     RunBuffers(const RunBuffers &) = delete;
     RunBuffers &operator=(const RunBuffers &) = delete;
     ~RunBuffers() {
-        if (!counters && !bin_of && !host_of && !hcnt && !racc && !marks && !groups) return;
+        if (!counters && !bin_of && !host_of && !hcnt && !racc && !marks && !groups && !hbcnt) return;
         (void)dev_set(device);
-        for (void *p : {(void *)host_of, (void *)hcnt, (void *)marks, (void *)groups, (void *)counters, (void *)racc, (void *)bin_of})
+        for (void *p : {(void *)host_of, (void *)hcnt, (void *)marks, (void *)groups, (void *)counters, (void *)racc, (void *)bin_of, (void *)hbcnt})
             if (p) (void)hipFree(p);
     }
 };
@@ -1538,7 +1563,7 @@ struct RunBuffers {
 // (hipMemcpy / hipMemset block: the tables and the zeroes are in place before the slots' streams, which do not wait for the legacy
 // stream, carry the first batch)
 static int alloc_run_buffers(RunBuffers &b, const Engine *e, const std::vector<uint8_t> &bin_of, const std::vector<uint8_t> &host_of, bool rst,
-                             size_t md_mark_bytes, size_t md_nodes, bool mdt) {
+                             size_t md_mark_bytes, size_t md_nodes, bool mdt, bool hbo) {
     b.device = e->device;
     const size_t nb = (CNT_N + 12) * sizeof(uint64_t);  // (+12: the words of the instrumented kernel variant)
     if (dev_set(e->device) != hipSuccess || dev_malloc((void **)&b.counters, nb) != hipSuccess || hipMemset(b.counters, 0, nb) != hipSuccess)
@@ -1557,6 +1582,9 @@ static int alloc_run_buffers(RunBuffers &b, const Engine *e, const std::vector<u
         if (dev_malloc((void **)&b.racc, sizeof init) != hipSuccess || hipMemcpy(b.racc, init, sizeof init, hipMemcpyHostToDevice) != hipSuccess)
             return set_error(NH_EDEVICE, "cannot allocate the read statistics' accumulators on device %d", e->device);
     }
+    if (hbo && (dev_set(e->device) != hipSuccess || dev_malloc((void **)&b.hbcnt, 24) != hipSuccess || hipMemset(b.hbcnt, 0, 24) != hipSuccess ||
+                hipDeviceSynchronize() != hipSuccess))
+        return set_error(NH_EDEVICE, "cannot allocate the host bases' counters on device %d", e->device);
     if (mdt) {
         if (dev_malloc((void **)&b.marks, std::max<size_t>(md_mark_bytes, 4)) != hipSuccess ||
             dev_malloc((void **)&b.groups, std::max<size_t>(md_nodes, 1) * 8) != hipSuccess)
@@ -1605,6 +1633,25 @@ static void collect_host_counts(const std::vector<RunBuffers> &dbuf, RunState &r
         char msg[200];
         snprintf(msg, sizeof msg, "host filter: the devices counted %llu host / %llu spared fragments, the writer %llu / %llu", (unsigned long long)dev_host[0],
                  (unsigned long long)dev_host[1], (unsigned long long)rs.host_frags, (unsigned long long)rs.spared_frags);
+        rs.fail(NH_EDEVICE, msg);
+    }
+}
+
+// host bases only: the devices' {host, masked, closed} bases summed into the run's
+static void collect_hostbases(const std::vector<RunBuffers> &dbuf, RunState &rs) {
+    for (size_t g = 0; g < dbuf.size() && rs.err_code == NH_OK; g++) {
+        unsigned long long c[3] = {0, 0, 0};
+        if (dev_set(dbuf[g].device) != hipSuccess || hipMemcpy(c, dbuf[g].hbcnt, 24, hipMemcpyDeviceToHost) != hipSuccess) {
+            rs.fail(NH_EDEVICE, "reading the host bases' counters failed");
+            break;
+        }
+        for (int k = 0; k < 3; k++) rs.hb_bases[k] += c[k];
+    }
+    // (the bases of the fragments the writer saw as host are the checker of what the builder counted)
+    if (rs.err_code == NH_OK && rs.hb_bases[0] != rs.hb_host_written) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "host bases only: the devices counted %llu host bases, the writer %llu", (unsigned long long)rs.hb_bases[0],
+                 (unsigned long long)rs.hb_host_written);
         rs.fail(NH_EDEVICE, msg);
     }
 }
@@ -1745,6 +1792,9 @@ struct RunShape {
     bool taxa, qm, rst, mdt, hsel;
     bool dust;         // --dust-reads: k_rdust in front of the classifier
     bool cover;        // --host-intervals: k_cover_mark and the two builders behind the classifier
+    bool hbo;          // --host-bases-only: k_cover_mark (one pass for both), the closing (gap > 0), the mask builder on the bitmap
+    uint32_t gap;
+    bool mark;         // the batch's cover bitmap is made (cover or hbo)
     bool idl;          // a builder prints mate 1's id: the id lengths go to the device (the read lists, the host intervals)
     bool qtext;        // the classifier and the minimizer data's marks read the slot's masked text, not the batch's (qm or dust)
     bool want_rec;     // a kernel of the run reads the record table
@@ -1766,6 +1816,7 @@ struct RunShape {
         dust = r.dust, qtext = qm || dust;
         mdt = r.md && (r.md->in_report || r.md->table || r.md->taxa);
         cover = r.hi_path != nullptr, idl = lists || cover;
+        hbo = r.hbo, gap = hbo ? r.hb->gap : 0, mark = cover || hbo;
         want_rec = split || mask || lists || qm || rst || taxa || cover;
         gzip_family = a->out_codec == NH_CODEC_GZIP || a->out_codec == NH_CODEC_BGZF || bamout;
         G = (int)n_engines;
@@ -1893,7 +1944,7 @@ struct Pipeline {
         if (sh.taxa) builders.push_back({&Slot::taxon, 4 * (size_t)sh.K, &RunState::taxon_kernel_ms});
         if (sh.mask) builders.push_back({&Slot::mask, 4, &RunState::mask_kernel_ms});
         if (sh.lists) builders.push_back({&Slot::lists, 4, &RunState::list_kernel_ms});
-        if (sh.cover) builders.push_back({&Slot::cover, 4, &RunState::cover_kernel_ms});
+        if (sh.mark) builders.push_back({&Slot::cover, 4, &RunState::cover_kernel_ms});
         if (sh.qm) passes.push_back({&Slot::qev, &RunState::qmask_kernel_ms});
         if (sh.dust) passes.push_back({&Slot::duev, &RunState::dust_kernel_ms});
         if (sh.rst) passes.push_back({&Slot::rev, &RunState::rstats_kernel_ms});
@@ -2323,6 +2374,7 @@ struct Pipeline {
             built_sink(ma, s.mask, mates, s);
             ma.total = s.mask.d_total = ma.blk + 2 * ma.nblk;
             ma.fast = (uint32_t *)(ma.total + 4);
+            if (sh.hbo) ma.cover = s.d_cover, ma.hb = dbuf[(size_t)b.dev_index].hbcnt;  // (build_cover's, in front of this on the stream)
             timed_launch(rs, s.stream, s.mask.ev, "mask builder", [&] { return launch_mask(ma, s.stream); });
         } else {
             for (int m = 0; m < mates && !*rc; m++) {
@@ -2333,6 +2385,8 @@ struct Pipeline {
             rs.mask_nblk += mask_blocks(b.n) * (uint64_t)mates;
             for (int m = 0; m < mates; m++) rs.mask_fast += s.mask.h_total[2 + m];
             for (size_t i = 0; i < b.n; i++) rs.mask_masked += (s.host_res()[i].call != 0) * (uint64_t)mates;
+            for (size_t i = 0; sh.hbo && i < b.n; i++)
+                if (s.host_res()[i].call != 0) rs.hb_host_written += (uint64_t)b.h1->recs[b.off1 + i].slen + (b.h2 ? b.h2->recs[b.off2 + i].slen : 0);
         }
     }
 
@@ -2431,12 +2485,13 @@ struct Pipeline {
         const int mates = sh.mates;
         const size_t nseq = b.n * (size_t)mates;
         const size_t pass_words = (size_t)std::max(cover_mark_scratch_words(nseq), cover_intervals_scratch_words(nseq));
+        // (--host-bases-only without the report: the bitmap and the mark pass's scratch alone, no record, no line)
         if (step == RESERVE) {
             size_t nbytes = 0;
-            const size_t nrec = cover_max_records(b, &nbytes);
+            const size_t nrec = sh.cover ? cover_max_records(b, &nbytes) : 0;
             const size_t out_cap[2] = {nbytes + 64, (nrec + 1) * 12};
             if (!*rc) *rc = slot_reserve_rec(s, nseq);
-            if (!*rc) *rc = slot_reserve_idl(s, b.n);
+            if (!*rc && sh.cover) *rc = slot_reserve_idl(s, b.n);
             // (the scratch: the larger of the mark pass's and the interval builder's, the records' total, the line builder's block sums and totals)
             if (!*rc) *rc = built_reserve(s.cover, pass_words + 1 + 3 * (size_t)cover_line_blocks(nrec) + 4, out_cap, 2, "host-interval buffers");
             const size_t cw = (size_t)cover_words(b.ntext());
@@ -2448,7 +2503,7 @@ struct Pipeline {
             }
         } else if (step == LAUNCH) {
             const uint64_t ntext = b.ntext();
-            const size_t nrec = cover_max_records(b, nullptr);
+            const size_t nrec = sh.cover ? cover_max_records(b, nullptr) : 0;
             int *const d_error = s.e->d_error + LAUNCH_SLOTS;
             uint64_t *const scratch = (uint64_t *)s.cover.d_blk;
             uint64_t *const n_ivl = scratch + pass_words;
@@ -2469,11 +2524,17 @@ struct Pipeline {
             la.blk = n_ivl + 1, la.nblk = cover_line_blocks(nrec);
             la.total = s.cover.d_total = la.blk + 3 * la.nblk;
             la.error = d_error;
+            CoverCloseArgs cl{};
+            cl.cover = s.d_cover, cl.ntext = ntext, cl.seq_off = ca.seq_off, cl.seq_len = ca.seq_len, cl.n_seq = nseq;
+            cl.res = (const nh_result *)(sh.hsel ? s.d_hres : s.d_res), cl.mates = mates;  // (the host fragments alone: closed_bases counts what is masked)
+            cl.gap = sh.gap, cl.closed = sh.hbo ? dbuf[(size_t)b.dev_index].hbcnt + 2 : nullptr, cl.error = d_error;
             timed_launch(rs, s.stream, s.cover.ev, "host intervals", [&] {
                 hipError_t he = hipMemsetAsync(s.d_cover, 0, (size_t)cover_words(ntext) * 4, s.stream);
                 if (he == hipSuccess) he = launch_cover_mark(s.e, ca, s.stream);
-                if (he == hipSuccess) he = launch_cover_intervals(ia, s.stream);
-                if (he == hipSuccess) he = launch_cover_lines(la, s.stream);
+                if (he == hipSuccess && sh.cover) he = launch_cover_intervals(ia, s.stream);
+                if (he == hipSuccess && sh.cover) he = launch_cover_lines(la, s.stream);
+                if (he == hipSuccess && !sh.cover) he = hipMemsetAsync(la.total, 0, 4 * sizeof(uint64_t), s.stream);  // (the totals go back all the same)
+                if (he == hipSuccess && sh.hbo) he = launch_cover_close(cl, s.stream);  // (behind the report: the BED is the coverage before the closing)
                 return he;
             });
         } else {
@@ -2597,7 +2658,7 @@ struct Pipeline {
         if (sh.mask) build_mask(RESERVE, s, b, nullptr, &rc);
         if (sh.bamout) build_bam(RESERVE, s, b, nullptr, &rc);
         if (sh.lists) build_lists(RESERVE, s, b, nullptr, &rc);
-        if (sh.cover) build_cover(RESERVE, s, b, nullptr, &rc);
+        if (sh.mark) build_cover(RESERVE, s, b, nullptr, &rc);
         if (!rc && sh.qm) rc = slot_reserve_qmask(s, b.ntext(), b.n * (size_t)sh.mates);
         if (!rc && sh.dust) rc = slot_reserve_dust(s, b.ntext(), b.n * (size_t)sh.mates);
         if (!rc && sh.rst) rc = slot_reserve_rec(s, b.n * (size_t)sh.mates);
@@ -2690,7 +2751,7 @@ struct Pipeline {
 
     // the batch's launches on the slot's stream, in this order: the quality mask, the read DUST (on a copy of the text where no
     // quality mask has written the sequences), the classifier, the host filter, the read
-    // statistics, the minimizer data's marks, then the builders -- lists, host intervals, split, BAM out, per-taxon, mask.  Each goes out only
+    // statistics, the minimizer data's marks, then the builders -- lists, host intervals (the cover bitmap, its closing), split, BAM out, per-taxon, mask.  Each goes out only
     // while the run has not failed.
     void launch(Slot &s, const Batch &b, uint64_t nbases, bool staged) {
         const int mates = sh.mates;
@@ -2741,7 +2802,7 @@ struct Pipeline {
             });
         int none = NH_OK;  // (a launch fails the run itself)
         if (!rs.failed() && sh.lists) build_lists(LAUNCH, s, b, nullptr, &none);
-        if (!rs.failed() && sh.cover) build_cover(LAUNCH, s, b, nullptr, &none);
+        if (!rs.failed() && sh.mark) build_cover(LAUNCH, s, b, nullptr, &none);
         if (!rs.failed() && sh.split) build_human(LAUNCH, s, b, nullptr, &none);
         if (!rs.failed() && sh.bamout) build_bam(LAUNCH, s, b, nullptr, &none);
         if (!rs.failed() && sh.taxa) build_taxon(LAUNCH, s, b, nullptr, &none);
@@ -2822,6 +2883,10 @@ static void print_run_trace(const RunShape &sh, RunState &rs, const StageClock &
         fprintf(stderr, "[nohuman trace] host-intervals: %llu intervals in %llu fragments, %llu bases covered, %llu bytes built on device; kernels %.3f ms\n",
                 (unsigned long long)rs.cover_ivls, (unsigned long long)rs.cover_frags, (unsigned long long)rs.cover_bases,
                 (unsigned long long)rs.cover_bytes, rs.cover_kernel_ms);
+    if (sh.hbo)
+        fprintf(stderr, "[nohuman trace] host-bases-only: %llu of %llu host bases masked, %llu by closing; gap %u, cover kernels %.3f ms, mask builder kernels %.3f ms\n",
+                (unsigned long long)rs.hb_bases[1], (unsigned long long)rs.hb_bases[0], (unsigned long long)rs.hb_bases[2], sh.gap, rs.cover_kernel_ms,
+                rs.mask_kernel_ms);
     if (sh.qm)
         fprintf(stderr, "[nohuman trace] qmask: Q %u, %llu of %llu bases masked, kernel %.3f ms\n", sh.minq,
                 (unsigned long long)rs.qmask_masked, (unsigned long long)rs.total_bases, rs.qmask_kernel_ms);
@@ -2965,10 +3030,11 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
         if ((rc = host_table(engines[0], r.hf, host_of))) return rc;
         r.hf->host_fragments = r.hf->spared_fragments = 0;
     }
-    for (size_t g = 0; sh.cover && g < engines.size(); g++)
+    for (size_t g = 0; sh.mark && g < engines.size(); g++)
         if ((rc = cover_check_db(engines[g]))) return rc;
     if (r.rd) r.rd->masked_bases = 0;
     if (sh.cover) r.hi->fragments = r.hi->intervals = r.hi->covered_bases = 0;
+    if (sh.hbo) r.hb->host_bases = r.hb->masked_bases = r.hb->closed_bases = 0;
     if (sh.split || sh.lists || sh.taxa || sh.cover)
         for (Engine *e : engines)
             if ((rc = ensure_device_external(e))) return rc;
@@ -2993,7 +3059,7 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
     std::vector<nh_read_class> racc;  // read statistics: the devices' blocks summed: [class][mate]
     rs.d_run_counters.assign((size_t)sh.G, nullptr);
     for (int g = 0; g < sh.G; g++) {
-        if ((rc = alloc_run_buffers(dbuf[g], engines[g], bin_of, host_of, sh.rst, md_mark_bytes, engines[0]->external.size(), sh.mdt))) return rc;
+        if ((rc = alloc_run_buffers(dbuf[g], engines[g], bin_of, host_of, sh.rst, md_mark_bytes, engines[0]->external.size(), sh.mdt, sh.hbo))) return rc;
         rs.d_run_counters[g] = dbuf[g].counters;
     }
     if ((rc = p.create_slots())) return rc;
@@ -3006,6 +3072,7 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
     uint64_t dev_host[2] = {0, 0};  // host selection: the devices' {host, spared} fragments summed
     if (sh.hsel) collect_host_counts(dbuf, rs, dev_host);
     if (sh.rst) collect_rstats(dbuf, rs, racc);
+    if (sh.hbo) collect_hostbases(dbuf, rs);
     if (sh.mdt) collect_mdata(dbuf, rs, md_mark_bytes, mdn, &md_count_ms);
     for (auto &s : p.slots) slot_free(s);
     if (sh.trace_run)
@@ -3031,6 +3098,7 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
     if (sh.hsel) r.hf->host_fragments = rs.host_frags, r.hf->spared_fragments = rs.spared_frags;
     if (sh.dust) r.rd->masked_bases = rs.dust_masked;
     if (sh.cover) r.hi->fragments = rs.cover_frags, r.hi->intervals = rs.cover_ivls, r.hi->covered_bases = rs.cover_bases;
+    if (sh.hbo) r.hb->host_bases = rs.hb_bases[0], r.hb->masked_bases = rs.hb_bases[1], r.hb->closed_bases = rs.hb_bases[2];
     if (sh.mdt && (rc = report_mdata(mdview, mdn, r.md))) return rc;
     if (stats) {
         nh_stats st;
@@ -3120,6 +3188,15 @@ int nh_run_engine_intervals(nh_engine *e, const nh_run_args *args, const nh_run_
                             nh_host_filter *hf, nh_read_dust *rd, nh_host_intervals *hi, nh_stats *stats) {
     return run_on_engine(
         e, nh::make_request(nh::RunRequest::RUN, args, extras, nullptr, nullptr, min_base_quality, read_stats_path, read_stats, outs, n_outs, md, hf, rd, hi),
+        stats);
+}
+
+// (hb NULL, or its enable 0: the request is nh_run_engine_intervals')
+int nh_run_engine_hostbases(nh_engine *e, const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality,
+                            const char *read_stats_path, nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs, nh_minimizer_data *md,
+                            nh_host_filter *hf, nh_read_dust *rd, nh_host_intervals *hi, nh_host_bases *hb, nh_stats *stats) {
+    return run_on_engine(
+        e, nh::make_request(nh::RunRequest::RUN, args, extras, nullptr, nullptr, min_base_quality, read_stats_path, read_stats, outs, n_outs, md, hf, rd, hi, hb),
         stats);
 }
 
@@ -3402,6 +3479,15 @@ int nh_run_intervals(const nh_run_args *args, const nh_run_extras *extras, uint3
                      nh_host_intervals *hi, nh_stats *stats) {
     return run_standalone(
         nh::make_request(nh::RunRequest::RUN, args, extras, nullptr, nullptr, min_base_quality, read_stats_path, read_stats, outs, n_outs, md, hf, rd, hi),
+        stats);
+}
+
+// (hb NULL, or its enable 0: the request is nh_run_intervals')
+int nh_run_hostbases(const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality, const char *read_stats_path,
+                     nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs, nh_minimizer_data *md, nh_host_filter *hf, nh_read_dust *rd,
+                     nh_host_intervals *hi, nh_host_bases *hb, nh_stats *stats) {
+    return run_standalone(
+        nh::make_request(nh::RunRequest::RUN, args, extras, nullptr, nullptr, min_base_quality, read_stats_path, read_stats, outs, n_outs, md, hf, rd, hi, hb),
         stats);
 }
 

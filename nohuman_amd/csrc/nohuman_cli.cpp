@@ -254,6 +254,9 @@ struct Args {
     bool dust_reads = false;        // classify every read with its low-complexity stretches as ambiguous bases (nh_run_dust)
     std::string read_stats;         // the read statistics table (nh_run_rstats)
     std::string host_intervals;     // the BED file of the bases that host k-mers cover (nh_run_intervals)
+    bool host_bases_only = false;   // a masked run that writes N over the bases that host k-mers cover alone (nh_run_hostbases)
+    unsigned host_gap = 0;          // ... and over the uncovered runs of at most so many bases between two of them
+    bool has_host_gap = false;
     bool report_minimizer_data = false;  // kraken2's flag: two more columns in the report (nh_run_mdata)
     std::string minimizer_table;         // the minimizer table (nh_run_mdata)
     // per-taxon outputs (nh_run_taxa): the selectors in the order given -- taxid (0: `other`), the path as given ('#' in it: the mate)
@@ -310,6 +313,12 @@ static void usage(FILE *f) {
           "maximal run of bases covered by k-mers whose minimizer is in the database (with --host-taxid: in the host clades), 0-based and half-open, in input order. Plain text, never "
           "compressed; no other output changes. With --minimum-base-quality / --dust-reads the masked bases are not covered. For BAM input the coordinates are those of the FASTQ "
           "record the read is transcoded to: a reverse-strand record is counted on its reverse complement\n"
+          // (the help keeps a single line that mentions the masked run's own flag: these two say "a masked run")
+          "      --host-bases-only        Make the run a masked run that writes N only over the bases of a human read that host k-mers cover (the intervals of --host-intervals) and keeps "
+          "the rest of the read: every read is written, in input order. Not with -H\n"
+          "      --host-gap <INT>         With --host-bases-only: also write N over an uncovered run of at most INT bases that lies between two covered bases of the same read "
+          "(each mate on its own; never a run that touches an end of the read). 34 (k - 1) is recommended for noisy long reads, whose sequencing errors break a host stretch "
+          "into pieces with leftovers too short to hold a k-mer (0-4096) [default: 0]\n"
           "  -k, --kraken-output <FILE>   Write the Kraken2 read classification output to a file\n"
           "  -r, --kraken-report <FILE>   Write the Kraken2 report with aggregate counts/clade to file\n"
           "      --report-minimizer-data  Report, per clade, the minimizer hits of the reads and how many distinct minimizers they were, as columns 4 and 5 of the Kraken2 report "
@@ -433,6 +442,16 @@ static Args parse_args(int argc, char **argv) {
         else if (s == "--human-ids") a.human_ids = val();
         else if (s == "--read-stats") a.read_stats = val();
         else if (s == "--host-intervals") a.host_intervals = val();
+        else if (s == "--host-bases-only") a.host_bases_only = true;
+        else if (s == "--host-gap") {
+            std::string t = val();
+            char *end;
+            errno = 0;
+            long n = strtol(t.c_str(), &end, 10);
+            if (*end || t.empty() || t[0] == ' ' || t[0] == '\t') arg_error("invalid value '%s' for '--host-gap <INT>': invalid digit found in string", t.c_str());
+            if (errno || n < 0 || n > NH_HOST_GAP_MAX) arg_error("invalid value '%s' for '--host-gap <INT>': %s is not in 0..=%d", t.c_str(), t.c_str(), NH_HOST_GAP_MAX);
+            a.host_gap = (unsigned)n, a.has_host_gap = true;
+        }
         else if (s == "--report-minimizer-data") a.report_minimizer_data = true;
         else if (s == "--minimizer-table") a.minimizer_table = val();
         else if (s == "--taxon-out") {
@@ -518,7 +537,7 @@ static Args parse_args(int argc, char **argv) {
                              : !a.minimizer_table.empty() ? "--minimizer-table" : a.has_type ? "--output-type"
                              : a.bgzf ? "--bgzf" : a.bam_out ? "--bam-out" : a.mask ? "--mask" : a.human ? "--human" : !a.taxon_out.empty() ? "--taxon-out"
                              : !a.host_taxids.empty() ? "--host-taxid" : !a.keep_taxids.empty() ? "--keep-taxid" : a.dust_reads ? "--dust-reads"
-                             : !a.host_intervals.empty() ? "--host-intervals" : nullptr;
+                             : !a.host_intervals.empty() ? "--host-intervals" : a.host_bases_only ? "--host-bases-only" : a.has_host_gap ? "--host-gap" : nullptr;
         if (out_flag) arg_error("the argument '--build-db <DIR>' cannot be used with '%s'", out_flag);
         if (a.has_extend_db) {
             if (a.capacity) arg_error("the argument '--extend-db <DIR>' cannot be used with '--capacity <INT>': an extension keeps the capacity of its base");
@@ -542,6 +561,9 @@ static Args parse_args(int argc, char **argv) {
     if (a.input.empty() && !a.check && !a.download && !a.list)
         arg_error("the following required arguments were not provided:\n  <INPUT>...");
     if (a.mask && a.human) arg_error("the argument '--mask' cannot be used with '--human'");
+    if (a.host_bases_only && a.human) arg_error("the argument '--host-bases-only' cannot be used with '--human'");
+    if (a.has_host_gap && !a.host_bases_only) arg_error("the argument '--host-gap <INT>' needs '--host-bases-only': it closes the gaps between the bases that run masks");
+    if (a.host_bases_only) a.mask = true;  // (a masked run in everything else)
     // BAM output (--bam-out): the kept records of ONE BAM input, copied; its container is BGZF, whatever -F or the names say
     if (a.bam_out) {
         if (a.has_type) arg_error("the argument '--bam-out' cannot be used with '--output-type <FORMAT>': a BAM file is its own container");
@@ -1059,7 +1081,14 @@ int main(int argc, char **argv) {
     memset(&hi, 0, sizeof hi);
     hi.struct_size = (uint32_t)sizeof hi;
     hi.path = args.host_intervals.empty() ? nullptr : bpart.c_str();
-    const int run_rc = hi.path ? nh_run_intervals(&ra, lists || args.mask || split ? &rx : nullptr, args.min_base_quality,
+    nh_host_bases hbs;
+    memset(&hbs, 0, sizeof hbs);
+    hbs.struct_size = (uint32_t)sizeof hbs;
+    hbs.enable = args.host_bases_only ? 1 : 0, hbs.gap = args.host_gap;
+    const int run_rc = hbs.enable ? nh_run_hostbases(&ra, &rx, args.min_base_quality, args.read_stats.empty() ? nullptr : spart.c_str(), nullptr,
+                                                     touts.empty() ? nullptr : touts.data(), (uint32_t)touts.size(), md.in_report || md.table ? &md : nullptr,
+                                                     hsel ? &hf : nullptr, &rd, hi.path ? &hi : nullptr, &hbs, &st)
+                       : hi.path ? nh_run_intervals(&ra, lists || args.mask || split ? &rx : nullptr, args.min_base_quality,
                                                   args.read_stats.empty() ? nullptr : spart.c_str(), nullptr, touts.empty() ? nullptr : touts.data(),
                                                   (uint32_t)touts.size(), md.in_report || md.table ? &md : nullptr, hsel ? &hf : nullptr, &rd, &hi, &st)
                        : args.dust_reads ? nh_run_dust(&ra, lists || args.mask || split ? &rx : nullptr, args.min_base_quality,
@@ -1111,6 +1140,9 @@ int main(int argc, char **argv) {
         DEBUG("Host intervals: %llu intervals in %llu reads, %llu bases covered by host k-mers (%.2f %% of the bases)", (unsigned long long)hi.intervals,
               (unsigned long long)hi.fragments, (unsigned long long)hi.covered_bases,
               st.total_bases ? 100.0 * (double)hi.covered_bases / (double)st.total_bases : 0.0);
+    if (hbs.enable)
+        DEBUG("Host bases only: %llu of %llu bases of the human reads written as N, %llu of them by closing gaps of at most %u bases",
+              (unsigned long long)hbs.masked_bases, (unsigned long long)hbs.host_bases, (unsigned long long)hbs.closed_bases, hbs.gap);
     if (g_verbose) {  // a BAM input: what the reader made of its records (the host side of the reader once more: nh_bam_scan)
         nh_bam_info bi;
         memset(&bi, 0, sizeof bi);
