@@ -264,17 +264,32 @@ int nh_run(const nh_run_args *args, nh_stats *stats);
  * Needs no GPU. */
 int nh_fastx_scan(const char *path, uint64_t *n_records, uint64_t *n_bases, uint64_t *digest);
 /*
- * BAM input.  in1 of every nh_run* may be a BAM file -- unaligned (ONT, PacBio HiFi, uBAM) or aligned, single-end: a file whose
+ * BAM input.  in1 of every nh_run* may be a BAM file -- unaligned (ONT, PacBio HiFi, uBAM) or aligned, single-end or collated
+ * pairs (below): a file whose
  * first gzip member carries the BGZF extra field and whose inflated stream begins "BAM\1"; anything else is read as before.  Its
  * records are transcoded on the GPU to the canonical FASTQ `samtools fastq` would write (as far as that is recalled: DESIGN.md
  * 6.16) and everything behind the reader runs on that text: "@name\nSEQ\n+\nQUAL\n", bases from "=ACMGRSVTWYHKDBN", qualities
  * + 33 (absent qualities, first byte 0xFF: every quality '"'), reverse-strand records (flag 0x10) reverse-complemented with their
  * qualities reversed, no tags in the header (the tags survive only in BAM output, NH_CODEC_BAM below).  Secondary and supplementary records (0x100, 0x800) and records without bases are
- * skipped; a paired record (0x1) fails the run with NH_EIO, as every malformed record does, with the record's ordinal in the
- * message.  A BAM in1 with an in2, or a BAM in2, is NH_EINVAL before any device is touched.
+ * skipped.  A BAM in1 with an in2, or a BAM in2, is NH_EINVAL before any device is touched.
+ *
+ * Paired BAM.  A file is paired iff its first kept record has flag 0x1 (a file without a kept record is single-end).  In a
+ * single-end file a later 0x1 record fails the run with NH_EIO, as every malformed record does, with the record's ordinal and
+ * name in the message.  In a paired file the kept records are taken two at a time, in file order, skipped records in between
+ * stepped over: both have 0x1, exactly one has 0x40 and the other 0x80, their names are equal byte for byte; the 0x40 record is
+ * mate 1 whichever comes first (`samtools collate` promises no order).  Anything else -- a kept record without 0x1, with both
+ * or neither of 0x40 / 0x80, two records of one mate, two names (the file is not collated), a last record without a partner, a
+ * record whose mate is empty and therefore skipped -- is NH_EIO with the record's ordinal and name.  Each mate is transcoded as
+ * a single-end record is and its name written as it is, without "/1" or "/2" (`samtools fastq -n -1 -2`, as far as recalled).
+ * The run is, in every output, the run on the two FASTQ files the mates transcode to: it is a paired run with in2 NULL, and
+ * wants out2, human_out2 and the selectors' out2 as one with in2 does (NH_EINVAL without them), except with NH_CODEC_BAM, where
+ * one BAM holds both mates and out2 / human_out2 are NH_EINVAL.  nh_bam_paired: 1 for a paired BAM file, 0 for anything else.
  *
  * nh_bam_scan: the host side alone, no device -- the counts of a BAM file and nh_fastx_scan's digest of the FASTQ it transcodes
- * to.  NH_EINVAL: a null argument, a struct_size below the struct's, a file that is no BAM; NH_EIO: a malformed one.
+ * to (a paired file: of its kept records in file order; the counts cover all kept records).  NH_EINVAL: a null argument, a
+ * struct_size below the struct's, a file that is no BAM; NH_EIO: a malformed one.
+ * nh_bam_scan_pairs: the same pass, and what a paired file has besides -- the pairs, each mate's bases and nh_fastx_scan's digest
+ * of each mate's FASTQ (a single-end file: paired 0, no pairs, the digests of empty files).
  */
 typedef struct nh_bam_info {
     uint32_t struct_size;          /* sizeof(nh_bam_info), set by the caller */
@@ -289,6 +304,15 @@ typedef struct nh_bam_info {
     uint64_t digest;
 } nh_bam_info;
 int nh_bam_scan(const char *path, uint32_t threads, nh_bam_info *info);
+typedef struct nh_bam_pair_info {
+    uint32_t struct_size;          /* sizeof(nh_bam_pair_info), set by the caller */
+    uint32_t paired;               /* 1: the first kept record has flag 0x1 */
+    uint64_t pairs;
+    uint64_t bases1, bases2;       /* bases of the mates 1 (flag 0x40), of the mates 2 */
+    uint64_t digest1, digest2;     /* nh_fastx_scan's digest of mate 1's FASTQ, of mate 2's */
+} nh_bam_pair_info;
+int nh_bam_scan_pairs(const char *path, uint32_t threads, nh_bam_info *info, nh_bam_pair_info *pairs);
+int nh_bam_paired(const char *path);
 /* The kernel alone, asynchronous on `stream`, on the engine's device.  d_bam: bam_len BAM bytes (4-byte aligned, readable up to
  * bam_len rounded up to a multiple of 4); d_table: two uint64 a record -- the offset of its block_size field in d_bam and the
  * offset of its '@' in d_text, the latter ascending; d_text: text_cap bytes (4-byte aligned) of which [0, text_len) is the text.
@@ -298,7 +322,7 @@ int nh_bam_scan(const char *path, uint32_t threads, nh_bam_info *info);
 int nh_bam_to_fastq_device(nh_engine *e, const void *d_bam, uint64_t bam_len, const void *d_table, uint64_t n_records,
                            void *d_text, uint64_t text_cap, uint64_t text_len, int *error_bits, void *stream);
 /*
- * BAM output.  With out_codec = NH_CODEC_BAM and a BAM in1, out1 (and human_out1 of a split run) is a BAM file: the input's
+ * BAM output.  With out_codec = NH_CODEC_BAM and a BAM in1, single-end or paired, out1 (and human_out1 of a split run) is a BAM file: the input's
  * header copied byte for byte (magic, l_text, text, n_ref, references; no @PG line is added), then the selected records of the
  * input in input order, each copied byte for byte with its block_size field -- tags (MM / ML, mv, RG ...), CIGAR, flags and a
  * reverse-strand record's orientation untouched -- framed as BGZF and closed by bgzip's EOF member.  Which records are selected
@@ -308,9 +332,10 @@ int nh_bam_to_fastq_device(nh_engine *e, const void *d_bam, uint64_t bam_len, co
  * and are written NOWHERE (nh_bam_scan counts them).  No call is added to a record: it is in `calls` and kraken_output.  Every
  * other output (kraken_output, report, calls, human_ids, read statistics, minimizer data, nh_stats) is byte for byte what the
  * same run with a FASTQ codec writes.  The records are selected and compacted on the GPU from the BAM bytes the reader holds
- * there (nh_bamout.hip) and encoded by NH_CODEC_BGZF's encoders.
+ * there (nh_bamout.hip) and encoded by NH_CODEC_BGZF's encoders.  A paired BAM: the two records of a pair are selected
+ * together, by the pair's call, and written in the order they have in the file.
  * NH_EINVAL, before any device is touched and with nothing created: NH_CODEC_BAM with an in1 that is not a BAM file, with in2,
- * in a masked run, with per-taxon outputs (the last two: not built yet).  nh_compress_file* refuse it: a FASTQ file cannot be
+ * with out2 or human_out2 beside a paired BAM, in a masked run, with per-taxon outputs (the last two: not built yet).  nh_compress_file* refuse it: a FASTQ file cannot be
  * made a BAM.
  *
  * nh_bam_select_device: the select-and-compact kernels alone, on the engine's device and `stream`.  d_bam / bam_len as for
@@ -321,10 +346,17 @@ int nh_bam_to_fastq_device(nh_engine *e, const void *d_bam, uint64_t bam_len, co
  * block_size field or whose bytes [offset, offset + 4 + block_size) do not lie inside [0, bam_len) sets bit 1 and is not
  * written (the others are); a total above out_cap sets bit 4, nothing is written and *d_total is 0.  The call waits for
  * `stream` (its scratch is the call's own).  NOHUMAN_BAM_SPAN: the bytes one wave copies of a long record (test / tuning knob).
+ *
+ * nh_bam_select_pairs_device: the same on pairs.  d_table: the paired reader's, two uint64 a PAIR -- the offsets of its two
+ * records' block_size fields, in file order; d_results: n_pairs nh_result, one a pair.  Both records of a selected pair are
+ * written, in table order.  A record outside the BAM bytes sets bit 1 and is written nowhere, and neither is its mate.
  */
 int nh_bam_select_device(nh_engine *e, const void *d_bam, uint64_t bam_len, const void *d_table, uint64_t n_records,
                          const void *d_results, int want, void *d_out, uint64_t out_cap, uint64_t *d_total, int *error_bits,
                          void *stream);
+int nh_bam_select_pairs_device(nh_engine *e, const void *d_bam, uint64_t bam_len, const void *d_table, uint64_t n_pairs,
+                               const void *d_results, int want, void *d_out, uint64_t out_cap, uint64_t *d_total, int *error_bits,
+                               void *stream);
 /* Output compression stage: replaces CompressionFormat::compress
  * (/root/reference/src/compression.rs:182-200, called from src/main.rs:342-368).  Compresses file
  * `in` to file `out`; gzip runs block-parallel on `threads` workers like the reference's gzp

@@ -184,6 +184,11 @@ class nh_bam_info(C.Structure):
                 ("reverse_complemented", C.c_uint64), ("missing_qualities", C.c_uint64), ("digest", C.c_uint64)]
 
 
+class nh_bam_pair_info(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("paired", C.c_uint32), ("pairs", C.c_uint64), ("bases1", C.c_uint64),
+                ("bases2", C.c_uint64), ("digest1", C.c_uint64), ("digest2", C.c_uint64)]
+
+
 # every symbol include/nohuman_engine.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -226,6 +231,9 @@ SYMBOLS = {
     "nh_fastx_scan": (C.c_int, [C.c_char_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                 C.POINTER(C.c_uint64)]),
     "nh_bam_scan": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(nh_bam_info)]),
+    "nh_bam_scan_pairs": (C.c_int, [C.c_char_p, C.c_uint32, C.POINTER(nh_bam_info), C.POINTER(nh_bam_pair_info)]),
+    "nh_bam_paired": (C.c_int, [C.c_char_p]),
+    "nh_bam_select_pairs_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, _P, C.c_int, _P, C.c_uint64, _P, _P, _P]),
     "nh_bam_to_fastq_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, _P, C.c_uint64, C.c_uint64, _P, _P]),
     "nh_bam_select_device": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, _P, C.c_int, _P, C.c_uint64, _P, _P, _P]),
     "nh_run": (C.c_int, [C.POINTER(nh_run_args), C.POINTER(nh_stats)]),

@@ -116,13 +116,76 @@ bool bam_name_fields(const uint8_t *name, uint32_t n, uint32_t *hlen, uint32_t *
     return true;
 }
 
+// the refusal of a 0x1 record in a single-end file
+int BamStream::refuse_paired(uint64_t ord, const char *name, int name_len, std::string &err) {
+    err = fmt("%s: BAM record %llu (%.*s) is paired (flag 0x1) in a single-end BAM file (its first kept record has no flag 0x1): a paired BAM "
+              "begins with a pair and holds nothing but collated pairs; or split the mates with `samtools fastq -1 R1.fq -2 R2.fq` and give both files",
+              name_.c_str(), (unsigned long long)ord, name_len, name);
+    return -1;
+}
+
+// a kept record of a paired file: the first of its pair is remembered, the second is held against it; -1: it breaks the chain
+int BamStream::chain_pair(const BamRec &x, const uint8_t *name, std::string &err) {
+    const unsigned long long ord = (unsigned long long)x.ordinal;
+    const int nl = (int)x.name_len();
+    if (!(x.flag & 0x1)) {
+        err = fmt("%s: BAM record %llu (%.*s) is not paired (no flag 0x1) in a paired BAM file: every kept record of a paired BAM is a mate", name_.c_str(),
+                  ord, nl, (const char *)name);
+        return -1;
+    }
+    if (((x.flag & 0x40) != 0) == ((x.flag & 0x80) != 0)) {
+        err = fmt("%s: BAM record %llu (%.*s) has %s of the flags 0x40 and 0x80: a mate is the first or the second of its pair", name_.c_str(), ord, nl,
+                  (const char *)name, x.flag & 0x40 ? "both" : "neither");
+        return -1;
+    }
+    if (!half_) {
+        half_ = true;
+        half_ord_ = x.ordinal;
+        half_flag_ = x.flag;
+        half_name_.assign((const char *)name, (size_t)nl);
+        return 0;
+    }
+    if (half_name_.size() != (size_t)nl || memcmp(half_name_.data(), name, (size_t)nl) != 0) {
+        err = fmt("%s: BAM record %llu (%.*s) follows record %llu (%s), which has another name and no mate: the file is not collated -- the two mates "
+                  "of a pair must be neighbours (`samtools collate`)",
+                  name_.c_str(), ord, nl, (const char *)name, (unsigned long long)half_ord_, half_name_.c_str());
+        return -1;
+    }
+    if ((half_flag_ & 0xC0) == (x.flag & 0xC0)) {
+        err = fmt("%s: BAM record %llu (%.*s) and record %llu are both mate %d of their pair (flag 0x%x)", name_.c_str(), ord, nl, (const char *)name,
+                  (unsigned long long)half_ord_, x.flag & 0x40 ? 1 : 2, x.flag & 0xC0);
+        return -1;
+    }
+    half_ = false;
+    return 0;
+}
+
+int BamStream::next_pair(BamRec *a, BamRec *b, std::string &err) {
+    int rc = next(a, err);
+    if (rc != 1) return rc;
+    holding = true;  // (*a points into the window: a stretch of skipped records in front of its mate does not compact it)
+    rc = next(b, err);
+    if (rc == 0) err = name_ + ": the BAM stream ends inside a pair";  // (unreachable: next() refuses the record without a partner)
+    return rc == 1 ? 1 : -1;
+}
+
 int BamStream::next(BamRec *r, std::string &err) {
     for (;;) {
         const uint64_t ord = cnt_.records + 1;
         int rc = ensure(4, err);
         if (rc < 0) return -1;
         if (rc == 0) {
-            if (len_ == pos_) return 0;
+            if (len_ == pos_) {
+                // (a file without a kept record is single-end: a 0x1 record among the skipped ones is refused as ever)
+                if (!mode_known_ && early_ord_) return refuse_paired(early_ord_, early_name_.data(), (int)early_name_.size(), err);
+                if (half_) {
+                    err = fmt("%s: BAM record %llu (%s) is the last kept record and has no mate: the file is not collated, or a mate is missing or empty "
+                              "(`samtools collate`)",
+                              name_.c_str(), (unsigned long long)half_ord_, half_name_.c_str());
+                    return -1;
+                }
+                return 0;
+            }
             err = fmt("%s: the BAM stream ends inside record %llu", name_.c_str(), (unsigned long long)ord);
             return -1;
         }
@@ -168,11 +231,18 @@ int BamStream::next(BamRec *r, std::string &err) {
             err = fmt("%s: BAM record %llu: the read name is not NUL-terminated", name_.c_str(), (unsigned long long)ord);
             return -1;
         }
+        const bool is_kept = !(x.flag & 0x900) && x.l_seq != 0;
         if (x.flag & 0x1) {
-            err = fmt("%s: BAM record %llu (%.*s) is paired (flag 0x1): paired BAM is not supported, split the mates with "
-                      "`samtools fastq -1 R1.fq -2 R2.fq` and give both files",
-                      name_.c_str(), (unsigned long long)ord, (int)x.name_len(), (const char *)p + 36);
-            return -1;
+            if (mode_known_ && !paired_) return refuse_paired(ord, (const char *)p + 36, (int)x.name_len(), err);
+            if (!mode_known_ && !is_kept && !early_ord_) {  // (refused once the first kept record shows a single-end file)
+                early_ord_ = ord;
+                early_name_.assign((const char *)p + 36, x.name_len());
+            }
+        }
+        if (is_kept && !mode_known_) {
+            if (!(x.flag & 0x1) && early_ord_) return refuse_paired(early_ord_, early_name_.data(), (int)early_name_.size(), err);
+            mode_known_ = true;
+            paired_ = (x.flag & 0x1) != 0;
         }
         cnt_.records++;
         pos_ += 4 + (size_t)x.block_size;
@@ -190,6 +260,7 @@ int BamStream::next(BamRec *r, std::string &err) {
                           (unsigned long long)ord);
                 return -1;
             }
+            if (paired_ && chain_pair(x, p + 36, err)) return -1;
             cnt_.reads++;
             cnt_.bases += x.l_seq;
             if (x.flag & 0x10) cnt_.reverse_complemented++;
@@ -222,12 +293,18 @@ void bam_transcode(const uint8_t *bam, const BamRec &r, char *out) {
     *o++ = '\n';
 }
 
-int bam_scan_stream(BamStream &s, BamCounts *counts, uint64_t *digest, std::string &err) {
+int bam_scan_stream(BamStream &s, BamCounts *counts, uint64_t *digest, std::string &err, BamPairCounts *pairs) {
     if (s.read_header(err)) return -1;
-    uint64_t h = 0xcbf29ce484222325ull;
-    auto mix = [&](const char *p, size_t len) {
+    // [0]: every kept record in file order; [1], [2]: the mates of a paired file
+    uint64_t hs[3] = {0xcbf29ce484222325ull, 0xcbf29ce484222325ull, 0xcbf29ce484222325ull}, mate_bases[3] = {0, 0, 0};
+    auto mix1 = [](uint64_t h, const char *p, size_t len) {
         for (size_t i = 0; i < len; i++) h = (h ^ (unsigned char)p[i]) * 0x100000001b3ull;
-        h = (h ^ 0) * 0x100000001b3ull;
+        return (h ^ 0) * 0x100000001b3ull;
+    };
+    int mate = 0;
+    auto mix = [&](const char *p, size_t len) {
+        hs[0] = mix1(hs[0], p, len);
+        if (mate) hs[mate] = mix1(hs[mate], p, len);
     };
     std::vector<char> text;
     for (;;) {
@@ -239,13 +316,21 @@ int bam_scan_stream(BamStream &s, BamCounts *counts, uint64_t *digest, std::stri
         bam_transcode(s.data(), r, text.data());
         uint32_t hlen = 0, idlen = 0;
         (void)bam_name_fields(s.data() + r.name(), r.name_len(), &hlen, &idlen);
+        mate = !s.paired() ? 0 : r.flag & 0x40 ? 1 : 2;
+        mate_bases[mate] += r.l_seq;
         mix(text.data(), hlen);
         mix(text.data() + r.name_len() + 2, r.l_seq);
         mix(text.data() + r.name_len() + 5 + r.l_seq, r.l_seq);
         if (s.cursor() > (8u << 20)) s.compact();
     }
     *counts = s.counts();
-    *digest = h;
+    *digest = hs[0];
+    if (pairs) {
+        pairs->paired = s.paired();
+        pairs->pairs = s.paired() ? s.counts().reads / 2 : 0;
+        pairs->bases1 = mate_bases[1], pairs->bases2 = mate_bases[2];
+        pairs->digest1 = hs[1], pairs->digest2 = hs[2];
+    }
     return 0;
 }
 
@@ -292,6 +377,27 @@ bool bam_wants(const char *path) {
 
 namespace nh {
 
+bool bam_sniff(const char *path, size_t max_recs, uint64_t max_text, const std::function<void(const BamRec &)> &each) {
+    if (!bam_wants(path)) return false;
+    ByteSource src;
+    std::string err;
+    if (src.open(path, err) != 0) return false;
+    BamStream bs;
+    bs.open([&](uint8_t *b, size_t n) { return src.read(b, n); }, path);
+    bs.chunk = 1u << 20;
+    if (bs.read_header(err) != 0) return false;
+    bs.holding = true;
+    BamRec br;
+    uint64_t t = 0;
+    for (size_t i = 0; i < max_recs && t < max_text && bs.next(&br, err) == 1; i++) {
+        if (each) each(br);
+        t += br.text_len();
+    }
+    return bs.paired();  // (known with the first kept record, also where that record is then refused)
+}
+
+bool bam_paired(const char *path) { return path && bam_sniff(path, 1, ~0ull, nullptr); }
+
 // Buffers of one batch in flight: page-locked staging of the batch's BAM bytes and its table, their copies in HBM, the text.
 struct BamSet {
     int dev = -1;
@@ -301,14 +407,14 @@ struct BamSet {
     char *d_text = nullptr;
     int *h_err = nullptr, *d_err = nullptr;
     size_t cap_bam = 0, cap_tab = 0, cap_text = 0;
-    bool busy = false;
+    int held = 0;  // the halves handed out that point into the set and have not been released: 1 a single-end batch, 2 a paired one
 };
 
 class BamReaderImpl {
 public:
     ~BamReaderImpl() { close(); }
 
-    int open(const char *path, const int *devices, int n_devices, std::string &err, unsigned gz_threads) {
+    int open(const char *path, const int *devices, int n_devices, std::string &err, unsigned gz_threads, int paired) {
         close();
         if (n_devices < 1) {
             err = "BamReader: no device";
@@ -324,6 +430,7 @@ public:
         sets_.assign((size_t)(SETS_PER_DEVICE * n_devices), BamSet());
         for (size_t i = 0; i < sets_.size(); i++) sets_[i].dev = devices[i % (size_t)n_devices];
         path_ = path;
+        paired_ = paired < 0 ? bam_paired(path) : paired != 0;
         open_ = true;
         return 0;
     }
@@ -354,6 +461,11 @@ public:
                 done_ = true;
                 break;
             }
+            if (stream_.paired() != paired_) {  // (the request found a single-end file)
+                hb.error = path_ + ": the input changed while it was read (it was a single-end BAM when the run was checked)";
+                done_ = true;
+                return;
+            }
             if (text + r.text_len() > 0xFFFFFFF0ull) {
                 hb.error = path_ + ": BAM record " + std::to_string(r.ordinal) + ": its FASTQ text cannot be addressed with the batch's 32-bit offsets";
                 done_ = true;
@@ -370,7 +482,7 @@ public:
         BamSet &s = sets_[(size_t)(batches_ % sets_.size())];
         {
             std::unique_lock<std::mutex> lk(mu_);
-            cv_.wait(lk, [&] { return !s.busy; });
+            cv_.wait(lk, [&] { return s.held == 0; });
         }
         std::string derr = reserve(s, b1 - b0, recs_.size(), (size_t)text);
         if (derr.empty()) {
@@ -414,19 +526,111 @@ public:
         hb.host_text_valid = false;
         {
             std::lock_guard<std::mutex> lk(mu_);
-            s.busy = true;
+            s.held = 1;
         }
-        BamSet *sp = &s;
-        hb.release = [this, sp] {
-            {
-                std::lock_guard<std::mutex> lk(mu_);
-                sp->busy = false;
-            }
-            cv_.notify_all();
-        };
+        hb.release = releaser(&s);
         batches_++;
     }
 
+    // A paired file: the pairs of the batch chained, their BAM bytes uploaded once, both mates' texts written by one launch.
+    void next_batch(HalfBatch &h1, HalfBatch &h2, size_t max_recs, size_t max_text) {
+        h1.reset();
+        h2.reset();
+        h1.format = h2.format = FMT_FASTQ;
+        if (!open_ || done_) {
+            h1.eof = h2.eof = true;
+            return;
+        }
+        auto fail = [&](const std::string &msg) {
+            h1.recs.clear();
+            h2.recs.clear();
+            h1.error = h2.error = msg;
+            h1.eof = h2.eof = done_ = true;
+        };
+        if (max_recs == 0) max_recs = 1;
+        // (the two texts lie in one buffer, and in one batch of the pipeline behind: together below its 32-bit offsets)
+        max_text = std::min<size_t>(max_text ? max_text : (size_t)0x7F000000u, (size_t)0x7F000000u);
+        stream_.holding = false;
+        stream_.compact();
+        recs_.clear();  // (file order: the pair p is recs_[2p], recs_[2p + 1])
+        uint64_t text[2] = {0, 0};
+        std::string err;
+        while (recs_.size() / 2 < max_recs && text[0] < max_text && text[1] < max_text) {
+            BamRec a, b;
+            const int rc = stream_.next_pair(&a, &b, err);
+            if (rc < 0) return fail(src_.error().empty() ? err : path_ + ": " + src_.error());
+            if (rc == 0) {
+                done_ = true;
+                break;
+            }
+            if (!stream_.paired()) return fail(path_ + ": the input changed while it was read (it was a paired BAM when the run was checked)");
+            const BamRec &m1 = a.flag & 0x40 ? a : b, &m2 = a.flag & 0x40 ? b : a;
+            if (text[0] + m1.text_len() > 0x7FFFFF00ull || text[1] + m2.text_len() > 0x7FFFFF00ull)
+                return fail(path_ + ": BAM record " + std::to_string(a.ordinal) + ": the FASTQ text of its pair cannot be addressed with the batch's 32-bit offsets");
+            recs_.push_back(a);
+            recs_.push_back(b);
+            text[0] += m1.text_len();
+            text[1] += m2.text_len();
+        }
+        h1.eof = h2.eof = done_;
+        if (recs_.empty()) return;
+        const size_t P = recs_.size() / 2;
+        const size_t b0 = recs_.front().off, b1 = recs_.back().off + 4 + recs_.back().block_size;
+        const size_t base2 = ((size_t)text[0] + 255) & ~(size_t)255, ntext = base2 + (size_t)text[1];
+        BamSet &s = sets_[(size_t)(batches_ % sets_.size())];
+        {
+            std::unique_lock<std::mutex> lk(mu_);
+            cv_.wait(lk, [&] { return s.held == 0; });
+        }
+        // the table: 2P records of k_bam_fastq's (mate 1's, then mate 2's: the text offsets ascend), then a word a record in file order
+        std::string derr = reserve(s, b1 - b0, 3 * P, ntext);
+        if (derr.empty()) {
+            memcpy(s.h_bam, stream_.data() + b0, b1 - b0);
+            h1.recs.resize(P);
+            h2.recs.resize(P);
+            uint64_t t[2] = {0, 0};
+            for (size_t p = 0; p < P; p++) {
+                const BamRec &a = recs_[2 * p], &b = recs_[2 * p + 1];
+                s.h_tab[4 * P + 2 * p] = a.off - b0;
+                s.h_tab[4 * P + 2 * p + 1] = b.off - b0;
+                for (int m = 0; m < 2; m++) {
+                    const BamRec &r = ((a.flag & 0x40) != 0) == (m == 0) ? a : b;
+                    s.h_tab[2 * (m * P + p)] = r.off - b0;
+                    s.h_tab[2 * (m * P + p) + 1] = (m ? base2 : 0) + t[m];
+                    RecRef &x = (m ? h2 : h1).recs[p];
+                    (void)bam_name_fields(stream_.data() + r.name(), r.name_len(), &x.hlen, &x.idlen);
+                    x.h = (uint32_t)t[m];
+                    x.s = (uint32_t)(t[m] + r.name_len() + 2);
+                    x.slen = x.qlen = r.l_seq;
+                    x.q = x.s + r.l_seq + 3;
+                    t[m] += r.text_len();
+                    x.raw_end = x.hlen == 1 + r.name_len() ? (uint32_t)t[m] : 0;
+                }
+            }
+            derr = transcode(s, b1 - b0, 2 * P, ntext, 3 * P);
+        }
+        if (!derr.empty()) return fail(path_ + ": " + derr);
+        for (int m = 0; m < 2; m++) {
+            HalfBatch &hb = m ? h2 : h1;
+            hb.text.clear();
+            if (!hb.text.reserve(64)) return fail("out of memory");
+            hb.text.set_size((size_t)text[m]);
+            hb.dev_text = (const uint8_t *)s.d_text + (m ? base2 : 0);
+            hb.dev_device = s.dev;
+            hb.host_text_valid = false;
+        }
+        h1.dev_bam = s.d_bam;
+        h1.dev_bam_table = s.d_tab + 4 * P;
+        h1.bam_len = b1 - b0;
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            s.held = 2;  // (the halves are let go of independently: the set is free when both have been)
+        }
+        h1.release = h2.release = releaser(&s);
+        batches_++;
+    }
+
+    bool paired() const { return paired_; }
     const BamCounts &counts() const { return stream_.counts(); }
     std::string take_header() { return stream_.take_header(); }
 
@@ -436,7 +640,7 @@ public:
             std::unique_lock<std::mutex> lk(mu_);
             cv_.wait(lk, [&] {
                 for (const BamSet &s : sets_)
-                    if (s.busy) return false;
+                    if (s.held) return false;
                 return true;
             });
         }
@@ -460,6 +664,17 @@ public:
 
 private:
     enum { SETS_PER_DEVICE = 4 };
+
+    // what a half's release does: one hold less on its set
+    std::function<void()> releaser(BamSet *sp) {
+        return [this, sp] {
+            {
+                std::lock_guard<std::mutex> lk(mu_);
+                if (sp->held > 0) sp->held--;
+            }
+            cv_.notify_all();
+        };
+    }
 
     // grow-only: room for the batch (a quarter more than asked for, so that batches of about one size allocate once)
     std::string reserve(BamSet &s, size_t bam, size_t n, size_t text) {
@@ -496,10 +711,11 @@ private:
     }
 
     // the batch's bytes and table to the device, k_bam_fastq, the error word back; waits for all of it
-    std::string transcode(BamSet &s, size_t bam, size_t n, size_t text) {
+    // (tab: the table's size in records of 16 bytes where it is more than the n the kernel reads: a paired batch's pair table behind them)
+    std::string transcode(BamSet &s, size_t bam, size_t n, size_t text, size_t tab = 0) {
         *s.h_err = 0;
         hipError_t he = hipMemcpyAsync(s.d_bam, s.h_bam, bam, hipMemcpyHostToDevice, s.stream);
-        if (he == hipSuccess) he = hipMemcpyAsync(s.d_tab, s.h_tab, n * 16, hipMemcpyHostToDevice, s.stream);
+        if (he == hipSuccess) he = hipMemcpyAsync(s.d_tab, s.h_tab, std::max(n, tab) * 16, hipMemcpyHostToDevice, s.stream);
         if (he == hipSuccess) he = hipMemsetAsync(s.d_err, 0, sizeof(int), s.stream);
         if (he == hipSuccess) {
             BamFastqArgs a{};
@@ -529,25 +745,30 @@ private:
     std::mutex mu_;
     std::condition_variable cv_;
     uint64_t batches_ = 0;
-    bool open_ = false, done_ = false;
+    bool open_ = false, done_ = false, paired_ = false;
 };
 
 BamReader::BamReader() : impl_(new BamReaderImpl()) {}
 BamReader::~BamReader() { delete impl_; }
-int BamReader::open(const char *path, const int *devices, int n_devices, std::string &err, unsigned gz_threads) {
-    return impl_->open(path, devices, n_devices, err, gz_threads);
+int BamReader::open(const char *path, const int *devices, int n_devices, std::string &err, unsigned gz_threads, int paired) {
+    return impl_->open(path, devices, n_devices, err, gz_threads, paired);
 }
 void BamReader::next_batch(HalfBatch &hb, size_t max_recs, size_t max_text) { impl_->next_batch(hb, max_recs, max_text); }
+void BamReader::next_batch(HalfBatch &h1, HalfBatch &h2, size_t max_recs, size_t max_text) { impl_->next_batch(h1, h2, max_recs, max_text); }
+bool BamReader::paired() const { return impl_->paired(); }
 const BamCounts &BamReader::counts() const { return impl_->counts(); }
 std::string BamReader::take_header() { return impl_->take_header(); }
 void BamReader::close() { impl_->close(); }
 
 }  // namespace nh
 
-extern "C" int nh_bam_scan(const char *path, uint32_t threads, nh_bam_info *info) {
-    if (!path || !info) return nh::set_error(NH_EINVAL, "nh_bam_scan: null argument");
+// nh_bam_scan and nh_bam_scan_pairs (pinfo given): one pass over the file
+static int bam_scan_file(const char *who, const char *path, uint32_t threads, nh_bam_info *info, nh_bam_pair_info *pinfo) {
+    if (!path || !info) return nh::set_error(NH_EINVAL, "%s: null argument", who);
     if (info->struct_size < sizeof(nh_bam_info))
-        return nh::set_error(NH_EINVAL, "nh_bam_scan: struct_size %u is smaller than nh_bam_info (%zu bytes)", info->struct_size, sizeof(nh_bam_info));
+        return nh::set_error(NH_EINVAL, "%s: struct_size %u is smaller than nh_bam_info (%zu bytes)", who, info->struct_size, sizeof(nh_bam_info));
+    if (pinfo && pinfo->struct_size < sizeof(nh_bam_pair_info))
+        return nh::set_error(NH_EINVAL, "%s: struct_size %u is smaller than nh_bam_pair_info (%zu bytes)", who, pinfo->struct_size, sizeof(nh_bam_pair_info));
     {
         FILE *f = fopen(path, "rb");
         if (!f) return nh::set_error(NH_EIO, "cannot open %s", path);
@@ -560,8 +781,9 @@ extern "C" int nh_bam_scan(const char *path, uint32_t threads, nh_bam_info *info
     nh::BamStream s;
     s.open([&](uint8_t *b, size_t n) { return src.read(b, n); }, path);
     nh::BamCounts c;
+    nh::BamPairCounts pc;
     uint64_t digest = 0;
-    if (nh::bam_scan_stream(s, &c, &digest, err) != 0) {
+    if (nh::bam_scan_stream(s, &c, &digest, err, &pc) != 0) {
         if (!src.error().empty()) err = std::string(path) + ": " + src.error();
         return nh::set_error(NH_EIO, "%s", err.c_str());
     }
@@ -573,6 +795,21 @@ extern "C" int nh_bam_scan(const char *path, uint32_t threads, nh_bam_info *info
     info->reverse_complemented = c.reverse_complemented;
     info->missing_qualities = c.missing_qualities;
     info->digest = digest;
+    if (pinfo) {
+        pinfo->paired = pc.paired;
+        pinfo->pairs = pc.pairs;
+        pinfo->bases1 = pc.bases1, pinfo->bases2 = pc.bases2;
+        pinfo->digest1 = pc.digest1, pinfo->digest2 = pc.digest2;
+    }
     return NH_OK;
 }
+
+extern "C" int nh_bam_scan(const char *path, uint32_t threads, nh_bam_info *info) { return bam_scan_file("nh_bam_scan", path, threads, info, nullptr); }
+
+extern "C" int nh_bam_scan_pairs(const char *path, uint32_t threads, nh_bam_info *info, nh_bam_pair_info *pairs) {
+    if (!pairs) return nh::set_error(NH_EINVAL, "nh_bam_scan_pairs: null argument");
+    return bam_scan_file("nh_bam_scan_pairs", path, threads, info, pairs);
+}
+
+extern "C" int nh_bam_paired(const char *path) { return nh::bam_paired(path) ? 1 : 0; }
 #endif

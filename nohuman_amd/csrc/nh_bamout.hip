@@ -3,7 +3,10 @@
 // The fifth builder on nh_outbuild.h.  A piece is a whole record as it lies in the input: its block_size field and the block_size
 // bytes behind it, copied byte for byte -- tags, CIGAR, flags untouched.  Output o receives, in table order and contiguous, the
 // records whose host-ness (call != 0) is want[o]; a split run's two outputs are made in one pass.  tests/bamout_model.py is the
-// specification; DESIGN.md 6.17.
+// specification; DESIGN.md 6.17.  The records of a paired BAM (BamOutArgs::pairs; tests/bam_pair_model.py) are
+// selected by their pair's call and written in file order: the work item is still a record, only where its offset and its result
+// come from changes -- table[i] of the reader's pair table and res[i >> 1] -- and a record whose mate lies outside the BAM bytes
+// has no bytes either.
 //
 // Three launches on the batch's stream, the scheme of nh_outbuild.h:
 //   k_bout_sizes  per block of BO_RECS records and per output: the sum of 4 + block_size over the records that go there
@@ -41,13 +44,12 @@ constexpr uint32_t BO_SPAN_DEFAULT = 16384;          // k_bam_fastq's (tools/bam
 constexpr uint32_t BO_SPAN_MIN = 16, BO_SPAN_MAX = 1u << 24;
 constexpr unsigned BO_MAX_Y = 64;  // workgroups that share one block's slots
 
-// bytes of record i in the outputs (4 + block_size), 0 (and the error bit, where `report`) for one outside the BAM bytes;
-// *host: whether its call is not 0
-__device__ __forceinline__ uint64_t rec_len(const BamOutArgs &a, uint64_t i, bool report, bool *host) {
-    *host = false;
-    if (i >= a.n) return 0;
-    *host = a.res[i].call != 0;
-    const uint64_t off = a.table[2 * i];
+// where record i lies in the BAM bytes: the reader's table, two words a record (the first is used) -- pairs: one word a record,
+// the two of a pair side by side in file order
+__device__ __forceinline__ uint64_t rec_off(const BamOutArgs &a, uint64_t i) { return a.table[a.pairs ? i : 2 * i]; }
+
+// bytes of the record at `off` (4 + block_size), 0 (and the error bit, where `report`) for one outside the BAM bytes
+__device__ __forceinline__ uint64_t len_at(const BamOutArgs &a, uint64_t off, bool report) {
     if (a.bam_len < 4 || off > a.bam_len - 4) {
         if (report) atomicOr(a.error, a.err_fields);
         return 0;
@@ -58,6 +60,17 @@ __device__ __forceinline__ uint64_t rec_len(const BamOutArgs &a, uint64_t i, boo
         return 0;
     }
     return 4ull + block_size;
+}
+
+// bytes of record i in the outputs, 0 for one outside the BAM bytes -- pairs: and for one whose mate is; *host: whether its
+// call (pairs: its pair's) is not 0
+__device__ __forceinline__ uint64_t rec_len(const BamOutArgs &a, uint64_t i, bool report, bool *host) {
+    *host = false;
+    if (i >= a.n) return 0;
+    *host = a.res[a.pairs ? i >> 1 : i].call != 0;
+    const uint64_t len = len_at(a, rec_off(a, i), report);
+    if (a.pairs && len_at(a, rec_off(a, i ^ 1), false) == 0) return 0;  // (n is even: the mate is a record of the table)
+    return len;
 }
 
 // ... of record i in output o: 0 as well for a record that does not go there
@@ -124,7 +137,7 @@ __global__ void __launch_bounds__(OB_THREADS) k_bout_copy(BamOutArgs a) {
                 if (lane == 0) atomicOr(a.error, a.err_total);
                 continue;
             }
-            const uint64_t src = a.table[2 * (ib + i)] + p0;  // (len != 0: rec_len() found the record inside the BAM bytes)
+            const uint64_t src = rec_off(a, ib + i) + p0;  // (len != 0: rec_len() found the record inside the BAM bytes)
             wave_write(
                 out, base + t + p0, (p0 + span < len ? p0 + span : len) - p0, lane, [&](uint64_t q) { return (uint8_t)bam[src + q]; },
                 [&](uint64_t q, uint32_t *v) {
@@ -151,7 +164,7 @@ uint32_t bam_out_span(uint32_t span) {
 uint64_t bam_out_blocks(uint64_t n) { return (n + BO_RECS - 1) / BO_RECS; }
 
 hipError_t launch_bam_out(const BamOutArgs &a_, hipStream_t stream) {
-    if (a_.n_out < 1 || a_.n_out > 2) return hipErrorInvalidValue;
+    if (a_.n_out < 1 || a_.n_out > 2 || (a_.pairs && (a_.n & 1))) return hipErrorInvalidValue;
     if (a_.n == 0) return hipMemsetAsync(a_.total, 0, 2 * sizeof(uint64_t), stream);
     BamOutArgs a = a_;
     a.span = bam_out_span(a.span);
@@ -166,9 +179,10 @@ hipError_t launch_bam_out(const BamOutArgs &a_, hipStream_t stream) {
 
 }  // namespace nh
 
-extern "C" int nh_bam_select_device(nh_engine *e_, const void *d_bam, uint64_t bam_len, const void *d_table, uint64_t n_records,
-                                    const void *d_results, int want, void *d_out, uint64_t out_cap, uint64_t *d_total, int *error_bits,
-                                    void *stream) {
+// nh_bam_select_device (pairs 0: n records) and nh_bam_select_pairs_device (pairs 1: n pairs)
+static int bam_select(nh_engine *e_, const void *d_bam, uint64_t bam_len, const void *d_table, uint64_t n, int pairs, const void *d_results, int want,
+                      void *d_out, uint64_t out_cap, uint64_t *d_total, int *error_bits, void *stream) {
+    const uint64_t n_records = pairs ? 2 * n : n;
     nh::Engine *e = (nh::Engine *)e_;
     if (!e || !error_bits || !d_total) return nh::set_error(NH_EINVAL, "null argument");
     if (n_records && (!d_bam || !d_table || !d_results || (!d_out && out_cap))) return nh::set_error(NH_EINVAL, "null argument");
@@ -176,9 +190,10 @@ extern "C" int nh_bam_select_device(nh_engine *e_, const void *d_bam, uint64_t b
     if (((uintptr_t)d_bam | (uintptr_t)d_out | (uintptr_t)d_results) & 3)
         return nh::set_error(NH_EINVAL, "the BAM bytes, the results and the output must be 4-byte aligned");
     if (((uintptr_t)d_table | (uintptr_t)d_total) & 7) return nh::set_error(NH_EINVAL, "the table and the total must be 8-byte aligned");
-    if (n_records > (1ull << 34)) return nh::set_error(NH_EINVAL, "too many records for one launch");
+    if (n_records > (1ull << 34) || n > (1ull << 34)) return nh::set_error(NH_EINVAL, "too many records for one launch");
     if (nh::dev_set(e->device) != hipSuccess) return nh::set_error(NH_EDEVICE, "hipSetDevice failed");
     nh::BamOutArgs a{};
+    a.pairs = pairs;
     a.bam = (const uint8_t *)d_bam;
     a.bam_len = bam_len;
     a.table = (const uint64_t *)d_table;
@@ -205,4 +220,16 @@ extern "C" int nh_bam_select_device(nh_engine *e_, const void *d_bam, uint64_t b
     if (he == hipSuccess) he = se;
     if (he != hipSuccess) return nh::set_error(NH_EDEVICE, "BAM select launch: %s", hipGetErrorString(he));
     return NH_OK;
+}
+
+extern "C" int nh_bam_select_device(nh_engine *e, const void *d_bam, uint64_t bam_len, const void *d_table, uint64_t n_records,
+                                    const void *d_results, int want, void *d_out, uint64_t out_cap, uint64_t *d_total, int *error_bits,
+                                    void *stream) {
+    return bam_select(e, d_bam, bam_len, d_table, n_records, 0, d_results, want, d_out, out_cap, d_total, error_bits, stream);
+}
+
+extern "C" int nh_bam_select_pairs_device(nh_engine *e, const void *d_bam, uint64_t bam_len, const void *d_table, uint64_t n_pairs,
+                                          const void *d_results, int want, void *d_out, uint64_t out_cap, uint64_t *d_total, int *error_bits,
+                                          void *stream) {
+    return bam_select(e, d_bam, bam_len, d_table, n_pairs, 1, d_results, want, d_out, out_cap, d_total, error_bits, stream);
 }

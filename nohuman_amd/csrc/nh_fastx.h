@@ -156,7 +156,9 @@ struct HalfBatch {  // the records one input file contributes to a batch
     bool host_text_valid = true;
     // A batch of the BAM reader (nh_bam.h) besides: the BAM bytes its records were transcoded from (bam_len of them) and the
     // reader's table -- two uint64 a record of `recs`, the first where its block_size field lies in dev_bam -- in the memory of
-    // dev_device, valid until release().  Only BamReaderImpl sets them; BAM output (nh_bamout.hip) reads them.
+    // dev_device, valid until release().  A batch of a PAIRED BAM: mate 1's half carries them for both halves (mate 2's has none),
+    // and the table is two uint64 a PAIR -- recs[i] of the two halves --, where its two records lie in dev_bam, in file order.
+    // Only BamReaderImpl sets them; BAM output (nh_bamout.hip) reads them.
     const uint8_t *dev_bam = nullptr;
     const uint64_t *dev_bam_table = nullptr;
     size_t bam_len = 0;

@@ -292,21 +292,13 @@ static size_t estimate_batch_frags(const char *path, size_t *mean_record_bytes) 
     *mean_record_bytes = 0;
     HalfBatch hb;
     if (bam_wants(path)) {  // the first kept records of a BAM: their lengths as the FASTQ text they become
-        ByteSource src;
-        if (src.open(path, err) != 0) return 1u << 18;
-        BamStream bs;
-        bs.open([&](uint8_t *b, size_t n) { return src.read(b, n); }, path);
-        bs.chunk = 1u << 20;
-        if (bs.read_header(err) != 0) return 1u << 18;
-        bs.holding = true;
-        BamRec br;
         uint32_t t = 0;
-        while (hb.recs.size() < 256 && t < (64u << 20) && bs.next(&br, err) == 1) {
+        (void)bam_sniff(path, 256, 64u << 20, [&](const BamRec &br) {
             RecRef x{};
             x.s = t + br.name_len() + 2, x.slen = x.qlen = br.l_seq, x.q = x.s + br.l_seq + 3;
             t += (uint32_t)br.text_len();
             hb.recs.push_back(x);
-        }
+        });
     } else {
         BlockReader r;
         if (r.open(path, err) != 0) return 1u << 18;
@@ -916,9 +908,39 @@ static bool device_reader_pays(const char *path, size_t mean_record_bytes, bool 
     return !(bulk_by_host && sz >= ((uint64_t)128u << 20) && sz < ((uint64_t)2u << 30));
 }
 
-static void reader_main(const char *path, BoundedQueue<std::unique_ptr<HalfBatch>> *out, RunState *rs,
-                        BatchPool *pool, StageClock *clk, int which, size_t batch_frags, size_t batch_text,
+// a paired BAM's loop: both mates' halves from one reader, one thread -- mate 1's into out1, mate 2's into out2
+static void paired_bam_read(BamReader &br, BoundedQueue<std::unique_ptr<HalfBatch>> *out1, BoundedQueue<std::unique_ptr<HalfBatch>> *out2, RunState *rs,
+                            BatchPool *pool1, BatchPool *pool2, StageClock *clk, size_t batch_frags, size_t batch_text) {
+    for (;;) {
+        std::unique_ptr<HalfBatch> h1 = pool1->get(), h2 = pool2->get();
+        h1->recs.reserve(batch_frags);
+        h2->recs.reserve(batch_frags);
+        const uint64_t t0 = StageClock::now();
+        br.next_batch(*h1, *h2, batch_frags, batch_text);
+        const uint64_t t1 = StageClock::now();
+        clk->ns[ST_READ1] += t1 - t0;
+        if (!h1->error.empty()) {
+            rs->fail(NH_EIO, h1->error);
+            break;
+        }
+        const bool eof = h1->eof;
+        out1->push(std::move(h1));
+        out2->push(std::move(h2));
+        clk->ns[ST_RPUSH1] += StageClock::now() - t1;
+        if (eof || rs->failed()) break;
+    }
+}
+
+// out2 / pool2: given for a paired BAM alone -- the one reader of the run feeds both queues, and closes both on every way out
+static void reader_main(const char *path, BoundedQueue<std::unique_ptr<HalfBatch>> *out, BoundedQueue<std::unique_ptr<HalfBatch>> *out2, RunState *rs,
+                        BatchPool *pool, BatchPool *pool2, StageClock *clk, int which, size_t batch_frags, size_t batch_text,
                         unsigned gz_threads, std::vector<int> gz_devices, bool device_reader, unsigned hybrid_threads) {
+    struct CloseSecond {  // (a queue closed twice stays closed)
+        BoundedQueue<std::unique_ptr<HalfBatch>> *q;
+        ~CloseSecond() {
+            if (q) q->close();
+        }
+    } close_second{out2};
     const int gz_device = gz_devices.empty() ? -1 : gz_devices[0];
     // BAM: inflated and chained on the host, transcoded to FASTQ text on the GPU (nh_bam.h); the batches are born there
     const bool is_bam = bam_wants(path);
@@ -926,14 +948,15 @@ static void reader_main(const char *path, BoundedQueue<std::unique_ptr<HalfBatch
     if (is_bam) {
         BamReader br;
         std::string err;
-        if (gz_devices.empty() || br.open(path, gz_devices.data(), (int)gz_devices.size(), err, gz_threads) != 0) {
+        if (gz_devices.empty() || br.open(path, gz_devices.data(), (int)gz_devices.size(), err, gz_threads, out2 != nullptr) != 0) {
             rs->fail(NH_EIO, gz_devices.empty() ? std::string(path) + ": BAM input needs a device" : err);
             if (which == 0) rs->set_bam_header("");
             out->close();
             return;
         }
         if (which == 0) rs->set_bam_header(br.take_header());
-        host_read(br, out, rs, pool, clk, which, batch_frags, batch_text, 0);
+        if (out2) paired_bam_read(br, out, out2, rs, pool, pool2, clk, batch_frags, batch_text);
+        else host_read(br, out, rs, pool, clk, which, batch_frags, batch_text, 0);
         if (getenv("NOHUMAN_TRACE")) {
             const BamCounts &c = br.counts();
             fprintf(stderr, "[nohuman trace] BAM reader: %llu records, %llu kept, %llu secondary or supplementary and %llu empty skipped, %llu reverse-complemented\n",
@@ -941,6 +964,7 @@ static void reader_main(const char *path, BoundedQueue<std::unique_ptr<HalfBatch
                     (unsigned long long)c.skipped_empty, (unsigned long long)c.reverse_complemented);
         }
         out->close();
+        if (out2) out2->close();  // (before close() waits: the main thread must see the end of both)
         br.close();  // (waits for the batches still in the pipeline: they point into its buffers)
         return;
     }
@@ -1153,6 +1177,8 @@ struct RunRequest {
     enum Form { RUN, SPLIT, MASK, EX } form = RUN;
     const char *who = "nh_run";  // the entry's name, for messages
     const nh_run_args *a = nullptr;
+    // the run is paired: in2 is given, or in1 is a paired BAM (nh_bam.h).  Found once, by make_request; everything that asks reads it here
+    bool paired = false;
     const nh_run_extras *x = nullptr;  // the caller's extras as given: what is wrong with the struct itself is said in check_request's order
     // hout1 set: a split run (nh_run_split) -- a->keep_human is 0, hout1 / hout2 receive the classified records
     const char *hout1 = nullptr, *hout2 = nullptr;
@@ -1214,6 +1240,7 @@ RunRequest make_request(RunRequest::Form form, const nh_run_args *a, const nh_ru
     r.form = form == RunRequest::RUN && x ? RunRequest::EX : form;
     r.who = names[r.form];
     r.a = a, r.x = x;
+    r.paired = a && (a->in2 || (a->in1 && bam_paired(a->in1)));
     r.hout1 = h1, r.hout2 = h2, r.mask = form == RunRequest::MASK;
     if (x && x->struct_size >= sizeof(nh_run_extras))  // (a smaller struct: check_request refuses it, nothing else of it is read)
         r.hout1 = x->human_out1, r.hout2 = x->human_out2, r.mask = x->mask != 0, r.calls = x->calls, r.ids = x->human_ids;
@@ -1297,8 +1324,9 @@ static int check_split_args(const RunRequest &r) {
     const char *h1 = r.hout1, *h2 = r.hout2, *who = r.mask ? "nh_run_mask" : "nh_run_split";
     if (!h1 || !h1[0]) return set_error(NH_EINVAL, "%s: human_out1 is required", who);
     if (a->keep_human != 0) return set_error(NH_EINVAL, "%s: keep_human must be 0 (the human reads go to human_out1 / human_out2)", who);
-    if (a->in2 && !h2) return set_error(NH_EINVAL, "%s: paired input needs human_out2", who);
-    if (!a->in2 && h2) return set_error(NH_EINVAL, "%s: human_out2 is given without in2", who);
+    // (BAM output of a paired BAM: one file holds both mates -- check_out_codec refuses a human_out2 there)
+    if (r.paired && !h2 && a->out_codec != NH_CODEC_BAM) return set_error(NH_EINVAL, "%s: paired input needs human_out2", who);
+    if (!r.paired && h2) return set_error(NH_EINVAL, "%s: human_out2 is given without in2", who);
     if (h2 && !strcmp(h1, h2)) return set_error(NH_EINVAL, "%s: human_out1 and human_out2 are the same file", who);
     return check_files(r, F_HUMAN);
 }
@@ -1368,8 +1396,8 @@ static int check_taxon_args(const RunRequest &r) {
         const nh_taxon_out &t = outs[i];
         if (!t.out1 || !t.out1[0]) return set_error(NH_EINVAL, "nh_run_taxa: outs[%u].out1 is required", i);
         if (t.out2 && !t.out2[0]) return set_error(NH_EINVAL, "nh_run_taxa: outs[%u].out2 is an empty path", i);
-        if (a->in2 && !t.out2) return set_error(NH_EINVAL, "nh_run_taxa: paired input needs outs[%u].out2", i);
-        if (!a->in2 && t.out2) return set_error(NH_EINVAL, "nh_run_taxa: outs[%u].out2 is given without in2", i);
+        if (r.paired && !t.out2) return set_error(NH_EINVAL, "nh_run_taxa: paired input needs outs[%u].out2", i);
+        if (!r.paired && t.out2) return set_error(NH_EINVAL, "nh_run_taxa: outs[%u].out2 is given without in2", i);
         for (uint32_t j = 0; j < i; j++)
             if (outs[j].taxid == t.taxid) {
                 if (t.taxid == NH_TAXON_OTHER) return set_error(NH_EINVAL, "nh_run_taxa: outs[%u].taxid: `other` is given twice", i);
@@ -1424,8 +1452,13 @@ static int check_out_codec(const RunRequest &r) {
     const nh_run_args *a = r.a;
     if (!a) return NH_OK;
     if (a->out_codec < NH_CODEC_NONE || a->out_codec > NH_CODEC_BAM) return set_error(NH_EINVAL, "nh_run: unknown out_codec %d", a->out_codec);
+    // (a paired BAM makes a paired run without an in2: said here, before any device is touched; with an in2 run_engines says it)
+    if (a->out_codec != NH_CODEC_BAM && r.paired && !a->in2 && !a->out2) return set_error(NH_EINVAL, "nh_run: paired input needs out2");
     if (a->out_codec != NH_CODEC_BAM) return NH_OK;
     if (a->in2) return set_error(NH_EINVAL, "nh_run: BAM output (out_codec %d) with in2 %s: BAM input is single-end, so is BAM output", NH_CODEC_BAM, a->in2);
+    if (r.paired && a->out2) return set_error(NH_EINVAL, "nh_run: BAM output (out_codec %d) of a paired BAM with out2 %s: one BAM file holds both mates", NH_CODEC_BAM, a->out2);
+    if (r.paired && r.hout2)
+        return set_error(NH_EINVAL, "nh_run: BAM output (out_codec %d) of a paired BAM with human_out2 %s: one BAM file holds both mates", NH_CODEC_BAM, r.hout2);
     if (r.mask) return set_error(NH_EINVAL, "nh_run_mask: BAM output (out_codec %d) of a masked run is not supported: a masked record is not a record of the input", NH_CODEC_BAM);
     if (r.n_touts) return set_error(NH_EINVAL, "nh_run_taxa: BAM output (out_codec %d) with per-taxon outputs is not supported", NH_CODEC_BAM);
     if (!a->in1 || !bam_wants(a->in1))
@@ -1451,7 +1484,7 @@ int check_request(const RunRequest &r) {
     if (!rc) rc = check_out_codec(r);
     return rc;
 }
-// BAM input is single-end: NH_EINVAL -- before any device is touched -- for a BAM in1 beside an in2, and for a BAM in2
+// A BAM is one input, paired or not: NH_EINVAL -- before any device is touched -- for a BAM in1 beside an in2, and for a BAM in2
 int check_bam_inputs(const nh_run_args *a) {
     if (!a || !a->in2) return NH_OK;
     if (bam_wants(a->in2)) return set_error(NH_EINVAL, "nh_run: in2 %s is a BAM file: BAM input is single-end, give it alone as in1", a->in2);
@@ -1803,6 +1836,7 @@ struct RunShape {
     bool trace, trace_run;  // NOHUMAN_TRACE is set: events around the launches, the trace lines; it begins with 1: the run's own lines at its end
     // set_outputs() (outs_take_hbm: out1 / out2 are gzip-family encoders on the GPU that take device spans):
     int mates = 1;
+    bool files2 = false;  // the second mate has files of its own: a paired run, but for BAM output (one BAM holds both mates)
     uint32_t flags = 0;
     bool outs_take_hbm = false, host_text_wanted = false, human_in_hbm = false, mask_in_hbm = false, bam_in_hbm = false, taxon_in_hbm = false;
 
@@ -1831,8 +1865,9 @@ struct RunShape {
     void set_outputs(const nh_run_args *a, const RunState &rs, RunFiles &f) {
         auto takes = [](const OutFile &o) { return o.enc && o.enc->takes_device_spans(); };
         mates = rs.paired ? 2 : 1;
+        files2 = rs.paired && !bamout;
         flags = rs.paired ? NH_FLAG_PAIRED : 0;
-        outs_take_hbm = gzip_family && takes(f.o1) && (!rs.paired || takes(f.o2));
+        outs_take_hbm = gzip_family && takes(f.o1) && (!files2 || takes(f.o2));
         // Batches of the reader on the GPU keep their text in HBM.  The host needs the bytes for plain outputs and the host's
         // codecs, for the ids of --output lines and for the suffix of classified-out headers; gzip outputs encoded on the GPU
         // take the kept records from HBM (a record that needs reformatting -- CRLF, "+id" -- makes the writer fetch its batch).
@@ -2009,7 +2044,7 @@ struct Pipeline {
     void start() {
         start_readers();
         if (sh.bamout) write_bam_header();
-        if (rs.paired) tw2 = std::thread([this] { mate2_flusher_main(); });
+        if (sh.files2) tw2 = std::thread([this] { mate2_flusher_main(); });
         tf = std::thread([this] { flusher_main(); });
         tw = std::thread([this] { writer_main(); });
     }
@@ -2047,18 +2082,20 @@ struct Pipeline {
         // do -- the same choice; with GPU gzip outputs nothing does and the reader on the GPU is taken, profiles/mask_e2e.txt)
         const bool text_to_host = host_text_wanted || (sh.mask && !sh.mask_in_hbm);
         dev_reader1 = !off && dev_gunzip_wants(a->in1) && (named || device_reader_pays(a->in1, mean_rec, text_to_host, by_host));
-        dev_reader2 = rs.paired && !off && dev_gunzip_wants(a->in2) && (named || device_reader_pays(a->in2, mean_rec, text_to_host, by_host));
-        if (rs.paired && !named && dev_reader1 != dev_reader2 && dev_gunzip_wants(a->in1) && dev_gunzip_wants(a->in2)) dev_reader1 = dev_reader2 = false;
+        const bool two_inputs = a->in2 != nullptr;  // (a paired BAM is a paired run from one file, one reader, one thread)
+        dev_reader2 = two_inputs && !off && dev_gunzip_wants(a->in2) && (named || device_reader_pays(a->in2, mean_rec, text_to_host, by_host));
+        if (two_inputs && !named && dev_reader1 != dev_reader2 && dev_gunzip_wants(a->in1) && dev_gunzip_wants(a->in2)) dev_reader1 = dev_reader2 = false;
         // "split": the two mate files on the two KINDS of reader at once -- file 1 inflated and indexed on the GPU, file 2 by all
         // the host's inflate workers (round 6: the GPU's codec kernels and the host's cores idle in turn otherwise)
-        split_readers = rs.paired && how && !strcmp(how, "split") && dev_gunzip_wants(a->in1) && dev_gunzip_wants(a->in2);
+        split_readers = two_inputs && how && !strcmp(how, "split") && dev_gunzip_wants(a->in1) && dev_gunzip_wants(a->in2);
         if (split_readers) dev_reader1 = true, dev_reader2 = false;
         if (bam_wants(a->in1)) {  // (its own reader, whatever NOHUMAN_GZ_READER says; its batches are born on the GPU as well)
             dev_reader1 = false;
             if (!host_text_wanted) pool1.first_reserve = 0, prefill1 = 0;
+            if (!two_inputs) pool2.first_reserve = pool1.first_reserve, prefill2 = prefill1;  // (a paired BAM: mate 2's halves are of the same kind)
         }
         if (sh.trace)
-            fprintf(stderr, "[nohuman trace] gzip reader: %s%s%s\n", dev_reader1 ? "GPU" : "host", rs.paired ? (dev_reader2 ? " / GPU" : " / host") : "",
+            fprintf(stderr, "[nohuman trace] gzip reader: %s%s%s\n", dev_reader1 ? "GPU" : "host", two_inputs ? (dev_reader2 ? " / GPU" : " / host") : "",
                     how ? " (NOHUMAN_GZ_READER)" : "");
         // batches of the reader on the GPU carry no host text unless an output needs it: no page-locked buffers made ahead for them
         if (dev_reader1 && !host_text_wanted) pool1.first_reserve = 0, prefill1 = 0;
@@ -2066,7 +2103,8 @@ struct Pipeline {
         if (prefill1) pool1.start_prefill(prefill1);
         if (rs.paired && prefill2) pool2.start_prefill(prefill2);
         // gzip inputs are inflated by `threads` workers in all, shared between the files
-        unsigned gz_threads = (a->threads ? a->threads : 1) / (unsigned)mates;
+        // (a paired BAM is one file: its inflate workers are not halved for a second file that does not exist)
+        unsigned gz_threads = (a->threads ? a->threads : 1) / (two_inputs ? 2u : 1u);
         if (gz_threads < 1) gz_threads = 1;
         if (gz_threads > 16) gz_threads = 16;  // beyond that the record parser of the file is the limit
         unsigned gz_threads2 = gz_threads;
@@ -2099,9 +2137,10 @@ struct Pipeline {
             if (sh.trace && (dev_reader1 || dev_reader2))
                 fprintf(stderr, "[nohuman trace] gzip reader: hybrid %s (%u host workers per file)\n", hybrid_threads ? "on" : "off", hybrid_threads);
         }
-        t1 = std::thread(reader_main, a->in1, &q1, &rs, &pool1, &clk, 0, batch_frags, batch_text, gz_threads, devs1, dev_reader1, hybrid_threads);
-        if (rs.paired)
-            t2 = std::thread(reader_main, a->in2, &q2, &rs, &pool2, &clk, 1, batch_frags, batch_text, gz_threads2, devs2, dev_reader2, hybrid_threads);
+        t1 = std::thread(reader_main, a->in1, &q1, rs.paired && !two_inputs ? &q2 : nullptr, &rs, &pool1, &pool2, &clk, 0, batch_frags, batch_text, gz_threads,
+                         devs1, dev_reader1, hybrid_threads);
+        if (two_inputs)
+            t2 = std::thread(reader_main, a->in2, &q2, nullptr, &rs, &pool2, nullptr, &clk, 1, batch_frags, batch_text, gz_threads2, devs2, dev_reader2, hybrid_threads);
     }
 
     // BAM output: the input's header, as the reader found it, is the first thing in every record output (a host span: the
@@ -2159,10 +2198,10 @@ struct Pipeline {
                 // (a part that fetched its own host copy has its spans there: they are staged like any host memory)
                 // (a masked run's spans are the built text: in HBM, mapped below, or in the slot's page-locked copy)
                 if (f.o1.enc && !sh.mask && !sh.bamout) f.o1.enc->map_device(b.h1->text.data(), b.len1, s.d_text, s.e->device, b.h1->host_text_valid);
-                if (rs.paired && f.o2.enc && !sh.mask)
+                if (sh.files2 && f.o2.enc && !sh.mask)
                     f.o2.enc->map_device(b.h2->text.data(), b.len2, (const char *)s.d_text + b.base2(), s.e->device, b.h2->host_text_valid);
                 for (const auto &d : j->dev) d.first->enc->map_device(d.second.iov_base, d.second.iov_len, d.second.iov_base, s.e->device, false);
-                if (rs.paired) {
+                if (sh.files2) {
                     std::lock_guard<std::mutex> lk(w2_mu);
                     w2_spans = &j->s2;
                     w2_hspans = sh.split ? &j->hs2 : nullptr;
@@ -2178,7 +2217,7 @@ struct Pipeline {
                 if (!wrc && sh.calls) wrc = f.oc.flush(j->sc);
                 if (!wrc && sh.ids) wrc = f.oi.flush(j->si);
                 if (!wrc && sh.cover) wrc = f.ohi.flush(j->shi);
-                if (rs.paired) {
+                if (sh.files2) {
                     std::unique_lock<std::mutex> lk(w2_mu);
                     w2_cv.wait(lk, [&] { return w2_state == 2; });
                     w2_state = 0;
@@ -2394,17 +2433,20 @@ struct Pipeline {
     // [1], one span an output, in HBM or copied by the writer
     void build_bam(BuildStep step, Slot &s, const Batch &b, FlushJob *j, int *rc) {
         const int n_bout = sh.n_bout;
+        const size_t nrec = b.n * (size_t)sh.mates;  // (the builder's items are records: two a pair)
         if (step == RESERVE) {  // an output's records: the batch's BAM bytes at most
             const size_t out_cap[2] = {b.h1->bam_len + 64, b.h1->bam_len + 64};
             if (!*rc && (!b.h1->dev_bam || !b.h1->dev_bam_table || b.h1->dev_device != s.e->device))
                 *rc = set_error(NH_EDEVICE, "BAM output: a batch without its BAM bytes on the device that classifies it");
             // (the scratch: block offsets of every output, totals: BamOutArgs)
-            if (!*rc) *rc = built_reserve(s.bam, (size_t)n_bout * bam_out_blocks(b.n) + 2, out_cap, n_bout, "BAM-out buffers");
+            if (!*rc) *rc = built_reserve(s.bam, (size_t)n_bout * bam_out_blocks(nrec) + 2, out_cap, n_bout, "BAM-out buffers");
         } else if (step == LAUNCH) {
             BamOutArgs ba{};
             ba.bam = b.h1->dev_bam, ba.bam_len = b.h1->bam_len;
-            ba.table = b.h1->dev_bam_table + 2 * b.off1;  // (a part of a half: a range of its table)
-            ba.n = b.n, ba.nblk = bam_out_blocks(b.n);
+            // (a part of a half: a range of its table, two words a record -- of a paired BAM: two a pair, its records in file order)
+            ba.table = b.h1->dev_bam_table + 2 * b.off1;
+            ba.pairs = rs.paired;
+            ba.n = nrec, ba.nblk = bam_out_blocks(nrec);
             ba.res = (const nh_result *)(sh.hsel ? s.d_hres : s.d_res);
             ba.n_out = n_bout;
             ba.want[0] = sh.split_files ? 0 : a->keep_human != 0;  // out1: the non-host records, with keep_human the host records
@@ -2420,7 +2462,7 @@ struct Pipeline {
                 const size_t tot = (size_t)s.bam.h_total[o];
                 rs.bam_bytes[o] += tot;
                 const bool want_host = sh.split_files ? o == 1 : a->keep_human != 0;
-                for (size_t i = 0; i < b.n; i++) rs.bam_records[o] += (s.host_res()[i].call != 0) == want_host;
+                for (size_t i = 0; i < b.n; i++) rs.bam_records[o] += (uint64_t)sh.mates * ((s.host_res()[i].call != 0) == want_host);
                 if (!tot) continue;
                 if (tot > s.bam.cap_out[o]) {
                     *rc = set_error(NH_EDEVICE, "BAM-out builder: an output ends outside its buffer");
@@ -2675,7 +2717,7 @@ struct Pipeline {
                 const HalfBatch &hb = m ? *b.h2 : *b.h1;
                 const RecRef &rr = hb.recs[(m ? b.off2 : b.off1) + i];
                 if (hb.format == FMT_FASTQ && rr.qlen != rr.slen)
-                    return set_error(NH_EIO, "%s, read %llu: sequence length (%u) != quality string length (%u), which %s", m ? a->in2 : a->in1,
+                    return set_error(NH_EIO, "%s, read %llu: sequence length (%u) != quality string length (%u), which %s", m && a->in2 ? a->in2 : a->in1,
                                      (unsigned long long)(frags_out + i + 1), rr.slen, rr.qlen,
                                      sh.qm ? "--minimum-base-quality cannot mask" : "--read-stats cannot count");
             }
@@ -2913,7 +2955,7 @@ static void print_run_trace(const RunShape &sh, RunState &rs, const StageClock &
 // closes the outputs: the record files side by side (the last chunks of two GPU encoders, their buffers' release), then the
 // selectors' files, the -k file and the read lists one after the other
 static int close_run_files(RunFiles &f, const RunShape &sh, const RunState &rs) {
-    int rc = record_files_side_by_side(f, rs.paired, sh.split_files, [](OutFile &of, int) { return of.close(); });
+    int rc = record_files_side_by_side(f, sh.files2, sh.split_files, [](OutFile &of, int) { return of.close(); });
     if (rc) return rc;
     for (int k = 0; k < sh.K; k++)
         for (int m = 0; m < sh.mates; m++)
@@ -2991,7 +3033,7 @@ static int report_mdata(const TaxoView &view, const MdataNumbers &mdn, nh_minimi
 // what run_engines refuses before it touches a device or a file: the arguments, unreadable inputs, an output that is an input
 static int check_run_files(const RunRequest &r, const RunState &rs) {
     const nh_run_args *a = r.a;
-    if (rs.paired && !a->out2) return set_error(NH_EINVAL, "nh_run: paired input needs out2");
+    if (rs.paired && !a->out2 && a->out_codec != NH_CODEC_BAM) return set_error(NH_EINVAL, "nh_run: paired input needs out2");
     if (!(a->confidence >= 0.0 && a->confidence <= 1.0)) return set_error(NH_EINVAL, "Confidence score must be in the closed interval [0, 1]");
     for (const char *p : {a->in1, a->in2}) {  // fail on unreadable inputs before creating outputs
         if (!p) continue;
@@ -3040,13 +3082,13 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
             if ((rc = ensure_device_external(e))) return rc;
     RunState rs;
     rs.a = a, rs.engines = engines;
-    rs.paired = a->in2 != nullptr;
+    rs.paired = r.paired;
     rs.want_k = a->kraken_output && a->kraken_output[0] && strcmp(a->kraken_output, "/dev/null") != 0;
     rs.call_counts.assign(engines[0]->external.size(), 0);
     rs.dev_counts.assign(4 * engines.size(), 0);
     if ((rc = check_run_files(r, rs))) return rc;
     RunFiles files;
-    if ((rc = open_run_files(files, r, engines, rs.paired, rs.want_k))) return rc;
+    if ((rc = open_run_files(files, r, engines, rs.paired && !sh.bamout, rs.want_k))) return rc;
     std::vector<RunBuffers> dbuf((size_t)sh.G);  // per device, for the run
     Pipeline p(sh, rs, files, dbuf, bin_of);
     p.batch_limits();
@@ -3236,7 +3278,8 @@ int nh_fastx_scan(const char *path, uint64_t *n_records, uint64_t *n_bases, uint
 
 // Test hook (not part of the ABI in include/nohuman_engine.h, like nh_debug_sched): one reader driven alone -- no engine, no
 // classification, no outputs -- and what it handed out, record by record.  reader 0: the host's BlockReader; 1: DevFastqReader
-// on `device`; 2: BamReader on `device` (the batches' bytes are copied back from HalfBatch::dev_text; every batch is released).  next_batch() is called
+// on `device`; 2: BamReader on `device` (the batches' bytes are copied back from HalfBatch::dev_text; every batch is released); 3 and 4: the
+// paired BamReader's halves of mate 1 and of mate 2 (both halves of every batch are made and released, one is reported).  next_batch() is called
 // until the reader reports the end of the input, hands the file over to the host reader (reported, not followed) or fails.
 //   recs     NH_DUMP_REC_WORDS words a record, in input order: hlen, idlen, slen, qlen, canonical (raw_end != 0), raw length
 //            (raw_end - h), index of its batch, digest of header / sequence / qualities (mixed like nh_fastx_scan, from the
@@ -3249,7 +3292,7 @@ enum { NH_DUMP_REC_WORDS = 9 };
 int nh_debug_reader_dump(const char *path, int reader, int device, uint64_t batch_recs, uint64_t max_text, uint64_t *recs, uint64_t rec_cap,
                          uint64_t *n_recs, uint64_t *batches, uint64_t batch_cap, uint64_t *n_batches, uint64_t *pieces, uint64_t piece_cap,
                          uint64_t *n_pieces, int *end, char *msg, uint64_t msg_cap) {
-    if (!path || !recs || !n_recs || !batches || !n_batches || !pieces || !n_pieces || !end || !msg || !msg_cap || !batch_recs || reader < 0 || reader > 2)
+    if (!path || !recs || !n_recs || !batches || !n_batches || !pieces || !n_pieces || !end || !msg || !msg_cap || !batch_recs || reader < 0 || reader > 4)
         return nh::set_error(NH_EINVAL, "nh_debug_reader_dump: bad argument");
     auto fnv = [](const uint8_t *p, size_t len, uint64_t h) {
         for (size_t i = 0; i < len; i++) h = (h ^ p[i]) * 0x100000001b3ull;
@@ -3302,6 +3345,35 @@ int nh_debug_reader_dump(const char *path, int reader, int device, uint64_t batc
             if (!hb.recs.empty() || !hb.eof) (void)take(hb);
             if (hb.eof) break;
         }
+    } else if (reader == 3 || reader == 4) {
+        nh::BamReader br;
+        nh::HalfBatch other;
+        if (!nh::bam_paired(path)) return nh::set_error(NH_EINVAL, "nh_debug_reader_dump: %s is no paired BAM file", path);
+        if (br.open(path, &device, 1, err, 1) != 0) return nh::set_error(NH_EIO, "%s", err.c_str());
+        nh::HalfBatch &mine = hb, &h1 = reader == 3 ? hb : other, &h2 = reader == 3 ? other : hb;
+        for (;;) {
+            br.next_batch(h1, h2, (size_t)batch_recs, (size_t)max_text);
+            if (!mine.error.empty()) {
+                *end = 2;
+                text = mine.error;
+                break;
+            }
+            const bool same = h1.recs.size() == h2.recs.size() && h1.eof == h2.eof;
+            if (!same || ((!mine.recs.empty() || !mine.eof) && !take(mine))) {
+                h1.reset();
+                h2.reset();
+                br.close();
+                return nh::set_error(NH_EDEVICE, same ? "nh_debug_reader_dump: a batch's text could not be copied back"
+                                                      : "nh_debug_reader_dump: the two halves of a paired batch differ in their records");
+            }
+            const bool eof = mine.eof;
+            h1.reset();  // (the set is free when BOTH halves have been released: close() waits for that)
+            h2.reset();
+            if (eof) break;
+        }
+        h1.reset();
+        h2.reset();
+        br.close();
     } else if (reader == 2) {
         nh::BamReader br;
         if (!nh::bam_wants(path)) return nh::set_error(NH_EINVAL, "nh_debug_reader_dump: %s is no BAM file", path);

@@ -175,6 +175,12 @@ static bool is_bam_file(const std::string &p) {
     inflateEnd(&z);
     return four && memcmp(magic, "BAM\1", 4) == 0;
 }
+
+// Is the run paired: two inputs, or one input that is a paired BAM (its first kept record has flag 0x1: the library's test).
+// Asked once, when the arguments have been read (Args::paired); every question of the kind reads the answer there.
+static bool paired_input(const std::vector<std::string> &input) {
+    return input.size() == 1 ? nh_bam_paired(input[0].c_str()) != 0 : input.size() == 2;
+}
 static std::string add_extension(Codec c, const std::string &p) {
     if (c == C_NONE) return p;
     return p + "." + codec_ext(c);  // "a.fq" -> "a.fq.gz", "a" -> "a.gz"
@@ -242,6 +248,7 @@ static std::vector<Installed> installed_databases(const std::string &root) {
 }
 
 struct Args {
+    bool paired = false;  // the run classifies pairs: two inputs, or a paired BAM (paired_input, once the inputs are known)
     std::vector<std::string> input;
     std::string out1, out2, database, db_version, kraken_output, kraken_report;
     std::string human_out1, human_out2;  // split run: the human reads in the same pass (nh_run_split)
@@ -283,7 +290,7 @@ struct Args {
 
 static void usage(FILE *f) {
     fputs("Usage: nohuman [OPTIONS] [INPUT]...\n\n"
-          "Arguments:\n  [INPUT]...  Input file(s) to remove human reads from (FASTA or FASTQ, plain, gzip or bzip2; or one BAM file of single-end reads)\n\n"
+          "Arguments:\n  [INPUT]...  Input file(s) to remove human reads from (FASTA or FASTQ, plain, gzip or bzip2; or one BAM file of single-end reads or of collated pairs: mates adjacent, as `samtools collate` leaves them)\n\n"
           "Options:\n"
           "  -o, --out1 <OUTPUT_1>        First output file\n"
           "  -O, --out2 <OUTPUT_2>        Second output file\n"
@@ -296,7 +303,8 @@ static void usage(FILE *f) {
           "      --bgzf                   Write gzip outputs as BGZF (blocked gzip, as bgzip writes it); needs the output format g\n"
           "      --bam-out                Write the kept records of a BAM input as BAM: the input's header (no @PG line is added) and records copied byte for byte, "
           "tags (MM/ML, mv, RG ...) intact, BGZF framed [default output: <stem>.nohuman.bam]. Secondary, supplementary and empty records are written nowhere; the call "
-          "is not added to a record (see --calls, -k). Not with another output format or container, a masked run, per-taxon outputs, two inputs or an input that is not a BAM\n"
+          "is not added to a record (see --calls, -k). A paired BAM's two mates go to the one file, in the order they have in the input. Not with another output format or container, a masked run, per-taxon outputs, two inputs, "
+          "-O / --human-out2 or an input that is not a BAM\n"
           "  -t, --threads <INT>          Number of threads to use [default: 1]\n"
           "  -H, --human                  Output human reads instead of removing them\n"
           "      --human-out1 <PATH>      Also write the human reads, in the same run, to this file (as -H would)\n"
@@ -523,6 +531,7 @@ static Args parse_args(int argc, char **argv) {
             a.input.push_back(s);
         }
     }
+    a.paired = paired_input(a.input);
     if (a.has_build_db) {  // builds and exits: nothing of a run may come with it
         if (a.has_taxa) {
             const char *with = !a.reference.empty() ? "--reference <FILE>" : a.has_taxid ? "--taxid <INT>" : a.has_taxon_name ? "--taxon-name <NAME>" : nullptr;
@@ -570,7 +579,9 @@ static Args parse_args(int argc, char **argv) {
         if (a.bgzf) arg_error("the argument '--bam-out' cannot be used with '--bgzf': a BAM file is BGZF framed already");
         if (a.mask) arg_error("the argument '--bam-out' cannot be used with '--mask'");
         if (!a.taxon_out.empty()) arg_error("the argument '--bam-out' cannot be used with '--taxon-out <TAXID|other>:<PATH>'");
-        if (a.input.size() > 1) arg_error("the argument '--bam-out' cannot be used with two inputs: BAM input is single-end");
+        if (a.input.size() > 1) arg_error("the argument '--bam-out' cannot be used with two inputs: a BAM holds both mates of a pair, and is given alone");
+        if (a.has_out2) arg_error("the argument '--bam-out' cannot be used with '--out2 <OUT2>': one BAM file holds both mates");
+        if (a.has_human_out2) arg_error("the argument '--bam-out' cannot be used with '--human-out2 <PATH>': one BAM file holds both mates");
         if (a.input.size() == 1 && !is_bam_file(a.input[0]))
             arg_error("the argument '--bam-out' needs a BAM input: %s is not a BAM file", quoted(a.input[0]).c_str());
     }
@@ -578,12 +589,12 @@ static Args parse_args(int argc, char **argv) {
         arg_error("the argument '--keep-taxid <TAXID>' needs '--host-taxid <TAXID>': it keeps a clade inside a host clade");
     // split run (--human-out1 / --human-out2): the non-human reads to -o / -O, the human ones to these, in one pass
     if (a.has_human_out1 || a.has_human_out2) {
-        const bool paired = a.input.size() == 2;
+        const bool paired = a.paired && !a.bam_out;  // (the second mate has files of its own)
         if (a.human) arg_error("the argument '--human' cannot be used with '--human-out1 <PATH>'");
         if (!a.has_human_out1) arg_error("the following required arguments were not provided:\n  --human-out1 <PATH>");
-        if (a.has_human_out2 && !paired) arg_error("the argument '--human-out2 <PATH>' needs two inputs");
+        if (a.has_human_out2 && !paired) arg_error("the argument '--human-out2 <PATH>' needs two inputs, or a paired BAM");
         if (paired && !a.has_human_out2)
-            arg_error("the following required arguments were not provided:\n  --human-out2 <PATH> (two inputs)");
+            arg_error("the following required arguments were not provided:\n  --human-out2 <PATH> (two inputs, or a paired BAM)");
         for (const std::string *h : {&a.human_out1, &a.human_out2}) {
             if (h == &a.human_out2 && !a.has_human_out2) continue;
             const char *flag = h == &a.human_out1 ? "--human-out1" : "--human-out2";
@@ -595,13 +606,13 @@ static Args parse_args(int argc, char **argv) {
     }
     // per-taxon outputs (--taxon-out): a file per selector and mate, written in the same pass
     if (!a.taxon_out.empty()) {
-        const bool paired = a.input.size() == 2;
+        const bool paired = a.paired;
         if (a.human) arg_error("the argument '--human' cannot be used with '--taxon-out <TAXID|other>:<PATH>'");
         std::vector<std::string> mine;
         for (const auto &o : a.taxon_out) {
             const bool hash = o.second.find('#') != std::string::npos;
-            if (paired && !hash) arg_error("invalid value '%s' for '--taxon-out <TAXID|other>:<PATH>': with two inputs the path needs a '#' (it becomes _1 / _2)", o.second.c_str());
-            if (!paired && hash) arg_error("invalid value '%s' for '--taxon-out <TAXID|other>:<PATH>': a '#' in the path needs two inputs", o.second.c_str());
+            if (paired && !hash) arg_error("invalid value '%s' for '--taxon-out <TAXID|other>:<PATH>': with two inputs, or a paired BAM, the path needs a '#' (it becomes _1 / _2)", o.second.c_str());
+            if (!paired && hash) arg_error("invalid value '%s' for '--taxon-out <TAXID|other>:<PATH>': a '#' in the path needs two inputs, or a paired BAM", o.second.c_str());
             for (int m = 0; m < (paired ? 2 : 1); m++) {
                 const std::string p = taxon_out_path(o.second, m);
                 const char *other = (a.has_out1 && p == a.out1) ? "--out1" : (a.has_out2 && p == a.out2) ? "--out2"
@@ -663,6 +674,19 @@ static double confidence_as_kraken2_sees_it(float c, std::string &text) {
 // --bam-out: "<stem>.nohuman.bam" beside the input (the stem without a trailing ".bam")
 static std::string default_bam_out_name(const std::string &in) {
     return join(parent_of(in), (extension(in) == "bam" ? file_stem(in) : file_name(in)) + ".nohuman.bam");
+}
+
+// a paired BAM's two FASTQ outputs: "<stem>.nohuman_1.fq[.ext]" and "<stem>.nohuman_2.fq[.ext]" beside the input
+static std::string default_pair_out_name(const std::string &in, Codec out_codec, int mate) {
+    const std::string stem = extension(in) == "bam" ? file_stem(in) : file_name(in);
+    return add_extension(out_codec, join(parent_of(in), stem + (mate ? ".nohuman_2.fq" : ".nohuman_1.fq")));
+}
+
+static std::string default_out_name(const std::string &in, Codec out_codec);
+// the default name of mate m's record output: beside its own input; a paired BAM is the input of both
+static std::string default_mate_out_name(const std::vector<std::string> &input, bool paired, Codec out_codec, int mate) {
+    if (input.size() == 1 && paired) return default_pair_out_name(input[0], out_codec, mate);
+    return default_out_name(input[mate && input.size() > 1 ? 1 : 0], out_codec);
 }
 
 static std::string default_out_name(const std::string &in, Codec out_codec) {
@@ -794,8 +818,9 @@ int main(int argc, char **argv) {
     }
     if (args.has_human_out1 && !args.input.empty()) {  // a human output equal to a DEFAULT output name: an argument error as well
         const Codec c = args.has_type ? args.type : args.has_out1 ? codec_from_path(args.out1) : codec_from_magic(args.input[0]);
-        const std::string o1 = args.has_out1 ? args.out1 : args.bam_out ? default_bam_out_name(args.input[0]) : default_out_name(args.input[0], c);
-        const std::string o2 = args.input.size() == 2 ? (args.has_out2 ? args.out2 : default_out_name(args.input[1], c)) : "";
+        const bool two = args.paired && !args.bam_out;
+        const std::string o1 = args.has_out1 ? args.out1 : args.bam_out ? default_bam_out_name(args.input[0]) : default_mate_out_name(args.input, args.paired, c, 0);
+        const std::string o2 = two ? (args.has_out2 ? args.out2 : default_mate_out_name(args.input, args.paired, c, 1)) : "";
         for (const std::string *h : {&args.human_out1, &args.human_out2})
             if (!h->empty() && (*h == o1 || *h == o2))
                 arg_error("the argument '%s <PATH>' names the same file as the output %s", h == &args.human_out1 ? "--human-out1" : "--human-out2",
@@ -803,10 +828,11 @@ int main(int argc, char **argv) {
     }
     if (!args.taxon_out.empty() && !args.input.empty()) {  // and a per-taxon file equal to a DEFAULT output name
         const Codec c = args.has_type ? args.type : args.has_out1 ? codec_from_path(args.out1) : codec_from_magic(args.input[0]);
-        const std::string o1 = args.has_out1 ? args.out1 : default_out_name(args.input[0], c);
-        const std::string o2 = args.input.size() == 2 ? (args.has_out2 ? args.out2 : default_out_name(args.input[1], c)) : "";
+        const bool two = args.paired;
+        const std::string o1 = args.has_out1 ? args.out1 : default_mate_out_name(args.input, args.paired, c, 0);
+        const std::string o2 = two ? (args.has_out2 ? args.out2 : default_mate_out_name(args.input, args.paired, c, 1)) : "";
         for (const auto &o : args.taxon_out)
-            for (int m = 0; m < (int)args.input.size() && m < 2; m++) {
+            for (int m = 0; m < (two ? 2 : 1); m++) {
                 const std::string p = taxon_out_path(o.second, m);
                 if (p == o1 || p == o2) arg_error("the argument '--taxon-out <TAXID|other>:<PATH>' names the same file as the output %s", p.c_str());
             }
@@ -944,15 +970,16 @@ int main(int argc, char **argv) {
     else
         INFO("Using database at %s", quoted(db_path).c_str());
 
-    const bool paired = args.input.size() == 2;
+    // paired: the run classifies pairs; two: the second mate has files of its own (not with --bam-out: one BAM holds both mates)
+    const bool paired = args.paired, two = paired && !args.bam_out;
     Codec out_codec = args.has_type ? args.type : args.has_out1 ? codec_from_path(args.out1) : codec_from_magic(args.input[0]);
 
     // The reference lets kraken2 write kraken_out*.fq into a temporary directory "nohuman*" in the current
     // directory (src/main.rs:248-257) and compresses them to the output paths afterwards
     // (src/main.rs:342-368).  Here the engine's writer feeds the kept records straight into the output
     // encoder: no temporary file, one pass.
-    std::string out1 = args.has_out1 ? args.out1 : args.bam_out ? default_bam_out_name(args.input[0]) : default_out_name(args.input[0], out_codec);
-    std::string out2 = paired ? (args.has_out2 ? args.out2 : default_out_name(args.input[1], out_codec)) : "";
+    std::string out1 = args.has_out1 ? args.out1 : args.bam_out ? default_bam_out_name(args.input[0]) : default_mate_out_name(args.input, args.paired, out_codec, 0);
+    std::string out2 = two ? (args.has_out2 ? args.out2 : default_mate_out_name(args.input, args.paired, out_codec, 1)) : "";
     const int codec = args.bam_out ? NH_CODEC_BAM : out_codec == C_GZ ? (args.bgzf ? NH_CODEC_BGZF : NH_CODEC_GZIP) : out_codec == C_BZ2 ? NH_CODEC_BZIP2 : out_codec == C_XZ ? NH_CODEC_XZ
                     : out_codec == C_ZST ? NH_CODEC_ZSTD : NH_CODEC_NONE;
     INFO(args.mask ? "Masking human reads..." : args.human ? "Keeping human reads..." : "Removing human reads...");
@@ -968,7 +995,7 @@ int main(int argc, char **argv) {
     memset(&ra, 0, sizeof ra);
     ra.db_dir = db_path.c_str();
     ra.in1 = args.input[0].c_str();
-    ra.in2 = paired ? args.input[1].c_str() : nullptr;
+    ra.in2 = args.input.size() == 2 ? args.input[1].c_str() : nullptr;
     // The engine writes to "<out>.partial" and the finished file is renamed over the output path: a run
     // that fails -- before or after it created anything -- leaves a file already at the output path
     // untouched, and `-o` equal to an input path works as in the reference (the input is replaced after
@@ -979,15 +1006,15 @@ int main(int argc, char **argv) {
         if (stat(out.c_str(), &sb) == 0 && !S_ISREG(sb.st_mode)) return out;
         return out + ".partial";
     };
-    const std::string part1 = staged(out1), part2 = paired ? staged(out2) : "";
+    const std::string part1 = staged(out1), part2 = two ? staged(out2) : "";
     const bool split = args.has_human_out1;
-    const std::string hpart1 = split ? staged(args.human_out1) : "", hpart2 = split && paired ? staged(args.human_out2) : "";
+    const std::string hpart1 = split ? staged(args.human_out1) : "", hpart2 = split && two ? staged(args.human_out2) : "";
     // the staged files of this run (final path, the one written): removed when the run fails
     // (renamed in this order: the human outputs first, so that a rename that fails part-way never leaves the non-human outputs --
     // what the next step of a pipeline looks for -- in place without their human counterparts)
     std::vector<std::pair<std::string, std::string>> staged_files;
     if (split) staged_files.push_back({args.human_out1, hpart1});
-    if (split && paired) staged_files.push_back({args.human_out2, hpart2});
+    if (split && two) staged_files.push_back({args.human_out2, hpart2});
     const bool lists = !args.calls.empty() || !args.human_ids.empty();
     const std::string cpart = args.calls.empty() ? "" : staged(args.calls), ipart = args.human_ids.empty() ? "" : staged(args.human_ids);
     if (!args.calls.empty()) staged_files.push_back({args.calls, cpart});
@@ -1014,15 +1041,15 @@ int main(int argc, char **argv) {
         touts[k].fragments = 0;
     }
     staged_files.push_back({out1, part1});
-    if (paired) staged_files.push_back({out2, part2});
+    if (two) staged_files.push_back({out2, part2});
     auto unlink_staged = [&] {
         for (const auto &f : staged_files)
             if (f.second != f.first) unlink(f.second.c_str());
     };
     ra.out1 = part1.c_str();
-    ra.out2 = paired ? part2.c_str() : nullptr;
+    ra.out2 = two ? part2.c_str() : nullptr;
     ra.out_codec = codec;
-    ra.codec_threads = paired ? (args.threads / 2 ? args.threads / 2 : 1) : args.threads;  // src/main.rs:342-346
+    ra.codec_threads = two ? (args.threads / 2 ? args.threads / 2 : 1) : args.threads;  // src/main.rs:342-346
     ra.kraken_output = args.kraken_output.empty() ? "/dev/null" : args.kraken_output.c_str();
     ra.report = args.kraken_report.empty() ? nullptr : args.kraken_report.c_str();
     ra.confidence = conf64;
@@ -1039,7 +1066,7 @@ int main(int argc, char **argv) {
         ra.device_ids = devs.data();
     }
     nh_stats st;
-    const char *hp1 = split ? hpart1.c_str() : nullptr, *hp2 = split && paired ? hpart2.c_str() : nullptr;
+    const char *hp1 = split ? hpart1.c_str() : nullptr, *hp2 = split && two ? hpart2.c_str() : nullptr;
     nh_run_extras rx;
     memset(&rx, 0, sizeof rx);
     rx.struct_size = (uint32_t)sizeof rx;
@@ -1145,25 +1172,32 @@ int main(int argc, char **argv) {
               (unsigned long long)hbs.masked_bases, (unsigned long long)hbs.host_bases, (unsigned long long)hbs.closed_bases, hbs.gap);
     if (g_verbose) {  // a BAM input: what the reader made of its records (the host side of the reader once more: nh_bam_scan)
         nh_bam_info bi;
+        nh_bam_pair_info bp;
         memset(&bi, 0, sizeof bi);
+        memset(&bp, 0, sizeof bp);
         bi.struct_size = (uint32_t)sizeof bi;
-        if (nh_bam_scan(args.input[0].c_str(), args.threads, &bi) == 0)
+        bp.struct_size = (uint32_t)sizeof bp;
+        if (nh_bam_scan_pairs(args.input[0].c_str(), args.threads, &bi, &bp) == 0) {
             DEBUG("BAM input: %llu records, %llu kept, %llu secondary or supplementary and %llu without bases skipped, %llu reverse-complemented",
                   (unsigned long long)bi.records, (unsigned long long)bi.reads, (unsigned long long)bi.skipped_secondary,
                   (unsigned long long)bi.skipped_empty, (unsigned long long)bi.reverse_complemented);
+            if (bp.paired)
+                DEBUG("BAM input: paired, %llu pairs, %llu bases in the first mates and %llu in the second", (unsigned long long)bp.pairs,
+                      (unsigned long long)bp.bases1, (unsigned long long)bp.bases2);
+        }
     }
     INFO("Kraken2 finished. Organising output...");
 
-    if (paired && args.threads / 2 > 1) {  // the reference announces both files before its two compress threads run
+    if (two && args.threads / 2 > 1) {  // the reference announces both files before its two compress threads run
         INFO("Writing output file to: %s", quoted(out1).c_str());
         INFO("Writing output file to: %s", quoted(out2).c_str());
     } else {
         INFO("Output file written to: %s", quoted(out1).c_str());
-        if (paired) INFO("Output file written to: %s", quoted(out2).c_str());
+        if (two) INFO("Output file written to: %s", quoted(out2).c_str());
     }
     if (split) {
         INFO("Human reads written to: %s", quoted(args.human_out1).c_str());
-        if (paired) INFO("Human reads written to: %s", quoted(args.human_out2).c_str());
+        if (two) INFO("Human reads written to: %s", quoted(args.human_out2).c_str());
     }
     for (size_t k = 0; k < touts.size(); k++) {
         const unsigned long long id = args.taxon_out[k].first;

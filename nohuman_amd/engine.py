@@ -459,6 +459,25 @@ def bam_scan(path, threads: int = 1) -> BamInfo:
     return BamInfo(*(int(getattr(info, f)) for f in BamInfo._fields))
 
 
+BamPairInfo = collections.namedtuple("BamPairInfo", "paired pairs bases1 bases2 digest1 digest2")
+
+
+def bam_scan_pairs(path, threads: int = 1):
+    """nh_bam_scan_pairs: bam_scan's pass and what a paired BAM has besides -> (BamInfo, BamPairInfo): whether the file is paired
+    (its first kept record has flag 0x1), its pairs, each mate's bases and the digest (nh_fastx_scan's) of each mate's FASTQ.  A
+    file whose pairs do not chain -- an orphan, two names, two records of one mate -- is EngineError -2 naming the record."""
+    info, pinfo = _lib.nh_bam_info(), _lib.nh_bam_pair_info()
+    info.struct_size, pinfo.struct_size = C.sizeof(info), C.sizeof(pinfo)
+    _check(_lib.lib().nh_bam_scan_pairs(os.fsencode(path), int(threads), C.byref(info), C.byref(pinfo)))
+    return (BamInfo(*(int(getattr(info, f)) for f in BamInfo._fields)),
+            BamPairInfo(bool(pinfo.paired), *(int(getattr(pinfo, f)) for f in BamPairInfo._fields[1:])))
+
+
+def bam_paired(path) -> bool:
+    """nh_bam_paired: is the file a paired BAM -- a BAM whose first kept record has flag 0x1 (False for anything else)"""
+    return bool(_lib.lib().nh_bam_paired(os.fsencode(path)))
+
+
 def device_count() -> int:
     n = C.c_int(0)
     _check(_lib.lib().nh_device_count(C.byref(n)))
@@ -703,6 +722,15 @@ class Engine:
         total is above out_cap -- nothing is written, the total is 0.  Waits for `stream`."""
         _check(self._L.nh_bam_select_device(self._h, d_bam or None, int(bam_len), d_table or None, int(n_records), d_results or None,
                                             int(want), d_out or None, int(out_cap), d_total or None, d_error_bits or None, stream or None))
+
+    def bam_select_pairs_device(self, d_bam: int, bam_len: int, d_table: int, n_pairs: int, d_results: int, want: int, d_out: int, out_cap: int,
+                                d_total: int, d_error_bits: int, stream: int = 0):
+        """bam_select_device on the pairs of a paired BAM (nh_bam_select_pairs_device): d_table is the paired reader's, two uint64
+        a PAIR -- where its two records lie in d_bam, in file order --, d_results one nh_result a pair.  Both records of a
+        selected pair are written, in table order; a record outside d_bam sets bit 1 and is written nowhere, and neither is its
+        mate.  Everything else as bam_select_device."""
+        _check(self._L.nh_bam_select_pairs_device(self._h, d_bam or None, int(bam_len), d_table or None, int(n_pairs), d_results or None,
+                                                  int(want), d_out or None, int(out_cap), d_total or None, d_error_bits or None, stream or None))
 
     def read_stats_device(self, d_text: int, text_len: int, d_seq_starts: int, d_seq_lens: int, d_qual_starts: int,
                           d_results: int, n_frag: int, d_acc: int, paired: bool = False, max_workgroups: int = 0, stream: int = 0):

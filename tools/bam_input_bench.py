@@ -7,7 +7,11 @@
            --reps after a warm-up, and where the wall time of the last repetition went (NOHUMAN_TRACE's stage lines); a third
            leg, the same FASTQ through the gzip reader on the GPU, is there to tell the BAM reader from the hand-over of batches
            born in HBM
+  --paired the paired leg alone (profiles/bam_paired.txt): --pairs pairs of 150 bases as ONE collated BAM (every third
+           pair stored mate 2 first) against the same reads as TWO BGZF FASTQ files through the host reader, files to files,
+           two gzip outputs encoded on the GPU; interleaved, the median and the spread of --reps after a warm-up
     python tools/bam_input_bench.py [--ont-reads 20000] [--short-reads 1500000] [--spans 1024,2048,...] [--reps 3]
+    python tools/bam_input_bench.py --paired [--pairs 750000] [--reps 3]
 The database is the synthetic one of tools/human_out_bench.py; a tenth of the reads are pieces of its "human" genome."""
 import argparse
 import json
@@ -122,6 +126,67 @@ def make_files(rng, genome, tmp, tag, lengths, lib, threads):
     return paths, stream, len(text), np.concatenate(table), sum(L * n for L, n in lengths)
 
 
+def paired_blocks(rng, genome, n, tags=None):
+    """n pairs of 150 bases with one name a pair -> (the records (n, 2, R) in file order: every third pair mate 2 first, the
+    two mates' FASTQ (n, T) each); tags: (n, W) bytes appended to every record"""
+    names = names_block(rng, 0, n, False)
+    bams, fqs = [], []
+    for m in (0, 1):
+        seq, q, rev, noq = reads_block(rng, genome, n, 150, 0.1)
+        bam, fq = block_bytes(seq, q, rev, noq, names)
+        bam[:, 4 + 14] = np.where(rev, 0x10, 0) | (0x4D if m == 0 else 0x8D)  # (paired, unmapped, mate unmapped, first / second)
+        if tags is not None:
+            bam = np.concatenate([bam, tags], axis=1)
+            bam[:, :4] = np.frombuffer(struct.pack("<i", bam.shape[1] - 4), np.uint8)
+        bams.append(bam)
+        fqs.append(fq)
+    pair = np.stack(bams, axis=1)
+    swap = np.arange(n) % 3 == 2
+    pair[swap] = pair[swap][:, ::-1]
+    return pair, fqs
+
+
+def compress(lib, tmp, name, data, threads):
+    plain, path = os.path.join(tmp, name + ".plain"), os.path.join(tmp, name)
+    open(plain, "wb").write(data)
+    assert lib.nh_compress_file(plain.encode(), path.encode(), 5, threads) == 0, lib.nh_last_error()
+    os.remove(plain)
+    return path
+
+
+def paired_e2e(eng, rng, genome, tmp, n, lib, threads, reps):
+    pair, fqs = paired_blocks(rng, genome, n)
+    paths = {"bam": compress(lib, tmp, "pe.bam", HEADER + pair.tobytes(), threads),
+             "fq1": compress(lib, tmp, "pe_1.fq.gz", fqs[0].tobytes(), threads), "fq2": compress(lib, tmp, "pe_2.fq.gz", fqs[1].tobytes(), threads)}
+    del pair, fqs
+    o1, o2 = os.path.join(tmp, "out_1.fq.gz"), os.path.join(tmp, "out_2.fq.gz")
+    legs = {"paired_bam": dict(in1=paths["bam"]), "two_bgzf_fastq_host_reader": dict(in1=paths["fq1"], in2=paths["fq2"])}
+    res = {k: {"wall_s": []} for k in legs}
+    os.environ["NOHUMAN_GZ_READER"] = "host"
+    try:
+        for r in range(reps + 1):  # rep 0 warms the buffers and the page cache
+            for leg, ins in legs.items():
+                for o in (o1, o2):
+                    if os.path.exists(o):
+                        os.remove(o)
+                st, dt, tr = timed(lambda: eng.run(out1=o1, out2=o2, threads=threads, out_codec=2, codec_threads=threads // 2, **ins))
+                if r == 0:
+                    continue
+                x = res[leg]
+                x["wall_s"].append(round(dt, 3))
+                x["pairs"], x["classified"], x["out_bytes"] = st.total_sequences, st.classified, [os.path.getsize(o1), os.path.getsize(o2)]
+                x["trace"] = [t.split("] ", 1)[-1] for t in tr.splitlines() if "wall " in t or "BAM reader" in t]
+    finally:
+        os.environ.pop("NOHUMAN_GZ_READER", None)
+    for x in res.values():
+        x["median_s"] = statistics.median(x["wall_s"])
+        x["spread_s"] = round(max(x["wall_s"]) - min(x["wall_s"]), 3)
+    assert len({(x["pairs"], x["classified"], tuple(x["out_bytes"])) for x in res.values()}) == 1, res
+    res["bam_over_fastq"] = round(res["paired_bam"]["median_s"] / res["two_bgzf_fastq_host_reader"]["median_s"], 3)
+    res["file_bytes"] = {k: os.path.getsize(v) for k, v in paths.items()}
+    return res
+
+
 def kernel_bench(eng, stream, table, text_len, spans, rounds=20):
     import torch
     raw = np.zeros((len(stream) + 3) // 4 * 4 + 8, np.uint8)
@@ -189,6 +254,8 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--capacity", type=int, default=1 << 25)
+    ap.add_argument("--paired", action="store_true")
+    ap.add_argument("--pairs", type=int, default=750_000)
     a = ap.parse_args()
     from nohuman_amd import Engine, _lib
     base = "/dev/shm" if os.access("/dev/shm", os.W_OK) else None
@@ -201,6 +268,11 @@ def main():
         # ONT-like: log-normal lengths (median 6 kb, a tail to 150 kb), in 64 groups of one length each
         lens = np.clip(rng.lognormal(np.log(6000), 0.9, 64), 300, 150_000).astype(int)
         sets = {"ont": [(int(L), max(1, a.ont_reads // 64)) for L in lens], "short": [(150, a.short_reads)]}
+        if a.paired:
+            with Engine.open(db) as eng:
+                res = {"reads": "150-base pairs", "pairs": a.pairs, "e2e": paired_e2e(eng, rng, genome, tmp, a.pairs, _lib.lib(), a.threads, a.reps)}
+            print("BAM_PAIRED_INPUT " + json.dumps(res), flush=True)
+            return
         with Engine.open(db) as eng:
             for tag, lengths in sets.items():
                 paths, stream, text_len, table, bases = make_files(rng, genome, tmp, tag, lengths, _lib.lib(), a.threads)

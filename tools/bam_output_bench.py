@@ -7,7 +7,14 @@ ML: a modification call every eighth base, a dozen short tags), and 150 bp reads
   e2e      files to files on one GPU: BAM -> BAM with this library against BAM -> BGZF FASTQ of the same reads with the library
            of --parent-lib (a build of the parent commit; without one: this library, and the result says so); a leg is a child
            process that runs a warm-up and --reps runs; the medians, their ratio and the output sizes
+  --paired the paired legs alone (profiles/bam_paired.txt) on --pairs pairs of 150 bases with an RG tag, as one collated
+           BAM: the builder on pairs (nh_bam_select_pairs_device) beside the single-end builder on the same records in the same
+           order (every record with its pair's call), at the default span; a paired BAM -> BAM run against the same file -> two
+           BGZF FASTQ files, interleaved in one process, the median and the spread of --reps after a warm-up; and, with
+           --parent-lib, the single-end legs (150-base records -> BGZF FASTQ, -> BAM) with this build and with the parent's,
+           twice each in turn, with both spreads
     python tools/bam_output_bench.py [--ont-reads 20000] [--short-reads 1500000] [--spans 4096,16384,65536] [--reps 3] [--parent-lib PATH]
+    python tools/bam_output_bench.py --paired [--pairs 750000] [--short-reads 1500000] [--reps 3] [--parent-lib PATH]
 The database is the synthetic one of tools/human_out_bench.py."""
 import argparse
 import json
@@ -25,7 +32,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 import numpy as np  # noqa: E402
 
-from bam_input_bench import ACGT, HEADER, block_bytes, names_block, reads_block  # noqa: E402
+from bam_input_bench import ACGT, HEADER, block_bytes, compress, names_block, paired_blocks, reads_block  # noqa: E402
 
 
 def tag_block(rng, n, L, ont):
@@ -102,6 +109,130 @@ def kernel_bench(eng, stream, table, spans, rounds=20):
     return out
 
 
+def paired_kernel_bench(eng, stream, n, rec_bytes, rounds=20):
+    """the builder on the n pairs of the stream (records of rec_bytes each, two a pair) and the single-end builder on the same 2n records"""
+    import torch
+    rng = np.random.default_rng(9)
+    raw = np.zeros((len(stream) + 3) // 4 * 4 + 8, np.uint8)
+    raw[:len(stream)] = np.frombuffer(stream, np.uint8)
+    d_bam = torch.from_numpy(raw).cuda()
+    offs = len(HEADER) + np.arange(2 * n, dtype=np.uint64) * np.uint64(rec_bytes)
+    single = np.zeros((2 * n, 2), np.uint64)
+    single[:, 0] = offs
+    d_pair_tab = torch.from_numpy(offs.view(np.int64).copy()).cuda()  # (two words a pair: its records in file order)
+    d_single_tab = torch.from_numpy(single.view(np.int64).copy()).cuda()
+    host = rng.random(n) < 0.1
+    res_p, res_s = np.zeros((n, 4), np.uint32), np.zeros((2 * n, 4), np.uint32)
+    res_p[:, 0] = host * 30
+    res_s[:, 0] = np.repeat(host, 2) * 30
+    d_res_p, d_res_s = torch.from_numpy(res_p.view(np.int32).copy()).cuda(), torch.from_numpy(res_s.view(np.int32).copy()).cuda()
+    total = int((~host).sum()) * 2 * rec_bytes
+    d_out = torch.zeros(len(stream) + 64, dtype=torch.uint8, device="cuda")
+    d_copy = torch.zeros(total + 8, dtype=torch.uint8, device="cuda")
+    d_tot = torch.zeros(1, dtype=torch.int64, device="cuda")
+    d_err = torch.zeros(1, dtype=torch.int32, device="cuda")
+
+    def rate(fn):
+        fn()
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        for _ in range(rounds):
+            fn()
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t) / rounds
+        return {"ms": round(dt * 1e3, 3), "gbs": round(total / dt / 1e9, 1)}
+
+    out = {"pairs": n, "record_bytes": rec_bytes, "selected_bytes": total, "memcpy_d2d": rate(lambda: d_copy.copy_(d_out[:total + 8]))}
+    outs = {}
+    for name, fn in (("pairs", lambda: eng.bam_select_pairs_device(d_bam.data_ptr(), len(stream), d_pair_tab.data_ptr(), n, d_res_p.data_ptr(), 0,
+                                                                   d_out.data_ptr(), len(stream) + 64, d_tot.data_ptr(), d_err.data_ptr())),
+                     ("single_end_same_records", lambda: eng.bam_select_device(d_bam.data_ptr(), len(stream), d_single_tab.data_ptr(), 2 * n, d_res_s.data_ptr(), 0,
+                                                                               d_out.data_ptr(), len(stream) + 64, d_tot.data_ptr(), d_err.data_ptr())),
+                     ("pairs_again", None), ("single_end_same_records_again", None)):
+        fn = fn or outs[name[:-6]][1]
+        out["builder_" + name] = rate(fn)
+        assert int(d_tot.cpu()[0]) == total and int(d_err.cpu()[0]) == 0
+        outs[name] = (d_out[:total].cpu().numpy().tobytes(), fn)
+    assert outs["pairs"][0] == outs["single_end_same_records"][0]  # (the same bytes: both records of a pair, in file order)
+    return out
+
+
+def paired_e2e(eng, bam, tmp, threads, reps):
+    """a paired BAM -> BAM against the same file -> two BGZF FASTQ files, interleaved"""
+    from human_out_bench import timed
+    o1, o2 = os.path.join(tmp, "pe_out_1"), os.path.join(tmp, "pe_out_2")
+    legs = {"paired_bam_to_bam": dict(out_codec=6), "paired_bam_to_two_bgzf_fastq": dict(out_codec=5, out2=o2)}
+    res = {k: {"wall_s": []} for k in legs}
+    for r in range(reps + 1):  # rep 0 warms the buffers and the page cache
+        for leg, kw in legs.items():
+            for o in (o1, o2):
+                if os.path.exists(o):
+                    os.remove(o)
+            st, dt, tr = timed(lambda: eng.run(bam, o1, threads=threads, codec_threads=threads // 2, **kw))
+            if r == 0:
+                continue
+            x = res[leg]
+            x["wall_s"].append(round(dt, 3))
+            x["pairs"], x["classified"], x["out_bytes"] = st.total_sequences, st.classified, sum(os.path.getsize(o) for o in (o1, o2) if os.path.exists(o))
+            x["trace"] = [t.split("] ", 1)[-1] for t in tr.splitlines() if "wall " in t or "bam-out" in t]
+    for x in res.values():
+        x["median_s"] = statistics.median(x["wall_s"])
+        x["spread_s"] = round(max(x["wall_s"]) - min(x["wall_s"]), 3)
+    assert len({(x["pairs"], x["classified"]) for x in res.values()}) == 1, res
+    res["bam_over_fastq"] = round(res["paired_bam_to_bam"]["median_s"] / res["paired_bam_to_two_bgzf_fastq"]["median_s"], 3)
+    return res
+
+
+def single_end_against_parent(a, tmp, db, bam):
+    """the single-end legs with this build and the parent's, twice each in turn: every run's wall time, the medians, the spreads"""
+    res = {}
+    for turn in range(2):
+        for codec, what in ((5, "bam_to_bgzf_fastq"), (6, "bam_to_bam")):
+            for lib, who in ((None, "this_build"), (a.parent_lib, "parent")):
+                env = dict(os.environ)
+                if lib:
+                    env["NOHUMAN_ENGINE_LIB"] = os.path.abspath(lib)
+                out = subprocess.run([sys.executable, os.path.abspath(__file__), "--leg", str(codec), "--tmp", tmp, "--db", db, "--bam", bam, "--reps", str(a.reps),
+                                      "--threads", str(a.threads)], env=env, capture_output=True, text=True, timeout=1500)
+                assert out.returncode == 0, out.stderr[-3000:]
+                leg = json.loads(out.stdout.split("LEG ")[1])
+                r = res.setdefault(what, {}).setdefault(who, {"wall_s": []})
+                r["wall_s"] += leg["wall_s"]
+                r["reads"], r["classified"], r["out_bytes"] = leg["reads"], leg["classified"], leg["out_bytes"]
+    for what in res.values():
+        for r in what.values():
+            r["median_s"] = statistics.median(r["wall_s"])
+            r["spread_s"] = round(max(r["wall_s"]) - min(r["wall_s"]), 3)
+            r["min_s"], r["max_s"] = min(r["wall_s"]), max(r["wall_s"])
+        what["this_over_parent"] = round(what["this_build"]["median_s"] / what["parent"]["median_s"], 3)
+        what["inside_parent_spread"] = what["parent"]["min_s"] <= what["this_build"]["median_s"] <= what["parent"]["max_s"]
+        assert (what["this_build"]["reads"], what["this_build"]["classified"], what["this_build"]["out_bytes"]) == \
+            (what["parent"]["reads"], what["parent"]["classified"], what["parent"]["out_bytes"])
+    return res
+
+
+def paired_main(a, tmp, db, rng, genome, lib):
+    from nohuman_amd import Engine
+    n = a.pairs
+    pair, _ = paired_blocks(rng, genome, n, tags=np.tile(np.frombuffer(b"RGZlane1\0", np.uint8), (n, 1)))
+    stream = HEADER + pair.tobytes()
+    rec_bytes = pair.shape[2]
+    del pair
+    bam = compress(lib, tmp, "pe.bam", stream, a.threads)
+    res = {"reads": "150-base pairs, RG tag", "pairs": n, "bam_file_bytes": os.path.getsize(bam), "bam_stream_bytes": len(stream)}
+    with Engine.open(db) as eng:
+        res["kernel"] = paired_kernel_bench(eng, stream, n, rec_bytes)
+        del stream
+        res["e2e"] = paired_e2e(eng, bam, tmp, a.threads, a.reps)
+    print("BAM_PAIRED_OUTPUT " + json.dumps(res), flush=True)
+    os.remove(bam)
+    if a.parent_lib:
+        path, stream, table, _ = make_bam(rng, genome, tmp, "short", [(150, a.short_reads)], lib, a.threads)
+        del stream, table
+        print("BAM_SINGLE_END_AGAINST_PARENT " + json.dumps({"records": a.short_reads, "parent_lib": a.parent_lib,
+                                                              "legs": single_end_against_parent(a, tmp, db, path)}), flush=True)
+
+
 def leg_main(a):
     """a child process: one leg of the files-to-files comparison with the library NOHUMAN_ENGINE_LIB names"""
     import ctypes
@@ -158,6 +289,8 @@ def main():
     ap.add_argument("--tmp")
     ap.add_argument("--db")
     ap.add_argument("--bam")
+    ap.add_argument("--paired", action="store_true")
+    ap.add_argument("--pairs", type=int, default=750_000)
     a = ap.parse_args()
     if a.leg is not None:
         return leg_main(a)
@@ -170,6 +303,8 @@ def main():
         genome = ACGT[rng.integers(0, 4, size=4_000_000)].copy()
         db = os.path.join(tmp, "db")
         make_db(db, a.capacity, 0.5, genome)
+        if a.paired:
+            return paired_main(a, tmp, db, rng, genome, _lib.lib())
         lens = np.clip(rng.lognormal(np.log(6000), 0.9, 64), 300, 150_000).astype(int)
         sets = {"ont": [(int(L), max(1, a.ont_reads // 64)) for L in lens], "short": [(150, a.short_reads)]}
         for tag, lengths in sets.items():
