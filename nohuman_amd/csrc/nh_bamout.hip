@@ -208,15 +208,14 @@ static int bam_select(nh_engine *e_, const void *d_bam, uint64_t bam_len, const 
     a.err_fields = nh::BAM_ERR_FIELDS;
     a.err_total = nh::BAM_ERR_OUT;
     a.span = 0;
-    uint64_t *scratch = nullptr;  // the block sums, then the two totals
-    if (nh::dev_malloc(&scratch, (a.nblk + 2) * sizeof(uint64_t)) != hipSuccess) return nh::set_error(NH_EOOM, "cannot allocate the builder's scratch");
+    nh::DevBuf<uint64_t> scratch;  // the block sums, then the two totals
+    if (scratch.reserve(a.nblk + 2) != hipSuccess) return nh::set_error(NH_EOOM, "cannot allocate the builder's scratch");
     a.blk = scratch;
     a.total = scratch + a.nblk;
     hipStream_t s = (hipStream_t)stream;
     hipError_t he = nh::launch_bam_out(a, s);
     if (he == hipSuccess) he = hipMemcpyAsync(d_total, a.total, sizeof(uint64_t), hipMemcpyDeviceToDevice, s);
     const hipError_t se = hipStreamSynchronize(s);  // (the scratch is this call's)
-    (void)hipFree(scratch);
     if (he == hipSuccess) he = se;
     if (he != hipSuccess) return nh::set_error(NH_EDEVICE, "BAM select launch: %s", hipGetErrorString(he));
     return NH_OK;

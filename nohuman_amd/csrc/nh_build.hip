@@ -416,29 +416,27 @@ struct Builder {
     // device
     hipStream_t stream = nullptr;
     int grid_max = 0;
-    char *d_text = nullptr;
-    uint64_t *d_starts = nullptr;
-    uint32_t *d_lens = nullptr;
-    uint32_t *d_values = nullptr;
-    uint64_t piece_cap = 0;
+    // (every buffer and event below is the builder's own: ~Builder selects the device, they go back behind it)
+    DevBuf<char> d_text;
+    DevBuf<uint64_t> d_starts;  // the pieces' arrays: regrown together, when a batch has more pieces than they hold
+    DevBuf<uint32_t> d_lens;
+    DevBuf<uint32_t> d_values;
     // several taxa: the node table and the cells per node, resident for the whole build
     bool multi = false;
     uint32_t node_count = 3, vbits = 2;
     std::vector<uint32_t> parent;  // 2^vbits entries
-    uint32_t *d_parent = nullptr;
-    unsigned long long *d_cells = nullptr;
+    DevBuf<uint32_t> d_parent;
+    DevBuf<unsigned long long> d_cells;
     double t_cells = 0;  // k_value_cells alone
-    char *d_raw = nullptr;  // masking: the batch as it was uploaded, which the mask kernel reads while it writes d_text
-    DustTile *d_tiles = nullptr;
-    uint64_t tile_cap = 0;
+    DevBuf<char> d_raw;  // masking: the batch as it was uploaded, which the mask kernel reads while it writes d_text
+    DevBuf<DustTile> d_tiles;
     int dust_grid = 0;
-    unsigned long long *d_counters = nullptr;  // N_COUNTERS: two counters, then `full` as an int, then the masked bases, ...
-    unsigned long long *d_set = nullptr;
-    uint64_t set_cap = 0;
-    uint32_t *d_table = nullptr;
+    DevBuf<unsigned long long> d_counters;  // N_COUNTERS: two counters, then `full` as an int, then the masked bases, ...
+    DevBuf<unsigned long long> d_set;  // (d_set.cap: its slots)
+    DevBuf<uint32_t> d_table;
     uint64_t capacity = 0;
     bool filter = false;  // the set carries the flags of an EXCLUDE pass: INSERT skips what is flagged
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    Events<4> ev;  // around the pass's kernel [0, 1] and the mask kernel [2, 3]
     // the pass that is running, and what it has found so far
     Pass kind = Pass::INSERT;
     bool dust = false;  // it masks its text: `mask`, but never EXCLUDE
@@ -448,15 +446,10 @@ struct Builder {
 
     ~Builder() {
         if (device >= 0 && stream) (void)dev_set(device);
-        for (void *p : {(void *)d_text, (void *)d_starts, (void *)d_lens, (void *)d_counters, (void *)d_set, (void *)d_table, (void *)d_raw,
-                        (void *)d_tiles, (void *)d_values, (void *)d_parent, (void *)d_cells})
-            if (p) (void)hipFree(p);
-        for (hipEvent_t e : ev)
-            if (e) (void)hipEventDestroy(e);
         if (stream) (void)hipStreamDestroy(stream);
     }
 
-    int *d_full() const { return (int *)(d_counters + 2); }
+    int *d_full() const { return (int *)(d_counters.p + 2); }
 
     int init() {
         BUILD_TRY(dev_set(device));
@@ -469,18 +462,19 @@ struct Builder {
         }
         grid_max = prop.multiProcessorCount * (per_cu > 8 ? 8 : per_cu);
         BUILD_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        for (hipEvent_t &e : ev) BUILD_TRY(hipEventCreate(&e));
+        BUILD_TRY(ev.create());
         // (masking: up to 63 bases of context at either end of a batch)
-        BUILD_TRY(dev_malloc(&d_text, batch_cap + (mask ? 2 * DUST_CONTEXT : 0) + 64));
+        const size_t text_cap = batch_cap + (mask ? 2 * DUST_CONTEXT : 0) + 64;
+        BUILD_TRY(d_text.reserve(text_cap));
         if (mask) {
-            BUILD_TRY(dev_malloc(&d_raw, batch_cap + 2 * DUST_CONTEXT + 64));
+            BUILD_TRY(d_raw.reserve(text_cap));
             dust_grid = dust_grid_max();
         }
-        BUILD_TRY(dev_malloc(&d_counters, N_COUNTERS * sizeof(unsigned long long)));
+        BUILD_TRY(d_counters.reserve(N_COUNTERS));
         if (multi) {
-            BUILD_TRY(dev_malloc(&d_parent, parent.size() * sizeof(uint32_t)));
+            BUILD_TRY(d_parent.reserve(parent.size()));
             BUILD_TRY(hipMemcpyAsync(d_parent, parent.data(), parent.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-            BUILD_TRY(dev_malloc(&d_cells, (size_t)node_count * sizeof(unsigned long long)));
+            BUILD_TRY(d_cells.reserve(node_count));
             BUILD_TRY(hipMemsetAsync(d_cells, 0, (size_t)node_count * sizeof(unsigned long long), stream));
             BUILD_TRY(hipStreamSynchronize(stream));
         }
@@ -491,11 +485,12 @@ struct Builder {
     // COUNT: slots >= 2 x (keys in the set + keys this batch can add)
     int grow_set(uint64_t need_keys) {
         uint64_t need = 2 * need_keys + 64;
+        const uint64_t set_cap = d_set.cap;
         if (need <= set_cap) return NH_OK;
         uint64_t ncap = set_cap ? set_cap : (1ull << 16);
         while (ncap < need) ncap *= 2;
-        unsigned long long *nset = nullptr;
-        hipError_t he = dev_malloc(&nset, ncap * sizeof(unsigned long long));
+        DevBuf<unsigned long long> nset;  // (beside the old set, which it is rehashed from)
+        hipError_t he = nset.reserve(ncap);
         if (he != hipSuccess) {
             (void)hipGetLastError();
             return set_error(NH_EOOM, "cannot allocate the counting set of the build (%llu slots, %.1f GiB, beside %.1f GiB in use): give the "
@@ -510,20 +505,15 @@ struct Builder {
             he = hipGetLastError();
         }
         if (he == hipSuccess) he = hipStreamSynchronize(stream);
-        if (he != hipSuccess) {
-            (void)hipFree(nset);
-            return set_error(NH_EDEVICE, "growing the counting set: %s", hipGetErrorString(he));
-        }
-        if (d_set) (void)hipFree(d_set);
-        d_set = nset;
-        set_cap = ncap;
+        if (he != hipSuccess) return set_error(NH_EDEVICE, "growing the counting set: %s", hipGetErrorString(he));
+        d_set = std::move(nset);  // (the old set goes back here)
         return NH_OK;
     }
 
     int alloc_table(uint64_t cap) {
         capacity = cap;
         const uint64_t cells = ((cap + 3) & ~3ull) + 32;
-        hipError_t he = dev_malloc(&d_table, cells * sizeof(uint32_t));
+        hipError_t he = d_table.reserve(cells);
         if (he != hipSuccess) {
             (void)hipGetLastError();
             return set_error(NH_EOOM, "cannot allocate the hash table of the build (%llu cells, %.1f GiB)", (unsigned long long)cap,
@@ -532,12 +522,6 @@ struct Builder {
         BUILD_TRY(hipMemsetAsync(d_table, 0, cells * sizeof(uint32_t), stream));
         BUILD_TRY(hipStreamSynchronize(stream));
         return NH_OK;
-    }
-
-    void free_set() {
-        if (d_set) (void)hipFree(d_set);
-        d_set = nullptr;
-        set_cap = 0;
     }
 
     // the batch to the device, one launch, its totals back
@@ -553,17 +537,10 @@ struct Builder {
             int rc = grow_set(res.claimed + batch_kmers);
             if (rc) return rc;
         }
-        if (n_piece > piece_cap) {
-            if (d_starts) (void)hipFree(d_starts);
-            if (d_lens) (void)hipFree(d_lens);
-            if (d_values) (void)hipFree(d_values);
-            d_starts = nullptr, d_lens = nullptr, d_values = nullptr, piece_cap = 0;
-            const uint64_t ncap = n_piece + n_piece / 2 + 1024;
-            BUILD_TRY(dev_malloc(&d_starts, ncap * sizeof(uint64_t)));
-            BUILD_TRY(dev_malloc(&d_lens, ncap * sizeof(uint32_t)));
-            if (multi) BUILD_TRY(dev_malloc(&d_values, ncap * sizeof(uint32_t)));
-            piece_cap = ncap;
-        }
+        const uint64_t piece_cap = n_piece + n_piece / 2 + 1024;
+        BUILD_TRY(d_starts.reserve(n_piece, piece_cap));
+        BUILD_TRY(d_lens.reserve(n_piece, piece_cap));
+        if (multi) BUILD_TRY(d_values.reserve(n_piece, piece_cap));
         BUILD_TRY(hipMemcpyAsync(d_text, text.data(), text.size(), hipMemcpyHostToDevice, stream));
         BUILD_TRY(hipMemsetAsync(d_text + text.size(), 0, 64, stream));
         if (n_piece) {
@@ -573,13 +550,7 @@ struct Builder {
         }
         const bool masking = !tiles.empty();
         if (masking) {
-            if (tiles.size() > tile_cap) {
-                if (d_tiles) (void)hipFree(d_tiles);
-                d_tiles = nullptr, tile_cap = 0;
-                const uint64_t ncap = tiles.size() + tiles.size() / 2 + 1024;
-                BUILD_TRY(dev_malloc(&d_tiles, ncap * sizeof(DustTile)));
-                tile_cap = ncap;
-            }
+            BUILD_TRY(d_tiles.reserve(tiles.size(), tiles.size() + tiles.size() / 2 + 1024));
             BUILD_TRY(hipMemcpyAsync(d_tiles, tiles.data(), tiles.size() * sizeof(DustTile), hipMemcpyHostToDevice, stream));
             BUILD_TRY(hipMemcpyAsync(d_raw, d_text, text.size() + 64, hipMemcpyDeviceToDevice, stream));
             BUILD_TRY(hipEventRecord(ev[2], stream));
@@ -605,7 +576,7 @@ struct Builder {
         d.revcom_version = 1;
         d.linear_probing = 1;
         d.ambig_rule = ambig_rule;
-        ka.bases = (const uint8_t *)d_text;
+        ka.bases = (const uint8_t *)d_text.p;
         ka.seq_off = d_starts;
         ka.seq_len = d_lens;
         ka.bases_end = text.size();
@@ -613,7 +584,7 @@ struct Builder {
         BuildDev b;
         memset(&b, 0, sizeof b);
         b.set = d_set;
-        b.set_cap = kind != Pass::INSERT || filter ? set_cap : 1;
+        b.set_cap = kind != Pass::INSERT || filter ? d_set.cap : 1;
         b.set_magic = ~0ull / b.set_cap;
         b.counters = d_counters;
         b.full = d_full();
@@ -662,7 +633,7 @@ struct Builder {
         tiles.clear();
         batch_kmers = ctx_bytes = 0;
         res.seconds_gpu += since(t0);
-        if (full && kind == Pass::COUNT) return set_error(NH_EDEVICE, "the counting set of the build overflowed (%llu slots): this is a bug", (unsigned long long)set_cap);
+        if (full && kind == Pass::COUNT) return set_error(NH_EDEVICE, "the counting set of the build overflowed (%llu slots): this is a bug", (unsigned long long)d_set.cap);
         if (full)
             return set_error(NH_ECAPACITY, "the table of %llu cells is full: the input has more distinct minimizers than `capacity` holds "
                              "(leave capacity 0 and it is counted)", (unsigned long long)capacity);
@@ -1178,7 +1149,7 @@ int build_db(const nh_build_args *a, nh_build_stats *stats, const nh_exclude_arg
         if (rc) return rc;
         s.distinct_minimizers = count.claimed;
         s.seconds_count = count.seconds_gpu;
-        if (!excluding) B.free_set();
+        if (!excluding) B.d_set.reset();
         if (s.distinct_minimizers == 0) return no_kmer(count);
         uint64_t kept = s.distinct_minimizers;
         if (excluding) {  // the exclusion input against the set
@@ -1234,7 +1205,7 @@ int build_db(const nh_build_args *a, nh_build_stats *stats, const nh_exclude_arg
     if (getenv("NOHUMAN_TRACE") && excluding)
         fprintf(stderr, "[nohuman trace] build exclude: %llu k-mers of the exclusion input, %llu look-ups, %llu of %llu distinct minimizers excluded; "
                         "kernels alone: exclude %.4f s (set of %llu slots)\n", (unsigned long long)xv.kmers, (unsigned long long)xv.lookups,
-                (unsigned long long)xv.excluded_minimizers, (unsigned long long)s.distinct_minimizers, excl.seconds_kernel, (unsigned long long)B.set_cap);
+                (unsigned long long)xv.excluded_minimizers, (unsigned long long)s.distinct_minimizers, excl.seconds_kernel, (unsigned long long)B.d_set.cap);
     give_taxon_stats(a, P, B.per_node);
     if (stats) memcpy(stats, &s, stats_size);
     give_stats(xs, xv);

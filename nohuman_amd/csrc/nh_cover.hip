@@ -670,8 +670,8 @@ extern "C" int nh_host_cover_device(nh_engine *e_, const void *d_text, uint64_t 
     if (const int rc = nh::cover_check_db(e)) return rc;
     if (n_seq == 0 || text_len == 0) return NH_OK;
     if (nh::dev_set(e->device) != hipSuccess) return nh::set_error(NH_EDEVICE, "hipSetDevice failed");
-    uint64_t *scratch = nullptr;
-    if (nh::dev_malloc(&scratch, nh::cover_mark_scratch_words(n_seq) * 8) != hipSuccess) {
+    nh::DevBuf<uint64_t> scratch;
+    if (scratch.reserve(nh::cover_mark_scratch_words(n_seq)) != hipSuccess) {
         (void)hipGetLastError();
         return nh::set_error(NH_EOOM, "nh_host_cover_device: cannot allocate %llu words of scratch", (unsigned long long)nh::cover_mark_scratch_words(n_seq));
     }
@@ -684,7 +684,6 @@ extern "C" int nh_host_cover_device(nh_engine *e_, const void *d_text, uint64_t 
     hipError_t he = nh::launch_cover_mark(e, c, (hipStream_t)stream);
     const hipError_t se = hipStreamSynchronize((hipStream_t)stream);  // (the scratch is the launches' until they are done)
     if (he == hipSuccess) he = se;
-    (void)hipFree(scratch);
     if (he != hipSuccess) return nh::set_error(NH_EDEVICE, "host intervals, mark launch: %s", hipGetErrorString(he));
     return NH_OK;
 }
@@ -698,8 +697,8 @@ extern "C" int nh_cover_intervals_device(nh_engine *e_, const void *d_cover, uin
         return nh::set_error(NH_EINVAL, "nh_cover_intervals_device: the bitmap, the records and the error word must be 4-byte aligned, the total 8-byte aligned");
     if (n_seq > (1ull << 32) || text_len >= (1ull << 40)) return nh::set_error(NH_EINVAL, "nh_cover_intervals_device: too many sequences or too much text for one launch");
     if (nh::dev_set(e->device) != hipSuccess) return nh::set_error(NH_EDEVICE, "hipSetDevice failed");
-    uint64_t *scratch = nullptr;
-    if (n_seq && nh::dev_malloc(&scratch, nh::cover_intervals_scratch_words(n_seq) * 8) != hipSuccess) {
+    nh::DevBuf<uint64_t> scratch;
+    if (n_seq && scratch.reserve(nh::cover_intervals_scratch_words(n_seq)) != hipSuccess) {
         (void)hipGetLastError();
         return nh::set_error(NH_EOOM, "nh_cover_intervals_device: cannot allocate %llu words of scratch", (unsigned long long)nh::cover_intervals_scratch_words(n_seq));
     }
@@ -711,7 +710,6 @@ extern "C" int nh_cover_intervals_device(nh_engine *e_, const void *d_cover, uin
     hipError_t he = nh::launch_cover_intervals(a, (hipStream_t)stream);
     const hipError_t se = hipStreamSynchronize((hipStream_t)stream);
     if (he == hipSuccess) he = se;
-    if (scratch) (void)hipFree(scratch);
     if (he != hipSuccess) return nh::set_error(NH_EDEVICE, "host intervals, interval launch: %s", hipGetErrorString(he));
     return NH_OK;
 }

@@ -465,14 +465,12 @@ namespace {
         }                                                                                                                      \
     } while (0)
 
-struct DustBuffers {
-    char *src = nullptr, *dst = nullptr;
-    DustTile *tiles = nullptr;
-    unsigned long long *count = nullptr;
+struct DustBuffers {  // (one call's: the caller has selected the device)
+    DevBuf<char> src, dst;
+    DevBuf<DustTile> tiles;
+    DevBuf<unsigned long long> count;
     hipStream_t stream = nullptr;
     ~DustBuffers() {
-        for (void *p : {(void *)src, (void *)dst, (void *)tiles, (void *)count})
-            if (p) (void)hipFree(p);
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
@@ -494,10 +492,10 @@ int dust_mask(int32_t device, char *text, uint64_t n_bytes, const uint64_t *seg_
     DUST_TRY(dev_set(device));
     DustBuffers B;
     DUST_TRY(hipStreamCreateWithFlags(&B.stream, hipStreamNonBlocking));
-    DUST_TRY(dev_malloc(&B.src, n_bytes + 64));
-    DUST_TRY(dev_malloc(&B.dst, n_bytes + 64));
-    DUST_TRY(dev_malloc(&B.tiles, tiles.size() * sizeof(DustTile)));
-    DUST_TRY(dev_malloc(&B.count, sizeof(unsigned long long)));
+    DUST_TRY(B.src.reserve(n_bytes + 64));
+    DUST_TRY(B.dst.reserve(n_bytes + 64));
+    DUST_TRY(B.tiles.reserve(tiles.size()));
+    DUST_TRY(B.count.reserve(1));
     DUST_TRY(hipMemcpyAsync(B.src, text, n_bytes, hipMemcpyHostToDevice, B.stream));
     DUST_TRY(hipMemcpyAsync(B.dst, B.src, n_bytes, hipMemcpyDeviceToDevice, B.stream));
     DUST_TRY(hipMemcpyAsync(B.tiles, tiles.data(), tiles.size() * sizeof(DustTile), hipMemcpyHostToDevice, B.stream));
@@ -532,8 +530,8 @@ extern "C" int nh_dust_reads_device(nh_engine *e_, const void *d_text, uint64_t 
     if (n_seq > (1ull << 31)) return nh::set_error(NH_EINVAL, "nh_dust_reads_device: too many sequences for one launch");
     if (n_seq == 0) return NH_OK;
     if (nh::dev_set(e->device) != hipSuccess) return nh::set_error(NH_EDEVICE, "hipSetDevice failed");
-    uint64_t *scratch = nullptr;
-    if (nh::dev_malloc(&scratch, nh::read_dust_scratch_words(n_seq) * 8) != hipSuccess) {
+    nh::DevBuf<uint64_t> scratch;
+    if (scratch.reserve(nh::read_dust_scratch_words(n_seq)) != hipSuccess) {
         (void)hipGetLastError();
         return nh::set_error(NH_EOOM, "nh_dust_reads_device: cannot allocate %llu words of scratch", (unsigned long long)nh::read_dust_scratch_words(n_seq));
     }
@@ -545,7 +543,6 @@ extern "C" int nh_dust_reads_device(nh_engine *e_, const void *d_text, uint64_t 
     hipError_t he = nh::launch_read_dust(a, scratch, nh::read_dust_grid_max(), (hipStream_t)stream);
     const hipError_t se = hipStreamSynchronize((hipStream_t)stream);  // (the scratch is the launches' until they are done)
     if (he == hipSuccess) he = se;
-    (void)hipFree(scratch);
     if (he != hipSuccess) return nh::set_error(NH_EDEVICE, "read DUST launch: %s", hipGetErrorString(he));
     return NH_OK;
 }

@@ -177,56 +177,48 @@ int ext_rekey(ExtendTable &t) {
     bool identity = t.new_vb == t.old_vb;
     for (uint32_t i = 0; i < base_nodes; i++) identity = identity && t.remap[i] == i;
     t.rekeyed = !identity;
-    uint16_t *d_remap = nullptr;
-    unsigned long long *d_out = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    auto run = [&]() -> int {
-        EXT_TRY(dev_malloc(&d_remap, (size_t)EXT_REMAP_MAX * sizeof(uint16_t)));
-        EXT_TRY(dev_malloc(&d_out, EXT_COUNTERS * sizeof(unsigned long long)));
-        EXT_TRY(hipMemsetAsync(d_remap, 0, (size_t)EXT_REMAP_MAX * sizeof(uint16_t), t.stream));
-        EXT_TRY(hipMemcpyAsync(d_remap, t.remap.data(), (size_t)base_nodes * sizeof(uint16_t), hipMemcpyHostToDevice, t.stream));
-        EXT_TRY(hipMemsetAsync(d_out, 0, EXT_COUNTERS * sizeof(unsigned long long), t.stream));
-        for (hipEvent_t &e : ev) EXT_TRY(hipEventCreate(&e));
-        const uint64_t want = (((t.capacity + 3) >> 2) + 255) / 256;
-        const unsigned grid = (unsigned)(want < (uint64_t)t.grid_max ? (want ? want : 1) : (uint64_t)t.grid_max);
-        const uint32_t delta = t.new_vb - t.old_vb;
-        EXT_TRY(hipEventRecord(ev[0], t.stream));
-        if (identity)
-            hipLaunchKernelGGL(k_ext_rekey<false>, dim3(grid), dim3(256), 0, t.stream, t.d_table, t.capacity, t.old_vb, delta, t.new_vb, d_remap,
-                               base_nodes, d_out);
-        else
-            hipLaunchKernelGGL(k_ext_rekey<true>, dim3(grid), dim3(256), 0, t.stream, t.d_table, t.capacity, t.old_vb, delta, t.new_vb, d_remap,
-                               base_nodes, d_out);
+    DevBuf<uint16_t> d_remap;  // (the three go back when the call returns, on every path: t's device is the thread's)
+    DevBuf<unsigned long long> d_out;
+    Events<3> ev;
+    EXT_TRY(d_remap.reserve(EXT_REMAP_MAX));
+    EXT_TRY(d_out.reserve(EXT_COUNTERS));
+    EXT_TRY(hipMemsetAsync(d_remap, 0, (size_t)EXT_REMAP_MAX * sizeof(uint16_t), t.stream));
+    EXT_TRY(hipMemcpyAsync(d_remap, t.remap.data(), (size_t)base_nodes * sizeof(uint16_t), hipMemcpyHostToDevice, t.stream));
+    EXT_TRY(hipMemsetAsync(d_out, 0, EXT_COUNTERS * sizeof(unsigned long long), t.stream));
+    EXT_TRY(ev.create());
+    const uint64_t want = (((t.capacity + 3) >> 2) + 255) / 256;
+    const unsigned grid = (unsigned)(want < (uint64_t)t.grid_max ? (want ? want : 1) : (uint64_t)t.grid_max);
+    const uint32_t delta = t.new_vb - t.old_vb;
+    EXT_TRY(hipEventRecord(ev[0], t.stream));
+    if (identity)
+        hipLaunchKernelGGL(k_ext_rekey<false>, dim3(grid), dim3(256), 0, t.stream, t.d_table, t.capacity, t.old_vb, delta, t.new_vb, d_remap,
+                           base_nodes, d_out);
+    else
+        hipLaunchKernelGGL(k_ext_rekey<true>, dim3(grid), dim3(256), 0, t.stream, t.d_table, t.capacity, t.old_vb, delta, t.new_vb, d_remap,
+                           base_nodes, d_out);
+    EXT_TRY(hipGetLastError());
+    EXT_TRY(hipEventRecord(ev[2], t.stream));
+    unsigned long long out[EXT_COUNTERS] = {0, 0, 0};
+    EXT_TRY(hipMemcpyAsync(out, d_out, sizeof out, hipMemcpyDeviceToHost, t.stream));
+    EXT_TRY(hipStreamSynchronize(t.stream));
+    t.non_empty = out[0];
+    t.bad_value = out[1] != 0;
+    if (delta > 0 && !t.bad_value) {  // (a bad value fails the call: nothing more is done to the table)
+        const uint64_t want1 = (t.capacity + 255) / 256;
+        const unsigned grid1 = (unsigned)(want1 < (uint64_t)t.grid_max ? (want1 ? want1 : 1) : (uint64_t)t.grid_max);
+        hipLaunchKernelGGL(k_ext_shadow, dim3(grid1), dim3(256), 0, t.stream, t.d_table, t.capacity, t.new_vb, t.d_parent, d_out);
         EXT_TRY(hipGetLastError());
-        EXT_TRY(hipEventRecord(ev[2], t.stream));
-        unsigned long long out[EXT_COUNTERS] = {0, 0, 0};
-        EXT_TRY(hipMemcpyAsync(out, d_out, sizeof out, hipMemcpyDeviceToHost, t.stream));
-        EXT_TRY(hipStreamSynchronize(t.stream));
-        t.non_empty = out[0];
-        t.bad_value = out[1] != 0;
-        if (delta > 0 && !t.bad_value) {  // (a bad value fails the call: nothing more is done to the table)
-            const uint64_t want1 = (t.capacity + 255) / 256;
-            const unsigned grid1 = (unsigned)(want1 < (uint64_t)t.grid_max ? (want1 ? want1 : 1) : (uint64_t)t.grid_max);
-            hipLaunchKernelGGL(k_ext_shadow, dim3(grid1), dim3(256), 0, t.stream, t.d_table, t.capacity, t.new_vb, t.d_parent, d_out);
-            EXT_TRY(hipGetLastError());
-        }
-        EXT_TRY(hipEventRecord(ev[1], t.stream));
-        EXT_TRY(hipMemcpyAsync(out, d_out, sizeof out, hipMemcpyDeviceToHost, t.stream));
-        EXT_TRY(hipStreamSynchronize(t.stream));
-        t.shadowed = out[2];
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) t.seconds_rekey = ms * 1e-3;
-        else (void)hipGetLastError();
-        if (hipEventElapsedTime(&ms, ev[0], ev[2]) == hipSuccess) t.seconds_pass = ms * 1e-3;
-        else (void)hipGetLastError();
-        return NH_OK;
-    };
-    const int rc = run();
-    if (d_remap) (void)hipFree(d_remap);
-    if (d_out) (void)hipFree(d_out);
-    for (hipEvent_t e : ev)
-        if (e) (void)hipEventDestroy(e);
-    return rc;
+    }
+    EXT_TRY(hipEventRecord(ev[1], t.stream));
+    EXT_TRY(hipMemcpyAsync(out, d_out, sizeof out, hipMemcpyDeviceToHost, t.stream));
+    EXT_TRY(hipStreamSynchronize(t.stream));
+    t.shadowed = out[2];
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) t.seconds_rekey = ms * 1e-3;
+    else (void)hipGetLastError();
+    if (hipEventElapsedTime(&ms, ev[0], ev[2]) == hipSuccess) t.seconds_pass = ms * 1e-3;
+    else (void)hipGetLastError();
+    return NH_OK;
 }
 
 }  // namespace nh

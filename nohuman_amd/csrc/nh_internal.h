@@ -373,6 +373,65 @@ template <class T>
 inline hipError_t host_malloc(T **p, size_t bytes, unsigned flags = hipHostMallocDefault) {
     return host_malloc((void **)p, bytes, flags);
 }
+// A block of device memory (PINNED: of page-locked host memory) with one owner: `cap` elements at `p`, freed exactly once.  The
+// destructor frees under the device the thread has selected -- whoever holds buffers of a device (a slot, a run's RunBuffers,
+// the build's Builder) selects it in its own destructor, which runs before its members'; a local's owner has it selected.
+template <class T, bool PINNED>
+struct Buf {
+    T *p = nullptr;
+    size_t cap = 0;  // elements
+    Buf() = default;
+    Buf(Buf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+    Buf &operator=(Buf &&o) noexcept {
+        if (this != &o) reset(), p = o.p, cap = o.cap, o.p = nullptr, o.cap = 0;
+        return *this;
+    }
+    ~Buf() { reset(); }
+    void reset() {
+        if (p) (void)(PINNED ? hipHostFree(p) : hipFree(p));
+        p = nullptr, cap = 0;
+    }
+    // room for `need` elements: nothing to do where there is; else the block is freed FIRST -- the peak is one block, no content
+    // is kept -- and `new_cap` elements are allocated (the caller's growth policy).  A failure leaves the buffer empty.
+    hipError_t reserve(size_t need, size_t new_cap) {
+        if (need <= cap) return hipSuccess;
+        reset();
+        const hipError_t he = PINNED ? host_malloc(&p, new_cap * sizeof(T)) : dev_malloc(&p, new_cap * sizeof(T));
+        if (he == hipSuccess) cap = new_cap;
+        else p = nullptr;
+        return he;
+    }
+    hipError_t reserve(size_t n) { return reserve(n, n); }  // exactly n: a buffer that does not grow
+    operator T *() const { return p; }
+};
+template <class T>
+using DevBuf = Buf<T, false>;
+template <class T>
+using PinBuf = Buf<T, true>;
+// The events around stretches of a stream, a pair as a rule (NOHUMAN_TRACE, the build's kernel times): made on request under the
+// owner's device, destroyed with their owner; without create() all are null and nobody records them.
+template <int N>
+struct Events {
+    hipEvent_t ev[N] = {};
+    Events() = default;
+    Events(Events &&o) noexcept { std::swap(ev, o.ev); }
+    Events &operator=(Events &&o) noexcept {
+        std::swap(ev, o.ev);
+        return *this;
+    }
+    ~Events() {
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    hipError_t create() {
+        hipError_t he = hipSuccess;
+        for (hipEvent_t &e : ev)
+            if (he == hipSuccess && !e) he = hipEventCreate(&e);
+        return he;
+    }
+    hipEvent_t operator[](int i) const { return ev[i]; }
+};
+using EventPair = Events<2>;
 // the path's only collective: rows[g] = counters of device ids[g] -> every row = the sum (RCCL, nh_collective.hip)
 // (d_src[g] != NULL: the four counters lie in device ids[g]'s memory and are reduced from there)
 int allreduce_counters(const int *ids, int n_dev, uint64_t *rows, std::string &backend,

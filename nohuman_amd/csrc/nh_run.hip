@@ -383,38 +383,40 @@ struct Batch {
 // the classifier, the builder's scratch, its totals as they come back with the results (in the order its kernel writes them:
 // *Args::total), and the page-locked copies the writer makes where the consumer cannot take the HBM range.
 struct BuiltOut {
-    void *d_blk = nullptr;  // block sums / offsets, then the totals (d_total), then what else the builder keeps (*Args)
-    size_t cap_blk = 0;     // in 8-byte words
-    char *d_out[2] = {nullptr, nullptr}, *h_out[2] = {nullptr, nullptr};
-    size_t cap_out[2] = {0, 0}, cap_host[2] = {0, 0};
+    DevBuf<uint64_t> d_blk;  // block sums / offsets, then the totals (d_total), then what else the builder keeps (*Args)
+    DevBuf<char> d_out[2];
+    PinBuf<char> h_out[2];
     uint64_t *d_total = nullptr;  // where in d_blk the batch's launch leaves its totals
-    uint64_t *h_total = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around the builder's launches (its kernel time)
+    PinBuf<uint64_t> h_total;
+    EventPair ev;  // NOHUMAN_TRACE: around the builder's launches (its kernel time)
 };
 
-struct Slot {  // pinned host + device buffers of one in-flight batch
+// The pinned host + device buffers of one in-flight batch.  A slot owns them and its stream: they go back when the slot does, under
+// the slot's device -- ~Slot selects it and destroys the stream, the members free themselves behind it -- and a slot is made in
+// place and never copied or moved (Pipeline::slots).
+struct Slot {
     Engine *e = nullptr;
     hipStream_t stream = nullptr;
     // The sequences are classified IN PLACE: the raw text of the batch (both mate files' record text, as
     // read) is copied to the device as it is, and the kernel gets (start, length) of every sequence.
-    uint64_t *h_off = nullptr;   // n_seq starts into d_text
-    uint32_t *h_len = nullptr;   // n_seq lengths
-    nh_result *h_res = nullptr;
-    uint32_t *h_taxa = nullptr;
-    uint64_t *h_taxa_off = nullptr;
-    int *h_flag = nullptr;  // the engine's sticky error bits as of the end of this slot's batch (copied on its stream)
-    void *d_text = nullptr, *d_off = nullptr, *d_len = nullptr, *d_res = nullptr, *d_taxa = nullptr, *d_taxa_off = nullptr;
-    size_t cap_text = 0, cap_frag = 0, cap_taxa = 0;
+    PinBuf<uint64_t> h_off;   // n_seq starts into d_text
+    PinBuf<uint32_t> h_len;   // n_seq lengths
+    PinBuf<nh_result> h_res;
+    PinBuf<uint32_t> h_taxa;
+    PinBuf<uint64_t> h_taxa_off;
+    PinBuf<int> h_flag;  // the engine's sticky error bits as of the end of this slot's batch (copied on its stream)
+    DevBuf<char> d_text;
+    DevBuf<uint64_t> d_off, d_taxa_off;
+    DevBuf<uint32_t> d_len, d_taxa;
+    DevBuf<nh_result> d_res;
     uint64_t n_taxa = 0;
     bool busy = false;
     // the record table, per sequence {h, hlen, q, qlen}: what the builders, the quality mask and the read statistics read
-    uint32_t *h_rec = nullptr;
-    void *d_rec = nullptr;
-    size_t cap_rec = 0;
+    PinBuf<uint32_t[4]> h_rec;
+    DevBuf<uint32_t[4]> d_rec;
     // read lists: mate 1's id lengths beside the record table
-    uint32_t *h_idl = nullptr;
-    void *d_idl = nullptr;
-    size_t cap_idl = 0;
+    PinBuf<uint32_t> h_idl;
+    DevBuf<uint32_t> d_idl;
     BuiltOut human;  // split runs (nh_run_split): the classified-out records per mate; totals: bytes[2]
     BuiltOut mask;   // masked runs (nh_run_mask): every record per mate; totals: bytes[2], FAST blocks[2]
     BuiltOut lists;  // read lists (nh_run_ex): the calls table [0] and the human ids [1]; totals: bytes[2], lines[2]
@@ -423,139 +425,92 @@ struct Slot {  // pinned host + device buffers of one in-flight batch
     // host intervals (nh_run_intervals): the BED lines [0] and the interval records they are made from [1]; totals: bytes, lines,
     // fragments, covered bases -- and the bitmap k_cover_mark ORs into, one bit a byte of the batch's text, zeroed per batch
     BuiltOut cover;
-    uint32_t *d_cover = nullptr;
-    size_t cap_cover = 0;  // in words
+    DevBuf<uint32_t> d_cover;
     // runs with a minimum base quality (nh_run_minq): the text-sized buffer the classifier reads instead of d_text -- the
     // sequences with 'N' where the quality is low (nh_qmask.hip; the record table tells where the qualities lie) -- allocated
     // when first needed, and the masked bases of the slot's batches, read once, at the end of the run
-    void *d_qtext = nullptr;
-    unsigned long long *d_qcnt = nullptr;
-    size_t cap_qtext = 0;
-    hipEvent_t qev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around k_qmask
+    DevBuf<char> d_qtext;
+    DevBuf<unsigned long long> d_qcnt;
+    EventPair qev;  // NOHUMAN_TRACE: around k_qmask
     // runs that mask the reads' low-complexity stretches (nh_run_dust): d_qtext is reserved for them as well -- a copy of the text,
     // or the quality mask's output, in which k_rdust (nh_dust.hip) writes 'N' --, the scratch of its scan, the masked bases of the
     // slot's batches, the blocks that fill the slot's device once
-    uint64_t *d_dscr = nullptr;
-    size_t cap_dscr = 0;
-    unsigned long long *d_dcnt = nullptr;
+    DevBuf<uint64_t> d_dscr;
+    DevBuf<unsigned long long> d_dcnt;
     int dust_grid = 0;
-    hipEvent_t duev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around the three launches of the read DUST
-    hipEvent_t rev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around k_rstats (runs with read statistics)
-    hipEvent_t mev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around k_mdata_mark (runs with minimizer data)
+    EventPair duev;  // NOHUMAN_TRACE: around the three launches of the read DUST
+    EventPair rev;   // NOHUMAN_TRACE: around k_rstats (runs with read statistics)
+    EventPair mev;   // NOHUMAN_TRACE: around k_mdata_mark (runs with minimizer data)
     // runs with a host selection (nh_run_host): the results with call = 0 where the fragment is not host (nh_host.hip) -- what
     // decides host-ness on the device (d_hres: the builders that remove, mask, list or count host reads) and on the host (h_hres:
-    // the writer); d_res / h_res keep the true calls.  NULL in a run without a selection: the host-ness is then h_res's call != 0
-    void *d_hres = nullptr;
-    nh_result *h_hres = nullptr;
-    size_t cap_hres = 0;
-    hipEvent_t hev[2] = {nullptr, nullptr};  // NOHUMAN_TRACE: around k_host_filter
+    // the writer); d_res / h_res keep the true calls.  Empty in a run without a selection: the host-ness is then h_res's call != 0
+    DevBuf<nh_result> d_hres;
+    PinBuf<nh_result> h_hres;
+    EventPair hev;  // NOHUMAN_TRACE: around k_host_filter
     // the results that decide which fragments are host reads
     const nh_result *host_res() const { return h_hres ? h_hres : h_res; }
+
+    Slot() = default;
+    Slot(const Slot &) = delete;
+    Slot &operator=(const Slot &) = delete;
+    ~Slot() {
+        if (e) (void)dev_set(e->device);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
 };
 
 // what a buffer that must hold `need` is allocated with: some room, so that batches a little larger do not reallocate
 static size_t grow(size_t need) { return need + need / 4 + 4096; }
+// room for n elements in a buffer of a slot, grown by grow(); false: the allocation failed, the caller words the message
+template <class B>
+static bool have(B &buf, size_t n) { return buf.reserve(n, grow(n)) == hipSuccess; }
 
 static int slot_reserve(Slot &s, size_t ntext, size_t nfrag, size_t ntaxa) {
     if (dev_set(s.e->device) != hipSuccess) return set_error(NH_EDEVICE, "hipSetDevice failed");
     if (!s.h_flag) {
-        if (host_malloc((void **)&s.h_flag, 64, hipHostMallocDefault) != hipSuccess) return set_error(NH_EOOM, "cannot allocate batch buffers");
+        if (s.h_flag.reserve(1, 16) != hipSuccess) return set_error(NH_EOOM, "cannot allocate batch buffers");
         *s.h_flag = 0;
     }
-    if (ntext + 64 > s.cap_text) {
-        if (s.d_text) (void)hipFree(s.d_text);
-        s.cap_text = grow(ntext + 64);
-        if (dev_malloc(&s.d_text, s.cap_text) != hipSuccess)
-            return set_error(NH_EOOM, "cannot allocate batch buffers (%zu bytes)", s.cap_text);
-    }
-    if (nfrag > s.cap_frag) {
-        for (void *p : {(void *)s.h_off, (void *)s.h_len, (void *)s.h_res, (void *)s.h_taxa_off})
-            if (p) (void)hipHostFree(p);
-        for (void *p : {s.d_off, s.d_len, s.d_res, s.d_taxa_off})
-            if (p) (void)hipFree(p);
-        s.cap_frag = grow(nfrag);
-        const size_t ns = 2 * s.cap_frag + 2;
-        if (host_malloc((void **)&s.h_off, ns * 8, hipHostMallocDefault) != hipSuccess ||
-            host_malloc((void **)&s.h_len, ns * 4, hipHostMallocDefault) != hipSuccess ||
-            host_malloc((void **)&s.h_res, s.cap_frag * sizeof(nh_result), hipHostMallocDefault) != hipSuccess ||
-            host_malloc((void **)&s.h_taxa_off, (s.cap_frag + 1) * 8, hipHostMallocDefault) != hipSuccess ||
-            dev_malloc(&s.d_off, ns * 8) != hipSuccess || dev_malloc(&s.d_len, ns * 4) != hipSuccess ||
-            dev_malloc(&s.d_res, s.cap_frag * sizeof(nh_result)) != hipSuccess ||
-            dev_malloc(&s.d_taxa_off, (s.cap_frag + 1) * 8) != hipSuccess)
-            return set_error(NH_EOOM, "cannot allocate batch buffers (%zu fragments)", s.cap_frag);
-    }
-    if (ntaxa > s.cap_taxa) {
-        if (s.h_taxa) (void)hipHostFree(s.h_taxa);
-        if (s.d_taxa) (void)hipFree(s.d_taxa);
-        s.cap_taxa = grow(ntaxa);
-        if (host_malloc((void **)&s.h_taxa, s.cap_taxa * 4, hipHostMallocDefault) != hipSuccess ||
-            dev_malloc(&s.d_taxa, s.cap_taxa * 4) != hipSuccess)
-            return set_error(NH_EOOM, "cannot allocate k-mer taxa buffers");
-    }
+    if (!have(s.d_text, ntext + 64)) return set_error(NH_EOOM, "cannot allocate batch buffers (%zu bytes)", grow(ntext + 64));
+    // (2 * cap + 2 starts and lengths, cap results, cap + 1 offsets: all eight grow at the same batch)
+    const size_t cap = grow(nfrag), ns = 2 * cap + 2;
+    if (s.h_off.reserve(2 * nfrag + 2, ns) != hipSuccess || s.h_len.reserve(2 * nfrag + 2, ns) != hipSuccess ||
+        s.h_res.reserve(nfrag, cap) != hipSuccess || s.h_taxa_off.reserve(nfrag + 1, cap + 1) != hipSuccess ||
+        s.d_off.reserve(2 * nfrag + 2, ns) != hipSuccess || s.d_len.reserve(2 * nfrag + 2, ns) != hipSuccess ||
+        s.d_res.reserve(nfrag, cap) != hipSuccess || s.d_taxa_off.reserve(nfrag + 1, cap + 1) != hipSuccess)
+        return set_error(NH_EOOM, "cannot allocate batch buffers (%zu fragments)", cap);
+    if (!have(s.h_taxa, ntaxa) || !have(s.d_taxa, ntaxa)) return set_error(NH_EOOM, "cannot allocate k-mer taxa buffers");
     return NH_OK;
 }
 
 // a builder's buffers of a slot: blk_words words of scratch, out_cap[i] bytes of text for each of its n_out outputs;
 // `what` names the text buffers in the error message
 static int built_reserve(BuiltOut &o, size_t blk_words, const size_t out_cap[2], int n_out, const char *what) {
-    if (!o.h_total && host_malloc((void **)&o.h_total, 64, hipHostMallocDefault) != hipSuccess)
-        return set_error(NH_EOOM, "cannot allocate batch buffers");
-    if (blk_words > o.cap_blk) {
-        if (o.d_blk) (void)hipFree(o.d_blk);
-        o.d_blk = nullptr;
-        o.cap_blk = grow(blk_words);
-        if (dev_malloc(&o.d_blk, o.cap_blk * 8) != hipSuccess) return set_error(NH_EOOM, "cannot allocate batch buffers");
-    }
+    if (!have(o.d_blk, blk_words)) return set_error(NH_EOOM, "cannot allocate batch buffers");
     for (int i = 0; i < n_out; i++)
-        if (out_cap[i] > o.cap_out[i]) {
-            if (o.d_out[i]) (void)hipFree(o.d_out[i]);
-            o.d_out[i] = nullptr;
-            o.cap_out[i] = grow(out_cap[i]);
-            if (dev_malloc((void **)&o.d_out[i], o.cap_out[i]) != hipSuccess)
-                return set_error(NH_EOOM, "cannot allocate %s (%zu bytes)", what, o.cap_out[i]);
-        }
+        if (!have(o.d_out[i], out_cap[i])) return set_error(NH_EOOM, "cannot allocate %s (%zu bytes)", what, grow(out_cap[i]));
     return NH_OK;
 }
 
-// page-locked room for `n` bytes of a builder's output i on the host (the writer's copy for host encoders and files)
-static int built_reserve_host(BuiltOut &o, int i, size_t n, const char *what) {
-    if (n <= o.cap_host[i]) return NH_OK;
-    if (o.h_out[i]) (void)hipHostFree(o.h_out[i]);
-    o.cap_host[i] = grow(n);
-    if (host_malloc((void **)&o.h_out[i], o.cap_host[i], hipHostMallocDefault) != hipSuccess) {
-        o.h_out[i] = nullptr, o.cap_host[i] = 0;
-        return set_error(NH_EOOM, "cannot allocate %s (%zu bytes)", what, n);
-    }
-    return NH_OK;
-}
-
-// a page-locked array of a slot and its twin in HBM: n elements of `elem` bytes (`what`: their name in the message)
-static int slot_reserve_pair(void **h, void **d, size_t *cap, size_t n, size_t elem, const char *what) {
-    if (n <= *cap) return NH_OK;
-    if (*h) (void)hipHostFree(*h);
-    if (*d) (void)hipFree(*d);
-    *h = nullptr, *d = nullptr;
-    *cap = grow(n);
-    if (host_malloc(h, *cap * elem, hipHostMallocDefault) != hipSuccess || dev_malloc(d, *cap * elem) != hipSuccess)
-        return set_error(NH_EOOM, "cannot allocate batch buffers (%zu %s)", *cap, what);
-    return NH_OK;
+// a page-locked array of a slot and its twin in HBM: n elements (`what`: their name in the message)
+template <class T>
+static int slot_reserve_pair(PinBuf<T> &h, DevBuf<T> &d, size_t n, const char *what) {
+    if (have(h, n) && have(d, n)) return NH_OK;
+    return set_error(NH_EOOM, "cannot allocate batch buffers (%zu %s)", grow(n), what);
 }
 // the record table of nrec sequences of a slot (read statistics need nothing else)
-static int slot_reserve_rec(Slot &s, size_t nrec) { return slot_reserve_pair((void **)&s.h_rec, &s.d_rec, &s.cap_rec, nrec, 16, "records"); }
+static int slot_reserve_rec(Slot &s, size_t nrec) { return slot_reserve_pair(s.h_rec, s.d_rec, nrec, "records"); }
 // mate 1's id lengths of n fragments of a slot (read lists)
-static int slot_reserve_idl(Slot &s, size_t n) { return slot_reserve_pair((void **)&s.h_idl, &s.d_idl, &s.cap_idl, n, 4, "id lengths"); }
-// the second results array of nfrag fragments of a slot (runs with a host selection)
-static int slot_reserve_hres(Slot &s, size_t n) { return slot_reserve_pair((void **)&s.h_hres, &s.d_hres, &s.cap_hres, n, sizeof(nh_result), "host-filtered results"); }
+static int slot_reserve_idl(Slot &s, size_t n) { return slot_reserve_pair(s.h_idl, s.d_idl, n, "id lengths"); }
 
 // ntext bytes of masked text of a slot: what the classifier reads in a run with a minimum base quality or with --dust-reads
 static int slot_reserve_qtext(Slot &s, size_t ntext) {
-    if (ntext + 64 > s.cap_qtext) {
-        if (s.d_qtext) (void)hipFree(s.d_qtext);
-        s.d_qtext = nullptr;
-        s.cap_qtext = grow(ntext + 64);
-        if (dev_malloc(&s.d_qtext, s.cap_qtext) != hipSuccess)
-            return set_error(NH_EOOM, "cannot allocate the masked text (%zu bytes)", s.cap_qtext);
-    }
+    return have(s.d_qtext, ntext + 64) ? NH_OK : set_error(NH_EOOM, "cannot allocate the masked text (%zu bytes)", grow(ntext + 64));
+}
+// one of a slot's counters of masked bases: allocated once, zeroed on the slot's stream; `what` names it in the message
+static int slot_counter(Slot &s, DevBuf<unsigned long long> &c, const char *what) {
+    if (c.reserve(1) != hipSuccess) return set_error(NH_EOOM, "cannot allocate batch buffers");
+    if (hipMemsetAsync(c, 0, 8, s.stream) != hipSuccess) return set_error(NH_EDEVICE, "cannot clear the %s's counter", what);
     return NH_OK;
 }
 
@@ -564,18 +519,10 @@ static int slot_reserve_dust(Slot &s, size_t ntext, size_t nseq) {
     const int trc = slot_reserve_qtext(s, ntext);
     if (trc) return trc;
     const size_t words = (size_t)read_dust_scratch_words(nseq);
-    if (words > s.cap_dscr) {
-        if (s.d_dscr) (void)hipFree(s.d_dscr);
-        s.d_dscr = nullptr;
-        s.cap_dscr = grow(words);
-        if (dev_malloc(&s.d_dscr, s.cap_dscr * 8) != hipSuccess) return set_error(NH_EOOM, "cannot allocate the read DUST's scratch (%zu words)", s.cap_dscr);
-    }
-    if (!s.d_dcnt) {
-        if (dev_malloc((void **)&s.d_dcnt, 8) != hipSuccess) return set_error(NH_EOOM, "cannot allocate batch buffers");
-        if (hipMemsetAsync(s.d_dcnt, 0, 8, s.stream) != hipSuccess) return set_error(NH_EDEVICE, "cannot clear the read DUST's counter");
-        s.dust_grid = read_dust_grid_max();
-    }
-    return NH_OK;
+    if (!have(s.d_dscr, words)) return set_error(NH_EOOM, "cannot allocate the read DUST's scratch (%zu words)", grow(words));
+    if (s.d_dcnt) return NH_OK;
+    s.dust_grid = read_dust_grid_max();
+    return slot_counter(s, s.d_dcnt, "read DUST");
 }
 
 // the quality mask's buffers of a slot: the record table of nrec sequences, ntext bytes of masked text, the counter
@@ -584,37 +531,7 @@ static int slot_reserve_qmask(Slot &s, size_t ntext, size_t nrec) {
     if (rrc) return rrc;
     const int trc = slot_reserve_qtext(s, ntext);
     if (trc) return trc;
-    if (!s.d_qcnt) {
-        if (dev_malloc((void **)&s.d_qcnt, 8) != hipSuccess) return set_error(NH_EOOM, "cannot allocate batch buffers");
-        if (hipMemsetAsync(s.d_qcnt, 0, 8, s.stream) != hipSuccess) return set_error(NH_EDEVICE, "cannot clear the quality mask's counter");
-    }
-    return NH_OK;
-}
-
-static void slot_free(Slot &s) {
-    if (!s.e) return;
-    (void)dev_set(s.e->device);
-    for (BuiltOut *o : {&s.human, &s.mask, &s.lists, &s.taxon, &s.bam, &s.cover}) {
-        for (void *p : {(void *)o->h_out[0], (void *)o->h_out[1], (void *)o->h_total})
-            if (p) (void)hipHostFree(p);
-        for (void *p : {o->d_blk, (void *)o->d_out[0], (void *)o->d_out[1]})
-            if (p) (void)hipFree(p);
-        for (hipEvent_t ev : o->ev)
-            if (ev) (void)hipEventDestroy(ev);
-    }
-    for (void *p : {(void *)s.h_rec, (void *)s.h_idl, (void *)s.h_hres})
-        if (p) (void)hipHostFree(p);
-    for (void *p : {s.d_rec, s.d_idl, s.d_hres})
-        if (p) (void)hipFree(p);
-    for (void *p : {s.d_qtext, (void *)s.d_qcnt, (void *)s.d_dscr, (void *)s.d_dcnt, (void *)s.d_cover})
-        if (p) (void)hipFree(p);
-    for (hipEvent_t ev : {s.duev[0], s.duev[1], s.qev[0], s.qev[1], s.rev[0], s.rev[1], s.mev[0], s.mev[1], s.hev[0], s.hev[1]})
-        if (ev) (void)hipEventDestroy(ev);
-    for (void *p : {(void *)s.h_off, (void *)s.h_len, (void *)s.h_res, (void *)s.h_taxa, (void *)s.h_taxa_off, (void *)s.h_flag})
-        if (p) (void)hipHostFree(p);
-    for (void *p : {s.d_text, s.d_off, s.d_len, s.d_res, s.d_taxa, s.d_taxa_off})
-        if (p) (void)hipFree(p);
-    if (s.stream) (void)hipStreamDestroy(s.stream);
+    return s.d_qcnt ? NH_OK : slot_counter(s, s.d_qcnt, "quality mask");
 }
 
 // page-locked text buffers of the batches (RawBuf allocator): the H2D copy of a batch's raw text runs
@@ -818,7 +735,7 @@ private:
 
 // NOHUMAN_TRACE: the time between a slot's pair of events is added to *sum (the slot's stream was synchronised: both have
 // completed; without the trace there are no events)
-static void add_event_ms(const hipEvent_t ev[2], double *sum) {
+static void add_event_ms(const EventPair &ev, double *sum) {
     float ms = 0;
     if (ev[1] && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) *sum += ms;
 }
@@ -827,7 +744,7 @@ static void add_event_ms(const hipEvent_t ev[2], double *sum) {
 // to the slot's page-locked buffer and counted as fetched.  `what` / `item` name the buffers / the text in the error messages.
 static char *built_span(BuiltOut &o, int i, size_t tot, bool in_hbm, RunState &rs, int *wrc, const char *what, const char *item) {
     if (in_hbm) return o.d_out[i];
-    *wrc = built_reserve_host(o, i, tot, what);
+    if (!have(o.h_out[i], tot)) *wrc = set_error(NH_EOOM, "cannot allocate %s (%zu bytes)", what, tot);
     if (!*wrc && hipMemcpy(o.h_out[i], o.d_out[i], tot, hipMemcpyDeviceToHost) != hipSuccess)
         *wrc = set_error(NH_EDEVICE, "fetching a batch's %s from the device failed", item);
     rs.text_fetched += tot;
@@ -1157,14 +1074,12 @@ static int ensure_device_external(Engine *e) {
     std::lock_guard<std::mutex> lk(e->mu);
     if (e->d_external) return NH_OK;
     if (dev_set(e->device) != hipSuccess) return set_error(NH_EDEVICE, "hipSetDevice failed");
-    const size_t nb = std::max<size_t>(1, e->external.size()) * sizeof(uint64_t);
-    uint64_t *d = nullptr;
-    if (dev_malloc(&d, nb) != hipSuccess) return set_error(NH_EOOM, "cannot allocate the taxon id table on device %d", e->device);
-    if (!e->external.empty() && hipMemcpy(d, e->external.data(), e->external.size() * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(d);
+    const size_t n = std::max<size_t>(1, e->external.size());
+    DevBuf<uint64_t> d;
+    if (d.reserve(n) != hipSuccess) return set_error(NH_EOOM, "cannot allocate the taxon id table on device %d", e->device);
+    if (!e->external.empty() && hipMemcpy(d, e->external.data(), e->external.size() * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess)
         return set_error(NH_EDEVICE, "cannot copy the taxon id table to device %d", e->device);
-    }
-    e->d_external = d;
+    e->d_external = d.p, d.p = nullptr;  // (the engine's from here on: it frees it with its other fields)
     return NH_OK;
 }
 
@@ -1572,24 +1487,19 @@ static int selector_bins(const Engine *e0, const RunRequest &r, std::vector<uint
 // What one device holds for the whole run, given back when the run's scope ends
 struct RunBuffers {
     int device = -1;
-    uint64_t *counters = nullptr;  // the counters the classify kernels of this run add to (RunState::d_run_counters points here)
-    uint8_t *bin_of = nullptr;     // per-taxon outputs: the selectors' bins
+    DevBuf<uint64_t> counters;  // the counters the classify kernels of this run add to (RunState::d_run_counters points here)
+    DevBuf<uint8_t> bin_of;     // per-taxon outputs: the selectors' bins
     // host selection: host_of, and the pair of counters {host, spared} k_host_filter adds to
-    uint8_t *host_of = nullptr;
-    unsigned long long *hcnt = nullptr;
-    unsigned long long *racc = nullptr;  // read statistics: one block of four accumulators, zeroed with min_len all-ones
-    unsigned long long *hbcnt = nullptr; // host bases only: {host, masked, closed} bases the mask builder and the closing add to
+    DevBuf<uint8_t> host_of;
+    DevBuf<unsigned long long> hcnt;
+    DevBuf<unsigned long long> racc;  // read statistics: one block of four accumulators, zeroed with min_len all-ones
+    DevBuf<unsigned long long> hbcnt; // host bases only: {host, masked, closed} bases the mask builder and the closing add to
     // minimizer data: one zeroed bitmap (a bit a cell) and one array of hit groups per node
-    uint32_t *marks = nullptr;
-    unsigned long long *groups = nullptr;
+    DevBuf<uint32_t> marks;
+    DevBuf<unsigned long long> groups;
     RunBuffers() = default;
-    RunBuffers(const RunBuffers &) = delete;
-    RunBuffers &operator=(const RunBuffers &) = delete;
-    ~RunBuffers() {
-        if (!counters && !bin_of && !host_of && !hcnt && !racc && !marks && !groups && !hbcnt) return;
-        (void)dev_set(device);
-        for (void *p : {(void *)host_of, (void *)hcnt, (void *)marks, (void *)groups, (void *)counters, (void *)racc, (void *)bin_of, (void *)hbcnt})
-            if (p) (void)hipFree(p);
+    ~RunBuffers() {  // (the members go back behind this, under their device)
+        if (device >= 0) (void)dev_set(device);
     }
 };
 
@@ -1598,13 +1508,13 @@ struct RunBuffers {
 static int alloc_run_buffers(RunBuffers &b, const Engine *e, const std::vector<uint8_t> &bin_of, const std::vector<uint8_t> &host_of, bool rst,
                              size_t md_mark_bytes, size_t md_nodes, bool mdt, bool hbo) {
     b.device = e->device;
-    const size_t nb = (CNT_N + 12) * sizeof(uint64_t);  // (+12: the words of the instrumented kernel variant)
-    if (dev_set(e->device) != hipSuccess || dev_malloc((void **)&b.counters, nb) != hipSuccess || hipMemset(b.counters, 0, nb) != hipSuccess)
+    const size_t nc = CNT_N + 12, nb = nc * sizeof(uint64_t);  // (+12: the words of the instrumented kernel variant)
+    if (dev_set(e->device) != hipSuccess || b.counters.reserve(nc) != hipSuccess || hipMemset(b.counters, 0, nb) != hipSuccess)
         return set_error(NH_EDEVICE, "cannot allocate the run's counters on device %d", e->device);
-    if (!bin_of.empty() && (dev_malloc((void **)&b.bin_of, bin_of.size()) != hipSuccess ||
+    if (!bin_of.empty() && (b.bin_of.reserve(bin_of.size()) != hipSuccess ||
                             hipMemcpy(b.bin_of, bin_of.data(), bin_of.size(), hipMemcpyHostToDevice) != hipSuccess))
         return set_error(NH_EDEVICE, "cannot copy the selectors' bins to device %d", e->device);
-    if (!host_of.empty() && (dev_malloc((void **)&b.host_of, host_of.size()) != hipSuccess || dev_malloc((void **)&b.hcnt, 16) != hipSuccess ||
+    if (!host_of.empty() && (b.host_of.reserve(host_of.size()) != hipSuccess || b.hcnt.reserve(2) != hipSuccess ||
                              hipMemcpy(b.host_of, host_of.data(), host_of.size(), hipMemcpyHostToDevice) != hipSuccess ||
                              hipMemset(b.hcnt, 0, 16) != hipSuccess || hipDeviceSynchronize() != hipSuccess))
         return set_error(NH_EDEVICE, "cannot copy the host selection's table to device %d", e->device);
@@ -1612,15 +1522,15 @@ static int alloc_run_buffers(RunBuffers &b, const Engine *e, const std::vector<u
         nh_read_class init[4];
         memset(init, 0, sizeof init);
         for (nh_read_class &c : init) c.min_len = ~0ull;
-        if (dev_malloc((void **)&b.racc, sizeof init) != hipSuccess || hipMemcpy(b.racc, init, sizeof init, hipMemcpyHostToDevice) != hipSuccess)
+        if (b.racc.reserve(sizeof init / 8) != hipSuccess || hipMemcpy(b.racc, init, sizeof init, hipMemcpyHostToDevice) != hipSuccess)
             return set_error(NH_EDEVICE, "cannot allocate the read statistics' accumulators on device %d", e->device);
     }
-    if (hbo && (dev_set(e->device) != hipSuccess || dev_malloc((void **)&b.hbcnt, 24) != hipSuccess || hipMemset(b.hbcnt, 0, 24) != hipSuccess ||
+    if (hbo && (dev_set(e->device) != hipSuccess || b.hbcnt.reserve(3) != hipSuccess || hipMemset(b.hbcnt, 0, 24) != hipSuccess ||
                 hipDeviceSynchronize() != hipSuccess))
         return set_error(NH_EDEVICE, "cannot allocate the host bases' counters on device %d", e->device);
     if (mdt) {
-        if (dev_malloc((void **)&b.marks, std::max<size_t>(md_mark_bytes, 4)) != hipSuccess ||
-            dev_malloc((void **)&b.groups, std::max<size_t>(md_nodes, 1) * 8) != hipSuccess)
+        const size_t mark_words = std::max<size_t>((md_mark_bytes + 3) / 4, 1), n_groups = std::max<size_t>(md_nodes, 1);
+        if (b.marks.reserve(mark_words) != hipSuccess || b.groups.reserve(n_groups) != hipSuccess)
             return set_error(NH_EOOM, "minimizer data: cannot allocate the bitmap of %zu bytes and %zu counters on device %d", md_mark_bytes, md_nodes,
                              e->device);
         if (hipMemset(b.marks, 0, std::max<size_t>(md_mark_bytes, 4)) != hipSuccess ||
@@ -1739,9 +1649,9 @@ static void collect_mdata(const std::vector<RunBuffers> &dbuf, RunState &rs, siz
     }
     mdn.v[3].assign(sum.begin(), sum.end());
     // two counts with the array of hit groups as their bins: the marked cells, then all cells
-    hipEvent_t cev[2] = {nullptr, nullptr};
+    EventPair cev;
     if (he == hipSuccess) he = dev_set(e0->device);
-    if (he == hipSuccess && getenv("NOHUMAN_TRACE") && (hipEventCreate(&cev[0]) != hipSuccess || hipEventCreate(&cev[1]) != hipSuccess)) he = hipErrorUnknown;
+    if (he == hipSuccess && getenv("NOHUMAN_TRACE") && cev.create() != hipSuccess) he = hipErrorUnknown;
     for (int pass = 0; pass < 2 && he == hipSuccess; pass++) {
         he = hipMemsetAsync(dbuf[0].groups, 0, md_nodes * 8, e0->stream);
         if (he == hipSuccess && cev[0]) he = hipEventRecord(cev[0], e0->stream);
@@ -1752,8 +1662,6 @@ static void collect_mdata(const std::vector<RunBuffers> &dbuf, RunState &rs, siz
         mdn.v[pass == 0 ? 5 : 7].assign(part.begin(), part.end());
         if (he == hipSuccess && pass == 0) add_event_ms(cev, md_count_ms);
     }
-    for (hipEvent_t ev : cev)
-        if (ev) (void)hipEventDestroy(ev);
     if (he != hipSuccess) rs.fail(NH_EDEVICE, std::string("minimizer data, counting the bitmap: ") + hipGetErrorString(he));
 }
 
@@ -1904,11 +1812,11 @@ struct FlushJob {
 // One active output builder of a run: which BuiltOut of the slot, how many words of totals come back with the results, where its
 // kernel time is summed.  One pass in front of or behind the classifier: its pair of events, where its kernel time is summed.
 struct Builder { BuiltOut Slot::*out; size_t total_words; double RunState::*ms; };
-struct Pass { hipEvent_t (Slot::*ev)[2]; double RunState::*ms; };
+struct Pass { EventPair Slot::*ev; double RunState::*ms; };
 
 // a launch on the slot's stream between a pair of events (NOHUMAN_TRACE; none without it); a failure fails the run under `name`
 template <class F>
-static void timed_launch(RunState &rs, hipStream_t stream, const hipEvent_t ev[2], const char *name, F launch) {
+static void timed_launch(RunState &rs, hipStream_t stream, const EventPair &ev, const char *name, F launch) {
     if (ev[0]) (void)hipEventRecord(ev[0], stream);
     hipError_t he = launch();
     if (ev[1] && he == hipSuccess) he = hipEventRecord(ev[1], stream);
@@ -1920,7 +1828,7 @@ template <class A>
 static void batch_records(A &x, const Slot &s, const Batch &b) {
     x.text = (const char *)s.d_text, x.ntext = b.ntext();
     x.seq_len = (const uint32_t *)s.d_len;
-    x.rec = (const uint32_t *)s.d_rec;
+    x.rec = (const uint32_t *)s.d_rec.p;
     x.mates = b.h2 ? 2 : 1;
 }
 // ... the sequences' starts and which mate is FASTQ (HumanOutArgs, TaxonOutArgs, MaskArgs, QmaskArgs, RstatsArgs)
@@ -1933,7 +1841,7 @@ static void batch_source(A &x, const Slot &s, const Batch &b) {
 // where a builder's kernels write: its n_out outputs, its scratch, the engine's error word
 template <class A>
 static void built_sink(A &x, const BuiltOut &o, int n_out, const Slot &s) {
-    for (int i = 0; i < n_out; i++) x.out[i] = o.d_out[i], x.cap[i] = o.cap_out[i];
+    for (int i = 0; i < n_out; i++) x.out[i] = o.d_out[i], x.cap[i] = o.d_out[i].cap;
     x.blk = (uint64_t *)o.d_blk;
     x.error = s.e->d_error + LAUNCH_SLOTS;
 }
@@ -2007,19 +1915,14 @@ struct Pipeline {
 
     // the stream and, under NOHUMAN_TRACE, the events of every slot
     int create_slots() {
-        slots.resize((size_t)sh.NS * sh.G);
+        slots = std::vector<Slot>((size_t)sh.NS * sh.G);
         for (int i = 0; i < sh.NS * sh.G; i++) {
             Slot &s = slots[i];
             s.e = engines[i / sh.NS];
             bool ok = dev_set(s.e->device) == hipSuccess && hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) == hipSuccess;
-            for (const Builder &bd : builders)
-                for (hipEvent_t &ev : (s.*bd.out).ev) ok = ok && (!sh.trace || hipEventCreate(&ev) == hipSuccess);
-            for (const Pass &ps : passes)
-                for (hipEvent_t &ev : s.*ps.ev) ok = ok && (!sh.trace || hipEventCreate(&ev) == hipSuccess);
-            if (!ok) {
-                for (auto &x : slots) slot_free(x);
-                return set_error(NH_EDEVICE, "cannot create streams");
-            }
+            for (const Builder &bd : builders) ok = ok && (!sh.trace || (s.*bd.out).ev.create() == hipSuccess);
+            for (const Pass &ps : passes) ok = ok && (!sh.trace || (s.*ps.ev).create() == hipSuccess);
+            if (!ok) return set_error(NH_EDEVICE, "cannot create streams");
         }
         return NH_OK;
     }
@@ -2356,8 +2259,6 @@ struct Pipeline {
         if (step == RESERVE) {  // a mate's bins: the classified-out text at most, and the bins' alignment
             const size_t out_cap[2] = {b.len1 + b.n * 36 + 64 + 256 * (size_t)K, b.len2 + b.n * 36 + 64 + 256 * (size_t)K};
             if (!*rc) *rc = slot_reserve_rec(s, b.n * (size_t)mates);
-            if (!*rc && !s.taxon.h_total && host_malloc((void **)&s.taxon.h_total, 4 * NH_MAX_TAXON_OUTS * sizeof(uint64_t), hipHostMallocDefault) != hipSuccess)
-                *rc = set_error(NH_EOOM, "cannot allocate batch buffers");
             // (the scratch: block sums of every mate and bin, then start[2][K] and total[2][K]: TaxonOutArgs)
             if (!*rc) *rc = built_reserve(s.taxon, 2 * (size_t)K * human_out_blocks(b.n) + 4 * (size_t)K, out_cap, mates, "per-taxon buffers");
         } else if (step == LAUNCH) {
@@ -2378,7 +2279,7 @@ struct Pipeline {
                 for (int k = 0; k < K; k++)
                     if (bytes[k]) end = (size_t)(start[k] + bytes[k]);
                 if (!end) continue;
-                if (end > s.taxon.cap_out[m]) {
+                if (end > s.taxon.d_out[m].cap) {
                     *rc = set_error(NH_EDEVICE, "per-taxon builder: a bin ends outside its buffer");
                     break;
                 }
@@ -2464,7 +2365,7 @@ struct Pipeline {
                 const bool want_host = sh.split_files ? o == 1 : a->keep_human != 0;
                 for (size_t i = 0; i < b.n; i++) rs.bam_records[o] += (uint64_t)sh.mates * ((s.host_res()[i].call != 0) == want_host);
                 if (!tot) continue;
-                if (tot > s.bam.cap_out[o]) {
+                if (tot > s.bam.d_out[o].cap) {
                     *rc = set_error(NH_EDEVICE, "BAM-out builder: an output ends outside its buffer");
                     break;
                 }
@@ -2537,12 +2438,7 @@ struct Pipeline {
             // (the scratch: the larger of the mark pass's and the interval builder's, the records' total, the line builder's block sums and totals)
             if (!*rc) *rc = built_reserve(s.cover, pass_words + 1 + 3 * (size_t)cover_line_blocks(nrec) + 4, out_cap, 2, "host-interval buffers");
             const size_t cw = (size_t)cover_words(b.ntext());
-            if (!*rc && cw > s.cap_cover) {
-                if (s.d_cover) (void)hipFree(s.d_cover);
-                s.d_cover = nullptr;
-                s.cap_cover = grow(cw);
-                if (dev_malloc((void **)&s.d_cover, s.cap_cover * 4) != hipSuccess) *rc = set_error(NH_EOOM, "cannot allocate the host intervals' bitmap (%zu words)", s.cap_cover);
-            }
+            if (!*rc && !have(s.d_cover, cw)) *rc = set_error(NH_EOOM, "cannot allocate the host intervals' bitmap (%zu words)", grow(cw));
         } else if (step == LAUNCH) {
             const uint64_t ntext = b.ntext();
             const size_t nrec = sh.cover ? cover_max_records(b, nullptr) : 0;
@@ -2556,13 +2452,13 @@ struct Pipeline {
             ca.cover = s.d_cover, ca.scratch = scratch, ca.error = d_error;
             CoverIvlArgs ia{};
             ia.cover = s.d_cover, ia.ntext = ntext, ia.seq_off = ca.seq_off, ia.seq_len = ca.seq_len, ia.n_seq = nseq;
-            ia.rec = (uint32_t *)s.cover.d_out[1], ia.cap = nrec, ia.total = n_ivl, ia.scratch = scratch, ia.error = d_error;
+            ia.rec = (uint32_t *)s.cover.d_out[1].p, ia.cap = nrec, ia.total = n_ivl, ia.scratch = scratch, ia.error = d_error;
             CoverLinesArgs la{};
             la.text = (const char *)s.d_text, la.ntext = ntext;
-            la.rec = (const uint32_t *)s.d_rec, la.idlen = (const uint32_t *)s.d_idl, la.res = (const nh_result *)s.d_res;
+            la.rec = (const uint32_t *)s.d_rec.p, la.idlen = (const uint32_t *)s.d_idl, la.res = (const nh_result *)s.d_res;
             la.ext = s.e->d_external, la.n_ext = s.e->external.size(), la.n = b.n, la.mates = mates;
             la.ivl = ia.rec, la.n_ivl = n_ivl, la.cap_ivl = nrec;
-            la.out = s.cover.d_out[0], la.cap = s.cover.cap_out[0];
+            la.out = s.cover.d_out[0], la.cap = s.cover.d_out[0].cap;
             la.blk = n_ivl + 1, la.nblk = cover_line_blocks(nrec);
             la.total = s.cover.d_total = la.blk + 3 * la.nblk;
             la.error = d_error;
@@ -2695,6 +2591,8 @@ struct Pipeline {
         uint64_t ntaxa = 0;
         for (size_t i = 0; rs.want_k && i < b.n; i++) ntaxa += b.kmer_taxa(i, s.e->info.k);
         int rc = slot_reserve(s, b.ntext(), b.n, ntaxa + 1);
+        for (const Builder &bd : builders)  // (the totals that come back with the results: queue_results copies total_words of them)
+            if (!rc && (s.*bd.out).h_total.reserve(bd.total_words) != hipSuccess) rc = set_error(NH_EOOM, "cannot allocate batch buffers");
         if (sh.split) build_human(RESERVE, s, b, nullptr, &rc);
         if (sh.taxa) build_taxon(RESERVE, s, b, nullptr, &rc);
         if (sh.mask) build_mask(RESERVE, s, b, nullptr, &rc);
@@ -2704,7 +2602,7 @@ struct Pipeline {
         if (!rc && sh.qm) rc = slot_reserve_qmask(s, b.ntext(), b.n * (size_t)sh.mates);
         if (!rc && sh.dust) rc = slot_reserve_dust(s, b.ntext(), b.n * (size_t)sh.mates);
         if (!rc && sh.rst) rc = slot_reserve_rec(s, b.n * (size_t)sh.mates);
-        if (!rc && sh.hsel) rc = slot_reserve_hres(s, b.n);
+        if (!rc && sh.hsel) rc = slot_reserve_pair(s.h_hres, s.d_hres, b.n, "host-filtered results");
         if (!rc && (sh.qm || sh.rst)) rc = check_quality_lengths(b);
         return rc;
     }
@@ -2737,7 +2635,7 @@ struct Pipeline {
             nbases += r1.slen;
             if (sh.idl) s.h_idl[i] = r1.idlen;
             if (sh.want_rec) {
-                uint32_t *hr = s.h_rec + 4 * i * mates;
+                uint32_t *hr = s.h_rec[i * mates];
                 hr[0] = r1.h, hr[1] = r1.hlen, hr[2] = r1.q, hr[3] = r1.qlen;
                 if (rs.paired) {
                     const RecRef &r2 = b.h2->recs[b.off2 + i];
@@ -3116,7 +3014,7 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
     if (sh.rst) collect_rstats(dbuf, rs, racc);
     if (sh.hbo) collect_hostbases(dbuf, rs);
     if (sh.mdt) collect_mdata(dbuf, rs, md_mark_bytes, mdn, &md_count_ms);
-    for (auto &s : p.slots) slot_free(s);
+    p.slots.clear();  // (every slot's buffers, events and stream go back here, each under its device)
     if (sh.trace_run)
         print_run_trace(sh, rs, p.clk, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), racc, mdn, md_count_ms, dev_host);
     if (rs.err_code != NH_OK) return set_error(rs.err_code, "%s", rs.err_msg.c_str());
