@@ -1051,6 +1051,68 @@ int nh_run_engine_hostbases(nh_engine *e, const nh_run_args *args, const nh_run_
 int nh_cover_close_device(nh_engine *e, void *d_cover, uint64_t text_len, const void *d_seq_starts, const void *d_seq_lens,
                           uint64_t n_seq, uint32_t gap, void *d_closed_bases, void *stream);
 
+/*
+ * Host cut (--host-cut, --host-min-piece; nh_cut.hip; tests/hostcut_model.py is the specification): a masked run
+ * that CUTS the host stretches out of a host fragment and writes what is left as records of their own, where --host-bases-only
+ * writes 'N' over them.  A run of 300 'N' in the middle of a 40 kb read breaks assemblers, polishers and mappers; a ligation chimera
+ * should leave the run as its non-host half, not as that half with a tail of 'N'.
+ *
+ * COVERAGE and CLOSING are host bases only's (above), bit for bit: the mark pass on the copy the classifier read, with the host
+ * selection where the run has one, closed with gap = G over the sequences of host fragments.  PIECES: the maximal runs [a, b) of
+ * bases of a host fragment's sequence that the closed coverage does not cover, with b - a >= min_piece (runs that touch an end of
+ * the sequence included).  A piece's RECORD: the header's first 1 + idlen bytes (the id as the read lists print it, with '@' / '>'),
+ * ":<a>-<b>" in decimal (0-based, half-open: the BED's coordinates), the rest of the header, "\n", the INPUT's own bases [a, b) (their
+ * case kept; never the quality- or DUST-masked copy) and, FASTQ, "\n+\n" and the qualities [a, b), "\n".  Pieces are written in
+ * input order, by fragment, then by a.  A host fragment without a piece writes nothing; one without a covered base writes one piece,
+ * "<id>:0-<len>".  Every other fragment is written whole, as nh_run_mask writes an unclassified record.  Every other output of the
+ * run (-k, the report, the read lists, human_out1 -- the host records whole --, per-taxon outputs, the read statistics, the minimizer
+ * data, the three totals, a host intervals' file: the coverage BEFORE the closing) is byte for byte the masked run's; not enabled,
+ * nothing is allocated or launched.  SINGLE-END ONLY: the pieces of two mates cannot stay in step.  A FASTQ record whose quality
+ * line is not as long as its sequence ends the run (NH_EIO), as with a minimum base quality: a piece's qualities are a slice.
+ *
+ * nh_run_hostcut / nh_run_engine_hostcut: nh_run_hostbases with the struct.  hc NULL or hc->enable 0: exactly nh_run_hostbases.  A
+ * struct_size smaller than the struct, enable without extras->mask, enable together with an enabled nh_host_bases, gap above
+ * NH_HOST_GAP_MAX, min_piece 0 or above 2^31 - 1, a second input or a paired BAM as in1: NH_EINVAL before any device is touched,
+ * nothing created.  The database must be one the mark pass supports: NH_EINVAL, the reason named, once it is open.  The counts are
+ * exact, summed over the run's devices, and 0 where the run fails after its arguments were accepted: host_bases (the sequence bases
+ * of host fragments) = piece_bases (written in `pieces` pieces) + cut_bases (the closed coverage inside host sequences) + short_bases
+ * (uncovered, in runs shorter than min_piece); dropped_reads (host fragments without a piece); closed_bases (as in nh_host_bases).
+ *
+ * nh_host_cut_device: the item list and the text builder on caller-owned device buffers, on the engine's device, on `stream`; it
+ * waits for the stream.  d_text (4-byte aligned, text_len < 2^32 bytes, only read, no byte behind the dword of its last byte),
+ * d_records (n x {uint32 header start, header length, qualities start, qualities length}, 16-byte aligned), d_seq_starts (uint64),
+ * d_seq_lens, d_idlen (uint32), d_results (nh_result: call != 0 is a host fragment), fastq (0: FASTA records, no qualities),
+ * d_cover (ceil(text_len / 32) uint32, laid out as nh_host_cover_device leaves it; a bit outside a sequence changes nothing),
+ * min_piece (1 .. 2^31 - 1).  d_out receives the text, at most cap bytes, *d_total (uint64) its length; d_counts: NULL, or six
+ * uint64 in device memory that are ADDED to: host_bases, pieces, piece_bases, cut_bases, short_bases, dropped_reads.  *error_bits
+ * (an int32 of the caller's in device memory) gets bit 4096 for a sequence or a record's field outside the text or an id longer than
+ * its header, bit 16384 for a FASTQ host record whose quality line is not as long as its sequence (nothing of such a record is
+ * written), bit 8192 for a text above cap: total 0 and nothing written.
+ */
+typedef struct {
+    uint32_t struct_size;    /* sizeof(nh_host_cut) of the caller */
+    uint32_t enable;         /* 0: no such run */
+    uint32_t gap;            /* 0 .. NH_HOST_GAP_MAX */
+    uint32_t min_piece;      /* 1 .. 2^31 - 1; the CLI's default is 35 = k */
+    uint64_t host_bases;     /* out */
+    uint64_t pieces;         /* out */
+    uint64_t piece_bases;    /* out */
+    uint64_t cut_bases;      /* out */
+    uint64_t short_bases;    /* out */
+    uint64_t dropped_reads;  /* out */
+    uint64_t closed_bases;   /* out */
+} nh_host_cut;
+int nh_run_hostcut(const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality, const char *read_stats_path,
+                   nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs, nh_minimizer_data *md, nh_host_filter *hf,
+                   nh_read_dust *rd, nh_host_intervals *hi, nh_host_bases *hb, nh_host_cut *hc, nh_stats *stats);
+int nh_run_engine_hostcut(nh_engine *e, const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality,
+                          const char *read_stats_path, nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs,
+                          nh_minimizer_data *md, nh_host_filter *hf, nh_read_dust *rd, nh_host_intervals *hi, nh_host_bases *hb,
+                          nh_host_cut *hc, nh_stats *stats);
+int nh_host_cut_device(nh_engine *e, const void *d_text, uint64_t text_len, const void *d_records, const void *d_seq_starts,
+                       const void *d_seq_lens, const void *d_idlen, const void *d_results, uint64_t n, int fastq, const void *d_cover,
+                       uint32_t min_piece, void *d_out, uint64_t cap, void *d_total, void *d_counts, void *error_bits, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

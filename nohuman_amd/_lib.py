@@ -111,6 +111,15 @@ class nh_host_bases(C.Structure):
 NH_HOST_GAP_MAX = 4096
 
 
+class nh_host_cut(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("enable", C.c_uint32), ("gap", C.c_uint32), ("min_piece", C.c_uint32),
+                ("host_bases", C.c_uint64), ("pieces", C.c_uint64), ("piece_bases", C.c_uint64), ("cut_bases", C.c_uint64),
+                ("short_bases", C.c_uint64), ("dropped_reads", C.c_uint64), ("closed_bases", C.c_uint64)]
+
+
+HOST_CUT_COUNTS = ("host_bases", "pieces", "piece_bases", "cut_bases", "short_bases", "dropped_reads")  # nh_host_cut_device's d_counts
+
+
 class nh_gzip_model_opts(C.Structure):
     _fields_ = [("ways", C.c_uint32), ("region_bytes", C.c_uint32), ("chunk_bytes", C.c_uint64), ("prices", C.c_int32),
                 ("bgzf", C.c_int32), ("threads", C.c_uint32), ("reserved", C.c_uint32),
@@ -288,6 +297,15 @@ SYMBOLS = {
                                           C.POINTER(nh_read_stats), C.POINTER(nh_taxon_out), C.c_uint32, C.POINTER(nh_minimizer_data),
                                           C.POINTER(nh_host_filter), C.POINTER(nh_read_dust), C.POINTER(nh_host_intervals),
                                           C.POINTER(nh_host_bases), C.POINTER(nh_stats)]),
+    "nh_run_hostcut": (C.c_int, [C.POINTER(nh_run_args), C.POINTER(nh_run_extras), C.c_uint32, C.c_char_p, C.POINTER(nh_read_stats),
+                                 C.POINTER(nh_taxon_out), C.c_uint32, C.POINTER(nh_minimizer_data), C.POINTER(nh_host_filter),
+                                 C.POINTER(nh_read_dust), C.POINTER(nh_host_intervals), C.POINTER(nh_host_bases), C.POINTER(nh_host_cut),
+                                 C.POINTER(nh_stats)]),
+    "nh_run_engine_hostcut": (C.c_int, [_P, C.POINTER(nh_run_args), C.POINTER(nh_run_extras), C.c_uint32, C.c_char_p,
+                                        C.POINTER(nh_read_stats), C.POINTER(nh_taxon_out), C.c_uint32, C.POINTER(nh_minimizer_data),
+                                        C.POINTER(nh_host_filter), C.POINTER(nh_read_dust), C.POINTER(nh_host_intervals),
+                                        C.POINTER(nh_host_bases), C.POINTER(nh_host_cut), C.POINTER(nh_stats)]),
+    "nh_host_cut_device": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, _P, _P, C.c_uint64, C.c_int, _P, C.c_uint32, _P, C.c_uint64, _P, _P, _P, _P]),
     "nh_cover_close_device": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint64, C.c_uint32, _P, _P]),
     "nh_host_cover_device": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint64, _P, C.c_uint64, _P, _P]),
     "nh_cover_intervals_device": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint64, _P, C.c_uint64, _P, _P, _P]),

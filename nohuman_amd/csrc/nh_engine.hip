@@ -1006,6 +1006,12 @@ int check_error_flag(Engine *e) {
             return set_error(NH_EDEVICE, "host intervals: a sequence or a record's header lies outside its batch's text (it was skipped: nothing of it was read or marked)");
         if (flag & NH_ERR_COVER_CAP)
             return set_error(NH_EDEVICE, "host intervals: the intervals of a batch do not fit their buffer (nothing of them was written)");
+        if (flag & NH_ERR_CUT)
+            return set_error(NH_EDEVICE, "host cut: a sequence or a record's field lies outside its batch's text, or an id is longer than its header (nothing of the record was written)");
+        if (flag & NH_ERR_CUT_CAP)
+            return set_error(NH_EDEVICE, "host cut: the items or the text of a batch do not fit their buffer (nothing of them was written)");
+        if (flag & NH_ERR_CUT_QLEN)
+            return set_error(NH_EIO, "host cut: a host record's quality line is not as long as its sequence (nothing of the record was written)");
         if (flag & 32)
             return set_error(NH_EIO,"quality mask / read statistics: a record's quality line is not as long as its sequence, or the record lies outside its batch's text");
         return set_error(NH_ECAPACITY, "a fragment hit more than 2048 distinct taxa");

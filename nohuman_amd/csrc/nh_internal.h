@@ -336,6 +336,39 @@ hipError_t launch_cover_mark(Engine *e, const CoverArgs &c, hipStream_t stream);
 hipError_t launch_cover_intervals(const CoverIvlArgs &a, hipStream_t stream);
 hipError_t launch_cover_lines(const CoverLinesArgs &a, hipStream_t stream);
 hipError_t launch_cover_close(const CoverCloseArgs &a, hipStream_t stream);
+// Host cut (nh_cut.hip; nh_run_hostcut): a single-end masked run whose host fragments are written as PIECES -- the
+// maximal runs of at least min_piece bases that the closed cover bitmap does not cover, each a record of its own, "<id>:<a>-<b>" --
+// and every other fragment whole.  k_cut_item_* turn the bitmap and the calls into the items {seq, a, b} (a whole record: 0, slen),
+// k_cut_* the items into text.  The engine's sticky error word: NH_ERR_CUT, a record whose fields leave the text or whose id is
+// longer than its header (nothing of it is written); NH_ERR_CUT_QLEN, a FASTQ host record whose quality line is not as long as its
+// sequence (nothing of it is written); NH_ERR_CUT_CAP, a list or a text above its capacity, total 0 and nothing written.
+constexpr int NH_ERR_CUT = 4096, NH_ERR_CUT_CAP = 8192, NH_ERR_CUT_QLEN = 16384;
+enum { CUT_HOST_BASES, CUT_PIECES, CUT_PIECE_BASES, CUT_CUT_BASES, CUT_SHORT_BASES, CUT_DROPPED, CUT_COUNTS };
+struct CutArgs {
+    const char *text;         // the batch's text (d_text: the INPUT's bases), ntext bytes
+    uint64_t ntext;
+    const uint64_t *seq_off;  // n sequence starts (absolute), as classified
+    const uint32_t *seq_len;  // n sequence lengths
+    const uint32_t *rec;      // n {header start (absolute), header length, qualities start (absolute), length}
+    const uint32_t *idlen;    // n: the length of the id (RecRef::idlen)
+    const nh_result *res;     // n results: call != 0 is a host fragment
+    uint64_t n;
+    int fastq;
+    const uint32_t *cover;    // cover_words(ntext) words: the closed coverage, one bit a byte of the text
+    uint32_t min_piece;       // >= 1
+    uint32_t *items;          // cap_items items of three words: sequence, a, b
+    uint64_t cap_items;
+    uint64_t max_item;        // bytes of the longest item's output there can be: the write kernel's spans
+    char *out;                // cap bytes
+    uint64_t cap;
+    uint64_t *scratch;        // cut_scratch_words(n, cap_items) words
+    uint64_t *total;          // two words: the bytes written, the items
+    unsigned long long *counts;  // NULL or CUT_COUNTS counters the waves add to
+    int *error;
+};
+uint64_t cut_scratch_words(uint64_t n, uint64_t cap_items);
+uint64_t cut_max_pieces(uint64_t slen, uint32_t min_piece);  // P(L) = (L + k) / (M + k), 0 where L < M
+hipError_t launch_cut(const CutArgs &a, hipStream_t stream);
 // buffers kept between the runs of a process (nh_run.hip: page-locked batch text; nh_gunzip.hip: the gzip reader's HBM and
 // staging): emptied when an engine is closed
 void run_cache_trim();

@@ -645,6 +645,9 @@ struct RunState {
     // host bases only: {host, masked, closed} bases as the devices counted them (nh_host_bases), fetched once at the end, and the
     // sequence bases of the host fragments as the writer saw them
     uint64_t hb_bases[3] = {0, 0, 0}, hb_host_written = 0;
+    // host cut: the CUT_COUNTS counts as the devices counted them (nh_host_cut; closed_bases is hb_bases[2], the writer's check
+    // hb_host_written), the items the builder made
+    uint64_t cut_counts[CUT_COUNTS] = {}, cut_items = 0;
     // BAM output (NOHUMAN_TRACE): the records and bytes the builder selected per output, its kernel time
     uint64_t bam_records[2] = {0, 0}, bam_bytes[2] = {0, 0};
     double bam_kernel_ms = 0;
@@ -1142,6 +1145,11 @@ struct RunRequest {
     // alone (nh_mask.hip).  Not enabled: nothing of this runs.
     nh_host_bases *hb = nullptr;
     bool hbo = false;
+    // given (nh_run_hostcut): the struct as the caller gave it -- check_request looks at its size --, and `cut` where it enables the
+    // mode: a single-end masked run with the same mark pass and closing (hc->gap), whose out1 is made by the cut builder (nh_cut.hip):
+    // a host fragment as its uncovered pieces of at least hc->min_piece bases, every other fragment whole.  Not enabled: nothing runs.
+    nh_host_cut *hc = nullptr;
+    bool cut = false;
 };
 
 // The request of an entry: its args, its extras (NULL where it has none, or was given none) or the bare human paths of
@@ -1149,7 +1157,7 @@ struct RunRequest {
 RunRequest make_request(RunRequest::Form form, const nh_run_args *a, const nh_run_extras *x, const char *h1 = nullptr, const char *h2 = nullptr,
                         uint32_t minq = 0, const char *rs_path = nullptr, nh_read_stats *rs_out = nullptr, nh_taxon_out *touts = nullptr,
                         uint32_t n_touts = 0, nh_minimizer_data *md = nullptr, nh_host_filter *hf = nullptr, nh_read_dust *rd = nullptr,
-                        nh_host_intervals *hi = nullptr, nh_host_bases *hb = nullptr) {
+                        nh_host_intervals *hi = nullptr, nh_host_bases *hb = nullptr, nh_host_cut *hc = nullptr) {
     static const char *const names[] = {"nh_run", "nh_run_split", "nh_run_mask", "nh_run_ex"};
     RunRequest r;
     r.form = form == RunRequest::RUN && x ? RunRequest::EX : form;
@@ -1164,6 +1172,7 @@ RunRequest make_request(RunRequest::Form form, const nh_run_args *a, const nh_ru
     r.rd = rd, r.dust = rd && rd->struct_size >= sizeof(nh_read_dust) && rd->enable != 0;
     r.hi = hi, r.hi_path = hi && hi->struct_size >= sizeof(nh_host_intervals) ? hi->path : nullptr;
     r.hb = hb, r.hbo = hb && hb->struct_size >= sizeof(nh_host_bases) && hb->enable != 0;
+    r.hc = hc, r.cut = hc && hc->struct_size >= sizeof(nh_host_cut) && hc->enable != 0;
     return r;
 }
 
@@ -1360,6 +1369,24 @@ static int check_hostbases_args(const RunRequest &r) {
     return NH_OK;
 }
 
+// nh_run_hostcut's own arguments: the struct, a masked run that is not a host-bases-only run, the gap, the shortest piece, one input
+static int check_hostcut_args(const RunRequest &r) {
+    const nh_host_cut *hc = r.hc;
+    if (!hc) return NH_OK;
+    if (hc->struct_size < sizeof(nh_host_cut))
+        return set_error(NH_EINVAL, "nh_run_hostcut: struct_size %u is smaller than nh_host_cut (%zu bytes)", hc->struct_size, sizeof(nh_host_cut));
+    if (!r.cut) return NH_OK;
+    if (!r.a) return set_error(NH_EINVAL, "nh_run_hostcut: null arguments");
+    if (!r.mask) return set_error(NH_EINVAL, "nh_run_hostcut: enable is set without a masked run (extras->mask): the mode writes every read, host reads as their pieces");
+    if (r.hbo) return set_error(NH_EINVAL, "nh_run_hostcut: enable is set together with an enabled nh_host_bases: a host stretch is cut out or written as N, not both");
+    if (hc->gap > NH_HOST_GAP_MAX) return set_error(NH_EINVAL, "nh_run_hostcut: gap %u is above NH_HOST_GAP_MAX (%d)", hc->gap, NH_HOST_GAP_MAX);
+    if (hc->min_piece == 0 || hc->min_piece > 0x7FFFFFFFu) return set_error(NH_EINVAL, "nh_run_hostcut: min_piece %u is not in 1..2147483647", hc->min_piece);
+    if (r.paired)
+        return set_error(NH_EINVAL, "nh_run_hostcut: paired input (%s): the mode is single-end only, the pieces of two mates cannot stay in step",
+                         r.a->in2 ? "in2 is given" : "in1 is a paired BAM");
+    return NH_OK;
+}
+
 // The container of the record outputs: a codec there is none of, and what BAM output (NH_CODEC_BAM: the selected records of a BAM
 // in1, copied) does not go with -- a second input, a masked run, per-taxon outputs (the last two: not built yet), an in1 that is
 // no BAM file.  (A request without arguments is refused by its entry.)
@@ -1384,7 +1411,7 @@ static int check_out_codec(const RunRequest &r) {
 
 // Every entry's checks, in one order: the host selection's own, the minimum base quality (the highest printable quality is '~',
 // Phred 93), the read DUST's struct, the extras (the mask or the human outputs, then the read lists), the read statistics' table, the selectors, the
-// minimizer data, the host intervals, the host bases, the container.  What an entry cannot ask for is not set in its request and checks nothing.
+// minimizer data, the host intervals, the host bases, the host cut, the container.  What an entry cannot ask for is not set in its request and checks nothing.
 int check_request(const RunRequest &r) {
     int rc = check_host_filter(r.hf);
     if (!rc && r.minq > 93) rc = set_error(NH_EINVAL, "minimum base quality %u is not in 0..93 (Phred+33)", r.minq);
@@ -1396,6 +1423,7 @@ int check_request(const RunRequest &r) {
     if (!rc) rc = check_mdata_args(r);
     if (!rc) rc = check_cover_args(r);
     if (!rc) rc = check_hostbases_args(r);
+    if (!rc) rc = check_hostcut_args(r);
     if (!rc) rc = check_out_codec(r);
     return rc;
 }
@@ -1493,7 +1521,8 @@ struct RunBuffers {
     DevBuf<uint8_t> host_of;
     DevBuf<unsigned long long> hcnt;
     DevBuf<unsigned long long> racc;  // read statistics: one block of four accumulators, zeroed with min_len all-ones
-    DevBuf<unsigned long long> hbcnt; // host bases only: {host, masked, closed} bases the mask builder and the closing add to
+    // host bases only: {host, masked, closed} bases the mask builder and the closing add to; host cut: [2] closed, then CUT_COUNTS words
+    DevBuf<unsigned long long> hbcnt;
     // minimizer data: one zeroed bitmap (a bit a cell) and one array of hit groups per node
     DevBuf<uint32_t> marks;
     DevBuf<unsigned long long> groups;
@@ -1506,7 +1535,7 @@ struct RunBuffers {
 // (hipMemcpy / hipMemset block: the tables and the zeroes are in place before the slots' streams, which do not wait for the legacy
 // stream, carry the first batch)
 static int alloc_run_buffers(RunBuffers &b, const Engine *e, const std::vector<uint8_t> &bin_of, const std::vector<uint8_t> &host_of, bool rst,
-                             size_t md_mark_bytes, size_t md_nodes, bool mdt, bool hbo) {
+                             size_t md_mark_bytes, size_t md_nodes, bool mdt, size_t hb_words) {
     b.device = e->device;
     const size_t nc = CNT_N + 12, nb = nc * sizeof(uint64_t);  // (+12: the words of the instrumented kernel variant)
     if (dev_set(e->device) != hipSuccess || b.counters.reserve(nc) != hipSuccess || hipMemset(b.counters, 0, nb) != hipSuccess)
@@ -1525,7 +1554,7 @@ static int alloc_run_buffers(RunBuffers &b, const Engine *e, const std::vector<u
         if (b.racc.reserve(sizeof init / 8) != hipSuccess || hipMemcpy(b.racc, init, sizeof init, hipMemcpyHostToDevice) != hipSuccess)
             return set_error(NH_EDEVICE, "cannot allocate the read statistics' accumulators on device %d", e->device);
     }
-    if (hbo && (dev_set(e->device) != hipSuccess || b.hbcnt.reserve(3) != hipSuccess || hipMemset(b.hbcnt, 0, 24) != hipSuccess ||
+    if (hb_words && (dev_set(e->device) != hipSuccess || b.hbcnt.reserve(hb_words) != hipSuccess || hipMemset(b.hbcnt, 0, 8 * hb_words) != hipSuccess ||
                 hipDeviceSynchronize() != hipSuccess))
         return set_error(NH_EDEVICE, "cannot allocate the host bases' counters on device %d", e->device);
     if (mdt) {
@@ -1595,6 +1624,32 @@ static void collect_hostbases(const std::vector<RunBuffers> &dbuf, RunState &rs)
         char msg[200];
         snprintf(msg, sizeof msg, "host bases only: the devices counted %llu host bases, the writer %llu", (unsigned long long)rs.hb_bases[0],
                  (unsigned long long)rs.hb_host_written);
+        rs.fail(NH_EDEVICE, msg);
+    }
+}
+
+// host cut: the devices' closed bases and CUT_COUNTS counts summed into the run's, and the identities they must keep
+static void collect_hostcut(const std::vector<RunBuffers> &dbuf, RunState &rs) {
+    for (size_t g = 0; g < dbuf.size() && rs.err_code == NH_OK; g++) {
+        unsigned long long c[3 + CUT_COUNTS] = {};
+        if (dev_set(dbuf[g].device) != hipSuccess || hipMemcpy(c, dbuf[g].hbcnt, sizeof c, hipMemcpyDeviceToHost) != hipSuccess) {
+            rs.fail(NH_EDEVICE, "reading the host cut's counters failed");
+            break;
+        }
+        rs.hb_bases[2] += c[2];
+        for (int k = 0; k < CUT_COUNTS; k++) rs.cut_counts[k] += c[3 + k];
+    }
+    if (rs.err_code != NH_OK) return;
+    const uint64_t *c = rs.cut_counts;
+    char msg[240];
+    // (the bases of the fragments the writer saw as host are the checker of what the builder counted)
+    if (c[CUT_HOST_BASES] != rs.hb_host_written) {
+        snprintf(msg, sizeof msg, "host cut: the devices counted %llu host bases, the writer %llu", (unsigned long long)c[CUT_HOST_BASES],
+                 (unsigned long long)rs.hb_host_written);
+        rs.fail(NH_EDEVICE, msg);
+    } else if (c[CUT_HOST_BASES] != c[CUT_PIECE_BASES] + c[CUT_CUT_BASES] + c[CUT_SHORT_BASES]) {
+        snprintf(msg, sizeof msg, "host cut: %llu host bases are not %llu in pieces + %llu cut + %llu in short runs", (unsigned long long)c[CUT_HOST_BASES],
+                 (unsigned long long)c[CUT_PIECE_BASES], (unsigned long long)c[CUT_CUT_BASES], (unsigned long long)c[CUT_SHORT_BASES]);
         rs.fail(NH_EDEVICE, msg);
     }
 }
@@ -1734,9 +1789,11 @@ struct RunShape {
     bool dust;         // --dust-reads: k_rdust in front of the classifier
     bool cover;        // --host-intervals: k_cover_mark and the two builders behind the classifier
     bool hbo;          // --host-bases-only: k_cover_mark (one pass for both), the closing (gap > 0), the mask builder on the bitmap
-    uint32_t gap;
-    bool mark;         // the batch's cover bitmap is made (cover or hbo)
-    bool idl;          // a builder prints mate 1's id: the id lengths go to the device (the read lists, the host intervals)
+    bool cut;          // --host-cut: the same mark pass and closing, the cut builder (nh_cut.hip) in the mask builder's place
+    uint32_t gap, min_piece;
+    bool close;        // the bitmap is closed behind the report (hbo or cut)
+    bool mark;         // the batch's cover bitmap is made (cover, hbo or cut)
+    bool idl;          // a builder prints mate 1's id: the id lengths go to the device (the read lists, the host intervals, the host cut)
     bool qtext;        // the classifier and the minimizer data's marks read the slot's masked text, not the batch's (qm or dust)
     bool want_rec;     // a kernel of the run reads the record table
     bool gzip_family;  // the codecs the GPU encodes
@@ -1757,8 +1814,9 @@ struct RunShape {
         qm = minq > 0, rst = r.rs_path || r.rs_out, hsel = r.hf != nullptr;
         dust = r.dust, qtext = qm || dust;
         mdt = r.md && (r.md->in_report || r.md->table || r.md->taxa);
-        cover = r.hi_path != nullptr, idl = lists || cover;
-        hbo = r.hbo, gap = hbo ? r.hb->gap : 0, mark = cover || hbo;
+        cover = r.hi_path != nullptr;
+        hbo = r.hbo, cut = r.cut, close = hbo || cut, gap = hbo ? r.hb->gap : cut ? r.hc->gap : 0, min_piece = cut ? r.hc->min_piece : 0;
+        mark = cover || close, idl = lists || cover || cut;
         want_rec = split || mask || lists || qm || rst || taxa || cover;
         gzip_family = a->out_codec == NH_CODEC_GZIP || a->out_codec == NH_CODEC_BGZF || bamout;
         G = (int)n_engines;
@@ -2301,6 +2359,7 @@ struct Pipeline {
     // a masked run's records (nh_mask.hip): every record of both mates, masked, one span a mate -- in HBM, or copied by the writer
     void build_mask(BuildStep step, Slot &s, const Batch &b, FlushJob *j, int *rc) {
         const int mates = sh.mates;
+        if (sh.cut) return build_cut(step, s, b, j, rc);
         if (step == RESERVE) {  // a mate's masked text: its records less what normalisation drops, plus a final newline each
             const size_t out_cap[2] = {b.len1 + b.n + 64, b.len2 + b.n + 64};
             if (!*rc) *rc = slot_reserve_rec(s, b.n * (size_t)mates);
@@ -2327,6 +2386,56 @@ struct Pipeline {
             for (size_t i = 0; i < b.n; i++) rs.mask_masked += (s.host_res()[i].call != 0) * (uint64_t)mates;
             for (size_t i = 0; sh.hbo && i < b.n; i++)
                 if (s.host_res()[i].call != 0) rs.hb_host_written += (uint64_t)b.h1->recs[b.off1 + i].slen + (b.h2 ? b.h2->recs[b.off2 + i].slen : 0);
+        }
+    }
+
+    // a host-cut run's records (nh_cut.hip), in the mask builder's place and buffers: out1's text [0] and the item list it is made
+    // from [1]; totals: bytes, items.  A sequence of L bases holds at most cut_max_pieces(L) pieces -- a piece is min_piece bases at
+    // least and a covered run of k at least lies between two --, a piece's record is its bases and qualities, its header and at
+    // most 22 bytes of coordinates and 5 of seams
+    size_t cut_caps(const Batch &b, size_t *extra, size_t *max_item = nullptr) const {
+        size_t pieces = 0, bytes = 0, longest = 0;
+        for (size_t i = 0; i < b.n; i++) {
+            const RecRef &r = b.h1->recs[b.off1 + i];
+            const size_t p = (size_t)cut_max_pieces(r.slen, sh.min_piece);
+            pieces += p, bytes += p * ((size_t)r.hlen + 29);
+            longest = std::max(longest, (size_t)r.hlen + 29 + r.slen + r.qlen);
+        }
+        if (extra) *extra = bytes;
+        if (max_item) *max_item = longest;
+        return b.n + pieces;
+    }
+    void build_cut(BuildStep step, Slot &s, const Batch &b, FlushJob *j, int *rc) {
+        if (step == RESERVE) {
+            size_t extra = 0;
+            const size_t cap_items = cut_caps(b, &extra);
+            const size_t out_cap[2] = {b.len1 + b.n + 64 + extra, 12 * cap_items + 16};
+            if (!*rc) *rc = slot_reserve_rec(s, b.n);
+            if (!*rc) *rc = slot_reserve_idl(s, b.n);
+            // (the scratch: the sequences' counts, the block offsets of both stages; then the totals: CutArgs)
+            if (!*rc) *rc = built_reserve(s.mask, (size_t)cut_scratch_words(b.n, cap_items) + 4, out_cap, 2, "host-cut buffers");
+        } else if (step == LAUNCH) {
+            CutArgs ca{};
+            ca.text = (const char *)s.d_text, ca.ntext = b.ntext();  // (the input's bases, never the masked copy)
+            ca.seq_off = (const uint64_t *)s.d_off, ca.seq_len = (const uint32_t *)s.d_len, ca.rec = (const uint32_t *)s.d_rec.p;
+            ca.idlen = (const uint32_t *)s.d_idl, ca.res = (const nh_result *)(sh.hsel ? s.d_hres : s.d_res);
+            ca.n = b.n, ca.fastq = b.h1->format == FMT_FASTQ;
+            ca.cover = s.d_cover, ca.min_piece = sh.min_piece;  // (build_cover's, closed, in front of this on the stream)
+            size_t longest = 0;
+            ca.items = (uint32_t *)s.mask.d_out[1].p, ca.cap_items = cut_caps(b, nullptr, &longest), ca.max_item = longest;
+            ca.out = s.mask.d_out[0], ca.cap = s.mask.d_out[0].cap;
+            ca.scratch = (uint64_t *)s.mask.d_blk;
+            ca.total = s.mask.d_total = ca.scratch + cut_scratch_words(b.n, ca.cap_items);
+            ca.counts = dbuf[(size_t)b.dev_index].hbcnt + 3, ca.error = s.e->d_error + LAUNCH_SLOTS;
+            timed_launch(rs, s.stream, s.mask.ev, "host-cut builder", [&] {
+                const hipError_t he = hipMemsetAsync(ca.total, 0, 4 * sizeof(uint64_t), s.stream);  // (four words go back; the builder writes two)
+                return he == hipSuccess ? launch_cut(ca, s.stream) : he;
+            });
+        } else {
+            one_span(j, s.mask, 0, sh.mask_in_hbm, f.o1, f.o1.sp, &rs.mask_bytes, rc, "host-cut buffers", "cut records");
+            rs.mask_records += b.n, rs.cut_items += s.mask.h_total[1];
+            for (size_t i = 0; i < b.n; i++)
+                if (s.host_res()[i].call != 0) rs.mask_masked++, rs.hb_host_written += b.h1->recs[b.off1 + i].slen;
         }
     }
 
@@ -2465,14 +2574,14 @@ struct Pipeline {
             CoverCloseArgs cl{};
             cl.cover = s.d_cover, cl.ntext = ntext, cl.seq_off = ca.seq_off, cl.seq_len = ca.seq_len, cl.n_seq = nseq;
             cl.res = (const nh_result *)(sh.hsel ? s.d_hres : s.d_res), cl.mates = mates;  // (the host fragments alone: closed_bases counts what is masked)
-            cl.gap = sh.gap, cl.closed = sh.hbo ? dbuf[(size_t)b.dev_index].hbcnt + 2 : nullptr, cl.error = d_error;
+            cl.gap = sh.gap, cl.closed = sh.close ? dbuf[(size_t)b.dev_index].hbcnt + 2 : nullptr, cl.error = d_error;
             timed_launch(rs, s.stream, s.cover.ev, "host intervals", [&] {
                 hipError_t he = hipMemsetAsync(s.d_cover, 0, (size_t)cover_words(ntext) * 4, s.stream);
                 if (he == hipSuccess) he = launch_cover_mark(s.e, ca, s.stream);
                 if (he == hipSuccess && sh.cover) he = launch_cover_intervals(ia, s.stream);
                 if (he == hipSuccess && sh.cover) he = launch_cover_lines(la, s.stream);
                 if (he == hipSuccess && !sh.cover) he = hipMemsetAsync(la.total, 0, 4 * sizeof(uint64_t), s.stream);  // (the totals go back all the same)
-                if (he == hipSuccess && sh.hbo) he = launch_cover_close(cl, s.stream);  // (behind the report: the BED is the coverage before the closing)
+                if (he == hipSuccess && sh.close) he = launch_cover_close(cl, s.stream);  // (behind the report: the BED is the coverage before the closing)
                 return he;
             });
         } else {
@@ -2603,7 +2712,7 @@ struct Pipeline {
         if (!rc && sh.dust) rc = slot_reserve_dust(s, b.ntext(), b.n * (size_t)sh.mates);
         if (!rc && sh.rst) rc = slot_reserve_rec(s, b.n * (size_t)sh.mates);
         if (!rc && sh.hsel) rc = slot_reserve_pair(s.h_hres, s.d_hres, b.n, "host-filtered results");
-        if (!rc && (sh.qm || sh.rst)) rc = check_quality_lengths(b);
+        if (!rc && (sh.qm || sh.rst || sh.cut)) rc = check_quality_lengths(b);
         return rc;
     }
 
@@ -2617,7 +2726,7 @@ struct Pipeline {
                 if (hb.format == FMT_FASTQ && rr.qlen != rr.slen)
                     return set_error(NH_EIO, "%s, read %llu: sequence length (%u) != quality string length (%u), which %s", m && a->in2 ? a->in2 : a->in1,
                                      (unsigned long long)(frags_out + i + 1), rr.slen, rr.qlen,
-                                     sh.qm ? "--minimum-base-quality cannot mask" : "--read-stats cannot count");
+                                     sh.qm ? "--minimum-base-quality cannot mask" : sh.rst ? "--read-stats cannot count" : "--host-cut cannot slice");
             }
         return NH_OK;
     }
@@ -2827,6 +2936,11 @@ static void print_run_trace(const RunShape &sh, RunState &rs, const StageClock &
         fprintf(stderr, "[nohuman trace] host-bases-only: %llu of %llu host bases masked, %llu by closing; gap %u, cover kernels %.3f ms, mask builder kernels %.3f ms\n",
                 (unsigned long long)rs.hb_bases[1], (unsigned long long)rs.hb_bases[0], (unsigned long long)rs.hb_bases[2], sh.gap, rs.cover_kernel_ms,
                 rs.mask_kernel_ms);
+    if (sh.cut)
+        fprintf(stderr, "[nohuman trace] host-cut: %llu host bases: %llu in %llu pieces, %llu cut (%llu by closing), %llu in short runs; %llu reads dropped; %llu items; gap %u, min piece %u, cover kernels %.3f ms, cut builder kernels %.3f ms\n",
+                (unsigned long long)rs.cut_counts[CUT_HOST_BASES], (unsigned long long)rs.cut_counts[CUT_PIECE_BASES], (unsigned long long)rs.cut_counts[CUT_PIECES],
+                (unsigned long long)rs.cut_counts[CUT_CUT_BASES], (unsigned long long)rs.hb_bases[2], (unsigned long long)rs.cut_counts[CUT_SHORT_BASES],
+                (unsigned long long)rs.cut_counts[CUT_DROPPED], (unsigned long long)rs.cut_items, sh.gap, sh.min_piece, rs.cover_kernel_ms, rs.mask_kernel_ms);
     if (sh.qm)
         fprintf(stderr, "[nohuman trace] qmask: Q %u, %llu of %llu bases masked, kernel %.3f ms\n", sh.minq,
                 (unsigned long long)rs.qmask_masked, (unsigned long long)rs.total_bases, rs.qmask_kernel_ms);
@@ -2975,6 +3089,7 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
     if (r.rd) r.rd->masked_bases = 0;
     if (sh.cover) r.hi->fragments = r.hi->intervals = r.hi->covered_bases = 0;
     if (sh.hbo) r.hb->host_bases = r.hb->masked_bases = r.hb->closed_bases = 0;
+    if (sh.cut) r.hc->host_bases = r.hc->pieces = r.hc->piece_bases = r.hc->cut_bases = r.hc->short_bases = r.hc->dropped_reads = r.hc->closed_bases = 0;
     if (sh.split || sh.lists || sh.taxa || sh.cover)
         for (Engine *e : engines)
             if ((rc = ensure_device_external(e))) return rc;
@@ -2999,7 +3114,7 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
     std::vector<nh_read_class> racc;  // read statistics: the devices' blocks summed: [class][mate]
     rs.d_run_counters.assign((size_t)sh.G, nullptr);
     for (int g = 0; g < sh.G; g++) {
-        if ((rc = alloc_run_buffers(dbuf[g], engines[g], bin_of, host_of, sh.rst, md_mark_bytes, engines[0]->external.size(), sh.mdt, sh.hbo))) return rc;
+        if ((rc = alloc_run_buffers(dbuf[g], engines[g], bin_of, host_of, sh.rst, md_mark_bytes, engines[0]->external.size(), sh.mdt, sh.hbo ? 3 : sh.cut ? 3 + CUT_COUNTS : 0))) return rc;
         rs.d_run_counters[g] = dbuf[g].counters;
     }
     if ((rc = p.create_slots())) return rc;
@@ -3013,6 +3128,7 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
     if (sh.hsel) collect_host_counts(dbuf, rs, dev_host);
     if (sh.rst) collect_rstats(dbuf, rs, racc);
     if (sh.hbo) collect_hostbases(dbuf, rs);
+    if (sh.cut) collect_hostcut(dbuf, rs);
     if (sh.mdt) collect_mdata(dbuf, rs, md_mark_bytes, mdn, &md_count_ms);
     p.slots.clear();  // (every slot's buffers, events and stream go back here, each under its device)
     if (sh.trace_run)
@@ -3039,6 +3155,11 @@ int run_engines(const std::vector<Engine *> &engines, const RunRequest &r, nh_st
     if (sh.dust) r.rd->masked_bases = rs.dust_masked;
     if (sh.cover) r.hi->fragments = rs.cover_frags, r.hi->intervals = rs.cover_ivls, r.hi->covered_bases = rs.cover_bases;
     if (sh.hbo) r.hb->host_bases = rs.hb_bases[0], r.hb->masked_bases = rs.hb_bases[1], r.hb->closed_bases = rs.hb_bases[2];
+    if (sh.cut) {
+        const uint64_t *c = rs.cut_counts;
+        r.hc->host_bases = c[CUT_HOST_BASES], r.hc->pieces = c[CUT_PIECES], r.hc->piece_bases = c[CUT_PIECE_BASES], r.hc->cut_bases = c[CUT_CUT_BASES];
+        r.hc->short_bases = c[CUT_SHORT_BASES], r.hc->dropped_reads = c[CUT_DROPPED], r.hc->closed_bases = rs.hb_bases[2];
+    }
     if (sh.mdt && (rc = report_mdata(mdview, mdn, r.md))) return rc;
     if (stats) {
         nh_stats st;
@@ -3137,6 +3258,15 @@ int nh_run_engine_hostbases(nh_engine *e, const nh_run_args *args, const nh_run_
                             nh_host_filter *hf, nh_read_dust *rd, nh_host_intervals *hi, nh_host_bases *hb, nh_stats *stats) {
     return run_on_engine(
         e, nh::make_request(nh::RunRequest::RUN, args, extras, nullptr, nullptr, min_base_quality, read_stats_path, read_stats, outs, n_outs, md, hf, rd, hi, hb),
+        stats);
+}
+
+// (hc NULL, or its enable 0: the request is nh_run_engine_hostbases')
+int nh_run_engine_hostcut(nh_engine *e, const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality,
+                          const char *read_stats_path, nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs, nh_minimizer_data *md,
+                          nh_host_filter *hf, nh_read_dust *rd, nh_host_intervals *hi, nh_host_bases *hb, nh_host_cut *hc, nh_stats *stats) {
+    return run_on_engine(
+        e, nh::make_request(nh::RunRequest::RUN, args, extras, nullptr, nullptr, min_base_quality, read_stats_path, read_stats, outs, n_outs, md, hf, rd, hi, hb, hc),
         stats);
 }
 
@@ -3458,6 +3588,15 @@ int nh_run_hostbases(const nh_run_args *args, const nh_run_extras *extras, uint3
                      nh_host_intervals *hi, nh_host_bases *hb, nh_stats *stats) {
     return run_standalone(
         nh::make_request(nh::RunRequest::RUN, args, extras, nullptr, nullptr, min_base_quality, read_stats_path, read_stats, outs, n_outs, md, hf, rd, hi, hb),
+        stats);
+}
+
+// (hc NULL, or its enable 0: the request is nh_run_hostbases')
+int nh_run_hostcut(const nh_run_args *args, const nh_run_extras *extras, uint32_t min_base_quality, const char *read_stats_path,
+                   nh_read_stats *read_stats, nh_taxon_out *outs, uint32_t n_outs, nh_minimizer_data *md, nh_host_filter *hf, nh_read_dust *rd,
+                   nh_host_intervals *hi, nh_host_bases *hb, nh_host_cut *hc, nh_stats *stats) {
+    return run_standalone(
+        nh::make_request(nh::RunRequest::RUN, args, extras, nullptr, nullptr, min_base_quality, read_stats_path, read_stats, outs, n_outs, md, hf, rd, hi, hb, hc),
         stats);
 }
 

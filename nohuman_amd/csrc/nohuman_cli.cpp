@@ -264,6 +264,9 @@ struct Args {
     bool host_bases_only = false;   // a masked run that writes N over the bases that host k-mers cover alone (nh_run_hostbases)
     unsigned host_gap = 0;          // ... and over the uncovered runs of at most so many bases between two of them
     bool has_host_gap = false;
+    bool host_cut = false;          // a masked run that cuts the host stretches out and writes the rest of a human read as pieces (nh_run_hostcut)
+    unsigned host_min_piece = 35;   // ... of at least so many bases (k: a shorter piece holds no k-mer)
+    bool has_host_min_piece = false;
     bool report_minimizer_data = false;  // kraken2's flag: two more columns in the report (nh_run_mdata)
     std::string minimizer_table;         // the minimizer table (nh_run_mdata)
     // per-taxon outputs (nh_run_taxa): the selectors in the order given -- taxid (0: `other`), the path as given ('#' in it: the mate)
@@ -327,6 +330,11 @@ static void usage(FILE *f) {
           "      --host-gap <INT>         With --host-bases-only: also write N over an uncovered run of at most INT bases that lies between two covered bases of the same read "
           "(each mate on its own; never a run that touches an end of the read). 34 (k - 1) is recommended for noisy long reads, whose sequencing errors break a host stretch "
           "into pieces with leftovers too short to hold a k-mer (0-4096) [default: 0]\n"
+          "      --host-cut               Make the run a masked run that cuts the bases that host k-mers cover out of a human read and writes what is left as records of their own, "
+          "named '<id>:<start>-<end>' (0-based, half-open: the coordinates of --host-intervals), in input order; a human read with nothing left is not written, every other read is "
+          "written whole. --host-gap closes gaps as with --host-bases-only. Single-end input only. Not with -H or --host-bases-only\n"
+          "      --host-min-piece <INT>   With --host-cut: the shortest piece that is written, in bases; shorter leftovers are dropped. The default is k: a shorter piece holds no "
+          "k-mer (1-2147483647) [default: 35]\n"
           "  -k, --kraken-output <FILE>   Write the Kraken2 read classification output to a file\n"
           "  -r, --kraken-report <FILE>   Write the Kraken2 report with aggregate counts/clade to file\n"
           "      --report-minimizer-data  Report, per clade, the minimizer hits of the reads and how many distinct minimizers they were, as columns 4 and 5 of the Kraken2 report "
@@ -460,6 +468,16 @@ static Args parse_args(int argc, char **argv) {
             if (errno || n < 0 || n > NH_HOST_GAP_MAX) arg_error("invalid value '%s' for '--host-gap <INT>': %s is not in 0..=%d", t.c_str(), t.c_str(), NH_HOST_GAP_MAX);
             a.host_gap = (unsigned)n, a.has_host_gap = true;
         }
+        else if (s == "--host-cut") a.host_cut = true;
+        else if (s == "--host-min-piece") {
+            std::string t = val();
+            char *end;
+            errno = 0;
+            long long n = strtoll(t.c_str(), &end, 10);
+            if (*end || t.empty() || t[0] == ' ' || t[0] == '\t') arg_error("invalid value '%s' for '--host-min-piece <INT>': invalid digit found in string", t.c_str());
+            if (errno || n < 1 || n > 2147483647ll) arg_error("invalid value '%s' for '--host-min-piece <INT>': %s is not in 1..=2147483647", t.c_str(), t.c_str());
+            a.host_min_piece = (unsigned)n, a.has_host_min_piece = true;
+        }
         else if (s == "--report-minimizer-data") a.report_minimizer_data = true;
         else if (s == "--minimizer-table") a.minimizer_table = val();
         else if (s == "--taxon-out") {
@@ -546,7 +564,8 @@ static Args parse_args(int argc, char **argv) {
                              : !a.minimizer_table.empty() ? "--minimizer-table" : a.has_type ? "--output-type"
                              : a.bgzf ? "--bgzf" : a.bam_out ? "--bam-out" : a.mask ? "--mask" : a.human ? "--human" : !a.taxon_out.empty() ? "--taxon-out"
                              : !a.host_taxids.empty() ? "--host-taxid" : !a.keep_taxids.empty() ? "--keep-taxid" : a.dust_reads ? "--dust-reads"
-                             : !a.host_intervals.empty() ? "--host-intervals" : a.host_bases_only ? "--host-bases-only" : a.has_host_gap ? "--host-gap" : nullptr;
+                             : !a.host_intervals.empty() ? "--host-intervals" : a.host_bases_only ? "--host-bases-only" : a.has_host_gap ? "--host-gap"
+                             : a.host_cut ? "--host-cut" : a.has_host_min_piece ? "--host-min-piece" : nullptr;
         if (out_flag) arg_error("the argument '--build-db <DIR>' cannot be used with '%s'", out_flag);
         if (a.has_extend_db) {
             if (a.capacity) arg_error("the argument '--extend-db <DIR>' cannot be used with '--capacity <INT>': an extension keeps the capacity of its base");
@@ -571,8 +590,12 @@ static Args parse_args(int argc, char **argv) {
         arg_error("the following required arguments were not provided:\n  <INPUT>...");
     if (a.mask && a.human) arg_error("the argument '--mask' cannot be used with '--human'");
     if (a.host_bases_only && a.human) arg_error("the argument '--host-bases-only' cannot be used with '--human'");
-    if (a.has_host_gap && !a.host_bases_only) arg_error("the argument '--host-gap <INT>' needs '--host-bases-only': it closes the gaps between the bases that run masks");
-    if (a.host_bases_only) a.mask = true;  // (a masked run in everything else)
+    if (a.host_cut && a.human) arg_error("the argument '--host-cut' cannot be used with '--human'");
+    if (a.host_cut && a.host_bases_only) arg_error("the argument '--host-cut' cannot be used with '--host-bases-only': a host stretch is cut out or written as N, not both");
+    if (a.host_cut && a.input.size() > 1) arg_error("the argument '--host-cut' cannot be used with two inputs: the pieces of two mates cannot stay in step");
+    if (a.has_host_min_piece && !a.host_cut) arg_error("the argument '--host-min-piece <INT>' needs '--host-cut': it is the shortest piece that run writes");
+    if (a.has_host_gap && !a.host_bases_only && !a.host_cut) arg_error("the argument '--host-gap <INT>' needs '--host-bases-only': it closes the gaps between the bases that run masks");
+    if (a.host_bases_only || a.host_cut) a.mask = true;  // (a masked run in everything else)
     // BAM output (--bam-out): the kept records of ONE BAM input, copied; its container is BGZF, whatever -F or the names say
     if (a.bam_out) {
         if (a.has_type) arg_error("the argument '--bam-out' cannot be used with '--output-type <FORMAT>': a BAM file is its own container");
@@ -1112,7 +1135,14 @@ int main(int argc, char **argv) {
     memset(&hbs, 0, sizeof hbs);
     hbs.struct_size = (uint32_t)sizeof hbs;
     hbs.enable = args.host_bases_only ? 1 : 0, hbs.gap = args.host_gap;
-    const int run_rc = hbs.enable ? nh_run_hostbases(&ra, &rx, args.min_base_quality, args.read_stats.empty() ? nullptr : spart.c_str(), nullptr,
+    nh_host_cut hcs;
+    memset(&hcs, 0, sizeof hcs);
+    hcs.struct_size = (uint32_t)sizeof hcs;
+    hcs.enable = args.host_cut ? 1 : 0, hcs.gap = args.host_gap, hcs.min_piece = args.host_min_piece;
+    const int run_rc = hcs.enable ? nh_run_hostcut(&ra, &rx, args.min_base_quality, args.read_stats.empty() ? nullptr : spart.c_str(), nullptr,
+                                                   touts.empty() ? nullptr : touts.data(), (uint32_t)touts.size(), md.in_report || md.table ? &md : nullptr,
+                                                   hsel ? &hf : nullptr, &rd, hi.path ? &hi : nullptr, nullptr, &hcs, &st)
+                       : hbs.enable ? nh_run_hostbases(&ra, &rx, args.min_base_quality, args.read_stats.empty() ? nullptr : spart.c_str(), nullptr,
                                                      touts.empty() ? nullptr : touts.data(), (uint32_t)touts.size(), md.in_report || md.table ? &md : nullptr,
                                                      hsel ? &hf : nullptr, &rd, hi.path ? &hi : nullptr, &hbs, &st)
                        : hi.path ? nh_run_intervals(&ra, lists || args.mask || split ? &rx : nullptr, args.min_base_quality,
@@ -1170,6 +1200,11 @@ int main(int argc, char **argv) {
     if (hbs.enable)
         DEBUG("Host bases only: %llu of %llu bases of the human reads written as N, %llu of them by closing gaps of at most %u bases",
               (unsigned long long)hbs.masked_bases, (unsigned long long)hbs.host_bases, (unsigned long long)hbs.closed_bases, hbs.gap);
+    if (hcs.enable)
+        DEBUG("Host cut: %llu bases of the human reads: %llu written in %llu pieces of at least %u bases, %llu cut out (%llu of them by closing gaps of at most %u bases), "
+              "%llu in shorter leftovers; %llu human reads left nothing",
+              (unsigned long long)hcs.host_bases, (unsigned long long)hcs.piece_bases, (unsigned long long)hcs.pieces, hcs.min_piece, (unsigned long long)hcs.cut_bases,
+              (unsigned long long)hcs.closed_bases, hcs.gap, (unsigned long long)hcs.short_bases, (unsigned long long)hcs.dropped_reads);
     if (g_verbose) {  // a BAM input: what the reader made of its records (the host side of the reader once more: nh_bam_scan)
         nh_bam_info bi;
         nh_bam_pair_info bp;

@@ -45,7 +45,8 @@ def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
         codec_threads: int = 0, human_out1=None, human_out2=None, mask: bool = False, calls=None,
         human_ids=None, min_base_quality: int = 0, read_stats=None, taxon_outs=None, report_minimizer_data: bool = False,
         minimizer_table=None, minimizer_data=None, host_taxids=None, keep_taxids=None, dust_reads: bool = False,
-        host_intervals=None, host_bases_only: bool = False, host_gap: int = 0) -> "_lib.nh_stats":
+        host_intervals=None, host_bases_only: bool = False, host_gap: int = 0, host_cut: bool = False,
+        host_min_piece: int = 35) -> "_lib.nh_stats":
     """nh_run: whole run, database loaded into every listed device (default: all visible).  human_out1 (and, paired,
     human_out2) given: nh_run_split -- the non-human reads go to out1 / out2 and, in the same pass, the human reads to
     human_out1 / human_out2 exactly as a keep_human run would write them.  mask: nh_run_mask -- every read goes to
@@ -94,7 +95,13 @@ def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
     coverage of host_intervals, on the copy the classifier read -- of a host fragment and keeps the input's own bases elsewhere;
     every other byte of every output is the masked run's.  host_gap (0..4096, needs host_bases_only): an uncovered run of at most
     so many bases between two covered ones of the same sequence is masked as well (mates apart, never a run that touches an end);
-    34 (k - 1) is the recommendation for noisy long reads.  The stats returned then carry host_bases, masked_bases and closed_bases."""
+    34 (k - 1) is the recommendation for noisy long reads.  The stats returned then carry host_bases, masked_bases and closed_bases.
+    host_cut (nh_run_hostcut; implies mask; single-end only, not with host_bases_only): a masked run that cuts the closed coverage
+    (host_gap as above) out of a host fragment and writes every uncovered run of at least host_min_piece bases (1..2^31-1, default
+    35 = k) as a record of its own, `<id>:<start>-<end>` (0-based, half-open) in front of the rest of the header, the input's own
+    bases and qualities of the run; a host fragment with no such run is not written, every other fragment is written whole.  Every
+    other output is the masked run's.  The stats returned then carry host_bases, pieces, piece_bases, cut_bases, short_bases,
+    dropped_reads and closed_bases (host_bases = piece_bases + cut_bases + short_bases)."""
     a = _lib.nh_run_args()
     a.db_dir = os.fsencode(db_dir)
     a.in1 = os.fsencode(in1)
@@ -118,24 +125,29 @@ def run(db_dir, in1, out1, in2=None, out2=None, kraken_output=None, report=None,
         a.device_ids = None
     return _run_entry("nh_run", (), lambda: _taxo_nodes(os.fspath(db_dir)), a, human_out1, human_out2, mask, calls, human_ids,
                       min_base_quality, read_stats, taxon_outs, report_minimizer_data, minimizer_table, minimizer_data, host_taxids,
-                      keep_taxids, dust_reads, host_intervals, host_bases_only, host_gap)
+                      keep_taxids, dust_reads, host_intervals, host_bases_only, host_gap, host_cut, host_min_piece)
 
 
 def _run_entry(prefix, lead, nodes, a, human_out1, human_out2, mask, calls, human_ids, min_base_quality, read_stats, taxon_outs,
                report_minimizer_data, minimizer_table, minimizer_data, host_taxids, keep_taxids, dust_reads=False,
-               host_intervals=None, host_bases_only=False, host_gap=0) -> "_lib.nh_stats":
+               host_intervals=None, host_bases_only=False, host_gap=0, host_cut=False, host_min_piece=35) -> "_lib.nh_stats":
     """run() and Engine.run(): the entry of the family `prefix` (nh_run / nh_run_engine, behind the arguments `lead`: none / the
-    handle) that the options ask for -- the first of hostbases, intervals, dust, host, mdata, taxa, rstats, minq, ex, mask, split, none that has one -- and
+    handle) that the options ask for -- the first of hostcut, hostbases, intervals, dust, host, mdata, taxa, rstats, minq, ex, mask, split, none that has one -- and
     what it hands back, on the stats.  nodes(): the nodes of the taxonomy, asked only where minimizer data wants a list."""
     fn = lambda suffix: getattr(_lib.lib(), prefix + suffix)
     s = _lib.nh_stats()
     head = tuple(lead) + (C.byref(a),)
     want_md = report_minimizer_data or minimizer_table is not None or minimizer_data is not None
     host_gap = int(host_gap)
-    if host_gap < 0 or (host_gap and not host_bases_only):
+    if host_gap < 0 or (host_gap and not host_bases_only and not host_cut):
         raise EngineError(-1, "host_gap %d: it is 0..%d and needs host_bases_only" % (host_gap, _lib.NH_HOST_GAP_MAX))
-    mask = mask or bool(host_bases_only)
-    if host_bases_only or host_intervals is not None or dust_reads or host_taxids or keep_taxids or want_md or taxon_outs or read_stats is not None or min_base_quality:
+    host_min_piece = int(host_min_piece)
+    if host_min_piece != 35 and not host_cut:
+        raise EngineError(-1, "host_min_piece %d: it needs host_cut" % host_min_piece)
+    if host_cut and not 1 <= host_min_piece <= 0x7FFFFFFF:
+        raise EngineError(-1, "host_min_piece %d: it is 1..2147483647" % host_min_piece)
+    mask = mask or bool(host_bases_only) or bool(host_cut)
+    if host_cut or host_bases_only or host_intervals is not None or dust_reads or host_taxids or keep_taxids or want_md or taxon_outs or read_stats is not None or min_base_quality:
         # the entries that take nh_run_minq's list and, each, one thing more: every one gets the list as far as its own last argument
         x = _extras_or_none(mask, human_out1, human_out2, calls, human_ids)
         rs = _read_stats(read_stats) if read_stats is not None else None
@@ -146,10 +158,12 @@ def _run_entry(prefix, lead, nodes, a, human_out1, human_out2, mask, calls, huma
         hi = (_lib.nh_host_intervals(C.sizeof(_lib.nh_host_intervals), 0, os.fsencode(host_intervals), 0, 0, 0)
               if host_intervals is not None else None)
         hb = (_lib.nh_host_bases(C.sizeof(_lib.nh_host_bases), 1, min(host_gap, 0xFFFFFFFF), 0, 0, 0, 0) if host_bases_only else None)
+        hc = (_lib.nh_host_cut(C.sizeof(_lib.nh_host_cut), 1, min(host_gap, 0xFFFFFFFF), host_min_piece) if host_cut else None)
         tail = [x, _minq(min_base_quality), _path_or_none(rs.path) if rs else None, C.byref(rs.raw) if rs else None,
                 t if len(t) else None, len(t), C.byref(md) if md is not None else None, C.byref(hf) if hf is not None else None,
-                C.byref(rd) if rd is not None else None, C.byref(hi) if hi is not None else None, C.byref(hb) if hb is not None else None]
-        suffix, n = (("_hostbases", 11) if hb is not None else ("_intervals", 10) if hi is not None else ("_dust", 9) if rd is not None else ("_host", 8) if hf is not None else ("_mdata", 7) if want_md else ("_taxa", 6) if taxon_outs else
+                C.byref(rd) if rd is not None else None, C.byref(hi) if hi is not None else None, C.byref(hb) if hb is not None else None,
+                C.byref(hc) if hc is not None else None]
+        suffix, n = (("_hostcut", 12) if hc is not None else ("_hostbases", 11) if hb is not None else ("_intervals", 10) if hi is not None else ("_dust", 9) if rd is not None else ("_host", 8) if hf is not None else ("_mdata", 7) if want_md else ("_taxa", 6) if taxon_outs else
                      ("_rstats", 4) if rs is not None else ("_minq", 2))
         _check(fn(suffix)(*head, *tail[:n], C.byref(s)))
         if md is not None:
@@ -164,6 +178,9 @@ def _run_entry(prefix, lead, nodes, a, human_out1, human_out2, mask, calls, huma
             s.interval_fragments, s.intervals, s.covered_bases = int(hi.fragments), int(hi.intervals), int(hi.covered_bases)
         if hb is not None:
             s.host_bases, s.masked_bases, s.closed_bases = int(hb.host_bases), int(hb.masked_bases), int(hb.closed_bases)
+        if hc is not None:
+            for k in _lib.HOST_CUT_COUNTS + ("closed_bases",):
+                setattr(s, k, int(getattr(hc, k)))
     elif calls is not None or human_ids is not None:
         x = _extras(mask, human_out1, human_out2, calls, human_ids)
         _check(fn("_ex")(*head, C.byref(x), C.byref(s)))
@@ -693,6 +710,20 @@ class Engine:
         _check(self._L.nh_cover_close_device(self._h, d_cover or None, int(text_len), d_seq_starts or None, d_seq_lens or None, int(n_seq),
                                              int(gap), d_closed_bases or None, stream or None))
 
+    def host_cut_device(self, d_text: int, text_len: int, d_records: int, d_seq_starts: int, d_seq_lens: int, d_idlen: int, d_results: int,
+                        n: int, fastq: bool, d_cover: int, min_piece: int, d_out: int, cap: int, d_total: int, d_error_bits: int,
+                        d_counts: int = 0, stream: int = 0) -> None:
+        """--host-cut's item list and text builder on a bitmap laid out as host_cover_device leaves it (nh_host_cut_device): fragment
+        i (sequence d_text[start, +len), record d_records[i] = {header start, header length, qualities start, length} uint32, id
+        length d_idlen[i]) is written to d_out whole where d_results[i].call is 0, and as its uncovered runs of at least min_piece
+        bases, `<id>:<a>-<b>` records, where it is not.  d_total (uint64): the bytes; d_counts: 0, or six uint64 the kernels add to
+        (_lib.HOST_CUT_COUNTS).  d_error_bits (int32): 4096 a sequence or a field outside the text or an id longer than its header,
+        16384 a FASTQ host record whose quality line is not as long as its sequence (such a record writes nothing), 8192 a text
+        above cap (total 0, nothing written).  A bit outside a sequence changes nothing.  Waits for `stream`."""
+        _check(self._L.nh_host_cut_device(self._h, d_text or None, int(text_len), d_records or None, d_seq_starts or None, d_seq_lens or None,
+                                          d_idlen or None, d_results or None, int(n), int(bool(fastq)), d_cover or None, int(min_piece),
+                                          d_out or None, int(cap), d_total or None, d_counts or None, d_error_bits or None, stream or None))
+
     def cover_intervals_device(self, d_cover: int, text_len: int, d_seq_starts: int, d_seq_lens: int, n_seq: int, d_intervals: int,
                                cap_records: int, d_total: int, d_error_bits: int, stream: int = 0):
         """host_cover_device's bitmap into records (nh_cover_intervals_device): d_intervals receives {uint32 seq, start, end} for
@@ -787,12 +818,13 @@ class Engine:
             codec_threads: int = 0, human_out1=None, human_out2=None, mask: bool = False, calls=None,
             human_ids=None, min_base_quality: int = 0, read_stats=None, taxon_outs=None, report_minimizer_data: bool = False,
             minimizer_table=None, minimizer_data=None, host_taxids=None, keep_taxids=None, dust_reads: bool = False,
-            host_intervals=None, host_bases_only: bool = False, host_gap: int = 0) -> _lib.nh_stats:
+            host_intervals=None, host_bases_only: bool = False, host_gap: int = 0, host_cut: bool = False,
+            host_min_piece: int = 35) -> _lib.nh_stats:
         """nh_run_engine; with human_out1 (and, paired, human_out2): nh_run_engine_split; mask: nh_run_engine_mask; with
         calls / human_ids: nh_run_engine_ex; with min_base_quality: nh_run_engine_minq; with read_stats:
         nh_run_engine_rstats; with taxon_outs: nh_run_engine_taxa; with report_minimizer_data / minimizer_table / minimizer_data:
         nh_run_engine_mdata; with host_taxids / keep_taxids: nh_run_engine_host; with dust_reads: nh_run_engine_dust; with host_intervals:
-        nh_run_engine_intervals; with host_bases_only (and host_gap): nh_run_engine_hostbases -- as run() above."""
+        nh_run_engine_intervals; with host_bases_only (and host_gap): nh_run_engine_hostbases; with host_cut (host_gap, host_min_piece): nh_run_engine_hostcut -- as run() above."""
         a = _lib.nh_run_args()
         a.db_dir = None
         a.in1 = os.fsencode(in1)
@@ -810,4 +842,4 @@ class Engine:
         a.codec_threads = int(codec_threads)
         return _run_entry("nh_run_engine", (self._h,), lambda: self.info.node_count, a, human_out1, human_out2, mask, calls, human_ids,
                           min_base_quality, read_stats, taxon_outs, report_minimizer_data, minimizer_table, minimizer_data, host_taxids,
-                          keep_taxids, dust_reads, host_intervals, host_bases_only, host_gap)
+                          keep_taxids, dust_reads, host_intervals, host_bases_only, host_gap, host_cut, host_min_piece)
